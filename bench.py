@@ -17,8 +17,13 @@ Workloads (BASELINE.json `configs`, 1-based like SURVEY §8):
                        config's full spp) on ONE GPU — how configs 3 and 5 are exercised without an
                        8-GPU node.
 
-Prints ONE JSON line on rank 0 and exits non-zero if an in-run parity check failed.  Extra objects:
-  roofline       the bound that limits the kernel: fp32 VALU issue without FMA credit.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the headline (`value`,
+`ms_per_step`, the workload in `config`); nothing else is launched.  --dump-outputs DIR writes what the last timed step
+computed as DIR/*.npy (dump_outputs below).  --full adds everything after the timed region — the extra launches, the
+checks and the objects below — and then exits non-zero if an in-run parity check failed.  Objects of --full:
+  per_rank       every rank's launch time, gather time, rays per sample, executed lane-ops and launch shape.
+  stripe_parity_vs_single_device   (N > 1) the gathered frame against a single-device render of the whole frame.
+  roofline      the bound that limits the kernel: fp32 VALU issue without FMA credit.
                  `achieved` = EXECUTED lane-operations per launch / kernel time, and the executed work is COUNTED BY
                  THE RUN ITSELF: one extra, untimed launch of the same shape with SRT_RENDER_COUNT_WORK returns what the
                  kernel's loops did (pool steps, sphere / bound / box / BVH-child / triangle tests, srt_get_work_counts);
@@ -145,6 +150,34 @@ def load_json(path):
         return {}
 
 
+DUMP_BUDGET = 64 * 10**6  # bytes of --dump-outputs files, all together
+
+
+def dump_outputs(out_dir, framebuffer, accumulator):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files in out_dir.
+      framebuffer.npy   [rows, W, 3]  the packed pixels' r, g, b bytes (0..255; the alpha byte is 0 by construction of the tone-map)
+      accumulator.npy   [rows, W, 4]  the float4 accumulator (r, g, b, a), turned into memory-row order like the framebuffer
+    framebuffer: uint32 [rows, W] (a << 24 | r << 16 | g << 8 | b); accumulator: float32 [rows, W, 4] or None (N > 1: rank 0 has
+    the gathered frame but only its own band's accumulator).  Over DUMP_BUDGET the same fixed, seeded sample of pixels is taken
+    from every array: [k, channels] each, plus pixel_index.npy (float64, row-major index into the dumped rows)."""
+    import numpy as np
+
+    fb = np.ascontiguousarray(framebuffer).view(np.uint32)
+    arrays = {"framebuffer": np.stack([(fb >> s) & 0xFF for s in (16, 8, 0)], axis=-1).astype(np.float32)}
+    if accumulator is not None:
+        arrays["accumulator"] = np.ascontiguousarray(accumulator, dtype=np.float32)
+    n_px = fb.size
+    per_px = sum(a.nbytes for a in arrays.values()) // n_px
+    if n_px * per_px > DUMP_BUDGET:
+        k = (DUMP_BUDGET - 4096) // (per_px + 8)  # (+ the index; 4 KB for the .npy headers)
+        idx = np.sort(np.random.default_rng(SEED).choice(n_px, size=k, replace=False))
+        arrays = {n: a.reshape(n_px, -1)[idx] for n, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(out_dir, n + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -158,7 +191,13 @@ def main():
     ap.add_argument("--spp", type=int, default=None, help="samples per pixel of the launch (N > 1 without --config: per GPU-share, x N)")
     ap.add_argument("--bounces", type=int, default=None)
     ap.add_argument("--mesh", type=int, default=None, metavar="N", help="EXTENSION: replace Scene1's big ball by an N x N tessellation")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything besides the headline: the counting and steady-state launches (roofline, "
+                         "algorithmic, roofline_hbm, per_rank), the N > 1 stripe parity, readback, a fresh context's first launch and "
+                         "the CPU baseline with its parity check")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; a fixed sample above 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--cpu-spp", type=int, default=16, help="spp of the bounded CPU sample (16 spp at 1080p = about 20 s of CPU work)")
     ap.add_argument("--balance", default="probe", choices=["equal", "probe"],
                     help="row-stripe split for N > 1 (and for --rank): 'probe' (default): contiguous bands of equal estimated cost from the "
@@ -321,7 +360,7 @@ def main():
     n_warm = max(args.warmup, 1) if world > 1 else args.warmup
     for i in range(n_warm):
         step()
-        if i == 0:
+        if i == 0 and args.full:
             cold_ms = float(pt.stats().kernel_ms)  # synchronises; warm-up only
     fence()
 
@@ -338,184 +377,23 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     stream_ms = ev0.elapsed_time(ev1) / args.steps  # per step on the launch stream (kernels + gather enqueue)
-    step()                                           # one more identical step, outside the timed region, with the library's own event pair:
-    last_launch_ms = float(pt.stats().kernel_ms)     # the kernel time of a steady-state launch as srt_get_stats reports it
+    if args.dump_outputs and rank == 0:
+        # before anything else renders: the frame and the accumulator still hold the last timed step's result
+        acc = pt.accumulator()[::-1][rb:re] if world == 1 else None  # (scene rows -> memory rows)
+        dump_outputs(args.dump_outputs, (gather_frame if world > 1 else frame[rb:re]).cpu().numpy(), acc)
+    if args.full:
+        step()                                           # one more identical step, outside the timed region, with the library's own event pair:
+        last_launch_ms = float(pt.stats().kernel_ms)     # the kernel time of a steady-state launch as srt_get_stats reports it
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    launch_ms_mean = sum(a.elapsed_time(b) for a, b, _ in kernel_events) / len(kernel_events) if kernel_events else stream_ms  # this rank's srt_render launches only
-    gather_ms_mean = sum(b.elapsed_time(c) for _, b, c in kernel_events) / len(kernel_events) if kernel_events else 0.0  # ... and its gathers (stream time behind the kernel)
-    k_ms = stream_ms if world == 1 else launch_ms_mean
-    st_timed = pt.stats()  # the shape of the last timed launch
-
-    # rays per sample and the executed work (both deterministic): one extra, untimed launch of the same shape with the counters on
-    step(count_rays=True, count_work=True)
-    st_last = pt.stats()
-    rays = st_last.rays
-    wc = pt.work_counts().as_dict()
-    counting_launch_ms = float(st_last.kernel_ms)
-    shape = {"tile_rows": int(st_last.tile_rows), "grid_layers": int(st_last.sample_chunks), "chunk_samples": int(st_last.chunk_samples),
-             "shape_source": "work record of the band's first launch" if st_last.shape_source else "static rule (request and grid)",
-             "same_as_timed_launches": (st_last.tile_rows, st_last.sample_chunks, st_last.chunk_samples) == (st_timed.tile_rows, st_timed.sample_chunks, st_timed.chunk_samples)}
-    # sample-chunked launch (srt_stats.sample_chunks > 1): the colours of every TRACED sample go through HBM once (16 B
-    # written by pathtrace_kernel, 16 B read by fold_kernel).  Traced pixels = pixels whose primary ray hits something:
-    # a 1-spp / 1-bounce launch casts exactly one extra ray for each of them.
-    chunks = int(st_last.sample_chunks)
-    traced_samples = 0
-    if chunks > 1:
-        pt.render(spp=1, bounces=1, seed=SEED, first_sample=1, reset=True, rows=(rb, re), count_rays=True)
-        traced_samples = (pt.stats().rays - W * (re - rb)) * spp
-    local_samples = W * (re - rb) * spp
-    rbar_local = rays / local_samples
-
     total_samples = (W * (re - rb) if share else W * H) * spp
     value = total_samples * args.steps / dt
 
-    ex_local = executed_laneops(wc, local_samples, bool(n_tri))
-    mine = [k_ms, float(rays), float(local_samples), float(ex_local if ex_local is not None else -1.0), gather_ms_mean,
-            float(wc["pool_steps"]), float(st_last.sample_chunks), float(st_last.tile_rows)]
-    if world > 1:
-        info = torch.tensor(mine, dtype=torch.float64, device=cdev)
-        allinfo = [torch.zeros_like(info) for _ in range(world)]
-        dist.all_gather(allinfo, info)
-        per_rank = [[float(x) for x in t.tolist()] for t in allinfo]
-    else:
-        per_rank = [mine]
-
-    # the gathered multi-rank frame must equal a single-device render of the whole frame
-    stripe_parity = None
-    if world > 1:
-        step()
-        fence()
-        if rank == 0:
-            import numpy as np
-
-            gathered = (host_frame if rehearsal else frame.cpu()).numpy().view(np.uint32)
-            chk = new_tracer()
-            chk.render(spp=spp, bounces=bounces, seed=SEED)
-            stripe_parity = bool(np.array_equal(chk.framebuffer(), gathered))
-            chk.close()
-
-    # ---- the frame's way into host memory (N = 1): where the reference's frame ends (renderSurface->pixels, Raytracer.cpp:64,75).
-    # After the timed region, never in `value`: srt_read_framebuffer into pinned and into pageable memory, and a double-buffered
-    # loop — frame k is copied on a second stream while frame k + 1 renders into the other framebuffer (srt_bind_output does
-    # not wait) — the way a host that blits every frame would run it.
-    readback = None
-    if world == 1 and rank == 0:
-        import numpy as np
-
-        step_ms = dt / args.steps * 1e3
-        pinned = torch.empty((H, W), dtype=torch.int32).pin_memory()
-        pageable = np.empty((H, W), dtype=np.uint32)
-
-        def read_ms(ptr, reps=5):
-            best = None
-            for _ in range(reps):
-                t = time.perf_counter()
-                pt._ck(pt.L.srt_read_framebuffer(pt._h, C.c_void_p(ptr), W * 4, rb, re))
-                e = (time.perf_counter() - t) * 1e3
-                best = e if best is None else min(best, e)
-            return best
-
-        pin_ms = read_ms(pinned.data_ptr() + rb * W * 4)
-        page_ms = read_ms(pageable.ctypes.data + rb * W * 4)
-        frames = [frame, torch.zeros_like(frame)]
-        hosts = [pinned, torch.empty((H, W), dtype=torch.int32).pin_memory()]
-        copy_stream = torch.cuda.Stream(dev)
-        copied = [torch.cuda.Event() for _ in range(2)]
-        n_ov = max(args.steps, 4)
-
-        def overlapped(n):
-            for k in range(n):
-                i = k & 1
-                if k >= 2:
-                    stream.wait_event(copied[i])  # the copy of frame k - 2 has left this framebuffer
-                pt.bind_output(d_framebuffer=frames[i].data_ptr())
-                pt.render(spp=spp, bounces=bounces, seed=SEED, first_sample=1, reset=True, rows=(rb, re))
-                # srt_read_framebuffer_async: the copy of THIS frame on the copy stream, behind the render just enqueued
-                pt.read_framebuffer_async(hosts[i].data_ptr() + rb * W * 4, rows=(rb, re), copy_stream=copy_stream.cuda_stream)
-                copied[i].record(copy_stream)
-
-        overlapped(2)
-        torch.cuda.synchronize(dev)
-        t_ov = time.perf_counter()
-        overlapped(n_ov)
-        torch.cuda.synchronize(dev)
-        ov_ms = (time.perf_counter() - t_ov) * 1e3 / n_ov
-        same = bool(torch.equal(hosts[0][rb:re], hosts[1][rb:re]) and torch.equal(hosts[0][rb:re], frames[0][rb:re].cpu()))
-        pt.bind_output(d_framebuffer=frame.data_ptr())
-        readback = {
-            "frame_to_host_ms": pin_ms, "frame_to_host_ms_pageable": page_ms, "bytes": W * (re - rb) * 4,
-            "how": "srt_read_framebuffer (synchronous hipMemcpy2D) of this launch's rows into pinned / pageable host memory, best of 5, after the timed region",
-            "fraction_of_a_step": pin_ms / step_ms,
-            "value_including_readback": total_samples / ((step_ms + pin_ms) * 1e-3),
-            "ms_per_step_with_overlapped_readback": ov_ms,
-            "value_with_overlapped_readback": total_samples / (ov_ms * 1e-3),
-            "overlapped_how": "%d steps, two framebuffers: frame k is copied device-to-pinned on a second stream (srt_read_framebuffer_async) while frame k + 1 renders (srt_bind_output does not wait); wall clock / steps" % n_ov,
-            "overlapped_frames_identical": same,
-        }
-
-    # ---- the first launch of a frame with WARM clocks (N = 1): a fresh context — no recorded costs, the dispatch order estimated on
-    # the device — renders the same frame right after the timed region; next to kernel_ms_cold_first_launch (the run's very first
-    # step, which also pays the clock ramp of a GPU that was idle a moment ago) this separates what the missing record costs
-    # from what the power management does.  Event pair on the stream around srt_render, order estimate included.
-    warm_first_ms = None
-    if world == 1 and rank == 0:
-        trials = []
-        for _ in range(2):  # (two fresh contexts, the smaller figure: a lone outlier of tens of milliseconds has been seen on this pool)
-            fresh = new_tracer()
-            fresh.bind_output(d_framebuffer=frames[1].data_ptr())
-            fresh.set_stream(stream.cuda_stream)
-            # (what a context allocates once, on its first launch of a grid — the cost-record buffers, 1 MB of pinned memory at 1080p,
-            # tens of milliseconds of host time — is initialisation like srt_create: a first pass allocates, then srt_set_scene makes
-            # the context forget everything it has learned about the frame, as after any scene change)
-            fresh.render(spp=4, bounces=1, seed=SEED, first_sample=1, reset=True, rows=(rb, re))
-            fresh.wait()
-            fresh.set_meshes(meshes, n_mesh)
-            fresh.set_scene(objs, n_obj)
-            for _ in range(3):
-                pt.render(spp=spp, bounces=bounces, seed=SEED, first_sample=1, reset=True, rows=(rb, re))
-            f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            f0.record(stream)
-            fresh.render(spp=spp, bounces=bounces, seed=SEED, first_sample=1, reset=True, rows=(rb, re))
-            f1.record(stream)
-            torch.cuda.synchronize(dev)
-            trials.append(f0.elapsed_time(f1))
-            fresh.close()
-        warm_first_ms = min(trials)
-
     out = None
     if rank == 0:
-        rbar = sum(p[1] for p in per_rank) / sum(p[2] for p in per_rank)
         key = workload_key(cfg["scene"], cfg["mesh"], W, H, (rb, re), spp, bounces)
-        all_counters = load_json(os.path.join(ROOT, "profiles", "counters.json"))
-        counters = all_counters.get(key, {}) if world == 1 else {}
-        rank_rows = [tuple(bands[i]) if not share else (rb, re) for i in range(len(per_rank))]
-        # EXECUTED lane-ops of every rank's launch, counted by that rank's own counting launch (executed_laneops); one rank -> its
-        # launch; N ranks -> the sum over the SLOWEST rank's launch time against N GPUs' peak, every rank's own fraction in per_rank.
-        # Next to it, outside the roofline: the brute-force-equivalent count of the SURVEY §8d formula with that rank's own rays per
-        # sample (mesh scenes: the BVH work as counted) — what a kernel without culling would have had to execute.
-        counted_ok = all(p[3] >= 0 for p in per_rank)
-        rank_ex = [p[3] if p[3] >= 0 else 0.0 for p in per_rank]
-        rank_bf = []
-        for (k_i, rays_i, samples_i, *_rest) in per_rank:
-            rank_bf.append(algorithmic_laneops_per_sample(rays_i / samples_i, n_sph, n_box, n_tri) * samples_i)
-        slowest_ms = max(p[0] for p in per_rank)
-        achieved_valu = sum(rank_ex) / (slowest_ms * 1e-3)
-        bruteforce_valu = sum(rank_bf) / (slowest_ms * 1e-3)
-        peak_valu = VALU_PEAK_LANEOPS * len(per_rank)
-        abytes = algorithmic_bytes(W, re - rb, n_obj, resume=False)
-        abytes += 32 * traced_samples  # sample-chunked launch: + 16 B written and 16 B read per traced sample (the fold's stream; an upper figure since the chained chunks)
-        achieved_gbs = abytes / (k_ms * 1e-3) / 1e9
-        kind = ("executed lane-ops COUNTED by this run (one untimed launch of the same shape with SRT_RENDER_COUNT_WORK; `counted`) priced with "
-                "`valu_model`: tests x the SURVEY §8d constants + the stated per-bound / per-BVH-child / per-step figures (DESIGN.md §4.7)")
-        if not counted_ok:
-            kind = "UNCOUNTED: a launch whose scene image lives in HBM keeps no loop counts; `achieved` is 0"
-        if world > 1:
-            kind += "; N = %d: sum of all ranks' executed lane-ops / the slowest rank's launch time, peak = %d GPUs" % (world, world)
-        # pipe utilisation as rocprofv3 saw it: computed INSIDE the counter pass (its own SQ_INSTS_VALU over its own launch time), copied from profiles
-        measured_issue = counters.get("valu_issue_frac")
         custom = any(getattr(args, k) is not None for k in ("scene", "width", "height", "spp", "bounces", "mesh"))
         what = "custom workload (config %d with overrides)" % cfg_id if custom else "config %d" % cfg_id
         if world > 1 and not args.config and not custom:
@@ -548,157 +426,329 @@ def main():
                                  args.balance,
                                  "dist.gather over RCCL" if gather_method == "gather" else "RCCL gather (%s)" % gather_method),
                 "bands": bands if not share else [[rb, re]],
-                "rays_per_sample": rbar,
-                # what srt_render chose for this rank's launch (srt_stats): a function of the request, the grid, the CU count and the
-                # band's recorded loop counts — the same in every run
-                "launch_shape": shape,
             },
-            "roofline": {
-                "bound": "valu",
-                "achieved": achieved_valu / 1e12,
-                "peak": peak_valu / 1e12,
-                "unit": "TFLOP/s",
-                "frac": achieved_valu / peak_valu,
-                "traffic": counters.get("hbm_bytes_per_launch"),
-                "kernel": "srt::pathtrace_kernel" + (" + srt::fold_kernel (%d sample chunks)" % chunks if chunks > 1 else ""),
-                "kernel_ms": slowest_ms,
-                "kernel_ms_source": "HIP events on the launch stream around the %d timed steps / %d" % (args.steps, args.steps)
-                                    if world == 1 else "the SLOWEST rank's mean over the HIP event pairs around each timed step's srt_render (the gather outside); all ranks in per_rank",
-                "kernel_ms_last_timed_launch": last_launch_ms,  # (the launch right after the timed region: the timed ones carry no events)
-                "kernel_ms_cold_first_launch": cold_ms,
-                "kernel_ms_first_launch_warm_clocks": warm_first_ms,
-                "kernel_ms_counting_launch": counting_launch_ms,  # the same launch through the instantiation that keeps the loop counts (untimed)
-                "peak_note": "%sfp32 VALU without FMA credit: 256 CU x 4 SIMD x 32 lanes x 2.4 GHz (contraction is forbidden by the bit-exactness contract)" %
-                             ("%d GPUs x " % world if world > 1 else ""),
-                "achieved_kind": kind,
-                "counted": wc if world == 1 else {"note": "rank 0's counts; every rank's executed lane-ops in per_rank", **wc},
-                "valu_model": VALU_MODEL,
-                "executed_laneops_per_sample": sum(rank_ex) / sum(p[2] for p in per_rank),
-                # bounce rays (every ray but the samples' primary ones) per lane-step of the pool: how full its 64 lanes are
-                "pool_lane_efficiency": (rays - local_samples) / (64.0 * wc["pool_steps"]) if wc.get("pool_steps") else None,
-                "rays_per_sample": rbar,
-                "measured_valu_issue_frac": measured_issue,
-                "measured_valu_issue_frac_note": "from profiles/counters.json, NOT from this run: SQ_INSTS_VALU x 64 / the launch time of the rocprofv3 pass "
-                                                 "that counted it / peak (valu_issue_pass_launch_ms); clock-independent twin: measured_valu_issue_frac_grbm" if measured_issue else None,
-                "measured_valu_issue_frac_grbm": counters.get("valu_issue_frac_grbm"),
-                "measured_pass_launch_ms": counters.get("valu_issue_pass_launch_ms"),
-                "measured_source": counters.get("source"),
-            },
-            "algorithmic": {
-                "bruteforce_equivalent_tflops": bruteforce_valu / 1e12,
-                "speedup_vs_bruteforce": bruteforce_valu / achieved_valu if achieved_valu else None,
-                "laneops_per_sample": sum(rank_bf) / sum(p[2] for p in per_rank),
-                "note": "SURVEY §8d formula F = R(24 N_sph + 35 N_box + 40 N_tri) + 60 R + 30 with this run's rays per sample: what a scan of every primitive for every ray "
-                        "would execute in the same time; NOT a utilisation (it passes the peak where the kernel culls, walks a BVH and shares the primary hit among a pixel's samples)",
-            },
-            "roofline_hbm": {
-                "bound": "hbm",
-                "achieved": achieved_gbs,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved_gbs / HBM_PEAK_GBS,
-                "traffic": counters.get("hbm_bytes_per_launch"),
-                "algorithmic_bytes_per_launch": abytes,
-                "note": "compulsory bytes only (20 B/pixel + scene%s); not the limiting resource" %
-                        (" + 32 B per traced sample of the chunked launch's sample buffer — what the launch moves if every chunk goes through the buffer; chunks that "
-                         "find their tile's running mean at their own first sample fold their samples themselves (chained chunks, DESIGN.md §4.5), so `traffic` can come out "
-                         "BELOW this figure" if chunks > 1 else ""),
-            },
-            "per_rank": [{"kernel_ms": p[0], "gather_ms": p[4] if world > 1 else None, "rays_per_sample": p[1] / p[2], "rows": list(rank_rows[i]),
-                          "executed_laneops": rank_ex[i], "frac": rank_ex[i] / (p[0] * 1e-3) / VALU_PEAK_LANEOPS, "pool_steps": p[5],
-                          "grid_layers": int(p[6]), "tile_rows": int(p[7])} for i, p in enumerate(per_rank)],
         }
-        if readback:
-            out["readback"] = readback
         if calibration:
             out["config"].update(calibration)
             out["config"]["value_including_probe_once"] = total_samples * args.steps / (dt + calibration["probe_ms"] * 1e-3)
-        if world > 1:
-            # the N > 1 step = this rank's launch + the one gather: both halves, as the stream saw them (event pairs)
-            out["gather_ms"] = max(p[4] for p in per_rank)
-            out["gather_ms_note"] = "stream time between the end of a rank's kernel and the end of its part of the gather (rank 0: + the unpack copies), mean over the timed steps, max over ranks; unverified on > 1 GPU until the driver's run"
-        if world > 1 or share:
-            # what every rank's launch of this split took when the ranks were run one after the other on ONE GPU (kernel times
-            # only, no gather; tools/emulate_ranks.py, committed as profiles/emulated_ranks.json) — both splits, so that the
-            # line of an N-GPU run can be read against it.  No scaling curve has been measured on more than one GPU.
-            emu = load_json(os.path.join(ROOT, "profiles", "emulated_ranks.json")).get("config %d" % cfg_id, {})
-            n_key = str(share[1] if share else world)
-            if emu.get(n_key):
-                out["config"]["emulated_on_one_gpu"] = dict(emu[n_key], note=emu.get("note"))
-        if world > 1:
-            out["stripe_parity_vs_single_device"] = stripe_parity
-            if stripe_parity is False:
-                out["value"] = None
-                out["error"] = "gathered row stripes differ from the single-device frame; speed not reported"
         if rehearsal:
             out["rehearsal"] = "all ranks on cuda:0, gloo + host staging: control-flow test only, not a measurement"
 
-    # ---- CPU baseline + in-run parity (rank 0, N = 1 only) -----------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        import numpy as np
-        import srt_oracle_py as O
+    # ---- --full: everything besides the headline (launches after the timed region, checks, other figures) ------------
+    if args.full:
+        launch_ms_mean = sum(a.elapsed_time(b) for a, b, _ in kernel_events) / len(kernel_events) if kernel_events else stream_ms  # this rank's srt_render launches only
+        gather_ms_mean = sum(b.elapsed_time(c) for _, b, c in kernel_events) / len(kernel_events) if kernel_events else 0.0  # ... and its gathers (stream time behind the kernel)
+        k_ms = stream_ms if world == 1 else launch_ms_mean
+        st_timed = pt.stats()  # the shape of the last timed launch
 
-        cores = host_cpu_share()
-        oarr = C.cast(objs, C.POINTER(O.Object))
-        omesh = (C.cast(meshes, C.POINTER(O.Mesh)), n_mesh) if n_mesh else None
-        if n_tri:
-            # the CPU port scans every triangle for every ray (~10^5 x the work of an analytic ray): the bounded
-            # sample is a 32 x 16 pixel window over the mesh, inside this rank's rows, at the config's bounces
-            cspp = min(args.cpu_spp, 4)
-            cy = min(max(H // 2, (H - re) + 8), (H - rb) - 8)  # scene row nearest the image centre inside the band
-            mr = H - 1 - cy
-            rows_w, cols_w = (max(rb, mr - 8), min(re, mr + 8)), (W // 2 - 16, W // 2 + 16)
+        # rays per sample and the executed work (both deterministic): one extra, untimed launch of the same shape with the counters on
+        step(count_rays=True, count_work=True)
+        st_last = pt.stats()
+        rays = st_last.rays
+        wc = pt.work_counts().as_dict()
+        counting_launch_ms = float(st_last.kernel_ms)
+        shape = {"tile_rows": int(st_last.tile_rows), "grid_layers": int(st_last.sample_chunks), "chunk_samples": int(st_last.chunk_samples),
+                 "shape_source": "work record of the band's first launch" if st_last.shape_source else "static rule (request and grid)",
+                 "same_as_timed_launches": (st_last.tile_rows, st_last.sample_chunks, st_last.chunk_samples) == (st_timed.tile_rows, st_timed.sample_chunks, st_timed.chunk_samples)}
+        # sample-chunked launch (srt_stats.sample_chunks > 1): the colours of every TRACED sample go through HBM once (16 B
+        # written by pathtrace_kernel, 16 B read by fold_kernel).  Traced pixels = pixels whose primary ray hits something:
+        # a 1-spp / 1-bounce launch casts exactly one extra ray for each of them.
+        chunks = int(st_last.sample_chunks)
+        traced_samples = 0
+        if chunks > 1:
+            pt.render(spp=1, bounces=1, seed=SEED, first_sample=1, reset=True, rows=(rb, re), count_rays=True)
+            traced_samples = (pt.stats().rays - W * (re - rb)) * spp
+        local_samples = W * (re - rb) * spp
+        rbar_local = rays / local_samples
+
+        ex_local = executed_laneops(wc, local_samples, bool(n_tri))
+        mine = [k_ms, float(rays), float(local_samples), float(ex_local if ex_local is not None else -1.0), gather_ms_mean,
+                float(wc["pool_steps"]), float(st_last.sample_chunks), float(st_last.tile_rows)]
+        if world > 1:
+            info = torch.tensor(mine, dtype=torch.float64, device=cdev)
+            allinfo = [torch.zeros_like(info) for _ in range(world)]
+            dist.all_gather(allinfo, info)
+            per_rank = [[float(x) for x in t.tolist()] for t in allinfo]
         else:
-            cspp = args.cpu_spp
-            rows_w, cols_w = (rb, re), None
-        t1 = time.perf_counter()
-        ofb, oacc, orays = O.render(oarr, n_obj, O.default_environment(), O.default_camera(FOV), W, H, spp=cspp,
-                                    bounces=bounces, seed=SEED, pow_mode=O.POW_SHARED, threads=cores, rows=rows_w, cols=cols_w, meshes=omesh)
-        cpu_dt = time.perf_counter() - t1
-        cw = (cols_w[1] - cols_w[0]) if cols_w else W
-        cpu_samples = cw * (rows_w[1] - rows_w[0]) * cspp
-        # same sample on the GPU: the frames must match before any speed is reported
-        pt.bind_output()  # own buffers
-        pt.render(spp=cspp, bounces=bounces, seed=SEED, rows=(rb, re))
-        gfb, gacc = pt.framebuffer(), pt.accumulator()
-        cs = slice(*cols_w) if cols_w else slice(None)
-        ys = slice(H - rows_w[1], H - rows_w[0])  # scene rows of the window (accumulator layout)
-        g_win, o_win = gfb[rows_w[0]:rows_w[1], cs], ofb[rows_w[0]:rows_w[1], cs]
-        parity = bool(np.array_equal(g_win, o_win) and np.array_equal(gacc[ys, cs].view(np.uint32), oacc[ys, cs].view(np.uint32)))
-        ref_split = None
-        if not n_tri and not share:
-            # reference-faithful split (16 column stripes, Raytracer.cpp:330-342), 1 spp
-            t2 = time.perf_counter()
-            O.render(oarr, n_obj, O.default_environment(), O.default_camera(FOV), W, H, spp=1, bounces=bounces,
-                     seed=SEED, pow_mode=O.POW_LIBM, threads=16, split=O.SPLIT_REF_COLS)
-            ref_dt = time.perf_counter() - t2
-            ref_split = {"value": W * H / ref_dt, "threads": 16, "spp": 1, "seconds": ref_dt}
-        cpu_model = ""
-        try:
-            for line in open("/proc/cpuinfo"):
-                if line.startswith("model name"):
-                    cpu_model = line.split(":", 1)[1].strip()
-                    break
-        except OSError:
-            pass
-        out["cpu_baseline"] = {
-            "value": cpu_samples / cpu_dt,
-            "unit": "path-samples/s",
-            "cores": cores,
-            "kind": "port",
-            "sample": "same scene/camera/seed, %s of the %dx%d frame, %d spp, %d bounces, over %d threads (%.2f s)" %
-                      ("memory rows %d-%d x columns %d-%d" % (rows_w + cols_w) if cols_w else "memory rows %d-%d" % rows_w,
-                       W, H, cspp, bounces, cores, cpu_dt),
-            "cpu_model": cpu_model,
-            "reference_split_16_column_stripes": ref_split,
-            "parity_frame_hash_gpu": O.frame_hash(g_win),
-            "parity_frame_hash_cpu": O.frame_hash(o_win),
-            "parity_bit_exact": parity,
-        }
-        if not parity:
-            out["value"] = None
-            out["error"] = "GPU frame differs from the CPU oracle on the baseline sample; speed not reported"
+            per_rank = [mine]
+
+        # the gathered multi-rank frame must equal a single-device render of the whole frame
+        stripe_parity = None
+        if world > 1:
+            step()
+            fence()
+            if rank == 0:
+                import numpy as np
+
+                gathered = (host_frame if rehearsal else frame.cpu()).numpy().view(np.uint32)
+                chk = new_tracer()
+                chk.render(spp=spp, bounces=bounces, seed=SEED)
+                stripe_parity = bool(np.array_equal(chk.framebuffer(), gathered))
+                chk.close()
+
+        # ---- the frame's way into host memory (N = 1): where the reference's frame ends (renderSurface->pixels, Raytracer.cpp:64,75).
+        # After the timed region, never in `value`: srt_read_framebuffer into pinned and into pageable memory, and a double-buffered
+        # loop — frame k is copied on a second stream while frame k + 1 renders into the other framebuffer (srt_bind_output does
+        # not wait) — the way a host that blits every frame would run it.
+        readback = None
+        if world == 1 and rank == 0:
+            import numpy as np
+
+            step_ms = dt / args.steps * 1e3
+            pinned = torch.empty((H, W), dtype=torch.int32).pin_memory()
+            pageable = np.empty((H, W), dtype=np.uint32)
+
+            def read_ms(ptr, reps=5):
+                best = None
+                for _ in range(reps):
+                    t = time.perf_counter()
+                    pt._ck(pt.L.srt_read_framebuffer(pt._h, C.c_void_p(ptr), W * 4, rb, re))
+                    e = (time.perf_counter() - t) * 1e3
+                    best = e if best is None else min(best, e)
+                return best
+
+            pin_ms = read_ms(pinned.data_ptr() + rb * W * 4)
+            page_ms = read_ms(pageable.ctypes.data + rb * W * 4)
+            frames = [frame, torch.zeros_like(frame)]
+            hosts = [pinned, torch.empty((H, W), dtype=torch.int32).pin_memory()]
+            copy_stream = torch.cuda.Stream(dev)
+            copied = [torch.cuda.Event() for _ in range(2)]
+            n_ov = max(args.steps, 4)
+
+            def overlapped(n):
+                for k in range(n):
+                    i = k & 1
+                    if k >= 2:
+                        stream.wait_event(copied[i])  # the copy of frame k - 2 has left this framebuffer
+                    pt.bind_output(d_framebuffer=frames[i].data_ptr())
+                    pt.render(spp=spp, bounces=bounces, seed=SEED, first_sample=1, reset=True, rows=(rb, re))
+                    # srt_read_framebuffer_async: the copy of THIS frame on the copy stream, behind the render just enqueued
+                    pt.read_framebuffer_async(hosts[i].data_ptr() + rb * W * 4, rows=(rb, re), copy_stream=copy_stream.cuda_stream)
+                    copied[i].record(copy_stream)
+
+            overlapped(2)
+            torch.cuda.synchronize(dev)
+            t_ov = time.perf_counter()
+            overlapped(n_ov)
+            torch.cuda.synchronize(dev)
+            ov_ms = (time.perf_counter() - t_ov) * 1e3 / n_ov
+            same = bool(torch.equal(hosts[0][rb:re], hosts[1][rb:re]) and torch.equal(hosts[0][rb:re], frames[0][rb:re].cpu()))
+            pt.bind_output(d_framebuffer=frame.data_ptr())
+            readback = {
+                "frame_to_host_ms": pin_ms, "frame_to_host_ms_pageable": page_ms, "bytes": W * (re - rb) * 4,
+                "how": "srt_read_framebuffer (synchronous hipMemcpy2D) of this launch's rows into pinned / pageable host memory, best of 5, after the timed region",
+                "fraction_of_a_step": pin_ms / step_ms,
+                "value_including_readback": total_samples / ((step_ms + pin_ms) * 1e-3),
+                "ms_per_step_with_overlapped_readback": ov_ms,
+                "value_with_overlapped_readback": total_samples / (ov_ms * 1e-3),
+                "overlapped_how": "%d steps, two framebuffers: frame k is copied device-to-pinned on a second stream (srt_read_framebuffer_async) while frame k + 1 renders (srt_bind_output does not wait); wall clock / steps" % n_ov,
+                "overlapped_frames_identical": same,
+            }
+
+        # ---- the first launch of a frame with WARM clocks (N = 1): a fresh context — no recorded costs, the dispatch order estimated on
+        # the device — renders the same frame right after the timed region; next to kernel_ms_cold_first_launch (the run's very first
+        # step, which also pays the clock ramp of a GPU that was idle a moment ago) this separates what the missing record costs
+        # from what the power management does.  Event pair on the stream around srt_render, order estimate included.
+        warm_first_ms = None
+        if world == 1 and rank == 0:
+            trials = []
+            for _ in range(2):  # (two fresh contexts, the smaller figure: a lone outlier of tens of milliseconds has been seen)
+                fresh = new_tracer()
+                fresh.bind_output(d_framebuffer=frames[1].data_ptr())
+                fresh.set_stream(stream.cuda_stream)
+                # (what a context allocates once, on its first launch of a grid — the cost-record buffers, 1 MB of pinned memory at 1080p,
+                # tens of milliseconds of host time — is initialisation like srt_create: a first pass allocates, then srt_set_scene makes
+                # the context forget everything it has learned about the frame, as after any scene change)
+                fresh.render(spp=4, bounces=1, seed=SEED, first_sample=1, reset=True, rows=(rb, re))
+                fresh.wait()
+                fresh.set_meshes(meshes, n_mesh)
+                fresh.set_scene(objs, n_obj)
+                for _ in range(3):
+                    pt.render(spp=spp, bounces=bounces, seed=SEED, first_sample=1, reset=True, rows=(rb, re))
+                f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                f0.record(stream)
+                fresh.render(spp=spp, bounces=bounces, seed=SEED, first_sample=1, reset=True, rows=(rb, re))
+                f1.record(stream)
+                torch.cuda.synchronize(dev)
+                trials.append(f0.elapsed_time(f1))
+                fresh.close()
+            warm_first_ms = min(trials)
+
+        if rank == 0:
+            rbar = sum(p[1] for p in per_rank) / sum(p[2] for p in per_rank)
+            all_counters = load_json(os.path.join(ROOT, "profiles", "counters.json"))
+            counters = all_counters.get(key, {}) if world == 1 else {}
+            rank_rows = [tuple(bands[i]) if not share else (rb, re) for i in range(len(per_rank))]
+            # EXECUTED lane-ops of every rank's launch, counted by that rank's own counting launch (executed_laneops); one rank -> its
+            # launch; N ranks -> the sum over the SLOWEST rank's launch time against N GPUs' peak, every rank's own fraction in per_rank.
+            # Next to it, outside the roofline: the brute-force-equivalent count of the SURVEY §8d formula with that rank's own rays per
+            # sample (mesh scenes: the BVH work as counted) — what a kernel without culling would have had to execute.
+            counted_ok = all(p[3] >= 0 for p in per_rank)
+            rank_ex = [p[3] if p[3] >= 0 else 0.0 for p in per_rank]
+            rank_bf = []
+            for (k_i, rays_i, samples_i, *_rest) in per_rank:
+                rank_bf.append(algorithmic_laneops_per_sample(rays_i / samples_i, n_sph, n_box, n_tri) * samples_i)
+            slowest_ms = max(p[0] for p in per_rank)
+            achieved_valu = sum(rank_ex) / (slowest_ms * 1e-3)
+            bruteforce_valu = sum(rank_bf) / (slowest_ms * 1e-3)
+            peak_valu = VALU_PEAK_LANEOPS * len(per_rank)
+            abytes = algorithmic_bytes(W, re - rb, n_obj, resume=False)
+            abytes += 32 * traced_samples  # sample-chunked launch: + 16 B written and 16 B read per traced sample (the fold's stream; an upper figure since the chained chunks)
+            achieved_gbs = abytes / (k_ms * 1e-3) / 1e9
+            kind = ("executed lane-ops COUNTED by this run (one untimed launch of the same shape with SRT_RENDER_COUNT_WORK; `counted`) priced with "
+                    "`valu_model`: tests x the SURVEY §8d constants + the stated per-bound / per-BVH-child / per-step figures (DESIGN.md §4.7)")
+            if not counted_ok:
+                kind = "UNCOUNTED: a launch whose scene image lives in HBM keeps no loop counts; `achieved` is 0"
+            if world > 1:
+                kind += "; N = %d: sum of all ranks' executed lane-ops / the slowest rank's launch time, peak = %d GPUs" % (world, world)
+            # pipe utilisation as rocprofv3 saw it: computed INSIDE the counter pass (its own SQ_INSTS_VALU over its own launch time), copied from profiles
+            measured_issue = counters.get("valu_issue_frac")
+            out["config"]["rays_per_sample"] = rbar
+            # what srt_render chose for this rank's launch (srt_stats): a function of the request, the grid, the CU count and the
+            # band's recorded loop counts — the same in every run
+            out["config"]["launch_shape"] = shape
+            out.update({
+                "roofline": {
+                    "bound": "valu",
+                    "achieved": achieved_valu / 1e12,
+                    "peak": peak_valu / 1e12,
+                    "unit": "TFLOP/s",
+                    "frac": achieved_valu / peak_valu,
+                    "traffic": counters.get("hbm_bytes_per_launch"),
+                    "kernel": "srt::pathtrace_kernel" + (" + srt::fold_kernel (%d sample chunks)" % chunks if chunks > 1 else ""),
+                    "kernel_ms": slowest_ms,
+                    "kernel_ms_source": "HIP events on the launch stream around the %d timed steps / %d" % (args.steps, args.steps)
+                                        if world == 1 else "the SLOWEST rank's mean over the HIP event pairs around each timed step's srt_render (the gather outside); all ranks in per_rank",
+                    "kernel_ms_last_timed_launch": last_launch_ms,  # (the launch right after the timed region: the timed ones carry no events)
+                    "kernel_ms_cold_first_launch": cold_ms,
+                    "kernel_ms_first_launch_warm_clocks": warm_first_ms,
+                    "kernel_ms_counting_launch": counting_launch_ms,  # the same launch through the instantiation that keeps the loop counts (untimed)
+                    "peak_note": "%sfp32 VALU without FMA credit: 256 CU x 4 SIMD x 32 lanes x 2.4 GHz (contraction is forbidden by the bit-exactness contract)" %
+                                 ("%d GPUs x " % world if world > 1 else ""),
+                    "achieved_kind": kind,
+                    "counted": wc if world == 1 else {"note": "rank 0's counts; every rank's executed lane-ops in per_rank", **wc},
+                    "valu_model": VALU_MODEL,
+                    "executed_laneops_per_sample": sum(rank_ex) / sum(p[2] for p in per_rank),
+                    # bounce rays (every ray but the samples' primary ones) per lane-step of the pool: how full its 64 lanes are
+                    "pool_lane_efficiency": (rays - local_samples) / (64.0 * wc["pool_steps"]) if wc.get("pool_steps") else None,
+                    "rays_per_sample": rbar,
+                    "measured_valu_issue_frac": measured_issue,
+                    "measured_valu_issue_frac_note": "from profiles/counters.json, NOT from this run: SQ_INSTS_VALU x 64 / the launch time of the rocprofv3 pass "
+                                                     "that counted it / peak (valu_issue_pass_launch_ms); clock-independent twin: measured_valu_issue_frac_grbm" if measured_issue else None,
+                    "measured_valu_issue_frac_grbm": counters.get("valu_issue_frac_grbm"),
+                    "measured_pass_launch_ms": counters.get("valu_issue_pass_launch_ms"),
+                    "measured_source": counters.get("source"),
+                },
+                "algorithmic": {
+                    "bruteforce_equivalent_tflops": bruteforce_valu / 1e12,
+                    "speedup_vs_bruteforce": bruteforce_valu / achieved_valu if achieved_valu else None,
+                    "laneops_per_sample": sum(rank_bf) / sum(p[2] for p in per_rank),
+                    "note": "SURVEY §8d formula F = R(24 N_sph + 35 N_box + 40 N_tri) + 60 R + 30 with this run's rays per sample: what a scan of every primitive for every ray "
+                            "would execute in the same time; NOT a utilisation (it passes the peak where the kernel culls, walks a BVH and shares the primary hit among a pixel's samples)",
+                },
+                "roofline_hbm": {
+                    "bound": "hbm",
+                    "achieved": achieved_gbs,
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": achieved_gbs / HBM_PEAK_GBS,
+                    "traffic": counters.get("hbm_bytes_per_launch"),
+                    "algorithmic_bytes_per_launch": abytes,
+                    "note": "compulsory bytes only (20 B/pixel + scene%s); not the limiting resource" %
+                            (" + 32 B per traced sample of the chunked launch's sample buffer — what the launch moves if every chunk goes through the buffer; chunks that "
+                             "find their tile's running mean at their own first sample fold their samples themselves (chained chunks, DESIGN.md §4.5), so `traffic` can come out "
+                             "BELOW this figure" if chunks > 1 else ""),
+                },
+                "per_rank": [{"kernel_ms": p[0], "gather_ms": p[4] if world > 1 else None, "rays_per_sample": p[1] / p[2], "rows": list(rank_rows[i]),
+                              "executed_laneops": rank_ex[i], "frac": rank_ex[i] / (p[0] * 1e-3) / VALU_PEAK_LANEOPS, "pool_steps": p[5],
+                              "grid_layers": int(p[6]), "tile_rows": int(p[7])} for i, p in enumerate(per_rank)],
+            })
+            if readback:
+                out["readback"] = readback
+            if world > 1:
+                # the N > 1 step = this rank's launch + the one gather: both halves, as the stream saw them (event pairs)
+                out["gather_ms"] = max(p[4] for p in per_rank)
+                out["gather_ms_note"] = "stream time between the end of a rank's kernel and the end of its part of the gather (rank 0: + the unpack copies), mean over the timed steps, max over ranks; not yet measured on more than one GPU"
+            if world > 1 or share:
+                # what every rank's launch of this split took when the ranks were run one after the other on ONE GPU (kernel times
+                # only, no gather; tools/emulate_ranks.py, committed as profiles/emulated_ranks.json) — both splits, so that the
+                # line of an N-GPU run can be read against it.  No scaling curve has been measured on more than one GPU.
+                emu = load_json(os.path.join(ROOT, "profiles", "emulated_ranks.json")).get("config %d" % cfg_id, {})
+                n_key = str(share[1] if share else world)
+                if emu.get(n_key):
+                    out["config"]["emulated_on_one_gpu"] = dict(emu[n_key], note=emu.get("note"))
+            if world > 1:
+                out["stripe_parity_vs_single_device"] = stripe_parity
+                if stripe_parity is False:
+                    out["value"] = None
+                    out["error"] = "gathered row stripes differ from the single-device frame; speed not reported"
+
+        # ---- CPU baseline + in-run parity (rank 0, N = 1 only) -----------------------------
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            sys.path.insert(0, os.path.join(ROOT, "oracle"))
+            import numpy as np
+            import srt_oracle_py as O
+
+            cores = host_cpu_share()
+            oarr = C.cast(objs, C.POINTER(O.Object))
+            omesh = (C.cast(meshes, C.POINTER(O.Mesh)), n_mesh) if n_mesh else None
+            if n_tri:
+                # the CPU port scans every triangle for every ray (~10^5 x the work of an analytic ray): the bounded
+                # sample is a 32 x 16 pixel window over the mesh, inside this rank's rows, at the config's bounces
+                cspp = min(args.cpu_spp, 4)
+                cy = min(max(H // 2, (H - re) + 8), (H - rb) - 8)  # scene row nearest the image centre inside the band
+                mr = H - 1 - cy
+                rows_w, cols_w = (max(rb, mr - 8), min(re, mr + 8)), (W // 2 - 16, W // 2 + 16)
+            else:
+                cspp = args.cpu_spp
+                rows_w, cols_w = (rb, re), None
+            t1 = time.perf_counter()
+            ofb, oacc, orays = O.render(oarr, n_obj, O.default_environment(), O.default_camera(FOV), W, H, spp=cspp,
+                                        bounces=bounces, seed=SEED, pow_mode=O.POW_SHARED, threads=cores, rows=rows_w, cols=cols_w, meshes=omesh)
+            cpu_dt = time.perf_counter() - t1
+            cw = (cols_w[1] - cols_w[0]) if cols_w else W
+            cpu_samples = cw * (rows_w[1] - rows_w[0]) * cspp
+            # same sample on the GPU: the frames must match before any speed is reported
+            pt.bind_output()  # own buffers
+            pt.render(spp=cspp, bounces=bounces, seed=SEED, rows=(rb, re))
+            gfb, gacc = pt.framebuffer(), pt.accumulator()
+            cs = slice(*cols_w) if cols_w else slice(None)
+            ys = slice(H - rows_w[1], H - rows_w[0])  # scene rows of the window (accumulator layout)
+            g_win, o_win = gfb[rows_w[0]:rows_w[1], cs], ofb[rows_w[0]:rows_w[1], cs]
+            parity = bool(np.array_equal(g_win, o_win) and np.array_equal(gacc[ys, cs].view(np.uint32), oacc[ys, cs].view(np.uint32)))
+            ref_split = None
+            if not n_tri and not share:
+                # reference-faithful split (16 column stripes, Raytracer.cpp:330-342), 1 spp
+                t2 = time.perf_counter()
+                O.render(oarr, n_obj, O.default_environment(), O.default_camera(FOV), W, H, spp=1, bounces=bounces,
+                         seed=SEED, pow_mode=O.POW_LIBM, threads=16, split=O.SPLIT_REF_COLS)
+                ref_dt = time.perf_counter() - t2
+                ref_split = {"value": W * H / ref_dt, "threads": 16, "spp": 1, "seconds": ref_dt}
+            cpu_model = ""
+            try:
+                for line in open("/proc/cpuinfo"):
+                    if line.startswith("model name"):
+                        cpu_model = line.split(":", 1)[1].strip()
+                        break
+            except OSError:
+                pass
+            out["cpu_baseline"] = {
+                "value": cpu_samples / cpu_dt,
+                "unit": "path-samples/s",
+                "cores": cores,
+                "kind": "port",
+                "sample": "same scene/camera/seed, %s of the %dx%d frame, %d spp, %d bounces, over %d threads (%.2f s)" %
+                          ("memory rows %d-%d x columns %d-%d" % (rows_w + cols_w) if cols_w else "memory rows %d-%d" % rows_w,
+                           W, H, cspp, bounces, cores, cpu_dt),
+                "cpu_model": cpu_model,
+                "reference_split_16_column_stripes": ref_split,
+                "parity_frame_hash_gpu": O.frame_hash(g_win),
+                "parity_frame_hash_cpu": O.frame_hash(o_win),
+                "parity_bit_exact": parity,
+            }
+            if not parity:
+                out["value"] = None
+                out["error"] = "GPU frame differs from the CPU oracle on the baseline sample; speed not reported"
 
     failed = False
     if rank == 0:

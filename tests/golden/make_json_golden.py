@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Generates tests/golden/json_reference.json: inputs + what the REFERENCE's own JSON library
 (/root/reference/Raytracer/json.hpp, run through oracle/_ref/ref_json — `make -C oracle ref`) makes of them.
-Data only: documents, numbers and the reference's outputs.  Needs /root/reference; the fixture travels."""
+Data only: documents, numbers and the reference's outputs.  Needs the reference's sources (oracle/Makefile REFERENCE); the fixtures travel.
+Also tests/golden/json_reference_live.json: the larger differential runs (6000 documents at both indents, 60,000
+numbers; their inputs are regenerated from json_corpus' seeds by the tests) and the shipped scenes through the
+reference library, pinned by SHA-256 digests of the reference's outputs (json_corpus.block_digests)."""
 import base64
 import json
 import os
@@ -13,6 +16,8 @@ sys.path.insert(0, os.path.dirname(HERE))
 import json_corpus  # noqa: E402
 
 REF = os.path.join(HERE, "..", "..", "oracle", "_ref", "ref_json")
+LIVE_DOCS = (6000, 12345, 100)      # count, json_corpus seed, digest block
+LIVE_NUMBERS = (60000, 99, 1000)
 
 
 def ref_lines(docs, indent):
@@ -42,6 +47,36 @@ def main():
     with open(os.path.join(HERE, "json_reference.json"), "w") as f:
         json.dump(fixture, f, separators=(",", ":"))
     print("documents", len(docs), "rejected", sum(a is None for a in d4), "numbers", len(nums))
+    live()
+
+
+def live():
+    import hashlib
+
+    scene_dir = os.path.join(HERE, "..", "..", "software-raytracer_amd", "scenes")
+    fx = {"generator": "tests/golden/make_json_golden.py", "reference": "Raytracer/json.hpp (nlohmann/json 3.11.2) via oracle/ref_json_harness.cpp",
+          "digest": "json_corpus.block_digests: SHA-256 per block of consecutive outputs; *_tags: base64 of json_corpus.item_tags, 2 bytes per output"}
+    b64 = lambda b: base64.b64encode(b).decode()
+    docs = json_corpus.documents(LIVE_DOCS[0], seed=LIVE_DOCS[1])
+    fx["documents"] = {"count": LIVE_DOCS[0], "seed": LIVE_DOCS[1], "block": LIVE_DOCS[2]}
+    for indent, key in ((4, "dump4"), (-1, "dump")):
+        outs = ref_lines(docs, indent)
+        fx["documents"][key] = json_corpus.block_digests(outs, LIVE_DOCS[2])
+        fx["documents"][key + "_tags"] = b64(json_corpus.item_tags(outs))
+    vals = json_corpus.numbers(LIVE_NUMBERS[0], seed=LIVE_NUMBERS[1])
+    outs = [s.encode() for s in ref_numbers(vals)]
+    fx["numbers"] = {"count": LIVE_NUMBERS[0], "seed": LIVE_NUMBERS[1], "block": LIVE_NUMBERS[2],
+                     "digests": json_corpus.block_digests(outs, LIVE_NUMBERS[2]), "digests_tags": b64(json_corpus.item_tags(outs))}
+    scenes = {}
+    for name in sorted(f[:-5] for f in os.listdir(scene_dir) if f.endswith(".json")):
+        path = os.path.join(scene_dir, name + ".json")
+        r = subprocess.run([REF, "dump", path], capture_output=True, check=True)
+        scenes[name] = hashlib.sha256(r.stdout).hexdigest()
+    fx["scenes_dump4_sha256"] = scenes
+    with open(os.path.join(HERE, "json_reference_live.json"), "w") as f:
+        json.dump(fx, f, indent=1)
+        f.write("\n")
+    print("live: documents", len(docs), "numbers", len(vals), "scenes", len(scenes))
 
 
 if __name__ == "__main__":

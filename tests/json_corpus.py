@@ -83,3 +83,30 @@ def numbers(n, seed=11):
         if v == v and abs(v) != float('inf'):
             out.append(float(v))
     return out
+
+
+def _framed(it):
+    return b"\0" if it is None else b"\1" + struct.pack('<Q', len(it)) + it
+
+
+def block_digests(items, block):
+    """SHA-256 of every `block` consecutive outputs (None = rejected, or bytes): how the larger differential runs are pinned in
+    tests/golden/json_reference_live.json without storing every output.  Each item is framed (tag + length) so that no two
+    different sequences share an encoding."""
+    import hashlib
+
+    out = []
+    for i in range(0, len(items), block):
+        h = hashlib.sha256()
+        for it in items[i:i + block]:
+            h.update(_framed(it))
+        out.append(h.hexdigest())
+    return out
+
+
+def item_tags(items):
+    """The first 2 bytes of each framed output's SHA-256, concatenated: not the check (block_digests is), but what lets a failing
+    block name the first input whose own output changed."""
+    import hashlib
+
+    return b"".join(hashlib.sha256(_framed(it)).digest()[:2] for it in items)

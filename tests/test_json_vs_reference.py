@@ -5,13 +5,15 @@ Scene.hpp:34 parse, :89-99 dump(4)).  That header is the one part of the referen
 this image as it lies, so oracle/ref_json_harness.cpp drives it directly:
   * tests/golden/json_reference.json holds 600 documents (a third byte-mutated: accept/reject
     agreement) and 4000 numbers with the reference library's outputs — checked everywhere;
-  * when oracle/_ref/ref_json is present (this container; built by `make -C oracle ref`), a larger
-    live differential run and the shipped scene files go through the reference library as well.
+  * tests/golden/json_reference_live.json pins a larger differential run (6000 documents, 60,000 numbers, regenerated
+    here from json_corpus' seeds) and the shipped scene files as the reference library dumps them: SHA-256 digests of
+    the reference's outputs per block (json_corpus.block_digests), written by tests/golden/make_json_golden.py from
+    oracle/_ref/ref_json (`make -C oracle ref`).
 The code under test is software-raytracer_amd/host/json_min.hpp (parser, Grisu2 writer, layout)."""
 import base64
+import hashlib
 import json
 import os
-import subprocess
 
 import pytest
 
@@ -19,8 +21,23 @@ import json_corpus
 from conftest import SCENE_NAMES, scene_path
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = os.path.join(HERE, "..", "oracle", "_ref", "ref_json")
-needs_ref = pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref/ref_json not built (needs /root/reference)")
+
+
+def _live():
+    return json.load(open(os.path.join(HERE, "golden", "json_reference_live.json")))
+
+
+def _same_blocks(mine, want, want_tags, block, inputs):
+    """mine: this library's outputs; want: the reference's block digests (the check); want_tags: base64 of its per-output tags,
+    which name the first input of a differing block whose own output changed."""
+    got = json_corpus.block_digests(mine, block)
+    assert len(got) == len(want)
+    tags = base64.b64decode(want_tags)
+    for i, (g, w) in enumerate(zip(got, want)):
+        if g != w:
+            first = next((j for j in range(i * block, min((i + 1) * block, len(mine))) if json_corpus.item_tags([mine[j]]) != tags[2 * j:2 * j + 2]), None)
+            where = "item %d: input %r, this library gives %r" % (first, inputs[first], mine[first]) if first is not None else "the item could not be named"
+            raise AssertionError("items %d..%d differ from the reference library's outputs; first changed %s" % (i * block, (i + 1) * block - 1, where))
 
 
 def _b(x):
@@ -51,34 +68,25 @@ def test_golden_numbers(srt):
         assert srt.host.format_double(float.fromhex(hx)) == want, hx
 
 
-@needs_ref
 def test_live_differential_documents(srt):
-    docs = json_corpus.documents(6000, seed=12345)
-    for indent in (4, -1):
-        r = subprocess.run([REF, "lines", str(indent)], input=b"\n".join(docs) + b"\n", capture_output=True, check=True)
-        ref = r.stdout.split(b"\n")[:-1]
-        assert len(ref) == len(docs)
-        for doc, want in zip(docs, ref):
-            want = None if want == b"EXCEPTION" else want.replace(b"\x1e", b"\n")
-            assert _mine(srt, doc, indent) == want, doc
+    fx = _live()["documents"]
+    docs = json_corpus.documents(fx["count"], seed=fx["seed"])
+    assert len(docs) == fx["count"] == 6000
+    for indent, key in ((4, "dump4"), (-1, "dump")):
+        _same_blocks([_mine(srt, doc, indent) for doc in docs], fx[key], fx[key + "_tags"], fx["block"], docs)
 
 
-@needs_ref
 def test_live_differential_numbers(srt):
-    vals = json_corpus.numbers(60000, seed=99)
-    r = subprocess.run([REF, "numbers"], input=("\n".join(v.hex() for v in vals) + "\n").encode(), capture_output=True, check=True)
-    ref = r.stdout.decode().split("\n")[:-1]
-    assert len(ref) == len(vals)
-    for v, want in zip(vals, ref):
-        assert srt.host.format_double(v) == want, v.hex()
+    fx = _live()["numbers"]
+    vals = json_corpus.numbers(fx["count"], seed=fx["seed"])
+    assert len(vals) == fx["count"] == 60000
+    _same_blocks([srt.host.format_double(v).encode() for v in vals], fx["digests"], fx["digests_tags"], fx["block"], [v.hex() for v in vals])
 
 
-@needs_ref
 @pytest.mark.parametrize("name", SCENE_NAMES)
 def test_shipped_scenes_through_the_reference_library(srt, name):
     """file --(reference parse + dump(4))--> same bytes --(our Scene load + Dump)--> same bytes."""
     path = scene_path(name)
     raw = open(path, "rb").read()
-    r = subprocess.run([REF, "dump", path], capture_output=True, check=True)
-    assert r.stdout == raw
+    assert hashlib.sha256(raw).hexdigest() == _live()["scenes_dump4_sha256"][name]
     assert srt.host.Scene(path).dump().encode() == raw

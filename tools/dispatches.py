@@ -1,6 +1,6 @@
 """Which kernel dispatches of a rocprofv3 run of bench.py belong to which of bench.py's launches.
 
-bench.py (N = 1) makes its srt_render calls in a fixed order:
+bench.py --full (N = 1) makes its srt_render calls in a fixed order (a plain run stops after the timed steps):
 
     1 priming launch (8 rows, 1 spp)  |  W warm-up steps  |  K TIMED steps  |  1 ray-count launch
     [| 1 one-sample probe when the launch is sample-chunked]  [| parity re-renders of the cpu_baseline leg]

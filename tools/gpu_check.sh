@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc $?" | tee -a $OUT/pytest.log; tail -3 $OUT/pytest.log
-run() { name=$1; shift; timeout -k 10 300 python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc $? $(python -c "import json,sys; d=json.load(open('$OUT/$name.json')); r=d['roofline']; print('%.4g samples/s  kernel %.3f ms cold %.3f  valu frac %.3f' % (d['value'] or 0, r['kernel_ms'], r['kernel_ms_cold_first_launch'] or 0, r['frac']))" 2>&1)"; }
+run() { name=$1; shift; timeout -k 10 300 python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc $? $(python -c "import json,sys; d=json.load(open('$OUT/$name.json')); r=d['roofline']; print('%.4g samples/s  kernel %.3f ms cold %.3f  valu frac %.3f' % (d['value'] or 0, r['kernel_ms'], r['kernel_ms_cold_first_launch'] or 0, r['frac']))" 2>&1)"; }
 run bench_c2 --steps 20 --warmup 5
 run bench_indirect --scene Scene_indirect --steps 10 --warmup 3
 run bench_c3_r0 --config 3 --rank 0/8 --steps 10 --warmup 3

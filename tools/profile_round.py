@@ -74,7 +74,7 @@ def main():
             continue
         steps = [] if "--steps" in args else ["--steps", "10", "--warmup", "3"]
         # 1. a first bench line: the workload key, rays per sample, samples per launch
-        r = run(bench + args + steps + ["--no-cpu-baseline"], cwd=ROOT)
+        r = run(bench + args + steps + ["--full", "--no-cpu-baseline"], cwd=ROOT)
         if r.returncode != 0:
             print(name, "bench failed:", r.stderr[-500:])
             continue
@@ -90,7 +90,7 @@ def main():
         d = os.path.join(scratch, "trace_" + name)
         shutil.rmtree(d, ignore_errors=True)
         r = None if bench_only else run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", "python3", os.path.join(ROOT, "bench.py")] + args + steps +
-                ["--no-cpu-baseline"], cwd="/tmp", env=env, timeout=900)
+                ["--full", "--no-cpu-baseline"], cwd="/tmp", env=env, timeout=900)
         st = glob.glob(d + "/**/*kernel_stats.csv", recursive=True)
         if st:
             open(os.path.join(out, "kernel_stats_%s.csv" % name), "w").write(open(st[0]).read())
@@ -129,7 +129,7 @@ def main():
         elif not bench_only:
             print(name, "pmc failed:", r.stdout[-300:], r.stderr[-300:])
         # 4. the bench line that is committed (reads the counters written above; with the CPU baseline where it is cheap)
-        r = run(bench + args + steps, cwd=ROOT)
+        r = run(bench + args + steps + ["--full"], cwd=ROOT)
         js = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if js:
             open(os.path.join(out, "bench_%s.json" % name), "w").write(js[-1] + "\n")
