@@ -1,7 +1,7 @@
 /*
  * srt_pathtrace.h — C-ABI of the MI355X path-trace library (libsrt_pathtrace.so).
  *
- * (ABI 6.)  This is the drop-in boundary for ONE hot path of JoshuaLim007/Software-Raytracer:
+ * (ABI 7.)  This is the drop-in boundary for ONE hot path of JoshuaLim007/Software-Raytracer:
  * the per-pixel trace / shade / accumulate loop.  The reference has no plugin or
  * FFI interface; the seam this ABI replaces is the tile worker
  *
@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define SRT_ABI_VERSION 6
+#define SRT_ABI_VERSION 7
 
 typedef enum srt_status {
     SRT_OK = 0,
@@ -240,6 +240,50 @@ int srt_get_work_counts(srt_context* ctx, srt_work_counts* out);
  * with y in SCENE rows (the reference flips the mouse y first, :532).  *object_index = list
  * index of the hit object or -1.  Synchronous. */
 int srt_pick(srt_context* ctx, int x, int y, int* object_index);
+
+/* ---- first-hit buffers (G-buffer / AOVs; ABI 7) ----------------------------------------
+ * For every pixel (x, y) of a band: the camera ray GetRayDirection(camera, x, y) from camera.position against the current
+ * scene — the same ray, ray generation and closest-hit tie rule as srt_pick and as the primary ray of srt_render — i.e.
+ * GetClosestObject's RayHitObject (Raytracer.cpp:123-140, Common.hpp:320-325) and the hit object's material.BaseColor
+ * (Raytracer.cpp:163-165).  The reference has no sub-pixel jitter (:106-122): this first hit is the same for every sample.
+ * One ray per pixel, always (no progressive blocks).  Outputs, one bit each:
+ *
+ *   bit                      element  hit                                                  miss
+ *   SRT_GBUF_OBJECT          int32    list index of the hit object (what srt_pick returns)  -1
+ *   SRT_GBUF_NORMAL_DEPTH    float4   rayHit.normal xyz, w = rayHit.distance                (0, 0, 0, +inf)
+ *   SRT_GBUF_POSITION        float4   rayHit.point xyz, w = 1                               (0, 0, 0, 0)
+ *   SRT_GBUF_ALBEDO          float4   material.base_color rgb of the hit object, w = 0      (0, 0, 0, 0)
+ *                                     (as the reference's Color holds it: negative components clamped to 0, Common.hpp:253-262)
+ *
+ * Layout: W*H elements indexed x + y*W with the SCENE row y, exactly like the float4 accumulator.  A band is given in MEMORY
+ * rows like srt_render_params.row_begin / row_end and writes scene rows [H - row_end, H - row_begin), nothing else.  On hits,
+ * normal, distance and point are the bits GetClosestObject computes, the sign of zero included; meshes (the extension) use
+ * the triangle definition of srt_mesh.  A NaN camera direction gives a miss everywhere, as in srt_pick. */
+#define SRT_GBUF_OBJECT 1u
+#define SRT_GBUF_NORMAL_DEPTH 2u
+#define SRT_GBUF_POSITION 4u
+#define SRT_GBUF_ALBEDO 8u
+#define SRT_GBUF_ALL 15u
+
+typedef struct srt_gbuffer_params {
+    int32_t row_begin;  /* first memory row (inclusive) */
+    int32_t row_end;    /* one past the last memory row */
+    uint32_t outputs;   /* SRT_GBUF_* bits, at least one */
+    uint32_t flags;     /* reserved, must be 0 */
+} srt_gbuffer_params;
+
+/* Asynchronous on the launch stream (the handle's own or the one given to srt_set_stream), behind earlier renders; scene and
+ * camera are captured at enqueue.  srt_wait / srt_poll cover it.  SRT_ERR_STATE before srt_set_scene and srt_set_camera;
+ * SRT_ERR_INVALID_ARG for an empty or out-of-range band, outputs == 0, unknown output bits or non-zero flags.  Touches neither
+ * framebuffer nor accumulator, and leaves what srt_get_stats / srt_get_work_counts report (the last srt_render) and the
+ * launch shape of later renders as they are.  Handle-owned G-buffer memory is allocated on first use, per output. */
+int srt_render_gbuffer(srt_context* ctx, const srt_gbuffer_params* params);
+/* Write ONE output (a single SRT_GBUF_* bit) into a caller DEVICE buffer of W*H elements (e.g. a torch tensor's data_ptr)
+ * instead of the handle's own; NULL = own.  Same rules as srt_bind_output: does not wait, enqueued work keeps its buffer. */
+int srt_bind_gbuffer(srt_context* ctx, uint32_t output, void* d_ptr);
+/* Wait, then copy the whole W*H buffer of ONE output (bound or own) to host memory, as srt_read_accumulator does.
+ * SRT_ERR_STATE when that output has neither been bound nor written yet. */
+int srt_read_gbuffer(srt_context* ctx, uint32_t output, void* dst);
 
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first

@@ -23,6 +23,7 @@ from . import capi  # noqa: F401
 from .capi import (  # noqa: F401
     Camera,
     Environment,
+    GBufferParams,
     Material,
     Mesh,
     Object,
@@ -40,6 +41,6 @@ from . import host  # noqa: F401
 
 __all__ = [
     "capi", "host", "PathTracer", "SrtError", "Object", "Material", "Camera", "Environment",
-    "RenderParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
+    "RenderParams", "GBufferParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
     "load_library",
 ]

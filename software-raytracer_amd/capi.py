@@ -16,7 +16,11 @@ _LIB = os.path.join(_PKG, "libsrt_pathtrace.so")
 OK, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_STATE, ERR_OOM = range(6)
 OBJ_NONE, OBJ_SPHERE, OBJ_BOX, OBJ_MESH = 0, 1, 2, 3
 RENDER_RESET, RENDER_COUNT_RAYS, RENDER_PREVIEW, RENDER_COUNT_WORK, RENDER_NO_TIMING = 1, 2, 4, 8, 16
-ABI_VERSION = 6
+GBUF_OBJECT, GBUF_NORMAL_DEPTH, GBUF_POSITION, GBUF_ALBEDO, GBUF_ALL = 1, 2, 4, 8, 15
+# first-hit buffer names (PathTracer.gbuffer / bind_gbuffer) -> (output bit, numpy dtype, per-pixel channels)
+GBUFFERS = {"object": (GBUF_OBJECT, np.int32, 1), "normal_depth": (GBUF_NORMAL_DEPTH, np.float32, 4),
+            "position": (GBUF_POSITION, np.float32, 4), "albedo": (GBUF_ALBEDO, np.float32, 4)}
+ABI_VERSION = 7
 
 # every symbol include/srt_pathtrace.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -25,7 +29,7 @@ EXPORTS = [
     "srt_set_stream", "srt_bind_output", "srt_device_framebuffer", "srt_device_accumulator",
     "srt_render", "srt_wait", "srt_poll", "srt_get_stats", "srt_get_work_counts", "srt_pick", "srt_read_framebuffer",
     "srt_read_framebuffer_async", "srt_read_accumulator", "srt_write_accumulator", "srt_gather_band", "srt_gather_path", "srt_estimate_row_costs",
-    "srt_selftest_arith",
+    "srt_selftest_arith", "srt_render_gbuffer", "srt_bind_gbuffer", "srt_read_gbuffer",
 ]
 
 
@@ -98,6 +102,10 @@ class RenderParams(C.Structure):
         ("stripe_width", C.c_int32),
         ("selected_object", C.c_int32),
     ]
+
+
+class GBufferParams(C.Structure):
+    _fields_ = [("row_begin", C.c_int32), ("row_end", C.c_int32), ("outputs", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -195,11 +203,34 @@ def open_library(path):
     L.srt_gather_path.restype = C.c_char_p
     L.srt_estimate_row_costs.argtypes = [ctx, C.c_int, C.c_uint32, C.POINTER(C.c_float)]
     L.srt_selftest_arith.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.srt_render_gbuffer.argtypes = [ctx, C.POINTER(GBufferParams)]
+    L.srt_bind_gbuffer.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_read_gbuffer.argtypes = [ctx, C.c_uint32, C.c_void_p]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
             fn.restype = C.c_int
     return L
+
+
+def gbuffer_outputs(outputs):
+    """An SRT_GBUF_* mask from an int or from names of GBUFFERS ("object", "normal_depth", "position", "albedo")."""
+    if isinstance(outputs, str):
+        outputs = [outputs]
+    if isinstance(outputs, (int, np.integer)):
+        return int(outputs)
+    mask = 0
+    for name in outputs:
+        if name not in GBUFFERS:
+            raise ValueError("unknown G-buffer output %r (one of %s)" % (name, ", ".join(GBUFFERS)))
+        mask |= GBUFFERS[name][0]
+    return mask
+
+
+def _gbuffer_spec(name):
+    if name not in GBUFFERS:
+        raise ValueError("unknown G-buffer output %r (one of %s)" % (name, ", ".join(GBUFFERS)))
+    return GBUFFERS[name]
 
 
 def _f3(v):
@@ -231,6 +262,7 @@ class PathTracer:
     def __init__(self, width, height, device=0, lib=None):
         self.L = lib if lib is not None else load_library()
         self.width, self.height = int(width), int(height)
+        self.device = int(device)
         self._h = C.c_void_p()
         rc = self.L.srt_create(int(device), self.width, self.height, C.byref(self._h))
         if rc:
@@ -288,6 +320,49 @@ class PathTracer:
                  (RENDER_COUNT_WORK if count_work else 0) | (0 if timing else RENDER_NO_TIMING))
         p = RenderParams(rb, re, first_sample, spp, bounces, seed, flags, steps, stripe_width, selected)
         self._ck(self.L.srt_render(self._h, C.byref(p)))
+
+    def render_gbuffer(self, rows=None, outputs=GBUF_ALL, flags=0):
+        """srt_render_gbuffer: the first-hit buffers of memory rows `rows` (default: the whole frame).  `outputs`: an SRT_GBUF_*
+        mask or names of GBUFFERS.  Asynchronous, like render()."""
+        rb, re = rows if rows is not None else (0, self.height)
+        p = GBufferParams(int(rb), int(re), gbuffer_outputs(outputs), int(flags))
+        self._ck(self.L.srt_render_gbuffer(self._h, C.byref(p)))
+
+    def _gbuffer_shape(self, name):
+        _, dtype, ch = _gbuffer_spec(name)
+        return dtype, ((self.height, self.width) if ch == 1 else (self.height, self.width, ch))
+
+    def gbuffer(self, name):
+        """srt_read_gbuffer: the whole buffer of one output as a numpy array, rows = scene rows (the orientation of
+        accumulator()): "object" (H, W) int32, the others (H, W, 4) float32."""
+        dtype, shape = self._gbuffer_shape(name)
+        out = np.empty(shape, dtype=dtype)
+        self._ck(self.L.srt_read_gbuffer(self._h, GBUFFERS[name][0], out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def bind_gbuffer(self, name, tensor):
+        """srt_bind_gbuffer: write output `name` into a torch tensor on this tracer's device (None: the handle's own buffer).
+        Device, dtype, shape and contiguity are checked here, before any native call; the caller keeps the tensor alive
+        until the work that writes it has finished."""
+        bit = _gbuffer_spec(name)[0]
+        if tensor is None:
+            self._ck(self.L.srt_bind_gbuffer(self._h, bit, None))
+            return
+        import torch
+
+        dtype, shape = self._gbuffer_shape(name)
+        want = torch.int32 if dtype == np.int32 else torch.float32
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError("bind_gbuffer(%r): expected a torch.Tensor, got %s" % (name, type(tensor).__name__))
+        if tensor.device.type != "cuda" or tensor.device.index != self.device:
+            raise ValueError("bind_gbuffer(%r): tensor on %s, the tracer renders on cuda:%d" % (name, tensor.device, self.device))
+        if tensor.dtype != want:
+            raise TypeError("bind_gbuffer(%r): dtype %s, want %s" % (name, tensor.dtype, want))
+        if tuple(tensor.shape) != shape:
+            raise ValueError("bind_gbuffer(%r): shape %s, want %s" % (name, tuple(tensor.shape), shape))
+        if not tensor.is_contiguous():
+            raise ValueError("bind_gbuffer(%r): tensor is not contiguous" % name)
+        self._ck(self.L.srt_bind_gbuffer(self._h, bit, C.c_void_p(tensor.data_ptr())))
 
     def wait(self):
         self._ck(self.L.srt_wait(self._h))

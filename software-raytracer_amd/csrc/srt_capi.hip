@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "srt_kernel.hip.h"
+#include "srt_gbuffer.hip.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -170,6 +171,11 @@ struct srt_context {
     bool pick_in_lds[2] = {true, true};
     int variant = -1;  // >= 0 overrides SRT_KERNEL (set through srt_debug_set_variant)
 
+    // first-hit buffers (srt_render_gbuffer), one slot per SRT_GBUF_* bit: the handle's own (allocated on first use) and the
+    // caller's bound one (srt_bind_gbuffer; NULL = own)
+    void* d_gbuf_own[4] = {nullptr, nullptr, nullptr, nullptr};
+    void* d_gbuf_bound[4] = {nullptr, nullptr, nullptr, nullptr};
+
     char error[512] = "";
 };
 
@@ -310,6 +316,8 @@ int srt_destroy(srt_context* ctx) {
     if (ctx->ev_read) (void)hipEventDestroy(ctx->ev_read);
     if (ctx->d_tile_masks) (void)hipFree(ctx->d_tile_masks);
     if (ctx->d_tile_chain) (void)hipFree(ctx->d_tile_chain);
+    for (int i = 0; i < 4; ++i)
+        if (ctx->d_gbuf_own[i]) (void)hipFree(ctx->d_gbuf_own[i]);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -1025,6 +1033,92 @@ int srt_pick(srt_context* ctx, int x, int y, int* object_index) {
     SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *object_index = idx[0];
     memcpy(ctx->last_pick, idx, sizeof idx);
+    return SRT_OK;
+}
+
+// ---- first-hit buffers --------------------------------------------------------------------------------------------
+// slot of a single SRT_GBUF_* bit, -1 for anything else
+static int gbuf_slot(uint32_t output) {
+    switch (output) {
+        case SRT_GBUF_OBJECT: return 0;
+        case SRT_GBUF_NORMAL_DEPTH: return 1;
+        case SRT_GBUF_POSITION: return 2;
+        case SRT_GBUF_ALBEDO: return 3;
+        default: return -1;
+    }
+}
+static size_t gbuf_elem_bytes(int slot) { return slot == 0 ? sizeof(int32_t) : sizeof(float4); }
+
+int srt_render_gbuffer(srt_context* ctx, const srt_gbuffer_params* g) {
+    if (!ctx || !g) return SRT_ERR_INVALID_ARG;
+    if (!ctx->scene_set) return fail(ctx, SRT_ERR_STATE, "srt_render_gbuffer: srt_set_scene has not been called");
+    if (!ctx->camera.set) return fail(ctx, SRT_ERR_STATE, "srt_render_gbuffer: srt_set_camera has not been called");
+    const int H = ctx->height;
+    if (g->row_begin < 0 || g->row_end > H || g->row_begin >= g->row_end)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render_gbuffer: bad row band [%d,%d) for height %d", g->row_begin, g->row_end, H);
+    if (g->outputs == 0 || (g->outputs & ~SRT_GBUF_ALL))
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render_gbuffer: outputs 0x%x: want a non-empty set of SRT_GBUF_* bits", g->outputs);
+    if (g->flags != 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render_gbuffer: flags must be 0");
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)ctx->width * (size_t)H;
+    void* dst[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 4; ++i) {
+        if (!(g->outputs & (1u << i))) continue;
+        if (ctx->d_gbuf_bound[i]) {
+            dst[i] = ctx->d_gbuf_bound[i];
+            continue;
+        }
+        if (!ctx->d_gbuf_own[i]) SRT_HIP(ctx, hipMalloc(&ctx->d_gbuf_own[i], px * gbuf_elem_bytes(i)));
+        dst[i] = ctx->d_gbuf_own[i];
+    }
+    // the render's kernel parameters for this band: camera, scene image, the scene_in_lds judgement and the LDS bytes
+    srt_render_params p{};
+    p.row_begin = g->row_begin, p.row_end = g->row_end, p.first_sample = 1, p.sample_count = 1;
+    srt::KernelParams K;
+    size_t lds_bytes = 0;
+    int use = 0, img = 0;
+    if (const int frc = fill_kernel_params(ctx, &p, K, lds_bytes, use, img)) return frc;
+    K.flags &= srt::KF_BOXES_FINITE;
+    K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // the G-buffer touches none of them
+    const srt::GBufferOut out{(int32_t*)dst[0], (float4*)dst[1], (float4*)dst[2], (float4*)dst[3]};
+    const bool in_lds = ctx->scene_in_lds[img], mesh = K.n_tris > 0;
+    const void* kern = in_lds ? (mesh ? (const void*)srt::gbuffer_kernel<true, true> : (const void*)srt::gbuffer_kernel<true, false>)
+                              : (mesh ? (const void*)srt::gbuffer_kernel<false, true> : (const void*)srt::gbuffer_kernel<false, false>);
+    // persistent workgroups: each stages the scene once and its waves stride over 8 x 8 tiles; about CUs x resident workgroups
+    // (LDS and registers decide; at most four per CU), never more than there are tiles for
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, srt::WG_THREADS, lds_bytes) != hipSuccess || per_cu < 1)
+        per_cu = 1, (void)hipGetLastError();
+    per_cu = per_cu > 4 ? 4 : per_cu;
+    const long long tiles = (long long)((ctx->width + srt::TILE_W - 1) / srt::TILE_W) * ((K.rows + srt::TILE_H - 1) / srt::TILE_H);
+    const long long need = (tiles + srt::WG_TILES_X * srt::WG_TILES_Y - 1) / (srt::WG_TILES_X * srt::WG_TILES_Y);
+    const long long wgs = std::min<long long>(need, (long long)ctx->cu_count * per_cu);
+    const dim3 grid((unsigned)wgs), block(srt::WG_THREADS);
+    if (in_lds && mesh) hipLaunchKernelGGL((srt::gbuffer_kernel<true, true>), grid, block, lds_bytes, ctx->stream, K, out);
+    else if (in_lds) hipLaunchKernelGGL((srt::gbuffer_kernel<true, false>), grid, block, lds_bytes, ctx->stream, K, out);
+    else if (mesh) hipLaunchKernelGGL((srt::gbuffer_kernel<false, true>), grid, block, lds_bytes, ctx->stream, K, out);
+    else hipLaunchKernelGGL((srt::gbuffer_kernel<false, false>), grid, block, lds_bytes, ctx->stream, K, out);
+    SRT_HIP(ctx, hipGetLastError());
+    return SRT_OK;
+}
+
+int srt_bind_gbuffer(srt_context* ctx, uint32_t output, void* d_ptr) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    const int i = gbuf_slot(output);
+    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_gbuffer: output 0x%x is not a single SRT_GBUF_* bit", output);
+    ctx->d_gbuf_bound[i] = d_ptr;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_output)
+    return SRT_OK;
+}
+
+int srt_read_gbuffer(srt_context* ctx, uint32_t output, void* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const int i = gbuf_slot(output);
+    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_gbuffer: output 0x%x is not a single SRT_GBUF_* bit", output);
+    const void* src = ctx->d_gbuf_bound[i] ? ctx->d_gbuf_bound[i] : ctx->d_gbuf_own[i];
+    if (!src) return fail(ctx, SRT_ERR_STATE, "srt_read_gbuffer: output 0x%x has neither been bound nor rendered", output);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * gbuf_elem_bytes(i), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
 

@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .capi import Mesh, Object, Stats
+from .capi import GBUFFERS, Mesh, Object, Stats, gbuffer_outputs
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_PKG, "libsrt_host.so")
@@ -22,6 +22,7 @@ EXPORTS = [
     "srt_host_renderer_invalidate", "srt_host_renderer_mode", "srt_host_renderer_pick", "srt_host_renderer_render_frame", "srt_host_renderer_render_samples",
     "srt_host_renderer_accumulation_frames", "srt_host_renderer_wait", "srt_host_renderer_read_framebuffer",
     "srt_host_renderer_read_accumulator", "srt_host_renderer_stats", "srt_host_renderer_handle",
+    "srt_host_renderer_render_gbuffer", "srt_host_renderer_read_gbuffer",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -95,6 +96,8 @@ def load_library():
     L.srt_host_renderer_read_accumulator.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_stats.argtypes = [vp, C.POINTER(Stats)]
     L.srt_host_renderer_handle.argtypes = [vp]
+    L.srt_host_renderer_render_gbuffer.argtypes = [vp, C.c_uint32]
+    L.srt_host_renderer_read_gbuffer.argtypes = [vp, C.c_uint32, vp]
     L.srt_host_multi_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]
     L.srt_host_multi_create.restype = vp
     L.srt_host_multi_destroy.argtypes = [vp]
@@ -283,6 +286,17 @@ class Renderer:
     def accumulator(self):
         out = np.empty((self.height, self.width, 4), dtype=np.float32)
         self._ck(self.L.srt_host_renderer_read_accumulator(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def render_gbuffer(self, outputs=15):
+        """PathTraceRenderer::RenderGBuffer: first-hit buffers of the band with the current camera (SRT_GBUF_* mask or names)."""
+        self._ck(self.L.srt_host_renderer_render_gbuffer(self._h, gbuffer_outputs(outputs)))
+
+    def gbuffer(self, name):
+        """PathTraceRenderer::ReadGBuffer: one output, scene rows, as capi.PathTracer.gbuffer returns it."""
+        bit, dtype, ch = GBUFFERS[name]
+        out = np.empty((self.height, self.width) if ch == 1 else (self.height, self.width, ch), dtype=dtype)
+        self._ck(self.L.srt_host_renderer_read_gbuffer(self._h, bit, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def stats(self):

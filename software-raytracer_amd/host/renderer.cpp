@@ -138,6 +138,17 @@ void PathTraceRenderer::ReadFramebuffer(void* pixels, size_t pitch_bytes) {
     check(srt_read_framebuffer(ctx_, pixels, pitch_bytes, row_begin_, row_end_), "srt_read_framebuffer");
 }
 
+void PathTraceRenderer::RenderGBufferRows(uint32_t outputs, int row_begin, int row_end) {
+    push_camera();
+    srt_gbuffer_params g{};
+    g.row_begin = row_begin;
+    g.row_end = row_end;
+    g.outputs = outputs;
+    check(srt_render_gbuffer(ctx_, &g), "srt_render_gbuffer");
+}
+
+void PathTraceRenderer::ReadGBuffer(uint32_t output, void* dst) { check(srt_read_gbuffer(ctx_, output, dst), "srt_read_gbuffer"); }
+
 std::vector<float> PathTraceRenderer::ReadAccumulator() {
     std::vector<float> out((size_t)width_ * height_ * 4);
     check(srt_read_accumulator(ctx_, out.data()), "srt_read_accumulator");
@@ -284,6 +295,8 @@ void MultiGpuRenderer::RenderSamples(uint32_t count, bool count_rays) {
 void MultiGpuRenderer::Wait() {
     for (size_t i = parts_.size(); i-- > 0;) parts_[i]->Wait();  // part 0 last: its stream waits for every band
 }
+
+void MultiGpuRenderer::RenderGBuffer(uint32_t outputs) { parts_[0]->RenderGBufferRows(outputs, 0, height_); }
 
 void MultiGpuRenderer::ReadFramebuffer(void* pixels, size_t pitch_bytes) {
     Wait();

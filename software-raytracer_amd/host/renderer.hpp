@@ -108,6 +108,11 @@ class PathTraceRenderer {
     // blit: copy the band into an SDL-surface-like buffer (renderSurface->pixels, :64)
     void ReadFramebuffer(void* pixels, size_t pitch_bytes);
     std::vector<float> ReadAccumulator();
+    // First-hit buffers (srt_render_gbuffer) of the band with the current camera: `outputs` = SRT_GBUF_* bits.  Asynchronous;
+    // ReadGBuffer waits and copies the whole W x H buffer of ONE output (int32 or float4 per pixel, scene rows).
+    void RenderGBuffer(uint32_t outputs) { RenderGBufferRows(outputs, row_begin_, row_end_); }
+    void RenderGBufferRows(uint32_t outputs, int row_begin, int row_end);  // any memory-row band (MultiGpuRenderer: the whole frame)
+    void ReadGBuffer(uint32_t output, void* dst);
 
     void PushCamera() { push_camera(); }  // srt_set_camera with the members as they stand (used by MultiGpuRenderer)
 
@@ -175,6 +180,9 @@ class MultiGpuRenderer {
     void RenderSamples(uint32_t count, bool count_rays = false);
     void Wait();
     void ReadFramebuffer(void* pixels, size_t pitch_bytes);  // the whole frame, from part 0
+    // first-hit buffers of the WHOLE frame, made on part 0 (one ray per pixel: a fraction of a sample-frame, no gather)
+    void RenderGBuffer(uint32_t outputs);
+    void ReadGBuffer(uint32_t output, void* dst) { parts_[0]->ReadGBuffer(output, dst); }
     // per part: kernel time of its last launch and its ray count (imbalance of static bands, SURVEY §8e caveat)
     std::vector<srt_stats> Stats();
 

@@ -12,17 +12,69 @@
 
 using namespace srt_host;
 
+// One array as a NumPy .npy file (format 1.0: magic, version, little-endian header length, a Python-literal header padded
+// with spaces to a multiple of 64 bytes and ended by a newline, then the raw C-order data).  `rows` rows of `row_bytes`.
+static bool write_npy(const std::string& path, const char* descr, int h, int w, int channels, const std::vector<const char*>& rows, size_t row_bytes) {
+    char shape[64];
+    if (channels == 1) std::snprintf(shape, sizeof shape, "(%d, %d)", h, w);
+    else std::snprintf(shape, sizeof shape, "(%d, %d, %d)", h, w, channels);
+    std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape + ", }";
+    const size_t pre = 10;  // magic (6) + version (2) + header length (2)
+    while ((pre + header.size() + 1) % 64) header += ' ';
+    header += '\n';
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) {
+        std::perror(path.c_str());
+        return false;
+    }
+    const unsigned char magic[8] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0};
+    const unsigned char len[2] = {(unsigned char)(header.size() & 255), (unsigned char)(header.size() >> 8)};
+    bool ok = std::fwrite(magic, 1, 8, f) == 8 && std::fwrite(len, 1, 2, f) == 2 && std::fwrite(header.data(), 1, header.size(), f) == header.size();
+    for (const char* r : rows) ok = ok && std::fwrite(r, 1, row_bytes, f) == row_bytes;
+    ok = (std::fclose(f) == 0) && ok;
+    if (!ok) std::fprintf(stderr, "%s: write failed\n", path.c_str());
+    return ok;
+}
+
+// --gbuffer PREFIX: the four first-hit buffers, rows top-down (memory rows, as the PPM): memory row m = scene row H - 1 - m.
+// (Little-endian hosts: the .npy descriptors say '<'.)
+template <class R>
+static int write_gbuffers(R& r, const std::string& prefix, int W, int H) {
+    struct Out {
+        uint32_t bit;
+        const char* name;
+        const char* descr;
+        int channels;
+    };
+    const Out outs[4] = {{SRT_GBUF_OBJECT, "object", "<i4", 1}, {SRT_GBUF_NORMAL_DEPTH, "normal_depth", "<f4", 4},
+                         {SRT_GBUF_POSITION, "position", "<f4", 4}, {SRT_GBUF_ALBEDO, "albedo", "<f4", 4}};
+    r.RenderGBuffer(SRT_GBUF_ALL);
+    for (const Out& o : outs) {
+        const size_t row_bytes = (size_t)W * 4 * (size_t)o.channels;
+        std::vector<char> buf(row_bytes * (size_t)H);
+        r.ReadGBuffer(o.bit, buf.data());
+        std::vector<const char*> rows((size_t)H);
+        for (int m = 0; m < H; ++m) rows[(size_t)m] = buf.data() + (size_t)(H - 1 - m) * row_bytes;
+        if (!write_npy(prefix + "_" + o.name + ".npy", o.descr, H, W, o.channels, rows, row_bytes)) return 1;
+    }
+    return 0;
+}
+
 static void usage() {
     std::fprintf(stderr,
                  "usage: srt_render --scene FILE [--width 1280] [--height 720] [--spp 32] [--bounces 2]\n"
                  "                  [--fov 55] [--seed 0] [--device 0 | --devices 0,1,2,...] [--out frame.ppm] [--resave FILE]\n"
+                 "                  [--gbuffer PREFIX]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
-                 "             and means the same), --equal-bands: bands of equal height\n");
+                 "             and means the same), --equal-bands: bands of equal height\n"
+                 "  --gbuffer: also write the first-hit buffers as PREFIX_object.npy (int32 HxW), PREFIX_normal_depth.npy,\n"
+                 "             PREFIX_position.npy and PREFIX_albedo.npy (float32 HxWx4), rows top-down like the PPM\n"
+                 "             (with --devices: made for the whole frame on the first device)\n");
 }
 
 int main(int argc, char** argv) {
-    std::string scene_path, out = "frame.ppm", resave;
+    std::string scene_path, out = "frame.ppm", resave, gbuffer;
     int W = 1280, H = 720, spp = 32, bounces = 2, fov = 55, device = 0;  // Raytracer.cpp:26-27,31-32
     unsigned seed = 0;
     std::vector<int> devices;
@@ -54,6 +106,7 @@ int main(int argc, char** argv) {
         }
         else if (!std::strcmp(argv[i], "--out")) out = need("--out");
         else if (!std::strcmp(argv[i], "--resave")) resave = need("--resave");
+        else if (!std::strcmp(argv[i], "--gbuffer")) gbuffer = need("--gbuffer");
         else {
             usage();
             return 2;
@@ -104,7 +157,9 @@ int main(int argc, char** argv) {
             }
             std::fprintf(stderr, "%dx%d spp=%d bounces=%d over %zu parts: slowest kernel %.3f ms, render + gather + read-back wall %.3f ms\n", W, H, spp, bounces,
                          st.size(), slowest, wall * 1e3);
-            return write_ppm(fb);
+            if (write_ppm(fb)) return 1;
+            if (!gbuffer.empty() && write_gbuffers(m, gbuffer, W, H)) return 1;
+            return 0;
         } catch (const std::exception& e) {
             std::fprintf(stderr, "error: %s\n", e.what());
             return 1;
@@ -127,6 +182,7 @@ int main(int argc, char** argv) {
         std::vector<uint32_t> fb((size_t)W * H);
         r.ReadFramebuffer(fb.data(), (size_t)W * 4);
         if (write_ppm(fb)) return 1;
+        if (!gbuffer.empty() && write_gbuffers(r, gbuffer, W, H)) return 1;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());
         return 1;
