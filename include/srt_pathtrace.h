@@ -285,6 +285,51 @@ int srt_bind_gbuffer(srt_context* ctx, uint32_t output, void* d_ptr);
  * SRT_ERR_STATE when that output has neither been bound nor written yet. */
 int srt_read_gbuffer(srt_context* ctx, uint32_t output, void* dst);
 
+/* ---- denoiser (edge-avoiding à-trous wavelet filter guided by the first-hit buffers; ABI 7, backward compatible) -------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.
+ *
+ * Inputs, W*H in the accumulator's layout (x + y*W, scene rows): the colour c_p is the accumulator's rgb (bound or own) as it
+ * stands when the filter runs; the guides o_p (SRT_GBUF_OBJECT), n_p, d_p (SRT_GBUF_NORMAL_DEPTH), x_p (SRT_GBUF_POSITION) and
+ * a_p (SRT_GBUF_ALBEDO) are the G-buffer slots, bound or own.  srt_denoise does NOT render the G-buffer: call
+ * srt_render_gbuffer first (or bind guides of your own).
+ *   1. miss pixels (o_p == -1): output = input, all four channels bit for bit; never used as taps.
+ *   2. SRT_DENOISE_ALBEDO: per channel m_p = a_p >= 1e-3 ? a_p : 1; the filter runs on c_p / m_p and the result is multiplied
+ *      by m_p after the last level.  Without the flag m_p = 1.
+ *   3. levels i = 0 .. L-1, step s = 2^i, taps q = p + s*(dx, dy), dx, dy in -2..2, h = [1, 4, 6, 4, 1] / 16; taps outside the
+ *      frame are skipped (not clamped); out_p = sum w(p,q) c_q / sum w(p,q) with
+ *        w(p,q) = h(dx) h(dy) [o_q == o_p] * max(0, n_p.n_q)^sigma_normal            (sigma_normal = 0: term off)
+ *                 * exp(-|n_p.(x_q - x_p)| / (sigma_plane * d_p))                   (sigma_plane = 0: term off)
+ *                 * exp(-|c_p - c_q|^2 / (sigma_color * 2^-i)^2)                    (sigma_color = 0: term off; rgb of this
+ *                                                                                      level's working colour)
+ *      A tap of another object is skipped before any of its values is used (non-finite values there change nothing); the
+ *      centre tap always weighs 36/256.  So a pixel of object A depends on input pixels of object A only.
+ *   4. output alpha = input alpha of p.
+ *   5. fixed tap order (dy outer, dx inner), no atomics: repeated calls give the same bits. */
+#define SRT_DENOISE_ALBEDO 1u       /* demodulate by the ALBEDO guide before filtering, remodulate after */
+#define SRT_DENOISE_FRAMEBUFFER 2u  /* also write tone_map(result) into the framebuffer (all memory rows) */
+
+typedef struct srt_denoise_params {
+    int32_t iterations;   /* à-trous levels L, 1..8 (footprint +-2*(2^L - 1) px) */
+    float sigma_color;    /* sigma_c, >= 0 */
+    float sigma_normal;   /* sigma_n, >= 0 */
+    float sigma_plane;    /* sigma_x, >= 0 */
+    uint32_t flags;       /* SRT_DENOISE_* */
+} srt_denoise_params;
+
+/* The library's defaults (pure host, no device needed). */
+int srt_denoise_params_default(srt_denoise_params* out);
+/* The whole frame, asynchronous on the launch stream behind earlier renders and G-buffer passes; srt_wait / srt_poll cover it.
+ * SRT_ERR_INVALID_ARG for iterations outside 1..8, a negative or NaN sigma or unknown flags; SRT_ERR_STATE when a guide it needs
+ * (OBJECT, NORMAL_DEPTH, POSITION, plus ALBEDO with SRT_DENOISE_ALBEDO) has never been bound or rendered.  Writes neither the
+ * accumulator nor the G-buffer, the framebuffer only with SRT_DENOISE_FRAMEBUFFER (through the render's tone map and packing),
+ * and leaves srt_get_stats / srt_get_work_counts and the launch shape of later renders as they are.  The output buffer and
+ * one ping-pong buffer (16 B per pixel each) are allocated on first use. */
+int srt_denoise(srt_context* ctx, const srt_denoise_params* params);
+/* Write the result into a caller DEVICE buffer of W*H float4 instead of the handle's own; NULL = own.  Does not wait. */
+int srt_bind_denoised(srt_context* ctx, void* d_float4);
+/* Wait, then copy the W*H float4 result (scene rows) to host memory.  SRT_ERR_STATE before the first srt_denoise. */
+int srt_read_denoised(srt_context* ctx, float* dst_rgba);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

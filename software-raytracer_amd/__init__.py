@@ -22,6 +22,7 @@ except ImportError:  # plumbing only; the native libraries work without it
 from . import capi  # noqa: F401
 from .capi import (  # noqa: F401
     Camera,
+    DenoiseParams,
     Environment,
     GBufferParams,
     Material,
@@ -41,6 +42,6 @@ from . import host  # noqa: F401
 
 __all__ = [
     "capi", "host", "PathTracer", "SrtError", "Object", "Material", "Camera", "Environment",
-    "RenderParams", "GBufferParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
+    "RenderParams", "GBufferParams", "DenoiseParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
     "load_library",
 ]

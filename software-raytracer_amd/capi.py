@@ -20,6 +20,9 @@ GBUF_OBJECT, GBUF_NORMAL_DEPTH, GBUF_POSITION, GBUF_ALBEDO, GBUF_ALL = 1, 2, 4, 
 # first-hit buffer names (PathTracer.gbuffer / bind_gbuffer) -> (output bit, numpy dtype, per-pixel channels)
 GBUFFERS = {"object": (GBUF_OBJECT, np.int32, 1), "normal_depth": (GBUF_NORMAL_DEPTH, np.float32, 4),
             "position": (GBUF_POSITION, np.float32, 4), "albedo": (GBUF_ALBEDO, np.float32, 4)}
+DENOISE_ALBEDO, DENOISE_FRAMEBUFFER = 1, 2
+# guides srt_denoise reads: OBJECT, NORMAL_DEPTH and POSITION always, ALBEDO when demodulating
+DENOISE_GUIDES = GBUF_OBJECT | GBUF_NORMAL_DEPTH | GBUF_POSITION
 ABI_VERSION = 7
 
 # every symbol include/srt_pathtrace.h declares (tests check the library exports them all)
@@ -30,6 +33,7 @@ EXPORTS = [
     "srt_render", "srt_wait", "srt_poll", "srt_get_stats", "srt_get_work_counts", "srt_pick", "srt_read_framebuffer",
     "srt_read_framebuffer_async", "srt_read_accumulator", "srt_write_accumulator", "srt_gather_band", "srt_gather_path", "srt_estimate_row_costs",
     "srt_selftest_arith", "srt_render_gbuffer", "srt_bind_gbuffer", "srt_read_gbuffer",
+    "srt_denoise_params_default", "srt_denoise", "srt_bind_denoised", "srt_read_denoised",
 ]
 
 
@@ -106,6 +110,11 @@ class RenderParams(C.Structure):
 
 class GBufferParams(C.Structure):
     _fields_ = [("row_begin", C.c_int32), ("row_end", C.c_int32), ("outputs", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("flags", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -206,6 +215,10 @@ def open_library(path):
     L.srt_render_gbuffer.argtypes = [ctx, C.POINTER(GBufferParams)]
     L.srt_bind_gbuffer.argtypes = [ctx, C.c_uint32, C.c_void_p]
     L.srt_read_gbuffer.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_denoise_params_default.argtypes = [C.POINTER(DenoiseParams)]
+    L.srt_denoise.argtypes = [ctx, C.POINTER(DenoiseParams)]
+    L.srt_bind_denoised.argtypes = [ctx, C.c_void_p]
+    L.srt_read_denoised.argtypes = [ctx, C.POINTER(C.c_float)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -231,6 +244,33 @@ def _gbuffer_spec(name):
     if name not in GBUFFERS:
         raise ValueError("unknown G-buffer output %r (one of %s)" % (name, ", ".join(GBUFFERS)))
     return GBUFFERS[name]
+
+
+def denoise_defaults(lib=None):
+    """srt_denoise_params_default as a dict (pure host: no GPU needed)."""
+    p = DenoiseParams()
+    rc = (lib if lib is not None else load_library()).srt_denoise_params_default(C.byref(p))
+    if rc:
+        raise SrtError(rc, "srt_denoise_params_default")
+    return {n: getattr(p, n) for n, _ in DenoiseParams._fields_}
+
+
+def __getattr__(name):
+    # DENOISE_DEFAULTS: the library's defaults (denoise_defaults()), read when first asked for, so that importing this module
+    # does not need the built library
+    if name == "DENOISE_DEFAULTS":
+        return denoise_defaults()
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+def denoise_params(iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None, albedo=True, framebuffer=False, lib=None):
+    """A DenoiseParams: the library defaults, with every argument that is not None put in their place."""
+    d = denoise_defaults(lib)
+    flags = (DENOISE_ALBEDO if albedo else 0) | (DENOISE_FRAMEBUFFER if framebuffer else 0)
+    return DenoiseParams(int(d["iterations"] if iterations is None else iterations),
+                         float(d["sigma_color"] if sigma_color is None else sigma_color),
+                         float(d["sigma_normal"] if sigma_normal is None else sigma_normal),
+                         float(d["sigma_plane"] if sigma_plane is None else sigma_plane), flags)
 
 
 def _f3(v):
@@ -363,6 +403,43 @@ class PathTracer:
         if not tensor.is_contiguous():
             raise ValueError("bind_gbuffer(%r): tensor is not contiguous" % name)
         self._ck(self.L.srt_bind_gbuffer(self._h, bit, C.c_void_p(tensor.data_ptr())))
+
+    def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None, albedo=True, framebuffer=False,
+                gbuffer=True):
+        """srt_denoise over the whole frame: the accumulator as it stands, guided by the first-hit buffers.  Arguments left at
+        None take DENOISE_DEFAULTS.  gbuffer=True first enqueues render_gbuffer() for the guides the filter reads (with the
+        current scene and camera); gbuffer=False uses the guides as they are (rendered earlier or bound).  Asynchronous."""
+        p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, albedo, framebuffer, lib=self.L)
+        if gbuffer:
+            self.render_gbuffer(outputs=DENOISE_GUIDES | (GBUF_ALBEDO if albedo else 0))
+        self._ck(self.L.srt_denoise(self._h, C.byref(p)))
+
+    def denoised(self):
+        """srt_read_denoised: the result, (H, W, 4) float32, rows = scene rows (the orientation of accumulator())."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self.L.srt_read_denoised(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def bind_denoised(self, tensor):
+        """srt_bind_denoised: write the result into a torch tensor on this tracer's device, (H, W, 4) float32 and contiguous
+        (None: the handle's own buffer).  Checked here, before any native call, as bind_gbuffer checks."""
+        if tensor is None:
+            self._ck(self.L.srt_bind_denoised(self._h, None))
+            return
+        import torch
+
+        shape = (self.height, self.width, 4)
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError("bind_denoised: expected a torch.Tensor, got %s" % type(tensor).__name__)
+        if tensor.device.type != "cuda" or tensor.device.index != self.device:
+            raise ValueError("bind_denoised: tensor on %s, the tracer renders on cuda:%d" % (tensor.device, self.device))
+        if tensor.dtype != torch.float32:
+            raise TypeError("bind_denoised: dtype %s, want torch.float32" % tensor.dtype)
+        if tuple(tensor.shape) != shape:
+            raise ValueError("bind_denoised: shape %s, want %s" % (tuple(tensor.shape), shape))
+        if not tensor.is_contiguous():
+            raise ValueError("bind_denoised: tensor is not contiguous")
+        self._ck(self.L.srt_bind_denoised(self._h, C.c_void_p(tensor.data_ptr())))
 
     def wait(self):
         self._ck(self.L.srt_wait(self._h))

@@ -18,6 +18,7 @@
 
 #include "srt_kernel.hip.h"
 #include "srt_gbuffer.hip.h"
+#include "srt_denoise.hip.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -176,6 +177,14 @@ struct srt_context {
     void* d_gbuf_own[4] = {nullptr, nullptr, nullptr, nullptr};
     void* d_gbuf_bound[4] = {nullptr, nullptr, nullptr, nullptr};
 
+    // denoiser (srt_denoise): the handle's own result buffer and the ping-pong buffer of the preparation pass and the levels
+    // before the last (both allocated on first use), the caller's bound result buffer (srt_bind_denoised; NULL = own), and whether a denoise has been
+    // enqueued yet (srt_read_denoised before that is SRT_ERR_STATE)
+    float4* d_dn_own = nullptr;
+    float4* d_dn_tmp = nullptr;
+    float4* d_dn_bound = nullptr;
+    bool dn_written = false;
+
     char error[512] = "";
 };
 
@@ -318,6 +327,8 @@ int srt_destroy(srt_context* ctx) {
     if (ctx->d_tile_chain) (void)hipFree(ctx->d_tile_chain);
     for (int i = 0; i < 4; ++i)
         if (ctx->d_gbuf_own[i]) (void)hipFree(ctx->d_gbuf_own[i]);
+    if (ctx->d_dn_own) (void)hipFree(ctx->d_dn_own);
+    if (ctx->d_dn_tmp) (void)hipFree(ctx->d_dn_tmp);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -1119,6 +1130,89 @@ int srt_read_gbuffer(srt_context* ctx, uint32_t output, void* dst) {
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * gbuf_elem_bytes(i), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+// ---- denoiser ------------------------------------------------------------------------------------------------------
+int srt_denoise_params_default(srt_denoise_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    // chosen by tools/denoise_time.py --sweep on Scene1 and Scene_indirect
+    out->iterations = 4;
+    out->sigma_color = 0.0f;
+    out->sigma_normal = 32.0f;
+    out->sigma_plane = 0.02f;
+    out->flags = SRT_DENOISE_ALBEDO;
+    return SRT_OK;
+}
+
+int srt_denoise(srt_context* ctx, const srt_denoise_params* d) {
+    if (!ctx || !d) return SRT_ERR_INVALID_ARG;
+    if (d->iterations < 1 || d->iterations > 8)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_denoise: iterations %d outside 1..8", d->iterations);
+    // (written so that a NaN fails too)
+    if (!(d->sigma_color >= 0.0f) || !(d->sigma_normal >= 0.0f) || !(d->sigma_plane >= 0.0f))
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_denoise: sigmas must be >= 0 (color %g, normal %g, plane %g)", d->sigma_color,
+                    d->sigma_normal, d->sigma_plane);
+    if (d->flags & ~(SRT_DENOISE_ALBEDO | SRT_DENOISE_FRAMEBUFFER))
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_denoise: unknown flags 0x%x", d->flags);
+    const bool demod = (d->flags & SRT_DENOISE_ALBEDO) != 0;
+    const void* guide[4];
+    for (int i = 0; i < 4; ++i) guide[i] = ctx->d_gbuf_bound[i] ? ctx->d_gbuf_bound[i] : ctx->d_gbuf_own[i];
+    static const char* const names[4] = {"OBJECT", "NORMAL_DEPTH", "POSITION", "ALBEDO"};
+    for (int i = 0; i < (demod ? 4 : 3); ++i)
+        if (!guide[i])
+            return fail(ctx, SRT_ERR_STATE, "srt_denoise: the %s guide has neither been bound nor rendered (srt_render_gbuffer)", names[i]);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)ctx->width * (size_t)ctx->height;
+    if (!ctx->d_dn_bound && !ctx->d_dn_own) SRT_HIP(ctx, hipMalloc((void**)&ctx->d_dn_own, px * sizeof(float4)));
+    if (!ctx->d_dn_tmp) SRT_HIP(ctx, hipMalloc((void**)&ctx->d_dn_tmp, px * sizeof(float4)));
+    float4* const out = ctx->d_dn_bound ? ctx->d_dn_bound : ctx->d_dn_own;
+    srt::DenoiseLevel L{};
+    L.acc = ctx->d_acc;
+    L.object = (const int32_t*)guide[0];
+    L.normal_depth = (const float4*)guide[1];
+    L.position = (const float4*)guide[2];
+    L.albedo = demod ? (const float4*)guide[3] : nullptr;
+    L.width = ctx->width, L.height = ctx->height;
+    L.sigma_normal = d->sigma_normal;
+    L.sigma_plane = d->sigma_plane;
+    const dim3 grid((unsigned)((ctx->width + srt::WG_W - 1) / srt::WG_W), (unsigned)((ctx->height + srt::WG_H - 1) / srt::WG_H)),
+        block(srt::WG_THREADS);
+    // the preparation pass and the levels alternate between the ping-pong buffer and the result buffer so that the last
+    // level lands in the result
+    const int n = d->iterations;
+    L.dst = (n & 1) ? ctx->d_dn_tmp : out;
+    hipLaunchKernelGGL(srt::denoise_prep_kernel, grid, block, 0, ctx->stream, L);
+    SRT_HIP(ctx, hipGetLastError());
+    for (int i = 0; i < n; ++i) {
+        const bool last = i == n - 1;
+        L.src = L.dst;
+        L.dst = ((n - 1 - i) & 1) ? ctx->d_dn_tmp : out;
+        L.step = 1 << i;
+        const float sc = d->sigma_color * ldexpf(1.0f, -i);
+        L.color_scale = sc > 0.0f ? 1.0f / (sc * sc) : 0.0f;
+        L.framebuffer = last && (d->flags & SRT_DENOISE_FRAMEBUFFER) ? ctx->d_fb : nullptr;
+        if (last) hipLaunchKernelGGL((srt::denoise_kernel<true>), grid, block, 0, ctx->stream, L);
+        else hipLaunchKernelGGL((srt::denoise_kernel<false>), grid, block, 0, ctx->stream, L);
+        SRT_HIP(ctx, hipGetLastError());
+    }
+    ctx->dn_written = true;
+    return SRT_OK;
+}
+
+int srt_bind_denoised(srt_context* ctx, void* d_float4) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    ctx->d_dn_bound = (float4*)d_float4;  // (no synchronisation: enqueued levels keep the buffer they were given)
+    return SRT_OK;
+}
+
+int srt_read_denoised(srt_context* ctx, float* dst_rgba) {
+    if (!ctx || !dst_rgba) return SRT_ERR_INVALID_ARG;
+    const float4* src = ctx->d_dn_bound ? ctx->d_dn_bound : ctx->d_dn_own;
+    if (!ctx->dn_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_read_denoised: nothing has been denoised into this buffer yet");
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SRT_HIP(ctx, hipMemcpy(dst_rgba, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
 

@@ -7,7 +7,8 @@ import subprocess
 
 import numpy as np
 
-from .capi import GBUFFERS, Mesh, Object, Stats, gbuffer_outputs
+from .capi import (DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, DenoiseParams, Mesh, Object, Stats, denoise_params,
+                   gbuffer_outputs)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_PKG, "libsrt_host.so")
@@ -22,7 +23,7 @@ EXPORTS = [
     "srt_host_renderer_invalidate", "srt_host_renderer_mode", "srt_host_renderer_pick", "srt_host_renderer_render_frame", "srt_host_renderer_render_samples",
     "srt_host_renderer_accumulation_frames", "srt_host_renderer_wait", "srt_host_renderer_read_framebuffer",
     "srt_host_renderer_read_accumulator", "srt_host_renderer_stats", "srt_host_renderer_handle",
-    "srt_host_renderer_render_gbuffer", "srt_host_renderer_read_gbuffer",
+    "srt_host_renderer_render_gbuffer", "srt_host_renderer_read_gbuffer", "srt_host_renderer_denoise", "srt_host_renderer_read_denoised",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -98,6 +99,8 @@ def load_library():
     L.srt_host_renderer_handle.argtypes = [vp]
     L.srt_host_renderer_render_gbuffer.argtypes = [vp, C.c_uint32]
     L.srt_host_renderer_read_gbuffer.argtypes = [vp, C.c_uint32, vp]
+    L.srt_host_renderer_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
+    L.srt_host_renderer_read_denoised.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_multi_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]
     L.srt_host_multi_create.restype = vp
     L.srt_host_multi_destroy.argtypes = [vp]
@@ -297,6 +300,20 @@ class Renderer:
         bit, dtype, ch = GBUFFERS[name]
         out = np.empty((self.height, self.width) if ch == 1 else (self.height, self.width, ch), dtype=dtype)
         self._ck(self.L.srt_host_renderer_read_gbuffer(self._h, bit, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None, albedo=True, framebuffer=False,
+                gbuffer=True):
+        """PathTraceRenderer::Denoise, with the arguments of capi.PathTracer.denoise (gbuffer=True: render_gbuffer first)."""
+        p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, albedo, framebuffer)
+        if gbuffer:
+            self.render_gbuffer(DENOISE_GUIDES | (GBUF_ALBEDO if albedo else 0))
+        self._ck(self.L.srt_host_renderer_denoise(self._h, C.byref(p)))
+
+    def denoised(self):
+        """PathTraceRenderer::ReadDenoised: (H, W, 4) float32, scene rows, as capi.PathTracer.denoised returns it."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_denoised(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
     def stats(self):

@@ -205,6 +205,9 @@ int srt_host_renderer_read_accumulator(srt_host_renderer* h, float* dst) {
 // first-hit buffers of the renderer's band with its current camera (srt_render_gbuffer / srt_read_gbuffer)
 int srt_host_renderer_render_gbuffer(srt_host_renderer* h, uint32_t outputs) { SRT_HOST_TRY(h, h->r->RenderGBuffer(outputs)) }
 int srt_host_renderer_read_gbuffer(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->ReadGBuffer(output, dst)) }
+// denoiser over the whole frame with the guides as they stand (srt_denoise / srt_read_denoised)
+int srt_host_renderer_denoise(srt_host_renderer* h, const srt_denoise_params* p) { SRT_HOST_TRY(h, h->r->Denoise(*p)) }
+int srt_host_renderer_read_denoised(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadDenoised(dst)) }
 int srt_host_renderer_stats(srt_host_renderer* h, srt_stats* out) { SRT_HOST_TRY(h, *out = h->r->Stats()) }
 void* srt_host_renderer_handle(srt_host_renderer* h) { return h->r->handle(); }
 

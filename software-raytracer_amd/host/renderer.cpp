@@ -149,6 +149,10 @@ void PathTraceRenderer::RenderGBufferRows(uint32_t outputs, int row_begin, int r
 
 void PathTraceRenderer::ReadGBuffer(uint32_t output, void* dst) { check(srt_read_gbuffer(ctx_, output, dst), "srt_read_gbuffer"); }
 
+void PathTraceRenderer::Denoise(const srt_denoise_params& params) { check(srt_denoise(ctx_, &params), "srt_denoise"); }
+
+void PathTraceRenderer::ReadDenoised(float* dst_rgba) { check(srt_read_denoised(ctx_, dst_rgba), "srt_read_denoised"); }
+
 std::vector<float> PathTraceRenderer::ReadAccumulator() {
     std::vector<float> out((size_t)width_ * height_ * 4);
     check(srt_read_accumulator(ctx_, out.data()), "srt_read_accumulator");

@@ -113,6 +113,10 @@ class PathTraceRenderer {
     void RenderGBuffer(uint32_t outputs) { RenderGBufferRows(outputs, row_begin_, row_end_); }
     void RenderGBufferRows(uint32_t outputs, int row_begin, int row_end);  // any memory-row band (MultiGpuRenderer: the whole frame)
     void ReadGBuffer(uint32_t output, void* dst);
+    // Denoiser (srt_denoise) over the whole frame: the accumulator guided by the first-hit buffers as they stand (call
+    // RenderGBuffer first).  Asynchronous; ReadDenoised waits and copies the W x H float4 result (scene rows).
+    void Denoise(const srt_denoise_params& params);
+    void ReadDenoised(float* dst_rgba);
 
     void PushCamera() { push_camera(); }  // srt_set_camera with the members as they stand (used by MultiGpuRenderer)
 

@@ -64,17 +64,19 @@ static void usage() {
     std::fprintf(stderr,
                  "usage: srt_render --scene FILE [--width 1280] [--height 720] [--spp 32] [--bounces 2]\n"
                  "                  [--fov 55] [--seed 0] [--device 0 | --devices 0,1,2,...] [--out frame.ppm] [--resave FILE]\n"
-                 "                  [--gbuffer PREFIX]\n"
+                 "                  [--gbuffer PREFIX] [--denoise PATH]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
                  "             and means the same), --equal-bands: bands of equal height\n"
                  "  --gbuffer: also write the first-hit buffers as PREFIX_object.npy (int32 HxW), PREFIX_normal_depth.npy,\n"
                  "             PREFIX_position.npy and PREFIX_albedo.npy (float32 HxWx4), rows top-down like the PPM\n"
-                 "             (with --devices: made for the whole frame on the first device)\n");
+                 "             (with --devices: made for the whole frame on the first device)\n"
+                 "  --denoise: also render the first-hit buffers, denoise the accumulator with the library's defaults\n"
+                 "             (srt_denoise) and write the tone-mapped result to PATH as a PPM (single device only)\n");
 }
 
 int main(int argc, char** argv) {
-    std::string scene_path, out = "frame.ppm", resave, gbuffer;
+    std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise;
     int W = 1280, H = 720, spp = 32, bounces = 2, fov = 55, device = 0;  // Raytracer.cpp:26-27,31-32
     unsigned seed = 0;
     std::vector<int> devices;
@@ -107,6 +109,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--out")) out = need("--out");
         else if (!std::strcmp(argv[i], "--resave")) resave = need("--resave");
         else if (!std::strcmp(argv[i], "--gbuffer")) gbuffer = need("--gbuffer");
+        else if (!std::strcmp(argv[i], "--denoise")) denoise = need("--denoise");
         else {
             usage();
             return 2;
@@ -116,15 +119,19 @@ int main(int argc, char** argv) {
         usage();
         return 2;
     }
+    if (!denoise.empty() && !devices.empty()) {
+        std::fprintf(stderr, "--denoise works on one device only: the accumulator bands of --devices live on different GPUs\n");
+        return 2;
+    }
     Scene scene(scene_path);
     scene.Load();
     if (!scene.lastError().empty()) std::fprintf(stderr, "scene: %s\n", scene.lastError().c_str());  // Scene.hpp:76
     std::fprintf(stderr, "scene %s: %zu objects\n", scene_path.c_str(), scene.GetObjects().size());
     if (!resave.empty()) scene.SaveAs(resave);
-    auto write_ppm = [&](const std::vector<uint32_t>& fb) {
-        FILE* f = std::fopen(out.c_str(), "wb");
+    auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {
+        FILE* f = std::fopen(path.c_str(), "wb");
         if (!f) {
-            std::perror(out.c_str());
+            std::perror(path.c_str());
             return 1;
         }
         std::fprintf(f, "P6\n%d %d\n255\n", W, H);
@@ -157,7 +164,7 @@ int main(int argc, char** argv) {
             }
             std::fprintf(stderr, "%dx%d spp=%d bounces=%d over %zu parts: slowest kernel %.3f ms, render + gather + read-back wall %.3f ms\n", W, H, spp, bounces,
                          st.size(), slowest, wall * 1e3);
-            if (write_ppm(fb)) return 1;
+            if (write_ppm(fb, out)) return 1;
             if (!gbuffer.empty() && write_gbuffers(m, gbuffer, W, H)) return 1;
             return 0;
         } catch (const std::exception& e) {
@@ -181,8 +188,19 @@ int main(int argc, char** argv) {
                      (double)st.rays / (double)st.path_samples);
         std::vector<uint32_t> fb((size_t)W * H);
         r.ReadFramebuffer(fb.data(), (size_t)W * 4);
-        if (write_ppm(fb)) return 1;
+        if (write_ppm(fb, out)) return 1;
         if (!gbuffer.empty() && write_gbuffers(r, gbuffer, W, H)) return 1;
+        if (!denoise.empty()) {
+            // the guides of the whole frame, then the filter with the library's defaults; the kernel tone-maps its result into
+            // the framebuffer (--out is already written), read back top-down like --out
+            srt_denoise_params dp{};
+            srt_denoise_params_default(&dp);
+            dp.flags |= SRT_DENOISE_FRAMEBUFFER;
+            r.RenderGBuffer(SRT_GBUF_ALL);
+            r.Denoise(dp);
+            r.ReadFramebuffer(fb.data(), (size_t)W * 4);
+            if (write_ppm(fb, denoise)) return 1;
+        }
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());
         return 1;
