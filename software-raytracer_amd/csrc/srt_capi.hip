@@ -171,6 +171,19 @@ struct srt_context {
     bool scene_in_lds[2] = {true, true};  // per scene image: does it fit into LDS next to the scratch?
     bool pick_in_lds[2] = {true, true};
     int variant = -1;  // >= 0 overrides SRT_KERNEL (set through srt_debug_set_variant)
+#ifdef SRT_DEV
+    // srt_debug_set_chain / srt_debug_set_shape: per-handle development settings (the environment switches are read once per process)
+    int chain_mode = srt::DEV_CHAIN_NATURAL;
+    uint32_t chain_arg = 0;
+    int shape_defer = -2;     // < -1: SRT_DEFER
+    int shape_no_taper = -1;  // < 0: SRT_KFLAGS & 0x400
+    // the last sample-chunked launch, for srt_debug_read_chain
+    int chain_layers = 0, chain_chunk = 0, chain_chunk_full = 0, chain_wg_x = 0;
+    size_t chain_tiles = 0;
+    bool chain_used = false;  // it had a chain buffer (KernelParams.tile_chain)
+    int chain_used_mode = srt::DEV_CHAIN_NATURAL;
+    uint32_t chain_used_arg = 0;
+#endif
 
     // first-hit buffers (srt_render_gbuffer), one slot per SRT_GBUF_* bit: the handle's own (allocated on first use) and the
     // caller's bound one (srt_bind_gbuffer; NULL = own)
@@ -771,6 +784,10 @@ int srt_render(srt_context* ctx, const srt_render_params* p) {
     srt::ShapeOverrides ov;
     ov.tile_h = dev_switches().tile_h, ov.defer = dev_switches().defer, ov.chunk_beta = dev_switches().chunk_beta;
     ov.no_taper = (dev_switches().kernel_flags & 0x400) != 0, ov.fill_min = SRT_FILL_MIN;
+#ifdef SRT_DEV
+    if (ctx->shape_defer >= -1) ov.defer = ctx->shape_defer;
+    if (ctx->shape_no_taper >= 0) ov.no_taper = ctx->shape_no_taper != 0;
+#endif
     srt::LaunchShape shape = srt::plan_launch_shape(req, &ctx->work, ov);
 #ifdef SRT_DEV
     if (getenv("SRT_DEBUG_CHUNKS") && shape.source)
@@ -820,6 +837,16 @@ int srt_render(srt_context* ctx, const srt_render_params* p) {
     // KernelParams.tile_chain); the counts start at zero
     K.tile_chain = defer && dev_switches().chain ? ctx->d_tile_chain : nullptr;
     K.chunk_layers = chunks;
+#ifdef SRT_DEV
+    if (ctx->chain_mode == srt::DEV_CHAIN_OFF) K.tile_chain = nullptr;
+    K.chain_mode = ctx->chain_mode, K.chain_arg = ctx->chain_arg;
+    if (defer) {
+        ctx->chain_layers = chunks, ctx->chain_chunk = chunk, ctx->chain_chunk_full = shape.chunk_full, ctx->chain_wg_x = (int)wg_x;
+        ctx->chain_tiles = (size_t)wg8 * srt::WG_TILES_X * srt::WG_TILES_Y;
+        ctx->chain_used = K.tile_chain != nullptr;
+        ctx->chain_used_mode = ctx->chain_mode, ctx->chain_used_arg = ctx->chain_arg;
+    }
+#endif
     if (K.tile_chain) SRT_HIP(ctx, hipMemsetAsync(K.tile_chain, 0, (size_t)wg8 * srt::WG_TILES_X * srt::WG_TILES_Y * sizeof(uint32_t), ctx->stream));
     dim3 grid((unsigned)wg_x, (unsigned)((grid_h + tile_h * srt::WG_TILES_Y - 1) / (tile_h * srt::WG_TILES_Y)), (unsigned)chunks);
     dim3 block(srt::WG_THREADS);
@@ -983,6 +1010,47 @@ int srt_debug_last_pick(srt_context* ctx, int* out4) {
 int srt_debug_set_variant(srt_context* ctx, int variant) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
     ctx->variant = variant;
+    return SRT_OK;
+}
+
+// The chained chunks of sample-chunked launches (KernelParams.tile_chain), per handle: mode 0 as shipped, 1 no chain buffer (as
+// SRT_CHAIN=0), 2 chunk z may chain only if z < arg, 3 tile t's chain is cut at a layer in [0, layers] drawn from (arg, t)
+// (srt::dev_chain_cut).  A cut can only shorten a chain.
+int srt_debug_set_chain(srt_context* ctx, int mode, unsigned arg) {
+    if (!ctx || mode < srt::DEV_CHAIN_NATURAL || mode > srt::DEV_CHAIN_TILES) return SRT_ERR_INVALID_ARG;
+    ctx->chain_mode = mode, ctx->chain_arg = arg;
+    return SRT_OK;
+}
+
+// Per-handle SRT_DEFER and SRT_KFLAGS & 0x400: defer -1 the rule, 0 never chunk samples, n > 0 n samples per chunk; no_taper 0 / 1.
+// defer < -1 and no_taper < 0 go back to the environment.
+int srt_debug_set_shape(srt_context* ctx, int defer, int no_taper) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    ctx->shape_defer = defer, ctx->shape_no_taper = no_taper;
+    return SRT_OK;
+}
+
+// The last sample-chunked launch, once it has finished: every tile's count of chunks folded in order (where fold_kernel took the
+// tile up; 0 for every tile without a chain buffer) and the cut srt_debug_set_chain applied to it (0 without a chain buffer).
+// info[6]: layers, chunk, chunk_full, tiles, blocks of tiles across, chain buffer or not.  out_at / out_cut may be NULL; otherwise they
+// hold n >= tiles entries (tile t = 4 x block + wave, the block's waves 2 x 2 across and down).
+int srt_debug_read_chain(srt_context* ctx, uint32_t* out_at, uint32_t* out_cut, size_t n, int* info) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    const size_t tiles = ctx->chain_tiles;
+    if ((out_at || out_cut) && n < tiles) return SRT_ERR_INVALID_ARG;
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (info) {
+        info[0] = ctx->chain_layers, info[1] = ctx->chain_chunk, info[2] = ctx->chain_chunk_full;
+        info[3] = (int)tiles, info[4] = ctx->chain_wg_x, info[5] = ctx->chain_used ? 1 : 0;
+    }
+    if (out_at && tiles) {
+        if (ctx->chain_used) SRT_HIP(ctx, hipMemcpy(out_at, ctx->d_tile_chain, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        else memset(out_at, 0, tiles * sizeof(uint32_t));
+    }
+    if (out_cut)
+        for (size_t t = 0; t < tiles; ++t)
+            out_cut[t] = ctx->chain_used ? srt::dev_chain_cut(ctx->chain_used_mode, ctx->chain_used_arg, (uint32_t)ctx->chain_layers, (uint32_t)t) : 0u;
     return SRT_OK;
 }
 #endif  // SRT_DEV

@@ -54,6 +54,7 @@
 #include <type_traits>
 
 #include "srt_defs.h"
+#include "srt_launch_shape.h"
 
 namespace srt {
 
@@ -113,7 +114,30 @@ struct KernelParams {
     float4* accumulator;
     uint32_t* framebuffer;
     unsigned long long* ray_counter;
+#ifdef SRT_DEV
+    // srt_debug_set_chain (development library only): DEV_CHAIN_* and its argument, see dev_chain_cut
+    int32_t chain_mode;
+    uint32_t chain_arg;
+#endif
 };
+
+#ifdef SRT_DEV
+// srt_debug_set_chain: which chained chunks a development launch allows.  A cut only SHORTENS a tile's chain — chunk z of tile t may
+// chain only if z < dev_chain_cut(..., t) — so that tests reach the hand-offs that otherwise happen only by the luck of scheduling
+// (a chain that breaks at chunk_full, inside the half chunks, or never starts).  Nothing ever waits for another workgroup.
+enum : int32_t {
+    DEV_CHAIN_NATURAL = 0,  // as the shipped library
+    DEV_CHAIN_OFF = 1,      // no chain buffer at all (KernelParams.tile_chain = NULL, round 3's form)
+    DEV_CHAIN_CUT = 2,      // every tile's chain is cut at layer `arg`
+    DEV_CHAIN_TILES = 3,    // tile t's chain is cut at a layer in [0, layers] drawn from (arg, t)
+};
+__host__ __device__ inline uint32_t dev_chain_cut(int32_t mode, uint32_t arg, uint32_t layers, uint32_t tile) {
+    if (mode == DEV_CHAIN_CUT) return arg < layers ? arg : layers;
+    if (mode == DEV_CHAIN_TILES) return srt_mix32(srt_mix32(arg ^ 0x9E3779B9u) + tile) % (layers + 1u);
+    if (mode == DEV_CHAIN_OFF) return 0u;
+    return layers;
+}
+#endif
 
 // internal KernelParams.flags bit (srt_render sets it): progressive-block launch whose lanes stand for steps x steps
 // blocks instead of pixels — a lane traces its block's ray and writes all of the block's pixels
@@ -1447,9 +1471,9 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
     uint32_t s_base = 0u, count = P.sample_count;
     if constexpr (DEFER) {
         const uint32_t z = blockIdx.z, zf = (uint32_t)P.chunk_full, S = (uint32_t)P.chunk, half = S >> 1;
-        s_base = z < zf ? z * S : zf * S + (z - zf) * half;
+        s_base = SRT_CHUNK_FIRST(z, S, zf, half);  // = chunk_first(z, S, zf) (srt_launch_shape.h)
         const uint32_t want = z < zf ? S : half;
-        count = P.sample_count - s_base < want ? P.sample_count - s_base : want;
+        count = P.sample_count - s_base < want ? P.sample_count - s_base : want;  // = chunk_count(z, S, zf, P.sample_count)
     }
     const int B = P.max_bounces;
     unsigned rays = 0;
@@ -1575,6 +1599,9 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
             if (P.tile_chain) {
                 const uint32_t at = blockIdx.z == 0 ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)coherent_load(P.tile_chain + tile_id));
                 chained = at == blockIdx.z;
+#ifdef SRT_DEV
+                chained = chained && blockIdx.z < dev_chain_cut(P.chain_mode, P.chain_arg, gridDim.z, (uint32_t)tile_id);
+#endif
                 if (chained && owner && (blockIdx.z > 0 || !reset)) acc = coherent_load(P.accumulator + own_pixel);
             }
         }
@@ -1930,8 +1957,7 @@ __global__ void __launch_bounds__(256) fold_kernel(const KernelParams P, int til
     if (P.tile_chain) {
         const uint32_t at = P.tile_chain[tile_id];
         if (at >= (uint32_t)P.chunk_layers) return;  // all of them: the last one stored the pixel
-        const uint32_t zf = (uint32_t)P.chunk_full, S = (uint32_t)P.chunk, half = S >> 1;
-        first = at < zf ? at * S : zf * S + (at - zf) * half;  // (pathtrace_kernel's s_base)
+        first = chunk_first(at, (uint32_t)P.chunk, (uint32_t)P.chunk_full);  // (pathtrace_kernel's s_base)
     }
     float4 acc = ((P.flags & 1u) && first == 0u) ? make_float4(0, 0, 0, 0) : P.accumulator[pixel];
     // (Round 3 tried the layout [tile][group of 8 samples][slot][8 samples] — a 128-byte line = 8 consecutive samples of ONE slot,

@@ -196,6 +196,26 @@ inline LaunchShape plan_launch_shape(const ShapeRequest& q, const WorkRecord* re
     return s;
 }
 
+// Layer z of a sample-chunked launch traces samples [chunk_first(z), chunk_first(z) + chunk_count(z)) of its tiles: `chunk` each in
+// the layers z < chunk_full, half as many behind them, the last layer what is left.  One formula for pathtrace_kernel (which samples a
+// workgroup traces) and fold_kernel (where a tile's chain stopped); the kernels' unsigned arithmetic.  pathtrace_kernel spells it
+// through SRT_CHUNK_FIRST in its own body: the same bits from the inlined function, but a register allocation one or two VGPRs larger
+// in three of its instantiations.
+#define SRT_CHUNK_FIRST(z, chunk, chunk_full, half) ((z) < (chunk_full) ? (z) * (chunk) : (chunk_full) * (chunk) + ((z) - (chunk_full)) * (half))
+#ifdef __HIPCC__
+#define SRT_SHAPE_HD __host__ __device__
+#else
+#define SRT_SHAPE_HD
+#endif
+SRT_SHAPE_HD inline uint32_t chunk_first(uint32_t z, uint32_t chunk, uint32_t chunk_full) {
+    return SRT_CHUNK_FIRST(z, chunk, chunk_full, chunk >> 1);
+}
+SRT_SHAPE_HD inline uint32_t chunk_count(uint32_t z, uint32_t chunk, uint32_t chunk_full, uint32_t sample_count) {
+    const uint32_t first = chunk_first(z, chunk, chunk_full), want = z < chunk_full ? chunk : chunk >> 1;
+    return sample_count - first < want ? sample_count - first : want;
+}
+#undef SRT_SHAPE_HD
+
 // The sample buffer could not be had: everything in one workgroup per tile, with the small tiles chosen for the grid.
 inline void shape_without_sample_buffer(LaunchShape& s) {
     s.chunk = 0, s.chunks = 1, s.chunk_full = 1;

@@ -142,6 +142,65 @@ int main() {
         srt::finish_launch_shape(t, 512);
         CHECK(t.chunks == 1 && t.chunk == 0 && t.tile_h == small && small < 8);
     }
+    // ---- the layers of every sample-chunked shape tile the samples (srt::chunk_first / chunk_count, the kernels' formula) ----
+    {
+        long long shapes = 0;
+        auto tiles_exactly = [&](const srt::LaunchShape& s, uint32_t n) -> bool {
+            if (s.chunks < 2) return true;
+            ++shapes;
+            if (s.chunk < 1 || s.chunk_full < 1 || s.chunk_full > s.chunks) return false;
+            uint32_t next = 0u;
+            for (int z = 0; z < s.chunks; ++z) {
+                const uint32_t first = srt::chunk_first((uint32_t)z, (uint32_t)s.chunk, (uint32_t)s.chunk_full);
+                const uint32_t count = srt::chunk_count((uint32_t)z, (uint32_t)s.chunk, (uint32_t)s.chunk_full, n);
+                // (a layer that starts at or past the end would wrap `n - first` around and trace `want` samples that do not exist)
+                if (first != next || first >= n || count == 0u || count > n - first) return false;
+                next = first + count;
+            }
+            return next == n;
+        };
+        std::vector<uint32_t> counts;
+        for (uint32_t n = 32; n <= 4096; ++n) counts.push_back(n);
+        counts.push_back(100003u);
+        const long long grids[][2] = {{13, 7}, {320, 48}, {640, 64}, {1920, 32}, {1920, 135}, {3840, 270}, {1920, 1080}};
+        const int cus[] = {8, 80, 256};
+        for (uint32_t n : counts) {
+            for (const auto& g : grids)
+                for (int cu : cus)
+                    for (int mesh = 0; mesh < 2; ++mesh)
+                        for (int taper = 0; taper < 2; ++taper) {
+                            // (the heavy sweep over defer overrides on a few sample counts only: every count with the rule's own chunks)
+                            const bool all_defers = n <= 300 || n % 97 == 0 || n == 4096 || n == 100003u;
+                            for (int defer = -1; defer <= (all_defers ? 130 : -1); ++defer) {
+                                if (defer == 0) continue;
+                                srt::ShapeRequest q = request(g[0], (int)g[1], n, mesh != 0);
+                                q.cu_count = cu;
+                                srt::ShapeOverrides ov;
+                                ov.defer = defer, ov.no_taper = taper == 0;
+                                srt::LaunchShape s = srt::plan_launch_shape(q, nullptr, ov);
+                                srt::finish_launch_shape(s, n, ov);
+                                if (!tiles_exactly(s, n)) {
+                                    std::printf("FAILED layers: n %u grid %lldx%lld cu %d mesh %d taper %d defer %d -> chunk %d chunks %d full %d\n", n, g[0], g[1], cu,
+                                                mesh, taper, defer, s.chunk, s.chunks, s.chunk_full);
+                                    return 1;
+                                }
+                            }
+                        }
+        }
+        CHECK(shapes > 1000000);
+        // the kernels' edge cases by hand: chunk 24 (the smallest that tapers), 25 (odd: half 12), a short last half chunk
+        srt::ShapeOverrides ov;
+        ov.defer = 25;
+        srt::LaunchShape s = srt::plan_launch_shape(request(640, 64, 65, false), nullptr, ov);
+        srt::finish_launch_shape(s, 65, ov);
+        CHECK(s.chunk == 25 && s.chunk_full == 2 && s.chunks == 4);  // 25 + 25 + 12 + 3
+        CHECK(srt::chunk_first(3, 25, 2) == 62 && srt::chunk_count(3, 25, 2, 65) == 3);
+        ov.defer = 24;
+        s = srt::plan_launch_shape(request(640, 64, 97, false), nullptr, ov);
+        srt::finish_launch_shape(s, 97, ov);
+        CHECK(s.chunk == 24 && s.chunk_full == 3 && s.chunks == 6);  // 3 x 24 + 12 + 12 + 1
+        CHECK(srt::chunk_first(5, 24, 3) == 96 && srt::chunk_count(5, 24, 3, 97) == 1);
+    }
     std::printf("ok %d checks\n", checks);
     return 0;
 }

@@ -34,7 +34,9 @@ def test_scene_image_and_bvh_builders(tmp_path):
 
 def test_launch_shape_rule(tmp_path):
     """csrc/srt_launch_shape.h — tile height, sample chunks, taper, the fill simulation — is a pure function of its inputs (round 4):
-    the shapes BASELINE's configs take on the GPU, reproduced on the CPU under ASan + UBSan."""
+    the shapes BASELINE's configs take on the GPU, reproduced on the CPU under ASan + UBSan; and for every chunked shape of 32..4096
+    samples (and one larger count), forced chunk sizes 1..130, taper on and off, meshes or not, several grids and CU counts, the
+    layers [chunk_first(z), + chunk_count(z)) the kernels trace tile the samples exactly, none empty."""
     exe = _build(tmp_path, "shape_check.cpp", ["-I" + os.path.join(ROOT, "software-raytracer_amd", "csrc")])
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout[-600:] + r.stderr[-2000:]
