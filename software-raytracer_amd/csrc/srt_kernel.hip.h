@@ -1199,6 +1199,20 @@ __device__ __forceinline__ RGB environment(const Lds& S, V3 d) {
     }
     return RGB{t.r + Sun.r, t.g + Sun.g, t.b + Sun.b};  // :83 / :87 (NN: t comes out of Color::Lerp's clamp)
 }
+// The alpha of GetEnvironmentColor's colour: Color::Lerp's 0 * (1 - t) + 0 * t (:81-82, :87), which is +0 for a finite t and NaN
+// for t = NaN or infinity — exactly when `upd` is not finite, i.e. when a component of the direction is not.  (The r, g, b of such
+// a colour are NaN as well.)
+__device__ __forceinline__ float environment_alpha(V3 d) {
+    const float upd = (d.x * 0.0f + d.y * 1.0f) + d.z * 0.0f;  // (environment's :78)
+    return upd - upd;
+}
+// A sample colour's alpha is +0 or NaN (the reference's Color carries it: +0 from every colour of the scene, NaN from an environment
+// lerp on a non-finite direction, through incomingLight += env * hitColor, :179).  Where a sample colour travels as a float4 whose w
+// is a sample index — the path pool's ring, the sample buffer, the block grid's kept colour — the alpha is bit 31 of that word
+// (sample indices stay below 2^20).
+constexpr uint32_t TAG_ALPHA_NAN = 0x80000000u;
+__device__ __forceinline__ uint32_t alpha_tag(float a) { return a != a ? TAG_ALPHA_NAN : 0u; }
+__device__ __forceinline__ float tag_alpha(uint32_t tag) { return (tag & TAG_ALPHA_NAN) ? __builtin_nanf("") : 0.0f; }
 
 // (int)f with x86 cvttss2si semantics (reference platform), see oracle cvtt_x86
 __device__ __forceinline__ int cvtt_x86(float f) {
@@ -1212,11 +1226,11 @@ __device__ __forceinline__ uint32_t pack_channel(float v) {  // Common.hpp:190-2
 }
 
 // SetScreenPixel accumulate half (Raytracer.cpp:65-71) for sample index sidx (0-based in
-// this launch); the colour's alpha is always +0
-__device__ __forceinline__ void accumulate_sample(const KernelParams& P, float4& acc, RGB c, uint32_t sidx) {
+// this launch); the colour's alpha `a` is +0 or NaN (see alpha_tag)
+__device__ __forceinline__ void accumulate_sample(const KernelParams& P, float4& acc, RGB c, float a, uint32_t sidx) {
     const uint32_t frame = P.first_sample + sidx;
     if (sidx == 0 && (P.flags & 1u) != 0) {
-        acc = make_float4(c.r, c.g, c.b, 0.0f);
+        acc = make_float4(c.r, c.g, c.b, a);
     } else {
         // :66  float weight = 1.0 / ACCUMULATIONFRAMES (double divide, rounded once).  For
         // frame <= 2^24 the float divide gives the same bits (1/f cannot sit within 2^-53
@@ -1228,7 +1242,7 @@ __device__ __forceinline__ void accumulate_sample(const KernelParams& P, float4&
         acc.x = clamp0(acc.x * om) + c.r * weight;
         acc.y = clamp0(acc.y * om) + c.g * weight;
         acc.z = clamp0(acc.z * om) + c.b * weight;
-        acc.w = clamp0(acc.w * om) + 0.0f * weight;
+        acc.w = clamp0(acc.w * om) + a * weight;
     }
 }
 // SetScreenPixel tone-map + pack + the two stores (Raytracer.cpp:64,73-75)
@@ -1383,7 +1397,8 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
     // Block grid: the pixels of the wave's finished blocks are written by ALL lanes together — lane groups of steps^2 lanes
     // take a block each (steps = 8: a block per pass, eight rows of eight neighbouring pixels) — instead of every block's
     // lane looping over its own steps^2 pixels.  `val` is the block's running mean (the launch starts the frame: the same
-    // for all its pixels, tone-mapped once) or its ONE sample colour (`keep`: every pixel folds it into its own mean).
+    // for all its pixels, tone-mapped once) or its ONE sample colour (`keep`: every pixel folds it into its own mean; its w is a tag
+    // word whose bit 31 is the colour's alpha, alpha_tag).
     // A block's pixels: inside its stripe, the image and the band.
     auto write_blocks = [&](bool have, int bx0, int by0, float4 val, bool keep) {
         const unsigned long long m = __builtin_amdgcn_ballot_w64(have);
@@ -1424,7 +1439,7 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
                     const uint32_t pp = (uint32_t)(xx + yy * W);
                     if (keep) {
                         float4 a = P.accumulator[pp];
-                        accumulate_sample(P, a, RGB{v.x, v.y, v.z}, 0);
+                        accumulate_sample(P, a, RGB{v.x, v.y, v.z}, tag_alpha(__float_as_uint(v.w)), 0);
                         P.accumulator[pp] = a;
                         P.framebuffer[(size_t)(H - 1 - yy) * W + xx] = tone_map(a);
                     } else {
@@ -1478,7 +1493,7 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
     const int B = P.max_bounces;
     unsigned rays = 0;
 
-    auto accumulate = [&](float4& acc, RGB c, uint32_t sidx) { accumulate_sample(P, acc, c, sidx); };
+    auto accumulate = [&](float4& acc, RGB c, float a, uint32_t sidx) { accumulate_sample(P, acc, c, a, sidx); };
     auto write_pixel = [&](uint32_t pix, const float4 acc) { store_pixel(P, pix, acc); };
 
     // ---- pixels whose colour does not depend on the sample: finish them right here --------
@@ -1492,12 +1507,15 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
     tally.add(TALLY_WAVES, 1u);
     if (!PROBE && in_range && !pix_traced && (!DEFER || blockIdx.z == 0)) {  // (chunked: once, by the first chunk, for all samples)
         RGB c;
+        float ca = 0.0f;  // the colour's alpha (+0 from the emissive colour, :162)
         if (h0.prim < 0) {
             c = environment(S, dir0);
+            ca = environment_alpha(dir0);
         } else if (preview) {
             float4 m0 = S.mat(h0.prim, 0), m1 = S.mat(h0.prim, 1);
             float k2 = 2 * dot3(dir0, h0.n);  // rayDirection.Reflect(normal), Common.hpp:163-165
-            RGB refl = environment(S, v3(dir0.x - h0.n.x * k2, dir0.y - h0.n.y * k2, dir0.z - h0.n.z * k2));  // :148
+            const V3 rd = v3(dir0.x - h0.n.x * k2, dir0.y - h0.n.y * k2, dir0.z - h0.n.z * k2);
+            RGB refl = environment(S, rd);  // :148
             const float k = m0.y, sm = m0.x;  // :149-150
             float fresnal = 0;
             if (S.order(h0.prim) == P.selected) {  // :153
@@ -1519,19 +1537,23 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
                   clamp0(clamp0(clamp0(base.g * omk) + clamp0(clamp0(refl.g * k) * sm)) + emis.g),
                   clamp0(clamp0(clamp0(base.b * omk) + clamp0(clamp0(refl.b * k) * sm)) + emis.b)};
             c = color_lerp(a, RGB{3.0f, 3.0f, 0.0f}, fresnal);
+            // the same on the alphas (base, emissive and the lerp's target have alpha +0): +0, or NaN from the environment's alpha or
+            // from a non-finite k, s or fresnal
+            const float aa = clamp0(clamp0(clamp0(0.0f * omk) + clamp0(clamp0(environment_alpha(rd) * k) * sm)) + 0.0f);
+            ca = clamp0(aa * (1 - fresnal) + 0.0f * fresnal);
         } else {
             float4 m1 = S.mat(h0.prim, 1);
             c = RGB{clamp0(m1.y), clamp0(m1.z), clamp0(m1.w)};
         }
         if (bgrid) {  // (written below, by the whole wave)
-            untraced_val = make_float4(c.r, c.g, c.b, 0.0f);
+            untraced_val = make_float4(c.r, c.g, c.b, __uint_as_float(alpha_tag(ca)));
             if (reset) {
                 untraced_val = make_float4(0, 0, 0, 0);
-                for (uint32_t i = 0; i < P.sample_count; ++i) accumulate(untraced_val, c, i);
+                for (uint32_t i = 0; i < P.sample_count; ++i) accumulate(untraced_val, c, ca, i);
             }
         } else {
             float4 acc = reset ? make_float4(0, 0, 0, 0) : P.accumulator[pixel];
-            for (uint32_t i = 0; i < P.sample_count; ++i) accumulate(acc, c, i);
+            for (uint32_t i = 0; i < P.sample_count; ++i) accumulate(acc, c, ca, i);
             write_pixel(pixel, acc);
         }
         if (is_leader) rays += P.sample_count;  // one GetClosestObject call per block and frame
@@ -1569,7 +1591,7 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
         // sample -> ring row: a mask when depth is a power of two (full tiles: 4), else a real modulo (~20 instructions)
         const bool depth_pow2 = (depth & (depth - 1)) == 0;
         auto ring_row = [&](uint32_t s) { return depth_pow2 ? (s & (uint32_t)(depth - 1)) : (s % (uint32_t)depth); };
-        float4* ring = S.ring;                        // [depth][n_hit] of (r, g, b, tag)
+        float4* ring = S.ring;                        // [depth][n_hit] of (r, g, b, tag: sample | alpha_tag)
         for (int i = lane; i < 64 * ring_depth; i += 64) ring[i] = make_float4(0, 0, 0, __uint_as_float(0xFFFFFFFFu));
         __builtin_amdgcn_wave_barrier();
 
@@ -1640,7 +1662,7 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
                 float4 e = make_float4(0, 0, 0, 0);
                 if (own_done < count) {
                     e = ring[ring_row(own_done) * n_hit + lane];
-                    ready = __float_as_uint(e.w) == own_done;
+                    ready = (__float_as_uint(e.w) & ~TAG_ALPHA_NAN) == own_done;
                 }
                 if constexpr (MULTI) {
                     if (blocks) {  // the pixels of a block fold; the owner only advances the slot's fold point
@@ -1648,11 +1670,11 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
                         float4 f = make_float4(0, 0, 0, 0);
                         if (fdone < count) {
                             f = ring[ring_row(fdone) * n_hit + fslot];
-                            ready_px = __float_as_uint(f.w) == fdone;
+                            ready_px = (__float_as_uint(f.w) & ~TAG_ALPHA_NAN) == fdone;
                         }
                         if (__builtin_amdgcn_ballot_w64(ready | ready_px) == 0ull) break;
                         if (ready_px) {
-                            accumulate(acc, RGB{f.x, f.y, f.z}, fdone);
+                            accumulate(acc, RGB{f.x, f.y, f.z}, tag_alpha(__float_as_uint(f.w)), fdone);
                             ++fdone;
                         }
                         if (ready) ++own_done;
@@ -1675,13 +1697,13 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
                     break;
                 if (ready) {
                     if (DEFER && chained)  // this chunk is the tile's next one: straight into the running mean
-                        accumulate(acc, RGB{e.x, e.y, e.z}, s_base + own_done);
-                    else if constexpr (DEFER)  // row (tile, sample) of the sample buffer: 64 slots of 16 B, coalesced
+                        accumulate(acc, RGB{e.x, e.y, e.z}, tag_alpha(__float_as_uint(e.w)), s_base + own_done);
+                    else if constexpr (DEFER)  // row (tile, sample) of the sample buffer: 64 slots of 16 B, coalesced (w: the tag)
                         P.sample_rows[(tile_id * P.sample_count + s_base + own_done) * 64 + lane] = e;
-                    else if (MULTI && bgrid_keep)
+                    else if (MULTI && bgrid_keep)  // (the tag comes along: write_blocks reads the alpha from it)
                         acc = e;
                     else
-                        accumulate(acc, RGB{e.x, e.y, e.z}, own_done);
+                        accumulate(acc, RGB{e.x, e.y, e.z}, tag_alpha(__float_as_uint(e.w)), own_done);
                     ++own_done;
                 }
             }
@@ -1825,9 +1847,11 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
             if (busy && !(MESH && parked)) {
                 ++rays;
                 bool end_path;
+                uint32_t atag = 0u;  // the sample's alpha: NaN only from the environment (T's alpha is +0: NaN * +0 or +0 * +0)
                 if (h.prim < 0) {  // :178-181
                     RGB e = environment(S, sray);
                     L = RGB{L.r + e.r * T.r, L.g + e.g * T.g, L.b + e.b * T.b};  // (NN)
+                    atag = alpha_tag(environment_alpha(sray));
                     end_path = true;
                 } else {
                     float4 m0 = S.mat(h.prim, 0), m1 = S.mat(h.prim, 1), m2 = S.mat(h.prim, 2);
@@ -1848,7 +1872,7 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
                 }
                 if (end_path) {  // hand the sample colour to the slot's owner
                     const uint32_t sidx = task >> 6;
-                    ring[ring_row(sidx) * n_hit + (int)(task & 63u)] = make_float4(L.r, L.g, L.b, __uint_as_float(sidx));
+                    ring[ring_row(sidx) * n_hit + (int)(task & 63u)] = make_float4(L.r, L.g, L.b, __uint_as_float(sidx | atag));
                     busy = false;
                 }
             }
@@ -1972,11 +1996,11 @@ __global__ void __launch_bounds__(256) fold_kernel(const KernelParams P, int til
 #pragma unroll
         for (int k = 0; k < 8; ++k) c[k] = row[(size_t)(s + k) * 64];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) accumulate_sample(P, acc, RGB{c[k].x, c[k].y, c[k].z}, s + k);
+        for (int k = 0; k < 8; ++k) accumulate_sample(P, acc, RGB{c[k].x, c[k].y, c[k].z}, tag_alpha(__float_as_uint(c[k].w)), s + k);
     }
     for (; s < n; ++s) {
         const float4 c = row[(size_t)s * 64];
-        accumulate_sample(P, acc, RGB{c.x, c.y, c.z}, s);
+        accumulate_sample(P, acc, RGB{c.x, c.y, c.z}, tag_alpha(__float_as_uint(c.w)), s);
     }
     store_pixel(P, pixel, acc);
 }

@@ -34,9 +34,10 @@ def dev(srt):
 
 
 def _scene(oracle, kind):
-    """(objects, meshes, camera) as oracle arrays: Scene1, Scene_indirect, a mesh scene, a "far" fuzz scene."""
+    """(objects, meshes, camera) as oracle arrays: Scene1, Scene_indirect, a mesh scene, a "far" fuzz scene; "hbm" and "hbm mesh":
+    Scene1 and the mesh scene with a sphere of radius 0, which sends the scene image to HBM (outside the short square root's window)."""
     cam, meshes = oracle.default_camera(), []
-    if kind == "mesh":
+    if kind in ("mesh", "hbm mesh"):
         objs = oracle.load_scene_json_py(scene_path("Scene_indirect"))
         objs.insert(2, dict(type=oracle.OBJ_MESH, position=(0.4, -0.2, 3.0), mesh=0, base=(.9, .3, .2), specular_amount=0.5, smoothness=0.8))
         objs.append(dict(type=oracle.OBJ_MESH, position=(-0.8, 0.2, 3.6), mesh=0, base=(.2, .8, .3), emissive=(0.4, 0.4, 0.1)))
@@ -45,7 +46,9 @@ def _scene(oracle, kind):
         objs, meshes, off, scale = _random_scene(oracle, np.random.default_rng(4242), "far")
         cam.position = oracle.f3(off - np.array([0, 0, 6.0]) * scale)
     else:
-        objs = oracle.load_scene_json_py(scene_path(kind))
+        objs = oracle.load_scene_json_py(scene_path("Scene1" if kind == "hbm" else kind))
+    if kind.startswith("hbm"):
+        objs.insert(3, dict(type=oracle.OBJ_SPHERE, position=(0.0, 0.0, 2.0), radius=0.0, base=(.9, .2, .1), emissive=(0.5, 0.5, 0.5)))
     oarr, n = oracle.make_objects(objs)
     marr, mn, keep = oracle.make_meshes(meshes) if meshes else (None, 0, None)
     return dict(objs=(oarr, n), meshes=(marr, mn) if mn else None, cam=cam, keep=keep)
@@ -95,6 +98,8 @@ CASES = [
     ("mesh", 120, 72, (3, 58), 130, 33, True, True),
     ("mesh", 72, 48, None, 97, 24, False, False),               # untapered
     ("far", 100, 60, (0, 45), 130, 25, True, True),
+    ("hbm", 96, 64, (2, 61), 97, 25, True, True),               # scene images in HBM
+    ("hbm mesh", 120, 72, (3, 58), 130, 33, True, True),
 ]
 
 
@@ -114,6 +119,11 @@ def test_forced_cuts_equal_the_oracle(srt, oracle, dev, case):
         kw.update(first_sample=9, reset=False)
     ofb, oacc, orays = oracle.render(sc["objs"][0], sc["objs"][1], oracle.default_environment(), sc["cam"], w, h, accumulator=acc0,
                                      meshes=sc["meshes"], threads=ORACLE_THREADS, **kw)
+    if kind.startswith("hbm"):  # (a counting launch keeps work counts only with the image in LDS)
+        probe = _tracer(srt, sc, 16, 16, lib=dev)
+        probe.render(spp=1, bounces=1, seed=0, count_work=True)
+        assert probe.work_counts().valid == 0, "the scene image must be in HBM"
+        probe.close()
     pt = _tracer(srt, sc, w, h, lib=dev)
     assert dev.srt_debug_set_shape(pt._h, chunk, 0 if taper else 1) == 0
 

@@ -50,6 +50,70 @@ def _random_scene(oracle, rng, kind):
 
 import os
 
+SUN_GATE = np.uint32(0x3F7D70A4).view(np.float32)  # (double)sd > 0.99 exactly when sd >= this float (the kernel's environment())
+
+
+def _same_bits(a, b):
+    """Bit equality, NaNs compared as NaNs (their sign and payload are the processor's)."""
+    nan = np.isnan(a) | np.isnan(b)
+    return np.where(nan, np.isnan(a) & np.isnan(b), a.view(np.uint32) == b.view(np.uint32)).all(-1)
+
+
+def _sun_dot(d, s):
+    """GetEnvironmentColor's Dot(rayDirection, SunDirection * -1) in float32, in the reference's order (no FMA)"""
+    d, s = np.asarray(d, np.float32), np.asarray(s, np.float32)
+    m = s * np.float32(-1)
+    return (d[0] * m[0] + d[1] * m[1]) + d[2] * m[2]
+
+
+def _sun_at_the_gate(oracle, rng, cam, w, h):
+    """a sun direction against the primary ray of a pixel of the frame such that that ray's sd lies a few ULPs from 0.99, on
+    either side of the gate"""
+    d = (C.c_float * 3)()
+    oracle.lib().srt_oracle_ray_direction(C.byref(cam), w, h, int(rng.integers(0, w)), int(rng.integers(0, h)), d)
+    d = np.array(d[:], np.float32)
+    if not np.isfinite(d).all():
+        return np.float32([0.0, -1.0, 0.0])
+    perp = np.cross(d.astype(np.float64), rng.normal(size=3))
+    perp /= np.linalg.norm(perp)
+    s0 = -(0.99 * d.astype(np.float64) + float(rng.choice([np.sqrt(1 - 0.99 ** 2), 0.5, 3.0])) * perp)  # (|s| need not be 1)
+    want = int(SUN_GATE.view(np.uint32)) + int(rng.integers(-3, 4))
+    best = s0.astype(np.float32)
+    for t in np.linspace(1 - 2e-6, 1 + 2e-6, 801):  # (sd moves by ~1e-8 per step of t: every float near 0.99 is reached)
+        s = (s0 * t).astype(np.float32)
+        sd = _sun_dot(d, s)
+        if abs(int(sd.view(np.uint32)) - int(want)) < abs(int(_sun_dot(d, best).view(np.uint32)) - int(want)):
+            best = s
+    return best
+
+
+def _random_environment(oracle, seed, cam, w, h):
+    """The environment of a fuzz case, drawn from a generator of its own (the scene, camera and parameter draws stay those of the
+    seed): the default one for a quarter of the cases, otherwise a sun direction that is normalised, of length 0.3 or 40, zero,
+    with a NaN component or a few ULPs either side of the sun's gate for a ray of the frame, and colours with negative, -0, 0,
+    1e-38, 1e6, infinite and NaN components"""
+    env = oracle.default_environment()
+    if seed % 4 == 0:
+        return env, "default"
+    rng = np.random.default_rng(9000 + seed)
+    kind = ["unit", "0.3", "40", "zero", "nan", "gate"][seed % 6]
+    v = rng.normal(size=3)
+    v /= np.linalg.norm(v)
+    sun = {"unit": v, "0.3": 0.3 * v, "40": 40 * v, "zero": np.zeros(3), "nan": v, "gate": None}[kind]
+    if kind == "nan":
+        sun[int(rng.integers(0, 3))] = np.nan
+    if kind == "gate":
+        sun = _sun_at_the_gate(oracle, rng, cam, w, h)
+    env.sun_direction = oracle.f3(sun)
+    odd = [-1.5, -0.0, 0.0, 1e-38, 1e6, np.inf, np.nan]
+    for field in ("sky_color", "horizon_color", "ground_color", "sun_color"):
+        c = rng.uniform(0, 2, 3)
+        for i in range(3):
+            if rng.uniform() < 0.3:
+                c[i] = odd[int(rng.integers(0, len(odd)))]
+        setattr(env, field, oracle.f3(c))
+    return env, kind
+
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("SRT_FUZZ_N", "24"))))
 def test_random_scene_parity(srt, oracle, seed):
@@ -77,16 +141,19 @@ def test_random_scene_parity(srt, oracle, seed):
               first_sample=int(rng.integers(1, 50)), reset=bool(rng.integers(0, 2)))
     acc0 = rng.uniform(0, 2, (h, w, 4)).astype(np.float32)
     acc0[..., 3] = 0
+    env, env_kind = _random_environment(oracle, seed, cam, w, h)
     pt = srt.PathTracer(w, h)
+    pt.set_environment(srt.Environment.from_buffer_copy(bytes(env)))
     pt.set_meshes(C.cast(marr, C.POINTER(srt.Mesh)), mn)
     pt.set_scene(C.cast(oarr, C.POINTER(srt.Object)), n)
     pt.set_camera(srt.Camera.from_buffer_copy(bytes(cam)))
     pt.write_accumulator(acc0)
     pt.render(count_rays=True, **kw)
-    ofb, oacc, orays = oracle.render(oarr, n, oracle.default_environment(), cam, w, h, accumulator=acc0, meshes=(marr, mn) if mn else None, **kw)
+    ofb, oacc, orays = oracle.render(oarr, n, env, cam, w, h, accumulator=acc0, meshes=(marr, mn) if mn else None, **kw)
     gacc = pt.accumulator()
     assert pt.stats().rays == orays, (kind, n)
-    assert np.array_equal(gacc.view(np.uint32), oacc.view(np.uint32)), (kind, n, int((gacc.view(np.uint32) != oacc.view(np.uint32)).any(-1).sum()))
+    same = _same_bits(gacc, oacc)
+    assert same.all(), (kind, env_kind, n, int((~same).sum()))
     assert np.array_equal(pt.framebuffer(), ofb)
     pt.close()
 
@@ -116,15 +183,18 @@ def test_random_scene_progressive_blocks(srt, oracle, seed):
               preview=bool(rng.uniform() < 0.3), rows=(rb, re))
     acc0 = rng.uniform(0, 2, (h, w, 4)).astype(np.float32)
     acc0[..., 3] = 0
+    env, env_kind = _random_environment(oracle, seed, cam, w, h)
     pt = srt.PathTracer(w, h)
+    pt.set_environment(srt.Environment.from_buffer_copy(bytes(env)))
     pt.set_meshes(C.cast(marr, C.POINTER(srt.Mesh)), mn)
     pt.set_scene(C.cast(oarr, C.POINTER(srt.Object)), n)
     pt.set_camera(srt.Camera.from_buffer_copy(bytes(cam)))
     pt.write_accumulator(acc0)
     pt.render(**kw)
-    ofb, oacc, _ = oracle.render(oarr, n, oracle.default_environment(), cam, w, h, accumulator=acc0, meshes=(marr, mn) if mn else None, **kw)
+    ofb, oacc, _ = oracle.render(oarr, n, env, cam, w, h, accumulator=acc0, meshes=(marr, mn) if mn else None, **kw)
     gacc = pt.accumulator()
-    assert np.array_equal(gacc.view(np.uint32), oacc.view(np.uint32)), (kind, n, kw, int((gacc.view(np.uint32) != oacc.view(np.uint32)).any(-1).sum()))
+    same = _same_bits(gacc, oacc)
+    assert same.all(), (kind, env_kind, n, kw, int((~same).sum()))
     assert np.array_equal(pt.framebuffer(rows=(rb, re)), ofb[rb:re]), (kind, n, kw)
     pt.close()
 
