@@ -330,6 +330,58 @@ int srt_bind_denoised(srt_context* ctx, void* d_float4);
 /* Wait, then copy the W*H float4 result (scene rows) to host memory.  SRT_ERR_STATE before the first srt_denoise. */
 int srt_read_denoised(srt_context* ctx, float* dst_rgba);
 
+/* ---- temporal reprojection (keeps the accumulated estimate across camera moves; ABI 7, backward compatible) -----------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.
+ *
+ * Inputs, W*H in the accumulator's layout (x + y*W, scene rows): p is a current pixel, its guides o_p (SRT_GBUF_OBJECT),
+ * n_p, d_p (SRT_GBUF_NORMAL_DEPTH) and x_p (SRT_GBUF_POSITION) are the G-buffer slots, bound or own, and c_p is the
+ * accumulator's rgb (bound or own) as it stands when the call runs; it must hold n = samples samples of the current camera.
+ * Primed values are the history the previous call stored: its camera C' (fov included), result colour h', history length
+ * L', object o', normal n' and point x'.
+ *   1. miss pixels (o_p == -1): the accumulator is untouched, bit for bit; L_p = 0; never used as taps.
+ *   2. projection: B' = [right'*rd' | up'*ld' | forward'*clip] (columns; rd', ld', clip as srt_render folds them from C' and
+ *      W / H), inverted once per call on the host in double and passed as float.  (a, b, g) = B'^-1 (x_p - C'.position); if
+ *      g <= 0 p has no history, else u = (a/g + 1) * W/2, v = (b/g + 1) * H/2: the exact inverse of the primary ray (no
+ *      jitter, no half-pixel offset), so pixel (x, y) of an unchanged camera lands on (x, y).
+ *   3. taps: the 2x2 bilinear footprint of (u, v), x0 = floor(u), fx = u - x0 (the same for v).  A tap q counts when it lies
+ *      inside the frame, o'_q == o_p, |n_p.(x'_q - x_p)| <= plane_tolerance * d_p and (unless normal_threshold <= -1)
+ *      n_p.n'_q >= normal_threshold.  Taps that fail, or whose bilinear weight is 0, are skipped before their colour is
+ *      loaded.  w_q = bilinear_q * [q counts], W = sum w_q.
+ *   4. blend: if W == 0 or the history is invalid, c_p is kept bit for bit and L_p = n.  Otherwise H_p = sum w_q h'_q / W,
+ *      Lh_p = sum w_q L'_q / W, L_p = min(Lh_p + n, max_samples), a_p = n / L_p and the result is (1 - a_p) H_p + a_p c_p
+ *      per channel.  With max_samples = inf and a still camera that is the running mean of all frames.
+ *   5. output: the result replaces the accumulator's rgb in place (its alpha is never written), so srt_denoise,
+ *      srt_read_accumulator and bound tensors see it.  The accumulator then holds an estimate of L_p samples that no render
+ *      can continue: the next srt_render must use SRT_RENDER_RESET.  SRT_TEMPORAL_FRAMEBUFFER also writes tone_map(result)
+ *      into the framebuffer (all memory rows, the render's packing; miss pixels: tone_map of the accumulator).
+ *   6. history: result colour, L, object, normal and point per pixel (48 B) plus the camera, in two handle-owned slots
+ *      allocated on first use (96 B per pixel).  A call reads one slot and writes the other: one launch, no pixel reads what
+ *      another writes.  The history is invalid on the first call, with SRT_TEMPORAL_RESET, and after srt_set_scene,
+ *      srt_set_meshes or srt_set_environment; srt_set_camera does NOT invalidate it.
+ *   7. whole frame only, asynchronous on the launch stream behind earlier work (srt_wait / srt_poll cover it).  Leaves
+ *      srt_get_stats, srt_get_work_counts, the G-buffer and the launch shape of later renders as they are.  No atomics: the
+ *      same sequence of calls gives the same bits. */
+#define SRT_TEMPORAL_RESET 1u        /* drop the history: every hit pixel keeps its input, history length = samples */
+#define SRT_TEMPORAL_FRAMEBUFFER 2u  /* also write tone_map(result) into the framebuffer (all memory rows) */
+
+typedef struct srt_temporal_params {
+    uint32_t samples;        /* n: samples per pixel the accumulator holds for THIS frame, >= 1 */
+    float max_samples;       /* L_max: cap on the history length, >= samples (inf: no cap) */
+    float plane_tolerance;   /* sigma_t > 0: a tap is kept when |n_p.(x_q - x_p)| <= sigma_t * d_p */
+    float normal_threshold;  /* a tap is kept when n_p.n_q >= this; -1 (or less) turns the term off */
+    uint32_t flags;          /* SRT_TEMPORAL_* */
+} srt_temporal_params;
+
+/* The library's defaults, samples = 1 (pure host, no device needed). */
+int srt_temporal_params_default(srt_temporal_params* out);
+/* SRT_ERR_INVALID_ARG for samples == 0, max_samples < samples or NaN, plane_tolerance <= 0 or NaN, a NaN normal_threshold or
+ * unknown flags.  SRT_ERR_STATE before srt_set_camera, when OBJECT, NORMAL_DEPTH or POSITION has never been bound or
+ * rendered, or when one of those three is the handle's own and was last rendered with a camera other than the current one
+ * (bound guides cannot be checked: the caller answers for their matching the current camera). */
+int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* params);
+/* Wait, then copy the W*H history lengths L_p of the last call (float, scene rows).  SRT_ERR_STATE before the first call. */
+int srt_read_history_length(srt_context* ctx, float* dst);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

@@ -32,6 +32,7 @@ from .capi import (  # noqa: F401
     RenderParams,
     SrtError,
     Stats,
+    TemporalParams,
     build_native,
     default_camera,
     default_environment,
@@ -42,6 +43,6 @@ from . import host  # noqa: F401
 
 __all__ = [
     "capi", "host", "PathTracer", "SrtError", "Object", "Material", "Camera", "Environment",
-    "RenderParams", "GBufferParams", "DenoiseParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
+    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
     "load_library",
 ]

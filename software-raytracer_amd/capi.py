@@ -23,6 +23,9 @@ GBUFFERS = {"object": (GBUF_OBJECT, np.int32, 1), "normal_depth": (GBUF_NORMAL_D
 DENOISE_ALBEDO, DENOISE_FRAMEBUFFER = 1, 2
 # guides srt_denoise reads: OBJECT, NORMAL_DEPTH and POSITION always, ALBEDO when demodulating
 DENOISE_GUIDES = GBUF_OBJECT | GBUF_NORMAL_DEPTH | GBUF_POSITION
+TEMPORAL_RESET, TEMPORAL_FRAMEBUFFER = 1, 2
+# guides srt_temporal_accumulate reads
+TEMPORAL_GUIDES = GBUF_OBJECT | GBUF_NORMAL_DEPTH | GBUF_POSITION
 ABI_VERSION = 7
 
 # every symbol include/srt_pathtrace.h declares (tests check the library exports them all)
@@ -34,6 +37,7 @@ EXPORTS = [
     "srt_read_framebuffer_async", "srt_read_accumulator", "srt_write_accumulator", "srt_gather_band", "srt_gather_path", "srt_estimate_row_costs",
     "srt_selftest_arith", "srt_render_gbuffer", "srt_bind_gbuffer", "srt_read_gbuffer",
     "srt_denoise_params_default", "srt_denoise", "srt_bind_denoised", "srt_read_denoised",
+    "srt_temporal_params_default", "srt_temporal_accumulate", "srt_read_history_length",
 ]
 
 
@@ -115,6 +119,11 @@ class GBufferParams(C.Structure):
 class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
                 ("flags", C.c_uint32)]
+
+
+class TemporalParams(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("max_samples", C.c_float), ("plane_tolerance", C.c_float),
+                ("normal_threshold", C.c_float), ("flags", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -219,6 +228,9 @@ def open_library(path):
     L.srt_denoise.argtypes = [ctx, C.POINTER(DenoiseParams)]
     L.srt_bind_denoised.argtypes = [ctx, C.c_void_p]
     L.srt_read_denoised.argtypes = [ctx, C.POINTER(C.c_float)]
+    L.srt_temporal_params_default.argtypes = [C.POINTER(TemporalParams)]
+    L.srt_temporal_accumulate.argtypes = [ctx, C.POINTER(TemporalParams)]
+    L.srt_read_history_length.argtypes = [ctx, C.POINTER(C.c_float)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -255,11 +267,22 @@ def denoise_defaults(lib=None):
     return {n: getattr(p, n) for n, _ in DenoiseParams._fields_}
 
 
+def temporal_defaults(lib=None):
+    """srt_temporal_params_default as a dict (pure host: no GPU needed)."""
+    p = TemporalParams()
+    rc = (lib if lib is not None else load_library()).srt_temporal_params_default(C.byref(p))
+    if rc:
+        raise SrtError(rc, "srt_temporal_params_default")
+    return {n: getattr(p, n) for n, _ in TemporalParams._fields_}
+
+
 def __getattr__(name):
-    # DENOISE_DEFAULTS: the library's defaults (denoise_defaults()), read when first asked for, so that importing this module
-    # does not need the built library
+    # DENOISE_DEFAULTS / TEMPORAL_DEFAULTS: the library's defaults (denoise_defaults(), temporal_defaults()), read when first
+    # asked for, so that importing this module does not need the built library
     if name == "DENOISE_DEFAULTS":
         return denoise_defaults()
+    if name == "TEMPORAL_DEFAULTS":
+        return temporal_defaults()
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -271,6 +294,16 @@ def denoise_params(iterations=None, sigma_color=None, sigma_normal=None, sigma_p
                          float(d["sigma_color"] if sigma_color is None else sigma_color),
                          float(d["sigma_normal"] if sigma_normal is None else sigma_normal),
                          float(d["sigma_plane"] if sigma_plane is None else sigma_plane), flags)
+
+
+def temporal_params(samples=1, max_samples=None, plane_tolerance=None, normal_threshold=None, reset=False, framebuffer=False,
+                    lib=None):
+    """A TemporalParams: the library defaults, with every argument that is not None put in their place."""
+    d = temporal_defaults(lib)
+    flags = (TEMPORAL_RESET if reset else 0) | (TEMPORAL_FRAMEBUFFER if framebuffer else 0)
+    return TemporalParams(int(samples), float(d["max_samples"] if max_samples is None else max_samples),
+                          float(d["plane_tolerance"] if plane_tolerance is None else plane_tolerance),
+                          float(d["normal_threshold"] if normal_threshold is None else normal_threshold), flags)
 
 
 def _f3(v):
@@ -440,6 +473,23 @@ class PathTracer:
         if not tensor.is_contiguous():
             raise ValueError("bind_denoised: tensor is not contiguous")
         self._ck(self.L.srt_bind_denoised(self._h, C.c_void_p(tensor.data_ptr())))
+
+    def temporal(self, samples=1, max_samples=None, plane_tolerance=None, normal_threshold=None, reset=False, framebuffer=False,
+                 gbuffer=True):
+        """srt_temporal_accumulate: blend the accumulator (which must hold `samples` samples of the current camera) with the
+        history of the previous call, reprojected, in place.  Arguments left at None take TEMPORAL_DEFAULTS.  gbuffer=True
+        first enqueues render_gbuffer() for the guides it reads (current scene and camera); gbuffer=False uses the guides as
+        they are.  Asynchronous.  The next render() must reset."""
+        p = temporal_params(samples, max_samples, plane_tolerance, normal_threshold, reset, framebuffer, lib=self.L)
+        if gbuffer:
+            self.render_gbuffer(outputs=TEMPORAL_GUIDES)
+        self._ck(self.L.srt_temporal_accumulate(self._h, C.byref(p)))
+
+    def history_length(self):
+        """srt_read_history_length: L of the last temporal() call, (H, W) float32, rows = scene rows."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self._ck(self.L.srt_read_history_length(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     def wait(self):
         self._ck(self.L.srt_wait(self._h))

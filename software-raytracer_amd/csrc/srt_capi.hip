@@ -19,6 +19,7 @@
 #include "srt_kernel.hip.h"
 #include "srt_gbuffer.hip.h"
 #include "srt_denoise.hip.h"
+#include "srt_temporal.hip.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -198,6 +199,19 @@ struct srt_context {
     float4* d_dn_bound = nullptr;
     bool dn_written = false;
 
+    // the camera each own first-hit slot was last rendered with (srt_temporal_accumulate refuses own guides of another camera)
+    srt_camera gbuf_own_cam[4] = {};
+    bool gbuf_own_cam_set[4] = {false, false, false, false};
+
+    // temporal reprojection (srt_temporal_accumulate): two history slots of three W*H float4 arrays each (allocated on first
+    // use), the slot the last call wrote and the camera it was written with, whether that history may be reprojected (false
+    // after a scene, mesh or environment change), and whether any call has been enqueued yet (srt_read_history_length)
+    float4* d_tp[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    int tp_cur = 0;
+    srt_camera tp_cam{};
+    bool tp_valid = false;
+    bool tp_written = false;
+
     char error[512] = "";
 };
 
@@ -342,6 +356,9 @@ int srt_destroy(srt_context* ctx) {
         if (ctx->d_gbuf_own[i]) (void)hipFree(ctx->d_gbuf_own[i]);
     if (ctx->d_dn_own) (void)hipFree(ctx->d_dn_own);
     if (ctx->d_dn_tmp) (void)hipFree(ctx->d_dn_tmp);
+    for (int i = 0; i < 2; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (ctx->d_tp[i][k]) (void)hipFree(ctx->d_tp[i][k]);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -443,6 +460,7 @@ static int set_scene_impl(srt_context* ctx, const srt_object* objects, size_t co
 
 // Host-side allocation failures (std::bad_alloc from the image / BVH builders) must not cross the C boundary.
 int srt_set_scene(srt_context* ctx, const srt_object* objects, size_t count) {
+    if (ctx) ctx->tp_valid = false;  // the temporal history's object indices and points belong to the old scene
     try {
         return set_scene_impl(ctx, objects, count);
     } catch (const std::bad_alloc&) {
@@ -472,6 +490,7 @@ static int set_meshes_impl(srt_context* ctx, const srt_mesh* meshes, size_t coun
 }
 
 int srt_set_meshes(srt_context* ctx, const srt_mesh* meshes, size_t count) {
+    if (ctx) ctx->tp_valid = false;
     try {
         return set_meshes_impl(ctx, meshes, count);
     } catch (const std::bad_alloc&) {
@@ -484,6 +503,7 @@ int srt_set_meshes(srt_context* ctx, const srt_mesh* meshes, size_t count) {
 int srt_set_environment(srt_context* ctx, const srt_environment* env) {
     if (!ctx || !env) return SRT_ERR_INVALID_ARG;
     ctx->env = *env;
+    ctx->tp_valid = false;  // the lighting changed: the temporal history's colours are another image's
     // the environment lives in the scene image's constants block (srt_scene_image.h): patch the uploaded images in place
     if (ctx->scene_set) {
         SRT_HIP(ctx, hipSetDevice(ctx->device));
@@ -539,22 +559,27 @@ int srt_device_accumulator(srt_context* ctx, void** d_ptr) {
 
 }  // extern "C"
 
-static int fill_kernel_params(srt_context* ctx, const srt_render_params* p, srt::KernelParams& K, size_t& lds_bytes, int& use, int& img) {
-    const int W = ctx->width, H = ctx->height;
-    memset(&K, 0, sizeof K);
-    const srt_camera& c = ctx->camera.cam;
-    // frame-constant part of GetRayDirection (Raytracer.cpp:107-115)
+// frame-constant part of GetRayDirection (Raytracer.cpp:107-115): the ray basis right * rd, up * ld, forward * clipDistance
+// (srt_render, srt_render_gbuffer and the reprojection of srt_temporal_accumulate fold it the same way)
+static void fold_camera(const srt_camera& c, int W, int H, float* right_rd, float* up_ld, float* fwd_clip) {
     const float clipDistance = .01f;
     float aspecRatio = (float)W / (float)H;
     float hFov = (float)(c.fov_degrees * 3.14159265358979323846 / 180.0f);
     float rd = (clipDistance * tanf(hFov / 2.0f)) * aspecRatio;
     float ld = (clipDistance * tanf(hFov / 2.0f));
     for (int i = 0; i < 3; ++i) {
-        K.cam_pos[i] = c.position[i];
-        K.right_rd[i] = c.right[i] * rd;
-        K.up_ld[i] = c.up[i] * ld;
-        K.fwd_clip[i] = c.forward[i] * clipDistance;
+        right_rd[i] = c.right[i] * rd;
+        up_ld[i] = c.up[i] * ld;
+        fwd_clip[i] = c.forward[i] * clipDistance;
     }
+}
+
+static int fill_kernel_params(srt_context* ctx, const srt_render_params* p, srt::KernelParams& K, size_t& lds_bytes, int& use, int& img) {
+    const int W = ctx->width, H = ctx->height;
+    memset(&K, 0, sizeof K);
+    const srt_camera& c = ctx->camera.cam;
+    fold_camera(c, W, H, K.right_rd, K.up_ld, K.fwd_clip);
+    for (int i = 0; i < 3; ++i) K.cam_pos[i] = c.position[i];
     K.width = W;
     K.height = H;
     K.y0 = H - p->row_end;  // memory rows [rb,re) = scene rows [H-re, H-rb)
@@ -1149,6 +1174,8 @@ int srt_render_gbuffer(srt_context* ctx, const srt_gbuffer_params* g) {
         }
         if (!ctx->d_gbuf_own[i]) SRT_HIP(ctx, hipMalloc(&ctx->d_gbuf_own[i], px * gbuf_elem_bytes(i)));
         dst[i] = ctx->d_gbuf_own[i];
+        ctx->gbuf_own_cam[i] = ctx->camera.cam;
+        ctx->gbuf_own_cam_set[i] = true;
     }
     // the render's kernel parameters for this band: camera, scene image, the scene_in_lds judgement and the LDS bytes
     srt_render_params p{};
@@ -1281,6 +1308,114 @@ int srt_read_denoised(srt_context* ctx, float* dst_rgba) {
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     SRT_HIP(ctx, hipMemcpy(dst_rgba, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+// ---- temporal reprojection ------------------------------------------------------------------------------------------
+int srt_temporal_params_default(srt_temporal_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    // chosen by tools/temporal_time.py sweep on Scene1 and Scene_indirect
+    out->samples = 1;
+    out->max_samples = 32.0f;
+    out->plane_tolerance = 0.02f;
+    out->normal_threshold = 0.9f;
+    out->flags = 0;
+    return SRT_OK;
+}
+
+static bool same_camera(const srt_camera& a, const srt_camera& b) {
+    for (int i = 0; i < 3; ++i)
+        if (a.position[i] != b.position[i] || a.right[i] != b.right[i] || a.up[i] != b.up[i] || a.forward[i] != b.forward[i]) return false;
+    return a.fov_degrees == b.fov_degrees;
+}
+
+// B^-1 of the camera's ray basis B = [right * rd | up * ld | forward * clip] (columns, the floats srt_render uses), inverted in
+// double and rounded to float, row-major.  False when B is singular or not finite.
+static bool invert_ray_basis(const srt_camera& c, int W, int H, float inv[9]) {
+    float r[3], u[3], f[3];
+    fold_camera(c, W, H, r, u, f);
+    const double m[3][3] = {{r[0], u[0], f[0]}, {r[1], u[1], f[1]}, {r[2], u[2], f[2]}};
+    const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2],
+                 c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+    const double det = m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02;
+    if (!(det != 0.0) || !std::isfinite(det)) return false;
+    const double adj[3][3] = {{c00, m[0][2] * m[2][1] - m[0][1] * m[2][2], m[0][1] * m[1][2] - m[0][2] * m[1][1]},
+                              {c01, m[0][0] * m[2][2] - m[0][2] * m[2][0], m[0][2] * m[1][0] - m[0][0] * m[1][2]},
+                              {c02, m[0][1] * m[2][0] - m[0][0] * m[2][1], m[0][0] * m[1][1] - m[0][1] * m[1][0]}};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            inv[3 * i + j] = (float)(adj[i][j] / det);
+            if (!std::isfinite(inv[3 * i + j])) return false;
+        }
+    return true;
+}
+
+int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
+    if (!ctx || !t) return SRT_ERR_INVALID_ARG;
+    if (t->samples == 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_temporal_accumulate: samples must be >= 1");
+    // (written so that a NaN fails too)
+    if (!(t->max_samples >= (float)t->samples))
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_temporal_accumulate: max_samples %g < samples %u", t->max_samples, t->samples);
+    if (!(t->plane_tolerance > 0.0f))
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_temporal_accumulate: plane_tolerance must be > 0 (%g)", t->plane_tolerance);
+    if (t->normal_threshold != t->normal_threshold) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_temporal_accumulate: normal_threshold is NaN");
+    if (t->flags & ~(SRT_TEMPORAL_RESET | SRT_TEMPORAL_FRAMEBUFFER))
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_temporal_accumulate: unknown flags 0x%x", t->flags);
+    if (!ctx->camera.set) return fail(ctx, SRT_ERR_STATE, "srt_temporal_accumulate: srt_set_camera has not been called");
+    const void* guide[3];
+    static const char* const names[3] = {"OBJECT", "NORMAL_DEPTH", "POSITION"};
+    for (int i = 0; i < 3; ++i) {
+        guide[i] = ctx->d_gbuf_bound[i] ? ctx->d_gbuf_bound[i] : ctx->d_gbuf_own[i];
+        if (!guide[i])
+            return fail(ctx, SRT_ERR_STATE, "srt_temporal_accumulate: the %s guide has neither been bound nor rendered (srt_render_gbuffer)", names[i]);
+        // the handle's own guides must show the camera the history will be stored with (bound ones cannot be checked)
+        if (!ctx->d_gbuf_bound[i] && (!ctx->gbuf_own_cam_set[i] || !same_camera(ctx->gbuf_own_cam[i], ctx->camera.cam)))
+            return fail(ctx, SRT_ERR_STATE, "srt_temporal_accumulate: the %s guide was rendered with another camera (srt_render_gbuffer after srt_set_camera)",
+                        names[i]);
+    }
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)ctx->width * (size_t)ctx->height;
+    for (int i = 0; i < 2; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (!ctx->d_tp[i][k]) SRT_HIP(ctx, hipMalloc((void**)&ctx->d_tp[i][k], px * sizeof(float4)));
+    const int a = ctx->tp_cur, b = 1 - a;  // read slot a (when valid), write slot b
+    srt::TemporalLaunch T{};
+    T.acc = ctx->d_acc;
+    T.object = (const int32_t*)guide[0];
+    T.normal_depth = (const float4*)guide[1];
+    T.position = (const float4*)guide[2];
+    T.prev = srt::TemporalSlot{ctx->d_tp[a][0], ctx->d_tp[a][1], ctx->d_tp[a][2]};
+    T.next = srt::TemporalSlot{ctx->d_tp[b][0], ctx->d_tp[b][1], ctx->d_tp[b][2]};
+    T.framebuffer = (t->flags & SRT_TEMPORAL_FRAMEBUFFER) ? ctx->d_fb : nullptr;
+    T.width = ctx->width, T.height = ctx->height;
+    T.valid = ctx->tp_written && ctx->tp_valid && !(t->flags & SRT_TEMPORAL_RESET) &&
+              invert_ray_basis(ctx->tp_cam, ctx->width, ctx->height, T.inv);
+    for (int i = 0; i < 3; ++i) T.cam_pos[i] = ctx->tp_cam.position[i];
+    T.samples = (float)t->samples;
+    T.max_samples = t->max_samples;
+    T.plane_tolerance = t->plane_tolerance;
+    T.normal_threshold = t->normal_threshold;
+    const dim3 grid((unsigned)((ctx->width + srt::WG_W - 1) / srt::WG_W), (unsigned)((ctx->height + srt::WG_H - 1) / srt::WG_H)),
+        block(srt::WG_THREADS);
+    hipLaunchKernelGGL(srt::temporal_kernel, grid, block, 0, ctx->stream, T);
+    SRT_HIP(ctx, hipGetLastError());
+    ctx->tp_cur = b;
+    ctx->tp_cam = ctx->camera.cam;
+    ctx->tp_valid = true;
+    ctx->tp_written = true;
+    return SRT_OK;
+}
+
+int srt_read_history_length(srt_context* ctx, float* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    if (!ctx->tp_written) return fail(ctx, SRT_ERR_STATE, "srt_read_history_length: srt_temporal_accumulate has not been called");
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // L is the w of the history colour
+    const size_t px = (size_t)ctx->width * ctx->height;
+    std::vector<float4> tmp(px);
+    SRT_HIP(ctx, hipMemcpy(tmp.data(), ctx->d_tp[ctx->tp_cur][0], px * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < px; ++i) dst[i] = tmp[i].w;
     return SRT_OK;
 }
 

@@ -1,0 +1,117 @@
+// srt_temporal.hip.h — gfx950 temporal reprojection (srt_temporal_accumulate): the accumulator of the current camera is
+// blended with the history of the previous call, reprojected through the previous camera, so that a moving camera keeps
+// the samples it has already taken (the temporal stage of SVGF, Schied et al. 2017, without the variance estimate).
+//
+// One launch per call.  Each pixel projects its own first-hit point x_p into the previous camera (the host passes B'^-1,
+// the inverse of the previous frame's ray basis, see include/srt_pathtrace.h), takes the 2 x 2 bilinear footprint there,
+// tests every tap against the stored guides of the previous call (object, plane distance, normal) and blends the counted
+// taps' colour and history length.  The history lives in two slots: the launch reads slot A and writes slot B, so no pixel
+// reads what another writes and no grid-wide barrier is needed.
+// Work shape as denoise_kernel: a wave per 8 x 8 tile (lane -> x = lane & 7, y = lane >> 3), four waves per workgroup
+// (16 x 16 pixels), so every float4 row segment a wave touches is one 128-byte line.  No LDS, no atomics, no scratch.
+#pragma once
+
+#include "srt_kernel.hip.h"
+
+namespace srt {
+
+// One history slot: three W*H float4 arrays, index x + y * width, SCENE rows.
+struct TemporalSlot {
+    float4* color;       // result rgb, history length L in w (0 on a miss)
+    float4* pos_object;  // x_p xyz, object index o_p in w (as int bits; -1 on a miss)
+    float4* normal;      // n_p xyz, 0
+};
+
+struct TemporalLaunch {
+    float4* acc;                 // the accumulator: read, and its rgb replaced in place (alpha rewritten with its own bits)
+    const int32_t* object;       // SRT_GBUF_OBJECT
+    const float4* normal_depth;  // SRT_GBUF_NORMAL_DEPTH: n xyz, d w
+    const float4* position;      // SRT_GBUF_POSITION: x xyz
+    TemporalSlot prev;           // the previous call's history (read only when valid)
+    TemporalSlot next;           // this call's history (written for every pixel)
+    uint32_t* framebuffer;       // SRT_TEMPORAL_FRAMEBUFFER, else NULL (memory row H - 1 - y)
+    int width, height;
+    int valid;                   // the previous slot holds a history for this scene
+    float inv[9];                // B'^-1, row-major
+    float cam_pos[3];            // C'.position
+    float samples;               // n
+    float max_samples;           // L_max
+    float plane_tolerance;       // sigma_t
+    float normal_threshold;      // <= -1: term off
+};
+
+__global__ void __launch_bounds__(WG_THREADS) temporal_kernel(const TemporalLaunch T) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = (int)blockIdx.x * WG_W + (wave % WG_TILES_X) * TILE_W + (lane & 7);
+    const int y = (int)blockIdx.y * WG_H + (wave / WG_TILES_X) * TILE_H + (lane >> 3);
+    const int W = T.width, H = T.height;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)x + (size_t)y * (size_t)W;
+    const int op = T.object[p];
+    if (op < 0) {  // miss: the accumulator untouched, L = 0, never a tap
+        T.next.color[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        T.next.pos_object[p] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+        T.next.normal[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (T.framebuffer) T.framebuffer[(size_t)(H - 1 - y) * W + x] = tone_map(T.acc[p]);
+        return;
+    }
+    const float4 c = T.acc[p];
+    const float4 nd = T.normal_depth[p];
+    const float4 xx = T.position[p];
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f;
+    if (T.valid) {
+        const float rx = xx.x - T.cam_pos[0], ry = xx.y - T.cam_pos[1], rz = xx.z - T.cam_pos[2];
+        const float a = T.inv[0] * rx + T.inv[1] * ry + T.inv[2] * rz;
+        const float b = T.inv[3] * rx + T.inv[4] * ry + T.inv[5] * rz;
+        const float g = T.inv[6] * rx + T.inv[7] * ry + T.inv[8] * rz;
+        if (g > 0.0f) {
+            const float u = (a / g + 1.0f) * ((float)W * 0.5f);
+            const float v = (b / g + 1.0f) * ((float)H * 0.5f);
+            // some tap of positive weight lies inside the frame only for u in (-1, W) and v in (-1, H) (also keeps NaN and
+            // huge values away from the integer conversion)
+            if (u > -1.0f && u < (float)W && v > -1.0f && v < (float)H) {
+                const float fu = floorf(u), fv = floorf(v);
+                const int x0 = (int)fu, y0 = (int)fv;
+                const float fx = u - fu, fy = v - fv;
+                const float tol = T.plane_tolerance * nd.w;
+                const bool use_n = T.normal_threshold > -1.0f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
+                    const float w = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
+                    if (w <= 0.0f || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                    const size_t q = (size_t)qx + (size_t)qy * (size_t)W;
+                    const float4 po = T.prev.pos_object[q];
+                    if (__float_as_int(po.w) != op) continue;  // another object or a miss
+                    const float d = nd.x * (po.x - xx.x) + nd.y * (po.y - xx.y) + nd.z * (po.z - xx.z);
+                    if (!(fabsf(d) <= tol)) continue;
+                    if (use_n) {
+                        const float4 nq = T.prev.normal[q];
+                        if (!(nd.x * nq.x + nd.y * nq.y + nd.z * nq.z >= T.normal_threshold)) continue;
+                    }
+                    const float4 h = T.prev.color[q];
+                    sw = sw + w;
+                    sr = sr + w * h.x;
+                    sg = sg + w * h.y;
+                    sb = sb + w * h.z;
+                    sl = sl + w * h.w;
+                }
+            }
+        }
+    }
+    float4 out = c;
+    float L = T.samples;
+    if (sw > 0.0f) {
+        const float inv_w = 1.0f / sw;
+        L = fminf(sl * inv_w + T.samples, T.max_samples);
+        const float al = T.samples / L, bl = 1.0f - al;
+        out = make_float4(bl * (sr * inv_w) + al * c.x, bl * (sg * inv_w) + al * c.y, bl * (sb * inv_w) + al * c.z, c.w);
+        T.acc[p] = out;
+    }
+    T.next.color[p] = make_float4(out.x, out.y, out.z, L);
+    T.next.pos_object[p] = make_float4(xx.x, xx.y, xx.z, __int_as_float(op));
+    T.next.normal[p] = make_float4(nd.x, nd.y, nd.z, 0.0f);
+    if (T.framebuffer) T.framebuffer[(size_t)(H - 1 - y) * W + x] = tone_map(out);
+}
+
+}  // namespace srt

@@ -7,8 +7,8 @@ import subprocess
 
 import numpy as np
 
-from .capi import (DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, DenoiseParams, Mesh, Object, Stats, denoise_params,
-                   gbuffer_outputs)
+from .capi import (DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, DenoiseParams, Mesh, Object, Stats, TemporalParams,
+                   denoise_params, gbuffer_outputs, temporal_params)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_PKG, "libsrt_host.so")
@@ -24,6 +24,8 @@ EXPORTS = [
     "srt_host_renderer_accumulation_frames", "srt_host_renderer_wait", "srt_host_renderer_read_framebuffer",
     "srt_host_renderer_read_accumulator", "srt_host_renderer_stats", "srt_host_renderer_handle",
     "srt_host_renderer_render_gbuffer", "srt_host_renderer_read_gbuffer", "srt_host_renderer_denoise", "srt_host_renderer_read_denoised",
+    "srt_host_renderer_temporal", "srt_host_renderer_read_history_length", "srt_host_renderer_render_temporal_frame",
+    "srt_host_renderer_move_camera",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -101,6 +103,10 @@ def load_library():
     L.srt_host_renderer_read_gbuffer.argtypes = [vp, C.c_uint32, vp]
     L.srt_host_renderer_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
     L.srt_host_renderer_read_denoised.argtypes = [vp, C.POINTER(C.c_float)]
+    L.srt_host_renderer_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
+    L.srt_host_renderer_read_history_length.argtypes = [vp, C.POINTER(C.c_float)]
+    L.srt_host_renderer_render_temporal_frame.argtypes = [vp, C.c_uint32, C.c_int]
+    L.srt_host_renderer_move_camera.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.srt_host_multi_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]
     L.srt_host_multi_create.restype = vp
     L.srt_host_multi_destroy.argtypes = [vp]
@@ -315,6 +321,30 @@ class Renderer:
         out = np.empty((self.height, self.width, 4), dtype=np.float32)
         self._ck(self.L.srt_host_renderer_read_denoised(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def temporal(self, samples=1, max_samples=None, plane_tolerance=None, normal_threshold=None, reset=False, framebuffer=False,
+                 gbuffer=True):
+        """PathTraceRenderer::Temporal, with the arguments of capi.PathTracer.temporal (gbuffer=True: render_gbuffer first)."""
+        p = temporal_params(samples, max_samples, plane_tolerance, normal_threshold, reset, framebuffer)
+        if gbuffer:
+            self.render_gbuffer(TEMPORAL_GUIDES)
+        self._ck(self.L.srt_host_renderer_temporal(self._h, C.byref(p)))
+
+    def history_length(self):
+        """PathTraceRenderer::ReadHistoryLength: (H, W) float32, scene rows."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_history_length(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def render_temporal_frame(self, spp=1, denoise=False):
+        """PathTraceRenderer::RenderTemporalFrame: render, guides, reprojection (and the denoiser) into the framebuffer."""
+        self._ck(self.L.srt_host_renderer_render_temporal_frame(self._h, int(spp), 1 if denoise else 0))
+
+    def move_camera(self, position, basis9):
+        """set_camera without Invalidate(): a camera move that keeps the temporal history."""
+        p = (C.c_float * 3)(*[float(x) for x in position])
+        b = (C.c_float * 9)(*[float(x) for x in basis9])
+        self._ck(self.L.srt_host_renderer_move_camera(self._h, p, b))
 
     def stats(self):
         s = Stats()

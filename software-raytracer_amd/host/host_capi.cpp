@@ -208,6 +208,21 @@ int srt_host_renderer_read_gbuffer(srt_host_renderer* h, uint32_t output, void* 
 // denoiser over the whole frame with the guides as they stand (srt_denoise / srt_read_denoised)
 int srt_host_renderer_denoise(srt_host_renderer* h, const srt_denoise_params* p) { SRT_HOST_TRY(h, h->r->Denoise(*p)) }
 int srt_host_renderer_read_denoised(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadDenoised(dst)) }
+// temporal reprojection (srt_temporal_accumulate / srt_read_history_length) and the temporal frame of a moving camera
+int srt_host_renderer_temporal(srt_host_renderer* h, const srt_temporal_params* p) { SRT_HOST_TRY(h, h->r->Temporal(*p)) }
+int srt_host_renderer_read_history_length(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadHistoryLength(dst)) }
+int srt_host_renderer_render_temporal_frame(srt_host_renderer* h, uint32_t spp, int denoise) {
+    SRT_HOST_TRY(h, h->r->RenderTemporalFrame(spp, denoise != 0))
+}
+// a camera move that keeps the temporal history: srt_host_renderer_set_camera without the Invalidate()
+int srt_host_renderer_move_camera(srt_host_renderer* h, const float* pos, const float* right_up_forward) {
+    Transform& t = h->r->camera;
+    t.position = Vec3(pos[0], pos[1], pos[2]);
+    t.right = Vec3(right_up_forward[0], right_up_forward[1], right_up_forward[2]);
+    t.up = Vec3(right_up_forward[3], right_up_forward[4], right_up_forward[5]);
+    t.forward = Vec3(right_up_forward[6], right_up_forward[7], right_up_forward[8]);
+    return 0;
+}
 int srt_host_renderer_stats(srt_host_renderer* h, srt_stats* out) { SRT_HOST_TRY(h, *out = h->r->Stats()) }
 void* srt_host_renderer_handle(srt_host_renderer* h) { return h->r->handle(); }
 

@@ -26,19 +26,19 @@ void PathTraceRenderer::SetScene(const Scene& scene) {
     std::vector<srt_mesh> meshes = scene.MeshViews();  // EXTENSION: geometry of "Mesh" renderers
     check(srt_set_meshes(ctx_, meshes.data(), meshes.size()), "srt_set_meshes");
     check(srt_set_scene(ctx_, flat.data(), flat.size()), "srt_set_scene");
-    doSetFrame_ = true;
+    Invalidate();
 }
 
 void PathTraceRenderer::SetEnvironment(const srt_environment& env) {
     check(srt_set_environment(ctx_, &env), "srt_set_environment");
-    doSetFrame_ = true;
+    Invalidate();
 }
 
 void PathTraceRenderer::SetRowBand(int begin, int end) {
     if (begin < 0 || end > height_ || begin >= end) throw RendererError(SRT_ERR_INVALID_ARG, "SetRowBand: bad band");
     row_begin_ = begin;
     row_end_ = end;
-    doSetFrame_ = true;
+    Invalidate();
 }
 
 void PathTraceRenderer::push_camera() {
@@ -152,6 +152,47 @@ void PathTraceRenderer::ReadGBuffer(uint32_t output, void* dst) { check(srt_read
 void PathTraceRenderer::Denoise(const srt_denoise_params& params) { check(srt_denoise(ctx_, &params), "srt_denoise"); }
 
 void PathTraceRenderer::ReadDenoised(float* dst_rgba) { check(srt_read_denoised(ctx_, dst_rgba), "srt_read_denoised"); }
+
+void PathTraceRenderer::Temporal(const srt_temporal_params& params) { check(srt_temporal_accumulate(ctx_, &params), "srt_temporal_accumulate"); }
+
+void PathTraceRenderer::ReadHistoryLength(float* dst) { check(srt_read_history_length(ctx_, dst), "srt_read_history_length"); }
+
+void PathTraceRenderer::RenderTemporalFrame(uint32_t spp, bool denoise) {
+    if (spp == 0) throw RendererError(SRT_ERR_INVALID_ARG, "RenderTemporalFrame: spp must be >= 1");
+    if (row_begin_ != 0 || row_end_ != height_)
+        throw RendererError(SRT_ERR_STATE, "RenderTemporalFrame: the renderer has a row band; temporal frames cover the whole frame");
+    push_camera();
+    srt_render_params p{};
+    p.row_begin = 0;
+    p.row_end = height_;
+    p.first_sample = 1;
+    p.sample_count = spp;
+    p.max_bounces = MAXBOUNCES < 0 ? 0 : MAXBOUNCES;
+    p.seed = seed + temporal_frames_;
+    p.flags = SRT_RENDER_RESET;
+    p.steps = 1;
+    p.selected_object = -1;
+    check(srt_render(ctx_, &p), "srt_render");
+    RenderGBuffer(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION | (denoise ? SRT_GBUF_ALBEDO : 0u));
+    srt_temporal_params t{};
+    check(srt_temporal_params_default(&t), "srt_temporal_params_default");
+    t.samples = spp;
+    if (t.max_samples < (float)spp) t.max_samples = (float)spp;
+    t.flags = (temporal_reset_ ? SRT_TEMPORAL_RESET : 0u) | (denoise ? 0u : SRT_TEMPORAL_FRAMEBUFFER);
+    Temporal(t);
+    if (denoise) {
+        srt_denoise_params d{};
+        check(srt_denoise_params_default(&d), "srt_denoise_params_default");
+        d.flags |= SRT_DENOISE_FRAMEBUFFER;
+        Denoise(d);
+    }
+    temporal_reset_ = false;
+    ++temporal_frames_;
+    // the accumulator now holds a blended estimate no render can continue
+    doSetFrame_ = true;
+    clean_reset_ = true;
+    first_frame_ = false;
+}
 
 std::vector<float> PathTraceRenderer::ReadAccumulator() {
     std::vector<float> out((size_t)width_ * height_ * 4);

@@ -83,8 +83,10 @@ class PathTraceRenderer {
     // restrict rendering to memory rows [begin,end) (multi-GPU row stripes)
     void SetRowBand(int begin, int end);
     void RowBand(int* begin, int* end) const { *begin = row_begin_, *end = row_end_; }
-    // doSetFrame = true: any camera / object / setting edit (:391,453,461,469,476,497,522)
-    void Invalidate() { doSetFrame_ = true; }
+    // doSetFrame = true: any camera / object / setting edit (:391,453,461,469,476,497,522).  Also drops the temporal
+    // history: the next RenderTemporalFrame starts afresh (SRT_TEMPORAL_RESET).  A temporal camera move changes `camera`
+    // without calling this.
+    void Invalidate() { doSetFrame_ = true, temporal_reset_ = true; }
 
     // One iteration of the reference's frame loop as far as rendering is concerned: the
     // accumulate state machine (:572-590) followed by releasing the workers for ONE frame
@@ -117,6 +119,17 @@ class PathTraceRenderer {
     // RenderGBuffer first).  Asynchronous; ReadDenoised waits and copies the W x H float4 result (scene rows).
     void Denoise(const srt_denoise_params& params);
     void ReadDenoised(float* dst_rgba);
+    // Temporal reprojection (srt_temporal_accumulate) over the whole frame with the guides as they stand; ReadHistoryLength
+    // waits and copies the W x H history lengths (scene rows).
+    void Temporal(const srt_temporal_params& params);
+    void ReadHistoryLength(float* dst);
+    // One frame of a moving camera that keeps its samples (whole frame only): push the camera, render `spp` samples with
+    // SRT_RENDER_RESET and seed + k (k = the number of temporal frames this renderer has rendered before, so that the noise
+    // does not stay fixed to the screen), the first-hit guides, srt_temporal_accumulate with the library's defaults
+    // (samples = spp, max_samples raised to spp if below; SRT_TEMPORAL_RESET on the first temporal frame and after
+    // Invalidate(), SetScene, SetEnvironment or SetRowBand), then with `denoise` srt_denoise with its defaults.  The last step
+    // writes the framebuffer.  Later RenderFrame / RenderSamples calls start a fresh accumulation.
+    void RenderTemporalFrame(uint32_t spp, bool denoise);
 
     void PushCamera() { push_camera(); }  // srt_set_camera with the members as they stand (used by MultiGpuRenderer)
 
@@ -127,6 +140,8 @@ class PathTraceRenderer {
     int width_, height_;
     int row_begin_, row_end_;
     bool doSetFrame_ = false;
+    bool temporal_reset_ = true;    // the next RenderTemporalFrame drops the history
+    uint32_t temporal_frames_ = 0;  // RenderTemporalFrame calls so far (the seed offset)
     bool first_frame_ = true;
     bool clean_reset_ = true;  // RenderSamples: next call starts at sample 1 with reset
     uint32_t next_clean_sample_ = 1;

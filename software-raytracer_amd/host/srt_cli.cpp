@@ -64,7 +64,7 @@ static void usage() {
     std::fprintf(stderr,
                  "usage: srt_render --scene FILE [--width 1280] [--height 720] [--spp 32] [--bounces 2]\n"
                  "                  [--fov 55] [--seed 0] [--device 0 | --devices 0,1,2,...] [--out frame.ppm] [--resave FILE]\n"
-                 "                  [--gbuffer PREFIX] [--denoise PATH]\n"
+                 "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
                  "             and means the same), --equal-bands: bands of equal height\n"
@@ -72,11 +72,17 @@ static void usage() {
                  "             PREFIX_position.npy and PREFIX_albedo.npy (float32 HxWx4), rows top-down like the PPM\n"
                  "             (with --devices: made for the whole frame on the first device)\n"
                  "  --denoise: also render the first-hit buffers, denoise the accumulator with the library's defaults\n"
-                 "             (srt_denoise) and write the tone-mapped result to PATH as a PPM (single device only)\n");
+                 "             (srt_denoise) and write the tone-mapped result to PATH as a PPM (single device only)\n"
+                 "  --temporal: render FRAMES frames of --spp samples each while the camera moves, keeping samples across\n"
+                 "             frames (srt_temporal_accumulate), and write the last one to --out (--denoise PATH: also its\n"
+                 "             denoised form); before every frame but the first the camera moves by R, U, F along its right,\n"
+                 "             up and forward axes (--move) and turns by DEG degrees about world up (--turn); single device only\n");
 }
 
 int main(int argc, char** argv) {
     std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise;
+    int temporal = 0;
+    float move[3] = {0, 0, 0}, turn_deg = 0;
     int W = 1280, H = 720, spp = 32, bounces = 2, fov = 55, device = 0;  // Raytracer.cpp:26-27,31-32
     unsigned seed = 0;
     std::vector<int> devices;
@@ -110,17 +116,35 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--resave")) resave = need("--resave");
         else if (!std::strcmp(argv[i], "--gbuffer")) gbuffer = need("--gbuffer");
         else if (!std::strcmp(argv[i], "--denoise")) denoise = need("--denoise");
+        else if (!std::strcmp(argv[i], "--temporal")) temporal = std::atoi(need("--temporal"));
+        else if (!std::strcmp(argv[i], "--turn")) turn_deg = std::strtof(need("--turn"), nullptr);
+        else if (!std::strcmp(argv[i], "--move")) {
+            const char* p = need("--move");
+            for (int k = 0; k < 3; ++k) {
+                char* end = nullptr;
+                move[k] = std::strtof(p, &end);
+                if (end == p || (k < 2 && *end != ',') || (k == 2 && *end)) {
+                    std::fprintf(stderr, "--move wants R,U,F\n");
+                    return 2;
+                }
+                p = end + 1;
+            }
+        }
         else {
             usage();
             return 2;
         }
     }
-    if (scene_path.empty() || W <= 0 || H <= 0 || spp <= 0) {
+    if (scene_path.empty() || W <= 0 || H <= 0 || spp <= 0 || temporal < 0) {
         usage();
         return 2;
     }
     if (!denoise.empty() && !devices.empty()) {
         std::fprintf(stderr, "--denoise works on one device only: the accumulator bands of --devices live on different GPUs\n");
+        return 2;
+    }
+    if (temporal && !devices.empty()) {
+        std::fprintf(stderr, "--temporal works on one device only: the history of --devices would be split over different GPUs\n");
         return 2;
     }
     Scene scene(scene_path);
@@ -178,6 +202,43 @@ int main(int argc, char** argv) {
         r.MAXBOUNCES = bounces;
         r.seed = seed;
         r.SetScene(scene);
+        if (temporal) {
+            // a moving camera that keeps its samples: every frame renders spp samples, reprojects the history and writes the
+            // framebuffer; each frame's camera is printed exactly (%.9g round-trips a float) so that callers can replay it
+            std::vector<uint32_t> fb((size_t)W * H);
+            const Vec3 world_up(0, 1, 0);
+            const float turn = (float)(turn_deg * 3.14159265358979323846 / 180.0);
+            auto t0 = std::chrono::steady_clock::now();
+            for (int k = 0; k < temporal; ++k) {
+                if (k > 0) {
+                    Transform& c = r.camera;
+                    c.position = c.position + c.right * move[0] + c.up * move[1] + c.forward * move[2];
+                    if (turn != 0) c.RotateAboutAxis(turn, world_up);
+                }
+                const Transform& c = r.camera;
+                std::fprintf(stderr, "temporal frame %d camera %.9g %.9g %.9g  %.9g %.9g %.9g  %.9g %.9g %.9g  %.9g %.9g %.9g\n", k, c.position.x,
+                             c.position.y, c.position.z, c.right.x, c.right.y, c.right.z, c.up.x, c.up.y, c.up.z, c.forward.x, c.forward.y,
+                             c.forward.z);
+                r.RenderTemporalFrame((uint32_t)spp, false);
+            }
+            r.Wait();
+            double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            std::fprintf(stderr, "%dx%d spp=%d bounces=%d: %d temporal frames, wall %.3f ms\n", W, H, spp, bounces, temporal, wall * 1e3);
+            r.ReadFramebuffer(fb.data(), (size_t)W * 4);
+            if (write_ppm(fb, out)) return 1;
+            if (!gbuffer.empty() && write_gbuffers(r, gbuffer, W, H)) return 1;
+            if (!denoise.empty()) {
+                // the last frame's accumulator (the reprojected result) through the denoiser, as RenderTemporalFrame(spp, true) does
+                srt_denoise_params dp{};
+                srt_denoise_params_default(&dp);
+                dp.flags |= SRT_DENOISE_FRAMEBUFFER;
+                r.RenderGBuffer(SRT_GBUF_ALL);
+                r.Denoise(dp);
+                r.ReadFramebuffer(fb.data(), (size_t)W * 4);
+                if (write_ppm(fb, denoise)) return 1;
+            }
+            return 0;
+        }
         auto t0 = std::chrono::steady_clock::now();
         r.RenderSamples((uint32_t)spp, true);
         r.Wait();

@@ -26,6 +26,9 @@
 // and, standing in for the inspector's "Settings" (:461-483):
 //   M  switch render mode (SIMPLEDRAW)     F / G  FOV -/+ 1 (15..103)     B / N  light bounces -/+ 1
 //   1..4  render scale 0.25 / 0.5 / 0.75 / 1.0 (clamped to 0.5 in preview mode, :481-483)
+//   T  temporal mode (not in the reference): every frame is a full path-traced frame of one sample
+//      (PathTraceRenderer::RenderTemporalFrame) that keeps its samples across camera moves by reprojection; there, turning
+//      and moving the camera do not call Invalidate(), every other edit still does (and so does toggling T)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -52,7 +55,7 @@ struct InputState {  // one frame's worth, what SDLInputManager hands the loop
     int mouse_dx = 0, mouse_dy = 0;  // relative motion of this frame
     bool left_down = false;          // edge
     int mouse_x = 0, mouse_y = 0;    // window coordinates of the click, y down
-    std::string pressed;             // key-down edges of this frame: any of "PMFGBN1234X" (X = DELETE)
+    std::string pressed;             // key-down edges of this frame: any of "PMFGBN1234XT" (X = DELETE)
 };
 
 class ViewerCore {
@@ -64,6 +67,7 @@ class ViewerCore {
     }
     PathTraceRenderer& renderer() { return r_; }
     bool paused() const { return pause_; }
+    bool temporal() const { return temporal_; }
     int selected() const { return r_.selectedObject; }
 
     // one pass of the loop body between "thread safe after this point" (:385) and the release of the
@@ -72,7 +76,7 @@ class ViewerCore {
         const float mouseSpeed = .08f, moveSpeed = 1;  // :353-354
         for (char k : in.pressed) Key(k);
         if (in.right_held) {  // :390-396
-            r_.Invalidate();
+            if (!temporal_) r_.Invalidate();
             r_.camera.RotateAboutAxis((float)(in.mouse_dx * mouseSpeed * 0.03), Vec3(0, 1, 0));
             r_.camera.RotateAboutAxis((float)(in.mouse_dy * mouseSpeed * 0.03), r_.camera.right);
         }
@@ -86,18 +90,20 @@ class ViewerCore {
         if (in.s) p = p - r_.camera.forward * speed;
         if (in.e) p = p + r_.camera.up * speed;
         if (in.q) p = p - r_.camera.up * speed;
-        if (p.x != before.x || p.y != before.y || p.z != before.z) r_.Invalidate();  // :519-521
+        if ((p.x != before.x || p.y != before.y || p.z != before.z) && !temporal_) r_.Invalidate();  // :519-521
         if (in.left_down) {  // :525-541
             if (r_.selectedObject >= 0) r_.selectedObject = -1;
             else r_.selectedObject = r_.Pick(in.mouse_x, in.mouse_y);
         }
-        r_.RenderFrame();  // :572-595
+        if (temporal_) r_.RenderTemporalFrame(1, false);
+        else r_.RenderFrame();  // :572-595
     }
 
    private:
     void Key(char k) {
         switch (k) {
             case 'P': pause_ = !pause_; break;                                     // :386-388
+            case 'T': temporal_ = !temporal_; r_.Invalidate(); break;
             case 'M': r_.SIMPLEDRAW = !r_.SIMPLEDRAW; r_.Invalidate(); break;      // :462-465
             case 'F': case 'G': {                                                  // :468-473
                 int f = r_.FOV + (k == 'G' ? 1 : -1);
@@ -126,6 +132,7 @@ class ViewerCore {
     Scene scene_;
     PathTraceRenderer r_;
     bool pause_ = false;
+    bool temporal_ = false;
 };
 
 void write_ppm(PathTraceRenderer& r, const std::string& path) {
@@ -142,9 +149,9 @@ void write_ppm(PathTraceRenderer& r, const std::string& path) {
 
 // Script of the headless back end, one command per line ('#' starts a comment):
 //   delta SECONDS | hold KEYS | release KEYS   (KEYS out of W A S D E Q and L for LSHIFT)
-//   press KEYS (P M F G B N 1 2 3 4 X, applied to the next frame only)
+//   press KEYS (P M F G B N 1 2 3 4 X T, applied to the next frame only)
 //   rmb down|up | move DX DY (relative mouse motion of the next frame) | click X Y
-//   frames N | save FILE.ppm | print
+//   frames N | save FILE.ppm | print | camera (position, right, up, forward and temporal mode, exactly: %.9g)
 int run_script(ViewerCore& core, std::istream& script) {
     InputState in;
     float delta = 1.0f / 60.0f;
@@ -180,6 +187,11 @@ int run_script(ViewerCore& core, std::istream& script) {
             std::printf("frames %d acc %d simpledraw %d fov %d bounces %d scale %.2f selected %d pos %.9g %.9g %.9g fwd %.9g %.9g %.9g paused %d\n", frames_run,
                         r.ACCUMULATIONFRAMES, (int)r.SIMPLEDRAW, r.FOV, r.MAXBOUNCES, r.SCREEN_SCALE, core.selected(), r.camera.position.x, r.camera.position.y,
                         r.camera.position.z, r.camera.forward.x, r.camera.forward.y, r.camera.forward.z, (int)core.paused());
+        } else if (cmd == "camera") {
+            const Transform& c = core.renderer().camera;
+            std::printf("camera %.9g %.9g %.9g  %.9g %.9g %.9g  %.9g %.9g %.9g  %.9g %.9g %.9g temporal %d\n", c.position.x, c.position.y,
+                        c.position.z, c.right.x, c.right.y, c.right.z, c.up.x, c.up.y, c.up.z, c.forward.x, c.forward.y, c.forward.z,
+                        (int)core.temporal());
         } else {
             std::fprintf(stderr, "script: unknown command '%s'\n", cmd.c_str());
             return 2;
@@ -223,7 +235,7 @@ int run_window(ViewerCore& core) {
                     case SDL_SCANCODE_B: in.pressed += 'B'; break; case SDL_SCANCODE_N: in.pressed += 'N'; break;
                     case SDL_SCANCODE_1: in.pressed += '1'; break; case SDL_SCANCODE_2: in.pressed += '2'; break;
                     case SDL_SCANCODE_3: in.pressed += '3'; break; case SDL_SCANCODE_4: in.pressed += '4'; break;
-                    case SDL_SCANCODE_DELETE: in.pressed += 'X'; break; case SDL_SCANCODE_ESCAPE: quit = true; break;
+                    case SDL_SCANCODE_DELETE: in.pressed += 'X'; break; case SDL_SCANCODE_T: in.pressed += 'T'; break; case SDL_SCANCODE_ESCAPE: quit = true; break;
                     default: break;
                 }
             }
