@@ -89,55 +89,97 @@ struct HostCamera {
     bool set = false;
 };
 
+// Owners of one HIP resource each: the destructor frees it, with the context's device current (srt_destroy sets it).
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy&) = delete;
+    NoCopy& operator=(const NoCopy&) = delete;
+};
+
+// Device (or pinned host) memory.  ensure(bytes) allocates when the buffer is empty or smaller than bytes, without keeping the old
+// contents; after a failure the buffer is empty.
+template <class T, bool PINNED = false>
+class Buffer : NoCopy {
+  public:
+    ~Buffer() { reset(); }
+    operator T*() const { return p_; }
+    size_t bytes() const { return bytes_; }
+    void reset() {
+        if (p_) (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr, bytes_ = 0;
+    }
+    hipError_t ensure(size_t bytes) {
+        if (p_ && bytes <= bytes_) return hipSuccess;
+        reset();
+        const hipError_t e = PINNED ? hipHostMalloc((void**)&p_, bytes, hipHostMallocDefault) : hipMalloc((void**)&p_, bytes);
+        if (e == hipSuccess) bytes_ = bytes;
+        else p_ = nullptr;
+        return e;
+    }
+
+  private:
+    T* p_ = nullptr;
+    size_t bytes_ = 0;
+};
+template <class T> using DeviceBuffer = Buffer<T>;
+template <class T> using PinnedBuffer = Buffer<T, true>;
+
+// An event or stream, created into h.
+template <class H, hipError_t (*DESTROY)(H)>
+struct Handle : NoCopy {
+    H h = nullptr;
+    ~Handle() { if (h) (void)DESTROY(h); }
+    operator H() const { return h; }
+};
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+
 }  // namespace
 
+// Members are destroyed in reverse order: the buffers and events first, the own stream last.
 struct srt_context {
     int device = 0;
     int width = 0, height = 0;
-    hipStream_t own_stream = nullptr;
+    Stream own_stream;
     hipStream_t stream = nullptr;  // launch stream (own or caller's)
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    Event ev_begin, ev_end;
     bool launched = false;
 
     // device buffers
     // two images of the same scene: [0] clustered (default), [1] plain brute force (A/B aid)
-    float4* d_scene[2] = {nullptr, nullptr};
-    size_t scene_capacity_vec4[2] = {0, 0};
+    DeviceBuffer<float4> d_scene[2];
     srt::SceneLayout layout[2];
     bool scene_set = false;
     std::vector<float4> h_scene[2];  // staging for the async upload
 
-    uint32_t* d_fb_own = nullptr;
-    float4* d_acc_own = nullptr;
+    DeviceBuffer<uint32_t> d_fb_own;
+    DeviceBuffer<float4> d_acc_own;
     uint32_t* d_fb = nullptr;
     float4* d_acc = nullptr;
-    unsigned long long* d_rays = nullptr;
-    unsigned long long* d_work = nullptr;  // SRT_RENDER_COUNT_WORK: the launch's loop counts (srt::TALLY_ALL words)
-    int* d_pick = nullptr;
+    DeviceBuffer<unsigned long long> d_rays;
+    DeviceBuffer<unsigned long long> d_work;  // SRT_RENDER_COUNT_WORK: the launch's loop counts (srt::TALLY_ALL words)
+    DeviceBuffer<int> d_pick;
     int last_pick[4] = {0, 0, 0, 0};  // list index, distance bits, primitive id, normal.z bits (debug)
 
     // EXTENSION: triangle meshes
     std::vector<srt::HostMesh> meshes;
     srt::MeshImage mesh_image;
-    float4* d_bvh_nodes = nullptr;
-    float4* d_bvh_tris = nullptr;
-    int32_t* d_bvh_gidpos = nullptr;
+    DeviceBuffer<float4> d_bvh_nodes;
+    DeviceBuffer<float4> d_bvh_tris;
+    DeviceBuffer<int32_t> d_bvh_gidpos;
 
     // sample-chunked launches (narrow row bands at high sample counts): sample colours + per-tile masks
-    float4* d_samples = nullptr;
-    size_t samples_capacity = 0;  // bytes
-    unsigned long long* d_tile_masks = nullptr;
-    size_t tile_masks_capacity = 0;  // entries
-    uint32_t* d_tile_chain = nullptr;  // sample-chunked launches: chunks of a tile folded in order so far (KernelParams.tile_chain), same capacity
+    DeviceBuffer<float4> d_samples;
+    DeviceBuffer<unsigned long long> d_tile_masks;
+    DeviceBuffer<uint32_t> d_tile_chain;  // sample-chunked launches: chunks of a tile folded in order so far (KernelParams.tile_chain)
 
     // cost-ordered dispatch: a launch may record the ray count of every block of tiles; once that copy has
     // arrived (polled, never waited for) later launches of the same grid start the expensive blocks first
-    uint32_t* d_wg_cost = nullptr;
-    uint32_t* d_wg_est = nullptr;    // estimated block costs (block_cost_kernel), input of order_sort_kernel
-    uint32_t* d_wg_order = nullptr;
-    uint32_t* h_wg_cost = nullptr;   // pinned
-    uint32_t* h_wg_order = nullptr;  // pinned
-    size_t wg_capacity = 0;
+    DeviceBuffer<uint32_t> d_wg_cost;
+    DeviceBuffer<uint32_t> d_wg_est;  // estimated block costs (block_cost_kernel), input of order_sort_kernel
+    DeviceBuffer<uint32_t> d_wg_order;
+    PinnedBuffer<uint32_t> h_wg_cost;
+    PinnedBuffer<uint32_t> h_wg_order;
     unsigned order_gx = 0, order_gy = 0;  // grid the order in d_wg_order was made for (0 = none)
     unsigned rec_gx = 0, rec_gy = 0;      // grid of the recording in flight
     bool recording = false;               // a cost copy is in flight (ev_cost)
@@ -151,7 +193,7 @@ struct srt_context {
     int band_y0 = -1, band_rows = -1;     // the row band the order, the recording and the cost figures above belong to
     bool estimate_stale = true;           // the scene changed since the order was last estimated on the device
     bool order_disabled = false;          // buffers for the feedback could not be allocated
-    hipEvent_t ev_cost = nullptr, ev_order = nullptr, ev_gather = nullptr, ev_read = nullptr;
+    Event ev_cost, ev_order, ev_gather, ev_read;
     unsigned long long peer_asked = 0;    // srt_gather_band: destination devices this context has asked hipDeviceCanAccessPeer about (once per pair)
     unsigned long long peer_direct = 0;   // ... and those it may reach directly (peer access enabled)
     char gather_path[160] = "no gather yet";  // which way this context's last srt_gather_band went (srt_gather_path)
@@ -188,14 +230,14 @@ struct srt_context {
 
     // first-hit buffers (srt_render_gbuffer), one slot per SRT_GBUF_* bit: the handle's own (allocated on first use) and the
     // caller's bound one (srt_bind_gbuffer; NULL = own)
-    void* d_gbuf_own[4] = {nullptr, nullptr, nullptr, nullptr};
+    DeviceBuffer<void> d_gbuf_own[4];
     void* d_gbuf_bound[4] = {nullptr, nullptr, nullptr, nullptr};
 
     // denoiser (srt_denoise): the handle's own result buffer and the ping-pong buffer of the preparation pass and the levels
     // before the last (both allocated on first use), the caller's bound result buffer (srt_bind_denoised; NULL = own), and whether a denoise has been
     // enqueued yet (srt_read_denoised before that is SRT_ERR_STATE)
-    float4* d_dn_own = nullptr;
-    float4* d_dn_tmp = nullptr;
+    DeviceBuffer<float4> d_dn_own;
+    DeviceBuffer<float4> d_dn_tmp;
     float4* d_dn_bound = nullptr;
     bool dn_written = false;
 
@@ -206,7 +248,7 @@ struct srt_context {
     // temporal reprojection (srt_temporal_accumulate): two history slots of three W*H float4 arrays each (allocated on first
     // use), the slot the last call wrote and the camera it was written with, whether that history may be reprojected (false
     // after a scene, mesh or environment change), and whether any call has been enqueued yet (srt_read_history_length)
-    float4* d_tp[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    DeviceBuffer<float4> d_tp[2][3];
     int tp_cur = 0;
     srt_camera tp_cam{};
     bool tp_valid = false;
@@ -235,6 +277,24 @@ int fail(srt_context* ctx, int code, const char* fmt, ...) {
     } while (0)
 
 float clamp0h(float v) { return v < 0 ? 0.0f : v; }
+
+// the context's device made current and everything enqueued on its stream finished
+int finish_stream(srt_context* ctx) {
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SRT_OK;
+}
+
+// the buffer a first-hit output or the denoised image lives in: the caller's bound one, else the handle's own (NULL before its first use)
+template <class T>
+T* bound_or_own(T* bound, const DeviceBuffer<T>& own) {
+    return bound ? bound : (T*)own;
+}
+
+// the full frame in workgroups of 2 x 2 waves, one wave per 8 x 8 tile
+dim3 frame_tile_grid(const srt_context* ctx) {
+    return dim3((unsigned)((ctx->width + srt::WG_W - 1) / srt::WG_W), (unsigned)((ctx->height + srt::WG_H - 1) / srt::WG_H));
+}
 
 }  // namespace
 
@@ -302,16 +362,16 @@ int srt_create(int device, int width, int height, srt_context** out) {
         return code;
     };
     if ((e = hipSetDevice(device)) != hipSuccess) return bail(e, "hipSetDevice");
-    if ((e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
+    if ((e = hipStreamCreateWithFlags(&ctx->own_stream.h, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
     ctx->stream = ctx->own_stream;
-    if ((e = hipEventCreate(&ctx->ev_begin)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipEventCreate(&ctx->ev_end)) != hipSuccess) return bail(e, "hipEventCreate");
+    if ((e = hipEventCreate(&ctx->ev_begin.h)) != hipSuccess) return bail(e, "hipEventCreate");
+    if ((e = hipEventCreate(&ctx->ev_end.h)) != hipSuccess) return bail(e, "hipEventCreate");
     const size_t px = (size_t)width * height;
-    if ((e = hipMalloc((void**)&ctx->d_fb_own, px * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMalloc framebuffer");
-    if ((e = hipMalloc((void**)&ctx->d_acc_own, px * sizeof(float4))) != hipSuccess) return bail(e, "hipMalloc accumulator");
-    if ((e = hipMalloc((void**)&ctx->d_rays, sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc counter");
-    if ((e = hipMalloc((void**)&ctx->d_pick, 4 * sizeof(int))) != hipSuccess) return bail(e, "hipMalloc pick");
-    if ((e = hipMalloc((void**)&ctx->d_work, srt::TALLY_ALL * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc work counters");
+    if ((e = ctx->d_fb_own.ensure(px * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMalloc framebuffer");
+    if ((e = ctx->d_acc_own.ensure(px * sizeof(float4))) != hipSuccess) return bail(e, "hipMalloc accumulator");
+    if ((e = ctx->d_rays.ensure(sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc counter");
+    if ((e = ctx->d_pick.ensure(4 * sizeof(int))) != hipSuccess) return bail(e, "hipMalloc pick");
+    if ((e = ctx->d_work.ensure(srt::TALLY_ALL * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc work counters");
     if ((e = hipMemsetAsync(ctx->d_fb_own, 0, px * sizeof(uint32_t), ctx->stream)) != hipSuccess) return bail(e, "hipMemset");
     if ((e = hipMemsetAsync(ctx->d_acc_own, 0, px * sizeof(float4), ctx->stream)) != hipSuccess) return bail(e, "hipMemset");
     if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
@@ -330,39 +390,7 @@ int srt_destroy(srt_context* ctx) {
     if (!ctx) return SRT_OK;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (int i = 0; i < 2; ++i)
-        if (ctx->d_scene[i]) (void)hipFree(ctx->d_scene[i]);
-    if (ctx->d_fb_own) (void)hipFree(ctx->d_fb_own);
-    if (ctx->d_acc_own) (void)hipFree(ctx->d_acc_own);
-    if (ctx->d_rays) (void)hipFree(ctx->d_rays);
-    if (ctx->d_work) (void)hipFree(ctx->d_work);
-    if (ctx->d_bvh_nodes) (void)hipFree(ctx->d_bvh_nodes);
-    if (ctx->d_bvh_tris) (void)hipFree(ctx->d_bvh_tris);
-    if (ctx->d_bvh_gidpos) (void)hipFree(ctx->d_bvh_gidpos);
-    if (ctx->d_pick) (void)hipFree(ctx->d_pick);
-    if (ctx->d_samples) (void)hipFree(ctx->d_samples);
-    if (ctx->d_wg_cost) (void)hipFree(ctx->d_wg_cost);
-    if (ctx->d_wg_est) (void)hipFree(ctx->d_wg_est);
-    if (ctx->d_wg_order) (void)hipFree(ctx->d_wg_order);
-    if (ctx->h_wg_cost) (void)hipHostFree(ctx->h_wg_cost);
-    if (ctx->h_wg_order) (void)hipHostFree(ctx->h_wg_order);
-    if (ctx->ev_cost) (void)hipEventDestroy(ctx->ev_cost);
-    if (ctx->ev_order) (void)hipEventDestroy(ctx->ev_order);
-    if (ctx->ev_gather) (void)hipEventDestroy(ctx->ev_gather);
-    if (ctx->ev_read) (void)hipEventDestroy(ctx->ev_read);
-    if (ctx->d_tile_masks) (void)hipFree(ctx->d_tile_masks);
-    if (ctx->d_tile_chain) (void)hipFree(ctx->d_tile_chain);
-    for (int i = 0; i < 4; ++i)
-        if (ctx->d_gbuf_own[i]) (void)hipFree(ctx->d_gbuf_own[i]);
-    if (ctx->d_dn_own) (void)hipFree(ctx->d_dn_own);
-    if (ctx->d_dn_tmp) (void)hipFree(ctx->d_dn_tmp);
-    for (int i = 0; i < 2; ++i)
-        for (int k = 0; k < 3; ++k)
-            if (ctx->d_tp[i][k]) (void)hipFree(ctx->d_tp[i][k]);
-    if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
-    if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;  // (the members free their resources)
     return SRT_OK;
 }
 
@@ -403,12 +431,7 @@ static int set_scene_impl(srt_context* ctx, const srt_object* objects, size_t co
         const size_t mesh_scratch = has_mesh ? (size_t)(srt::WG_MESH_SCRATCH_BYTES) : 0;
         ctx->scene_in_lds[v] = L.radii_in_sqrt_window && image_bytes + (size_t)srt::WG_SCRATCH_BYTES + mesh_scratch <= (size_t)ctx->lds_limit_bytes;
         ctx->pick_in_lds[v] = L.radii_in_sqrt_window && image_bytes + srt::WAVE_SCRATCH_BYTES + srt::MESH_WAVE_BYTES <= (size_t)ctx->lds_limit_bytes;
-        if (ctx->h_scene[v].size() > ctx->scene_capacity_vec4[v] || !ctx->d_scene[v]) {
-            if (ctx->d_scene[v]) SRT_HIP(ctx, hipFree(ctx->d_scene[v]));
-            ctx->d_scene[v] = nullptr;
-            SRT_HIP(ctx, hipMalloc((void**)&ctx->d_scene[v], ctx->h_scene[v].size() * sizeof(float4)));
-            ctx->scene_capacity_vec4[v] = ctx->h_scene[v].size();
-        }
+        SRT_HIP(ctx, ctx->d_scene[v].ensure(ctx->h_scene[v].size() * sizeof(float4)));
         SRT_HIP(ctx, hipMemcpyAsync(ctx->d_scene[v], ctx->h_scene[v].data(), ctx->h_scene[v].size() * sizeof(float4),
                                     hipMemcpyHostToDevice, ctx->stream));
         ctx->layout[v] = L;
@@ -423,11 +446,10 @@ static int set_scene_impl(srt_context* ctx, const srt_object* objects, size_t co
             return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: %llu mesh triangles exceed the limit of 2^24 - 1 per scene", total_tris);
     }
     srt::build_mesh_image(objects, count, ctx->meshes, ctx->layout[0].nsT + ctx->layout[0].nb, ctx->mesh_image);
-    if (ctx->d_bvh_nodes) SRT_HIP(ctx, hipFree(ctx->d_bvh_nodes));
-    if (ctx->d_bvh_tris) SRT_HIP(ctx, hipFree(ctx->d_bvh_tris));
-    if (ctx->d_bvh_gidpos) SRT_HIP(ctx, hipFree(ctx->d_bvh_gidpos));
-    ctx->d_bvh_nodes = ctx->d_bvh_tris = nullptr;
-    ctx->d_bvh_gidpos = nullptr;
+    // (allocated to size for every scene, not grown)
+    ctx->d_bvh_nodes.reset();
+    ctx->d_bvh_tris.reset();
+    ctx->d_bvh_gidpos.reset();
     if (ctx->mesh_image.n_tris > 0) {
         // strict depth-first traversal (the kernel's last resort) keeps at most 7 entries per level
         if (7 * ctx->mesh_image.max_depth + 80 > srt::MESH_Q)
@@ -437,13 +459,13 @@ static int set_scene_impl(srt_context* ctx, const srt_object* objects, size_t co
         for (int ax = 0; ax < 3; ++ax)  // keeps cell * slope finite in the kernel's plane distances
             if (!(fabsf(ctx->mesh_image.center[ax]) + ctx->mesh_image.half[ax] <= 1e9f))
                 return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: mesh coordinates beyond 1e9 are not supported");
-        SRT_HIP(ctx, hipMalloc((void**)&ctx->d_bvh_nodes, ctx->mesh_image.nodes.size() * sizeof(float4)));
-        SRT_HIP(ctx, hipMalloc((void**)&ctx->d_bvh_tris, ctx->mesh_image.tris.size() * sizeof(float4)));
+        SRT_HIP(ctx, ctx->d_bvh_nodes.ensure(ctx->mesh_image.nodes.size() * sizeof(float4)));
+        SRT_HIP(ctx, ctx->d_bvh_tris.ensure(ctx->mesh_image.tris.size() * sizeof(float4)));
         SRT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh_nodes, ctx->mesh_image.nodes.data(), ctx->mesh_image.nodes.size() * sizeof(float4),
                                     hipMemcpyHostToDevice, ctx->stream));
         SRT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh_tris, ctx->mesh_image.tris.data(), ctx->mesh_image.tris.size() * sizeof(float4),
                                     hipMemcpyHostToDevice, ctx->stream));
-        SRT_HIP(ctx, hipMalloc((void**)&ctx->d_bvh_gidpos, ctx->mesh_image.gidpos.size() * sizeof(int32_t)));
+        SRT_HIP(ctx, ctx->d_bvh_gidpos.ensure(ctx->mesh_image.gidpos.size() * sizeof(int32_t)));
         SRT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh_gidpos, ctx->mesh_image.gidpos.data(), ctx->mesh_image.gidpos.size() * sizeof(int32_t),
                                     hipMemcpyHostToDevice, ctx->stream));
     }
@@ -529,8 +551,7 @@ int srt_set_camera(srt_context* ctx, const srt_camera* camera) {
 
 int srt_set_stream(srt_context* ctx, void* hip_stream) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = finish_stream(ctx)) return rc;
     ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
     return SRT_OK;
 }
@@ -574,7 +595,13 @@ static void fold_camera(const srt_camera& c, int W, int H, float* right_rd, floa
     }
 }
 
-static int fill_kernel_params(srt_context* ctx, const srt_render_params* p, srt::KernelParams& K, size_t& lds_bytes, int& use, int& img) {
+struct KernelSetup {
+    size_t lds_bytes;  // of a pathtrace_kernel workgroup
+    int use;           // tuning variant (srt_debug_set_variant, SRT_KERNEL)
+    int img;           // scene image: 0 clustered, 1 plain brute force
+};
+
+static KernelSetup fill_kernel_params(srt_context* ctx, const srt_render_params* p, srt::KernelParams& K) {
     const int W = ctx->width, H = ctx->height;
     memset(&K, 0, sizeof K);
     const srt_camera& c = ctx->camera.cam;
@@ -595,8 +622,8 @@ static int fill_kernel_params(srt_context* ctx, const srt_render_params* p, srt:
     K.steps = p->steps > 1 ? p->steps : 1;
     K.stripe_width = p->stripe_width > 0 ? p->stripe_width : 0;
     K.selected = p->selected_object;
-    use = ctx->variant >= 0 ? ctx->variant : dev_switches().kernel;
-    img = (use == 2) ? 1 : 0;  // variant 2: plain brute-force image
+    const int use = ctx->variant >= 0 ? ctx->variant : dev_switches().kernel;
+    const int img = (use == 2) ? 1 : 0;  // variant 2: plain brute-force image
     K.mesh_defer = use >= 100 && use < 200 ? use - 100 : 12;  // variants 100 + n: mesh phases wait for n rays
     K.mesh_wait = use >= 200 && use < 300 ? use - 200 : 3;   // variants 200 + w: ... for at most w steps
     if (use >= 300 && use < 500) K.mesh_defer = (use - 300) / 10, K.mesh_wait = (use - 300) % 10;  // variants 300 + 10 n + w: both
@@ -628,9 +655,9 @@ static int fill_kernel_params(srt_context* ctx, const srt_render_params* p, srt:
     K.framebuffer = ctx->d_fb;
     K.ray_counter = ctx->d_rays;
 
-    lds_bytes = (ctx->scene_in_lds[img] ? (size_t)(SL.total_vec4 > 0 ? SL.total_vec4 : 1) * sizeof(float4) : 0) +
-                srt::WG_SCRATCH_BYTES + (ctx->mesh_image.n_tris > 0 ? srt::WG_MESH_SCRATCH_BYTES : 0);
-    return SRT_OK;
+    const size_t lds_bytes = (ctx->scene_in_lds[img] ? (size_t)(SL.total_vec4 > 0 ? SL.total_vec4 : 1) * sizeof(float4) : 0) +
+                             srt::WG_SCRATCH_BYTES + (ctx->mesh_image.n_tris > 0 ? srt::WG_MESH_SCRATCH_BYTES : 0);
+    return KernelSetup{lds_bytes, use, img};
 }
 
 // What a block costs, from its counts: the weights are wave instructions per trip of the loop counted (a pool step costs its fixed
@@ -666,6 +693,7 @@ static double probe_block_cost(const uint32_t* c, const srt::KernelParams& K, co
 static int consume_record(srt_context* ctx) {
     ctx->recording = false;
     const size_t n = (size_t)ctx->rec_gx * ctx->rec_gy;
+    const uint32_t* const cost = ctx->h_wg_cost;
     if (ctx->order_gx) (void)hipEventSynchronize(ctx->ev_order);  // (long done) the previous upload read h_wg_order
     // linear buckets between the cheapest and the dearest block, expensive first; the counting sort
     // keeps the spatial order inside a bucket
@@ -674,7 +702,7 @@ static int consume_record(srt_context* ctx) {
     // natural order: nothing to gain, and neighbouring blocks stay together
     bool uniform = false;
     {
-        std::vector<uint32_t> tmp(ctx->h_wg_cost, ctx->h_wg_cost + n);
+        std::vector<uint32_t> tmp(cost, cost + n);
         std::nth_element(tmp.begin(), tmp.begin() + n / 20, tmp.end());
         const double p05 = (double)tmp[n / 20];
         std::nth_element(tmp.begin(), tmp.begin() + (n - 1 - n / 20), tmp.end());
@@ -682,14 +710,14 @@ static int consume_record(srt_context* ctx) {
         uniform = p95 <= 1.5 * p05;
     }
     uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    for (size_t i = 0; i < n; ++i) lo = ctx->h_wg_cost[i] < lo ? ctx->h_wg_cost[i] : lo, hi = ctx->h_wg_cost[i] > hi ? ctx->h_wg_cost[i] : hi;
+    for (size_t i = 0; i < n; ++i) lo = cost[i] < lo ? cost[i] : lo, hi = cost[i] > hi ? cost[i] : hi;
     // the launch-shape record: behind the times, the loop counts of every wave (present when the recording launch kept them)
     ctx->work.clear();
-    if (ctx->rec_has_work) srt::weigh_record(ctx->h_wg_cost + n, n, ctx->rec_gx, ctx->rec_gy, ctx->rec_step_w, ctx->mesh_image.n_tris > 0, ctx->work);
+    if (ctx->rec_has_work) srt::weigh_record(cost + n, n, ctx->rec_gx, ctx->rec_gy, ctx->rec_step_w, ctx->mesh_image.n_tris > 0, ctx->work);
 #ifdef SRT_DEV
     if (getenv("SRT_DEBUG_CHUNKS")) {  // the time-based figures of round 3 next to the counted ones, for calibration
         double tsum = 0.0;
-        for (size_t i = 0; i < n; ++i) tsum += (double)ctx->h_wg_cost[i];
+        for (size_t i = 0; i < n; ++i) tsum += (double)cost[i];
         float ms = 0.0f;
         double tfill = 0.0;
         if (ctx->pending_timed && hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end) == hipSuccess && ms > 0.0f)
@@ -713,7 +741,7 @@ static int consume_record(srt_context* ctx) {
             const uint32_t head[10] = {0x53525452u, ctx->rec_gx, ctx->rec_gy, (uint32_t)ctx->band_y0, (uint32_t)ctx->band_rows, ms_bits, sw_bits,
                                        (uint32_t)ctx->cu_count, ctx->mesh_image.n_tris > 0 ? 1u : 0u, ctx->rec_has_work ? 1u : 0u};
             fwrite(head, 4, 10, f);
-            fwrite(ctx->h_wg_cost, 4, n * REC_WORDS, f);
+            fwrite(cost, 4, n * REC_WORDS, f);
             fclose(f);
         }
     }
@@ -721,9 +749,9 @@ static int consume_record(srt_context* ctx) {
     const double scale = hi > lo ? (double)(NB - 1) / (double)(hi - lo) : 0.0;
     auto bucket = [&](uint32_t c) { return (NB - 1) - (int)((double)(c - lo) * scale); };
     std::vector<size_t> start((size_t)NB + 1, 0);
-    for (size_t i = 0; i < n; ++i) ++start[(size_t)bucket(ctx->h_wg_cost[i]) + 1];
+    for (size_t i = 0; i < n; ++i) ++start[(size_t)bucket(cost[i]) + 1];
     for (int k = 0; k < NB; ++k) start[(size_t)k + 1] += start[(size_t)k];
-    for (size_t i = 0; i < n; ++i) ctx->h_wg_order[start[(size_t)bucket(ctx->h_wg_cost[i])]++] = (uint32_t)i;
+    for (size_t i = 0; i < n; ++i) ctx->h_wg_order[start[(size_t)bucket(cost[i])]++] = (uint32_t)i;
     if (uniform)
         for (size_t i = 0; i < n; ++i) ctx->h_wg_order[i] = (uint32_t)i;
     SRT_HIP(ctx, hipMemcpyAsync(ctx->d_wg_order, ctx->h_wg_order, n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -732,15 +760,12 @@ static int consume_record(srt_context* ctx) {
     return SRT_OK;
 }
 
-extern "C" {
-
-int srt_render(srt_context* ctx, const srt_render_params* p) {
+static int check_render_params(srt_context* ctx, const srt_render_params* p) {
     if (!ctx || !p) return SRT_ERR_INVALID_ARG;
     if (!ctx->scene_set) return fail(ctx, SRT_ERR_STATE, "srt_render: srt_set_scene has not been called");
     if (!ctx->camera.set) return fail(ctx, SRT_ERR_STATE, "srt_render: srt_set_camera has not been called");
-    const int W = ctx->width, H = ctx->height;
-    if (p->row_begin < 0 || p->row_end > H || p->row_begin >= p->row_end)
-        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render: bad row band [%d,%d) for height %d", p->row_begin, p->row_end, H);
+    if (p->row_begin < 0 || p->row_end > ctx->height || p->row_begin >= p->row_end)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render: bad row band [%d,%d) for height %d", p->row_begin, p->row_end, ctx->height);
     if (p->first_sample < 1 || p->sample_count < 1 || p->max_bounces < 0)
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render: first_sample/sample_count must be >= 1 and max_bounces >= 0");
     if (p->steps < 0 || p->stripe_width < 0)
@@ -749,20 +774,18 @@ int srt_render(srt_context* ctx, const srt_render_params* p) {
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render: sample_count is limited to 2^20 per call (render in several calls)");
     if ((uint64_t)p->first_sample + p->sample_count > 0x7fffffffull)
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render: sample index overflows int (ACCUMULATIONFRAMES is an int)");
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    return SRT_OK;
+}
 
-    srt::KernelParams K;
-    size_t lds_bytes = 0;
-    int use = 0;
-    int img = 0;
-    const int fill_rc = fill_kernel_params(ctx, p, K, lds_bytes, use, img);
-    if (fill_rc != SRT_OK) return fill_rc;
-    ctx->count_rays = (p->flags & SRT_RENDER_COUNT_RAYS) != 0;
-    if (ctx->count_rays) SRT_HIP(ctx, hipMemsetAsync(ctx->d_rays, 0, sizeof(unsigned long long), ctx->stream));
-    // The learned dispatch order, a cost copy in flight and the work record of the chunk rule describe ONE row band.  Another
-    // band of the same height has the same grid but other blocks behind every index: it starts from a fresh estimate, like a new
-    // scene.  (Found the hard way: a 270-row band of config 5 launched after its neighbour inherited "no sample chunks" and
-    // ran 46 ms instead of 12.)
+// The learned dispatch order, a cost copy in flight and the work record of the chunk rule describe ONE row band.  Another
+// band of the same height has the same grid but other blocks behind every index: it starts from a fresh estimate, like a new
+// scene.  (Found the hard way: a 270-row band of config 5 launched after its neighbour inherited "no sample chunks" and
+// ran 46 ms instead of 12.)
+// A record in flight is WAITED for (round 3 polled it): the launch after a recording launch always sees the record, whatever the
+// host's timing — so which launch of a sequence changes to the recorded shape and order does not vary from run to run.  The
+// wait ends when the recording launch does; it happens once per scene / camera / band change (a launch records only then),
+// and costs the one enqueue that could have overlapped that launch's tail.
+static int enter_band(srt_context* ctx, const srt::KernelParams& K) {
     if (K.y0 != ctx->band_y0 || K.rows != ctx->band_rows) {
         if (ctx->recording) (void)hipEventSynchronize(ctx->ev_cost);  // (nothing may still write h_wg_cost when the next record starts)
         ctx->band_y0 = K.y0, ctx->band_rows = K.rows;
@@ -771,28 +794,34 @@ int srt_render(srt_context* ctx, const srt_render_params* p) {
         ctx->recording = false;
         ctx->order_gx = ctx->order_gy = 0;
     }
-    // A record in flight is WAITED for (round 3 polled it): the launch after a recording launch always sees the record, whatever the
-    // host's timing — so which launch of a sequence changes to the recorded shape and order does not vary from run to run.  The
-    // wait ends when the recording launch does; it happens once per scene / camera / band change (a launch records only then),
-    // and costs the one enqueue that could have overlapped that launch's tail.
-    if (ctx->recording) {
-        SRT_HIP(ctx, hipEventSynchronize(ctx->ev_cost));
-        const int rc = consume_record(ctx);
-        if (rc != SRT_OK) return rc;
-    }
+    if (!ctx->recording) return SRT_OK;
+    SRT_HIP(ctx, hipEventSynchronize(ctx->ev_cost));
+    return consume_record(ctx);
+}
 
-    // Tile height: with few rows and many samples per pixel (a narrow stripe of a multi-GPU frame) 8-row
-    // tiles give too few workgroups to fill 256 CUs x 4 resident workgroups and leave nothing to balance
-    // the tail with; halve the tile (twice the workgroups, same lanes at work in each wave's path pool)
-    // until there are about four rounds of workgroups.  Results do not depend on the tiling.
-    // Progressive blocks (steps > 1): when every pixel of a block ends up with a value that one lane can produce — the
-    // launch starts the frame (all pixels of a block then hold the same running mean) or adds ONE sample (each pixel folds
-    // the block's colour into its own mean) — the launch's lanes are blocks, not pixels: 1 / steps^2 of the lanes, one
-    // ray per block, steps^2 pixel stores per lane (Raytracer.cpp:235-248).  Anything else (several samples onto an
-    // accumulated frame) keeps one lane per pixel with the block's ray traced once per wave tile.
-    const bool bgrid = K.steps > 1 && ((K.flags & SRT_RENDER_RESET) || p->sample_count == 1);
+// What srt_render's steps decide about its launch.
+struct RenderLaunch {
+    srt::LaunchShape shape;
+    bool bgrid = false;   // progressive blocks: one lane per block
+    bool defer = false;   // sample chunks (shape.chunks >= 2)
+    dim3 grid;
+    bool record = false;  // the launch records its blocks' costs
+};
+
+// Tile height: with few rows and many samples per pixel (a narrow stripe of a multi-GPU frame) 8-row
+// tiles give too few workgroups to fill 256 CUs x 4 resident workgroups and leave nothing to balance
+// the tail with; halve the tile (twice the workgroups, same lanes at work in each wave's path pool)
+// until there are about four rounds of workgroups.  Results do not depend on the tiling.
+// Progressive blocks (steps > 1): when every pixel of a block ends up with a value that one lane can produce — the
+// launch starts the frame (all pixels of a block then hold the same running mean) or adds ONE sample (each pixel folds
+// the block's colour into its own mean) — the launch's lanes are blocks, not pixels: 1 / steps^2 of the lanes, one
+// ray per block, steps^2 pixel stores per lane (Raytracer.cpp:235-248).  Anything else (several samples onto an
+// accumulated frame) keeps one lane per pixel with the block's ray traced once per wave tile.
+static int plan_launch(srt_context* ctx, const srt_render_params* p, srt::KernelParams& K, RenderLaunch& L) {
+    const int W = ctx->width;
+    L.bgrid = K.steps > 1 && ((K.flags & SRT_RENDER_RESET) || p->sample_count == 1);
     long long grid_w = W, grid_h = K.rows;
-    if (bgrid) {
+    if (L.bgrid) {
         const long long sw = K.stripe_width > 0 ? K.stripe_width : W;
         grid_w = ((W + sw - 1) / sw) * ((sw + K.steps - 1) / K.steps);
         grid_h = (K.y0 + K.rows - 1) / K.steps - K.y0 / K.steps + 1;  // block rows that meet the band (scene rows)
@@ -805,7 +834,7 @@ int srt_render(srt_context* ctx, const srt_render_params* p) {
     // the CPU (tests/native/shape_check.cpp).  The one thing outside it: whether the sample buffer can be had.
     srt::ShapeRequest req;
     req.grid_w = grid_w, req.grid_h = grid_h, req.rows = K.rows, req.sample_count = p->sample_count, req.steps = K.steps;
-    req.block_grid = bgrid, req.mesh = K.n_tris > 0, req.cu_count = ctx->cu_count;
+    req.block_grid = L.bgrid, req.mesh = K.n_tris > 0, req.cu_count = ctx->cu_count;
     srt::ShapeOverrides ov;
     ov.tile_h = dev_switches().tile_h, ov.defer = dev_switches().defer, ov.chunk_beta = dev_switches().chunk_beta;
     ov.no_taper = (dev_switches().kernel_flags & 0x400) != 0, ov.fill_min = SRT_FILL_MIN;
@@ -813,145 +842,140 @@ int srt_render(srt_context* ctx, const srt_render_params* p) {
     if (ctx->shape_defer >= -1) ov.defer = ctx->shape_defer;
     if (ctx->shape_no_taper >= 0) ov.no_taper = ctx->shape_no_taper != 0;
 #endif
-    srt::LaunchShape shape = srt::plan_launch_shape(req, &ctx->work, ov);
+    srt::LaunchShape& shape = L.shape;
+    shape = srt::plan_launch_shape(req, &ctx->work, ov);
 #ifdef SRT_DEV
     if (getenv("SRT_DEBUG_CHUNKS") && shape.source)
         fprintf(stderr, "chunks: dearest %.0f sum %.0f blocks %lld ratio %.3f fill %.3f -> %d layer(s) of %d\n", ctx->work.max, ctx->work.sum, shape.wg8, shape.ratio, shape.fill, shape.chunks, shape.chunk);
 #endif
-    const long long wg_x = shape.wg_x, wg8 = shape.wg8;
+    const size_t tiles = (size_t)shape.wg8 * srt::WG_TILES_X * srt::WG_TILES_Y;
     if (shape.chunks >= 2) {
         // Costs 1 KiB of HBM per tile and sample; falls back to small tiles when that is not available
-        const size_t tiles = (size_t)wg8 * srt::WG_TILES_X * srt::WG_TILES_Y;
         const size_t need = tiles * (size_t)p->sample_count * 64 * sizeof(float4);
         bool ok = need <= ((size_t)96 << 30);  // (a third of the 288 GB; 24 GB until round 3 — the sky half of config 5 at 4K x 1024 spp needs 67)
-        if (ok && need > ctx->samples_capacity) {  // growing: take at most a quarter of what is free
+        if (ok && need > ctx->d_samples.bytes()) {  // growing: take at most a quarter of what is free
             size_t free_b = 0, total_b = 0;
-            ok = hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= (free_b + ctx->samples_capacity) / 4;
+            ok = hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= (free_b + ctx->d_samples.bytes()) / 4;
         }
-        if (ok && need > ctx->samples_capacity) {
-            if (ctx->d_samples) (void)hipFree(ctx->d_samples);
-            ctx->d_samples = nullptr;
-            ctx->samples_capacity = 0;
-            if (hipMalloc((void**)&ctx->d_samples, need) == hipSuccess) ctx->samples_capacity = need;
-            else ok = false, (void)hipGetLastError();
-        }
-        if (ok && tiles > ctx->tile_masks_capacity) {
-            if (ctx->d_tile_masks) (void)hipFree(ctx->d_tile_masks);
-            if (ctx->d_tile_chain) (void)hipFree(ctx->d_tile_chain);
-            ctx->d_tile_masks = nullptr;
-            ctx->d_tile_chain = nullptr;
-            ctx->tile_masks_capacity = 0;
-            if (hipMalloc((void**)&ctx->d_tile_masks, tiles * sizeof(unsigned long long)) == hipSuccess &&
-                hipMalloc((void**)&ctx->d_tile_chain, tiles * sizeof(uint32_t)) == hipSuccess)
-                ctx->tile_masks_capacity = tiles;
-            else
-                ok = false, (void)hipGetLastError();
-        }
+        if (ok && (ctx->d_samples.ensure(need) != hipSuccess || ctx->d_tile_masks.ensure(tiles * sizeof(unsigned long long)) != hipSuccess ||
+                   ctx->d_tile_chain.ensure(tiles * sizeof(uint32_t)) != hipSuccess))
+            ok = false, (void)hipGetLastError();
         if (!ok) srt::shape_without_sample_buffer(shape);  // no room for the sample buffer: small tiles instead
     }
     srt::finish_launch_shape(shape, p->sample_count, ov);
-    const bool defer = shape.chunks >= 2;
-    const int tile_h = shape.tile_h, chunk = shape.chunk, chunks = shape.chunks;
-    const uint32_t shape_source = shape.source;
-    K.tile_h = tile_h;
-    K.chunk = defer ? chunk : 0;
+    L.defer = shape.chunks >= 2;
+    K.tile_h = shape.tile_h;
+    K.chunk = L.defer ? shape.chunk : 0;
     K.chunk_full = shape.chunk_full;
     K.sample_rows = ctx->d_samples;
     K.tile_masks = ctx->d_tile_masks;
     // chained chunks: a chunk that finds its tile's running mean at its own first sample folds its samples itself (srt_kernel.hip.h,
     // KernelParams.tile_chain); the counts start at zero
-    K.tile_chain = defer && dev_switches().chain ? ctx->d_tile_chain : nullptr;
-    K.chunk_layers = chunks;
+    K.tile_chain = L.defer && dev_switches().chain ? (uint32_t*)ctx->d_tile_chain : nullptr;
+    K.chunk_layers = shape.chunks;
 #ifdef SRT_DEV
     if (ctx->chain_mode == srt::DEV_CHAIN_OFF) K.tile_chain = nullptr;
     K.chain_mode = ctx->chain_mode, K.chain_arg = ctx->chain_arg;
-    if (defer) {
-        ctx->chain_layers = chunks, ctx->chain_chunk = chunk, ctx->chain_chunk_full = shape.chunk_full, ctx->chain_wg_x = (int)wg_x;
-        ctx->chain_tiles = (size_t)wg8 * srt::WG_TILES_X * srt::WG_TILES_Y;
+    if (L.defer) {
+        ctx->chain_layers = shape.chunks, ctx->chain_chunk = shape.chunk, ctx->chain_chunk_full = shape.chunk_full, ctx->chain_wg_x = (int)shape.wg_x;
+        ctx->chain_tiles = tiles;
         ctx->chain_used = K.tile_chain != nullptr;
         ctx->chain_used_mode = ctx->chain_mode, ctx->chain_used_arg = ctx->chain_arg;
     }
 #endif
-    if (K.tile_chain) SRT_HIP(ctx, hipMemsetAsync(K.tile_chain, 0, (size_t)wg8 * srt::WG_TILES_X * srt::WG_TILES_Y * sizeof(uint32_t), ctx->stream));
-    dim3 grid((unsigned)wg_x, (unsigned)((grid_h + tile_h * srt::WG_TILES_Y - 1) / (tile_h * srt::WG_TILES_Y)), (unsigned)chunks);
-    dim3 block(srt::WG_THREADS);
-    // Cost-ordered dispatch.  The hardware starts workgroups in linear order; with the natural order the
-    // last ones to start are whatever lies at the top of the band, and the chip idles while a few expensive
-    // blocks finish.  Starting blocks in order of decreasing cost (coarse buckets, so that neighbours stay
-    // together) removes most of that tail: Scene1 3.39 -> 3.25 ms, config 4 19.7 -> 17.5 ms.  Costs are
-    // the blocks' wave-cycles in the band's recording launch (the first after a scene, camera or band change), copied back
-    // asynchronously; the next srt_render of the handle waits for that copy (see above).  Any order gives the same image.
-    const bool order_env = dev_switches().lpt;
-    bool record = false;
-    const size_t nwg = (size_t)grid.x * grid.y;
-    const bool in_lds = ctx->scene_in_lds[img];
-    if (order_env && !ctx->order_disabled && nwg >= SRT_ORDER_MIN_WG && p->sample_count >= 4 && !(p->flags & SRT_RENDER_PREVIEW) && !bgrid) {
-        if (nwg > ctx->wg_capacity) {
-            SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_wg_cost) (void)hipFree(ctx->d_wg_cost);
-            if (ctx->d_wg_est) (void)hipFree(ctx->d_wg_est);
-            if (ctx->d_wg_order) (void)hipFree(ctx->d_wg_order);
-            if (ctx->h_wg_cost) (void)hipHostFree(ctx->h_wg_cost);
-            if (ctx->h_wg_order) (void)hipHostFree(ctx->h_wg_order);
-            ctx->d_wg_cost = ctx->d_wg_est = ctx->d_wg_order = ctx->h_wg_cost = ctx->h_wg_order = nullptr;
-            ctx->wg_capacity = 0;
-            ctx->order_gx = ctx->order_gy = 0;
-            ctx->recording = false;
-            // an optimisation must not be able to fail a render: if anything here cannot be had (pinned host
-            // memory, for one), the handle simply keeps the natural order from now on
-            // (cost buffers: the blocks' wave times, then the loop counts of every wave of every block)
-            const bool ok = hipMalloc((void**)&ctx->d_wg_cost, REC_WORDS * nwg * 4) == hipSuccess && hipMalloc((void**)&ctx->d_wg_order, nwg * 4) == hipSuccess &&
-                            hipMalloc((void**)&ctx->d_wg_est, 2 * nwg * 4) == hipSuccess &&  // raw + smoothed
-                            hipHostMalloc((void**)&ctx->h_wg_cost, REC_WORDS * nwg * 4, hipHostMallocDefault) == hipSuccess &&
-                            hipHostMalloc((void**)&ctx->h_wg_order, nwg * 4, hipHostMallocDefault) == hipSuccess &&
-                            (ctx->ev_cost || hipEventCreateWithFlags(&ctx->ev_cost, hipEventDisableTiming) == hipSuccess) &&
-                            (ctx->ev_order || hipEventCreateWithFlags(&ctx->ev_order, hipEventDisableTiming) == hipSuccess);
-            if (ok) {
-                ctx->wg_capacity = nwg;
-            } else {
-                (void)hipGetLastError();
-                ctx->order_disabled = true;
-            }
+    if (K.tile_chain) SRT_HIP(ctx, hipMemsetAsync(K.tile_chain, 0, tiles * sizeof(uint32_t), ctx->stream));
+    L.grid = dim3((unsigned)shape.wg_x, (unsigned)((grid_h + shape.tile_h * srt::WG_TILES_Y - 1) / (shape.tile_h * srt::WG_TILES_Y)), (unsigned)shape.chunks);
+    return SRT_OK;
+}
+
+// Cost-ordered dispatch.  The hardware starts workgroups in linear order; with the natural order the
+// last ones to start are whatever lies at the top of the band, and the chip idles while a few expensive
+// blocks finish.  Starting blocks in order of decreasing cost (coarse buckets, so that neighbours stay
+// together) removes most of that tail: Scene1 3.39 -> 3.25 ms, config 4 19.7 -> 17.5 ms.  Costs are
+// the blocks' wave-cycles in the band's recording launch (the first after a scene, camera or band change), copied back
+// asynchronously; the next srt_render of the handle waits for that copy (see enter_band).  Any order gives the same image.
+static int plan_cost_order(srt_context* ctx, const srt_render_params* p, srt::KernelParams& K, const KernelSetup& ks, RenderLaunch& L) {
+    const size_t nwg = (size_t)L.grid.x * L.grid.y;
+    const bool eligible = dev_switches().lpt && !ctx->order_disabled && nwg >= SRT_ORDER_MIN_WG && p->sample_count >= 4 &&
+                          !(p->flags & SRT_RENDER_PREVIEW) && !L.bgrid;
+    if (!eligible) return SRT_OK;
+    if (REC_WORDS * nwg * 4 > ctx->h_wg_cost.bytes()) {
+        SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (h_wg_cost may still be the target of a cost copy)
+        ctx->order_gx = ctx->order_gy = 0;
+        ctx->recording = false;
+        // an optimisation must not be able to fail a render: if anything here cannot be had (pinned host
+        // memory, for one), the handle simply keeps the natural order from now on
+        // (cost buffers: the blocks' wave times, then the loop counts of every wave of every block)
+        const bool ok = ctx->d_wg_cost.ensure(REC_WORDS * nwg * 4) == hipSuccess && ctx->d_wg_order.ensure(nwg * 4) == hipSuccess &&
+                        ctx->d_wg_est.ensure(2 * nwg * 4) == hipSuccess &&  // raw + smoothed
+                        ctx->h_wg_cost.ensure(REC_WORDS * nwg * 4) == hipSuccess && ctx->h_wg_order.ensure(nwg * 4) == hipSuccess &&
+                        (ctx->ev_cost || hipEventCreateWithFlags(&ctx->ev_cost.h, hipEventDisableTiming) == hipSuccess) &&
+                        (ctx->ev_order || hipEventCreateWithFlags(&ctx->ev_order.h, hipEventDisableTiming) == hipSuccess);
+        if (!ok) {
+            (void)hipGetLastError();
+            ctx->order_disabled = true;
+            return SRT_OK;
         }
     }
-    if (order_env && !ctx->order_disabled && ctx->wg_capacity >= nwg && nwg >= SRT_ORDER_MIN_WG && p->sample_count >= 4 && !(p->flags & SRT_RENDER_PREVIEW) && !bgrid) {
-        // No recorded costs for this frame yet (first launch, or the scene has changed): estimate the blocks'
-        // costs on the device — 16 one-sample probe paths per block, block_cost_kernel — and sort them there (order_sort_kernel);
-        // both run on the launch stream ahead of the frame, nothing comes back to the host.  Measured with warm clocks:
-        // first launch of a frame vs the learned order: config 4 +13 % -> see DESIGN.md, Scene1 +3 %.
-        if (dev_switches().host_order && (ctx->estimate_stale || ctx->order_gx != grid.x || ctx->order_gy != grid.y)) {
-            const size_t image_bytes = (size_t)(K.scene_vec4 > 0 ? K.scene_vec4 : 1) * sizeof(float4);
-            const size_t est_lds = (ctx->pick_in_lds[img] ? image_bytes : 0) + srt::WAVE_SCRATCH_BYTES + srt::MESH_WAVE_BYTES;
-            if (ctx->pick_in_lds[img])
-                hipLaunchKernelGGL(srt::block_cost_kernel<true>, dim3((unsigned)((nwg + 3) / 4)), dim3(64), est_lds, ctx->stream, K, ctx->d_wg_est, (int)grid.x, (int)nwg);
-            else
-                hipLaunchKernelGGL(srt::block_cost_kernel<false>, dim3((unsigned)((nwg + 3) / 4)), dim3(64), est_lds, ctx->stream, K, ctx->d_wg_est, (int)grid.x, (int)nwg);
-            hipLaunchKernelGGL(srt::smooth_cost_kernel, dim3((unsigned)((nwg + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_wg_est, ctx->d_wg_est + nwg, (int)nwg, (int)grid.x);
-            hipLaunchKernelGGL(srt::order_sort_kernel, dim3(1), dim3(srt::ORDER_SORT_THREADS), 0, ctx->stream, ctx->d_wg_est + nwg, ctx->d_wg_order, (int)nwg);
-            if (hipGetLastError() == hipSuccess) {
-                ctx->order_gx = grid.x, ctx->order_gy = grid.y;
-                ctx->estimate_stale = false;
-            } else {
-                ctx->order_gx = ctx->order_gy = 0;  // an optimisation must not fail the render: natural order
-            }
-        }
-        if (ctx->order_gx == grid.x && ctx->order_gy == grid.y) K.wg_order = ctx->d_wg_order;
-        if (ctx->order_stale || ctx->order_gx != grid.x || ctx->order_gy != grid.y) {  // (no record is in flight here: it was waited for above)
-            SRT_HIP(ctx, hipMemsetAsync(ctx->d_wg_cost, 0, REC_WORDS * nwg * 4, ctx->stream));
-            K.wg_cost = ctx->d_wg_cost;
-            K.wg_blocks = (uint32_t)nwg;
-            record = true;
+    // No recorded costs for this frame yet (first launch, or the scene has changed): estimate the blocks'
+    // costs on the device — 16 one-sample probe paths per block, block_cost_kernel — and sort them there (order_sort_kernel);
+    // both run on the launch stream ahead of the frame, nothing comes back to the host.  Measured with warm clocks:
+    // first launch of a frame vs the learned order: config 4 +13 % -> see DESIGN.md, Scene1 +3 %.
+    const dim3 grid = L.grid;
+    if (dev_switches().host_order && (ctx->estimate_stale || ctx->order_gx != grid.x || ctx->order_gy != grid.y)) {
+        const size_t image_bytes = (size_t)(K.scene_vec4 > 0 ? K.scene_vec4 : 1) * sizeof(float4);
+        const size_t est_lds = (ctx->pick_in_lds[ks.img] ? image_bytes : 0) + srt::WAVE_SCRATCH_BYTES + srt::MESH_WAVE_BYTES;
+        void (*const estimate)(srt::KernelParams, uint32_t*, int, int) = ctx->pick_in_lds[ks.img] ? srt::block_cost_kernel<true> : srt::block_cost_kernel<false>;
+        hipLaunchKernelGGL(estimate, dim3((unsigned)((nwg + 3) / 4)), dim3(64), est_lds, ctx->stream, K, ctx->d_wg_est, (int)grid.x, (int)nwg);
+        hipLaunchKernelGGL(srt::smooth_cost_kernel, dim3((unsigned)((nwg + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_wg_est, ctx->d_wg_est + nwg, (int)nwg, (int)grid.x);
+        hipLaunchKernelGGL(srt::order_sort_kernel, dim3(1), dim3(srt::ORDER_SORT_THREADS), 0, ctx->stream, ctx->d_wg_est + nwg, ctx->d_wg_order, (int)nwg);
+        if (hipGetLastError() == hipSuccess) {
+            ctx->order_gx = grid.x, ctx->order_gy = grid.y;
+            ctx->estimate_stale = false;
+        } else {
+            ctx->order_gx = ctx->order_gy = 0;  // an optimisation must not fail the render: natural order
         }
     }
-    // The TALLY instantiations keep the wave-uniform loop counts (srt_kernel.hip.h, Tally): the recording launch of a band (its
-    // blocks' work is the launch-shape record) and launches with SRT_RENDER_COUNT_WORK.  Scene images that live in HBM have none
-    // (a correctness fallback): such launches keep the static shape rule and report no work counts.
-    // (A recording launch keeps the counts only where the sample-chunk rule could ever read them — launches of the sample counts the
-    // rule applies to.  A 32-sample analytic frame, config 2, records its blocks' times with the plain instantiation: the counting
-    // one is 0..2 % slower, bench.py's kernel_ms_counting_launch, and that would be the frame's FIRST launch.)
+    if (ctx->order_gx == grid.x && ctx->order_gy == grid.y) K.wg_order = ctx->d_wg_order;
+    if (ctx->order_stale || ctx->order_gx != grid.x || ctx->order_gy != grid.y) {  // (no record is in flight here: it was waited for in enter_band)
+        SRT_HIP(ctx, hipMemsetAsync(ctx->d_wg_cost, 0, REC_WORDS * nwg * 4, ctx->stream));
+        K.wg_cost = ctx->d_wg_cost;
+        K.wg_blocks = (uint32_t)nwg;
+        L.record = true;
+    }
+    return SRT_OK;
+}
+
+// The nine pathtrace_kernel instantiations of one <MIN_WAVES, MESH> pair: scene image in LDS or HBM, full tiles / small tiles
+// (multi-sample hand-out) / sample chunks, with or without the loop counts.  All are bit-identical.  Each is named once, by the
+// comment that tests/test_gpu_paths.py reads.
+template <int MIN_WAVES, bool MESH>
+static void launch_pathtrace(bool tally, bool in_lds, bool multi, bool defer, dim3 grid, size_t lds_bytes, hipStream_t stream, const srt::KernelParams& K) {
+    using srt::pathtrace_kernel;
+    void (*const kernel)(srt::KernelParams) =
+        tally && defer    ? pathtrace_kernel<MIN_WAVES, MESH, true, false, true, false, true>   // t_lds_defer
+        : tally && multi  ? pathtrace_kernel<MIN_WAVES, MESH, true, true, false, false, true>   // t_lds_multi
+        : tally           ? pathtrace_kernel<MIN_WAVES, MESH, true, false, false, false, true>  // t_lds
+        : in_lds && defer ? pathtrace_kernel<MIN_WAVES, MESH, true, false, true>                // k_lds_defer
+        : in_lds && multi ? pathtrace_kernel<MIN_WAVES, MESH, true, true, false>                // k_lds_multi
+        : in_lds          ? pathtrace_kernel<MIN_WAVES, MESH, true, false, false>               // k_lds
+        : defer           ? pathtrace_kernel<MIN_WAVES, MESH, false, false, true>               // k_hbm_defer
+        : multi           ? pathtrace_kernel<MIN_WAVES, MESH, false, true, false>               // k_hbm_multi
+                          : pathtrace_kernel<MIN_WAVES, MESH, false, false, false>;             // k_hbm
+    hipLaunchKernelGGL(kernel, grid, dim3(srt::WG_THREADS), lds_bytes, stream, K);
+}
+
+// The TALLY instantiations keep the wave-uniform loop counts (srt_kernel.hip.h, Tally): the recording launch of a band (its
+// blocks' work is the launch-shape record) and launches with SRT_RENDER_COUNT_WORK.  Scene images that live in HBM have none
+// (a correctness fallback): such launches keep the static shape rule and report no work counts.
+// (A recording launch keeps the counts only where the sample-chunk rule could ever read them — launches of the sample counts the
+// rule applies to.  A 32-sample analytic frame, config 2, records its blocks' times with the plain instantiation: the counting
+// one is 0..2 % slower, bench.py's kernel_ms_counting_launch, and that would be the frame's FIRST launch.)
+static int launch_render(srt_context* ctx, const srt_render_params* p, srt::KernelParams& K, const KernelSetup& ks, const RenderLaunch& L) {
+    const bool in_lds = ctx->scene_in_lds[ks.img];
     const bool want_work = (p->flags & SRT_RENDER_COUNT_WORK) != 0;
     const bool rule_applies = (p->sample_count >= 64 || K.n_tris > 0) && p->sample_count >= 32 && K.steps <= 1;
-    const bool tally = ((record && rule_applies) || want_work) && in_lds;
+    const bool tally = ((L.record && rule_applies) || want_work) && in_lds;
     ctx->count_work = want_work;
     ctx->count_work_valid = want_work && tally;
     if (tally && want_work) {
@@ -960,66 +984,68 @@ int srt_render(srt_context* ctx, const srt_render_params* p) {
     }
     const bool timing = !(p->flags & SRT_RENDER_NO_TIMING);
     if (timing) SRT_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
-    // instantiation: mesh or not, scene image in LDS or HBM, full tiles / small tiles (multi-sample
-    // hand-out) / sample chunks, with or without the loop counts; variants 1 / 3 are a development aid for in-process A/B
-    // timing.  All are bit-identical.
-    const bool multi = tile_h < srt::TILE_H || (K.steps > 1 && !(K.flags & SRT_RENDER_PREVIEW)) || bgrid;
-    auto launch = [&](auto k_lds, auto k_lds_multi, auto k_lds_defer, auto k_hbm, auto k_hbm_multi, auto k_hbm_defer, auto t_lds, auto t_lds_multi, auto t_lds_defer) {
-        if (tally && defer) hipLaunchKernelGGL(t_lds_defer, grid, block, lds_bytes, ctx->stream, K);
-        else if (tally && multi) hipLaunchKernelGGL(t_lds_multi, grid, block, lds_bytes, ctx->stream, K);
-        else if (tally) hipLaunchKernelGGL(t_lds, grid, block, lds_bytes, ctx->stream, K);
-        else if (in_lds && defer) hipLaunchKernelGGL(k_lds_defer, grid, block, lds_bytes, ctx->stream, K);
-        else if (in_lds && multi) hipLaunchKernelGGL(k_lds_multi, grid, block, lds_bytes, ctx->stream, K);
-        else if (in_lds) hipLaunchKernelGGL(k_lds, grid, block, lds_bytes, ctx->stream, K);
-        else if (defer) hipLaunchKernelGGL(k_hbm_defer, grid, block, lds_bytes, ctx->stream, K);
-        else if (multi) hipLaunchKernelGGL(k_hbm_multi, grid, block, lds_bytes, ctx->stream, K);
-        else hipLaunchKernelGGL(k_hbm, grid, block, lds_bytes, ctx->stream, K);
-    };
-    if (K.n_tris > 0)  // EXTENSION: scenes with triangle meshes use the BVH-enabled instantiation
-        launch(srt::pathtrace_kernel<4, true, true, false, false>, srt::pathtrace_kernel<4, true, true, true, false>,
-               srt::pathtrace_kernel<4, true, true, false, true>, srt::pathtrace_kernel<4, true, false, false, false>,
-               srt::pathtrace_kernel<4, true, false, true, false>, srt::pathtrace_kernel<4, true, false, false, true>,
-               srt::pathtrace_kernel<4, true, true, false, false, false, true>, srt::pathtrace_kernel<4, true, true, true, false, false, true>,
-               srt::pathtrace_kernel<4, true, true, false, true, false, true>);
+    // variants 1 / 3 are a development aid for in-process A/B timing
+    const bool multi = L.shape.tile_h < srt::TILE_H || (K.steps > 1 && !(K.flags & SRT_RENDER_PREVIEW)) || L.bgrid;
+    if (K.n_tris > 0)  // EXTENSION: scenes with triangle meshes use the BVH-enabled instantiations
+        launch_pathtrace<4, true>(tally, in_lds, multi, L.defer, L.grid, ks.lds_bytes, ctx->stream, K);
 #ifdef SRT_DEV  // occupancy variants for A/B timing; never in the shipped library
-    else if (use == 1 && in_lds && !multi && !defer && !tally)
-        hipLaunchKernelGGL((srt::pathtrace_kernel<4, false>), grid, block, lds_bytes, ctx->stream, K);
-    else if (use == 3 && in_lds && !multi && !defer && !tally)
-        hipLaunchKernelGGL((srt::pathtrace_kernel<3, false>), grid, block, lds_bytes, ctx->stream, K);
+    else if (ks.use == 1 && in_lds && !multi && !L.defer && !tally)
+        hipLaunchKernelGGL((srt::pathtrace_kernel<4, false>), L.grid, dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K);
+    else if (ks.use == 3 && in_lds && !multi && !L.defer && !tally)
+        hipLaunchKernelGGL((srt::pathtrace_kernel<3, false>), L.grid, dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K);
 #endif
     else
         // (five waves per SIMD, 96 VGPRs.  Since srt_powf's coefficients come from the LDS constants block — the 64-bit literals had
         // been living in hoisted register pairs — the kernels need 85..95 registers, the multi-sample hand-out of small tiles /
         // progressive blocks included (it stayed at four waves before: 111), and the mesh kernels 119..125: four waves, no spill)
-        launch(srt::pathtrace_kernel<5, false, true, false, false>, srt::pathtrace_kernel<5, false, true, true, false>,
-               srt::pathtrace_kernel<5, false, true, false, true>, srt::pathtrace_kernel<5, false, false, false, false>,
-               srt::pathtrace_kernel<5, false, false, true, false>, srt::pathtrace_kernel<5, false, false, false, true>,
-               srt::pathtrace_kernel<5, false, true, false, false, false, true>, srt::pathtrace_kernel<5, false, true, true, false, false, true>,
-               srt::pathtrace_kernel<5, false, true, false, true, false, true>);
-    if (defer) {
+        launch_pathtrace<5, false>(tally, in_lds, multi, L.defer, L.grid, ks.lds_bytes, ctx->stream, K);
+    if (L.defer) {
         SRT_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(srt::fold_kernel, dim3((unsigned)wg8), dim3(256), 0, ctx->stream, K, (int)wg_x);
+        hipLaunchKernelGGL(srt::fold_kernel, dim3((unsigned)L.shape.wg8), dim3(256), 0, ctx->stream, K, (int)L.shape.wg_x);
     }
     SRT_HIP(ctx, hipGetLastError());
     if (timing) SRT_HIP(ctx, hipEventRecord(ctx->ev_end, ctx->stream));
     ctx->pending_timed = timing;
-    if (record) {
+    if (L.record) {
+        const size_t nwg = (size_t)L.grid.x * L.grid.y;
         SRT_HIP(ctx, hipMemcpyAsync(ctx->h_wg_cost, ctx->d_wg_cost, REC_WORDS * nwg * 4, hipMemcpyDeviceToHost, ctx->stream));
         SRT_HIP(ctx, hipEventRecord(ctx->ev_cost, ctx->stream));
         ctx->recording = true;
-        ctx->rec_gx = grid.x, ctx->rec_gy = grid.y;
+        ctx->rec_gx = L.grid.x, ctx->rec_gy = L.grid.y;
         ctx->rec_has_work = tally;  // (a counting launch that also records does keep them)
         ctx->rec_step_w = probe_step_weight(K, ProbeWeights());
         ctx->order_stale = false;
     }
+    return SRT_OK;
+}
+
+// what srt_get_stats reports for the launch
+static void note_pending(srt_context* ctx, const srt_render_params* p, const srt::KernelParams& K, const RenderLaunch& L) {
     ctx->launched = true;
     ctx->stats_pending = true;
-    ctx->pending_samples = (uint64_t)W * (uint64_t)K.rows * p->sample_count;
-    ctx->pending_chunks = (uint32_t)chunks;
-    ctx->pending_tile_rows = (uint32_t)tile_h;
-    ctx->pending_chunk_samples = defer ? (uint32_t)chunk : 0u;
-    ctx->pending_shape_source = shape_source;
+    ctx->pending_samples = (uint64_t)ctx->width * (uint64_t)K.rows * p->sample_count;
+    ctx->pending_chunks = (uint32_t)L.shape.chunks;
+    ctx->pending_tile_rows = (uint32_t)L.shape.tile_h;
+    ctx->pending_chunk_samples = L.defer ? (uint32_t)L.shape.chunk : 0u;
+    ctx->pending_shape_source = L.shape.source;
     ctx->work_layout[0] = K.nu, ctx->work_layout[1] = K.nc, ctx->work_layout[2] = K.K, ctx->work_layout[3] = K.nb;
+}
+
+extern "C" {
+
+int srt_render(srt_context* ctx, const srt_render_params* p) {
+    if (const int rc = check_render_params(ctx, p)) return rc;
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    srt::KernelParams K;
+    const KernelSetup ks = fill_kernel_params(ctx, p, K);
+    ctx->count_rays = (p->flags & SRT_RENDER_COUNT_RAYS) != 0;
+    if (ctx->count_rays) SRT_HIP(ctx, hipMemsetAsync(ctx->d_rays, 0, sizeof(unsigned long long), ctx->stream));
+    RenderLaunch L;
+    if (const int rc = enter_band(ctx, K)) return rc;
+    if (const int rc = plan_launch(ctx, p, K, L)) return rc;
+    if (const int rc = plan_cost_order(ctx, p, K, ks, L)) return rc;
+    if (const int rc = launch_render(ctx, p, K, ks, L)) return rc;
+    note_pending(ctx, p, K, L);
     return SRT_OK;
 }
 
@@ -1063,8 +1089,7 @@ int srt_debug_read_chain(srt_context* ctx, uint32_t* out_at, uint32_t* out_cut, 
     if (!ctx) return SRT_ERR_INVALID_ARG;
     const size_t tiles = ctx->chain_tiles;
     if ((out_at || out_cut) && n < tiles) return SRT_ERR_INVALID_ARG;
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = finish_stream(ctx)) return rc;
     if (info) {
         info[0] = ctx->chain_layers, info[1] = ctx->chain_chunk, info[2] = ctx->chain_chunk_full;
         info[3] = (int)tiles, info[4] = ctx->chain_wg_x, info[5] = ctx->chain_used ? 1 : 0;
@@ -1120,17 +1145,13 @@ int srt_pick(srt_context* ctx, int x, int y, int* object_index) {
     p.first_sample = 1;
     p.sample_count = 1;
     srt::KernelParams K;
-    size_t lds_bytes = 0;
-    int use = 0;
-    int img = 0;
-    if (const int frc = fill_kernel_params(ctx, &p, K, lds_bytes, use, img)) return frc;
+    const int img = fill_kernel_params(ctx, &p, K).img;
     int* d_out = ctx->d_pick;
     // one wave: image (if it fits) + one wave's scratch + one wave's mesh queues
     const size_t image_bytes = (size_t)(K.scene_vec4 > 0 ? K.scene_vec4 : 1) * sizeof(float4);
-    if (ctx->pick_in_lds[img])
-        hipLaunchKernelGGL(srt::pick_kernel<true>, dim3(1), dim3(64), image_bytes + srt::WAVE_SCRATCH_BYTES + srt::MESH_WAVE_BYTES, ctx->stream, K, x, y, d_out);
-    else
-        hipLaunchKernelGGL(srt::pick_kernel<false>, dim3(1), dim3(64), (size_t)(srt::WAVE_SCRATCH_BYTES + srt::MESH_WAVE_BYTES), ctx->stream, K, x, y, d_out);
+    const bool in_lds = ctx->pick_in_lds[img];
+    hipLaunchKernelGGL(in_lds ? srt::pick_kernel<true> : srt::pick_kernel<false>, dim3(1), dim3(64),
+                       (in_lds ? image_bytes : 0) + srt::WAVE_SCRATCH_BYTES + srt::MESH_WAVE_BYTES, ctx->stream, K, x, y, d_out);
     SRT_HIP(ctx, hipGetLastError());
     int idx[4] = {-1, 0, 0, 0};
     SRT_HIP(ctx, hipMemcpyAsync(idx, d_out, sizeof idx, hipMemcpyDeviceToHost, ctx->stream));
@@ -1153,6 +1174,25 @@ static int gbuf_slot(uint32_t output) {
 }
 static size_t gbuf_elem_bytes(int slot) { return slot == 0 ? sizeof(int32_t) : sizeof(float4); }
 
+static bool same_camera(const srt_camera& a, const srt_camera& b) {
+    for (int i = 0; i < 3; ++i)
+        if (a.position[i] != b.position[i] || a.right[i] != b.right[i] || a.up[i] != b.up[i] || a.forward[i] != b.forward[i]) return false;
+    return a.fov_degrees == b.fov_degrees;
+}
+
+// The first-hit guides [0, n) of a pass (srt_denoise, srt_temporal_accumulate), bound or own; SRT_ERR_STATE for the first that is
+// missing or, given a camera, is an own one rendered with another camera (bound ones cannot be checked).
+static int find_guides(srt_context* ctx, const char* fn, int n, const srt_camera* cam, const void** guide) {
+    static const char* const names[4] = {"OBJECT", "NORMAL_DEPTH", "POSITION", "ALBEDO"};
+    for (int i = 0; i < n; ++i) {
+        guide[i] = bound_or_own(ctx->d_gbuf_bound[i], ctx->d_gbuf_own[i]);
+        if (!guide[i]) return fail(ctx, SRT_ERR_STATE, "%s: the %s guide has neither been bound nor rendered (srt_render_gbuffer)", fn, names[i]);
+        if (cam && !ctx->d_gbuf_bound[i] && (!ctx->gbuf_own_cam_set[i] || !same_camera(ctx->gbuf_own_cam[i], *cam)))
+            return fail(ctx, SRT_ERR_STATE, "%s: the %s guide was rendered with another camera (srt_render_gbuffer after srt_set_camera)", fn, names[i]);
+    }
+    return SRT_OK;
+}
+
 int srt_render_gbuffer(srt_context* ctx, const srt_gbuffer_params* g) {
     if (!ctx || !g) return SRT_ERR_INVALID_ARG;
     if (!ctx->scene_set) return fail(ctx, SRT_ERR_STATE, "srt_render_gbuffer: srt_set_scene has not been called");
@@ -1168,42 +1208,34 @@ int srt_render_gbuffer(srt_context* ctx, const srt_gbuffer_params* g) {
     void* dst[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i < 4; ++i) {
         if (!(g->outputs & (1u << i))) continue;
-        if (ctx->d_gbuf_bound[i]) {
-            dst[i] = ctx->d_gbuf_bound[i];
-            continue;
+        if (!ctx->d_gbuf_bound[i]) {
+            SRT_HIP(ctx, ctx->d_gbuf_own[i].ensure(px * gbuf_elem_bytes(i)));
+            ctx->gbuf_own_cam[i] = ctx->camera.cam;
+            ctx->gbuf_own_cam_set[i] = true;
         }
-        if (!ctx->d_gbuf_own[i]) SRT_HIP(ctx, hipMalloc(&ctx->d_gbuf_own[i], px * gbuf_elem_bytes(i)));
-        dst[i] = ctx->d_gbuf_own[i];
-        ctx->gbuf_own_cam[i] = ctx->camera.cam;
-        ctx->gbuf_own_cam_set[i] = true;
+        dst[i] = bound_or_own(ctx->d_gbuf_bound[i], ctx->d_gbuf_own[i]);
     }
     // the render's kernel parameters for this band: camera, scene image, the scene_in_lds judgement and the LDS bytes
     srt_render_params p{};
     p.row_begin = g->row_begin, p.row_end = g->row_end, p.first_sample = 1, p.sample_count = 1;
     srt::KernelParams K;
-    size_t lds_bytes = 0;
-    int use = 0, img = 0;
-    if (const int frc = fill_kernel_params(ctx, &p, K, lds_bytes, use, img)) return frc;
+    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
     K.flags &= srt::KF_BOXES_FINITE;
     K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // the G-buffer touches none of them
     const srt::GBufferOut out{(int32_t*)dst[0], (float4*)dst[1], (float4*)dst[2], (float4*)dst[3]};
-    const bool in_lds = ctx->scene_in_lds[img], mesh = K.n_tris > 0;
-    const void* kern = in_lds ? (mesh ? (const void*)srt::gbuffer_kernel<true, true> : (const void*)srt::gbuffer_kernel<true, false>)
-                              : (mesh ? (const void*)srt::gbuffer_kernel<false, true> : (const void*)srt::gbuffer_kernel<false, false>);
+    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
+    void (*const kernel)(srt::KernelParams, srt::GBufferOut) = in_lds ? (mesh ? srt::gbuffer_kernel<true, true> : srt::gbuffer_kernel<true, false>)
+                                                                      : (mesh ? srt::gbuffer_kernel<false, true> : srt::gbuffer_kernel<false, false>);
     // persistent workgroups: each stages the scene once and its waves stride over 8 x 8 tiles; about CUs x resident workgroups
     // (LDS and registers decide; at most four per CU), never more than there are tiles for
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, srt::WG_THREADS, lds_bytes) != hipSuccess || per_cu < 1)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, srt::WG_THREADS, ks.lds_bytes) != hipSuccess || per_cu < 1)
         per_cu = 1, (void)hipGetLastError();
     per_cu = per_cu > 4 ? 4 : per_cu;
     const long long tiles = (long long)((ctx->width + srt::TILE_W - 1) / srt::TILE_W) * ((K.rows + srt::TILE_H - 1) / srt::TILE_H);
     const long long need = (tiles + srt::WG_TILES_X * srt::WG_TILES_Y - 1) / (srt::WG_TILES_X * srt::WG_TILES_Y);
     const long long wgs = std::min<long long>(need, (long long)ctx->cu_count * per_cu);
-    const dim3 grid((unsigned)wgs), block(srt::WG_THREADS);
-    if (in_lds && mesh) hipLaunchKernelGGL((srt::gbuffer_kernel<true, true>), grid, block, lds_bytes, ctx->stream, K, out);
-    else if (in_lds) hipLaunchKernelGGL((srt::gbuffer_kernel<true, false>), grid, block, lds_bytes, ctx->stream, K, out);
-    else if (mesh) hipLaunchKernelGGL((srt::gbuffer_kernel<false, true>), grid, block, lds_bytes, ctx->stream, K, out);
-    else hipLaunchKernelGGL((srt::gbuffer_kernel<false, false>), grid, block, lds_bytes, ctx->stream, K, out);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, out);
     SRT_HIP(ctx, hipGetLastError());
     return SRT_OK;
 }
@@ -1220,10 +1252,9 @@ int srt_read_gbuffer(srt_context* ctx, uint32_t output, void* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
     const int i = gbuf_slot(output);
     if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_gbuffer: output 0x%x is not a single SRT_GBUF_* bit", output);
-    const void* src = ctx->d_gbuf_bound[i] ? ctx->d_gbuf_bound[i] : ctx->d_gbuf_own[i];
+    const void* src = bound_or_own(ctx->d_gbuf_bound[i], ctx->d_gbuf_own[i]);
     if (!src) return fail(ctx, SRT_ERR_STATE, "srt_read_gbuffer: output 0x%x has neither been bound nor rendered", output);
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = finish_stream(ctx)) return rc;
     SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * gbuf_elem_bytes(i), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
@@ -1251,17 +1282,13 @@ int srt_denoise(srt_context* ctx, const srt_denoise_params* d) {
     if (d->flags & ~(SRT_DENOISE_ALBEDO | SRT_DENOISE_FRAMEBUFFER))
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_denoise: unknown flags 0x%x", d->flags);
     const bool demod = (d->flags & SRT_DENOISE_ALBEDO) != 0;
-    const void* guide[4];
-    for (int i = 0; i < 4; ++i) guide[i] = ctx->d_gbuf_bound[i] ? ctx->d_gbuf_bound[i] : ctx->d_gbuf_own[i];
-    static const char* const names[4] = {"OBJECT", "NORMAL_DEPTH", "POSITION", "ALBEDO"};
-    for (int i = 0; i < (demod ? 4 : 3); ++i)
-        if (!guide[i])
-            return fail(ctx, SRT_ERR_STATE, "srt_denoise: the %s guide has neither been bound nor rendered (srt_render_gbuffer)", names[i]);
+    const void* guide[4] = {};
+    if (const int rc = find_guides(ctx, "srt_denoise", demod ? 4 : 3, nullptr, guide)) return rc;
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)ctx->width * (size_t)ctx->height;
-    if (!ctx->d_dn_bound && !ctx->d_dn_own) SRT_HIP(ctx, hipMalloc((void**)&ctx->d_dn_own, px * sizeof(float4)));
-    if (!ctx->d_dn_tmp) SRT_HIP(ctx, hipMalloc((void**)&ctx->d_dn_tmp, px * sizeof(float4)));
-    float4* const out = ctx->d_dn_bound ? ctx->d_dn_bound : ctx->d_dn_own;
+    if (!ctx->d_dn_bound) SRT_HIP(ctx, ctx->d_dn_own.ensure(px * sizeof(float4)));
+    SRT_HIP(ctx, ctx->d_dn_tmp.ensure(px * sizeof(float4)));
+    float4* const out = bound_or_own(ctx->d_dn_bound, ctx->d_dn_own);
     srt::DenoiseLevel L{};
     L.acc = ctx->d_acc;
     L.object = (const int32_t*)guide[0];
@@ -1271,8 +1298,7 @@ int srt_denoise(srt_context* ctx, const srt_denoise_params* d) {
     L.width = ctx->width, L.height = ctx->height;
     L.sigma_normal = d->sigma_normal;
     L.sigma_plane = d->sigma_plane;
-    const dim3 grid((unsigned)((ctx->width + srt::WG_W - 1) / srt::WG_W), (unsigned)((ctx->height + srt::WG_H - 1) / srt::WG_H)),
-        block(srt::WG_THREADS);
+    const dim3 grid = frame_tile_grid(ctx), block(srt::WG_THREADS);
     // the preparation pass and the levels alternate between the ping-pong buffer and the result buffer so that the last
     // level lands in the result
     const int n = d->iterations;
@@ -1287,8 +1313,7 @@ int srt_denoise(srt_context* ctx, const srt_denoise_params* d) {
         const float sc = d->sigma_color * ldexpf(1.0f, -i);
         L.color_scale = sc > 0.0f ? 1.0f / (sc * sc) : 0.0f;
         L.framebuffer = last && (d->flags & SRT_DENOISE_FRAMEBUFFER) ? ctx->d_fb : nullptr;
-        if (last) hipLaunchKernelGGL((srt::denoise_kernel<true>), grid, block, 0, ctx->stream, L);
-        else hipLaunchKernelGGL((srt::denoise_kernel<false>), grid, block, 0, ctx->stream, L);
+        hipLaunchKernelGGL(last ? srt::denoise_kernel<true> : srt::denoise_kernel<false>, grid, block, 0, ctx->stream, L);
         SRT_HIP(ctx, hipGetLastError());
     }
     ctx->dn_written = true;
@@ -1303,10 +1328,9 @@ int srt_bind_denoised(srt_context* ctx, void* d_float4) {
 
 int srt_read_denoised(srt_context* ctx, float* dst_rgba) {
     if (!ctx || !dst_rgba) return SRT_ERR_INVALID_ARG;
-    const float4* src = ctx->d_dn_bound ? ctx->d_dn_bound : ctx->d_dn_own;
+    const float4* src = bound_or_own(ctx->d_dn_bound, ctx->d_dn_own);
     if (!ctx->dn_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_read_denoised: nothing has been denoised into this buffer yet");
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = finish_stream(ctx)) return rc;
     SRT_HIP(ctx, hipMemcpy(dst_rgba, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
@@ -1321,12 +1345,6 @@ int srt_temporal_params_default(srt_temporal_params* out) {
     out->normal_threshold = 0.9f;
     out->flags = 0;
     return SRT_OK;
-}
-
-static bool same_camera(const srt_camera& a, const srt_camera& b) {
-    for (int i = 0; i < 3; ++i)
-        if (a.position[i] != b.position[i] || a.right[i] != b.right[i] || a.up[i] != b.up[i] || a.forward[i] != b.forward[i]) return false;
-    return a.fov_degrees == b.fov_degrees;
 }
 
 // B^-1 of the camera's ray basis B = [right * rd | up * ld | forward * clip] (columns, the floats srt_render uses), inverted in
@@ -1362,22 +1380,13 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
     if (t->flags & ~(SRT_TEMPORAL_RESET | SRT_TEMPORAL_FRAMEBUFFER))
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_temporal_accumulate: unknown flags 0x%x", t->flags);
     if (!ctx->camera.set) return fail(ctx, SRT_ERR_STATE, "srt_temporal_accumulate: srt_set_camera has not been called");
-    const void* guide[3];
-    static const char* const names[3] = {"OBJECT", "NORMAL_DEPTH", "POSITION"};
-    for (int i = 0; i < 3; ++i) {
-        guide[i] = ctx->d_gbuf_bound[i] ? ctx->d_gbuf_bound[i] : ctx->d_gbuf_own[i];
-        if (!guide[i])
-            return fail(ctx, SRT_ERR_STATE, "srt_temporal_accumulate: the %s guide has neither been bound nor rendered (srt_render_gbuffer)", names[i]);
-        // the handle's own guides must show the camera the history will be stored with (bound ones cannot be checked)
-        if (!ctx->d_gbuf_bound[i] && (!ctx->gbuf_own_cam_set[i] || !same_camera(ctx->gbuf_own_cam[i], ctx->camera.cam)))
-            return fail(ctx, SRT_ERR_STATE, "srt_temporal_accumulate: the %s guide was rendered with another camera (srt_render_gbuffer after srt_set_camera)",
-                        names[i]);
-    }
+    // the handle's own guides must show the camera the history will be stored with
+    const void* guide[3] = {};
+    if (const int rc = find_guides(ctx, "srt_temporal_accumulate", 3, &ctx->camera.cam, guide)) return rc;
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)ctx->width * (size_t)ctx->height;
     for (int i = 0; i < 2; ++i)
-        for (int k = 0; k < 3; ++k)
-            if (!ctx->d_tp[i][k]) SRT_HIP(ctx, hipMalloc((void**)&ctx->d_tp[i][k], px * sizeof(float4)));
+        for (int k = 0; k < 3; ++k) SRT_HIP(ctx, ctx->d_tp[i][k].ensure(px * sizeof(float4)));
     const int a = ctx->tp_cur, b = 1 - a;  // read slot a (when valid), write slot b
     srt::TemporalLaunch T{};
     T.acc = ctx->d_acc;
@@ -1395,9 +1404,7 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
     T.max_samples = t->max_samples;
     T.plane_tolerance = t->plane_tolerance;
     T.normal_threshold = t->normal_threshold;
-    const dim3 grid((unsigned)((ctx->width + srt::WG_W - 1) / srt::WG_W), (unsigned)((ctx->height + srt::WG_H - 1) / srt::WG_H)),
-        block(srt::WG_THREADS);
-    hipLaunchKernelGGL(srt::temporal_kernel, grid, block, 0, ctx->stream, T);
+    hipLaunchKernelGGL(srt::temporal_kernel, frame_tile_grid(ctx), dim3(srt::WG_THREADS), 0, ctx->stream, T);
     SRT_HIP(ctx, hipGetLastError());
     ctx->tp_cur = b;
     ctx->tp_cam = ctx->camera.cam;
@@ -1409,8 +1416,7 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
 int srt_read_history_length(srt_context* ctx, float* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
     if (!ctx->tp_written) return fail(ctx, SRT_ERR_STATE, "srt_read_history_length: srt_temporal_accumulate has not been called");
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = finish_stream(ctx)) return rc;
     // L is the w of the history colour
     const size_t px = (size_t)ctx->width * ctx->height;
     std::vector<float4> tmp(px);
@@ -1421,8 +1427,7 @@ int srt_read_history_length(srt_context* ctx, float* dst) {
 
 int srt_wait(srt_context* ctx) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = finish_stream(ctx)) return rc;
     return SRT_OK;
 }
 
@@ -1445,8 +1450,7 @@ int srt_poll(srt_context* ctx, int* done) {
 int srt_get_stats(srt_context* ctx, srt_stats* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
     if (!ctx->launched) return fail(ctx, SRT_ERR_STATE, "srt_get_stats: nothing rendered yet");
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = finish_stream(ctx)) return rc;
     if (ctx->stats_pending) {
         float ms = 0.0f;
         if (ctx->pending_timed) SRT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
@@ -1504,8 +1508,7 @@ int srt_read_framebuffer(srt_context* ctx, void* dst, size_t pitch_bytes, int ro
     const size_t rowb = (size_t)ctx->width * 4;
     if (row_begin < 0 || row_end > ctx->height || row_begin >= row_end || pitch_bytes < rowb)
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_framebuffer: bad rows [%d,%d) or pitch %zu", row_begin, row_end, pitch_bytes);
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = finish_stream(ctx)) return rc;
     SRT_HIP(ctx, hipMemcpy2D(dst, pitch_bytes, (const char*)ctx->d_fb + (size_t)row_begin * rowb, rowb, rowb,
                              (size_t)(row_end - row_begin), hipMemcpyDeviceToHost));
     return SRT_OK;
@@ -1519,7 +1522,7 @@ int srt_read_framebuffer_async(srt_context* ctx, void* dst, size_t pitch_bytes, 
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t cs = copy_stream ? (hipStream_t)copy_stream : ctx->stream;
     if (cs != ctx->stream) {  // the copy starts when the renders enqueued so far have finished, not before
-        if (!ctx->ev_read) SRT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_read, hipEventDisableTiming));
+        if (!ctx->ev_read) SRT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_read.h, hipEventDisableTiming));
         SRT_HIP(ctx, hipEventRecord(ctx->ev_read, ctx->stream));
         SRT_HIP(ctx, hipStreamWaitEvent(cs, ctx->ev_read, 0));
     }
@@ -1530,8 +1533,7 @@ int srt_read_framebuffer_async(srt_context* ctx, void* dst, size_t pitch_bytes, 
 
 int srt_read_accumulator(srt_context* ctx, float* dst_rgba) {
     if (!ctx || !dst_rgba) return SRT_ERR_INVALID_ARG;
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = finish_stream(ctx)) return rc;
     SRT_HIP(ctx, hipMemcpy(dst_rgba, ctx->d_acc, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
@@ -1546,36 +1548,32 @@ constexpr int PROBE_SAMPLES = 32;
 static_assert(PROBE_SAMPLES == 32, "ProbeWeights were fitted on probes of 32 samples (shorter pools take 12..37 % more steps per sample, unevenly over a frame): refit them (tools/band_fit.py) when this changes");
 static int run_pool_probe(srt_context* ctx, int max_bounces, uint32_t seed, std::vector<uint32_t>& counts, int& bx, int& by) {
     SRT_HIP(ctx, hipSetDevice(ctx->device));
-    const int W = ctx->width, H = ctx->height;
     srt_render_params p{};
-    p.row_begin = 0, p.row_end = H, p.first_sample = 1, p.sample_count = PROBE_SAMPLES, p.max_bounces = max_bounces, p.seed = seed;
+    p.row_begin = 0, p.row_end = ctx->height, p.first_sample = 1, p.sample_count = PROBE_SAMPLES, p.max_bounces = max_bounces, p.seed = seed;
     p.flags = SRT_RENDER_RESET;
     srt::KernelParams K;
-    size_t lds_bytes = 0;
-    int use = 0, img = 0;
-    if (const int frc = fill_kernel_params(ctx, &p, K, lds_bytes, use, img)) return frc;
+    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
     K.flags = (K.flags & srt::KF_BOXES_FINITE) | SRT_RENDER_RESET;
     K.tile_h = srt::TILE_H;
     K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // the probe touches none of them
-    bx = (W + srt::WG_W - 1) / srt::WG_W, by = (H + srt::WG_H - 1) / srt::WG_H;
-    const size_t n = (size_t)bx * by, words = n * srt::TALLY_N;
-    uint32_t* d = nullptr;
-    SRT_HIP(ctx, hipMalloc((void**)&d, words * sizeof(uint32_t)));
+    const dim3 grid = frame_tile_grid(ctx), block(srt::WG_THREADS);
+    bx = (int)grid.x, by = (int)grid.y;
+    const size_t words = (size_t)bx * by * srt::TALLY_N;
+    DeviceBuffer<uint32_t> d;
+    SRT_HIP(ctx, d.ensure(words * sizeof(uint32_t)));
     hipError_t e = hipMemsetAsync(d, 0, words * sizeof(uint32_t), ctx->stream);
     K.wg_cost = d;
-    const dim3 grid((unsigned)bx, (unsigned)by, 1), block(srt::WG_THREADS);
     if (e == hipSuccess) {
-        const bool in_lds = ctx->scene_in_lds[img];
-        if (K.n_tris > 0 && in_lds) hipLaunchKernelGGL((srt::pathtrace_kernel<4, true, true, false, false, true>), grid, block, lds_bytes, ctx->stream, K);
-        else if (K.n_tris > 0) hipLaunchKernelGGL((srt::pathtrace_kernel<4, true, false, false, false, true>), grid, block, lds_bytes, ctx->stream, K);
-        else if (in_lds) hipLaunchKernelGGL((srt::pathtrace_kernel<4, false, true, false, false, true>), grid, block, lds_bytes, ctx->stream, K);
-        else hipLaunchKernelGGL((srt::pathtrace_kernel<4, false, false, false, false, true>), grid, block, lds_bytes, ctx->stream, K);
+        const bool in_lds = ctx->scene_in_lds[ks.img];
+        if (K.n_tris > 0 && in_lds) hipLaunchKernelGGL((srt::pathtrace_kernel<4, true, true, false, false, true>), grid, block, ks.lds_bytes, ctx->stream, K);
+        else if (K.n_tris > 0) hipLaunchKernelGGL((srt::pathtrace_kernel<4, true, false, false, false, true>), grid, block, ks.lds_bytes, ctx->stream, K);
+        else if (in_lds) hipLaunchKernelGGL((srt::pathtrace_kernel<4, false, true, false, false, true>), grid, block, ks.lds_bytes, ctx->stream, K);
+        else hipLaunchKernelGGL((srt::pathtrace_kernel<4, false, false, false, false, true>), grid, block, ks.lds_bytes, ctx->stream, K);
         e = hipGetLastError();
     }
     counts.resize(words);
     if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(ctx, SRT_ERR_HIP, "balance probe: %s", hipGetErrorString(e));
     return SRT_OK;
 }
@@ -1593,9 +1591,7 @@ int srt_estimate_row_costs(srt_context* ctx, int max_bounces, uint32_t seed, flo
     srt_render_params p{};
     p.row_begin = 0, p.row_end = H, p.first_sample = 1, p.sample_count = 1, p.max_bounces = max_bounces;
     srt::KernelParams K;
-    size_t lds_bytes = 0;
-    int use = 0, img = 0;
-    if (const int frc = fill_kernel_params(ctx, &p, K, lds_bytes, use, img)) return frc;
+    fill_kernel_params(ctx, &p, K);
     const ProbeWeights w;
     // a block covers WG_H scene rows; its cost is spread evenly over them; memory row m = scene row H - 1 - m
     for (int m = 0; m < H; ++m) row_costs[m] = 0.0f;
@@ -1630,9 +1626,9 @@ int srt_selftest_arith(int device, uint32_t seed, uint64_t vectors, uint64_t* mi
         (void)hipGetLastError();
         return SRT_ERR_NO_DEVICE;
     }
-    unsigned long long* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, sizeof *d);
-    if (e == hipSuccess) e = hipMemset(d, 0, sizeof *d);
+    DeviceBuffer<unsigned long long> d;
+    hipError_t e = d.ensure(sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(d, 0, sizeof(unsigned long long));
     for (uint64_t done = 0; e == hipSuccess && done < vectors; done += 1ull << 28) {  // grids of at most 2^20 blocks
         const uint64_t part = vectors - done < (1ull << 28) ? vectors - done : (1ull << 28);
         hipLaunchKernelGGL(srt::selftest_normalize_kernel, dim3((unsigned)((part + 255) / 256)), dim3(256), 0, 0, seed + (uint32_t)(done >> 28) * 0x85EBCA6Bu, (unsigned long long)done, part, d);
@@ -1640,7 +1636,7 @@ int srt_selftest_arith(int device, uint32_t seed, uint64_t vectors, uint64_t* mi
     }
     unsigned long long h = 0;
     if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
-    if (d) (void)hipFree(d);
+    d.reset();  // (on its device)
     (void)hipSetDevice(prev);
     if (e != hipSuccess) return SRT_ERR_HIP;
     *mismatches = h;
@@ -1686,7 +1682,7 @@ int srt_gather_band(srt_context* dst, srt_context* src, int row_begin, int row_e
         what = "hipMemcpyAsync";
         e = hipMemcpyAsync((char*)dst->d_fb + off, (const char*)src->d_fb + off, bytes, hipMemcpyDeviceToDevice, src->stream);
     }
-    if (e == hipSuccess && !src->ev_gather) what = "hipEventCreate", e = hipEventCreateWithFlags(&src->ev_gather, hipEventDisableTiming);
+    if (e == hipSuccess && !src->ev_gather) what = "hipEventCreate", e = hipEventCreateWithFlags(&src->ev_gather.h, hipEventDisableTiming);
     if (e == hipSuccess) what = "hipEventRecord", e = hipEventRecord(src->ev_gather, src->stream);
     const hipError_t back = hipSetDevice(dst->device);
     if (e == hipSuccess) what = "hipSetDevice", e = back;
@@ -1699,8 +1695,7 @@ const char* srt_gather_path(const srt_context* src) { return src ? src->gather_p
 
 int srt_write_accumulator(srt_context* ctx, const float* src_rgba) {
     if (!ctx || !src_rgba) return SRT_ERR_INVALID_ARG;
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    SRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = finish_stream(ctx)) return rc;
     SRT_HIP(ctx, hipMemcpy(ctx->d_acc, src_rgba, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyHostToDevice));
     return SRT_OK;
 }

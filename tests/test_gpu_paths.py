@@ -1,10 +1,11 @@
 """Every pathtrace_kernel instantiation srt_render ships, and every launch path that reads or writes the accumulator, against the
 oracle bit for bit (NaNs compared as NaNs): accumulator, framebuffer and ray count.
 
-srt_render picks one of nine instantiations for analytic scenes and nine for mesh scenes (srt_capi.hip, the `launch` lambda): scene
+srt_render picks one of nine instantiations for analytic scenes and nine for mesh scenes (srt_capi.hip, launch_pathtrace): scene
 image in LDS or in HBM (too big, or a sphere's r*r outside the short square root's window), full tiles / small tiles (the multi-sample
-hand-out) / sample chunks, with or without the loop counts (TALLY).  A cell of the matrix below is named after the lambda argument it
-is meant to reach and asserts, from the launch's stats and work counts, that it did.  Every cell runs from a reset and then resumed on
+hand-out) / sample chunks, with or without the loop counts (TALLY).  A cell of the matrix below is named after the instantiation it
+is meant to reach (the name launch_pathtrace gives it in a comment) and asserts, from the launch's stats and work counts, that it
+did.  Every cell runs from a reset and then resumed on
 a caller's accumulator that holds what the kernel's clamp elimination must not be fooled by (negatives, -0, 1e-38, a non-zero alpha),
 on a ragged band."""
 import ctypes as C
@@ -276,12 +277,11 @@ def test_frame_numbers_past_2_24_and_at_the_limit(srt, oracle, path, first_sampl
 
 # ---- the matrix covers every shipped instantiation
 def _shipped_instantiations():
-    """(kind, lambda argument) of every pathtrace_kernel<...> that srt_render's shipped (non-SRT_DEV) launch code names"""
+    """(kind, cell name, template arguments) of every pathtrace_kernel<...> that srt_render's shipped (non-SRT_DEV) code launches:
+    the cells of launch_pathtrace<MIN_WAVES, MESH>, each named by its comment, for every <MIN_WAVES, MESH> the shipped code calls"""
     src = open(os.path.join(ROOT, "software-raytracer_amd", "csrc", "srt_capi.hip")).read()
-    start = src.index("int srt_render(srt_context* ctx, const srt_render_params* p)")
-    body = src[start:src.index("\n}\n", start)]
     shipped, skip = [], 0
-    for line in body.split("\n"):  # drop #ifdef SRT_DEV ... #endif blocks
+    for line in src.split("\n"):  # drop #ifdef SRT_DEV ... #endif blocks
         t = line.strip()
         if t.startswith("#if"):
             skip += 1 if (skip or "SRT_DEV" in t) else 0
@@ -291,20 +291,23 @@ def _shipped_instantiations():
             continue
         if not skip:
             shipped.append(line)
-    body = "\n".join(shipped)
-    params = re.search(r"auto launch = \[&\]\(([^)]*)\)", body).group(1)
-    names = [p.split()[-1] for p in params.split(",")]
-    found = []
-    for m in re.finditer(r"\blaunch\((srt::pathtrace_kernel<.*?)\);", body, re.S):
-        kernels = re.findall(r"srt::pathtrace_kernel<([^>]*)>", m.group(1))
-        assert len(kernels) == len(names), kernels
-        for args, nm in zip(kernels, names):
-            mesh = args.split(",")[1].strip() == "true"
-            found.append(("mesh" if mesh else "analytic", nm, args.replace(" ", "")))
-    return found
+    src = "\n".join(shipped)
+    start = src.index("static void launch_pathtrace(")
+    helper = src[start:src.index("\n}\n", start)]
+    cells = []
+    for line in helper.split("\n"):
+        if "pathtrace_kernel<" not in line:
+            continue
+        m = re.search(r"pathtrace_kernel<MIN_WAVES, MESH, ([^>]*)>.*//\s*(\w+)\s*$", line)
+        assert m, "a launch_pathtrace cell without a name: " + line
+        cells.append((m.group(1).replace(" ", ""), m.group(2)))
+    calls = re.findall(r"\blaunch_pathtrace<(\d+), (true|false)>\(", src)
+    assert calls, "srt_render launches no launch_pathtrace<MIN_WAVES, MESH>"
+    return [("mesh" if mesh == "true" else "analytic", name, "%s,%s,%s" % (waves, mesh, args))
+            for waves, mesh in calls for args, name in cells]
 
 
-def test_matrix_covers_every_shipped_instantiation():
+def test_matrix_covers_every_launch_pathtrace_instantiation():
     found = _shipped_instantiations()
     assert len(found) == 18, found
     assert len({f[2] for f in found}) == 18, "an instantiation is named twice"
