@@ -303,6 +303,12 @@ int srt_read_gbuffer(srt_context* ctx, uint32_t output, void* dst);
  *                                                                                      level's working colour)
  *      A tap of another object is skipped before any of its values is used (non-finite values there change nothing); the
  *      centre tap always weighs 36/256.  So a pixel of object A depends on input pixels of object A only.
+ *      Every sigma >= 0 is accepted, +inf and subnormals included, and an exact tie keeps its weight 1 at all of them
+ *      (max(0, 1)^inf = 1, exp(-0 / tiny) = 1): the kernel's reciprocal scales 1 / (sigma_color 2^-i)^2 and
+ *      1 / (sigma_plane d_p), and the exponent sigma_normal, stop at FLT_MAX instead of reaching inf.  So a tiny sigma gives
+ *      an exact tie the weight 1 and a difference whose square (colour) or size (plane) times FLT_MAX is large the weight
+ *      0; only differences below about 1e-19 (colour) or 1e-37 (plane) then weigh more than the definition says.  A
+ *      negative d_p (a first hit behind the camera) turns the plane term into exp(+...), which can overflow.
  *   4. output alpha = input alpha of p.
  *   5. fixed tap order (dy outer, dx inner), no atomics: repeated calls give the same bits. */
 #define SRT_DENOISE_ALBEDO 1u       /* demodulate by the ALBEDO guide before filtering, remodulate after */

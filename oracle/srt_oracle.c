@@ -703,10 +703,18 @@ int srt_oracle_triangle(const float v0[3], const float v1[3], const float v2[3],
 int srt_oracle_closest(const srt_object* objects, size_t count, const float origin[3],
                        const float dir[3], float out_normal[3], float out_point[3],
                        float* out_distance) {
+    return srt_oracle_closest_m(objects, count, NULL, 0, origin, dir, out_normal, out_point, out_distance);
+}
+
+int srt_oracle_closest_m(const srt_object* objects, size_t count, const srt_mesh* meshes, size_t mesh_count,
+                         const float origin[3], const float dir[3], float out_normal[3], float out_point[3],
+                         float* out_distance) {
     octx c;
     memset(&c, 0, sizeof c);
     c.objects = objects;
     c.count = count;
+    c.meshes = meshes;
+    c.mesh_count = mesh_count;
     rayhitobject h =
         get_closest_object(&c, f3_make(origin[0], origin[1], origin[2]), f3_make(dir[0], dir[1], dir[2]));
     put3(out_normal, h.rayHit.normal);

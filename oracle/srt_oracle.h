@@ -68,6 +68,10 @@ int srt_oracle_triangle(const float v0[3], const float v1[3], const float v2[3],
 int srt_oracle_closest(const srt_object* objects, size_t count, const float origin[3],
                        const float dir[3], float out_normal[3], float out_point[3],
                        float* out_distance);
+/* EXTENSION: srt_oracle_closest with the geometry of SRT_OBJ_MESH objects */
+int srt_oracle_closest_m(const srt_object* objects, size_t count, const srt_mesh* meshes, size_t mesh_count,
+                         const float origin[3], const float dir[3], float out_normal[3], float out_point[3],
+                         float* out_distance);
 /* GetEnvironmentColor (Raytracer.cpp:77-89) */
 void srt_oracle_environment(const srt_environment* env, const float dir[3], int32_t pow_mode,
                             float out_rgb[3]);

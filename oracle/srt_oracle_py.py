@@ -139,6 +139,8 @@ def lib():
         L.srt_oracle_intersect.restype = C.c_int
         L.srt_oracle_closest.argtypes = [C.POINTER(Object), C.c_size_t, f3, f3, f3, f3, f3]
         L.srt_oracle_closest.restype = C.c_int
+        L.srt_oracle_closest_m.argtypes = [C.POINTER(Object), C.c_size_t, C.POINTER(Mesh), C.c_size_t, f3, f3, f3, f3, f3]
+        L.srt_oracle_closest_m.restype = C.c_int
         L.srt_oracle_environment.argtypes = [C.POINTER(Environment), f3, C.c_int32, f3]
         L.srt_oracle_environment.restype = None
         L.srt_oracle_trace_sample.argtypes = [

@@ -1296,7 +1296,9 @@ int srt_denoise(srt_context* ctx, const srt_denoise_params* d) {
     L.position = (const float4*)guide[2];
     L.albedo = demod ? (const float4*)guide[3] : nullptr;
     L.width = ctx->width, L.height = ctx->height;
-    L.sigma_normal = d->sigma_normal;
+    // an infinite exponent becomes FLT_MAX: the same 0 for n_p.n_q < 1 and inf above 1, and 1 (FLT_MAX * log2 1 = 0, where
+    // inf * 0 would be NaN) for an exact n_p.n_q == 1, as on one face of a box
+    L.sigma_normal = fminf(d->sigma_normal, FLT_MAX);
     L.sigma_plane = d->sigma_plane;
     const dim3 grid = frame_tile_grid(ctx), block(srt::WG_THREADS);
     // the preparation pass and the levels alternate between the ping-pong buffer and the result buffer so that the last
@@ -1310,8 +1312,10 @@ int srt_denoise(srt_context* ctx, const srt_denoise_params* d) {
         L.src = L.dst;
         L.dst = ((n - 1 - i) & 1) ? ctx->d_dn_tmp : out;
         L.step = 1 << i;
+        // any sigma_color > 0 keeps the term on at every level; a reciprocal past FLT_MAX (sigma_color * 2^-i below about
+        // 5.4e-20, or rounded to 0) stops there, so an exact tie c_p == c_q keeps its weight 1 (0 * inf would be NaN)
         const float sc = d->sigma_color * ldexpf(1.0f, -i);
-        L.color_scale = sc > 0.0f ? 1.0f / (sc * sc) : 0.0f;
+        L.color_scale = d->sigma_color > 0.0f ? fminf(1.0f / (sc * sc), FLT_MAX) : 0.0f;
         L.framebuffer = last && (d->flags & SRT_DENOISE_FRAMEBUFFER) ? ctx->d_fb : nullptr;
         hipLaunchKernelGGL(last ? srt::denoise_kernel<true> : srt::denoise_kernel<false>, grid, block, 0, ctx->stream, L);
         SRT_HIP(ctx, hipGetLastError());

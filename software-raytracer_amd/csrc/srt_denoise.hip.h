@@ -16,6 +16,8 @@
 // values is loaded, so non-finite colours or guides there cannot reach the sums; the centre tap weighs exactly 36/256.
 #pragma once
 
+#include <cfloat>
+
 #include "srt_kernel.hip.h"
 
 namespace srt {
@@ -31,9 +33,9 @@ struct DenoiseLevel {
     const float4* albedo;      // SRT_GBUF_ALBEDO, NULL without demodulation
     uint32_t* framebuffer;     // last level with SRT_DENOISE_FRAMEBUFFER, else NULL (memory row H - 1 - y)
     int width, height, step;   // step = 2^i
-    float sigma_normal;        // exponent of the normal term, 0 = off
+    float sigma_normal;        // exponent of the normal term (at most FLT_MAX), 0 = off
     float sigma_plane;         // 0 = off
-    float color_scale;         // 1 / (sigma_color * 2^-i)^2, 0 = off
+    float color_scale;         // 1 / (sigma_color * 2^-i)^2 (at most FLT_MAX), 0 = off
 };
 
 // demodulation factor of one channel: the albedo where it is at least 1e-3, else 1
@@ -86,7 +88,12 @@ __global__ void __launch_bounds__(WG_THREADS) denoise_kernel(const DenoiseLevel 
     if (use_n || use_x) {
         const float4 nd = L.normal_depth[p];
         np = make_float3(nd.x, nd.y, nd.z);
-        if (use_x) plane_scale = 1.0f / (L.sigma_plane * nd.w);
+        if (use_x) {
+            plane_scale = 1.0f / (L.sigma_plane * nd.w);
+            // sigma_plane * d_p below about 2.9e-39 in magnitude: +-FLT_MAX instead of +-inf, so that an exact tie
+            // n_p.(x_q - x_p) == 0 keeps its weight 1 (0 * inf would be NaN)
+            if (__builtin_isinf(plane_scale)) plane_scale = copysignf(FLT_MAX, plane_scale);
+        }
     }
     if (use_x) {
         const float4 xx = L.position[p];

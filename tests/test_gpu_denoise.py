@@ -141,6 +141,8 @@ def _same_bits(a, b):
 CASES = [  # iterations, sigma_color, sigma_normal, sigma_plane, albedo
     (1, 0.0, 0.0, 0.0, False), (1, 0.5, 128.0, 0.05, True), (2, 0.0, 128.0, 0.0, True), (3, 0.0, 0.0, 0.05, False),
     (3, 1.0, 0.0, 0.0, True), (4, 0.5, 16.0, 0.05, False), (5, 0.0, 128.0, 0.02, True), (5, 2.0, 64.0, 0.1, True),
+    # levels 6..8: steps 32, 64 and 128 (at 67 x 45, step 64 leaves only taps of one row or column, step 128 only the centre)
+    (6, 0.5, 32.0, 0.02, True), (7, 1.0, 128.0, 0.05, False), (8, 0.0, 32.0, 0.02, True), (8, 2.0, 64.0, 0.0, False),
 ]
 
 

@@ -32,8 +32,9 @@ def _gbuffers(pt):
     return {k: pt.gbuffer(k) for k in NAMES}
 
 
-def _oracle_hits(oracle, oarr, n, cam, w, h, xs, ys):
-    """srt_oracle_closest for the camera rays of pixels (xs[i], ys[i]) (scene rows): index, normal, point, distance."""
+def _oracle_hits(oracle, oarr, n, cam, w, h, xs, ys, meshes=None):
+    """srt_oracle_closest for the camera rays of pixels (xs[i], ys[i]) (scene rows): index, normal, point, distance.  With
+    meshes = (oracle mesh array, count): srt_oracle_closest_m, which also hits SRT_OBJ_MESH objects."""
     L = oracle.lib()
     d, nn, pp, t = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_float * 3)(), C.c_float()
     origin = (C.c_float * 3)(*cam.position)
@@ -42,7 +43,10 @@ def _oracle_hits(oracle, oarr, n, cam, w, h, xs, ys):
     nrm, pnt, dist = np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.float32)
     for i, (x, y) in enumerate(zip(xs, ys)):
         L.srt_oracle_ray_direction(C.byref(cam), w, h, int(x), int(y), d)
-        idx[i] = L.srt_oracle_closest(oarr, n, origin, d, nn, pp, C.byref(t))
+        if meshes:
+            idx[i] = L.srt_oracle_closest_m(oarr, n, meshes[0], meshes[1], origin, d, nn, pp, C.byref(t))
+        else:
+            idx[i] = L.srt_oracle_closest(oarr, n, origin, d, nn, pp, C.byref(t))
         if idx[i] >= 0:
             nrm[i], pnt[i], dist[i] = nn[:], pp[:], t.value
     return idx, nrm, pnt, dist
@@ -55,8 +59,8 @@ def _same_bits(a, b):
     return bool(np.all(np.where(nan, np.isnan(a) & np.isnan(b), a.view(np.uint32) == b.view(np.uint32))))
 
 
-def _check_against_oracle(g, oracle, oarr, n, cam, w, h, xs, ys):
-    idx, nrm, pnt, dist = _oracle_hits(oracle, oarr, n, cam, w, h, xs, ys)
+def _check_against_oracle(g, oracle, oarr, n, cam, w, h, xs, ys, meshes=None):
+    idx, nrm, pnt, dist = _oracle_hits(oracle, oarr, n, cam, w, h, xs, ys, meshes)
     obj, nd, pos, alb = g["object"][ys, xs], g["normal_depth"][ys, xs], g["position"][ys, xs], g["albedo"][ys, xs]
     assert np.array_equal(obj, idx), "object index differs at %d pixels" % int((obj != idx).sum())
     hit, miss = idx >= 0, idx < 0

@@ -95,6 +95,15 @@ def cast(cam, w, h):
 
 
 # ---- the definition -----------------------------------------------------------------------------------------------------
+def exact_f32_dot(a, b):
+    """Where a . b (float32 values, last axis 3) is exact in float32 whatever the order and fusing of its operations: every
+    product and the running sums x, x + y, x + y + z are float32 values."""
+    t = a * b
+    parts = [t[..., 0], t[..., 1], t[..., 2], t[..., 0] + t[..., 1], t[..., 0] + t[..., 1] + t[..., 2]]
+    with np.errstate(all="ignore"):
+        return np.logical_and.reduce([np.isfinite(v) & (v.astype(np.float32).astype(np.float64) == v) for v in parts])
+
+
 def reference(acc, obj, nd, pos, hist, n, max_samples, sigma_t, thr):
     """The blend of include/srt_pathtrace.h in float64.  hist: None (no history) or dict(cam, color (H,W,4) f32 with rgb = the
     previous result, L (H,W), obj, nd, pos).  Returns (result rgb, L, sensitive, scale, counted W, footprint of other objects
@@ -142,10 +151,14 @@ def reference(acc, obj, nd, pos, hist, n, max_samples, sigma_t, thr):
         same_any |= same
         dist = np.abs(np.sum(n_p * (hist["pos"][cy, cx, :3].astype(np.float64) - x_p), axis=2))
         dot = np.sum(n_p * hist["nd"][cy, cx, :3].astype(np.float64), axis=2)
-        sens |= same & (np.abs(dist - tol) <= 1e-3 * tol)
+        # (an infinite tolerance or threshold has no rounding band: |x - inf| <= 1e-3 * inf would mark every tap)
+        sens |= same & np.isfinite(tol) & (np.abs(dist - tol) <= 1e-3 * tol)
         counted = same & (dist <= tol)
         if thr > -1:
-            sens |= counted & (np.abs(dot - thr) <= 1e-3 * max(abs(thr), 1e-3))
+            # a dot product that float32 computes exactly (an exact tie such as two equal axis normals) compares as here
+            exact = exact_f32_dot(n_p, hist["nd"][cy, cx, :3].astype(np.float64))
+            if math.isfinite(thr):
+                sens |= counted & ~exact & (np.abs(dot - thr) <= 1e-3 * max(abs(thr), 1e-3))
             counted &= dot >= thr
         w = np.where(counted, wq, 0.0)
         hq = hist["color"][cy, cx, :3].astype(np.float64)
