@@ -88,9 +88,17 @@ typedef struct srt_object {
  * valid for 0.01 <= t <= 10000 (the Box bounds, Object.hpp:226); the normal is the unit geometric
  * normal turned against the ray.  Among equal distances the earlier object in ObjectsToRender
  * wins, then the lower triangle index.  Vertices: 3 floats each; indices: 3 uint32 per triangle.
- * Limits (srt_set_scene fails with SRT_ERR_INVALID_ARG beyond them): 20 M triangles per mesh, 16 M in a
- * scene, world coordinates of magnitude <= 1e9, BVH depth <= 72 levels.  Triangles with an index out of
- * range or a non-finite vertex are ignored (they cannot produce a valid hit). */
+ * Limits (SRT_ERR_INVALID_ARG beyond them, with a message that names the limit): 2^24 - 1 = 16,777,215
+ * triangles in one mesh (srt_set_meshes) and over all SRT_OBJ_MESH objects of a scene (srt_set_scene: a
+ * mesh counts once per object that uses it, triangles that are ignored included), 2^26 - 1 BVH nodes
+ * (more than that many triangles can make), world coordinates of magnitude <= 1e9 (judged on the box
+ * around all triangles), a `mesh` index within the meshes set, and a BVH of <= 61 levels of 8-wide nodes
+ * (7 * depth + 80 entries of the 512-entry traversal buffer).  The builder makes at most
+ * 40 + log2(triangles / 4) levels: no scene of up to 2^23 triangles can reach the depth limit, and a larger
+ * one only if its tree does not collapse by a single level, so no test provokes that error; the check of
+ * the builders (tests/native/builders_check.cpp) asserts the bound for every mesh it builds.  After a
+ * refused scene the context holds either the previous scene or none, never half of one.  Triangles with
+ * an index out of range or a non-finite vertex are ignored (they cannot produce a valid hit). */
 typedef struct srt_mesh {
     const float* vertices;
     size_t vertex_count;

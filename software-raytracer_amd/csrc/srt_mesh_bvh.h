@@ -95,8 +95,9 @@ inline void build_mesh_image(const srt_object* objects, size_t count, const std:
             t.prim = prim;
             t.gid = (int32_t)tris.size();
             t.ord = (int32_t)i;
-            bool finite = true;
-            for (int ax = 0; ax < 3; ++ax) finite = finite && std::isfinite(t.lo[ax]) && std::isfinite(t.hi[ax]);
+            bool finite = true;  // (every vertex: min / max pass a NaN in the second or third one by)
+            for (int q = 0; q < 3; ++q)
+                for (int ax = 0; ax < 3; ++ax) finite = finite && std::isfinite(v[q][ax]);
             if (finite) tris.push_back(t);  // a non-finite triangle can never produce a valid hit
         }
     }
@@ -345,7 +346,18 @@ inline void build_mesh_image(const srt_object* objects, size_t count, const std:
     }
     // quantize: child boxes on a 256^3 grid spanned by the node's own box.  origin = node.lo (float),
     // cell = 2^e per axis (the smallest power of two with 255 cells >= extent); lo is rounded down,
-    // hi up, in exact double arithmetic, so  origin + q*cell  (as real numbers) encloses the child.
+    // hi up, so  origin + q*cell  (as real numbers) encloses the child.  A difference of two floats is only exact in double
+    // while their exponents are within 29 of each other (a vertex at 6e-17 in a box that starts at -1 is not), so the
+    // differences carry their rounding error along (Knuth's TwoSum) and a quotient that lands exactly on a cell boundary
+    // is pushed outwards by it.  (TwoSum relies on IEEE addition as written: no -ffast-math / reassociation on a translation unit
+    // that includes this header.)
+    struct Diff {
+        double d, err;  // a - b = d + err exactly
+    };
+    auto diff = [](float a, float b) {
+        const double x = (double)a, y = -(double)b, s = x + y, yy = s - x;
+        return Diff{s, (x - (s - yy)) + (y - yy)};
+    };
     out.n_nodes = (int)wide.size();
     out.nodes.assign(wide.size() * NODE_VEC4, make_float4(0, 0, 0, 0));
     for (size_t k = 0; k < wide.size(); ++k) {
@@ -359,9 +371,9 @@ inline void build_mesh_image(const srt_object* objects, size_t count, const std:
         uint32_t expo[3];
         double cell[3];
         for (int ax = 0; ax < 3; ++ax) {
-            const double ext = (double)hi[ax] - (double)lo[ax];
+            const Diff ext = diff(hi[ax], lo[ax]);
             int e = -126;
-            while (e < 127 && ldexp(255.0, e) < ext) ++e;
+            while (e < 127 && (ldexp(255.0, e) < ext.d || (ldexp(255.0, e) == ext.d && ext.err > 0))) ++e;
             expo[ax] = (uint32_t)(e + 127);
             cell[ax] = ldexp(1.0, e);
         }
@@ -375,8 +387,11 @@ inline void build_mesh_image(const srt_object* objects, size_t count, const std:
             }
             const Node& ch = nodes[w.child[c]];
             for (int ax = 0; ax < 3; ++ax) {
-                double ql = floor(((double)ch.lo[ax] - (double)lo[ax]) / cell[ax]);
-                double qh = ceil(((double)ch.hi[ax] - (double)lo[ax]) / cell[ax]);
+                const Diff dl = diff(ch.lo[ax], lo[ax]), dh = diff(ch.hi[ax], lo[ax]);
+                double ql = floor(dl.d / cell[ax]);  // (a division by a power of two: exact)
+                double qh = ceil(dh.d / cell[ax]);
+                if (ql * cell[ax] == dl.d && dl.err < 0) ql -= 1;
+                if (qh * cell[ax] == dh.d && dh.err > 0) qh += 1;
                 ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql);
                 qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
                 q[ax][c] = (uint8_t)ql;

@@ -1,6 +1,11 @@
 """Host-side builders (scene image, 8-wide BVH, JSON / Scene code) under ASan + UBSan on random and
 degenerate inputs (NaN / inf / huge coordinates, zero-area and duplicate triangles, out-of-range indices,
-mutated JSON), plus a structural check of the BVH: every triangle is referenced by exactly one leaf.
+mutated JSON).  The BVH image of every mesh built — the random ones and adversarial generators: flat grids in the axis planes, a
+4000-unit ground with a fine sphere, 1e5 : 1 slivers, repeated triangles, coordinates up to 9e8, extents of exactly 255 * 2^e
+and an ulp either side, bad mesh indices between valid ones, a deep tree — is decoded the way the kernel decodes it and checked in
+double: every triangle in exactly one leaf, every child box, the root box and the bounding sphere enclose what lies below them,
+max_depth is the walked depth and fits the traversal buffer, the triangle rows are the inputs' bits in (list index, triangle
+index) order, a second build gives the same bytes.
 CPU builds only — GPU sanitizers are not available on this pool."""
 import os
 import shutil
