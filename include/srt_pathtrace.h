@@ -396,6 +396,50 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* params)
 /* Wait, then copy the W*H history lengths L_p of the last call (float, scene rows).  SRT_ERR_STATE before the first call. */
 int srt_read_history_length(srt_context* ctx, float* dst);
 
+/* ---- moving objects and motion vectors (the temporal history across scene edits; ABI 7, backward compatible) -----------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7, srt_temporal_params keeps its 20 bytes
+ * and there is no new SRT_TEMPORAL_* bit.  A sequence of calls that uses none of them runs what it ran before, bit for bit.
+ *
+ * Every object is placed by its `position` alone (spheres; boxes, whose rotation the intersector ignores; meshes, as
+ * vertex + position), so an object edit that keeps the history is a per-object translation.
+ *
+ * srt_update_scene replaces the scene exactly as srt_set_scene does — the same validation, scene image, mesh BVH (rebuilt in
+ * full: an update costs what a set costs), and the same resets of dispatch order, recorded work and cost estimate — so
+ * srt_render, srt_render_gbuffer, srt_pick and srt_estimate_row_costs give the bits a fresh srt_set_scene of the same list
+ * gives.  The one difference: it does NOT invalidate the temporal history.  SRT_ERR_STATE when no scene is set,
+ * SRT_ERR_INVALID_ARG when count differs from the current scene's; both are found before anything is touched, so scene and
+ * history stay as they were.  Otherwise it fails as srt_set_scene fails: after a refused list the context holds the previous
+ * scene or none, and when it holds none the history is dropped too.
+ *
+ * The context keeps the current object list and a snapshot of the list as it stood at the last srt_temporal_accumulate.
+ * Updates between two temporal calls compose: the displacement is taken against the snapshot, not against the previous update.
+ * When srt_temporal_accumulate runs with a valid history it makes, for every object i,
+ *     delta_i = position_now - position_then   (three binary32 subtractions)
+ *     keep_i  = 1 when type, radius, half_size, material and mesh have the same bytes in both lists, else 0.
+ * If every delta_i is zero (either sign) and every keep_i is 1 the call is the one defined above, the same kernel included.
+ * Otherwise the table (count float4 rows (delta.xyz, keep)) is uploaded on the launch stream and the definition changes to
+ *   2'. x~_p = x_p - delta[o_p] (binary32); (a, b, g) = B'^-1 (x~_p - C'.position).
+ *   3'. the plane test is |n_p.(x'_q - x~_p)| <= plane_tolerance * d_p.  Object, normal and bilinear rules are unchanged.
+ *   4'. a pixel whose object has keep = 0 has no history: c_p is kept bit for bit, L_p = n.  (A reshaped or recoloured object
+ *       restarts its own pixels.  The light it sends to its neighbours is not restarted: their history lags behind the edit
+ *       by up to max_samples frames, as it does behind any moved object's shadow and bounce light.)
+ *   6'. the stored history point is x_p, not x~_p.
+ * An object index beyond the table (possible with bound guides only) counts as delta = 0, keep = 1.
+ *
+ * srt_motion_output switches a second output of srt_temporal_accumulate on or off (per context, off by default): W*H float4
+ * (u - x, v - y, Wsum, 0) in the accumulator's layout, scene rows.  u, v are step 2's (2''s) previous-frame coordinates of
+ * pixel (x, y), written whenever the pixel has a history (the history is valid and keep = 1), g > 0 and (u, v) lies in the
+ * window (-1, W) x (-1, H); otherwise (0, 0).  Wsum is W of step 3, the sum of the counted taps' weights (0 when none
+ * counted).  Miss pixels get (0, 0, 0, 0).  The buffer is the handle's own, allocated by the first call that writes it, or
+ * the caller's: srt_bind_motion follows srt_bind_denoised (NULL = own, does not wait), srt_read_motion follows
+ * srt_read_denoised (waits, copies W*H float4 of the current buffer, bound or own; SRT_ERR_STATE unless that buffer is the one
+ * the last call with the output on wrote).  With the output
+ * off nothing is allocated and nothing is written, a bound buffer included. */
+int srt_update_scene(srt_context* ctx, const srt_object* objects, size_t count);
+int srt_motion_output(srt_context* ctx, int enabled);
+int srt_bind_motion(srt_context* ctx, void* d_float4);
+int srt_read_motion(srt_context* ctx, float* dst);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

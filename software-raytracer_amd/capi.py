@@ -38,6 +38,7 @@ EXPORTS = [
     "srt_selftest_arith", "srt_render_gbuffer", "srt_bind_gbuffer", "srt_read_gbuffer",
     "srt_denoise_params_default", "srt_denoise", "srt_bind_denoised", "srt_read_denoised",
     "srt_temporal_params_default", "srt_temporal_accumulate", "srt_read_history_length",
+    "srt_update_scene", "srt_motion_output", "srt_bind_motion", "srt_read_motion",
 ]
 
 
@@ -231,6 +232,10 @@ def open_library(path):
     L.srt_temporal_params_default.argtypes = [C.POINTER(TemporalParams)]
     L.srt_temporal_accumulate.argtypes = [ctx, C.POINTER(TemporalParams)]
     L.srt_read_history_length.argtypes = [ctx, C.POINTER(C.c_float)]
+    L.srt_update_scene.argtypes = [ctx, C.POINTER(Object), C.c_size_t]
+    L.srt_motion_output.argtypes = [ctx, C.c_int]
+    L.srt_bind_motion.argtypes = [ctx, C.c_void_p]
+    L.srt_read_motion.argtypes = [ctx, C.POINTER(C.c_float)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -368,6 +373,13 @@ class PathTracer:
         ptr = C.cast(objects, C.POINTER(Object)) if n else None
         self._ck(self.L.srt_set_scene(self._h, ptr, n))
 
+    def update_scene(self, objects, count=None):
+        """srt_update_scene: set_scene for a list of the same length that keeps the temporal history; the next temporal()
+        reprojects every object by how far its position moved since the previous one."""
+        n = len(objects) if count is None else count
+        ptr = C.cast(objects, C.POINTER(Object)) if n else None
+        self._ck(self.L.srt_update_scene(self._h, ptr, n))
+
     def set_meshes(self, meshes, count=None):
         """EXTENSION: geometry for SRT_OBJ_MESH objects; call before set_scene."""
         n = len(meshes) if count is None else count
@@ -490,6 +502,37 @@ class PathTracer:
         out = np.empty((self.height, self.width), dtype=np.float32)
         self._ck(self.L.srt_read_history_length(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def motion_output(self, on=True):
+        """srt_motion_output: every later temporal() also writes the motion buffer (u - x, v - y, Wsum, 0)."""
+        self._ck(self.L.srt_motion_output(self._h, 1 if on else 0))
+
+    def motion(self):
+        """srt_read_motion: the motion buffer of the last temporal() call that wrote it, (H, W, 4) float32, scene rows."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self.L.srt_read_motion(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def bind_motion(self, tensor):
+        """srt_bind_motion: write the motion buffer into a torch tensor on this tracer's device, (H, W, 4) float32 and
+        contiguous (None: the handle's own buffer).  Checked here, before any native call, as bind_denoised checks."""
+        if tensor is None:
+            self._ck(self.L.srt_bind_motion(self._h, None))
+            return
+        import torch
+
+        shape = (self.height, self.width, 4)
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError("bind_motion: expected a torch.Tensor, got %s" % type(tensor).__name__)
+        if tensor.device.type != "cuda" or tensor.device.index != self.device:
+            raise ValueError("bind_motion: tensor on %s, the tracer renders on cuda:%d" % (tensor.device, self.device))
+        if tensor.dtype != torch.float32:
+            raise TypeError("bind_motion: dtype %s, want torch.float32" % tensor.dtype)
+        if tuple(tensor.shape) != shape:
+            raise ValueError("bind_motion: shape %s, want %s" % (tuple(tensor.shape), shape))
+        if not tensor.is_contiguous():
+            raise ValueError("bind_motion: tensor is not contiguous")
+        self._ck(self.L.srt_bind_motion(self._h, C.c_void_p(tensor.data_ptr())))
 
     def wait(self):
         self._ck(self.L.srt_wait(self._h))

@@ -254,6 +254,23 @@ struct srt_context {
     bool tp_valid = false;
     bool tp_written = false;
 
+    // object motion (srt_update_scene): the object list the scene was last made from, and the list as it stood at the last
+    // srt_temporal_accumulate (the one the history's points belong to).  The table of per-object displacements between the two
+    // is staged in h_tp_table and uploaded on the launch stream; ev_tp_table marks the end of that upload (the staging is not
+    // rewritten before).
+    std::vector<srt_object> objects;
+    std::vector<srt_object> tp_objects;
+    PinnedBuffer<float4> h_tp_table;
+    DeviceBuffer<float4> d_tp_table;
+    Event ev_tp_table;
+    bool tp_table_in_flight = false;
+    // the motion-vector output (srt_motion_output): own buffer (allocated on first use), the caller's (srt_bind_motion; NULL =
+    // own), and the buffer the last call with the output on wrote (srt_read_motion reads no other)
+    bool mv_on = false;
+    DeviceBuffer<float4> d_mv_own;
+    float4* d_mv_bound = nullptr;
+    const float4* mv_last = nullptr;
+
     char error[512] = "";
 };
 
@@ -394,17 +411,17 @@ int srt_destroy(srt_context* ctx) {
     return SRT_OK;
 }
 
-static int set_scene_impl(srt_context* ctx, const srt_object* objects, size_t count) {
+static int set_scene_impl(srt_context* ctx, const char* fn, const srt_object* objects, size_t count) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    if (count && !objects) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: objects is NULL");
-    if (count > 0x3fffffff) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: too many objects");
+    if (count && !objects) return fail(ctx, SRT_ERR_INVALID_ARG, "%s: objects is NULL", fn);
+    if (count > 0x3fffffff) return fail(ctx, SRT_ERR_INVALID_ARG, "%s: too many objects", fn);
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     for (size_t i = 0; i < count; ++i) {
         int t = objects[i].type;
         if (t != SRT_OBJ_SPHERE && t != SRT_OBJ_BOX && t != SRT_OBJ_NONE && t != SRT_OBJ_MESH)
-            return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: object %zu has unknown type %d", i, t);
+            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: object %zu has unknown type %d", fn, i, t);
         if (t == SRT_OBJ_MESH && (objects[i].mesh < 0 || (size_t)objects[i].mesh >= ctx->meshes.size()))
-            return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: object %zu refers to mesh %d but %zu meshes are set (call srt_set_meshes first)",
+            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: object %zu refers to mesh %d but %zu meshes are set (call srt_set_meshes first)", fn,
                         i, objects[i].mesh, ctx->meshes.size());
     }
     // the previous upload may still be in flight from h_scene
@@ -412,6 +429,7 @@ static int set_scene_impl(srt_context* ctx, const srt_object* objects, size_t co
     // from here on the context holds no scene until this call completes: a failure below must not leave
     // a half-replaced one (new image, freed BVH) for srt_render to launch on
     ctx->scene_set = false;
+    ctx->objects.clear();
     const bool no_cluster = dev_switches().no_cluster;
     bool has_mesh = false;
     for (size_t i = 0; i < count; ++i) has_mesh = has_mesh || objects[i].type == SRT_OBJ_MESH;
@@ -421,7 +439,7 @@ static int set_scene_impl(srt_context* ctx, const srt_object* objects, size_t co
         srt::environment_rows(ctx->env, ctx->h_scene[v].data() + srt::SRT_CONST_ENV_ROW);
         // hit_key packs the list index in 15 bits and the primitive id in 16
         if (count >= 32768 || L.nsT + L.nb + L.nm >= 65536)
-            return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: %zu objects (%d sphere slots + %d boxes + %d meshes) exceed the 32767-object limit",
+            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: %zu objects (%d sphere slots + %d boxes + %d meshes) exceed the 32767-object limit", fn,
                         count, L.nsT, L.nb, L.nm);
         // an image that does not fit into LDS next to the per-wave scratch stays in HBM (slower kernel
         // instantiation, same bits); the pick kernel runs one wave, so it is judged separately.  The LDS instantiations also
@@ -443,7 +461,7 @@ static int set_scene_impl(srt_context* ctx, const srt_object* objects, size_t co
         for (size_t i = 0; i < count; ++i)
             if (objects[i].type == SRT_OBJ_MESH) total_tris += ctx->meshes[(size_t)objects[i].mesh].indices.size() / 3;
         if (total_tris >= (1ull << 24))
-            return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: %llu mesh triangles exceed the limit of 2^24 - 1 per scene", total_tris);
+            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: %llu mesh triangles exceed the limit of 2^24 - 1 per scene", fn, total_tris);
     }
     srt::build_mesh_image(objects, count, ctx->meshes, ctx->layout[0].nsT + ctx->layout[0].nb, ctx->mesh_image);
     // (allocated to size for every scene, not grown)
@@ -453,12 +471,12 @@ static int set_scene_impl(srt_context* ctx, const srt_object* objects, size_t co
     if (ctx->mesh_image.n_tris > 0) {
         // strict depth-first traversal (the kernel's last resort) keeps at most 7 entries per level
         if (7 * ctx->mesh_image.max_depth + 80 > srt::MESH_Q)
-            return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: BVH too deep (%d levels)", ctx->mesh_image.max_depth);
+            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: BVH too deep (%d levels)", fn, ctx->mesh_image.max_depth);
         if (ctx->mesh_image.n_nodes >= (1 << 26) || ctx->mesh_image.n_tris >= (1 << 24))  // (item encoding of the traversal queues)
-            return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: mesh too large (%d triangles)", ctx->mesh_image.n_tris);
+            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: mesh too large (%d triangles)", fn, ctx->mesh_image.n_tris);
         for (int ax = 0; ax < 3; ++ax)  // keeps cell * slope finite in the kernel's plane distances
             if (!(fabsf(ctx->mesh_image.center[ax]) + ctx->mesh_image.half[ax] <= 1e9f))
-                return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: mesh coordinates beyond 1e9 are not supported");
+                return fail(ctx, SRT_ERR_INVALID_ARG, "%s: mesh coordinates beyond 1e9 are not supported", fn);
         SRT_HIP(ctx, ctx->d_bvh_nodes.ensure(ctx->mesh_image.nodes.size() * sizeof(float4)));
         SRT_HIP(ctx, ctx->d_bvh_tris.ensure(ctx->mesh_image.tris.size() * sizeof(float4)));
         SRT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh_nodes, ctx->mesh_image.nodes.data(), ctx->mesh_image.nodes.size() * sizeof(float4),
@@ -469,6 +487,7 @@ static int set_scene_impl(srt_context* ctx, const srt_object* objects, size_t co
         SRT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh_gidpos, ctx->mesh_image.gidpos.data(), ctx->mesh_image.gidpos.size() * sizeof(int32_t),
                                     hipMemcpyHostToDevice, ctx->stream));
     }
+    ctx->objects.assign(objects, objects + count);
     ctx->scene_set = true;
     ctx->order_stale = true;
     ctx->estimate_stale = true;
@@ -481,17 +500,34 @@ static int set_scene_impl(srt_context* ctx, const srt_object* objects, size_t co
 }
 
 // Host-side allocation failures (std::bad_alloc from the image / BVH builders) must not cross the C boundary.
-int srt_set_scene(srt_context* ctx, const srt_object* objects, size_t count) {
-    if (ctx) ctx->tp_valid = false;  // the temporal history's object indices and points belong to the old scene
+static int set_scene_guarded(srt_context* ctx, const char* fn, const srt_object* objects, size_t count) {
     try {
-        return set_scene_impl(ctx, objects, count);
+        return set_scene_impl(ctx, fn, objects, count);
     } catch (const std::bad_alloc&) {
         if (ctx) ctx->scene_set = false;
-        return fail(ctx, SRT_ERR_OOM, "srt_set_scene: host allocation failed");
+        return fail(ctx, SRT_ERR_OOM, "%s: host allocation failed", fn);
     } catch (const std::exception& e) {
         if (ctx) ctx->scene_set = false;
-        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_scene: %s", e.what());
+        return fail(ctx, SRT_ERR_INVALID_ARG, "%s: %s", fn, e.what());
     }
+}
+
+int srt_set_scene(srt_context* ctx, const srt_object* objects, size_t count) {
+    if (ctx) ctx->tp_valid = false;  // the temporal history's object indices and points belong to the old scene
+    return set_scene_guarded(ctx, "srt_set_scene", objects, count);
+}
+
+// srt_set_scene for a list of the same length that keeps the temporal history: srt_temporal_accumulate compares the new list
+// with the one its history was stored for and reprojects every object by its displacement.
+int srt_update_scene(srt_context* ctx, const srt_object* objects, size_t count) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    if (!ctx->scene_set) return fail(ctx, SRT_ERR_STATE, "srt_update_scene: srt_set_scene has not been called");
+    if (count != ctx->objects.size())
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_update_scene: %zu objects, the scene has %zu (a list of another length goes through srt_set_scene)",
+                    count, ctx->objects.size());
+    const int rc = set_scene_guarded(ctx, "srt_update_scene", objects, count);
+    if (!ctx->scene_set) ctx->tp_valid = false;  // the refused list left no scene: nothing for the history to belong to
+    return rc;
 }
 
 static int set_meshes_impl(srt_context* ctx, const srt_mesh* meshes, size_t count) {
@@ -1372,6 +1408,44 @@ static bool invert_ray_basis(const srt_camera& c, int W, int H, float inv[9]) {
     return true;
 }
 
+// The per-object motion table of this call: row i = (position now - position at the previous call, keep), keep = 1 when every
+// other field of the object has the same bytes in both lists.  moved = false (and nothing uploaded) when no object moved or
+// changed: the call then runs the kernel without a table.
+static int build_motion_table(srt_context* ctx, bool& moved) {
+    const size_t n = ctx->objects.size();
+    moved = false;
+    for (size_t i = 0; i < n && !moved; ++i) {
+        srt_object then = ctx->tp_objects[i];
+        const srt_object& now = ctx->objects[i];
+        for (int k = 0; k < 3; ++k) {
+            moved = moved || now.position[k] - then.position[k] != 0.0f;
+            then.position[k] = now.position[k];
+        }
+        moved = moved || memcmp(&then, &now, sizeof(srt_object)) != 0;
+    }
+    if (!moved) return SRT_OK;
+    if (ctx->tp_table_in_flight) SRT_HIP(ctx, hipEventSynchronize(ctx->ev_tp_table));
+    ctx->tp_table_in_flight = false;
+    SRT_HIP(ctx, ctx->h_tp_table.ensure(n * sizeof(float4)));
+    SRT_HIP(ctx, ctx->d_tp_table.ensure(n * sizeof(float4)));
+    if (!ctx->ev_tp_table.h) SRT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_tp_table.h, hipEventDisableTiming));
+    float4* rows = ctx->h_tp_table;
+    for (size_t i = 0; i < n; ++i) {
+        srt_object then = ctx->tp_objects[i];
+        const srt_object& now = ctx->objects[i];
+        float d[3];
+        for (int k = 0; k < 3; ++k) {
+            d[k] = now.position[k] - then.position[k];
+            then.position[k] = now.position[k];
+        }
+        rows[i] = make_float4(d[0], d[1], d[2], memcmp(&then, &now, sizeof(srt_object)) == 0 ? 1.0f : 0.0f);
+    }
+    SRT_HIP(ctx, hipMemcpyAsync(ctx->d_tp_table, rows, n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    SRT_HIP(ctx, hipEventRecord(ctx->ev_tp_table, ctx->stream));
+    ctx->tp_table_in_flight = true;
+    return SRT_OK;
+}
+
 int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
     if (!ctx || !t) return SRT_ERR_INVALID_ARG;
     if (t->samples == 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_temporal_accumulate: samples must be >= 1");
@@ -1408,12 +1482,49 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
     T.max_samples = t->max_samples;
     T.plane_tolerance = t->plane_tolerance;
     T.normal_threshold = t->normal_threshold;
-    hipLaunchKernelGGL(srt::temporal_kernel, frame_tile_grid(ctx), dim3(srt::WG_THREADS), 0, ctx->stream, T);
+    // object motion: only a valid history of a list of the same length can have moved
+    bool motion = false;
+    if (T.valid && !ctx->objects.empty() && ctx->objects.size() == ctx->tp_objects.size()) {
+        if (const int rc = build_motion_table(ctx, motion)) return rc;
+    }
+    if (motion) T.table = ctx->d_tp_table, T.table_count = (int)ctx->objects.size();
+    if (ctx->mv_on) {
+        if (!ctx->d_mv_bound) SRT_HIP(ctx, ctx->d_mv_own.ensure(px * sizeof(float4)));
+        T.motion = bound_or_own(ctx->d_mv_bound, ctx->d_mv_own);
+    }
+    const dim3 grid = frame_tile_grid(ctx), block(srt::WG_THREADS);
+    if (!motion && !ctx->mv_on) hipLaunchKernelGGL(srt::temporal_kernel, grid, block, 0, ctx->stream, T);
+    else if (!motion) hipLaunchKernelGGL((srt::temporal_motion_kernel<false, true>), grid, block, 0, ctx->stream, T);
+    else if (!ctx->mv_on) hipLaunchKernelGGL((srt::temporal_motion_kernel<true, false>), grid, block, 0, ctx->stream, T);
+    else hipLaunchKernelGGL((srt::temporal_motion_kernel<true, true>), grid, block, 0, ctx->stream, T);
     SRT_HIP(ctx, hipGetLastError());
     ctx->tp_cur = b;
     ctx->tp_cam = ctx->camera.cam;
+    ctx->tp_objects = ctx->objects;  // the list this history's points belong to
     ctx->tp_valid = true;
     ctx->tp_written = true;
+    if (ctx->mv_on) ctx->mv_last = T.motion;
+    return SRT_OK;
+}
+
+int srt_motion_output(srt_context* ctx, int enabled) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    ctx->mv_on = enabled != 0;
+    return SRT_OK;
+}
+
+int srt_bind_motion(srt_context* ctx, void* d_float4) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    ctx->d_mv_bound = (float4*)d_float4;  // (no synchronisation: an enqueued call keeps the buffer it was given)
+    return SRT_OK;
+}
+
+int srt_read_motion(srt_context* ctx, float* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const float4* src = bound_or_own(ctx->d_mv_bound, ctx->d_mv_own);
+    if (!src || src != ctx->mv_last) return fail(ctx, SRT_ERR_STATE, "srt_read_motion: no srt_temporal_accumulate has written this buffer yet");
+    if (const int rc = finish_stream(ctx)) return rc;
+    SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
 

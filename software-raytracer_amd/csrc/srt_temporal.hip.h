@@ -9,6 +9,9 @@
 // reads what another writes and no grid-wide barrier is needed.
 // Work shape as denoise_kernel: a wave per 8 x 8 tile (lane -> x = lane & 7, y = lane >> 3), four waves per workgroup
 // (16 x 16 pixels), so every float4 row segment a wave touches is one 128-byte line.  No LDS, no atomics, no scratch.
+// Moving objects (srt_update_scene) add a per-object table (displacement since the previous call, keep flag), a per-lane
+// 16-byte gather keyed by the pixel's object index; srt_motion_output adds one float4 store per pixel.  Both are template
+// options of the one pixel routine, and the call that uses neither runs temporal_kernel as it always was.
 #pragma once
 
 #include "srt_kernel.hip.h"
@@ -38,9 +41,17 @@ struct TemporalLaunch {
     float max_samples;           // L_max
     float plane_tolerance;       // sigma_t
     float normal_threshold;      // <= -1: term off
+    // object motion and the motion-vector output (srt_update_scene, srt_motion_output); appended behind the fields above so
+    // that the plain instantiation reads its arguments where it always did
+    const float4* table;         // MOTION: table_count rows (position now - position at the previous call, keep), else unused
+    int table_count;             // rows of the table; an object index beyond it (bound guides) has moved by 0 and is kept
+    float4* motion;              // MV: W*H rows (u - x, v - y, sum of the counted taps' weights, 0), else unused
 };
 
-__global__ void __launch_bounds__(WG_THREADS) temporal_kernel(const TemporalLaunch T) {
+// MOTION: the hit object's row of T.table moves x_p back to where the object was at the previous call (x~_p = x_p - delta),
+// and a row with keep == 0 (the object was reshaped or recoloured) leaves the pixel without history.  MV: T.motion is written.
+template <bool MOTION, bool MV>
+__device__ __forceinline__ void temporal_pixel(const TemporalLaunch& T) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = (int)blockIdx.x * WG_W + (wave % WG_TILES_X) * TILE_W + (lane & 7);
     const int y = (int)blockIdx.y * WG_H + (wave / WG_TILES_X) * TILE_H + (lane >> 3);
@@ -53,14 +64,23 @@ __global__ void __launch_bounds__(WG_THREADS) temporal_kernel(const TemporalLaun
         T.next.pos_object[p] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
         T.next.normal[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (T.framebuffer) T.framebuffer[(size_t)(H - 1 - y) * W + x] = tone_map(T.acc[p]);
+        if (MV) T.motion[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
     const float4 c = T.acc[p];
     const float4 nd = T.normal_depth[p];
     const float4 xx = T.position[p];
+    float4 xt = xx;  // x~_p
+    bool keep = true;
+    if (MOTION && op < T.table_count) {
+        const float4 row = T.table[op];
+        xt = make_float4(xx.x - row.x, xx.y - row.y, xx.z - row.z, 0.0f);
+        keep = row.w != 0.0f;
+    }
+    float mu = 0.0f, mv = 0.0f;
     float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f;
-    if (T.valid) {
-        const float rx = xx.x - T.cam_pos[0], ry = xx.y - T.cam_pos[1], rz = xx.z - T.cam_pos[2];
+    if (T.valid && keep) {
+        const float rx = xt.x - T.cam_pos[0], ry = xt.y - T.cam_pos[1], rz = xt.z - T.cam_pos[2];
         const float a = T.inv[0] * rx + T.inv[1] * ry + T.inv[2] * rz;
         const float b = T.inv[3] * rx + T.inv[4] * ry + T.inv[5] * rz;
         const float g = T.inv[6] * rx + T.inv[7] * ry + T.inv[8] * rz;
@@ -70,6 +90,7 @@ __global__ void __launch_bounds__(WG_THREADS) temporal_kernel(const TemporalLaun
             // some tap of positive weight lies inside the frame only for u in (-1, W) and v in (-1, H) (also keeps NaN and
             // huge values away from the integer conversion)
             if (u > -1.0f && u < (float)W && v > -1.0f && v < (float)H) {
+                if (MV) mu = u - (float)x, mv = v - (float)y;
                 const float fu = floorf(u), fv = floorf(v);
                 const int x0 = (int)fu, y0 = (int)fv;
                 const float fx = u - fu, fy = v - fv;
@@ -83,7 +104,7 @@ __global__ void __launch_bounds__(WG_THREADS) temporal_kernel(const TemporalLaun
                     const size_t q = (size_t)qx + (size_t)qy * (size_t)W;
                     const float4 po = T.prev.pos_object[q];
                     if (__float_as_int(po.w) != op) continue;  // another object or a miss
-                    const float d = nd.x * (po.x - xx.x) + nd.y * (po.y - xx.y) + nd.z * (po.z - xx.z);
+                    const float d = nd.x * (po.x - xt.x) + nd.y * (po.y - xt.y) + nd.z * (po.z - xt.z);
                     if (!(fabsf(d) <= tol)) continue;
                     if (use_n) {
                         const float4 nq = T.prev.normal[q];
@@ -112,6 +133,16 @@ __global__ void __launch_bounds__(WG_THREADS) temporal_kernel(const TemporalLaun
     T.next.pos_object[p] = make_float4(xx.x, xx.y, xx.z, __int_as_float(op));
     T.next.normal[p] = make_float4(nd.x, nd.y, nd.z, 0.0f);
     if (T.framebuffer) T.framebuffer[(size_t)(H - 1 - y) * W + x] = tone_map(out);
+    if (MV) T.motion[p] = make_float4(mu, mv, sw, 0.0f);
+}
+
+// the call without object motion and without the motion output
+__global__ void __launch_bounds__(WG_THREADS) temporal_kernel(const TemporalLaunch T) { temporal_pixel<false, false>(T); }
+
+// ... and with either or both
+template <bool MOTION, bool MV>
+__global__ void __launch_bounds__(WG_THREADS) temporal_motion_kernel(const TemporalLaunch T) {
+    temporal_pixel<MOTION, MV>(T);
 }
 
 }  // namespace srt

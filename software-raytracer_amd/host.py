@@ -16,7 +16,7 @@ _LIB = os.path.join(_PKG, "libsrt_host.so")
 EXPORTS = [
     "srt_host_scene_load", "srt_host_scene_new", "srt_host_scene_free", "srt_host_scene_count",
     "srt_host_scene_objects", "srt_host_scene_mesh_count", "srt_host_scene_mesh", "srt_host_scene_error", "srt_host_scene_name", "srt_host_scene_object_name",
-    "srt_host_scene_add", "srt_host_scene_remove", "srt_host_scene_save_as", "srt_host_scene_dump",
+    "srt_host_scene_add", "srt_host_scene_remove", "srt_host_scene_set_position", "srt_host_scene_save_as", "srt_host_scene_dump",
     "srt_host_format_double", "srt_host_json_roundtrip", "srt_host_rotate_about_axis", "srt_host_last_error",
     "srt_host_renderer_create", "srt_host_renderer_destroy", "srt_host_renderer_set_scene",
     "srt_host_renderer_set_band", "srt_host_renderer_settings", "srt_host_renderer_set_camera",
@@ -26,6 +26,7 @@ EXPORTS = [
     "srt_host_renderer_render_gbuffer", "srt_host_renderer_read_gbuffer", "srt_host_renderer_denoise", "srt_host_renderer_read_denoised",
     "srt_host_renderer_temporal", "srt_host_renderer_read_history_length", "srt_host_renderer_render_temporal_frame",
     "srt_host_renderer_move_camera",
+    "srt_host_renderer_update_scene", "srt_host_renderer_motion_output", "srt_host_renderer_read_motion",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -70,6 +71,8 @@ def load_library():
     L.srt_host_scene_add.restype = None
     L.srt_host_scene_remove.argtypes = [vp, C.c_size_t]
     L.srt_host_scene_remove.restype = C.c_int
+    L.srt_host_scene_set_position.argtypes = [vp, C.c_size_t, C.c_float, C.c_float, C.c_float]
+    L.srt_host_scene_set_position.restype = C.c_int
     L.srt_host_scene_save_as.argtypes = [vp, C.c_char_p]
     L.srt_host_scene_save_as.restype = None
     L.srt_host_format_double.argtypes = [C.c_double, C.c_char_p, C.c_size_t]
@@ -107,6 +110,9 @@ def load_library():
     L.srt_host_renderer_read_history_length.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_render_temporal_frame.argtypes = [vp, C.c_uint32, C.c_int]
     L.srt_host_renderer_move_camera.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.srt_host_renderer_update_scene.argtypes = [vp, vp]
+    L.srt_host_renderer_motion_output.argtypes = [vp, C.c_int]
+    L.srt_host_renderer_read_motion.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_multi_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]
     L.srt_host_multi_create.restype = vp
     L.srt_host_multi_destroy.argtypes = [vp]
@@ -187,6 +193,11 @@ class Scene:
     def remove(self, index):
         return bool(self.L.srt_host_scene_remove(self._h, index))
 
+    def set_position(self, index, position):
+        """transform.position of object `index` (the inspector's position edit)."""
+        if not self.L.srt_host_scene_set_position(self._h, index, *[float(v) for v in position]):
+            raise IndexError("scene has no object %d" % index)
+
     def save_as(self, path):
         self.L.srt_host_scene_save_as(self._h, path.encode())
 
@@ -246,6 +257,10 @@ class Renderer:
 
     def set_scene(self, scene):
         self._ck(self.L.srt_host_renderer_set_scene(self._h, scene._h))
+
+    def update_scene(self, scene):
+        """PathTraceRenderer::UpdateScene: an object edit that keeps the temporal history (srt_update_scene)."""
+        self._ck(self.L.srt_host_renderer_update_scene(self._h, scene._h))
 
     def set_band(self, rb, re):
         self._ck(self.L.srt_host_renderer_set_band(self._h, rb, re))
@@ -345,6 +360,16 @@ class Renderer:
         p = (C.c_float * 3)(*[float(x) for x in position])
         b = (C.c_float * 9)(*[float(x) for x in basis9])
         self._ck(self.L.srt_host_renderer_move_camera(self._h, p, b))
+
+    def motion_output(self, on=True):
+        """PathTraceRenderer::MotionOutput: later temporal frames also write the motion buffer."""
+        self._ck(self.L.srt_host_renderer_motion_output(self._h, 1 if on else 0))
+
+    def motion(self):
+        """PathTraceRenderer::ReadMotion: (H, W, 4) float32 (u - x, v - y, Wsum, 0), scene rows."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_motion(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     def stats(self):
         s = Stats()

@@ -52,6 +52,13 @@ const char* srt_host_scene_object_name(const srt_host_scene* s, size_t i) {
     return i < s->scene.GetObjects().size() ? s->scene.GetObjects()[i].name.c_str() : "";
 }
 // Scene::AddObject (Scene.hpp:105-107)
+// transform.position of object `index` (the inspector's position edit); 0 when there is no such object
+int srt_host_scene_set_position(srt_host_scene* s, size_t index, float x, float y, float z) {
+    if (index >= s->scene.Objects().size()) return 0;
+    float* p = s->scene.Objects()[index].position;
+    p[0] = x, p[1] = y, p[2] = z;
+    return 1;
+}
 void srt_host_scene_add(srt_host_scene* s, const srt_object* o, const char* name) {
     SceneObject so;
     so.type = (RendererType)o->type;
@@ -223,6 +230,10 @@ int srt_host_renderer_move_camera(srt_host_renderer* h, const float* pos, const 
     t.forward = Vec3(right_up_forward[6], right_up_forward[7], right_up_forward[8]);
     return 0;
 }
+// an object edit that keeps the temporal history (srt_update_scene), and the motion-vector output (srt_motion_output / srt_read_motion)
+int srt_host_renderer_update_scene(srt_host_renderer* h, srt_host_scene* s) { SRT_HOST_TRY(h, h->r->UpdateScene(s->scene)) }
+int srt_host_renderer_motion_output(srt_host_renderer* h, int on) { SRT_HOST_TRY(h, h->r->MotionOutput(on != 0)) }
+int srt_host_renderer_read_motion(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadMotion(dst)) }
 int srt_host_renderer_stats(srt_host_renderer* h, srt_stats* out) { SRT_HOST_TRY(h, *out = h->r->Stats()) }
 void* srt_host_renderer_handle(srt_host_renderer* h) { return h->r->handle(); }
 

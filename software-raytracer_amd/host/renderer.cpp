@@ -1,6 +1,9 @@
 // renderer.cpp — see renderer.hpp.
 #include "renderer.hpp"
 
+#include <algorithm>
+#include <cstring>
+
 namespace srt_host {
 
 void PathTraceRenderer::check(int rc, const char* what) {
@@ -25,8 +28,45 @@ void PathTraceRenderer::SetScene(const Scene& scene) {
     std::vector<srt_object> flat = scene.Flatten();
     std::vector<srt_mesh> meshes = scene.MeshViews();  // EXTENSION: geometry of "Mesh" renderers
     check(srt_set_meshes(ctx_, meshes.data(), meshes.size()), "srt_set_meshes");
+    scene_set_ = false;
     check(srt_set_scene(ctx_, flat.data(), flat.size()), "srt_set_scene");
+    scene_set_ = true;
+    scene_count_ = flat.size();
+    mesh_vertices_.clear();
+    mesh_indices_.clear();
+    for (const srt_mesh& m : meshes) {
+        mesh_vertices_.emplace_back(m.vertices, m.vertices + 3 * m.vertex_count);
+        mesh_indices_.emplace_back(m.indices, m.indices + 3 * m.triangle_count);
+    }
     Invalidate();
+}
+
+bool PathTraceRenderer::SameMeshes(const std::vector<srt_mesh>& meshes) const {
+    if (meshes.size() != mesh_vertices_.size()) return false;
+    for (size_t i = 0; i < meshes.size(); ++i) {
+        const srt_mesh& m = meshes[i];
+        if (3 * m.vertex_count != mesh_vertices_[i].size() || 3 * m.triangle_count != mesh_indices_[i].size()) return false;
+        if (!std::equal(mesh_vertices_[i].begin(), mesh_vertices_[i].end(), m.vertices, [](float a, float b) { return std::memcmp(&a, &b, 4) == 0; }))
+            return false;
+        if (!std::equal(mesh_indices_[i].begin(), mesh_indices_[i].end(), m.indices)) return false;
+    }
+    return true;
+}
+
+void PathTraceRenderer::UpdateScene(const Scene& scene) {
+    std::vector<srt_object> flat = scene.Flatten();
+    if (!scene_set_ || flat.size() != scene_count_ || !SameMeshes(scene.MeshViews())) {
+        SetScene(scene);
+        return;
+    }
+    const int rc = srt_update_scene(ctx_, flat.data(), flat.size());
+    if (rc != SRT_OK) {
+        // a refused list may have left the context without a scene: start afresh (the next edit goes through SetScene)
+        scene_set_ = false;
+        Invalidate();
+    }
+    check(rc, "srt_update_scene");
+    doSetFrame_ = true;
 }
 
 void PathTraceRenderer::SetEnvironment(const srt_environment& env) {
@@ -156,6 +196,10 @@ void PathTraceRenderer::ReadDenoised(float* dst_rgba) { check(srt_read_denoised(
 void PathTraceRenderer::Temporal(const srt_temporal_params& params) { check(srt_temporal_accumulate(ctx_, &params), "srt_temporal_accumulate"); }
 
 void PathTraceRenderer::ReadHistoryLength(float* dst) { check(srt_read_history_length(ctx_, dst), "srt_read_history_length"); }
+
+void PathTraceRenderer::MotionOutput(bool on) { check(srt_motion_output(ctx_, on ? 1 : 0), "srt_motion_output"); }
+
+void PathTraceRenderer::ReadMotion(float* dst) { check(srt_read_motion(ctx_, dst), "srt_read_motion"); }
 
 void PathTraceRenderer::RenderTemporalFrame(uint32_t spp, bool denoise) {
     if (spp == 0) throw RendererError(SRT_ERR_INVALID_ARG, "RenderTemporalFrame: spp must be >= 1");

@@ -79,6 +79,12 @@ class PathTraceRenderer {
 
     // ObjectsToRender = scene.GetObjects(); doSetFrame = true   (:293, :421-423)
     void SetScene(const Scene& scene);
+    // An object edit that keeps the temporal history (srt_update_scene): the same list with other positions (or other fields,
+    // whose objects then restart their own pixels).  doSetFrame = true for the plain accumulate loop, as any edit; the next
+    // RenderTemporalFrame does NOT reset but reprojects every object by its displacement.  Falls back to SetScene when no
+    // scene was set, the number of objects changed or the geometry of a mesh changed (srt_update_scene keeps the meshes of
+    // the last srt_set_meshes).
+    void UpdateScene(const Scene& scene);
     void SetEnvironment(const srt_environment& env);
     // restrict rendering to memory rows [begin,end) (multi-GPU row stripes)
     void SetRowBand(int begin, int end);
@@ -123,6 +129,10 @@ class PathTraceRenderer {
     // waits and copies the W x H history lengths (scene rows).
     void Temporal(const srt_temporal_params& params);
     void ReadHistoryLength(float* dst);
+    // Motion vectors (srt_motion_output): with `on` every later Temporal / RenderTemporalFrame also writes W x H float4
+    // (u - x, v - y, Wsum, 0); ReadMotion waits and copies them (scene rows).
+    void MotionOutput(bool on);
+    void ReadMotion(float* dst);
     // One frame of a moving camera that keeps its samples (whole frame only): push the camera, render `spp` samples with
     // SRT_RENDER_RESET and seed + k (k = the number of temporal frames this renderer has rendered before, so that the noise
     // does not stay fixed to the screen), the first-hit guides, srt_temporal_accumulate with the library's defaults
@@ -140,6 +150,11 @@ class PathTraceRenderer {
     int width_, height_;
     int row_begin_, row_end_;
     bool doSetFrame_ = false;
+    bool scene_set_ = false;        // SetScene has succeeded
+    size_t scene_count_ = 0;        // ... with this many objects (UpdateScene takes lists of that length)
+    std::vector<std::vector<float>> mesh_vertices_;     // ... and this mesh geometry (UpdateScene takes no other)
+    std::vector<std::vector<uint32_t>> mesh_indices_;
+    bool SameMeshes(const std::vector<srt_mesh>& meshes) const;
     bool temporal_reset_ = true;    // the next RenderTemporalFrame drops the history
     uint32_t temporal_frames_ = 0;  // RenderTemporalFrame calls so far (the seed offset)
     bool first_frame_ = true;

@@ -64,7 +64,8 @@ static void usage() {
     std::fprintf(stderr,
                  "usage: srt_render --scene FILE [--width 1280] [--height 720] [--spp 32] [--bounces 2]\n"
                  "                  [--fov 55] [--seed 0] [--device 0 | --devices 0,1,2,...] [--out frame.ppm] [--resave FILE]\n"
-                 "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]]\n"
+                 "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]\n"
+                 "                  [--move-object IDX:DX,DY,DZ]...]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
                  "             and means the same), --equal-bands: bands of equal height\n"
@@ -76,13 +77,20 @@ static void usage() {
                  "  --temporal: render FRAMES frames of --spp samples each while the camera moves, keeping samples across\n"
                  "             frames (srt_temporal_accumulate), and write the last one to --out (--denoise PATH: also its\n"
                  "             denoised form); before every frame but the first the camera moves by R, U, F along its right,\n"
-                 "             up and forward axes (--move) and turns by DEG degrees about world up (--turn); single device only\n");
+                 "             up and forward axes (--move) and turns by DEG degrees about world up (--turn); single device only\n"
+                 "  --move-object: with --temporal, before every frame but the first add DX, DY, DZ to the position of object IDX\n"
+                 "             (list order) and keep the history across the edit (srt_update_scene); may be given several times\n");
 }
 
 int main(int argc, char** argv) {
     std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise;
     int temporal = 0;
     float move[3] = {0, 0, 0}, turn_deg = 0;
+    struct ObjectMove {
+        size_t index;
+        float step[3];
+    };
+    std::vector<ObjectMove> object_moves;
     int W = 1280, H = 720, spp = 32, bounces = 2, fov = 55, device = 0;  // Raytracer.cpp:26-27,31-32
     unsigned seed = 0;
     std::vector<int> devices;
@@ -130,10 +138,31 @@ int main(int argc, char** argv) {
                 p = end + 1;
             }
         }
+        else if (!std::strcmp(argv[i], "--move-object")) {
+            const char* p = need("--move-object");
+            char* end = nullptr;
+            ObjectMove m{};
+            m.index = (size_t)std::strtoul(p, &end, 10);
+            bool ok = end != p && *end == ':';
+            for (int k = 0; ok && k < 3; ++k) {
+                p = end + 1;
+                m.step[k] = std::strtof(p, &end);
+                ok = end != p && (k < 2 ? *end == ',' : !*end);
+            }
+            if (!ok) {
+                std::fprintf(stderr, "--move-object wants IDX:DX,DY,DZ\n");
+                return 2;
+            }
+            object_moves.push_back(m);
+        }
         else {
             usage();
             return 2;
         }
+    }
+    if (!object_moves.empty() && !temporal) {
+        std::fprintf(stderr, "--move-object needs --temporal\n");
+        return 2;
     }
     if (scene_path.empty() || W <= 0 || H <= 0 || spp <= 0 || temporal < 0) {
         usage();
@@ -152,6 +181,11 @@ int main(int argc, char** argv) {
     if (!scene.lastError().empty()) std::fprintf(stderr, "scene: %s\n", scene.lastError().c_str());  // Scene.hpp:76
     std::fprintf(stderr, "scene %s: %zu objects\n", scene_path.c_str(), scene.GetObjects().size());
     if (!resave.empty()) scene.SaveAs(resave);
+    for (const auto& m : object_moves)
+        if (m.index >= scene.GetObjects().size()) {
+            std::fprintf(stderr, "--move-object: the scene has no object %zu\n", m.index);
+            return 2;
+        }
     auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {
         FILE* f = std::fopen(path.c_str(), "wb");
         if (!f) {
@@ -214,6 +248,16 @@ int main(int argc, char** argv) {
                     Transform& c = r.camera;
                     c.position = c.position + c.right * move[0] + c.up * move[1] + c.forward * move[2];
                     if (turn != 0) c.RotateAboutAxis(turn, world_up);
+                    // object edits: each moved object's position is printed exactly, like the camera
+                    for (const auto& m : object_moves) {
+                        float* pos = scene.Objects()[m.index].position;
+                        for (int a = 0; a < 3; ++a) pos[a] = pos[a] + m.step[a];
+                    }
+                    if (!object_moves.empty()) r.UpdateScene(scene);
+                }
+                for (const auto& m : object_moves) {
+                    const float* pos = scene.GetObjects()[m.index].position;
+                    std::fprintf(stderr, "temporal frame %d object %zu position %.9g %.9g %.9g\n", k, m.index, pos[0], pos[1], pos[2]);
                 }
                 const Transform& c = r.camera;
                 std::fprintf(stderr, "temporal frame %d camera %.9g %.9g %.9g  %.9g %.9g %.9g  %.9g %.9g %.9g  %.9g %.9g %.9g\n", k, c.position.x,

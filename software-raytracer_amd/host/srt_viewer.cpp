@@ -26,6 +26,9 @@
 // and, standing in for the inspector's "Settings" (:461-483):
 //   M  switch render mode (SIMPLEDRAW)     F / G  FOV -/+ 1 (15..103)     B / N  light bounces -/+ 1
 //   1..4  render scale 0.25 / 0.5 / 0.75 / 1.0 (clamped to 0.5 in preview mode, :481-483)
+//   I / K, J / L, U / O  (held) the inspector's position edit (Object.hpp OnGUI, "Position"): move the selected object along
+//      +z / -z, -x / +x, +y / -y by moveSpeed * delta per frame (PathTraceRenderer::UpdateScene); in temporal mode the edit keeps
+//      the history, outside it raises doSetFrame as every edit does
 //   T  temporal mode (not in the reference): every frame is a full path-traced frame of one sample
 //      (PathTraceRenderer::RenderTemporalFrame) that keeps its samples across camera moves by reprojection; there, turning
 //      and moving the camera do not call Invalidate(), every other edit still does (and so does toggling T)
@@ -51,6 +54,7 @@ namespace {
 
 struct InputState {  // one frame's worth, what SDLInputManager hands the loop
     bool w = false, a = false, s = false, d = false, e = false, q = false, lshift = false;  // held
+    bool i = false, k = false, j = false, l = false, u = false, o = false;                  // held: move the selected object
     bool right_held = false;
     int mouse_dx = 0, mouse_dy = 0;  // relative motion of this frame
     bool left_down = false;          // edge
@@ -69,6 +73,7 @@ class ViewerCore {
     bool paused() const { return pause_; }
     bool temporal() const { return temporal_; }
     int selected() const { return r_.selectedObject; }
+    const Scene& scene() const { return scene_; }
 
     // one pass of the loop body between "thread safe after this point" (:385) and the release of the
     // workers (:592-595); delta in seconds (:558-560)
@@ -91,6 +96,21 @@ class ViewerCore {
         if (in.e) p = p + r_.camera.up * speed;
         if (in.q) p = p - r_.camera.up * speed;
         if ((p.x != before.x || p.y != before.y || p.z != before.z) && !temporal_) r_.Invalidate();  // :519-521
+        if (r_.selectedObject >= 0 && (size_t)r_.selectedObject < scene_.GetObjects().size()) {
+            const float step = moveSpeed * delta;
+            float* op = scene_.Objects()[(size_t)r_.selectedObject].position;
+            const float was[3] = {op[0], op[1], op[2]};
+            if (in.i) op[2] = op[2] + step;
+            if (in.k) op[2] = op[2] - step;
+            if (in.l) op[0] = op[0] + step;
+            if (in.j) op[0] = op[0] - step;
+            if (in.u) op[1] = op[1] + step;
+            if (in.o) op[1] = op[1] - step;
+            if (op[0] != was[0] || op[1] != was[1] || op[2] != was[2]) {
+                r_.UpdateScene(scene_);
+                if (!temporal_) r_.Invalidate();
+            }
+        }
         if (in.left_down) {  // :525-541
             if (r_.selectedObject >= 0) r_.selectedObject = -1;
             else r_.selectedObject = r_.Pick(in.mouse_x, in.mouse_y);
@@ -148,10 +168,13 @@ void write_ppm(PathTraceRenderer& r, const std::string& path) {
 }
 
 // Script of the headless back end, one command per line ('#' starts a comment):
-//   delta SECONDS | hold KEYS | release KEYS   (KEYS out of W A S D E Q and L for LSHIFT)
+//   delta SECONDS | hold KEYS | release KEYS   (KEYS out of W A S D E Q and L for LSHIFT; the object-move keys in lower case,
+//     i k j l u o, because the upper-case L is taken)
 //   press KEYS (P M F G B N 1 2 3 4 X T, applied to the next frame only)
 //   rmb down|up | move DX DY (relative mouse motion of the next frame) | click X Y
 //   frames N | save FILE.ppm | print | camera (position, right, up, forward and temporal mode, exactly: %.9g)
+//   select INDEX (selectedObject by list index, -1 = none; what a click's pick would set) | object (the selected object's
+//     index and position, exactly: %.9g)
 int run_script(ViewerCore& core, std::istream& script) {
     InputState in;
     float delta = 1.0f / 60.0f;
@@ -167,7 +190,9 @@ int run_script(ViewerCore& core, std::istream& script) {
     auto set_keys = [&](const std::string& keys, bool v) {
         for (char k : keys) switch (k) {
             case 'W': in.w = v; break; case 'A': in.a = v; break; case 'S': in.s = v; break; case 'D': in.d = v; break;
-            case 'E': in.e = v; break; case 'Q': in.q = v; break; case 'L': in.lshift = v; break; default: break;
+            case 'E': in.e = v; break; case 'Q': in.q = v; break; case 'L': in.lshift = v; break;
+            case 'i': in.i = v; break; case 'k': in.k = v; break; case 'j': in.j = v; break; case 'l': in.l = v; break;
+            case 'u': in.u = v; break; case 'o': in.o = v; break; default: break;
         }
     };
     while (std::getline(script, line)) {
@@ -187,6 +212,17 @@ int run_script(ViewerCore& core, std::istream& script) {
             std::printf("frames %d acc %d simpledraw %d fov %d bounces %d scale %.2f selected %d pos %.9g %.9g %.9g fwd %.9g %.9g %.9g paused %d\n", frames_run,
                         r.ACCUMULATIONFRAMES, (int)r.SIMPLEDRAW, r.FOV, r.MAXBOUNCES, r.SCREEN_SCALE, core.selected(), r.camera.position.x, r.camera.position.y,
                         r.camera.position.z, r.camera.forward.x, r.camera.forward.y, r.camera.forward.z, (int)core.paused());
+        } else if (cmd == "select") {
+            int idx = -1;
+            ss >> idx;
+            core.renderer().selectedObject = idx >= 0 && (size_t)idx < core.scene().GetObjects().size() ? idx : -1;
+        } else if (cmd == "object") {
+            const int idx = core.selected();
+            if (idx < 0) std::printf("object -1\n");
+            else {
+                const float* op = core.scene().GetObjects()[(size_t)idx].position;
+                std::printf("object %d position %.9g %.9g %.9g\n", idx, op[0], op[1], op[2]);
+            }
         } else if (cmd == "camera") {
             const Transform& c = core.renderer().camera;
             std::printf("camera %.9g %.9g %.9g  %.9g %.9g %.9g  %.9g %.9g %.9g  %.9g %.9g %.9g temporal %d\n", c.position.x, c.position.y,
@@ -243,6 +279,8 @@ int run_window(ViewerCore& core) {
         const Uint8* keys = SDL_GetKeyboardState(nullptr);
         in.w = keys[SDL_SCANCODE_W], in.a = keys[SDL_SCANCODE_A], in.s = keys[SDL_SCANCODE_S], in.d = keys[SDL_SCANCODE_D];
         in.e = keys[SDL_SCANCODE_E], in.q = keys[SDL_SCANCODE_Q], in.lshift = keys[SDL_SCANCODE_LSHIFT];
+        in.i = keys[SDL_SCANCODE_I], in.k = keys[SDL_SCANCODE_K], in.j = keys[SDL_SCANCODE_J], in.l = keys[SDL_SCANCODE_L];
+        in.u = keys[SDL_SCANCODE_U], in.o = keys[SDL_SCANCODE_O];
         const Uint32 buttons = SDL_GetRelativeMouseState(&in.mouse_dx, &in.mouse_dy);
         in.right_held = (buttons & SDL_BUTTON(SDL_BUTTON_RIGHT)) != 0;
         core.Frame(in, delta);
