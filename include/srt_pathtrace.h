@@ -440,6 +440,68 @@ int srt_motion_output(srt_context* ctx, int enabled);
 int srt_bind_motion(srt_context* ctx, void* d_float4);
 int srt_read_motion(srt_context* ctx, float* dst);
 
+/* ---- guided upsampling of progressive-resolution blocks (ABI 7, backward compatible) -------------------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.
+ *
+ * srt_render with steps > 1 traces one ray per steps x steps block, through the block's ANCHOR pixel, and copies its colour
+ * into the block.  There is no sub-pixel jitter, so the full-resolution first-hit buffers hold at the anchor exactly the
+ * first hit the block's colour belongs to.  srt_upsample rebuilds every other pixel from the anchors around it, weighed
+ * bilinearly and by how well the anchor's first hit agrees with the pixel's own (a joint-bilateral upsample).
+ *
+ * Inputs, W*H in the accumulator's layout (x + y*W, scene rows): the colour c is the accumulator's rgb (bound or own) as it
+ * stands when the pass runs; the guides o (SRT_GBUF_OBJECT), n, d (SRT_GBUF_NORMAL_DEPTH) and x (SRT_GBUF_POSITION) are the
+ * G-buffer slots, bound or own.  srt_upsample does NOT render the G-buffer: call srt_render_gbuffer first (or bind guides).
+ *   1. anchors: rows — the scene rows that are multiples of steps; columns — with S = stripe_width > 0 ? stripe_width : W,
+ *      the columns k*S + j*steps that lie inside stripe k (below (k + 1)*S) and inside the frame.  These are exactly the
+ *      pixels srt_render traces for the same steps / stripe_width.  For a pixel p = (px, py): x0 = the largest anchor column
+ *      <= px, x1 = the smallest anchor column > px (there may be none; it may be the next stripe's first column and closer
+ *      than steps), fx = (px - x0) / (x1 - x0) in binary32, fx = 0 without x1; y0, y1, fy alike on rows.
+ *   2. taps: the up to four anchors q = (x0 | x1, y0 | y1) with bilinear weights b_q = (1 - fx | fx) (1 - fy | fy), in the
+ *      fixed order y outer, x inner.  A tap counts when it exists, b_q != 0 and o_q == o_p; one that does not is skipped
+ *      before any of its other values is loaded, so non-finite colours or guides of another object cannot reach p.
+ *      A miss pixel (o_p == -1) takes miss anchors with w_q = b_q: the sky is interpolated too.  A hit pixel weighs
+ *        w_q = b_q * max(0, n_p.n_q)^sigma_normal                    (sigma_normal = 0: term off)
+ *                  * exp(-|n_p.(x_q - x_p)| / (sigma_plane * d_p))   (sigma_plane = 0: term off)
+ *      with the denoiser's arithmetic and clamping rules (srt_denoise, step 3): every sigma >= 0 is accepted, the exponent
+ *      and the reciprocal scale 1 / (sigma_plane d_p) stop at FLT_MAX, an exact tie keeps its weight 1.
+ *   3. result: sum w_q c_q / sum w_q per channel.  When no tap counts, or the weights sum to 0, the pixel keeps c_p bit for
+ *      bit: an object thinner than a block that no anchor of the four sees keeps the block colour (there is no wider
+ *      search).  An anchor pixel's one tap is itself, with weight exactly 1 (the two terms are not evaluated): it keeps its
+ *      bits, and steps = 1 is the identity on every pixel.  Output alpha = input alpha of p.
+ *   4. only ANCHOR pixels of c are read as taps: whether the other pixels of a block hold the block's colour (srt_render
+ *      with SRT_RENDER_RESET), a running mean of their own (later one-sample renders) or anything else does not matter.
+ *   5. output: W*H float4 into the handle's own "upsampled" buffer (allocated on first use) or a bound one.
+ *      SRT_UPSAMPLE_FRAMEBUFFER also writes tone_map(result) into the framebuffer (all memory rows, the render's packing).
+ *      SRT_UPSAMPLE_IN_PLACE instead writes the rgb of the NON-anchor pixels that step 3 recomputes into the accumulator;
+ *      anchor pixels, all alphas and the upsampled buffer are not written.  The pass then reads only anchors and writes
+ *      only non-anchors — no pixel reads what another writes, and a second call gives the same bits — and srt_denoise and
+ *      srt_temporal_accumulate can follow on the accumulator.  The accumulator then holds an estimate that no render can
+ *      continue: the next srt_render must use SRT_RENDER_RESET.
+ *   6. whole frame only, one launch, asynchronous on the launch stream behind earlier work (srt_wait / srt_poll cover it).
+ *      Leaves srt_get_stats, srt_get_work_counts, the G-buffer, the temporal history and the launch shape of later renders
+ *      as they are.  No atomics: repeated calls give the same bits. */
+#define SRT_UPSAMPLE_IN_PLACE 1u     /* write the non-anchor pixels' rgb into the accumulator instead of the upsampled buffer */
+#define SRT_UPSAMPLE_FRAMEBUFFER 2u  /* also write tone_map(result) into the framebuffer (all memory rows) */
+
+typedef struct srt_upsample_params {
+    int32_t steps;         /* block size of the render being reconstructed, 1..32768 (1: the identity) */
+    int32_t stripe_width;  /* that render's stripe_width, >= 0 (0: a single stripe) */
+    float sigma_normal;    /* sigma_n, >= 0 */
+    float sigma_plane;     /* sigma_x, >= 0 */
+    uint32_t flags;        /* SRT_UPSAMPLE_* */
+} srt_upsample_params;
+
+/* The library's defaults: steps = 2, stripe_width = 0, the denoiser's sigma_normal and sigma_plane (pure host, no device needed). */
+int srt_upsample_params_default(srt_upsample_params* out);
+/* SRT_ERR_INVALID_ARG for steps outside 1..32768, a negative stripe_width, a negative or NaN sigma or unknown flags;
+ * SRT_ERR_STATE when OBJECT, NORMAL_DEPTH or POSITION has never been bound or rendered. */
+int srt_upsample(srt_context* ctx, const srt_upsample_params* params);
+/* Write the result into a caller DEVICE buffer of W*H float4 instead of the handle's own; NULL = own.  Does not wait. */
+int srt_bind_upsampled(srt_context* ctx, void* d_float4);
+/* Wait, then copy the W*H float4 result (scene rows) to host memory.  SRT_ERR_STATE before the first srt_upsample without
+ * SRT_UPSAMPLE_IN_PLACE. */
+int srt_read_upsampled(srt_context* ctx, float* dst_rgba);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

@@ -33,6 +33,7 @@ from .capi import (  # noqa: F401
     SrtError,
     Stats,
     TemporalParams,
+    UpsampleParams,
     build_native,
     default_camera,
     default_environment,
@@ -43,6 +44,6 @@ from . import host  # noqa: F401
 
 __all__ = [
     "capi", "host", "PathTracer", "SrtError", "Object", "Material", "Camera", "Environment",
-    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
+    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
     "load_library",
 ]

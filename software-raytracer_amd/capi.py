@@ -26,6 +26,9 @@ DENOISE_GUIDES = GBUF_OBJECT | GBUF_NORMAL_DEPTH | GBUF_POSITION
 TEMPORAL_RESET, TEMPORAL_FRAMEBUFFER = 1, 2
 # guides srt_temporal_accumulate reads
 TEMPORAL_GUIDES = GBUF_OBJECT | GBUF_NORMAL_DEPTH | GBUF_POSITION
+UPSAMPLE_IN_PLACE, UPSAMPLE_FRAMEBUFFER = 1, 2
+# guides srt_upsample reads
+UPSAMPLE_GUIDES = GBUF_OBJECT | GBUF_NORMAL_DEPTH | GBUF_POSITION
 ABI_VERSION = 7
 
 # every symbol include/srt_pathtrace.h declares (tests check the library exports them all)
@@ -39,6 +42,7 @@ EXPORTS = [
     "srt_denoise_params_default", "srt_denoise", "srt_bind_denoised", "srt_read_denoised",
     "srt_temporal_params_default", "srt_temporal_accumulate", "srt_read_history_length",
     "srt_update_scene", "srt_motion_output", "srt_bind_motion", "srt_read_motion",
+    "srt_upsample_params_default", "srt_upsample", "srt_bind_upsampled", "srt_read_upsampled",
 ]
 
 
@@ -125,6 +129,11 @@ class DenoiseParams(C.Structure):
 class TemporalParams(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("max_samples", C.c_float), ("plane_tolerance", C.c_float),
                 ("normal_threshold", C.c_float), ("flags", C.c_uint32)]
+
+
+class UpsampleParams(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("stripe_width", C.c_int32), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("flags", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -236,6 +245,10 @@ def open_library(path):
     L.srt_motion_output.argtypes = [ctx, C.c_int]
     L.srt_bind_motion.argtypes = [ctx, C.c_void_p]
     L.srt_read_motion.argtypes = [ctx, C.POINTER(C.c_float)]
+    L.srt_upsample_params_default.argtypes = [C.POINTER(UpsampleParams)]
+    L.srt_upsample.argtypes = [ctx, C.POINTER(UpsampleParams)]
+    L.srt_bind_upsampled.argtypes = [ctx, C.c_void_p]
+    L.srt_read_upsampled.argtypes = [ctx, C.POINTER(C.c_float)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -281,13 +294,24 @@ def temporal_defaults(lib=None):
     return {n: getattr(p, n) for n, _ in TemporalParams._fields_}
 
 
+def upsample_defaults(lib=None):
+    """srt_upsample_params_default as a dict (pure host: no GPU needed)."""
+    p = UpsampleParams()
+    rc = (lib if lib is not None else load_library()).srt_upsample_params_default(C.byref(p))
+    if rc:
+        raise SrtError(rc, "srt_upsample_params_default")
+    return {n: getattr(p, n) for n, _ in UpsampleParams._fields_}
+
+
 def __getattr__(name):
-    # DENOISE_DEFAULTS / TEMPORAL_DEFAULTS: the library's defaults (denoise_defaults(), temporal_defaults()), read when first
-    # asked for, so that importing this module does not need the built library
+    # DENOISE_DEFAULTS / TEMPORAL_DEFAULTS / UPSAMPLE_DEFAULTS: the library's defaults (denoise_defaults(), temporal_defaults(),
+    # upsample_defaults()), read when first asked for, so that importing this module does not need the built library
     if name == "DENOISE_DEFAULTS":
         return denoise_defaults()
     if name == "TEMPORAL_DEFAULTS":
         return temporal_defaults()
+    if name == "UPSAMPLE_DEFAULTS":
+        return upsample_defaults()
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -309,6 +333,15 @@ def temporal_params(samples=1, max_samples=None, plane_tolerance=None, normal_th
     return TemporalParams(int(samples), float(d["max_samples"] if max_samples is None else max_samples),
                           float(d["plane_tolerance"] if plane_tolerance is None else plane_tolerance),
                           float(d["normal_threshold"] if normal_threshold is None else normal_threshold), flags)
+
+
+def upsample_params(steps=None, stripe_width=None, sigma_normal=None, sigma_plane=None, in_place=False, framebuffer=False, lib=None):
+    """An UpsampleParams: the library defaults, with every argument that is not None put in their place."""
+    d = upsample_defaults(lib)
+    flags = (UPSAMPLE_IN_PLACE if in_place else 0) | (UPSAMPLE_FRAMEBUFFER if framebuffer else 0)
+    return UpsampleParams(int(d["steps"] if steps is None else steps), int(d["stripe_width"] if stripe_width is None else stripe_width),
+                          float(d["sigma_normal"] if sigma_normal is None else sigma_normal),
+                          float(d["sigma_plane"] if sigma_plane is None else sigma_plane), flags)
 
 
 def _f3(v):
@@ -449,6 +482,26 @@ class PathTracer:
             raise ValueError("bind_gbuffer(%r): tensor is not contiguous" % name)
         self._ck(self.L.srt_bind_gbuffer(self._h, bit, C.c_void_p(tensor.data_ptr())))
 
+    def _float4_tensor_ptr(self, what, tensor):
+        """The device pointer of a tensor a float4 output is bound to: on this tracer's device, (H, W, 4) float32 and
+        contiguous; None passes through (the handle's own buffer)."""
+        if tensor is None:
+            return None
+        import torch
+
+        shape = (self.height, self.width, 4)
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError("%s: expected a torch.Tensor, got %s" % (what, type(tensor).__name__))
+        if tensor.device.type != "cuda" or tensor.device.index != self.device:
+            raise ValueError("%s: tensor on %s, the tracer renders on cuda:%d" % (what, tensor.device, self.device))
+        if tensor.dtype != torch.float32:
+            raise TypeError("%s: dtype %s, want torch.float32" % (what, tensor.dtype))
+        if tuple(tensor.shape) != shape:
+            raise ValueError("%s: shape %s, want %s" % (what, tuple(tensor.shape), shape))
+        if not tensor.is_contiguous():
+            raise ValueError("%s: tensor is not contiguous" % what)
+        return C.c_void_p(tensor.data_ptr())
+
     def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None, albedo=True, framebuffer=False,
                 gbuffer=True):
         """srt_denoise over the whole frame: the accumulator as it stands, guided by the first-hit buffers.  Arguments left at
@@ -468,23 +521,7 @@ class PathTracer:
     def bind_denoised(self, tensor):
         """srt_bind_denoised: write the result into a torch tensor on this tracer's device, (H, W, 4) float32 and contiguous
         (None: the handle's own buffer).  Checked here, before any native call, as bind_gbuffer checks."""
-        if tensor is None:
-            self._ck(self.L.srt_bind_denoised(self._h, None))
-            return
-        import torch
-
-        shape = (self.height, self.width, 4)
-        if not isinstance(tensor, torch.Tensor):
-            raise TypeError("bind_denoised: expected a torch.Tensor, got %s" % type(tensor).__name__)
-        if tensor.device.type != "cuda" or tensor.device.index != self.device:
-            raise ValueError("bind_denoised: tensor on %s, the tracer renders on cuda:%d" % (tensor.device, self.device))
-        if tensor.dtype != torch.float32:
-            raise TypeError("bind_denoised: dtype %s, want torch.float32" % tensor.dtype)
-        if tuple(tensor.shape) != shape:
-            raise ValueError("bind_denoised: shape %s, want %s" % (tuple(tensor.shape), shape))
-        if not tensor.is_contiguous():
-            raise ValueError("bind_denoised: tensor is not contiguous")
-        self._ck(self.L.srt_bind_denoised(self._h, C.c_void_p(tensor.data_ptr())))
+        self._ck(self.L.srt_bind_denoised(self._h, self._float4_tensor_ptr("bind_denoised", tensor)))
 
     def temporal(self, samples=1, max_samples=None, plane_tolerance=None, normal_threshold=None, reset=False, framebuffer=False,
                  gbuffer=True):
@@ -516,23 +553,30 @@ class PathTracer:
     def bind_motion(self, tensor):
         """srt_bind_motion: write the motion buffer into a torch tensor on this tracer's device, (H, W, 4) float32 and
         contiguous (None: the handle's own buffer).  Checked here, before any native call, as bind_denoised checks."""
-        if tensor is None:
-            self._ck(self.L.srt_bind_motion(self._h, None))
-            return
-        import torch
+        self._ck(self.L.srt_bind_motion(self._h, self._float4_tensor_ptr("bind_motion", tensor)))
 
-        shape = (self.height, self.width, 4)
-        if not isinstance(tensor, torch.Tensor):
-            raise TypeError("bind_motion: expected a torch.Tensor, got %s" % type(tensor).__name__)
-        if tensor.device.type != "cuda" or tensor.device.index != self.device:
-            raise ValueError("bind_motion: tensor on %s, the tracer renders on cuda:%d" % (tensor.device, self.device))
-        if tensor.dtype != torch.float32:
-            raise TypeError("bind_motion: dtype %s, want torch.float32" % tensor.dtype)
-        if tuple(tensor.shape) != shape:
-            raise ValueError("bind_motion: shape %s, want %s" % (tuple(tensor.shape), shape))
-        if not tensor.is_contiguous():
-            raise ValueError("bind_motion: tensor is not contiguous")
-        self._ck(self.L.srt_bind_motion(self._h, C.c_void_p(tensor.data_ptr())))
+    def upsample(self, steps=None, stripe_width=None, sigma_normal=None, sigma_plane=None, in_place=False, framebuffer=False,
+                 gbuffer=True):
+        """srt_upsample over the whole frame: every pixel rebuilt from the anchors of the steps x steps blocks a render(steps=...,
+        stripe_width=...) traced, guided by the first-hit buffers.  Arguments left at None take UPSAMPLE_DEFAULTS.
+        in_place=True writes the non-anchor pixels into the accumulator (the next render() must reset) instead of the
+        upsampled buffer.  gbuffer=True first enqueues render_gbuffer() for the guides it reads (current scene and camera);
+        gbuffer=False uses the guides as they are.  Asynchronous."""
+        p = upsample_params(steps, stripe_width, sigma_normal, sigma_plane, in_place, framebuffer, lib=self.L)
+        if gbuffer:
+            self.render_gbuffer(outputs=UPSAMPLE_GUIDES)
+        self._ck(self.L.srt_upsample(self._h, C.byref(p)))
+
+    def upsampled(self):
+        """srt_read_upsampled: the result, (H, W, 4) float32, rows = scene rows (the orientation of accumulator())."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self.L.srt_read_upsampled(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def bind_upsampled(self, tensor):
+        """srt_bind_upsampled: write the result into a torch tensor on this tracer's device, (H, W, 4) float32 and contiguous
+        (None: the handle's own buffer).  Checked here, before any native call, as bind_denoised checks."""
+        self._ck(self.L.srt_bind_upsampled(self._h, self._float4_tensor_ptr("bind_upsampled", tensor)))
 
     def wait(self):
         self._ck(self.L.srt_wait(self._h))

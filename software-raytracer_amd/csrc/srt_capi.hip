@@ -20,6 +20,7 @@
 #include "srt_gbuffer.hip.h"
 #include "srt_denoise.hip.h"
 #include "srt_temporal.hip.h"
+#include "srt_upsample.hip.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -270,6 +271,12 @@ struct srt_context {
     DeviceBuffer<float4> d_mv_own;
     float4* d_mv_bound = nullptr;
     const float4* mv_last = nullptr;
+
+    // guided upsampler (srt_upsample): the handle's own result buffer (allocated on first use), the caller's bound one
+    // (srt_bind_upsampled; NULL = own), and whether a call has written a result buffer yet (srt_read_upsampled)
+    DeviceBuffer<float4> d_up_own;
+    float4* d_up_bound = nullptr;
+    bool up_written = false;
 
     char error[512] = "";
 };
@@ -1537,6 +1544,68 @@ int srt_read_history_length(srt_context* ctx, float* dst) {
     std::vector<float4> tmp(px);
     SRT_HIP(ctx, hipMemcpy(tmp.data(), ctx->d_tp[ctx->tp_cur][0], px * sizeof(float4), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < px; ++i) dst[i] = tmp[i].w;
+    return SRT_OK;
+}
+
+// ---- guided upsampler ------------------------------------------------------------------------------------------------
+int srt_upsample_params_default(srt_upsample_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    // the denoiser's normal and plane sigmas (tools/upsample_time.py sweep is the tool that revisits them)
+    srt_denoise_params d{};
+    (void)srt_denoise_params_default(&d);
+    out->steps = 2;
+    out->stripe_width = 0;
+    out->sigma_normal = d.sigma_normal;
+    out->sigma_plane = d.sigma_plane;
+    out->flags = 0;
+    return SRT_OK;
+}
+
+int srt_upsample(srt_context* ctx, const srt_upsample_params* u) {
+    if (!ctx || !u) return SRT_ERR_INVALID_ARG;
+    if (u->steps < 1 || u->steps > 32768) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_upsample: steps %d outside 1..32768", u->steps);
+    if (u->stripe_width < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_upsample: stripe_width must be >= 0 (%d)", u->stripe_width);
+    // (written so that a NaN fails too)
+    if (!(u->sigma_normal >= 0.0f) || !(u->sigma_plane >= 0.0f))
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_upsample: sigmas must be >= 0 (normal %g, plane %g)", u->sigma_normal, u->sigma_plane);
+    if (u->flags & ~(SRT_UPSAMPLE_IN_PLACE | SRT_UPSAMPLE_FRAMEBUFFER))
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_upsample: unknown flags 0x%x", u->flags);
+    const void* guide[3] = {};
+    if (const int rc = find_guides(ctx, "srt_upsample", 3, nullptr, guide)) return rc;
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const bool in_place = (u->flags & SRT_UPSAMPLE_IN_PLACE) != 0;
+    if (!in_place && !ctx->d_up_bound) SRT_HIP(ctx, ctx->d_up_own.ensure((size_t)ctx->width * (size_t)ctx->height * sizeof(float4)));
+    srt::UpsampleLaunch U{};
+    U.acc = ctx->d_acc;
+    U.dst = in_place ? nullptr : bound_or_own(ctx->d_up_bound, ctx->d_up_own);
+    U.acc_rgb = in_place ? (float*)ctx->d_acc : nullptr;
+    U.object = (const int32_t*)guide[0];
+    U.normal_depth = (const float4*)guide[1];
+    U.position = (const float4*)guide[2];
+    U.framebuffer = (u->flags & SRT_UPSAMPLE_FRAMEBUFFER) ? ctx->d_fb : nullptr;
+    U.width = ctx->width, U.height = ctx->height;
+    U.steps = u->steps;
+    U.stripe = u->stripe_width > 0 && u->stripe_width < ctx->width ? u->stripe_width : ctx->width;  // (a stripe as wide as the frame is a single one)
+    U.sigma_normal = fminf(u->sigma_normal, FLT_MAX);  // as srt_denoise: FLT_MAX * log2 1 = 0 where inf * 0 would be NaN
+    U.sigma_plane = u->sigma_plane;
+    hipLaunchKernelGGL(srt::upsample_kernel, frame_tile_grid(ctx), dim3(srt::WG_THREADS), 0, ctx->stream, U);
+    SRT_HIP(ctx, hipGetLastError());
+    if (!in_place) ctx->up_written = true;
+    return SRT_OK;
+}
+
+int srt_bind_upsampled(srt_context* ctx, void* d_float4) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    ctx->d_up_bound = (float4*)d_float4;  // (no synchronisation: an enqueued call keeps the buffer it was given)
+    return SRT_OK;
+}
+
+int srt_read_upsampled(srt_context* ctx, float* dst_rgba) {
+    if (!ctx || !dst_rgba) return SRT_ERR_INVALID_ARG;
+    const float4* src = bound_or_own(ctx->d_up_bound, ctx->d_up_own);
+    if (!ctx->up_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_read_upsampled: nothing has been upsampled into this buffer yet");
+    if (const int rc = finish_stream(ctx)) return rc;
+    SRT_HIP(ctx, hipMemcpy(dst_rgba, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
 

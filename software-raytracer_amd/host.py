@@ -7,8 +7,8 @@ import subprocess
 
 import numpy as np
 
-from .capi import (DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, DenoiseParams, Mesh, Object, Stats, TemporalParams,
-                   denoise_params, gbuffer_outputs, temporal_params)
+from .capi import (DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, DenoiseParams, Mesh, Object, Stats,
+                   TemporalParams, UpsampleParams, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_PKG, "libsrt_host.so")
@@ -27,6 +27,7 @@ EXPORTS = [
     "srt_host_renderer_temporal", "srt_host_renderer_read_history_length", "srt_host_renderer_render_temporal_frame",
     "srt_host_renderer_move_camera",
     "srt_host_renderer_update_scene", "srt_host_renderer_motion_output", "srt_host_renderer_read_motion",
+    "srt_host_renderer_upsample", "srt_host_renderer_read_upsampled", "srt_host_renderer_guided_upsample",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -113,6 +114,9 @@ def load_library():
     L.srt_host_renderer_update_scene.argtypes = [vp, vp]
     L.srt_host_renderer_motion_output.argtypes = [vp, C.c_int]
     L.srt_host_renderer_read_motion.argtypes = [vp, C.POINTER(C.c_float)]
+    L.srt_host_renderer_upsample.argtypes = [vp, C.POINTER(UpsampleParams)]
+    L.srt_host_renderer_read_upsampled.argtypes = [vp, C.POINTER(C.c_float)]
+    L.srt_host_renderer_guided_upsample.argtypes = [vp, C.c_int]
     L.srt_host_multi_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]
     L.srt_host_multi_create.restype = vp
     L.srt_host_multi_destroy.argtypes = [vp]
@@ -370,6 +374,25 @@ class Renderer:
         out = np.empty((self.height, self.width, 4), dtype=np.float32)
         self._ck(self.L.srt_host_renderer_read_motion(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def upsample(self, steps=None, stripe_width=None, sigma_normal=None, sigma_plane=None, in_place=False, framebuffer=False,
+                 gbuffer=True):
+        """PathTraceRenderer::Upsample, with the arguments of capi.PathTracer.upsample (gbuffer=True: render_gbuffer first)."""
+        p = upsample_params(steps, stripe_width, sigma_normal, sigma_plane, in_place, framebuffer)
+        if gbuffer:
+            self.render_gbuffer(UPSAMPLE_GUIDES)
+        self._ck(self.L.srt_host_renderer_upsample(self._h, C.byref(p)))
+
+    def upsampled(self):
+        """PathTraceRenderer::ReadUpsampled: (H, W, 4) float32, scene rows, as capi.PathTracer.upsampled returns it."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_upsampled(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def guided_upsample(self, on=True):
+        """PathTraceRenderer::guidedUpsample: render_frame() follows every frame of blocks with the guides and the upsampler
+        into the framebuffer."""
+        self._ck(self.L.srt_host_renderer_guided_upsample(self._h, 1 if on else 0))
 
     def stats(self):
         s = Stats()

@@ -234,6 +234,14 @@ int srt_host_renderer_move_camera(srt_host_renderer* h, const float* pos, const 
 int srt_host_renderer_update_scene(srt_host_renderer* h, srt_host_scene* s) { SRT_HOST_TRY(h, h->r->UpdateScene(s->scene)) }
 int srt_host_renderer_motion_output(srt_host_renderer* h, int on) { SRT_HOST_TRY(h, h->r->MotionOutput(on != 0)) }
 int srt_host_renderer_read_motion(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadMotion(dst)) }
+// guided upsampler over the whole frame with the guides as they stand (srt_upsample / srt_read_upsampled), and the
+// guidedUpsample setting of RenderFrame
+int srt_host_renderer_upsample(srt_host_renderer* h, const srt_upsample_params* p) { SRT_HOST_TRY(h, h->r->Upsample(*p)) }
+int srt_host_renderer_read_upsampled(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadUpsampled(dst)) }
+int srt_host_renderer_guided_upsample(srt_host_renderer* h, int on) {
+    h->r->guidedUpsample = on != 0;
+    return 0;
+}
 int srt_host_renderer_stats(srt_host_renderer* h, srt_stats* out) { SRT_HOST_TRY(h, *out = h->r->Stats()) }
 void* srt_host_renderer_handle(srt_host_renderer* h) { return h->r->handle(); }
 

@@ -95,6 +95,8 @@ void PathTraceRenderer::push_camera() {
 }
 
 bool PathTraceRenderer::RenderFrame() {
+    if (guidedUpsample && (row_begin_ != 0 || row_end_ != height_))
+        throw RendererError(SRT_ERR_STATE, "RenderFrame: guidedUpsample with a row band; the upsampler covers the whole frame");
     if (first_frame_) {
         first_frame_ = false;  // workers start with the initial globals (:30-35,47-48,271)
     } else {
@@ -125,6 +127,15 @@ bool PathTraceRenderer::RenderFrame() {
     p.selected_object = selectedObject;
     check(srt_render(ctx_, &p), "srt_render");
     clean_reset_ = true;
+    if (guidedUpsample && p.steps > 1) {
+        RenderGBuffer(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION);
+        srt_upsample_params u{};
+        check(srt_upsample_params_default(&u), "srt_upsample_params_default");
+        u.steps = p.steps;
+        u.stripe_width = p.stripe_width;
+        u.flags = SRT_UPSAMPLE_FRAMEBUFFER;  // (not in place: the accumulator stays what the reference accumulates)
+        Upsample(u);
+    }
     return true;
 }
 
@@ -135,7 +146,7 @@ int PathTraceRenderer::Pick(int mouse_x, int mouse_y) {
     return idx;
 }
 
-void PathTraceRenderer::RenderSamples(uint32_t count, bool count_rays) {
+void PathTraceRenderer::RenderSamples(uint32_t count, bool count_rays, int steps) {
     if (count == 0) return;
     bool reset = doSetFrame_ || clean_reset_;
     if (reset) next_clean_sample_ = 1;
@@ -150,7 +161,7 @@ void PathTraceRenderer::RenderSamples(uint32_t count, bool count_rays) {
     p.max_bounces = MAXBOUNCES < 0 ? 0 : MAXBOUNCES;
     p.seed = seed;
     p.flags = (reset ? SRT_RENDER_RESET : 0) | (count_rays ? SRT_RENDER_COUNT_RAYS : 0);
-    p.steps = 1;
+    p.steps = steps;
     p.selected_object = -1;
     check(srt_render(ctx_, &p), "srt_render");
     next_clean_sample_ += count;
@@ -200,6 +211,10 @@ void PathTraceRenderer::ReadHistoryLength(float* dst) { check(srt_read_history_l
 void PathTraceRenderer::MotionOutput(bool on) { check(srt_motion_output(ctx_, on ? 1 : 0), "srt_motion_output"); }
 
 void PathTraceRenderer::ReadMotion(float* dst) { check(srt_read_motion(ctx_, dst), "srt_read_motion"); }
+
+void PathTraceRenderer::Upsample(const srt_upsample_params& params) { check(srt_upsample(ctx_, &params), "srt_upsample"); }
+
+void PathTraceRenderer::ReadUpsampled(float* dst_rgba) { check(srt_read_upsampled(ctx_, dst_rgba), "srt_read_upsampled"); }
 
 void PathTraceRenderer::RenderTemporalFrame(uint32_t spp, bool denoise) {
     if (spp == 0) throw RendererError(SRT_ERR_INVALID_ARG, "RenderTemporalFrame: spp must be >= 1");

@@ -66,6 +66,10 @@ class PathTraceRenderer {
     int selectedObject = -1;                // :53 as an index into ObjectsToRender, -1 = NULL
     static constexpr int THREADS = 16;      // :28 — only used for the block anchoring of :235,330
     uint32_t seed = 0;  // the reference only ever names srand(0) (:263)
+    // not in the reference: RenderFrame follows a frame of steps x steps blocks (steps > 1) with the first-hit guides and
+    // srt_upsample into the framebuffer, so that the frame shown is reconstructed from the blocks' anchors instead of made of
+    // squares.  The accumulator stays what the reference accumulates.  Whole frame only.
+    bool guidedUpsample = false;
     Transform camera;   // :295-297
 
     PathTraceRenderer(int device, int width, int height);
@@ -102,13 +106,17 @@ class PathTraceRenderer {
     // resolution frame after an edit has setFrame == true AND ACCUMULATIONFRAMES == 2.
     // The very first call renders with the start-up globals, as the workers do before the
     // loop's first pass.  Returns false when nothing was launched (ACC == TARGETFRAMES, :572).
+    // With guidedUpsample a frame of blocks is followed by RenderGBuffer (the three guides) and Upsample with the library's
+    // defaults, the frame's own steps and stripe_width and SRT_UPSAMPLE_FRAMEBUFFER — never in place; SRT_ERR_STATE when the
+    // renderer has a row band.  Without it the calls are exactly the above.
     bool RenderFrame();
     // Picking (:525-541): x, y in window coordinates (y down, as the mouse reports it)
     int Pick(int mouse_x, int mouse_y);
 
     // Clean sequence used by benchmarks and fixtures: `count` further samples in ONE
-    // launch; the first call after Invalidate() starts at sample 1 with reset.
-    void RenderSamples(uint32_t count, bool count_rays = false);
+    // launch; the first call after Invalidate() starts at sample 1 with reset.  steps > 1: one ray per steps x steps block
+    // (a single stripe: anchors at x = 0), as srt_render_params.steps.
+    void RenderSamples(uint32_t count, bool count_rays = false, int steps = 1);
 
     void Wait();
     bool Done();
@@ -133,6 +141,10 @@ class PathTraceRenderer {
     // (u - x, v - y, Wsum, 0); ReadMotion waits and copies them (scene rows).
     void MotionOutput(bool on);
     void ReadMotion(float* dst);
+    // Guided upsampler (srt_upsample) over the whole frame: the accumulator's block anchors and the guides as they stand (call
+    // RenderGBuffer first).  Asynchronous; ReadUpsampled waits and copies the W x H float4 result (scene rows).
+    void Upsample(const srt_upsample_params& params);
+    void ReadUpsampled(float* dst_rgba);
     // One frame of a moving camera that keeps its samples (whole frame only): push the camera, render `spp` samples with
     // SRT_RENDER_RESET and seed + k (k = the number of temporal frames this renderer has rendered before, so that the noise
     // does not stay fixed to the screen), the first-hit guides, srt_temporal_accumulate with the library's defaults

@@ -65,7 +65,7 @@ static void usage() {
                  "usage: srt_render --scene FILE [--width 1280] [--height 720] [--spp 32] [--bounces 2]\n"
                  "                  [--fov 55] [--seed 0] [--device 0 | --devices 0,1,2,...] [--out frame.ppm] [--resave FILE]\n"
                  "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]\n"
-                 "                  [--move-object IDX:DX,DY,DZ]...]\n"
+                 "                  [--move-object IDX:DX,DY,DZ]...] [--steps N] [--upsample PATH]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
                  "             and means the same), --equal-bands: bands of equal height\n"
@@ -74,6 +74,11 @@ static void usage() {
                  "             (with --devices: made for the whole frame on the first device)\n"
                  "  --denoise: also render the first-hit buffers, denoise the accumulator with the library's defaults\n"
                  "             (srt_denoise) and write the tone-mapped result to PATH as a PPM (single device only)\n"
+                 "  --steps:   trace one ray per N x N block of pixels and copy its colour into the block (the progressive-resolution\n"
+                 "             blocks of the reference's interactive frames); single device, not with --temporal\n"
+                 "  --upsample: also render the first-hit buffers, rebuild the full-resolution frame from the blocks' anchor\n"
+                 "             pixels with the library's defaults (srt_upsample) and write the tone-mapped result to PATH as a PPM;\n"
+                 "             with --denoise the upsampler works in place and the denoiser runs on its result (single device only)\n"
                  "  --temporal: render FRAMES frames of --spp samples each while the camera moves, keeping samples across\n"
                  "             frames (srt_temporal_accumulate), and write the last one to --out (--denoise PATH: also its\n"
                  "             denoised form); before every frame but the first the camera moves by R, U, F along its right,\n"
@@ -83,8 +88,8 @@ static void usage() {
 }
 
 int main(int argc, char** argv) {
-    std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise;
-    int temporal = 0;
+    std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise, upsample;
+    int temporal = 0, steps = 1;
     float move[3] = {0, 0, 0}, turn_deg = 0;
     struct ObjectMove {
         size_t index;
@@ -124,6 +129,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--resave")) resave = need("--resave");
         else if (!std::strcmp(argv[i], "--gbuffer")) gbuffer = need("--gbuffer");
         else if (!std::strcmp(argv[i], "--denoise")) denoise = need("--denoise");
+        else if (!std::strcmp(argv[i], "--steps")) steps = std::atoi(need("--steps"));
+        else if (!std::strcmp(argv[i], "--upsample")) upsample = need("--upsample");
         else if (!std::strcmp(argv[i], "--temporal")) temporal = std::atoi(need("--temporal"));
         else if (!std::strcmp(argv[i], "--turn")) turn_deg = std::strtof(need("--turn"), nullptr);
         else if (!std::strcmp(argv[i], "--move")) {
@@ -164,12 +171,16 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--move-object needs --temporal\n");
         return 2;
     }
-    if (scene_path.empty() || W <= 0 || H <= 0 || spp <= 0 || temporal < 0) {
+    if (scene_path.empty() || W <= 0 || H <= 0 || spp <= 0 || temporal < 0 || steps < 1) {
         usage();
         return 2;
     }
     if (!denoise.empty() && !devices.empty()) {
         std::fprintf(stderr, "--denoise works on one device only: the accumulator bands of --devices live on different GPUs\n");
+        return 2;
+    }
+    if ((steps > 1 || !upsample.empty()) && (!devices.empty() || temporal)) {
+        std::fprintf(stderr, "--steps and --upsample work on one device only and not with --temporal\n");
         return 2;
     }
     if (temporal && !devices.empty()) {
@@ -284,7 +295,7 @@ int main(int argc, char** argv) {
             return 0;
         }
         auto t0 = std::chrono::steady_clock::now();
-        r.RenderSamples((uint32_t)spp, true);
+        r.RenderSamples((uint32_t)spp, true, steps);
         r.Wait();
         double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         srt_stats st = r.Stats();
@@ -295,6 +306,19 @@ int main(int argc, char** argv) {
         r.ReadFramebuffer(fb.data(), (size_t)W * 4);
         if (write_ppm(fb, out)) return 1;
         if (!gbuffer.empty() && write_gbuffers(r, gbuffer, W, H)) return 1;
+        if (!upsample.empty()) {
+            // the guides of the whole frame, then the blocks' anchors interpolated with the library's defaults; the kernel
+            // tone-maps its result into the framebuffer (--out is already written).  With --denoise the result replaces the
+            // accumulator's non-anchor pixels, which is what the denoiser below then filters.
+            srt_upsample_params up{};
+            srt_upsample_params_default(&up);
+            up.steps = steps;
+            up.flags = SRT_UPSAMPLE_FRAMEBUFFER | (denoise.empty() ? 0u : SRT_UPSAMPLE_IN_PLACE);
+            r.RenderGBuffer(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION);
+            r.Upsample(up);
+            r.ReadFramebuffer(fb.data(), (size_t)W * 4);
+            if (write_ppm(fb, upsample)) return 1;
+        }
         if (!denoise.empty()) {
             // the guides of the whole frame, then the filter with the library's defaults; the kernel tone-maps its result into
             // the framebuffer (--out is already written), read back top-down like --out
