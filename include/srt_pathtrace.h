@@ -502,6 +502,90 @@ int srt_bind_upsampled(srt_context* ctx, void* d_float4);
  * SRT_UPSAMPLE_IN_PLACE. */
 int srt_read_upsampled(srt_context* ctx, float* dst_rgba);
 
+/* ---- geometry-supersampled anti-aliasing (ABI 7, backward compatible) ------------------------------------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.
+ *
+ * The camera ray of a pixel is the same for every sample (no sub-pixel jitter, Raytracer.cpp:106-122): a frame converges in
+ * colour, never in coverage.  Two passes mend the silhouettes without touching srt_render (subpixel reconstruction
+ * anti-aliasing, Chajdas, McGuire and Luebke 2011): srt_render_subsamples traces the GEOMETRY at k x k sub-pixel positions,
+ * shading stays one estimate per pixel, and srt_antialias rebuilds each pixel as the coverage-weighted mix of its own colour
+ * and the colours of the neighbouring pixels whose object its sub-samples see.
+ *
+ * srt_render_subsamples.  k is 1..4, K = k*k.  Sub-sample s = j*k + i (i, j in 0..k-1) of pixel (x, y) is BY DEFINITION the
+ * ray GetRayDirection gives for the integer pixel
+ *     (X, Y) = (2k*x + 2i - (k-1), 2k*y + 2j - (k-1))
+ * of a virtual frame of (2k*W) x (2k*H) pixels, same camera, fov and origin: nX = ((float)X / (float)(2kW)) * 2 - 1 and the
+ * same folded basis ((float)(2kW) / (float)(2kH) == (float)W / (float)H exactly while 2kW, 2kH < 2^24; larger frames are
+ * refused).  X and Y are negative for some sub-samples of border pixels; the formula holds for them.  The sub-samples thus
+ * lie on a centred k x k grid at offsets (2i - (k-1)) / (2k) pixels from the pixel's own ray; for odd k the centre one IS the
+ * pixel's own ray, bit for bit, and k = 1 gives the SRT_GBUF_OBJECT output.  Output: the list index of the hit object or -1,
+ * from the same closest hit, scene image and tie rule as srt_render_gbuffer and srt_pick (meshes included), K*W*H int32,
+ * plane-major: sub[s][y][x] = index s*W*H + x + y*W with the SCENE row y.  Band, stream and asynchrony are those of
+ * srt_render_gbuffer: the band is given in memory rows, only scene rows [H - row_end, H - row_begin) of each plane are
+ * written, scene and camera are captured at enqueue, srt_wait / srt_poll cover the call; stats, work counts, the launch shape,
+ * the G-buffer, the accumulator and the framebuffer are left alone.  The handle's own buffer is allocated on first use and
+ * re-allocated when k grows. */
+typedef struct srt_subsample_params {
+    int32_t row_begin;  /* first memory row (inclusive) */
+    int32_t row_end;    /* one past the last memory row */
+    int32_t k;          /* 1..4: k x k sub-samples per pixel */
+    uint32_t flags;     /* reserved, must be 0 */
+} srt_subsample_params;
+
+/* SRT_ERR_STATE before srt_set_scene and srt_set_camera; SRT_ERR_INVALID_ARG for an empty or out-of-range band, k outside
+ * 1..4, non-zero flags, or a frame with 2k*W or 2k*H >= 2^24. */
+int srt_render_subsamples(srt_context* ctx, const srt_subsample_params* params);
+/* Write the sub-samples into a caller DEVICE buffer of K*W*H int32 instead of the handle's own; NULL = own.  As
+ * srt_bind_gbuffer: does not wait, enqueued work keeps its buffer.  What a bound buffer holds is the caller's responsibility. */
+int srt_bind_subsamples(srt_context* ctx, void* d_int32);
+/* Wait, then copy the K*W*H int32 of the k last rendered into the current buffer (bound or own) to host memory.
+ * SRT_ERR_STATE before the first srt_render_subsamples. */
+int srt_read_subsamples(srt_context* ctx, int32_t* dst);
+
+/* srt_antialias.  Inputs, W*H in the accumulator's layout (x + y*W, scene rows): the colour c from the chosen source (the
+ * accumulator, or the current "denoised" buffer); the pixel guide o = SRT_GBUF_OBJECT, bound or own; the sub-sample buffer
+ * sub, bound or own.  srt_antialias renders neither guide.
+ *   1. offsets: for sub-sample s = j*k + i of p = (x, y): dx = (float)(2i - (k-1)) / (float)(2k) in binary32, dy alike from j.
+ *   2. own sub-samples: sub[s][p] == o_p gives the sub-sample the colour C_s = c_p.
+ *   3. foreign sub-samples (sub[s][p] != o_p; a miss counts as the object -1 like any other, so the sky is mixed in at
+ *      silhouettes): the taps are the pixels q = p + (ax, ay), ax, ay in {-1, 0, 1}, inside the frame, with the tent weight
+ *      w_q = max(0, 1 - |ax - dx|) * max(0, 1 - |ay - dy|) — the 2 x 2 bilinear footprint of the sub-sample's position.  A tap
+ *      counts when w_q != 0 and o_q == sub[s][p]; one that does not is skipped before its colour is loaded.
+ *      C_s = sum w_q c_q / sum w_q per channel, taps in the fixed order ay outer, ax inner.  When no tap counts — the object
+ *      is thinner than a pixel there and no neighbour's own ray sees it — C_s = c_p.
+ *   4. result: (sum_s C_s) / K per channel, s ascending, in binary32.  If EVERY C_s is c_p by rule 2 or by the fallback of
+ *      rule 3, the output is the input pixel, all four channels bit for bit: every interior pixel is the identity, and so is
+ *      k = 1.  Output alpha = input alpha, always.
+ *   5. a pixel's output depends on c_p and on the colours of neighbouring pixels whose object one of its sub-samples sees, on
+ *      nothing else: non-finite colours on another object cannot reach it.
+ *   6. whole frame only, one launch, no atomics: repeated calls give the same bits.  Output: W*H float4 into the handle's own
+ *      "antialiased" buffer (allocated on first use) or a bound one — never into the source, whose neighbours the pass reads.
+ *      SRT_AA_FRAMEBUFFER also writes tone_map(result) into the framebuffer (all memory rows, the render's packing).
+ *      Asynchronous on the launch stream behind earlier work (srt_wait / srt_poll cover it).
+ *   7. leaves the accumulator, the denoised buffer, the G-buffer, the sub-sample buffer, the temporal history,
+ *      srt_get_stats, srt_get_work_counts and the launch shape of later renders as they are. */
+#define SRT_AA_FRAMEBUFFER 2u        /* also write tone_map(result) into the framebuffer (all memory rows) */
+#define SRT_AA_SOURCE_ACCUMULATOR 0  /* c = the accumulator, bound or own */
+#define SRT_AA_SOURCE_DENOISED 1     /* c = the current "denoised" buffer, bound or own; SRT_ERR_STATE before the first srt_denoise */
+
+typedef struct srt_antialias_params {
+    int32_t k;       /* the k of the sub-sample buffer, 1..4 (1: the identity) */
+    int32_t source;  /* SRT_AA_SOURCE_* */
+    uint32_t flags;  /* SRT_AA_* */
+} srt_antialias_params;
+
+/* The library's defaults: k = 2, the accumulator, flags 0 (pure host, no device needed). */
+int srt_antialias_params_default(srt_antialias_params* out);
+/* SRT_ERR_INVALID_ARG for k outside 1..4, an unknown source or unknown flags.  SRT_ERR_STATE when OBJECT has never been bound
+ * or rendered, when the sub-sample buffer has never been bound or rendered, and when that buffer is the handle's own and its
+ * last render used another k, has not covered the whole frame since the last scene or camera change, or used a camera other
+ * than the current one (a bound buffer is the caller's responsibility). */
+int srt_antialias(srt_context* ctx, const srt_antialias_params* params);
+/* Write the result into a caller DEVICE buffer of W*H float4 instead of the handle's own; NULL = own.  Does not wait. */
+int srt_bind_antialiased(srt_context* ctx, void* d_float4);
+/* Wait, then copy the W*H float4 result (scene rows) to host memory.  SRT_ERR_STATE before the first srt_antialias. */
+int srt_read_antialiased(srt_context* ctx, float* dst_rgba);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

@@ -21,6 +21,7 @@ except ImportError:  # plumbing only; the native libraries work without it
 
 from . import capi  # noqa: F401
 from .capi import (  # noqa: F401
+    AntialiasParams,
     Camera,
     DenoiseParams,
     Environment,
@@ -32,6 +33,7 @@ from .capi import (  # noqa: F401
     RenderParams,
     SrtError,
     Stats,
+    SubsampleParams,
     TemporalParams,
     UpsampleParams,
     build_native,
@@ -44,6 +46,6 @@ from . import host  # noqa: F401
 
 __all__ = [
     "capi", "host", "PathTracer", "SrtError", "Object", "Material", "Camera", "Environment",
-    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
+    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "SubsampleParams", "AntialiasParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
     "load_library",
 ]

@@ -29,6 +29,8 @@ TEMPORAL_GUIDES = GBUF_OBJECT | GBUF_NORMAL_DEPTH | GBUF_POSITION
 UPSAMPLE_IN_PLACE, UPSAMPLE_FRAMEBUFFER = 1, 2
 # guides srt_upsample reads
 UPSAMPLE_GUIDES = GBUF_OBJECT | GBUF_NORMAL_DEPTH | GBUF_POSITION
+AA_FRAMEBUFFER = 2
+AA_SOURCE_ACCUMULATOR, AA_SOURCE_DENOISED = 0, 1
 ABI_VERSION = 7
 
 # every symbol include/srt_pathtrace.h declares (tests check the library exports them all)
@@ -43,6 +45,8 @@ EXPORTS = [
     "srt_temporal_params_default", "srt_temporal_accumulate", "srt_read_history_length",
     "srt_update_scene", "srt_motion_output", "srt_bind_motion", "srt_read_motion",
     "srt_upsample_params_default", "srt_upsample", "srt_bind_upsampled", "srt_read_upsampled",
+    "srt_render_subsamples", "srt_bind_subsamples", "srt_read_subsamples",
+    "srt_antialias_params_default", "srt_antialias", "srt_bind_antialiased", "srt_read_antialiased",
 ]
 
 
@@ -134,6 +138,14 @@ class TemporalParams(C.Structure):
 class UpsampleParams(C.Structure):
     _fields_ = [("steps", C.c_int32), ("stripe_width", C.c_int32), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
                 ("flags", C.c_uint32)]
+
+
+class SubsampleParams(C.Structure):
+    _fields_ = [("row_begin", C.c_int32), ("row_end", C.c_int32), ("k", C.c_int32), ("flags", C.c_uint32)]
+
+
+class AntialiasParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("source", C.c_int32), ("flags", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -249,6 +261,13 @@ def open_library(path):
     L.srt_upsample.argtypes = [ctx, C.POINTER(UpsampleParams)]
     L.srt_bind_upsampled.argtypes = [ctx, C.c_void_p]
     L.srt_read_upsampled.argtypes = [ctx, C.POINTER(C.c_float)]
+    L.srt_render_subsamples.argtypes = [ctx, C.POINTER(SubsampleParams)]
+    L.srt_bind_subsamples.argtypes = [ctx, C.c_void_p]
+    L.srt_read_subsamples.argtypes = [ctx, C.POINTER(C.c_int32)]
+    L.srt_antialias_params_default.argtypes = [C.POINTER(AntialiasParams)]
+    L.srt_antialias.argtypes = [ctx, C.POINTER(AntialiasParams)]
+    L.srt_bind_antialiased.argtypes = [ctx, C.c_void_p]
+    L.srt_read_antialiased.argtypes = [ctx, C.POINTER(C.c_float)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -303,6 +322,15 @@ def upsample_defaults(lib=None):
     return {n: getattr(p, n) for n, _ in UpsampleParams._fields_}
 
 
+def antialias_defaults(lib=None):
+    """srt_antialias_params_default as a dict (pure host: no GPU needed)."""
+    p = AntialiasParams()
+    rc = (lib if lib is not None else load_library()).srt_antialias_params_default(C.byref(p))
+    if rc:
+        raise SrtError(rc, "srt_antialias_params_default")
+    return {n: getattr(p, n) for n, _ in AntialiasParams._fields_}
+
+
 def __getattr__(name):
     # DENOISE_DEFAULTS / TEMPORAL_DEFAULTS / UPSAMPLE_DEFAULTS: the library's defaults (denoise_defaults(), temporal_defaults(),
     # upsample_defaults()), read when first asked for, so that importing this module does not need the built library
@@ -312,6 +340,8 @@ def __getattr__(name):
         return temporal_defaults()
     if name == "UPSAMPLE_DEFAULTS":
         return upsample_defaults()
+    if name == "ANTIALIAS_DEFAULTS":
+        return antialias_defaults()
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -342,6 +372,13 @@ def upsample_params(steps=None, stripe_width=None, sigma_normal=None, sigma_plan
     return UpsampleParams(int(d["steps"] if steps is None else steps), int(d["stripe_width"] if stripe_width is None else stripe_width),
                           float(d["sigma_normal"] if sigma_normal is None else sigma_normal),
                           float(d["sigma_plane"] if sigma_plane is None else sigma_plane), flags)
+
+
+def antialias_params(k=None, denoised=False, framebuffer=False, lib=None):
+    """An AntialiasParams: the library's default k unless one is given, the source and the flag by name."""
+    d = antialias_defaults(lib)
+    return AntialiasParams(int(d["k"] if k is None else k), AA_SOURCE_DENOISED if denoised else AA_SOURCE_ACCUMULATOR,
+                           AA_FRAMEBUFFER if framebuffer else 0)
 
 
 def _f3(v):
@@ -463,44 +500,33 @@ class PathTracer:
         Device, dtype, shape and contiguity are checked here, before any native call; the caller keeps the tensor alive
         until the work that writes it has finished."""
         bit = _gbuffer_spec(name)[0]
-        if tensor is None:
-            self._ck(self.L.srt_bind_gbuffer(self._h, bit, None))
-            return
-        import torch
-
         dtype, shape = self._gbuffer_shape(name)
-        want = torch.int32 if dtype == np.int32 else torch.float32
-        if not isinstance(tensor, torch.Tensor):
-            raise TypeError("bind_gbuffer(%r): expected a torch.Tensor, got %s" % (name, type(tensor).__name__))
-        if tensor.device.type != "cuda" or tensor.device.index != self.device:
-            raise ValueError("bind_gbuffer(%r): tensor on %s, the tracer renders on cuda:%d" % (name, tensor.device, self.device))
-        if tensor.dtype != want:
-            raise TypeError("bind_gbuffer(%r): dtype %s, want %s" % (name, tensor.dtype, want))
-        if tuple(tensor.shape) != shape:
-            raise ValueError("bind_gbuffer(%r): shape %s, want %s" % (name, tuple(tensor.shape), shape))
-        if not tensor.is_contiguous():
-            raise ValueError("bind_gbuffer(%r): tensor is not contiguous" % name)
-        self._ck(self.L.srt_bind_gbuffer(self._h, bit, C.c_void_p(tensor.data_ptr())))
+        ptr = self._tensor_ptr("bind_gbuffer(%r)" % name, tensor, dtype, shape)  # (checked before the library is touched)
+        self._ck(self.L.srt_bind_gbuffer(self._h, bit, ptr))
 
-    def _float4_tensor_ptr(self, what, tensor):
-        """The device pointer of a tensor a float4 output is bound to: on this tracer's device, (H, W, 4) float32 and
-        contiguous; None passes through (the handle's own buffer)."""
+    def _tensor_ptr(self, what, tensor, dtype, shape):
+        """The device pointer of a tensor an output is bound to: on this tracer's device, of numpy dtype `dtype` (int32 or
+        float32), of `shape` and contiguous; None passes through (the handle's own buffer)."""
         if tensor is None:
             return None
         import torch
 
-        shape = (self.height, self.width, 4)
+        want = torch.int32 if dtype == np.int32 else torch.float32
         if not isinstance(tensor, torch.Tensor):
             raise TypeError("%s: expected a torch.Tensor, got %s" % (what, type(tensor).__name__))
         if tensor.device.type != "cuda" or tensor.device.index != self.device:
             raise ValueError("%s: tensor on %s, the tracer renders on cuda:%d" % (what, tensor.device, self.device))
-        if tensor.dtype != torch.float32:
-            raise TypeError("%s: dtype %s, want torch.float32" % (what, tensor.dtype))
-        if tuple(tensor.shape) != shape:
-            raise ValueError("%s: shape %s, want %s" % (what, tuple(tensor.shape), shape))
+        if tensor.dtype != want:
+            raise TypeError("%s: dtype %s, want %s" % (what, tensor.dtype, want))
+        if tuple(tensor.shape) != tuple(shape):
+            raise ValueError("%s: shape %s, want %s" % (what, tuple(tensor.shape), tuple(shape)))
         if not tensor.is_contiguous():
             raise ValueError("%s: tensor is not contiguous" % what)
         return C.c_void_p(tensor.data_ptr())
+
+    def _float4_tensor_ptr(self, what, tensor):
+        """_tensor_ptr for a float4 output: (H, W, 4) float32."""
+        return self._tensor_ptr(what, tensor, np.float32, (self.height, self.width, 4))
 
     def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None, albedo=True, framebuffer=False,
                 gbuffer=True):
@@ -577,6 +603,60 @@ class PathTracer:
         """srt_bind_upsampled: write the result into a torch tensor on this tracer's device, (H, W, 4) float32 and contiguous
         (None: the handle's own buffer).  Checked here, before any native call, as bind_denoised checks."""
         self._ck(self.L.srt_bind_upsampled(self._h, self._float4_tensor_ptr("bind_upsampled", tensor)))
+
+    def render_subsamples(self, k=None, rows=None, flags=0):
+        """srt_render_subsamples: the hit object of the k x k sub-pixel rays of every pixel of memory rows `rows` (default: the
+        whole frame); k None takes ANTIALIAS_DEFAULTS.  Asynchronous, like render_gbuffer()."""
+        rb, re = rows if rows is not None else (0, self.height)
+        p = SubsampleParams(int(rb), int(re), int(antialias_defaults(self.L)["k"] if k is None else k), int(flags))
+        self._ck(self.L.srt_render_subsamples(self._h, C.byref(p)))
+        self._subsample_k = p.k
+
+    def subsamples(self, k=None):
+        """srt_read_subsamples: (k*k, H, W) int32, rows = scene rows; k is that of the last render_subsamples of this tracer
+        unless given (a buffer filled by other means)."""
+        k = int(getattr(self, "_subsample_k", 0) if k is None else k)
+        out = np.empty((max(k, 1) ** 2, self.height, self.width), dtype=np.int32)
+        self._ck(self.L.srt_read_subsamples(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def bind_subsamples(self, tensor, k=None):
+        """srt_bind_subsamples: keep the sub-samples in a torch tensor on this tracer's device, (k*k, H, W) int32 and
+        contiguous (None: the handle's own buffer); k None takes the tensor's first dimension.  Checked before any native
+        call, as bind_gbuffer checks."""
+        if tensor is None:
+            self._ck(self.L.srt_bind_subsamples(self._h, None))
+            return
+        if k is None:
+            k = {1: 1, 4: 2, 9: 3, 16: 4}.get(tensor.shape[0] if getattr(tensor, "ndim", 0) == 3 else None)
+        if k not in (1, 2, 3, 4):
+            raise ValueError("bind_subsamples: want (k*k, H, W) for k in 1..4")
+        ptr = self._tensor_ptr("bind_subsamples", tensor, np.int32, (k * k, self.height, self.width))
+        self._ck(self.L.srt_bind_subsamples(self._h, ptr))
+        self._subsample_k = k
+
+    def antialias(self, k=None, denoised=False, framebuffer=False, guides=True):
+        """srt_antialias over the whole frame: every pixel rebuilt from its own colour and those of the neighbours whose object
+        its k x k sub-samples see.  The colour is the accumulator or, with denoised=True, the denoised buffer.  guides=True
+        first enqueues render_gbuffer("object") and render_subsamples(k) for the current scene and camera; guides=False
+        uses both as they are.  Asynchronous."""
+        p = antialias_params(k, denoised, framebuffer, lib=self.L)
+        if guides:
+            self.render_gbuffer(outputs=GBUF_OBJECT)
+            self.render_subsamples(p.k)
+        self._ck(self.L.srt_antialias(self._h, C.byref(p)))
+
+    def antialiased(self):
+        """srt_read_antialiased: the result, (H, W, 4) float32, rows = scene rows (the orientation of accumulator())."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self.L.srt_read_antialiased(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def bind_antialiased(self, tensor):
+        """srt_bind_antialiased: write the result into a torch tensor on this tracer's device, (H, W, 4) float32 and contiguous
+        (None: the handle's own buffer).  Checked here, before any native call, as bind_denoised checks."""
+        ptr = self._float4_tensor_ptr("bind_antialiased", tensor)
+        self._ck(self.L.srt_bind_antialiased(self._h, ptr))
 
     def wait(self):
         self._ck(self.L.srt_wait(self._h))

@@ -21,6 +21,7 @@
 #include "srt_denoise.hip.h"
 #include "srt_temporal.hip.h"
 #include "srt_upsample.hip.h"
+#include "srt_antialias.hip.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -278,6 +279,25 @@ struct srt_context {
     float4* d_up_bound = nullptr;
     bool up_written = false;
 
+    // anti-aliasing (srt_render_subsamples, srt_antialias).  The sub-sample planes: the handle's own buffer (allocated on first
+    // use, re-allocated when k grows), the caller's bound one (srt_bind_subsamples; NULL = own), and the k last rendered into
+    // the current buffer (0 = none; srt_read_subsamples).  What the OWN buffer holds: its k, the camera and the scene (a count
+    // of scene changes) it was rendered with, and the memory rows rendered with exactly those so far — srt_antialias refuses an
+    // own buffer that is not a whole frame of the current scene and camera.
+    DeviceBuffer<int32_t> d_ss_own;
+    int32_t* d_ss_bound = nullptr;
+    int ss_last_k = 0;
+    int ss_own_k = 0;
+    srt_camera ss_own_cam{};
+    uint64_t ss_own_scene = 0;
+    std::vector<bool> ss_own_rows;
+    uint64_t scene_changes = 0;  // srt_set_scene / srt_update_scene / srt_set_meshes calls so far
+    // the handle's own result buffer (allocated on first use), the caller's bound one (srt_bind_antialiased; NULL = own), and
+    // whether a call has been enqueued yet (srt_read_antialiased)
+    DeviceBuffer<float4> d_aa_own;
+    float4* d_aa_bound = nullptr;
+    bool aa_written = false;
+
     char error[512] = "";
 };
 
@@ -508,6 +528,7 @@ static int set_scene_impl(srt_context* ctx, const char* fn, const srt_object* ob
 
 // Host-side allocation failures (std::bad_alloc from the image / BVH builders) must not cross the C boundary.
 static int set_scene_guarded(srt_context* ctx, const char* fn, const srt_object* objects, size_t count) {
+    if (ctx) ++ctx->scene_changes;  // the handle's own sub-samples belong to the old scene
     try {
         return set_scene_impl(ctx, fn, objects, count);
     } catch (const std::bad_alloc&) {
@@ -555,7 +576,7 @@ static int set_meshes_impl(srt_context* ctx, const srt_mesh* meshes, size_t coun
 }
 
 int srt_set_meshes(srt_context* ctx, const srt_mesh* meshes, size_t count) {
-    if (ctx) ctx->tp_valid = false;
+    if (ctx) ctx->tp_valid = false, ++ctx->scene_changes;
     try {
         return set_meshes_impl(ctx, meshes, count);
     } catch (const std::bad_alloc&) {
@@ -1604,6 +1625,133 @@ int srt_read_upsampled(srt_context* ctx, float* dst_rgba) {
     if (!ctx || !dst_rgba) return SRT_ERR_INVALID_ARG;
     const float4* src = bound_or_own(ctx->d_up_bound, ctx->d_up_own);
     if (!ctx->up_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_read_upsampled: nothing has been upsampled into this buffer yet");
+    if (const int rc = finish_stream(ctx)) return rc;
+    SRT_HIP(ctx, hipMemcpy(dst_rgba, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+// ---- anti-aliasing: sub-sample first hits and the resolve ------------------------------------------------------------------
+int srt_render_subsamples(srt_context* ctx, const srt_subsample_params* g) {
+    if (!ctx || !g) return SRT_ERR_INVALID_ARG;
+    if (!ctx->scene_set) return fail(ctx, SRT_ERR_STATE, "srt_render_subsamples: srt_set_scene has not been called");
+    if (!ctx->camera.set) return fail(ctx, SRT_ERR_STATE, "srt_render_subsamples: srt_set_camera has not been called");
+    const int W = ctx->width, H = ctx->height;
+    if (g->row_begin < 0 || g->row_end > H || g->row_begin >= g->row_end)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render_subsamples: bad row band [%d,%d) for height %d", g->row_begin, g->row_end, H);
+    if (g->k < 1 || g->k > 4) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render_subsamples: k %d outside 1..4", g->k);
+    if (g->flags != 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render_subsamples: flags must be 0");
+    // the virtual frame's pixel coordinates and sizes must be exact in binary32 (and its aspect ratio the frame's own)
+    if (2ll * g->k * W >= (1ll << 24) || 2ll * g->k * H >= (1ll << 24))
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render_subsamples: 2k x the frame (%d x %d, k %d) must stay below 2^24", W, H, g->k);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)W * (size_t)H;
+    if (!ctx->d_ss_bound) {
+        SRT_HIP(ctx, ctx->d_ss_own.ensure((size_t)g->k * g->k * px * sizeof(int32_t)));
+        if (ctx->ss_own_k != g->k || ctx->ss_own_scene != ctx->scene_changes || !same_camera(ctx->ss_own_cam, ctx->camera.cam) ||
+            ctx->ss_own_rows.size() != (size_t)H) {
+            ctx->ss_own_k = g->k, ctx->ss_own_scene = ctx->scene_changes, ctx->ss_own_cam = ctx->camera.cam;
+            ctx->ss_own_rows.assign((size_t)H, false);
+        }
+        std::fill(ctx->ss_own_rows.begin() + g->row_begin, ctx->ss_own_rows.begin() + g->row_end, true);
+    }
+    // the render's kernel parameters for this band, as srt_render_gbuffer takes them
+    srt_render_params p{};
+    p.row_begin = g->row_begin, p.row_end = g->row_end, p.first_sample = 1, p.sample_count = 1;
+    srt::KernelParams K;
+    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
+    K.flags &= srt::KF_BOXES_FINITE;
+    K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // the pass touches none of them
+    const srt::SubsampleOut out{bound_or_own(ctx->d_ss_bound, ctx->d_ss_own), g->k};
+    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
+    void (*const kernel)(srt::KernelParams, srt::SubsampleOut) = in_lds ? (mesh ? srt::subsample_kernel<true, true> : srt::subsample_kernel<true, false>)
+                                                                        : (mesh ? srt::subsample_kernel<false, true> : srt::subsample_kernel<false, false>);
+    // persistent workgroups, sized as srt_render_gbuffer sizes them
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, srt::WG_THREADS, ks.lds_bytes) != hipSuccess || per_cu < 1)
+        per_cu = 1, (void)hipGetLastError();
+    per_cu = per_cu > 4 ? 4 : per_cu;
+    const long long tiles = (long long)((W + srt::TILE_W - 1) / srt::TILE_W) * ((K.rows + srt::TILE_H - 1) / srt::TILE_H);
+    const long long need = (tiles + srt::WG_TILES_X * srt::WG_TILES_Y - 1) / (srt::WG_TILES_X * srt::WG_TILES_Y);
+    const long long wgs = std::min<long long>(need, (long long)ctx->cu_count * per_cu);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, out);
+    SRT_HIP(ctx, hipGetLastError());
+    ctx->ss_last_k = g->k;
+    return SRT_OK;
+}
+
+int srt_bind_subsamples(srt_context* ctx, void* d_int32) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    ctx->d_ss_bound = (int32_t*)d_int32;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_gbuffer)
+    return SRT_OK;
+}
+
+int srt_read_subsamples(srt_context* ctx, int32_t* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const int32_t* src = bound_or_own(ctx->d_ss_bound, ctx->d_ss_own);
+    const int k = ctx->d_ss_bound ? ctx->ss_last_k : ctx->ss_own_k;
+    if (!src || k < 1) return fail(ctx, SRT_ERR_STATE, "srt_read_subsamples: no sub-samples have been rendered into this buffer yet");
+    if (const int rc = finish_stream(ctx)) return rc;
+    SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)k * k * ctx->width * ctx->height * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+int srt_antialias_params_default(srt_antialias_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    out->k = 2;
+    out->source = SRT_AA_SOURCE_ACCUMULATOR;
+    out->flags = 0;
+    return SRT_OK;
+}
+
+int srt_antialias(srt_context* ctx, const srt_antialias_params* a) {
+    if (!ctx || !a) return SRT_ERR_INVALID_ARG;
+    if (a->k < 1 || a->k > 4) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_antialias: k %d outside 1..4", a->k);
+    if (a->source != SRT_AA_SOURCE_ACCUMULATOR && a->source != SRT_AA_SOURCE_DENOISED)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_antialias: unknown source %d", a->source);
+    if (a->flags & ~SRT_AA_FRAMEBUFFER) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_antialias: unknown flags 0x%x", a->flags);
+    const void* guide[1] = {};
+    if (const int rc = find_guides(ctx, "srt_antialias", 1, nullptr, guide)) return rc;
+    const int32_t* const sub = bound_or_own(ctx->d_ss_bound, ctx->d_ss_own);
+    if (!sub) return fail(ctx, SRT_ERR_STATE, "srt_antialias: the sub-sample buffer has neither been bound nor rendered (srt_render_subsamples)");
+    if (!ctx->d_ss_bound) {  // the handle's own: a whole frame of this k, scene and camera, or nothing
+        if (ctx->ss_own_k != a->k) return fail(ctx, SRT_ERR_STATE, "srt_antialias: the sub-samples were rendered with k %d, not %d", ctx->ss_own_k, a->k);
+        if (ctx->ss_own_scene != ctx->scene_changes || !ctx->camera.set || !same_camera(ctx->ss_own_cam, ctx->camera.cam))
+            return fail(ctx, SRT_ERR_STATE, "srt_antialias: the sub-samples were rendered with another scene or camera (srt_render_subsamples after the change)");
+        if (std::find(ctx->ss_own_rows.begin(), ctx->ss_own_rows.end(), false) != ctx->ss_own_rows.end())
+            return fail(ctx, SRT_ERR_STATE, "srt_antialias: the sub-samples do not cover the whole frame since the last scene or camera change");
+    }
+    const float4* src = ctx->d_acc;
+    if (a->source == SRT_AA_SOURCE_DENOISED) {
+        src = bound_or_own(ctx->d_dn_bound, ctx->d_dn_own);
+        if (!ctx->dn_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_antialias: SRT_AA_SOURCE_DENOISED before the first srt_denoise");
+    }
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_aa_bound) SRT_HIP(ctx, ctx->d_aa_own.ensure((size_t)ctx->width * (size_t)ctx->height * sizeof(float4)));
+    srt::AntialiasLaunch A{};
+    A.src = src;
+    A.dst = bound_or_own(ctx->d_aa_bound, ctx->d_aa_own);
+    A.object = (const int32_t*)guide[0];
+    A.sub = sub;
+    A.framebuffer = (a->flags & SRT_AA_FRAMEBUFFER) ? ctx->d_fb : nullptr;
+    A.width = ctx->width, A.height = ctx->height;
+    void (*const kernel)(srt::AntialiasLaunch) = a->k == 1 ? srt::antialias_kernel<1> : a->k == 2 ? srt::antialias_kernel<2>
+                                                 : a->k == 3 ? srt::antialias_kernel<3> : srt::antialias_kernel<4>;
+    hipLaunchKernelGGL(kernel, frame_tile_grid(ctx), dim3(srt::WG_THREADS), 0, ctx->stream, A);
+    SRT_HIP(ctx, hipGetLastError());
+    ctx->aa_written = true;
+    return SRT_OK;
+}
+
+int srt_bind_antialiased(srt_context* ctx, void* d_float4) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    ctx->d_aa_bound = (float4*)d_float4;  // (no synchronisation: an enqueued call keeps the buffer it was given)
+    return SRT_OK;
+}
+
+int srt_read_antialiased(srt_context* ctx, float* dst_rgba) {
+    if (!ctx || !dst_rgba) return SRT_ERR_INVALID_ARG;
+    const float4* src = bound_or_own(ctx->d_aa_bound, ctx->d_aa_own);
+    if (!ctx->aa_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_read_antialiased: nothing has been anti-aliased into this buffer yet");
     if (const int rc = finish_stream(ctx)) return rc;
     SRT_HIP(ctx, hipMemcpy(dst_rgba, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
     return SRT_OK;

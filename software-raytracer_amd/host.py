@@ -7,8 +7,8 @@ import subprocess
 
 import numpy as np
 
-from .capi import (DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, DenoiseParams, Mesh, Object, Stats,
-                   TemporalParams, UpsampleParams, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
+from .capi import (DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, DenoiseParams, Mesh, Object, Stats,
+                   TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_PKG, "libsrt_host.so")
@@ -28,6 +28,7 @@ EXPORTS = [
     "srt_host_renderer_move_camera",
     "srt_host_renderer_update_scene", "srt_host_renderer_motion_output", "srt_host_renderer_read_motion",
     "srt_host_renderer_upsample", "srt_host_renderer_read_upsampled", "srt_host_renderer_guided_upsample",
+    "srt_host_renderer_antialias", "srt_host_renderer_read_antialiased", "srt_host_renderer_set_antialias",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -117,6 +118,9 @@ def load_library():
     L.srt_host_renderer_upsample.argtypes = [vp, C.POINTER(UpsampleParams)]
     L.srt_host_renderer_read_upsampled.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_guided_upsample.argtypes = [vp, C.c_int]
+    L.srt_host_renderer_antialias.argtypes = [vp, C.POINTER(AntialiasParams)]
+    L.srt_host_renderer_read_antialiased.argtypes = [vp, C.POINTER(C.c_float)]
+    L.srt_host_renderer_set_antialias.argtypes = [vp, C.c_int]
     L.srt_host_multi_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]
     L.srt_host_multi_create.restype = vp
     L.srt_host_multi_destroy.argtypes = [vp]
@@ -393,6 +397,22 @@ class Renderer:
         """PathTraceRenderer::guidedUpsample: render_frame() follows every frame of blocks with the guides and the upsampler
         into the framebuffer."""
         self._ck(self.L.srt_host_renderer_guided_upsample(self._h, 1 if on else 0))
+
+    def antialias(self, k=None, denoised=False, framebuffer=False):
+        """PathTraceRenderer::Antialias: the OBJECT guide and the k x k sub-samples when they are stale, then srt_antialias
+        on the accumulator (denoised=True: the denoised buffer).  k None takes capi.ANTIALIAS_DEFAULTS."""
+        p = antialias_params(k, denoised, framebuffer)
+        self._ck(self.L.srt_host_renderer_antialias(self._h, C.byref(p)))
+
+    def antialiased(self):
+        """PathTraceRenderer::ReadAntialiased: (H, W, 4) float32, scene rows, as capi.PathTracer.antialiased returns it."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_antialiased(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def set_antialias(self, k):
+        """PathTraceRenderer::antialias: render_frame() and render_temporal_frame() end in the resolve with this k (0: off)."""
+        self._ck(self.L.srt_host_renderer_set_antialias(self._h, int(k)))
 
     def stats(self):
         s = Stats()

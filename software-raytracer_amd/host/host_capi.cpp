@@ -242,6 +242,15 @@ int srt_host_renderer_guided_upsample(srt_host_renderer* h, int on) {
     h->r->guidedUpsample = on != 0;
     return 0;
 }
+// anti-aliasing over the whole frame (PathTraceRenderer::Antialias renders the OBJECT guide and the sub-samples when they are
+// stale), its result, and the antialias setting of RenderFrame / RenderTemporalFrame (0 = off)
+int srt_host_renderer_antialias(srt_host_renderer* h, const srt_antialias_params* p) { SRT_HOST_TRY(h, h->r->Antialias(p->k, p->source, p->flags)) }
+int srt_host_renderer_read_antialiased(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadAntialiased(dst)) }
+int srt_host_renderer_set_antialias(srt_host_renderer* h, int k) {
+    if (k < 0 || k > 4) return SRT_ERR_INVALID_ARG;
+    h->r->antialias = k;
+    return 0;
+}
 int srt_host_renderer_stats(srt_host_renderer* h, srt_stats* out) { SRT_HOST_TRY(h, *out = h->r->Stats()) }
 void* srt_host_renderer_handle(srt_host_renderer* h) { return h->r->handle(); }
 

@@ -29,6 +29,7 @@ void PathTraceRenderer::SetScene(const Scene& scene) {
     std::vector<srt_mesh> meshes = scene.MeshViews();  // EXTENSION: geometry of "Mesh" renderers
     check(srt_set_meshes(ctx_, meshes.data(), meshes.size()), "srt_set_meshes");
     scene_set_ = false;
+    aa_k_ = 0;
     check(srt_set_scene(ctx_, flat.data(), flat.size()), "srt_set_scene");
     scene_set_ = true;
     scene_count_ = flat.size();
@@ -59,6 +60,7 @@ void PathTraceRenderer::UpdateScene(const Scene& scene) {
         SetScene(scene);
         return;
     }
+    aa_k_ = 0;
     const int rc = srt_update_scene(ctx_, flat.data(), flat.size());
     if (rc != SRT_OK) {
         // a refused list may have left the context without a scene: start afresh (the next edit goes through SetScene)
@@ -81,7 +83,7 @@ void PathTraceRenderer::SetRowBand(int begin, int end) {
     Invalidate();
 }
 
-void PathTraceRenderer::push_camera() {
+srt_camera PathTraceRenderer::current_camera() const {
     srt_camera c{};
     const Vec3* src[4] = {&camera.position, &camera.right, &camera.up, &camera.forward};
     float* dst[4] = {c.position, c.right, c.up, c.forward};
@@ -91,12 +93,19 @@ void PathTraceRenderer::push_camera() {
         dst[i][2] = src[i]->z;
     }
     c.fov_degrees = FOV;
+    return c;
+}
+
+void PathTraceRenderer::push_camera() {
+    const srt_camera c = current_camera();
     check(srt_set_camera(ctx_, &c), "srt_set_camera");
 }
 
 bool PathTraceRenderer::RenderFrame() {
     if (guidedUpsample && (row_begin_ != 0 || row_end_ != height_))
         throw RendererError(SRT_ERR_STATE, "RenderFrame: guidedUpsample with a row band; the upsampler covers the whole frame");
+    if (antialias > 0 && (row_begin_ != 0 || row_end_ != height_))
+        throw RendererError(SRT_ERR_STATE, "RenderFrame: antialias with a row band; the resolve covers the whole frame");
     if (first_frame_) {
         first_frame_ = false;  // workers start with the initial globals (:30-35,47-48,271)
     } else {
@@ -135,6 +144,8 @@ bool PathTraceRenderer::RenderFrame() {
         u.stripe_width = p.stripe_width;
         u.flags = SRT_UPSAMPLE_FRAMEBUFFER;  // (not in place: the accumulator stays what the reference accumulates)
         Upsample(u);
+    } else if (antialias > 0) {
+        Antialias(antialias, SRT_AA_SOURCE_ACCUMULATOR, SRT_AA_FRAMEBUFFER);
     }
     return true;
 }
@@ -216,6 +227,25 @@ void PathTraceRenderer::Upsample(const srt_upsample_params& params) { check(srt_
 
 void PathTraceRenderer::ReadUpsampled(float* dst_rgba) { check(srt_read_upsampled(ctx_, dst_rgba), "srt_read_upsampled"); }
 
+void PathTraceRenderer::Antialias(int k, int source, uint32_t flags) {
+    if (row_begin_ != 0 || row_end_ != height_)
+        throw RendererError(SRT_ERR_STATE, "Antialias: the renderer has a row band; the resolve covers the whole frame");
+    const srt_camera c = current_camera();
+    if (aa_k_ != k || std::memcmp(&aa_cam_, &c, sizeof c) != 0) {
+        aa_k_ = 0;
+        RenderGBufferRows(SRT_GBUF_OBJECT, 0, height_);  // (pushes the camera)
+        srt_subsample_params s{};
+        s.row_begin = 0, s.row_end = height_, s.k = k;
+        check(srt_render_subsamples(ctx_, &s), "srt_render_subsamples");
+        aa_k_ = k, aa_cam_ = c;
+    }
+    srt_antialias_params a{};
+    a.k = k, a.source = source, a.flags = flags;
+    check(srt_antialias(ctx_, &a), "srt_antialias");
+}
+
+void PathTraceRenderer::ReadAntialiased(float* dst_rgba) { check(srt_read_antialiased(ctx_, dst_rgba), "srt_read_antialiased"); }
+
 void PathTraceRenderer::RenderTemporalFrame(uint32_t spp, bool denoise) {
     if (spp == 0) throw RendererError(SRT_ERR_INVALID_ARG, "RenderTemporalFrame: spp must be >= 1");
     if (row_begin_ != 0 || row_end_ != height_)
@@ -245,6 +275,7 @@ void PathTraceRenderer::RenderTemporalFrame(uint32_t spp, bool denoise) {
         d.flags |= SRT_DENOISE_FRAMEBUFFER;
         Denoise(d);
     }
+    if (antialias > 0) Antialias(antialias, denoise ? SRT_AA_SOURCE_DENOISED : SRT_AA_SOURCE_ACCUMULATOR, SRT_AA_FRAMEBUFFER);
     temporal_reset_ = false;
     ++temporal_frames_;
     // the accumulator now holds a blended estimate no render can continue

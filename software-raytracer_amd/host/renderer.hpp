@@ -70,6 +70,9 @@ class PathTraceRenderer {
     // srt_upsample into the framebuffer, so that the frame shown is reconstructed from the blocks' anchors instead of made of
     // squares.  The accumulator stays what the reference accumulates.  Whole frame only.
     bool guidedUpsample = false;
+    // not in the reference: 1..4 makes RenderFrame and RenderTemporalFrame end in the anti-aliasing resolve (srt_antialias with
+    // this k and SRT_AA_FRAMEBUFFER); 0 = off.  The accumulator stays what the reference accumulates.  Whole frame only.
+    int antialias = 0;
     Transform camera;   // :295-297
 
     PathTraceRenderer(int device, int width, int height);
@@ -109,6 +112,10 @@ class PathTraceRenderer {
     // With guidedUpsample a frame of blocks is followed by RenderGBuffer (the three guides) and Upsample with the library's
     // defaults, the frame's own steps and stripe_width and SRT_UPSAMPLE_FRAMEBUFFER — never in place; SRT_ERR_STATE when the
     // renderer has a row band.  Without it the calls are exactly the above.
+    // With antialias = k > 0 the frame ends in Antialias(k): the OBJECT guide and the k x k sub-samples are rendered when the
+    // scene, the camera or k has changed since they were last rendered — once per change, not per frame — and srt_antialias
+    // resolves the accumulator into the framebuffer.  A frame the upsampler has just reconstructed (guidedUpsample, steps > 1)
+    // is shown as the upsampler left it: its result is not a source of srt_antialias.  SRT_ERR_STATE with a row band.
     bool RenderFrame();
     // Picking (:525-541): x, y in window coordinates (y down, as the mouse reports it)
     int Pick(int mouse_x, int mouse_y);
@@ -145,11 +152,17 @@ class PathTraceRenderer {
     // RenderGBuffer first).  Asynchronous; ReadUpsampled waits and copies the W x H float4 result (scene rows).
     void Upsample(const srt_upsample_params& params);
     void ReadUpsampled(float* dst_rgba);
+    // Anti-aliasing over the whole frame: render the OBJECT guide and the k x k sub-samples (srt_render_subsamples) if the
+    // scene, the camera or k has changed since this renderer last rendered them, then srt_antialias with `source`
+    // (SRT_AA_SOURCE_*) and `flags` (SRT_AA_*).  Asynchronous; ReadAntialiased waits and copies the W x H float4 result.
+    void Antialias(int k, int source = SRT_AA_SOURCE_ACCUMULATOR, uint32_t flags = 0);
+    void ReadAntialiased(float* dst_rgba);
     // One frame of a moving camera that keeps its samples (whole frame only): push the camera, render `spp` samples with
     // SRT_RENDER_RESET and seed + k (k = the number of temporal frames this renderer has rendered before, so that the noise
     // does not stay fixed to the screen), the first-hit guides, srt_temporal_accumulate with the library's defaults
     // (samples = spp, max_samples raised to spp if below; SRT_TEMPORAL_RESET on the first temporal frame and after
-    // Invalidate(), SetScene, SetEnvironment or SetRowBand), then with `denoise` srt_denoise with its defaults.  The last step
+    // Invalidate(), SetScene, SetEnvironment or SetRowBand), then with `denoise` srt_denoise with its defaults, then with
+    // antialias > 0 Antialias on the denoised buffer (with `denoise`) or the accumulator.  The last step
     // writes the framebuffer.  Later RenderFrame / RenderSamples calls start a fresh accumulation.
     void RenderTemporalFrame(uint32_t spp, bool denoise);
 
@@ -158,6 +171,10 @@ class PathTraceRenderer {
    private:
     void check(int rc, const char* what);
     void push_camera();
+    srt_camera current_camera() const;
+    // the sub-samples and the OBJECT guide Antialias last rendered: their k (0: none, or the scene has changed since) and camera
+    int aa_k_ = 0;
+    srt_camera aa_cam_{};
     srt_context* ctx_ = nullptr;
     int width_, height_;
     int row_begin_, row_end_;

@@ -65,7 +65,7 @@ static void usage() {
                  "usage: srt_render --scene FILE [--width 1280] [--height 720] [--spp 32] [--bounces 2]\n"
                  "                  [--fov 55] [--seed 0] [--device 0 | --devices 0,1,2,...] [--out frame.ppm] [--resave FILE]\n"
                  "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]\n"
-                 "                  [--move-object IDX:DX,DY,DZ]...] [--steps N] [--upsample PATH]\n"
+                 "                  [--move-object IDX:DX,DY,DZ]...] [--steps N] [--upsample PATH] [--aa K]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
                  "             and means the same), --equal-bands: bands of equal height\n"
@@ -79,6 +79,9 @@ static void usage() {
                  "  --upsample: also render the first-hit buffers, rebuild the full-resolution frame from the blocks' anchor\n"
                  "             pixels with the library's defaults (srt_upsample) and write the tone-mapped result to PATH as a PPM;\n"
                  "             with --denoise the upsampler works in place and the denoiser runs on its result (single device only)\n"
+                 "  --aa:      anti-alias the silhouettes: trace the first hit at K x K sub-pixel positions (K in 1..4,\n"
+                 "             srt_render_subsamples) and write every PPM (--out, --upsample, --denoise, with or without --temporal) as\n"
+                 "             the resolve of its stage (srt_antialias); with --upsample the upsampler works in place (single device only)\n"
                  "  --temporal: render FRAMES frames of --spp samples each while the camera moves, keeping samples across\n"
                  "             frames (srt_temporal_accumulate), and write the last one to --out (--denoise PATH: also its\n"
                  "             denoised form); before every frame but the first the camera moves by R, U, F along its right,\n"
@@ -89,7 +92,8 @@ static void usage() {
 
 int main(int argc, char** argv) {
     std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise, upsample;
-    int temporal = 0, steps = 1;
+    int temporal = 0, steps = 1, aa = 0;
+    bool aa_given = false;
     float move[3] = {0, 0, 0}, turn_deg = 0;
     struct ObjectMove {
         size_t index;
@@ -131,6 +135,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--denoise")) denoise = need("--denoise");
         else if (!std::strcmp(argv[i], "--steps")) steps = std::atoi(need("--steps"));
         else if (!std::strcmp(argv[i], "--upsample")) upsample = need("--upsample");
+        else if (!std::strcmp(argv[i], "--aa")) aa = std::atoi(need("--aa")), aa_given = true;
         else if (!std::strcmp(argv[i], "--temporal")) temporal = std::atoi(need("--temporal"));
         else if (!std::strcmp(argv[i], "--turn")) turn_deg = std::strtof(need("--turn"), nullptr);
         else if (!std::strcmp(argv[i], "--move")) {
@@ -181,6 +186,10 @@ int main(int argc, char** argv) {
     }
     if ((steps > 1 || !upsample.empty()) && (!devices.empty() || temporal)) {
         std::fprintf(stderr, "--steps and --upsample work on one device only and not with --temporal\n");
+        return 2;
+    }
+    if (aa_given && (aa < 1 || aa > 4 || !devices.empty())) {
+        std::fprintf(stderr, "--aa takes K in 1..4 and works on one device only\n");
         return 2;
     }
     if (temporal && !devices.empty()) {
@@ -247,7 +256,12 @@ int main(int argc, char** argv) {
         r.MAXBOUNCES = bounces;
         r.seed = seed;
         r.SetScene(scene);
+        // --aa: the stage's result resolved into the framebuffer before it is read (the sub-samples are traced once per camera)
+        auto resolve = [&](int source) {
+            if (aa) r.Antialias(aa, source, SRT_AA_FRAMEBUFFER);
+        };
         if (temporal) {
+            r.antialias = aa;  // every temporal frame ends in the resolve
             // a moving camera that keeps its samples: every frame renders spp samples, reprojects the history and writes the
             // framebuffer; each frame's camera is printed exactly (%.9g round-trips a float) so that callers can replay it
             std::vector<uint32_t> fb((size_t)W * H);
@@ -289,6 +303,7 @@ int main(int argc, char** argv) {
                 dp.flags |= SRT_DENOISE_FRAMEBUFFER;
                 r.RenderGBuffer(SRT_GBUF_ALL);
                 r.Denoise(dp);
+                resolve(SRT_AA_SOURCE_DENOISED);
                 r.ReadFramebuffer(fb.data(), (size_t)W * 4);
                 if (write_ppm(fb, denoise)) return 1;
             }
@@ -303,19 +318,22 @@ int main(int argc, char** argv) {
                      bounces, st.kernel_ms, wall * 1e3, (double)st.path_samples / (st.kernel_ms * 1e-3),
                      (double)st.rays / (double)st.path_samples);
         std::vector<uint32_t> fb((size_t)W * H);
+        resolve(SRT_AA_SOURCE_ACCUMULATOR);
         r.ReadFramebuffer(fb.data(), (size_t)W * 4);
         if (write_ppm(fb, out)) return 1;
         if (!gbuffer.empty() && write_gbuffers(r, gbuffer, W, H)) return 1;
         if (!upsample.empty()) {
             // the guides of the whole frame, then the blocks' anchors interpolated with the library's defaults; the kernel
             // tone-maps its result into the framebuffer (--out is already written).  With --denoise the result replaces the
-            // accumulator's non-anchor pixels, which is what the denoiser below then filters.
+            // accumulator's non-anchor pixels, which is what the denoiser below then filters — and with --aa too, whose resolve
+            // reads the accumulator.
             srt_upsample_params up{};
             srt_upsample_params_default(&up);
             up.steps = steps;
-            up.flags = SRT_UPSAMPLE_FRAMEBUFFER | (denoise.empty() ? 0u : SRT_UPSAMPLE_IN_PLACE);
+            up.flags = SRT_UPSAMPLE_FRAMEBUFFER | (denoise.empty() && !aa ? 0u : SRT_UPSAMPLE_IN_PLACE);
             r.RenderGBuffer(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION);
             r.Upsample(up);
+            resolve(SRT_AA_SOURCE_ACCUMULATOR);
             r.ReadFramebuffer(fb.data(), (size_t)W * 4);
             if (write_ppm(fb, upsample)) return 1;
         }
@@ -327,6 +345,7 @@ int main(int argc, char** argv) {
             dp.flags |= SRT_DENOISE_FRAMEBUFFER;
             r.RenderGBuffer(SRT_GBUF_ALL);
             r.Denoise(dp);
+            resolve(SRT_AA_SOURCE_DENOISED);
             r.ReadFramebuffer(fb.data(), (size_t)W * 4);
             if (write_ppm(fb, denoise)) return 1;
         }

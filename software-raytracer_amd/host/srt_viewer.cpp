@@ -35,6 +35,9 @@
 //   R  guided upsampling (not in the reference; PathTraceRenderer::guidedUpsample): every frame of progressive-resolution
 //      blocks is shown reconstructed from the blocks' anchor pixels (srt_upsample) instead of as squares; the accumulation
 //      is untouched, so the toggle raises nothing
+//   C  anti-aliasing (not in the reference; PathTraceRenderer::antialias): every frame ends in the geometry-supersampled
+//      resolve of its silhouettes (srt_antialias) with 2 x 2 sub-samples per pixel, traced once per scene or camera change;
+//      the accumulation is untouched, so the toggle raises nothing
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -62,7 +65,7 @@ struct InputState {  // one frame's worth, what SDLInputManager hands the loop
     int mouse_dx = 0, mouse_dy = 0;  // relative motion of this frame
     bool left_down = false;          // edge
     int mouse_x = 0, mouse_y = 0;    // window coordinates of the click, y down
-    std::string pressed;             // key-down edges of this frame: any of "PMFGBN1234XTR" (X = DELETE)
+    std::string pressed;             // key-down edges of this frame: any of "PMFGBN1234XTRC" (X = DELETE)
 };
 
 class ViewerCore {
@@ -128,6 +131,7 @@ class ViewerCore {
             case 'P': pause_ = !pause_; break;                                     // :386-388
             case 'T': temporal_ = !temporal_; r_.Invalidate(); break;
             case 'R': r_.guidedUpsample = !r_.guidedUpsample; break;
+            case 'C': r_.antialias = r_.antialias ? 0 : 2; break;
             case 'M': r_.SIMPLEDRAW = !r_.SIMPLEDRAW; r_.Invalidate(); break;      // :462-465
             case 'F': case 'G': {                                                  // :468-473
                 int f = r_.FOV + (k == 'G' ? 1 : -1);
@@ -174,8 +178,9 @@ void write_ppm(PathTraceRenderer& r, const std::string& path) {
 // Script of the headless back end, one command per line ('#' starts a comment):
 //   delta SECONDS | hold KEYS | release KEYS   (KEYS out of W A S D E Q and L for LSHIFT; the object-move keys in lower case,
 //     i k j l u o, because the upper-case L is taken)
-//   press KEYS (P M F G B N 1 2 3 4 X T R, applied to the next frame only)
+//   press KEYS (P M F G B N 1 2 3 4 X T R C, applied to the next frame only)
 //   upsample on|off (guided upsampling of block frames, what the R key toggles)
+//   antialias K|off (anti-aliasing with K x K sub-samples, K in 1..4; the C key toggles K = 2)
 //   rmb down|up | move DX DY (relative mouse motion of the next frame) | click X Y
 //   frames N | save FILE.ppm | print | camera (position, right, up, forward and temporal mode, exactly: %.9g)
 //   select INDEX (selectedObject by list index, -1 = none; what a click's pick would set) | object (the selected object's
@@ -208,6 +213,13 @@ int run_script(ViewerCore& core, std::istream& script) {
         else if (cmd == "hold" || cmd == "release") { std::string k; ss >> k; set_keys(k, cmd == "hold"); }
         else if (cmd == "press") { std::string k; ss >> k; in.pressed += k; }
         else if (cmd == "upsample") { std::string v; ss >> v; core.renderer().guidedUpsample = v == "on"; }
+        else if (cmd == "antialias") {
+            std::string v;
+            ss >> v;
+            const int k = v == "off" ? 0 : std::atoi(v.c_str());
+            if (k < 0 || k > 4 || (k == 0 && v != "off")) { std::fprintf(stderr, "script: antialias %s: want 1..4 or off\n", v.c_str()); return 2; }
+            core.renderer().antialias = k;
+        }
         else if (cmd == "rmb") { std::string v; ss >> v; in.right_held = v == "down"; }
         else if (cmd == "move") ss >> in.mouse_dx >> in.mouse_dy;
         else if (cmd == "click") { ss >> in.mouse_x >> in.mouse_y; in.left_down = true; one_frame(); }
@@ -277,7 +289,7 @@ int run_window(ViewerCore& core) {
                     case SDL_SCANCODE_B: in.pressed += 'B'; break; case SDL_SCANCODE_N: in.pressed += 'N'; break;
                     case SDL_SCANCODE_1: in.pressed += '1'; break; case SDL_SCANCODE_2: in.pressed += '2'; break;
                     case SDL_SCANCODE_3: in.pressed += '3'; break; case SDL_SCANCODE_4: in.pressed += '4'; break;
-                    case SDL_SCANCODE_DELETE: in.pressed += 'X'; break; case SDL_SCANCODE_T: in.pressed += 'T'; break; case SDL_SCANCODE_R: in.pressed += 'R'; break; case SDL_SCANCODE_ESCAPE: quit = true; break;
+                    case SDL_SCANCODE_DELETE: in.pressed += 'X'; break; case SDL_SCANCODE_T: in.pressed += 'T'; break; case SDL_SCANCODE_R: in.pressed += 'R'; break; case SDL_SCANCODE_C: in.pressed += 'C'; break; case SDL_SCANCODE_ESCAPE: quit = true; break;
                     default: break;
                 }
             }
