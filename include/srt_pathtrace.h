@@ -586,6 +586,97 @@ int srt_bind_antialiased(srt_context* ctx, void* d_float4);
 /* Wait, then copy the W*H float4 result (scene rows) to host memory.  SRT_ERR_STATE before the first srt_antialias. */
 int srt_read_antialiased(srt_context* ctx, float* dst_rgba);
 
+/* ---- variance estimate and variance-guided denoiser (ABI 7, backward compatible) -------------------------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  srt_render, srt_denoise and
+ * srt_temporal_accumulate run what they ran before, bit for bit.
+ *
+ * srt_denoise has one global sigma_color: it cannot know which pixels are still noisy.  The remedy is the spatial stage of SVGF
+ * (Schied et al. 2017, §4.2–4.4): a per-pixel variance scales the colour edge-stop and is filtered along with the colour.  The
+ * variance comes from two independently seeded half renders A and B of the same frame (the dual-buffer estimate of Rousselle
+ * et al. 2012).  srt_bind_output lets a render accumulate into any device float4 buffer, so both halves come from srt_render:
+ *     srt_render(RESET, seed s, n samples)                                  -> half A, in the accumulator
+ *     srt_device_half(ctx, &half); srt_bind_output(ctx, NULL, half);
+ *     srt_render(RESET, another seed, n samples); srt_bind_output(ctx, NULL, NULL)   -> half B, in the half buffer
+ *     srt_render_gbuffer; srt_variance(SRT_VARIANCE_MERGE | ...); srt_denoise_variance
+ * All buffers are W*H in the accumulator's layout (x + y*W, scene rows).
+ *
+ * The second half buffer.  srt_device_half allocates the handle's own W*H float4 buffer on first use and returns it.
+ * srt_bind_half makes the passes read the caller's DEVICE buffer instead; NULL = the handle's own.  It does not wait, like the
+ * other bind calls.
+ *
+ * srt_variance.  Inputs: half A = the accumulator (bound or own) as it stands; half B = the half buffer (bound, or own once
+ * srt_device_half has fetched it); o = SRT_GBUF_OBJECT and, with SRT_VARIANCE_ALBEDO, a = SRT_GBUF_ALBEDO, bound or own.  The
+ * call renders no guide.  lum(c) = (0.2126f*r + 0.7152f*g) + 0.0722f*b in binary32, in this order, without FMA.
+ *   1. miss pixels (o_p == -1): v_p = 0.
+ *   2. m_p as srt_denoise rule 2 under SRT_VARIANCE_ALBEDO (per channel a_p >= 1e-3 ? a_p : 1), else 1.
+ *   3. lA = lum(A_p / m_p), lB = lum(B_p / m_p)  (per channel; no division without the flag).
+ *   4. d = 0.5f*lA - 0.5f*lB and v_p = d*d: the variance of the mean of the two halves.  Equal halves give +0, and swapping the
+ *      halves gives the same bits.
+ *   5. SRT_VARIANCE_MERGE also writes the mean 0.5f*A_p + 0.5f*B_p per rgb channel into the accumulator, in place, for every
+ *      pixel, misses included.  The alpha is never written; each pixel reads and writes only itself.  The accumulator then
+ *      holds an estimate that no render can continue: the next srt_render must use SRT_RENDER_RESET, as after
+ *      srt_temporal_accumulate.  Without the flag the accumulator is not written.
+ *   6. output: W*H float into the handle's own "variance" buffer (allocated on first use) or a bound one.  The context remembers
+ *      whether the last srt_variance into its own buffer used SRT_VARIANCE_ALBEDO.
+ *   7. whole frame, one launch, no atomics; asynchronous on the launch stream behind earlier work (srt_wait / srt_poll cover
+ *      it).  Leaves srt_get_stats, srt_get_work_counts, the launch shape of later renders, the G-buffer, the temporal history
+ *      and the denoised buffer as they are. */
+#define SRT_VARIANCE_ALBEDO 1u  /* the variance of the demodulated luminance: what srt_denoise_variance with SRT_DENOISE_ALBEDO filters */
+#define SRT_VARIANCE_MERGE 2u   /* also write the mean of the halves into the accumulator's rgb */
+
+typedef struct srt_variance_params {
+    uint32_t flags;  /* SRT_VARIANCE_* */
+} srt_variance_params;
+
+/* The library's defaults: SRT_VARIANCE_ALBEDO | SRT_VARIANCE_MERGE (pure host, no device needed). */
+int srt_variance_params_default(srt_variance_params* out);
+int srt_device_half(srt_context* ctx, void** d_ptr);
+int srt_bind_half(srt_context* ctx, void* d_float4);
+/* SRT_ERR_INVALID_ARG for unknown flags; SRT_ERR_STATE when OBJECT (or ALBEDO with SRT_VARIANCE_ALBEDO) has never been bound or
+ * rendered, and when the half buffer has neither been bound nor fetched with srt_device_half. */
+int srt_variance(srt_context* ctx, const srt_variance_params* params);
+/* Write the variance into a caller DEVICE buffer of W*H float instead of the handle's own; NULL = own.  Does not wait. */
+int srt_bind_variance(srt_context* ctx, void* d_float);
+/* Wait, then copy the W*H float variance (scene rows) to host memory.  SRT_ERR_STATE before the first srt_variance. */
+int srt_read_variance(srt_context* ctx, float* dst);
+
+/* srt_denoise_variance is srt_denoise with two changes.  Inputs: srt_denoise's (the accumulator and the four guides) and the
+ * variance v, the current "variance" buffer, bound or own.  The working variance of level 0 is v; like the working colour it
+ * is defined on hit pixels only.
+ *   A. a luminance term in place of the colour term:
+ *        w_l(p,q) = exp(-|lum(c_p) - lum(c_q)| / (sigma_luminance * sqrt(g_p) + 1e-10f))     (sigma_luminance = 0: term off)
+ *      on this level's working colour, where g_p is the 3 x 3 prefiltered working variance of this level: taps p + (dx, dy),
+ *      dx, dy in -1..1, at spacing 1 at every level, kernel [1,2,1] x [1,2,1] / 16; only taps inside the frame with o_q == o_p
+ *      count and the centre always counts; g_p = sum k v_q / sum k over the counted taps, in the order dy outer, dx inner.
+ *      As for srt_denoise's terms the reciprocal scale stops at FLT_MAX and an exact tie keeps its weight 1.  Every
+ *      sigma_luminance >= 0 is accepted; one above FLT_MAX (+inf) counts as FLT_MAX, so that a zero variance closes the stop at
+ *      every sigma (FLT_MAX * 0 = 0) and any other variance opens it (a scale of 0: weight 1 for every finite difference).
+ *   B. the variance is filtered with the colour: v_out_p = sum w(p,q)^2 v_q / (sum w(p,q))^2 over the same taps and weights,
+ *      ping-ponged per level next to the colour.  The last level's variance is not kept.
+ * Everything else is srt_denoise rules 1-5 to the letter: the taps, h, the step 2^i, the skipping of taps outside the frame,
+ * the object test before any other value of a tap is used, the normal and plane terms and their clamping, demodulation, the
+ * pass-through of miss pixels, the alpha and the tap order; the kernel calls the same device functions.  So with
+ * sigma_luminance = 0 the colour result equals srt_denoise's with sigma_color = 0 and otherwise equal parameters bit for bit,
+ * and a pixel of object A depends on colours and variances of object A only.
+ * Output: the colour goes to the current "denoised" buffer (bound or own), so srt_read_denoised, srt_bind_denoised and
+ * srt_antialias with SRT_AA_SOURCE_DENOISED work on it unchanged.  The variance buffer itself is never written.  Flags are
+ * SRT_DENOISE_ALBEDO and SRT_DENOISE_FRAMEBUFFER.  Asynchronous as srt_denoise; it leaves alone what srt_denoise leaves alone. */
+typedef struct srt_denoise_variance_params {
+    int32_t iterations;     /* à-trous levels L, 1..8 */
+    float sigma_luminance;  /* sigma_l, >= 0 */
+    float sigma_normal;     /* sigma_n, >= 0 */
+    float sigma_plane;      /* sigma_x, >= 0 */
+    uint32_t flags;         /* SRT_DENOISE_ALBEDO | SRT_DENOISE_FRAMEBUFFER */
+} srt_denoise_variance_params;
+
+/* The library's defaults: srt_denoise's for iterations, sigma_normal, sigma_plane and flags, sigma_luminance = 4 (SVGF's). */
+int srt_denoise_variance_params_default(srt_denoise_variance_params* out);
+/* SRT_ERR_INVALID_ARG for iterations outside 1..8, a negative or NaN sigma or unknown flags; SRT_ERR_STATE when a guide it needs
+ * (OBJECT, NORMAL_DEPTH, POSITION, plus ALBEDO with SRT_DENOISE_ALBEDO) has never been bound or rendered, when no variance buffer
+ * has been bound or written, and when the variance buffer is the handle's own and the srt_variance that wrote it disagrees
+ * with this call on the ALBEDO flag (a bound buffer is the caller's responsibility). */
+int srt_denoise_variance(srt_context* ctx, const srt_denoise_variance_params* params);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

@@ -24,6 +24,7 @@ from .capi import (  # noqa: F401
     AntialiasParams,
     Camera,
     DenoiseParams,
+    DenoiseVarianceParams,
     Environment,
     GBufferParams,
     Material,
@@ -36,6 +37,7 @@ from .capi import (  # noqa: F401
     SubsampleParams,
     TemporalParams,
     UpsampleParams,
+    VarianceParams,
     build_native,
     default_camera,
     default_environment,
@@ -46,6 +48,6 @@ from . import host  # noqa: F401
 
 __all__ = [
     "capi", "host", "PathTracer", "SrtError", "Object", "Material", "Camera", "Environment",
-    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "SubsampleParams", "AntialiasParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
+    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "SubsampleParams", "AntialiasParams", "VarianceParams", "DenoiseVarianceParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
     "load_library",
 ]

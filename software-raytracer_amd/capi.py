@@ -31,6 +31,7 @@ UPSAMPLE_IN_PLACE, UPSAMPLE_FRAMEBUFFER = 1, 2
 UPSAMPLE_GUIDES = GBUF_OBJECT | GBUF_NORMAL_DEPTH | GBUF_POSITION
 AA_FRAMEBUFFER = 2
 AA_SOURCE_ACCUMULATOR, AA_SOURCE_DENOISED = 0, 1
+VARIANCE_ALBEDO, VARIANCE_MERGE = 1, 2
 ABI_VERSION = 7
 
 # every symbol include/srt_pathtrace.h declares (tests check the library exports them all)
@@ -47,6 +48,8 @@ EXPORTS = [
     "srt_upsample_params_default", "srt_upsample", "srt_bind_upsampled", "srt_read_upsampled",
     "srt_render_subsamples", "srt_bind_subsamples", "srt_read_subsamples",
     "srt_antialias_params_default", "srt_antialias", "srt_bind_antialiased", "srt_read_antialiased",
+    "srt_variance_params_default", "srt_device_half", "srt_bind_half", "srt_variance", "srt_bind_variance", "srt_read_variance",
+    "srt_denoise_variance_params_default", "srt_denoise_variance",
 ]
 
 
@@ -146,6 +149,15 @@ class SubsampleParams(C.Structure):
 
 class AntialiasParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("source", C.c_int32), ("flags", C.c_uint32)]
+
+
+class VarianceParams(C.Structure):
+    _fields_ = [("flags", C.c_uint32)]
+
+
+class DenoiseVarianceParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("flags", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -268,6 +280,14 @@ def open_library(path):
     L.srt_antialias.argtypes = [ctx, C.POINTER(AntialiasParams)]
     L.srt_bind_antialiased.argtypes = [ctx, C.c_void_p]
     L.srt_read_antialiased.argtypes = [ctx, C.POINTER(C.c_float)]
+    L.srt_variance_params_default.argtypes = [C.POINTER(VarianceParams)]
+    L.srt_device_half.argtypes = [ctx, C.POINTER(C.c_void_p)]
+    L.srt_bind_half.argtypes = [ctx, C.c_void_p]
+    L.srt_variance.argtypes = [ctx, C.POINTER(VarianceParams)]
+    L.srt_bind_variance.argtypes = [ctx, C.c_void_p]
+    L.srt_read_variance.argtypes = [ctx, C.POINTER(C.c_float)]
+    L.srt_denoise_variance_params_default.argtypes = [C.POINTER(DenoiseVarianceParams)]
+    L.srt_denoise_variance.argtypes = [ctx, C.POINTER(DenoiseVarianceParams)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -331,6 +351,24 @@ def antialias_defaults(lib=None):
     return {n: getattr(p, n) for n, _ in AntialiasParams._fields_}
 
 
+def variance_defaults(lib=None):
+    """srt_variance_params_default as a dict (pure host: no GPU needed)."""
+    p = VarianceParams()
+    rc = (lib if lib is not None else load_library()).srt_variance_params_default(C.byref(p))
+    if rc:
+        raise SrtError(rc, "srt_variance_params_default")
+    return {n: getattr(p, n) for n, _ in VarianceParams._fields_}
+
+
+def denoise_variance_defaults(lib=None):
+    """srt_denoise_variance_params_default as a dict (pure host: no GPU needed)."""
+    p = DenoiseVarianceParams()
+    rc = (lib if lib is not None else load_library()).srt_denoise_variance_params_default(C.byref(p))
+    if rc:
+        raise SrtError(rc, "srt_denoise_variance_params_default")
+    return {n: getattr(p, n) for n, _ in DenoiseVarianceParams._fields_}
+
+
 def __getattr__(name):
     # DENOISE_DEFAULTS / TEMPORAL_DEFAULTS / UPSAMPLE_DEFAULTS: the library's defaults (denoise_defaults(), temporal_defaults(),
     # upsample_defaults()), read when first asked for, so that importing this module does not need the built library
@@ -342,6 +380,10 @@ def __getattr__(name):
         return upsample_defaults()
     if name == "ANTIALIAS_DEFAULTS":
         return antialias_defaults()
+    if name == "VARIANCE_DEFAULTS":
+        return variance_defaults()
+    if name == "DENOISE_VARIANCE_DEFAULTS":
+        return denoise_variance_defaults()
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -379,6 +421,26 @@ def antialias_params(k=None, denoised=False, framebuffer=False, lib=None):
     d = antialias_defaults(lib)
     return AntialiasParams(int(d["k"] if k is None else k), AA_SOURCE_DENOISED if denoised else AA_SOURCE_ACCUMULATOR,
                            AA_FRAMEBUFFER if framebuffer else 0)
+
+
+def variance_params(albedo=None, merge=None, lib=None):
+    """A VarianceParams: the library's default flags, each overridden by name when given."""
+    flags = variance_defaults(lib)["flags"]
+    for bit, on in ((VARIANCE_ALBEDO, albedo), (VARIANCE_MERGE, merge)):
+        if on is not None:
+            flags = (flags | bit) if on else (flags & ~bit)
+    return VarianceParams(flags)
+
+
+def denoise_variance_params(iterations=None, sigma_luminance=None, sigma_normal=None, sigma_plane=None, albedo=True,
+                            framebuffer=False, lib=None):
+    """A DenoiseVarianceParams: the library's defaults with the given fields replaced and the flags by name."""
+    d = denoise_variance_defaults(lib)
+    flags = (DENOISE_ALBEDO if albedo else 0) | (DENOISE_FRAMEBUFFER if framebuffer else 0)
+    return DenoiseVarianceParams(int(d["iterations"] if iterations is None else iterations),
+                                 float(d["sigma_luminance"] if sigma_luminance is None else sigma_luminance),
+                                 float(d["sigma_normal"] if sigma_normal is None else sigma_normal),
+                                 float(d["sigma_plane"] if sigma_plane is None else sigma_plane), flags)
 
 
 def _f3(v):
@@ -657,6 +719,49 @@ class PathTracer:
         (None: the handle's own buffer).  Checked here, before any native call, as bind_denoised checks."""
         ptr = self._float4_tensor_ptr("bind_antialiased", tensor)
         self._ck(self.L.srt_bind_antialiased(self._h, ptr))
+
+    def half_ptr(self):
+        """srt_device_half: the device address of the handle's own second-half buffer (allocated on first use), W*H float4.
+        Render into it with bind_output(None, half_ptr()), render(...), bind_output()."""
+        p = C.c_void_p()
+        self._ck(self.L.srt_device_half(self._h, C.byref(p)))
+        return p.value
+
+    def bind_half(self, tensor):
+        """srt_bind_half: take half B from a torch tensor on this tracer's device, (H, W, 4) float32 and contiguous (None: the
+        handle's own buffer).  Checked here, before any native call, as bind_denoised checks."""
+        self._ck(self.L.srt_bind_half(self._h, self._float4_tensor_ptr("bind_half", tensor)))
+
+    def variance(self, albedo=None, merge=None, gbuffer=True):
+        """srt_variance over the whole frame: the squared half-difference of the luminances of the accumulator and the half
+        buffer; merge=True also leaves the mean of the halves in the accumulator.  Arguments left at None take
+        VARIANCE_DEFAULTS.  gbuffer=True first enqueues render_gbuffer() for the guides the pass reads; gbuffer=False uses the
+        guides as they are.  Asynchronous."""
+        p = variance_params(albedo, merge, lib=self.L)
+        if gbuffer:
+            self.render_gbuffer(outputs=GBUF_OBJECT | (GBUF_ALBEDO if p.flags & VARIANCE_ALBEDO else 0))
+        self._ck(self.L.srt_variance(self._h, C.byref(p)))
+
+    def variance_map(self):
+        """srt_read_variance: the variance, (H, W) float32, rows = scene rows (the orientation of accumulator())."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self._ck(self.L.srt_read_variance(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def bind_variance(self, tensor):
+        """srt_bind_variance: keep the variance in a torch tensor on this tracer's device, (H, W) float32 and contiguous (None:
+        the handle's own buffer).  Checked here, before any native call, as bind_denoised checks."""
+        self._ck(self.L.srt_bind_variance(self._h, self._tensor_ptr("bind_variance", tensor, np.float32, (self.height, self.width))))
+
+    def denoise_variance(self, iterations=None, sigma_luminance=None, sigma_normal=None, sigma_plane=None, albedo=True,
+                         framebuffer=False, gbuffer=True):
+        """srt_denoise_variance over the whole frame: denoise() with the variance-scaled luminance edge-stop, on the accumulator
+        and the variance buffer as they stand; the result is what denoised() reads.  Arguments left at None take
+        DENOISE_VARIANCE_DEFAULTS.  gbuffer as in denoise().  Asynchronous."""
+        p = denoise_variance_params(iterations, sigma_luminance, sigma_normal, sigma_plane, albedo, framebuffer, lib=self.L)
+        if gbuffer:
+            self.render_gbuffer(outputs=DENOISE_GUIDES | (GBUF_ALBEDO if albedo else 0))
+        self._ck(self.L.srt_denoise_variance(self._h, C.byref(p)))
 
     def wait(self):
         self._ck(self.L.srt_wait(self._h))

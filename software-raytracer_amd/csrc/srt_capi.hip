@@ -22,6 +22,7 @@
 #include "srt_temporal.hip.h"
 #include "srt_upsample.hip.h"
 #include "srt_antialias.hip.h"
+#include "srt_variance.hip.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -297,6 +298,19 @@ struct srt_context {
     DeviceBuffer<float4> d_aa_own;
     float4* d_aa_bound = nullptr;
     bool aa_written = false;
+
+    // variance estimate and variance-guided denoiser (srt_variance, srt_denoise_variance).  The second half render: the
+    // handle's own buffer (allocated by the first srt_device_half) and the caller's bound one (srt_bind_half; NULL = own).  The
+    // variance: the handle's own buffer (allocated on first use), the caller's bound one (srt_bind_variance; NULL = own), whether
+    // a call has been enqueued yet (srt_read_variance), whether one has written the OWN buffer and whether that one used
+    // SRT_VARIANCE_ALBEDO (srt_denoise_variance refuses an own buffer of the other kind).
+    DeviceBuffer<float4> d_half_own;
+    float4* d_half_bound = nullptr;
+    DeviceBuffer<float> d_var_own;
+    float* d_var_bound = nullptr;
+    bool var_written = false;
+    bool var_own_written = false;
+    bool var_own_albedo = false;
 
     char error[512] = "";
 };
@@ -1754,6 +1768,148 @@ int srt_read_antialiased(srt_context* ctx, float* dst_rgba) {
     if (!ctx->aa_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_read_antialiased: nothing has been anti-aliased into this buffer yet");
     if (const int rc = finish_stream(ctx)) return rc;
     SRT_HIP(ctx, hipMemcpy(dst_rgba, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+// ---- variance estimate and variance-guided denoiser -----------------------------------------------------------------------
+int srt_variance_params_default(srt_variance_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    // what srt_denoise_variance's defaults expect: the demodulated variance, and the mean of the halves to filter
+    out->flags = SRT_VARIANCE_ALBEDO | SRT_VARIANCE_MERGE;
+    return SRT_OK;
+}
+
+int srt_device_half(srt_context* ctx, void** d_ptr) {
+    if (!ctx || !d_ptr) return SRT_ERR_INVALID_ARG;
+    if (!(float4*)ctx->d_half_own) {
+        SRT_HIP(ctx, hipSetDevice(ctx->device));
+        const size_t bytes = (size_t)ctx->width * (size_t)ctx->height * sizeof(float4);
+        SRT_HIP(ctx, ctx->d_half_own.ensure(bytes));
+        SRT_HIP(ctx, hipMemsetAsync(ctx->d_half_own, 0, bytes, ctx->stream));  // as the accumulator starts
+    }
+    *d_ptr = (float4*)ctx->d_half_own;
+    return SRT_OK;
+}
+
+int srt_bind_half(srt_context* ctx, void* d_float4) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    ctx->d_half_bound = (float4*)d_float4;  // (no synchronisation: an enqueued call keeps the buffer it was given)
+    return SRT_OK;
+}
+
+int srt_variance(srt_context* ctx, const srt_variance_params* v) {
+    if (!ctx || !v) return SRT_ERR_INVALID_ARG;
+    if (v->flags & ~(SRT_VARIANCE_ALBEDO | SRT_VARIANCE_MERGE)) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_variance: unknown flags 0x%x", v->flags);
+    const bool demod = (v->flags & SRT_VARIANCE_ALBEDO) != 0;
+    // OBJECT, and ALBEDO when demodulating (find_guides takes the slots in order: the two between are not needed here)
+    const void* guide[4] = {};
+    if (const int rc = find_guides(ctx, "srt_variance", 1, nullptr, guide)) return rc;
+    if (demod) {
+        guide[3] = bound_or_own(ctx->d_gbuf_bound[3], ctx->d_gbuf_own[3]);
+        if (!guide[3]) return fail(ctx, SRT_ERR_STATE, "srt_variance: the ALBEDO guide has neither been bound nor rendered (srt_render_gbuffer)");
+    }
+    const float4* half = bound_or_own(ctx->d_half_bound, ctx->d_half_own);
+    if (!half) return fail(ctx, SRT_ERR_STATE, "srt_variance: the half buffer has neither been bound (srt_bind_half) nor fetched (srt_device_half)");
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)ctx->width * (size_t)ctx->height;
+    if (!ctx->d_var_bound) SRT_HIP(ctx, ctx->d_var_own.ensure(px * sizeof(float)));
+    srt::VarianceLaunch V{};
+    V.acc = ctx->d_acc;
+    V.half = half;
+    V.object = (const int32_t*)guide[0];
+    V.albedo = demod ? (const float4*)guide[3] : nullptr;
+    V.variance = bound_or_own(ctx->d_var_bound, ctx->d_var_own);
+    V.pixels = px;
+    V.merge = (v->flags & SRT_VARIANCE_MERGE) ? 1 : 0;
+    const unsigned blocks = (unsigned)((px + srt::VARIANCE_THREADS - 1) / srt::VARIANCE_THREADS);
+    hipLaunchKernelGGL(srt::variance_kernel, dim3(blocks), dim3(srt::VARIANCE_THREADS), 0, ctx->stream, V);
+    SRT_HIP(ctx, hipGetLastError());
+    ctx->var_written = true;
+    if (!ctx->d_var_bound) ctx->var_own_written = true, ctx->var_own_albedo = demod;
+    return SRT_OK;
+}
+
+int srt_bind_variance(srt_context* ctx, void* d_float) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    ctx->d_var_bound = (float*)d_float;  // (no synchronisation: an enqueued call keeps the buffer it was given)
+    return SRT_OK;
+}
+
+int srt_read_variance(srt_context* ctx, float* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const float* src = bound_or_own(ctx->d_var_bound, ctx->d_var_own);
+    if (!ctx->var_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_read_variance: no variance has been written into this buffer yet");
+    if (const int rc = finish_stream(ctx)) return rc;
+    SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * sizeof(float), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+int srt_denoise_variance_params_default(srt_denoise_variance_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt_denoise_params d{};
+    (void)srt_denoise_params_default(&d);
+    out->iterations = d.iterations;
+    out->sigma_luminance = 4.0f;  // SVGF's (Schied et al. 2017, §4.4)
+    out->sigma_normal = d.sigma_normal;
+    out->sigma_plane = d.sigma_plane;
+    out->flags = d.flags;
+    return SRT_OK;
+}
+
+int srt_denoise_variance(srt_context* ctx, const srt_denoise_variance_params* d) {
+    if (!ctx || !d) return SRT_ERR_INVALID_ARG;
+    if (d->iterations < 1 || d->iterations > 8)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_denoise_variance: iterations %d outside 1..8", d->iterations);
+    // (written so that a NaN fails too)
+    if (!(d->sigma_luminance >= 0.0f) || !(d->sigma_normal >= 0.0f) || !(d->sigma_plane >= 0.0f))
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_denoise_variance: sigmas must be >= 0 (luminance %g, normal %g, plane %g)",
+                    d->sigma_luminance, d->sigma_normal, d->sigma_plane);
+    if (d->flags & ~(SRT_DENOISE_ALBEDO | SRT_DENOISE_FRAMEBUFFER))
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_denoise_variance: unknown flags 0x%x", d->flags);
+    const bool demod = (d->flags & SRT_DENOISE_ALBEDO) != 0;
+    const void* guide[4] = {};
+    if (const int rc = find_guides(ctx, "srt_denoise_variance", demod ? 4 : 3, nullptr, guide)) return rc;
+    const float* const var = ctx->d_var_bound ? ctx->d_var_bound : ctx->var_own_written ? (float*)ctx->d_var_own : nullptr;
+    if (!var) return fail(ctx, SRT_ERR_STATE, "srt_denoise_variance: no variance buffer has been bound (srt_bind_variance) or written (srt_variance)");
+    if (!ctx->d_var_bound && ctx->var_own_albedo != demod)
+        return fail(ctx, SRT_ERR_STATE, "srt_denoise_variance: the variance was estimated %s SRT_VARIANCE_ALBEDO, this call is %s SRT_DENOISE_ALBEDO",
+                    ctx->var_own_albedo ? "with" : "without", demod ? "with" : "without");
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)ctx->width * (size_t)ctx->height;
+    if (!ctx->d_dn_bound) SRT_HIP(ctx, ctx->d_dn_own.ensure(px * sizeof(float4)));
+    SRT_HIP(ctx, ctx->d_dn_tmp.ensure(px * sizeof(float4)));
+    float4* const out = bound_or_own(ctx->d_dn_bound, ctx->d_dn_own);
+    srt::VarianceLevel L{};
+    L.acc = ctx->d_acc;
+    L.object = (const int32_t*)guide[0];
+    L.normal_depth = (const float4*)guide[1];
+    L.position = (const float4*)guide[2];
+    L.albedo = demod ? (const float4*)guide[3] : nullptr;
+    L.variance = var;
+    L.width = ctx->width, L.height = ctx->height;
+    L.sigma_normal = fminf(d->sigma_normal, FLT_MAX);  // as srt_denoise
+    L.sigma_plane = d->sigma_plane;
+    // +inf counts as FLT_MAX: FLT_MAX * sqrt(0) = 0 closes the stop on a zero variance, where inf * 0 would be NaN
+    L.sigma_luminance = fminf(d->sigma_luminance, FLT_MAX);
+    const bool lum = d->sigma_luminance > 0.0f;
+    const dim3 grid = frame_tile_grid(ctx), block(srt::WG_THREADS);
+    // the preparation pass and the levels alternate between the ping-pong buffer and the result buffer as srt_denoise's do
+    const int n = d->iterations;
+    L.dst = (n & 1) ? ctx->d_dn_tmp : out;
+    hipLaunchKernelGGL(srt::denoise_variance_prep_kernel, grid, block, 0, ctx->stream, L);
+    SRT_HIP(ctx, hipGetLastError());
+    for (int i = 0; i < n; ++i) {
+        const bool last = i == n - 1;
+        L.src = L.dst;
+        L.dst = ((n - 1 - i) & 1) ? ctx->d_dn_tmp : out;
+        L.step = 1 << i;
+        L.framebuffer = last && (d->flags & SRT_DENOISE_FRAMEBUFFER) ? ctx->d_fb : nullptr;
+        void (*const kernel)(srt::VarianceLevel) = last ? (lum ? srt::denoise_variance_kernel<true, true> : srt::denoise_variance_kernel<true, false>)
+                                                        : (lum ? srt::denoise_variance_kernel<false, true> : srt::denoise_variance_kernel<false, false>);
+        hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, L);
+        SRT_HIP(ctx, hipGetLastError());
+    }
+    ctx->dn_written = true;
     return SRT_OK;
 }
 

@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .capi import (DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, DenoiseParams, Mesh, Object, Stats,
+from .capi import (DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, DenoiseParams, Mesh, Object, Stats,
                    TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -29,6 +29,7 @@ EXPORTS = [
     "srt_host_renderer_update_scene", "srt_host_renderer_motion_output", "srt_host_renderer_read_motion",
     "srt_host_renderer_upsample", "srt_host_renderer_read_upsampled", "srt_host_renderer_guided_upsample",
     "srt_host_renderer_antialias", "srt_host_renderer_read_antialiased", "srt_host_renderer_set_antialias",
+    "srt_host_renderer_denoise_variance", "srt_host_renderer_read_variance",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -121,6 +122,8 @@ def load_library():
     L.srt_host_renderer_antialias.argtypes = [vp, C.POINTER(AntialiasParams)]
     L.srt_host_renderer_read_antialiased.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_set_antialias.argtypes = [vp, C.c_int]
+    L.srt_host_renderer_denoise_variance.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.srt_host_renderer_read_variance.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_multi_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]
     L.srt_host_multi_create.restype = vp
     L.srt_host_multi_destroy.argtypes = [vp]
@@ -413,6 +416,17 @@ class Renderer:
     def set_antialias(self, k):
         """PathTraceRenderer::antialias: render_frame() and render_temporal_frame() end in the resolve with this k (0: off)."""
         self._ck(self.L.srt_host_renderer_set_antialias(self._h, int(k)))
+
+    def denoise_variance(self, spp, framebuffer=False):
+        """PathTraceRenderer::denoiseVariance: two half renders of spp / 2 samples, the guides, srt_variance with MERGE and
+        srt_denoise_variance with the library's defaults; denoised() reads the result.  spp must be even and >= 2."""
+        self._ck(self.L.srt_host_renderer_denoise_variance(self._h, int(spp), DENOISE_FRAMEBUFFER if framebuffer else 0))
+
+    def variance_map(self):
+        """PathTraceRenderer::ReadVariance: (H, W) float32, scene rows, as capi.PathTracer.variance_map returns it."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_variance(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     def stats(self):
         s = Stats()

@@ -251,6 +251,9 @@ int srt_host_renderer_set_antialias(srt_host_renderer* h, int k) {
     h->r->antialias = k;
     return 0;
 }
+// one variance-guided denoised frame of spp samples in two halves (PathTraceRenderer::denoiseVariance), and its variance estimate
+int srt_host_renderer_denoise_variance(srt_host_renderer* h, uint32_t spp, uint32_t flags) { SRT_HOST_TRY(h, h->r->denoiseVariance(spp, flags)) }
+int srt_host_renderer_read_variance(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadVariance(dst)) }
 int srt_host_renderer_stats(srt_host_renderer* h, srt_stats* out) { SRT_HOST_TRY(h, *out = h->r->Stats()) }
 void* srt_host_renderer_handle(srt_host_renderer* h) { return h->r->handle(); }
 

@@ -284,6 +284,52 @@ void PathTraceRenderer::RenderTemporalFrame(uint32_t spp, bool denoise) {
     first_frame_ = false;
 }
 
+void PathTraceRenderer::denoiseVariance(uint32_t spp, uint32_t flags) {
+    if (spp < 2 || (spp & 1u))
+        throw RendererError(SRT_ERR_INVALID_ARG, "denoiseVariance: spp must be even and >= 2 (two half renders of spp / 2 samples each)");
+    if (row_begin_ != 0 || row_end_ != height_)
+        throw RendererError(SRT_ERR_STATE, "denoiseVariance: the renderer has a row band; the variance passes cover the whole frame");
+    push_camera();
+    srt_render_params p{};
+    p.row_begin = 0;
+    p.row_end = height_;
+    p.first_sample = 1;
+    p.sample_count = spp / 2;
+    p.max_bounces = MAXBOUNCES < 0 ? 0 : MAXBOUNCES;
+    p.seed = seed;
+    p.flags = SRT_RENDER_RESET;
+    p.steps = 1;
+    p.selected_object = -1;
+    check(srt_render(ctx_, &p), "srt_render");  // half A, into the accumulator
+    // half B: the same frame with another seed, accumulated into the half buffer; then the binding as it was
+    void *fb = nullptr, *acc = nullptr, *half = nullptr;
+    check(srt_device_framebuffer(ctx_, &fb), "srt_device_framebuffer");
+    check(srt_device_accumulator(ctx_, &acc), "srt_device_accumulator");
+    check(srt_device_half(ctx_, &half), "srt_device_half");
+    check(srt_bind_output(ctx_, fb, half), "srt_bind_output");
+    p.seed = seed ^ 0x9E3779B9u;
+    const int rc = srt_render(ctx_, &p);
+    check(srt_bind_output(ctx_, fb, acc), "srt_bind_output");
+    check(rc, "srt_render");
+    RenderGBuffer(SRT_GBUF_ALL);
+    srt_variance_params v{};
+    check(srt_variance_params_default(&v), "srt_variance_params_default");
+    v.flags |= SRT_VARIANCE_MERGE;
+    srt_denoise_variance_params d{};
+    check(srt_denoise_variance_params_default(&d), "srt_denoise_variance_params_default");
+    d.flags |= flags;
+    // the estimate and the filter agree on demodulation
+    v.flags = (d.flags & SRT_DENOISE_ALBEDO) ? (v.flags | SRT_VARIANCE_ALBEDO) : (v.flags & ~SRT_VARIANCE_ALBEDO);
+    check(srt_variance(ctx_, &v), "srt_variance");
+    check(srt_denoise_variance(ctx_, &d), "srt_denoise_variance");
+    // the accumulator now holds the mean of the halves, which no render can continue
+    doSetFrame_ = true;
+    clean_reset_ = true;
+    first_frame_ = false;
+}
+
+void PathTraceRenderer::ReadVariance(float* dst) { check(srt_read_variance(ctx_, dst), "srt_read_variance"); }
+
 std::vector<float> PathTraceRenderer::ReadAccumulator() {
     std::vector<float> out((size_t)width_ * height_ * 4);
     check(srt_read_accumulator(ctx_, out.data()), "srt_read_accumulator");

@@ -165,6 +165,14 @@ class PathTraceRenderer {
     // antialias > 0 Antialias on the denoised buffer (with `denoise`) or the accumulator.  The last step
     // writes the framebuffer.  Later RenderFrame / RenderSamples calls start a fresh accumulation.
     void RenderTemporalFrame(uint32_t spp, bool denoise);
+    // One variance-guided denoised frame (whole frame only): push the camera, render spp / 2 samples with SRT_RENDER_RESET and
+    // the frame's seed into the accumulator, spp / 2 with seed ^ 0x9E3779B9 into the handle's half buffer through
+    // srt_bind_output (the binding is restored), the four guides, srt_variance with SRT_VARIANCE_MERGE, then
+    // srt_denoise_variance with the library's defaults and `flags` (SRT_DENOISE_FRAMEBUFFER) added.  SRT_ERR_INVALID_ARG for an
+    // odd spp or one below 2.  ReadDenoised gives the result, ReadVariance the W x H float variance estimate.  Later
+    // RenderFrame / RenderSamples calls start a fresh accumulation.
+    void denoiseVariance(uint32_t spp, uint32_t flags = 0);
+    void ReadVariance(float* dst);
 
     void PushCamera() { push_camera(); }  // srt_set_camera with the members as they stand (used by MultiGpuRenderer)
 

@@ -66,6 +66,7 @@ static void usage() {
                  "                  [--fov 55] [--seed 0] [--device 0 | --devices 0,1,2,...] [--out frame.ppm] [--resave FILE]\n"
                  "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]\n"
                  "                  [--move-object IDX:DX,DY,DZ]...] [--steps N] [--upsample PATH] [--aa K]\n"
+                 "                  [--denoise-variance PATH]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
                  "             and means the same), --equal-bands: bands of equal height\n"
@@ -74,6 +75,10 @@ static void usage() {
                  "             (with --devices: made for the whole frame on the first device)\n"
                  "  --denoise: also render the first-hit buffers, denoise the accumulator with the library's defaults\n"
                  "             (srt_denoise) and write the tone-mapped result to PATH as a PPM (single device only)\n"
+                 "  --denoise-variance: render the frame again as two independently seeded halves of --spp / 2 samples each, estimate\n"
+                 "             the per-pixel variance from them (srt_variance) and write the tone-mapped result of the variance-guided\n"
+                 "             filter with the library's defaults (srt_denoise_variance) to PATH as a PPM; needs an even --spp >= 2;\n"
+                 "             not with --denoise, --temporal, --steps, --upsample or --devices\n"
                  "  --steps:   trace one ray per N x N block of pixels and copy its colour into the block (the progressive-resolution\n"
                  "             blocks of the reference's interactive frames); single device, not with --temporal\n"
                  "  --upsample: also render the first-hit buffers, rebuild the full-resolution frame from the blocks' anchor\n"
@@ -91,7 +96,7 @@ static void usage() {
 }
 
 int main(int argc, char** argv) {
-    std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise, upsample;
+    std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise, upsample, denoise_variance;
     int temporal = 0, steps = 1, aa = 0;
     bool aa_given = false;
     float move[3] = {0, 0, 0}, turn_deg = 0;
@@ -133,6 +138,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--resave")) resave = need("--resave");
         else if (!std::strcmp(argv[i], "--gbuffer")) gbuffer = need("--gbuffer");
         else if (!std::strcmp(argv[i], "--denoise")) denoise = need("--denoise");
+        else if (!std::strcmp(argv[i], "--denoise-variance")) denoise_variance = need("--denoise-variance");
         else if (!std::strcmp(argv[i], "--steps")) steps = std::atoi(need("--steps"));
         else if (!std::strcmp(argv[i], "--upsample")) upsample = need("--upsample");
         else if (!std::strcmp(argv[i], "--aa")) aa = std::atoi(need("--aa")), aa_given = true;
@@ -187,6 +193,20 @@ int main(int argc, char** argv) {
     if ((steps > 1 || !upsample.empty()) && (!devices.empty() || temporal)) {
         std::fprintf(stderr, "--steps and --upsample work on one device only and not with --temporal\n");
         return 2;
+    }
+    if (!denoise_variance.empty()) {
+        if (!denoise.empty()) {
+            std::fprintf(stderr, "--denoise-variance and --denoise exclude each other: both write the denoised buffer\n");
+            return 2;
+        }
+        if (spp < 2 || (spp & 1)) {
+            std::fprintf(stderr, "--denoise-variance needs an even --spp >= 2: it renders two halves of --spp / 2 samples\n");
+            return 2;
+        }
+        if (!devices.empty() || temporal || steps > 1 || !upsample.empty()) {
+            std::fprintf(stderr, "--denoise-variance works on one device only and not with --temporal, --steps or --upsample\n");
+            return 2;
+        }
     }
     if (aa_given && (aa < 1 || aa > 4 || !devices.empty())) {
         std::fprintf(stderr, "--aa takes K in 1..4 and works on one device only\n");
@@ -348,6 +368,15 @@ int main(int argc, char** argv) {
             resolve(SRT_AA_SOURCE_DENOISED);
             r.ReadFramebuffer(fb.data(), (size_t)W * 4);
             if (write_ppm(fb, denoise)) return 1;
+        }
+        if (!denoise_variance.empty()) {
+            // the frame again as two halves, their variance and mean, the guides and the variance-guided filter with the
+            // library's defaults (PathTraceRenderer::denoiseVariance); the kernel tone-maps its result into the framebuffer
+            // (--out is already written)
+            r.denoiseVariance((uint32_t)spp, SRT_DENOISE_FRAMEBUFFER);
+            resolve(SRT_AA_SOURCE_DENOISED);
+            r.ReadFramebuffer(fb.data(), (size_t)W * 4);
+            if (write_ppm(fb, denoise_variance)) return 1;
         }
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());
