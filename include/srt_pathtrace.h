@@ -316,6 +316,8 @@ int srt_read_gbuffer(srt_context* ctx, uint32_t output, void* dst);
  *      1 / (sigma_plane d_p), and the exponent sigma_normal, stop at FLT_MAX instead of reaching inf.  So a tiny sigma gives
  *      an exact tie the weight 1 and a difference whose square (colour) or size (plane) times FLT_MAX is large the weight
  *      0; only differences below about 1e-19 (colour) or 1e-37 (plane) then weigh more than the definition says.  A
+ *      sigma_plane above FLT_MAX (+inf) counts as FLT_MAX, so that the scale of a first hit at d_p = 0 is FLT_MAX like that
+ *      of any other vanishing sigma_plane * d_p (an exact tie weighs 1, every other tap 0) instead of 1 / (inf * 0).  A
  *      negative d_p (a first hit behind the camera) turns the plane term into exp(+...), which can overflow.
  *   4. output alpha = input alpha of p.
  *   5. fixed tap order (dy outer, dx inner), no atomics: repeated calls give the same bits. */
@@ -648,6 +650,8 @@ int srt_read_variance(srt_context* ctx, float* dst);
  *      on this level's working colour, where g_p is the 3 x 3 prefiltered working variance of this level: taps p + (dx, dy),
  *      dx, dy in -1..1, at spacing 1 at every level, kernel [1,2,1] x [1,2,1] / 16; only taps inside the frame with o_q == o_p
  *      count and the centre always counts; g_p = sum k v_q / sum k over the counted taps, in the order dy outer, dx inner.
+ *      The products k v_q are binary32 products: one at or below 2^-150, half the smallest subnormal, is 0, so a variance of
+ *      a few times 1.4e-45 counts as a variance of 0.
  *      As for srt_denoise's terms the reciprocal scale stops at FLT_MAX and an exact tie keeps its weight 1.  Every
  *      sigma_luminance >= 0 is accepted; one above FLT_MAX (+inf) counts as FLT_MAX, so that a zero variance closes the stop at
  *      every sigma (FLT_MAX * 0 = 0) and any other variance opens it (a scale of 0: weight 1 for every finite difference).

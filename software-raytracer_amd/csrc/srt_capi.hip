@@ -1377,7 +1377,9 @@ int srt_denoise(srt_context* ctx, const srt_denoise_params* d) {
     // an infinite exponent becomes FLT_MAX: the same 0 for n_p.n_q < 1 and inf above 1, and 1 (FLT_MAX * log2 1 = 0, where
     // inf * 0 would be NaN) for an exact n_p.n_q == 1, as on one face of a box
     L.sigma_normal = fminf(d->sigma_normal, FLT_MAX);
-    L.sigma_plane = d->sigma_plane;
+    // ... and so does an infinite sigma_plane: FLT_MAX * d_p is 0 for a first hit at d_p = 0, where inf * 0 would be NaN and
+    // turn every weight of the pixel, exact ties included, into NaN; for every other d_p the weights keep their bits
+    L.sigma_plane = fminf(d->sigma_plane, FLT_MAX);
     const dim3 grid = frame_tile_grid(ctx), block(srt::WG_THREADS);
     // the preparation pass and the levels alternate between the ping-pong buffer and the result buffer so that the last
     // level lands in the result
@@ -1622,7 +1624,7 @@ int srt_upsample(srt_context* ctx, const srt_upsample_params* u) {
     U.steps = u->steps;
     U.stripe = u->stripe_width > 0 && u->stripe_width < ctx->width ? u->stripe_width : ctx->width;  // (a stripe as wide as the frame is a single one)
     U.sigma_normal = fminf(u->sigma_normal, FLT_MAX);  // as srt_denoise: FLT_MAX * log2 1 = 0 where inf * 0 would be NaN
-    U.sigma_plane = u->sigma_plane;
+    U.sigma_plane = fminf(u->sigma_plane, FLT_MAX);  // as srt_denoise: FLT_MAX * 0 = 0 where inf * 0 (a first hit at d_p = 0) would be NaN
     hipLaunchKernelGGL(srt::upsample_kernel, frame_tile_grid(ctx), dim3(srt::WG_THREADS), 0, ctx->stream, U);
     SRT_HIP(ctx, hipGetLastError());
     if (!in_place) ctx->up_written = true;
@@ -1888,7 +1890,7 @@ int srt_denoise_variance(srt_context* ctx, const srt_denoise_variance_params* d)
     L.variance = var;
     L.width = ctx->width, L.height = ctx->height;
     L.sigma_normal = fminf(d->sigma_normal, FLT_MAX);  // as srt_denoise
-    L.sigma_plane = d->sigma_plane;
+    L.sigma_plane = fminf(d->sigma_plane, FLT_MAX);    // as srt_denoise
     // +inf counts as FLT_MAX: FLT_MAX * sqrt(0) = 0 closes the stop on a zero variance, where inf * 0 would be NaN
     L.sigma_luminance = fminf(d->sigma_luminance, FLT_MAX);
     const bool lum = d->sigma_luminance > 0.0f;

@@ -56,8 +56,9 @@ def motion_reference(acc, obj, nd, pos, hist, delta, keep, n, max_samples, sigma
     hit = obj >= 0
     d = np.zeros((H, W, 3), np.float32)
     k = np.ones((H, W), bool)
-    d[hit] = np.asarray(delta, np.float32)[obj[hit]]
-    k[hit] = np.asarray(keep, bool)[obj[hit]]
+    listed = hit & (obj < len(delta))  # an object index beyond the table counts as delta = 0, keep = 1
+    d[listed] = np.asarray(delta, np.float32)[obj[listed]]
+    k[listed] = np.asarray(keep, bool)[obj[listed]]
     pos_t = pos.copy()
     pos_t[..., :3] = pos[..., :3] - d  # float32 - float32, rounded to float32
     out, L, sens, scale, sw, others = reference(acc, obj, nd, pos_t, hist, n, max_samples, sigma_t, thr)

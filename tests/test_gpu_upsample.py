@@ -17,9 +17,11 @@ CLI = os.path.join(ROOT, "software-raytracer_amd", "srt_render")
 VIEWER = os.path.join(ROOT, "software-raytracer_amd", "srt_viewer")
 GUIDES = ["object", "normal_depth", "position"]
 # The denoiser's bound (tests/test_gpu_denoise.py REL_TOL): the same hardware exp2 / log2 weights with four taps instead of 25.
-# The kernel's maximum over test_upsample_matches_the_definition on the MI355X has NOT been recorded yet (the test prints it);
-# a host transcription of the kernel with libm's exp2f / log2f / expf in place of the hardware ones gives 1.5e-5.
+# The kernel's maximum over test_upsample_matches_the_definition, measured on the MI355X: 1.5e-5 at 67 x 45 and 1.2e-5 at
+# 256 x 160 (a host transcription with libm's exp2f / log2f / expf in place of the hardware ones gives 1.5e-5 too); over the
+# shapes and extremes of tests/test_gpu_pass_edges.py 2.3e-6.
 REL_TOL = 1e-4
+FLT_MAX = float(np.finfo(np.float32).max)
 
 
 def host_stripe(w):
@@ -77,7 +79,11 @@ def reference(acc, obj, nd, pos, steps, stripe, sigma_normal, sigma_plane):
                 if sigma_normal > 0:
                     w = np.where(hit, w * np.maximum(0.0, np.sum(n * n[cy, cx], axis=2)) ** sigma_normal, w)
                 if sigma_plane > 0:
-                    w = np.where(hit, w * np.exp(-np.abs(np.sum(n * (x[cy, cx] - x), axis=2)) / (sigma_plane * d)), w)
+                    # the header's clamping: a sigma above FLT_MAX counts as FLT_MAX, the reciprocal scale stops at +-FLT_MAX
+                    # (d_p = 0 included) and an exact tie keeps its weight 1
+                    scale = np.clip(1.0 / (min(float(sigma_plane), FLT_MAX) * d), -FLT_MAX, FLT_MAX)
+                    dist = np.abs(np.sum(n * (x[cy, cx] - x), axis=2))
+                    w = np.where(hit, w * np.where(dist == 0, 1.0, np.exp(-dist * scale)), w)
                 w = np.where(take, w, 0.0)
                 sw += w
                 sc += np.where(take[..., None], w[..., None] * np.where(take[..., None], c[cy, cx], 0.0), 0.0)

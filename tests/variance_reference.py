@@ -48,7 +48,11 @@ def prefilter(v, obj):
             k = K3[dx + 1] * K3[dy + 1]
             sk += np.where(take, k, 0.0)
             with np.errstate(all="ignore"):
-                sg += np.where(take, k * np.where(take, v[qy, qx], 0.0), 0.0)
+                kv = k * np.where(take, v[qy, qx], 0.0)
+                # The header's rule for the products: one at or below 2^-150, half the smallest subnormal, is 0.  Only that
+                # flush to zero is modelled; a product between 2^-150 and 2^-126 stays unrounded here while binary32 rounds
+                # it to a subnormal: a change of g_p of less than 2^-149 per tap, far below what any weight can show.
+                sg += np.where(take & (kv > 2.0 ** -150), kv, 0.0)
     with np.errstate(all="ignore"):
         return sg / sk
 
