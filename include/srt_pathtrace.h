@@ -681,6 +681,71 @@ int srt_denoise_variance_params_default(srt_denoise_variance_params* out);
  * with this call on the ALBEDO flag (a bound buffer is the caller's responsibility). */
 int srt_denoise_variance(srt_context* ctx, const srt_denoise_variance_params* params);
 
+/* ---- variance from the temporal history (SVGF's luminance moments; ABI 7, backward compatible) ---------------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7, srt_temporal_params keeps its 20 bytes
+ * and there is no new SRT_TEMPORAL_* bit.  A sequence of calls that uses none of them runs what it ran before, bit for bit, and
+ * with the output off srt_temporal_accumulate launches the kernels it launched before.
+ *
+ * srt_variance needs the frame rendered twice.  A frame that goes through srt_temporal_accumulate can have its variance from
+ * the history instead, at one render per frame: the temporal call keeps, next to the colour, the running first and second
+ * moments of the frames' luminance (Schied et al. 2017, §4.2), and srt_temporal_variance turns them into the variance buffer
+ * that srt_denoise_variance reads.
+ *
+ * Moments.  srt_moments_output switches a further output of srt_temporal_accumulate on or off (per context, off by default);
+ * flags is 0 or SRT_VARIANCE_ALBEDO.  With it on the call keeps a second history of one float4 record (M1, M2, Lm, 0) per
+ * pixel in two handle-owned slots allocated on first use (32 B per pixel); they flip with the colour slots: a call reads one
+ * and writes the other.  In the terms of srt_temporal_accumulate's rules, n = samples:
+ *   1. miss pixels store (0, 0, 0, 0).
+ *   2. mu_p = lum(c_p / m_p): c_p is the accumulator's rgb as the call finds it, before blending; lum and m_p are those of
+ *      srt_variance rules 2-3 (m_p = 1, and no division, without SRT_VARIANCE_ALBEDO).  With the flag the ALBEDO guide is
+ *      required, under the rule of the other three guides (SRT_ERR_STATE when it is missing or an own one of another camera).
+ *   3. the taps are exactly the taps the colour blend counts (rule 3, 3'), with the same weights w_q, in the same order:
+ *      s1 = sum w_q M1'_q, s2 = sum w_q M2'_q, sm = sum w_q Lm'_q.  A tap that does not count is skipped before its record is
+ *      loaded.
+ *   4. if the moments history is valid and W > 0: Lm = min(sm / W + n, max_samples), a = n / Lm,
+ *      M1 = (1 - a) * (s1 / W) + a * mu, M2 = (1 - a) * (s2 / W) + a * (mu * mu); binary32, without FMA, in this order.
+ *      Otherwise M1 = mu, M2 = mu * mu, Lm = n.  A pixel whose object has keep = 0 restarts, because it has W = 0.
+ *   5. the moments history is valid only when the immediately preceding srt_temporal_accumulate wrote it with the same flags
+ *      AND the colour history is valid for this call.  So srt_moments_output with another `enabled` or other flags drops it,
+ *      and so do SRT_TEMPORAL_RESET and everything that invalidates the colour history.  Lm is the moments' own length: a
+ *      sequence that switches the output on midway starts at Lm = n whatever L_p says.
+ *   6. turning the output on changes no bit of the accumulator, the history length, the motion output or the framebuffer.
+ * srt_read_moments waits and copies the W*H records (scene rows) of the last srt_temporal_accumulate; SRT_ERR_STATE when that
+ * call ran with the output off, or there has been none.
+ *
+ * srt_temporal_variance.  Inputs: the records the last srt_temporal_accumulate wrote, its n (the context remembers it), and
+ * o = SRT_GBUF_OBJECT, bound or own, which must be the guide that call read.  The call renders no guide.
+ *   1. miss pixels (o_p == -1): v_p = 0.
+ *   2. if Lm_p >= min_frames * n (a binary32 product) the temporal estimate applies: s = fmaxf(0, M2_p - M1_p * M1_p).
+ *   3. otherwise the pixel is young and the spatial estimate applies: taps q = p + (dx, dy), |dx|, |dy| <= radius, inside the
+ *      frame, with o_q == o_p (the centre always counts), in the order dy outer, dx inner; A1 = sum M1_q / cnt,
+ *      A2 = sum M2_q / cnt, s = fmaxf(0, A2 - A1 * A1).  A tap of another object is rejected on its object index before its
+ *      record is used, so a pixel of object A depends on records of object A only.
+ *   4. v_p = s * (n / Lm_p): the variance of the estimate the accumulator holds, the quantity srt_variance also defines.
+ *      min_frames = 0 means always temporal, +inf always spatial.
+ *   5. output: the current "variance" buffer, bound or own: the buffer and the state srt_variance writes, so that
+ *      srt_denoise_variance, srt_read_variance and srt_bind_variance work on it unchanged.  An own buffer is marked with the
+ *      records' SRT_VARIANCE_ALBEDO flag, and srt_denoise_variance's flag check applies.
+ *   6. whole frame, one launch, no atomics: repeated calls give the same bits.  Asynchronous on the launch stream behind
+ *      earlier work (srt_wait / srt_poll cover it).  It leaves alone what srt_variance leaves alone, the accumulator and the
+ *      moments themselves included. */
+int srt_moments_output(srt_context* ctx, int enabled, uint32_t flags);
+int srt_read_moments(srt_context* ctx, float* dst);
+
+typedef struct srt_temporal_variance_params {
+    float min_frames;  /* a record of at least min_frames * n samples is used alone; >= 0, +inf allowed */
+    int32_t radius;    /* the young pixels' window is (2 * radius + 1)^2, 1..3 */
+    uint32_t flags;    /* 0 */
+} srt_temporal_variance_params;
+
+/* The library's defaults: min_frames = 4 and radius = 3 (SVGF's four frames and 7 x 7 window), flags = 0 (pure host, no
+ * device needed). */
+int srt_temporal_variance_params_default(srt_temporal_variance_params* out);
+/* SRT_ERR_INVALID_ARG for unknown flags (both calls), a negative or NaN min_frames or a radius outside 1..3; SRT_ERR_STATE
+ * when the last srt_temporal_accumulate wrote no moments or there has been none, and when OBJECT has never been bound or
+ * rendered.  All are found before anything is touched. */
+int srt_temporal_variance(srt_context* ctx, const srt_temporal_variance_params* params);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

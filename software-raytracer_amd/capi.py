@@ -50,6 +50,7 @@ EXPORTS = [
     "srt_antialias_params_default", "srt_antialias", "srt_bind_antialiased", "srt_read_antialiased",
     "srt_variance_params_default", "srt_device_half", "srt_bind_half", "srt_variance", "srt_bind_variance", "srt_read_variance",
     "srt_denoise_variance_params_default", "srt_denoise_variance",
+    "srt_moments_output", "srt_read_moments", "srt_temporal_variance_params_default", "srt_temporal_variance",
 ]
 
 
@@ -158,6 +159,10 @@ class VarianceParams(C.Structure):
 class DenoiseVarianceParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
                 ("flags", C.c_uint32)]
+
+
+class TemporalVarianceParams(C.Structure):
+    _fields_ = [("min_frames", C.c_float), ("radius", C.c_int32), ("flags", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -288,6 +293,10 @@ def open_library(path):
     L.srt_read_variance.argtypes = [ctx, C.POINTER(C.c_float)]
     L.srt_denoise_variance_params_default.argtypes = [C.POINTER(DenoiseVarianceParams)]
     L.srt_denoise_variance.argtypes = [ctx, C.POINTER(DenoiseVarianceParams)]
+    L.srt_moments_output.argtypes = [ctx, C.c_int, C.c_uint32]
+    L.srt_read_moments.argtypes = [ctx, C.POINTER(C.c_float)]
+    L.srt_temporal_variance_params_default.argtypes = [C.POINTER(TemporalVarianceParams)]
+    L.srt_temporal_variance.argtypes = [ctx, C.POINTER(TemporalVarianceParams)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -369,6 +378,15 @@ def denoise_variance_defaults(lib=None):
     return {n: getattr(p, n) for n, _ in DenoiseVarianceParams._fields_}
 
 
+def temporal_variance_defaults(lib=None):
+    """srt_temporal_variance_params_default as a dict (pure host: no GPU needed)."""
+    p = TemporalVarianceParams()
+    rc = (lib if lib is not None else load_library()).srt_temporal_variance_params_default(C.byref(p))
+    if rc:
+        raise SrtError(rc, "srt_temporal_variance_params_default")
+    return {n: getattr(p, n) for n, _ in TemporalVarianceParams._fields_}
+
+
 def __getattr__(name):
     # DENOISE_DEFAULTS / TEMPORAL_DEFAULTS / UPSAMPLE_DEFAULTS: the library's defaults (denoise_defaults(), temporal_defaults(),
     # upsample_defaults()), read when first asked for, so that importing this module does not need the built library
@@ -384,6 +402,8 @@ def __getattr__(name):
         return variance_defaults()
     if name == "DENOISE_VARIANCE_DEFAULTS":
         return denoise_variance_defaults()
+    if name == "TEMPORAL_VARIANCE_DEFAULTS":
+        return temporal_variance_defaults()
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -441,6 +461,13 @@ def denoise_variance_params(iterations=None, sigma_luminance=None, sigma_normal=
                                  float(d["sigma_luminance"] if sigma_luminance is None else sigma_luminance),
                                  float(d["sigma_normal"] if sigma_normal is None else sigma_normal),
                                  float(d["sigma_plane"] if sigma_plane is None else sigma_plane), flags)
+
+
+def temporal_variance_params(min_frames=None, radius=None, lib=None):
+    """A TemporalVarianceParams: the library's defaults with the given fields replaced."""
+    d = temporal_variance_defaults(lib)
+    return TemporalVarianceParams(float(d["min_frames"] if min_frames is None else min_frames),
+                                  int(d["radius"] if radius is None else radius), int(d["flags"]))
 
 
 def _f3(v):
@@ -619,7 +646,7 @@ class PathTracer:
         they are.  Asynchronous.  The next render() must reset."""
         p = temporal_params(samples, max_samples, plane_tolerance, normal_threshold, reset, framebuffer, lib=self.L)
         if gbuffer:
-            self.render_gbuffer(outputs=TEMPORAL_GUIDES)
+            self.render_gbuffer(outputs=TEMPORAL_GUIDES | (GBUF_ALBEDO if getattr(self, "_moments_albedo", False) else 0))
         self._ck(self.L.srt_temporal_accumulate(self._h, C.byref(p)))
 
     def history_length(self):
@@ -762,6 +789,27 @@ class PathTracer:
         if gbuffer:
             self.render_gbuffer(outputs=DENOISE_GUIDES | (GBUF_ALBEDO if albedo else 0))
         self._ck(self.L.srt_denoise_variance(self._h, C.byref(p)))
+
+    def moments_output(self, on=True, albedo=False):
+        """srt_moments_output: every later temporal() also keeps the luminance moments (M1, M2, Lm, 0) of the history;
+        albedo=True takes the luminance of the demodulated colour (SRT_VARIANCE_ALBEDO; temporal(gbuffer=True) then renders the
+        ALBEDO guide too).  Switching it, or changing albedo, starts the moments afresh."""
+        self._ck(self.L.srt_moments_output(self._h, 1 if on else 0, VARIANCE_ALBEDO if albedo else 0))
+        self._moments_albedo = bool(on and albedo)
+
+    def moments(self):
+        """srt_read_moments: the records of the last temporal() call, (H, W, 4) float32 (M1, M2, Lm, 0), scene rows."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self.L.srt_read_moments(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def temporal_variance(self, min_frames=None, radius=None):
+        """srt_temporal_variance over the whole frame: the variance buffer (variance_map(), denoise_variance()) from the
+        moments of the last temporal() call and the OBJECT guide as it stands; pixels whose moments are younger than
+        min_frames frames take a spatial estimate over (2 * radius + 1)^2 pixels.  Arguments left at None take
+        TEMPORAL_VARIANCE_DEFAULTS.  Asynchronous."""
+        p = temporal_variance_params(min_frames, radius, lib=self.L)
+        self._ck(self.L.srt_temporal_variance(self._h, C.byref(p)))
 
     def wait(self):
         self._ck(self.L.srt_wait(self._h))

@@ -23,6 +23,7 @@
 #include "srt_upsample.hip.h"
 #include "srt_antialias.hip.h"
 #include "srt_variance.hip.h"
+#include "srt_moments.hip.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -311,6 +312,19 @@ struct srt_context {
     bool var_written = false;
     bool var_own_written = false;
     bool var_own_albedo = false;
+
+    // luminance moments of the temporal history (srt_moments_output, srt_temporal_variance): whether the output is on and
+    // with which flags; two slots of W*H float4 records (allocated on first use) that flip with d_tp, so d_mom[tp_cur] is what
+    // the last srt_temporal_accumulate wrote; whether that call wrote it at all (srt_read_moments, srt_temporal_variance), with
+    // which flags and which n; and whether the next call may blend with it (dropped when the output is switched or its flags
+    // change, and by a call that ran with the output off).
+    bool mom_on = false;
+    uint32_t mom_flags = 0;
+    DeviceBuffer<float4> d_mom[2];
+    bool mom_written = false;
+    uint32_t mom_written_flags = 0;
+    float mom_samples = 0.0f;
+    bool mom_history = false;
 
     char error[512] = "";
 };
@@ -1505,10 +1519,21 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
     // the handle's own guides must show the camera the history will be stored with
     const void* guide[3] = {};
     if (const int rc = find_guides(ctx, "srt_temporal_accumulate", 3, &ctx->camera.cam, guide)) return rc;
+    // the moments of the demodulated luminance need the ALBEDO guide, under the same rule
+    const float4* mom_albedo = nullptr;
+    if (ctx->mom_on && (ctx->mom_flags & SRT_VARIANCE_ALBEDO)) {
+        const void* g4[4] = {};
+        if (const int rc = find_guides(ctx, "srt_temporal_accumulate (srt_moments_output with SRT_VARIANCE_ALBEDO)", 4, &ctx->camera.cam, g4)) return rc;
+        mom_albedo = (const float4*)g4[3];
+    }
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)ctx->width * (size_t)ctx->height;
     for (int i = 0; i < 2; ++i)
         for (int k = 0; k < 3; ++k) SRT_HIP(ctx, ctx->d_tp[i][k].ensure(px * sizeof(float4)));
+    if (ctx->mom_on && (!(float4*)ctx->d_mom[0] || !(float4*)ctx->d_mom[1])) {
+        ctx->mom_written = ctx->mom_history = false;
+        for (int i = 0; i < 2; ++i) SRT_HIP(ctx, ctx->d_mom[i].ensure(px * sizeof(float4)));
+    }
     const int a = ctx->tp_cur, b = 1 - a;  // read slot a (when valid), write slot b
     srt::TemporalLaunch T{};
     T.acc = ctx->d_acc;
@@ -1536,12 +1561,28 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
         if (!ctx->d_mv_bound) SRT_HIP(ctx, ctx->d_mv_own.ensure(px * sizeof(float4)));
         T.motion = bound_or_own(ctx->d_mv_bound, ctx->d_mv_own);
     }
+    if (ctx->mom_on) {
+        T.mom_prev = ctx->d_mom[a];
+        T.mom_next = ctx->d_mom[b];
+        T.albedo = mom_albedo;
+        T.mom_valid = T.valid && ctx->mom_history && ctx->mom_written && ctx->mom_written_flags == ctx->mom_flags;
+    }
     const dim3 grid = frame_tile_grid(ctx), block(srt::WG_THREADS);
-    if (!motion && !ctx->mv_on) hipLaunchKernelGGL(srt::temporal_kernel, grid, block, 0, ctx->stream, T);
+    if (ctx->mom_on) {
+        void (*const kernel)(srt::TemporalLaunch) =
+            motion ? (ctx->mv_on ? srt::temporal_moments_kernel<true, true> : srt::temporal_moments_kernel<true, false>)
+                   : (ctx->mv_on ? srt::temporal_moments_kernel<false, true> : srt::temporal_moments_kernel<false, false>);
+        hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, T);
+    }
+    else if (!motion && !ctx->mv_on) hipLaunchKernelGGL(srt::temporal_kernel, grid, block, 0, ctx->stream, T);
     else if (!motion) hipLaunchKernelGGL((srt::temporal_motion_kernel<false, true>), grid, block, 0, ctx->stream, T);
     else if (!ctx->mv_on) hipLaunchKernelGGL((srt::temporal_motion_kernel<true, false>), grid, block, 0, ctx->stream, T);
     else hipLaunchKernelGGL((srt::temporal_motion_kernel<true, true>), grid, block, 0, ctx->stream, T);
     SRT_HIP(ctx, hipGetLastError());
+    // the records of slot b: this call's, or (output off) none
+    ctx->mom_written = ctx->mom_on;
+    ctx->mom_history = ctx->mom_on;
+    if (ctx->mom_on) ctx->mom_written_flags = ctx->mom_flags, ctx->mom_samples = T.samples;
     ctx->tp_cur = b;
     ctx->tp_cam = ctx->camera.cam;
     ctx->tp_objects = ctx->objects;  // the list this history's points belong to
@@ -1569,6 +1610,63 @@ int srt_read_motion(srt_context* ctx, float* dst) {
     if (!src || src != ctx->mv_last) return fail(ctx, SRT_ERR_STATE, "srt_read_motion: no srt_temporal_accumulate has written this buffer yet");
     if (const int rc = finish_stream(ctx)) return rc;
     SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+int srt_moments_output(srt_context* ctx, int enabled, uint32_t flags) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    if (flags & ~SRT_VARIANCE_ALBEDO) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_moments_output: unknown flags 0x%x", flags);
+    const bool on = enabled != 0;
+    if (on != ctx->mom_on || flags != ctx->mom_flags) ctx->mom_history = false;  // the next call starts the moments afresh
+    ctx->mom_on = on;
+    ctx->mom_flags = flags;
+    return SRT_OK;
+}
+
+int srt_read_moments(srt_context* ctx, float* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    if (!ctx->mom_written) return fail(ctx, SRT_ERR_STATE, "srt_read_moments: the last srt_temporal_accumulate wrote no moments (srt_moments_output)");
+    if (const int rc = finish_stream(ctx)) return rc;
+    SRT_HIP(ctx, hipMemcpy(dst, ctx->d_mom[ctx->tp_cur], (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+int srt_temporal_variance_params_default(srt_temporal_variance_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    out->min_frames = 4.0f;  // SVGF's (Schied et al. 2017, §4.2)
+    out->radius = 3;         // its 7 x 7 window
+    out->flags = 0;
+    return SRT_OK;
+}
+
+int srt_temporal_variance(srt_context* ctx, const srt_temporal_variance_params* v) {
+    if (!ctx || !v) return SRT_ERR_INVALID_ARG;
+    if (v->flags != 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_temporal_variance: unknown flags 0x%x", v->flags);
+    // (written so that a NaN fails too)
+    if (!(v->min_frames >= 0.0f)) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_temporal_variance: min_frames must be >= 0 (%g)", v->min_frames);
+    if (v->radius < 1 || v->radius > srt::MT_MAX_RADIUS)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_temporal_variance: radius %d outside 1..%d", v->radius, srt::MT_MAX_RADIUS);
+    if (!ctx->mom_written)
+        return fail(ctx, SRT_ERR_STATE, "srt_temporal_variance: the last srt_temporal_accumulate wrote no moments (srt_moments_output)");
+    const void* guide[1] = {};
+    if (const int rc = find_guides(ctx, "srt_temporal_variance", 1, nullptr, guide)) return rc;
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)ctx->width * (size_t)ctx->height;
+    if (!ctx->d_var_bound) SRT_HIP(ctx, ctx->d_var_own.ensure(px * sizeof(float)));
+    srt::MomentsLaunch M{};
+    M.moments = ctx->d_mom[ctx->tp_cur];
+    M.object = (const int32_t*)guide[0];
+    M.variance = bound_or_own(ctx->d_var_bound, ctx->d_var_own);
+    M.width = ctx->width, M.height = ctx->height;
+    M.samples = ctx->mom_samples;
+    M.old_length = v->min_frames * ctx->mom_samples;
+    void (*const kernel)(srt::MomentsLaunch) = v->radius == 1   ? srt::temporal_variance_kernel<1>
+                                               : v->radius == 2 ? srt::temporal_variance_kernel<2>
+                                                                : srt::temporal_variance_kernel<3>;
+    hipLaunchKernelGGL(kernel, frame_tile_grid(ctx), dim3(srt::WG_THREADS), 0, ctx->stream, M);
+    SRT_HIP(ctx, hipGetLastError());
+    ctx->var_written = true;
+    if (!ctx->d_var_bound) ctx->var_own_written = true, ctx->var_own_albedo = (ctx->mom_written_flags & SRT_VARIANCE_ALBEDO) != 0;
     return SRT_OK;
 }
 

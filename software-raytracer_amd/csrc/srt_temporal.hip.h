@@ -12,9 +12,14 @@
 // Moving objects (srt_update_scene) add a per-object table (displacement since the previous call, keep flag), a per-lane
 // 16-byte gather keyed by the pixel's object index; srt_motion_output adds one float4 store per pixel.  Both are template
 // options of the one pixel routine, and the call that uses neither runs temporal_kernel as it always was.
+// srt_moments_output adds a second history that rides the same reprojection: one float4 (M1, M2, Lm, 0) per pixel, the running
+// first and second moments of the frames' luminance and their own length, blended over the taps the colour blend counts with
+// the same weights (up to four more 16-byte loads and one more 16-byte store per pixel, and the albedo when demodulating).  It
+// is a third template option; srt_moments.hip.h turns the records into a variance.
 #pragma once
 
 #include "srt_kernel.hip.h"
+#include "srt_variance.hip.h"  // luminance, demod_factor
 
 namespace srt {
 
@@ -46,11 +51,17 @@ struct TemporalLaunch {
     const float4* table;         // MOTION: table_count rows (position now - position at the previous call, keep), else unused
     int table_count;             // rows of the table; an object index beyond it (bound guides) has moved by 0 and is kept
     float4* motion;              // MV: W*H rows (u - x, v - y, sum of the counted taps' weights, 0), else unused
+    // the moments history (srt_moments_output), appended in the same way
+    const float4* mom_prev;      // MOM: the previous call's records (M1, M2, Lm, 0), read only when mom_valid; else unused
+    float4* mom_next;            // MOM: this call's records, written for every pixel
+    const float4* albedo;        // MOM: SRT_GBUF_ALBEDO when the luminance is demodulated, else NULL
+    int mom_valid;               // MOM: mom_prev belongs to the history `prev` and was written with the same flags
 };
 
 // MOTION: the hit object's row of T.table moves x_p back to where the object was at the previous call (x~_p = x_p - delta),
 // and a row with keep == 0 (the object was reshaped or recoloured) leaves the pixel without history.  MV: T.motion is written.
-template <bool MOTION, bool MV>
+// MOM: T.mom_next is written (include/srt_pathtrace.h, "moments"); no other value depends on it.
+template <bool MOTION, bool MV, bool MOM = false>
 __device__ __forceinline__ void temporal_pixel(const TemporalLaunch& T) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = (int)blockIdx.x * WG_W + (wave % WG_TILES_X) * TILE_W + (lane & 7);
@@ -65,6 +76,7 @@ __device__ __forceinline__ void temporal_pixel(const TemporalLaunch& T) {
         T.next.normal[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (T.framebuffer) T.framebuffer[(size_t)(H - 1 - y) * W + x] = tone_map(T.acc[p]);
         if (MV) T.motion[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (MOM) T.mom_next[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
     const float4 c = T.acc[p];
@@ -79,6 +91,7 @@ __device__ __forceinline__ void temporal_pixel(const TemporalLaunch& T) {
     }
     float mu = 0.0f, mv = 0.0f;
     float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f;
+    float s1 = 0.0f, s2 = 0.0f, sm = 0.0f;  // MOM: the counted taps' M1', M2' and Lm' under the colour blend's weights
     if (T.valid && keep) {
         const float rx = xt.x - T.cam_pos[0], ry = xt.y - T.cam_pos[1], rz = xt.z - T.cam_pos[2];
         const float a = T.inv[0] * rx + T.inv[1] * ry + T.inv[2] * rz;
@@ -116,9 +129,33 @@ __device__ __forceinline__ void temporal_pixel(const TemporalLaunch& T) {
                     sg = sg + w * h.y;
                     sb = sb + w * h.z;
                     sl = sl + w * h.w;
+                    if (MOM && T.mom_valid) {
+                        const float4 m = T.mom_prev[q];
+                        s1 = s1 + w * m.x;
+                        s2 = s2 + w * m.y;
+                        sm = sm + w * m.z;
+                    }
                 }
             }
         }
+    }
+    if (MOM) {
+        // this frame's luminance: the accumulator as the call finds it, demodulated like srt_variance's halves
+        float lum;
+        if (T.albedo) {
+            const float4 a4 = T.albedo[p];
+            lum = luminance(c.x / demod_factor(a4.x), c.y / demod_factor(a4.y), c.z / demod_factor(a4.z));
+        } else {
+            lum = luminance(c.x, c.y, c.z);
+        }
+        float m1 = lum, m2 = lum * lum, lm = T.samples;
+        if (T.mom_valid && sw > 0.0f) {
+            lm = fminf(sm / sw + T.samples, T.max_samples);
+            const float al = T.samples / lm, bl = 1.0f - al;
+            m1 = bl * (s1 / sw) + al * lum;
+            m2 = bl * (s2 / sw) + al * (lum * lum);
+        }
+        T.mom_next[p] = make_float4(m1, m2, lm, 0.0f);
     }
     float4 out = c;
     float L = T.samples;
@@ -143,6 +180,12 @@ __global__ void __launch_bounds__(WG_THREADS) temporal_kernel(const TemporalLaun
 template <bool MOTION, bool MV>
 __global__ void __launch_bounds__(WG_THREADS) temporal_motion_kernel(const TemporalLaunch T) {
     temporal_pixel<MOTION, MV>(T);
+}
+
+// ... and any of the four with the moments history (srt_moments_output)
+template <bool MOTION, bool MV>
+__global__ void __launch_bounds__(WG_THREADS) temporal_moments_kernel(const TemporalLaunch T) {
+    temporal_pixel<MOTION, MV, true>(T);
 }
 
 }  // namespace srt

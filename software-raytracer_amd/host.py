@@ -30,6 +30,7 @@ EXPORTS = [
     "srt_host_renderer_upsample", "srt_host_renderer_read_upsampled", "srt_host_renderer_guided_upsample",
     "srt_host_renderer_antialias", "srt_host_renderer_read_antialiased", "srt_host_renderer_set_antialias",
     "srt_host_renderer_denoise_variance", "srt_host_renderer_read_variance",
+    "srt_host_renderer_temporal_variance", "srt_host_renderer_read_moments",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -124,6 +125,8 @@ def load_library():
     L.srt_host_renderer_set_antialias.argtypes = [vp, C.c_int]
     L.srt_host_renderer_denoise_variance.argtypes = [vp, C.c_uint32, C.c_uint32]
     L.srt_host_renderer_read_variance.argtypes = [vp, C.POINTER(C.c_float)]
+    L.srt_host_renderer_temporal_variance.argtypes = [vp, C.c_int]
+    L.srt_host_renderer_read_moments.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_multi_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]
     L.srt_host_multi_create.restype = vp
     L.srt_host_multi_destroy.argtypes = [vp]
@@ -426,6 +429,17 @@ class Renderer:
         """PathTraceRenderer::ReadVariance: (H, W) float32, scene rows, as capi.PathTracer.variance_map returns it."""
         out = np.empty((self.height, self.width), dtype=np.float32)
         self._ck(self.L.srt_host_renderer_read_variance(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def temporal_variance(self, on=True):
+        """PathTraceRenderer::temporalVariance: render_temporal_frame() also keeps the luminance moments of the history and,
+        with denoise=True, shows the frame through srt_temporal_variance + srt_denoise_variance instead of srt_denoise."""
+        self._ck(self.L.srt_host_renderer_temporal_variance(self._h, 1 if on else 0))
+
+    def moments(self):
+        """PathTraceRenderer::ReadMoments: (H, W, 4) float32 (M1, M2, Lm, 0), scene rows, as capi.PathTracer.moments returns it."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_moments(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
     def stats(self):

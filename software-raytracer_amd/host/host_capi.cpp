@@ -254,6 +254,12 @@ int srt_host_renderer_set_antialias(srt_host_renderer* h, int k) {
 // one variance-guided denoised frame of spp samples in two halves (PathTraceRenderer::denoiseVariance), and its variance estimate
 int srt_host_renderer_denoise_variance(srt_host_renderer* h, uint32_t spp, uint32_t flags) { SRT_HOST_TRY(h, h->r->denoiseVariance(spp, flags)) }
 int srt_host_renderer_read_variance(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadVariance(dst)) }
+// the temporalVariance setting of RenderTemporalFrame, and the moments of the last temporal frame (srt_read_moments)
+int srt_host_renderer_temporal_variance(srt_host_renderer* h, int on) {
+    h->r->temporalVariance = on != 0;
+    return 0;
+}
+int srt_host_renderer_read_moments(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadMoments(dst)) }
 int srt_host_renderer_stats(srt_host_renderer* h, srt_stats* out) { SRT_HOST_TRY(h, *out = h->r->Stats()) }
 void* srt_host_renderer_handle(srt_host_renderer* h) { return h->r->handle(); }
 

@@ -262,14 +262,18 @@ void PathTraceRenderer::RenderTemporalFrame(uint32_t spp, bool denoise) {
     p.steps = 1;
     p.selected_object = -1;
     check(srt_render(ctx_, &p), "srt_render");
-    RenderGBuffer(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION | (denoise ? SRT_GBUF_ALBEDO : 0u));
+    RenderGBuffer(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION | (denoise || temporalVariance ? SRT_GBUF_ALBEDO : 0u));
+    // the moments of the demodulated luminance: what srt_denoise_variance's defaults filter
+    check(srt_moments_output(ctx_, temporalVariance ? 1 : 0, temporalVariance ? SRT_VARIANCE_ALBEDO : 0u), "srt_moments_output");
     srt_temporal_params t{};
     check(srt_temporal_params_default(&t), "srt_temporal_params_default");
     t.samples = spp;
     if (t.max_samples < (float)spp) t.max_samples = (float)spp;
     t.flags = (temporal_reset_ ? SRT_TEMPORAL_RESET : 0u) | (denoise ? 0u : SRT_TEMPORAL_FRAMEBUFFER);
     Temporal(t);
-    if (denoise) {
+    if (denoise && temporalVariance) {
+        DenoiseTemporalVariance(SRT_DENOISE_FRAMEBUFFER);
+    } else if (denoise) {
         srt_denoise_params d{};
         check(srt_denoise_params_default(&d), "srt_denoise_params_default");
         d.flags |= SRT_DENOISE_FRAMEBUFFER;
@@ -329,6 +333,18 @@ void PathTraceRenderer::denoiseVariance(uint32_t spp, uint32_t flags) {
 }
 
 void PathTraceRenderer::ReadVariance(float* dst) { check(srt_read_variance(ctx_, dst), "srt_read_variance"); }
+
+void PathTraceRenderer::DenoiseTemporalVariance(uint32_t flags) {
+    srt_temporal_variance_params v{};
+    check(srt_temporal_variance_params_default(&v), "srt_temporal_variance_params_default");
+    srt_denoise_variance_params d{};
+    check(srt_denoise_variance_params_default(&d), "srt_denoise_variance_params_default");
+    d.flags |= flags;
+    check(srt_temporal_variance(ctx_, &v), "srt_temporal_variance");
+    check(srt_denoise_variance(ctx_, &d), "srt_denoise_variance");
+}
+
+void PathTraceRenderer::ReadMoments(float* dst) { check(srt_read_moments(ctx_, dst), "srt_read_moments"); }
 
 std::vector<float> PathTraceRenderer::ReadAccumulator() {
     std::vector<float> out((size_t)width_ * height_ * 4);

@@ -73,6 +73,10 @@ class PathTraceRenderer {
     // not in the reference: 1..4 makes RenderFrame and RenderTemporalFrame end in the anti-aliasing resolve (srt_antialias with
     // this k and SRT_AA_FRAMEBUFFER); 0 = off.  The accumulator stays what the reference accumulates.  Whole frame only.
     int antialias = 0;
+    // not in the reference: RenderTemporalFrame also keeps the luminance moments of the history (srt_moments_output with
+    // SRT_VARIANCE_ALBEDO) and, when it denoises, runs srt_temporal_variance + srt_denoise_variance at the library's defaults
+    // where it otherwise runs srt_denoise: the per-pixel variance of a temporal frame at one render per frame.
+    bool temporalVariance = false;
     Transform camera;   // :295-297
 
     PathTraceRenderer(int device, int width, int height);
@@ -161,7 +165,8 @@ class PathTraceRenderer {
     // SRT_RENDER_RESET and seed + k (k = the number of temporal frames this renderer has rendered before, so that the noise
     // does not stay fixed to the screen), the first-hit guides, srt_temporal_accumulate with the library's defaults
     // (samples = spp, max_samples raised to spp if below; SRT_TEMPORAL_RESET on the first temporal frame and after
-    // Invalidate(), SetScene, SetEnvironment or SetRowBand), then with `denoise` srt_denoise with its defaults, then with
+    // Invalidate(), SetScene, SetEnvironment or SetRowBand), then with `denoise` srt_denoise with its defaults (with
+    // temporalVariance: DenoiseTemporalVariance, and the moments are kept whether or not the frame is denoised), then with
     // antialias > 0 Antialias on the denoised buffer (with `denoise`) or the accumulator.  The last step
     // writes the framebuffer.  Later RenderFrame / RenderSamples calls start a fresh accumulation.
     void RenderTemporalFrame(uint32_t spp, bool denoise);
@@ -173,6 +178,12 @@ class PathTraceRenderer {
     // RenderFrame / RenderSamples calls start a fresh accumulation.
     void denoiseVariance(uint32_t spp, uint32_t flags = 0);
     void ReadVariance(float* dst);
+    // The variance-guided filter of a temporal frame rendered with temporalVariance (whole frame, the four guides as they
+    // stand): srt_temporal_variance and srt_denoise_variance with the library's defaults and `flags` (SRT_DENOISE_FRAMEBUFFER)
+    // added.  RenderTemporalFrame(spp, true) ends in it.  ReadMoments waits and copies the W x H float4 records
+    // (M1, M2, Lm, 0) of the last temporal frame (scene rows).
+    void DenoiseTemporalVariance(uint32_t flags = 0);
+    void ReadMoments(float* dst);
 
     void PushCamera() { push_camera(); }  // srt_set_camera with the members as they stand (used by MultiGpuRenderer)
 

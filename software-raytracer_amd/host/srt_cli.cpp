@@ -66,7 +66,7 @@ static void usage() {
                  "                  [--fov 55] [--seed 0] [--device 0 | --devices 0,1,2,...] [--out frame.ppm] [--resave FILE]\n"
                  "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]\n"
                  "                  [--move-object IDX:DX,DY,DZ]...] [--steps N] [--upsample PATH] [--aa K]\n"
-                 "                  [--denoise-variance PATH]\n"
+                 "                  [--denoise-variance PATH] [--temporal-variance]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
                  "             and means the same), --equal-bands: bands of equal height\n"
@@ -92,13 +92,17 @@ static void usage() {
                  "             denoised form); before every frame but the first the camera moves by R, U, F along its right,\n"
                  "             up and forward axes (--move) and turns by DEG degrees about world up (--turn); single device only\n"
                  "  --move-object: with --temporal, before every frame but the first add DX, DY, DZ to the position of object IDX\n"
-                 "             (list order) and keep the history across the edit (srt_update_scene); may be given several times\n");
+                 "             (list order) and keep the history across the edit (srt_update_scene); may be given several times\n"
+                 "  --temporal-variance: with --temporal, also keep the luminance moments of the history (srt_moments_output) and\n"
+                 "             filter the --denoise frame by the per-pixel variance they give (srt_temporal_variance,\n"
+                 "             srt_denoise_variance, the library's defaults) instead of srt_denoise; not with --steps, --upsample or\n"
+                 "             --devices\n");
 }
 
 int main(int argc, char** argv) {
     std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise, upsample, denoise_variance;
     int temporal = 0, steps = 1, aa = 0;
-    bool aa_given = false;
+    bool aa_given = false, temporal_variance = false;
     float move[3] = {0, 0, 0}, turn_deg = 0;
     struct ObjectMove {
         size_t index;
@@ -142,6 +146,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--steps")) steps = std::atoi(need("--steps"));
         else if (!std::strcmp(argv[i], "--upsample")) upsample = need("--upsample");
         else if (!std::strcmp(argv[i], "--aa")) aa = std::atoi(need("--aa")), aa_given = true;
+        else if (!std::strcmp(argv[i], "--temporal-variance")) temporal_variance = true;
         else if (!std::strcmp(argv[i], "--temporal")) temporal = std::atoi(need("--temporal"));
         else if (!std::strcmp(argv[i], "--turn")) turn_deg = std::strtof(need("--turn"), nullptr);
         else if (!std::strcmp(argv[i], "--move")) {
@@ -184,6 +189,10 @@ int main(int argc, char** argv) {
     }
     if (scene_path.empty() || W <= 0 || H <= 0 || spp <= 0 || temporal < 0 || steps < 1) {
         usage();
+        return 2;
+    }
+    if (temporal_variance && (!temporal || !devices.empty() || steps > 1 || !upsample.empty())) {
+        std::fprintf(stderr, "--temporal-variance needs --temporal and works on one device only, not with --steps or --upsample\n");
         return 2;
     }
     if (!denoise.empty() && !devices.empty()) {
@@ -282,6 +291,7 @@ int main(int argc, char** argv) {
         };
         if (temporal) {
             r.antialias = aa;  // every temporal frame ends in the resolve
+            r.temporalVariance = temporal_variance;  // every temporal frame keeps the moments
             // a moving camera that keeps its samples: every frame renders spp samples, reprojects the history and writes the
             // framebuffer; each frame's camera is printed exactly (%.9g round-trips a float) so that callers can replay it
             std::vector<uint32_t> fb((size_t)W * H);
@@ -322,7 +332,9 @@ int main(int argc, char** argv) {
                 srt_denoise_params_default(&dp);
                 dp.flags |= SRT_DENOISE_FRAMEBUFFER;
                 r.RenderGBuffer(SRT_GBUF_ALL);
-                r.Denoise(dp);
+                // --temporal-variance: the variance of the history's moments and the variance-guided filter in its place
+                if (temporal_variance) r.DenoiseTemporalVariance(SRT_DENOISE_FRAMEBUFFER);
+                else r.Denoise(dp);
                 resolve(SRT_AA_SOURCE_DENOISED);
                 r.ReadFramebuffer(fb.data(), (size_t)W * 4);
                 if (write_ppm(fb, denoise)) return 1;

@@ -41,6 +41,10 @@
 //   V  variance-guided mode (not in the reference; PathTraceRenderer::denoiseVariance): every frame is a full path-traced
 //      frame of two samples, one per independently seeded half, shown through the variance-guided filter
 //      (srt_variance, srt_denoise_variance); it takes precedence over temporal mode, and toggling it calls Invalidate()
+//   Y  temporal variance (not in the reference; PathTraceRenderer::temporalVariance): effective in temporal mode, where every
+//      frame then also keeps the luminance moments of its history and is shown through the variance-guided filter on the
+//      variance they give (srt_temporal_variance, srt_denoise_variance), still at one sample per frame; the colour history
+//      is untouched, so the toggle raises nothing (the moments start afresh)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -68,7 +72,7 @@ struct InputState {  // one frame's worth, what SDLInputManager hands the loop
     int mouse_dx = 0, mouse_dy = 0;  // relative motion of this frame
     bool left_down = false;          // edge
     int mouse_x = 0, mouse_y = 0;    // window coordinates of the click, y down
-    std::string pressed;             // key-down edges of this frame: any of "PMFGBN1234XTRCV" (X = DELETE)
+    std::string pressed;             // key-down edges of this frame: any of "PMFGBN1234XTRCVY" (X = DELETE)
 };
 
 class ViewerCore {
@@ -126,7 +130,7 @@ class ViewerCore {
             else r_.selectedObject = r_.Pick(in.mouse_x, in.mouse_y);
         }
         if (variance_) r_.denoiseVariance(2, SRT_DENOISE_FRAMEBUFFER);
-        else if (temporal_) r_.RenderTemporalFrame(1, false);
+        else if (temporal_) r_.RenderTemporalFrame(1, r_.temporalVariance);
         else r_.RenderFrame();  // :572-595
     }
 
@@ -138,6 +142,7 @@ class ViewerCore {
             case 'R': r_.guidedUpsample = !r_.guidedUpsample; break;
             case 'C': r_.antialias = r_.antialias ? 0 : 2; break;
             case 'V': variance_ = !variance_; r_.Invalidate(); break;
+            case 'Y': r_.temporalVariance = !r_.temporalVariance; break;
             case 'M': r_.SIMPLEDRAW = !r_.SIMPLEDRAW; r_.Invalidate(); break;      // :462-465
             case 'F': case 'G': {                                                  // :468-473
                 int f = r_.FOV + (k == 'G' ? 1 : -1);
@@ -185,7 +190,7 @@ void write_ppm(PathTraceRenderer& r, const std::string& path) {
 // Script of the headless back end, one command per line ('#' starts a comment):
 //   delta SECONDS | hold KEYS | release KEYS   (KEYS out of W A S D E Q and L for LSHIFT; the object-move keys in lower case,
 //     i k j l u o, because the upper-case L is taken)
-//   press KEYS (P M F G B N 1 2 3 4 X T R C V, applied to the next frame only)
+//   press KEYS (P M F G B N 1 2 3 4 X T R C V Y, applied to the next frame only)
 //   upsample on|off (guided upsampling of block frames, what the R key toggles)
 //   antialias K|off (anti-aliasing with K x K sub-samples, K in 1..4; the C key toggles K = 2)
 //   rmb down|up | move DX DY (relative mouse motion of the next frame) | click X Y
@@ -296,7 +301,7 @@ int run_window(ViewerCore& core) {
                     case SDL_SCANCODE_B: in.pressed += 'B'; break; case SDL_SCANCODE_N: in.pressed += 'N'; break;
                     case SDL_SCANCODE_1: in.pressed += '1'; break; case SDL_SCANCODE_2: in.pressed += '2'; break;
                     case SDL_SCANCODE_3: in.pressed += '3'; break; case SDL_SCANCODE_4: in.pressed += '4'; break;
-                    case SDL_SCANCODE_DELETE: in.pressed += 'X'; break; case SDL_SCANCODE_T: in.pressed += 'T'; break; case SDL_SCANCODE_R: in.pressed += 'R'; break; case SDL_SCANCODE_C: in.pressed += 'C'; break; case SDL_SCANCODE_V: in.pressed += 'V'; break; case SDL_SCANCODE_ESCAPE: quit = true; break;
+                    case SDL_SCANCODE_DELETE: in.pressed += 'X'; break; case SDL_SCANCODE_T: in.pressed += 'T'; break; case SDL_SCANCODE_R: in.pressed += 'R'; break; case SDL_SCANCODE_C: in.pressed += 'C'; break; case SDL_SCANCODE_V: in.pressed += 'V'; break; case SDL_SCANCODE_Y: in.pressed += 'Y'; break; case SDL_SCANCODE_ESCAPE: quit = true; break;
                     default: break;
                 }
             }
