@@ -406,7 +406,7 @@ int srt_read_history_length(srt_context* ctx, float* dst);
  * vertex + position), so an object edit that keeps the history is a per-object translation.
  *
  * srt_update_scene replaces the scene exactly as srt_set_scene does — the same validation, scene image, mesh BVH (rebuilt in
- * full: an update costs what a set costs), and the same resets of dispatch order, recorded work and cost estimate — so
+ * full: an update costs what a set costs, unless srt_update_mode below allows a refit), and the same resets of dispatch order, recorded work and cost estimate — so
  * srt_render, srt_render_gbuffer, srt_pick and srt_estimate_row_costs give the bits a fresh srt_set_scene of the same list
  * gives.  The one difference: it does NOT invalidate the temporal history.  SRT_ERR_STATE when no scene is set,
  * SRT_ERR_INVALID_ARG when count differs from the current scene's; both are found before anything is touched, so scene and
@@ -441,6 +441,60 @@ int srt_update_scene(srt_context* ctx, const srt_object* objects, size_t count);
 int srt_motion_output(srt_context* ctx, int enabled);
 int srt_bind_motion(srt_context* ctx, void* d_float4);
 int srt_read_motion(srt_context* ctx, float* dst);
+
+/* ---- refitting the mesh BVH when an update only moves objects (ABI 7, backward compatible) -------------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  With the mode left at its default,
+ * SRT_UPDATE_REBUILD, srt_update_scene does what it did before, bit for bit, and launches and uploads nothing else.
+ *
+ * srt_update_mode sets, per context, what srt_update_scene may do to the mesh image (SRT_ERR_INVALID_ARG for another value).
+ * The mode is read when srt_set_scene / srt_update_scene run: a mesh image built under SRT_UPDATE_REFIT is followed to the
+ * device by its refit data (the meshes' vertices, the triangles' vertex indices, scratch for the exact boxes); a scene set
+ * while the mode was SRT_UPDATE_REBUILD has none, so its first update under SRT_UPDATE_REFIT rebuilds (reason 4) and uploads it.
+ *
+ * Under SRT_UPDATE_REFIT srt_update_scene runs the same validation first (SRT_ERR_STATE, the count check), then picks a path
+ * for the mesh image:
+ *   kept (3)    old and new list differ at most in `position` of objects that are not SRT_OBJ_MESH (or the scene has no
+ *               triangles).  The mesh image, its device buffers and the triangle-id table are not touched.
+ *   refit (2)   the lists differ only in `position`, at least one mesh object moved, the refit data is on the device, every
+ *               mesh object's position is finite in both lists and the build dropped no triangle of a moved object's mesh for a
+ *               non-finite vertex (so the set of valid triangles is the same).  The root box is derived on the host from the
+ *               per-object boxes and the positions, and the limit of 1e9 on world coordinates is checked there, before anything
+ *               is enqueued: SRT_ERR_INVALID_ARG with srt_set_scene's message, and the previous scene stands.  Then two kernels
+ *               rewrite the image in place on the launch stream, behind every render already enqueued: every triangle record
+ *               (vertex + position, the edges; the .w words kept) and, level by level from the deepest, every node's origin,
+ *               exponents and child bytes from the exact boxes below it.  All triangles and all levels are rewritten, not
+ *               only the moved objects'.  Nothing is read back and nothing waits for the kernels.
+ *   rebuilt (1) in every other case (also after srt_set_meshes): exactly the code of SRT_UPDATE_REBUILD.
+ * In all three paths the analytic scene image is rebuilt on the host and uploaded, dispatch order, recorded work and the cost
+ * estimate are reset, and the temporal history and the displacement table are handled as srt_update_scene documents above.
+ *
+ * Guarantee: after a refit, srt_render, srt_render_gbuffer, srt_render_subsamples and srt_pick give the bits that a fresh
+ * srt_set_scene of the same list gives: the triangle records are identical, the child boxes enclose the exact boxes, and the
+ * closest-hit key (distance, list order, global triangle id) does not depend on traversal order.  Not promised, and free to
+ * differ from a fresh set: srt_estimate_row_costs, srt_get_work_counts, the launch shape of later renders, times.  A tree
+ * refitted after a large move is a worse tree; srt_set_scene, or an update under SRT_UPDATE_REBUILD, rebuilds it.  The root's
+ * bounding sphere after a refit is the root box's, looser than the per-vertex one of a build.
+ *
+ * srt_get_update_info describes the last successful srt_update_scene of the context (path 0 before the first).
+ *
+ * Diagnostics: srt_mesh_image_size gives the bytes of the node array (80 per node) and of the triangle array (48 per triangle)
+ * as the kernels read them, 0 and 0 for a scene without triangles; srt_read_mesh_image waits, then copies both (a NULL
+ * destination is allowed for an array of 0 bytes).  SRT_ERR_STATE before srt_set_scene. */
+#define SRT_UPDATE_REBUILD 0 /* default: srt_update_scene rebuilds the mesh image */
+#define SRT_UPDATE_REFIT 1
+typedef struct srt_update_info {
+    int32_t path;      /* 0: no srt_update_scene yet; 1: rebuilt; 2: refitted; 3: mesh image kept */
+    int32_t reason;    /* path 1 only: 1 the mode is REBUILD; 2 a field other than position differs; 3 the valid-triangle set
+                          cannot be shown unchanged; 4 the scene was set without refit data (or srt_set_meshes came since) */
+    int32_t levels;    /* path 2: launches of the level kernel (= depth of the wide tree) */
+    uint32_t triangles; /* path 2: triangle records rewritten */
+    uint32_t nodes;     /* path 2: nodes requantized */
+    uint32_t moved_mesh_objects; /* mesh objects whose position differs between the two lists */
+} srt_update_info;
+int srt_update_mode(srt_context* ctx, int mode);
+int srt_get_update_info(srt_context* ctx, srt_update_info* out);
+int srt_mesh_image_size(srt_context* ctx, size_t* node_bytes, size_t* triangle_bytes);
+int srt_read_mesh_image(srt_context* ctx, void* nodes, void* triangles);
 
 /* ---- guided upsampling of progressive-resolution blocks (ABI 7, backward compatible) -------------------------------------
  * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.

@@ -32,6 +32,9 @@ UPSAMPLE_GUIDES = GBUF_OBJECT | GBUF_NORMAL_DEPTH | GBUF_POSITION
 AA_FRAMEBUFFER = 2
 AA_SOURCE_ACCUMULATOR, AA_SOURCE_DENOISED = 0, 1
 VARIANCE_ALBEDO, VARIANCE_MERGE = 1, 2
+UPDATE_REBUILD, UPDATE_REFIT = 0, 1
+# srt_update_info.path by name
+UPDATE_PATHS = {0: "none", 1: "rebuilt", 2: "refitted", 3: "kept"}
 ABI_VERSION = 7
 
 # every symbol include/srt_pathtrace.h declares (tests check the library exports them all)
@@ -51,6 +54,7 @@ EXPORTS = [
     "srt_variance_params_default", "srt_device_half", "srt_bind_half", "srt_variance", "srt_bind_variance", "srt_read_variance",
     "srt_denoise_variance_params_default", "srt_denoise_variance",
     "srt_moments_output", "srt_read_moments", "srt_temporal_variance_params_default", "srt_temporal_variance",
+    "srt_update_mode", "srt_get_update_info", "srt_mesh_image_size", "srt_read_mesh_image",
 ]
 
 
@@ -163,6 +167,15 @@ class DenoiseVarianceParams(C.Structure):
 
 class TemporalVarianceParams(C.Structure):
     _fields_ = [("min_frames", C.c_float), ("radius", C.c_int32), ("flags", C.c_uint32)]
+
+
+class UpdateInfo(C.Structure):
+    """srt_update_info: what the last successful srt_update_scene did to the mesh image."""
+    _fields_ = [("path", C.c_int32), ("reason", C.c_int32), ("levels", C.c_int32), ("triangles", C.c_uint32), ("nodes", C.c_uint32),
+                ("moved_mesh_objects", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -297,6 +310,10 @@ def open_library(path):
     L.srt_read_moments.argtypes = [ctx, C.POINTER(C.c_float)]
     L.srt_temporal_variance_params_default.argtypes = [C.POINTER(TemporalVarianceParams)]
     L.srt_temporal_variance.argtypes = [ctx, C.POINTER(TemporalVarianceParams)]
+    L.srt_update_mode.argtypes = [ctx, C.c_int]
+    L.srt_get_update_info.argtypes = [ctx, C.POINTER(UpdateInfo)]
+    L.srt_mesh_image_size.argtypes = [ctx, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.srt_read_mesh_image.argtypes = [ctx, C.c_void_p, C.c_void_p]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -538,6 +555,26 @@ class PathTracer:
         n = len(objects) if count is None else count
         ptr = C.cast(objects, C.POINTER(Object)) if n else None
         self._ck(self.L.srt_update_scene(self._h, ptr, n))
+
+    def update_mode(self, refit=True):
+        """srt_update_mode: let update_scene() refit the mesh BVH on the device when the lists differ only in positions
+        (refit=False: rebuild it every time, the default)."""
+        self._ck(self.L.srt_update_mode(self._h, UPDATE_REFIT if refit else UPDATE_REBUILD))
+
+    def update_info(self):
+        """srt_get_update_info: what the last update_scene() did, as a dict (path 1 rebuilt, 2 refitted, 3 kept; UPDATE_PATHS)."""
+        u = UpdateInfo()
+        self._ck(self.L.srt_get_update_info(self._h, C.byref(u)))
+        return u.as_dict()
+
+    def mesh_image(self):
+        """srt_read_mesh_image: the mesh image as the kernels read it: (nodes (N, 5, 4) float32, triangles (T, 3, 4) float32)."""
+        nb, tb = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self.L.srt_mesh_image_size(self._h, C.byref(nb), C.byref(tb)))
+        nodes = np.empty((nb.value // 80, 5, 4), dtype=np.float32)
+        tris = np.empty((tb.value // 48, 3, 4), dtype=np.float32)
+        self._ck(self.L.srt_read_mesh_image(self._h, nodes.ctypes.data_as(C.c_void_p), tris.ctypes.data_as(C.c_void_p)))
+        return nodes, tris
 
     def set_meshes(self, meshes, count=None):
         """EXTENSION: geometry for SRT_OBJ_MESH objects; call before set_scene."""

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -24,6 +25,7 @@
 #include "srt_antialias.hip.h"
 #include "srt_variance.hip.h"
 #include "srt_moments.hip.h"
+#include "srt_refit.hip.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -171,6 +173,23 @@ struct srt_context {
     DeviceBuffer<float4> d_bvh_nodes;
     DeviceBuffer<float4> d_bvh_tris;
     DeviceBuffer<int32_t> d_bvh_gidpos;
+
+    // refitting the mesh image (srt_update_mode, srt_refit.hip.h): the mode, what the last successful srt_update_scene did, and the
+    // refit data — every mesh's vertices, the triangles' vertex indices, the exact boxes of triangles and nodes, the objects'
+    // positions — which is on the device only for a mesh image built while the mode was SRT_UPDATE_REFIT (refit_ready) and is
+    // out of date once srt_set_meshes has replaced the geometry (meshes_stale, until the next build).  The staging vectors are
+    // rewritten only behind the stream synchronisation every scene change starts with.
+    int update_mode = SRT_UPDATE_REBUILD;
+    srt_update_info update_info{};
+    bool refit_ready = false;
+    bool meshes_stale = false;
+    DeviceBuffer<float4> d_refit_verts;
+    DeviceBuffer<uint32_t> d_refit_tri_verts;
+    DeviceBuffer<float4> d_refit_tri_box;
+    DeviceBuffer<float4> d_refit_node_box;
+    DeviceBuffer<float4> d_refit_pos;
+    std::vector<float4> h_refit_verts;
+    std::vector<float4> h_refit_pos;
 
     // sample-chunked launches (narrow row bands at high sample counts): sample colours + per-tile masks
     DeviceBuffer<float4> d_samples;
@@ -466,7 +485,101 @@ int srt_destroy(srt_context* ctx) {
     return SRT_OK;
 }
 
-static int set_scene_impl(srt_context* ctx, const char* fn, const srt_object* objects, size_t count) {
+// what a scene change does to the mesh image (srt_update_info.path)
+enum { MESH_REBUILD = 1, MESH_REFIT = 2, MESH_KEEP = 3 };
+
+// the mesh image's root as the host derives it for a refit (srt::refit_root)
+struct RefitRoot {
+    float center[3], half[3], bs_radius;
+};
+
+// The refit data of the mesh image just built, uploaded behind it (only while the mode is SRT_UPDATE_REFIT).
+static int upload_refit_data(srt_context* ctx, size_t count) {
+    const srt::MeshImage& I = ctx->mesh_image;
+    ctx->h_refit_verts = srt::refit_vertices(ctx->meshes);
+    SRT_HIP(ctx, ctx->d_refit_verts.ensure(std::max<size_t>(ctx->h_refit_verts.size(), 1) * sizeof(float4)));
+    SRT_HIP(ctx, ctx->d_refit_tri_verts.ensure(I.tri_verts.size() * sizeof(uint32_t)));
+    SRT_HIP(ctx, ctx->d_refit_tri_box.ensure((size_t)I.n_tris * 2 * sizeof(float4)));
+    SRT_HIP(ctx, ctx->d_refit_node_box.ensure((size_t)I.n_nodes * 2 * sizeof(float4)));
+    SRT_HIP(ctx, ctx->d_refit_pos.ensure(std::max<size_t>(count, 1) * sizeof(float4)));
+    if (!ctx->h_refit_verts.empty())
+        SRT_HIP(ctx, hipMemcpyAsync(ctx->d_refit_verts, ctx->h_refit_verts.data(), ctx->h_refit_verts.size() * sizeof(float4),
+                                    hipMemcpyHostToDevice, ctx->stream));
+    SRT_HIP(ctx, hipMemcpyAsync(ctx->d_refit_tri_verts, I.tri_verts.data(), I.tri_verts.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                ctx->stream));
+    ctx->refit_ready = true;
+    return SRT_OK;
+}
+
+// The refit itself: the positions, then the triangle kernel and one level kernel per level of the tree, deepest first, all on the
+// launch stream.  Nothing is read back; the root box comes from the host (root).
+static int enqueue_refit(srt_context* ctx, const srt_object* objects, size_t count, const RefitRoot& root) {
+    srt::MeshImage& I = ctx->mesh_image;
+    ctx->h_refit_pos.resize(count);
+    for (size_t i = 0; i < count; ++i) ctx->h_refit_pos[i] = make_float4(objects[i].position[0], objects[i].position[1], objects[i].position[2], 0.0f);
+    SRT_HIP(ctx, hipMemcpyAsync(ctx->d_refit_pos, ctx->h_refit_pos.data(), count * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    srt::RefitLaunch R{};
+    R.tris = ctx->d_bvh_tris, R.nodes = ctx->d_bvh_nodes;
+    R.tri_verts = ctx->d_refit_tri_verts, R.verts = ctx->d_refit_verts, R.positions = ctx->d_refit_pos;
+    R.tri_box = ctx->d_refit_tri_box, R.node_box = ctx->d_refit_node_box;
+    R.n_tris = (uint32_t)I.n_tris, R.n_nodes = (uint32_t)I.n_nodes;
+    hipLaunchKernelGGL(srt::refit_triangles_kernel, dim3((R.n_tris + srt::REFIT_THREADS - 1) / srt::REFIT_THREADS), dim3(srt::REFIT_THREADS), 0,
+                       ctx->stream, R);
+    SRT_HIP(ctx, hipGetLastError());
+    for (size_t l = I.level_first.size(); l-- > 0;) {
+        R.level_first = (uint32_t)I.level_first[l];
+        R.level_nodes = (uint32_t)(l + 1 < I.level_first.size() ? I.level_first[l + 1] : I.n_nodes) - R.level_first;
+        hipLaunchKernelGGL(srt::refit_level_kernel, dim3((8 * R.level_nodes + srt::REFIT_THREADS - 1) / srt::REFIT_THREADS),
+                           dim3(srt::REFIT_THREADS), 0, ctx->stream, R);
+        SRT_HIP(ctx, hipGetLastError());
+    }
+    for (int ax = 0; ax < 3; ++ax) I.center[ax] = root.center[ax], I.half[ax] = root.half[ax];
+    I.bs_radius = root.bs_radius;
+    return SRT_OK;
+}
+
+// EXTENSION: flatten mesh objects into a world-space triangle list + BVH (HBM resident).  The size limits
+// of the device encoding (24-bit triangle ids, 26-bit node ids) are checked BEFORE the build and the uploads.
+static int rebuild_mesh_image(srt_context* ctx, const char* fn, const srt_object* objects, size_t count) {
+    ctx->refit_ready = false;
+    {
+        unsigned long long total_tris = 0;
+        for (size_t i = 0; i < count; ++i)
+            if (objects[i].type == SRT_OBJ_MESH) total_tris += ctx->meshes[(size_t)objects[i].mesh].indices.size() / 3;
+        if (total_tris >= (1ull << 24))
+            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: %llu mesh triangles exceed the limit of 2^24 - 1 per scene", fn, total_tris);
+    }
+    srt::build_mesh_image(objects, count, ctx->meshes, ctx->layout[0].nsT + ctx->layout[0].nb, ctx->mesh_image);
+    // (allocated to size for every scene, not grown)
+    ctx->d_bvh_nodes.reset();
+    ctx->d_bvh_tris.reset();
+    ctx->d_bvh_gidpos.reset();
+    ctx->d_refit_verts.reset(), ctx->d_refit_tri_verts.reset(), ctx->d_refit_tri_box.reset(), ctx->d_refit_node_box.reset(), ctx->d_refit_pos.reset();
+    ctx->meshes_stale = false;
+    if (ctx->mesh_image.n_tris > 0) {
+        // strict depth-first traversal (the kernel's last resort) keeps at most 7 entries per level
+        if (7 * ctx->mesh_image.max_depth + 80 > srt::MESH_Q)
+            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: BVH too deep (%d levels)", fn, ctx->mesh_image.max_depth);
+        if (ctx->mesh_image.n_nodes >= (1 << 26) || ctx->mesh_image.n_tris >= (1 << 24))  // (item encoding of the traversal queues)
+            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: mesh too large (%d triangles)", fn, ctx->mesh_image.n_tris);
+        for (int ax = 0; ax < 3; ++ax)  // keeps cell * slope finite in the kernel's plane distances
+            if (!(fabsf(ctx->mesh_image.center[ax]) + ctx->mesh_image.half[ax] <= 1e9f))
+                return fail(ctx, SRT_ERR_INVALID_ARG, "%s: mesh coordinates beyond 1e9 are not supported", fn);
+        SRT_HIP(ctx, ctx->d_bvh_nodes.ensure(ctx->mesh_image.nodes.size() * sizeof(float4)));
+        SRT_HIP(ctx, ctx->d_bvh_tris.ensure(ctx->mesh_image.tris.size() * sizeof(float4)));
+        SRT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh_nodes, ctx->mesh_image.nodes.data(), ctx->mesh_image.nodes.size() * sizeof(float4),
+                                    hipMemcpyHostToDevice, ctx->stream));
+        SRT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh_tris, ctx->mesh_image.tris.data(), ctx->mesh_image.tris.size() * sizeof(float4),
+                                    hipMemcpyHostToDevice, ctx->stream));
+        SRT_HIP(ctx, ctx->d_bvh_gidpos.ensure(ctx->mesh_image.gidpos.size() * sizeof(int32_t)));
+        SRT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh_gidpos, ctx->mesh_image.gidpos.data(), ctx->mesh_image.gidpos.size() * sizeof(int32_t),
+                                    hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (ctx->update_mode == SRT_UPDATE_REFIT && ctx->mesh_image.n_tris > 0) return upload_refit_data(ctx, count);
+    return SRT_OK;
+}
+
+static int set_scene_impl(srt_context* ctx, const char* fn, const srt_object* objects, size_t count, int mesh_path, const RefitRoot* root) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
     if (count && !objects) return fail(ctx, SRT_ERR_INVALID_ARG, "%s: objects is NULL", fn);
     if (count > 0x3fffffff) return fail(ctx, SRT_ERR_INVALID_ARG, "%s: too many objects", fn);
@@ -509,38 +622,11 @@ static int set_scene_impl(srt_context* ctx, const char* fn, const srt_object* ob
                                     hipMemcpyHostToDevice, ctx->stream));
         ctx->layout[v] = L;
     }
-    // EXTENSION: flatten mesh objects into a world-space triangle list + BVH (HBM resident).  The size limits
-    // of the device encoding (24-bit triangle ids, 26-bit node ids) are checked BEFORE the build and the uploads.
-    {
-        unsigned long long total_tris = 0;
-        for (size_t i = 0; i < count; ++i)
-            if (objects[i].type == SRT_OBJ_MESH) total_tris += ctx->meshes[(size_t)objects[i].mesh].indices.size() / 3;
-        if (total_tris >= (1ull << 24))
-            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: %llu mesh triangles exceed the limit of 2^24 - 1 per scene", fn, total_tris);
-    }
-    srt::build_mesh_image(objects, count, ctx->meshes, ctx->layout[0].nsT + ctx->layout[0].nb, ctx->mesh_image);
-    // (allocated to size for every scene, not grown)
-    ctx->d_bvh_nodes.reset();
-    ctx->d_bvh_tris.reset();
-    ctx->d_bvh_gidpos.reset();
-    if (ctx->mesh_image.n_tris > 0) {
-        // strict depth-first traversal (the kernel's last resort) keeps at most 7 entries per level
-        if (7 * ctx->mesh_image.max_depth + 80 > srt::MESH_Q)
-            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: BVH too deep (%d levels)", fn, ctx->mesh_image.max_depth);
-        if (ctx->mesh_image.n_nodes >= (1 << 26) || ctx->mesh_image.n_tris >= (1 << 24))  // (item encoding of the traversal queues)
-            return fail(ctx, SRT_ERR_INVALID_ARG, "%s: mesh too large (%d triangles)", fn, ctx->mesh_image.n_tris);
-        for (int ax = 0; ax < 3; ++ax)  // keeps cell * slope finite in the kernel's plane distances
-            if (!(fabsf(ctx->mesh_image.center[ax]) + ctx->mesh_image.half[ax] <= 1e9f))
-                return fail(ctx, SRT_ERR_INVALID_ARG, "%s: mesh coordinates beyond 1e9 are not supported", fn);
-        SRT_HIP(ctx, ctx->d_bvh_nodes.ensure(ctx->mesh_image.nodes.size() * sizeof(float4)));
-        SRT_HIP(ctx, ctx->d_bvh_tris.ensure(ctx->mesh_image.tris.size() * sizeof(float4)));
-        SRT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh_nodes, ctx->mesh_image.nodes.data(), ctx->mesh_image.nodes.size() * sizeof(float4),
-                                    hipMemcpyHostToDevice, ctx->stream));
-        SRT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh_tris, ctx->mesh_image.tris.data(), ctx->mesh_image.tris.size() * sizeof(float4),
-                                    hipMemcpyHostToDevice, ctx->stream));
-        SRT_HIP(ctx, ctx->d_bvh_gidpos.ensure(ctx->mesh_image.gidpos.size() * sizeof(int32_t)));
-        SRT_HIP(ctx, hipMemcpyAsync(ctx->d_bvh_gidpos, ctx->mesh_image.gidpos.data(), ctx->mesh_image.gidpos.size() * sizeof(int32_t),
-                                    hipMemcpyHostToDevice, ctx->stream));
+    // an update that only moved objects (srt_update_scene under SRT_UPDATE_REFIT) keeps the mesh image or refits it in place
+    if (mesh_path == MESH_REFIT) {
+        if (const int rc = enqueue_refit(ctx, objects, count, *root)) return rc;
+    } else if (mesh_path == MESH_REBUILD) {
+        if (const int rc = rebuild_mesh_image(ctx, fn, objects, count)) return rc;
     }
     ctx->objects.assign(objects, objects + count);
     ctx->scene_set = true;
@@ -555,10 +641,11 @@ static int set_scene_impl(srt_context* ctx, const char* fn, const srt_object* ob
 }
 
 // Host-side allocation failures (std::bad_alloc from the image / BVH builders) must not cross the C boundary.
-static int set_scene_guarded(srt_context* ctx, const char* fn, const srt_object* objects, size_t count) {
+static int set_scene_guarded(srt_context* ctx, const char* fn, const srt_object* objects, size_t count, int mesh_path = MESH_REBUILD,
+                             const RefitRoot* root = nullptr) {
     if (ctx) ++ctx->scene_changes;  // the handle's own sub-samples belong to the old scene
     try {
-        return set_scene_impl(ctx, fn, objects, count);
+        return set_scene_impl(ctx, fn, objects, count, mesh_path, root);
     } catch (const std::bad_alloc&) {
         if (ctx) ctx->scene_set = false;
         return fail(ctx, SRT_ERR_OOM, "%s: host allocation failed", fn);
@@ -566,6 +653,44 @@ static int set_scene_guarded(srt_context* ctx, const char* fn, const srt_object*
         if (ctx) ctx->scene_set = false;
         return fail(ctx, SRT_ERR_INVALID_ARG, "%s: %s", fn, e.what());
     }
+}
+
+// What srt_update_scene does to the mesh image (info.path, info.reason; for a refit also the root the host derives).  Pure host
+// work on the old and the new list; the one failure, a refit beyond the coordinate limit, is found here, before anything is
+// touched or enqueued.
+static int choose_update_path(srt_context* ctx, const srt_object* objects, size_t count, srt_update_info& info, RefitRoot& root) {
+    info = srt_update_info{};
+    info.path = MESH_REBUILD;
+    if (count && !objects) return SRT_OK;  // (refused by the common validation)
+    const srt::MeshImage& I = ctx->mesh_image;
+    bool same_but_position = true, finite = true, dropped = false;
+    for (size_t i = 0; i < count; ++i) {
+        const srt_object &a = ctx->objects[i], &b = objects[i];
+        constexpr size_t after = offsetof(srt_object, position) + sizeof(a.position);
+        if (a.type != b.type || memcmp((const char*)&a + after, (const char*)&b + after, sizeof(srt_object) - after) != 0) same_but_position = false;
+        if (a.type != SRT_OBJ_MESH || b.type != SRT_OBJ_MESH) continue;
+        for (int ax = 0; ax < 3; ++ax) finite = finite && std::isfinite(a.position[ax]) && std::isfinite(b.position[ax]);
+        if (memcmp(a.position, b.position, sizeof(a.position)) != 0) {
+            ++info.moved_mesh_objects;
+            if (b.mesh >= 0 && (size_t)b.mesh < I.mesh_dropped.size() && I.mesh_dropped[(size_t)b.mesh]) dropped = true;
+        }
+    }
+    if (ctx->update_mode != SRT_UPDATE_REFIT) return info.reason = 1, SRT_OK;
+    if (!same_but_position) return info.reason = 2, SRT_OK;
+    if (ctx->meshes_stale) return info.reason = 4, SRT_OK;  // (srt_set_meshes since the build: the image is of other geometry)
+    if (info.moved_mesh_objects == 0 || I.n_tris == 0) return info.path = MESH_KEEP, SRT_OK;
+    if (!ctx->refit_ready) return info.reason = 4, SRT_OK;
+    if (!finite || dropped) return info.reason = 3, SRT_OK;
+    float lo[3], hi[3];
+    if (!srt::refit_root(I, objects, lo, hi, root.center, root.half, root.bs_radius)) return info.reason = 3, SRT_OK;
+    for (int ax = 0; ax < 3; ++ax)  // (the limit srt_set_scene applies)
+        if (!(fabsf(root.center[ax]) + root.half[ax] <= 1e9f))
+            return fail(ctx, SRT_ERR_INVALID_ARG, "srt_update_scene: mesh coordinates beyond 1e9 are not supported");
+    info.path = MESH_REFIT;
+    info.levels = (int32_t)I.level_first.size();
+    info.triangles = (uint32_t)I.n_tris;
+    info.nodes = (uint32_t)I.n_nodes;
+    return SRT_OK;
 }
 
 int srt_set_scene(srt_context* ctx, const srt_object* objects, size_t count) {
@@ -581,9 +706,46 @@ int srt_update_scene(srt_context* ctx, const srt_object* objects, size_t count) 
     if (count != ctx->objects.size())
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_update_scene: %zu objects, the scene has %zu (a list of another length goes through srt_set_scene)",
                     count, ctx->objects.size());
-    const int rc = set_scene_guarded(ctx, "srt_update_scene", objects, count);
+    srt_update_info info{};
+    RefitRoot root{};
+    if (const int rc = choose_update_path(ctx, objects, count, info, root)) return rc;  // (nothing touched: the previous scene stands)
+    const int rc = set_scene_guarded(ctx, "srt_update_scene", objects, count, info.path, &root);
     if (!ctx->scene_set) ctx->tp_valid = false;  // the refused list left no scene: nothing for the history to belong to
+    if (rc == SRT_OK) ctx->update_info = info;
     return rc;
+}
+
+int srt_update_mode(srt_context* ctx, int mode) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    if (mode != SRT_UPDATE_REBUILD && mode != SRT_UPDATE_REFIT) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_update_mode: unknown mode %d", mode);
+    ctx->update_mode = mode;
+    return SRT_OK;
+}
+
+int srt_get_update_info(srt_context* ctx, srt_update_info* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    *out = ctx->update_info;
+    return SRT_OK;
+}
+
+int srt_mesh_image_size(srt_context* ctx, size_t* node_bytes, size_t* triangle_bytes) {
+    if (!ctx || !node_bytes || !triangle_bytes) return SRT_ERR_INVALID_ARG;
+    if (!ctx->scene_set) return fail(ctx, SRT_ERR_STATE, "srt_mesh_image_size: srt_set_scene has not been called");
+    const bool any = ctx->mesh_image.n_tris > 0;
+    *node_bytes = any ? (size_t)ctx->mesh_image.n_nodes * srt::NODE_VEC4 * sizeof(float4) : 0;
+    *triangle_bytes = any ? (size_t)ctx->mesh_image.n_tris * 3 * sizeof(float4) : 0;
+    return SRT_OK;
+}
+
+int srt_read_mesh_image(srt_context* ctx, void* nodes, void* triangles) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    size_t nb = 0, tb = 0;
+    if (const int rc = srt_mesh_image_size(ctx, &nb, &tb)) return rc;
+    if ((nb && !nodes) || (tb && !triangles)) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_mesh_image: NULL destination");
+    if (const int rc = finish_stream(ctx)) return rc;
+    if (nb) SRT_HIP(ctx, hipMemcpy(nodes, ctx->d_bvh_nodes, nb, hipMemcpyDeviceToHost));
+    if (tb) SRT_HIP(ctx, hipMemcpy(triangles, ctx->d_bvh_tris, tb, hipMemcpyDeviceToHost));
+    return SRT_OK;
 }
 
 static int set_meshes_impl(srt_context* ctx, const srt_mesh* meshes, size_t count) {
@@ -604,7 +766,7 @@ static int set_meshes_impl(srt_context* ctx, const srt_mesh* meshes, size_t coun
 }
 
 int srt_set_meshes(srt_context* ctx, const srt_mesh* meshes, size_t count) {
-    if (ctx) ctx->tp_valid = false, ++ctx->scene_changes;
+    if (ctx) ctx->tp_valid = false, ++ctx->scene_changes, ctx->meshes_stale = true;
     try {
         return set_meshes_impl(ctx, meshes, count);
     } catch (const std::bad_alloc&) {

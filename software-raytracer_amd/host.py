@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .capi import (DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, DenoiseParams, Mesh, Object, Stats,
+from .capi import (DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
                    TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -28,6 +28,7 @@ EXPORTS = [
     "srt_host_renderer_move_camera",
     "srt_host_renderer_update_scene", "srt_host_renderer_motion_output", "srt_host_renderer_read_motion",
     "srt_host_renderer_upsample", "srt_host_renderer_read_upsampled", "srt_host_renderer_guided_upsample",
+    "srt_host_renderer_refit_updates", "srt_host_renderer_update_info",
     "srt_host_renderer_antialias", "srt_host_renderer_read_antialiased", "srt_host_renderer_set_antialias",
     "srt_host_renderer_denoise_variance", "srt_host_renderer_read_variance",
     "srt_host_renderer_temporal_variance", "srt_host_renderer_read_moments",
@@ -120,6 +121,8 @@ def load_library():
     L.srt_host_renderer_upsample.argtypes = [vp, C.POINTER(UpsampleParams)]
     L.srt_host_renderer_read_upsampled.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_guided_upsample.argtypes = [vp, C.c_int]
+    L.srt_host_renderer_refit_updates.argtypes = [vp, C.c_int]
+    L.srt_host_renderer_update_info.argtypes = [vp, C.POINTER(UpdateInfo)]
     L.srt_host_renderer_antialias.argtypes = [vp, C.POINTER(AntialiasParams)]
     L.srt_host_renderer_read_antialiased.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_set_antialias.argtypes = [vp, C.c_int]
@@ -403,6 +406,17 @@ class Renderer:
         """PathTraceRenderer::guidedUpsample: render_frame() follows every frame of blocks with the guides and the upsampler
         into the framebuffer."""
         self._ck(self.L.srt_host_renderer_guided_upsample(self._h, 1 if on else 0))
+
+    def refit_updates(self, on=True):
+        """PathTraceRenderer::refitUpdates: set_scene() and update_scene() run under SRT_UPDATE_REFIT, so an update that only
+        moves objects refits the mesh BVH on the device.  Read when a scene is set or updated."""
+        self._ck(self.L.srt_host_renderer_refit_updates(self._h, 1 if on else 0))
+
+    def update_info(self):
+        """PathTraceRenderer::UpdateInfo: what the last update_scene() did to the mesh BVH, as capi.UpdateInfo's dict."""
+        u = UpdateInfo()
+        self._ck(self.L.srt_host_renderer_update_info(self._h, C.byref(u)))
+        return u.as_dict()
 
     def antialias(self, k=None, denoised=False, framebuffer=False):
         """PathTraceRenderer::Antialias: the OBJECT guide and the k x k sub-samples when they are stale, then srt_antialias

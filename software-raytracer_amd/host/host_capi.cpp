@@ -232,6 +232,12 @@ int srt_host_renderer_move_camera(srt_host_renderer* h, const float* pos, const 
 }
 // an object edit that keeps the temporal history (srt_update_scene), and the motion-vector output (srt_motion_output / srt_read_motion)
 int srt_host_renderer_update_scene(srt_host_renderer* h, srt_host_scene* s) { SRT_HOST_TRY(h, h->r->UpdateScene(s->scene)) }
+// the refitUpdates setting of SetScene / UpdateScene (srt_update_mode) and what the last update did (srt_get_update_info)
+int srt_host_renderer_refit_updates(srt_host_renderer* h, int on) {
+    h->r->refitUpdates = on != 0;
+    return 0;
+}
+int srt_host_renderer_update_info(srt_host_renderer* h, srt_update_info* out) { SRT_HOST_TRY(h, *out = h->r->UpdateInfo()) }
 int srt_host_renderer_motion_output(srt_host_renderer* h, int on) { SRT_HOST_TRY(h, h->r->MotionOutput(on != 0)) }
 int srt_host_renderer_read_motion(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadMotion(dst)) }
 // guided upsampler over the whole frame with the guides as they stand (srt_upsample / srt_read_upsampled), and the

@@ -28,6 +28,7 @@ void PathTraceRenderer::SetScene(const Scene& scene) {
     std::vector<srt_object> flat = scene.Flatten();
     std::vector<srt_mesh> meshes = scene.MeshViews();  // EXTENSION: geometry of "Mesh" renderers
     check(srt_set_meshes(ctx_, meshes.data(), meshes.size()), "srt_set_meshes");
+    check(srt_update_mode(ctx_, refitUpdates ? SRT_UPDATE_REFIT : SRT_UPDATE_REBUILD), "srt_update_mode");
     scene_set_ = false;
     aa_k_ = 0;
     check(srt_set_scene(ctx_, flat.data(), flat.size()), "srt_set_scene");
@@ -61,6 +62,7 @@ void PathTraceRenderer::UpdateScene(const Scene& scene) {
         return;
     }
     aa_k_ = 0;
+    check(srt_update_mode(ctx_, refitUpdates ? SRT_UPDATE_REFIT : SRT_UPDATE_REBUILD), "srt_update_mode");
     const int rc = srt_update_scene(ctx_, flat.data(), flat.size());
     if (rc != SRT_OK) {
         // a refused list may have left the context without a scene: start afresh (the next edit goes through SetScene)
@@ -69,6 +71,12 @@ void PathTraceRenderer::UpdateScene(const Scene& scene) {
     }
     check(rc, "srt_update_scene");
     doSetFrame_ = true;
+}
+
+srt_update_info PathTraceRenderer::UpdateInfo() {
+    srt_update_info info{};
+    check(srt_get_update_info(ctx_, &info), "srt_get_update_info");
+    return info;
 }
 
 void PathTraceRenderer::SetEnvironment(const srt_environment& env) {

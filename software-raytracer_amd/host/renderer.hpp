@@ -77,6 +77,10 @@ class PathTraceRenderer {
     // SRT_VARIANCE_ALBEDO) and, when it denoises, runs srt_temporal_variance + srt_denoise_variance at the library's defaults
     // where it otherwise runs srt_denoise: the per-pixel variance of a temporal frame at one render per frame.
     bool temporalVariance = false;
+    // not in the reference: SetScene and UpdateScene run under SRT_UPDATE_REFIT (srt_update_mode), so an UpdateScene that only
+    // moves objects refits the mesh BVH on the device instead of rebuilding it on the host.  Same pictures; read when a scene
+    // is set or updated, so a scene set before it was switched on rebuilds once more.
+    bool refitUpdates = false;
     Transform camera;   // :295-297
 
     PathTraceRenderer(int device, int width, int height);
@@ -96,6 +100,8 @@ class PathTraceRenderer {
     // scene was set, the number of objects changed or the geometry of a mesh changed (srt_update_scene keeps the meshes of
     // the last srt_set_meshes).
     void UpdateScene(const Scene& scene);
+    // what the last UpdateScene that reached srt_update_scene did to the mesh image (srt_get_update_info)
+    srt_update_info UpdateInfo();
     void SetEnvironment(const srt_environment& env);
     // restrict rendering to memory rows [begin,end) (multi-GPU row stripes)
     void SetRowBand(int begin, int end);

@@ -65,7 +65,7 @@ static void usage() {
                  "usage: srt_render --scene FILE [--width 1280] [--height 720] [--spp 32] [--bounces 2]\n"
                  "                  [--fov 55] [--seed 0] [--device 0 | --devices 0,1,2,...] [--out frame.ppm] [--resave FILE]\n"
                  "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]\n"
-                 "                  [--move-object IDX:DX,DY,DZ]...] [--steps N] [--upsample PATH] [--aa K]\n"
+                 "                  [--move-object IDX:DX,DY,DZ]... [--refit]] [--steps N] [--upsample PATH] [--aa K]\n"
                  "                  [--denoise-variance PATH] [--temporal-variance]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
@@ -93,6 +93,8 @@ static void usage() {
                  "             up and forward axes (--move) and turns by DEG degrees about world up (--turn); single device only\n"
                  "  --move-object: with --temporal, before every frame but the first add DX, DY, DZ to the position of object IDX\n"
                  "             (list order) and keep the history across the edit (srt_update_scene); may be given several times\n"
+                 "  --refit:   with --move-object, refit the mesh BVH on the device after every edit instead of rebuilding it on the\n"
+                 "             host (srt_update_mode); the same frames; what every update did is printed\n"
                  "  --temporal-variance: with --temporal, also keep the luminance moments of the history (srt_moments_output) and\n"
                  "             filter the --denoise frame by the per-pixel variance they give (srt_temporal_variance,\n"
                  "             srt_denoise_variance, the library's defaults) instead of srt_denoise; not with --steps, --upsample or\n"
@@ -102,7 +104,7 @@ static void usage() {
 int main(int argc, char** argv) {
     std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise, upsample, denoise_variance;
     int temporal = 0, steps = 1, aa = 0;
-    bool aa_given = false, temporal_variance = false;
+    bool aa_given = false, temporal_variance = false, refit = false;
     float move[3] = {0, 0, 0}, turn_deg = 0;
     struct ObjectMove {
         size_t index;
@@ -147,6 +149,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--upsample")) upsample = need("--upsample");
         else if (!std::strcmp(argv[i], "--aa")) aa = std::atoi(need("--aa")), aa_given = true;
         else if (!std::strcmp(argv[i], "--temporal-variance")) temporal_variance = true;
+        else if (!std::strcmp(argv[i], "--refit")) refit = true;
         else if (!std::strcmp(argv[i], "--temporal")) temporal = std::atoi(need("--temporal"));
         else if (!std::strcmp(argv[i], "--turn")) turn_deg = std::strtof(need("--turn"), nullptr);
         else if (!std::strcmp(argv[i], "--move")) {
@@ -185,6 +188,10 @@ int main(int argc, char** argv) {
     }
     if (!object_moves.empty() && !temporal) {
         std::fprintf(stderr, "--move-object needs --temporal\n");
+        return 2;
+    }
+    if (refit && object_moves.empty()) {
+        std::fprintf(stderr, "--refit needs --move-object\n");
         return 2;
     }
     if (scene_path.empty() || W <= 0 || H <= 0 || spp <= 0 || temporal < 0 || steps < 1) {
@@ -284,6 +291,7 @@ int main(int argc, char** argv) {
         r.FOV = fov;
         r.MAXBOUNCES = bounces;
         r.seed = seed;
+        r.refitUpdates = refit;
         r.SetScene(scene);
         // --aa: the stage's result resolved into the framebuffer before it is read (the sub-samples are traced once per camera)
         auto resolve = [&](int source) {
@@ -309,6 +317,11 @@ int main(int argc, char** argv) {
                         for (int a = 0; a < 3; ++a) pos[a] = pos[a] + m.step[a];
                     }
                     if (!object_moves.empty()) r.UpdateScene(scene);
+                    if (refit) {
+                        const srt_update_info u = r.UpdateInfo();
+                        std::fprintf(stderr, "temporal frame %d update path %d reason %d levels %d triangles %u nodes %u\n", k, u.path, u.reason, u.levels,
+                                     u.triangles, u.nodes);
+                    }
                 }
                 for (const auto& m : object_moves) {
                     const float* pos = scene.GetObjects()[m.index].position;

@@ -45,6 +45,9 @@
 //      frame then also keeps the luminance moments of its history and is shown through the variance-guided filter on the
 //      variance they give (srt_temporal_variance, srt_denoise_variance), still at one sample per frame; the colour history
 //      is untouched, so the toggle raises nothing (the moments start afresh)
+//   H  refit (not in the reference; PathTraceRenderer::refitUpdates): an object move refits the mesh BVH on the device
+//      (srt_update_mode) instead of rebuilding it on the host; the pictures are the same, so the toggle raises nothing.  The
+//      status line (script command `update`, the window's title) names what the last move did: rebuilt, refitted or kept
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -72,7 +75,7 @@ struct InputState {  // one frame's worth, what SDLInputManager hands the loop
     int mouse_dx = 0, mouse_dy = 0;  // relative motion of this frame
     bool left_down = false;          // edge
     int mouse_x = 0, mouse_y = 0;    // window coordinates of the click, y down
-    std::string pressed;             // key-down edges of this frame: any of "PMFGBN1234XTRCVY" (X = DELETE)
+    std::string pressed;             // key-down edges of this frame: any of "PMFGBN1234XTRCVYH" (X = DELETE)
 };
 
 class ViewerCore {
@@ -88,6 +91,15 @@ class ViewerCore {
     bool variance() const { return variance_; }
     int selected() const { return r_.selectedObject; }
     const Scene& scene() const { return scene_; }
+    // the status line: refit mode and what the last object move did to the mesh BVH
+    std::string UpdateStatus() {
+        static const char* const names[] = {"none", "rebuilt", "refitted", "kept"};
+        const srt_update_info u = r_.UpdateInfo();
+        char text[160];
+        std::snprintf(text, sizeof text, "update refit %s path %s reason %d levels %d triangles %u nodes %u moved %u", r_.refitUpdates ? "on" : "off",
+                      names[u.path >= 0 && u.path <= 3 ? u.path : 0], u.reason, u.levels, u.triangles, u.nodes, u.moved_mesh_objects);
+        return text;
+    }
 
     // one pass of the loop body between "thread safe after this point" (:385) and the release of the
     // workers (:592-595); delta in seconds (:558-560)
@@ -143,6 +155,7 @@ class ViewerCore {
             case 'C': r_.antialias = r_.antialias ? 0 : 2; break;
             case 'V': variance_ = !variance_; r_.Invalidate(); break;
             case 'Y': r_.temporalVariance = !r_.temporalVariance; break;
+            case 'H': r_.refitUpdates = !r_.refitUpdates; break;
             case 'M': r_.SIMPLEDRAW = !r_.SIMPLEDRAW; r_.Invalidate(); break;      // :462-465
             case 'F': case 'G': {                                                  // :468-473
                 int f = r_.FOV + (k == 'G' ? 1 : -1);
@@ -190,7 +203,8 @@ void write_ppm(PathTraceRenderer& r, const std::string& path) {
 // Script of the headless back end, one command per line ('#' starts a comment):
 //   delta SECONDS | hold KEYS | release KEYS   (KEYS out of W A S D E Q and L for LSHIFT; the object-move keys in lower case,
 //     i k j l u o, because the upper-case L is taken)
-//   press KEYS (P M F G B N 1 2 3 4 X T R C V Y, applied to the next frame only)
+//   press KEYS (P M F G B N 1 2 3 4 X T R C V Y H, applied to the next frame only)
+//   update (the status line: refit mode and what the last object move did to the mesh BVH)
 //   upsample on|off (guided upsampling of block frames, what the R key toggles)
 //   antialias K|off (anti-aliasing with K x K sub-samples, K in 1..4; the C key toggles K = 2)
 //   rmb down|up | move DX DY (relative mouse motion of the next frame) | click X Y
@@ -224,6 +238,7 @@ int run_script(ViewerCore& core, std::istream& script) {
         if (cmd == "delta") ss >> delta;
         else if (cmd == "hold" || cmd == "release") { std::string k; ss >> k; set_keys(k, cmd == "hold"); }
         else if (cmd == "press") { std::string k; ss >> k; in.pressed += k; }
+        else if (cmd == "update") std::printf("%s\n", core.UpdateStatus().c_str());
         else if (cmd == "upsample") { std::string v; ss >> v; core.renderer().guidedUpsample = v == "on"; }
         else if (cmd == "antialias") {
             std::string v;
@@ -301,7 +316,7 @@ int run_window(ViewerCore& core) {
                     case SDL_SCANCODE_B: in.pressed += 'B'; break; case SDL_SCANCODE_N: in.pressed += 'N'; break;
                     case SDL_SCANCODE_1: in.pressed += '1'; break; case SDL_SCANCODE_2: in.pressed += '2'; break;
                     case SDL_SCANCODE_3: in.pressed += '3'; break; case SDL_SCANCODE_4: in.pressed += '4'; break;
-                    case SDL_SCANCODE_DELETE: in.pressed += 'X'; break; case SDL_SCANCODE_T: in.pressed += 'T'; break; case SDL_SCANCODE_R: in.pressed += 'R'; break; case SDL_SCANCODE_C: in.pressed += 'C'; break; case SDL_SCANCODE_V: in.pressed += 'V'; break; case SDL_SCANCODE_Y: in.pressed += 'Y'; break; case SDL_SCANCODE_ESCAPE: quit = true; break;
+                    case SDL_SCANCODE_DELETE: in.pressed += 'X'; break; case SDL_SCANCODE_T: in.pressed += 'T'; break; case SDL_SCANCODE_R: in.pressed += 'R'; break; case SDL_SCANCODE_C: in.pressed += 'C'; break; case SDL_SCANCODE_V: in.pressed += 'V'; break; case SDL_SCANCODE_Y: in.pressed += 'Y'; break; case SDL_SCANCODE_H: in.pressed += 'H'; break; case SDL_SCANCODE_ESCAPE: quit = true; break;
                     default: break;
                 }
             }
@@ -314,6 +329,7 @@ int run_window(ViewerCore& core) {
         const Uint32 buttons = SDL_GetRelativeMouseState(&in.mouse_dx, &in.mouse_dy);
         in.right_held = (buttons & SDL_BUTTON(SDL_BUTTON_RIGHT)) != 0;
         core.Frame(in, delta);
+        SDL_SetWindowTitle(window, core.UpdateStatus().c_str());
         r.Wait();
         SDL_LockSurface(frame);
         r.ReadFramebuffer(frame->pixels, (size_t)frame->pitch);  // the blit (:64,75): ARGB8888, top row first
