@@ -800,6 +800,73 @@ int srt_temporal_variance_params_default(srt_temporal_variance_params* out);
  * rendered.  All are found before anything is touched. */
 int srt_temporal_variance(srt_context* ctx, const srt_temporal_variance_params* params);
 
+/* ---- ray queries: closest hits of caller-supplied rays (ABI 7, backward compatible) ---------------------------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of
+ * them runs what it ran before.
+ *
+ * Every other call traces rays that start at the camera.  srt_trace_rays answers, for N rays (o, d) of the caller's, what
+ * GetClosestObject(o, d) (Raytracer.cpp:123-140) returns against the current scene: the same closest-hit code, scene image,
+ * instantiation (scene in LDS or in memory, with or without the mesh BVH) and tie rule — the earlier entry of the object list
+ * keeps an exact distance tie — as srt_render_gbuffer and srt_pick.  No camera is needed.
+ *
+ * Rays.  A batch is N rays, 1 <= N <= 2^30, in two arrays of N float4:
+ *   origin[i]    = (o.xyz, w ignored): the (point, 1) elements of SRT_GBUF_POSITION can be bound as they stand;
+ *   direction[i] = (d.xyz, w = t_max); t_max is read by the OCCLUDED output only.
+ * srt_write_rays copies host arrays (4 * count floats each) into handle-owned device buffers, which grow on demand, waits like
+ * srt_write_accumulator, and makes them the current rays (a binding made by srt_bind_rays ends).  srt_bind_rays makes caller
+ * DEVICE arrays (e.g. torch tensors' data_ptr) the current rays; it does not wait and copies nothing: the caller keeps the
+ * arrays alive and unchanged until the traces that read them have finished.  NULL, NULL, 0 returns to the handle's own buffers
+ * (the current rays are then the last ones written, none before the first srt_write_rays).  SRT_ERR_INVALID_ARG for a NULL
+ * array or a count outside 1..2^30; the previous rays stay.
+ *
+ * Outputs, N elements each, indexed by ray, one bit each.  The four SRT_GBUF_* bits have the element types and the hit / miss
+ * values of the srt_render_gbuffer table above, and
+ *   SRT_RAYS_OCCLUDED        int32    1 when the ray has a closest hit and rayHit.distance < t_max, else 0
+ *                                     (a binary32 <: t_max = NaN gives 0, t_max = +inf gives 1 on every hit; a miss gives 0).
+ * OCCLUDED is defined on the CLOSEST hit: it is not an any-hit test of the segment, and an intersection that
+ * GetClosestObject does not report does not occlude.
+ * The buffers are the handle's own (allocated on first use, grown when a batch needs more) or the caller's: srt_bind_ray_output
+ * binds ONE output (a single bit) to a DEVICE buffer of at least N elements, NULL = own, under srt_bind_gbuffer's rules (does
+ * not wait, enqueued work keeps its buffer).  They are separate from the G-buffer slots: a trace never touches the G-buffer.
+ * srt_read_ray_output waits, then copies the N elements that the last srt_trace_rays wrote for ONE output, from the buffer
+ * that trace wrote; SRT_ERR_STATE when the last trace did not write that output (or there has been none).
+ *
+ * Directions are used as given.  With SRT_RAYS_NORMALIZE the kernel first replaces d by float3::Normalized(d)
+ * (Common.hpp:159-162): sqrtf((x*x + y*y) + z*z), then three IEEE divisions.  Input domain:
+ *   - unit-length directions (|d.d - 1| <= 1e-6 in binary32, which SRT_RAYS_NORMALIZE provides for every finite non-zero d
+ *     whose squared length neither overflows nor underflows) with finite origins: the bits of GetClosestObject, for analytic
+ *     objects and for meshes (the triangle definition of srt_mesh), the sign of zero included.  Zero and -0.0 components,
+ *     origins inside or exactly on an object and coincident objects are part of this domain.
+ *   - a direction with a NaN component: a miss, as in srt_pick.
+ *   - other finite non-zero directions (not unit length): handled as srt_render handles the ray of a degenerate lerp.  Spheres
+ *     and boxes are tested without the cluster culling, and the result is still exactly GetClosestObject's.  In a scene with
+ *     triangles only unit-length directions are pinned: the BVH's culling distances assume them.
+ *   - an all-zero direction, infinite components, or origins beyond 1e29 are outside what srt_render itself produces; the
+ *     result is some valid output element, not necessarily the reference's.
+ *
+ * srt_trace_rays is asynchronous on the launch stream behind earlier work; srt_wait / srt_poll cover it.  The scene is captured
+ * at enqueue: a trace enqueued after srt_update_scene (rebuilt, refitted or kept) sees the new scene, one enqueued before it the
+ * old.  The rays and the output buffers are those current at enqueue.  Errors, all found before anything is touched:
+ * SRT_ERR_STATE before srt_set_scene and when no rays have been written or bound; SRT_ERR_INVALID_ARG for outputs == 0,
+ * unknown output bits or unknown flags.  The call leaves alone: framebuffer, accumulator, G-buffer, every pass buffer, the
+ * temporal history, what srt_get_stats / srt_get_work_counts report and the launch shape of later renders.  No atomics reach
+ * the outputs: repeated calls give the same bits. */
+#define SRT_RAYS_OCCLUDED 16u
+#define SRT_RAYS_NORMALIZE 1u /* srt_trace_params.flags: normalize every direction first */
+
+typedef struct srt_trace_params {
+    uint32_t outputs; /* SRT_GBUF_* bits and SRT_RAYS_OCCLUDED, at least one */
+    uint32_t flags;   /* 0 or SRT_RAYS_NORMALIZE */
+} srt_trace_params;
+
+/* All five outputs, flags = 0 (pure host, no device needed). */
+int srt_trace_params_default(srt_trace_params* out);
+int srt_write_rays(srt_context* ctx, const float* origins, const float* directions, size_t count);
+int srt_bind_rays(srt_context* ctx, const void* d_origins, const void* d_directions, size_t count);
+int srt_bind_ray_output(srt_context* ctx, uint32_t output, void* d_ptr);
+int srt_trace_rays(srt_context* ctx, const srt_trace_params* params);
+int srt_read_ray_output(srt_context* ctx, uint32_t output, void* dst);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

@@ -37,6 +37,7 @@ from .capi import (  # noqa: F401
     SubsampleParams,
     TemporalParams,
     TemporalVarianceParams,
+    TraceParams,
     UpsampleParams,
     VarianceParams,
     build_native,
@@ -49,6 +50,6 @@ from . import host  # noqa: F401
 
 __all__ = [
     "capi", "host", "PathTracer", "SrtError", "Object", "Material", "Camera", "Environment",
-    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "SubsampleParams", "AntialiasParams", "VarianceParams", "DenoiseVarianceParams", "TemporalVarianceParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
+    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "SubsampleParams", "AntialiasParams", "VarianceParams", "DenoiseVarianceParams", "TemporalVarianceParams", "TraceParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
     "load_library",
 ]

@@ -20,6 +20,11 @@ GBUF_OBJECT, GBUF_NORMAL_DEPTH, GBUF_POSITION, GBUF_ALBEDO, GBUF_ALL = 1, 2, 4, 
 # first-hit buffer names (PathTracer.gbuffer / bind_gbuffer) -> (output bit, numpy dtype, per-pixel channels)
 GBUFFERS = {"object": (GBUF_OBJECT, np.int32, 1), "normal_depth": (GBUF_NORMAL_DEPTH, np.float32, 4),
             "position": (GBUF_POSITION, np.float32, 4), "albedo": (GBUF_ALBEDO, np.float32, 4)}
+# ray queries (srt_trace_rays): the four G-buffer bits plus OCCLUDED, and the one flag
+RAYS_OCCLUDED, RAYS_ALL = 16, 31
+RAYS_NORMALIZE = 1
+# ray output names (PathTracer.ray_output / bind_ray_output) -> (output bit, numpy dtype, per-ray channels)
+RAY_OUTPUTS = dict(GBUFFERS, occluded=(RAYS_OCCLUDED, np.int32, 1))
 DENOISE_ALBEDO, DENOISE_FRAMEBUFFER = 1, 2
 # guides srt_denoise reads: OBJECT, NORMAL_DEPTH and POSITION always, ALBEDO when demodulating
 DENOISE_GUIDES = GBUF_OBJECT | GBUF_NORMAL_DEPTH | GBUF_POSITION
@@ -55,6 +60,7 @@ EXPORTS = [
     "srt_denoise_variance_params_default", "srt_denoise_variance",
     "srt_moments_output", "srt_read_moments", "srt_temporal_variance_params_default", "srt_temporal_variance",
     "srt_update_mode", "srt_get_update_info", "srt_mesh_image_size", "srt_read_mesh_image",
+    "srt_trace_params_default", "srt_write_rays", "srt_bind_rays", "srt_bind_ray_output", "srt_trace_rays", "srt_read_ray_output",
 ]
 
 
@@ -167,6 +173,10 @@ class DenoiseVarianceParams(C.Structure):
 
 class TemporalVarianceParams(C.Structure):
     _fields_ = [("min_frames", C.c_float), ("radius", C.c_int32), ("flags", C.c_uint32)]
+
+
+class TraceParams(C.Structure):
+    _fields_ = [("outputs", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class UpdateInfo(C.Structure):
@@ -314,6 +324,12 @@ def open_library(path):
     L.srt_get_update_info.argtypes = [ctx, C.POINTER(UpdateInfo)]
     L.srt_mesh_image_size.argtypes = [ctx, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.srt_read_mesh_image.argtypes = [ctx, C.c_void_p, C.c_void_p]
+    L.srt_trace_params_default.argtypes = [C.POINTER(TraceParams)]
+    L.srt_write_rays.argtypes = [ctx, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]
+    L.srt_bind_rays.argtypes = [ctx, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.srt_bind_ray_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_trace_rays.argtypes = [ctx, C.POINTER(TraceParams)]
+    L.srt_read_ray_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -339,6 +355,34 @@ def _gbuffer_spec(name):
     if name not in GBUFFERS:
         raise ValueError("unknown G-buffer output %r (one of %s)" % (name, ", ".join(GBUFFERS)))
     return GBUFFERS[name]
+
+
+def ray_outputs(outputs):
+    """An output mask of srt_trace_rays from an int or from names of RAY_OUTPUTS ("object", "normal_depth", "position",
+    "albedo", "occluded")."""
+    if isinstance(outputs, str):
+        outputs = [outputs]
+    if isinstance(outputs, (int, np.integer)):
+        return int(outputs)
+    mask = 0
+    for name in outputs:
+        mask |= _ray_output_spec(name)[0]
+    return mask
+
+
+def _ray_output_spec(name):
+    if name not in RAY_OUTPUTS:
+        raise ValueError("unknown ray output %r (one of %s)" % (name, ", ".join(RAY_OUTPUTS)))
+    return RAY_OUTPUTS[name]
+
+
+def trace_defaults(lib=None):
+    """srt_trace_params_default as a dict (pure host: no GPU needed)."""
+    p = TraceParams()
+    rc = (lib if lib is not None else load_library()).srt_trace_params_default(C.byref(p))
+    if rc:
+        raise SrtError(rc, "srt_trace_params_default")
+    return {n: getattr(p, n) for n, _ in TraceParams._fields_}
 
 
 def denoise_defaults(lib=None):
@@ -421,6 +465,8 @@ def __getattr__(name):
         return denoise_variance_defaults()
     if name == "TEMPORAL_VARIANCE_DEFAULTS":
         return temporal_variance_defaults()
+    if name == "TRACE_DEFAULTS":
+        return trace_defaults()
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -629,6 +675,123 @@ class PathTracer:
         dtype, shape = self._gbuffer_shape(name)
         ptr = self._tensor_ptr("bind_gbuffer(%r)" % name, tensor, dtype, shape)  # (checked before the library is touched)
         self._ck(self.L.srt_bind_gbuffer(self._h, bit, ptr))
+
+    # ---- ray queries -------------------------------------------------------------------
+    def _ray_array(self, what, a):
+        """A ray array as (kind, object, count): a host array of N x 4 float32 (numpy, or anything numpy converts) or a torch
+        tensor on this tracer's device, float32, contiguous, of shape (N, 4)."""
+        try:
+            import torch
+        except ImportError:  # numpy input needs no torch
+            torch = None
+        if torch is not None and isinstance(a, torch.Tensor):
+            if a.device.type != "cuda":
+                a = a.detach().numpy()
+            else:
+                if a.device.index != self.device:
+                    raise ValueError("%s: tensor on %s, the tracer renders on cuda:%d" % (what, a.device, self.device))
+                if a.dtype != torch.float32:
+                    raise TypeError("%s: dtype %s, want torch.float32" % (what, a.dtype))
+                if a.dim() != 2 or a.shape[1] != 4 or a.shape[0] < 1:
+                    raise ValueError("%s: shape %s, want (N, 4)" % (what, tuple(a.shape)))
+                if not a.is_contiguous():
+                    raise ValueError("%s: tensor is not contiguous" % what)
+                return "device", a, int(a.shape[0])
+        h = np.ascontiguousarray(a, dtype=np.float32)
+        if h.ndim != 2 or h.shape[1] != 4 or h.shape[0] < 1:
+            raise ValueError("%s: shape %s, want (N, 4)" % (what, h.shape))
+        return "host", h, int(h.shape[0])
+
+    def write_rays(self, origins, directions):
+        """srt_write_rays: copy N rays from host arrays (N, 4) float32 — origin (x, y, z, ignored), direction (x, y, z, t_max) —
+        into the handle's own buffers and make them the current rays.  Waits for enqueued work."""
+        ko, o, n = self._ray_array("write_rays(origins)", origins)
+        kd, d, m = self._ray_array("write_rays(directions)", directions)
+        if ko != "host" or kd != "host":
+            raise TypeError("write_rays: host arrays wanted (device tensors go through bind_rays)")
+        if n != m:
+            raise ValueError("write_rays: %d origins, %d directions" % (n, m))
+        f = C.POINTER(C.c_float)
+        self._ck(self.L.srt_write_rays(self._h, o.ctypes.data_as(f), d.ctypes.data_as(f), n))
+        self._ray_count = self._ray_own_count = n
+        self._ray_bound = None
+
+    def bind_rays(self, origins, directions, count=None):
+        """srt_bind_rays: make two device arrays the current rays: torch tensors (N, 4) float32 on this tracer's device, or raw
+        device pointers (ints) with `count`.  None, None returns to the handle's own buffers.  Does not wait or copy: the
+        caller keeps the arrays alive until the traces that read them have finished."""
+        if origins is None and directions is None:
+            self._ck(self.L.srt_bind_rays(self._h, None, None, 0))
+            self._ray_count = getattr(self, "_ray_own_count", None)
+            self._ray_bound = None
+            return
+        if isinstance(origins, (int, np.integer)) and isinstance(directions, (int, np.integer)):
+            if count is None:
+                raise ValueError("bind_rays: raw device pointers need count")
+            po, pd, n = int(origins), int(directions), int(count)
+            keep = None
+        else:
+            ko, o, n = self._ray_array("bind_rays(origins)", origins)
+            kd, d, m = self._ray_array("bind_rays(directions)", directions)
+            if ko != "device" or kd != "device":
+                raise TypeError("bind_rays: device tensors wanted (host arrays go through write_rays)")
+            if n != m:
+                raise ValueError("bind_rays: %d origins, %d directions" % (n, m))
+            if count is not None:
+                if not 1 <= int(count) <= n:
+                    raise ValueError("bind_rays: count %d of %d rays" % (int(count), n))
+                n = int(count)
+            po, pd = o.data_ptr(), d.data_ptr()
+            keep = (o, d)
+        self._ck(self.L.srt_bind_rays(self._h, C.c_void_p(po), C.c_void_p(pd), n))
+        self._ray_count = n
+        self._ray_bound = keep  # (bound tensors stay referenced for as long as they are bound)
+
+    def trace_rays(self, outputs=RAYS_ALL, normalize=False, flags=0):
+        """srt_trace_rays: the closest hit of every current ray against the current scene.  `outputs`: a mask or names of
+        RAY_OUTPUTS; normalize=True normalizes every direction first (SRT_RAYS_NORMALIZE).  Asynchronous, like render()."""
+        p = TraceParams(ray_outputs(outputs), int(flags) | (RAYS_NORMALIZE if normalize else 0))
+        n = getattr(self, "_ray_count", None)
+        for name, t in getattr(self, "_ray_out_bound", {}).items():
+            if n is not None and (p.outputs & RAY_OUTPUTS[name][0]) and t.shape[0] < n:
+                raise ValueError("trace_rays: the tensor bound to %r holds %d elements, the batch has %d rays" % (name, t.shape[0], n))
+        self._ck(self.L.srt_trace_rays(self._h, C.byref(p)))
+        self._ray_traced = n
+
+    def ray_output(self, name, count=None):
+        """srt_read_ray_output: one output of the last trace_rays() as a numpy array: "object" and "occluded" (N,) int32, the
+        others (N, 4) float32.  `count`: N, for rays bound by raw pointer on another PathTracer object (default: this one's)."""
+        bit, dtype, ch = _ray_output_spec(name)
+        n = count if count is not None else getattr(self, "_ray_traced", None)
+        if n is None:
+            raise SrtError(ERR_STATE, "ray_output(%r): no trace_rays() yet" % name)
+        out = np.empty((n,) if ch == 1 else (n, ch), dtype=dtype)
+        self._ck(self.L.srt_read_ray_output(self._h, bit, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def bind_ray_output(self, name, tensor):
+        """srt_bind_ray_output: write output `name` into a torch tensor on this tracer's device (None: the handle's own buffer):
+        (M,) int32 for "object" / "occluded", (M, 4) float32 for the others, contiguous, M at least the batch size (checked by
+        trace_rays).  Checked here, before any native call; the caller keeps the tensor alive until the traces have finished."""
+        bit, dtype, ch = _ray_output_spec(name)
+        if tensor is not None:
+            import torch
+
+            if not isinstance(tensor, torch.Tensor):
+                raise TypeError("bind_ray_output(%r): expected a torch.Tensor, got %s" % (name, type(tensor).__name__))
+            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
+            if m < 1:
+                raise ValueError("bind_ray_output(%r): shape %s, want at least one element" % (name, tuple(tensor.shape)))
+            shape = (m,) if ch == 1 else (m, ch)
+            ptr = self._tensor_ptr("bind_ray_output(%r)" % name, tensor, dtype, shape)
+        else:
+            ptr = None
+        self._ck(self.L.srt_bind_ray_output(self._h, bit, ptr))
+        bound = self.__dict__.setdefault("_ray_out_bound", {})
+        if tensor is None:
+            bound.pop(name, None)
+        else:
+            bound[name] = tensor
 
     def _tensor_ptr(self, what, tensor, dtype, shape):
         """The device pointer of a tensor an output is bound to: on this tracer's device, of numpy dtype `dtype` (int32 or

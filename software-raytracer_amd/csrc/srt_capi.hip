@@ -26,6 +26,8 @@
 #include "srt_variance.hip.h"
 #include "srt_moments.hip.h"
 #include "srt_refit.hip.h"
+#include "srt_rays.hip.h"
+#include "srt_rays_host.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -344,6 +346,15 @@ struct srt_context {
     uint32_t mom_written_flags = 0;
     float mom_samples = 0.0f;
     bool mom_history = false;
+
+    // ray queries (srt_trace_rays): the handle's own ray arrays (srt_write_rays; they grow on demand) and output buffers, one slot
+    // per output bit (allocated on first use, grown when a batch needs more), the caller's bound outputs (srt_bind_ray_output;
+    // NULL = own), and the host-side state (srt_rays_host.h): which arrays are the current rays and what the last trace wrote
+    DeviceBuffer<float4> d_ray_origin;
+    DeviceBuffer<float4> d_ray_direction;
+    DeviceBuffer<void> d_rayout_own[srt::RAYS_SLOTS];
+    void* d_rayout_bound[srt::RAYS_SLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    srt::RaysState rays;
 
     char error[512] = "";
 };
@@ -1510,6 +1521,117 @@ int srt_read_gbuffer(srt_context* ctx, uint32_t output, void* dst) {
     if (!src) return fail(ctx, SRT_ERR_STATE, "srt_read_gbuffer: output 0x%x has neither been bound nor rendered", output);
     if (const int rc = finish_stream(ctx)) return rc;
     SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * gbuf_elem_bytes(i), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+// ---- ray queries ---------------------------------------------------------------------------------------------------
+static_assert(SRT_GBUF_OBJECT == srt::RAYS_OUT_OBJECT && SRT_GBUF_NORMAL_DEPTH == srt::RAYS_OUT_NORMAL_DEPTH && SRT_GBUF_POSITION == srt::RAYS_OUT_POSITION &&
+              SRT_GBUF_ALBEDO == srt::RAYS_OUT_ALBEDO && SRT_RAYS_OCCLUDED == srt::RAYS_OUT_OCCLUDED && SRT_RAYS_NORMALIZE == srt::RAYS_FLAG_NORMALIZE &&
+              (int)SRT_OK == (int)srt::RAYS_OK && (int)SRT_ERR_INVALID_ARG == (int)srt::RAYS_INVALID_ARG && (int)SRT_ERR_STATE == (int)srt::RAYS_STATE,
+              "srt_rays_host.h and srt_pathtrace.h disagree");
+
+int srt_trace_params_default(srt_trace_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    out->outputs = SRT_GBUF_ALL | SRT_RAYS_OCCLUDED;
+    out->flags = 0;
+    return SRT_OK;
+}
+
+int srt_write_rays(srt_context* ctx, const float* origins, const float* directions, size_t count) {
+    if (!ctx || !origins || !directions) return SRT_ERR_INVALID_ARG;
+    if (!srt::rays_count_ok(count)) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_write_rays: %zu rays: want 1 .. 2^30", count);
+    if (const int rc = finish_stream(ctx)) return rc;  // (traces in flight read the own arrays; they may be re-allocated below)
+    const size_t bytes = count * sizeof(float4);
+    if (ctx->d_ray_origin.bytes() < bytes || ctx->d_ray_direction.bytes() < bytes) {
+        ctx->rays.own_count = 0;  // (a failed allocation leaves no own rays)
+        SRT_HIP(ctx, ctx->d_ray_origin.ensure(bytes));
+        SRT_HIP(ctx, ctx->d_ray_direction.ensure(bytes));
+    }
+    SRT_HIP(ctx, hipMemcpy(ctx->d_ray_origin, origins, bytes, hipMemcpyHostToDevice));
+    SRT_HIP(ctx, hipMemcpy(ctx->d_ray_direction, directions, bytes, hipMemcpyHostToDevice));
+    srt::rays_written(ctx->rays, count);
+    return SRT_OK;
+}
+
+int srt_bind_rays(srt_context* ctx, const void* d_origins, const void* d_directions, size_t count) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    // (no synchronisation: enqueued traces keep the arrays they were given, as srt_bind_gbuffer)
+    if (srt::rays_bind(ctx->rays, d_origins, d_directions, count) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_rays: want two device arrays and 1 .. 2^30 rays, or NULL, NULL, 0 (got %zu rays)", count);
+    return SRT_OK;
+}
+
+int srt_bind_ray_output(srt_context* ctx, uint32_t output, void* d_ptr) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    const int i = srt::rays_slot(output);
+    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_ray_output: output 0x%x is not a single SRT_GBUF_* / SRT_RAYS_OCCLUDED bit", output);
+    ctx->d_rayout_bound[i] = d_ptr;  // (no synchronisation: enqueued traces keep the buffer they were given, as srt_bind_gbuffer)
+    return SRT_OK;
+}
+
+int srt_trace_rays(srt_context* ctx, const srt_trace_params* t) {
+    if (!ctx || !t) return SRT_ERR_INVALID_ARG;
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::rays_check_trace(ctx->rays, ctx->scene_set, t->outputs, t->flags, &why))
+        return fail(ctx, (int)rs, "srt_trace_rays: %s (outputs 0x%x, flags 0x%x)", why, t->outputs, t->flags);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = ctx->rays.count();
+    // own outputs that are too small for this batch: earlier traces may still be writing the old buffer, so wait before it goes
+    bool grow = false;
+    for (int i = 0; i < srt::RAYS_SLOTS; ++i)
+        grow = grow || ((t->outputs & (1u << i)) && !ctx->d_rayout_bound[i] && ctx->d_rayout_own[i].bytes() < n * srt::rays_elem_bytes(i));
+    if (grow) {
+        if (const int rc = finish_stream(ctx)) return rc;
+    }
+    void* dst[srt::RAYS_SLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < srt::RAYS_SLOTS; ++i) {
+        if (!(t->outputs & (1u << i))) continue;
+        if (!ctx->d_rayout_bound[i]) {
+            if (ctx->d_rayout_own[i].bytes() < n * srt::rays_elem_bytes(i) && ctx->rays.last_dst[i] == (void*)ctx->d_rayout_own[i])
+                ctx->rays.last_dst[i] = nullptr, ctx->rays.last_outputs &= ~(1u << i);  // (the last trace's copy of this output goes with the buffer)
+            SRT_HIP(ctx, ctx->d_rayout_own[i].ensure(n * srt::rays_elem_bytes(i)));
+        }
+        dst[i] = bound_or_own(ctx->d_rayout_bound[i], ctx->d_rayout_own[i]);
+    }
+    // the scene side of the render's kernel parameters: scene image, mesh image, the scene_in_lds judgement and the LDS bytes (the
+    // camera terms are filled from whatever camera there is and read by nobody)
+    srt_render_params p{};
+    p.row_begin = 0, p.row_end = ctx->height, p.first_sample = 1, p.sample_count = 1;
+    srt::KernelParams K;
+    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
+    K.flags &= srt::KF_BOXES_FINITE;
+    K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // a trace touches none of them
+    srt::RaysIO io{};
+    io.origin = ctx->rays.bound() ? (const float4*)ctx->rays.bound_origin : (const float4*)ctx->d_ray_origin;
+    io.direction = ctx->rays.bound() ? (const float4*)ctx->rays.bound_direction : (const float4*)ctx->d_ray_direction;
+    io.count = (uint32_t)n;
+    io.normalize = (t->flags & SRT_RAYS_NORMALIZE) ? 1u : 0u;
+    io.object = (int32_t*)dst[0], io.normal_depth = (float4*)dst[1], io.position = (float4*)dst[2], io.albedo = (float4*)dst[3], io.occluded = (int32_t*)dst[4];
+    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
+    void (*const kernel)(srt::KernelParams, srt::RaysIO) = in_lds ? (mesh ? srt::rays_kernel<true, true> : srt::rays_kernel<true, false>)
+                                                                  : (mesh ? srt::rays_kernel<false, true> : srt::rays_kernel<false, false>);
+    // persistent workgroups, sized as srt_render_gbuffer sizes them: about CUs x resident workgroups (at most four per CU), never
+    // more than there are blocks of 64 rays for
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, srt::WG_THREADS, ks.lds_bytes) != hipSuccess || per_cu < 1)
+        per_cu = 1, (void)hipGetLastError();
+    per_cu = per_cu > 4 ? 4 : per_cu;
+    const unsigned wgs = srt::rays_grid(n, srt::WG_TILES_X * srt::WG_TILES_Y, (long long)ctx->cu_count * per_cu);
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io);
+    SRT_HIP(ctx, hipGetLastError());
+    srt::rays_traced(ctx->rays, t->outputs, dst);
+    return SRT_OK;
+}
+
+int srt_read_ray_output(srt_context* ctx, uint32_t output, void* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    const srt::RaysStatus rs = srt::rays_check_read(ctx->rays, output, &src, &bytes);
+    if (rs == srt::RAYS_INVALID_ARG) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_ray_output: output 0x%x is not a single SRT_GBUF_* / SRT_RAYS_OCCLUDED bit", output);
+    if (rs != srt::RAYS_OK) return fail(ctx, SRT_ERR_STATE, "srt_read_ray_output: output 0x%x was not written by the last srt_trace_rays", output);
+    if (const int rc = finish_stream(ctx)) return rc;
+    SRT_HIP(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return SRT_OK;
 }
 

@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .capi import (DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
+from .capi import (RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
                    TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -32,6 +32,7 @@ EXPORTS = [
     "srt_host_renderer_antialias", "srt_host_renderer_read_antialiased", "srt_host_renderer_set_antialias",
     "srt_host_renderer_denoise_variance", "srt_host_renderer_read_variance",
     "srt_host_renderer_temporal_variance", "srt_host_renderer_read_moments",
+    "srt_host_renderer_trace_rays", "srt_host_renderer_read_ray_output",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -109,6 +110,8 @@ def load_library():
     L.srt_host_renderer_handle.argtypes = [vp]
     L.srt_host_renderer_render_gbuffer.argtypes = [vp, C.c_uint32]
     L.srt_host_renderer_read_gbuffer.argtypes = [vp, C.c_uint32, vp]
+    L.srt_host_renderer_trace_rays.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_uint32, C.c_uint32]
+    L.srt_host_renderer_read_ray_output.argtypes = [vp, C.c_uint32, vp]
     L.srt_host_renderer_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
     L.srt_host_renderer_read_denoised.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
@@ -338,6 +341,31 @@ class Renderer:
         bit, dtype, ch = GBUFFERS[name]
         out = np.empty((self.height, self.width) if ch == 1 else (self.height, self.width, ch), dtype=dtype)
         self._ck(self.L.srt_host_renderer_read_gbuffer(self._h, bit, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def trace_rays(self, origins, directions, outputs=RAYS_ALL, normalize=False):
+        """PathTraceRenderer::traceRays: copy N rays from host arrays (N, 4) float32 — origin (x, y, z, ignored), direction
+        (x, y, z, t_max) — and enqueue their closest-hit query against the renderer's scene (outputs: a mask or names of
+        capi.RAY_OUTPUTS; normalize: SRT_RAYS_NORMALIZE)."""
+        o = np.ascontiguousarray(origins, dtype=np.float32)
+        d = np.ascontiguousarray(directions, dtype=np.float32)
+        if o.ndim != 2 or o.shape[1] != 4 or o.shape != d.shape or o.shape[0] < 1:
+            raise ValueError("trace_rays: origins %s and directions %s, want two (N, 4) arrays" % (o.shape, d.shape))
+        f = C.POINTER(C.c_float)
+        self._ck(self.L.srt_host_renderer_trace_rays(self._h, o.ctypes.data_as(f), d.ctypes.data_as(f), o.shape[0], ray_outputs(outputs),
+                                                     RAYS_NORMALIZE if normalize else 0))
+        self._ray_traced = int(o.shape[0])
+
+    def ray_output(self, name):
+        """PathTraceRenderer::readRayOutput: one output of the last trace_rays(), as capi.PathTracer.ray_output returns it."""
+        if name not in RAY_OUTPUTS:
+            raise ValueError("unknown ray output %r (one of %s)" % (name, ", ".join(RAY_OUTPUTS)))
+        bit, dtype, ch = RAY_OUTPUTS[name]
+        n = getattr(self, "_ray_traced", None)
+        if n is None:
+            raise RuntimeError("ray_output(%r): no trace_rays() yet" % name)
+        out = np.empty((n,) if ch == 1 else (n, ch), dtype=dtype)
+        self._ck(self.L.srt_host_renderer_read_ray_output(self._h, bit, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None, albedo=True, framebuffer=False,

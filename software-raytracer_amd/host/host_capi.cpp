@@ -212,6 +212,11 @@ int srt_host_renderer_read_accumulator(srt_host_renderer* h, float* dst) {
 // first-hit buffers of the renderer's band with its current camera (srt_render_gbuffer / srt_read_gbuffer)
 int srt_host_renderer_render_gbuffer(srt_host_renderer* h, uint32_t outputs) { SRT_HOST_TRY(h, h->r->RenderGBuffer(outputs)) }
 int srt_host_renderer_read_gbuffer(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->ReadGBuffer(output, dst)) }
+// ray queries against the renderer's scene (srt_write_rays + srt_trace_rays / srt_read_ray_output)
+int srt_host_renderer_trace_rays(srt_host_renderer* h, const float* origins, const float* directions, size_t count, uint32_t outputs, uint32_t flags) {
+    SRT_HOST_TRY(h, h->r->traceRays(origins, directions, count, outputs, flags))
+}
+int srt_host_renderer_read_ray_output(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->readRayOutput(output, dst)) }
 // denoiser over the whole frame with the guides as they stand (srt_denoise / srt_read_denoised)
 int srt_host_renderer_denoise(srt_host_renderer* h, const srt_denoise_params* p) { SRT_HOST_TRY(h, h->r->Denoise(*p)) }
 int srt_host_renderer_read_denoised(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->ReadDenoised(dst)) }

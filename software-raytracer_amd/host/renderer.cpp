@@ -219,6 +219,16 @@ void PathTraceRenderer::RenderGBufferRows(uint32_t outputs, int row_begin, int r
 
 void PathTraceRenderer::ReadGBuffer(uint32_t output, void* dst) { check(srt_read_gbuffer(ctx_, output, dst), "srt_read_gbuffer"); }
 
+void PathTraceRenderer::traceRays(const float* origins, const float* directions, size_t count, uint32_t outputs, uint32_t flags) {
+    check(srt_write_rays(ctx_, origins, directions, count), "srt_write_rays");
+    srt_trace_params t{};
+    t.outputs = outputs;
+    t.flags = flags;
+    check(srt_trace_rays(ctx_, &t), "srt_trace_rays");
+}
+
+void PathTraceRenderer::readRayOutput(uint32_t output, void* dst) { check(srt_read_ray_output(ctx_, output, dst), "srt_read_ray_output"); }
+
 void PathTraceRenderer::Denoise(const srt_denoise_params& params) { check(srt_denoise(ctx_, &params), "srt_denoise"); }
 
 void PathTraceRenderer::ReadDenoised(float* dst_rgba) { check(srt_read_denoised(ctx_, dst_rgba), "srt_read_denoised"); }

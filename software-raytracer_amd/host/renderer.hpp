@@ -146,6 +146,12 @@ class PathTraceRenderer {
     void RenderGBuffer(uint32_t outputs) { RenderGBufferRows(outputs, row_begin_, row_end_); }
     void RenderGBufferRows(uint32_t outputs, int row_begin, int row_end);  // any memory-row band (MultiGpuRenderer: the whole frame)
     void ReadGBuffer(uint32_t output, void* dst);
+    // Ray queries (srt_write_rays + srt_trace_rays): the closest hit of `count` caller-supplied rays against the current scene.
+    // origins / directions: count x 4 floats each, (o.xyz, ignored) and (d.xyz, t_max); outputs: SRT_GBUF_* bits and
+    // SRT_RAYS_OCCLUDED; flags: 0 or SRT_RAYS_NORMALIZE.  No camera is involved.  Asynchronous once the rays are copied;
+    // readRayOutput waits and copies the `count` elements of ONE output of the last traceRays (int32 or float4 per ray).
+    void traceRays(const float* origins, const float* directions, size_t count, uint32_t outputs, uint32_t flags = 0);
+    void readRayOutput(uint32_t output, void* dst);
     // Denoiser (srt_denoise) over the whole frame: the accumulator guided by the first-hit buffers as they stand (call
     // RenderGBuffer first).  Asynchronous; ReadDenoised waits and copies the W x H float4 result (scene rows).
     void Denoise(const srt_denoise_params& params);

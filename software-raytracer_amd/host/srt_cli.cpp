@@ -60,6 +60,58 @@ static int write_gbuffers(R& r, const std::string& prefix, int W, int H) {
     return 0;
 }
 
+// --rays IN.f32 --rays-out OUT.bin: closest-hit queries for the rays of a file (N records of 8 float32: origin xyzw, direction
+// xyz + t_max) against the scene; the five outputs of srt_trace_rays follow each other in OUT.bin in the order of their bits.
+static int trace_ray_file(const Scene& scene, int device, const std::string& in, const std::string& out, bool normalize) {
+    FILE* f = std::fopen(in.c_str(), "rb");
+    if (!f) {
+        std::perror(in.c_str());
+        return 1;
+    }
+    std::vector<float> rec;
+    float buf[2048];
+    for (size_t got; (got = std::fread(buf, sizeof(float), 2048, f)) > 0;) rec.insert(rec.end(), buf, buf + got);
+    std::fclose(f);
+    if (rec.empty() || rec.size() % 8) {
+        std::fprintf(stderr, "%s: %zu floats: want N >= 1 records of 8 float32\n", in.c_str(), rec.size());
+        return 2;
+    }
+    const size_t n = rec.size() / 8;
+    std::vector<float> o(4 * n), d(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+        std::memcpy(&o[4 * i], &rec[8 * i], 4 * sizeof(float));
+        std::memcpy(&d[4 * i], &rec[8 * i + 4], 4 * sizeof(float));
+    }
+    try {
+        PathTraceRenderer r(device, 8, 8);  // (the frame size plays no part in a ray query)
+        r.SetScene(scene);
+        const uint32_t all = SRT_GBUF_ALL | SRT_RAYS_OCCLUDED;
+        r.traceRays(o.data(), d.data(), n, all, normalize ? SRT_RAYS_NORMALIZE : 0u);
+        FILE* g = std::fopen(out.c_str(), "wb");
+        if (!g) {
+            std::perror(out.c_str());
+            return 1;
+        }
+        bool ok = true;
+        std::vector<char> data;
+        for (uint32_t bit = 1; bit <= SRT_RAYS_OCCLUDED; bit <<= 1) {
+            data.resize(n * ((bit == SRT_GBUF_OBJECT || bit == SRT_RAYS_OCCLUDED) ? sizeof(int32_t) : 4 * sizeof(float)));
+            r.readRayOutput(bit, data.data());
+            ok = ok && std::fwrite(data.data(), 1, data.size(), g) == data.size();
+        }
+        ok = (std::fclose(g) == 0) && ok;
+        if (!ok) {
+            std::fprintf(stderr, "%s: write failed\n", out.c_str());
+            return 1;
+        }
+        std::fprintf(stderr, "%zu rays traced%s: %s\n", n, normalize ? " (directions normalized)" : "", out.c_str());
+        return 0;
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+}
+
 static void usage() {
     std::fprintf(stderr,
                  "usage: srt_render --scene FILE [--width 1280] [--height 720] [--spp 32] [--bounces 2]\n"
@@ -67,6 +119,7 @@ static void usage() {
                  "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]\n"
                  "                  [--move-object IDX:DX,DY,DZ]... [--refit]] [--steps N] [--upsample PATH] [--aa K]\n"
                  "                  [--denoise-variance PATH] [--temporal-variance]\n"
+                 "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--device 0]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
                  "             and means the same), --equal-bands: bands of equal height\n"
@@ -98,11 +151,16 @@ static void usage() {
                  "  --temporal-variance: with --temporal, also keep the luminance moments of the history (srt_moments_output) and\n"
                  "             filter the --denoise frame by the per-pixel variance they give (srt_temporal_variance,\n"
                  "             srt_denoise_variance, the library's defaults) instead of srt_denoise; not with --steps, --upsample or\n"
-                 "             --devices\n");
+                 "             --devices\n"
+                 "  --rays:    instead of rendering a frame, answer closest-hit queries (srt_trace_rays) for the rays in IN.f32: N records\n"
+                 "             of 8 float32, origin x y z w (w ignored) and direction x y z t_max; --rays-out receives the five outputs\n"
+                 "             one after the other: object (N int32), normal_depth, position, albedo (N x 4 float32 each), occluded\n"
+                 "             (N int32); --rays-normalize normalizes every direction first; single device, no other output\n");
 }
 
 int main(int argc, char** argv) {
-    std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise, upsample, denoise_variance;
+    std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise, upsample, denoise_variance, rays_in, rays_out;
+    bool rays_normalize = false;
     int temporal = 0, steps = 1, aa = 0;
     bool aa_given = false, temporal_variance = false, refit = false;
     float move[3] = {0, 0, 0}, turn_deg = 0;
@@ -150,6 +208,9 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--aa")) aa = std::atoi(need("--aa")), aa_given = true;
         else if (!std::strcmp(argv[i], "--temporal-variance")) temporal_variance = true;
         else if (!std::strcmp(argv[i], "--refit")) refit = true;
+        else if (!std::strcmp(argv[i], "--rays")) rays_in = need("--rays");
+        else if (!std::strcmp(argv[i], "--rays-out")) rays_out = need("--rays-out");
+        else if (!std::strcmp(argv[i], "--rays-normalize")) rays_normalize = true;
         else if (!std::strcmp(argv[i], "--temporal")) temporal = std::atoi(need("--temporal"));
         else if (!std::strcmp(argv[i], "--turn")) turn_deg = std::strtof(need("--turn"), nullptr);
         else if (!std::strcmp(argv[i], "--move")) {
@@ -198,6 +259,15 @@ int main(int argc, char** argv) {
         usage();
         return 2;
     }
+    if (rays_in.empty() != rays_out.empty() || (rays_normalize && rays_in.empty())) {
+        std::fprintf(stderr, "--rays, --rays-out and --rays-normalize go together: --rays IN.f32 --rays-out OUT.bin [--rays-normalize]\n");
+        return 2;
+    }
+    if (!rays_in.empty() && (!devices.empty() || temporal || steps > 1 || aa_given || !gbuffer.empty() || !denoise.empty() || !upsample.empty() ||
+                             !denoise_variance.empty())) {
+        std::fprintf(stderr, "--rays answers ray queries instead of rendering a frame: single device, no frame options\n");
+        return 2;
+    }
     if (temporal_variance && (!temporal || !devices.empty() || steps > 1 || !upsample.empty())) {
         std::fprintf(stderr, "--temporal-variance needs --temporal and works on one device only, not with --steps or --upsample\n");
         return 2;
@@ -242,6 +312,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--move-object: the scene has no object %zu\n", m.index);
             return 2;
         }
+    if (!rays_in.empty()) return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize);
     auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {
         FILE* f = std::fopen(path.c_str(), "wb");
         if (!f) {

@@ -1,0 +1,116 @@
+// rays_check.cpp — the host-side rules of the ray queries (software-raytracer_amd/csrc/srt_rays_host.h) as a stand-alone
+// program: output slots and element sizes, the count limits, which arrays are the current rays through write / bind / unbind,
+// srt_trace_rays' checks in their order with the state untouched by every refusal, the record of the last trace that
+// srt_read_ray_output reads, and the grid of persistent workgroups.  Built with -fsanitize=address,undefined and run on the CPU.
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "srt_pathtrace.h"
+#include "srt_rays_host.h"
+
+using namespace srt;
+
+static int failures = 0;
+#define CHECK(cond)                                                     \
+    do {                                                                \
+        if (!(cond)) {                                                  \
+            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+            ++failures;                                                 \
+        }                                                               \
+    } while (0)
+
+static bool same(const RaysState& a, const RaysState& b) {
+    bool eq = a.bound_origin == b.bound_origin && a.bound_direction == b.bound_direction && a.bound_count == b.bound_count && a.own_count == b.own_count &&
+              a.last_count == b.last_count && a.last_outputs == b.last_outputs;
+    for (int i = 0; i < RAYS_SLOTS; ++i) eq = eq && a.last_dst[i] == b.last_dst[i];
+    return eq;
+}
+
+int main() {
+    // the header's constants are the ones the rules use
+    CHECK(SRT_GBUF_OBJECT == RAYS_OUT_OBJECT && SRT_GBUF_NORMAL_DEPTH == RAYS_OUT_NORMAL_DEPTH && SRT_GBUF_POSITION == RAYS_OUT_POSITION);
+    CHECK(SRT_GBUF_ALBEDO == RAYS_OUT_ALBEDO && SRT_RAYS_OCCLUDED == RAYS_OUT_OCCLUDED && (SRT_GBUF_ALL | SRT_RAYS_OCCLUDED) == RAYS_OUT_ALL);
+    CHECK(SRT_RAYS_NORMALIZE == RAYS_FLAG_NORMALIZE && (int)SRT_ERR_INVALID_ARG == (int)RAYS_INVALID_ARG && (int)SRT_ERR_STATE == (int)RAYS_STATE);
+    CHECK(sizeof(srt_trace_params) == 8 && offsetof(srt_trace_params, outputs) == 0 && offsetof(srt_trace_params, flags) == 4);
+
+    // slots: exactly the five single bits
+    for (uint32_t v = 0; v < 70; ++v) {
+        const int want = v == 1 ? 0 : v == 2 ? 1 : v == 4 ? 2 : v == 8 ? 3 : v == 16 ? 4 : -1;
+        CHECK(rays_slot(v) == want);
+    }
+    CHECK(rays_slot(0x80000000u) == -1 && rays_slot(~0u) == -1);
+    CHECK(rays_elem_bytes(0) == 4 && rays_elem_bytes(4) == 4 && rays_elem_bytes(1) == 16 && rays_elem_bytes(2) == 16 && rays_elem_bytes(3) == 16);
+    CHECK(!rays_count_ok(0) && rays_count_ok(1) && rays_count_ok((size_t)1 << 30) && !rays_count_ok(((size_t)1 << 30) + 1) && !rays_count_ok(~(size_t)0));
+
+    // current rays
+    std::vector<float> a(8), b(8);
+    RaysState s;
+    const char* why = nullptr;
+    CHECK(s.count() == 0 && !s.bound());
+    CHECK(rays_check_trace(s, false, RAYS_OUT_ALL, 0, &why) == RAYS_STATE && std::strstr(why, "srt_set_scene"));
+    CHECK(rays_check_trace(s, true, RAYS_OUT_ALL, 0, &why) == RAYS_STATE && std::strstr(why, "no rays"));
+    CHECK(rays_check_trace(s, true, RAYS_OUT_ALL, 0, nullptr) == RAYS_STATE);  // (a NULL reason is allowed)
+    rays_written(s, 2);
+    CHECK(s.count() == 2 && !s.bound());
+    CHECK(rays_check_trace(s, true, RAYS_OUT_ALL, 0, &why) == RAYS_OK);
+    CHECK(rays_bind(s, a.data(), b.data(), 5) == RAYS_OK && s.bound() && s.count() == 5);
+    {  // every refused bind leaves the state as it was
+        const RaysState before = s;
+        CHECK(rays_bind(s, nullptr, b.data(), 5) == RAYS_INVALID_ARG && same(s, before));
+        CHECK(rays_bind(s, a.data(), nullptr, 5) == RAYS_INVALID_ARG && same(s, before));
+        CHECK(rays_bind(s, a.data(), b.data(), 0) == RAYS_INVALID_ARG && same(s, before));
+        CHECK(rays_bind(s, nullptr, nullptr, 3) == RAYS_INVALID_ARG && same(s, before));
+        CHECK(rays_bind(s, a.data(), b.data(), ((size_t)1 << 30) + 1) == RAYS_INVALID_ARG && same(s, before));
+    }
+    CHECK(rays_bind(s, a.data(), b.data(), (size_t)1 << 30) == RAYS_OK && s.count() == (size_t)1 << 30);
+    CHECK(rays_bind(s, nullptr, nullptr, 0) == RAYS_OK && !s.bound() && s.count() == 2);  // back to the own rays
+    CHECK(rays_bind(s, a.data(), b.data(), 7) == RAYS_OK);
+    rays_written(s, 3);  // a write ends a binding
+    CHECK(!s.bound() && s.count() == 3);
+
+    // trace checks: order and untouched state
+    {
+        const RaysState before = s;
+        CHECK(rays_check_trace(s, true, 0, 0, &why) == RAYS_INVALID_ARG && std::strstr(why, "outputs"));
+        CHECK(rays_check_trace(s, true, 32, 0, &why) == RAYS_INVALID_ARG);
+        CHECK(rays_check_trace(s, true, 31 | 64, 0, &why) == RAYS_INVALID_ARG);
+        CHECK(rays_check_trace(s, true, 1, 2, &why) == RAYS_INVALID_ARG && std::strstr(why, "flags"));
+        CHECK(rays_check_trace(s, true, 1, 0x80000000u, &why) == RAYS_INVALID_ARG);
+        CHECK(rays_check_trace(s, false, 0, 2, &why) == RAYS_STATE);  // the scene comes first
+        for (uint32_t m = 1; m <= 31; ++m) CHECK(rays_check_trace(s, true, m, 0, &why) == RAYS_OK && rays_check_trace(s, true, m, 1, &why) == RAYS_OK);
+        CHECK(same(s, before));
+    }
+
+    // the record of the last trace
+    const void* src = nullptr;
+    size_t bytes = 0;
+    for (uint32_t bit = 1; bit <= 16; bit <<= 1) CHECK(rays_check_read(s, bit, &src, &bytes) == RAYS_STATE);
+    CHECK(rays_check_read(s, 3, &src, &bytes) == RAYS_INVALID_ARG && rays_check_read(s, 0, &src, &bytes) == RAYS_INVALID_ARG);
+    int dummy[RAYS_SLOTS];
+    void* dst[RAYS_SLOTS] = {&dummy[0], &dummy[1], &dummy[2], &dummy[3], &dummy[4]};
+    rays_traced(s, RAYS_OUT_OBJECT | RAYS_OUT_POSITION | RAYS_OUT_OCCLUDED, dst);
+    CHECK(rays_check_read(s, 1, &src, &bytes) == RAYS_OK && src == dst[0] && bytes == 3 * 4);
+    CHECK(rays_check_read(s, 4, &src, &bytes) == RAYS_OK && src == dst[2] && bytes == 3 * 16);
+    CHECK(rays_check_read(s, 16, &src, &bytes) == RAYS_OK && src == dst[4] && bytes == 3 * 4);
+    CHECK(rays_check_read(s, 2, &src, &bytes) == RAYS_STATE && rays_check_read(s, 8, &src, &bytes) == RAYS_STATE);
+    // a later bind changes the current rays, not what the last trace wrote
+    CHECK(rays_bind(s, a.data(), b.data(), 9) == RAYS_OK);
+    CHECK(rays_check_read(s, 1, &src, &bytes) == RAYS_OK && bytes == 3 * 4);
+    rays_traced(s, RAYS_OUT_ALBEDO, dst);
+    CHECK(rays_check_read(s, 8, &src, &bytes) == RAYS_OK && src == dst[3] && bytes == 9 * 16);
+    CHECK(rays_check_read(s, 1, &src, &bytes) == RAYS_STATE);
+
+    // the grid: never more workgroups than blocks of 64 rays need, never more than are resident, never none
+    CHECK(rays_grid(1, 4, 1024) == 1 && rays_grid(64, 4, 1024) == 1 && rays_grid(256, 4, 1024) == 1 && rays_grid(257, 4, 1024) == 2);
+    CHECK(rays_grid(4099, 4, 1024) == 17 && rays_grid((size_t)1 << 30, 4, 1024) == 1024 && rays_grid((size_t)1 << 30, 4, 1) == 1);
+    CHECK(rays_grid(100, 4, 0) == 1);
+    for (size_t n : {(size_t)1, (size_t)63, (size_t)65, (size_t)4099, (size_t)1 << 21, (size_t)1 << 30}) {
+        const unsigned g = rays_grid(n, 4, 1024);
+        CHECK((unsigned long long)(g - 1) * 4 * 64 < n);  // the last workgroup's first wave has a ray
+    }
+
+    if (failures) return 1;
+    std::printf("ok rays host rules\n");
+    return 0;
+}
