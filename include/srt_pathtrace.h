@@ -867,6 +867,64 @@ int srt_bind_ray_output(srt_context* ctx, uint32_t output, void* d_ptr);
 int srt_trace_rays(srt_context* ctx, const srt_trace_params* params);
 int srt_read_ray_output(srt_context* ctx, uint32_t output, void* dst);
 
+/* ---- any-hit queries: is a segment occluded? (ABI 7, backward compatible) ----------------------------------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of
+ * them runs what it ran before; srt_trace_params.flags and the output bits of srt_trace_rays are as they were.
+ *
+ * A shadow, ambient-occlusion or visibility ray knows how far it has to look (t_max), needs one bit, and may stop at the first
+ * occluder.  srt_trace_occlusion answers, for every current ray, "does some object report a valid hit with distance < t_max?"
+ * — the same predicate as "the closest hit's distance is < t_max", so no new definition is needed — with a kernel of its own
+ * that culls by the segment, leaves each primitive scan at the first occluder and never builds a hit record.
+ *
+ * Rays.  The current rays of srt_write_rays / srt_bind_rays: origin.w is ignored, direction.w is t_max.  The input domain is
+ * that of srt_trace_rays: unit-length directions with finite origins are pinned, a direction with a NaN component gives what
+ * GetClosestObject gives it (a miss against spheres and triangles; Box::iBox drops a NaN slab distance in its max / min, so a
+ * box can still report its hit), other finite non-zero directions are pinned in analytic scenes only.  SRT_OCCLUSION_NORMALIZE is SRT_RAYS_NORMALIZE.
+ *
+ * Output.  One int32 per ray, written to the SRT_RAYS_OCCLUDED slot: the handle's own buffer or the one bound through
+ * srt_bind_ray_output(SRT_RAYS_OCCLUDED).  The call counts as "the last trace", having written that one output:
+ * srt_read_ray_output(SRT_RAYS_OCCLUDED) reads it, and the four SRT_GBUF_* outputs give SRT_ERR_STATE until the next
+ * srt_trace_rays writes them again.
+ *
+ * Guarantee.  out[i] equals, bit for bit, what srt_trace_rays writes for SRT_RAYS_OCCLUDED on the same rays and scene, for
+ * every ray of that call's pinned domain: t_max = NaN gives 0, +inf gives 1 on every hit, and t_max = 0, a negative t_max or
+ * a t_max exactly at or one ulp either side of the closest distance compare as the binary32 < does.  (Box and triangle hits
+ * have distances >= 0.01; Sphere::Raytrace reports a negative distance from inside a sphere, so a segment with t_max <= 0
+ * can be occluded by a sphere around its origin and by nothing else.)  The closest occluder is not found and no order of
+ * testing is promised.
+ *
+ * Scene and asynchrony.  The scene is captured at enqueue (set, updated, refitted or kept), the rays and the output buffer
+ * are those current at enqueue.  Asynchronous on the launch stream behind earlier work; srt_wait / srt_poll cover it.  Errors
+ * are those of srt_trace_rays, all found before anything is touched: SRT_ERR_STATE before srt_set_scene and when no rays have
+ * been written or bound; SRT_ERR_INVALID_ARG for unknown flags or reserved != 0.  The call leaves alone everything
+ * srt_trace_rays leaves alone, and the other four ray outputs' buffers.
+ *
+ * Work counts.  With SRT_OCCLUSION_COUNT_WORK the launch counts the lane-level tests it EXECUTED for rays of the batch (lanes
+ * past the batch count nothing).  The counts are deterministic — the same calls give the same numbers — are summed per wave
+ * and added with one vector atomic per wave at the end into a handle-owned record, never into the outputs; without the flag
+ * there are no atomics at all.  srt_get_occlusion_work waits and copies the record of the last srt_trace_occlusion;
+ * SRT_ERR_STATE unless that trace had SRT_OCCLUSION_COUNT_WORK (or when there has been none). */
+#define SRT_OCCLUSION_NORMALIZE 1u  /* as SRT_RAYS_NORMALIZE */
+#define SRT_OCCLUSION_COUNT_WORK 2u /* fill srt_occlusion_work for this trace */
+
+typedef struct srt_occlusion_params {
+    uint32_t flags;    /* SRT_OCCLUSION_* bits */
+    uint32_t reserved; /* must be 0 */
+} srt_occlusion_params;
+
+typedef struct srt_occlusion_work { /* lane-level tests EXECUTED for rays of the batch */
+    uint32_t valid, reserved;       /* 1, 0 */
+    uint64_t rays, occluded;        /* rays of the batch; those with output 1 */
+    uint64_t analytic_tests;        /* Sphere::Raytrace + Box::Raytrace evaluations */
+    uint64_t node_visits;           /* (ray, BVH node) pairs whose child boxes were tested */
+    uint64_t triangle_tests;        /* Moller-Trumbore evaluations */
+} srt_occlusion_work;
+
+/* flags = 0, reserved = 0 (pure host, no device needed). */
+int srt_occlusion_params_default(srt_occlusion_params* out);
+int srt_trace_occlusion(srt_context* ctx, const srt_occlusion_params* params);
+int srt_get_occlusion_work(srt_context* ctx, srt_occlusion_work* out);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

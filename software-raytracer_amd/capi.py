@@ -23,6 +23,8 @@ GBUFFERS = {"object": (GBUF_OBJECT, np.int32, 1), "normal_depth": (GBUF_NORMAL_D
 # ray queries (srt_trace_rays): the four G-buffer bits plus OCCLUDED, and the one flag
 RAYS_OCCLUDED, RAYS_ALL = 16, 31
 RAYS_NORMALIZE = 1
+# any-hit queries (srt_trace_occlusion): the flags of srt_occlusion_params
+OCCLUSION_NORMALIZE, OCCLUSION_COUNT_WORK = 1, 2
 # ray output names (PathTracer.ray_output / bind_ray_output) -> (output bit, numpy dtype, per-ray channels)
 RAY_OUTPUTS = dict(GBUFFERS, occluded=(RAYS_OCCLUDED, np.int32, 1))
 DENOISE_ALBEDO, DENOISE_FRAMEBUFFER = 1, 2
@@ -61,6 +63,7 @@ EXPORTS = [
     "srt_moments_output", "srt_read_moments", "srt_temporal_variance_params_default", "srt_temporal_variance",
     "srt_update_mode", "srt_get_update_info", "srt_mesh_image_size", "srt_read_mesh_image",
     "srt_trace_params_default", "srt_write_rays", "srt_bind_rays", "srt_bind_ray_output", "srt_trace_rays", "srt_read_ray_output",
+    "srt_occlusion_params_default", "srt_trace_occlusion", "srt_get_occlusion_work",
 ]
 
 
@@ -177,6 +180,20 @@ class TemporalVarianceParams(C.Structure):
 
 class TraceParams(C.Structure):
     _fields_ = [("outputs", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class OcclusionParams(C.Structure):
+    """srt_occlusion_params: OCCLUSION_* flags; reserved must be 0."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class OcclusionWork(C.Structure):
+    """srt_occlusion_work: lane-level tests executed by the last counting srt_trace_occlusion for rays of its batch."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("rays", C.c_uint64), ("occluded", C.c_uint64),
+                ("analytic_tests", C.c_uint64), ("node_visits", C.c_uint64), ("triangle_tests", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class UpdateInfo(C.Structure):
@@ -330,6 +347,9 @@ def open_library(path):
     L.srt_bind_ray_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
     L.srt_trace_rays.argtypes = [ctx, C.POINTER(TraceParams)]
     L.srt_read_ray_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_occlusion_params_default.argtypes = [C.POINTER(OcclusionParams)]
+    L.srt_trace_occlusion.argtypes = [ctx, C.POINTER(OcclusionParams)]
+    L.srt_get_occlusion_work.argtypes = [ctx, C.POINTER(OcclusionWork)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -757,6 +777,33 @@ class PathTracer:
                 raise ValueError("trace_rays: the tensor bound to %r holds %d elements, the batch has %d rays" % (name, t.shape[0], n))
         self._ck(self.L.srt_trace_rays(self._h, C.byref(p)))
         self._ray_traced = n
+
+    def trace_occlusion(self, origins=None, directions=None, normalize=False, count_work=False, flags=0):
+        """srt_trace_occlusion: for every ray, is there a valid hit with distance < t_max (direction w)?  The any-hit counterpart
+        of trace_rays("occluded"), with the same bits.  `origins` / `directions`: numpy arrays (N, 4) float32 (written with
+        write_rays) or torch tensors on this tracer's device (bound with bind_rays, by data_ptr, no copy); both None: the current
+        rays.  normalize: SRT_OCCLUSION_NORMALIZE; count_work: SRT_OCCLUSION_COUNT_WORK (occlusion_work() then reads the
+        record).  Asynchronous, like render(); ray_output("occluded") reads the result."""
+        if (origins is None) != (directions is None):
+            raise ValueError("trace_occlusion: origins and directions go together")
+        if origins is not None:
+            if self._ray_array("trace_occlusion(origins)", origins)[0] == "host":
+                self.write_rays(origins, directions)
+            else:
+                self.bind_rays(origins, directions)
+        p = OcclusionParams(int(flags) | (OCCLUSION_NORMALIZE if normalize else 0) | (OCCLUSION_COUNT_WORK if count_work else 0), 0)
+        n = getattr(self, "_ray_count", None)
+        t = getattr(self, "_ray_out_bound", {}).get("occluded")
+        if n is not None and t is not None and t.shape[0] < n:
+            raise ValueError("trace_occlusion: the tensor bound to 'occluded' holds %d elements, the batch has %d rays" % (t.shape[0], n))
+        self._ck(self.L.srt_trace_occlusion(self._h, C.byref(p)))
+        self._ray_traced = n
+
+    def occlusion_work(self):
+        """srt_get_occlusion_work: the work counts of the last trace_occlusion(count_work=True) as a dict.  Waits."""
+        w = OcclusionWork()
+        self._ck(self.L.srt_get_occlusion_work(self._h, C.byref(w)))
+        return w.as_dict()
 
     def ray_output(self, name, count=None):
         """srt_read_ray_output: one output of the last trace_rays() as a numpy array: "object" and "occluded" (N,) int32, the

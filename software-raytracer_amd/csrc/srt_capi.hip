@@ -28,6 +28,8 @@
 #include "srt_refit.hip.h"
 #include "srt_rays.hip.h"
 #include "srt_rays_host.h"
+#include "srt_occlusion.hip.h"
+#include "srt_occlusion_host.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -355,6 +357,10 @@ struct srt_context {
     DeviceBuffer<void> d_rayout_own[srt::RAYS_SLOTS];
     void* d_rayout_bound[srt::RAYS_SLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     srt::RaysState rays;
+    // any-hit queries (srt_trace_occlusion): whether the last one counted its work, and the record its kernel adds to
+    // (srt::OCC_WORK_N words, zeroed on the stream in front of a counting launch; never an output buffer)
+    srt::OcclusionState occlusion;
+    DeviceBuffer<unsigned long long> d_occlusion_work;
 
     char error[512] = "";
 };
@@ -1632,6 +1638,85 @@ int srt_read_ray_output(srt_context* ctx, uint32_t output, void* dst) {
     if (rs != srt::RAYS_OK) return fail(ctx, SRT_ERR_STATE, "srt_read_ray_output: output 0x%x was not written by the last srt_trace_rays", output);
     if (const int rc = finish_stream(ctx)) return rc;
     SRT_HIP(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+// ---- any-hit queries -----------------------------------------------------------------------------------------------
+static_assert(SRT_OCCLUSION_NORMALIZE == srt::OCCLUSION_FLAG_NORMALIZE && SRT_OCCLUSION_COUNT_WORK == srt::OCCLUSION_FLAG_COUNT_WORK &&
+              sizeof(srt_occlusion_params) == 8 && sizeof(srt_occlusion_work) == 48,
+              "srt_occlusion_host.h and srt_pathtrace.h disagree");
+
+int srt_occlusion_params_default(srt_occlusion_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    out->flags = 0;
+    out->reserved = 0;
+    return SRT_OK;
+}
+
+int srt_trace_occlusion(srt_context* ctx, const srt_occlusion_params* t) {
+    if (!ctx || !t) return SRT_ERR_INVALID_ARG;
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::occlusion_check_trace(ctx->rays, ctx->scene_set, t->flags, t->reserved, &why))
+        return fail(ctx, (int)rs, "srt_trace_occlusion: %s (flags 0x%x, reserved 0x%x)", why, t->flags, t->reserved);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = ctx->rays.count();
+    const int slot = srt::OCCLUSION_SLOT;
+    const bool count = (t->flags & SRT_OCCLUSION_COUNT_WORK) != 0;
+    // an own output that is too small for this batch: earlier traces may still be writing the old buffer, so wait before it goes
+    if (!ctx->d_rayout_bound[slot] && ctx->d_rayout_own[slot].bytes() < n * sizeof(int32_t)) {
+        if (const int rc = finish_stream(ctx)) return rc;
+        if (ctx->rays.last_dst[slot] == (void*)ctx->d_rayout_own[slot])
+            ctx->rays.last_dst[slot] = nullptr, ctx->rays.last_outputs &= ~SRT_RAYS_OCCLUDED;  // (the last trace's copy of this output goes with the buffer)
+        SRT_HIP(ctx, ctx->d_rayout_own[slot].ensure(n * sizeof(int32_t)));
+    }
+    if (count) {
+        if (!ctx->d_occlusion_work) SRT_HIP(ctx, ctx->d_occlusion_work.ensure(srt::OCC_WORK_N * sizeof(unsigned long long)));
+        SRT_HIP(ctx, hipMemsetAsync(ctx->d_occlusion_work, 0, srt::OCC_WORK_N * sizeof(unsigned long long), ctx->stream));
+    }
+    void* dst = bound_or_own(ctx->d_rayout_bound[slot], ctx->d_rayout_own[slot]);
+    // the scene side of the kernel parameters, as srt_trace_rays fills it
+    srt_render_params p{};
+    p.row_begin = 0, p.row_end = ctx->height, p.first_sample = 1, p.sample_count = 1;
+    srt::KernelParams K;
+    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
+    K.flags &= srt::KF_BOXES_FINITE;
+    K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // a trace touches none of them
+    srt::OcclusionIO io{};
+    io.origin = ctx->rays.bound() ? (const float4*)ctx->rays.bound_origin : (const float4*)ctx->d_ray_origin;
+    io.direction = ctx->rays.bound() ? (const float4*)ctx->rays.bound_direction : (const float4*)ctx->d_ray_direction;
+    io.count = (uint32_t)n;
+    io.normalize = (t->flags & SRT_OCCLUSION_NORMALIZE) ? 1u : 0u;
+    io.occluded = (int32_t*)dst;
+    io.work = count ? (unsigned long long*)ctx->d_occlusion_work : nullptr;
+    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
+    using Kernel = void (*)(srt::KernelParams, srt::OcclusionIO);
+    const Kernel plain = in_lds ? (mesh ? srt::occlusion_kernel<true, true, false> : srt::occlusion_kernel<true, false, false>)
+                                : (mesh ? srt::occlusion_kernel<false, true, false> : srt::occlusion_kernel<false, false, false>);
+    const Kernel counting = in_lds ? (mesh ? srt::occlusion_kernel<true, true, true> : srt::occlusion_kernel<true, false, true>)
+                                   : (mesh ? srt::occlusion_kernel<false, true, true> : srt::occlusion_kernel<false, false, true>);
+    const Kernel kernel = count ? counting : plain;
+    // persistent workgroups, sized as srt_trace_rays sizes them
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, srt::WG_THREADS, ks.lds_bytes) != hipSuccess || per_cu < 1)
+        per_cu = 1, (void)hipGetLastError();
+    per_cu = per_cu > 4 ? 4 : per_cu;
+    const unsigned wgs = srt::rays_grid(n, srt::WG_TILES_X * srt::WG_TILES_Y, (long long)ctx->cu_count * per_cu);
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io);
+    SRT_HIP(ctx, hipGetLastError());
+    srt::occlusion_traced(ctx->rays, ctx->occlusion, dst, t->flags);
+    return SRT_OK;
+}
+
+int srt_get_occlusion_work(srt_context* ctx, srt_occlusion_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::occlusion_check_work(ctx->occlusion) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_occlusion_work: the last srt_trace_occlusion did not ask for SRT_OCCLUSION_COUNT_WORK (or there has been none)");
+    if (const int rc = finish_stream(ctx)) return rc;
+    unsigned long long w[srt::OCC_WORK_N];
+    SRT_HIP(ctx, hipMemcpy(w, ctx->d_occlusion_work, sizeof w, hipMemcpyDeviceToHost));
+    out->valid = 1, out->reserved = 0;
+    out->rays = w[srt::OCC_WORK_RAYS], out->occluded = w[srt::OCC_WORK_OCCLUDED];
+    out->analytic_tests = w[srt::OCC_WORK_ANALYTIC], out->node_visits = w[srt::OCC_WORK_NODES], out->triangle_tests = w[srt::OCC_WORK_TRIANGLES];
     return SRT_OK;
 }
 

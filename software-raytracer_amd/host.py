@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .capi import (RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
+from .capi import (OCCLUSION_COUNT_WORK, OCCLUSION_NORMALIZE, OcclusionWork, RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
                    TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -33,6 +33,7 @@ EXPORTS = [
     "srt_host_renderer_denoise_variance", "srt_host_renderer_read_variance",
     "srt_host_renderer_temporal_variance", "srt_host_renderer_read_moments",
     "srt_host_renderer_trace_rays", "srt_host_renderer_read_ray_output",
+    "srt_host_renderer_trace_occlusion", "srt_host_renderer_occlusion_work",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -112,6 +113,8 @@ def load_library():
     L.srt_host_renderer_read_gbuffer.argtypes = [vp, C.c_uint32, vp]
     L.srt_host_renderer_trace_rays.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_uint32, C.c_uint32]
     L.srt_host_renderer_read_ray_output.argtypes = [vp, C.c_uint32, vp]
+    L.srt_host_renderer_trace_occlusion.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_uint32]
+    L.srt_host_renderer_occlusion_work.argtypes = [vp, C.POINTER(OcclusionWork)]
     L.srt_host_renderer_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
     L.srt_host_renderer_read_denoised.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
@@ -355,6 +358,24 @@ class Renderer:
         self._ck(self.L.srt_host_renderer_trace_rays(self._h, o.ctypes.data_as(f), d.ctypes.data_as(f), o.shape[0], ray_outputs(outputs),
                                                      RAYS_NORMALIZE if normalize else 0))
         self._ray_traced = int(o.shape[0])
+
+    def trace_occlusion(self, origins, directions, normalize=False, count_work=False):
+        """PathTraceRenderer::traceOcclusion: copy N rays from host arrays (N, 4) float32 and enqueue their any-hit query (is
+        there a valid hit with distance < t_max, the directions' w?); ray_output("occluded") reads the result."""
+        o = np.ascontiguousarray(origins, dtype=np.float32)
+        d = np.ascontiguousarray(directions, dtype=np.float32)
+        if o.ndim != 2 or o.shape[1] != 4 or o.shape != d.shape or o.shape[0] < 1:
+            raise ValueError("trace_occlusion: origins %s and directions %s, want two (N, 4) arrays" % (o.shape, d.shape))
+        f = C.POINTER(C.c_float)
+        self._ck(self.L.srt_host_renderer_trace_occlusion(self._h, o.ctypes.data_as(f), d.ctypes.data_as(f), o.shape[0],
+                                                          (OCCLUSION_NORMALIZE if normalize else 0) | (OCCLUSION_COUNT_WORK if count_work else 0)))
+        self._ray_traced = int(o.shape[0])
+
+    def occlusion_work(self):
+        """PathTraceRenderer::occlusionWork: the work counts of the last trace_occlusion(count_work=True) as a dict."""
+        w = OcclusionWork()
+        self._ck(self.L.srt_host_renderer_occlusion_work(self._h, C.byref(w)))
+        return w.as_dict()
 
     def ray_output(self, name):
         """PathTraceRenderer::readRayOutput: one output of the last trace_rays(), as capi.PathTracer.ray_output returns it."""

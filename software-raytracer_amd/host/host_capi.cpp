@@ -216,6 +216,11 @@ int srt_host_renderer_read_gbuffer(srt_host_renderer* h, uint32_t output, void* 
 int srt_host_renderer_trace_rays(srt_host_renderer* h, const float* origins, const float* directions, size_t count, uint32_t outputs, uint32_t flags) {
     SRT_HOST_TRY(h, h->r->traceRays(origins, directions, count, outputs, flags))
 }
+// any-hit queries against the renderer's scene (srt_write_rays + srt_trace_occlusion; the result is read_ray_output's SRT_RAYS_OCCLUDED)
+int srt_host_renderer_trace_occlusion(srt_host_renderer* h, const float* origins, const float* directions, size_t count, uint32_t flags) {
+    SRT_HOST_TRY(h, h->r->traceOcclusion(origins, directions, count, flags))
+}
+int srt_host_renderer_occlusion_work(srt_host_renderer* h, srt_occlusion_work* out) { SRT_HOST_TRY(h, *out = h->r->occlusionWork()) }
 int srt_host_renderer_read_ray_output(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->readRayOutput(output, dst)) }
 // denoiser over the whole frame with the guides as they stand (srt_denoise / srt_read_denoised)
 int srt_host_renderer_denoise(srt_host_renderer* h, const srt_denoise_params* p) { SRT_HOST_TRY(h, h->r->Denoise(*p)) }

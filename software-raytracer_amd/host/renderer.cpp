@@ -227,6 +227,19 @@ void PathTraceRenderer::traceRays(const float* origins, const float* directions,
     check(srt_trace_rays(ctx_, &t), "srt_trace_rays");
 }
 
+void PathTraceRenderer::traceOcclusion(const float* origins, const float* directions, size_t count, uint32_t flags) {
+    check(srt_write_rays(ctx_, origins, directions, count), "srt_write_rays");
+    srt_occlusion_params t{};
+    t.flags = flags;
+    check(srt_trace_occlusion(ctx_, &t), "srt_trace_occlusion");
+}
+
+srt_occlusion_work PathTraceRenderer::occlusionWork() {
+    srt_occlusion_work w{};
+    check(srt_get_occlusion_work(ctx_, &w), "srt_get_occlusion_work");
+    return w;
+}
+
 void PathTraceRenderer::readRayOutput(uint32_t output, void* dst) { check(srt_read_ray_output(ctx_, output, dst), "srt_read_ray_output"); }
 
 void PathTraceRenderer::Denoise(const srt_denoise_params& params) { check(srt_denoise(ctx_, &params), "srt_denoise"); }

@@ -152,6 +152,12 @@ class PathTraceRenderer {
     // readRayOutput waits and copies the `count` elements of ONE output of the last traceRays (int32 or float4 per ray).
     void traceRays(const float* origins, const float* directions, size_t count, uint32_t outputs, uint32_t flags = 0);
     void readRayOutput(uint32_t output, void* dst);
+    // Any-hit queries (srt_write_rays + srt_trace_occlusion): for each of `count` caller-supplied rays, is there a valid hit with
+    // distance < t_max (directions' w)?  flags: SRT_OCCLUSION_* bits.  Asynchronous once the rays are copied; the result is the
+    // SRT_RAYS_OCCLUDED output of readRayOutput (count int32), with the bits srt_trace_rays gives it.  occlusionWork waits and
+    // returns the work counts of a trace that had SRT_OCCLUSION_COUNT_WORK.
+    void traceOcclusion(const float* origins, const float* directions, size_t count, uint32_t flags = 0);
+    srt_occlusion_work occlusionWork();
     // Denoiser (srt_denoise) over the whole frame: the accumulator guided by the first-hit buffers as they stand (call
     // RenderGBuffer first).  Asynchronous; ReadDenoised waits and copies the W x H float4 result (scene rows).
     void Denoise(const srt_denoise_params& params);

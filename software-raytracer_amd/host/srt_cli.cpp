@@ -62,7 +62,8 @@ static int write_gbuffers(R& r, const std::string& prefix, int W, int H) {
 
 // --rays IN.f32 --rays-out OUT.bin: closest-hit queries for the rays of a file (N records of 8 float32: origin xyzw, direction
 // xyz + t_max) against the scene; the five outputs of srt_trace_rays follow each other in OUT.bin in the order of their bits.
-static int trace_ray_file(const Scene& scene, int device, const std::string& in, const std::string& out, bool normalize) {
+// With --any-hit the rays go through srt_trace_occlusion instead and OUT.bin receives the occluded array (N int32) alone.
+static int trace_ray_file(const Scene& scene, int device, const std::string& in, const std::string& out, bool normalize, bool any_hit) {
     FILE* f = std::fopen(in.c_str(), "rb");
     if (!f) {
         std::perror(in.c_str());
@@ -85,8 +86,8 @@ static int trace_ray_file(const Scene& scene, int device, const std::string& in,
     try {
         PathTraceRenderer r(device, 8, 8);  // (the frame size plays no part in a ray query)
         r.SetScene(scene);
-        const uint32_t all = SRT_GBUF_ALL | SRT_RAYS_OCCLUDED;
-        r.traceRays(o.data(), d.data(), n, all, normalize ? SRT_RAYS_NORMALIZE : 0u);
+        if (any_hit) r.traceOcclusion(o.data(), d.data(), n, normalize ? SRT_OCCLUSION_NORMALIZE : 0u);
+        else r.traceRays(o.data(), d.data(), n, SRT_GBUF_ALL | SRT_RAYS_OCCLUDED, normalize ? SRT_RAYS_NORMALIZE : 0u);
         FILE* g = std::fopen(out.c_str(), "wb");
         if (!g) {
             std::perror(out.c_str());
@@ -94,7 +95,7 @@ static int trace_ray_file(const Scene& scene, int device, const std::string& in,
         }
         bool ok = true;
         std::vector<char> data;
-        for (uint32_t bit = 1; bit <= SRT_RAYS_OCCLUDED; bit <<= 1) {
+        for (uint32_t bit = any_hit ? SRT_RAYS_OCCLUDED : 1u; bit <= SRT_RAYS_OCCLUDED; bit <<= 1) {
             data.resize(n * ((bit == SRT_GBUF_OBJECT || bit == SRT_RAYS_OCCLUDED) ? sizeof(int32_t) : 4 * sizeof(float)));
             r.readRayOutput(bit, data.data());
             ok = ok && std::fwrite(data.data(), 1, data.size(), g) == data.size();
@@ -104,7 +105,7 @@ static int trace_ray_file(const Scene& scene, int device, const std::string& in,
             std::fprintf(stderr, "%s: write failed\n", out.c_str());
             return 1;
         }
-        std::fprintf(stderr, "%zu rays traced%s: %s\n", n, normalize ? " (directions normalized)" : "", out.c_str());
+        std::fprintf(stderr, "%zu rays traced%s%s: %s\n", n, any_hit ? " (any hit)" : "", normalize ? " (directions normalized)" : "", out.c_str());
         return 0;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());
@@ -119,7 +120,7 @@ static void usage() {
                  "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]\n"
                  "                  [--move-object IDX:DX,DY,DZ]... [--refit]] [--steps N] [--upsample PATH] [--aa K]\n"
                  "                  [--denoise-variance PATH] [--temporal-variance]\n"
-                 "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--device 0]\n"
+                 "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--any-hit] [--device 0]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
                  "             and means the same), --equal-bands: bands of equal height\n"
@@ -155,12 +156,14 @@ static void usage() {
                  "  --rays:    instead of rendering a frame, answer closest-hit queries (srt_trace_rays) for the rays in IN.f32: N records\n"
                  "             of 8 float32, origin x y z w (w ignored) and direction x y z t_max; --rays-out receives the five outputs\n"
                  "             one after the other: object (N int32), normal_depth, position, albedo (N x 4 float32 each), occluded\n"
-                 "             (N int32); --rays-normalize normalizes every direction first; single device, no other output\n");
+                 "             (N int32); --rays-normalize normalizes every direction first; single device, no other output\n"
+                 "  --any-hit: with --rays, ask srt_trace_occlusion (is there a hit with distance < t_max?) instead; --rays-out then receives\n"
+                 "             the occluded array (N int32) alone, with the bits the closest-hit query gives it\n");
 }
 
 int main(int argc, char** argv) {
     std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise, upsample, denoise_variance, rays_in, rays_out;
-    bool rays_normalize = false;
+    bool rays_normalize = false, rays_any_hit = false;
     int temporal = 0, steps = 1, aa = 0;
     bool aa_given = false, temporal_variance = false, refit = false;
     float move[3] = {0, 0, 0}, turn_deg = 0;
@@ -211,6 +214,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rays")) rays_in = need("--rays");
         else if (!std::strcmp(argv[i], "--rays-out")) rays_out = need("--rays-out");
         else if (!std::strcmp(argv[i], "--rays-normalize")) rays_normalize = true;
+        else if (!std::strcmp(argv[i], "--any-hit")) rays_any_hit = true;
         else if (!std::strcmp(argv[i], "--temporal")) temporal = std::atoi(need("--temporal"));
         else if (!std::strcmp(argv[i], "--turn")) turn_deg = std::strtof(need("--turn"), nullptr);
         else if (!std::strcmp(argv[i], "--move")) {
@@ -259,8 +263,8 @@ int main(int argc, char** argv) {
         usage();
         return 2;
     }
-    if (rays_in.empty() != rays_out.empty() || (rays_normalize && rays_in.empty())) {
-        std::fprintf(stderr, "--rays, --rays-out and --rays-normalize go together: --rays IN.f32 --rays-out OUT.bin [--rays-normalize]\n");
+    if (rays_in.empty() != rays_out.empty() || ((rays_normalize || rays_any_hit) && rays_in.empty())) {
+        std::fprintf(stderr, "--rays, --rays-out, --rays-normalize and --any-hit go together: --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--any-hit]\n");
         return 2;
     }
     if (!rays_in.empty() && (!devices.empty() || temporal || steps > 1 || aa_given || !gbuffer.empty() || !denoise.empty() || !upsample.empty() ||
@@ -312,7 +316,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--move-object: the scene has no object %zu\n", m.index);
             return 2;
         }
-    if (!rays_in.empty()) return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize);
+    if (!rays_in.empty()) return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize, rays_any_hit);
     auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {
         FILE* f = std::fopen(path.c_str(), "wb");
         if (!f) {

@@ -1,0 +1,102 @@
+// occlusion_check.cpp — the host-side rules of the any-hit queries (software-raytracer_amd/csrc/srt_occlusion_host.h) as a
+// stand-alone program: the header's constants and struct layouts, srt_trace_occlusion's checks in their order with the state
+// untouched by every refusal, the "last trace" record an occlusion trace leaves for srt_read_ray_output — OCCLUDED alone, the
+// other four outputs unreadable until srt_trace_rays writes them again — and when srt_get_occlusion_work may report.  Built with
+// -fsanitize=address,undefined and run on the CPU.
+#include <cstddef>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "srt_pathtrace.h"
+#include "srt_occlusion_host.h"
+
+using namespace srt;
+
+static int failures = 0;
+#define CHECK(cond)                                                     \
+    do {                                                                \
+        if (!(cond)) {                                                  \
+            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+            ++failures;                                                 \
+        }                                                               \
+    } while (0)
+
+static bool same(const RaysState& a, const RaysState& b) {
+    bool eq = a.bound_origin == b.bound_origin && a.bound_direction == b.bound_direction && a.bound_count == b.bound_count && a.own_count == b.own_count &&
+              a.last_count == b.last_count && a.last_outputs == b.last_outputs;
+    for (int i = 0; i < RAYS_SLOTS; ++i) eq = eq && a.last_dst[i] == b.last_dst[i];
+    return eq;
+}
+
+int main() {
+    // the header's constants and layouts are the ones the rules use
+    CHECK(SRT_OCCLUSION_NORMALIZE == OCCLUSION_FLAG_NORMALIZE && SRT_OCCLUSION_COUNT_WORK == OCCLUSION_FLAG_COUNT_WORK);
+    CHECK((SRT_OCCLUSION_NORMALIZE | SRT_OCCLUSION_COUNT_WORK) == OCCLUSION_FLAG_ALL && SRT_OCCLUSION_NORMALIZE == SRT_RAYS_NORMALIZE);
+    CHECK(rays_slot(SRT_RAYS_OCCLUDED) == OCCLUSION_SLOT && rays_elem_bytes(OCCLUSION_SLOT) == sizeof(int32_t));
+    CHECK(sizeof(srt_occlusion_params) == 8 && offsetof(srt_occlusion_params, flags) == 0 && offsetof(srt_occlusion_params, reserved) == 4);
+    CHECK(sizeof(srt_occlusion_work) == 48 && offsetof(srt_occlusion_work, valid) == 0 && offsetof(srt_occlusion_work, reserved) == 4);
+    CHECK(offsetof(srt_occlusion_work, rays) == 8 && offsetof(srt_occlusion_work, occluded) == 16 && offsetof(srt_occlusion_work, analytic_tests) == 24);
+    CHECK(offsetof(srt_occlusion_work, node_visits) == 32 && offsetof(srt_occlusion_work, triangle_tests) == 40);
+
+    // the checks, in srt_trace_rays' order: the scene, the arguments, the rays
+    std::vector<float> a(8), b(8);
+    RaysState s;
+    OcclusionState w;
+    const char* why = nullptr;
+    CHECK(occlusion_check_work(w) == RAYS_STATE);  // no trace yet
+    CHECK(occlusion_check_trace(s, false, 0, 0, &why) == RAYS_STATE && std::strstr(why, "srt_set_scene"));
+    CHECK(occlusion_check_trace(s, false, 4, 1, &why) == RAYS_STATE);  // the scene comes first
+    CHECK(occlusion_check_trace(s, true, 4, 0, &why) == RAYS_INVALID_ARG && std::strstr(why, "flags"));  // the arguments before the rays
+    CHECK(occlusion_check_trace(s, true, 0, 0, &why) == RAYS_STATE && std::strstr(why, "no rays"));
+    CHECK(occlusion_check_trace(s, true, 0, 0, nullptr) == RAYS_STATE);  // (a NULL reason is allowed)
+    rays_written(s, 3);
+    {
+        const RaysState before = s;
+        for (uint32_t f = 0; f <= 3; ++f) CHECK(occlusion_check_trace(s, true, f, 0, &why) == RAYS_OK);
+        for (uint32_t f : {4u, 8u, 7u, 0x80000000u, ~0u}) CHECK(occlusion_check_trace(s, true, f, 0, &why) == RAYS_INVALID_ARG && std::strstr(why, "flags"));
+        for (uint32_t r : {1u, 2u, 0x80000000u, ~0u}) CHECK(occlusion_check_trace(s, true, 0, r, &why) == RAYS_INVALID_ARG && std::strstr(why, "reserved"));
+        CHECK(occlusion_check_trace(s, true, 3, 1, &why) == RAYS_INVALID_ARG);
+        CHECK(same(s, before));
+    }
+    CHECK(rays_bind(s, a.data(), b.data(), (size_t)1 << 30) == RAYS_OK && occlusion_check_trace(s, true, 0, 0, &why) == RAYS_OK);
+    CHECK(rays_bind(s, nullptr, nullptr, 0) == RAYS_OK && s.count() == 3);
+
+    // the record of the last trace: a closest-hit trace of all five, then an occlusion trace
+    const void* src = nullptr;
+    size_t bytes = 0;
+    int dummy[RAYS_SLOTS], own;
+    void* dst[RAYS_SLOTS] = {&dummy[0], &dummy[1], &dummy[2], &dummy[3], &dummy[4]};
+    rays_traced(s, RAYS_OUT_ALL, dst);
+    for (uint32_t bit = 1; bit <= 16; bit <<= 1) CHECK(rays_check_read(s, bit, &src, &bytes) == RAYS_OK);
+    occlusion_traced(s, w, &own, 0);
+    CHECK(rays_check_read(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_OK && src == &own && bytes == 3 * sizeof(int32_t));
+    for (uint32_t bit = 1; bit <= 8; bit <<= 1) CHECK(rays_check_read(s, bit, &src, &bytes) == RAYS_STATE);
+    CHECK(s.last_outputs == RAYS_OUT_OCCLUDED && s.last_count == 3);
+    for (int i = 0; i < RAYS_SLOTS; ++i) CHECK(s.last_dst[i] == (i == OCCLUSION_SLOT ? (const void*)&own : nullptr));
+    CHECK(occlusion_check_work(w) == RAYS_STATE);  // traced, but not counted
+    // a later bind changes the current rays, not what the last trace wrote; the next occlusion trace takes the new count
+    CHECK(rays_bind(s, a.data(), b.data(), 9) == RAYS_OK);
+    CHECK(rays_check_read(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_OK && bytes == 3 * sizeof(int32_t));
+    occlusion_traced(s, w, &dummy[4], OCCLUSION_FLAG_COUNT_WORK | OCCLUSION_FLAG_NORMALIZE);
+    CHECK(rays_check_read(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_OK && src == &dummy[4] && bytes == 9 * sizeof(int32_t));
+    CHECK(occlusion_check_work(w) == RAYS_OK);
+    occlusion_traced(s, w, &dummy[4], OCCLUSION_FLAG_NORMALIZE);  // a trace without the flag ends the record
+    CHECK(occlusion_check_work(w) == RAYS_STATE);
+    occlusion_traced(s, w, &dummy[4], OCCLUSION_FLAG_COUNT_WORK);
+    CHECK(occlusion_check_work(w) == RAYS_OK);
+    // srt_trace_rays afterwards: its outputs are readable again; the work record is the last OCCLUSION trace's and stays
+    rays_traced(s, RAYS_OUT_OBJECT | RAYS_OUT_ALBEDO, dst);
+    CHECK(rays_check_read(s, 1, &src, &bytes) == RAYS_OK && rays_check_read(s, 8, &src, &bytes) == RAYS_OK && bytes == 9 * 16);
+    CHECK(rays_check_read(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_STATE);
+    CHECK(occlusion_check_work(w) == RAYS_OK);
+    // a refused check in between changes neither
+    {
+        const RaysState before = s;
+        CHECK(occlusion_check_trace(s, true, 4, 0, &why) == RAYS_INVALID_ARG && same(s, before) && occlusion_check_work(w) == RAYS_OK);
+    }
+
+    if (failures) return 1;
+    std::printf("ok occlusion host rules\n");
+    return 0;
+}
