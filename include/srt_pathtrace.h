@@ -925,6 +925,87 @@ int srt_occlusion_params_default(srt_occlusion_params* out);
 int srt_trace_occlusion(srt_context* ctx, const srt_occlusion_params* params);
 int srt_get_occlusion_work(srt_context* ctx, srt_occlusion_work* out);
 
+/* ---- per-pixel visibility: ambient occlusion and sun shadows (ABI 7, backward compatible) -------------------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of
+ * them runs what it ran before.
+ *
+ * srt_render_visibility is a fused device-side pass over the first-hit buffers: per pixel it builds ambient-occlusion and sun
+ * segments at the first hit and asks the any-hit query of srt_trace_occlusion about each, without a ray ever leaving the device.
+ * Outputs, W*H floats each, indexed x + y*W with the SCENE row y like the G-buffer:
+ *   SRT_VIS_AO    the fraction of the pixel's n hemisphere segments that reach ao_radius unoccluded; 1 on a miss
+ *   SRT_VIS_SUN   n . s when the ray towards the sun is unoccluded, else 0 (s = -sun_direction); 0 on a miss
+ *
+ * Rules.
+ * 1. Inputs.  Three G-buffer slots, bound (srt_bind_gbuffer) or own (srt_render_gbuffer): o from SRT_GBUF_OBJECT, n from
+ *    SRT_GBUF_NORMAL_DEPTH.xyz, x from SRT_GBUF_POSITION.xyz.  The pass renders no guide and needs no camera.  The scene is the
+ *    one captured at enqueue (set, updated, refitted or kept), exactly as for srt_trace_occlusion; that the guides belong to
+ *    that scene is the caller's business — the pass cannot check it.
+ * 2. Origin.  All arithmetic is binary32 without FMA.  O = (x.x + n.x * .00001f, x.y + n.y * .00001f, x.z + n.z * .00001f), the
+ *    bounce origin of Raytracer.cpp:177.
+ * 3. AO.  For f = first_sample .. first_sample + n - 1: key = srt_rng_key(seed, px + py*W, f) with scene coordinates;
+ *    r_k = srt_rng_draw(key, k) for k = 1, 2, 3 (draw 0, the specular lottery that srt_render's sample f spends before its first
+ *    bounce, is left out, so this is the hemisphere direction that sample draws); sr = ((float)r_k / 32767 - 0.5f) * 2 per
+ *    component; d = float3::Normalized(sr), turned by * -1 when (d.x*n.x + d.y*n.y) + d.z*n.z < 0
+ *    (GetRandomNormalOrientedHemisphere, :90-105).  The segment (O, d, t_max = ao_radius) is OPEN when the any-hit query reports
+ *    no occluder; ao = (float)open_count / (float)n, an IEEE division of an integer count: no order of evaluation matters.
+ * 4. Sun.  s = -sun_direction of the environment captured at enqueue; c = (n.x*s.x + n.y*s.y) + n.z*s.z.  If !(c > 0), sun = 0
+ *    and no segment is traced; otherwise sun = 0 when the segment (O, s, t_max = +inf) is occluded, else c.  A sun_direction
+ *    that is not unit length is pinned in analytic scenes only (srt_trace_occlusion's domain rule).
+ * 5. Miss pixels (o == -1): ao = 1, sun = 0; nothing is traced and none of their other guide values is loaded.
+ * 6. Pinned domain.  Guides written by srt_render_gbuffer are pinned bit for bit, and so are bound guides with unit normals and
+ *    finite points.  Anything else gives some float per pixel and does not fault.
+ * 7. Band.  As srt_gbuffer_params: a band is given in MEMORY rows and only scene rows [H - row_end, H - row_begin) of each
+ *    requested output are written.
+ * 8. Buffers.  The handle's own (allocated on first use) or the caller's: srt_bind_visibility binds ONE output (a single bit)
+ *    to a DEVICE buffer of W*H floats, NULL = own, under srt_bind_gbuffer's rules (does not wait, enqueued work keeps its
+ *    buffer).  srt_read_visibility waits, then copies the W*H floats of ONE output from the buffer the last
+ *    srt_render_visibility wrote it to; SRT_ERR_STATE unless that call wrote that output (or when there has been none).
+ * 9. Side effects.  Asynchronous on the launch stream behind earlier work; srt_wait / srt_poll cover it.  The call leaves alone
+ *    everything srt_trace_occlusion leaves alone, and the ray buffers and ray outputs as well.
+ * 10. Errors, all found before anything is touched, in this order: SRT_ERR_STATE before srt_set_scene; SRT_ERR_INVALID_ARG for
+ *    an empty or out-of-range band, outputs == 0, unknown output or flag bits and, with SRT_VIS_AO, ao_samples outside 1..4096,
+ *    first_sample == 0, first_sample + ao_samples - 1 > 2^32 - 1, or an ao_radius that is NaN or <= 0; SRT_ERR_STATE when
+ *    OBJECT, NORMAL_DEPTH or POSITION has never been bound or rendered.  ao_samples, first_sample, seed and ao_radius are
+ *    not read without SRT_VIS_AO.
+ * 11. Work counts.  With SRT_VIS_COUNT_WORK the launch counts, deterministically: the segments it traced (n per hit pixel with
+ *    SRT_VIS_AO, one per pixel with c > 0 with SRT_VIS_SUN), those with no occluder, the wave-level any-hit calls — a wave packs
+ *    the h * n AO segments of its 8 x 8 tile (h hit pixels) into ceil(h * n / 64) calls and spends one more on the tile's sun
+ *    segments when some pixel has c > 0 — and the lane-level tests of srt_occlusion_work.  The counts are summed per wave and
+ *    added with one vector atomic per wave into a handle-owned record; without the flag there are no atomics at all.
+ *    srt_get_visibility_work waits and copies the record of the last srt_render_visibility; SRT_ERR_STATE unless that call had
+ *    SRT_VIS_COUNT_WORK (or when there has been none). */
+#define SRT_VIS_AO 1u         /* float per pixel */
+#define SRT_VIS_SUN 2u        /* float per pixel */
+#define SRT_VIS_COUNT_WORK 1u /* flags: fill srt_visibility_work for this call */
+
+typedef struct srt_visibility_params {
+    int32_t row_begin;     /* first memory row (inclusive), as srt_gbuffer_params */
+    int32_t row_end;       /* one past the last memory row */
+    uint32_t outputs;      /* SRT_VIS_AO | SRT_VIS_SUN, at least one */
+    uint32_t flags;        /* 0 or SRT_VIS_COUNT_WORK */
+    uint32_t ao_samples;   /* n: 1..4096 (read with SRT_VIS_AO only) */
+    uint32_t first_sample; /* f0 >= 1, f0 + n - 1 <= 2^32 - 1 */
+    uint32_t seed;
+    float ao_radius;       /* t_max of the AO segments: > 0, +inf allowed; NaN, 0 and negative values are refused */
+} srt_visibility_params;
+
+typedef struct srt_visibility_work {
+    uint32_t valid, reserved;  /* 1, 0 */
+    uint64_t segments, open;   /* segments traced; those with no occluder */
+    uint64_t wave_trips;       /* wave-level any-hit calls */
+    uint64_t analytic_tests;   /* as srt_occlusion_work */
+    uint64_t node_visits;
+    uint64_t triangle_tests;
+} srt_visibility_work;
+
+/* outputs = AO | SUN, flags = 0, ao_samples = 16, first_sample = 1, seed = 0, ao_radius = +inf; row_begin = row_end = 0: the
+ * band is the caller's to fill (pure host, no device needed). */
+int srt_visibility_params_default(srt_visibility_params* out);
+int srt_render_visibility(srt_context* ctx, const srt_visibility_params* params);
+int srt_bind_visibility(srt_context* ctx, uint32_t output, void* d_float);
+int srt_read_visibility(srt_context* ctx, uint32_t output, float* dst);
+int srt_get_visibility_work(srt_context* ctx, srt_visibility_work* out);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

@@ -40,6 +40,8 @@ from .capi import (  # noqa: F401
     TraceParams,
     OcclusionParams,
     OcclusionWork,
+    VisibilityParams,
+    VisibilityWork,
     UpsampleParams,
     VarianceParams,
     build_native,
@@ -52,6 +54,6 @@ from . import host  # noqa: F401
 
 __all__ = [
     "capi", "host", "PathTracer", "SrtError", "Object", "Material", "Camera", "Environment",
-    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "SubsampleParams", "AntialiasParams", "VarianceParams", "DenoiseVarianceParams", "TemporalVarianceParams", "TraceParams", "OcclusionParams", "OcclusionWork", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
+    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "SubsampleParams", "AntialiasParams", "VarianceParams", "DenoiseVarianceParams", "TemporalVarianceParams", "TraceParams", "OcclusionParams", "OcclusionWork", "VisibilityParams", "VisibilityWork", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
     "load_library",
 ]

@@ -25,6 +25,11 @@ RAYS_OCCLUDED, RAYS_ALL = 16, 31
 RAYS_NORMALIZE = 1
 # any-hit queries (srt_trace_occlusion): the flags of srt_occlusion_params
 OCCLUSION_NORMALIZE, OCCLUSION_COUNT_WORK = 1, 2
+# per-pixel visibility (srt_render_visibility): the output bits, their names, the one flag and the sample limit
+VIS_AO, VIS_SUN, VIS_ALL = 1, 2, 3
+VIS_COUNT_WORK = 1
+VIS_MAX_SAMPLES = 4096
+VISIBILITY = {"ao": VIS_AO, "sun": VIS_SUN}
 # ray output names (PathTracer.ray_output / bind_ray_output) -> (output bit, numpy dtype, per-ray channels)
 RAY_OUTPUTS = dict(GBUFFERS, occluded=(RAYS_OCCLUDED, np.int32, 1))
 DENOISE_ALBEDO, DENOISE_FRAMEBUFFER = 1, 2
@@ -64,6 +69,7 @@ EXPORTS = [
     "srt_update_mode", "srt_get_update_info", "srt_mesh_image_size", "srt_read_mesh_image",
     "srt_trace_params_default", "srt_write_rays", "srt_bind_rays", "srt_bind_ray_output", "srt_trace_rays", "srt_read_ray_output",
     "srt_occlusion_params_default", "srt_trace_occlusion", "srt_get_occlusion_work",
+    "srt_visibility_params_default", "srt_render_visibility", "srt_bind_visibility", "srt_read_visibility", "srt_get_visibility_work",
 ]
 
 
@@ -190,6 +196,21 @@ class OcclusionParams(C.Structure):
 class OcclusionWork(C.Structure):
     """srt_occlusion_work: lane-level tests executed by the last counting srt_trace_occlusion for rays of its batch."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("rays", C.c_uint64), ("occluded", C.c_uint64),
+                ("analytic_tests", C.c_uint64), ("node_visits", C.c_uint64), ("triangle_tests", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class VisibilityParams(C.Structure):
+    """srt_visibility_params: a band in memory rows, VIS_* outputs, 0 or VIS_COUNT_WORK, and the AO sample range, seed and radius."""
+    _fields_ = [("row_begin", C.c_int32), ("row_end", C.c_int32), ("outputs", C.c_uint32), ("flags", C.c_uint32),
+                ("ao_samples", C.c_uint32), ("first_sample", C.c_uint32), ("seed", C.c_uint32), ("ao_radius", C.c_float)]
+
+
+class VisibilityWork(C.Structure):
+    """srt_visibility_work: what the last counting srt_render_visibility traced."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("segments", C.c_uint64), ("open", C.c_uint64), ("wave_trips", C.c_uint64),
                 ("analytic_tests", C.c_uint64), ("node_visits", C.c_uint64), ("triangle_tests", C.c_uint64)]
 
     def as_dict(self):
@@ -350,6 +371,11 @@ def open_library(path):
     L.srt_occlusion_params_default.argtypes = [C.POINTER(OcclusionParams)]
     L.srt_trace_occlusion.argtypes = [ctx, C.POINTER(OcclusionParams)]
     L.srt_get_occlusion_work.argtypes = [ctx, C.POINTER(OcclusionWork)]
+    L.srt_visibility_params_default.argtypes = [C.POINTER(VisibilityParams)]
+    L.srt_render_visibility.argtypes = [ctx, C.POINTER(VisibilityParams)]
+    L.srt_bind_visibility.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_read_visibility.argtypes = [ctx, C.c_uint32, C.POINTER(C.c_float)]
+    L.srt_get_visibility_work.argtypes = [ctx, C.POINTER(VisibilityWork)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -803,6 +829,43 @@ class PathTracer:
         """srt_get_occlusion_work: the work counts of the last trace_occlusion(count_work=True) as a dict.  Waits."""
         w = OcclusionWork()
         self._ck(self.L.srt_get_occlusion_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    # ---- per-pixel visibility ------------------------------------------------------------
+    def render_visibility(self, ao_samples=None, radius=None, sun=True, ao=True, first_sample=1, seed=0, rows=None, count_work=False):
+        """srt_render_visibility: ambient occlusion ("ao": the fraction of `ao_samples` hemisphere segments of length `radius` that
+        are unoccluded; defaults 16 and +inf) and sun visibility ("sun": n . -sun_direction where the sun is seen, else 0) per
+        pixel, from the OBJECT, NORMAL_DEPTH and POSITION guides as they stand (render_gbuffer() first, or bind them).  `rows`:
+        a band of memory rows (default: the whole frame).  count_work: SRT_VIS_COUNT_WORK (visibility_work() then reads the
+        record).  Asynchronous, like render(); visibility("ao" | "sun") reads a result."""
+        p = VisibilityParams()
+        self._ck(self.L.srt_visibility_params_default(C.byref(p)))
+        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
+        p.outputs = (VIS_AO if ao else 0) | (VIS_SUN if sun else 0)
+        p.flags = VIS_COUNT_WORK if count_work else 0
+        if ao_samples is not None:
+            p.ao_samples = int(ao_samples)
+        if radius is not None:
+            p.ao_radius = float(radius)
+        p.first_sample, p.seed = int(first_sample), int(seed)
+        self._ck(self.L.srt_render_visibility(self._h, C.byref(p)))
+
+    def visibility(self, name):
+        """srt_read_visibility: output "ao" or "sun" of the last render_visibility() as an (H, W) float32 array, rows = scene rows."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self._ck(self.L.srt_read_visibility(self._h, VISIBILITY[name], out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def bind_visibility(self, name, tensor):
+        """srt_bind_visibility: write output "ao" or "sun" into a torch tensor (H, W) float32 on this tracer's device (None: the
+        handle's own buffer), checked like bind_gbuffer's."""
+        ptr = self._tensor_ptr("bind_visibility(%r)" % name, tensor, np.float32, (self.height, self.width))
+        self._ck(self.L.srt_bind_visibility(self._h, VISIBILITY[name], ptr))
+
+    def visibility_work(self):
+        """srt_get_visibility_work: the work counts of the last render_visibility(count_work=True) as a dict.  Waits."""
+        w = VisibilityWork()
+        self._ck(self.L.srt_get_visibility_work(self._h, C.byref(w)))
         return w.as_dict()
 
     def ray_output(self, name, count=None):

@@ -30,6 +30,8 @@
 #include "srt_rays_host.h"
 #include "srt_occlusion.hip.h"
 #include "srt_occlusion_host.h"
+#include "srt_visibility.hip.h"
+#include "srt_visibility_host.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -361,6 +363,13 @@ struct srt_context {
     // (srt::OCC_WORK_N words, zeroed on the stream in front of a counting launch; never an output buffer)
     srt::OcclusionState occlusion;
     DeviceBuffer<unsigned long long> d_occlusion_work;
+    // per-pixel visibility (srt_render_visibility), one slot per SRT_VIS_* bit: the handle's own W*H floats (allocated on first
+    // use) and the caller's bound ones (srt_bind_visibility; NULL = own); what the last call wrote and whether it counted; the
+    // record a counting launch adds to (srt::VIS_WORK_N words, zeroed on the stream in front of it; never an output buffer)
+    DeviceBuffer<void> d_vis_own[srt::VIS_SLOTS];
+    void* d_vis_bound[srt::VIS_SLOTS] = {nullptr, nullptr};
+    srt::VisibilityState visibility;
+    DeviceBuffer<unsigned long long> d_visibility_work;
 
     char error[512] = "";
 };
@@ -1717,6 +1726,112 @@ int srt_get_occlusion_work(srt_context* ctx, srt_occlusion_work* out) {
     out->valid = 1, out->reserved = 0;
     out->rays = w[srt::OCC_WORK_RAYS], out->occluded = w[srt::OCC_WORK_OCCLUDED];
     out->analytic_tests = w[srt::OCC_WORK_ANALYTIC], out->node_visits = w[srt::OCC_WORK_NODES], out->triangle_tests = w[srt::OCC_WORK_TRIANGLES];
+    return SRT_OK;
+}
+
+// ---- per-pixel visibility ------------------------------------------------------------------------------------------
+static_assert(SRT_VIS_AO == srt::VIS_OUT_AO && SRT_VIS_SUN == srt::VIS_OUT_SUN && SRT_VIS_COUNT_WORK == srt::VIS_FLAG_COUNT_WORK &&
+              sizeof(srt_visibility_params) == 32 && sizeof(srt::VisibilityCall) == 32 && sizeof(srt_visibility_work) == 56,
+              "srt_visibility_host.h and srt_pathtrace.h disagree");
+
+int srt_visibility_params_default(srt_visibility_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    out->row_begin = 0, out->row_end = 0;
+    out->outputs = SRT_VIS_AO | SRT_VIS_SUN;
+    out->flags = 0;
+    out->ao_samples = 16, out->first_sample = 1, out->seed = 0;
+    out->ao_radius = INFINITY;
+    return SRT_OK;
+}
+
+int srt_render_visibility(srt_context* ctx, const srt_visibility_params* v) {
+    if (!ctx || !v) return SRT_ERR_INVALID_ARG;
+    const srt::VisibilityCall call{v->row_begin, v->row_end, v->outputs, v->flags, v->ao_samples, v->first_sample, v->seed, v->ao_radius};
+    bool present[srt::VIS_GUIDES];
+    for (int i = 0; i < srt::VIS_GUIDES; ++i) present[i] = bound_or_own(ctx->d_gbuf_bound[i], ctx->d_gbuf_own[i]) != nullptr;
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::visibility_check(call, ctx->scene_set, ctx->height, present, &why))
+        return fail(ctx, (int)rs, "srt_render_visibility: %s (rows [%d,%d) of %d, outputs 0x%x, flags 0x%x, ao_samples %u, first_sample %u, ao_radius %g)", why,
+                    v->row_begin, v->row_end, ctx->height, v->outputs, v->flags, v->ao_samples, v->first_sample, (double)v->ao_radius);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)ctx->width * (size_t)ctx->height;
+    const bool count = (v->flags & SRT_VIS_COUNT_WORK) != 0;
+    void* dst[srt::VIS_SLOTS] = {nullptr, nullptr};
+    for (int i = 0; i < srt::VIS_SLOTS; ++i) {
+        if (!(v->outputs & (1u << i))) continue;
+        if (!ctx->d_vis_bound[i]) SRT_HIP(ctx, ctx->d_vis_own[i].ensure(px * sizeof(float)));
+        dst[i] = bound_or_own(ctx->d_vis_bound[i], ctx->d_vis_own[i]);
+    }
+    if (count) {
+        if (!ctx->d_visibility_work) SRT_HIP(ctx, ctx->d_visibility_work.ensure(srt::VIS_WORK_N * sizeof(unsigned long long)));
+        SRT_HIP(ctx, hipMemsetAsync(ctx->d_visibility_work, 0, srt::VIS_WORK_N * sizeof(unsigned long long), ctx->stream));
+    }
+    // the scene side of the kernel parameters for this band, as srt_render_gbuffer takes them (the camera part is not read)
+    srt_render_params p{};
+    p.row_begin = v->row_begin, p.row_end = v->row_end, p.first_sample = 1, p.sample_count = 1;
+    srt::KernelParams K;
+    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
+    K.flags &= srt::KF_BOXES_FINITE;
+    K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // the pass touches none of them
+    const bool ao = (v->outputs & SRT_VIS_AO) != 0;
+    srt::VisibilityIO io{};
+    io.object = (const int32_t*)bound_or_own(ctx->d_gbuf_bound[0], ctx->d_gbuf_own[0]);
+    io.normal_depth = (const float4*)bound_or_own(ctx->d_gbuf_bound[1], ctx->d_gbuf_own[1]);
+    io.position = (const float4*)bound_or_own(ctx->d_gbuf_bound[2], ctx->d_gbuf_own[2]);
+    io.ao = (float*)dst[0], io.sun = (float*)dst[1];
+    io.n = ao ? v->ao_samples : 1u, io.first_sample = ao ? v->first_sample : 1u, io.seed = ao ? v->seed : 0u;
+    io.radius = ao ? v->ao_radius : INFINITY;
+    io.work = count ? (unsigned long long*)ctx->d_visibility_work : nullptr;
+    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
+    using Kernel = void (*)(srt::KernelParams, srt::VisibilityIO);
+    const Kernel plain = in_lds ? (mesh ? srt::visibility_kernel<true, true, false> : srt::visibility_kernel<true, false, false>)
+                                : (mesh ? srt::visibility_kernel<false, true, false> : srt::visibility_kernel<false, false, false>);
+    const Kernel counting = in_lds ? (mesh ? srt::visibility_kernel<true, true, true> : srt::visibility_kernel<true, false, true>)
+                                   : (mesh ? srt::visibility_kernel<false, true, true> : srt::visibility_kernel<false, false, true>);
+    const Kernel kernel = count ? counting : plain;
+    // persistent workgroups, sized as srt_render_gbuffer sizes them
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, srt::WG_THREADS, ks.lds_bytes) != hipSuccess || per_cu < 1)
+        per_cu = 1, (void)hipGetLastError();
+    per_cu = per_cu > 4 ? 4 : per_cu;
+    const long long tiles = (long long)((ctx->width + srt::TILE_W - 1) / srt::TILE_W) * ((K.rows + srt::TILE_H - 1) / srt::TILE_H);
+    const long long need = (tiles + srt::WG_TILES_X * srt::WG_TILES_Y - 1) / (srt::WG_TILES_X * srt::WG_TILES_Y);
+    const long long wgs = std::min<long long>(need, (long long)ctx->cu_count * per_cu);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io);
+    SRT_HIP(ctx, hipGetLastError());
+    srt::visibility_rendered(ctx->visibility, v->outputs, dst, v->flags);
+    return SRT_OK;
+}
+
+int srt_bind_visibility(srt_context* ctx, uint32_t output, void* d_float) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    const int i = srt::visibility_slot(output);
+    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_visibility: output 0x%x is not a single SRT_VIS_* bit", output);
+    ctx->d_vis_bound[i] = d_float;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_gbuffer)
+    return SRT_OK;
+}
+
+int srt_read_visibility(srt_context* ctx, uint32_t output, float* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const void* src = nullptr;
+    if (const srt::RaysStatus rs = srt::visibility_check_read(ctx->visibility, output, &src))
+        return fail(ctx, (int)rs, rs == srt::RAYS_STATE ? "srt_read_visibility: the last srt_render_visibility did not write output 0x%x (or there has been none)"
+                                                        : "srt_read_visibility: output 0x%x is not a single SRT_VIS_* bit", output);
+    if (const int rc = finish_stream(ctx)) return rc;
+    SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * sizeof(float), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+int srt_get_visibility_work(srt_context* ctx, srt_visibility_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::visibility_check_work(ctx->visibility) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_visibility_work: the last srt_render_visibility did not ask for SRT_VIS_COUNT_WORK (or there has been none)");
+    if (const int rc = finish_stream(ctx)) return rc;
+    unsigned long long w[srt::VIS_WORK_N];
+    SRT_HIP(ctx, hipMemcpy(w, ctx->d_visibility_work, sizeof w, hipMemcpyDeviceToHost));
+    out->valid = 1, out->reserved = 0;
+    out->segments = w[srt::VIS_WORK_SEGMENTS], out->open = w[srt::VIS_WORK_OPEN], out->wave_trips = w[srt::VIS_WORK_TRIPS];
+    out->analytic_tests = w[srt::VIS_WORK_ANALYTIC], out->node_visits = w[srt::VIS_WORK_NODES], out->triangle_tests = w[srt::VIS_WORK_TRIANGLES];
     return SRT_OK;
 }
 

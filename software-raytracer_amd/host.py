@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .capi import (OCCLUSION_COUNT_WORK, OCCLUSION_NORMALIZE, OcclusionWork, RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
+from .capi import (VIS_AO, VIS_COUNT_WORK, VIS_SUN, VISIBILITY, VisibilityParams, VisibilityWork, OCCLUSION_COUNT_WORK, OCCLUSION_NORMALIZE, OcclusionWork, RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
                    TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -34,6 +34,7 @@ EXPORTS = [
     "srt_host_renderer_temporal_variance", "srt_host_renderer_read_moments",
     "srt_host_renderer_trace_rays", "srt_host_renderer_read_ray_output",
     "srt_host_renderer_trace_occlusion", "srt_host_renderer_occlusion_work",
+    "srt_host_renderer_render_visibility", "srt_host_renderer_read_visibility", "srt_host_renderer_visibility_work",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -115,6 +116,9 @@ def load_library():
     L.srt_host_renderer_read_ray_output.argtypes = [vp, C.c_uint32, vp]
     L.srt_host_renderer_trace_occlusion.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_uint32]
     L.srt_host_renderer_occlusion_work.argtypes = [vp, C.POINTER(OcclusionWork)]
+    L.srt_host_renderer_render_visibility.argtypes = [vp, C.POINTER(VisibilityParams)]
+    L.srt_host_renderer_read_visibility.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float)]
+    L.srt_host_renderer_visibility_work.argtypes = [vp, C.POINTER(VisibilityWork)]
     L.srt_host_renderer_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
     L.srt_host_renderer_read_denoised.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
@@ -375,6 +379,26 @@ class Renderer:
         """PathTraceRenderer::occlusionWork: the work counts of the last trace_occlusion(count_work=True) as a dict."""
         w = OcclusionWork()
         self._ck(self.L.srt_host_renderer_occlusion_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def render_visibility(self, ao_samples=16, radius=float("inf"), sun=True, ao=True, first_sample=1, seed=0, rows=None, count_work=False):
+        """PathTraceRenderer::renderVisibility: render the three guides of the band with the current scene and camera, then
+        enqueue srt_render_visibility (capi.PathTracer.render_visibility's arguments; rows=None: the renderer's own band)."""
+        rb, re = (int(rows[0]), int(rows[1])) if rows is not None else (0, 0)
+        p = VisibilityParams(rb, re, (VIS_AO if ao else 0) | (VIS_SUN if sun else 0), VIS_COUNT_WORK if count_work else 0,
+                             int(ao_samples), int(first_sample), int(seed), float(radius))
+        self._ck(self.L.srt_host_renderer_render_visibility(self._h, C.byref(p)))
+
+    def visibility(self, name):
+        """PathTraceRenderer::readVisibility: output "ao" or "sun" of the last render_visibility() as an (H, W) float32 array."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_visibility(self._h, VISIBILITY[name], out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def visibility_work(self):
+        """PathTraceRenderer::visibilityWork: the work counts of the last render_visibility(count_work=True) as a dict."""
+        w = VisibilityWork()
+        self._ck(self.L.srt_host_renderer_visibility_work(self._h, C.byref(w)))
         return w.as_dict()
 
     def ray_output(self, name):

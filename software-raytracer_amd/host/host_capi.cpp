@@ -221,6 +221,10 @@ int srt_host_renderer_trace_occlusion(srt_host_renderer* h, const float* origins
     SRT_HOST_TRY(h, h->r->traceOcclusion(origins, directions, count, flags))
 }
 int srt_host_renderer_occlusion_work(srt_host_renderer* h, srt_occlusion_work* out) { SRT_HOST_TRY(h, *out = h->r->occlusionWork()) }
+// per-pixel visibility: the guides of the band, then srt_render_visibility (a band of [0, 0) means the renderer's own)
+int srt_host_renderer_render_visibility(srt_host_renderer* h, const srt_visibility_params* p) { SRT_HOST_TRY(h, h->r->renderVisibility(*p)) }
+int srt_host_renderer_read_visibility(srt_host_renderer* h, uint32_t output, float* dst) { SRT_HOST_TRY(h, h->r->readVisibility(output, dst)) }
+int srt_host_renderer_visibility_work(srt_host_renderer* h, srt_visibility_work* out) { SRT_HOST_TRY(h, *out = h->r->visibilityWork()) }
 int srt_host_renderer_read_ray_output(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->readRayOutput(output, dst)) }
 // denoiser over the whole frame with the guides as they stand (srt_denoise / srt_read_denoised)
 int srt_host_renderer_denoise(srt_host_renderer* h, const srt_denoise_params* p) { SRT_HOST_TRY(h, h->r->Denoise(*p)) }

@@ -240,6 +240,21 @@ srt_occlusion_work PathTraceRenderer::occlusionWork() {
     return w;
 }
 
+void PathTraceRenderer::renderVisibility(const srt_visibility_params& params) {
+    srt_visibility_params v = params;
+    if (v.row_begin == 0 && v.row_end == 0) v.row_begin = row_begin_, v.row_end = row_end_;
+    RenderGBufferRows(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION, v.row_begin, v.row_end);  // (pushes the camera)
+    check(srt_render_visibility(ctx_, &v), "srt_render_visibility");
+}
+
+void PathTraceRenderer::readVisibility(uint32_t output, float* dst) { check(srt_read_visibility(ctx_, output, dst), "srt_read_visibility"); }
+
+srt_visibility_work PathTraceRenderer::visibilityWork() {
+    srt_visibility_work w{};
+    check(srt_get_visibility_work(ctx_, &w), "srt_get_visibility_work");
+    return w;
+}
+
 void PathTraceRenderer::readRayOutput(uint32_t output, void* dst) { check(srt_read_ray_output(ctx_, output, dst), "srt_read_ray_output"); }
 
 void PathTraceRenderer::Denoise(const srt_denoise_params& params) { check(srt_denoise(ctx_, &params), "srt_denoise"); }

@@ -158,6 +158,15 @@ class PathTraceRenderer {
     // returns the work counts of a trace that had SRT_OCCLUSION_COUNT_WORK.
     void traceOcclusion(const float* origins, const float* directions, size_t count, uint32_t flags = 0);
     srt_occlusion_work occlusionWork();
+    // Per-pixel visibility (srt_render_visibility): ambient occlusion and sun visibility at the first hit.  renderVisibility first
+    // renders the three guides the pass reads (OBJECT, NORMAL_DEPTH, POSITION) for the band with the current scene and camera —
+    // the renderer cannot know whether the ones in the handle are stale, as with the denoiser's — and then enqueues the pass;
+    // a params band of [0, 0) (srt_visibility_params_default's) means the renderer's own band.  Asynchronous.  readVisibility
+    // waits and copies the W x H floats of ONE output (SRT_VIS_AO or SRT_VIS_SUN, scene rows); visibilityWork waits and returns
+    // the work counts of a call that had SRT_VIS_COUNT_WORK.
+    void renderVisibility(const srt_visibility_params& params);
+    void readVisibility(uint32_t output, float* dst);
+    srt_visibility_work visibilityWork();
     // Denoiser (srt_denoise) over the whole frame: the accumulator guided by the first-hit buffers as they stand (call
     // RenderGBuffer first).  Asynchronous; ReadDenoised waits and copies the W x H float4 result (scene rows).
     void Denoise(const srt_denoise_params& params);

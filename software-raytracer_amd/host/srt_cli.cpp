@@ -2,6 +2,7 @@
 // JSON format, path-trace it on one MI355X, write the framebuffer as a binary PPM (P6)
 // top-down (the framebuffer's memory rows are already in blit order, Raytracer.cpp:64).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -120,6 +121,7 @@ static void usage() {
                  "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]\n"
                  "                  [--move-object IDX:DX,DY,DZ]... [--refit]] [--steps N] [--upsample PATH] [--aa K]\n"
                  "                  [--denoise-variance PATH] [--temporal-variance]\n"
+                 "                  [--ao N [--ao-radius R]] [--sun-visibility] [--vis-out FILE]\n"
                  "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--any-hit] [--device 0]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
@@ -158,12 +160,21 @@ static void usage() {
                  "             one after the other: object (N int32), normal_depth, position, albedo (N x 4 float32 each), occluded\n"
                  "             (N int32); --rays-normalize normalizes every direction first; single device, no other output\n"
                  "  --any-hit: with --rays, ask srt_trace_occlusion (is there a hit with distance < t_max?) instead; --rays-out then receives\n"
-                 "             the occluded array (N int32) alone, with the bits the closest-hit query gives it\n");
+                 "             the occluded array (N int32) alone, with the bits the closest-hit query gives it\n"
+                 "  --ao N:    after the frame, per-pixel ambient occlusion (srt_render_visibility): the fraction of N (1..4096) hemisphere\n"
+                 "             segments of length --ao-radius (default: unbounded) at the first hit that are unoccluded; samples 1..N, --seed\n"
+                 "  --sun-visibility: after the frame, per-pixel sun visibility: n . -sunDirection where the sun is seen, else 0\n"
+                 "  --vis-out: receives the raw float32 planes (W x H each, scene rows), AO then SUN, whichever were asked for;\n"
+                 "             needs --ao or --sun-visibility; single device, not with --temporal\n");
 }
 
 int main(int argc, char** argv) {
     std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise, upsample, denoise_variance, rays_in, rays_out;
     bool rays_normalize = false, rays_any_hit = false;
+    std::string vis_out;
+    int ao = 0;
+    bool ao_given = false, sun_visibility = false;
+    float ao_radius = INFINITY;
     int temporal = 0, steps = 1, aa = 0;
     bool aa_given = false, temporal_variance = false, refit = false;
     float move[3] = {0, 0, 0}, turn_deg = 0;
@@ -215,6 +226,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rays-out")) rays_out = need("--rays-out");
         else if (!std::strcmp(argv[i], "--rays-normalize")) rays_normalize = true;
         else if (!std::strcmp(argv[i], "--any-hit")) rays_any_hit = true;
+        else if (!std::strcmp(argv[i], "--ao")) ao = std::atoi(need("--ao")), ao_given = true;
+        else if (!std::strcmp(argv[i], "--ao-radius")) ao_radius = std::strtof(need("--ao-radius"), nullptr);
+        else if (!std::strcmp(argv[i], "--sun-visibility")) sun_visibility = true;
+        else if (!std::strcmp(argv[i], "--vis-out")) vis_out = need("--vis-out");
         else if (!std::strcmp(argv[i], "--temporal")) temporal = std::atoi(need("--temporal"));
         else if (!std::strcmp(argv[i], "--turn")) turn_deg = std::strtof(need("--turn"), nullptr);
         else if (!std::strcmp(argv[i], "--move")) {
@@ -270,6 +285,12 @@ int main(int argc, char** argv) {
     if (!rays_in.empty() && (!devices.empty() || temporal || steps > 1 || aa_given || !gbuffer.empty() || !denoise.empty() || !upsample.empty() ||
                              !denoise_variance.empty())) {
         std::fprintf(stderr, "--rays answers ray queries instead of rendering a frame: single device, no frame options\n");
+        return 2;
+    }
+    if ((ao_given || sun_visibility) == vis_out.empty() || (ao_given && (ao < 1 || ao > 4096)) || (!ao_given && ao_radius != INFINITY) || !(ao_radius > 0) ||
+        (!vis_out.empty() && (!devices.empty() || temporal || !rays_in.empty()))) {
+        std::fprintf(stderr, "--ao N (1..4096) [--ao-radius R > 0] and --sun-visibility need --vis-out FILE and the other way round; single device, "
+                             "not with --temporal or --rays\n");
         return 2;
     }
     if (temporal_variance && (!temporal || !devices.empty() || steps > 1 || !upsample.empty())) {
@@ -442,6 +463,32 @@ int main(int argc, char** argv) {
         r.ReadFramebuffer(fb.data(), (size_t)W * 4);
         if (write_ppm(fb, out)) return 1;
         if (!gbuffer.empty() && write_gbuffers(r, gbuffer, W, H)) return 1;
+        if (!vis_out.empty()) {
+            // the guides of the whole frame, then the visibility pass; the planes asked for follow each other in the file, AO first
+            srt_visibility_params vp{};
+            srt_visibility_params_default(&vp);
+            vp.outputs = (ao_given ? SRT_VIS_AO : 0u) | (sun_visibility ? SRT_VIS_SUN : 0u);
+            if (ao_given) vp.ao_samples = (uint32_t)ao, vp.ao_radius = ao_radius;
+            vp.seed = seed;
+            r.renderVisibility(vp);
+            FILE* g = std::fopen(vis_out.c_str(), "wb");
+            if (!g) {
+                std::perror(vis_out.c_str());
+                return 1;
+            }
+            bool ok = true;
+            std::vector<float> plane((size_t)W * H);
+            for (uint32_t bit = SRT_VIS_AO; bit <= SRT_VIS_SUN; bit <<= 1) {
+                if (!(vp.outputs & bit)) continue;
+                r.readVisibility(bit, plane.data());
+                ok = ok && std::fwrite(plane.data(), sizeof(float), plane.size(), g) == plane.size();
+            }
+            ok = (std::fclose(g) == 0) && ok;
+            if (!ok) {
+                std::fprintf(stderr, "%s: write failed\n", vis_out.c_str());
+                return 1;
+            }
+        }
         if (!upsample.empty()) {
             // the guides of the whole frame, then the blocks' anchors interpolated with the library's defaults; the kernel
             // tone-maps its result into the framebuffer (--out is already written).  With --denoise the result replaces the
