@@ -1084,6 +1084,7 @@ struct RenderLaunch {
     srt::LaunchShape shape;
     bool bgrid = false;   // progressive blocks: one lane per block
     bool defer = false;   // sample chunks (shape.chunks >= 2)
+    bool rows = false;    // one chunk whose sample colours go through rows of the sample buffer (srt::fold_from_rows)
     dim3 grid;
     bool record = false;  // the launch records its blocks' costs
 };
@@ -1097,7 +1098,7 @@ struct RenderLaunch {
 // the block's colour into its own mean) — the launch's lanes are blocks, not pixels: 1 / steps^2 of the lanes, one
 // ray per block, steps^2 pixel stores per lane (Raytracer.cpp:235-248).  Anything else (several samples onto an
 // accumulated frame) keeps one lane per pixel with the block's ray traced once per wave tile.
-static int plan_launch(srt_context* ctx, const srt_render_params* p, srt::KernelParams& K, RenderLaunch& L) {
+static int plan_launch(srt_context* ctx, const srt_render_params* p, srt::KernelParams& K, const KernelSetup& ks, RenderLaunch& L) {
     const int W = ctx->width;
     L.bgrid = K.steps > 1 && ((K.flags & SRT_RENDER_RESET) || p->sample_count == 1);
     long long grid_w = W, grid_h = K.rows;
@@ -1144,6 +1145,13 @@ static int plan_launch(srt_context* ctx, const srt_render_params* p, srt::Kernel
     }
     srt::finish_launch_shape(shape, p->sample_count, ov);
     L.defer = shape.chunks >= 2;
+    // One chunk of full tiles: the colours go through rows of the sample buffer and the ring leaves LDS (srt_launch_shape.h,
+    // fold_from_rows).  Without the buffer the launch keeps the ring: same bits.
+    L.rows = srt::fold_from_rows(shape, req, (p->flags & SRT_RENDER_PREVIEW) != 0, ctx->scene_in_lds[ks.img]);
+    if (L.rows && ctx->d_samples.ensure((size_t)srt::rows_bytes(shape, p->sample_count)) != hipSuccess) {
+        (void)hipGetLastError();
+        L.rows = false;
+    }
     K.tile_h = shape.tile_h;
     K.chunk = L.defer ? shape.chunk : 0;
     K.chunk_full = shape.chunk_full;
@@ -1245,6 +1253,18 @@ static void launch_pathtrace(bool tally, bool in_lds, bool multi, bool defer, di
     hipLaunchKernelGGL(kernel, grid, dim3(srt::WG_THREADS), lds_bytes, stream, K);
 }
 
+// The ROWS instantiations of the analytic pair — a launch in one chunk of full tiles whose sample colours go through rows of the sample
+// buffer (RenderLaunch.rows; the scene image is in LDS) — in place of k_lds / t_lds: the recording and the counting launch keep the
+// timed launch's shape.  Their workgroups have no ring in LDS.  Bit-identical to the others.
+template <int MIN_WAVES, bool MESH>
+static void launch_pathtrace_rows(bool tally, dim3 grid, size_t lds_bytes, hipStream_t stream, const srt::KernelParams& K) {
+    using srt::pathtrace_kernel;
+    void (*const kernel)(srt::KernelParams) =
+        tally ? pathtrace_kernel<MIN_WAVES, MESH, true, false, false, false, true, true>     // t_lds_rows
+              : pathtrace_kernel<MIN_WAVES, MESH, true, false, false, false, false, true>;   // k_lds_rows
+    hipLaunchKernelGGL(kernel, grid, dim3(srt::WG_THREADS), lds_bytes - (size_t)(srt::WG_SCRATCH_BYTES - srt::WG_SCRATCH_BYTES_ROWS), stream, K);
+}
+
 // The TALLY instantiations keep the wave-uniform loop counts (srt_kernel.hip.h, Tally): the recording launch of a band (its
 // blocks' work is the launch-shape record) and launches with SRT_RENDER_COUNT_WORK.  Scene images that live in HBM have none
 // (a correctness fallback): such launches keep the static shape rule and report no work counts.
@@ -1274,6 +1294,8 @@ static int launch_render(srt_context* ctx, const srt_render_params* p, srt::Kern
     else if (ks.use == 3 && in_lds && !multi && !L.defer && !tally)
         hipLaunchKernelGGL((srt::pathtrace_kernel<3, false>), L.grid, dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K);
 #endif
+    else if (L.rows)  // (one chunk of full tiles of an analytic scene in LDS, never `multi` or L.defer)
+        launch_pathtrace_rows<5, false>(tally, L.grid, ks.lds_bytes, ctx->stream, K);
     else
         // (five waves per SIMD, 96 VGPRs.  Since srt_powf's coefficients come from the LDS constants block — the 64-bit literals had
         // been living in hoisted register pairs — the kernels need 85..95 registers, the multi-sample hand-out of small tiles /
@@ -1322,7 +1344,7 @@ int srt_render(srt_context* ctx, const srt_render_params* p) {
     if (ctx->count_rays) SRT_HIP(ctx, hipMemsetAsync(ctx->d_rays, 0, sizeof(unsigned long long), ctx->stream));
     RenderLaunch L;
     if (const int rc = enter_band(ctx, K)) return rc;
-    if (const int rc = plan_launch(ctx, p, K, L)) return rc;
+    if (const int rc = plan_launch(ctx, p, K, ks, L)) return rc;
     if (const int rc = plan_cost_order(ctx, p, K, ks, L)) return rc;
     if (const int rc = launch_render(ctx, p, K, ks, L)) return rc;
     note_pending(ctx, p, K, L);

@@ -13,7 +13,7 @@
 //   * primary rays do not depend on the sample (no jitter, Raytracer.cpp:109-110): the primary
 //     hit is found once per pixel; pixels whose colour is sample-invariant finish immediately.
 //   * wave-level path pool: traced pixels are compacted into slots (ballot + mbcnt); free lanes
-//     pull (slot, sample) tasks, finished sample colours go through an LDS ring and are folded
+//     pull (slot, sample) tasks, finished sample colours go through an LDS ring (ROWS instantiations: rows in global memory) and are folded
 //     into the order-dependent running mean (Raytracer.cpp:65-71) strictly in sample order by the
 //     slot's owner lane; one 16-byte accumulator store + one 4-byte ARGB store per pixel.
 //   * closest_hit runs in wave-uniform control flow (idle lanes help):
@@ -155,10 +155,17 @@ constexpr int WORK_MAX = 512;
 // runs FIVE waves per SIMD (96 VGPRs) and the mesh kernel FOUR (128): that many workgroups' LDS fit into a CU's 160 KiB only
 // with the shorter ring.  With unchanged occupancy the shorter ring costs 3..7 % (a slot whose sample runs long can have only one
 // more in flight); the extra wave wins that back and more: Scene_indirect -4.4 %, Scene3 -4.5 %, Scene1 -1.5 %, config 4 -5 %.
+// The ROWS instantiations of pathtrace_kernel (single-chunk launches of full tiles, srt_launch_shape.h: fold_from_rows) have no
+// ring at all: their sample colours go through rows of the sample buffer in global memory, and nothing limits how far a slot runs
+// ahead.  Everything else — small tiles, blocks, sample chunks, the probe — keeps this ring.
 constexpr int RING_DEPTH = 2;
-// per-wave: 64 result slots (8 B) | work list (2 B) | 64 pixel records (48 B) | ring (16 B)
-constexpr int WAVE_SCRATCH_BYTES = 64 * 8 + WORK_MAX * 2 + 64 * 12 * 4 + 64 * RING_DEPTH * 16;
+constexpr int WAVE_RING_BYTES = 64 * RING_DEPTH * 16;
+// per-wave: 64 result slots (8 B) | work list (2 B) | 64 pixel records (48 B) | ring (16 B; not in the ROWS instantiations)
+constexpr int WAVE_SCRATCH_BYTES = 64 * 8 + WORK_MAX * 2 + 64 * 12 * 4 + WAVE_RING_BYTES;
 constexpr int WG_SCRATCH_BYTES = WAVE_SCRATCH_BYTES * WG_TILES_X * WG_TILES_Y;
+// row loads a lane of the ROWS fold keeps in flight: 8, fold_kernel's count (4: config 2 +3 %, Scene3 +2.6 %, profiles/r05/ab_notes.txt)
+constexpr int ROWS_IN_FLIGHT = 8;
+constexpr int WG_SCRATCH_BYTES_ROWS = (WAVE_SCRATCH_BYTES - WAVE_RING_BYTES) * WG_TILES_X * WG_TILES_Y;
 // extra per-wave LDS of the mesh kernel: node LIFO + leaf queue of the cooperative BVH traversal
 // (sized so that three workgroups of the mesh kernel still fit into a CU's 160 KiB next to the Scene1-sized image)
 constexpr int MESH_Q = 512;  // entries of the traversal buffer: the node LIFO grows up from its bottom, the leaf queue down from its top
@@ -1265,9 +1272,9 @@ __device__ __forceinline__ void store_pixel(const KernelParams& P, uint32_t pix,
 // [waves x MESH_WAVE_BYTES (mesh kernel only)].  SCENE_LDS == false is the fallback for scene images
 // that do not fit next to the scratch (thousands of analytic primitives): the same image is then read
 // from HBM/L2 through the same accessors — slower per test, same arithmetic, same bits.
-template <bool SCENE_LDS>
+template <bool SCENE_LDS, bool ROWS = false>
 __device__ __forceinline__ Lds make_lds(const KernelParams& P, float4* lds, int waves, int wave) {
-    constexpr int stride = WAVE_SCRATCH_BYTES;
+    constexpr int stride = WAVE_SCRATCH_BYTES - (ROWS ? WAVE_RING_BYTES : 0);  // (ROWS: Lds::ring points past the wave's scratch and is never used)
     char* wg = reinterpret_cast<char*>(lds + (SCENE_LDS ? P.scene_vec4 : 0));
     char* scratch = wg + wave * stride;
     const float4* image;
@@ -1294,9 +1301,15 @@ __device__ __forceinline__ Lds make_lds(const KernelParams& P, float4* lds, int 
 // TALLY: the instantiation that keeps the wave-uniform loop counts (see Tally): the recording launch of a band, and launches with
 // SRT_RENDER_COUNT_WORK.  Same results; a few scalar adds per pool step and some scalar-register pressure the steady-state
 // instantiations do not pay.
-template <int MIN_WAVES, bool MESH, bool SCENE_LDS = true, bool MULTI = false, bool DEFER = false, bool PROBE = false, bool TALLY_ = false>
+// ROWS: a single-chunk launch of full tiles whose sample colours go through GLOBAL memory instead of the LDS ring (the host's
+// rule: srt_launch_shape.h, fold_from_rows).  A finished path stores its colour into row (tile, sample), slot k, of P.sample_rows
+// — the sample-chunked launches' layout — and the wave folds its own tile ONCE, after its pool has drained: all 64 lanes at work,
+// in sample order, coalesced 16-byte loads.  No ring in LDS, no fold inside the loop, and a slot may run any number of samples
+// ahead, so a long path never stalls its slot's hand-out.  Same bits: the same colours meet the same running mean in the same order.
+template <int MIN_WAVES, bool MESH, bool SCENE_LDS = true, bool MULTI = false, bool DEFER = false, bool PROBE = false, bool TALLY_ = false, bool ROWS = false>
 __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const KernelParams P) {
     static_assert(!PROBE || (!MULTI && !DEFER), "the probe runs the full-tile pool");
+    static_assert(!ROWS || (!MULTI && !DEFER && !PROBE), "rows of the sample buffer: one chunk, full tiles, a real launch");
     constexpr bool TALLY = TALLY_ || PROBE;
     extern __shared__ float4 lds_scene[];
     Tally<TALLY> tally{};
@@ -1326,7 +1339,7 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
         for (int i = (int)threadIdx.x + STAGE * WG_THREADS; i < n; i += WG_THREADS) lds_scene[i] = P.scene[i];
         __syncthreads();
     }
-    const Lds S = make_lds<SCENE_LDS>(P, lds_scene, WG_TILES_X * WG_TILES_Y, threadIdx.x >> 6);
+    const Lds S = make_lds<SCENE_LDS, ROWS>(P, lds_scene, WG_TILES_X * WG_TILES_Y, threadIdx.x >> 6);
     // the probe: ONE of the workgroup's four waves — the four hold the same mix of pixels (dealt pixel by pixel, see below), so a
     // quarter of the pixels stands for the block, and the samples go into depth instead: a pool that runs 8 samples per pixel has
     // 12..37 % more steps per sample than a launch's chunks of 32 and more (the tail of a tile), unevenly over the frame
@@ -1586,13 +1599,16 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
             r[10] = __uint_as_float(srt_mix32(srt_mix32(P.seed ^ 0xA511E9B3U) + rng_pixel));
             r[11] = __uint_as_float(pixel);
         }
+        // (ROWS: none of the ring's bookkeeping — depth, ring_row, ring, own_done, fold_pace — is used; it stays declared for the
+        // code the two forms share and compiles to nothing)
         constexpr int ring_depth = RING_DEPTH;
         const int depth = (64 * ring_depth) / n_hit;  // ring entries per slot (>= ring_depth)
         // sample -> ring row: a mask when depth is a power of two (full tiles: 4), else a real modulo (~20 instructions)
         const bool depth_pow2 = (depth & (depth - 1)) == 0;
         auto ring_row = [&](uint32_t s) { return depth_pow2 ? (s & (uint32_t)(depth - 1)) : (s % (uint32_t)depth); };
         float4* ring = S.ring;                        // [depth][n_hit] of (r, g, b, tag: sample | alpha_tag)
-        for (int i = lane; i < 64 * ring_depth; i += 64) ring[i] = make_float4(0, 0, 0, __uint_as_float(0xFFFFFFFFu));
+        if constexpr (!ROWS)
+            for (int i = lane; i < 64 * ring_depth; i += 64) ring[i] = make_float4(0, 0, 0, __uint_as_float(0xFFFFFFFFu));
         __builtin_amdgcn_wave_barrier();
 
         // owner state (lane k owns slot k)
@@ -1611,7 +1627,7 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
         uint32_t fdone = fold_px ? 0u : count;
         if (blocks) {
             if (fold_px && !reset) acc = P.accumulator[pixel];
-        } else if (owner) {
+        } else if (!ROWS && owner) {  // (ROWS: read after the loop, where the fold is)
             own_pixel = __float_as_uint(rec[lane * 12 + 11]);
             if (!DEFER && !reset && !bgrid) acc = P.accumulator[own_pixel];
         }
@@ -1639,7 +1655,8 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
 
         // per-slot hand-out state, kept by the owner lane: samples [0, own_next) have been
         // handed out, [0, own_done) folded.  A slot may run `depth` samples ahead of its own
-        // fold point (ring capacity); slots do not wait for each other.
+        // fold point (ring capacity); slots do not wait for each other.  (ROWS: nothing is folded in the loop, own_done stays
+        // put, and the capacity is the launch's sample count.)
         uint32_t own_next = own_done;
         int rot = 0;  // wave-uniform rotation of the slot priority
         unsigned handed = 0;  // wave-uniform: samples handed out so far (n_hit x the mean own_next)
@@ -1653,6 +1670,9 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
             // second sample ready (finished out of order) wait for the next step, where they share the iteration with many
             // others — a further iteration for their sake costs the whole wave a fold.  Once the hand-out has ended, or nothing
             // runs, everything ready is folded.
+            if constexpr (ROWS) {  // no fold here: leave when nothing runs and nothing is left to hand out
+                if (__builtin_amdgcn_ballot_w64(busy || own_next < count) == 0ull) break;
+            } else {
             const bool drain = __builtin_amdgcn_ballot_w64(busy) == 0ull || __builtin_amdgcn_ballot_w64(own_next < count) == 0ull;
             // (Round 3, with the ring of two entries: folding eagerly — every step, up to `depth` iterations, no waiting for a
             // fifth of the slots — frees ring capacity sooner but costs more folds than it gains: +2..+7 %.)
@@ -1708,6 +1728,7 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
                 }
             }
             if (__builtin_amdgcn_ballot_w64(own_done < count) == 0ull) break;  // every slot finished
+            }
 
             SRT_TICK(0);
             // ---- hand out tasks: the i-th free lane takes the next sample of the i-th slot that has ring
@@ -1721,7 +1742,7 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
             bool fresh = false;
             for (int pass = 0; pass < 2; ++pass) {
                 const unsigned long long freem = __builtin_amdgcn_ballot_w64(!busy);
-                const uint32_t lim = count < own_done + (uint32_t)depth ? count : own_done + (uint32_t)depth;
+                const uint32_t lim = ROWS ? count : count < own_done + (uint32_t)depth ? count : own_done + (uint32_t)depth;
                 const int avail = own_next < lim ? (int)(lim - own_next) : 0;
                 const bool can = avail > 0;
                 const unsigned long long canm = __builtin_amdgcn_ballot_w64(can);
@@ -1733,6 +1754,8 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
                 // entries a slot that fell behind stalls the tail of the tile (lanes idle while its last samples run one after
                 // the other); serving the laggards first keeps the slots level, ~5 % fewer pool steps (tests/pool_stats.py)
                 rot = (rot + 23) & 63;
+                // (ROWS, no ring to run out of: the tier still pays — level slots keep more of them handing out at the tile's tail;
+                // without it config 2 +1 %, Scene1_reflection +2.6 %, Scene_indirect -1 %, profiles/r05/ab_notes.txt)
                 const unsigned long long lagm = __builtin_amdgcn_ballot_w64(can && (unsigned)__umul24(own_next, (unsigned)n_hit) <= handed);
                 const unsigned long long restm = canm & ~lagm;
                 // rank inside a tier, counted cyclically from lane `rot`: bits below the lane, minus the bits below `rot`,
@@ -1872,13 +1895,45 @@ __global__ void __launch_bounds__(WG_THREADS, MIN_WAVES) pathtrace_kernel(const 
                 }
                 if (end_path) {  // hand the sample colour to the slot's owner
                     const uint32_t sidx = task >> 6;
-                    ring[ring_row(sidx) * n_hit + (int)(task & 63u)] = make_float4(L.r, L.g, L.b, __uint_as_float(sidx | atag));
+                    const float4 e = make_float4(L.r, L.g, L.b, __uint_as_float(sidx | atag));
+                    if constexpr (ROWS)  // row (tile, sample) of the sample buffer, the slot's 16 bytes — (tile * count + sample) * 64 + slot,
+                        P.sample_rows[tile_id * count * 64 + task] = e;  // and task = sample * 64 + slot; written exactly once
+                    else
+                        ring[ring_row(sidx) * n_hit + (int)(task & 63u)] = e;
                     busy = false;
                 }
             }
             __builtin_amdgcn_wave_barrier();
         }
-        if (blocks) {
+        if constexpr (ROWS) {
+            // The wave's own stores, made by whichever lane ran the path, are read back by the slots' owner lanes.  The release /
+            // acquire pair at workgroup scope keeps the compiler from moving the loads above the stores and is what the memory model
+            // asks for; on gfx950 (no threadgroup-split mode) it emits no s_waitcnt vmcnt and no cache operation.  What the read-back
+            // relies on in hardware: the wave's vector memory operations reach this CU's L1 in issue order, the L1 is write-through, and
+            // no other wave, on this CU or another, ever touches the tile's rows.
+            SRT_TICK(7);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            if (owner) {  // lane k folds rows 0 .. count-1 of slot k, in sample order (fold_kernel's loop)
+                own_pixel = __float_as_uint(rec[lane * 12 + 11]);
+                if (!reset) acc = P.accumulator[own_pixel];
+                const float4* row = P.sample_rows + tile_id * count * 64 + lane;
+                uint32_t s = 0;
+                for (; s + ROWS_IN_FLIGHT <= count; s += ROWS_IN_FLIGHT) {
+                    float4 c[ROWS_IN_FLIGHT];
+#pragma unroll
+                    for (int k = 0; k < ROWS_IN_FLIGHT; ++k) c[k] = row[(size_t)(s + k) * 64];
+#pragma unroll
+                    for (int k = 0; k < ROWS_IN_FLIGHT; ++k) accumulate(acc, RGB{c[k].x, c[k].y, c[k].z}, tag_alpha(__float_as_uint(c[k].w)), s + k);
+                }
+                for (; s < count; ++s) {
+                    const float4 c = row[(size_t)s * 64];
+                    accumulate(acc, RGB{c.x, c.y, c.z}, tag_alpha(__float_as_uint(c.w)), s);
+                }
+                write_pixel(own_pixel, acc);
+            }
+            SRT_TICK(0);  // (the fold's section)
+        } else if (blocks) {
             if (fold_px) write_pixel(pixel, acc);
         } else if (MULTI && bgrid) {
             const int oy = (int)(own_pixel / (uint32_t)W), ox = (int)(own_pixel - (uint32_t)oy * (uint32_t)W);

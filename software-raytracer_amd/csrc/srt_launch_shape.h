@@ -238,4 +238,32 @@ inline void finish_launch_shape(LaunchShape& s, uint32_t sample_count, const Sha
     }
 }
 
+// Fold from rows (pathtrace_kernel's ROWS instantiations): a launch that keeps every tile in ONE workgroup sends its finished sample
+// colours through rows of the sample buffer in global memory instead of the ring in LDS, and every wave folds its tile once, after
+// its pool has drained.  For launches in one chunk of full 8-row tiles, one lane per pixel (no progressive blocks, no block grid, no
+// preview shader: those are the small-tile hand-out's or trace nothing), analytic scenes whose image is in LDS, from ROWS_MIN_SAMPLES samples on, while the rows — 1 KiB
+// per tile and sample — stay within ROWS_MAX_BYTES.  The cap is a constant, not a share of what the device has free: the same
+// request takes the same kernel on every machine.  (Whether the buffer can then be had is the caller's to find out; without it
+// the launch keeps the ring.)  Call with the finished shape (finish_launch_shape).
+// The minimum, measured (interleaved A/B against the ring kernel, Scene1 at 1080p, profiles/r05/ab_notes.txt): 2 samples -5 %,
+// 3 / 4 / 6 / 8 -9 %, 16 -7 % (noise floor 0.1 .. 1.8 %); Scene_indirect 4 / 8 samples -5 %.  No count with a loss was found; a
+// one-sample launch has nothing to run ahead of and keeps the ring.
+constexpr uint32_t ROWS_MIN_SAMPLES = 2;
+constexpr unsigned long long ROWS_MAX_BYTES = 4ull << 30;  // a 1080p frame of 32 samples takes 1.0 GiB, a 4K frame of 32 samples 3.96 GiB
+inline bool fold_from_rows(const LaunchShape& s, const ShapeRequest& q, bool preview, bool scene_in_lds) {
+    if (s.chunks >= 2 || s.tile_h != SHAPE_TILE_H || q.block_grid || q.steps > 1 || preview) return false;
+    // Mesh scenes keep the ring: the mesh kernel waits for BVH loads all through its loop, and each of those waits then also
+    // waits for the row stores before it — config 4 +4.7 % with rows (noise floor 0.8 %, profiles/r05/ab_notes.txt).
+    // A scene image that lives in memory, not in LDS, has the same loads in its loop: Scene1 with such an image +1.2 % at 32 samples
+    // (floor 0.3 %), Scene_indirect +2.3 % (0.2 %), Scene1 at 8 samples -2.4 %.  These keep the ring too.
+    if (q.mesh || !scene_in_lds) return false;
+    if (q.sample_count < ROWS_MIN_SAMPLES || s.wg8 < 1) return false;
+    // tiles x samples KiB <= the cap, without a product that could wrap
+    return (unsigned long long)s.wg8 <= ROWS_MAX_BYTES / 1024ull / q.sample_count / SHAPE_WAVES_PER_WG;
+}
+// the rows of a launch that fold_from_rows accepts
+inline unsigned long long rows_bytes(const LaunchShape& s, uint32_t sample_count) {
+    return (unsigned long long)s.wg8 * SHAPE_WAVES_PER_WG * sample_count * 1024ull;
+}
+
 }  // namespace srt

@@ -1,0 +1,221 @@
+"""Launches whose sample colours go through rows of the sample buffer (pathtrace_kernel's ROWS instantiations, chosen by
+srt::fold_from_rows in csrc/srt_launch_shape.h) against the oracle: framebuffer and all four accumulator lanes bit for bit, NaNs
+compared as NaNs.
+
+The frame is 40 x 24: 3 x 2 blocks of 16 x 16 pixels with partial blocks in both directions (waves with 32 and with 16 pixels in
+range), tiles that mix sky and traced pixels (fewer than 64 slots), more than one workgroup.  On such a frame the rule takes the
+rows path for ROWS_MIN_SAMPLES <= spp < 16 (from 16 samples on a frame of few blocks gets small tiles, from 64 sample chunks,
+tests/native/rows_rule_check.cpp): the sample counts below lie on both sides of each of these thresholds, and those inside the
+window cover a fold of whole groups of row loads (8), of a group and a remainder (12, 13, 15), of a remainder alone (3, 7) and of
+the minimum.  Mesh scenes and scenes whose image lives in memory keep the ring (the rule excludes them: both measured slower
+with rows); the mesh and the NaN-alpha case pin that such launches are unchanged.  The library does not report which kernel a
+launch took (no ABI change).  The counting launch's pool steps tell: on this frame the rows hand-out takes 241 steps at 8 samples
+and 394 at 15, the ring of two entries 331 and 543 (counts, the same in every run); test_counting_launch pins them, so a launch
+that silently fell back to the ring fails there.  The rule itself is checked on the CPU.
+"""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, scene_path
+
+W, H = 40, 24
+THREADS = 16
+
+
+def _rows_min():
+    src = open(os.path.join(ROOT, "software-raytracer_amd", "csrc", "srt_launch_shape.h")).read()
+    return int(re.search(r"constexpr uint32_t ROWS_MIN_SAMPLES = (\d+);", src).group(1))
+
+
+MIN = _rows_min()
+_SCENES, _ORACLE = {}, {}
+
+
+def _scene(oracle, kind):
+    """kind -> (objects, count, meshes or None); built once"""
+    if kind not in _SCENES:
+        objs = oracle.load_scene_json_py(scene_path("Scene1"))
+        meshes = None
+        if kind == "mesh":  # a small tessellated ball (8 x 8) in front of the scene, and a second instance of it
+            objs.insert(2, dict(type=oracle.OBJ_MESH, position=(0.4, -0.2, 3.0), mesh=0, base=(.9, .3, .2), specular_amount=0.5, smoothness=0.8))
+            objs.append(dict(type=oracle.OBJ_MESH, position=(-0.8, 0.2, 3.6), mesh=0, base=(.2, .8, .3), emissive=(0.4, 0.4, 0.1)))
+            marr, mn, keep = oracle.make_meshes([oracle.uv_sphere(0.7, 8, 8)])
+            meshes = (marr, mn, keep)
+        elif kind == "rinf":  # test_gpu_parity's spheres of infinite radius: bounce rays turn NaN, and with them the samples' alpha
+            inf = float("inf")
+            objs.insert(3, dict(type=oracle.OBJ_SPHERE, position=(0.0, 0.0, 2.0), radius=inf, base=(.9, .2, .1), emissive=(0.5, 0.5, 0.5)))
+            objs.append(dict(type=oracle.OBJ_SPHERE, position=(0.3, 0.1, 3.0), radius=inf, base=(.1, .9, .1)))
+        elif kind == "nansmooth":
+            objs.append(dict(type=oracle.OBJ_SPHERE, position=(0.3, 0.1, 3.0), radius=0.6, base=(.9, .2, .1), specular_amount=0.5, smoothness=float("nan")))
+        else:
+            assert kind == "scene1"
+        oarr, n = oracle.make_objects(objs)
+        _SCENES[kind] = (oarr, n, meshes)
+    return _SCENES[kind]
+
+
+def _tracer(srt, sc):
+    pt = srt.PathTracer(W, H)
+    if sc[2]:
+        pt.set_meshes(C.cast(sc[2][0], C.POINTER(srt.Mesh)), sc[2][1])
+    pt.set_scene(C.cast(sc[0], C.POINTER(srt.Object)), sc[1])
+    pt.set_camera(srt.default_camera())
+    return pt
+
+
+def _reference(oracle, kind, **call):
+    """the oracle's (framebuffer, accumulator, rays) of a request that starts a frame; computed once per request"""
+    key = (kind,) + tuple(sorted(call.items()))
+    if key not in _ORACLE:
+        sc = _scene(oracle, kind)
+        fb, acc, rays = oracle.render(sc[0], sc[1], oracle.default_environment(), oracle.default_camera(), W, H, threads=THREADS,
+                                      accumulator=np.zeros((H, W, 4), np.float32), meshes=(sc[2][0], sc[2][1]) if sc[2] else None, **call)
+        fb.setflags(write=False), acc.setflags(write=False)
+        _ORACLE[key] = (fb, acc, rays)
+    return _ORACLE[key]
+
+
+def _assert_same(pt, ref, rows=None):
+    ofb, oacc, _ = ref
+    acc = pt.accumulator()
+    nan = np.isnan(acc) | np.isnan(oacc)
+    assert np.array_equal(np.isnan(acc), np.isnan(oacc))
+    bad = np.where(nan, False, acc.view(np.uint32) != oacc.view(np.uint32))
+    assert not bad.any(), (int(bad.sum()), np.argwhere(bad)[:8].tolist())
+    rb, re_ = rows if rows is not None else (0, H)
+    assert np.array_equal(pt.framebuffer(rows=(rb, re_)), ofb[rb:re_])
+
+
+SPPS = sorted({MIN - 1, MIN, 3, 7, 8, 12, 13, 15, 16, 32, 33})
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("spp", SPPS)
+def test_sample_counts_around_the_thresholds(srt, oracle, spp):
+    pt = _tracer(srt, _scene(oracle, "scene1"))
+    pt.render(spp=spp, bounces=8, seed=5, count_rays=True)
+    ref = _reference(oracle, "scene1", spp=spp, bounces=8, seed=5)
+    assert pt.stats().rays == ref[2]
+    _assert_same(pt, ref)
+    pt.close()
+
+
+@pytest.mark.gpu
+def test_resumed_frame(srt, oracle):
+    """5 samples, then 12 more onto them (the fold starts from the stored accumulator): the oracle's 17"""
+    pt = _tracer(srt, _scene(oracle, "scene1"))
+    pt.render(spp=5, bounces=8, seed=5)
+    pt.render(spp=12, bounces=8, seed=5, first_sample=6, reset=False)
+    _assert_same(pt, _reference(oracle, "scene1", spp=17, bounces=8, seed=5))
+    pt.close()
+
+
+@pytest.mark.gpu
+def test_sub_band(srt, oracle):
+    band = (3, 21)
+    pt = _tracer(srt, _scene(oracle, "scene1"))
+    pt.write_accumulator(np.zeros((H, W, 4), np.float32))
+    pt.render(spp=9, bounces=8, seed=6, rows=band)
+    _assert_same(pt, _reference(oracle, "scene1", spp=9, bounces=8, seed=6, rows=band), rows=band)
+    pt.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bounces", [1, 16])
+def test_bounce_limits(srt, oracle, bounces):
+    """1: every path ends at its first ray, all 64 lanes store in the same step; 16: long paths, slots far apart"""
+    pt = _tracer(srt, _scene(oracle, "scene1"))
+    pt.render(spp=9, bounces=bounces, seed=7, count_rays=True)
+    ref = _reference(oracle, "scene1", spp=9, bounces=bounces, seed=7)
+    assert pt.stats().rays == ref[2]
+    _assert_same(pt, ref)
+    pt.close()
+
+
+@pytest.mark.gpu
+def test_nan_alpha(srt, oracle):
+    """the radius-inf spheres of test_gpu_parity.py at a sample count inside the rows window.  This scene's image lives in memory
+    (the radius is outside the short square root's window), and such scenes keep the ring; a NaN alpha on the rows path — bit 31
+    of the row entry's tag word — is test_nan_alpha_through_rows below."""
+    pt = _tracer(srt, _scene(oracle, "rinf"))
+    pt.render(spp=9, bounces=4, seed=11, count_rays=True)
+    ref = _reference(oracle, "rinf", spp=9, bounces=4, seed=11)
+    assert np.isnan(ref[1][..., 3]).any()
+    assert pt.stats().rays == ref[2]
+    _assert_same(pt, ref)
+    pt.close()
+
+
+@pytest.mark.gpu
+def test_nan_alpha_through_rows(srt, oracle):
+    """a sphere whose smoothness is NaN: the rays that leave it are NaN, and so is the alpha of the samples that end in the
+    environment behind them (a quarter of the frame's pixels, not all).  Nothing about this scene sends its image to memory —
+    a counting launch reports valid work counts, which only the LDS instantiations keep — so the launch takes the rows path."""
+    pt = _tracer(srt, _scene(oracle, "nansmooth"))
+    pt.render(spp=9, bounces=8, seed=12, count_rays=True, count_work=True)
+    ref = _reference(oracle, "nansmooth", spp=9, bounces=8, seed=12)
+    alpha_nan = np.isnan(ref[1][..., 3])
+    assert alpha_nan.any() and not alpha_nan.all()
+    assert pt.work_counts().as_dict()["valid"] == 1
+    assert pt.stats().rays == ref[2]
+    _assert_same(pt, ref)
+    pt.close()
+
+
+@pytest.mark.gpu
+def test_mesh_scene(srt, oracle):
+    pt = _tracer(srt, _scene(oracle, "mesh"))
+    pt.render(spp=8, bounces=8, seed=8, count_rays=True)
+    ref = _reference(oracle, "mesh", spp=8, bounces=8, seed=8)
+    assert pt.stats().rays == ref[2]
+    _assert_same(pt, ref)
+    pt.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("spps", [(8, 64), (8, 15, 9)], ids=["8-then-64", "8-15-9"])
+def test_buffer_regrows(srt, oracle, spps):
+    """one context, frames of different sample counts with different seeds: the buffer grows (8 -> 64: for the sample chunks'
+    rows; 8 -> 15: for the rows path's own), and a launch that finds a larger buffer than it needs, holding another frame's
+    rows at another row stride (15 -> 9), reads only what it wrote"""
+    pt = _tracer(srt, _scene(oracle, "scene1"))
+    for i, spp in enumerate(spps):
+        pt.render(spp=spp, bounces=8, seed=20 + i)
+        _assert_same(pt, _reference(oracle, "scene1", spp=spp, bounces=8, seed=20 + i))
+    pt.close()
+
+
+@pytest.mark.gpu
+def test_counting_launch(srt, oracle):
+    """count_rays / count_work: the counting instantiation of the rows path gives the same bits, the oracle's ray count, and
+    one closest_hit call per pool step plus one per wave (the primary hit).  The step counts are the rows hand-out's (module
+    docstring): the ring's are 331 and 543."""
+    pt = _tracer(srt, _scene(oracle, "scene1"))
+    pt.render(spp=8, bounces=8, seed=5, count_rays=True, count_work=True)
+    ref = _reference(oracle, "scene1", spp=8, bounces=8, seed=5)
+    assert pt.stats().rays == ref[2]
+    c = pt.work_counts().as_dict()
+    assert c["valid"] == 1 and c["waves"] > 0
+    assert c["closest_hit_calls"] == c["pool_steps"] + c["waves"]
+    _assert_same(pt, ref)
+    assert c["pool_steps"] == 241
+    pt.render(spp=15, bounces=8, seed=5, count_work=True)
+    assert pt.work_counts().as_dict()["pool_steps"] == 394
+    pt.close()
+
+
+def test_shape_rule(tmp_path):
+    """srt::fold_from_rows on both sides of the sample minimum and of the byte cap and for every excluded launch kind
+    (tests/native/rows_rule_check.cpp, a stand-alone program under ASan + UBSan)"""
+    exe = str(tmp_path / "rows_rule_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-I" + os.path.join(ROOT, "software-raytracer_amd", "csrc"), os.path.join(ROOT, "tests", "native", "rows_rule_check.cpp"), "-o", exe],
+                   check=True, capture_output=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout[-600:] + r.stderr[-2000:]
+    assert r.stdout.split()[-1] == str(MIN)
