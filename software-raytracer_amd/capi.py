@@ -422,97 +422,66 @@ def _ray_output_spec(name):
     return RAY_OUTPUTS[name]
 
 
+def _defaults(struct, symbol, lib=None):
+    """The library's defaults of one parameter struct as a dict (pure host: no GPU needed)."""
+    p = struct()
+    rc = getattr(lib if lib is not None else load_library(), symbol)(C.byref(p))
+    if rc:
+        raise SrtError(rc, symbol)
+    return {n: getattr(p, n) for n, _ in struct._fields_}
+
+
 def trace_defaults(lib=None):
     """srt_trace_params_default as a dict (pure host: no GPU needed)."""
-    p = TraceParams()
-    rc = (lib if lib is not None else load_library()).srt_trace_params_default(C.byref(p))
-    if rc:
-        raise SrtError(rc, "srt_trace_params_default")
-    return {n: getattr(p, n) for n, _ in TraceParams._fields_}
+    return _defaults(TraceParams, "srt_trace_params_default", lib)
 
 
 def denoise_defaults(lib=None):
     """srt_denoise_params_default as a dict (pure host: no GPU needed)."""
-    p = DenoiseParams()
-    rc = (lib if lib is not None else load_library()).srt_denoise_params_default(C.byref(p))
-    if rc:
-        raise SrtError(rc, "srt_denoise_params_default")
-    return {n: getattr(p, n) for n, _ in DenoiseParams._fields_}
+    return _defaults(DenoiseParams, "srt_denoise_params_default", lib)
 
 
 def temporal_defaults(lib=None):
     """srt_temporal_params_default as a dict (pure host: no GPU needed)."""
-    p = TemporalParams()
-    rc = (lib if lib is not None else load_library()).srt_temporal_params_default(C.byref(p))
-    if rc:
-        raise SrtError(rc, "srt_temporal_params_default")
-    return {n: getattr(p, n) for n, _ in TemporalParams._fields_}
+    return _defaults(TemporalParams, "srt_temporal_params_default", lib)
 
 
 def upsample_defaults(lib=None):
     """srt_upsample_params_default as a dict (pure host: no GPU needed)."""
-    p = UpsampleParams()
-    rc = (lib if lib is not None else load_library()).srt_upsample_params_default(C.byref(p))
-    if rc:
-        raise SrtError(rc, "srt_upsample_params_default")
-    return {n: getattr(p, n) for n, _ in UpsampleParams._fields_}
+    return _defaults(UpsampleParams, "srt_upsample_params_default", lib)
 
 
 def antialias_defaults(lib=None):
     """srt_antialias_params_default as a dict (pure host: no GPU needed)."""
-    p = AntialiasParams()
-    rc = (lib if lib is not None else load_library()).srt_antialias_params_default(C.byref(p))
-    if rc:
-        raise SrtError(rc, "srt_antialias_params_default")
-    return {n: getattr(p, n) for n, _ in AntialiasParams._fields_}
+    return _defaults(AntialiasParams, "srt_antialias_params_default", lib)
 
 
 def variance_defaults(lib=None):
     """srt_variance_params_default as a dict (pure host: no GPU needed)."""
-    p = VarianceParams()
-    rc = (lib if lib is not None else load_library()).srt_variance_params_default(C.byref(p))
-    if rc:
-        raise SrtError(rc, "srt_variance_params_default")
-    return {n: getattr(p, n) for n, _ in VarianceParams._fields_}
+    return _defaults(VarianceParams, "srt_variance_params_default", lib)
 
 
 def denoise_variance_defaults(lib=None):
     """srt_denoise_variance_params_default as a dict (pure host: no GPU needed)."""
-    p = DenoiseVarianceParams()
-    rc = (lib if lib is not None else load_library()).srt_denoise_variance_params_default(C.byref(p))
-    if rc:
-        raise SrtError(rc, "srt_denoise_variance_params_default")
-    return {n: getattr(p, n) for n, _ in DenoiseVarianceParams._fields_}
+    return _defaults(DenoiseVarianceParams, "srt_denoise_variance_params_default", lib)
 
 
 def temporal_variance_defaults(lib=None):
     """srt_temporal_variance_params_default as a dict (pure host: no GPU needed)."""
-    p = TemporalVarianceParams()
-    rc = (lib if lib is not None else load_library()).srt_temporal_variance_params_default(C.byref(p))
-    if rc:
-        raise SrtError(rc, "srt_temporal_variance_params_default")
-    return {n: getattr(p, n) for n, _ in TemporalVarianceParams._fields_}
+    return _defaults(TemporalVarianceParams, "srt_temporal_variance_params_default", lib)
+
+
+# DENOISE_DEFAULTS, TEMPORAL_DEFAULTS, ...: the library's defaults, read when first asked for, so that importing this module does
+# not need the built library
+_LAZY_DEFAULTS = {"DENOISE_DEFAULTS": denoise_defaults, "TEMPORAL_DEFAULTS": temporal_defaults, "UPSAMPLE_DEFAULTS": upsample_defaults,
+                  "ANTIALIAS_DEFAULTS": antialias_defaults, "VARIANCE_DEFAULTS": variance_defaults,
+                  "DENOISE_VARIANCE_DEFAULTS": denoise_variance_defaults, "TEMPORAL_VARIANCE_DEFAULTS": temporal_variance_defaults,
+                  "TRACE_DEFAULTS": trace_defaults}
 
 
 def __getattr__(name):
-    # DENOISE_DEFAULTS / TEMPORAL_DEFAULTS / UPSAMPLE_DEFAULTS: the library's defaults (denoise_defaults(), temporal_defaults(),
-    # upsample_defaults()), read when first asked for, so that importing this module does not need the built library
-    if name == "DENOISE_DEFAULTS":
-        return denoise_defaults()
-    if name == "TEMPORAL_DEFAULTS":
-        return temporal_defaults()
-    if name == "UPSAMPLE_DEFAULTS":
-        return upsample_defaults()
-    if name == "ANTIALIAS_DEFAULTS":
-        return antialias_defaults()
-    if name == "VARIANCE_DEFAULTS":
-        return variance_defaults()
-    if name == "DENOISE_VARIANCE_DEFAULTS":
-        return denoise_variance_defaults()
-    if name == "TEMPORAL_VARIANCE_DEFAULTS":
-        return temporal_variance_defaults()
-    if name == "TRACE_DEFAULTS":
-        return trace_defaults()
+    if name in _LAZY_DEFAULTS:
+        return _LAZY_DEFAULTS[name]()
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -701,6 +670,12 @@ class PathTracer:
         p = GBufferParams(int(rb), int(re), gbuffer_outputs(outputs), int(flags))
         self._ck(self.L.srt_render_gbuffer(self._h, C.byref(p)))
 
+    def _read_image(self, fn, shape, dtype, *args):
+        """One srt_read_*: a new array of `shape` filled by fn(handle, *args, pointer to the array's data)."""
+        out = np.empty(shape, dtype=dtype)
+        self._ck(fn(self._h, *args, out.ctypes.data_as(fn.argtypes[-1])))
+        return out
+
     def _gbuffer_shape(self, name):
         _, dtype, ch = _gbuffer_spec(name)
         return dtype, ((self.height, self.width) if ch == 1 else (self.height, self.width, ch))
@@ -709,9 +684,7 @@ class PathTracer:
         """srt_read_gbuffer: the whole buffer of one output as a numpy array, rows = scene rows (the orientation of
         accumulator()): "object" (H, W) int32, the others (H, W, 4) float32."""
         dtype, shape = self._gbuffer_shape(name)
-        out = np.empty(shape, dtype=dtype)
-        self._ck(self.L.srt_read_gbuffer(self._h, GBUFFERS[name][0], out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._read_image(self.L.srt_read_gbuffer, shape, dtype, GBUFFERS[name][0])
 
     def bind_gbuffer(self, name, tensor):
         """srt_bind_gbuffer: write output `name` into a torch tensor on this tracer's device (None: the handle's own buffer).
@@ -852,9 +825,7 @@ class PathTracer:
 
     def visibility(self, name):
         """srt_read_visibility: output "ao" or "sun" of the last render_visibility() as an (H, W) float32 array, rows = scene rows."""
-        out = np.empty((self.height, self.width), dtype=np.float32)
-        self._ck(self.L.srt_read_visibility(self._h, VISIBILITY[name], out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read_image(self.L.srt_read_visibility, (self.height, self.width), np.float32, VISIBILITY[name])
 
     def bind_visibility(self, name, tensor):
         """srt_bind_visibility: write output "ao" or "sun" into a torch tensor (H, W) float32 on this tracer's device (None: the
@@ -875,9 +846,7 @@ class PathTracer:
         n = count if count is not None else getattr(self, "_ray_traced", None)
         if n is None:
             raise SrtError(ERR_STATE, "ray_output(%r): no trace_rays() yet" % name)
-        out = np.empty((n,) if ch == 1 else (n, ch), dtype=dtype)
-        self._ck(self.L.srt_read_ray_output(self._h, bit, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._read_image(self.L.srt_read_ray_output, (n,) if ch == 1 else (n, ch), dtype, bit)
 
     def bind_ray_output(self, name, tensor):
         """srt_bind_ray_output: write output `name` into a torch tensor on this tracer's device (None: the handle's own buffer):
@@ -939,9 +908,7 @@ class PathTracer:
 
     def denoised(self):
         """srt_read_denoised: the result, (H, W, 4) float32, rows = scene rows (the orientation of accumulator())."""
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_read_denoised(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read_image(self.L.srt_read_denoised, (self.height, self.width, 4), np.float32)
 
     def bind_denoised(self, tensor):
         """srt_bind_denoised: write the result into a torch tensor on this tracer's device, (H, W, 4) float32 and contiguous
@@ -961,9 +928,7 @@ class PathTracer:
 
     def history_length(self):
         """srt_read_history_length: L of the last temporal() call, (H, W) float32, rows = scene rows."""
-        out = np.empty((self.height, self.width), dtype=np.float32)
-        self._ck(self.L.srt_read_history_length(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read_image(self.L.srt_read_history_length, (self.height, self.width), np.float32)
 
     def motion_output(self, on=True):
         """srt_motion_output: every later temporal() also writes the motion buffer (u - x, v - y, Wsum, 0)."""
@@ -971,9 +936,7 @@ class PathTracer:
 
     def motion(self):
         """srt_read_motion: the motion buffer of the last temporal() call that wrote it, (H, W, 4) float32, scene rows."""
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_read_motion(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read_image(self.L.srt_read_motion, (self.height, self.width, 4), np.float32)
 
     def bind_motion(self, tensor):
         """srt_bind_motion: write the motion buffer into a torch tensor on this tracer's device, (H, W, 4) float32 and
@@ -994,9 +957,7 @@ class PathTracer:
 
     def upsampled(self):
         """srt_read_upsampled: the result, (H, W, 4) float32, rows = scene rows (the orientation of accumulator())."""
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_read_upsampled(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read_image(self.L.srt_read_upsampled, (self.height, self.width, 4), np.float32)
 
     def bind_upsampled(self, tensor):
         """srt_bind_upsampled: write the result into a torch tensor on this tracer's device, (H, W, 4) float32 and contiguous
@@ -1015,9 +976,7 @@ class PathTracer:
         """srt_read_subsamples: (k*k, H, W) int32, rows = scene rows; k is that of the last render_subsamples of this tracer
         unless given (a buffer filled by other means)."""
         k = int(getattr(self, "_subsample_k", 0) if k is None else k)
-        out = np.empty((max(k, 1) ** 2, self.height, self.width), dtype=np.int32)
-        self._ck(self.L.srt_read_subsamples(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
-        return out
+        return self._read_image(self.L.srt_read_subsamples, (max(k, 1) ** 2, self.height, self.width), np.int32)
 
     def bind_subsamples(self, tensor, k=None):
         """srt_bind_subsamples: keep the sub-samples in a torch tensor on this tracer's device, (k*k, H, W) int32 and
@@ -1047,9 +1006,7 @@ class PathTracer:
 
     def antialiased(self):
         """srt_read_antialiased: the result, (H, W, 4) float32, rows = scene rows (the orientation of accumulator())."""
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_read_antialiased(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read_image(self.L.srt_read_antialiased, (self.height, self.width, 4), np.float32)
 
     def bind_antialiased(self, tensor):
         """srt_bind_antialiased: write the result into a torch tensor on this tracer's device, (H, W, 4) float32 and contiguous
@@ -1081,9 +1038,7 @@ class PathTracer:
 
     def variance_map(self):
         """srt_read_variance: the variance, (H, W) float32, rows = scene rows (the orientation of accumulator())."""
-        out = np.empty((self.height, self.width), dtype=np.float32)
-        self._ck(self.L.srt_read_variance(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read_image(self.L.srt_read_variance, (self.height, self.width), np.float32)
 
     def bind_variance(self, tensor):
         """srt_bind_variance: keep the variance in a torch tensor on this tracer's device, (H, W) float32 and contiguous (None:
@@ -1109,9 +1064,7 @@ class PathTracer:
 
     def moments(self):
         """srt_read_moments: the records of the last temporal() call, (H, W, 4) float32 (M1, M2, Lm, 0), scene rows."""
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_read_moments(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read_image(self.L.srt_read_moments, (self.height, self.width, 4), np.float32)
 
     def temporal_variance(self, min_frames=None, radius=None):
         """srt_temporal_variance over the whole frame: the variance buffer (variance_map(), denoise_variance()) from the
@@ -1160,9 +1113,7 @@ class PathTracer:
         self._ck(self.L.srt_read_framebuffer_async(self._h, C.c_void_p(dst_ptr), self.width * 4, rb, re, C.c_void_p(copy_stream or 0)))
 
     def accumulator(self):
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_read_accumulator(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read_image(self.L.srt_read_accumulator, (self.height, self.width, 4), np.float32)
 
     def write_accumulator(self, arr):
         a = np.ascontiguousarray(arr, dtype=np.float32)

@@ -27,6 +27,7 @@
 #include "srt_moments.hip.h"
 #include "srt_refit.hip.h"
 #include "srt_rays.hip.h"
+#include "srt_outputs_host.h"
 #include "srt_rays_host.h"
 #include "srt_occlusion.hip.h"
 #include "srt_occlusion_host.h"
@@ -93,6 +94,7 @@ constexpr const DevSwitches& dev_switches() { return k_dev_switches; }
 
 constexpr size_t REC_WORDS = 1 + 4 * srt::TALLY_N;  // per block in the cost record: wave time, then TALLY_N counts for each of the four waves
 // srt_launch_shape.h is host-only C++ (unit-tested on the CPU) and repeats the kernel's tile geometry:
+static_assert(srt::OUT_TILE == srt::TILE_W && srt::OUT_TILE == srt::TILE_H && srt::OUT_WG_UNITS == srt::WG_TILES_X * srt::WG_TILES_Y, "srt_outputs_host.h and srt_kernel.hip.h disagree");
 static_assert(srt::SHAPE_TILE_H == srt::TILE_H && srt::SHAPE_WG_W == srt::WG_W && srt::SHAPE_WG_H == srt::WG_H && srt::SHAPE_WG_TILES_Y == srt::WG_TILES_Y &&
               srt::SHAPE_WAVES_PER_WG == srt::WG_TILES_X * srt::WG_TILES_Y && srt::SHAPE_TALLY_N == srt::TALLY_N, "srt_launch_shape.h and srt_kernel.hip.h disagree");
 
@@ -257,18 +259,19 @@ struct srt_context {
     uint32_t chain_used_arg = 0;
 #endif
 
-    // first-hit buffers (srt_render_gbuffer), one slot per SRT_GBUF_* bit: the handle's own (allocated on first use) and the
-    // caller's bound one (srt_bind_gbuffer; NULL = own)
-    DeviceBuffer<void> d_gbuf_own[4];
-    void* d_gbuf_bound[4] = {nullptr, nullptr, nullptr, nullptr};
+    // Every output a caller can bind or read back is an own buffer (allocated on first use) and an srt::OutputSlot
+    // (srt_outputs_host.h): the caller's bound buffer (srt_bind_*; NULL = own) and the record of what has been written.  DESIGN.md
+    // §4.21 lists them with the rule each srt_read_* applies.
 
-    // denoiser (srt_denoise): the handle's own result buffer and the ping-pong buffer of the preparation pass and the levels
-    // before the last (both allocated on first use), the caller's bound result buffer (srt_bind_denoised; NULL = own), and whether a denoise has been
-    // enqueued yet (srt_read_denoised before that is SRT_ERR_STATE)
+    // first-hit buffers (srt_render_gbuffer), one per SRT_GBUF_* bit
+    DeviceBuffer<void> d_gbuf_own[4];
+    srt::OutputSlot gbuf[4];
+
+    // denoiser (srt_denoise, srt_denoise_variance): the result, and the ping-pong buffer of the preparation pass and the levels
+    // before the last
     DeviceBuffer<float4> d_dn_own;
     DeviceBuffer<float4> d_dn_tmp;
-    float4* d_dn_bound = nullptr;
-    bool dn_written = false;
+    srt::OutputSlot dn;
 
     // the camera each own first-hit slot was last rendered with (srt_temporal_accumulate refuses own guides of another camera)
     srt_camera gbuf_own_cam[4] = {};
@@ -293,48 +296,38 @@ struct srt_context {
     DeviceBuffer<float4> d_tp_table;
     Event ev_tp_table;
     bool tp_table_in_flight = false;
-    // the motion-vector output (srt_motion_output): own buffer (allocated on first use), the caller's (srt_bind_motion; NULL =
-    // own), and the buffer the last call with the output on wrote (srt_read_motion reads no other)
+    // the motion-vector output (srt_motion_output; srt_read_motion reads no buffer but the one the last call with the output on wrote)
     bool mv_on = false;
     DeviceBuffer<float4> d_mv_own;
-    float4* d_mv_bound = nullptr;
-    const float4* mv_last = nullptr;
+    srt::OutputSlot mv;
 
-    // guided upsampler (srt_upsample): the handle's own result buffer (allocated on first use), the caller's bound one
-    // (srt_bind_upsampled; NULL = own), and whether a call has written a result buffer yet (srt_read_upsampled)
+    // guided upsampler (srt_upsample; an in-place call writes no result buffer)
     DeviceBuffer<float4> d_up_own;
-    float4* d_up_bound = nullptr;
-    bool up_written = false;
+    srt::OutputSlot up;
 
-    // anti-aliasing (srt_render_subsamples, srt_antialias).  The sub-sample planes: the handle's own buffer (allocated on first
-    // use, re-allocated when k grows), the caller's bound one (srt_bind_subsamples; NULL = own), and the k last rendered into
-    // the current buffer (0 = none; srt_read_subsamples).  What the OWN buffer holds: its k, the camera and the scene (a count
-    // of scene changes) it was rendered with, and the memory rows rendered with exactly those so far — srt_antialias refuses an
-    // own buffer that is not a whole frame of the current scene and camera.
+    // anti-aliasing (srt_render_subsamples, srt_antialias).  The sub-sample planes: the own buffer is re-allocated when k grows,
+    // and the slot's count is the k of the last render, into whichever buffer.  What the OWN buffer holds: its k, the camera and the
+    // scene (a count of scene changes) it was rendered with, and the memory rows rendered with exactly those so far — srt_antialias
+    // refuses an own buffer that is not a whole frame of the current scene and camera.
     DeviceBuffer<int32_t> d_ss_own;
-    int32_t* d_ss_bound = nullptr;
-    int ss_last_k = 0;
+    srt::OutputSlot ss;
     int ss_own_k = 0;
     srt_camera ss_own_cam{};
     uint64_t ss_own_scene = 0;
     std::vector<bool> ss_own_rows;
     uint64_t scene_changes = 0;  // srt_set_scene / srt_update_scene / srt_set_meshes calls so far
-    // the handle's own result buffer (allocated on first use), the caller's bound one (srt_bind_antialiased; NULL = own), and
-    // whether a call has been enqueued yet (srt_read_antialiased)
+    // the resolve's result (srt_antialias)
     DeviceBuffer<float4> d_aa_own;
-    float4* d_aa_bound = nullptr;
-    bool aa_written = false;
+    srt::OutputSlot aa;
 
-    // variance estimate and variance-guided denoiser (srt_variance, srt_denoise_variance).  The second half render: the
-    // handle's own buffer (allocated by the first srt_device_half) and the caller's bound one (srt_bind_half; NULL = own).  The
-    // variance: the handle's own buffer (allocated on first use), the caller's bound one (srt_bind_variance; NULL = own), whether
-    // a call has been enqueued yet (srt_read_variance), whether one has written the OWN buffer and whether that one used
-    // SRT_VARIANCE_ALBEDO (srt_denoise_variance refuses an own buffer of the other kind).
+    // variance estimate and variance-guided denoiser (srt_variance, srt_temporal_variance, srt_denoise_variance).  The second half
+    // render is an input: its own buffer is allocated by the first srt_device_half and nothing records a write.  The variance:
+    // besides the slot, whether a call has written the OWN buffer and whether that one used SRT_VARIANCE_ALBEDO
+    // (srt_denoise_variance refuses an own buffer of the other kind).
     DeviceBuffer<float4> d_half_own;
-    float4* d_half_bound = nullptr;
+    srt::OutputSlot half;
     DeviceBuffer<float> d_var_own;
-    float* d_var_bound = nullptr;
-    bool var_written = false;
+    srt::OutputSlot var;
     bool var_own_written = false;
     bool var_own_albedo = false;
 
@@ -351,23 +344,23 @@ struct srt_context {
     float mom_samples = 0.0f;
     bool mom_history = false;
 
-    // ray queries (srt_trace_rays): the handle's own ray arrays (srt_write_rays; they grow on demand) and output buffers, one slot
-    // per output bit (allocated on first use, grown when a batch needs more), the caller's bound outputs (srt_bind_ray_output;
-    // NULL = own), and the host-side state (srt_rays_host.h): which arrays are the current rays and what the last trace wrote
+    // ray queries (srt_trace_rays): the handle's own ray arrays (srt_write_rays; they grow on demand) and output buffers, one
+    // per output bit (grown when a batch needs more) with its slot (the bound buffer only), and the host-side state
+    // (srt_rays_host.h): which arrays are the current rays and what the last trace wrote
     DeviceBuffer<float4> d_ray_origin;
     DeviceBuffer<float4> d_ray_direction;
     DeviceBuffer<void> d_rayout_own[srt::RAYS_SLOTS];
-    void* d_rayout_bound[srt::RAYS_SLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    srt::OutputSlot rayout[srt::RAYS_SLOTS];
     srt::RaysState rays;
     // any-hit queries (srt_trace_occlusion): whether the last one counted its work, and the record its kernel adds to
     // (srt::OCC_WORK_N words, zeroed on the stream in front of a counting launch; never an output buffer)
     srt::OcclusionState occlusion;
     DeviceBuffer<unsigned long long> d_occlusion_work;
-    // per-pixel visibility (srt_render_visibility), one slot per SRT_VIS_* bit: the handle's own W*H floats (allocated on first
-    // use) and the caller's bound ones (srt_bind_visibility; NULL = own); what the last call wrote and whether it counted; the
-    // record a counting launch adds to (srt::VIS_WORK_N words, zeroed on the stream in front of it; never an output buffer)
+    // per-pixel visibility (srt_render_visibility), one own buffer of W*H floats per SRT_VIS_* bit with its slot (the bound
+    // buffer only); what the last call wrote and whether it counted (srt_visibility_host.h); the record a counting launch adds to
+    // (srt::VIS_WORK_N words, zeroed on the stream in front of it; never an output buffer)
     DeviceBuffer<void> d_vis_own[srt::VIS_SLOTS];
-    void* d_vis_bound[srt::VIS_SLOTS] = {nullptr, nullptr};
+    srt::OutputSlot vis[srt::VIS_SLOTS];
     srt::VisibilityState visibility;
     DeviceBuffer<unsigned long long> d_visibility_work;
 
@@ -402,11 +395,56 @@ int finish_stream(srt_context* ctx) {
     return SRT_OK;
 }
 
-// the buffer a first-hit output or the denoised image lives in: the caller's bound one, else the handle's own (NULL before its first use)
+// the buffer an output lives in: the caller's bound one, else the handle's own (NULL before its first use)
 template <class T>
-T* bound_or_own(T* bound, const DeviceBuffer<T>& own) {
-    return bound ? bound : (T*)own;
+T* current(const srt::OutputSlot& s, const DeviceBuffer<T>& own) {
+    return (T*)const_cast<void*>(s.current((T*)own));
 }
+
+// dst = the buffer a call writes `nbytes` of an output to: the bound one, else the own one, allocated or grown first when it is too
+// small (a grown buffer takes the record of a last write into it along).  A macro, so that the text of a failed allocation names
+// the buffer.  _AFTER: `before_grow` (an int, SRT_OK to go on) runs in front of a re-allocation.
+#define SRT_WRITE_TARGET_AFTER(ctx, slot, own, nbytes, dst, before_grow) \
+    do {                                                                 \
+        if ((slot).target((own).bytes(), nbytes).grow) {                 \
+            if (const int rc_ = (before_grow)) return rc_;               \
+            (slot).own_released(own);                                    \
+            SRT_HIP(ctx, own.ensure(nbytes));                            \
+        }                                                                \
+        dst = current(slot, own);                                        \
+    } while (0)
+#define SRT_WRITE_TARGET(ctx, slot, own, nbytes, dst) SRT_WRITE_TARGET_AFTER(ctx, slot, own, nbytes, dst, SRT_OK)
+
+// ... in front of the re-allocation of own ray output `i` (srt_trace_rays, srt_trace_occlusion): earlier traces may still be
+// writing it, so the stream is finished, and the last trace's copy of the output goes with it
+int ray_output_released(srt_context* ctx, int i) {
+    if (const int rc = finish_stream(ctx)) return rc;
+    srt::rays_output_released(ctx->rays, i, (void*)ctx->d_rayout_own[i]);
+    return SRT_OK;
+}
+
+// The tail of every srt_read_*: `src` is what the output's read rule gave (NULL: refused with `why`, which may print `output`).
+int read_slot(srt_context* ctx, const void* src, void* dst, size_t bytes, const char* why, uint32_t output = 0) {
+    if (!src) return fail(ctx, SRT_ERR_STATE, why, output);
+    if (const int rc = finish_stream(ctx)) return rc;
+    SRT_HIP(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+// The work record of a counting launch (srt_trace_occlusion, srt_render_visibility): `words` counters, zeroed on the stream in
+// front of the launch, and read back once the stream has finished.
+int zero_work(srt_context* ctx, DeviceBuffer<unsigned long long>& d, size_t words) {
+    if (!d) SRT_HIP(ctx, d.ensure(words * sizeof(unsigned long long)));
+    SRT_HIP(ctx, hipMemsetAsync(d, 0, words * sizeof(unsigned long long), ctx->stream));
+    return SRT_OK;
+}
+int read_work(srt_context* ctx, const DeviceBuffer<unsigned long long>& d, unsigned long long* w, size_t words) {
+    if (const int rc = finish_stream(ctx)) return rc;
+    SRT_HIP(ctx, hipMemcpy(w, d, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+size_t frame_pixels(const srt_context* ctx) { return (size_t)ctx->width * (size_t)ctx->height; }
 
 // the full frame in workgroups of 2 x 2 waves, one wave per 8 x 8 tile
 dim3 frame_tile_grid(const srt_context* ctx) {
@@ -939,6 +977,55 @@ static KernelSetup fill_kernel_params(srt_context* ctx, const srt_render_params*
                              srt::WG_SCRATCH_BYTES + (ctx->mesh_image.n_tris > 0 ? srt::WG_MESH_SCRATCH_BYTES : 0);
     return KernelSetup{lds_bytes, use, img};
 }
+
+// The scene side of the kernel parameters for memory rows [row_begin, row_end): what the first-hit, ray and visibility passes
+// take from the render's — scene image, mesh image, the scene_in_lds judgement and the LDS bytes, the camera as it stands (the ray
+// passes do not read it) — with no flag but KF_BOXES_FINITE and none of the render's buffers.
+static KernelSetup scene_kernel_params(srt_context* ctx, int row_begin, int row_end, srt::KernelParams& K) {
+    srt_render_params p{};
+    p.row_begin = row_begin, p.row_end = row_end, p.first_sample = 1, p.sample_count = 1;
+    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
+    K.flags &= srt::KF_BOXES_FINITE;
+    K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;
+    return ks;
+}
+
+// Workgroups of `kernel` the chip keeps resident: LDS and registers decide how many per CU, at most four (one where the
+// runtime cannot say).
+static long long resident_workgroups(srt_context* ctx, const void* kernel, size_t lds_bytes) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, srt::WG_THREADS, lds_bytes) != hipSuccess || per_cu < 1)
+        per_cu = 1, (void)hipGetLastError();
+    return (long long)ctx->cu_count * (per_cu > 4 ? 4 : per_cu);
+}
+
+// Persistent workgroups: each stages the scene once and its waves stride over 8 x 8 tiles or blocks of 64 rays; about as many
+// as are resident, never more than there is work for (srt::persistent_grid).
+template <class IO>
+static int launch_persistent(srt_context* ctx, void (*kernel)(srt::KernelParams, IO), unsigned wgs, const KernelSetup& ks, const srt::KernelParams& K, const IO& io) {
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io);
+    SRT_HIP(ctx, hipGetLastError());
+    return SRT_OK;
+}
+// ... over the tiles of K's band
+template <class IO>
+static int launch_tiles(srt_context* ctx, void (*kernel)(srt::KernelParams, IO), const KernelSetup& ks, const srt::KernelParams& K, const IO& io) {
+    const long long resident = resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes);
+    return launch_persistent(ctx, kernel, srt::persistent_grid(srt::band_tiles(K.width, K.rows), srt::OUT_WG_UNITS, resident), ks, K, io);
+}
+// ... over n rays
+template <class IO>
+static int launch_rays(srt_context* ctx, void (*kernel)(srt::KernelParams, IO), size_t n, const KernelSetup& ks, const srt::KernelParams& K, const IO& io) {
+    return launch_persistent(ctx, kernel, srt::rays_grid(n, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes)), ks, K, io);
+}
+
+// The instantiation of a persistent kernel for a scene image in LDS or in memory, with or without meshes, and (the counting
+// passes) with or without the work record.
+#define SRT_KERNEL_LDS_MESH(kernel, in_lds, mesh) \
+    ((in_lds) ? ((mesh) ? kernel<true, true> : kernel<true, false>) : ((mesh) ? kernel<false, true> : kernel<false, false>))
+#define SRT_KERNEL_LDS_MESH_COUNT(kernel, in_lds, mesh, count)                                                                                  \
+    (!(count) ? ((in_lds) ? ((mesh) ? kernel<true, true, false> : kernel<true, false, false>) : ((mesh) ? kernel<false, true, false> : kernel<false, false, false>)) \
+              : ((in_lds) ? ((mesh) ? kernel<true, true, true> : kernel<true, false, true>) : ((mesh) ? kernel<false, true, true> : kernel<false, false, true>)))
 
 // What a block costs, from its counts: the weights are wave instructions per trip of the loop counted (a pool step costs its fixed
 // part plus the uniform-sphere groups, cluster bounds and boxes every step runs through), fitted on measured band times of
@@ -1487,9 +1574,9 @@ static bool same_camera(const srt_camera& a, const srt_camera& b) {
 static int find_guides(srt_context* ctx, const char* fn, int n, const srt_camera* cam, const void** guide) {
     static const char* const names[4] = {"OBJECT", "NORMAL_DEPTH", "POSITION", "ALBEDO"};
     for (int i = 0; i < n; ++i) {
-        guide[i] = bound_or_own(ctx->d_gbuf_bound[i], ctx->d_gbuf_own[i]);
+        guide[i] = current(ctx->gbuf[i], ctx->d_gbuf_own[i]);
         if (!guide[i]) return fail(ctx, SRT_ERR_STATE, "%s: the %s guide has neither been bound nor rendered (srt_render_gbuffer)", fn, names[i]);
-        if (cam && !ctx->d_gbuf_bound[i] && (!ctx->gbuf_own_cam_set[i] || !same_camera(ctx->gbuf_own_cam[i], *cam)))
+        if (cam && !ctx->gbuf[i].bound && (!ctx->gbuf_own_cam_set[i] || !same_camera(ctx->gbuf_own_cam[i], *cam)))
             return fail(ctx, SRT_ERR_STATE, "%s: the %s guide was rendered with another camera (srt_render_gbuffer after srt_set_camera)", fn, names[i]);
     }
     return SRT_OK;
@@ -1506,59 +1593,32 @@ int srt_render_gbuffer(srt_context* ctx, const srt_gbuffer_params* g) {
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render_gbuffer: outputs 0x%x: want a non-empty set of SRT_GBUF_* bits", g->outputs);
     if (g->flags != 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render_gbuffer: flags must be 0");
     SRT_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t px = (size_t)ctx->width * (size_t)H;
+    const size_t px = frame_pixels(ctx);
     void* dst[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i < 4; ++i) {
         if (!(g->outputs & (1u << i))) continue;
-        if (!ctx->d_gbuf_bound[i]) {
-            SRT_HIP(ctx, ctx->d_gbuf_own[i].ensure(px * gbuf_elem_bytes(i)));
-            ctx->gbuf_own_cam[i] = ctx->camera.cam;
-            ctx->gbuf_own_cam_set[i] = true;
-        }
-        dst[i] = bound_or_own(ctx->d_gbuf_bound[i], ctx->d_gbuf_own[i]);
+        SRT_WRITE_TARGET(ctx, ctx->gbuf[i], ctx->d_gbuf_own[i], px * gbuf_elem_bytes(i), dst[i]);
+        if (!ctx->gbuf[i].bound) ctx->gbuf_own_cam[i] = ctx->camera.cam, ctx->gbuf_own_cam_set[i] = true;
     }
-    // the render's kernel parameters for this band: camera, scene image, the scene_in_lds judgement and the LDS bytes
-    srt_render_params p{};
-    p.row_begin = g->row_begin, p.row_end = g->row_end, p.first_sample = 1, p.sample_count = 1;
     srt::KernelParams K;
-    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
-    K.flags &= srt::KF_BOXES_FINITE;
-    K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // the G-buffer touches none of them
+    const KernelSetup ks = scene_kernel_params(ctx, g->row_begin, g->row_end, K);
     const srt::GBufferOut out{(int32_t*)dst[0], (float4*)dst[1], (float4*)dst[2], (float4*)dst[3]};
-    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
-    void (*const kernel)(srt::KernelParams, srt::GBufferOut) = in_lds ? (mesh ? srt::gbuffer_kernel<true, true> : srt::gbuffer_kernel<true, false>)
-                                                                      : (mesh ? srt::gbuffer_kernel<false, true> : srt::gbuffer_kernel<false, false>);
-    // persistent workgroups: each stages the scene once and its waves stride over 8 x 8 tiles; about CUs x resident workgroups
-    // (LDS and registers decide; at most four per CU), never more than there are tiles for
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, srt::WG_THREADS, ks.lds_bytes) != hipSuccess || per_cu < 1)
-        per_cu = 1, (void)hipGetLastError();
-    per_cu = per_cu > 4 ? 4 : per_cu;
-    const long long tiles = (long long)((ctx->width + srt::TILE_W - 1) / srt::TILE_W) * ((K.rows + srt::TILE_H - 1) / srt::TILE_H);
-    const long long need = (tiles + srt::WG_TILES_X * srt::WG_TILES_Y - 1) / (srt::WG_TILES_X * srt::WG_TILES_Y);
-    const long long wgs = std::min<long long>(need, (long long)ctx->cu_count * per_cu);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, out);
-    SRT_HIP(ctx, hipGetLastError());
-    return SRT_OK;
+    return launch_tiles(ctx, SRT_KERNEL_LDS_MESH(srt::gbuffer_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0), ks, K, out);
 }
 
 int srt_bind_gbuffer(srt_context* ctx, uint32_t output, void* d_ptr) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
     const int i = gbuf_slot(output);
     if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_gbuffer: output 0x%x is not a single SRT_GBUF_* bit", output);
-    ctx->d_gbuf_bound[i] = d_ptr;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_output)
-    return SRT_OK;
+    return ctx->gbuf[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_output)
 }
 
 int srt_read_gbuffer(srt_context* ctx, uint32_t output, void* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
     const int i = gbuf_slot(output);
     if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_gbuffer: output 0x%x is not a single SRT_GBUF_* bit", output);
-    const void* src = bound_or_own(ctx->d_gbuf_bound[i], ctx->d_gbuf_own[i]);
-    if (!src) return fail(ctx, SRT_ERR_STATE, "srt_read_gbuffer: output 0x%x has neither been bound nor rendered", output);
-    if (const int rc = finish_stream(ctx)) return rc;
-    SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * gbuf_elem_bytes(i), hipMemcpyDeviceToHost));
-    return SRT_OK;
+    return read_slot(ctx, current(ctx->gbuf[i], ctx->d_gbuf_own[i]), dst, frame_pixels(ctx) * gbuf_elem_bytes(i),
+                     "srt_read_gbuffer: output 0x%x has neither been bound nor rendered", output);
 }
 
 // ---- ray queries ---------------------------------------------------------------------------------------------------
@@ -1602,8 +1662,7 @@ int srt_bind_ray_output(srt_context* ctx, uint32_t output, void* d_ptr) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
     const int i = srt::rays_slot(output);
     if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_ray_output: output 0x%x is not a single SRT_GBUF_* / SRT_RAYS_OCCLUDED bit", output);
-    ctx->d_rayout_bound[i] = d_ptr;  // (no synchronisation: enqueued traces keep the buffer they were given, as srt_bind_gbuffer)
-    return SRT_OK;
+    return ctx->rayout[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued traces keep the buffer they were given, as srt_bind_gbuffer)
 }
 
 int srt_trace_rays(srt_context* ctx, const srt_trace_params* t) {
@@ -1613,49 +1672,19 @@ int srt_trace_rays(srt_context* ctx, const srt_trace_params* t) {
         return fail(ctx, (int)rs, "srt_trace_rays: %s (outputs 0x%x, flags 0x%x)", why, t->outputs, t->flags);
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = ctx->rays.count();
-    // own outputs that are too small for this batch: earlier traces may still be writing the old buffer, so wait before it goes
-    bool grow = false;
-    for (int i = 0; i < srt::RAYS_SLOTS; ++i)
-        grow = grow || ((t->outputs & (1u << i)) && !ctx->d_rayout_bound[i] && ctx->d_rayout_own[i].bytes() < n * srt::rays_elem_bytes(i));
-    if (grow) {
-        if (const int rc = finish_stream(ctx)) return rc;
-    }
     void* dst[srt::RAYS_SLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < srt::RAYS_SLOTS; ++i) {
-        if (!(t->outputs & (1u << i))) continue;
-        if (!ctx->d_rayout_bound[i]) {
-            if (ctx->d_rayout_own[i].bytes() < n * srt::rays_elem_bytes(i) && ctx->rays.last_dst[i] == (void*)ctx->d_rayout_own[i])
-                ctx->rays.last_dst[i] = nullptr, ctx->rays.last_outputs &= ~(1u << i);  // (the last trace's copy of this output goes with the buffer)
-            SRT_HIP(ctx, ctx->d_rayout_own[i].ensure(n * srt::rays_elem_bytes(i)));
-        }
-        dst[i] = bound_or_own(ctx->d_rayout_bound[i], ctx->d_rayout_own[i]);
-    }
-    // the scene side of the render's kernel parameters: scene image, mesh image, the scene_in_lds judgement and the LDS bytes (the
-    // camera terms are filled from whatever camera there is and read by nobody)
-    srt_render_params p{};
-    p.row_begin = 0, p.row_end = ctx->height, p.first_sample = 1, p.sample_count = 1;
+    for (int i = 0; i < srt::RAYS_SLOTS; ++i)
+        if (t->outputs & (1u << i))
+            SRT_WRITE_TARGET_AFTER(ctx, ctx->rayout[i], ctx->d_rayout_own[i], n * srt::rays_elem_bytes(i), dst[i], ray_output_released(ctx, i));
     srt::KernelParams K;
-    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
-    K.flags &= srt::KF_BOXES_FINITE;
-    K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // a trace touches none of them
+    const KernelSetup ks = scene_kernel_params(ctx, 0, ctx->height, K);
     srt::RaysIO io{};
     io.origin = ctx->rays.bound() ? (const float4*)ctx->rays.bound_origin : (const float4*)ctx->d_ray_origin;
     io.direction = ctx->rays.bound() ? (const float4*)ctx->rays.bound_direction : (const float4*)ctx->d_ray_direction;
     io.count = (uint32_t)n;
     io.normalize = (t->flags & SRT_RAYS_NORMALIZE) ? 1u : 0u;
     io.object = (int32_t*)dst[0], io.normal_depth = (float4*)dst[1], io.position = (float4*)dst[2], io.albedo = (float4*)dst[3], io.occluded = (int32_t*)dst[4];
-    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
-    void (*const kernel)(srt::KernelParams, srt::RaysIO) = in_lds ? (mesh ? srt::rays_kernel<true, true> : srt::rays_kernel<true, false>)
-                                                                  : (mesh ? srt::rays_kernel<false, true> : srt::rays_kernel<false, false>);
-    // persistent workgroups, sized as srt_render_gbuffer sizes them: about CUs x resident workgroups (at most four per CU), never
-    // more than there are blocks of 64 rays for
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, srt::WG_THREADS, ks.lds_bytes) != hipSuccess || per_cu < 1)
-        per_cu = 1, (void)hipGetLastError();
-    per_cu = per_cu > 4 ? 4 : per_cu;
-    const unsigned wgs = srt::rays_grid(n, srt::WG_TILES_X * srt::WG_TILES_Y, (long long)ctx->cu_count * per_cu);
-    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io);
-    SRT_HIP(ctx, hipGetLastError());
+    if (const int rc = launch_rays(ctx, SRT_KERNEL_LDS_MESH(srt::rays_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0), n, ks, K, io)) return rc;
     srt::rays_traced(ctx->rays, t->outputs, dst);
     return SRT_OK;
 }
@@ -1666,10 +1695,7 @@ int srt_read_ray_output(srt_context* ctx, uint32_t output, void* dst) {
     size_t bytes = 0;
     const srt::RaysStatus rs = srt::rays_check_read(ctx->rays, output, &src, &bytes);
     if (rs == srt::RAYS_INVALID_ARG) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_ray_output: output 0x%x is not a single SRT_GBUF_* / SRT_RAYS_OCCLUDED bit", output);
-    if (rs != srt::RAYS_OK) return fail(ctx, SRT_ERR_STATE, "srt_read_ray_output: output 0x%x was not written by the last srt_trace_rays", output);
-    if (const int rc = finish_stream(ctx)) return rc;
-    SRT_HIP(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    return SRT_OK;
+    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, bytes, "srt_read_ray_output: output 0x%x was not written by the last srt_trace_rays", output);
 }
 
 // ---- any-hit queries -----------------------------------------------------------------------------------------------
@@ -1693,25 +1719,13 @@ int srt_trace_occlusion(srt_context* ctx, const srt_occlusion_params* t) {
     const size_t n = ctx->rays.count();
     const int slot = srt::OCCLUSION_SLOT;
     const bool count = (t->flags & SRT_OCCLUSION_COUNT_WORK) != 0;
-    // an own output that is too small for this batch: earlier traces may still be writing the old buffer, so wait before it goes
-    if (!ctx->d_rayout_bound[slot] && ctx->d_rayout_own[slot].bytes() < n * sizeof(int32_t)) {
-        if (const int rc = finish_stream(ctx)) return rc;
-        if (ctx->rays.last_dst[slot] == (void*)ctx->d_rayout_own[slot])
-            ctx->rays.last_dst[slot] = nullptr, ctx->rays.last_outputs &= ~SRT_RAYS_OCCLUDED;  // (the last trace's copy of this output goes with the buffer)
-        SRT_HIP(ctx, ctx->d_rayout_own[slot].ensure(n * sizeof(int32_t)));
-    }
+    void* dst = nullptr;
+    SRT_WRITE_TARGET_AFTER(ctx, ctx->rayout[slot], ctx->d_rayout_own[slot], n * sizeof(int32_t), dst, ray_output_released(ctx, slot));
     if (count) {
-        if (!ctx->d_occlusion_work) SRT_HIP(ctx, ctx->d_occlusion_work.ensure(srt::OCC_WORK_N * sizeof(unsigned long long)));
-        SRT_HIP(ctx, hipMemsetAsync(ctx->d_occlusion_work, 0, srt::OCC_WORK_N * sizeof(unsigned long long), ctx->stream));
+        if (const int rc = zero_work(ctx, ctx->d_occlusion_work, srt::OCC_WORK_N)) return rc;
     }
-    void* dst = bound_or_own(ctx->d_rayout_bound[slot], ctx->d_rayout_own[slot]);
-    // the scene side of the kernel parameters, as srt_trace_rays fills it
-    srt_render_params p{};
-    p.row_begin = 0, p.row_end = ctx->height, p.first_sample = 1, p.sample_count = 1;
     srt::KernelParams K;
-    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
-    K.flags &= srt::KF_BOXES_FINITE;
-    K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // a trace touches none of them
+    const KernelSetup ks = scene_kernel_params(ctx, 0, ctx->height, K);
     srt::OcclusionIO io{};
     io.origin = ctx->rays.bound() ? (const float4*)ctx->rays.bound_origin : (const float4*)ctx->d_ray_origin;
     io.direction = ctx->rays.bound() ? (const float4*)ctx->rays.bound_direction : (const float4*)ctx->d_ray_direction;
@@ -1719,21 +1733,7 @@ int srt_trace_occlusion(srt_context* ctx, const srt_occlusion_params* t) {
     io.normalize = (t->flags & SRT_OCCLUSION_NORMALIZE) ? 1u : 0u;
     io.occluded = (int32_t*)dst;
     io.work = count ? (unsigned long long*)ctx->d_occlusion_work : nullptr;
-    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
-    using Kernel = void (*)(srt::KernelParams, srt::OcclusionIO);
-    const Kernel plain = in_lds ? (mesh ? srt::occlusion_kernel<true, true, false> : srt::occlusion_kernel<true, false, false>)
-                                : (mesh ? srt::occlusion_kernel<false, true, false> : srt::occlusion_kernel<false, false, false>);
-    const Kernel counting = in_lds ? (mesh ? srt::occlusion_kernel<true, true, true> : srt::occlusion_kernel<true, false, true>)
-                                   : (mesh ? srt::occlusion_kernel<false, true, true> : srt::occlusion_kernel<false, false, true>);
-    const Kernel kernel = count ? counting : plain;
-    // persistent workgroups, sized as srt_trace_rays sizes them
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, srt::WG_THREADS, ks.lds_bytes) != hipSuccess || per_cu < 1)
-        per_cu = 1, (void)hipGetLastError();
-    per_cu = per_cu > 4 ? 4 : per_cu;
-    const unsigned wgs = srt::rays_grid(n, srt::WG_TILES_X * srt::WG_TILES_Y, (long long)ctx->cu_count * per_cu);
-    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io);
-    SRT_HIP(ctx, hipGetLastError());
+    if (const int rc = launch_rays(ctx, SRT_KERNEL_LDS_MESH_COUNT(srt::occlusion_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count), n, ks, K, io)) return rc;
     srt::occlusion_traced(ctx->rays, ctx->occlusion, dst, t->flags);
     return SRT_OK;
 }
@@ -1742,9 +1742,8 @@ int srt_get_occlusion_work(srt_context* ctx, srt_occlusion_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
     if (srt::occlusion_check_work(ctx->occlusion) != srt::RAYS_OK)
         return fail(ctx, SRT_ERR_STATE, "srt_get_occlusion_work: the last srt_trace_occlusion did not ask for SRT_OCCLUSION_COUNT_WORK (or there has been none)");
-    if (const int rc = finish_stream(ctx)) return rc;
     unsigned long long w[srt::OCC_WORK_N];
-    SRT_HIP(ctx, hipMemcpy(w, ctx->d_occlusion_work, sizeof w, hipMemcpyDeviceToHost));
+    if (const int rc = read_work(ctx, ctx->d_occlusion_work, w, srt::OCC_WORK_N)) return rc;
     out->valid = 1, out->reserved = 0;
     out->rays = w[srt::OCC_WORK_RAYS], out->occluded = w[srt::OCC_WORK_OCCLUDED];
     out->analytic_tests = w[srt::OCC_WORK_ANALYTIC], out->node_visits = w[srt::OCC_WORK_NODES], out->triangle_tests = w[srt::OCC_WORK_TRIANGLES];
@@ -1770,57 +1769,33 @@ int srt_render_visibility(srt_context* ctx, const srt_visibility_params* v) {
     if (!ctx || !v) return SRT_ERR_INVALID_ARG;
     const srt::VisibilityCall call{v->row_begin, v->row_end, v->outputs, v->flags, v->ao_samples, v->first_sample, v->seed, v->ao_radius};
     bool present[srt::VIS_GUIDES];
-    for (int i = 0; i < srt::VIS_GUIDES; ++i) present[i] = bound_or_own(ctx->d_gbuf_bound[i], ctx->d_gbuf_own[i]) != nullptr;
+    for (int i = 0; i < srt::VIS_GUIDES; ++i) present[i] = current(ctx->gbuf[i], ctx->d_gbuf_own[i]) != nullptr;
     const char* why = "";
     if (const srt::RaysStatus rs = srt::visibility_check(call, ctx->scene_set, ctx->height, present, &why))
         return fail(ctx, (int)rs, "srt_render_visibility: %s (rows [%d,%d) of %d, outputs 0x%x, flags 0x%x, ao_samples %u, first_sample %u, ao_radius %g)", why,
                     v->row_begin, v->row_end, ctx->height, v->outputs, v->flags, v->ao_samples, v->first_sample, (double)v->ao_radius);
     SRT_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t px = (size_t)ctx->width * (size_t)ctx->height;
     const bool count = (v->flags & SRT_VIS_COUNT_WORK) != 0;
+    const size_t px = frame_pixels(ctx);
     void* dst[srt::VIS_SLOTS] = {nullptr, nullptr};
-    for (int i = 0; i < srt::VIS_SLOTS; ++i) {
-        if (!(v->outputs & (1u << i))) continue;
-        if (!ctx->d_vis_bound[i]) SRT_HIP(ctx, ctx->d_vis_own[i].ensure(px * sizeof(float)));
-        dst[i] = bound_or_own(ctx->d_vis_bound[i], ctx->d_vis_own[i]);
-    }
+    for (int i = 0; i < srt::VIS_SLOTS; ++i)
+        if (v->outputs & (1u << i))
+            SRT_WRITE_TARGET(ctx, ctx->vis[i], ctx->d_vis_own[i], px * sizeof(float), dst[i]);
     if (count) {
-        if (!ctx->d_visibility_work) SRT_HIP(ctx, ctx->d_visibility_work.ensure(srt::VIS_WORK_N * sizeof(unsigned long long)));
-        SRT_HIP(ctx, hipMemsetAsync(ctx->d_visibility_work, 0, srt::VIS_WORK_N * sizeof(unsigned long long), ctx->stream));
+        if (const int rc = zero_work(ctx, ctx->d_visibility_work, srt::VIS_WORK_N)) return rc;
     }
-    // the scene side of the kernel parameters for this band, as srt_render_gbuffer takes them (the camera part is not read)
-    srt_render_params p{};
-    p.row_begin = v->row_begin, p.row_end = v->row_end, p.first_sample = 1, p.sample_count = 1;
     srt::KernelParams K;
-    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
-    K.flags &= srt::KF_BOXES_FINITE;
-    K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // the pass touches none of them
+    const KernelSetup ks = scene_kernel_params(ctx, v->row_begin, v->row_end, K);
     const bool ao = (v->outputs & SRT_VIS_AO) != 0;
     srt::VisibilityIO io{};
-    io.object = (const int32_t*)bound_or_own(ctx->d_gbuf_bound[0], ctx->d_gbuf_own[0]);
-    io.normal_depth = (const float4*)bound_or_own(ctx->d_gbuf_bound[1], ctx->d_gbuf_own[1]);
-    io.position = (const float4*)bound_or_own(ctx->d_gbuf_bound[2], ctx->d_gbuf_own[2]);
+    io.object = (const int32_t*)current(ctx->gbuf[0], ctx->d_gbuf_own[0]);
+    io.normal_depth = (const float4*)current(ctx->gbuf[1], ctx->d_gbuf_own[1]);
+    io.position = (const float4*)current(ctx->gbuf[2], ctx->d_gbuf_own[2]);
     io.ao = (float*)dst[0], io.sun = (float*)dst[1];
     io.n = ao ? v->ao_samples : 1u, io.first_sample = ao ? v->first_sample : 1u, io.seed = ao ? v->seed : 0u;
     io.radius = ao ? v->ao_radius : INFINITY;
     io.work = count ? (unsigned long long*)ctx->d_visibility_work : nullptr;
-    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
-    using Kernel = void (*)(srt::KernelParams, srt::VisibilityIO);
-    const Kernel plain = in_lds ? (mesh ? srt::visibility_kernel<true, true, false> : srt::visibility_kernel<true, false, false>)
-                                : (mesh ? srt::visibility_kernel<false, true, false> : srt::visibility_kernel<false, false, false>);
-    const Kernel counting = in_lds ? (mesh ? srt::visibility_kernel<true, true, true> : srt::visibility_kernel<true, false, true>)
-                                   : (mesh ? srt::visibility_kernel<false, true, true> : srt::visibility_kernel<false, false, true>);
-    const Kernel kernel = count ? counting : plain;
-    // persistent workgroups, sized as srt_render_gbuffer sizes them
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, srt::WG_THREADS, ks.lds_bytes) != hipSuccess || per_cu < 1)
-        per_cu = 1, (void)hipGetLastError();
-    per_cu = per_cu > 4 ? 4 : per_cu;
-    const long long tiles = (long long)((ctx->width + srt::TILE_W - 1) / srt::TILE_W) * ((K.rows + srt::TILE_H - 1) / srt::TILE_H);
-    const long long need = (tiles + srt::WG_TILES_X * srt::WG_TILES_Y - 1) / (srt::WG_TILES_X * srt::WG_TILES_Y);
-    const long long wgs = std::min<long long>(need, (long long)ctx->cu_count * per_cu);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io);
-    SRT_HIP(ctx, hipGetLastError());
+    if (const int rc = launch_tiles(ctx, SRT_KERNEL_LDS_MESH_COUNT(srt::visibility_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count), ks, K, io)) return rc;
     srt::visibility_rendered(ctx->visibility, v->outputs, dst, v->flags);
     return SRT_OK;
 }
@@ -1829,28 +1804,24 @@ int srt_bind_visibility(srt_context* ctx, uint32_t output, void* d_float) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
     const int i = srt::visibility_slot(output);
     if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_visibility: output 0x%x is not a single SRT_VIS_* bit", output);
-    ctx->d_vis_bound[i] = d_float;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_gbuffer)
-    return SRT_OK;
+    return ctx->vis[i].bind(d_float), SRT_OK;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_gbuffer)
 }
 
 int srt_read_visibility(srt_context* ctx, uint32_t output, float* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
     const void* src = nullptr;
-    if (const srt::RaysStatus rs = srt::visibility_check_read(ctx->visibility, output, &src))
-        return fail(ctx, (int)rs, rs == srt::RAYS_STATE ? "srt_read_visibility: the last srt_render_visibility did not write output 0x%x (or there has been none)"
-                                                        : "srt_read_visibility: output 0x%x is not a single SRT_VIS_* bit", output);
-    if (const int rc = finish_stream(ctx)) return rc;
-    SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * sizeof(float), hipMemcpyDeviceToHost));
-    return SRT_OK;
+    const srt::RaysStatus rs = srt::visibility_check_read(ctx->visibility, output, &src);
+    if (rs == srt::RAYS_INVALID_ARG) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_visibility: output 0x%x is not a single SRT_VIS_* bit", output);
+    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, frame_pixels(ctx) * sizeof(float),
+                     "srt_read_visibility: the last srt_render_visibility did not write output 0x%x (or there has been none)", output);
 }
 
 int srt_get_visibility_work(srt_context* ctx, srt_visibility_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
     if (srt::visibility_check_work(ctx->visibility) != srt::RAYS_OK)
         return fail(ctx, SRT_ERR_STATE, "srt_get_visibility_work: the last srt_render_visibility did not ask for SRT_VIS_COUNT_WORK (or there has been none)");
-    if (const int rc = finish_stream(ctx)) return rc;
     unsigned long long w[srt::VIS_WORK_N];
-    SRT_HIP(ctx, hipMemcpy(w, ctx->d_visibility_work, sizeof w, hipMemcpyDeviceToHost));
+    if (const int rc = read_work(ctx, ctx->d_visibility_work, w, srt::VIS_WORK_N)) return rc;
     out->valid = 1, out->reserved = 0;
     out->segments = w[srt::VIS_WORK_SEGMENTS], out->open = w[srt::VIS_WORK_OPEN], out->wave_trips = w[srt::VIS_WORK_TRIPS];
     out->analytic_tests = w[srt::VIS_WORK_ANALYTIC], out->node_visits = w[srt::VIS_WORK_NODES], out->triangle_tests = w[srt::VIS_WORK_TRIANGLES];
@@ -1883,10 +1854,10 @@ int srt_denoise(srt_context* ctx, const srt_denoise_params* d) {
     const void* guide[4] = {};
     if (const int rc = find_guides(ctx, "srt_denoise", demod ? 4 : 3, nullptr, guide)) return rc;
     SRT_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t px = (size_t)ctx->width * (size_t)ctx->height;
-    if (!ctx->d_dn_bound) SRT_HIP(ctx, ctx->d_dn_own.ensure(px * sizeof(float4)));
+    float4* out = nullptr;
+    const size_t px = frame_pixels(ctx);
+    SRT_WRITE_TARGET(ctx, ctx->dn, ctx->d_dn_own, px * sizeof(float4), out);
     SRT_HIP(ctx, ctx->d_dn_tmp.ensure(px * sizeof(float4)));
-    float4* const out = bound_or_own(ctx->d_dn_bound, ctx->d_dn_own);
     srt::DenoiseLevel L{};
     L.acc = ctx->d_acc;
     L.object = (const int32_t*)guide[0];
@@ -1920,23 +1891,18 @@ int srt_denoise(srt_context* ctx, const srt_denoise_params* d) {
         hipLaunchKernelGGL(last ? srt::denoise_kernel<true> : srt::denoise_kernel<false>, grid, block, 0, ctx->stream, L);
         SRT_HIP(ctx, hipGetLastError());
     }
-    ctx->dn_written = true;
+    ctx->dn.wrote(out);
     return SRT_OK;
 }
 
 int srt_bind_denoised(srt_context* ctx, void* d_float4) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    ctx->d_dn_bound = (float4*)d_float4;  // (no synchronisation: enqueued levels keep the buffer they were given)
-    return SRT_OK;
+    return ctx->dn.bind(d_float4), SRT_OK;  // (no synchronisation: enqueued levels keep the buffer they were given)
 }
 
 int srt_read_denoised(srt_context* ctx, float* dst_rgba) {
     if (!ctx || !dst_rgba) return SRT_ERR_INVALID_ARG;
-    const float4* src = bound_or_own(ctx->d_dn_bound, ctx->d_dn_own);
-    if (!ctx->dn_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_read_denoised: nothing has been denoised into this buffer yet");
-    if (const int rc = finish_stream(ctx)) return rc;
-    SRT_HIP(ctx, hipMemcpy(dst_rgba, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
-    return SRT_OK;
+    return read_slot(ctx, ctx->dn.read_any(ctx->d_dn_own), dst_rgba, frame_pixels(ctx) * sizeof(float4), "srt_read_denoised: nothing has been denoised into this buffer yet");
 }
 
 // ---- temporal reprojection ------------------------------------------------------------------------------------------
@@ -2064,8 +2030,7 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
     }
     if (motion) T.table = ctx->d_tp_table, T.table_count = (int)ctx->objects.size();
     if (ctx->mv_on) {
-        if (!ctx->d_mv_bound) SRT_HIP(ctx, ctx->d_mv_own.ensure(px * sizeof(float4)));
-        T.motion = bound_or_own(ctx->d_mv_bound, ctx->d_mv_own);
+        SRT_WRITE_TARGET(ctx, ctx->mv, ctx->d_mv_own, px * sizeof(float4), T.motion);
     }
     if (ctx->mom_on) {
         T.mom_prev = ctx->d_mom[a];
@@ -2094,7 +2059,7 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
     ctx->tp_objects = ctx->objects;  // the list this history's points belong to
     ctx->tp_valid = true;
     ctx->tp_written = true;
-    if (ctx->mv_on) ctx->mv_last = T.motion;
+    if (ctx->mv_on) ctx->mv.wrote(T.motion);
     return SRT_OK;
 }
 
@@ -2106,17 +2071,12 @@ int srt_motion_output(srt_context* ctx, int enabled) {
 
 int srt_bind_motion(srt_context* ctx, void* d_float4) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    ctx->d_mv_bound = (float4*)d_float4;  // (no synchronisation: an enqueued call keeps the buffer it was given)
-    return SRT_OK;
+    return ctx->mv.bind(d_float4), SRT_OK;  // (no synchronisation: an enqueued call keeps the buffer it was given)
 }
 
 int srt_read_motion(srt_context* ctx, float* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
-    const float4* src = bound_or_own(ctx->d_mv_bound, ctx->d_mv_own);
-    if (!src || src != ctx->mv_last) return fail(ctx, SRT_ERR_STATE, "srt_read_motion: no srt_temporal_accumulate has written this buffer yet");
-    if (const int rc = finish_stream(ctx)) return rc;
-    SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
-    return SRT_OK;
+    return read_slot(ctx, ctx->mv.read_last_only(ctx->d_mv_own), dst, frame_pixels(ctx) * sizeof(float4), "srt_read_motion: no srt_temporal_accumulate has written this buffer yet");
 }
 
 int srt_moments_output(srt_context* ctx, int enabled, uint32_t flags) {
@@ -2131,10 +2091,8 @@ int srt_moments_output(srt_context* ctx, int enabled, uint32_t flags) {
 
 int srt_read_moments(srt_context* ctx, float* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
-    if (!ctx->mom_written) return fail(ctx, SRT_ERR_STATE, "srt_read_moments: the last srt_temporal_accumulate wrote no moments (srt_moments_output)");
-    if (const int rc = finish_stream(ctx)) return rc;
-    SRT_HIP(ctx, hipMemcpy(dst, ctx->d_mom[ctx->tp_cur], (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
-    return SRT_OK;
+    return read_slot(ctx, ctx->mom_written ? (const float4*)ctx->d_mom[ctx->tp_cur] : nullptr, dst, frame_pixels(ctx) * sizeof(float4),
+                     "srt_read_moments: the last srt_temporal_accumulate wrote no moments (srt_moments_output)");
 }
 
 int srt_temporal_variance_params_default(srt_temporal_variance_params* out) {
@@ -2157,12 +2115,11 @@ int srt_temporal_variance(srt_context* ctx, const srt_temporal_variance_params* 
     const void* guide[1] = {};
     if (const int rc = find_guides(ctx, "srt_temporal_variance", 1, nullptr, guide)) return rc;
     SRT_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t px = (size_t)ctx->width * (size_t)ctx->height;
-    if (!ctx->d_var_bound) SRT_HIP(ctx, ctx->d_var_own.ensure(px * sizeof(float)));
     srt::MomentsLaunch M{};
+    const size_t px = frame_pixels(ctx);
+    SRT_WRITE_TARGET(ctx, ctx->var, ctx->d_var_own, px * sizeof(float), M.variance);
     M.moments = ctx->d_mom[ctx->tp_cur];
     M.object = (const int32_t*)guide[0];
-    M.variance = bound_or_own(ctx->d_var_bound, ctx->d_var_own);
     M.width = ctx->width, M.height = ctx->height;
     M.samples = ctx->mom_samples;
     M.old_length = v->min_frames * ctx->mom_samples;
@@ -2171,8 +2128,8 @@ int srt_temporal_variance(srt_context* ctx, const srt_temporal_variance_params* 
                                                                 : srt::temporal_variance_kernel<3>;
     hipLaunchKernelGGL(kernel, frame_tile_grid(ctx), dim3(srt::WG_THREADS), 0, ctx->stream, M);
     SRT_HIP(ctx, hipGetLastError());
-    ctx->var_written = true;
-    if (!ctx->d_var_bound) ctx->var_own_written = true, ctx->var_own_albedo = (ctx->mom_written_flags & SRT_VARIANCE_ALBEDO) != 0;
+    ctx->var.wrote(M.variance);
+    if (!ctx->var.bound) ctx->var_own_written = true, ctx->var_own_albedo = (ctx->mom_written_flags & SRT_VARIANCE_ALBEDO) != 0;
     return SRT_OK;
 }
 
@@ -2215,10 +2172,11 @@ int srt_upsample(srt_context* ctx, const srt_upsample_params* u) {
     if (const int rc = find_guides(ctx, "srt_upsample", 3, nullptr, guide)) return rc;
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const bool in_place = (u->flags & SRT_UPSAMPLE_IN_PLACE) != 0;
-    if (!in_place && !ctx->d_up_bound) SRT_HIP(ctx, ctx->d_up_own.ensure((size_t)ctx->width * (size_t)ctx->height * sizeof(float4)));
     srt::UpsampleLaunch U{};
+    if (!in_place) {
+        SRT_WRITE_TARGET(ctx, ctx->up, ctx->d_up_own, (size_t)ctx->width * (size_t)ctx->height * sizeof(float4), U.dst);
+    }
     U.acc = ctx->d_acc;
-    U.dst = in_place ? nullptr : bound_or_own(ctx->d_up_bound, ctx->d_up_own);
     U.acc_rgb = in_place ? (float*)ctx->d_acc : nullptr;
     U.object = (const int32_t*)guide[0];
     U.normal_depth = (const float4*)guide[1];
@@ -2231,23 +2189,18 @@ int srt_upsample(srt_context* ctx, const srt_upsample_params* u) {
     U.sigma_plane = fminf(u->sigma_plane, FLT_MAX);  // as srt_denoise: FLT_MAX * 0 = 0 where inf * 0 (a first hit at d_p = 0) would be NaN
     hipLaunchKernelGGL(srt::upsample_kernel, frame_tile_grid(ctx), dim3(srt::WG_THREADS), 0, ctx->stream, U);
     SRT_HIP(ctx, hipGetLastError());
-    if (!in_place) ctx->up_written = true;
+    if (!in_place) ctx->up.wrote(U.dst);
     return SRT_OK;
 }
 
 int srt_bind_upsampled(srt_context* ctx, void* d_float4) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    ctx->d_up_bound = (float4*)d_float4;  // (no synchronisation: an enqueued call keeps the buffer it was given)
-    return SRT_OK;
+    return ctx->up.bind(d_float4), SRT_OK;  // (no synchronisation: an enqueued call keeps the buffer it was given)
 }
 
 int srt_read_upsampled(srt_context* ctx, float* dst_rgba) {
     if (!ctx || !dst_rgba) return SRT_ERR_INVALID_ARG;
-    const float4* src = bound_or_own(ctx->d_up_bound, ctx->d_up_own);
-    if (!ctx->up_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_read_upsampled: nothing has been upsampled into this buffer yet");
-    if (const int rc = finish_stream(ctx)) return rc;
-    SRT_HIP(ctx, hipMemcpy(dst_rgba, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
-    return SRT_OK;
+    return read_slot(ctx, ctx->up.read_any(ctx->d_up_own), dst_rgba, frame_pixels(ctx) * sizeof(float4), "srt_read_upsampled: nothing has been upsampled into this buffer yet");
 }
 
 // ---- anti-aliasing: sub-sample first hits and the resolve ------------------------------------------------------------------
@@ -2264,9 +2217,10 @@ int srt_render_subsamples(srt_context* ctx, const srt_subsample_params* g) {
     if (2ll * g->k * W >= (1ll << 24) || 2ll * g->k * H >= (1ll << 24))
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_render_subsamples: 2k x the frame (%d x %d, k %d) must stay below 2^24", W, H, g->k);
     SRT_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t px = (size_t)W * (size_t)H;
-    if (!ctx->d_ss_bound) {
-        SRT_HIP(ctx, ctx->d_ss_own.ensure((size_t)g->k * g->k * px * sizeof(int32_t)));
+    srt::SubsampleOut out{nullptr, g->k};
+    const size_t px = frame_pixels(ctx);
+    SRT_WRITE_TARGET(ctx, ctx->ss, ctx->d_ss_own, (size_t)g->k * g->k * px * sizeof(int32_t), out.sub);
+    if (!ctx->ss.bound) {
         if (ctx->ss_own_k != g->k || ctx->ss_own_scene != ctx->scene_changes || !same_camera(ctx->ss_own_cam, ctx->camera.cam) ||
             ctx->ss_own_rows.size() != (size_t)H) {
             ctx->ss_own_k = g->k, ctx->ss_own_scene = ctx->scene_changes, ctx->ss_own_cam = ctx->camera.cam;
@@ -2274,45 +2228,24 @@ int srt_render_subsamples(srt_context* ctx, const srt_subsample_params* g) {
         }
         std::fill(ctx->ss_own_rows.begin() + g->row_begin, ctx->ss_own_rows.begin() + g->row_end, true);
     }
-    // the render's kernel parameters for this band, as srt_render_gbuffer takes them
-    srt_render_params p{};
-    p.row_begin = g->row_begin, p.row_end = g->row_end, p.first_sample = 1, p.sample_count = 1;
     srt::KernelParams K;
-    const KernelSetup ks = fill_kernel_params(ctx, &p, K);
-    K.flags &= srt::KF_BOXES_FINITE;
-    K.accumulator = nullptr, K.framebuffer = nullptr, K.ray_counter = nullptr;  // the pass touches none of them
-    const srt::SubsampleOut out{bound_or_own(ctx->d_ss_bound, ctx->d_ss_own), g->k};
-    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
-    void (*const kernel)(srt::KernelParams, srt::SubsampleOut) = in_lds ? (mesh ? srt::subsample_kernel<true, true> : srt::subsample_kernel<true, false>)
-                                                                        : (mesh ? srt::subsample_kernel<false, true> : srt::subsample_kernel<false, false>);
-    // persistent workgroups, sized as srt_render_gbuffer sizes them
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, srt::WG_THREADS, ks.lds_bytes) != hipSuccess || per_cu < 1)
-        per_cu = 1, (void)hipGetLastError();
-    per_cu = per_cu > 4 ? 4 : per_cu;
-    const long long tiles = (long long)((W + srt::TILE_W - 1) / srt::TILE_W) * ((K.rows + srt::TILE_H - 1) / srt::TILE_H);
-    const long long need = (tiles + srt::WG_TILES_X * srt::WG_TILES_Y - 1) / (srt::WG_TILES_X * srt::WG_TILES_Y);
-    const long long wgs = std::min<long long>(need, (long long)ctx->cu_count * per_cu);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, out);
-    SRT_HIP(ctx, hipGetLastError());
-    ctx->ss_last_k = g->k;
+    const KernelSetup ks = scene_kernel_params(ctx, g->row_begin, g->row_end, K);
+    if (const int rc = launch_tiles(ctx, SRT_KERNEL_LDS_MESH(srt::subsample_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0), ks, K, out)) return rc;
+    ctx->ss.wrote(out.sub, (size_t)g->k);
     return SRT_OK;
 }
 
 int srt_bind_subsamples(srt_context* ctx, void* d_int32) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    ctx->d_ss_bound = (int32_t*)d_int32;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_gbuffer)
-    return SRT_OK;
+    return ctx->ss.bind(d_int32), SRT_OK;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_gbuffer)
 }
 
 int srt_read_subsamples(srt_context* ctx, int32_t* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
-    const int32_t* src = bound_or_own(ctx->d_ss_bound, ctx->d_ss_own);
-    const int k = ctx->d_ss_bound ? ctx->ss_last_k : ctx->ss_own_k;
-    if (!src || k < 1) return fail(ctx, SRT_ERR_STATE, "srt_read_subsamples: no sub-samples have been rendered into this buffer yet");
-    if (const int rc = finish_stream(ctx)) return rc;
-    SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)k * k * ctx->width * ctx->height * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return SRT_OK;
+    // (the k of a bound buffer is the last render's, into whichever buffer; the own buffer's is its own)
+    const size_t k = ctx->ss.bound ? ctx->ss.last_count : (size_t)ctx->ss_own_k;
+    return read_slot(ctx, k ? current(ctx->ss, ctx->d_ss_own) : nullptr, dst, k * k * frame_pixels(ctx) * sizeof(int32_t),
+                     "srt_read_subsamples: no sub-samples have been rendered into this buffer yet");
 }
 
 int srt_antialias_params_default(srt_antialias_params* out) {
@@ -2331,9 +2264,9 @@ int srt_antialias(srt_context* ctx, const srt_antialias_params* a) {
     if (a->flags & ~SRT_AA_FRAMEBUFFER) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_antialias: unknown flags 0x%x", a->flags);
     const void* guide[1] = {};
     if (const int rc = find_guides(ctx, "srt_antialias", 1, nullptr, guide)) return rc;
-    const int32_t* const sub = bound_or_own(ctx->d_ss_bound, ctx->d_ss_own);
+    const int32_t* const sub = current(ctx->ss, ctx->d_ss_own);
     if (!sub) return fail(ctx, SRT_ERR_STATE, "srt_antialias: the sub-sample buffer has neither been bound nor rendered (srt_render_subsamples)");
-    if (!ctx->d_ss_bound) {  // the handle's own: a whole frame of this k, scene and camera, or nothing
+    if (!ctx->ss.bound) {  // the handle's own: a whole frame of this k, scene and camera, or nothing
         if (ctx->ss_own_k != a->k) return fail(ctx, SRT_ERR_STATE, "srt_antialias: the sub-samples were rendered with k %d, not %d", ctx->ss_own_k, a->k);
         if (ctx->ss_own_scene != ctx->scene_changes || !ctx->camera.set || !same_camera(ctx->ss_own_cam, ctx->camera.cam))
             return fail(ctx, SRT_ERR_STATE, "srt_antialias: the sub-samples were rendered with another scene or camera (srt_render_subsamples after the change)");
@@ -2342,14 +2275,13 @@ int srt_antialias(srt_context* ctx, const srt_antialias_params* a) {
     }
     const float4* src = ctx->d_acc;
     if (a->source == SRT_AA_SOURCE_DENOISED) {
-        src = bound_or_own(ctx->d_dn_bound, ctx->d_dn_own);
-        if (!ctx->dn_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_antialias: SRT_AA_SOURCE_DENOISED before the first srt_denoise");
+        src = (const float4*)ctx->dn.read_any(ctx->d_dn_own);
+        if (!src) return fail(ctx, SRT_ERR_STATE, "srt_antialias: SRT_AA_SOURCE_DENOISED before the first srt_denoise");
     }
     SRT_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_aa_bound) SRT_HIP(ctx, ctx->d_aa_own.ensure((size_t)ctx->width * (size_t)ctx->height * sizeof(float4)));
     srt::AntialiasLaunch A{};
+    SRT_WRITE_TARGET(ctx, ctx->aa, ctx->d_aa_own, (size_t)ctx->width * (size_t)ctx->height * sizeof(float4), A.dst);
     A.src = src;
-    A.dst = bound_or_own(ctx->d_aa_bound, ctx->d_aa_own);
     A.object = (const int32_t*)guide[0];
     A.sub = sub;
     A.framebuffer = (a->flags & SRT_AA_FRAMEBUFFER) ? ctx->d_fb : nullptr;
@@ -2358,23 +2290,18 @@ int srt_antialias(srt_context* ctx, const srt_antialias_params* a) {
                                                  : a->k == 3 ? srt::antialias_kernel<3> : srt::antialias_kernel<4>;
     hipLaunchKernelGGL(kernel, frame_tile_grid(ctx), dim3(srt::WG_THREADS), 0, ctx->stream, A);
     SRT_HIP(ctx, hipGetLastError());
-    ctx->aa_written = true;
+    ctx->aa.wrote(A.dst);
     return SRT_OK;
 }
 
 int srt_bind_antialiased(srt_context* ctx, void* d_float4) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    ctx->d_aa_bound = (float4*)d_float4;  // (no synchronisation: an enqueued call keeps the buffer it was given)
-    return SRT_OK;
+    return ctx->aa.bind(d_float4), SRT_OK;  // (no synchronisation: an enqueued call keeps the buffer it was given)
 }
 
 int srt_read_antialiased(srt_context* ctx, float* dst_rgba) {
     if (!ctx || !dst_rgba) return SRT_ERR_INVALID_ARG;
-    const float4* src = bound_or_own(ctx->d_aa_bound, ctx->d_aa_own);
-    if (!ctx->aa_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_read_antialiased: nothing has been anti-aliased into this buffer yet");
-    if (const int rc = finish_stream(ctx)) return rc;
-    SRT_HIP(ctx, hipMemcpy(dst_rgba, src, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
-    return SRT_OK;
+    return read_slot(ctx, ctx->aa.read_any(ctx->d_aa_own), dst_rgba, frame_pixels(ctx) * sizeof(float4), "srt_read_antialiased: nothing has been anti-aliased into this buffer yet");
 }
 
 // ---- variance estimate and variance-guided denoiser -----------------------------------------------------------------------
@@ -2399,8 +2326,7 @@ int srt_device_half(srt_context* ctx, void** d_ptr) {
 
 int srt_bind_half(srt_context* ctx, void* d_float4) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    ctx->d_half_bound = (float4*)d_float4;  // (no synchronisation: an enqueued call keeps the buffer it was given)
-    return SRT_OK;
+    return ctx->half.bind(d_float4), SRT_OK;  // (no synchronisation: an enqueued call keeps the buffer it was given)
 }
 
 int srt_variance(srt_context* ctx, const srt_variance_params* v) {
@@ -2411,43 +2337,37 @@ int srt_variance(srt_context* ctx, const srt_variance_params* v) {
     const void* guide[4] = {};
     if (const int rc = find_guides(ctx, "srt_variance", 1, nullptr, guide)) return rc;
     if (demod) {
-        guide[3] = bound_or_own(ctx->d_gbuf_bound[3], ctx->d_gbuf_own[3]);
+        guide[3] = current(ctx->gbuf[3], ctx->d_gbuf_own[3]);
         if (!guide[3]) return fail(ctx, SRT_ERR_STATE, "srt_variance: the ALBEDO guide has neither been bound nor rendered (srt_render_gbuffer)");
     }
-    const float4* half = bound_or_own(ctx->d_half_bound, ctx->d_half_own);
+    const float4* half = current(ctx->half, ctx->d_half_own);
     if (!half) return fail(ctx, SRT_ERR_STATE, "srt_variance: the half buffer has neither been bound (srt_bind_half) nor fetched (srt_device_half)");
     SRT_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t px = (size_t)ctx->width * (size_t)ctx->height;
-    if (!ctx->d_var_bound) SRT_HIP(ctx, ctx->d_var_own.ensure(px * sizeof(float)));
+    const size_t px = frame_pixels(ctx);
     srt::VarianceLaunch V{};
+    SRT_WRITE_TARGET(ctx, ctx->var, ctx->d_var_own, px * sizeof(float), V.variance);
     V.acc = ctx->d_acc;
     V.half = half;
     V.object = (const int32_t*)guide[0];
     V.albedo = demod ? (const float4*)guide[3] : nullptr;
-    V.variance = bound_or_own(ctx->d_var_bound, ctx->d_var_own);
     V.pixels = px;
     V.merge = (v->flags & SRT_VARIANCE_MERGE) ? 1 : 0;
     const unsigned blocks = (unsigned)((px + srt::VARIANCE_THREADS - 1) / srt::VARIANCE_THREADS);
     hipLaunchKernelGGL(srt::variance_kernel, dim3(blocks), dim3(srt::VARIANCE_THREADS), 0, ctx->stream, V);
     SRT_HIP(ctx, hipGetLastError());
-    ctx->var_written = true;
-    if (!ctx->d_var_bound) ctx->var_own_written = true, ctx->var_own_albedo = demod;
+    ctx->var.wrote(V.variance);
+    if (!ctx->var.bound) ctx->var_own_written = true, ctx->var_own_albedo = demod;
     return SRT_OK;
 }
 
 int srt_bind_variance(srt_context* ctx, void* d_float) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    ctx->d_var_bound = (float*)d_float;  // (no synchronisation: an enqueued call keeps the buffer it was given)
-    return SRT_OK;
+    return ctx->var.bind(d_float), SRT_OK;  // (no synchronisation: an enqueued call keeps the buffer it was given)
 }
 
 int srt_read_variance(srt_context* ctx, float* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
-    const float* src = bound_or_own(ctx->d_var_bound, ctx->d_var_own);
-    if (!ctx->var_written || !src) return fail(ctx, SRT_ERR_STATE, "srt_read_variance: no variance has been written into this buffer yet");
-    if (const int rc = finish_stream(ctx)) return rc;
-    SRT_HIP(ctx, hipMemcpy(dst, src, (size_t)ctx->width * ctx->height * sizeof(float), hipMemcpyDeviceToHost));
-    return SRT_OK;
+    return read_slot(ctx, ctx->var.read_any(ctx->d_var_own), dst, frame_pixels(ctx) * sizeof(float), "srt_read_variance: no variance has been written into this buffer yet");
 }
 
 int srt_denoise_variance_params_default(srt_denoise_variance_params* out) {
@@ -2475,16 +2395,16 @@ int srt_denoise_variance(srt_context* ctx, const srt_denoise_variance_params* d)
     const bool demod = (d->flags & SRT_DENOISE_ALBEDO) != 0;
     const void* guide[4] = {};
     if (const int rc = find_guides(ctx, "srt_denoise_variance", demod ? 4 : 3, nullptr, guide)) return rc;
-    const float* const var = ctx->d_var_bound ? ctx->d_var_bound : ctx->var_own_written ? (float*)ctx->d_var_own : nullptr;
+    const float* const var = ctx->var.bound ? (const float*)ctx->var.bound : ctx->var_own_written ? (float*)ctx->d_var_own : nullptr;
     if (!var) return fail(ctx, SRT_ERR_STATE, "srt_denoise_variance: no variance buffer has been bound (srt_bind_variance) or written (srt_variance)");
-    if (!ctx->d_var_bound && ctx->var_own_albedo != demod)
+    if (!ctx->var.bound && ctx->var_own_albedo != demod)
         return fail(ctx, SRT_ERR_STATE, "srt_denoise_variance: the variance was estimated %s SRT_VARIANCE_ALBEDO, this call is %s SRT_DENOISE_ALBEDO",
                     ctx->var_own_albedo ? "with" : "without", demod ? "with" : "without");
     SRT_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t px = (size_t)ctx->width * (size_t)ctx->height;
-    if (!ctx->d_dn_bound) SRT_HIP(ctx, ctx->d_dn_own.ensure(px * sizeof(float4)));
+    float4* out = nullptr;
+    const size_t px = frame_pixels(ctx);
+    SRT_WRITE_TARGET(ctx, ctx->dn, ctx->d_dn_own, px * sizeof(float4), out);
     SRT_HIP(ctx, ctx->d_dn_tmp.ensure(px * sizeof(float4)));
-    float4* const out = bound_or_own(ctx->d_dn_bound, ctx->d_dn_own);
     srt::VarianceLevel L{};
     L.acc = ctx->d_acc;
     L.object = (const int32_t*)guide[0];
@@ -2515,7 +2435,7 @@ int srt_denoise_variance(srt_context* ctx, const srt_denoise_variance_params* d)
         hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, L);
         SRT_HIP(ctx, hipGetLastError());
     }
-    ctx->dn_written = true;
+    ctx->dn.wrote(out);
     return SRT_OK;
 }
 

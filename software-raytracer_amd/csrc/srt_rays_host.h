@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "srt_outputs_host.h"
+
 namespace srt {
 
 constexpr uint32_t RAYS_OUT_OBJECT = 1u, RAYS_OUT_NORMAL_DEPTH = 2u, RAYS_OUT_POSITION = 4u, RAYS_OUT_ALBEDO = 8u, RAYS_OUT_OCCLUDED = 16u;
@@ -85,6 +87,12 @@ inline void rays_traced(RaysState& s, uint32_t outputs, void* const dst[RAYS_SLO
     for (int i = 0; i < RAYS_SLOTS; ++i) s.last_dst[i] = (outputs & (1u << i)) ? dst[i] : nullptr;
 }
 
+// The handle's own buffer of output `slot`, at `own`, is about to be re-allocated for a larger batch: the last trace's copy of that
+// output goes with it.
+inline void rays_output_released(RaysState& s, int slot, const void* own) {
+    if (own && s.last_dst[slot] == own) s.last_dst[slot] = nullptr, s.last_outputs &= ~(1u << slot);
+}
+
 // srt_read_ray_output: the buffer and byte count to copy, or why not.
 inline RaysStatus rays_check_read(const RaysState& s, uint32_t output, const void** src, size_t* bytes) {
     const int i = rays_slot(output);
@@ -96,11 +104,6 @@ inline RaysStatus rays_check_read(const RaysState& s, uint32_t output, const voi
 }
 
 // Persistent workgroups of `waves` waves for `count` rays in blocks of 64: as many as there are blocks for, at most `resident`.
-inline unsigned rays_grid(size_t count, int waves, long long resident) {
-    const long long blocks = (long long)((count + 63) / 64);
-    const long long need = (blocks + waves - 1) / waves;
-    const long long g = need < resident ? need : resident;
-    return (unsigned)(g < 1 ? 1 : g);
-}
+inline unsigned rays_grid(size_t count, int waves, long long resident) { return persistent_grid((long long)((count + 63) / 64), waves, resident); }
 
 }  // namespace srt
