@@ -99,9 +99,8 @@ struct AntialiasLaunch {
 template <int KK>  // k
 __global__ void __launch_bounds__(WG_THREADS) antialias_kernel(const AntialiasLaunch A) {
     constexpr int K = KK * KK;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = (int)blockIdx.x * WG_W + (wave % WG_TILES_X) * TILE_W + (lane & 7);
-    const int y = (int)blockIdx.y * WG_H + (wave / WG_TILES_X) * TILE_H + (lane >> 3);
+    const TilePixel tp = tile_pixel();
+    const int x = tp.x, y = tp.y;
     const int W = A.width, H = A.height;
     if (x >= W || y >= H) return;
     const size_t plane = (size_t)W * (size_t)H;
@@ -155,8 +154,7 @@ __global__ void __launch_bounds__(WG_THREADS) antialias_kernel(const AntialiasLa
         }
         if (changed) out = make_float4(sr / (float)K, sg / (float)K, sb / (float)K, c.w);
     }
-    A.dst[p] = out;
-    if (A.framebuffer) A.framebuffer[(size_t)(H - 1 - y) * W + x] = tone_map(out);
+    store_result(A.dst, p, A.framebuffer, x, y, W, H, out);
 }
 
 }  // namespace srt

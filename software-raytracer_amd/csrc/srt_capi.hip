@@ -1840,6 +1840,61 @@ int srt_denoise_params_default(srt_denoise_params* out) {
     return SRT_OK;
 }
 
+// The à-trous levels of srt_denoise (variance NULL: the colour stop of sigma_color) and srt_denoise_variance (the luminance stop of
+// sigma_luminance over `variance`), after their checks: `guide` is what find_guides gave (ALBEDO with SRT_DENOISE_ALBEDO).
+static int atrous_filter(srt_context* ctx, const void* const* guide, int iterations, uint32_t flags, float sigma_normal, float sigma_plane,
+                         float sigma_color, float sigma_luminance, const float* variance) {
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    float4* out = nullptr;
+    const size_t px = frame_pixels(ctx);
+    SRT_WRITE_TARGET(ctx, ctx->dn, ctx->d_dn_own, px * sizeof(float4), out);
+    SRT_HIP(ctx, ctx->d_dn_tmp.ensure(px * sizeof(float4)));
+    srt::AtrousLevel L{};
+    L.acc = ctx->d_acc;
+    L.object = (const int32_t*)guide[0];
+    L.normal_depth = (const float4*)guide[1];
+    L.position = (const float4*)guide[2];
+    L.albedo = (flags & SRT_DENOISE_ALBEDO) ? (const float4*)guide[3] : nullptr;
+    L.variance = variance;
+    L.width = ctx->width, L.height = ctx->height;
+    // an infinite exponent becomes FLT_MAX: the same 0 for n_p.n_q < 1 and inf above 1, and 1 (FLT_MAX * log2 1 = 0, where
+    // inf * 0 would be NaN) for an exact n_p.n_q == 1, as on one face of a box
+    L.sigma_normal = fminf(sigma_normal, FLT_MAX);
+    // ... and so does an infinite sigma_plane: FLT_MAX * d_p is 0 for a first hit at d_p = 0, where inf * 0 would be NaN and
+    // turn every weight of the pixel, exact ties included, into NaN; for every other d_p the weights keep their bits
+    L.sigma_plane = fminf(sigma_plane, FLT_MAX);
+    // ... and sigma_luminance: FLT_MAX * sqrt(0) = 0 closes the stop on a zero variance, where inf * 0 would be NaN
+    L.sigma_luminance = fminf(sigma_luminance, FLT_MAX);
+    // [stop][last]: srt_denoise has the colour stop; srt_denoise_variance the luminance stop, or none with sigma_luminance = 0
+    using Kernel = void (*)(srt::AtrousLevel);
+    static const Kernel kernels[3][2] = {{srt::atrous_kernel<false, srt::STOP_COLOR>, srt::atrous_kernel<true, srt::STOP_COLOR>},
+                                         {srt::atrous_kernel<false, srt::STOP_LUMINANCE>, srt::atrous_kernel<true, srt::STOP_LUMINANCE>},
+                                         {srt::atrous_kernel<false, srt::STOP_NONE>, srt::atrous_kernel<true, srt::STOP_NONE>}};
+    const Kernel* const level = kernels[!variance ? srt::STOP_COLOR : sigma_luminance > 0.0f ? srt::STOP_LUMINANCE : srt::STOP_NONE];
+    const dim3 grid = frame_tile_grid(ctx), block(srt::WG_THREADS);
+    // the preparation pass and the levels alternate between the ping-pong buffer and the result buffer so that the last
+    // level lands in the result
+    const int n = iterations;
+    L.dst = (n & 1) ? ctx->d_dn_tmp : out;
+    hipLaunchKernelGGL(srt::atrous_prep_kernel, grid, block, 0, ctx->stream, L);
+    SRT_HIP(ctx, hipGetLastError());
+    for (int i = 0; i < n; ++i) {
+        const bool last = i == n - 1;
+        L.src = L.dst;
+        L.dst = ((n - 1 - i) & 1) ? ctx->d_dn_tmp : out;
+        L.step = 1 << i;
+        // any sigma_color > 0 keeps the term on at every level; a reciprocal past FLT_MAX (sigma_color * 2^-i below about
+        // 5.4e-20, or rounded to 0) stops there, so an exact tie c_p == c_q keeps its weight 1 (0 * inf would be NaN)
+        const float sc = sigma_color * ldexpf(1.0f, -i);
+        L.color_scale = sigma_color > 0.0f ? fminf(1.0f / (sc * sc), FLT_MAX) : 0.0f;
+        L.framebuffer = last && (flags & SRT_DENOISE_FRAMEBUFFER) ? ctx->d_fb : nullptr;
+        hipLaunchKernelGGL(level[last], grid, block, 0, ctx->stream, L);
+        SRT_HIP(ctx, hipGetLastError());
+    }
+    ctx->dn.wrote(out);
+    return SRT_OK;
+}
+
 int srt_denoise(srt_context* ctx, const srt_denoise_params* d) {
     if (!ctx || !d) return SRT_ERR_INVALID_ARG;
     if (d->iterations < 1 || d->iterations > 8)
@@ -1853,46 +1908,7 @@ int srt_denoise(srt_context* ctx, const srt_denoise_params* d) {
     const bool demod = (d->flags & SRT_DENOISE_ALBEDO) != 0;
     const void* guide[4] = {};
     if (const int rc = find_guides(ctx, "srt_denoise", demod ? 4 : 3, nullptr, guide)) return rc;
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    float4* out = nullptr;
-    const size_t px = frame_pixels(ctx);
-    SRT_WRITE_TARGET(ctx, ctx->dn, ctx->d_dn_own, px * sizeof(float4), out);
-    SRT_HIP(ctx, ctx->d_dn_tmp.ensure(px * sizeof(float4)));
-    srt::DenoiseLevel L{};
-    L.acc = ctx->d_acc;
-    L.object = (const int32_t*)guide[0];
-    L.normal_depth = (const float4*)guide[1];
-    L.position = (const float4*)guide[2];
-    L.albedo = demod ? (const float4*)guide[3] : nullptr;
-    L.width = ctx->width, L.height = ctx->height;
-    // an infinite exponent becomes FLT_MAX: the same 0 for n_p.n_q < 1 and inf above 1, and 1 (FLT_MAX * log2 1 = 0, where
-    // inf * 0 would be NaN) for an exact n_p.n_q == 1, as on one face of a box
-    L.sigma_normal = fminf(d->sigma_normal, FLT_MAX);
-    // ... and so does an infinite sigma_plane: FLT_MAX * d_p is 0 for a first hit at d_p = 0, where inf * 0 would be NaN and
-    // turn every weight of the pixel, exact ties included, into NaN; for every other d_p the weights keep their bits
-    L.sigma_plane = fminf(d->sigma_plane, FLT_MAX);
-    const dim3 grid = frame_tile_grid(ctx), block(srt::WG_THREADS);
-    // the preparation pass and the levels alternate between the ping-pong buffer and the result buffer so that the last
-    // level lands in the result
-    const int n = d->iterations;
-    L.dst = (n & 1) ? ctx->d_dn_tmp : out;
-    hipLaunchKernelGGL(srt::denoise_prep_kernel, grid, block, 0, ctx->stream, L);
-    SRT_HIP(ctx, hipGetLastError());
-    for (int i = 0; i < n; ++i) {
-        const bool last = i == n - 1;
-        L.src = L.dst;
-        L.dst = ((n - 1 - i) & 1) ? ctx->d_dn_tmp : out;
-        L.step = 1 << i;
-        // any sigma_color > 0 keeps the term on at every level; a reciprocal past FLT_MAX (sigma_color * 2^-i below about
-        // 5.4e-20, or rounded to 0) stops there, so an exact tie c_p == c_q keeps its weight 1 (0 * inf would be NaN)
-        const float sc = d->sigma_color * ldexpf(1.0f, -i);
-        L.color_scale = d->sigma_color > 0.0f ? fminf(1.0f / (sc * sc), FLT_MAX) : 0.0f;
-        L.framebuffer = last && (d->flags & SRT_DENOISE_FRAMEBUFFER) ? ctx->d_fb : nullptr;
-        hipLaunchKernelGGL(last ? srt::denoise_kernel<true> : srt::denoise_kernel<false>, grid, block, 0, ctx->stream, L);
-        SRT_HIP(ctx, hipGetLastError());
-    }
-    ctx->dn.wrote(out);
-    return SRT_OK;
+    return atrous_filter(ctx, guide, d->iterations, d->flags, d->sigma_normal, d->sigma_plane, d->sigma_color, 0.0f, nullptr);
 }
 
 int srt_bind_denoised(srt_context* ctx, void* d_float4) {
@@ -2400,43 +2416,7 @@ int srt_denoise_variance(srt_context* ctx, const srt_denoise_variance_params* d)
     if (!ctx->var.bound && ctx->var_own_albedo != demod)
         return fail(ctx, SRT_ERR_STATE, "srt_denoise_variance: the variance was estimated %s SRT_VARIANCE_ALBEDO, this call is %s SRT_DENOISE_ALBEDO",
                     ctx->var_own_albedo ? "with" : "without", demod ? "with" : "without");
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    float4* out = nullptr;
-    const size_t px = frame_pixels(ctx);
-    SRT_WRITE_TARGET(ctx, ctx->dn, ctx->d_dn_own, px * sizeof(float4), out);
-    SRT_HIP(ctx, ctx->d_dn_tmp.ensure(px * sizeof(float4)));
-    srt::VarianceLevel L{};
-    L.acc = ctx->d_acc;
-    L.object = (const int32_t*)guide[0];
-    L.normal_depth = (const float4*)guide[1];
-    L.position = (const float4*)guide[2];
-    L.albedo = demod ? (const float4*)guide[3] : nullptr;
-    L.variance = var;
-    L.width = ctx->width, L.height = ctx->height;
-    L.sigma_normal = fminf(d->sigma_normal, FLT_MAX);  // as srt_denoise
-    L.sigma_plane = fminf(d->sigma_plane, FLT_MAX);    // as srt_denoise
-    // +inf counts as FLT_MAX: FLT_MAX * sqrt(0) = 0 closes the stop on a zero variance, where inf * 0 would be NaN
-    L.sigma_luminance = fminf(d->sigma_luminance, FLT_MAX);
-    const bool lum = d->sigma_luminance > 0.0f;
-    const dim3 grid = frame_tile_grid(ctx), block(srt::WG_THREADS);
-    // the preparation pass and the levels alternate between the ping-pong buffer and the result buffer as srt_denoise's do
-    const int n = d->iterations;
-    L.dst = (n & 1) ? ctx->d_dn_tmp : out;
-    hipLaunchKernelGGL(srt::denoise_variance_prep_kernel, grid, block, 0, ctx->stream, L);
-    SRT_HIP(ctx, hipGetLastError());
-    for (int i = 0; i < n; ++i) {
-        const bool last = i == n - 1;
-        L.src = L.dst;
-        L.dst = ((n - 1 - i) & 1) ? ctx->d_dn_tmp : out;
-        L.step = 1 << i;
-        L.framebuffer = last && (d->flags & SRT_DENOISE_FRAMEBUFFER) ? ctx->d_fb : nullptr;
-        void (*const kernel)(srt::VarianceLevel) = last ? (lum ? srt::denoise_variance_kernel<true, true> : srt::denoise_variance_kernel<true, false>)
-                                                        : (lum ? srt::denoise_variance_kernel<false, true> : srt::denoise_variance_kernel<false, false>);
-        hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, L);
-        SRT_HIP(ctx, hipGetLastError());
-    }
-    ctx->dn.wrote(out);
-    return SRT_OK;
+    return atrous_filter(ctx, guide, d->iterations, d->flags, d->sigma_normal, d->sigma_plane, 0.0f, d->sigma_luminance, var);
 }
 
 int srt_wait(srt_context* ctx) {

@@ -148,6 +148,19 @@ constexpr int TILE_W = 8, TILE_H = 8;       // per wavefront
 constexpr int WG_TILES_X = 2, WG_TILES_Y = 2;  // waves per workgroup
 constexpr int WG_THREADS = 64 * WG_TILES_X * WG_TILES_Y;
 constexpr int WG_W = TILE_W * WG_TILES_X, WG_H = TILE_H * WG_TILES_Y;
+// The pixel of a thread of the image passes (denoise, upsample, antialias, temporal, moments): a wave per TILE_W x TILE_H tile
+// (lane -> x = lane & 7, y = lane >> 3), WG_TILES_X x WG_TILES_Y waves per workgroup.  (lx, ly) is the pixel within the
+// workgroup's WG_W x WG_H, (x, y) within the frame; the caller checks it against the frame's size.
+struct TilePixel {
+    int lx, ly, x, y;
+};
+__device__ __forceinline__ TilePixel tile_pixel() {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    TilePixel t;
+    t.lx = (wave % WG_TILES_X) * TILE_W + (lane & 7), t.ly = (wave / WG_TILES_X) * TILE_H + (lane >> 3);
+    t.x = (int)blockIdx.x * WG_W + t.lx, t.y = (int)blockIdx.y * WG_H + t.ly;
+    return t;
+}
 // per-wave LDS scratch behind the scene image: work list of (ray lane, cluster) items + one
 // 64-bit result slot per lane (balanced phase 2 of closest_hit)
 constexpr int WORK_MAX = 512;
@@ -1260,6 +1273,15 @@ __device__ __forceinline__ uint32_t tone_map(const float4 acc) {
     float b = acc.z / (1.0f + acc.z);
     float a = acc.w / (0.0f + acc.w);
     return pack_channel(a) << 24 | pack_channel(r) << 16 | pack_channel(g) << 8 | pack_channel(b);
+}
+// The tail of an image pass: the tone-mapped pixel (x, y) of SCENE rows into memory row H - 1 - y, when a framebuffer is given
+__device__ __forceinline__ void store_framebuffer(uint32_t* framebuffer, int x, int y, int W, int H, const float4 r) {
+    if (framebuffer) framebuffer[(size_t)(H - 1 - y) * W + x] = tone_map(r);
+}
+// ... after the result pixel itself, p = x + y * W
+__device__ __forceinline__ void store_result(float4* dst, size_t p, uint32_t* framebuffer, int x, int y, int W, int H, const float4 r) {
+    dst[p] = r;
+    store_framebuffer(framebuffer, x, y, W, H, r);
 }
 __device__ __forceinline__ void store_pixel(const KernelParams& P, uint32_t pix, const float4 acc) {
     P.accumulator[pix] = acc;

@@ -45,9 +45,8 @@ __global__ void __launch_bounds__(WG_THREADS) temporal_variance_kernel(const Mom
     // (M1, M2, object as bits, 1); object -2 outside the frame.  The 1 is the tap's count: with all four components in use the
     // read stays one ds_read_b128
     __shared__ float4 tile[TH * MT_PITCH];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lx = (wave % WG_TILES_X) * TILE_W + (lane & 7), ly = (wave / WG_TILES_X) * TILE_H + (lane >> 3);
-    const int x = (int)blockIdx.x * WG_W + lx, y = (int)blockIdx.y * WG_H + ly;
+    const TilePixel tp = tile_pixel();
+    const int lx = tp.lx, ly = tp.ly, x = tp.x, y = tp.y;
     const int W = M.width, H = M.height;
     const bool inside = x < W && y < H;
     const size_t p = (size_t)x + (size_t)y * (size_t)W;

@@ -7,7 +7,7 @@
 // tests every tap against the stored guides of the previous call (object, plane distance, normal) and blends the counted
 // taps' colour and history length.  The history lives in two slots: the launch reads slot A and writes slot B, so no pixel
 // reads what another writes and no grid-wide barrier is needed.
-// Work shape as denoise_kernel: a wave per 8 x 8 tile (lane -> x = lane & 7, y = lane >> 3), four waves per workgroup
+// Work shape as atrous_kernel: a wave per 8 x 8 tile (lane -> x = lane & 7, y = lane >> 3), four waves per workgroup
 // (16 x 16 pixels), so every float4 row segment a wave touches is one 128-byte line.  No LDS, no atomics, no scratch.
 // Moving objects (srt_update_scene) add a per-object table (displacement since the previous call, keep flag), a per-lane
 // 16-byte gather keyed by the pixel's object index; srt_motion_output adds one float4 store per pixel.  Both are template
@@ -63,9 +63,8 @@ struct TemporalLaunch {
 // MOM: T.mom_next is written (include/srt_pathtrace.h, "moments"); no other value depends on it.
 template <bool MOTION, bool MV, bool MOM = false>
 __device__ __forceinline__ void temporal_pixel(const TemporalLaunch& T) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = (int)blockIdx.x * WG_W + (wave % WG_TILES_X) * TILE_W + (lane & 7);
-    const int y = (int)blockIdx.y * WG_H + (wave / WG_TILES_X) * TILE_H + (lane >> 3);
+    const TilePixel tp = tile_pixel();
+    const int x = tp.x, y = tp.y;
     const int W = T.width, H = T.height;
     if (x >= W || y >= H) return;
     const size_t p = (size_t)x + (size_t)y * (size_t)W;

@@ -8,14 +8,12 @@
 // around it (its own block's, the next block's to the right, above, and diagonally), weighs them bilinearly and by how well
 // their first hit agrees with its own, and never looks at a non-anchor pixel of the colour buffer.
 //
-// One launch.  Work shape as denoise_kernel and temporal_kernel: a wave per 8 x 8 tile (lane -> x = lane & 7, y = lane >> 3),
+// One launch.  Work shape as atrous_kernel and temporal_kernel: a wave per 8 x 8 tile (lane -> x = lane & 7, y = lane >> 3),
 // four waves per workgroup (16 x 16 pixels), so every float4 row segment a wave touches is one 128-byte line.  No LDS, no
-// atomics, no scratch.  The weights are the denoiser's (pow_pos, __expf, the clamped reciprocal plane scale).
+// atomics, no scratch.  The weights are the denoiser's (EdgeStop).
 // In place (SRT_UPSAMPLE_IN_PLACE) the launch reads anchors only and writes non-anchors only: no pixel reads what another
 // writes, so one launch needs no second buffer and no grid-wide barrier.
 #pragma once
-
-#include <cfloat>
 
 #include "srt_denoise.hip.h"
 
@@ -49,9 +47,8 @@ __device__ __forceinline__ void upsample_axis(int v, int origin, int end, int li
 }
 
 __global__ void __launch_bounds__(WG_THREADS) upsample_kernel(const UpsampleLaunch U) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = (int)blockIdx.x * WG_W + (wave % WG_TILES_X) * TILE_W + (lane & 7);
-    const int y = (int)blockIdx.y * WG_H + (wave / WG_TILES_X) * TILE_H + (lane >> 3);
+    const TilePixel tp = tile_pixel();
+    const int x = tp.x, y = tp.y;
     const int W = U.width, H = U.height;
     if (x >= W || y >= H) return;
     const size_t p = (size_t)x + (size_t)y * (size_t)W;
@@ -65,20 +62,8 @@ __global__ void __launch_bounds__(WG_THREADS) upsample_kernel(const UpsampleLaun
     const bool anchor = x == x0 && y == y0;  // its one tap is itself, weight 1: the input bits
     if (!anchor) {
         const int op = U.object[p];
-        const bool hit = op >= 0;
-        const bool use_n = hit && U.sigma_normal > 0.0f, use_x = hit && U.sigma_plane > 0.0f;
-        float3 np = make_float3(0.0f, 0.0f, 0.0f), xp = np;
-        float plane_scale = 0.0f;  // 1 / (sigma_plane * d_p), clamped as in denoise_kernel
-        if (use_n || use_x) {
-            const float4 nd = U.normal_depth[p];
-            np = make_float3(nd.x, nd.y, nd.z);
-            if (use_x) {
-                plane_scale = 1.0f / (U.sigma_plane * nd.w);
-                if (__builtin_isinf(plane_scale)) plane_scale = copysignf(FLT_MAX, plane_scale);
-                const float4 xx = U.position[p];
-                xp = make_float3(xx.x, xx.y, xx.z);
-            }
-        }
+        EdgeStop geo;  // a miss has no first hit to compare with: its taps (other misses) are weighed bilinearly alone
+        geo.load(U.normal_depth, U.position, p, U.sigma_normal, U.sigma_plane, op >= 0);
         float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -87,15 +72,7 @@ __global__ void __launch_bounds__(WG_THREADS) upsample_kernel(const UpsampleLaun
             if (qx < 0 || qy < 0 || w == 0.0f) continue;
             const size_t q = (size_t)qx + (size_t)qy * (size_t)W;
             if (U.object[q] != op) continue;  // another object: skipped before anything else of it is read
-            if (use_n) {
-                const float4 nq = U.normal_depth[q];
-                w = w * pow_pos(np.x * nq.x + np.y * nq.y + np.z * nq.z, U.sigma_normal);
-            }
-            if (use_x) {
-                const float4 xq = U.position[q];
-                const float d = np.x * (xq.x - xp.x) + np.y * (xq.y - xp.y) + np.z * (xq.z - xp.z);
-                w = w * __expf(-fabsf(d) * plane_scale);
-            }
+            w = geo.weight(U.normal_depth, U.position, q, w);
             const float4 cq = U.acc[q];
             sw = sw + w;
             sr = sr + w * cq.x;
@@ -111,7 +88,7 @@ __global__ void __launch_bounds__(WG_THREADS) upsample_kernel(const UpsampleLaun
         }
     }
     if (U.dst) U.dst[p] = out;
-    if (U.framebuffer) U.framebuffer[(size_t)(H - 1 - y) * W + x] = tone_map(out);
+    store_framebuffer(U.framebuffer, x, y, W, H, out);
 }
 
 }  // namespace srt
