@@ -96,7 +96,8 @@ constexpr size_t REC_WORDS = 1 + 4 * srt::TALLY_N;  // per block in the cost rec
 // srt_launch_shape.h is host-only C++ (unit-tested on the CPU) and repeats the kernel's tile geometry:
 static_assert(srt::OUT_TILE == srt::TILE_W && srt::OUT_TILE == srt::TILE_H && srt::OUT_WG_UNITS == srt::WG_TILES_X * srt::WG_TILES_Y, "srt_outputs_host.h and srt_kernel.hip.h disagree");
 static_assert(srt::SHAPE_TILE_H == srt::TILE_H && srt::SHAPE_WG_W == srt::WG_W && srt::SHAPE_WG_H == srt::WG_H && srt::SHAPE_WG_TILES_Y == srt::WG_TILES_Y &&
-              srt::SHAPE_WAVES_PER_WG == srt::WG_TILES_X * srt::WG_TILES_Y && srt::SHAPE_TALLY_N == srt::TALLY_N, "srt_launch_shape.h and srt_kernel.hip.h disagree");
+              srt::SHAPE_WAVES_PER_WG == srt::WG_TILES_X * srt::WG_TILES_Y && srt::SHAPE_TALLY_N == srt::TALLY_N && srt::SHAPE_ROWS_WG_SCRATCH_BYTES == (size_t)srt::WG_SCRATCH_BYTES_ROWS,
+              "srt_launch_shape.h and srt_kernel.hip.h disagree");
 
 struct HostCamera {
     srt_camera cam;
@@ -1340,16 +1341,19 @@ static void launch_pathtrace(bool tally, bool in_lds, bool multi, bool defer, di
     hipLaunchKernelGGL(kernel, grid, dim3(srt::WG_THREADS), lds_bytes, stream, K);
 }
 
-// The ROWS instantiations of the analytic pair — a launch in one chunk of full tiles whose sample colours go through rows of the sample
+// The ROWS instantiations of the analytic scenes — a launch in one chunk of full tiles whose sample colours go through rows of the sample
 // buffer (RenderLaunch.rows; the scene image is in LDS) — in place of k_lds / t_lds: the recording and the counting launch keep the
-// timed launch's shape.  Their workgroups have no ring in LDS.  Bit-identical to the others.
-template <int MIN_WAVES, bool MESH>
-static void launch_pathtrace_rows(bool tally, dim3 grid, size_t lds_bytes, hipStream_t stream, const srt::KernelParams& K) {
+// timed launch's shape.  Their workgroups have no ring in LDS (`lds_bytes` is theirs), and where six of them fit into a CU's LDS
+// (srt::rows_six_waves) the timed launch runs at six waves per SIMD: 80 VGPRs, no scratch.  A larger image keeps the five-wave
+// kernel (a bound of six would cost it three registers for nothing), and so does the counting instantiation, which would spill at
+// six.  Bit-identical to the others: the pool is per wave, and register allocation changes no bit under -ffp-contract=off.
+static void launch_pathtrace_rows(bool tally, bool six, dim3 grid, size_t lds_bytes, hipStream_t stream, const srt::KernelParams& K) {
     using srt::pathtrace_kernel;
     void (*const kernel)(srt::KernelParams) =
-        tally ? pathtrace_kernel<MIN_WAVES, MESH, true, false, false, false, true, true>     // t_lds_rows
-              : pathtrace_kernel<MIN_WAVES, MESH, true, false, false, false, false, true>;   // k_lds_rows
-    hipLaunchKernelGGL(kernel, grid, dim3(srt::WG_THREADS), lds_bytes - (size_t)(srt::WG_SCRATCH_BYTES - srt::WG_SCRATCH_BYTES_ROWS), stream, K);
+        tally ? pathtrace_kernel<5, false, true, false, false, false, true, true>     // t_lds_rows
+        : six ? pathtrace_kernel<6, false, true, false, false, false, false, true>    // k_lds_rows6
+              : pathtrace_kernel<5, false, true, false, false, false, false, true>;   // k_lds_rows
+    hipLaunchKernelGGL(kernel, grid, dim3(srt::WG_THREADS), lds_bytes, stream, K);
 }
 
 // The TALLY instantiations keep the wave-uniform loop counts (srt_kernel.hip.h, Tally): the recording launch of a band (its
@@ -1371,7 +1375,7 @@ static int launch_render(srt_context* ctx, const srt_render_params* p, srt::Kern
     }
     const bool timing = !(p->flags & SRT_RENDER_NO_TIMING);
     if (timing) SRT_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
-    // variants 1 / 3 are a development aid for in-process A/B timing
+    // variants 1 / 3 / 5 are a development aid for in-process A/B timing
     const bool multi = L.shape.tile_h < srt::TILE_H || (K.steps > 1 && !(K.flags & SRT_RENDER_PREVIEW)) || L.bgrid;
     if (K.n_tris > 0)  // EXTENSION: scenes with triangle meshes use the BVH-enabled instantiations
         launch_pathtrace<4, true>(tally, in_lds, multi, L.defer, L.grid, ks.lds_bytes, ctx->stream, K);
@@ -1381,8 +1385,14 @@ static int launch_render(srt_context* ctx, const srt_render_params* p, srt::Kern
     else if (ks.use == 3 && in_lds && !multi && !L.defer && !tally)
         hipLaunchKernelGGL((srt::pathtrace_kernel<3, false>), L.grid, dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K);
 #endif
-    else if (L.rows)  // (one chunk of full tiles of an analytic scene in LDS, never `multi` or L.defer)
-        launch_pathtrace_rows<5, false>(tally, L.grid, ks.lds_bytes, ctx->stream, K);
+    else if (L.rows) {  // (one chunk of full tiles of an analytic scene in LDS, never `multi` or L.defer)
+        const size_t rows_lds = ks.lds_bytes - (size_t)(srt::WG_SCRATCH_BYTES - srt::WG_SCRATCH_BYTES_ROWS);
+        bool six = srt::rows_six_waves(rows_lds);
+#ifdef SRT_DEV  // variant 5 keeps the five-wave rows kernel, for A/B timing against the six-wave one inside one library
+        if (ks.use == 5) six = false;
+#endif
+        launch_pathtrace_rows(tally, six, L.grid, rows_lds, ctx->stream, K);
+    }
     else
         // (five waves per SIMD, 96 VGPRs.  Since srt_powf's coefficients come from the LDS constants block — the 64-bit literals had
         // been living in hoisted register pairs — the kernels need 85..95 registers, the multi-sample hand-out of small tiles /

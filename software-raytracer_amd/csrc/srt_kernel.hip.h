@@ -8,7 +8,8 @@
 // it is MI355X-first and shares nothing with the reference's structure:
 //
 //   * one work-item = one pixel for set-up and output; wavefront (64 lanes) = 8x8 pixel tile;
-//     workgroup = 4 waves = 16x16 pixels (dealt to the waves pixel by pixel); 85..95 VGPRs -> 5 waves per SIMD (mesh: 120, 4).
+//     workgroup = 4 waves = 16x16 pixels (dealt to the waves pixel by pixel); 85..95 VGPRs -> 5 waves per SIMD (mesh: 120, 4; the timed
+//     ROWS instantiation: 80 VGPRs and no ring in LDS -> 6 waves where six workgroups' LDS fit, srt_launch_shape.h: rows_six_waves).
 //   * the flattened scene image (srt_scene_image.h) is staged ONCE per workgroup into LDS.
 //   * primary rays do not depend on the sample (no jitter, Raytracer.cpp:109-110): the primary
 //     hit is found once per pixel; pixels whose colour is sample-invariant finish immediately.
@@ -170,7 +171,8 @@ constexpr int WORK_MAX = 512;
 // more in flight); the extra wave wins that back and more: Scene_indirect -4.4 %, Scene3 -4.5 %, Scene1 -1.5 %, config 4 -5 %.
 // The ROWS instantiations of pathtrace_kernel (single-chunk launches of full tiles, srt_launch_shape.h: fold_from_rows) have no
 // ring at all: their sample colours go through rows of the sample buffer in global memory, and nothing limits how far a slot runs
-// ahead.  Everything else — small tiles, blocks, sample chunks, the probe — keeps this ring.
+// ahead; without the ring six of their workgroups fit into a CU's LDS, and the timed one runs SIX waves per SIMD (80 VGPRs) where
+// they do (srt_launch_shape.h: rows_six_waves).  Everything else — small tiles, blocks, sample chunks, the probe — keeps this ring.
 constexpr int RING_DEPTH = 2;
 constexpr int WAVE_RING_BYTES = 64 * RING_DEPTH * 16;
 // per-wave: 64 result slots (8 B) | work list (2 B) | 64 pixel records (48 B) | ring (16 B; not in the ROWS instantiations)
