@@ -1,7 +1,14 @@
 // srt::fold_from_rows (csrc/srt_launch_shape.h) — which launches send their sample colours through rows of the sample buffer —
 // on both sides of the sample minimum and of the byte cap, for every excluded launch kind, and through plan_launch_shape /
-// finish_launch_shape for the shapes real requests take.  Prints "ok <checks> min <ROWS_MIN_SAMPLES>".
+// finish_launch_shape for the shapes real requests take.
+//   rows_rule_check          the checks.  Prints "ok <checks> min <ROWS_MIN_SAMPLES>".
+//   rows_rule_check --ask    reads requests "w rows spp cu_count mesh preview steps block_grid scene_in_lds lds_bytes" (w x rows: the
+//                            launch's lanes; lds_bytes: what a rows workgroup asks for, six_wave_rule_check's figure) and prints for
+//                            each "tile_h chunks wg8 rows six rows_bytes": the finished shape of a first launch, fold_from_rows,
+//                            rows_six_waves(lds_bytes), and the rows' bytes (0 without rows).  The GPU tests take the kernel they
+//                            expect from here (tests/test_gpu_rows_at_scale.py, tests/test_gpu_paths.py).
 #include <stdio.h>
+#include <string.h>
 
 #include "srt_launch_shape.h"
 
@@ -24,8 +31,31 @@ static srt::LaunchShape shape_of(srt::ShapeRequest& q, int w, int rows, uint32_t
     return s;
 }
 
-int main() {
+// --ask: the rule's answer for the requests on stdin, as srt_render plans a first launch (no work record, no overrides)
+static int ask() {
+    long long w, rows;
+    unsigned spp;
+    int cu, mesh, preview, steps, block_grid, in_lds;
+    unsigned long long lds_bytes;
+    int n;
+    while ((n = scanf("%lld %lld %u %d %d %d %d %d %d %llu", &w, &rows, &spp, &cu, &mesh, &preview, &steps, &block_grid, &in_lds, &lds_bytes)) == 10) {
+        if (w < 1 || rows < 1 || rows > 0x7FFFFFFF || spp < 1 || cu < 1 || steps < 1) return 2;
+        srt::ShapeRequest q;
+        q.grid_w = w, q.grid_h = rows, q.rows = (int)rows, q.sample_count = spp, q.cu_count = cu;
+        q.mesh = mesh != 0, q.steps = steps, q.block_grid = block_grid != 0;
+        srt::LaunchShape s = srt::plan_launch_shape(q, nullptr);
+        srt::finish_launch_shape(s, spp);
+        const bool r = srt::fold_from_rows(s, q, preview != 0, in_lds != 0);
+        printf("%d %d %lld %d %d %llu\n", s.tile_h, s.chunks, s.wg8, r ? 1 : 0, srt::rows_six_waves((size_t)lds_bytes) ? 1 : 0,
+               r ? srt::rows_bytes(s, spp) : 0ull);
+    }
+    return n == EOF ? 0 : 2;  // (a line that does not parse is an error, not the end)
+}
+
+int main(int argc, char** argv) {
     using namespace srt;
+    if (argc == 2 && !strcmp(argv[1], "--ask")) return ask();
+    if (argc != 1) return 2;
     const uint32_t MIN = ROWS_MIN_SAMPLES;
     CHECK(MIN >= 2 && MIN <= 16);  // (from 16 samples on small frames take small tiles: below that the minimum can be met on any frame)
     ShapeRequest q;

@@ -3,22 +3,30 @@ oracle bit for bit (NaNs compared as NaNs): accumulator, framebuffer and ray cou
 
 srt_render picks one of nine instantiations for analytic scenes and nine for mesh scenes (srt_capi.hip, launch_pathtrace): scene
 image in LDS or in HBM (too big, or a sphere's r*r outside the short square root's window), full tiles / small tiles (the multi-sample
-hand-out) / sample chunks, with or without the loop counts (TALLY).  A cell of the matrix below is named after the instantiation it
-is meant to reach (the name launch_pathtrace gives it in a comment) and asserts, from the launch's stats and work counts, that it
-did.  Every cell runs from a reset and then resumed on
+hand-out) / sample chunks, with or without the loop counts (TALLY); and, for analytic scenes in LDS, one of three ROWS instantiations
+(launch_pathtrace_rows) in place of k_lds / t_lds where srt::fold_from_rows sends the sample colours through rows of the sample
+buffer: from two samples on in one chunk of full tiles, at six waves per SIMD where srt::rows_six_waves lets it.  A cell of the
+matrix below is named after the instantiation it is meant to reach (the name its launcher gives it in a comment) and asserts that
+it did: from the launch's stats and work counts and, as the library does not report rows / six waves (no ABI change), from the
+rule's own answer for the launch's request (tests/native/rows_rule_check.cpp --ask, tests/rows_rule.py).  The analytic ring kernels
+k_lds / t_lds are what one-sample launches (`loop`) and the preview shader keep.  Every cell runs from a reset and then resumed on
 a caller's accumulator that holds what the kernel's clamp elimination must not be fooled by (negatives, -0, 1e-38, a non-zero alpha),
 on a ragged band."""
 import ctypes as C
+import json
 import os
 import re
 
 import numpy as np
 import pytest
 
+import rows_rule
 from conftest import ROOT, scene_path
+from test_gpu_six_waves import _extra_sphere, threshold_counts
 
 ORACLE_THREADS = 16
-NAMES = ["k_lds", "k_lds_multi", "k_lds_defer", "k_hbm", "k_hbm_multi", "k_hbm_defer", "t_lds", "t_lds_multi", "t_lds_defer"]
+NAMES = ["k_lds", "k_lds_multi", "k_lds_defer", "k_hbm", "k_hbm_multi", "k_hbm_defer", "t_lds", "t_lds_multi", "t_lds_defer",
+         "k_lds_rows", "k_lds_rows6", "t_lds_rows"]
 NASTY = [(-1.0, 0.5, 2.0), (-0.0, 0.0, 1.0), (1e6, 1e-30, -1e6), (3.0, 0.25, -0.0), (1e-38, 1.0, -3.0), (0.0, -0.0, 7.5)]
 
 
@@ -53,9 +61,9 @@ def _odd_spheres(oracle, objs, r):
     objs.append(dict(type=oracle.OBJ_SPHERE, position=(0.3, 0.1, 3.0), radius=r, base=(.1, .9, .1)))
 
 
-def _scene(oracle, kind):
+def _scene(oracle, kind, n_over=0):
     """kind -> dict(objs, meshes, env, cam, hbm): the scene's objects, meshes, environment and camera as oracle structures, and
-    whether srt_set_scene must place its image in HBM"""
+    whether srt_set_scene must place its image in HBM.  n_over: the spheres of the extra "over" (test_gpu_six_waves's grid)"""
     env, cam, meshes = oracle.default_environment(), oracle.default_camera(), []
     base, _, extra = kind.partition("+")
     if base == "indirect":
@@ -88,6 +96,11 @@ def _scene(oracle, kind):
             hbm = True
         elif e == "farbox":  # a box beyond the NaN-free slab test's bound (KF_BOXES_FINITE off), out of view
             objs.append(dict(type=oracle.OBJ_BOX, position=(0.0, 0.0, -1e30), half_size=(1.0, 1.0, 1.0), base=(.5, .5, .5)))
+        elif e == "over":  # so many small spheres that six rows workgroups' LDS no longer fit into a CU: the five-wave rows kernel
+            assert n_over > 0
+            for k in range(n_over):
+                x, y, z, r = _extra_sphere(k)
+                objs.append(dict(type=oracle.OBJ_SPHERE, position=(x, y, z), radius=r, base=(.2 + .05 * (k % 13), .8, .3), smoothness=0.7))
         elif e == "nancam":  # every camera ray NaN: the oracle's alpha is NaN in every pixel
             cam.forward = oracle.f3((float("nan"), 0.0, 1.0))
         else:
@@ -145,18 +158,58 @@ def _path(path, mesh, w, h):
     }[path]
 
 
-def _cell_name(in_lds, counting, multi, defer):
+def _cell_name(in_lds, counting, multi, defer, rows=False, six=False):
+    """rows, six: the rule's answer for the launch's request (rows_rule.ask)"""
+    if rows:
+        assert in_lds and not multi and not defer
+        return "t_lds_rows" if counting else "k_lds_rows6" if six else "k_lds_rows"
     return ("t_" if counting and in_lds else "k_") + ("lds" if in_lds else "hbm") + ("_defer" if defer else "_multi" if multi else "")
+
+
+_LDS_BYTES = {}
+
+
+def _over_count(six_exe):
+    if "over" not in _LDS_BYTES:
+        _LDS_BYTES["over"] = threshold_counts(six_exe)
+    return _LDS_BYTES["over"]
+
+
+def _rows_lds_bytes(kind, six_exe, tmp_dir):
+    """LDS bytes of a rows workgroup for an analytic scene kind whose image lives in LDS, from six_wave_rule_check --grow: the kind's
+    scene file (materials, environment and camera do not enter the image's size), a far box appended to a copy of it, the grid's
+    spheres given as the program's input"""
+    base, _, extra = kind.partition("+")
+    extras = set(filter(None, extra.split("+"))) - {"nancam"}
+    key = (base if base != "clamps" else "indirect",) + tuple(sorted(extras))
+    if key not in _LDS_BYTES:
+        path = scene_path({"indirect": "Scene_indirect", "scene1": "Scene1"}[key[0]])
+        if "farbox" in extras:
+            doc = json.load(open(path))
+            doc["SceneObjects"].append({"Material": doc["SceneObjects"][0]["Material"], "Name": "", "Position": [0.0, 0.0, -1e30],
+                                        "Renderer": {"Size": [1.0, 1.0, 1.0], "Type": "Cube"}})
+            path = os.path.join(str(tmp_dir), "-".join(key) + ".json")
+            json.dump(doc, open(path, "w"))
+        assert extras <= {"farbox", "over"}, kind
+        n = _over_count(six_exe)["over"] if "over" in extras else 0
+        _LDS_BYTES[key] = rows_rule.grow(six_exe, path, [_extra_sphere(k) for k in range(n)])[n][1]
+    return _LDS_BYTES[key]
 
 
 # (name it must reach, scene kind, launch path, frame w, h); mesh cells have "mesh" in the kind
 ANALYTIC_LDS, ANALYTIC_HBM = ["indirect", "clamps", "scene1+farbox"], ["scene1+r0", "scene1+r1e-12", "clamps+r0", "scene1+farbox+r0", "scene1+rinf"]
 CELLS = []
 for kind in ANALYTIC_LDS + ["mesh"]:
-    CELLS += [("k_lds", kind, "full", 64, 40), ("k_lds_multi", kind, "small", 160, 24), ("k_lds_defer", kind, "chunks", 160, 24),
-              ("t_lds", kind, "full", 64, 40), ("t_lds_multi", kind, "small", 160, 24), ("t_lds_defer", kind, "chunks", 160, 24),
+    # `full` on an analytic scene in LDS (3 and 5 samples) goes through rows; mesh scenes keep the ring
+    full, full_counting = ("k_lds", "t_lds") if kind == "mesh" else ("k_lds_rows6", "t_lds_rows")
+    CELLS += [(full, kind, "full", 64, 40), ("k_lds_multi", kind, "small", 160, 24), ("k_lds_defer", kind, "chunks", 160, 24),
+              (full_counting, kind, "full", 64, 40), ("t_lds_multi", kind, "small", 160, 24), ("t_lds_defer", kind, "chunks", 160, 24),
               ("k_lds_multi", kind, "blocks", 70, 36), ("k_lds_multi", kind, "bgrid", 70, 36), ("k_lds", kind, "preview", 64, 40),
               ("k_lds", kind, "loop", 64, 40)]
+# the analytic ring kernel that counts: one-sample launches and the preview shader with SRT_RENDER_COUNT_WORK
+CELLS += [("t_lds", kind, "loop", 64, 40) for kind in ANALYTIC_LDS] + [("t_lds", "indirect", "preview", 64, 40)]
+# the five-wave rows kernel: Scene1 with the grid of small spheres that takes six workgroups' LDS over a CU's
+CELLS += [("k_lds_rows", "scene1+over", "full", 64, 40), ("t_lds_rows", "scene1+over", "full", 64, 40)]
 for kind in ANALYTIC_HBM + ["mesh+r0"]:
     CELLS += [("k_hbm", kind, "full", 64, 40), ("k_hbm_multi", kind, "small", 160, 24), ("k_hbm_defer", kind, "chunks", 160, 24),
               ("k_hbm_multi", kind, "blocks", 70, 36), ("k_hbm_multi", kind, "bgrid", 70, 36), ("k_hbm", kind, "preview", 64, 40),
@@ -165,7 +218,7 @@ CELLS += [("k_hbm", "big", "full", 48, 32), ("k_hbm_multi", "big", "small", 64, 
 # a band of 256 blocks: the first launch records its work (the TALLY kernel in any case), the resumed one runs with the recorded shape
 CELLS += [("t_lds_defer", "indirect", "chunks", 256, 261)]
 # every camera ray NaN
-CELLS += [("k_lds", "indirect+nancam", "full", 64, 40), ("k_lds_multi", "indirect+nancam", "bgrid", 70, 36), ("k_lds", "indirect+nancam", "preview", 64, 40),
+CELLS += [("k_lds_rows6", "indirect+nancam", "full", 64, 40), ("k_lds_multi", "indirect+nancam", "bgrid", 70, 36), ("k_lds", "indirect+nancam", "preview", 64, 40),
           ("k_lds_defer", "indirect+nancam", "chunks", 160, 24), ("k_hbm_multi", "scene1+r0+nancam", "small", 160, 24)]
 
 
@@ -192,12 +245,29 @@ def _render_both(srt, oracle, pt, sc, w, h, kw, acc_in, bounces, seed, first_sam
     return ofb, oacc, orays, stats, rows
 
 
+@pytest.fixture(scope="module")
+def rule(tmp_path_factory):
+    return rows_rule.rows_rule_exe(tmp_path_factory)
+
+
+@pytest.fixture(scope="module")
+def six_exe(tmp_path_factory):
+    return rows_rule.six_wave_rule_exe(tmp_path_factory)
+
+
+@pytest.fixture(scope="module")
+def cu_count():
+    import torch
+
+    return int(torch.cuda.get_device_properties(0).multi_processor_count)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("cell", CELLS, ids=[_cell_id(c) for c in CELLS])
-def test_launch_path_equals_the_oracle(srt, oracle, cell):
+def test_launch_path_equals_the_oracle(srt, oracle, rule, six_exe, cu_count, tmp_path, cell):
     name, kind, path, w, h = cell
     mesh = "mesh" in kind
-    sc = _scene(oracle, kind)
+    sc = _scene(oracle, kind, _over_count(six_exe)["over"] if "over" in kind else 0)
     in_lds = _placed_in_lds(srt, sc)
     assert in_lds == (not sc["hbm"]), (kind, in_lds)
     counting = name.startswith("t_")
@@ -211,14 +281,20 @@ def test_launch_path_equals_the_oracle(srt, oracle, cell):
             acc = _caller_accumulator(h, w, 1000 + len(name) + w)
             pt.write_accumulator(acc)
         ofb, oacc, orays, stats, rows = _render_both(srt, oracle, pt, sc, w, h, kw, acc, bounces, 31 + run, fs, reset, counting)
+        # the rule's answer for this request (w x rows: the pixels; a block grid has fewer lanes, and never rows)
+        steps = kw.get("steps", 1)
+        ans = rows_rule.ask(rule, [dict(w=w, rows=rows[1] - rows[0] if rows is not None else h, spp=kw["spp"], cu_count=cu_count, mesh=mesh,
+                                        preview=kw.get("preview", False), steps=steps, block_grid=steps > 1 and (reset or kw["spp"] == 1),
+                                        scene_in_lds=in_lds, lds_bytes=_rows_lds_bytes(kind, six_exe, tmp_path) if in_lds and not mesh else 0)])[0]
         for st in stats:
             rays, tile_rows, chunks, chunk_samples, source, valid = st
-            steps = kw.get("steps", 1)
             multi = tile_rows < 8 or (steps > 1 and not kw.get("preview"))
             defer = chunks >= 2
-            print("%s %s %s run %d: tile_rows %d sample_chunks %d chunk_samples %d shape_source %d work_valid %s" %
-                  (name, kind, path, run, tile_rows, chunks, chunk_samples, source, valid))
-            assert _cell_name(in_lds, counting, multi, defer) == name, (st, kw)
+            print("%s %s %s run %d: tile_rows %d sample_chunks %d chunk_samples %d shape_source %d work_valid %s; rule: rows %d six %d" %
+                  (name, kind, path, run, tile_rows, chunks, chunk_samples, source, valid, ans.rows, ans.six))
+            if ans.rows:  # (the rule plans a first launch; a recorded band changes only the chunks of 32 samples and more)
+                assert (tile_rows, chunks) == (ans.tile_h, ans.chunks) == (8, 1), (st, ans)
+            assert _cell_name(in_lds, counting, multi, defer, ans.rows, ans.six) == name, (st, kw, ans)
             assert (chunk_samples > 0) == defer and (tile_rows == 8 or not defer)
             if counting:
                 assert valid == 1
@@ -278,7 +354,8 @@ def test_frame_numbers_past_2_24_and_at_the_limit(srt, oracle, path, first_sampl
 # ---- the matrix covers every shipped instantiation
 def _shipped_instantiations():
     """(kind, cell name, template arguments) of every pathtrace_kernel<...> that srt_render's shipped (non-SRT_DEV) code launches:
-    the cells of launch_pathtrace<MIN_WAVES, MESH>, each named by its comment, for every <MIN_WAVES, MESH> the shipped code calls"""
+    the cells of launch_pathtrace<MIN_WAVES, MESH>, each named by its comment, for every <MIN_WAVES, MESH> the shipped code calls,
+    and the three of launch_pathtrace_rows, which spell their <MIN_WAVES, MESH> out"""
     src = open(os.path.join(ROOT, "software-raytracer_amd", "csrc", "srt_capi.hip")).read()
     shipped, skip = [], 0
     for line in src.split("\n"):  # drop #ifdef SRT_DEV ... #endif blocks
@@ -303,14 +380,26 @@ def _shipped_instantiations():
         cells.append((m.group(1).replace(" ", ""), m.group(2)))
     calls = re.findall(r"\blaunch_pathtrace<(\d+), (true|false)>\(", src)
     assert calls, "srt_render launches no launch_pathtrace<MIN_WAVES, MESH>"
-    return [("mesh" if mesh == "true" else "analytic", name, "%s,%s,%s" % (waves, mesh, args))
-            for waves, mesh in calls for args, name in cells]
+    found = [("mesh" if mesh == "true" else "analytic", name, "%s,%s,%s" % (waves, mesh, args))
+             for waves, mesh in calls for args, name in cells]
+    start = src.index("static void launch_pathtrace_rows(")
+    helper = src[start:src.index("\n}\n", start)]
+    for line in helper.split("\n"):
+        if "pathtrace_kernel<" not in line:
+            continue
+        m = re.search(r"pathtrace_kernel<(\d+), (true|false), ([^>]*)>.*//\s*(\w+)\s*$", line)
+        assert m, "a launch_pathtrace_rows cell without a name: " + line
+        assert m.group(3).replace(" ", "").endswith(",true") and m.group(3).count(",") == 5, "not a ROWS instantiation: " + line
+        found.append(("mesh" if m.group(2) == "true" else "analytic", m.group(4), "%s,%s,%s" % (m.group(1), m.group(2), m.group(3).replace(" ", ""))))
+    assert re.search(r"\blaunch_pathtrace_rows\(tally, six,", src), "srt_render does not call launch_pathtrace_rows"
+    return found
 
 
 def test_matrix_covers_every_launch_pathtrace_instantiation():
     found = _shipped_instantiations()
-    assert len(found) == 18, found
-    assert len({f[2] for f in found}) == 18, "an instantiation is named twice"
+    assert len(found) == 21, found
+    assert len({f[2] for f in found}) == 21, "an instantiation is named twice"
+    assert sorted(n for _, n, _ in found if "rows" in n) == ["k_lds_rows", "k_lds_rows6", "t_lds_rows"]
     shipped = {(k, n) for k, n, _ in found}
     covered = {("mesh" if "mesh" in c[1] else "analytic", c[0]) for c in CELLS}
     assert covered == shipped, ("not covered", sorted(shipped - covered), "not shipped", sorted(covered - shipped))

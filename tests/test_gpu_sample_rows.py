@@ -36,6 +36,12 @@ MIN = _rows_min()
 _SCENES, _ORACLE = {}, {}
 
 
+def nansmooth_sphere(oracle):
+    """a sphere whose smoothness is NaN: the rays that leave it are NaN, and so is the alpha of the samples that end in the
+    environment behind them"""
+    return dict(type=oracle.OBJ_SPHERE, position=(0.3, 0.1, 3.0), radius=0.6, base=(.9, .2, .1), specular_amount=0.5, smoothness=float("nan"))
+
+
 def _scene(oracle, kind):
     """kind -> (objects, count, meshes or None); built once"""
     if kind not in _SCENES:
@@ -51,7 +57,7 @@ def _scene(oracle, kind):
             objs.insert(3, dict(type=oracle.OBJ_SPHERE, position=(0.0, 0.0, 2.0), radius=inf, base=(.9, .2, .1), emissive=(0.5, 0.5, 0.5)))
             objs.append(dict(type=oracle.OBJ_SPHERE, position=(0.3, 0.1, 3.0), radius=inf, base=(.1, .9, .1)))
         elif kind == "nansmooth":
-            objs.append(dict(type=oracle.OBJ_SPHERE, position=(0.3, 0.1, 3.0), radius=0.6, base=(.9, .2, .1), specular_amount=0.5, smoothness=float("nan")))
+            objs.append(nansmooth_sphere(oracle))
         else:
             assert kind == "scene1"
         oarr, n = oracle.make_objects(objs)

@@ -46,27 +46,37 @@ def rule_exe(tmp_path_factory):
     return exe
 
 
-@pytest.fixture(scope="module")
-def counts(rule_exe):
-    """{"fits": k, "over": k + 1}: the sphere counts either side of the threshold, from the rule"""
-    text = "".join("%r %r %r %r\n" % _extra_sphere(k) for k in range(GROW_MAX))
-    r = subprocess.run([rule_exe, "--grow", scene_path("Scene1")], input=text, capture_output=True, text=True)
+def threshold_counts(exe, first=()):
+    """{"fits": k, "over": k + 1, "bytes": {k: LDS bytes}}: the counts of extra spheres either side of the threshold, from the rule,
+    for Scene1 plus the spheres `first` (x, y, z, radius) plus the first k of the grid"""
+    text = "".join("%r %r %r %r\n" % tuple(s) for s in list(first) + [_extra_sphere(k) for k in range(GROW_MAX)])
+    r = subprocess.run([exe, "--grow", scene_path("Scene1")], input=text, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-400:] + r.stderr[-2000:]
     rows = [tuple(int(v) for v in line.split()) for line in r.stdout.splitlines()]
-    assert [k for k, _, _ in rows] == list(range(GROW_MAX + 1))
+    assert [k for k, _, _ in rows] == list(range(len(first) + GROW_MAX + 1))
     assert rows[0][2] == 1, "plain Scene1 must pass the rule"
+    rows = [(k - len(first), b, six) for k, b, six in rows[len(first):]]  # (k counts the grid's spheres)
     over = next(k for k, _, six in rows if not six)
+    assert over >= 1, "the spheres ahead of the grid must leave the scene under the threshold"
     ring = 4 * 64 * 2 * 16  # (what the ring kernels' workgroups hold on top: whether an image lives in LDS is judged with it)
     print("six-wave threshold: %d spheres -> %d bytes (fits), %d -> %d bytes (over)" % (over - 1, rows[over - 1][1], over, rows[over][1]))
     assert rows[over - 1][2] == 1 and rows[over][1] > 26880 >= rows[over - 1][1]
     assert rows[over][1] + ring <= 64 * 1024, "the image must still live in LDS"
     # (Scene1's image is 5.2 KB; a small sphere costs four rows of 16 bytes and a quarter of a cluster bound: about 60 cross 8448 bytes)
-    assert 40 <= over <= 80, over
-    return {"fits": over - 1, "over": over}
+    assert 40 - 2 * len(first) <= over <= 80, over
+    return {"fits": over - 1, "over": over, "bytes": {k: b for k, b, _ in rows}}
 
 
-def _objects(oracle, n_extra):
+@pytest.fixture(scope="module")
+def counts(rule_exe):
+    """{"fits": k, "over": k + 1}: the sphere counts either side of the threshold, from the rule"""
+    return threshold_counts(rule_exe)
+
+
+def _objects(oracle, n_extra, first=()):
+    """Scene1, the objects `first`, and n_extra spheres of the grid"""
     objs = oracle.load_scene_json_py(scene_path("Scene1"))
+    objs.extend(first)
     for k in range(n_extra):
         x, y, z, r = _extra_sphere(k)
         objs.append(dict(type=oracle.OBJ_SPHERE, position=(x, y, z), radius=r, base=(.2 + .05 * (k % 13), .8, .3), specular_amount=0.25 * (k % 3),
