@@ -1006,6 +1006,84 @@ int srt_bind_visibility(srt_context* ctx, uint32_t output, void* d_float);
 int srt_read_visibility(srt_context* ctx, uint32_t output, float* dst);
 int srt_get_visibility_work(srt_context* ctx, srt_visibility_work* out);
 
+/* ---- radiance queries: path-traced radiance of caller-supplied rays (ABI 7, backward compatible) ------------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of
+ * them runs what it ran before.
+ *
+ * srt_trace_rays says what a ray hits, srt_trace_occlusion whether a segment is blocked, srt_render_visibility how open the
+ * hemisphere at a first hit is.  srt_trace_radiance says how much light arrives along a ray: srt_render's shading loop
+ * (RaytraceScene's path branch, Raytracer.cpp:162-185) and its running mean, without the camera, the pixel grid and the
+ * framebuffer — for irradiance and reflection probes, light-map texels, the secondary rays of a hybrid renderer.
+ *
+ * Rules.
+ * 1. Rays.  The current rays of srt_write_rays / srt_bind_rays.  origin.w and direction.w are ignored: there is no t_max.
+ *    The input domain is that of srt_trace_rays: finite origins with unit-length directions are pinned bit for bit
+ *    (SRT_RADIANCE_NORMALIZE provides unit length: float3::Normalized first, as SRT_RAYS_NORMALIZE); in analytic scenes other
+ *    finite non-zero directions are pinned as well; anything else gives some float4 per ray and does not fault.
+ * 2. Sample.  For f = first_sample .. first_sample + sample_count - 1 and ray i: key = srt_rng_key(seed, id_base + i, f) (the id
+ *    wraps modulo 2^32), draws counted from 0, and colour_f = RaytraceScene(o_i, d_i), the path branch of Raytracer.cpp:141-146,
+ *    162-185, 212, in binary32 without contraction — the arithmetic of srt_render's kernel.  Draw order: draw 0 is the specular
+ *    lottery at the first hit (:165); then, per bounce, three draws for the hemisphere direction (x, y, z; :90-105) and, when the
+ *    bounce ray hits, one lottery at that hit (:182).  The dissipation is 0.8 from the second bounce on (:169-171), a bounce ray
+ *    starts at point + normal * .00001f (:177), a ray that leaves the scene adds GetEnvironmentColor times the throughput and ends
+ *    the path (:178-181), a primary miss gives GetEnvironmentColor(d_i) (:143-145), and max_bounces = 0 gives the first hit's
+ *    emissive colour.  The colour has four lanes: the fourth is +0, or NaN exactly when the lerp parameter of an environment
+ *    lookup of the path is NaN (a non-finite direction), as in srt_render.
+ * 3. Mean.  out_i = SetScreenPixel's running mean (:63-71) over f in ascending order: with weight = (float)(1.0 / f),
+ *    out = clamp0(out * (1 - weight)) + colour_f * weight per lane.  With SRT_RADIANCE_RESET sample first_sample overwrites the
+ *    element (setFrame, :69-71); without it the mean continues from what the element holds, so a call with samples 1..3 and RESET
+ *    followed by one with samples 4..9 without gives the bits of one call with samples 1..9.  The fold order per ray is fixed:
+ *    repeated calls give the same bits however the kernel packs its work.
+ * 4. Equivalence.  For the rays (camera.position, GetRayDirection(camera, x, y)) in the order i = x + y*W (scene rows), with
+ *    id_base = 0 and equal seed, samples and bounces, out_i equals in all four lanes (NaN as NaN) the accumulator element srt_render
+ *    writes for that pixel — the scene in LDS or in memory, with or without meshes.
+ * 5. Splitting.  Tracing rays [a, b) as a batch of their own with id_base raised by a gives the bits of the whole batch.
+ * 6. Output.  N float4, the handle's own buffer (allocated on first use, grown when a batch needs more) or the caller's:
+ *    srt_bind_radiance binds a DEVICE buffer of at least N float4, NULL = own, under srt_bind_ray_output's rules (does not wait,
+ *    enqueued work keeps its buffer).  srt_read_radiance waits, then copies the N float4 the last srt_trace_radiance wrote, from
+ *    the buffer it wrote; SRT_ERR_STATE before the first trace.
+ * 7. Asynchrony.  Asynchronous on the launch stream behind earlier work; srt_wait / srt_poll cover it.  The scene and the
+ *    environment are those captured at enqueue (set, updated, refitted or kept); the rays and the output buffer are those current
+ *    at enqueue.
+ * 8. What it leaves alone.  Everything srt_trace_rays leaves alone, and the ray outputs and their "last trace" record as well:
+ *    srt_read_ray_output behaves as before the call.
+ * 9. Errors, all found before anything is touched: SRT_ERR_STATE before srt_set_scene; SRT_ERR_INVALID_ARG for unknown flags,
+ *    first_sample == 0, sample_count outside 1..4096, first_sample + sample_count - 1 > 2^32 - 1 or a negative max_bounces;
+ *    SRT_ERR_STATE when no rays have been written or bound.
+ * 10. Work counts.  With SRT_RADIANCE_COUNT_WORK the launch counts, deterministically: its rays, its samples (N * n), the
+ *    lane-level GetClosestObject calls by srt_stats.rays' rule (the primary call counts once PER SAMPLE, although the kernel
+ *    traces it once per ray), and the wave-level closest-hit invocations it executed, primaries included — a wave traces the
+ *    primary rays of 64 consecutive rays in one invocation and packs their samples' bounce rays, 64 to an invocation, whichever
+ *    ray they belong to.  The counts are summed per wave and added with one vector atomic per wave into a handle-owned record;
+ *    without the flag there are no atomics at all.  srt_get_radiance_work waits and copies the record of the last
+ *    srt_trace_radiance; SRT_ERR_STATE unless that trace had SRT_RADIANCE_COUNT_WORK (or when there has been none). */
+#define SRT_RADIANCE_RESET 1u      /* sample first_sample overwrites the output element; without it the running mean continues */
+#define SRT_RADIANCE_NORMALIZE 2u  /* as SRT_RAYS_NORMALIZE */
+#define SRT_RADIANCE_COUNT_WORK 4u /* fill srt_radiance_work for this call */
+
+typedef struct srt_radiance_params { /* 24 bytes */
+    uint32_t first_sample;           /* f0 >= 1 */
+    uint32_t sample_count;           /* n, 1..4096, f0 + n - 1 <= 2^32 - 1 */
+    int32_t max_bounces;             /* MAXBOUNCES, >= 0 */
+    uint32_t seed;
+    uint32_t id_base;                /* ray i draws from the stream of "pixel" id_base + i (mod 2^32) */
+    uint32_t flags;                  /* SRT_RADIANCE_* */
+} srt_radiance_params;
+
+typedef struct srt_radiance_work {
+    uint32_t valid, reserved; /* 1, 0 */
+    uint64_t rays, samples;   /* N; N * n */
+    uint64_t closest_calls;   /* lane-level GetClosestObject calls by srt_stats.rays' rule: the primary counts once PER SAMPLE */
+    uint64_t wave_calls;      /* wave-level closest-hit invocations the launch executed, primaries included */
+} srt_radiance_work;
+
+/* first_sample 1, sample_count 16, max_bounces 8, seed 0, id_base 0, flags SRT_RADIANCE_RESET (pure host, no device needed). */
+int srt_radiance_params_default(srt_radiance_params* out);
+int srt_trace_radiance(srt_context* ctx, const srt_radiance_params* params);
+int srt_bind_radiance(srt_context* ctx, void* d_float4);
+int srt_read_radiance(srt_context* ctx, float* dst_rgba);
+int srt_get_radiance_work(srt_context* ctx, srt_radiance_work* out);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

@@ -30,6 +30,9 @@ VIS_AO, VIS_SUN, VIS_ALL = 1, 2, 3
 VIS_COUNT_WORK = 1
 VIS_MAX_SAMPLES = 4096
 VISIBILITY = {"ao": VIS_AO, "sun": VIS_SUN}
+# radiance queries (srt_trace_radiance): the flags of srt_radiance_params and the sample limit
+RADIANCE_RESET, RADIANCE_NORMALIZE, RADIANCE_COUNT_WORK = 1, 2, 4
+RADIANCE_MAX_SAMPLES = 4096
 # ray output names (PathTracer.ray_output / bind_ray_output) -> (output bit, numpy dtype, per-ray channels)
 RAY_OUTPUTS = dict(GBUFFERS, occluded=(RAYS_OCCLUDED, np.int32, 1))
 DENOISE_ALBEDO, DENOISE_FRAMEBUFFER = 1, 2
@@ -70,6 +73,7 @@ EXPORTS = [
     "srt_trace_params_default", "srt_write_rays", "srt_bind_rays", "srt_bind_ray_output", "srt_trace_rays", "srt_read_ray_output",
     "srt_occlusion_params_default", "srt_trace_occlusion", "srt_get_occlusion_work",
     "srt_visibility_params_default", "srt_render_visibility", "srt_bind_visibility", "srt_read_visibility", "srt_get_visibility_work",
+    "srt_radiance_params_default", "srt_trace_radiance", "srt_bind_radiance", "srt_read_radiance", "srt_get_radiance_work",
 ]
 
 
@@ -212,6 +216,21 @@ class VisibilityWork(C.Structure):
     """srt_visibility_work: what the last counting srt_render_visibility traced."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("segments", C.c_uint64), ("open", C.c_uint64), ("wave_trips", C.c_uint64),
                 ("analytic_tests", C.c_uint64), ("node_visits", C.c_uint64), ("triangle_tests", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class RadianceParams(C.Structure):
+    """srt_radiance_params: the sample range, bounces, seed, the id of ray 0's random stream and RADIANCE_* flags."""
+    _fields_ = [("first_sample", C.c_uint32), ("sample_count", C.c_uint32), ("max_bounces", C.c_int32), ("seed", C.c_uint32),
+                ("id_base", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RadianceWork(C.Structure):
+    """srt_radiance_work: what the last counting srt_trace_radiance traced."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("rays", C.c_uint64), ("samples", C.c_uint64),
+                ("closest_calls", C.c_uint64), ("wave_calls", C.c_uint64)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
@@ -376,6 +395,11 @@ def open_library(path):
     L.srt_bind_visibility.argtypes = [ctx, C.c_uint32, C.c_void_p]
     L.srt_read_visibility.argtypes = [ctx, C.c_uint32, C.POINTER(C.c_float)]
     L.srt_get_visibility_work.argtypes = [ctx, C.POINTER(VisibilityWork)]
+    L.srt_radiance_params_default.argtypes = [C.POINTER(RadianceParams)]
+    L.srt_trace_radiance.argtypes = [ctx, C.POINTER(RadianceParams)]
+    L.srt_bind_radiance.argtypes = [ctx, C.c_void_p]
+    L.srt_read_radiance.argtypes = [ctx, C.POINTER(C.c_float)]
+    L.srt_get_radiance_work.argtypes = [ctx, C.POINTER(RadianceWork)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -837,6 +861,70 @@ class PathTracer:
         """srt_get_visibility_work: the work counts of the last render_visibility(count_work=True) as a dict.  Waits."""
         w = VisibilityWork()
         self._ck(self.L.srt_get_visibility_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    # ---- radiance queries ----------------------------------------------------------------
+    def trace_radiance(self, origins=None, directions=None, samples=None, bounces=None, seed=0, first_sample=1, reset=True, id_base=0,
+                       normalize=False, count_work=False, flags=0):
+        """srt_trace_radiance: the running mean of `samples` path-traced samples (default 16) of `bounces` bounces (default 8) along
+        every ray: what render() leaves in the accumulator for a pixel, for rays of the caller's.  `origins` / `directions`: numpy
+        arrays (N, 4) float32 (written with write_rays) or torch tensors on this tracer's device (bound with bind_rays); both None:
+        the current rays.  Ray i draws from the stream of pixel id_base + i; reset=False continues the mean the output holds;
+        normalize: SRT_RADIANCE_NORMALIZE; count_work: SRT_RADIANCE_COUNT_WORK (radiance_work() then reads the record).
+        Asynchronous, like render(); radiance() reads the result."""
+        if (origins is None) != (directions is None):
+            raise ValueError("trace_radiance: origins and directions go together")
+        if origins is not None:
+            if self._ray_array("trace_radiance(origins)", origins)[0] == "host":
+                self.write_rays(origins, directions)
+            else:
+                self.bind_rays(origins, directions)
+        p = RadianceParams()
+        self._ck(self.L.srt_radiance_params_default(C.byref(p)))
+        if samples is not None:
+            p.sample_count = int(samples)
+        if bounces is not None:
+            p.max_bounces = int(bounces)
+        p.first_sample, p.seed, p.id_base = int(first_sample), int(seed) & 0xFFFFFFFF, int(id_base) & 0xFFFFFFFF
+        p.flags = (int(flags) | (RADIANCE_RESET if reset else 0) | (RADIANCE_NORMALIZE if normalize else 0) |
+                   (RADIANCE_COUNT_WORK if count_work else 0))
+        n = getattr(self, "_ray_count", None)
+        t = getattr(self, "_radiance_bound", None)
+        if n is not None and t is not None and t.shape[0] < n:
+            raise ValueError("trace_radiance: the bound tensor holds %d elements, the batch has %d rays" % (t.shape[0], n))
+        self._ck(self.L.srt_trace_radiance(self._h, C.byref(p)))
+        self._radiance_traced = n
+
+    def bind_radiance(self, tensor):
+        """srt_bind_radiance: write the radiance into a torch tensor (M, 4) float32 on this tracer's device, contiguous, M at least
+        the batch size (checked by trace_radiance); None: the handle's own buffer.  The caller keeps the tensor alive until the
+        traces have finished."""
+        if tensor is not None:
+            import torch
+
+            if not isinstance(tensor, torch.Tensor):
+                raise TypeError("bind_radiance: expected a torch.Tensor, got %s" % type(tensor).__name__)
+            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
+            if m < 1:
+                raise ValueError("bind_radiance: shape %s, want at least one element" % (tuple(tensor.shape),))
+            ptr = self._tensor_ptr("bind_radiance", tensor, np.float32, (m, 4))
+        else:
+            ptr = None
+        self._ck(self.L.srt_bind_radiance(self._h, ptr))
+        self._radiance_bound = tensor
+
+    def radiance(self, count=None):
+        """srt_read_radiance: the result of the last trace_radiance() as an (N, 4) float32 array.  `count`: N, for rays bound by
+        raw pointer on another PathTracer object (default: this one's).  Waits."""
+        n = count if count is not None else getattr(self, "_radiance_traced", None)
+        if n is None:
+            raise SrtError(ERR_STATE, "radiance(): no trace_radiance() yet")
+        return self._read_image(self.L.srt_read_radiance, (n, 4), np.float32)
+
+    def radiance_work(self):
+        """srt_get_radiance_work: the work counts of the last trace_radiance(count_work=True) as a dict.  Waits."""
+        w = RadianceWork()
+        self._ck(self.L.srt_get_radiance_work(self._h, C.byref(w)))
         return w.as_dict()
 
     def ray_output(self, name, count=None):

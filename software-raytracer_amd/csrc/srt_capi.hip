@@ -33,6 +33,8 @@
 #include "srt_occlusion_host.h"
 #include "srt_visibility.hip.h"
 #include "srt_visibility_host.h"
+#include "srt_radiance.hip.h"
+#include "srt_radiance_host.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -364,6 +366,14 @@ struct srt_context {
     srt::OutputSlot vis[srt::VIS_SLOTS];
     srt::VisibilityState visibility;
     DeviceBuffer<unsigned long long> d_visibility_work;
+    // radiance queries (srt_trace_radiance): the own output buffer of N float4 (grown when a batch needs more) with its slot (the
+    // bound buffer only); what the last trace wrote and whether it counted (srt_radiance_host.h); the sample scratch of the
+    // launch's grid (grown when a launch has more workgroups); the record a counting launch adds to (srt::RAD_WORK_N words)
+    DeviceBuffer<float4> d_radiance_own;
+    srt::OutputSlot radiance_out;
+    srt::RadianceState radiance;
+    DeviceBuffer<float4> d_radiance_rows;
+    DeviceBuffer<unsigned long long> d_radiance_work;
 
     char error[512] = "";
 };
@@ -1835,6 +1845,96 @@ int srt_get_visibility_work(srt_context* ctx, srt_visibility_work* out) {
     out->valid = 1, out->reserved = 0;
     out->segments = w[srt::VIS_WORK_SEGMENTS], out->open = w[srt::VIS_WORK_OPEN], out->wave_trips = w[srt::VIS_WORK_TRIPS];
     out->analytic_tests = w[srt::VIS_WORK_ANALYTIC], out->node_visits = w[srt::VIS_WORK_NODES], out->triangle_tests = w[srt::VIS_WORK_TRIANGLES];
+    return SRT_OK;
+}
+
+// ---- radiance queries ----------------------------------------------------------------------------------------------
+static_assert(SRT_RADIANCE_RESET == srt::RADIANCE_FLAG_RESET && SRT_RADIANCE_NORMALIZE == srt::RADIANCE_FLAG_NORMALIZE &&
+              SRT_RADIANCE_COUNT_WORK == srt::RADIANCE_FLAG_COUNT_WORK && SRT_RADIANCE_RESET == SRT_RENDER_RESET &&
+              sizeof(srt_radiance_params) == 24 && sizeof(srt::RadianceCall) == 24 && sizeof(srt_radiance_work) == 40 &&
+              srt::RADIANCE_CHUNK == srt::RAD_CHUNK,
+              "srt_radiance_host.h, srt_radiance.hip.h and srt_pathtrace.h disagree");
+
+int srt_radiance_params_default(srt_radiance_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::RadianceCall c;
+    srt::radiance_call_default(c);
+    out->first_sample = c.first_sample, out->sample_count = c.sample_count, out->max_bounces = c.max_bounces;
+    out->seed = c.seed, out->id_base = c.id_base, out->flags = c.flags;
+    return SRT_OK;
+}
+
+// ... in front of the re-allocation of the own radiance buffer or of the sample scratch: earlier traces may still be using them
+static int radiance_output_released(srt_context* ctx) {
+    if (const int rc = finish_stream(ctx)) return rc;
+    srt::radiance_output_released(ctx->radiance, (void*)ctx->d_radiance_own);
+    return SRT_OK;
+}
+
+int srt_trace_radiance(srt_context* ctx, const srt_radiance_params* t) {
+    if (!ctx || !t) return SRT_ERR_INVALID_ARG;
+    const srt::RadianceCall call{t->first_sample, t->sample_count, t->max_bounces, t->seed, t->id_base, t->flags};
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::radiance_check_trace(ctx->rays, ctx->scene_set, call, &why))
+        return fail(ctx, (int)rs, "srt_trace_radiance: %s (first_sample %u, sample_count %u, max_bounces %d, flags 0x%x)", why, t->first_sample,
+                    t->sample_count, t->max_bounces, t->flags);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = ctx->rays.count();
+    const bool count = (t->flags & SRT_RADIANCE_COUNT_WORK) != 0;
+    float4* dst = nullptr;
+    SRT_WRITE_TARGET_AFTER(ctx, ctx->radiance_out, ctx->d_radiance_own, n * sizeof(float4), dst, radiance_output_released(ctx));
+    srt::KernelParams K;
+    const KernelSetup ks = scene_kernel_params(ctx, 0, ctx->height, K);
+    // (the fields accumulate_sample and the bounce loop read)
+    K.first_sample = t->first_sample, K.sample_count = t->sample_count, K.max_bounces = t->max_bounces, K.seed = t->seed;
+    if (t->flags & SRT_RADIANCE_RESET) K.flags |= SRT_RENDER_RESET;
+    const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::radiance_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    // the grid first: the sample scratch is sized by it
+    const unsigned wgs = srt::radiance_grid(n, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
+    const size_t scratch = srt::radiance_scratch_bytes(wgs, srt::OUT_WG_UNITS);
+    if (ctx->d_radiance_rows.bytes() < scratch) {
+        if (const int rc = finish_stream(ctx)) return rc;
+        SRT_HIP(ctx, ctx->d_radiance_rows.ensure(scratch));
+    }
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_radiance_work, srt::RAD_WORK_N)) return rc;
+    }
+    srt::RadianceIO io{};
+    io.origin = ctx->rays.bound() ? (const float4*)ctx->rays.bound_origin : (const float4*)ctx->d_ray_origin;
+    io.direction = ctx->rays.bound() ? (const float4*)ctx->rays.bound_direction : (const float4*)ctx->d_ray_direction;
+    io.count = (uint32_t)n;
+    io.normalize = (t->flags & SRT_RADIANCE_NORMALIZE) ? 1u : 0u;
+    io.id_base = t->id_base;
+    io.out = dst;
+    io.rows = ctx->d_radiance_rows;
+    io.work = count ? (unsigned long long*)ctx->d_radiance_work : nullptr;
+    if (const int rc = launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
+    srt::radiance_traced(ctx->radiance, n, dst, t->flags);
+    return SRT_OK;
+}
+
+int srt_bind_radiance(srt_context* ctx, void* d_float4) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    return ctx->radiance_out.bind(d_float4), SRT_OK;  // (no synchronisation: enqueued traces keep the buffer they were given, as srt_bind_ray_output)
+}
+
+int srt_read_radiance(srt_context* ctx, float* dst_rgba) {
+    if (!ctx || !dst_rgba) return SRT_ERR_INVALID_ARG;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    const srt::RaysStatus rs = srt::radiance_check_read(ctx->radiance, &src, &bytes);
+    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst_rgba, bytes, "srt_read_radiance: there has been no srt_trace_radiance (or its buffer has been re-allocated)");
+}
+
+int srt_get_radiance_work(srt_context* ctx, srt_radiance_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::radiance_check_work(ctx->radiance) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_radiance_work: the last srt_trace_radiance did not ask for SRT_RADIANCE_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::RAD_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_radiance_work, w, srt::RAD_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0;
+    out->rays = w[srt::RAD_WORK_RAYS], out->samples = w[srt::RAD_WORK_SAMPLES];
+    out->closest_calls = w[srt::RAD_WORK_CLOSEST], out->wave_calls = w[srt::RAD_WORK_WAVE_CALLS];
     return SRT_OK;
 }
 

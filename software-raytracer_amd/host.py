@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .capi import (VIS_AO, VIS_COUNT_WORK, VIS_SUN, VISIBILITY, VisibilityParams, VisibilityWork, OCCLUSION_COUNT_WORK, OCCLUSION_NORMALIZE, OcclusionWork, RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
+from .capi import (RADIANCE_COUNT_WORK, RADIANCE_NORMALIZE, RADIANCE_RESET, RadianceParams, RadianceWork, VIS_AO, VIS_COUNT_WORK, VIS_SUN, VISIBILITY, VisibilityParams, VisibilityWork, OCCLUSION_COUNT_WORK, OCCLUSION_NORMALIZE, OcclusionWork, RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
                    TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -35,6 +35,7 @@ EXPORTS = [
     "srt_host_renderer_trace_rays", "srt_host_renderer_read_ray_output",
     "srt_host_renderer_trace_occlusion", "srt_host_renderer_occlusion_work",
     "srt_host_renderer_render_visibility", "srt_host_renderer_read_visibility", "srt_host_renderer_visibility_work",
+    "srt_host_renderer_trace_radiance", "srt_host_renderer_read_radiance", "srt_host_renderer_radiance_work",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -119,6 +120,9 @@ def load_library():
     L.srt_host_renderer_render_visibility.argtypes = [vp, C.POINTER(VisibilityParams)]
     L.srt_host_renderer_read_visibility.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float)]
     L.srt_host_renderer_visibility_work.argtypes = [vp, C.POINTER(VisibilityWork)]
+    L.srt_host_renderer_trace_radiance.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.POINTER(RadianceParams)]
+    L.srt_host_renderer_read_radiance.argtypes = [vp, C.POINTER(C.c_float)]
+    L.srt_host_renderer_radiance_work.argtypes = [vp, C.POINTER(RadianceWork)]
     L.srt_host_renderer_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
     L.srt_host_renderer_read_denoised.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
@@ -379,6 +383,30 @@ class Renderer:
         """PathTraceRenderer::occlusionWork: the work counts of the last trace_occlusion(count_work=True) as a dict."""
         w = OcclusionWork()
         self._ck(self.L.srt_host_renderer_occlusion_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def trace_radiance(self, origins, directions, samples=16, bounces=8, seed=0, first_sample=1, reset=True, id_base=0, normalize=False,
+                       count_work=False):
+        """PathTraceRenderer::traceRadiance + readRadiance: copy N rays from host arrays (N, 4) float32, trace `samples` path-traced
+        samples of `bounces` bounces along each against the renderer's scene (srt_trace_radiance: ray i draws from the stream of
+        pixel id_base + i, samples first_sample .. first_sample + samples - 1; reset=False continues the running mean the handle's
+        buffer holds) and return the (N, 4) float32 running means.  Waits."""
+        o = np.ascontiguousarray(origins, dtype=np.float32)
+        d = np.ascontiguousarray(directions, dtype=np.float32)
+        if o.ndim != 2 or o.shape[1] != 4 or o.shape != d.shape or o.shape[0] < 1:
+            raise ValueError("trace_radiance: origins %s and directions %s, want two (N, 4) arrays" % (o.shape, d.shape))
+        p = RadianceParams(int(first_sample), int(samples), int(bounces), int(seed) & 0xFFFFFFFF, int(id_base) & 0xFFFFFFFF,
+                           (RADIANCE_RESET if reset else 0) | (RADIANCE_NORMALIZE if normalize else 0) | (RADIANCE_COUNT_WORK if count_work else 0))
+        f = C.POINTER(C.c_float)
+        self._ck(self.L.srt_host_renderer_trace_radiance(self._h, o.ctypes.data_as(f), d.ctypes.data_as(f), o.shape[0], C.byref(p)))
+        out = np.empty((o.shape[0], 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_radiance(self._h, out.ctypes.data_as(f)))
+        return out
+
+    def radiance_work(self):
+        """PathTraceRenderer::radianceWork: the work counts of the last trace_radiance(count_work=True) as a dict."""
+        w = RadianceWork()
+        self._ck(self.L.srt_host_renderer_radiance_work(self._h, C.byref(w)))
         return w.as_dict()
 
     def render_visibility(self, ao_samples=16, radius=float("inf"), sun=True, ao=True, first_sample=1, seed=0, rows=None, count_work=False):

@@ -221,6 +221,12 @@ int srt_host_renderer_trace_occlusion(srt_host_renderer* h, const float* origins
     SRT_HOST_TRY(h, h->r->traceOcclusion(origins, directions, count, flags))
 }
 int srt_host_renderer_occlusion_work(srt_host_renderer* h, srt_occlusion_work* out) { SRT_HOST_TRY(h, *out = h->r->occlusionWork()) }
+// radiance queries against the renderer's scene (srt_write_rays + srt_trace_radiance)
+int srt_host_renderer_trace_radiance(srt_host_renderer* h, const float* origins, const float* directions, size_t count, const srt_radiance_params* p) {
+    SRT_HOST_TRY(h, h->r->traceRadiance(origins, directions, count, *p))
+}
+int srt_host_renderer_read_radiance(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->readRadiance(dst)) }
+int srt_host_renderer_radiance_work(srt_host_renderer* h, srt_radiance_work* out) { SRT_HOST_TRY(h, *out = h->r->radianceWork()) }
 // per-pixel visibility: the guides of the band, then srt_render_visibility (a band of [0, 0) means the renderer's own)
 int srt_host_renderer_render_visibility(srt_host_renderer* h, const srt_visibility_params* p) { SRT_HOST_TRY(h, h->r->renderVisibility(*p)) }
 int srt_host_renderer_read_visibility(srt_host_renderer* h, uint32_t output, float* dst) { SRT_HOST_TRY(h, h->r->readVisibility(output, dst)) }

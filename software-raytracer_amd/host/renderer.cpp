@@ -240,6 +240,19 @@ srt_occlusion_work PathTraceRenderer::occlusionWork() {
     return w;
 }
 
+void PathTraceRenderer::traceRadiance(const float* origins, const float* directions, size_t count, const srt_radiance_params& params) {
+    check(srt_write_rays(ctx_, origins, directions, count), "srt_write_rays");
+    check(srt_trace_radiance(ctx_, &params), "srt_trace_radiance");
+}
+
+void PathTraceRenderer::readRadiance(float* dst_rgba) { check(srt_read_radiance(ctx_, dst_rgba), "srt_read_radiance"); }
+
+srt_radiance_work PathTraceRenderer::radianceWork() {
+    srt_radiance_work w{};
+    check(srt_get_radiance_work(ctx_, &w), "srt_get_radiance_work");
+    return w;
+}
+
 void PathTraceRenderer::renderVisibility(const srt_visibility_params& params) {
     srt_visibility_params v = params;
     if (v.row_begin == 0 && v.row_end == 0) v.row_begin = row_begin_, v.row_end = row_end_;

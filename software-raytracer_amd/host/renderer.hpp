@@ -158,6 +158,13 @@ class PathTraceRenderer {
     // returns the work counts of a trace that had SRT_OCCLUSION_COUNT_WORK.
     void traceOcclusion(const float* origins, const float* directions, size_t count, uint32_t flags = 0);
     srt_occlusion_work occlusionWork();
+    // Radiance queries (srt_write_rays + srt_trace_radiance): the running mean of params.sample_count path-traced samples along
+    // each of `count` caller-supplied rays — what Render leaves in the accumulator for a pixel, without a camera.  Asynchronous
+    // once the rays are copied; readRadiance waits and copies the `count` float4 of the last traceRadiance; radianceWork waits and
+    // returns the work counts of a trace that had SRT_RADIANCE_COUNT_WORK.
+    void traceRadiance(const float* origins, const float* directions, size_t count, const srt_radiance_params& params);
+    void readRadiance(float* dst_rgba);
+    srt_radiance_work radianceWork();
     // Per-pixel visibility (srt_render_visibility): ambient occlusion and sun visibility at the first hit.  renderVisibility first
     // renders the three guides the pass reads (OBJECT, NORMAL_DEPTH, POSITION) for the band with the current scene and camera —
     // the renderer cannot know whether the ones in the handle are stale, as with the denoiser's — and then enqueues the pass;

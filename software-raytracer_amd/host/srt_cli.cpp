@@ -64,7 +64,10 @@ static int write_gbuffers(R& r, const std::string& prefix, int W, int H) {
 // --rays IN.f32 --rays-out OUT.bin: closest-hit queries for the rays of a file (N records of 8 float32: origin xyzw, direction
 // xyz + t_max) against the scene; the five outputs of srt_trace_rays follow each other in OUT.bin in the order of their bits.
 // With --any-hit the rays go through srt_trace_occlusion instead and OUT.bin receives the occluded array (N int32) alone.
-static int trace_ray_file(const Scene& scene, int device, const std::string& in, const std::string& out, bool normalize, bool any_hit) {
+// With --radiance N (radiance_samples > 0) they go through srt_trace_radiance — samples 1..N, `bounces`, `seed`, id_base 0 — and
+// OUT.bin receives the N float4 running means alone.
+static int trace_ray_file(const Scene& scene, int device, const std::string& in, const std::string& out, bool normalize, bool any_hit,
+                          int radiance_samples, int bounces, unsigned seed) {
     FILE* f = std::fopen(in.c_str(), "rb");
     if (!f) {
         std::perror(in.c_str());
@@ -87,6 +90,28 @@ static int trace_ray_file(const Scene& scene, int device, const std::string& in,
     try {
         PathTraceRenderer r(device, 8, 8);  // (the frame size plays no part in a ray query)
         r.SetScene(scene);
+        if (radiance_samples > 0) {
+            srt_radiance_params rp{};
+            srt_radiance_params_default(&rp);
+            rp.sample_count = (uint32_t)radiance_samples, rp.max_bounces = bounces, rp.seed = seed;
+            if (normalize) rp.flags |= SRT_RADIANCE_NORMALIZE;
+            r.traceRadiance(o.data(), d.data(), n, rp);
+            std::vector<float> rad(4 * n);
+            r.readRadiance(rad.data());
+            FILE* g = std::fopen(out.c_str(), "wb");
+            if (!g) {
+                std::perror(out.c_str());
+                return 1;
+            }
+            bool ok = std::fwrite(rad.data(), sizeof(float), rad.size(), g) == rad.size();
+            ok = (std::fclose(g) == 0) && ok;
+            if (!ok) {
+                std::fprintf(stderr, "%s: write failed\n", out.c_str());
+                return 1;
+            }
+            std::fprintf(stderr, "%zu rays, %d samples of radiance each%s: %s\n", n, radiance_samples, normalize ? " (directions normalized)" : "", out.c_str());
+            return 0;
+        }
         if (any_hit) r.traceOcclusion(o.data(), d.data(), n, normalize ? SRT_OCCLUSION_NORMALIZE : 0u);
         else r.traceRays(o.data(), d.data(), n, SRT_GBUF_ALL | SRT_RAYS_OCCLUDED, normalize ? SRT_RAYS_NORMALIZE : 0u);
         FILE* g = std::fopen(out.c_str(), "wb");
@@ -123,6 +148,7 @@ static void usage() {
                  "                  [--denoise-variance PATH] [--temporal-variance]\n"
                  "                  [--ao N [--ao-radius R]] [--sun-visibility] [--vis-out FILE]\n"
                  "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--any-hit] [--device 0]\n"
+                 "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin --radiance N [--bounces B] [--seed S] [--rays-normalize]\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
                  "             and means the same), --equal-bands: bands of equal height\n"
@@ -161,6 +187,9 @@ static void usage() {
                  "             (N int32); --rays-normalize normalizes every direction first; single device, no other output\n"
                  "  --any-hit: with --rays, ask srt_trace_occlusion (is there a hit with distance < t_max?) instead; --rays-out then receives\n"
                  "             the occluded array (N int32) alone, with the bits the closest-hit query gives it\n"
+                 "  --radiance N: with --rays, ask srt_trace_radiance instead: the running mean of N (1..4096) path-traced samples of\n"
+                 "             --bounces bounces along every ray (samples 1..N, --seed, ray i draws from the stream of pixel i); --rays-out\n"
+                 "             then receives the N float4 alone; not with --any-hit\n"
                  "  --ao N:    after the frame, per-pixel ambient occlusion (srt_render_visibility): the fraction of N (1..4096) hemisphere\n"
                  "             segments of length --ao-radius (default: unbounded) at the first hit that are unoccluded; samples 1..N, --seed\n"
                  "  --sun-visibility: after the frame, per-pixel sun visibility: n . -sunDirection where the sun is seen, else 0\n"
@@ -171,6 +200,8 @@ static void usage() {
 int main(int argc, char** argv) {
     std::string scene_path, out = "frame.ppm", resave, gbuffer, denoise, upsample, denoise_variance, rays_in, rays_out;
     bool rays_normalize = false, rays_any_hit = false;
+    int radiance = 0;
+    bool radiance_given = false;
     std::string vis_out;
     int ao = 0;
     bool ao_given = false, sun_visibility = false;
@@ -226,6 +257,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rays-out")) rays_out = need("--rays-out");
         else if (!std::strcmp(argv[i], "--rays-normalize")) rays_normalize = true;
         else if (!std::strcmp(argv[i], "--any-hit")) rays_any_hit = true;
+        else if (!std::strcmp(argv[i], "--radiance")) radiance = std::atoi(need("--radiance")), radiance_given = true;
         else if (!std::strcmp(argv[i], "--ao")) ao = std::atoi(need("--ao")), ao_given = true;
         else if (!std::strcmp(argv[i], "--ao-radius")) ao_radius = std::strtof(need("--ao-radius"), nullptr);
         else if (!std::strcmp(argv[i], "--sun-visibility")) sun_visibility = true;
@@ -280,6 +312,10 @@ int main(int argc, char** argv) {
     }
     if (rays_in.empty() != rays_out.empty() || ((rays_normalize || rays_any_hit) && rays_in.empty())) {
         std::fprintf(stderr, "--rays, --rays-out, --rays-normalize and --any-hit go together: --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--any-hit]\n");
+        return 2;
+    }
+    if (radiance_given && (rays_in.empty() || rays_any_hit || radiance < 1 || radiance > 4096 || bounces < 0)) {
+        std::fprintf(stderr, "--radiance N (1..4096) needs --rays and --rays-out, a --bounces >= 0, and does not go with --any-hit\n");
         return 2;
     }
     if (!rays_in.empty() && (!devices.empty() || temporal || steps > 1 || aa_given || !gbuffer.empty() || !denoise.empty() || !upsample.empty() ||
@@ -337,7 +373,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--move-object: the scene has no object %zu\n", m.index);
             return 2;
         }
-    if (!rays_in.empty()) return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize, rays_any_hit);
+    if (!rays_in.empty()) return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize, rays_any_hit, radiance_given ? radiance : 0, bounces, seed);
     auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {
         FILE* f = std::fopen(path.c_str(), "wb");
         if (!f) {

@@ -1,0 +1,137 @@
+// radiance_check.cpp — the host-side rules of the radiance queries (software-raytracer_amd/csrc/srt_radiance_host.h) as a
+// stand-alone program: the header's constants and struct layouts, the defaults, srt_trace_radiance's checks in their order — every
+// refusal the header lists — with the ray state untouched by each, the record of the last radiance trace (its own: the ray outputs'
+// "last trace" stays as it was), when srt_read_radiance and srt_get_radiance_work may report, the grid for N = 1, 63, 64, 65 and
+// 2^30, and a sample scratch that depends on the grid alone.  Built with -fsanitize=address,undefined and run on the CPU.
+#include <cstddef>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "srt_pathtrace.h"
+#include "srt_radiance_host.h"
+
+using namespace srt;
+
+static int failures = 0;
+#define CHECK(cond)                                                     \
+    do {                                                                \
+        if (!(cond)) {                                                  \
+            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+            ++failures;                                                 \
+        }                                                               \
+    } while (0)
+
+static bool same(const RaysState& a, const RaysState& b) {
+    bool eq = a.bound_origin == b.bound_origin && a.bound_direction == b.bound_direction && a.bound_count == b.bound_count && a.own_count == b.own_count &&
+              a.last_count == b.last_count && a.last_outputs == b.last_outputs;
+    for (int i = 0; i < RAYS_SLOTS; ++i) eq = eq && a.last_dst[i] == b.last_dst[i];
+    return eq;
+}
+
+static RadianceCall call(uint32_t f0, uint32_t n, int32_t bounces, uint32_t flags) { return RadianceCall{f0, n, bounces, 0u, 0u, flags}; }
+
+int main() {
+    // the header's constants and layouts are the ones the rules use
+    CHECK(SRT_RADIANCE_RESET == RADIANCE_FLAG_RESET && SRT_RADIANCE_NORMALIZE == RADIANCE_FLAG_NORMALIZE && SRT_RADIANCE_COUNT_WORK == RADIANCE_FLAG_COUNT_WORK);
+    CHECK((SRT_RADIANCE_RESET | SRT_RADIANCE_NORMALIZE | SRT_RADIANCE_COUNT_WORK) == RADIANCE_FLAG_ALL && SRT_RADIANCE_RESET == SRT_RENDER_RESET);
+    CHECK(sizeof(srt_radiance_params) == 24 && sizeof(RadianceCall) == 24 && offsetof(srt_radiance_params, first_sample) == 0 &&
+          offsetof(srt_radiance_params, sample_count) == 4 && offsetof(srt_radiance_params, max_bounces) == 8 && offsetof(srt_radiance_params, seed) == 12 &&
+          offsetof(srt_radiance_params, id_base) == 16 && offsetof(srt_radiance_params, flags) == 20);
+    CHECK(offsetof(RadianceCall, first_sample) == 0 && offsetof(RadianceCall, sample_count) == 4 && offsetof(RadianceCall, max_bounces) == 8 &&
+          offsetof(RadianceCall, seed) == 12 && offsetof(RadianceCall, id_base) == 16 && offsetof(RadianceCall, flags) == 20);
+    CHECK(sizeof(srt_radiance_work) == 40 && offsetof(srt_radiance_work, valid) == 0 && offsetof(srt_radiance_work, reserved) == 4 &&
+          offsetof(srt_radiance_work, rays) == 8 && offsetof(srt_radiance_work, samples) == 16 && offsetof(srt_radiance_work, closest_calls) == 24 &&
+          offsetof(srt_radiance_work, wave_calls) == 32);
+    {
+        RadianceCall d = call(9, 9, -9, ~0u);
+        d.seed = 9, d.id_base = 9;
+        radiance_call_default(d);
+        CHECK(d.first_sample == 1 && d.sample_count == 16 && d.max_bounces == 8 && d.seed == 0 && d.id_base == 0 && d.flags == RADIANCE_FLAG_RESET);
+    }
+
+    // the checks: the scene, the arguments, the rays
+    std::vector<float> a(8), b(8);
+    RaysState s;
+    RadianceState r;
+    const char* why = nullptr;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    CHECK(radiance_check_work(r) == RAYS_STATE && radiance_check_read(r, &src, &bytes) == RAYS_STATE);  // no trace yet
+    const RadianceCall ok = call(1, 16, 8, RADIANCE_FLAG_RESET);
+    CHECK(radiance_check_trace(s, false, ok, &why) == RAYS_STATE && std::strstr(why, "srt_set_scene"));
+    CHECK(radiance_check_trace(s, false, call(0, 0, -1, 8), &why) == RAYS_STATE);                                 // the scene comes first
+    CHECK(radiance_check_trace(s, true, call(1, 16, 8, 8), &why) == RAYS_INVALID_ARG && std::strstr(why, "flags"));  // the arguments before the rays
+    CHECK(radiance_check_trace(s, true, ok, &why) == RAYS_STATE && std::strstr(why, "no rays"));
+    CHECK(radiance_check_trace(s, true, ok, nullptr) == RAYS_STATE);  // (a NULL reason is allowed)
+    rays_written(s, 3);
+    {
+        const RaysState before = s;
+        for (uint32_t f = 0; f <= 7; ++f) CHECK(radiance_check_trace(s, true, call(1, 16, 8, f), &why) == RAYS_OK);
+        for (uint32_t f : {8u, 16u, 15u, 0x80000000u, ~0u}) CHECK(radiance_check_trace(s, true, call(1, 16, 8, f), &why) == RAYS_INVALID_ARG && std::strstr(why, "flags"));
+        CHECK(radiance_check_trace(s, true, call(0, 16, 8, 1), &why) == RAYS_INVALID_ARG && std::strstr(why, "first_sample"));
+        for (uint32_t n : {0u, 4097u, 0x80000000u, ~0u}) CHECK(radiance_check_trace(s, true, call(1, n, 8, 1), &why) == RAYS_INVALID_ARG && std::strstr(why, "sample_count"));
+        for (uint32_t n : {1u, 2u, 64u, 65u, 4096u}) CHECK(radiance_check_trace(s, true, call(1, n, 8, 1), &why) == RAYS_OK);
+        // f0 + n - 1 <= 2^32 - 1
+        CHECK(radiance_check_trace(s, true, call(0xFFFFFFFFu, 1, 8, 1), &why) == RAYS_OK);
+        CHECK(radiance_check_trace(s, true, call(0xFFFFFFFFu, 2, 8, 1), &why) == RAYS_INVALID_ARG && std::strstr(why, "2^32"));
+        CHECK(radiance_check_trace(s, true, call(0xFFFFF000u, 4096, 8, 1), &why) == RAYS_OK);
+        CHECK(radiance_check_trace(s, true, call(0xFFFFF001u, 4096, 8, 1), &why) == RAYS_INVALID_ARG && std::strstr(why, "2^32"));
+        for (int32_t bnc : {-1, -8, (int32_t)0x80000000}) CHECK(radiance_check_trace(s, true, call(1, 16, bnc, 1), &why) == RAYS_INVALID_ARG && std::strstr(why, "max_bounces"));
+        for (int32_t bnc : {0, 1, 8, 0x7FFFFFFF}) CHECK(radiance_check_trace(s, true, call(1, 16, bnc, 1), &why) == RAYS_OK);
+        CHECK(same(s, before));
+    }
+    CHECK(rays_bind(s, a.data(), b.data(), (size_t)1 << 30) == RAYS_OK && radiance_check_trace(s, true, ok, &why) == RAYS_OK);
+    CHECK(rays_bind(s, nullptr, nullptr, 0) == RAYS_OK && s.count() == 3);
+
+    // the record of the last radiance trace is its own: the ray outputs' "last trace" stays what srt_trace_rays left
+    int dummy[RAYS_SLOTS], own, other;
+    void* dst[RAYS_SLOTS] = {&dummy[0], &dummy[1], &dummy[2], &dummy[3], &dummy[4]};
+    rays_traced(s, RAYS_OUT_ALL, dst);
+    {
+        const RaysState before = s;
+        radiance_traced(r, s.count(), &own, RADIANCE_FLAG_RESET);
+        CHECK(same(s, before));
+        for (uint32_t bit = 1; bit <= 16; bit <<= 1) CHECK(rays_check_read(s, bit, &src, &bytes) == RAYS_OK);
+    }
+    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_OK && src == &own && bytes == 3 * 16);
+    CHECK(radiance_check_work(r) == RAYS_STATE);  // traced, but not counted
+    // a later bind changes the current rays, not what the last trace wrote; the next trace takes the new count
+    CHECK(rays_bind(s, a.data(), b.data(), 9) == RAYS_OK);
+    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_OK && bytes == 3 * 16);
+    radiance_traced(r, s.count(), &other, RADIANCE_FLAG_COUNT_WORK | RADIANCE_FLAG_NORMALIZE);
+    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_OK && src == &other && bytes == 9 * 16);
+    CHECK(radiance_check_work(r) == RAYS_OK);
+    radiance_traced(r, s.count(), &other, RADIANCE_FLAG_RESET);  // a trace without the flag ends the record
+    CHECK(radiance_check_work(r) == RAYS_STATE);
+    radiance_traced(r, s.count(), &own, RADIANCE_FLAG_COUNT_WORK);
+    CHECK(radiance_check_work(r) == RAYS_OK);
+    // a refused check in between changes neither
+    CHECK(radiance_check_trace(s, true, call(1, 0, 8, 1), &why) == RAYS_INVALID_ARG && radiance_check_work(r) == RAYS_OK &&
+          radiance_check_read(r, &src, &bytes) == RAYS_OK && src == &own);
+    // the own buffer is re-allocated: the result goes with it; another buffer's release does not matter
+    radiance_output_released(r, &other);
+    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_OK);
+    radiance_output_released(r, nullptr);
+    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_OK);
+    radiance_output_released(r, &own);
+    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_STATE);
+
+    // the grid: blocks of 64 rays, four to a workgroup, at most the resident workgroups, never none
+    const long long resident = 1024;
+    CHECK(radiance_grid(1, 4, resident) == 1 && radiance_grid(63, 4, resident) == 1 && radiance_grid(64, 4, resident) == 1 && radiance_grid(65, 4, resident) == 1);
+    CHECK(radiance_grid(256, 4, resident) == 1 && radiance_grid(257, 4, resident) == 2 && radiance_grid(480, 4, resident) == 2);
+    CHECK(radiance_grid((size_t)1 << 30, 4, resident) == 1024 && radiance_grid((size_t)1 << 30, 4, 1) == 1 && radiance_grid(1, 4, 0) == 1);
+    CHECK(radiance_grid((size_t)1 << 30, 4, (long long)1 << 40) == ((size_t)1 << 22));
+    for (size_t n : {(size_t)1, (size_t)63, (size_t)64, (size_t)65, (size_t)1 << 30}) CHECK(radiance_grid(n, 4, resident) == rays_grid(n, 4, resident));
+    // the scratch: a function of the grid alone — every wave's RADIANCE_CHUNK rows of 64 float4 — whatever N and n are
+    CHECK(RADIANCE_CHUNK == 64);
+    CHECK(radiance_scratch_bytes(1, 4) == (size_t)4 * 64 * 64 * 16 && radiance_scratch_bytes(1024, 4) == (size_t)1024 * 4 * 64 * 64 * 16);
+    CHECK(radiance_scratch_bytes(radiance_grid((size_t)1 << 20, 4, resident), 4) == radiance_scratch_bytes(radiance_grid((size_t)1 << 30, 4, resident), 4));
+    CHECK(radiance_scratch_bytes(radiance_grid((size_t)1 << 30, 4, resident), 4) == (size_t)256 << 20);  // 256 MiB at 1024 resident workgroups, not N * n * 16
+    CHECK(radiance_scratch_bytes(radiance_grid(1, 4, resident), 4) == radiance_scratch_bytes(radiance_grid(256, 4, resident), 4));
+
+    if (failures) return 1;
+    std::printf("ok radiance host rules\n");
+    return 0;
+}
