@@ -1084,6 +1084,130 @@ int srt_bind_radiance(srt_context* ctx, void* d_float4);
 int srt_read_radiance(srt_context* ctx, float* dst_rgba);
 int srt_get_radiance_work(srt_context* ctx, srt_radiance_work* out);
 
+/* ---- adaptive sampling: per-pixel sample counts and a variance budget (ABI 7, backward compatible) -----------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of
+ * them runs what it ran before, bit for bit.
+ *
+ * srt_render gives every pixel of a band the same number of samples.  srt_variance and srt_temporal_variance say which pixels
+ * are still noisy; srt_sample_budget turns that variance into a per-pixel number of further samples and srt_render_adaptive
+ * traces exactly those, continuing every pixel's running mean where it stands.
+ *
+ * Two per-pixel buffers, both W*H uint32 indexed x + y*W with the scene row y, like the accumulator; both the handle's own
+ * (allocated on first use) or the caller's DEVICE buffer (srt_bind_*; NULL = own; does not wait, enqueued work keeps the buffer
+ * it was given):
+ *   sample counts  n_p: how many samples the accumulator element of pixel p holds;
+ *   sample budget  b_p: how many more samples the next adaptive render may add to it.
+ * srt_set_sample_counts fills the current counts buffer with one value, asynchronously on the launch stream: how a caller says
+ * "I have just run srt_render with n samples".  srt_write_* wait like srt_write_accumulator, then copy W*H uint32 from the host;
+ * srt_read_* wait, then copy to the host, and give SRT_ERR_STATE while the buffer has never been written, filled or bound.
+ *
+ * srt_render_adaptive.  Rules.
+ * 1. Effective budget.  For every pixel p = (x, y) of the band (scene coordinates, id = x + y*W):
+ *    e_p = min(b_p, max_samples, 2147483646 - n_p), and e_p = 0 when n_p >= 2147483646.  srt_render accepts frames up to
+ *    2^31 - 2; this call never goes past them.
+ * 2. Samples.  For f = n_p + 1 .. n_p + e_p: colour_f = RaytraceScene of the pixel's camera ray (GetRayDirection, no jitter), the
+ *    path branch, drawn from srt_rng_key(seed, id, f) in srt_render's draw order, folded in ascending f with weight
+ *    (float)(1.0 / f) into the accumulator element (SetScreenPixel's running mean).  When n_p = 0 sample 1 overwrites the
+ *    element (setFrame); otherwise the mean continues from what the element holds.  There is no preview and there are no
+ *    progressive blocks.
+ * 3. Equivalence.  After any sequence of adaptive calls with one seed and bounce count that started from n_p = 0, pixel p's
+ *    accumulator element equals the element srt_render writes with first_sample = 1, sample_count = n_p, SRT_RENDER_RESET, the
+ *    same seed and bounces: in all four lanes (NaN as NaN), and the framebuffer pixel (tone_map, memory row H - 1 - y) is equal
+ *    too — the scene in LDS or in memory, with or without meshes.  It also holds from a start of srt_render(1..n) followed by
+ *    srt_set_sample_counts(n).
+ * 4. Untouched pixels.  A pixel with e_p = 0 is not written: not its accumulator element, its framebuffer pixel or its count;
+ *    no ray is traced for it.  A tile of 8 x 8 pixels that all have e_p = 0 costs the loads of its budgets and counts.
+ * 5. Counts.  Without SRT_ADAPTIVE_KEEP_COUNTS, n_p += e_p.  With the flag the counts buffer is only read: for callers that keep
+ *    several estimates of the same frame with equal counts (the two halves of srt_variance advanced in turn through
+ *    srt_bind_output, the first call with the flag).  The budget buffer is never written.
+ * 6. Determinism.  No atomic reaches accumulator, framebuffer or counts and the fold order per pixel is fixed: repeated calls
+ *    from the same state give the same bits, whatever order the tiles run in.
+ * 7. Asynchrony and captured state.  Asynchronous on the launch stream behind earlier work; srt_wait / srt_poll cover it.
+ *    Scene, environment and camera are captured at enqueue; accumulator and framebuffer are those current at enqueue
+ *    (srt_bind_output), the counts and budget buffers likewise.
+ * 8. What it leaves alone.  srt_get_stats, srt_get_work_counts, the launch shape and dispatch order of later renders, the
+ *    G-buffer, every pass buffer, the temporal history, the ray and radiance outputs.
+ * 9. Errors, all found before anything is touched: SRT_ERR_STATE before srt_set_scene and srt_set_camera; SRT_ERR_INVALID_ARG
+ *    for an empty or out-of-range band, unknown flags, reserved != 0, max_samples outside 1..4096 or a negative max_bounces;
+ *    SRT_ERR_STATE when counts or budget have never been written, filled or bound.
+ * 10. Work counts.  With SRT_ADAPTIVE_COUNT_WORK the launch counts, deterministically: its pixels (those with e_p > 0), its
+ *    samples (the sum of e_p), the lane-level GetClosestObject calls by srt_stats.rays' rule (the primary counts once PER
+ *    SAMPLE, although the kernel traces it once per pixel) and the wave-level closest-hit invocations it executed, primaries
+ *    included: a wave traces a tile's primaries in one invocation and packs the bounce rays of its pixels' samples, 64 to an
+ *    invocation.  Summed per wave and added with one vector atomic per wave into a handle-owned record; srt_get_adaptive_work
+ *    waits and copies it, SRT_ERR_STATE unless the last srt_render_adaptive counted.
+ *
+ * srt_sample_budget.  Inputs: v = the current variance buffer, n = the counts, c = the accumulator's rgb, o = SRT_GBUF_OBJECT
+ * and, with SRT_BUDGET_ALBEDO, a = SRT_GBUF_ALBEDO; all bound or own, the pass renders no guide.  Binary32 without FMA, in
+ * this order:
+ *   1. o_p = -1 or n_p = 0: b_p = 0.  A primary miss is exactly converged after one sample; a pixel without samples has no
+ *      variance: seed the frame with a uniform render.
+ *   2. g_p = the 3 x 3 prefiltered variance of srt_denoise_variance rule A at level 0 (the same device function): a two-half
+ *      variance is far too noisy to use raw.
+ *   3. m_p and l_p = lum(c_p / m_p) as srt_variance rules 2-3 (no division without the flag); t = threshold * (l_p + floor);
+ *      T = t * t.
+ *   4. if !(g_p > T): b_p = 0.  Otherwise r = g_p / T (IEEE division), e = (float)n_p * r - (float)n_p, and b_p = max_budget
+ *      when !(e < (float)max_budget), else max(1, (uint32)ceilf(e)).  The variance of a mean falls as 1/n: n_p * r is the count at
+ *      which g_p would reach T.
+ *   5. output: the current budget buffer.  The sum of all b_p goes to a handle-owned uint64 (one integer vector atomic per
+ *      wave, zeroed before the launch); srt_get_budget_total waits and returns it: what the next adaptive render will cost.
+ *      SRT_ERR_STATE before the first srt_sample_budget.
+ *   6. whole frame, one launch; asynchronous; it leaves alone what srt_variance leaves alone, and the variance, the counts and
+ *      the accumulator as well.
+ *   7. SRT_ERR_INVALID_ARG for a NaN or non-positive threshold (+inf is allowed), a NaN or negative floor, max_budget outside
+ *      1..4096 or unknown flags; SRT_ERR_STATE for a missing guide, variance or counts buffer, and when the variance buffer is
+ *      the handle's own and the pass that wrote it disagrees with this call on the ALBEDO flag.
+ * n_p and b_p are in the unit of the counts buffer.  In the two-half workflow v is the variance of the mean of the halves, n
+ * the per-half count and b the per-half extra:
+ *     srt_render(RESET, seed sA, n) -> half A; srt_bind_output(ctx, NULL, half); srt_render(RESET, seed sB, n) -> half B
+ *     srt_set_sample_counts(n); srt_render_gbuffer (once)
+ *     per round: srt_bind_output(ctx, NULL, NULL); srt_variance(no MERGE); srt_sample_budget;
+ *                srt_render_adaptive(seed sA, KEEP_COUNTS); srt_bind_output(ctx, NULL, half); srt_render_adaptive(seed sB)
+ *     after the last round: srt_bind_output(ctx, NULL, NULL); srt_variance(MERGE)
+ * A and B are seeded differently throughout. */
+#define SRT_ADAPTIVE_KEEP_COUNTS 1u /* do not write the counts back */
+#define SRT_ADAPTIVE_COUNT_WORK 2u  /* fill srt_adaptive_work for this call */
+#define SRT_BUDGET_ALBEDO 1u        /* the luminance of the demodulated colour: must agree with the variance buffer */
+
+typedef struct srt_adaptive_params { /* 28 bytes */
+    int32_t row_begin, row_end;      /* memory rows, as srt_render_params */
+    int32_t max_bounces;             /* MAXBOUNCES, >= 0 */
+    uint32_t seed;
+    uint32_t max_samples;            /* 1..4096: cap on what one call adds to a pixel */
+    uint32_t flags;                  /* SRT_ADAPTIVE_* */
+    uint32_t reserved;               /* 0 */
+} srt_adaptive_params;
+
+typedef struct srt_adaptive_work {
+    uint32_t valid, reserved;  /* 1, 0 */
+    uint64_t pixels, samples;  /* pixels with e_p > 0; the sum of e_p */
+    uint64_t closest_calls;    /* lane-level GetClosestObject calls by srt_stats.rays' rule: the primary counts once PER SAMPLE */
+    uint64_t wave_calls;       /* wave-level closest-hit invocations the launch executed, primaries included */
+} srt_adaptive_work;
+
+typedef struct srt_budget_params { /* 16 bytes */
+    float threshold;               /* tau > 0 (+inf allowed): target relative standard error */
+    float floor;                   /* >= 0: added to the luminance so that dark pixels do not ask for everything */
+    uint32_t max_budget;           /* 1..4096 */
+    uint32_t flags;                /* 0 or SRT_BUDGET_ALBEDO */
+} srt_budget_params;
+
+int srt_set_sample_counts(srt_context* ctx, uint32_t value);
+int srt_write_sample_counts(srt_context* ctx, const uint32_t* src);
+int srt_read_sample_counts(srt_context* ctx, uint32_t* dst);
+int srt_bind_sample_counts(srt_context* ctx, void* d_u32);
+int srt_write_sample_budget(srt_context* ctx, const uint32_t* src);
+int srt_read_sample_budget(srt_context* ctx, uint32_t* dst);
+int srt_bind_sample_budget(srt_context* ctx, void* d_u32);
+/* max_bounces 8, seed 0, max_samples 4096, flags 0; the band is left to the caller (0, 0).  Pure host, no device needed. */
+int srt_adaptive_params_default(srt_adaptive_params* out);
+int srt_render_adaptive(srt_context* ctx, const srt_adaptive_params* params);
+int srt_get_adaptive_work(srt_context* ctx, srt_adaptive_work* out);
+/* threshold 0.05, floor 0.01, max_budget 64, flags SRT_BUDGET_ALBEDO: picks, not swept.  Pure host, no device needed. */
+int srt_budget_params_default(srt_budget_params* out);
+int srt_sample_budget(srt_context* ctx, const srt_budget_params* params);
+int srt_get_budget_total(srt_context* ctx, uint64_t* total);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

@@ -44,6 +44,9 @@ from .capi import (  # noqa: F401
     VisibilityWork,
     RadianceParams,
     RadianceWork,
+    AdaptiveParams,
+    AdaptiveWork,
+    BudgetParams,
     UpsampleParams,
     VarianceParams,
     build_native,
@@ -56,6 +59,6 @@ from . import host  # noqa: F401
 
 __all__ = [
     "capi", "host", "PathTracer", "SrtError", "Object", "Material", "Camera", "Environment",
-    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "SubsampleParams", "AntialiasParams", "VarianceParams", "DenoiseVarianceParams", "TemporalVarianceParams", "TraceParams", "OcclusionParams", "OcclusionWork", "VisibilityParams", "VisibilityWork", "RadianceParams", "RadianceWork", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
+    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "SubsampleParams", "AntialiasParams", "VarianceParams", "DenoiseVarianceParams", "TemporalVarianceParams", "TraceParams", "OcclusionParams", "OcclusionWork", "VisibilityParams", "VisibilityWork", "RadianceParams", "RadianceWork", "AdaptiveParams", "AdaptiveWork", "BudgetParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
     "load_library",
 ]

@@ -33,6 +33,12 @@ VISIBILITY = {"ao": VIS_AO, "sun": VIS_SUN}
 # radiance queries (srt_trace_radiance): the flags of srt_radiance_params and the sample limit
 RADIANCE_RESET, RADIANCE_NORMALIZE, RADIANCE_COUNT_WORK = 1, 2, 4
 RADIANCE_MAX_SAMPLES = 4096
+# adaptive sampling (srt_render_adaptive, srt_sample_budget): the flags, the limits of max_samples / max_budget, the last frame
+ADAPTIVE_KEEP_COUNTS, ADAPTIVE_COUNT_WORK = 1, 2
+ADAPTIVE_MAX_SAMPLES = 4096
+ADAPTIVE_FRAME_LIMIT = 2147483646
+BUDGET_ALBEDO = 1
+BUDGET_MAX = 4096
 # ray output names (PathTracer.ray_output / bind_ray_output) -> (output bit, numpy dtype, per-ray channels)
 RAY_OUTPUTS = dict(GBUFFERS, occluded=(RAYS_OCCLUDED, np.int32, 1))
 DENOISE_ALBEDO, DENOISE_FRAMEBUFFER = 1, 2
@@ -74,6 +80,10 @@ EXPORTS = [
     "srt_occlusion_params_default", "srt_trace_occlusion", "srt_get_occlusion_work",
     "srt_visibility_params_default", "srt_render_visibility", "srt_bind_visibility", "srt_read_visibility", "srt_get_visibility_work",
     "srt_radiance_params_default", "srt_trace_radiance", "srt_bind_radiance", "srt_read_radiance", "srt_get_radiance_work",
+    "srt_set_sample_counts", "srt_write_sample_counts", "srt_read_sample_counts", "srt_bind_sample_counts",
+    "srt_write_sample_budget", "srt_read_sample_budget", "srt_bind_sample_budget",
+    "srt_adaptive_params_default", "srt_render_adaptive", "srt_get_adaptive_work",
+    "srt_budget_params_default", "srt_sample_budget", "srt_get_budget_total",
 ]
 
 
@@ -234,6 +244,26 @@ class RadianceWork(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class AdaptiveParams(C.Structure):
+    """srt_adaptive_params: the band, bounces, seed, the cap on what one call adds to a pixel and ADAPTIVE_* flags."""
+    _fields_ = [("row_begin", C.c_int32), ("row_end", C.c_int32), ("max_bounces", C.c_int32), ("seed", C.c_uint32),
+                ("max_samples", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AdaptiveWork(C.Structure):
+    """srt_adaptive_work: what the last counting srt_render_adaptive traced."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_uint64), ("samples", C.c_uint64),
+                ("closest_calls", C.c_uint64), ("wave_calls", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class BudgetParams(C.Structure):
+    """srt_budget_params: the target relative standard error, the luminance floor, the largest budget and BUDGET_* flags."""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("max_budget", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class UpdateInfo(C.Structure):
@@ -400,6 +430,19 @@ def open_library(path):
     L.srt_bind_radiance.argtypes = [ctx, C.c_void_p]
     L.srt_read_radiance.argtypes = [ctx, C.POINTER(C.c_float)]
     L.srt_get_radiance_work.argtypes = [ctx, C.POINTER(RadianceWork)]
+    L.srt_set_sample_counts.argtypes = [ctx, C.c_uint32]
+    L.srt_write_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
+    L.srt_read_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
+    L.srt_bind_sample_counts.argtypes = [ctx, C.c_void_p]
+    L.srt_write_sample_budget.argtypes = [ctx, C.POINTER(C.c_uint32)]
+    L.srt_read_sample_budget.argtypes = [ctx, C.POINTER(C.c_uint32)]
+    L.srt_bind_sample_budget.argtypes = [ctx, C.c_void_p]
+    L.srt_adaptive_params_default.argtypes = [C.POINTER(AdaptiveParams)]
+    L.srt_render_adaptive.argtypes = [ctx, C.POINTER(AdaptiveParams)]
+    L.srt_get_adaptive_work.argtypes = [ctx, C.POINTER(AdaptiveWork)]
+    L.srt_budget_params_default.argtypes = [C.POINTER(BudgetParams)]
+    L.srt_sample_budget.argtypes = [ctx, C.POINTER(BudgetParams)]
+    L.srt_get_budget_total.argtypes = [ctx, C.POINTER(C.c_uint64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -925,6 +968,95 @@ class PathTracer:
         """srt_get_radiance_work: the work counts of the last trace_radiance(count_work=True) as a dict.  Waits."""
         w = RadianceWork()
         self._ck(self.L.srt_get_radiance_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    # ---- adaptive sampling -----------------------------------------------------------------
+    def _u32_frame(self, what, arr):
+        a = np.ascontiguousarray(arr, dtype=np.uint32)
+        if a.shape != (self.height, self.width):
+            raise ValueError("%s: shape %s, want %s" % (what, a.shape, (self.height, self.width)))
+        return a
+
+    def _u32_tensor_ptr(self, what, tensor):
+        """_tensor_ptr for a per-pixel uint32 buffer: an (H, W) torch.int32 tensor (the same 32 bits)."""
+        return self._tensor_ptr(what, tensor, np.int32, (self.height, self.width))
+
+    def set_sample_counts(self, value):
+        """srt_set_sample_counts: every pixel's sample count = value ("I have just rendered `value` samples").  Asynchronous."""
+        self._ck(self.L.srt_set_sample_counts(self._h, int(value)))
+
+    def write_sample_counts(self, arr):
+        """srt_write_sample_counts: the counts from an (H, W) array of uint32, rows = scene rows.  Waits."""
+        a = self._u32_frame("write_sample_counts", arr)
+        self._ck(self.L.srt_write_sample_counts(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+    def sample_counts(self):
+        """srt_read_sample_counts: (H, W) uint32, rows = scene rows (the orientation of accumulator()).  Waits."""
+        return self._read_image(self.L.srt_read_sample_counts, (self.height, self.width), np.uint32)
+
+    def bind_sample_counts(self, tensor):
+        """srt_bind_sample_counts: keep the counts in a torch tensor on this tracer's device, (H, W) int32 (read as uint32) and
+        contiguous (None: the handle's own buffer).  Checked here, before any native call, as bind_denoised checks."""
+        self._ck(self.L.srt_bind_sample_counts(self._h, self._u32_tensor_ptr("bind_sample_counts", tensor)))
+
+    def write_sample_budget(self, arr):
+        """srt_write_sample_budget: the budget from an (H, W) array of uint32, rows = scene rows.  Waits."""
+        a = self._u32_frame("write_sample_budget", arr)
+        self._ck(self.L.srt_write_sample_budget(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+    def sample_budget_map(self):
+        """srt_read_sample_budget: (H, W) uint32, rows = scene rows.  Waits."""
+        return self._read_image(self.L.srt_read_sample_budget, (self.height, self.width), np.uint32)
+
+    def bind_sample_budget(self, tensor):
+        """srt_bind_sample_budget: keep the budget in a torch tensor on this tracer's device, (H, W) int32 (read as uint32) and
+        contiguous (None: the handle's own buffer).  Checked here, before any native call."""
+        self._ck(self.L.srt_bind_sample_budget(self._h, self._u32_tensor_ptr("bind_sample_budget", tensor)))
+
+    def sample_budget(self, threshold=None, floor=None, max_budget=None, albedo=None, flags=None):
+        """srt_sample_budget over the whole frame: the variance buffer, the counts, the accumulator and the OBJECT (and ALBEDO)
+        guides as they stand -> the budget buffer.  Arguments left at None take srt_budget_params_default.  Asynchronous;
+        budget_total() reads the sum, sample_budget_map() the map."""
+        p = BudgetParams()
+        self._ck(self.L.srt_budget_params_default(C.byref(p)))
+        if threshold is not None:
+            p.threshold = float(threshold)
+        if floor is not None:
+            p.floor = float(floor)
+        if max_budget is not None:
+            p.max_budget = int(max_budget)
+        if albedo is not None:
+            p.flags = (p.flags & ~BUDGET_ALBEDO) | (BUDGET_ALBEDO if albedo else 0)
+        if flags is not None:
+            p.flags = int(flags)
+        self._ck(self.L.srt_sample_budget(self._h, C.byref(p)))
+
+    def budget_total(self):
+        """srt_get_budget_total: the sum of the budget the last sample_budget() wrote.  Waits."""
+        t = C.c_uint64(0)
+        self._ck(self.L.srt_get_budget_total(self._h, C.byref(t)))
+        return int(t.value)
+
+    def render_adaptive(self, bounces=None, seed=0, max_samples=None, rows=None, keep_counts=False, count_work=False, flags=0, reserved=0):
+        """srt_render_adaptive: every pixel of memory rows `rows` (default: the whole frame) takes min(budget, max_samples) more
+        samples, continuing its running mean from its count; the counts advance unless keep_counts.  Arguments left at None take
+        srt_adaptive_params_default.  Asynchronous, like render()."""
+        p = AdaptiveParams()
+        self._ck(self.L.srt_adaptive_params_default(C.byref(p)))
+        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
+        if bounces is not None:
+            p.max_bounces = int(bounces)
+        if max_samples is not None:
+            p.max_samples = int(max_samples)
+        p.seed = int(seed) & 0xFFFFFFFF
+        p.flags = int(flags) | (ADAPTIVE_KEEP_COUNTS if keep_counts else 0) | (ADAPTIVE_COUNT_WORK if count_work else 0)
+        p.reserved = int(reserved)
+        self._ck(self.L.srt_render_adaptive(self._h, C.byref(p)))
+
+    def adaptive_work(self):
+        """srt_get_adaptive_work: the work counts of the last render_adaptive(count_work=True) as a dict.  Waits."""
+        w = AdaptiveWork()
+        self._ck(self.L.srt_get_adaptive_work(self._h, C.byref(w)))
         return w.as_dict()
 
     def ray_output(self, name, count=None):

@@ -35,6 +35,8 @@
 #include "srt_visibility_host.h"
 #include "srt_radiance.hip.h"
 #include "srt_radiance_host.h"
+#include "srt_adaptive.hip.h"
+#include "srt_adaptive_host.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -374,6 +376,18 @@ struct srt_context {
     srt::RadianceState radiance;
     DeviceBuffer<float4> d_radiance_rows;
     DeviceBuffer<unsigned long long> d_radiance_work;
+    // adaptive sampling (srt_render_adaptive, srt_sample_budget): the per-pixel sample counts and sample budget, W*H uint32 each,
+    // own buffer and slot; whether the last adaptive render counted and whether a budget pass has run (srt_adaptive_host.h); the
+    // tile ticket of a launch (zeroed on the stream in front of it); the record a counting launch adds to (srt::ADP_WORK_N words);
+    // the budget pass's total (one word).  The sample scratch is the radiance pass's, d_radiance_rows: one stream runs both.
+    DeviceBuffer<uint32_t> d_counts_own;
+    srt::OutputSlot counts;
+    DeviceBuffer<uint32_t> d_budget_own;
+    srt::OutputSlot budget;
+    srt::AdaptiveState adaptive;
+    DeviceBuffer<uint32_t> d_adaptive_ticket;
+    DeviceBuffer<unsigned long long> d_adaptive_work;
+    DeviceBuffer<unsigned long long> d_budget_total;
 
     char error[512] = "";
 };
@@ -1935,6 +1949,178 @@ int srt_get_radiance_work(srt_context* ctx, srt_radiance_work* out) {
     out->valid = 1, out->reserved = 0;
     out->rays = w[srt::RAD_WORK_RAYS], out->samples = w[srt::RAD_WORK_SAMPLES];
     out->closest_calls = w[srt::RAD_WORK_CLOSEST], out->wave_calls = w[srt::RAD_WORK_WAVE_CALLS];
+    return SRT_OK;
+}
+
+// ---- adaptive sampling ---------------------------------------------------------------------------------------------
+static_assert(SRT_ADAPTIVE_KEEP_COUNTS == srt::ADAPTIVE_FLAG_KEEP_COUNTS && SRT_ADAPTIVE_COUNT_WORK == srt::ADAPTIVE_FLAG_COUNT_WORK &&
+              SRT_BUDGET_ALBEDO == srt::BUDGET_FLAG_ALBEDO && sizeof(srt_adaptive_params) == 28 && sizeof(srt::AdaptiveCall) == 28 &&
+              sizeof(srt_budget_params) == 16 && sizeof(srt::BudgetCall) == 16 && sizeof(srt_adaptive_work) == 40 &&
+              srt::ADP_FRAME_LIMIT == srt::ADAPTIVE_FRAME_LIMIT && (int)srt::ADP_WORK_N == (int)srt::RAD_WORK_N,
+              "srt_adaptive_host.h, srt_adaptive.hip.h and srt_pathtrace.h disagree");
+
+// The counts or the budget as a write target: the bound buffer, else the own one, allocated on first use.
+static int sample_buffer_target(srt_context* ctx, srt::OutputSlot& slot, DeviceBuffer<uint32_t>& own, uint32_t*& dst) {
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    SRT_WRITE_TARGET(ctx, slot, own, frame_pixels(ctx) * sizeof(uint32_t), dst);
+    return SRT_OK;
+}
+
+static int write_sample_buffer(srt_context* ctx, srt::OutputSlot& slot, DeviceBuffer<uint32_t>& own, const uint32_t* src) {
+    if (const int rc = finish_stream(ctx)) return rc;
+    uint32_t* dst = nullptr;
+    if (const int rc = sample_buffer_target(ctx, slot, own, dst)) return rc;
+    SRT_HIP(ctx, hipMemcpy(dst, src, frame_pixels(ctx) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    slot.wrote(dst);
+    return SRT_OK;
+}
+
+int srt_set_sample_counts(srt_context* ctx, uint32_t value) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    uint32_t* dst = nullptr;
+    if (const int rc = sample_buffer_target(ctx, ctx->counts, ctx->d_counts_own, dst)) return rc;
+    SRT_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)dst, (int)value, frame_pixels(ctx), ctx->stream));
+    ctx->counts.wrote(dst);
+    return SRT_OK;
+}
+
+int srt_write_sample_counts(srt_context* ctx, const uint32_t* src) {
+    if (!ctx || !src) return SRT_ERR_INVALID_ARG;
+    return write_sample_buffer(ctx, ctx->counts, ctx->d_counts_own, src);
+}
+
+int srt_read_sample_counts(srt_context* ctx, uint32_t* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    return read_slot(ctx, current(ctx->counts, ctx->d_counts_own), dst, frame_pixels(ctx) * sizeof(uint32_t),
+                     "srt_read_sample_counts: the sample counts have never been written, filled or bound");
+}
+
+int srt_bind_sample_counts(srt_context* ctx, void* d_u32) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    return ctx->counts.bind(d_u32), SRT_OK;  // (no synchronisation: an enqueued call keeps the buffer it was given)
+}
+
+int srt_write_sample_budget(srt_context* ctx, const uint32_t* src) {
+    if (!ctx || !src) return SRT_ERR_INVALID_ARG;
+    return write_sample_buffer(ctx, ctx->budget, ctx->d_budget_own, src);
+}
+
+int srt_read_sample_budget(srt_context* ctx, uint32_t* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    return read_slot(ctx, current(ctx->budget, ctx->d_budget_own), dst, frame_pixels(ctx) * sizeof(uint32_t),
+                     "srt_read_sample_budget: the sample budget has never been written or bound");
+}
+
+int srt_bind_sample_budget(srt_context* ctx, void* d_u32) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    return ctx->budget.bind(d_u32), SRT_OK;  // (no synchronisation: an enqueued call keeps the buffer it was given)
+}
+
+int srt_adaptive_params_default(srt_adaptive_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::AdaptiveCall c;
+    srt::adaptive_call_default(c);
+    out->row_begin = c.row_begin, out->row_end = c.row_end, out->max_bounces = c.max_bounces, out->seed = c.seed;
+    out->max_samples = c.max_samples, out->flags = c.flags, out->reserved = c.reserved;
+    return SRT_OK;
+}
+
+int srt_render_adaptive(srt_context* ctx, const srt_adaptive_params* a) {
+    if (!ctx || !a) return SRT_ERR_INVALID_ARG;
+    const srt::AdaptiveCall call{a->row_begin, a->row_end, a->max_bounces, a->seed, a->max_samples, a->flags, a->reserved};
+    uint32_t* const counts = current(ctx->counts, ctx->d_counts_own);
+    const uint32_t* const budget = current(ctx->budget, ctx->d_budget_own);
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::adaptive_check(call, ctx->scene_set, ctx->camera.set, ctx->height, counts != nullptr, budget != nullptr, &why))
+        return fail(ctx, (int)rs, "srt_render_adaptive: %s (rows [%d,%d) of %d, max_bounces %d, max_samples %u, flags 0x%x, reserved %u)", why, a->row_begin,
+                    a->row_end, ctx->height, a->max_bounces, a->max_samples, a->flags, a->reserved);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const bool count = (a->flags & SRT_ADAPTIVE_COUNT_WORK) != 0;
+    srt::KernelParams K;
+    const KernelSetup ks = scene_kernel_params(ctx, a->row_begin, a->row_end, K);
+    // (the fields the bounce loop and store_pixel read; the frames are per pixel)
+    K.max_bounces = a->max_bounces, K.seed = a->seed;
+    K.accumulator = ctx->d_acc, K.framebuffer = ctx->d_fb;
+    const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::adaptive_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    // the grid first: the sample scratch is sized by it
+    const unsigned wgs = srt::adaptive_grid(K.width, K.rows, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
+    const size_t scratch = srt::adaptive_scratch_bytes(wgs, srt::OUT_WG_UNITS);
+    if (ctx->d_radiance_rows.bytes() < scratch) {
+        if (const int rc = finish_stream(ctx)) return rc;
+        SRT_HIP(ctx, ctx->d_radiance_rows.ensure(scratch));
+    }
+    if (!ctx->d_adaptive_ticket) SRT_HIP(ctx, ctx->d_adaptive_ticket.ensure(sizeof(uint32_t)));
+    SRT_HIP(ctx, hipMemsetAsync(ctx->d_adaptive_ticket, 0, sizeof(uint32_t), ctx->stream));
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_adaptive_work, srt::ADP_WORK_N)) return rc;
+    }
+    srt::AdaptiveIO io{};
+    io.budget = budget;
+    io.counts = counts;
+    io.max_samples = a->max_samples;
+    io.keep_counts = (a->flags & SRT_ADAPTIVE_KEEP_COUNTS) ? 1u : 0u;
+    io.ticket = ctx->d_adaptive_ticket;
+    io.rows = ctx->d_radiance_rows;
+    io.work = count ? (unsigned long long*)ctx->d_adaptive_work : nullptr;
+    if (const int rc = launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
+    if (!io.keep_counts) ctx->counts.wrote(counts);
+    srt::adaptive_rendered(ctx->adaptive, a->flags);
+    return SRT_OK;
+}
+
+int srt_get_adaptive_work(srt_context* ctx, srt_adaptive_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::adaptive_check_work(ctx->adaptive) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_adaptive_work: the last srt_render_adaptive did not ask for SRT_ADAPTIVE_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::ADP_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_adaptive_work, w, srt::ADP_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0;
+    out->pixels = w[srt::ADP_WORK_PIXELS], out->samples = w[srt::ADP_WORK_SAMPLES];
+    out->closest_calls = w[srt::ADP_WORK_CLOSEST], out->wave_calls = w[srt::ADP_WORK_WAVE_CALLS];
+    return SRT_OK;
+}
+
+int srt_budget_params_default(srt_budget_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::BudgetCall c;
+    srt::budget_call_default(c);
+    out->threshold = c.threshold, out->floor = c.floor, out->max_budget = c.max_budget, out->flags = c.flags;
+    return SRT_OK;
+}
+
+int srt_sample_budget(srt_context* ctx, const srt_budget_params* b) {
+    if (!ctx || !b) return SRT_ERR_INVALID_ARG;
+    const srt::BudgetCall call{b->threshold, b->floor, b->max_budget, b->flags};
+    const bool demod = (b->flags & SRT_BUDGET_ALBEDO) != 0;
+    const int32_t* const object = (const int32_t*)current(ctx->gbuf[0], ctx->d_gbuf_own[0]);
+    const float4* const albedo = (const float4*)current(ctx->gbuf[3], ctx->d_gbuf_own[3]);
+    const float* const var = ctx->var.bound ? (const float*)ctx->var.bound : ctx->var_own_written ? (float*)ctx->d_var_own : nullptr;
+    const uint32_t* const counts = current(ctx->counts, ctx->d_counts_own);
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::budget_check(call, object != nullptr, albedo != nullptr, var != nullptr, !ctx->var.bound, ctx->var_own_albedo,
+                                                     counts != nullptr, &why))
+        return fail(ctx, (int)rs, "srt_sample_budget: %s (threshold %g, floor %g, max_budget %u, flags 0x%x)", why, (double)b->threshold, (double)b->floor,
+                    b->max_budget, b->flags);
+    srt::BudgetLaunch L{};
+    if (const int rc = sample_buffer_target(ctx, ctx->budget, ctx->d_budget_own, L.budget)) return rc;
+    if (const int rc = zero_work(ctx, ctx->d_budget_total, 1)) return rc;
+    L.variance = var, L.counts = counts, L.acc = ctx->d_acc, L.object = object, L.albedo = demod ? albedo : nullptr;
+    L.total = ctx->d_budget_total;
+    L.width = ctx->width, L.height = ctx->height;
+    L.threshold = b->threshold, L.floor = b->floor, L.max_budget = b->max_budget;
+    hipLaunchKernelGGL(srt::budget_kernel, frame_tile_grid(ctx), dim3(srt::WG_THREADS), 0, ctx->stream, L);
+    SRT_HIP(ctx, hipGetLastError());
+    ctx->budget.wrote(L.budget);
+    ctx->adaptive.budgeted = true;
+    return SRT_OK;
+}
+
+int srt_get_budget_total(srt_context* ctx, uint64_t* total) {
+    if (!ctx || !total) return SRT_ERR_INVALID_ARG;
+    if (srt::budget_check_total(ctx->adaptive) != srt::RAYS_OK) return fail(ctx, SRT_ERR_STATE, "srt_get_budget_total: there has been no srt_sample_budget");
+    unsigned long long w = 0ull;
+    if (const int rc = read_work(ctx, ctx->d_budget_total, &w, 1)) return rc;
+    *total = w;
     return SRT_OK;
 }
 

@@ -1247,11 +1247,10 @@ __device__ __forceinline__ uint32_t pack_channel(float v) {  // Common.hpp:190-2
     return (uint32_t)(uint8_t)s;
 }
 
-// SetScreenPixel accumulate half (Raytracer.cpp:65-71) for sample index sidx (0-based in
-// this launch); the colour's alpha `a` is +0 or NaN (see alpha_tag)
-__device__ __forceinline__ void accumulate_sample(const KernelParams& P, float4& acc, RGB c, float a, uint32_t sidx) {
-    const uint32_t frame = P.first_sample + sidx;
-    if (sidx == 0 && (P.flags & 1u) != 0) {
+// SetScreenPixel accumulate half (Raytracer.cpp:65-71) for ACCUMULATIONFRAMES == frame; `overwrite`: setFrame (:69-71).  The
+// colour's alpha `a` is +0 or NaN (see alpha_tag).  (adaptive_kernel calls this with a frame of the lane's own.)
+__device__ __forceinline__ void accumulate_frame(float4& acc, RGB c, float a, uint32_t frame, bool overwrite) {
+    if (overwrite) {
         acc = make_float4(c.r, c.g, c.b, a);
     } else {
         // :66  float weight = 1.0 / ACCUMULATIONFRAMES (double divide, rounded once).  For
@@ -1266,6 +1265,13 @@ __device__ __forceinline__ void accumulate_sample(const KernelParams& P, float4&
         acc.z = clamp0(acc.z * om) + c.b * weight;
         acc.w = clamp0(acc.w * om) + a * weight;
     }
+}
+// ... for sample index sidx (0-based in this launch) of a launch whose samples all pixels share
+__device__ __forceinline__ void accumulate_sample(const KernelParams& P, float4& acc, RGB c, float a, uint32_t sidx) {
+    const uint32_t frame = P.first_sample + sidx;
+    // (two calls with a constant flag: after inlining this is the branch the function had before it was split, instruction for instruction)
+    if (sidx == 0 && (P.flags & 1u) != 0) accumulate_frame(acc, c, a, frame, true);
+    else accumulate_frame(acc, c, a, frame, false);
 }
 // SetScreenPixel tone-map + pack + the two stores (Raytracer.cpp:64,73-75)
 __device__ __forceinline__ uint32_t tone_map(const float4 acc) {

@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .capi import (RADIANCE_COUNT_WORK, RADIANCE_NORMALIZE, RADIANCE_RESET, RadianceParams, RadianceWork, VIS_AO, VIS_COUNT_WORK, VIS_SUN, VISIBILITY, VisibilityParams, VisibilityWork, OCCLUSION_COUNT_WORK, OCCLUSION_NORMALIZE, OcclusionWork, RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
+from .capi import (ADAPTIVE_COUNT_WORK, ADAPTIVE_KEEP_COUNTS, BUDGET_ALBEDO, AdaptiveParams, BudgetParams, RADIANCE_COUNT_WORK, RADIANCE_NORMALIZE, RADIANCE_RESET, RadianceParams, RadianceWork, VIS_AO, VIS_COUNT_WORK, VIS_SUN, VISIBILITY, VisibilityParams, VisibilityWork, OCCLUSION_COUNT_WORK, OCCLUSION_NORMALIZE, OcclusionWork, RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
                    TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -36,6 +36,8 @@ EXPORTS = [
     "srt_host_renderer_trace_occlusion", "srt_host_renderer_occlusion_work",
     "srt_host_renderer_render_visibility", "srt_host_renderer_read_visibility", "srt_host_renderer_visibility_work",
     "srt_host_renderer_trace_radiance", "srt_host_renderer_read_radiance", "srt_host_renderer_radiance_work",
+    "srt_host_renderer_sample_budget", "srt_host_renderer_render_adaptive", "srt_host_renderer_set_sample_counts",
+    "srt_host_renderer_read_sample_counts", "srt_host_renderer_adaptive_frame",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
     "srt_host_multi_render_samples", "srt_host_multi_read_framebuffer", "srt_host_multi_band", "srt_host_multi_stats", "srt_host_multi_balance", "srt_host_multi_use_equal_bands",
     "srt_host_multi_use_manual_bands", "srt_host_multi_set_auto_balance_min_samples", "srt_host_multi_set_row_band",
@@ -123,6 +125,11 @@ def load_library():
     L.srt_host_renderer_trace_radiance.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.POINTER(RadianceParams)]
     L.srt_host_renderer_read_radiance.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_radiance_work.argtypes = [vp, C.POINTER(RadianceWork)]
+    L.srt_host_renderer_sample_budget.argtypes = [vp, C.POINTER(BudgetParams), C.POINTER(C.c_uint64)]
+    L.srt_host_renderer_render_adaptive.argtypes = [vp, C.POINTER(AdaptiveParams)]
+    L.srt_host_renderer_set_sample_counts.argtypes = [vp, C.c_uint32]
+    L.srt_host_renderer_read_sample_counts.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.srt_host_renderer_adaptive_frame.argtypes = [vp, C.c_uint32, C.c_int, C.POINTER(BudgetParams), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.srt_host_renderer_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
     L.srt_host_renderer_read_denoised.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
@@ -408,6 +415,41 @@ class Renderer:
         w = RadianceWork()
         self._ck(self.L.srt_host_renderer_radiance_work(self._h, C.byref(w)))
         return w.as_dict()
+
+    def _budget_params(self, threshold, floor, max_budget, albedo):
+        return BudgetParams(float(threshold), float(floor), int(max_budget), BUDGET_ALBEDO if albedo else 0)
+
+    def sample_budget(self, threshold=0.05, floor=0.01, max_budget=64, albedo=True):
+        """PathTraceRenderer::sampleBudget: srt_sample_budget on the handle's buffers as they stand; returns the budget's sum.  Waits."""
+        t = C.c_uint64(0)
+        self._ck(self.L.srt_host_renderer_sample_budget(self._h, C.byref(self._budget_params(threshold, floor, max_budget, albedo)), C.byref(t)))
+        return int(t.value)
+
+    def render_adaptive(self, bounces=8, seed=0, max_samples=4096, rows=None, keep_counts=False, count_work=False):
+        """PathTraceRenderer::renderAdaptive: srt_render_adaptive with the renderer's scene and camera (rows=None: its own band)."""
+        rb, re = rows if rows is not None else (0, 0)
+        p = AdaptiveParams(int(rb), int(re), int(bounces), int(seed) & 0xFFFFFFFF, int(max_samples),
+                           (ADAPTIVE_KEEP_COUNTS if keep_counts else 0) | (ADAPTIVE_COUNT_WORK if count_work else 0), 0)
+        self._ck(self.L.srt_host_renderer_render_adaptive(self._h, C.byref(p)))
+
+    def set_sample_counts(self, value):
+        """PathTraceRenderer::setSampleCounts (srt_set_sample_counts)."""
+        self._ck(self.L.srt_host_renderer_set_sample_counts(self._h, int(value)))
+
+    def sample_counts(self):
+        """PathTraceRenderer::readSampleCounts: (H, W) uint32, scene rows.  Waits."""
+        out = np.empty((self.height, self.width), dtype=np.uint32)
+        self._ck(self.L.srt_host_renderer_read_sample_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def render_adaptive_frame(self, spp, rounds=1, threshold=0.05, floor=0.01, max_budget=64, albedo=True, max_samples=None):
+        """PathTraceRenderer::renderAdaptiveFrame: the two-half adaptive workflow; returns (total samples, (H, W) uint32 samples per
+        pixel, both halves).  The accumulator then holds the mean of the halves.  Waits."""
+        t = C.c_uint64(0)
+        n = np.empty((self.height, self.width), dtype=np.uint32)
+        self._ck(self.L.srt_host_renderer_adaptive_frame(self._h, int(spp), int(rounds), C.byref(self._budget_params(threshold, floor, max_budget, albedo)),
+                                                         int(max_budget if max_samples is None else max_samples), n.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(t)))
+        return int(t.value), n
 
     def render_visibility(self, ao_samples=16, radius=float("inf"), sun=True, ao=True, first_sample=1, seed=0, rows=None, count_work=False):
         """PathTraceRenderer::renderVisibility: render the three guides of the band with the current scene and camera, then

@@ -227,6 +227,20 @@ int srt_host_renderer_trace_radiance(srt_host_renderer* h, const float* origins,
 }
 int srt_host_renderer_read_radiance(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->readRadiance(dst)) }
 int srt_host_renderer_radiance_work(srt_host_renderer* h, srt_radiance_work* out) { SRT_HOST_TRY(h, *out = h->r->radianceWork()) }
+// adaptive sampling on the handle's buffers as they stand (srt_sample_budget + srt_get_budget_total, srt_render_adaptive; a band
+// of [0, 0) means the renderer's own), and the two-half workflow (PathTraceRenderer::renderAdaptiveFrame; counts may be NULL)
+int srt_host_renderer_sample_budget(srt_host_renderer* h, const srt_budget_params* p, uint64_t* total) { SRT_HOST_TRY(h, *total = h->r->sampleBudget(*p)) }
+int srt_host_renderer_render_adaptive(srt_host_renderer* h, const srt_adaptive_params* p) { SRT_HOST_TRY(h, h->r->renderAdaptive(*p)) }
+int srt_host_renderer_set_sample_counts(srt_host_renderer* h, uint32_t value) { SRT_HOST_TRY(h, h->r->setSampleCounts(value)) }
+int srt_host_renderer_read_sample_counts(srt_host_renderer* h, uint32_t* dst) { SRT_HOST_TRY(h, h->r->readSampleCounts(dst)) }
+int srt_host_renderer_adaptive_frame(srt_host_renderer* h, uint32_t spp, int rounds, const srt_budget_params* budget, uint32_t max_samples, uint32_t* counts,
+                                     uint64_t* total) {
+    SRT_HOST_TRY(h, {
+        std::vector<uint32_t> n;
+        *total = h->r->renderAdaptiveFrame(spp, rounds, *budget, max_samples, counts ? &n : nullptr);
+        if (counts) std::memcpy(counts, n.data(), n.size() * sizeof(uint32_t));
+    })
+}
 // per-pixel visibility: the guides of the band, then srt_render_visibility (a band of [0, 0) means the renderer's own)
 int srt_host_renderer_render_visibility(srt_host_renderer* h, const srt_visibility_params* p) { SRT_HOST_TRY(h, h->r->renderVisibility(*p)) }
 int srt_host_renderer_read_visibility(srt_host_renderer* h, uint32_t output, float* dst) { SRT_HOST_TRY(h, h->r->readVisibility(output, dst)) }

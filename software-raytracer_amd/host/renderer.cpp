@@ -253,6 +253,85 @@ srt_radiance_work PathTraceRenderer::radianceWork() {
     return w;
 }
 
+uint64_t PathTraceRenderer::sampleBudget(const srt_budget_params& params) {
+    check(srt_sample_budget(ctx_, &params), "srt_sample_budget");
+    uint64_t total = 0;
+    check(srt_get_budget_total(ctx_, &total), "srt_get_budget_total");
+    return total;
+}
+
+void PathTraceRenderer::renderAdaptive(const srt_adaptive_params& params) {
+    srt_adaptive_params a = params;
+    if (a.row_begin == 0 && a.row_end == 0) a.row_begin = row_begin_, a.row_end = row_end_;
+    push_camera();
+    check(srt_render_adaptive(ctx_, &a), "srt_render_adaptive");
+}
+
+void PathTraceRenderer::setSampleCounts(uint32_t value) { check(srt_set_sample_counts(ctx_, value), "srt_set_sample_counts"); }
+
+void PathTraceRenderer::readSampleCounts(uint32_t* dst) { check(srt_read_sample_counts(ctx_, dst), "srt_read_sample_counts"); }
+
+uint64_t PathTraceRenderer::renderAdaptiveFrame(uint32_t spp, int rounds, const srt_budget_params& budget, uint32_t max_samples, std::vector<uint32_t>* counts) {
+    if (spp < 2 || (spp & 1u))
+        throw RendererError(SRT_ERR_INVALID_ARG, "renderAdaptiveFrame: spp must be even and >= 2 (two half renders of spp / 2 samples each)");
+    if (rounds < 0) throw RendererError(SRT_ERR_INVALID_ARG, "renderAdaptiveFrame: rounds must be >= 0");
+    if (row_begin_ != 0 || row_end_ != height_)
+        throw RendererError(SRT_ERR_STATE, "renderAdaptiveFrame: the renderer has a row band; the variance passes cover the whole frame");
+    push_camera();
+    srt_render_params p{};
+    p.row_begin = 0;
+    p.row_end = height_;
+    p.first_sample = 1;
+    p.sample_count = spp / 2;
+    p.max_bounces = MAXBOUNCES < 0 ? 0 : MAXBOUNCES;
+    p.seed = seed;
+    p.flags = SRT_RENDER_RESET;
+    p.steps = 1;
+    p.selected_object = -1;
+    const uint32_t seed_b = seed ^ 0x9E3779B9u;
+    check(srt_render(ctx_, &p), "srt_render");  // half A, into the accumulator
+    void *fb = nullptr, *acc = nullptr, *half = nullptr;
+    check(srt_device_framebuffer(ctx_, &fb), "srt_device_framebuffer");
+    check(srt_device_accumulator(ctx_, &acc), "srt_device_accumulator");
+    check(srt_device_half(ctx_, &half), "srt_device_half");
+    check(srt_bind_output(ctx_, fb, half), "srt_bind_output");
+    p.seed = seed_b;
+    int rc = srt_render(ctx_, &p);  // half B, into the half buffer; then the binding as it was
+    check(srt_bind_output(ctx_, fb, acc), "srt_bind_output");
+    check(rc, "srt_render");
+    setSampleCounts(spp / 2);
+    const bool demod = (budget.flags & SRT_BUDGET_ALBEDO) != 0;
+    RenderGBuffer(SRT_GBUF_OBJECT | (demod ? SRT_GBUF_ALBEDO : 0u));
+    srt_variance_params v{};
+    v.flags = demod ? SRT_VARIANCE_ALBEDO : 0u;
+    srt_adaptive_params a{};
+    check(srt_adaptive_params_default(&a), "srt_adaptive_params_default");
+    a.row_begin = 0, a.row_end = height_, a.max_bounces = p.max_bounces, a.max_samples = max_samples;
+    for (int k = 0; k < rounds; ++k) {
+        check(srt_variance(ctx_, &v), "srt_variance");
+        (void)sampleBudget(budget);
+        a.seed = seed, a.flags = SRT_ADAPTIVE_KEEP_COUNTS;
+        check(srt_render_adaptive(ctx_, &a), "srt_render_adaptive");  // half A: the counts stay for half B
+        check(srt_bind_output(ctx_, fb, half), "srt_bind_output");
+        a.seed = seed_b, a.flags = 0;
+        rc = srt_render_adaptive(ctx_, &a);
+        check(srt_bind_output(ctx_, fb, acc), "srt_bind_output");
+        check(rc, "srt_render_adaptive");
+    }
+    v.flags |= SRT_VARIANCE_MERGE;
+    check(srt_variance(ctx_, &v), "srt_variance");
+    std::vector<uint32_t> n((size_t)width_ * height_);
+    readSampleCounts(n.data());
+    uint64_t total = 0;
+    for (uint32_t& c : n) c *= 2u, total += c;
+    if (counts) counts->swap(n);
+    // the accumulator now holds the mean of the halves, which no render can continue
+    doSetFrame_ = true;
+    clean_reset_ = true;
+    first_frame_ = false;
+    return total;
+}
+
 void PathTraceRenderer::renderVisibility(const srt_visibility_params& params) {
     srt_visibility_params v = params;
     if (v.row_begin == 0 && v.row_end == 0) v.row_begin = row_begin_, v.row_end = row_end_;

@@ -165,6 +165,20 @@ class PathTraceRenderer {
     void traceRadiance(const float* origins, const float* directions, size_t count, const srt_radiance_params& params);
     void readRadiance(float* dst_rgba);
     srt_radiance_work radianceWork();
+    // Adaptive sampling (srt_sample_budget, srt_render_adaptive), on the handle's buffers as they stand.  sampleBudget turns the
+    // variance buffer, the sample counts, the accumulator and the guides into the per-pixel budget and returns its sum (waits).
+    // renderAdaptive enqueues the adaptive render with the renderer's scene and camera; a band of [0, 0) means the renderer's
+    // own.  setSampleCounts / readSampleCounts are srt_set_sample_counts / srt_read_sample_counts.
+    // renderAdaptiveFrame is the two-half workflow of the header (whole frame only): spp / 2 uniform samples per half (seed and
+    // seed ^ 0x9E3779B9, as denoiseVariance), the guides once, then `rounds` rounds of srt_variance without MERGE,
+    // sampleBudget(budget) and renderAdaptive on half A (KEEP_COUNTS) and half B, and srt_variance with MERGE at the end: the
+    // accumulator holds the mean of the halves.  Returns the samples of the frame, the sum over the pixels of twice the per-half
+    // count; `counts`, when given, receives W x H per-pixel samples (both halves, scene rows).
+    uint64_t sampleBudget(const srt_budget_params& params);
+    void renderAdaptive(const srt_adaptive_params& params);
+    void setSampleCounts(uint32_t value);
+    void readSampleCounts(uint32_t* dst);
+    uint64_t renderAdaptiveFrame(uint32_t spp, int rounds, const srt_budget_params& budget, uint32_t max_samples, std::vector<uint32_t>* counts = nullptr);
     // Per-pixel visibility (srt_render_visibility): ambient occlusion and sun visibility at the first hit.  renderVisibility first
     // renders the three guides the pass reads (OBJECT, NORMAL_DEPTH, POSITION) for the band with the current scene and camera —
     // the renderer cannot know whether the ones in the handle are stale, as with the denoiser's — and then enqueues the pass;

@@ -149,6 +149,7 @@ static void usage() {
                  "                  [--ao N [--ao-radius R]] [--sun-visibility] [--vis-out FILE]\n"
                  "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--any-hit] [--device 0]\n"
                  "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin --radiance N [--bounces B] [--seed S] [--rays-normalize]\n"
+                 "       srt_render --scene FILE --adaptive ROUNDS [--adaptive-threshold T] [--adaptive-max M] [--counts-out FILE] [--spp N] ...\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
                  "             and means the same), --equal-bands: bands of equal height\n"
@@ -190,6 +191,13 @@ static void usage() {
                  "  --radiance N: with --rays, ask srt_trace_radiance instead: the running mean of N (1..4096) path-traced samples of\n"
                  "             --bounces bounces along every ray (samples 1..N, --seed, ray i draws from the stream of pixel i); --rays-out\n"
                  "             then receives the N float4 alone; not with --any-hit\n"
+                 "  --adaptive ROUNDS: adaptive sampling in place of the uniform frame: an even --spp is the uniform seed, split into two\n"
+                 "             independently seeded halves; then ROUNDS (1..64) rounds of srt_variance, srt_sample_budget and srt_render_adaptive\n"
+                 "             on both halves, and the mean of the halves goes to --out; the frame's total samples are printed on stderr;\n"
+                 "             single device, no other frame option\n"
+                 "  --adaptive-threshold T: the budget's target relative standard error (> 0; default: the library's, 0.05)\n"
+                 "  --adaptive-max M: the most samples a round adds to a pixel of a half (1..4096; default: the library's, 64)\n"
+                 "  --counts-out FILE: with --adaptive, the per-pixel samples of the frame (W x H uint32, scene rows, both halves)\n"
                  "  --ao N:    after the frame, per-pixel ambient occlusion (srt_render_visibility): the fraction of N (1..4096) hemisphere\n"
                  "             segments of length --ao-radius (default: unbounded) at the first hit that are unoccluded; samples 1..N, --seed\n"
                  "  --sun-visibility: after the frame, per-pixel sun visibility: n . -sunDirection where the sun is seen, else 0\n"
@@ -202,6 +210,10 @@ int main(int argc, char** argv) {
     bool rays_normalize = false, rays_any_hit = false;
     int radiance = 0;
     bool radiance_given = false;
+    int adaptive = 0, adaptive_max = 0;
+    bool adaptive_given = false, adaptive_threshold_given = false, adaptive_max_given = false;
+    float adaptive_threshold = 0;
+    std::string counts_out;
     std::string vis_out;
     int ao = 0;
     bool ao_given = false, sun_visibility = false;
@@ -258,6 +270,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rays-normalize")) rays_normalize = true;
         else if (!std::strcmp(argv[i], "--any-hit")) rays_any_hit = true;
         else if (!std::strcmp(argv[i], "--radiance")) radiance = std::atoi(need("--radiance")), radiance_given = true;
+        else if (!std::strcmp(argv[i], "--adaptive")) adaptive = std::atoi(need("--adaptive")), adaptive_given = true;
+        else if (!std::strcmp(argv[i], "--adaptive-threshold")) adaptive_threshold = std::strtof(need("--adaptive-threshold"), nullptr), adaptive_threshold_given = true;
+        else if (!std::strcmp(argv[i], "--adaptive-max")) adaptive_max = std::atoi(need("--adaptive-max")), adaptive_max_given = true;
+        else if (!std::strcmp(argv[i], "--counts-out")) counts_out = need("--counts-out");
         else if (!std::strcmp(argv[i], "--ao")) ao = std::atoi(need("--ao")), ao_given = true;
         else if (!std::strcmp(argv[i], "--ao-radius")) ao_radius = std::strtof(need("--ao-radius"), nullptr);
         else if (!std::strcmp(argv[i], "--sun-visibility")) sun_visibility = true;
@@ -352,6 +368,23 @@ int main(int argc, char** argv) {
         }
         if (!devices.empty() || temporal || steps > 1 || !upsample.empty()) {
             std::fprintf(stderr, "--denoise-variance works on one device only and not with --temporal, --steps or --upsample\n");
+            return 2;
+        }
+    }
+    if (!adaptive_given && (adaptive_threshold_given || adaptive_max_given || !counts_out.empty())) {
+        std::fprintf(stderr, "--adaptive-threshold, --adaptive-max and --counts-out need --adaptive ROUNDS\n");
+        return 2;
+    }
+    if (adaptive_given) {
+        if (adaptive < 1 || adaptive > 64 || spp < 2 || (spp & 1) || bounces < 0 || (adaptive_threshold_given && !(adaptive_threshold > 0)) ||
+            (adaptive_max_given && (adaptive_max < 1 || adaptive_max > 4096))) {
+            std::fprintf(stderr, "--adaptive ROUNDS (1..64) needs an even --spp >= 2 and a --bounces >= 0; --adaptive-threshold T > 0; --adaptive-max M in 1..4096\n");
+            return 2;
+        }
+        if (!devices.empty() || temporal || steps > 1 || aa_given || !upsample.empty() || !denoise.empty() || !denoise_variance.empty() || !rays_in.empty() ||
+            !vis_out.empty()) {
+            std::fprintf(stderr, "--adaptive renders the frame itself: single device, not with --devices, --temporal, --steps, --aa, --upsample, --denoise, "
+                                 "--denoise-variance, --rays, --ao or --sun-visibility\n");
             return 2;
         }
     }
@@ -483,6 +516,47 @@ int main(int argc, char** argv) {
                 resolve(SRT_AA_SOURCE_DENOISED);
                 r.ReadFramebuffer(fb.data(), (size_t)W * 4);
                 if (write_ppm(fb, denoise)) return 1;
+            }
+            return 0;
+        }
+        if (adaptive_given) {
+            // the uniform seed in two halves, the rounds, the merge (PathTraceRenderer::renderAdaptiveFrame); --out is the merged
+            // accumulator through SetScreenPixel's tone map (memory row H - 1 - y), which no kernel has written for the mean
+            srt_budget_params bp{};
+            srt_budget_params_default(&bp);
+            if (adaptive_threshold_given) bp.threshold = adaptive_threshold;
+            if (adaptive_max_given) bp.max_budget = (uint32_t)adaptive_max;
+            std::vector<uint32_t> counts;
+            auto t0 = std::chrono::steady_clock::now();
+            const uint64_t total = r.renderAdaptiveFrame((uint32_t)spp, adaptive, bp, bp.max_budget, &counts);
+            double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            std::fprintf(stderr, "%dx%d spp=%d bounces=%d adaptive rounds=%d threshold=%g max=%u: total samples %llu (%.2f per pixel), wall %.3f ms\n", W, H, spp,
+                         bounces, adaptive, (double)bp.threshold, bp.max_budget, (unsigned long long)total, (double)total / ((double)W * H), wall * 1e3);
+            const std::vector<float> acc = r.ReadAccumulator();
+            std::vector<uint32_t> fb((size_t)W * H);
+            auto channel = [](float v) {
+                const float s = v / (1.0f + v) * 255;
+                return (uint32_t)(s != s || s < 0 ? 0 : s > 255 ? 255 : (int)s);
+            };
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x) {
+                    const float* c = &acc[4 * ((size_t)y * W + x)];
+                    fb[(size_t)(H - 1 - y) * W + x] = 0xFF000000u | channel(c[0]) << 16 | channel(c[1]) << 8 | channel(c[2]);
+                }
+            if (write_ppm(fb, out)) return 1;
+            if (!gbuffer.empty() && write_gbuffers(r, gbuffer, W, H)) return 1;
+            if (!counts_out.empty()) {
+                FILE* g = std::fopen(counts_out.c_str(), "wb");
+                if (!g) {
+                    std::perror(counts_out.c_str());
+                    return 1;
+                }
+                bool ok = std::fwrite(counts.data(), sizeof(uint32_t), counts.size(), g) == counts.size();
+                ok = (std::fclose(g) == 0) && ok;
+                if (!ok) {
+                    std::fprintf(stderr, "%s: write failed\n", counts_out.c_str());
+                    return 1;
+                }
             }
             return 0;
         }
