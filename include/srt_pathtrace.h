@@ -1208,6 +1208,106 @@ int srt_budget_params_default(srt_budget_params* out);
 int srt_sample_budget(srt_context* ctx, const srt_budget_params* params);
 int srt_get_budget_total(srt_context* ctx, uint64_t* total);
 
+/* ---- reflection guides: first-hit buffers traced through mirror chains (ABI 7, backward compatible) ---------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of
+ * them runs what it ran before, bit for bit.
+ *
+ * The first-hit buffers steer every post-process, and they cannot see reflected geometry: a mirror is filtered as one object.
+ * For a material with smoothness = specular_amount = 1 the path tracer has no randomness at the bounce (the specular lottery
+ * always succeeds and Lerp(random, reflected, 1) is the reflected ray), so the chain of mirror hits behind a pixel is the same in
+ * every sample and all of the pixel's noise is made at the first NON-mirror surface at the end of it.  That surface's object,
+ * normal, point and albedo are the right guides, and srt_render_reflection_gbuffer computes them once per camera.
+ *
+ * 1. Definition.  Binary32 without contraction.  For every pixel (x, y) of the band:
+ *    Start.     Ray 0 is the camera ray of srt_render_gbuffer, srt_pick and srt_render's primary: camera.position and
+ *               GetRayDirection(camera, x, y).  h_j = GetClosestObject of ray j: the closest_hit, scene image, instantiation and
+ *               tie rule of srt_render_gbuffer, meshes included.
+ *    Continue.  While ray j hits, j < max_bounces, and the hit object's material has smoothness >= min_smoothness &&
+ *               specular_amount >= min_specular (a NaN comparison fails), with d the direction of ray j, n and p the normal and
+ *               point of h_j:
+ *                 k  = 2 * ((d.x*n.x + d.y*n.y) + d.z*n.z)
+ *                 r  = (d.x - n.x*k, d.y - n.y*k, d.z - n.z*k)                 float3::Reflect, Common.hpp:163-165
+ *                 d' = float3::Normalized(r)                                   sqrtf((x*x + y*y) + z*z), three IEEE divisions, :176
+ *                 o' = (p.x + n.x*.00001f, p.y + n.y*.00001f, p.z + n.z*.00001f)   :177
+ *    Stop.      J is the index of the last ray traced.  The chain either ends on an object (h_J is the terminal hit) or leaves
+ *               the scene (ray J misses).
+ *    Defaults.  min_smoothness = min_specular = 1, max_bounces = 8.  At those thresholds ray j + 1 is the bounce ray srt_render
+ *               traces from h_j in every sample; the only possible difference is the sign of a zero component, which
+ *               Lerp(a, b, 1) = a*0 + b may change.
+ *    Wider.     Lower thresholds follow the mirror direction of glossy surfaces as an approximation; +inf thresholds or
+ *               max_bounces = 0 follow nothing.
+ * 2. Outputs, W*H elements each, indexed x + y*W with the scene row y, one bit each.  The first four have the element types of
+ *    the SRT_GBUF_* table, so a buffer of one can be bound with srt_bind_gbuffer:
+ *                                         chain ends on an object                      chain leaves the scene
+ *      SRT_REFL_OBJECT         int32      list index of the terminal object            -1
+ *      SRT_REFL_NORMAL_DEPTH   float4     terminal normal xyz, w = D                   (0, 0, 0, +inf)
+ *      SRT_REFL_POSITION       float4     terminal point, w = 1                        (0, 0, 0, 0)
+ *      SRT_REFL_ALBEDO         float4     throughput x terminal base colour, w = 0     (0, 0, 0, 0)
+ *      SRT_REFL_BOUNCES        int32      J                                            J
+ *    D is the path length ((t_0 + t_1) + ...) + t_J, summed in ascending order from the distances GetClosestObject reports: what
+ *    the plane edge-stops should scale by.
+ *    ALBEDO: colours are the ones the scene image holds (clamped at 0 like Color's constructor).  Per channel
+ *      T = base_0;  for j = 1 .. J: { if (j >= 2) T = T * 0.8f;  if (j < J) T = T * specular_j; }
+ *      albedo = J == 0 ? base_0 : T * base_J
+ *    which follows hitColor of Raytracer.cpp:163-184 along the chain — the dissipation from the second bounce on and the mirror's
+ *    Lerp(base, specular, 1) — with the base colour at the terminal, as SRT_GBUF_ALBEDO has it.
+ *    Identity: for J = 0 every one of the four guide outputs equals the SRT_GBUF_* output bit for bit.
+ * 3. Band, stream and asynchrony are srt_render_gbuffer's: the band is given in memory rows, only scene rows
+ *    [H - row_end, H - row_begin) are written; scene, meshes and camera are captured at enqueue; srt_wait / srt_poll cover it.
+ * 4. What it leaves alone: the framebuffer, the accumulator, the G-buffer slots, every pass buffer, srt_get_stats,
+ *    srt_get_work_counts and the launch shape of later renders.
+ * 5. Determinism.  No atomics reach the outputs; each pixel is written once and its value does not depend on how the kernel packs
+ *    its work.
+ * 6. Buffers.  The handle's own (allocated on first use) or the caller's: srt_bind_reflection binds ONE output (a single bit) to a
+ *    DEVICE buffer of W*H elements (NULL = own; does not wait, enqueued launches keep the buffer they were given).
+ *    srt_read_reflection waits, then copies the whole W*H buffer of ONE output to host memory under srt_read_gbuffer's rule:
+ *    SRT_ERR_STATE when that output has neither been bound nor written yet.  srt_device_reflection gives the address of the
+ *    handle's OWN buffer of one output, allocated (and zeroed) on first use, as srt_device_half: this is how the four guide outputs
+ *    are handed to srt_bind_gbuffer, after which srt_denoise, srt_denoise_variance, srt_variance and srt_sample_budget are steered
+ *    by the reflected geometry.  srt_temporal_accumulate reprojects with first hits; see DESIGN.md §4.25.
+ * 7. Errors, all found before anything is touched, in this order: SRT_ERR_STATE before srt_set_scene and srt_set_camera;
+ *    SRT_ERR_INVALID_ARG for an empty or out-of-range band, outputs == 0 or unknown output bits, unknown flags, reserved != 0,
+ *    max_bounces outside 0..64, a NaN threshold.
+ * 8. Work counts.  With SRT_REFL_COUNT_WORK the launch counts, deterministically on a given device: the pixels of the band, the
+ *    reflections (the sum of J over them), the wave-level closest-hit invocations and the waves that ran at least one.  Per-wave
+ *    sums, one vector atomic per wave into a handle-owned record zeroed before the launch; without the flag there are no
+ *    atomics at all.  The kernel keeps its lanes filled from a stream of pixel slots, so
+ *      wave_calls <= (64 * tiles + reflections) / 64 + waves * (max_bounces + 1)
+ *    with tiles = the 8 x 8 tiles that meet the band.  srt_get_reflection_work waits and copies the record of the last
+ *    srt_render_reflection_gbuffer; SRT_ERR_STATE unless that call had SRT_REFL_COUNT_WORK (or when there has been none). */
+#define SRT_REFL_OBJECT 1u
+#define SRT_REFL_NORMAL_DEPTH 2u
+#define SRT_REFL_POSITION 4u
+#define SRT_REFL_ALBEDO 8u
+#define SRT_REFL_BOUNCES 16u
+#define SRT_REFL_GUIDES 15u    /* the four outputs that have SRT_GBUF_* element types */
+#define SRT_REFL_ALL 31u
+#define SRT_REFL_COUNT_WORK 1u /* flags: fill srt_reflection_work for this call */
+
+typedef struct srt_reflection_params {  /* 32 bytes */
+    int32_t row_begin, row_end;         /* memory rows, as srt_gbuffer_params */
+    uint32_t outputs;                   /* SRT_REFL_* bits, at least one */
+    uint32_t flags;                     /* 0 or SRT_REFL_COUNT_WORK */
+    int32_t max_bounces;                /* 0..64 */
+    float min_smoothness, min_specular; /* not NaN; +inf allowed */
+    uint32_t reserved;                  /* 0 */
+} srt_reflection_params;
+
+typedef struct srt_reflection_work { /* 40 bytes */
+    uint32_t valid, reserved;        /* 1, 0 */
+    uint64_t pixels, reflections;    /* pixels of the band; the sum of J over them */
+    uint64_t wave_calls, waves;      /* wave-level closest-hit invocations; waves that ran at least one */
+} srt_reflection_work;
+
+/* outputs SRT_REFL_ALL, flags 0, max_bounces 8, min_smoothness 1, min_specular 1; the band is left to the caller (0, 0).  Pure
+ * host, no device needed. */
+int srt_reflection_params_default(srt_reflection_params* out);
+int srt_render_reflection_gbuffer(srt_context* ctx, const srt_reflection_params* params);
+int srt_bind_reflection(srt_context* ctx, uint32_t output, void* d_ptr);
+int srt_read_reflection(srt_context* ctx, uint32_t output, void* dst);
+int srt_device_reflection(srt_context* ctx, uint32_t output, void** d_ptr);
+int srt_get_reflection_work(srt_context* ctx, srt_reflection_work* out);
+
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first
  * pixel), pitch_bytes per row (>= 4*W) — the renderSurface->pixels layout (:64). Waits. */

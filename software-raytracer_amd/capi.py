@@ -30,6 +30,12 @@ VIS_AO, VIS_SUN, VIS_ALL = 1, 2, 3
 VIS_COUNT_WORK = 1
 VIS_MAX_SAMPLES = 4096
 VISIBILITY = {"ao": VIS_AO, "sun": VIS_SUN}
+# reflection guides (srt_render_reflection_gbuffer): the output bits, the one flag, the bounce limit, and the output names
+# (PathTracer.read_reflection / bind_reflection) -> (output bit, numpy dtype, per-pixel channels); the first four are GBUFFERS'
+REFL_OBJECT, REFL_NORMAL_DEPTH, REFL_POSITION, REFL_ALBEDO, REFL_BOUNCES, REFL_GUIDES, REFL_ALL = 1, 2, 4, 8, 16, 15, 31
+REFL_COUNT_WORK = 1
+REFL_MAX_BOUNCES = 64
+REFLECTION = dict(GBUFFERS, bounces=(REFL_BOUNCES, np.int32, 1))
 # radiance queries (srt_trace_radiance): the flags of srt_radiance_params and the sample limit
 RADIANCE_RESET, RADIANCE_NORMALIZE, RADIANCE_COUNT_WORK = 1, 2, 4
 RADIANCE_MAX_SAMPLES = 4096
@@ -79,6 +85,8 @@ EXPORTS = [
     "srt_trace_params_default", "srt_write_rays", "srt_bind_rays", "srt_bind_ray_output", "srt_trace_rays", "srt_read_ray_output",
     "srt_occlusion_params_default", "srt_trace_occlusion", "srt_get_occlusion_work",
     "srt_visibility_params_default", "srt_render_visibility", "srt_bind_visibility", "srt_read_visibility", "srt_get_visibility_work",
+    "srt_reflection_params_default", "srt_render_reflection_gbuffer", "srt_bind_reflection", "srt_read_reflection",
+    "srt_device_reflection", "srt_get_reflection_work",
     "srt_radiance_params_default", "srt_trace_radiance", "srt_bind_radiance", "srt_read_radiance", "srt_get_radiance_work",
     "srt_set_sample_counts", "srt_write_sample_counts", "srt_read_sample_counts", "srt_bind_sample_counts",
     "srt_write_sample_budget", "srt_read_sample_budget", "srt_bind_sample_budget",
@@ -226,6 +234,22 @@ class VisibilityWork(C.Structure):
     """srt_visibility_work: what the last counting srt_render_visibility traced."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("segments", C.c_uint64), ("open", C.c_uint64), ("wave_trips", C.c_uint64),
                 ("analytic_tests", C.c_uint64), ("node_visits", C.c_uint64), ("triangle_tests", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class ReflectionParams(C.Structure):
+    """srt_reflection_params: a band in memory rows, REFL_* outputs, 0 or REFL_COUNT_WORK, the bounce limit and the two thresholds;
+    reserved must be 0."""
+    _fields_ = [("row_begin", C.c_int32), ("row_end", C.c_int32), ("outputs", C.c_uint32), ("flags", C.c_uint32),
+                ("max_bounces", C.c_int32), ("min_smoothness", C.c_float), ("min_specular", C.c_float), ("reserved", C.c_uint32)]
+
+
+class ReflectionWork(C.Structure):
+    """srt_reflection_work: what the last counting srt_render_reflection_gbuffer traced."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_uint64), ("reflections", C.c_uint64),
+                ("wave_calls", C.c_uint64), ("waves", C.c_uint64)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
@@ -425,6 +449,12 @@ def open_library(path):
     L.srt_bind_visibility.argtypes = [ctx, C.c_uint32, C.c_void_p]
     L.srt_read_visibility.argtypes = [ctx, C.c_uint32, C.POINTER(C.c_float)]
     L.srt_get_visibility_work.argtypes = [ctx, C.POINTER(VisibilityWork)]
+    L.srt_reflection_params_default.argtypes = [C.POINTER(ReflectionParams)]
+    L.srt_render_reflection_gbuffer.argtypes = [ctx, C.POINTER(ReflectionParams)]
+    L.srt_bind_reflection.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_read_reflection.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_device_reflection.argtypes = [ctx, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.srt_get_reflection_work.argtypes = [ctx, C.POINTER(ReflectionWork)]
     L.srt_radiance_params_default.argtypes = [C.POINTER(RadianceParams)]
     L.srt_trace_radiance.argtypes = [ctx, C.POINTER(RadianceParams)]
     L.srt_bind_radiance.argtypes = [ctx, C.c_void_p]
@@ -462,6 +492,24 @@ def gbuffer_outputs(outputs):
             raise ValueError("unknown G-buffer output %r (one of %s)" % (name, ", ".join(GBUFFERS)))
         mask |= GBUFFERS[name][0]
     return mask
+
+
+def reflection_outputs(outputs):
+    """An SRT_REFL_* mask from an int or from names of REFLECTION (GBUFFERS' four and "bounces")."""
+    if isinstance(outputs, int):
+        return outputs
+    if isinstance(outputs, str):
+        outputs = [outputs]
+    mask = 0
+    for name in outputs:
+        mask |= _reflection_spec(name)[0]
+    return mask
+
+
+def _reflection_spec(name):
+    if name not in REFLECTION:
+        raise ValueError("unknown reflection output %r (one of %s)" % (name, ", ".join(REFLECTION)))
+    return REFLECTION[name]
 
 
 def _gbuffer_spec(name):
@@ -907,6 +955,78 @@ class PathTracer:
         return w.as_dict()
 
     # ---- radiance queries ----------------------------------------------------------------
+    # ---- reflection guides ----------------------------------------------------------------
+    def render_reflection_gbuffer(self, rows=None, outputs=REFL_ALL, max_bounces=None, min_smoothness=None, min_specular=None,
+                                  count_work=False, flags=0, reserved=0):
+        """srt_render_reflection_gbuffer: the first-hit buffers of memory rows `rows` (default: the whole frame) traced through
+        chains of mirror-like surfaces — the object, normal + path length, point and albedo of the first surface that is not
+        one, and the number of reflections.  `outputs`: an SRT_REFL_* mask or names of REFLECTION.  Arguments left at None take
+        the library's defaults (8 reflections, smoothness and specular amount of at least 1).  count_work: SRT_REFL_COUNT_WORK
+        (reflection_work() then reads the record).  Asynchronous, like render_gbuffer()."""
+        p = ReflectionParams()
+        self._ck(self.L.srt_reflection_params_default(C.byref(p)))
+        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
+        p.outputs = reflection_outputs(outputs)
+        p.flags = int(flags) | (REFL_COUNT_WORK if count_work else 0)
+        if max_bounces is not None:
+            p.max_bounces = int(max_bounces)
+        if min_smoothness is not None:
+            p.min_smoothness = float(min_smoothness)
+        if min_specular is not None:
+            p.min_specular = float(min_specular)
+        p.reserved = int(reserved)
+        self._ck(self.L.srt_render_reflection_gbuffer(self._h, C.byref(p)))
+
+    def _reflection_shape(self, name):
+        _, dtype, ch = _reflection_spec(name)
+        return dtype, ((self.height, self.width) if ch == 1 else (self.height, self.width, ch))
+
+    def read_reflection(self, name):
+        """srt_read_reflection: the whole buffer of one output as a numpy array, rows = scene rows: "object" and "bounces"
+        (H, W) int32, the others (H, W, 4) float32.  Waits."""
+        dtype, shape = self._reflection_shape(name)
+        return self._read_image(self.L.srt_read_reflection, shape, dtype, REFLECTION[name][0])
+
+    def bind_reflection(self, name, tensor):
+        """srt_bind_reflection: write output `name` into a torch tensor on this tracer's device (None: the handle's own
+        buffer), checked like bind_gbuffer's."""
+        bit = _reflection_spec(name)[0]
+        dtype, shape = self._reflection_shape(name)
+        ptr = self._tensor_ptr("bind_reflection(%r)" % name, tensor, dtype, shape)
+        self._ck(self.L.srt_bind_reflection(self._h, bit, ptr))
+
+    def reflection_ptr(self, name):
+        """srt_device_reflection: the device address of the handle's own buffer of output `name` (allocated on first use)."""
+        p = C.c_void_p()
+        self._ck(self.L.srt_device_reflection(self._h, _reflection_spec(name)[0], C.byref(p)))
+        return p.value
+
+    def reflection_work(self):
+        """srt_get_reflection_work: the work counts of the last render_reflection_gbuffer(count_work=True) as a dict.  Waits."""
+        w = ReflectionWork()
+        self._ck(self.L.srt_get_reflection_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def use_reflection_guides(self, on=True):
+        """Steer the guided passes by the reflection guides: with `on` the handle's own four reflection guide buffers are bound
+        into the four G-buffer slots (srt_bind_gbuffer), with off NULL is (the handle's own first-hit buffers again).  While on,
+        the gbuffer=True of denoise(), denoise_variance() and variance() renders the guides with render_reflection_gbuffer()
+        (library defaults) instead of render_gbuffer(); the passes that reproject or
+        resample by first hits — temporal(), upsample(), antialias() — refuse to render guides into those buffers: call them
+        with the guides off, or with gbuffer=False on buffers of your own."""
+        for name, (bit, _, _) in GBUFFERS.items():
+            ptr = C.c_void_p(self.reflection_ptr(name)) if on else None
+            self._ck(self.L.srt_bind_gbuffer(self._h, bit, ptr))
+        self._reflection_guides = bool(on)
+
+    def _render_guides(self, outputs, what, first_hit_only=False):
+        """The guides a pass with gbuffer=True renders first: first hits, or the reflection guides while they are in use."""
+        if not getattr(self, "_reflection_guides", False):
+            return self.render_gbuffer(outputs=outputs)
+        if first_hit_only:
+            raise ValueError("%s works on first hits: use_reflection_guides(False) first, or pass guides of your own" % what)
+        self.render_reflection_gbuffer(outputs=outputs)
+
     def trace_radiance(self, origins=None, directions=None, samples=None, bounces=None, seed=0, first_sample=1, reset=True, id_base=0,
                        normalize=False, count_work=False, flags=0):
         """srt_trace_radiance: the running mean of `samples` path-traced samples (default 16) of `bounces` bounces (default 8) along
@@ -1123,7 +1243,7 @@ class PathTracer:
         current scene and camera); gbuffer=False uses the guides as they are (rendered earlier or bound).  Asynchronous."""
         p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, albedo, framebuffer, lib=self.L)
         if gbuffer:
-            self.render_gbuffer(outputs=DENOISE_GUIDES | (GBUF_ALBEDO if albedo else 0))
+            self._render_guides(DENOISE_GUIDES | (GBUF_ALBEDO if albedo else 0), "denoise")
         self._ck(self.L.srt_denoise(self._h, C.byref(p)))
 
     def denoised(self):
@@ -1143,7 +1263,7 @@ class PathTracer:
         they are.  Asynchronous.  The next render() must reset."""
         p = temporal_params(samples, max_samples, plane_tolerance, normal_threshold, reset, framebuffer, lib=self.L)
         if gbuffer:
-            self.render_gbuffer(outputs=TEMPORAL_GUIDES | (GBUF_ALBEDO if getattr(self, "_moments_albedo", False) else 0))
+            self._render_guides(TEMPORAL_GUIDES | (GBUF_ALBEDO if getattr(self, "_moments_albedo", False) else 0), "temporal", True)
         self._ck(self.L.srt_temporal_accumulate(self._h, C.byref(p)))
 
     def history_length(self):
@@ -1172,7 +1292,7 @@ class PathTracer:
         gbuffer=False uses the guides as they are.  Asynchronous."""
         p = upsample_params(steps, stripe_width, sigma_normal, sigma_plane, in_place, framebuffer, lib=self.L)
         if gbuffer:
-            self.render_gbuffer(outputs=UPSAMPLE_GUIDES)
+            self._render_guides(UPSAMPLE_GUIDES, "upsample", True)
         self._ck(self.L.srt_upsample(self._h, C.byref(p)))
 
     def upsampled(self):
@@ -1220,7 +1340,7 @@ class PathTracer:
         uses both as they are.  Asynchronous."""
         p = antialias_params(k, denoised, framebuffer, lib=self.L)
         if guides:
-            self.render_gbuffer(outputs=GBUF_OBJECT)
+            self._render_guides(GBUF_OBJECT, "antialias", True)
             self.render_subsamples(p.k)
         self._ck(self.L.srt_antialias(self._h, C.byref(p)))
 
@@ -1253,7 +1373,7 @@ class PathTracer:
         guides as they are.  Asynchronous."""
         p = variance_params(albedo, merge, lib=self.L)
         if gbuffer:
-            self.render_gbuffer(outputs=GBUF_OBJECT | (GBUF_ALBEDO if p.flags & VARIANCE_ALBEDO else 0))
+            self._render_guides(GBUF_OBJECT | (GBUF_ALBEDO if p.flags & VARIANCE_ALBEDO else 0), "variance")
         self._ck(self.L.srt_variance(self._h, C.byref(p)))
 
     def variance_map(self):
@@ -1272,7 +1392,7 @@ class PathTracer:
         DENOISE_VARIANCE_DEFAULTS.  gbuffer as in denoise().  Asynchronous."""
         p = denoise_variance_params(iterations, sigma_luminance, sigma_normal, sigma_plane, albedo, framebuffer, lib=self.L)
         if gbuffer:
-            self.render_gbuffer(outputs=DENOISE_GUIDES | (GBUF_ALBEDO if albedo else 0))
+            self._render_guides(DENOISE_GUIDES | (GBUF_ALBEDO if albedo else 0), "denoise_variance")
         self._ck(self.L.srt_denoise_variance(self._h, C.byref(p)))
 
     def moments_output(self, on=True, albedo=False):

@@ -33,6 +33,8 @@
 #include "srt_occlusion_host.h"
 #include "srt_visibility.hip.h"
 #include "srt_visibility_host.h"
+#include "srt_reflection.hip.h"
+#include "srt_reflection_host.h"
 #include "srt_radiance.hip.h"
 #include "srt_radiance_host.h"
 #include "srt_adaptive.hip.h"
@@ -368,6 +370,13 @@ struct srt_context {
     srt::OutputSlot vis[srt::VIS_SLOTS];
     srt::VisibilityState visibility;
     DeviceBuffer<unsigned long long> d_visibility_work;
+    // reflection guides (srt_render_reflection_gbuffer): one own buffer of W*H elements per SRT_REFL_* bit with its slot, whether
+    // the last call counted (srt_reflection_host.h), and the record a counting launch adds to (srt::REFL_WORK_N words, zeroed on
+    // the stream in front of it; never an output buffer)
+    DeviceBuffer<void> d_refl_own[srt::REFL_SLOTS];
+    srt::ReflectionSlots refl;
+    srt::ReflectionState reflection;
+    DeviceBuffer<unsigned long long> d_reflection_work;
     // radiance queries (srt_trace_radiance): the own output buffer of N float4 (grown when a batch needs more) with its slot (the
     // bound buffer only); what the last trace wrote and whether it counted (srt_radiance_host.h); the sample scratch of the
     // launch's grid (grown when a launch has more workgroups); the record a counting launch adds to (srt::RAD_WORK_N words)
@@ -1859,6 +1868,98 @@ int srt_get_visibility_work(srt_context* ctx, srt_visibility_work* out) {
     out->valid = 1, out->reserved = 0;
     out->segments = w[srt::VIS_WORK_SEGMENTS], out->open = w[srt::VIS_WORK_OPEN], out->wave_trips = w[srt::VIS_WORK_TRIPS];
     out->analytic_tests = w[srt::VIS_WORK_ANALYTIC], out->node_visits = w[srt::VIS_WORK_NODES], out->triangle_tests = w[srt::VIS_WORK_TRIANGLES];
+    return SRT_OK;
+}
+
+// ---- reflection guides ---------------------------------------------------------------------------------------------
+static_assert(SRT_REFL_OBJECT == srt::REFL_OUT_OBJECT && SRT_REFL_NORMAL_DEPTH == srt::REFL_OUT_NORMAL_DEPTH && SRT_REFL_POSITION == srt::REFL_OUT_POSITION &&
+              SRT_REFL_ALBEDO == srt::REFL_OUT_ALBEDO && SRT_REFL_BOUNCES == srt::REFL_OUT_BOUNCES && SRT_REFL_GUIDES == srt::REFL_OUT_GUIDES &&
+              SRT_REFL_ALL == srt::REFL_OUT_ALL && SRT_REFL_COUNT_WORK == srt::REFL_FLAG_COUNT_WORK && SRT_REFL_GUIDES == SRT_GBUF_ALL &&
+              sizeof(srt_reflection_params) == 32 && sizeof(srt::ReflectionCall) == 32 && sizeof(srt_reflection_work) == 40,
+              "srt_reflection_host.h and srt_pathtrace.h disagree");
+
+int srt_reflection_params_default(srt_reflection_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    const srt::ReflectionCall c = srt::reflection_defaults();
+    out->row_begin = c.row_begin, out->row_end = c.row_end;
+    out->outputs = c.outputs, out->flags = c.flags;
+    out->max_bounces = c.max_bounces;
+    out->min_smoothness = c.min_smoothness, out->min_specular = c.min_specular;
+    out->reserved = c.reserved;
+    return SRT_OK;
+}
+
+int srt_render_reflection_gbuffer(srt_context* ctx, const srt_reflection_params* r) {
+    if (!ctx || !r) return SRT_ERR_INVALID_ARG;
+    const srt::ReflectionCall call{r->row_begin, r->row_end, r->outputs, r->flags, r->max_bounces, r->min_smoothness, r->min_specular, r->reserved};
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::reflection_check(call, ctx->scene_set, ctx->camera.set, ctx->height, &why))
+        return fail(ctx, (int)rs, "srt_render_reflection_gbuffer: %s (rows [%d,%d) of %d, outputs 0x%x, flags 0x%x, max_bounces %d, min_smoothness %g, min_specular %g, reserved %u)",
+                    why, r->row_begin, r->row_end, ctx->height, r->outputs, r->flags, r->max_bounces, (double)r->min_smoothness, (double)r->min_specular, r->reserved);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const bool count = (r->flags & SRT_REFL_COUNT_WORK) != 0;
+    const size_t px = frame_pixels(ctx);
+    void* dst[srt::REFL_SLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < srt::REFL_SLOTS; ++i)
+        if (r->outputs & (1u << i))
+            SRT_WRITE_TARGET(ctx, ctx->refl.out[i], ctx->d_refl_own[i], px * srt::reflection_elem_bytes(i), dst[i]);
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_reflection_work, srt::REFL_WORK_N)) return rc;
+    }
+    srt::KernelParams K;
+    const KernelSetup ks = scene_kernel_params(ctx, r->row_begin, r->row_end, K);
+    srt::ReflectionIO io{};
+    io.object = (int32_t*)dst[0], io.normal_depth = (float4*)dst[1], io.position = (float4*)dst[2], io.albedo = (float4*)dst[3];
+    io.bounces = (int32_t*)dst[4];
+    io.max_bounces = r->max_bounces, io.min_smoothness = r->min_smoothness, io.min_specular = r->min_specular;
+    io.work = count ? (unsigned long long*)ctx->d_reflection_work : nullptr;
+    if (const int rc = launch_tiles(ctx, SRT_KERNEL_LDS_MESH_COUNT(srt::reflection_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count), ks, K, io)) return rc;
+    srt::reflection_rendered(ctx->reflection, ctx->refl, r->outputs, dst, r->flags);
+    return SRT_OK;
+}
+
+int srt_bind_reflection(srt_context* ctx, uint32_t output, void* d_ptr) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    const int i = srt::reflection_slot(output);
+    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_reflection: output 0x%x is not a single SRT_REFL_* bit", output);
+    return ctx->refl.out[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_gbuffer)
+}
+
+int srt_read_reflection(srt_context* ctx, uint32_t output, void* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const void* own[srt::REFL_SLOTS];
+    for (int i = 0; i < srt::REFL_SLOTS; ++i) own[i] = (void*)ctx->d_refl_own[i];
+    const void* src = nullptr;
+    const srt::RaysStatus rs = srt::reflection_check_read(ctx->refl, output, own, &src);
+    if (rs == srt::RAYS_INVALID_ARG) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_reflection: output 0x%x is not a single SRT_REFL_* bit", output);
+    const int i = srt::reflection_slot(output);
+    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, frame_pixels(ctx) * srt::reflection_elem_bytes(i),
+                     "srt_read_reflection: output 0x%x has neither been bound nor rendered", output);
+}
+
+int srt_device_reflection(srt_context* ctx, uint32_t output, void** d_ptr) {
+    if (!ctx || !d_ptr) return SRT_ERR_INVALID_ARG;
+    const int i = srt::reflection_slot(output);
+    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_device_reflection: output 0x%x is not a single SRT_REFL_* bit", output);
+    if (!(void*)ctx->d_refl_own[i]) {
+        SRT_HIP(ctx, hipSetDevice(ctx->device));
+        const size_t bytes = frame_pixels(ctx) * srt::reflection_elem_bytes(i);
+        SRT_HIP(ctx, ctx->d_refl_own[i].ensure(bytes));
+        SRT_HIP(ctx, hipMemsetAsync(ctx->d_refl_own[i], 0, bytes, ctx->stream));  // as srt_device_half's buffer starts
+    }
+    *d_ptr = (void*)ctx->d_refl_own[i];
+    return SRT_OK;
+}
+
+int srt_get_reflection_work(srt_context* ctx, srt_reflection_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::reflection_check_work(ctx->reflection) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_reflection_work: the last srt_render_reflection_gbuffer did not ask for SRT_REFL_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::REFL_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_reflection_work, w, srt::REFL_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0;
+    out->pixels = w[srt::REFL_WORK_PIXELS], out->reflections = w[srt::REFL_WORK_REFLECTIONS];
+    out->wave_calls = w[srt::REFL_WORK_CALLS], out->waves = w[srt::REFL_WORK_WAVES];
     return SRT_OK;
 }
 

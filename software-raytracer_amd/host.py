@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .capi import (ADAPTIVE_COUNT_WORK, ADAPTIVE_KEEP_COUNTS, BUDGET_ALBEDO, AdaptiveParams, BudgetParams, RADIANCE_COUNT_WORK, RADIANCE_NORMALIZE, RADIANCE_RESET, RadianceParams, RadianceWork, VIS_AO, VIS_COUNT_WORK, VIS_SUN, VISIBILITY, VisibilityParams, VisibilityWork, OCCLUSION_COUNT_WORK, OCCLUSION_NORMALIZE, OcclusionWork, RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
+from .capi import (REFL_ALL, REFL_COUNT_WORK, REFLECTION, ReflectionParams, ReflectionWork, reflection_outputs, ADAPTIVE_COUNT_WORK, ADAPTIVE_KEEP_COUNTS, BUDGET_ALBEDO, AdaptiveParams, BudgetParams, RADIANCE_COUNT_WORK, RADIANCE_NORMALIZE, RADIANCE_RESET, RadianceParams, RadianceWork, VIS_AO, VIS_COUNT_WORK, VIS_SUN, VISIBILITY, VisibilityParams, VisibilityWork, OCCLUSION_COUNT_WORK, OCCLUSION_NORMALIZE, OcclusionWork, RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
                    TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -35,6 +35,8 @@ EXPORTS = [
     "srt_host_renderer_trace_rays", "srt_host_renderer_read_ray_output",
     "srt_host_renderer_trace_occlusion", "srt_host_renderer_occlusion_work",
     "srt_host_renderer_render_visibility", "srt_host_renderer_read_visibility", "srt_host_renderer_visibility_work",
+    "srt_host_renderer_render_reflection", "srt_host_renderer_read_reflection", "srt_host_renderer_reflection_work",
+    "srt_host_renderer_reflection_guides",
     "srt_host_renderer_trace_radiance", "srt_host_renderer_read_radiance", "srt_host_renderer_radiance_work",
     "srt_host_renderer_sample_budget", "srt_host_renderer_render_adaptive", "srt_host_renderer_set_sample_counts",
     "srt_host_renderer_read_sample_counts", "srt_host_renderer_adaptive_frame",
@@ -122,6 +124,10 @@ def load_library():
     L.srt_host_renderer_render_visibility.argtypes = [vp, C.POINTER(VisibilityParams)]
     L.srt_host_renderer_read_visibility.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float)]
     L.srt_host_renderer_visibility_work.argtypes = [vp, C.POINTER(VisibilityWork)]
+    L.srt_host_renderer_render_reflection.argtypes = [vp, C.POINTER(ReflectionParams)]
+    L.srt_host_renderer_read_reflection.argtypes = [vp, C.c_uint32, C.c_void_p]
+    L.srt_host_renderer_reflection_work.argtypes = [vp, C.POINTER(ReflectionWork)]
+    L.srt_host_renderer_reflection_guides.argtypes = [vp, C.c_int, C.c_int]
     L.srt_host_renderer_trace_radiance.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.POINTER(RadianceParams)]
     L.srt_host_renderer_read_radiance.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_radiance_work.argtypes = [vp, C.POINTER(RadianceWork)]
@@ -464,6 +470,33 @@ class Renderer:
         out = np.empty((self.height, self.width), dtype=np.float32)
         self._ck(self.L.srt_host_renderer_read_visibility(self._h, VISIBILITY[name], out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def render_reflection_gbuffer(self, rows=None, outputs=REFL_ALL, max_bounces=8, min_smoothness=1.0, min_specular=1.0, count_work=False):
+        """PathTraceRenderer::renderReflectionGBuffer: push the camera and enqueue srt_render_reflection_gbuffer
+        (capi.PathTracer.render_reflection_gbuffer's arguments; rows=None: the renderer's own band)."""
+        rb, re = (int(rows[0]), int(rows[1])) if rows is not None else (0, 0)
+        p = ReflectionParams(rb, re, reflection_outputs(outputs), REFL_COUNT_WORK if count_work else 0, int(max_bounces), float(min_smoothness),
+                             float(min_specular), 0)
+        self._ck(self.L.srt_host_renderer_render_reflection(self._h, C.byref(p)))
+
+    def read_reflection(self, name):
+        """PathTraceRenderer::readReflection: one output as a numpy array, "object" and "bounces" (H, W) int32, the others (H, W, 4) float32."""
+        bit, dtype, ch = REFLECTION[name]
+        out = np.empty((self.height, self.width) if ch == 1 else (self.height, self.width, ch), dtype=dtype)
+        self._ck(self.L.srt_host_renderer_read_reflection(self._h, bit, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def reflection_work(self):
+        """PathTraceRenderer::reflectionWork: the work counts of the last render_reflection_gbuffer(count_work=True) as a dict."""
+        w = ReflectionWork()
+        self._ck(self.L.srt_host_renderer_reflection_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def reflection_guides(self, on=True, bounces=None):
+        """PathTraceRenderer::reflectionGuides: with `on`, render_gbuffer() and every pass that takes its guides from it (denoise,
+        denoise_variance, the adaptive frame's variance and budget passes) get the reflection guides; the temporal frame, the
+        anti-aliasing resolve, the visibility pass and the guided upsampler keep first hits.  bounces: reflectionBounces."""
+        self._ck(self.L.srt_host_renderer_reflection_guides(self._h, 1 if on else 0, -1 if bounces is None else int(bounces)))
 
     def visibility_work(self):
         """PathTraceRenderer::visibilityWork: the work counts of the last render_visibility(count_work=True) as a dict."""

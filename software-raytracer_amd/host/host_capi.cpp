@@ -245,6 +245,18 @@ int srt_host_renderer_adaptive_frame(srt_host_renderer* h, uint32_t spp, int rou
 int srt_host_renderer_render_visibility(srt_host_renderer* h, const srt_visibility_params* p) { SRT_HOST_TRY(h, h->r->renderVisibility(*p)) }
 int srt_host_renderer_read_visibility(srt_host_renderer* h, uint32_t output, float* dst) { SRT_HOST_TRY(h, h->r->readVisibility(output, dst)) }
 int srt_host_renderer_visibility_work(srt_host_renderer* h, srt_visibility_work* out) { SRT_HOST_TRY(h, *out = h->r->visibilityWork()) }
+// reflection guides: the pass itself (a band of [0, 0) means the renderer's own), its outputs and work record, and the switch that
+// makes RenderGBuffer — so every pass that takes its guides from it — render them (PathTraceRenderer::reflectionGuides; bounces < 0
+// keeps reflectionBounces as it is)
+int srt_host_renderer_render_reflection(srt_host_renderer* h, const srt_reflection_params* p) { SRT_HOST_TRY(h, h->r->renderReflectionGBuffer(*p)) }
+int srt_host_renderer_read_reflection(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->readReflection(output, dst)) }
+int srt_host_renderer_reflection_work(srt_host_renderer* h, srt_reflection_work* out) { SRT_HOST_TRY(h, *out = h->r->reflectionWork()) }
+int srt_host_renderer_reflection_guides(srt_host_renderer* h, int on, int bounces) {
+    SRT_HOST_TRY(h, {
+        if (bounces >= 0) h->r->reflectionBounces = bounces;
+        h->r->reflectionGuides(on != 0);
+    })
+}
 int srt_host_renderer_read_ray_output(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->readRayOutput(output, dst)) }
 // denoiser over the whole frame with the guides as they stand (srt_denoise / srt_read_denoised)
 int srt_host_renderer_denoise(srt_host_renderer* h, const srt_denoise_params* p) { SRT_HOST_TRY(h, h->r->Denoise(*p)) }

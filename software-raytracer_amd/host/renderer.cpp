@@ -145,6 +145,7 @@ bool PathTraceRenderer::RenderFrame() {
     check(srt_render(ctx_, &p), "srt_render");
     clean_reset_ = true;
     if (guidedUpsample && p.steps > 1) {
+        FirstHitScope first_hits(*this);  // the block anchors are samples of the surfaces seen directly
         RenderGBuffer(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION);
         srt_upsample_params u{};
         check(srt_upsample_params_default(&u), "srt_upsample_params_default");
@@ -208,7 +209,50 @@ void PathTraceRenderer::ReadFramebuffer(void* pixels, size_t pitch_bytes) {
     check(srt_read_framebuffer(ctx_, pixels, pitch_bytes, row_begin_, row_end_), "srt_read_framebuffer");
 }
 
+void PathTraceRenderer::bind_guides(bool reflection) {
+    for (uint32_t bit = SRT_GBUF_OBJECT; bit <= SRT_GBUF_ALBEDO; bit <<= 1) {
+        void* p = nullptr;
+        if (reflection) check(srt_device_reflection(ctx_, bit, &p), "srt_device_reflection");  // (SRT_REFL_* guide bits are the SRT_GBUF_* bits)
+        check(srt_bind_gbuffer(ctx_, bit, p), "srt_bind_gbuffer");
+    }
+}
+
+void PathTraceRenderer::reflectionGuides(bool on) {
+    bind_guides(on);
+    reflection_guides_ = on;
+}
+
+void PathTraceRenderer::FirstHitScope::rebind(PathTraceRenderer& r) noexcept {
+    try {
+        r.bind_guides(true);
+        r.reflection_guides_ = true;
+    } catch (...) {  // (a destructor: the binding stays off, as reflectionGuides() then reports)
+    }
+}
+
+void PathTraceRenderer::renderReflectionGBuffer(const srt_reflection_params& params) {
+    srt_reflection_params r = params;
+    if (r.row_begin == 0 && r.row_end == 0) r.row_begin = row_begin_, r.row_end = row_end_;
+    push_camera();
+    check(srt_render_reflection_gbuffer(ctx_, &r), "srt_render_reflection_gbuffer");
+}
+
+void PathTraceRenderer::readReflection(uint32_t output, void* dst) { check(srt_read_reflection(ctx_, output, dst), "srt_read_reflection"); }
+
+srt_reflection_work PathTraceRenderer::reflectionWork() {
+    srt_reflection_work w{};
+    check(srt_get_reflection_work(ctx_, &w), "srt_get_reflection_work");
+    return w;
+}
+
 void PathTraceRenderer::RenderGBufferRows(uint32_t outputs, int row_begin, int row_end) {
+    if (reflection_guides_) {  // the same bits, traced through the mirrors, into the buffers the G-buffer slots are bound to
+        srt_reflection_params r{};
+        check(srt_reflection_params_default(&r), "srt_reflection_params_default");
+        r.row_begin = row_begin, r.row_end = row_end, r.outputs = outputs, r.max_bounces = reflectionBounces;
+        renderReflectionGBuffer(r);
+        return;
+    }
     push_camera();
     srt_gbuffer_params g{};
     g.row_begin = row_begin;
@@ -335,6 +379,7 @@ uint64_t PathTraceRenderer::renderAdaptiveFrame(uint32_t spp, int rounds, const 
 void PathTraceRenderer::renderVisibility(const srt_visibility_params& params) {
     srt_visibility_params v = params;
     if (v.row_begin == 0 && v.row_end == 0) v.row_begin = row_begin_, v.row_end = row_end_;
+    FirstHitScope first_hits(*this);  // visibility AT the first hit
     RenderGBufferRows(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION, v.row_begin, v.row_end);  // (pushes the camera)
     check(srt_render_visibility(ctx_, &v), "srt_render_visibility");
 }
@@ -369,6 +414,7 @@ void PathTraceRenderer::Antialias(int k, int source, uint32_t flags) {
     if (row_begin_ != 0 || row_end_ != height_)
         throw RendererError(SRT_ERR_STATE, "Antialias: the renderer has a row band; the resolve covers the whole frame");
     const srt_camera c = current_camera();
+    FirstHitScope first_hits(*this);  // the sub-samples are first hits, and so is the pixel guide they are compared with
     if (aa_k_ != k || std::memcmp(&aa_cam_, &c, sizeof c) != 0) {
         aa_k_ = 0;
         RenderGBufferRows(SRT_GBUF_OBJECT, 0, height_);  // (pushes the camera)
@@ -388,6 +434,9 @@ void PathTraceRenderer::RenderTemporalFrame(uint32_t spp, bool denoise) {
     if (spp == 0) throw RendererError(SRT_ERR_INVALID_ARG, "RenderTemporalFrame: spp must be >= 1");
     if (row_begin_ != 0 || row_end_ != height_)
         throw RendererError(SRT_ERR_STATE, "RenderTemporalFrame: the renderer has a row band; temporal frames cover the whole frame");
+    // the temporal pass keeps first-hit guides, also while reflectionGuides is on: it reprojects the surface seen directly, and the
+    // image in a mirror moves by another rule (out of scope); the frame's denoiser then filters with them too
+    FirstHitScope first_hits(*this);
     push_camera();
     srt_render_params p{};
     p.row_begin = 0;

@@ -188,6 +188,23 @@ class PathTraceRenderer {
     void renderVisibility(const srt_visibility_params& params);
     void readVisibility(uint32_t output, float* dst);
     srt_visibility_work visibilityWork();
+    // Reflection guides (srt_render_reflection_gbuffer): the first-hit buffers traced through chains of mirror-like surfaces.
+    // renderReflectionGBuffer pushes the camera and enqueues the pass; a params band of [0, 0) (srt_reflection_params_default's)
+    // means the renderer's own band.  readReflection waits and copies the W x H buffer of ONE output (SRT_REFL_* bit; int32 or
+    // float4 per pixel, scene rows); reflectionWork waits and returns the counts of a call that had SRT_REFL_COUNT_WORK.
+    // reflectionGuides(true) binds the handle's own four reflection guide buffers into the four G-buffer slots (srt_bind_gbuffer)
+    // and from then on RenderGBuffer / RenderGBufferRows render THEM, with reflectionBounces and the library's thresholds:
+    // Denoise, denoiseVariance, renderAdaptiveFrame's variance and budget passes — everything that takes its guides from
+    // RenderGBuffer — is steered by the reflected geometry, and the guides are re-rendered exactly when the first hits would
+    // be.  reflectionGuides(false) binds NULL: the handle's own first-hit buffers again.  The passes that reproject or
+    // resample by first hits keep first-hit guides: RenderTemporalFrame, Antialias, renderVisibility and RenderFrame's
+    // guidedUpsample switch the binding off around their own guide render and pass and restore it afterwards.
+    void reflectionGuides(bool on);
+    bool reflectionGuides() const { return reflection_guides_; }
+    int reflectionBounces = 8;
+    void renderReflectionGBuffer(const srt_reflection_params& params);
+    void readReflection(uint32_t output, void* dst);
+    srt_reflection_work reflectionWork();
     // Denoiser (srt_denoise) over the whole frame: the accumulator guided by the first-hit buffers as they stand (call
     // RenderGBuffer first).  Asynchronous; ReadDenoised waits and copies the W x H float4 result (scene rows).
     void Denoise(const srt_denoise_params& params);
@@ -211,7 +228,8 @@ class PathTraceRenderer {
     void ReadAntialiased(float* dst_rgba);
     // One frame of a moving camera that keeps its samples (whole frame only): push the camera, render `spp` samples with
     // SRT_RENDER_RESET and seed + k (k = the number of temporal frames this renderer has rendered before, so that the noise
-    // does not stay fixed to the screen), the first-hit guides, srt_temporal_accumulate with the library's defaults
+    // does not stay fixed to the screen), the first-hit guides (first hits even while reflectionGuides is on: the reprojection
+    // follows the surface seen directly), srt_temporal_accumulate with the library's defaults
     // (samples = spp, max_samples raised to spp if below; SRT_TEMPORAL_RESET on the first temporal frame and after
     // Invalidate(), SetScene, SetEnvironment or SetRowBand), then with `denoise` srt_denoise with its defaults (with
     // temporalVariance: DenoiseTemporalVariance, and the moments are kept whether or not the frame is denoised), then with
@@ -239,6 +257,20 @@ class PathTraceRenderer {
     void check(int rc, const char* what);
     void push_camera();
     srt_camera current_camera() const;
+    bool reflection_guides_ = false;
+    void bind_guides(bool reflection);  // the four G-buffer slots: the own reflection guide buffers, or NULL
+    // first hits for the lifetime of the object, whatever reflectionGuides says
+    struct FirstHitScope {
+        PathTraceRenderer& r;
+        const bool was;
+        explicit FirstHitScope(PathTraceRenderer& r_) : r(r_), was(r_.reflection_guides_) {
+            if (was) r.bind_guides(false), r.reflection_guides_ = false;
+        }
+        ~FirstHitScope() {
+            if (was) rebind(r);
+        }
+        static void rebind(PathTraceRenderer& r) noexcept;
+    };
     // the sub-samples and the OBJECT guide Antialias last rendered: their k (0: none, or the scene has changed since) and camera
     int aa_k_ = 0;
     srt_camera aa_cam_{};

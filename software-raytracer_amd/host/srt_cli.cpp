@@ -61,6 +61,32 @@ static int write_gbuffers(R& r, const std::string& prefix, int W, int H) {
     return 0;
 }
 
+// --reflection-out PREFIX: the five outputs of the reflection guides (srt_render_reflection_gbuffer with the library's thresholds
+// and `bounces` reflections at most), named and laid out like --gbuffer's, plus PREFIX_bounces.npy (int32 HxW).
+static int write_reflection(PathTraceRenderer& r, const std::string& prefix, int W, int H, int bounces) {
+    struct Out {
+        uint32_t bit;
+        const char* name;
+        const char* descr;
+        int channels;
+    };
+    const Out outs[5] = {{SRT_REFL_OBJECT, "object", "<i4", 1},    {SRT_REFL_NORMAL_DEPTH, "normal_depth", "<f4", 4}, {SRT_REFL_POSITION, "position", "<f4", 4},
+                         {SRT_REFL_ALBEDO, "albedo", "<f4", 4}, {SRT_REFL_BOUNCES, "bounces", "<i4", 1}};
+    srt_reflection_params rp{};
+    srt_reflection_params_default(&rp);
+    rp.row_begin = 0, rp.row_end = H, rp.max_bounces = bounces;
+    r.renderReflectionGBuffer(rp);
+    for (const Out& o : outs) {
+        const size_t row_bytes = (size_t)W * 4 * (size_t)o.channels;
+        std::vector<char> buf(row_bytes * (size_t)H);
+        r.readReflection(o.bit, buf.data());
+        std::vector<const char*> rows((size_t)H);
+        for (int m = 0; m < H; ++m) rows[(size_t)m] = buf.data() + (size_t)(H - 1 - m) * row_bytes;
+        if (!write_npy(prefix + "_" + o.name + ".npy", o.descr, H, W, o.channels, rows, row_bytes)) return 1;
+    }
+    return 0;
+}
+
 // --rays IN.f32 --rays-out OUT.bin: closest-hit queries for the rays of a file (N records of 8 float32: origin xyzw, direction
 // xyz + t_max) against the scene; the five outputs of srt_trace_rays follow each other in OUT.bin in the order of their bits.
 // With --any-hit the rays go through srt_trace_occlusion instead and OUT.bin receives the occluded array (N int32) alone.
@@ -147,6 +173,7 @@ static void usage() {
                  "                  [--move-object IDX:DX,DY,DZ]... [--refit]] [--steps N] [--upsample PATH] [--aa K]\n"
                  "                  [--denoise-variance PATH] [--temporal-variance]\n"
                  "                  [--ao N [--ao-radius R]] [--sun-visibility] [--vis-out FILE]\n"
+                 "                  [--reflection-guides] [--reflection-bounces N] [--reflection-out PREFIX]\n"
                  "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--any-hit] [--device 0]\n"
                  "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin --radiance N [--bounces B] [--seed S] [--rays-normalize]\n"
                  "       srt_render --scene FILE --adaptive ROUNDS [--adaptive-threshold T] [--adaptive-max M] [--counts-out FILE] [--spp N] ...\n"
@@ -202,7 +229,15 @@ static void usage() {
                  "             segments of length --ao-radius (default: unbounded) at the first hit that are unoccluded; samples 1..N, --seed\n"
                  "  --sun-visibility: after the frame, per-pixel sun visibility: n . -sunDirection where the sun is seen, else 0\n"
                  "  --vis-out: receives the raw float32 planes (W x H each, scene rows), AO then SUN, whichever were asked for;\n"
-                 "             needs --ao or --sun-visibility; single device, not with --temporal\n");
+                 "             needs --ao or --sun-visibility; single device, not with --temporal\n"
+                 "  --reflection-guides: --denoise and --denoise-variance are guided by the first-hit buffers traced through chains of\n"
+                 "             mirror-like surfaces (srt_render_reflection_gbuffer, the library's thresholds) instead of the first hits: a\n"
+                 "             mirror is filtered by what is seen in it; needs one of the two; not with --devices or --temporal\n"
+                 "  --reflection-bounces N: the most reflections a chain follows (0..64; default: the library's, 8); needs --reflection-guides\n"
+                 "             or --reflection-out\n"
+                 "  --reflection-out PREFIX: also write the reflection guides as PREFIX_object.npy, PREFIX_normal_depth.npy, PREFIX_position.npy,\n"
+                 "             PREFIX_albedo.npy (as --gbuffer's) and PREFIX_bounces.npy (int32 HxW: reflections followed); not with --devices\n"
+                 "             or --temporal\n");
 }
 
 int main(int argc, char** argv) {
@@ -218,6 +253,9 @@ int main(int argc, char** argv) {
     int ao = 0;
     bool ao_given = false, sun_visibility = false;
     float ao_radius = INFINITY;
+    bool reflection_guides = false, reflection_bounces_given = false;
+    int reflection_bounces = 8;
+    std::string reflection_out;
     int temporal = 0, steps = 1, aa = 0;
     bool aa_given = false, temporal_variance = false, refit = false;
     float move[3] = {0, 0, 0}, turn_deg = 0;
@@ -278,6 +316,9 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--ao-radius")) ao_radius = std::strtof(need("--ao-radius"), nullptr);
         else if (!std::strcmp(argv[i], "--sun-visibility")) sun_visibility = true;
         else if (!std::strcmp(argv[i], "--vis-out")) vis_out = need("--vis-out");
+        else if (!std::strcmp(argv[i], "--reflection-guides")) reflection_guides = true;
+        else if (!std::strcmp(argv[i], "--reflection-bounces")) reflection_bounces = std::atoi(need("--reflection-bounces")), reflection_bounces_given = true;
+        else if (!std::strcmp(argv[i], "--reflection-out")) reflection_out = need("--reflection-out");
         else if (!std::strcmp(argv[i], "--temporal")) temporal = std::atoi(need("--temporal"));
         else if (!std::strcmp(argv[i], "--turn")) turn_deg = std::strtof(need("--turn"), nullptr);
         else if (!std::strcmp(argv[i], "--move")) {
@@ -344,6 +385,14 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--ao N (1..4096) [--ao-radius R > 0] and --sun-visibility need --vis-out FILE and the other way round; single device, "
                              "not with --temporal or --rays\n");
         return 2;
+    }
+    if (reflection_guides || reflection_bounces_given || !reflection_out.empty()) {
+        if ((reflection_guides && denoise.empty() && denoise_variance.empty()) || (reflection_bounces_given && !reflection_guides && reflection_out.empty()) ||
+            reflection_bounces < 0 || reflection_bounces > 64 || !devices.empty() || temporal || !rays_in.empty() || adaptive_given) {
+            std::fprintf(stderr, "--reflection-guides needs --denoise or --denoise-variance; --reflection-bounces N (0..64) needs --reflection-guides or "
+                                 "--reflection-out; single device, not with --devices, --temporal, --rays or --adaptive\n");
+            return 2;
+        }
     }
     if (temporal_variance && (!temporal || !devices.empty() || steps > 1 || !upsample.empty())) {
         std::fprintf(stderr, "--temporal-variance needs --temporal and works on one device only, not with --steps or --upsample\n");
@@ -614,6 +663,10 @@ int main(int argc, char** argv) {
             r.ReadFramebuffer(fb.data(), (size_t)W * 4);
             if (write_ppm(fb, upsample)) return 1;
         }
+        if (!reflection_out.empty() && write_reflection(r, reflection_out, W, H, reflection_bounces)) return 1;
+        // --reflection-guides: from here on RenderGBuffer renders the reflection guides into the G-buffer slots (--gbuffer, the
+        // visibility pass and the upsampler above have had their first hits; --aa's resolve keeps first hits by itself)
+        if (reflection_guides) r.reflectionBounces = reflection_bounces, r.reflectionGuides(true);
         if (!denoise.empty()) {
             // the guides of the whole frame, then the filter with the library's defaults; the kernel tone-maps its result into
             // the framebuffer (--out is already written), read back top-down like --out
