@@ -1264,7 +1264,8 @@ int srt_get_budget_total(srt_context* ctx, uint64_t* total);
  *    SRT_ERR_STATE when that output has neither been bound nor written yet.  srt_device_reflection gives the address of the
  *    handle's OWN buffer of one output, allocated (and zeroed) on first use, as srt_device_half: this is how the four guide outputs
  *    are handed to srt_bind_gbuffer, after which srt_denoise, srt_denoise_variance, srt_variance and srt_sample_budget are steered
- *    by the reflected geometry.  srt_temporal_accumulate reprojects with first hits; see DESIGN.md §4.25.
+ *    by the reflected geometry.  srt_temporal_accumulate reprojects with first hits, and through the chains
+ *    only with the mirror history on (the block below), which reads four of these outputs next to the first hits.
  * 7. Errors, all found before anything is touched, in this order: SRT_ERR_STATE before srt_set_scene and srt_set_camera;
  *    SRT_ERR_INVALID_ARG for an empty or out-of-range band, outputs == 0 or unknown output bits, unknown flags, reserved != 0,
  *    max_bounces outside 0..64, a NaN threshold.
@@ -1307,6 +1308,68 @@ int srt_bind_reflection(srt_context* ctx, uint32_t output, void* d_ptr);
 int srt_read_reflection(srt_context* ctx, uint32_t output, void* dst);
 int srt_device_reflection(srt_context* ctx, uint32_t output, void** d_ptr);
 int srt_get_reflection_work(srt_context* ctx, srt_reflection_work* out);
+
+/* ---- mirror history: temporal reprojection through mirror chains, by the reflection guides (ABI 7, backward compatible) -------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7, srt_temporal_params keeps its 20 bytes
+ * and there is no new SRT_TEMPORAL_* bit.  A sequence of calls that uses none of them runs what it ran before, bit for bit.
+ *
+ * srt_temporal_accumulate reprojects first hits, so a mirror's pixels carry their history along the mirror's surface while the
+ * image in the mirror moves differently: reflections lag and smear.  The mirror history is a per-context mode, off by default.
+ * With it on a pixel whose camera ray goes through J >= 1 mirrors (srt_render_reflection_gbuffer's chain) is reprojected by the
+ * virtual image of the surface at the END of its chain, accepts a history tap only if that tap looked through the same mirror
+ * over a chain of the same length at nearly the same terminal point, and otherwise restarts.  It never smears.
+ * With the mode off every call runs the kernels it ran before.  With the mode on and no pixel with J >= 1 the results are bit for
+ * bit those of the mode off.
+ *
+ * Definition.  Binary32 without contraction.  Steps 1-7 of the temporal block and 2'-6' of the moving-objects block stand; with
+ * the mode on they change as follows.
+ * Inputs.  The G-buffer slots OBJECT, NORMAL_DEPTH, POSITION must hold FIRST hits, as before: per pixel m_p, t0_p (the w of
+ *      NORMAL_DEPTH) and x0_p.  Four reflection outputs are needed besides, bound or own: SRT_REFL_OBJECT, NORMAL_DEPTH, POSITION
+ *      and BOUNCES give J_p and, for J_p >= 1, the terminal o_p, n_p, D_p (the w) and x_p.  SRT_ERR_STATE when one of the four has
+ *      neither been bound nor written, or is the handle's own and was last rendered with a camera other than the current one
+ *      (bound ones cannot be checked, as the G-buffer's).
+ *  M1. tags: tag_p = 0 for J_p = 0, tag_p = J_p * 32768 + m_p for J_p >= 1 (object indices are < 32768, J <= 64).  The stored
+ *      history keeps tag_p as int bits in the w of its normal row, a word that is 0 without the mode.
+ *  M2. pixels with J_p = 0 (first-hit misses included) are handled exactly as before, from the G-buffer slots alone, with one
+ *      more test: a tap q counts only when tag'_q == 0.  In a frame without mirrors every tag is 0 and nothing changes.
+ *  M3. pixels with J_p >= 1 and o_p == -1 (the chain leaves the scene: reflected sky, the same value in every sample) have no
+ *      history: c_p is kept bit for bit, L_p = n.  They are stored with object -1, so they are never taps; colour row (c_p, n).
+ *  M4. pixels with J_p >= 1 and o_p >= 0.  C is the current camera's position,
+ *      rho = (float)((double)radius_pixels * 2 * tan(fov_degrees * pi / 360) / H), the angle of radius_pixels pixels, computed
+ *      once per call on the host, and r_p = rho * D_p.  Two candidates are tried in order:
+ *        candidate 1:  y = C + (x0_p - C) * (D_p / t0_p) per component — the virtual point, the mirror image of the terminal
+ *                      point for a flat mirror;
+ *        candidate 2:  y = x0_p — the mirror's own surface (a strongly curved mirror keeps the image near its surface).
+ *      For each: step 2 applied to y, the window test, the 2x2 footprint of step 3.  A tap counts when it lies inside the frame,
+ *      its bilinear weight is > 0, o'_q == o_p, tag'_q == tag_p, ((dx*dx + dy*dy) + dz*dz) <= r_p * r_p with d = x'_q - x_p (the
+ *      ball replaces the plane test; written so that a NaN fails) and step 3's normal test holds against the terminal normal n_p.
+ *      The first candidate whose counted weights sum to W > 0 is blended by step 4; the second is not evaluated then.  With no
+ *      such candidate c_p is kept and L_p = n.  The stored history is (result, L), (x_p, o_p), (n_p, tag_p).
+ *  M5. moving objects: when the call uses a displacement table (some delta non-zero or some keep = 0), a pixel with J_p >= 1 has
+ *      no history for this call — the chain's inner objects are not recorded, so their motion cannot be undone.  Its history is
+ *      still stored per M3 / M4.  Pixels with J_p = 0 follow 2'-6' unchanged.
+ *  M6. motion output: (u - x, v - y, W, 0) of the candidate that was blended; when neither counted a tap, candidate 1's (u, v)
+ *      under the rule of the moving-objects block and W = 0; (0, 0, 0, 0) for a pixel of M3 or M5.  The moments history rides the
+ *      taps the colour blend counted, as before.
+ *  M7. whole frame, one launch, no atomics: the same sequence of calls gives the same bits.
+ * Not covered: refraction; glossy surfaces below the reflection pass's thresholds; chains whose inner objects move; a search
+ * beyond the two candidates.
+ *
+ * srt_mirror_history sets the mode and the radius.  SRT_ERR_INVALID_ARG for enabled outside 0..1, a radius that is NaN or <= 0,
+ * non-zero flags or reserved; the previous setting then stands.  Changing `enabled` drops the colour history and the moments
+ * history — the next srt_temporal_accumulate behaves as with SRT_TEMPORAL_RESET — because a history written under one mode
+ * carries or lacks the tags the other relies on.  Changing only the radius keeps the history.  It touches no device memory and
+ * launches nothing. */
+typedef struct srt_mirror_history_params { /* 16 bytes */
+    int32_t enabled;                       /* 0 or 1 */
+    float radius_pixels;                   /* > 0, +inf allowed (the distance test always passes), NaN refused */
+    uint32_t flags;                        /* 0 */
+    uint32_t reserved;                     /* 0 */
+} srt_mirror_history_params;
+
+/* enabled 1, radius_pixels 2.  Pure host, no device needed. */
+int srt_mirror_history_params_default(srt_mirror_history_params* out);
+int srt_mirror_history(srt_context* ctx, const srt_mirror_history_params* params);
 
 /* ---- buffers the worker writes ------------------------------------------------- */
 /* Copies memory rows [row_begin,row_end) into dst (dst points at row_begin's first

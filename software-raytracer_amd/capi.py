@@ -36,6 +36,8 @@ REFL_OBJECT, REFL_NORMAL_DEPTH, REFL_POSITION, REFL_ALBEDO, REFL_BOUNCES, REFL_G
 REFL_COUNT_WORK = 1
 REFL_MAX_BOUNCES = 64
 REFLECTION = dict(GBUFFERS, bounces=(REFL_BOUNCES, np.int32, 1))
+# reflection outputs srt_temporal_accumulate reads with the mirror history on
+MIRROR_HISTORY_GUIDES = REFL_OBJECT | REFL_NORMAL_DEPTH | REFL_POSITION | REFL_BOUNCES
 # radiance queries (srt_trace_radiance): the flags of srt_radiance_params and the sample limit
 RADIANCE_RESET, RADIANCE_NORMALIZE, RADIANCE_COUNT_WORK = 1, 2, 4
 RADIANCE_MAX_SAMPLES = 4096
@@ -87,6 +89,7 @@ EXPORTS = [
     "srt_visibility_params_default", "srt_render_visibility", "srt_bind_visibility", "srt_read_visibility", "srt_get_visibility_work",
     "srt_reflection_params_default", "srt_render_reflection_gbuffer", "srt_bind_reflection", "srt_read_reflection",
     "srt_device_reflection", "srt_get_reflection_work",
+    "srt_mirror_history_params_default", "srt_mirror_history",
     "srt_radiance_params_default", "srt_trace_radiance", "srt_bind_radiance", "srt_read_radiance", "srt_get_radiance_work",
     "srt_set_sample_counts", "srt_write_sample_counts", "srt_read_sample_counts", "srt_bind_sample_counts",
     "srt_write_sample_budget", "srt_read_sample_budget", "srt_bind_sample_budget",
@@ -253,6 +256,11 @@ class ReflectionWork(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class MirrorHistoryParams(C.Structure):
+    """srt_mirror_history_params: the mode (0 or 1) and the radius of its distance test in pixels; flags and reserved must be 0."""
+    _fields_ = [("enabled", C.c_int32), ("radius_pixels", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class RadianceParams(C.Structure):
@@ -455,6 +463,8 @@ def open_library(path):
     L.srt_read_reflection.argtypes = [ctx, C.c_uint32, C.c_void_p]
     L.srt_device_reflection.argtypes = [ctx, C.c_uint32, C.POINTER(C.c_void_p)]
     L.srt_get_reflection_work.argtypes = [ctx, C.POINTER(ReflectionWork)]
+    L.srt_mirror_history_params_default.argtypes = [C.POINTER(MirrorHistoryParams)]
+    L.srt_mirror_history.argtypes = [ctx, C.POINTER(MirrorHistoryParams)]
     L.srt_radiance_params_default.argtypes = [C.POINTER(RadianceParams)]
     L.srt_trace_radiance.argtypes = [ctx, C.POINTER(RadianceParams)]
     L.srt_bind_radiance.argtypes = [ctx, C.c_void_p]
@@ -1019,6 +1029,19 @@ class PathTracer:
             self._ck(self.L.srt_bind_gbuffer(self._h, bit, ptr))
         self._reflection_guides = bool(on)
 
+    def mirror_history(self, on=True, radius_pixels=None):
+        """srt_mirror_history: with `on`, temporal() reprojects the pixels that look through mirrors by the virtual image of what
+        they show, and accepts only history seen through the same mirror near the same terminal point (radius_pixels: the radius
+        of that test in pixels; None: the library's default).  While on, temporal(gbuffer=True) renders the first hits AND the
+        four reflection outputs the mode reads (object, normal_depth, position, bounces).  Switching drops the history."""
+        p = MirrorHistoryParams()
+        self._ck(self.L.srt_mirror_history_params_default(C.byref(p)))
+        p.enabled = 1 if on else 0
+        if radius_pixels is not None:
+            p.radius_pixels = float(radius_pixels)
+        self._ck(self.L.srt_mirror_history(self._h, C.byref(p)))
+        self._mirror_history = bool(on)
+
     def _render_guides(self, outputs, what, first_hit_only=False):
         """The guides a pass with gbuffer=True renders first: first hits, or the reflection guides while they are in use."""
         if not getattr(self, "_reflection_guides", False):
@@ -1259,11 +1282,14 @@ class PathTracer:
                  gbuffer=True):
         """srt_temporal_accumulate: blend the accumulator (which must hold `samples` samples of the current camera) with the
         history of the previous call, reprojected, in place.  Arguments left at None take TEMPORAL_DEFAULTS.  gbuffer=True
-        first enqueues render_gbuffer() for the guides it reads (current scene and camera); gbuffer=False uses the guides as
-        they are.  Asynchronous.  The next render() must reset."""
+        first enqueues render_gbuffer() for the guides it reads (current scene and camera) and, while mirror_history() is on,
+        render_reflection_gbuffer() for the four reflection outputs that mode reads; gbuffer=False uses the guides as they
+        are.  Asynchronous.  The next render() must reset."""
         p = temporal_params(samples, max_samples, plane_tolerance, normal_threshold, reset, framebuffer, lib=self.L)
         if gbuffer:
             self._render_guides(TEMPORAL_GUIDES | (GBUF_ALBEDO if getattr(self, "_moments_albedo", False) else 0), "temporal", True)
+            if getattr(self, "_mirror_history", False):
+                self.render_reflection_gbuffer(outputs=MIRROR_HISTORY_GUIDES)
         self._ck(self.L.srt_temporal_accumulate(self._h, C.byref(p)))
 
     def history_length(self):

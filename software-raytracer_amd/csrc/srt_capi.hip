@@ -35,6 +35,8 @@
 #include "srt_visibility_host.h"
 #include "srt_reflection.hip.h"
 #include "srt_reflection_host.h"
+#include "srt_mirror_history.hip.h"
+#include "srt_mirror_history_host.h"
 #include "srt_radiance.hip.h"
 #include "srt_radiance_host.h"
 #include "srt_adaptive.hip.h"
@@ -377,6 +379,11 @@ struct srt_context {
     srt::ReflectionSlots refl;
     srt::ReflectionState reflection;
     DeviceBuffer<unsigned long long> d_reflection_work;
+    // the camera each own reflection slot was last rendered with, as gbuf_own_cam (srt_temporal_accumulate with the mirror history
+    // on refuses own reflection outputs of another camera), and the mirror history's setting (srt_mirror_history_host.h)
+    srt_camera refl_own_cam[srt::REFL_SLOTS] = {};
+    bool refl_own_cam_set[srt::REFL_SLOTS] = {false, false, false, false, false};
+    srt::MirrorHistoryState mirror;
     // radiance queries (srt_trace_radiance): the own output buffer of N float4 (grown when a batch needs more) with its slot (the
     // bound buffer only); what the last trace wrote and whether it counted (srt_radiance_host.h); the sample scratch of the
     // launch's grid (grown when a launch has more workgroups); the record a counting launch adds to (srt::RAD_WORK_N words)
@@ -1903,6 +1910,8 @@ int srt_render_reflection_gbuffer(srt_context* ctx, const srt_reflection_params*
     for (int i = 0; i < srt::REFL_SLOTS; ++i)
         if (r->outputs & (1u << i))
             SRT_WRITE_TARGET(ctx, ctx->refl.out[i], ctx->d_refl_own[i], px * srt::reflection_elem_bytes(i), dst[i]);
+    for (int i = 0; i < srt::REFL_SLOTS; ++i)
+        if ((r->outputs & (1u << i)) && !ctx->refl.out[i].bound) ctx->refl_own_cam[i] = ctx->camera.cam, ctx->refl_own_cam_set[i] = true;
     if (count) {
         if (const int rc = zero_work(ctx, ctx->d_reflection_work, srt::REFL_WORK_N)) return rc;
     }
@@ -2318,6 +2327,45 @@ int srt_read_denoised(srt_context* ctx, float* dst_rgba) {
     return read_slot(ctx, ctx->dn.read_any(ctx->d_dn_own), dst_rgba, frame_pixels(ctx) * sizeof(float4), "srt_read_denoised: nothing has been denoised into this buffer yet");
 }
 
+// ---- mirror history ------------------------------------------------------------------------------------------------
+static_assert(sizeof(srt_mirror_history_params) == 16 && sizeof(srt::MirrorHistoryCall) == 16 && srt::MIRROR_MAX_BOUNCES == srt::REFL_MAX_BOUNCES,
+              "srt_mirror_history_host.h and srt_pathtrace.h disagree");
+
+int srt_mirror_history_params_default(srt_mirror_history_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    const srt::MirrorHistoryCall c = srt::mirror_history_defaults();
+    out->enabled = c.enabled, out->radius_pixels = c.radius_pixels, out->flags = c.flags, out->reserved = c.reserved;
+    return SRT_OK;
+}
+
+int srt_mirror_history(srt_context* ctx, const srt_mirror_history_params* m) {
+    if (!ctx || !m) return SRT_ERR_INVALID_ARG;
+    const srt::MirrorHistoryCall call{m->enabled, m->radius_pixels, m->flags, m->reserved};
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::mirror_history_check(call, &why))
+        return fail(ctx, (int)rs, "srt_mirror_history: %s (enabled %d, radius_pixels %g, flags 0x%x, reserved %u)", why, m->enabled,
+                    (double)m->radius_pixels, m->flags, m->reserved);
+    // a history of the other mode carries or lacks the tags this one relies on: the next call starts afresh
+    if (srt::mirror_history_set(ctx->mirror, call)) ctx->tp_valid = false, ctx->mom_history = false;
+    return SRT_OK;
+}
+
+// The reflection outputs srt_temporal_accumulate reads with the mirror history on (OBJECT, NORMAL_DEPTH, POSITION, BOUNCES), by
+// slot, bound or own, under find_guides' rule: SRT_ERR_STATE for the first that is missing or is an own one of another camera.
+static int find_reflection_guides(srt_context* ctx, const char* fn, const srt_camera* cam, const void** guide) {
+    static const char* const names[srt::REFL_SLOTS] = {"OBJECT", "NORMAL_DEPTH", "POSITION", "ALBEDO", "BOUNCES"};
+    for (int i = 0; i < srt::REFL_SLOTS; ++i) {
+        if (i == 3) continue;  // (ALBEDO is not read)
+        const srt::OutputSlot& slot = ctx->refl.out[i];
+        guide[i] = slot.bound || slot.written ? slot.current((void*)ctx->d_refl_own[i]) : nullptr;
+        if (!guide[i])
+            return fail(ctx, SRT_ERR_STATE, "%s: the reflection output %s has neither been bound nor written (srt_render_reflection_gbuffer)", fn, names[i]);
+        if (!slot.bound && (!ctx->refl_own_cam_set[i] || !same_camera(ctx->refl_own_cam[i], *cam)))
+            return fail(ctx, SRT_ERR_STATE, "%s: the reflection output %s was rendered with another camera (srt_render_reflection_gbuffer after srt_set_camera)", fn, names[i]);
+    }
+    return SRT_OK;
+}
+
 // ---- temporal reprojection ------------------------------------------------------------------------------------------
 int srt_temporal_params_default(srt_temporal_params* out) {
     if (!out) return SRT_ERR_INVALID_ARG;
@@ -2411,6 +2459,11 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
         if (const int rc = find_guides(ctx, "srt_temporal_accumulate (srt_moments_output with SRT_VARIANCE_ALBEDO)", 4, &ctx->camera.cam, g4)) return rc;
         mom_albedo = (const float4*)g4[3];
     }
+    // the mirror history reads four reflection outputs next to the first hits, under the same rule
+    const void* refl_guide[srt::REFL_SLOTS] = {};
+    if (ctx->mirror.enabled) {
+        if (const int rc = find_reflection_guides(ctx, "srt_temporal_accumulate (srt_mirror_history)", &ctx->camera.cam, refl_guide)) return rc;
+    }
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)ctx->width * (size_t)ctx->height;
     for (int i = 0; i < 2; ++i)
@@ -2452,7 +2505,24 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
         T.mom_valid = T.valid && ctx->mom_history && ctx->mom_written && ctx->mom_written_flags == ctx->mom_flags;
     }
     const dim3 grid = frame_tile_grid(ctx), block(srt::WG_THREADS);
-    if (ctx->mom_on) {
+    if (ctx->mirror.enabled) {
+        srt::MirrorLaunch M{};
+        M.T = T;
+        M.r_object = (const int32_t*)refl_guide[0];
+        M.r_normal_depth = (const float4*)refl_guide[1];
+        M.r_position = (const float4*)refl_guide[2];
+        M.r_bounces = (const int32_t*)refl_guide[4];
+        for (int i = 0; i < 3; ++i) M.cam[i] = ctx->camera.cam.position[i];
+        M.rho = srt::mirror_rho(ctx->mirror.radius_pixels, ctx->camera.cam.fov_degrees, ctx->height);
+        const int pick = (motion ? 4 : 0) | (ctx->mv_on ? 2 : 0) | (ctx->mom_on ? 1 : 0);
+        void (*const kernels[8])(srt::MirrorLaunch) = {
+            srt::temporal_mirror_kernel<false, false, false>, srt::temporal_mirror_kernel<false, false, true>,
+            srt::temporal_mirror_kernel<false, true, false>,  srt::temporal_mirror_kernel<false, true, true>,
+            srt::temporal_mirror_kernel<true, false, false>,  srt::temporal_mirror_kernel<true, false, true>,
+            srt::temporal_mirror_kernel<true, true, false>,   srt::temporal_mirror_kernel<true, true, true>};
+        hipLaunchKernelGGL(kernels[pick], grid, block, 0, ctx->stream, M);
+    }
+    else if (ctx->mom_on) {
         void (*const kernel)(srt::TemporalLaunch) =
             motion ? (ctx->mv_on ? srt::temporal_moments_kernel<true, true> : srt::temporal_moments_kernel<true, false>)
                    : (ctx->mv_on ? srt::temporal_moments_kernel<false, true> : srt::temporal_moments_kernel<false, false>);

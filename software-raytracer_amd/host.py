@@ -36,7 +36,7 @@ EXPORTS = [
     "srt_host_renderer_trace_occlusion", "srt_host_renderer_occlusion_work",
     "srt_host_renderer_render_visibility", "srt_host_renderer_read_visibility", "srt_host_renderer_visibility_work",
     "srt_host_renderer_render_reflection", "srt_host_renderer_read_reflection", "srt_host_renderer_reflection_work",
-    "srt_host_renderer_reflection_guides",
+    "srt_host_renderer_reflection_guides", "srt_host_renderer_mirror_history",
     "srt_host_renderer_trace_radiance", "srt_host_renderer_read_radiance", "srt_host_renderer_radiance_work",
     "srt_host_renderer_sample_budget", "srt_host_renderer_render_adaptive", "srt_host_renderer_set_sample_counts",
     "srt_host_renderer_read_sample_counts", "srt_host_renderer_adaptive_frame",
@@ -128,6 +128,7 @@ def load_library():
     L.srt_host_renderer_read_reflection.argtypes = [vp, C.c_uint32, C.c_void_p]
     L.srt_host_renderer_reflection_work.argtypes = [vp, C.POINTER(ReflectionWork)]
     L.srt_host_renderer_reflection_guides.argtypes = [vp, C.c_int, C.c_int]
+    L.srt_host_renderer_mirror_history.argtypes = [vp, C.c_int, C.c_float]
     L.srt_host_renderer_trace_radiance.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.POINTER(RadianceParams)]
     L.srt_host_renderer_read_radiance.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_radiance_work.argtypes = [vp, C.POINTER(RadianceWork)]
@@ -497,6 +498,12 @@ class Renderer:
         denoise_variance, the adaptive frame's variance and budget passes) get the reflection guides; the temporal frame, the
         anti-aliasing resolve, the visibility pass and the guided upsampler keep first hits.  bounces: reflectionBounces."""
         self._ck(self.L.srt_host_renderer_reflection_guides(self._h, 1 if on else 0, -1 if bounces is None else int(bounces)))
+
+    def mirror_history(self, on=True, radius_pixels=None):
+        """PathTraceRenderer::mirrorHistory: with `on`, render_temporal_frame() reprojects the pixels that look through mirrors by
+        the virtual image of what they show (it renders the reflection outputs the mode reads itself).  radius_pixels:
+        mirrorRadius (None: as it stands).  Switching drops the history."""
+        self._ck(self.L.srt_host_renderer_mirror_history(self._h, 1 if on else 0, -1.0 if radius_pixels is None else float(radius_pixels)))
 
     def visibility_work(self):
         """PathTraceRenderer::visibilityWork: the work counts of the last render_visibility(count_work=True) as a dict."""

@@ -257,6 +257,13 @@ int srt_host_renderer_reflection_guides(srt_host_renderer* h, int on, int bounce
         h->r->reflectionGuides(on != 0);
     })
 }
+// the mirror history of RenderTemporalFrame (PathTraceRenderer::mirrorHistory; radius_pixels <= 0 keeps mirrorRadius as it is)
+int srt_host_renderer_mirror_history(srt_host_renderer* h, int on, float radius_pixels) {
+    SRT_HOST_TRY(h, {
+        if (radius_pixels > 0.0f) h->r->mirrorRadius = radius_pixels;
+        h->r->mirrorHistory(on != 0);
+    })
+}
 int srt_host_renderer_read_ray_output(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->readRayOutput(output, dst)) }
 // denoiser over the whole frame with the guides as they stand (srt_denoise / srt_read_denoised)
 int srt_host_renderer_denoise(srt_host_renderer* h, const srt_denoise_params* p) { SRT_HOST_TRY(h, h->r->Denoise(*p)) }

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <optional>
 
 namespace srt_host {
 
@@ -222,6 +223,15 @@ void PathTraceRenderer::reflectionGuides(bool on) {
     reflection_guides_ = on;
 }
 
+void PathTraceRenderer::mirrorHistory(bool on) {
+    srt_mirror_history_params m{};
+    check(srt_mirror_history_params_default(&m), "srt_mirror_history_params_default");
+    m.enabled = on ? 1 : 0;
+    m.radius_pixels = mirrorRadius;
+    check(srt_mirror_history(ctx_, &m), "srt_mirror_history");
+    mirror_history_ = on;
+}
+
 void PathTraceRenderer::FirstHitScope::rebind(PathTraceRenderer& r) noexcept {
     try {
         r.bind_guides(true);
@@ -434,9 +444,13 @@ void PathTraceRenderer::RenderTemporalFrame(uint32_t spp, bool denoise) {
     if (spp == 0) throw RendererError(SRT_ERR_INVALID_ARG, "RenderTemporalFrame: spp must be >= 1");
     if (row_begin_ != 0 || row_end_ != height_)
         throw RendererError(SRT_ERR_STATE, "RenderTemporalFrame: the renderer has a row band; temporal frames cover the whole frame");
-    // the temporal pass keeps first-hit guides, also while reflectionGuides is on: it reprojects the surface seen directly, and the
-    // image in a mirror moves by another rule (out of scope); the frame's denoiser then filters with them too
-    FirstHitScope first_hits(*this);
+    // the temporal pass keeps first-hit guides in the G-buffer slots, also while reflectionGuides is on: it reprojects the surface
+    // seen directly.  Without mirrorHistory the image in a mirror is carried along with the mirror and the
+    // frame's denoiser filters with the first hits too; with it the pass reads the reflection outputs next to the first hits
+    // (§4.26) and the scope ends behind the temporal call, so that the denoiser filters with whatever reflectionGuides says.
+    const bool denoise_by_reflection = mirror_history_ && reflection_guides_;
+    std::optional<FirstHitScope> first_hits;
+    first_hits.emplace(*this);
     push_camera();
     srt_render_params p{};
     p.row_begin = 0;
@@ -450,6 +464,14 @@ void PathTraceRenderer::RenderTemporalFrame(uint32_t spp, bool denoise) {
     p.selected_object = -1;
     check(srt_render(ctx_, &p), "srt_render");
     RenderGBuffer(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION | (denoise || temporalVariance ? SRT_GBUF_ALBEDO : 0u));
+    if (mirror_history_) {
+        mirrorHistory(true);  // (mirrorRadius as it stands now; a change of the radius alone keeps the history)
+        srt_reflection_params r{};
+        check(srt_reflection_params_default(&r), "srt_reflection_params_default");
+        r.row_begin = 0, r.row_end = height_, r.max_bounces = reflectionBounces;
+        r.outputs = SRT_REFL_OBJECT | SRT_REFL_NORMAL_DEPTH | SRT_REFL_POSITION | SRT_REFL_BOUNCES | (denoise_by_reflection && denoise ? SRT_REFL_ALBEDO : 0u);
+        renderReflectionGBuffer(r);
+    }
     // the moments of the demodulated luminance: what srt_denoise_variance's defaults filter
     check(srt_moments_output(ctx_, temporalVariance ? 1 : 0, temporalVariance ? SRT_VARIANCE_ALBEDO : 0u), "srt_moments_output");
     srt_temporal_params t{};
@@ -458,6 +480,7 @@ void PathTraceRenderer::RenderTemporalFrame(uint32_t spp, bool denoise) {
     if (t.max_samples < (float)spp) t.max_samples = (float)spp;
     t.flags = (temporal_reset_ ? SRT_TEMPORAL_RESET : 0u) | (denoise ? 0u : SRT_TEMPORAL_FRAMEBUFFER);
     Temporal(t);
+    if (mirror_history_) first_hits.reset();
     if (denoise && temporalVariance) {
         DenoiseTemporalVariance(SRT_DENOISE_FRAMEBUFFER);
     } else if (denoise) {

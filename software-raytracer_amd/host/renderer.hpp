@@ -235,7 +235,17 @@ class PathTraceRenderer {
     // temporalVariance: DenoiseTemporalVariance, and the moments are kept whether or not the frame is denoised), then with
     // antialias > 0 Antialias on the denoised buffer (with `denoise`) or the accumulator.  The last step
     // writes the framebuffer.  Later RenderFrame / RenderSamples calls start a fresh accumulation.
+    // With mirrorHistory on (below) the frame also renders the four reflection outputs the mode reads (object, normal + path
+    // length, point, bounces; reflectionBounces, the library's thresholds; the handle's own buffers) next to the first hits, and
+    // the first-hit binding covers the temporal call only: while reflectionGuides is on as well, the frame's denoiser filters with
+    // the reflection guides (rendered here, albedo included).  Without mirrorHistory the function does what is said above.
     void RenderTemporalFrame(uint32_t spp, bool denoise);
+    // Mirror history (srt_mirror_history): with `on` the temporal pass reprojects pixels that look through mirrors by the virtual
+    // image of what they show.  mirrorRadius is the radius of its distance test in pixels, taken when
+    // mirrorHistory(bool) is called and again by every RenderTemporalFrame while the mode is on.  Switching drops the history.
+    void mirrorHistory(bool on);
+    bool mirrorHistory() const { return mirror_history_; }
+    float mirrorRadius = 2.0f;
     // One variance-guided denoised frame (whole frame only): push the camera, render spp / 2 samples with SRT_RENDER_RESET and
     // the frame's seed into the accumulator, spp / 2 with seed ^ 0x9E3779B9 into the handle's half buffer through
     // srt_bind_output (the binding is restored), the four guides, srt_variance with SRT_VARIANCE_MERGE, then
@@ -258,6 +268,7 @@ class PathTraceRenderer {
     void push_camera();
     srt_camera current_camera() const;
     bool reflection_guides_ = false;
+    bool mirror_history_ = false;
     void bind_guides(bool reflection);  // the four G-buffer slots: the own reflection guide buffers, or NULL
     // first hits for the lifetime of the object, whatever reflectionGuides says
     struct FirstHitScope {

@@ -171,7 +171,7 @@ static void usage() {
                  "                  [--fov 55] [--seed 0] [--device 0 | --devices 0,1,2,...] [--out frame.ppm] [--resave FILE]\n"
                  "                  [--gbuffer PREFIX] [--denoise PATH] [--temporal FRAMES [--move R,U,F] [--turn DEG]\n"
                  "                  [--move-object IDX:DX,DY,DZ]... [--refit]] [--steps N] [--upsample PATH] [--aa K]\n"
-                 "                  [--denoise-variance PATH] [--temporal-variance]\n"
+                 "                  [--denoise-variance PATH] [--temporal-variance] [--mirror-history [--mirror-radius R]]\n"
                  "                  [--ao N [--ao-radius R]] [--sun-visibility] [--vis-out FILE]\n"
                  "                  [--reflection-guides] [--reflection-bounces N] [--reflection-out PREFIX]\n"
                  "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--any-hit] [--device 0]\n"
@@ -209,6 +209,9 @@ static void usage() {
                  "             filter the --denoise frame by the per-pixel variance they give (srt_temporal_variance,\n"
                  "             srt_denoise_variance, the library's defaults) instead of srt_denoise; not with --steps, --upsample or\n"
                  "             --devices\n"
+                 "  --mirror-history: with --temporal, reproject the pixels that look through mirrors by the virtual image of what they\n"
+                 "             show and keep only history seen through the same mirror near the same point (srt_mirror_history);\n"
+                 "             --mirror-radius R: the radius of that test in pixels (> 0; default: the library's, 2)\n"
                  "  --rays:    instead of rendering a frame, answer closest-hit queries (srt_trace_rays) for the rays in IN.f32: N records\n"
                  "             of 8 float32, origin x y z w (w ignored) and direction x y z t_max; --rays-out receives the five outputs\n"
                  "             one after the other: object (N int32), normal_depth, position, albedo (N x 4 float32 each), occluded\n"
@@ -258,6 +261,8 @@ int main(int argc, char** argv) {
     std::string reflection_out;
     int temporal = 0, steps = 1, aa = 0;
     bool aa_given = false, temporal_variance = false, refit = false;
+    bool mirror_history = false, mirror_radius_given = false;
+    float mirror_radius = 2.0f;
     float move[3] = {0, 0, 0}, turn_deg = 0;
     struct ObjectMove {
         size_t index;
@@ -317,6 +322,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--sun-visibility")) sun_visibility = true;
         else if (!std::strcmp(argv[i], "--vis-out")) vis_out = need("--vis-out");
         else if (!std::strcmp(argv[i], "--reflection-guides")) reflection_guides = true;
+        else if (!std::strcmp(argv[i], "--mirror-history")) mirror_history = true;
+        else if (!std::strcmp(argv[i], "--mirror-radius")) mirror_radius = (float)std::atof(need("--mirror-radius")), mirror_radius_given = true;
         else if (!std::strcmp(argv[i], "--reflection-bounces")) reflection_bounces = std::atoi(need("--reflection-bounces")), reflection_bounces_given = true;
         else if (!std::strcmp(argv[i], "--reflection-out")) reflection_out = need("--reflection-out");
         else if (!std::strcmp(argv[i], "--temporal")) temporal = std::atoi(need("--temporal"));
@@ -393,6 +400,10 @@ int main(int argc, char** argv) {
                                  "--reflection-out; single device, not with --devices, --temporal, --rays or --adaptive\n");
             return 2;
         }
+    }
+    if ((mirror_history && !temporal) || (mirror_radius_given && (!mirror_history || !(mirror_radius > 0.0f)))) {
+        std::fprintf(stderr, "--mirror-history needs --temporal; --mirror-radius R (> 0) needs --mirror-history\n");
+        return 2;
     }
     if (temporal_variance && (!temporal || !devices.empty() || steps > 1 || !upsample.empty())) {
         std::fprintf(stderr, "--temporal-variance needs --temporal and works on one device only, not with --steps or --upsample\n");
@@ -514,6 +525,10 @@ int main(int argc, char** argv) {
         if (temporal) {
             r.antialias = aa;  // every temporal frame ends in the resolve
             r.temporalVariance = temporal_variance;  // every temporal frame keeps the moments
+            if (mirror_history) {  // every temporal frame reprojects through the mirrors
+                if (mirror_radius_given) r.mirrorRadius = mirror_radius;
+                r.mirrorHistory(true);
+            }
             // a moving camera that keeps its samples: every frame renders spp samples, reprojects the history and writes the
             // framebuffer; each frame's camera is printed exactly (%.9g round-trips a float) so that callers can replay it
             std::vector<uint32_t> fb((size_t)W * H);
