@@ -1385,6 +1385,106 @@ int srt_read_framebuffer_async(srt_context* ctx, void* dst, size_t pitch_bytes, 
 int srt_read_accumulator(srt_context* ctx, float* dst_rgba);
 int srt_write_accumulator(srt_context* ctx, const float* src_rgba);
 
+/* ---- light probes: SH-projected path-traced radiance at probe points (ABI 7, backward compatible) ------------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of
+ * them runs what it ran before, bit for bit.
+ *
+ * srt_trace_radiance says how much light arrives along a ray.  A light probe wants that for K directions around each of P
+ * points and keeps nine spherical-harmonics coefficients per point.  srt_trace_light_probes forms the P*K rays on the device
+ * from P positions and K shared directions, path-traces them with srt_trace_radiance's sample semantics and projects each
+ * probe's K radiances onto the real SH basis of bands 0..2 in a fixed summation order: 16 * (P + K) bytes go up, 144 * P bytes
+ * come back, and nothing of size P*K exists in memory unless the caller asks for the RADIANCE output.
+ *
+ * Rules.
+ * 1. Inputs.  P probe positions (srt_write_light_probes copies them from the host and waits like srt_write_rays;
+ *    srt_bind_light_probes binds a DEVICE array, does not wait and does not copy; NULL, 0 returns to the own array): float4, xyz
+ *    used, w ignored, 1 <= P <= 2^30.  K directions shared by all probes (srt_write_light_probe_directions,
+ *    srt_bind_light_probe_directions, the same way): float4, xyz = direction, w = quadrature weight (solid angle),
+ *    1 <= K <= 4096.  P*K <= 2^30, srt_trace_radiance's batch limit.  Finite positions with unit directions and finite weights are
+ *    pinned bit for bit; other inputs give some value and do not fault.
+ * 2. Ray (p, k).  Origin = position_p; direction = d_k, or float3::Normalized(d_k) with SRT_LIGHT_PROBE_NORMALIZE, as
+ *    SRT_RADIANCE_NORMALIZE (the weight passes through unscaled); ray id = id_base + p*K + k (mod 2^32).  Its radiance L_{p,k}
+ *    is by definition element p*K + k of what srt_trace_radiance writes for the explicit batch of those rays with the same
+ *    first_sample, sample_count, max_bounces, seed, id_base and RESET: rules 2, 3 and 5 of that block, all four lanes, the
+ *    alpha-NaN rule included.
+ * 3. Basis.  Evaluated on the direction as traced (x, y, z), in binary32 without contraction, in exactly this order:
+ *      b0 = 0.282095f                     b1 = 0.488603f*y                 b2 = 0.488603f*z
+ *      b3 = 0.488603f*x                   b4 = 1.092548f*(x*y)             b5 = 1.092548f*(y*z)
+ *      b6 = 0.315392f*((3.0f*(z*z)) - 1.0f)   b7 = 1.092548f*(x*z)         b8 = 0.546274f*((x*x) - (y*y))
+ * 4. Term.  t_c = w_k * b_c, and the lane value v = (L.r*t_c, L.g*t_c, L.b*t_c, t_c).  The fourth lane is the projection of the
+ *    constant 1: a caller can renormalise an imperfect direction set with it.
+ * 5. Sum order.  Directions are taken in blocks j of 64, k = 64j + l; positions l with k >= K contribute +0.0f in all four
+ *    lanes.  Within a block a pairwise tree of six levels, v'[m] = v[2m] + v[2m+1]; across blocks S = B_0, then S = S + B_j for
+ *    j = 1, 2, ... ascending.  out[p*9 + c] = S, a float4: nine float4 per probe.  No atomics reach any output: repeated calls
+ *    give the same bits.
+ * 6. Outputs, a bit mask as the G-buffer's: SRT_LIGHT_PROBE_COEFFICIENTS, P*9 float4, and SRT_LIGHT_PROBE_RADIANCE, the P*K
+ *    float4 running means L_{p,k} (element p*K + k), optional.  Each is the handle's own buffer (allocated on first use, grown
+ *    when a call needs more) or the caller's: srt_bind_light_probe_output binds a DEVICE buffer, NULL = own, under
+ *    srt_bind_ray_output's rules.  Without RADIANCE nothing of size P*K is allocated.  srt_read_light_probe_output waits, then
+ *    copies what the last srt_trace_light_probes wrote of that output, from the buffer it wrote; SRT_ERR_STATE when the last trace
+ *    did not write it.
+ * 7. RESET.  Without SRT_LIGHT_PROBE_RESET the means continue from the RADIANCE buffer, as srt_trace_radiance's rule 3.  That
+ *    needs the RADIANCE output and a previous srt_trace_light_probes of the same P and K into the buffer now bound (or the own
+ *    one); otherwise the call returns SRT_ERR_STATE.
+ * 8. Asynchrony.  As rule 7 of the radiance block; positions, directions and output buffers are those current at enqueue.
+ * 9. What it leaves alone.  Everything srt_trace_radiance leaves alone, and the ray batch of srt_write_rays / srt_bind_rays, the
+ *    radiance output and its "last trace" record, and the accumulator as well.
+ * 10. Errors, all found before anything is touched: SRT_ERR_STATE before srt_set_scene; SRT_ERR_INVALID_ARG for unknown flags or
+ *    outputs, outputs == 0, first_sample == 0, sample_count outside 1..4096, first_sample + sample_count - 1 > 2^32 - 1, a
+ *    negative max_bounces or a non-zero reserved; SRT_ERR_STATE with no positions or no directions; SRT_ERR_INVALID_ARG for K
+ *    outside 1..4096 or P*K > 2^30; SRT_ERR_STATE by rule 7.  SRT_ERR_OOM when a buffer cannot be had.
+ * 11. Work counts.  With SRT_LIGHT_PROBE_COUNT_WORK the launch counts, deterministically: its probes, its rays (P*K), its
+ *    samples (P*K*n), the lane-level GetClosestObject calls by srt_stats.rays' rule and the wave-level closest-hit invocations, as
+ *    srt_radiance_work, and the waves of the launch.  One vector atomic per wave at the end; without the flag there are no atomics
+ *    at all.  srt_get_light_probe_work waits and copies the record of the last srt_trace_light_probes; SRT_ERR_STATE unless that
+ *    trace had the flag. */
+#define SRT_LIGHT_PROBE_RESET 1u      /* sample first_sample overwrites the means; without it they continue from the RADIANCE buffer */
+#define SRT_LIGHT_PROBE_NORMALIZE 2u  /* as SRT_RADIANCE_NORMALIZE */
+#define SRT_LIGHT_PROBE_COUNT_WORK 4u /* fill srt_light_probe_work for this call */
+#define SRT_LIGHT_PROBE_COEFFICIENTS 1u /* output: P*9 float4 */
+#define SRT_LIGHT_PROBE_RADIANCE 2u     /* output: P*K float4 */
+#define SRT_LIGHT_PROBE_MAX_DIRECTIONS 4096u
+
+typedef struct srt_light_probe_params { /* 32 bytes */
+    uint32_t first_sample;              /* f0 >= 1 */
+    uint32_t sample_count;              /* n, 1..4096, f0 + n - 1 <= 2^32 - 1 */
+    int32_t max_bounces;                /* MAXBOUNCES, >= 0 */
+    uint32_t seed;
+    uint32_t id_base;                   /* ray (p, k) draws from the stream of "pixel" id_base + p*K + k (mod 2^32) */
+    uint32_t flags;                     /* SRT_LIGHT_PROBE_RESET | _NORMALIZE | _COUNT_WORK */
+    uint32_t outputs;                   /* SRT_LIGHT_PROBE_COEFFICIENTS | _RADIANCE, not 0 */
+    uint32_t reserved;                  /* 0 */
+} srt_light_probe_params;
+
+typedef struct srt_light_probe_work { /* 56 bytes */
+    uint32_t valid, reserved;         /* 1, 0 */
+    uint64_t probes, rays, samples;   /* P; P*K; P*K*n */
+    uint64_t closest_calls;           /* lane-level GetClosestObject calls by srt_stats.rays' rule: the primary counts once PER SAMPLE */
+    uint64_t wave_calls;              /* wave-level closest-hit invocations the launch executed, primaries included */
+    uint64_t waves;                   /* waves of the launch */
+} srt_light_probe_work;
+
+int srt_write_light_probes(srt_context* ctx, const float* positions, size_t count);
+int srt_bind_light_probes(srt_context* ctx, const void* d_positions, size_t count);
+int srt_write_light_probe_directions(srt_context* ctx, const float* directions, size_t count);
+int srt_bind_light_probe_directions(srt_context* ctx, const void* d_directions, size_t count);
+/* first_sample 1, sample_count 16, max_bounces 8, seed 0, id_base 0, flags SRT_LIGHT_PROBE_RESET, outputs
+ * SRT_LIGHT_PROBE_COEFFICIENTS, reserved 0 (pure host, no device needed). */
+int srt_light_probe_params_default(srt_light_probe_params* out);
+int srt_trace_light_probes(srt_context* ctx, const srt_light_probe_params* params);
+int srt_bind_light_probe_output(srt_context* ctx, uint32_t output, void* d_ptr);
+int srt_read_light_probe_output(srt_context* ctx, uint32_t output, void* dst);
+int srt_get_light_probe_work(srt_context* ctx, srt_light_probe_work* out);
+/* Pure host, no device: fills `count` float4 (count >= 1) with a spherical Fibonacci set.  For i = 0 .. count - 1, in double:
+ * z = 1 - (2i + 1) / count, r = sqrt(1 - z*z), a = i * pi * (3 - sqrt(5)), (x, y) = (r cos a, r sin a); each component is rounded
+ * once to binary32, and every weight is (float)(4 pi / count). */
+int srt_light_probe_sphere(size_t count, float* dst);
+/* Pure host, no device: the irradiance at a unit normal n from nine float4 coefficients, rgb[l] for l = 0, 1, 2 (the fourth lanes are
+ * not read).  In binary32 without contraction: with b_c(n) as in rule 3 and A_0 = 3.14159274f (pi), A_1..3 = 2.09439516f (2 pi / 3),
+ * A_4..8 = 0.785398185f (pi / 4), term_c = (A_c * coefficient_c[l]) * b_c(n); E = term_0, then E = E + term_c for c = 1 .. 8
+ * ascending; rgb[l] = E. */
+int srt_light_probe_irradiance(const float* coefficients, const float* normal, float* rgb);
+
 /* ---- multi-GPU row stripes in ONE process -----------------------------
  * The reference splits a frame over 16 worker threads that write disjoint columns of one
  * surface (Raytracer.cpp:330-342); across GPUs the split is disjoint bands of MEMORY rows,

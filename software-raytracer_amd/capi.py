@@ -41,6 +41,11 @@ MIRROR_HISTORY_GUIDES = REFL_OBJECT | REFL_NORMAL_DEPTH | REFL_POSITION | REFL_B
 # radiance queries (srt_trace_radiance): the flags of srt_radiance_params and the sample limit
 RADIANCE_RESET, RADIANCE_NORMALIZE, RADIANCE_COUNT_WORK = 1, 2, 4
 RADIANCE_MAX_SAMPLES = 4096
+# light probes (srt_trace_light_probes): the flags and outputs of srt_light_probe_params, the direction limit, float4 per probe
+LIGHT_PROBE_RESET, LIGHT_PROBE_NORMALIZE, LIGHT_PROBE_COUNT_WORK = 1, 2, 4
+LIGHT_PROBE_COEFFICIENTS, LIGHT_PROBE_RADIANCE = 1, 2
+LIGHT_PROBE_MAX_DIRECTIONS = 4096
+LIGHT_PROBE_COEFFS = 9
 # adaptive sampling (srt_render_adaptive, srt_sample_budget): the flags, the limits of max_samples / max_budget, the last frame
 ADAPTIVE_KEEP_COUNTS, ADAPTIVE_COUNT_WORK = 1, 2
 ADAPTIVE_MAX_SAMPLES = 4096
@@ -95,6 +100,9 @@ EXPORTS = [
     "srt_write_sample_budget", "srt_read_sample_budget", "srt_bind_sample_budget",
     "srt_adaptive_params_default", "srt_render_adaptive", "srt_get_adaptive_work",
     "srt_budget_params_default", "srt_sample_budget", "srt_get_budget_total",
+    "srt_write_light_probes", "srt_bind_light_probes", "srt_write_light_probe_directions", "srt_bind_light_probe_directions",
+    "srt_light_probe_params_default", "srt_trace_light_probes", "srt_bind_light_probe_output", "srt_read_light_probe_output",
+    "srt_get_light_probe_work", "srt_light_probe_sphere", "srt_light_probe_irradiance",
 ]
 
 
@@ -298,6 +306,21 @@ class BudgetParams(C.Structure):
     _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("max_budget", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class LightProbeParams(C.Structure):
+    """srt_light_probe_params: the sample range, bounces, seed, the id of ray (0, 0)'s random stream, LIGHT_PROBE_* flags and outputs."""
+    _fields_ = [("first_sample", C.c_uint32), ("sample_count", C.c_uint32), ("max_bounces", C.c_int32), ("seed", C.c_uint32),
+                ("id_base", C.c_uint32), ("flags", C.c_uint32), ("outputs", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LightProbeWork(C.Structure):
+    """srt_light_probe_work: what the last counting srt_trace_light_probes traced."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("rays", C.c_uint64), ("samples", C.c_uint64),
+                ("closest_calls", C.c_uint64), ("wave_calls", C.c_uint64), ("waves", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class UpdateInfo(C.Structure):
     """srt_update_info: what the last successful srt_update_scene did to the mesh image."""
     _fields_ = [("path", C.c_int32), ("reason", C.c_int32), ("levels", C.c_int32), ("triangles", C.c_uint32), ("nodes", C.c_uint32),
@@ -470,6 +493,17 @@ def open_library(path):
     L.srt_bind_radiance.argtypes = [ctx, C.c_void_p]
     L.srt_read_radiance.argtypes = [ctx, C.POINTER(C.c_float)]
     L.srt_get_radiance_work.argtypes = [ctx, C.POINTER(RadianceWork)]
+    L.srt_write_light_probes.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t]
+    L.srt_bind_light_probes.argtypes = [ctx, C.c_void_p, C.c_size_t]
+    L.srt_write_light_probe_directions.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t]
+    L.srt_bind_light_probe_directions.argtypes = [ctx, C.c_void_p, C.c_size_t]
+    L.srt_light_probe_params_default.argtypes = [C.POINTER(LightProbeParams)]
+    L.srt_trace_light_probes.argtypes = [ctx, C.POINTER(LightProbeParams)]
+    L.srt_bind_light_probe_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_read_light_probe_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_get_light_probe_work.argtypes = [ctx, C.POINTER(LightProbeWork)]
+    L.srt_light_probe_sphere.argtypes = [C.c_size_t, C.POINTER(C.c_float)]
+    L.srt_light_probe_irradiance.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.srt_set_sample_counts.argtypes = [ctx, C.c_uint32]
     L.srt_write_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
     L.srt_read_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
@@ -683,6 +717,36 @@ def default_environment():
     if rc:
         raise SrtError(rc, "srt_environment_default")
     return e
+
+
+def light_probe_sphere(count, lib=None):
+    """srt_light_probe_sphere: `count` spherical Fibonacci directions as a (count, 4) float32 array: a unit direction and the
+    weight 4 pi / count.  Pure host."""
+    L = lib or load_library()
+    n = int(count)
+    if n < 1:
+        raise SrtError(ERR_INVALID_ARG, "srt_light_probe_sphere: want count >= 1, got %d" % n)
+    out = np.empty((n, 4), dtype=np.float32)
+    rc = L.srt_light_probe_sphere(n, out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc:
+        raise SrtError(rc, "srt_light_probe_sphere(%d)" % n)
+    return out
+
+
+def light_probe_irradiance(coefficients, normal, lib=None):
+    """srt_light_probe_irradiance: the irradiance (r, g, b) at the unit `normal` from a probe's coefficients, an array (9, 4)
+    float32 as light_probe_coefficients() returns per probe.  Pure host."""
+    L = lib or load_library()
+    c = np.ascontiguousarray(coefficients, dtype=np.float32)
+    n = np.ascontiguousarray(normal, dtype=np.float32).reshape(-1)
+    if c.shape != (LIGHT_PROBE_COEFFS, 4) or n.shape[0] < 3:
+        raise ValueError("light_probe_irradiance: coefficients %s and normal %s, want (9, 4) and (3,)" % (c.shape, n.shape))
+    out = np.empty(3, dtype=np.float32)
+    f = C.POINTER(C.c_float)
+    rc = L.srt_light_probe_irradiance(c.ctypes.data_as(f), n.ctypes.data_as(f), out.ctypes.data_as(f))
+    if rc:
+        raise SrtError(rc, "srt_light_probe_irradiance")
+    return out
 
 
 def default_camera(fov=55):
@@ -1200,6 +1264,105 @@ class PathTracer:
         """srt_get_adaptive_work: the work counts of the last render_adaptive(count_work=True) as a dict.  Waits."""
         w = AdaptiveWork()
         self._ck(self.L.srt_get_adaptive_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    # ---- light probes ----------------------------------------------------------------------
+    def _light_probe_input(self, what, a, write, bind, limit):
+        """Make `a` the current positions or directions: a host array (N, 4) is written, a device tensor bound."""
+        kind, arr, n = self._ray_array(what, a)
+        if n > limit:
+            raise ValueError("%s: %d elements, want 1 .. %d" % (what, n, limit))
+        if kind == "host":
+            self._ck(write(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n))
+            return n, None
+        self._ck(bind(self._h, C.c_void_p(arr.data_ptr()), n))
+        return n, arr  # (a bound tensor stays referenced for as long as it is bound)
+
+    def trace_light_probes(self, positions=None, directions=None, samples=None, bounces=None, seed=0, first_sample=1, reset=True, id_base=0,
+                           normalize=False, count_work=False, coefficients=True, radiance=False, flags=0):
+        """srt_trace_light_probes: for each of P probe positions, the running mean of `samples` path-traced samples (default 16) of
+        `bounces` bounces (default 8) along each of K shared directions, projected onto the nine SH coefficients of bands 0..2.
+        `positions`: numpy (P, 4) float32 (written) or a torch tensor on this tracer's device (bound); None: the current ones.
+        `directions`: the same, (K, 4) with the quadrature weight in w; an int K: light_probe_sphere(K); None: the current ones.
+        Ray (p, k) draws from the stream of pixel id_base + p*K + k.  coefficients / radiance: the outputs (light_probe_coefficients(),
+        light_probe_radiance()); reset=False continues the means the RADIANCE buffer holds; normalize: SRT_LIGHT_PROBE_NORMALIZE;
+        count_work: SRT_LIGHT_PROBE_COUNT_WORK (light_probe_work() then reads the record).  Asynchronous, like render()."""
+        L = self.L
+        if positions is not None:
+            self._probe_count, self._probe_bound = self._light_probe_input("trace_light_probes(positions)", positions, L.srt_write_light_probes,
+                                                                           L.srt_bind_light_probes, 1 << 30)
+        if directions is not None:
+            if isinstance(directions, (int, np.integer)):
+                directions = light_probe_sphere(int(directions), lib=L)
+            self._probe_dir_count, self._probe_dir_bound = self._light_probe_input("trace_light_probes(directions)", directions,
+                                                                                   L.srt_write_light_probe_directions,
+                                                                                   L.srt_bind_light_probe_directions, LIGHT_PROBE_MAX_DIRECTIONS)
+        p = LightProbeParams()
+        self._ck(L.srt_light_probe_params_default(C.byref(p)))
+        if samples is not None:
+            p.sample_count = int(samples)
+        if bounces is not None:
+            p.max_bounces = int(bounces)
+        p.first_sample, p.seed, p.id_base = int(first_sample), int(seed) & 0xFFFFFFFF, int(id_base) & 0xFFFFFFFF
+        p.flags = (int(flags) | (LIGHT_PROBE_RESET if reset else 0) | (LIGHT_PROBE_NORMALIZE if normalize else 0) |
+                   (LIGHT_PROBE_COUNT_WORK if count_work else 0))
+        p.outputs = (LIGHT_PROBE_COEFFICIENTS if coefficients else 0) | (LIGHT_PROBE_RADIANCE if radiance else 0)
+        np_, nk = getattr(self, "_probe_count", None), getattr(self, "_probe_dir_count", None)
+        if np_ is not None and nk is not None:
+            bound = self.__dict__.get("_probe_out_bound", {})
+            for bit, need in ((LIGHT_PROBE_COEFFICIENTS, np_ * LIGHT_PROBE_COEFFS), (LIGHT_PROBE_RADIANCE, np_ * nk)):
+                t = bound.get(bit)
+                if (p.outputs & bit) and t is not None and t.shape[0] < need:
+                    raise ValueError("trace_light_probes: the bound tensor holds %d elements, the call writes %d" % (t.shape[0], need))
+        self._ck(L.srt_trace_light_probes(self._h, C.byref(p)))
+        self._probes_traced = (np_, nk)
+
+    def bind_light_probe_output(self, output, tensor):
+        """srt_bind_light_probe_output: write output "coefficients" (P*9 float4) or "radiance" (P*K float4) into a torch tensor (M, 4)
+        float32 on this tracer's device, contiguous, M at least that many (checked by trace_light_probes); None: the handle's own
+        buffer.  The caller keeps the tensor alive until the traces have finished."""
+        bit = {"coefficients": LIGHT_PROBE_COEFFICIENTS, "radiance": LIGHT_PROBE_RADIANCE}.get(output, output)
+        if tensor is not None:
+            import torch
+
+            if not isinstance(tensor, torch.Tensor):
+                raise TypeError("bind_light_probe_output: expected a torch.Tensor, got %s" % type(tensor).__name__)
+            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
+            if m < 1:
+                raise ValueError("bind_light_probe_output: shape %s, want at least one element" % (tuple(tensor.shape),))
+            ptr = self._tensor_ptr("bind_light_probe_output", tensor, np.float32, (m, 4))
+        else:
+            ptr = None
+        self._ck(self.L.srt_bind_light_probe_output(self._h, int(bit), ptr))
+        bound = self.__dict__.setdefault("_probe_out_bound", {})
+        if tensor is None:
+            bound.pop(bit, None)
+        else:
+            bound[bit] = tensor
+
+    def _light_probe_counts(self, what, probes, directions):
+        t = getattr(self, "_probes_traced", None) or (None, None)
+        p = probes if probes is not None else t[0]
+        k = directions if directions is not None else t[1]
+        if p is None or k is None:
+            raise SrtError(ERR_STATE, "%s: no trace_light_probes() yet" % what)
+        return int(p), int(k)
+
+    def light_probe_coefficients(self, probes=None):
+        """srt_read_light_probe_output(COEFFICIENTS): the (P, 9, 4) float32 coefficients of the last trace_light_probes().  Waits."""
+        p, _ = self._light_probe_counts("light_probe_coefficients()", probes, 1)
+        return self._read_image(self.L.srt_read_light_probe_output, (p, LIGHT_PROBE_COEFFS, 4), np.float32, LIGHT_PROBE_COEFFICIENTS)
+
+    def light_probe_radiance(self, probes=None, directions=None):
+        """srt_read_light_probe_output(RADIANCE): the (P, K, 4) float32 running means of the last trace_light_probes(radiance=True).
+        Waits."""
+        p, k = self._light_probe_counts("light_probe_radiance()", probes, directions)
+        return self._read_image(self.L.srt_read_light_probe_output, (p, k, 4), np.float32, LIGHT_PROBE_RADIANCE)
+
+    def light_probe_work(self):
+        """srt_get_light_probe_work: the work counts of the last trace_light_probes(count_work=True) as a dict.  Waits."""
+        w = LightProbeWork()
+        self._ck(self.L.srt_get_light_probe_work(self._h, C.byref(w)))
         return w.as_dict()
 
     def ray_output(self, name, count=None):

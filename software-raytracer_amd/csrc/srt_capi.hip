@@ -39,6 +39,8 @@
 #include "srt_mirror_history_host.h"
 #include "srt_radiance.hip.h"
 #include "srt_radiance_host.h"
+#include "srt_light_probes.hip.h"
+#include "srt_light_probes_host.h"
 #include "srt_adaptive.hip.h"
 #include "srt_adaptive_host.h"
 #include "srt_launch_shape.h"
@@ -392,6 +394,18 @@ struct srt_context {
     srt::RadianceState radiance;
     DeviceBuffer<float4> d_radiance_rows;
     DeviceBuffer<unsigned long long> d_radiance_work;
+    // light probes (srt_trace_light_probes): the own position and direction arrays (srt_write_light_probes,
+    // srt_write_light_probe_directions; they grow on demand); one own output buffer per SRT_LIGHT_PROBE_* output bit (grown when
+    // a call needs more) with its slot (the bound buffer only); which arrays are current, what the last trace wrote and whether
+    // it counted (srt_light_probes_host.h); the block sums of a projection over more than one block of 64 directions; the record
+    // a counting launch adds to (srt::LP_WORK_N words).  The sample scratch is the radiance pass's, d_radiance_rows.
+    DeviceBuffer<float4> d_probe_position;
+    DeviceBuffer<float4> d_probe_direction;
+    DeviceBuffer<float4> d_probe_out_own[srt::LIGHT_PROBE_SLOTS];
+    srt::OutputSlot probe_out[srt::LIGHT_PROBE_SLOTS];
+    srt::LightProbeState probes;
+    DeviceBuffer<float4> d_probe_partial;
+    DeviceBuffer<unsigned long long> d_probe_work;
     // adaptive sampling (srt_render_adaptive, srt_sample_budget): the per-pixel sample counts and sample budget, W*H uint32 each,
     // own buffer and slot; whether the last adaptive render counted and whether a budget pass has run (srt_adaptive_host.h); the
     // tile ticket of a launch (zeroed on the stream in front of it); the record a counting launch adds to (srt::ADP_WORK_N words);
@@ -2059,6 +2073,174 @@ int srt_get_radiance_work(srt_context* ctx, srt_radiance_work* out) {
     out->valid = 1, out->reserved = 0;
     out->rays = w[srt::RAD_WORK_RAYS], out->samples = w[srt::RAD_WORK_SAMPLES];
     out->closest_calls = w[srt::RAD_WORK_CLOSEST], out->wave_calls = w[srt::RAD_WORK_WAVE_CALLS];
+    return SRT_OK;
+}
+
+// ---- light probes --------------------------------------------------------------------------------------------------
+static_assert(SRT_LIGHT_PROBE_RESET == srt::LIGHT_PROBE_FLAG_RESET && SRT_LIGHT_PROBE_NORMALIZE == srt::LIGHT_PROBE_FLAG_NORMALIZE &&
+              SRT_LIGHT_PROBE_COUNT_WORK == srt::LIGHT_PROBE_FLAG_COUNT_WORK && SRT_LIGHT_PROBE_RESET == SRT_RENDER_RESET &&
+              SRT_LIGHT_PROBE_COEFFICIENTS == srt::LIGHT_PROBE_OUT_COEFFICIENTS && SRT_LIGHT_PROBE_RADIANCE == srt::LIGHT_PROBE_OUT_RADIANCE &&
+              SRT_LIGHT_PROBE_MAX_DIRECTIONS == srt::LIGHT_PROBE_MAX_DIRECTIONS && sizeof(srt_light_probe_params) == 32 &&
+              sizeof(srt::LightProbeCall) == 32 && sizeof(srt_light_probe_work) == 56 && (int)srt::LIGHT_PROBE_COEFFS == (int)srt::LP_COEFFS &&
+              srt::LP_WORK_N == 6,
+              "srt_light_probes_host.h, srt_light_probes.hip.h and srt_pathtrace.h disagree");
+
+// srt_write_light_probes / srt_write_light_probe_directions: `count` float4 into the own array, which becomes the current one
+static int write_light_probe_input(srt_context* ctx, srt::LightProbeInput& in, DeviceBuffer<float4>& own, const float* src, size_t count, size_t limit,
+                                   const char* who) {
+    if (count < 1 || count > limit) return fail(ctx, SRT_ERR_INVALID_ARG, "%s: %zu elements: want 1 .. %zu", who, count, limit);
+    if (const int rc = finish_stream(ctx)) return rc;  // (traces in flight read the own array; it may be re-allocated below)
+    const size_t bytes = count * sizeof(float4);
+    if (own.bytes() < bytes) {
+        in.own_count = 0;  // (a failed allocation leaves no own array)
+        SRT_HIP(ctx, own.ensure(bytes));
+    }
+    SRT_HIP(ctx, hipMemcpy(own, src, bytes, hipMemcpyHostToDevice));
+    srt::light_probe_written(in, count);
+    return SRT_OK;
+}
+
+int srt_write_light_probes(srt_context* ctx, const float* positions, size_t count) {
+    if (!ctx || !positions) return SRT_ERR_INVALID_ARG;
+    return write_light_probe_input(ctx, ctx->probes.positions, ctx->d_probe_position, positions, count, srt::LIGHT_PROBE_MAX_RAYS, "srt_write_light_probes");
+}
+
+int srt_bind_light_probes(srt_context* ctx, const void* d_positions, size_t count) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    // (no synchronisation: enqueued traces keep the array they were given, as srt_bind_rays)
+    if (srt::light_probe_bind(ctx->probes.positions, d_positions, count, srt::LIGHT_PROBE_MAX_RAYS) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_light_probes: want a device array and 1 .. 2^30 positions, or NULL, 0 (got %zu)", count);
+    return SRT_OK;
+}
+
+int srt_write_light_probe_directions(srt_context* ctx, const float* directions, size_t count) {
+    if (!ctx || !directions) return SRT_ERR_INVALID_ARG;
+    return write_light_probe_input(ctx, ctx->probes.directions, ctx->d_probe_direction, directions, count, srt::LIGHT_PROBE_MAX_DIRECTIONS,
+                                   "srt_write_light_probe_directions");
+}
+
+int srt_bind_light_probe_directions(srt_context* ctx, const void* d_directions, size_t count) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    if (srt::light_probe_bind(ctx->probes.directions, d_directions, count, srt::LIGHT_PROBE_MAX_DIRECTIONS) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_light_probe_directions: want a device array and 1 .. 4096 directions, or NULL, 0 (got %zu)", count);
+    return SRT_OK;
+}
+
+int srt_light_probe_params_default(srt_light_probe_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::LightProbeCall c;
+    srt::light_probe_call_default(c);
+    out->first_sample = c.first_sample, out->sample_count = c.sample_count, out->max_bounces = c.max_bounces;
+    out->seed = c.seed, out->id_base = c.id_base, out->flags = c.flags, out->outputs = c.outputs, out->reserved = c.reserved;
+    return SRT_OK;
+}
+
+// ... in front of the re-allocation of own light-probe output `i`: earlier traces may still be writing it
+static int light_probe_output_released(srt_context* ctx, int i) {
+    if (const int rc = finish_stream(ctx)) return rc;
+    srt::light_probe_output_released(ctx->probes, i, (void*)ctx->d_probe_out_own[i]);
+    return SRT_OK;
+}
+
+int srt_trace_light_probes(srt_context* ctx, const srt_light_probe_params* t) {
+    if (!ctx || !t) return SRT_ERR_INVALID_ARG;
+    const srt::LightProbeCall call{t->first_sample, t->sample_count, t->max_bounces, t->seed, t->id_base, t->flags, t->outputs, t->reserved};
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::light_probe_check_trace(ctx->probes, ctx->scene_set, call, current(ctx->probe_out[1], ctx->d_probe_out_own[1]), &why))
+        return fail(ctx, (int)rs, "srt_trace_light_probes: %s (first_sample %u, sample_count %u, max_bounces %d, flags 0x%x, outputs 0x%x, reserved %u)", why,
+                    t->first_sample, t->sample_count, t->max_bounces, t->flags, t->outputs, t->reserved);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t np = ctx->probes.positions.count(), nk = ctx->probes.directions.count();
+    const size_t J = srt::light_probe_blocks(nk);
+    const bool count = (t->flags & SRT_LIGHT_PROBE_COUNT_WORK) != 0;
+    const bool coefficients = (t->outputs & SRT_LIGHT_PROBE_COEFFICIENTS) != 0;
+    float4* dst[srt::LIGHT_PROBE_SLOTS] = {nullptr, nullptr};
+    for (int i = 0; i < srt::LIGHT_PROBE_SLOTS; ++i)
+        if (t->outputs & (1u << i))
+            SRT_WRITE_TARGET_AFTER(ctx, ctx->probe_out[i], ctx->d_probe_out_own[i], srt::light_probe_elems(i, np, nk) * sizeof(float4), dst[i],
+                                   light_probe_output_released(ctx, i));
+    const size_t partial = coefficients ? srt::light_probe_partial_bytes(np, nk) : 0;
+    if (ctx->d_probe_partial.bytes() < partial) {
+        if (const int rc = finish_stream(ctx)) return rc;
+        SRT_HIP(ctx, ctx->d_probe_partial.ensure(partial));
+    }
+    srt::KernelParams K;
+    const KernelSetup ks = scene_kernel_params(ctx, 0, ctx->height, K);
+    // (the fields accumulate_sample and the bounce loop read)
+    K.first_sample = t->first_sample, K.sample_count = t->sample_count, K.max_bounces = t->max_bounces, K.seed = t->seed;
+    if (t->flags & SRT_LIGHT_PROBE_RESET) K.flags |= SRT_RENDER_RESET;
+    const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::light_probe_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    // the grid first: the sample scratch is sized by it
+    const unsigned wgs = srt::light_probe_grid(np, nk, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
+    const size_t scratch = srt::light_probe_scratch_bytes(wgs, srt::OUT_WG_UNITS);
+    if (ctx->d_radiance_rows.bytes() < scratch) {
+        if (const int rc = finish_stream(ctx)) return rc;
+        SRT_HIP(ctx, ctx->d_radiance_rows.ensure(scratch));
+    }
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_probe_work, srt::LP_WORK_N)) return rc;
+    }
+    srt::LightProbeIO io{};
+    io.position = ctx->probes.positions.bound ? (const float4*)ctx->probes.positions.bound : (const float4*)ctx->d_probe_position;
+    io.direction = ctx->probes.directions.bound ? (const float4*)ctx->probes.directions.bound : (const float4*)ctx->d_probe_direction;
+    io.probes = (uint32_t)np, io.directions = (uint32_t)nk, io.blocks = (uint32_t)J;
+    io.normalize = (t->flags & SRT_LIGHT_PROBE_NORMALIZE) ? 1u : 0u;
+    io.id_base = t->id_base;
+    io.coefficients = J == 1 ? dst[0] : nullptr;
+    io.partial = J > 1 && coefficients ? (float4*)ctx->d_probe_partial : nullptr;
+    io.radiance = dst[1];
+    io.rows = ctx->d_radiance_rows;
+    io.work = count ? (unsigned long long*)ctx->d_probe_work : nullptr;
+    if (const int rc = launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
+    if (J > 1 && coefficients) {  // the block sums of every probe, added in ascending block order
+        const size_t elems = np * (size_t)srt::LP_COEFFS;
+        hipLaunchKernelGGL(srt::light_probe_sum_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->d_probe_partial,
+                           dst[0], elems, (uint32_t)J);
+        SRT_HIP(ctx, hipGetLastError());
+    }
+    void* const wrote[srt::LIGHT_PROBE_SLOTS] = {dst[0], dst[1]};
+    srt::light_probe_traced(ctx->probes, np, nk, t->outputs, wrote, t->flags);
+    return SRT_OK;
+}
+
+int srt_bind_light_probe_output(srt_context* ctx, uint32_t output, void* d_ptr) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    const int i = srt::light_probe_slot(output);
+    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_light_probe_output: output 0x%x is not a single SRT_LIGHT_PROBE_COEFFICIENTS / _RADIANCE bit", output);
+    return ctx->probe_out[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued traces keep the buffer they were given, as srt_bind_ray_output)
+}
+
+int srt_read_light_probe_output(srt_context* ctx, uint32_t output, void* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    const srt::RaysStatus rs = srt::light_probe_check_read(ctx->probes, output, &src, &bytes);
+    if (rs == srt::RAYS_INVALID_ARG)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_light_probe_output: output 0x%x is not a single SRT_LIGHT_PROBE_COEFFICIENTS / _RADIANCE bit", output);
+    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, bytes, "srt_read_light_probe_output: output 0x%x was not written by the last srt_trace_light_probes", output);
+}
+
+int srt_get_light_probe_work(srt_context* ctx, srt_light_probe_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::light_probe_check_work(ctx->probes) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_light_probe_work: the last srt_trace_light_probes did not ask for SRT_LIGHT_PROBE_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::LP_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_probe_work, w, srt::LP_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0;
+    out->probes = w[srt::LP_WORK_PROBES], out->rays = w[srt::LP_WORK_RAYS], out->samples = w[srt::LP_WORK_SAMPLES];
+    out->closest_calls = w[srt::LP_WORK_CLOSEST], out->wave_calls = w[srt::LP_WORK_WAVE_CALLS], out->waves = w[srt::LP_WORK_WAVES];
+    return SRT_OK;
+}
+
+int srt_light_probe_sphere(size_t count, float* dst) {
+    if (count < 1 || !dst) return SRT_ERR_INVALID_ARG;
+    srt::light_probe_sphere(count, dst);
+    return SRT_OK;
+}
+
+int srt_light_probe_irradiance(const float* coefficients, const float* normal, float* rgb) {
+    if (!coefficients || !normal || !rgb) return SRT_ERR_INVALID_ARG;
+    srt::light_probe_irradiance(coefficients, normal, rgb);
     return SRT_OK;
 }
 

@@ -9,6 +9,8 @@ import numpy as np
 
 from .capi import (REFL_ALL, REFL_COUNT_WORK, REFLECTION, ReflectionParams, ReflectionWork, reflection_outputs, ADAPTIVE_COUNT_WORK, ADAPTIVE_KEEP_COUNTS, BUDGET_ALBEDO, AdaptiveParams, BudgetParams, RADIANCE_COUNT_WORK, RADIANCE_NORMALIZE, RADIANCE_RESET, RadianceParams, RadianceWork, VIS_AO, VIS_COUNT_WORK, VIS_SUN, VISIBILITY, VisibilityParams, VisibilityWork, OCCLUSION_COUNT_WORK, OCCLUSION_NORMALIZE, OcclusionWork, RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
                    TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
+from .capi import (LIGHT_PROBE_COEFFICIENTS, LIGHT_PROBE_COEFFS, LIGHT_PROBE_COUNT_WORK, LIGHT_PROBE_NORMALIZE, LIGHT_PROBE_RADIANCE, LIGHT_PROBE_RESET,
+                   LightProbeParams, LightProbeWork, light_probe_irradiance, light_probe_sphere)  # noqa: F401
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_PKG, "libsrt_host.so")
@@ -38,6 +40,7 @@ EXPORTS = [
     "srt_host_renderer_render_reflection", "srt_host_renderer_read_reflection", "srt_host_renderer_reflection_work",
     "srt_host_renderer_reflection_guides", "srt_host_renderer_mirror_history",
     "srt_host_renderer_trace_radiance", "srt_host_renderer_read_radiance", "srt_host_renderer_radiance_work",
+    "srt_host_renderer_trace_light_probes", "srt_host_renderer_read_light_probe_output", "srt_host_renderer_light_probe_work",
     "srt_host_renderer_sample_budget", "srt_host_renderer_render_adaptive", "srt_host_renderer_set_sample_counts",
     "srt_host_renderer_read_sample_counts", "srt_host_renderer_adaptive_frame",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
@@ -132,6 +135,9 @@ def load_library():
     L.srt_host_renderer_trace_radiance.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.POINTER(RadianceParams)]
     L.srt_host_renderer_read_radiance.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_radiance_work.argtypes = [vp, C.POINTER(RadianceWork)]
+    L.srt_host_renderer_trace_light_probes.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(LightProbeParams)]
+    L.srt_host_renderer_read_light_probe_output.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float)]
+    L.srt_host_renderer_light_probe_work.argtypes = [vp, C.POINTER(LightProbeWork)]
     L.srt_host_renderer_sample_budget.argtypes = [vp, C.POINTER(BudgetParams), C.POINTER(C.c_uint64)]
     L.srt_host_renderer_render_adaptive.argtypes = [vp, C.POINTER(AdaptiveParams)]
     L.srt_host_renderer_set_sample_counts.argtypes = [vp, C.c_uint32]
@@ -416,6 +422,46 @@ class Renderer:
         out = np.empty((o.shape[0], 4), dtype=np.float32)
         self._ck(self.L.srt_host_renderer_read_radiance(self._h, out.ctypes.data_as(f)))
         return out
+
+    def trace_light_probes(self, positions, directions, samples=16, bounces=8, seed=0, first_sample=1, reset=True, id_base=0, normalize=False,
+                           count_work=False, radiance=False):
+        """PathTraceRenderer::traceLightProbes + readLightProbeOutput: copy P positions and K directions (host arrays (N, 4) float32;
+        directions: an int K for light_probe_sphere(K)), trace srt_trace_light_probes against the renderer's scene and return the
+        (P, 9, 4) float32 SH coefficients; light_probe_radiance() then returns the (P, K, 4) running means when radiance=True.
+        reset=False continues the means of the handle's RADIANCE buffer (needs radiance=True).  Waits."""
+        if isinstance(directions, (int, np.integer)):
+            directions = light_probe_sphere(int(directions))
+        o = np.ascontiguousarray(positions, dtype=np.float32)
+        d = np.ascontiguousarray(directions, dtype=np.float32)
+        if o.ndim != 2 or o.shape[1] != 4 or o.shape[0] < 1 or d.ndim != 2 or d.shape[1] != 4 or d.shape[0] < 1:
+            raise ValueError("trace_light_probes: positions %s and directions %s, want (P, 4) and (K, 4) arrays" % (o.shape, d.shape))
+        p = LightProbeParams(int(first_sample), int(samples), int(bounces), int(seed) & 0xFFFFFFFF, int(id_base) & 0xFFFFFFFF,
+                             (LIGHT_PROBE_RESET if reset else 0) | (LIGHT_PROBE_NORMALIZE if normalize else 0) |
+                             (LIGHT_PROBE_COUNT_WORK if count_work else 0), LIGHT_PROBE_COEFFICIENTS | (LIGHT_PROBE_RADIANCE if radiance else 0), 0)
+        f = C.POINTER(C.c_float)
+        self._ck(self.L.srt_host_renderer_trace_light_probes(self._h, o.ctypes.data_as(f), o.shape[0], d.ctypes.data_as(f), d.shape[0], C.byref(p)))
+        self._probes_traced = (o.shape[0], d.shape[0])
+        out = np.empty((o.shape[0], LIGHT_PROBE_COEFFS, 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_light_probe_output(self._h, LIGHT_PROBE_COEFFICIENTS, out.ctypes.data_as(f)))
+        return out
+
+    def light_probe_coefficients(self):
+        """PathTraceRenderer::readLightProbeOutput(COEFFICIENTS): the (P, 9, 4) float32 coefficients of the last trace_light_probes()."""
+        out = np.empty((self._probes_traced[0], LIGHT_PROBE_COEFFS, 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_light_probe_output(self._h, LIGHT_PROBE_COEFFICIENTS, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def light_probe_radiance(self):
+        """PathTraceRenderer::readLightProbeOutput(RADIANCE): the (P, K, 4) float32 means of the last trace_light_probes(radiance=True)."""
+        out = np.empty(self._probes_traced + (4,), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_light_probe_output(self._h, LIGHT_PROBE_RADIANCE, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def light_probe_work(self):
+        """PathTraceRenderer::lightProbeWork: the work counts of the last trace_light_probes(count_work=True) as a dict."""
+        w = LightProbeWork()
+        self._ck(self.L.srt_host_renderer_light_probe_work(self._h, C.byref(w)))
+        return w.as_dict()
 
     def radiance_work(self):
         """PathTraceRenderer::radianceWork: the work counts of the last trace_radiance(count_work=True) as a dict."""

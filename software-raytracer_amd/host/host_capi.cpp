@@ -227,6 +227,13 @@ int srt_host_renderer_trace_radiance(srt_host_renderer* h, const float* origins,
 }
 int srt_host_renderer_read_radiance(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->readRadiance(dst)) }
 int srt_host_renderer_radiance_work(srt_host_renderer* h, srt_radiance_work* out) { SRT_HOST_TRY(h, *out = h->r->radianceWork()) }
+// light probes against the renderer's scene (srt_write_light_probes + srt_write_light_probe_directions + srt_trace_light_probes)
+int srt_host_renderer_trace_light_probes(srt_host_renderer* h, const float* positions, size_t probes, const float* directions, size_t direction_count,
+                                         const srt_light_probe_params* p) {
+    SRT_HOST_TRY(h, h->r->traceLightProbes(positions, probes, directions, direction_count, *p))
+}
+int srt_host_renderer_read_light_probe_output(srt_host_renderer* h, uint32_t output, float* dst) { SRT_HOST_TRY(h, h->r->readLightProbeOutput(output, dst)) }
+int srt_host_renderer_light_probe_work(srt_host_renderer* h, srt_light_probe_work* out) { SRT_HOST_TRY(h, *out = h->r->lightProbeWork()) }
 // adaptive sampling on the handle's buffers as they stand (srt_sample_budget + srt_get_budget_total, srt_render_adaptive; a band
 // of [0, 0) means the renderer's own), and the two-half workflow (PathTraceRenderer::renderAdaptiveFrame; counts may be NULL)
 int srt_host_renderer_sample_budget(srt_host_renderer* h, const srt_budget_params* p, uint64_t* total) { SRT_HOST_TRY(h, *total = h->r->sampleBudget(*p)) }

@@ -307,6 +307,23 @@ srt_radiance_work PathTraceRenderer::radianceWork() {
     return w;
 }
 
+void PathTraceRenderer::traceLightProbes(const float* positions, size_t probes, const float* directions, size_t direction_count,
+                                         const srt_light_probe_params& params) {
+    check(srt_write_light_probes(ctx_, positions, probes), "srt_write_light_probes");
+    check(srt_write_light_probe_directions(ctx_, directions, direction_count), "srt_write_light_probe_directions");
+    check(srt_trace_light_probes(ctx_, &params), "srt_trace_light_probes");
+}
+
+void PathTraceRenderer::readLightProbeOutput(uint32_t output, float* dst) {
+    check(srt_read_light_probe_output(ctx_, output, dst), "srt_read_light_probe_output");
+}
+
+srt_light_probe_work PathTraceRenderer::lightProbeWork() {
+    srt_light_probe_work w{};
+    check(srt_get_light_probe_work(ctx_, &w), "srt_get_light_probe_work");
+    return w;
+}
+
 uint64_t PathTraceRenderer::sampleBudget(const srt_budget_params& params) {
     check(srt_sample_budget(ctx_, &params), "srt_sample_budget");
     uint64_t total = 0;

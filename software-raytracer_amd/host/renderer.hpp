@@ -165,6 +165,14 @@ class PathTraceRenderer {
     void traceRadiance(const float* origins, const float* directions, size_t count, const srt_radiance_params& params);
     void readRadiance(float* dst_rgba);
     srt_radiance_work radianceWork();
+    // Light probes (srt_write_light_probes + srt_write_light_probe_directions + srt_trace_light_probes): `probes` positions and
+    // `directions` shared directions (float4 each; direction.w is the quadrature weight), path-traced as traceRadiance's rays and
+    // projected onto nine SH coefficients per probe.  Asynchronous once the arrays are copied; readLightProbeOutput waits and copies
+    // one output (SRT_LIGHT_PROBE_COEFFICIENTS: probes * 9 float4; SRT_LIGHT_PROBE_RADIANCE: probes * directions float4) of the
+    // last traceLightProbes; lightProbeWork waits and returns the work counts of a trace that had SRT_LIGHT_PROBE_COUNT_WORK.
+    void traceLightProbes(const float* positions, size_t probes, const float* directions, size_t direction_count, const srt_light_probe_params& params);
+    void readLightProbeOutput(uint32_t output, float* dst);
+    srt_light_probe_work lightProbeWork();
     // Adaptive sampling (srt_sample_budget, srt_render_adaptive), on the handle's buffers as they stand.  sampleBudget turns the
     // variance buffer, the sample counts, the accumulator and the guides into the per-pixel budget and returns its sum (waits).
     // renderAdaptive enqueues the adaptive render with the renderer's scene and camera; a band of [0, 0) means the renderer's

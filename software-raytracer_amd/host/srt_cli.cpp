@@ -165,6 +165,85 @@ static int trace_ray_file(const Scene& scene, int device, const std::string& in,
     }
 }
 
+// Every float32 of a file, or an empty vector (with a message) when it cannot be read or does not hold N >= 1 records of 4.
+static std::vector<float> read_float4_file(const std::string& path) {
+    std::vector<float> v;
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) {
+        std::perror(path.c_str());
+        return v;
+    }
+    float buf[2048];
+    for (size_t got; (got = std::fread(buf, sizeof(float), 2048, f)) > 0;) v.insert(v.end(), buf, buf + got);
+    std::fclose(f);
+    if (v.empty() || v.size() % 4) {
+        std::fprintf(stderr, "%s: %zu floats: want N >= 1 records of 4 float32\n", path.c_str(), v.size());
+        v.clear();
+    }
+    return v;
+}
+
+static bool write_floats(const std::string& path, const std::vector<float>& v) {
+    FILE* g = std::fopen(path.c_str(), "wb");
+    if (!g) {
+        std::perror(path.c_str());
+        return false;
+    }
+    bool ok = std::fwrite(v.data(), sizeof(float), v.size(), g) == v.size();
+    ok = (std::fclose(g) == 0) && ok;
+    if (!ok) std::fprintf(stderr, "%s: write failed\n", path.c_str());
+    return ok;
+}
+
+// --probes IN.f32 --probe-directions K|FILE.f32 --probes-out OUT.bin: light probes (srt_trace_light_probes) at the positions of a
+// file (P records of 4 float32: xyz, w ignored) over K spherical Fibonacci directions (srt_light_probe_sphere) or the directions
+// of a file (K records of 4 float32: xyz, weight) — samples 1..`samples`, `bounces`, `seed`, id_base 0.  OUT.bin receives the P*9
+// float4 coefficients; radiance_out, when given, the P*K float4 running means.
+static int trace_probe_file(const Scene& scene, int device, const std::string& in, const std::string& dirs, const std::string& out,
+                            const std::string& radiance_out, int samples, int bounces, unsigned seed) {
+    const std::vector<float> pos = read_float4_file(in);
+    if (pos.empty()) return 2;
+    std::vector<float> dir;
+    if (dirs.find_first_not_of("0123456789") == std::string::npos) {
+        const long k = std::atol(dirs.c_str());
+        if (k < 1 || k > (long)SRT_LIGHT_PROBE_MAX_DIRECTIONS) {
+            std::fprintf(stderr, "--probe-directions %s: want a count 1..4096 or a file\n", dirs.c_str());
+            return 2;
+        }
+        dir.resize(4 * (size_t)k);
+        srt_light_probe_sphere((size_t)k, dir.data());
+    } else {
+        dir = read_float4_file(dirs);
+        if (dir.empty() || dir.size() / 4 > SRT_LIGHT_PROBE_MAX_DIRECTIONS) {
+            std::fprintf(stderr, "--probe-directions %s: want 1..4096 records of 4 float32\n", dirs.c_str());
+            return 2;
+        }
+    }
+    const size_t np = pos.size() / 4, nk = dir.size() / 4;
+    try {
+        PathTraceRenderer r(device, 8, 8);  // (the frame size plays no part in a probe trace)
+        r.SetScene(scene);
+        srt_light_probe_params lp{};
+        srt_light_probe_params_default(&lp);
+        lp.sample_count = (uint32_t)samples, lp.max_bounces = bounces, lp.seed = seed;
+        if (!radiance_out.empty()) lp.outputs |= SRT_LIGHT_PROBE_RADIANCE;
+        r.traceLightProbes(pos.data(), np, dir.data(), nk, lp);
+        std::vector<float> coeff(np * 9 * 4);
+        r.readLightProbeOutput(SRT_LIGHT_PROBE_COEFFICIENTS, coeff.data());
+        if (!write_floats(out, coeff)) return 1;
+        if (!radiance_out.empty()) {
+            std::vector<float> rad(np * nk * 4);
+            r.readLightProbeOutput(SRT_LIGHT_PROBE_RADIANCE, rad.data());
+            if (!write_floats(radiance_out, rad)) return 1;
+        }
+        std::fprintf(stderr, "%zu probes x %zu directions, %d samples each: %s\n", np, nk, samples, out.c_str());
+        return 0;
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+}
+
 static void usage() {
     std::fprintf(stderr,
                  "usage: srt_render --scene FILE [--width 1280] [--height 720] [--spp 32] [--bounces 2]\n"
@@ -176,6 +255,8 @@ static void usage() {
                  "                  [--reflection-guides] [--reflection-bounces N] [--reflection-out PREFIX]\n"
                  "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--any-hit] [--device 0]\n"
                  "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin --radiance N [--bounces B] [--seed S] [--rays-normalize]\n"
+                 "       srt_render --scene FILE --probes IN.f32 --probe-directions K|FILE.f32 --probes-out OUT.bin [--radiance N]\n"
+                 "                  [--probe-radiance-out FILE] [--bounces B] [--seed S]\n"
                  "       srt_render --scene FILE --adaptive ROUNDS [--adaptive-threshold T] [--adaptive-max M] [--counts-out FILE] [--spp N] ...\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
@@ -221,6 +302,11 @@ static void usage() {
                  "  --radiance N: with --rays, ask srt_trace_radiance instead: the running mean of N (1..4096) path-traced samples of\n"
                  "             --bounces bounces along every ray (samples 1..N, --seed, ray i draws from the stream of pixel i); --rays-out\n"
                  "             then receives the N float4 alone; not with --any-hit\n"
+                 "  --probes:  instead of rendering a frame, trace light probes (srt_trace_light_probes) at the positions in IN.f32: P records\n"
+                 "             of 4 float32 (x y z w, w ignored); --probe-directions K: K (1..4096) spherical Fibonacci directions, or\n"
+                 "             FILE.f32: K records of 4 float32 (x y z weight); --radiance N: samples per ray (1..4096, default 16) of\n"
+                 "             --bounces bounces; --probes-out receives P x 9 float4 SH coefficients, --probe-radiance-out the P x K float4\n"
+                 "             running means; single device, not with --rays, no frame options\n"
                  "  --adaptive ROUNDS: adaptive sampling in place of the uniform frame: an even --spp is the uniform seed, split into two\n"
                  "             independently seeded halves; then ROUNDS (1..64) rounds of srt_variance, srt_sample_budget and srt_render_adaptive\n"
                  "             on both halves, and the mean of the halves goes to --out; the frame's total samples are printed on stderr;\n"
@@ -248,6 +334,7 @@ int main(int argc, char** argv) {
     bool rays_normalize = false, rays_any_hit = false;
     int radiance = 0;
     bool radiance_given = false;
+    std::string probes_in, probes_out, probe_directions, probe_radiance_out;
     int adaptive = 0, adaptive_max = 0;
     bool adaptive_given = false, adaptive_threshold_given = false, adaptive_max_given = false;
     float adaptive_threshold = 0;
@@ -313,6 +400,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rays-normalize")) rays_normalize = true;
         else if (!std::strcmp(argv[i], "--any-hit")) rays_any_hit = true;
         else if (!std::strcmp(argv[i], "--radiance")) radiance = std::atoi(need("--radiance")), radiance_given = true;
+        else if (!std::strcmp(argv[i], "--probes")) probes_in = need("--probes");
+        else if (!std::strcmp(argv[i], "--probes-out")) probes_out = need("--probes-out");
+        else if (!std::strcmp(argv[i], "--probe-directions")) probe_directions = need("--probe-directions");
+        else if (!std::strcmp(argv[i], "--probe-radiance-out")) probe_radiance_out = need("--probe-radiance-out");
         else if (!std::strcmp(argv[i], "--adaptive")) adaptive = std::atoi(need("--adaptive")), adaptive_given = true;
         else if (!std::strcmp(argv[i], "--adaptive-threshold")) adaptive_threshold = std::strtof(need("--adaptive-threshold"), nullptr), adaptive_threshold_given = true;
         else if (!std::strcmp(argv[i], "--adaptive-max")) adaptive_max = std::atoi(need("--adaptive-max")), adaptive_max_given = true;
@@ -378,9 +469,25 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--rays, --rays-out, --rays-normalize and --any-hit go together: --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--any-hit]\n");
         return 2;
     }
-    if (radiance_given && (rays_in.empty() || rays_any_hit || radiance < 1 || radiance > 4096 || bounces < 0)) {
+    if (radiance_given && probes_in.empty() && (rays_in.empty() || rays_any_hit || radiance < 1 || radiance > 4096 || bounces < 0)) {
         std::fprintf(stderr, "--radiance N (1..4096) needs --rays and --rays-out, a --bounces >= 0, and does not go with --any-hit\n");
         return 2;
+    }
+    if (!probes_in.empty() || !probes_out.empty() || !probe_directions.empty() || !probe_radiance_out.empty()) {
+        if (probes_in.empty() || probes_out.empty() || probe_directions.empty()) {
+            std::fprintf(stderr, "--probes, --probe-directions, --probes-out and --probe-radiance-out go together: --probes IN.f32 --probe-directions K|FILE.f32 "
+                                 "--probes-out OUT.bin [--radiance N] [--probe-radiance-out FILE]\n");
+            return 2;
+        }
+        if ((radiance_given && (radiance < 1 || radiance > 4096)) || bounces < 0) {
+            std::fprintf(stderr, "--probes: --radiance N takes 1..4096 samples and --bounces must be >= 0\n");
+            return 2;
+        }
+        if (!rays_in.empty() || !devices.empty() || temporal || steps > 1 || aa_given || !gbuffer.empty() || !denoise.empty() || !upsample.empty() ||
+            !denoise_variance.empty() || adaptive_given || ao_given || sun_visibility || !vis_out.empty() || reflection_guides || !reflection_out.empty()) {
+            std::fprintf(stderr, "--probes traces light probes instead of rendering a frame: single device, not with --rays, no frame options\n");
+            return 2;
+        }
     }
     if (!rays_in.empty() && (!devices.empty() || temporal || steps > 1 || aa_given || !gbuffer.empty() || !denoise.empty() || !upsample.empty() ||
                              !denoise_variance.empty())) {
@@ -466,6 +573,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--move-object: the scene has no object %zu\n", m.index);
             return 2;
         }
+    if (!probes_in.empty()) return trace_probe_file(scene, device, probes_in, probe_directions, probes_out, probe_radiance_out, radiance_given ? radiance : 16, bounces, seed);
     if (!rays_in.empty()) return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize, rays_any_hit, radiance_given ? radiance : 0, bounces, seed);
     auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {
         FILE* f = std::fopen(path.c_str(), "wb");
