@@ -1511,6 +1511,121 @@ const char* srt_gather_path(const srt_context* src);
  * equal ROW bands are worse (sky rows cost a tenth of floor rows).  Synchronous. */
 int srt_estimate_row_costs(srt_context* ctx, int max_bounces, uint32_t seed, float* row_costs);
 
+/* ---- probe-grid shading: per-pixel irradiance from a grid of light probes (ABI 7, backward compatible) ---------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of
+ * them runs what it ran before, bit for bit.
+ *
+ * srt_trace_light_probes leaves nine SH coefficients per probe on the device.  srt_shade_probe_grid is the pass that uses them:
+ * for probes on a regular grid it gives every pixel of a band the irradiance at its first hit — the eight probes around the point,
+ * weighted trilinearly, optionally by how far each lies in front of the surface, and optionally only those the surface can see
+ * (one any-hit query of srt_trace_occlusion per corner, on the device).  The output is W*H float4 (r, g, b, a), a = the sum of the
+ * weights that survived: a == 0 says that no probe was usable.  The coefficient layout is exactly SRT_LIGHT_PROBE_COEFFICIENTS
+ * (probe p's nine float4 at 9p .. 9p + 8), so a device buffer bound with srt_bind_light_probe_output can be bound here too and
+ * nothing crosses the bus.
+ *
+ * Rules.  All arithmetic is binary32 without contraction.  Per pixel of the band, with o from SRT_GBUF_OBJECT, n from
+ * SRT_GBUF_NORMAL_DEPTH.xyz and x from SRT_GBUF_POSITION.xyz (bound or own, as srt_render_visibility's rule 1), and albedo from
+ * SRT_GBUF_ALBEDO only with SRT_PROBE_GRID_ALBEDO:
+ * 1. Miss pixel (o == -1): out = (0, 0, 0, 0), and no other guide value is loaded.
+ * 2. Cell, per axis a with n_a = counts[a]: m = (float)(n_a - 1); u = (x_a - origin_a) / spacing_a;
+ *    u = !(u > 0) ? 0 : (u > m ? m : u), so a NaN gives 0; i = (int)u, lowered to n_a - 2 when i > n_a - 2 and n_a >= 2;
+ *    f = u - (float)i.  An axis with n_a == 1 has i = 0 and f = 0.
+ * 3. Corners c = 0 .. 7 with bits (cx, cy, cz) = (c & 1, (c >> 1) & 1, (c >> 2) & 1).  Per axis w_a = c_a ? f : (1.0f - f); the
+ *    trilinear weight t = (w_x * w_y) * w_z.  A corner whose bit is set on an axis with n_a == 1 does not exist; it has w_a = f = 0
+ *    and so weight 0.  A corner with !(t > 0) is skipped.
+ * 4. Probe position p_a = origin_a + (float)(i_a + c_a) * spacing_a.  srt_probe_grid_positions computes the same expression, so
+ *    the positions agree bit for bit.
+ * 5. Segment to the probe.  O = (x.x + n.x * .00001f, x.y + n.y * .00001f, x.z + n.z * .00001f) as visibility rule 2; v = p - O;
+ *    q = (v.x*v.x + v.y*v.y) + v.z*v.z; L = sqrtf(q).  If !(L > 0) the corner is skipped.  d = (v.x / L, v.y / L, v.z / L).
+ * 6. Normal weight.  With SRT_PROBE_GRID_NORMAL_WEIGHT: h = (((d.x*n.x + d.y*n.y) + d.z*n.z) + 1.0f) * 0.5f and
+ *    t = t * ((h*h) + 0.2f).
+ * 7. Visibility.  With SRT_PROBE_GRID_VISIBILITY the segment (O, d, t_max = L) goes through the any-hit query, exactly as
+ *    srt_trace_occlusion answers it for the scene captured at enqueue.  An occluded corner is skipped.  Corners skipped by rules
+ *    3 and 5 are never traced.
+ * 8. Corner irradiance.  With k = probe index (i_x + c_x) + n_x * ((i_y + c_y) + n_y * (i_z + c_z)), b_j(n) the basis of the
+ *    light-probe block's rule 3 on the normal, A_0 = band_weight[0], A_1..3 = band_weight[1], A_4..8 = band_weight[2]:
+ *    term_j = (A_j * coefficient[9k + j][l]) * b_j(n); e_c[l] = term_0, then e_c[l] = e_c[l] + term_j for j = 1 .. 8 ascending
+ *    (srt_light_probe_irradiance's rule), for l = 0, 1, 2.  The fourth lanes of the coefficients are not read.
+ * 9. Sum.  E[l] = +0.0f and T = +0.0f; then for c = 0 .. 7 ascending E[l] = E[l] + (t_c * e_c[l]) and T = T + t_c, where a skipped
+ *    corner contributes +0.0f to each.  If T > 0: out = (E[0] / T, E[1] / T, E[2] / T, T), with r, g, b multiplied by albedo.rgb
+ *    after the division with SRT_PROBE_GRID_ALBEDO.  Otherwise out = (0, 0, 0, 0): the caller sees a == 0 and can fall back, for
+ *    instance to a second call without SRT_PROBE_GRID_VISIBILITY.
+ * 10. Band weights.  The default (3.14159274f, 2.09439516f, 0.785398185f) are srt_light_probe_irradiance's constants: the
+ *    cosine-weighted integral.  (1.0f, 0.5f, 0.0f) is the MEAN over the hemisphere around n, which is what this renderer's diffuse
+ *    bounce averages, up to the non-uniformity of GetRandomDirection.
+ * 11. Band.  As srt_gbuffer_params: a band is given in MEMORY rows and only scene rows [H - row_end, H - row_begin) of the output
+ *    are written, indexed x + y*W with the SCENE row y.  Nothing outside the band is written.
+ * 12. Grid and coefficients.  srt_set_probe_grid copies the grid; it refuses, with SRT_ERR_INVALID_ARG, counts < 1, a product
+ *    nx*ny*nz > 2^30, a spacing that is NaN, infinite or <= 0 and a non-finite origin, and then leaves the previous grid.
+ *    srt_write_probe_grid_coefficients copies probes * 9 float4 from the host into the handle's own array and waits, like
+ *    srt_write_light_probes; srt_bind_probe_grid_coefficients binds a DEVICE array of probes * 9 float4, does not copy and does
+ *    not wait; NULL, 0 returns to the own array.  1 <= probes <= 2^30.
+ * 13. Output.  The handle's own buffer (allocated on first use) or the caller's: srt_bind_probe_grid_output binds a DEVICE buffer
+ *    of W*H float4, NULL = own, under srt_bind_gbuffer's rules (does not wait, enqueued work keeps its buffer).
+ *    srt_read_probe_grid_output waits, then copies the W*H float4 of the current buffer; SRT_ERR_STATE before the first
+ *    srt_shade_probe_grid.
+ * 14. Side effects.  Asynchronous on the launch stream behind earlier work; srt_wait / srt_poll cover it; grid, coefficients,
+ *    guides and output are those current at enqueue.  The call leaves alone everything srt_render_visibility leaves alone, and
+ *    the visibility outputs and the light-probe inputs, outputs and records as well.
+ * 15. Pinned domain.  Guides written by srt_render_gbuffer, or bound guides with unit normals and finite points, with finite
+ *    coefficients, are pinned bit for bit.  Other inputs give some value and do not fault: every probe index is clamped to the
+ *    grid by construction, so no coefficient load can leave the array.
+ * 16. Errors, all found before anything is touched, in this order: SRT_ERR_STATE before srt_set_scene; SRT_ERR_INVALID_ARG for an
+ *    empty or out-of-range band, unknown flags, a non-zero reserved word or a NaN band_weight; SRT_ERR_STATE when there is no
+ *    grid, when there are no coefficients, when OBJECT, NORMAL_DEPTH, POSITION or (with SRT_PROBE_GRID_ALBEDO) ALBEDO has never
+ *    been bound or rendered, or when the current coefficient count is not nx*ny*nz.
+ * 17. Work counts.  With SRT_PROBE_GRID_COUNT_WORK the launch counts, deterministically: the hit pixels; the corners that reach
+ *    rule 7 (weight > 0 and L > 0, with or without the query); the segments traced and those with no occluder (both 0 without
+ *    SRT_PROBE_GRID_VISIBILITY); the wave-level trips — a wave numbers the corners of its 8 x 8 tile's h hit pixels, in lane order,
+ *    j = 8 * rank + c and serves 64 of them per trip, so a tile takes ceil(h / 8) trips; the lane-level tests of
+ *    srt_occlusion_work; and the waves of the launch.  One vector atomic per wave at the end; without the flag there are no
+ *    atomics at all.  srt_get_probe_grid_work waits and copies the record of the last srt_shade_probe_grid; SRT_ERR_STATE unless
+ *    that call had the flag (or when there has been none). */
+#define SRT_PROBE_GRID_VISIBILITY 1u    /* rule 7 */
+#define SRT_PROBE_GRID_NORMAL_WEIGHT 2u /* rule 6 */
+#define SRT_PROBE_GRID_ALBEDO 4u        /* rule 9: rgb times SRT_GBUF_ALBEDO.rgb */
+#define SRT_PROBE_GRID_COUNT_WORK 8u    /* fill srt_probe_grid_work for this call */
+
+typedef struct srt_probe_grid { /* 36 bytes */
+    float origin[3];            /* position of probe (0,0,0) */
+    float spacing[3];           /* > 0, finite */
+    int32_t counts[3];          /* nx, ny, nz >= 1; nx*ny*nz <= 2^30; probe (ix,iy,iz) has index ix + nx*(iy + ny*iz) */
+} srt_probe_grid;
+
+typedef struct srt_probe_grid_params { /* 32 bytes */
+    int32_t row_begin;                 /* first memory row (inclusive), as srt_gbuffer_params / srt_visibility_params */
+    int32_t row_end;                   /* one past the last memory row */
+    uint32_t flags;                    /* SRT_PROBE_GRID_VISIBILITY | _NORMAL_WEIGHT | _ALBEDO | _COUNT_WORK */
+    float band_weight[3];              /* A for SH bands 0, 1, 2 (rule 10) */
+    uint32_t reserved[2];              /* 0 */
+} srt_probe_grid_params;
+
+typedef struct srt_probe_grid_work { /* 80 bytes */
+    uint32_t valid, reserved;        /* 1, 0 */
+    uint64_t pixels;                 /* hit pixels of the band */
+    uint64_t corners;                /* corners with weight > 0 and L > 0: those that reach the query */
+    uint64_t segments, open;         /* segments traced; those with no occluder */
+    uint64_t wave_trips;             /* sum over tiles of ceil(h / 8) */
+    uint64_t analytic_tests;         /* as srt_occlusion_work */
+    uint64_t node_visits;
+    uint64_t triangle_tests;
+    uint64_t waves;                  /* waves of the launch */
+} srt_probe_grid_work;
+
+/* Pure host, no device: fills nx*ny*nz float4 with the probe positions of rule 4 in index order, w = 0.  SRT_ERR_INVALID_ARG for
+ * a grid srt_set_probe_grid would refuse. */
+int srt_probe_grid_positions(const srt_probe_grid* grid, float* dst);
+/* flags = 0, band_weight = (3.14159274f, 2.09439516f, 0.785398185f), reserved = 0; row_begin = row_end = 0: the band is the
+ * caller's to fill (pure host, no device needed). */
+int srt_probe_grid_params_default(srt_probe_grid_params* out);
+int srt_set_probe_grid(srt_context* ctx, const srt_probe_grid* grid);
+int srt_write_probe_grid_coefficients(srt_context* ctx, const float* coefficients, size_t probes);
+int srt_bind_probe_grid_coefficients(srt_context* ctx, const void* d_ptr, size_t probes);
+int srt_shade_probe_grid(srt_context* ctx, const srt_probe_grid_params* params);
+int srt_bind_probe_grid_output(srt_context* ctx, void* d_float4);
+int srt_read_probe_grid_output(srt_context* ctx, float* dst);
+int srt_get_probe_grid_work(srt_context* ctx, srt_probe_grid_work* out);
+
 /* ---- diagnostics ----------------------------------------------------------------- */
 /* Self-test of the kernel's shortened arithmetic (csrc/srt_kernel.hip.h: float3::Normalized, the box slab slopes and the
  * accumulation weight 1 / frame without the rescaling and fix-up steps of the library sqrt / divide where those are

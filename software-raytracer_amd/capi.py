@@ -46,6 +46,10 @@ LIGHT_PROBE_RESET, LIGHT_PROBE_NORMALIZE, LIGHT_PROBE_COUNT_WORK = 1, 2, 4
 LIGHT_PROBE_COEFFICIENTS, LIGHT_PROBE_RADIANCE = 1, 2
 LIGHT_PROBE_MAX_DIRECTIONS = 4096
 LIGHT_PROBE_COEFFS = 9
+# probe-grid shading (srt_shade_probe_grid): the flags of srt_probe_grid_params and the two documented band weights
+PROBE_GRID_VISIBILITY, PROBE_GRID_NORMAL_WEIGHT, PROBE_GRID_ALBEDO, PROBE_GRID_COUNT_WORK = 1, 2, 4, 8
+PROBE_GRID_BAND_WEIGHT_IRRADIANCE = (3.14159274, 2.09439516, 0.785398185)  # srt_light_probe_irradiance's: the cosine-weighted integral
+PROBE_GRID_BAND_WEIGHT_HEMISPHERE = (1.0, 0.5, 0.0)  # the mean over the hemisphere around the normal
 # adaptive sampling (srt_render_adaptive, srt_sample_budget): the flags, the limits of max_samples / max_budget, the last frame
 ADAPTIVE_KEEP_COUNTS, ADAPTIVE_COUNT_WORK = 1, 2
 ADAPTIVE_MAX_SAMPLES = 4096
@@ -103,6 +107,9 @@ EXPORTS = [
     "srt_write_light_probes", "srt_bind_light_probes", "srt_write_light_probe_directions", "srt_bind_light_probe_directions",
     "srt_light_probe_params_default", "srt_trace_light_probes", "srt_bind_light_probe_output", "srt_read_light_probe_output",
     "srt_get_light_probe_work", "srt_light_probe_sphere", "srt_light_probe_irradiance",
+    "srt_probe_grid_positions", "srt_probe_grid_params_default", "srt_set_probe_grid", "srt_write_probe_grid_coefficients",
+    "srt_bind_probe_grid_coefficients", "srt_shade_probe_grid", "srt_bind_probe_grid_output", "srt_read_probe_grid_output",
+    "srt_get_probe_grid_work",
 ]
 
 
@@ -321,6 +328,27 @@ class LightProbeWork(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+class ProbeGrid(C.Structure):
+    """srt_probe_grid: the position of probe (0, 0, 0), the spacing and the probe counts per axis."""
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("counts", C.c_int32 * 3)]
+
+
+class ProbeGridParams(C.Structure):
+    """srt_probe_grid_params: the band of memory rows, PROBE_GRID_* flags and the weights of SH bands 0, 1, 2."""
+    _fields_ = [("row_begin", C.c_int32), ("row_end", C.c_int32), ("flags", C.c_uint32), ("band_weight", C.c_float * 3),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class ProbeGridWork(C.Structure):
+    """srt_probe_grid_work: what the last counting srt_shade_probe_grid did."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_uint64), ("corners", C.c_uint64), ("segments", C.c_uint64),
+                ("open", C.c_uint64), ("wave_trips", C.c_uint64), ("analytic_tests", C.c_uint64), ("node_visits", C.c_uint64),
+                ("triangle_tests", C.c_uint64), ("waves", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class UpdateInfo(C.Structure):
     """srt_update_info: what the last successful srt_update_scene did to the mesh image."""
     _fields_ = [("path", C.c_int32), ("reason", C.c_int32), ("levels", C.c_int32), ("triangles", C.c_uint32), ("nodes", C.c_uint32),
@@ -504,6 +532,15 @@ def open_library(path):
     L.srt_get_light_probe_work.argtypes = [ctx, C.POINTER(LightProbeWork)]
     L.srt_light_probe_sphere.argtypes = [C.c_size_t, C.POINTER(C.c_float)]
     L.srt_light_probe_irradiance.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.srt_probe_grid_positions.argtypes = [C.POINTER(ProbeGrid), C.POINTER(C.c_float)]
+    L.srt_probe_grid_params_default.argtypes = [C.POINTER(ProbeGridParams)]
+    L.srt_set_probe_grid.argtypes = [ctx, C.POINTER(ProbeGrid)]
+    L.srt_write_probe_grid_coefficients.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t]
+    L.srt_bind_probe_grid_coefficients.argtypes = [ctx, C.c_void_p, C.c_size_t]
+    L.srt_shade_probe_grid.argtypes = [ctx, C.POINTER(ProbeGridParams)]
+    L.srt_bind_probe_grid_output.argtypes = [ctx, C.c_void_p]
+    L.srt_read_probe_grid_output.argtypes = [ctx, C.POINTER(C.c_float)]
+    L.srt_get_probe_grid_work.argtypes = [ctx, C.POINTER(ProbeGridWork)]
     L.srt_set_sample_counts.argtypes = [ctx, C.c_uint32]
     L.srt_write_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
     L.srt_read_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
@@ -730,6 +767,31 @@ def light_probe_sphere(count, lib=None):
     rc = L.srt_light_probe_sphere(n, out.ctypes.data_as(C.POINTER(C.c_float)))
     if rc:
         raise SrtError(rc, "srt_light_probe_sphere(%d)" % n)
+    return out
+
+
+def probe_grid(origin, spacing, counts):
+    """An srt_probe_grid from three triples (a ProbeGrid passes through)."""
+    if isinstance(origin, ProbeGrid) and spacing is None and counts is None:
+        return origin
+    g = ProbeGrid()
+    for a in range(3):
+        g.origin[a], g.spacing[a], g.counts[a] = float(origin[a]), float(spacing[a]), int(counts[a])
+    return g
+
+
+def probe_grid_positions(origin, spacing=None, counts=None, lib=None):
+    """srt_probe_grid_positions: the positions of the grid's probes as an (nx*ny*nz, 4) float32 array in index order
+    ix + nx*(iy + ny*iz), w = 0 — what trace_light_probes() takes.  `origin`: a ProbeGrid, or three triples.  Pure host."""
+    L = lib or load_library()
+    g = probe_grid(origin, spacing, counts)
+    n = [int(c) for c in g.counts]
+    if min(n) < 1 or n[0] * n[1] * n[2] > 1 << 30:
+        raise SrtError(ERR_INVALID_ARG, "srt_probe_grid_positions: counts %s" % (n,))
+    out = np.empty((n[0] * n[1] * n[2], 4), dtype=np.float32)
+    rc = L.srt_probe_grid_positions(C.byref(g), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != OK:
+        raise SrtError(rc, "srt_probe_grid_positions")
     return out
 
 
@@ -1363,6 +1425,66 @@ class PathTracer:
         """srt_get_light_probe_work: the work counts of the last trace_light_probes(count_work=True) as a dict.  Waits."""
         w = LightProbeWork()
         self._ck(self.L.srt_get_light_probe_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    # ---- probe-grid shading -----------------------------------------------------------------
+    def set_probe_grid(self, origin, spacing=None, counts=None):
+        """srt_set_probe_grid: the grid later shade_probe_grid() calls interpolate on.  `origin`: a ProbeGrid, or three triples."""
+        g = probe_grid(origin, spacing, counts)
+        self._ck(self.L.srt_set_probe_grid(self._h, C.byref(g)))
+        self._probe_grid_probes = int(g.counts[0]) * int(g.counts[1]) * int(g.counts[2])
+
+    def shade_probe_grid(self, coefficients=None, visibility=False, normal_weight=False, albedo=False, band_weight=None, rows=None,
+                         count_work=False, output=None, flags=0, reserved=(0, 0)):
+        """srt_shade_probe_grid: per pixel of memory rows `rows` (default: the whole frame) the irradiance at the first hit from the
+        grid's probes — trilinear weights, times a normal weight (normal_weight), only probes the surface sees (visibility), times
+        the albedo guide (albedo) — from the OBJECT, NORMAL_DEPTH and POSITION guides as they stand (render_gbuffer() first, or bind
+        them).  `coefficients`: numpy (P, 9, 4) or (P*9, 4) float32 (written) or a torch tensor (P*9, 4) on this tracer's device
+        (bound, no copy: what bind_light_probe_output("coefficients", t) filled); None: the current ones.  `band_weight`: the weights
+        of SH bands 0, 1, 2 (default PROBE_GRID_BAND_WEIGHT_IRRADIANCE).  `output`: a torch tensor (H, W, 4) float32 to write
+        (bind_probe_grid_output).  count_work: SRT_PROBE_GRID_COUNT_WORK (probe_grid_work() then reads the record).  Asynchronous,
+        like render(); probe_grid_output() reads the result."""
+        L = self.L
+        if coefficients is not None:
+            a = coefficients
+            if isinstance(a, np.ndarray) and a.ndim == 3:
+                a = a.reshape(-1, 4)
+            kind, arr, n = self._ray_array("shade_probe_grid(coefficients)", a)
+            if n % LIGHT_PROBE_COEFFS:
+                raise ValueError("shade_probe_grid(coefficients): %d float4, want nine per probe" % n)
+            if kind == "host":
+                self._ck(L.srt_write_probe_grid_coefficients(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n // LIGHT_PROBE_COEFFS))
+                self._probe_grid_bound = None
+            else:
+                self._ck(L.srt_bind_probe_grid_coefficients(self._h, C.c_void_p(arr.data_ptr()), n // LIGHT_PROBE_COEFFS))
+                self._probe_grid_bound = arr  # (a bound tensor stays referenced for as long as it is bound)
+        if output is not None:
+            self.bind_probe_grid_output(output)
+        p = ProbeGridParams()
+        self._ck(L.srt_probe_grid_params_default(C.byref(p)))
+        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
+        p.flags = (int(flags) | (PROBE_GRID_VISIBILITY if visibility else 0) | (PROBE_GRID_NORMAL_WEIGHT if normal_weight else 0) |
+                   (PROBE_GRID_ALBEDO if albedo else 0) | (PROBE_GRID_COUNT_WORK if count_work else 0))
+        if band_weight is not None:
+            for b in range(3):
+                p.band_weight[b] = float(band_weight[b])
+        p.reserved[0], p.reserved[1] = int(reserved[0]), int(reserved[1])
+        self._ck(L.srt_shade_probe_grid(self._h, C.byref(p)))
+
+    def bind_probe_grid_output(self, tensor):
+        """srt_bind_probe_grid_output: write the result into a torch tensor on this tracer's device, (H, W, 4) float32 and contiguous
+        (None: the handle's own buffer).  Checked here, before any native call, as bind_gbuffer checks."""
+        self._ck(self.L.srt_bind_probe_grid_output(self._h, self._float4_tensor_ptr("bind_probe_grid_output", tensor)))
+        self._probe_grid_out_bound = tensor
+
+    def probe_grid_output(self):
+        """srt_read_probe_grid_output: (H, W, 4) float32, rows = scene rows: the irradiance and the surviving weight.  Waits."""
+        return self._read_image(self.L.srt_read_probe_grid_output, (self.height, self.width, 4), np.float32)
+
+    def probe_grid_work(self):
+        """srt_get_probe_grid_work: the work counts of the last shade_probe_grid(count_work=True) as a dict.  Waits."""
+        w = ProbeGridWork()
+        self._ck(self.L.srt_get_probe_grid_work(self._h, C.byref(w)))
         return w.as_dict()
 
     def ray_output(self, name, count=None):

@@ -41,6 +41,8 @@
 #include "srt_radiance_host.h"
 #include "srt_light_probes.hip.h"
 #include "srt_light_probes_host.h"
+#include "srt_probe_grid.hip.h"
+#include "srt_probe_grid_host.h"
 #include "srt_adaptive.hip.h"
 #include "srt_adaptive_host.h"
 #include "srt_launch_shape.h"
@@ -406,6 +408,14 @@ struct srt_context {
     srt::LightProbeState probes;
     DeviceBuffer<float4> d_probe_partial;
     DeviceBuffer<unsigned long long> d_probe_work;
+    // probe-grid shading (srt_shade_probe_grid): the grid, which coefficient array is current and whether the last call counted
+    // (srt_probe_grid_host.h); the own coefficient array (srt_write_probe_grid_coefficients; it grows on demand); the own output
+    // buffer of W*H float4 with its slot; the record a counting launch adds to (srt::PG_WORK_N words)
+    srt::ProbeGridState probe_grid;
+    DeviceBuffer<float4> d_probe_grid_coefficients;
+    DeviceBuffer<float4> d_probe_grid_own;
+    srt::OutputSlot probe_grid_out;
+    DeviceBuffer<unsigned long long> d_probe_grid_work;
     // adaptive sampling (srt_render_adaptive, srt_sample_budget): the per-pixel sample counts and sample budget, W*H uint32 each,
     // own buffer and slot; whether the last adaptive render counted and whether a budget pass has run (srt_adaptive_host.h); the
     // tile ticket of a launch (zeroed on the stream in front of it); the record a counting launch adds to (srt::ADP_WORK_N words);
@@ -2241,6 +2251,129 @@ int srt_light_probe_sphere(size_t count, float* dst) {
 int srt_light_probe_irradiance(const float* coefficients, const float* normal, float* rgb) {
     if (!coefficients || !normal || !rgb) return SRT_ERR_INVALID_ARG;
     srt::light_probe_irradiance(coefficients, normal, rgb);
+    return SRT_OK;
+}
+
+// ---- probe-grid shading --------------------------------------------------------------------------------------------
+static_assert(SRT_PROBE_GRID_VISIBILITY == srt::PROBE_GRID_FLAG_VISIBILITY && SRT_PROBE_GRID_NORMAL_WEIGHT == srt::PROBE_GRID_FLAG_NORMAL_WEIGHT &&
+              SRT_PROBE_GRID_ALBEDO == srt::PROBE_GRID_FLAG_ALBEDO && SRT_PROBE_GRID_COUNT_WORK == srt::PROBE_GRID_FLAG_COUNT_WORK &&
+              sizeof(srt_probe_grid) == 36 && sizeof(srt::ProbeGrid) == 36 && sizeof(srt_probe_grid_params) == 32 && sizeof(srt::ProbeGridCall) == 32 &&
+              sizeof(srt_probe_grid_work) == 80 && (int)srt::PG_COEFFS == (int)srt::LIGHT_PROBE_COEFFS,
+              "srt_probe_grid_host.h, srt_probe_grid.hip.h and srt_pathtrace.h disagree");
+
+static srt::ProbeGrid probe_grid_of(const srt_probe_grid* g) {
+    srt::ProbeGrid r;
+    for (int a = 0; a < 3; ++a) r.origin[a] = g->origin[a], r.spacing[a] = g->spacing[a], r.counts[a] = g->counts[a];
+    return r;
+}
+
+int srt_probe_grid_positions(const srt_probe_grid* grid, float* dst) {
+    if (!grid || !dst) return SRT_ERR_INVALID_ARG;
+    const srt::ProbeGrid g = probe_grid_of(grid);
+    if (srt::probe_grid_check(g, nullptr) != srt::RAYS_OK) return SRT_ERR_INVALID_ARG;
+    srt::probe_grid_positions(g, dst);
+    return SRT_OK;
+}
+
+int srt_probe_grid_params_default(srt_probe_grid_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::ProbeGridCall c;
+    srt::probe_grid_call_default(c);
+    memcpy(out, &c, sizeof c);
+    return SRT_OK;
+}
+
+int srt_set_probe_grid(srt_context* ctx, const srt_probe_grid* grid) {
+    if (!ctx || !grid) return SRT_ERR_INVALID_ARG;
+    const srt::ProbeGrid g = probe_grid_of(grid);
+    const char* why = "";
+    if (srt::probe_grid_check(g, &why) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_probe_grid: %s (origin %g %g %g, spacing %g %g %g, counts %d %d %d)", why, (double)g.origin[0],
+                    (double)g.origin[1], (double)g.origin[2], (double)g.spacing[0], (double)g.spacing[1], (double)g.spacing[2], g.counts[0], g.counts[1], g.counts[2]);
+    ctx->probe_grid.grid = g, ctx->probe_grid.grid_set = true;  // (an enqueued launch keeps the grid it was given: a kernel argument)
+    return SRT_OK;
+}
+
+int srt_write_probe_grid_coefficients(srt_context* ctx, const float* coefficients, size_t probes) {
+    if (!ctx || !coefficients) return SRT_ERR_INVALID_ARG;
+    if (probes < 1 || probes > srt::PROBE_GRID_MAX_PROBES)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_write_probe_grid_coefficients: %zu probes: want 1 .. 2^30", probes);
+    if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it may be re-allocated below)
+    const size_t bytes = probes * (size_t)srt::PG_COEFFS * sizeof(float4);
+    if (ctx->d_probe_grid_coefficients.bytes() < bytes) {
+        ctx->probe_grid.coefficients.own_count = 0;  // (a failed allocation leaves no own array)
+        SRT_HIP(ctx, ctx->d_probe_grid_coefficients.ensure(bytes));
+    }
+    SRT_HIP(ctx, hipMemcpy(ctx->d_probe_grid_coefficients, coefficients, bytes, hipMemcpyHostToDevice));
+    srt::light_probe_written(ctx->probe_grid.coefficients, probes);
+    return SRT_OK;
+}
+
+int srt_bind_probe_grid_coefficients(srt_context* ctx, const void* d_ptr, size_t probes) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    if (srt::light_probe_bind(ctx->probe_grid.coefficients, d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_grid_coefficients: want a device array and 1 .. 2^30 probes, or NULL, 0 (got %zu)", probes);
+    return SRT_OK;
+}
+
+int srt_shade_probe_grid(srt_context* ctx, const srt_probe_grid_params* s) {
+    if (!ctx || !s) return SRT_ERR_INVALID_ARG;
+    srt::ProbeGridCall call;
+    memcpy(&call, s, sizeof call);
+    bool present[srt::PROBE_GRID_GUIDES];
+    for (int i = 0; i < srt::PROBE_GRID_GUIDES; ++i) present[i] = current(ctx->gbuf[i], ctx->d_gbuf_own[i]) != nullptr;
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_grid_check_shade(ctx->probe_grid, call, ctx->scene_set, ctx->height, present, &why))
+        return fail(ctx, (int)rs, "srt_shade_probe_grid: %s (rows [%d,%d) of %d, flags 0x%x, band_weight %g %g %g, reserved %u %u)", why, s->row_begin, s->row_end,
+                    ctx->height, s->flags, (double)s->band_weight[0], (double)s->band_weight[1], (double)s->band_weight[2], s->reserved[0], s->reserved[1]);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const bool count = (s->flags & SRT_PROBE_GRID_COUNT_WORK) != 0;
+    float4* dst = nullptr;
+    SRT_WRITE_TARGET(ctx, ctx->probe_grid_out, ctx->d_probe_grid_own, frame_pixels(ctx) * sizeof(float4), dst);
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_probe_grid_work, srt::PG_WORK_N)) return rc;
+    }
+    srt::KernelParams K;
+    const KernelSetup ks = scene_kernel_params(ctx, s->row_begin, s->row_end, K);
+    const srt::ProbeGrid& g = ctx->probe_grid.grid;
+    srt::ProbeGridIO io{};
+    io.object = (const int32_t*)current(ctx->gbuf[0], ctx->d_gbuf_own[0]);
+    io.normal_depth = (const float4*)current(ctx->gbuf[1], ctx->d_gbuf_own[1]);
+    io.position = (const float4*)current(ctx->gbuf[2], ctx->d_gbuf_own[2]);
+    io.albedo = (s->flags & SRT_PROBE_GRID_ALBEDO) ? (const float4*)current(ctx->gbuf[3], ctx->d_gbuf_own[3]) : nullptr;
+    io.coefficients = ctx->probe_grid.coefficients.bound ? (const float4*)ctx->probe_grid.coefficients.bound : (const float4*)ctx->d_probe_grid_coefficients;
+    io.out = dst;
+    for (int a = 0; a < 3; ++a) io.origin[a] = g.origin[a], io.spacing[a] = g.spacing[a], io.counts[a] = g.counts[a], io.band_weight[a] = s->band_weight[a];
+    io.visibility = (s->flags & SRT_PROBE_GRID_VISIBILITY) ? 1u : 0u;
+    io.normal_weight = (s->flags & SRT_PROBE_GRID_NORMAL_WEIGHT) ? 1u : 0u;
+    io.work = count ? (unsigned long long*)ctx->d_probe_grid_work : nullptr;
+    if (const int rc = launch_tiles(ctx, SRT_KERNEL_LDS_MESH_COUNT(srt::probe_grid_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count), ks, K, io)) return rc;
+    ctx->probe_grid_out.wrote(dst);
+    srt::probe_grid_shaded(ctx->probe_grid, s->flags);
+    return SRT_OK;
+}
+
+int srt_bind_probe_grid_output(srt_context* ctx, void* d_float4) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    return ctx->probe_grid_out.bind(d_float4), SRT_OK;  // (no synchronisation: an enqueued call keeps the buffer it was given, as srt_bind_gbuffer)
+}
+
+int srt_read_probe_grid_output(srt_context* ctx, float* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    return read_slot(ctx, ctx->probe_grid_out.read_any(ctx->d_probe_grid_own), dst, frame_pixels(ctx) * sizeof(float4),
+                     "srt_read_probe_grid_output: there has been no srt_shade_probe_grid");
+}
+
+int srt_get_probe_grid_work(srt_context* ctx, srt_probe_grid_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::probe_grid_check_work(ctx->probe_grid) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_grid_work: the last srt_shade_probe_grid did not ask for SRT_PROBE_GRID_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::PG_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_probe_grid_work, w, srt::PG_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0;
+    out->pixels = w[srt::PG_WORK_PIXELS], out->corners = w[srt::PG_WORK_CORNERS], out->segments = w[srt::PG_WORK_SEGMENTS], out->open = w[srt::PG_WORK_OPEN];
+    out->wave_trips = w[srt::PG_WORK_TRIPS], out->analytic_tests = w[srt::PG_WORK_ANALYTIC], out->node_visits = w[srt::PG_WORK_NODES];
+    out->triangle_tests = w[srt::PG_WORK_TRIANGLES], out->waves = w[srt::PG_WORK_WAVES];
     return SRT_OK;
 }
 

@@ -11,6 +11,8 @@ from .capi import (REFL_ALL, REFL_COUNT_WORK, REFLECTION, ReflectionParams, Refl
                    TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 from .capi import (LIGHT_PROBE_COEFFICIENTS, LIGHT_PROBE_COEFFS, LIGHT_PROBE_COUNT_WORK, LIGHT_PROBE_NORMALIZE, LIGHT_PROBE_RADIANCE, LIGHT_PROBE_RESET,
                    LightProbeParams, LightProbeWork, light_probe_irradiance, light_probe_sphere)  # noqa: F401
+from .capi import (PROBE_GRID_ALBEDO, PROBE_GRID_BAND_WEIGHT_IRRADIANCE, PROBE_GRID_COUNT_WORK, PROBE_GRID_NORMAL_WEIGHT, PROBE_GRID_VISIBILITY,
+                   ProbeGrid, ProbeGridParams, ProbeGridWork, probe_grid, probe_grid_positions)  # noqa: F401
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_PKG, "libsrt_host.so")
@@ -41,6 +43,8 @@ EXPORTS = [
     "srt_host_renderer_reflection_guides", "srt_host_renderer_mirror_history",
     "srt_host_renderer_trace_radiance", "srt_host_renderer_read_radiance", "srt_host_renderer_radiance_work",
     "srt_host_renderer_trace_light_probes", "srt_host_renderer_read_light_probe_output", "srt_host_renderer_light_probe_work",
+    "srt_host_renderer_set_probe_grid", "srt_host_renderer_shade_probe_grid", "srt_host_renderer_read_probe_grid_output",
+    "srt_host_renderer_probe_grid_work",
     "srt_host_renderer_sample_budget", "srt_host_renderer_render_adaptive", "srt_host_renderer_set_sample_counts",
     "srt_host_renderer_read_sample_counts", "srt_host_renderer_adaptive_frame",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
@@ -138,6 +142,10 @@ def load_library():
     L.srt_host_renderer_trace_light_probes.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(LightProbeParams)]
     L.srt_host_renderer_read_light_probe_output.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float)]
     L.srt_host_renderer_light_probe_work.argtypes = [vp, C.POINTER(LightProbeWork)]
+    L.srt_host_renderer_set_probe_grid.argtypes = [vp, C.POINTER(ProbeGrid)]
+    L.srt_host_renderer_shade_probe_grid.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(ProbeGridParams)]
+    L.srt_host_renderer_read_probe_grid_output.argtypes = [vp, C.POINTER(C.c_float)]
+    L.srt_host_renderer_probe_grid_work.argtypes = [vp, C.POINTER(ProbeGridWork)]
     L.srt_host_renderer_sample_budget.argtypes = [vp, C.POINTER(BudgetParams), C.POINTER(C.c_uint64)]
     L.srt_host_renderer_render_adaptive.argtypes = [vp, C.POINTER(AdaptiveParams)]
     L.srt_host_renderer_set_sample_counts.argtypes = [vp, C.c_uint32]
@@ -461,6 +469,43 @@ class Renderer:
         """PathTraceRenderer::lightProbeWork: the work counts of the last trace_light_probes(count_work=True) as a dict."""
         w = LightProbeWork()
         self._ck(self.L.srt_host_renderer_light_probe_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def set_probe_grid(self, origin, spacing=None, counts=None):
+        """PathTraceRenderer::setProbeGrid: the grid shade_probe_grid() interpolates on (a capi.ProbeGrid, or three triples)."""
+        g = probe_grid(origin, spacing, counts)
+        self._ck(self.L.srt_host_renderer_set_probe_grid(self._h, C.byref(g)))
+
+    def shade_probe_grid(self, coefficients=None, visibility=False, normal_weight=False, albedo=False, band_weight=None, rows=None, count_work=False):
+        """PathTraceRenderer::shadeProbeGrid + readProbeGridOutput: copy the (P, 9, 4) float32 coefficients (None: the handle's
+        current ones), render the guides of the band with the current scene and camera, enqueue srt_shade_probe_grid
+        (capi.PathTracer.shade_probe_grid's arguments; rows=None: the renderer's own band) and return the (H, W, 4) float32 result.
+        Waits."""
+        f = C.POINTER(C.c_float)
+        ptr, n = None, 0
+        if coefficients is not None:
+            c = np.ascontiguousarray(coefficients, dtype=np.float32).reshape(-1, 4)
+            if c.shape[0] < LIGHT_PROBE_COEFFS or c.shape[0] % LIGHT_PROBE_COEFFS:
+                raise ValueError("shade_probe_grid: %d float4 of coefficients, want nine per probe" % c.shape[0])
+            ptr, n = c.ctypes.data_as(f), c.shape[0] // LIGHT_PROBE_COEFFS
+        rb, re = (int(rows[0]), int(rows[1])) if rows is not None else (0, 0)
+        bw = band_weight if band_weight is not None else PROBE_GRID_BAND_WEIGHT_IRRADIANCE
+        p = ProbeGridParams(rb, re, (PROBE_GRID_VISIBILITY if visibility else 0) | (PROBE_GRID_NORMAL_WEIGHT if normal_weight else 0) |
+                            (PROBE_GRID_ALBEDO if albedo else 0) | (PROBE_GRID_COUNT_WORK if count_work else 0),
+                            (C.c_float * 3)(float(bw[0]), float(bw[1]), float(bw[2])), (C.c_uint32 * 2)(0, 0))
+        self._ck(self.L.srt_host_renderer_shade_probe_grid(self._h, ptr, n, C.byref(p)))
+        return self.probe_grid_output()
+
+    def probe_grid_output(self):
+        """PathTraceRenderer::readProbeGridOutput: the (H, W, 4) float32 result of the last shade_probe_grid(), rows = scene rows."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_probe_grid_output(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def probe_grid_work(self):
+        """PathTraceRenderer::probeGridWork: the work counts of the last shade_probe_grid(count_work=True) as a dict."""
+        w = ProbeGridWork()
+        self._ck(self.L.srt_host_renderer_probe_grid_work(self._h, C.byref(w)))
         return w.as_dict()
 
     def radiance_work(self):

@@ -234,6 +234,14 @@ int srt_host_renderer_trace_light_probes(srt_host_renderer* h, const float* posi
 }
 int srt_host_renderer_read_light_probe_output(srt_host_renderer* h, uint32_t output, float* dst) { SRT_HOST_TRY(h, h->r->readLightProbeOutput(output, dst)) }
 int srt_host_renderer_light_probe_work(srt_host_renderer* h, srt_light_probe_work* out) { SRT_HOST_TRY(h, *out = h->r->lightProbeWork()) }
+// probe-grid shading with the renderer's scene and camera (PathTraceRenderer::setProbeGrid / shadeProbeGrid: the coefficients are
+// copied unless NULL, the guides rendered, a band of [0, 0) means the renderer's own)
+int srt_host_renderer_set_probe_grid(srt_host_renderer* h, const srt_probe_grid* g) { SRT_HOST_TRY(h, h->r->setProbeGrid(*g)) }
+int srt_host_renderer_shade_probe_grid(srt_host_renderer* h, const float* coefficients, size_t probes, const srt_probe_grid_params* p) {
+    SRT_HOST_TRY(h, h->r->shadeProbeGrid(coefficients, probes, *p))
+}
+int srt_host_renderer_read_probe_grid_output(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->readProbeGridOutput(dst)) }
+int srt_host_renderer_probe_grid_work(srt_host_renderer* h, srt_probe_grid_work* out) { SRT_HOST_TRY(h, *out = h->r->probeGridWork()) }
 // adaptive sampling on the handle's buffers as they stand (srt_sample_budget + srt_get_budget_total, srt_render_adaptive; a band
 // of [0, 0) means the renderer's own), and the two-half workflow (PathTraceRenderer::renderAdaptiveFrame; counts may be NULL)
 int srt_host_renderer_sample_budget(srt_host_renderer* h, const srt_budget_params* p, uint64_t* total) { SRT_HOST_TRY(h, *total = h->r->sampleBudget(*p)) }

@@ -324,6 +324,26 @@ srt_light_probe_work PathTraceRenderer::lightProbeWork() {
     return w;
 }
 
+void PathTraceRenderer::setProbeGrid(const srt_probe_grid& grid) { check(srt_set_probe_grid(ctx_, &grid), "srt_set_probe_grid"); }
+
+void PathTraceRenderer::shadeProbeGrid(const float* coefficients, size_t probes, const srt_probe_grid_params& params) {
+    srt_probe_grid_params s = params;
+    if (s.row_begin == 0 && s.row_end == 0) s.row_begin = row_begin_, s.row_end = row_end_;
+    if (coefficients) check(srt_write_probe_grid_coefficients(ctx_, coefficients, probes), "srt_write_probe_grid_coefficients");
+    FirstHitScope first_hits(*this);  // irradiance AT the first hit
+    RenderGBufferRows(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION | ((s.flags & SRT_PROBE_GRID_ALBEDO) ? SRT_GBUF_ALBEDO : 0u), s.row_begin,
+                      s.row_end);  // (pushes the camera)
+    check(srt_shade_probe_grid(ctx_, &s), "srt_shade_probe_grid");
+}
+
+void PathTraceRenderer::readProbeGridOutput(float* dst_rgba) { check(srt_read_probe_grid_output(ctx_, dst_rgba), "srt_read_probe_grid_output"); }
+
+srt_probe_grid_work PathTraceRenderer::probeGridWork() {
+    srt_probe_grid_work w{};
+    check(srt_get_probe_grid_work(ctx_, &w), "srt_get_probe_grid_work");
+    return w;
+}
+
 uint64_t PathTraceRenderer::sampleBudget(const srt_budget_params& params) {
     check(srt_sample_budget(ctx_, &params), "srt_sample_budget");
     uint64_t total = 0;

@@ -173,6 +173,18 @@ class PathTraceRenderer {
     void traceLightProbes(const float* positions, size_t probes, const float* directions, size_t direction_count, const srt_light_probe_params& params);
     void readLightProbeOutput(uint32_t output, float* dst);
     srt_light_probe_work lightProbeWork();
+    // Probe-grid shading (srt_set_probe_grid + srt_write_probe_grid_coefficients + srt_shade_probe_grid): per-pixel irradiance at the
+    // first hit from light probes on a regular grid.  setProbeGrid sets the grid.  shadeProbeGrid copies `probes` * 9 float4
+    // coefficients (what readLightProbeOutput(SRT_LIGHT_PROBE_COEFFICIENTS) gives for srt_probe_grid_positions' probes; NULL: the
+    // handle's current ones), renders the guides the pass reads (OBJECT, NORMAL_DEPTH, POSITION, and ALBEDO with
+    // SRT_PROBE_GRID_ALBEDO) for the band with the current scene and camera, as renderVisibility, and enqueues the pass; a params
+    // band of [0, 0) (srt_probe_grid_params_default's) means the renderer's own band.  Asynchronous once the coefficients are
+    // copied.  readProbeGridOutput waits and copies the W x H float4 (scene rows); probeGridWork waits and returns the work counts
+    // of a call that had SRT_PROBE_GRID_COUNT_WORK.
+    void setProbeGrid(const srt_probe_grid& grid);
+    void shadeProbeGrid(const float* coefficients, size_t probes, const srt_probe_grid_params& params);
+    void readProbeGridOutput(float* dst_rgba);
+    srt_probe_grid_work probeGridWork();
     // Adaptive sampling (srt_sample_budget, srt_render_adaptive), on the handle's buffers as they stand.  sampleBudget turns the
     // variance buffer, the sample counts, the accumulator and the guides into the per-pixel budget and returns its sum (waits).
     // renderAdaptive enqueues the adaptive render with the renderer's scene and camera; a band of [0, 0) means the renderer's

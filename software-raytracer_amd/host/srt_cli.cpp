@@ -244,6 +244,67 @@ static int trace_probe_file(const Scene& scene, int device, const std::string& i
     }
 }
 
+// --probe-grid OX,OY,OZ,SX,SY,SZ,NX,NY,NZ: false (with nothing written to g) unless the text is nine numbers, the last three integers
+static bool parse_probe_grid(const char* p, srt_probe_grid* g) {
+    char* end = nullptr;
+    for (int k = 0; k < 9; ++k) {
+        if (k < 6) (k < 3 ? g->origin[k] : g->spacing[k - 3]) = std::strtof(p, &end);
+        else {
+            const long n = std::strtol(p, &end, 10);
+            if (n < 1 || n > (1L << 30)) return false;
+            g->counts[k - 6] = (int32_t)n;
+        }
+        if (end == p || (k < 8 ? *end != ',' : *end != 0)) return false;
+        p = end + 1;
+    }
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(g->origin[a]) || !std::isfinite(g->spacing[a]) || !(g->spacing[a] > 0)) return false;
+    return (long long)g->counts[0] * g->counts[1] <= (1LL << 30) && (long long)g->counts[0] * g->counts[1] * g->counts[2] <= (1LL << 30);
+}
+
+// --probe-grid G --probe-directions K --irradiance-out FILE: a real-time preview of the diffuse indirect light.  The first-hit buffers of
+// the W x H frame, light probes (srt_trace_light_probes: K spherical Fibonacci directions, samples 1..`samples`, `bounces`, `seed`,
+// id_base 0) at the grid's positions (srt_probe_grid_positions), then srt_shade_probe_grid over the whole frame with `flags` and the
+// default or the hemisphere band weights.  FILE receives W*H float4, scene rows.
+static int shade_probe_grid_file(const Scene& scene, int device, int W, int H, int fov, const srt_probe_grid& grid, int directions, int samples, int bounces,
+                                 unsigned seed, uint32_t flags, bool hemisphere, const std::string& out) {
+    const size_t np = (size_t)grid.counts[0] * (size_t)grid.counts[1] * (size_t)grid.counts[2];
+    std::vector<float> pos(4 * np), dir(4 * (size_t)directions);
+    if (srt_probe_grid_positions(&grid, pos.data()) != SRT_OK) {
+        std::fprintf(stderr, "--probe-grid: want finite origins, finite spacings > 0, counts >= 1 and at most 2^30 probes\n");
+        return 2;
+    }
+    srt_light_probe_sphere((size_t)directions, dir.data());
+    try {
+        PathTraceRenderer r(device, W, H);
+        r.FOV = fov;
+        r.MAXBOUNCES = bounces;
+        r.seed = seed;
+        r.SetScene(scene);
+        srt_light_probe_params lp{};
+        srt_light_probe_params_default(&lp);
+        lp.sample_count = (uint32_t)samples, lp.max_bounces = bounces, lp.seed = seed;
+        r.traceLightProbes(pos.data(), np, dir.data(), (size_t)directions, lp);
+        std::vector<float> coeff(np * 9 * 4);
+        r.readLightProbeOutput(SRT_LIGHT_PROBE_COEFFICIENTS, coeff.data());
+        srt_probe_grid_params sp{};
+        srt_probe_grid_params_default(&sp);
+        sp.row_begin = 0, sp.row_end = H, sp.flags = flags;
+        if (hemisphere) sp.band_weight[0] = 1.0f, sp.band_weight[1] = 0.5f, sp.band_weight[2] = 0.0f;
+        r.setProbeGrid(grid);
+        r.shadeProbeGrid(coeff.data(), np, sp);
+        std::vector<float> img((size_t)W * H * 4);
+        r.readProbeGridOutput(img.data());
+        if (!write_floats(out, img)) return 1;
+        std::fprintf(stderr, "%dx%d: %zu probes x %d directions, %d samples each, flags 0x%x%s: %s\n", W, H, np, directions, samples, flags,
+                     hemisphere ? " (hemisphere band weights)" : "", out.c_str());
+        return 0;
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+}
+
 static void usage() {
     std::fprintf(stderr,
                  "usage: srt_render --scene FILE [--width 1280] [--height 720] [--spp 32] [--bounces 2]\n"
@@ -257,6 +318,8 @@ static void usage() {
                  "       srt_render --scene FILE --rays IN.f32 --rays-out OUT.bin --radiance N [--bounces B] [--seed S] [--rays-normalize]\n"
                  "       srt_render --scene FILE --probes IN.f32 --probe-directions K|FILE.f32 --probes-out OUT.bin [--radiance N]\n"
                  "                  [--probe-radiance-out FILE] [--bounces B] [--seed S]\n"
+                 "       srt_render --scene FILE --probe-grid OX,OY,OZ,SX,SY,SZ,NX,NY,NZ --probe-directions K [--radiance N] --irradiance-out FILE\n"
+                 "                  [--probe-visibility] [--probe-normal-weight] [--probe-albedo] [--probe-hemisphere] [--width W] [--height H] ...\n"
                  "       srt_render --scene FILE --adaptive ROUNDS [--adaptive-threshold T] [--adaptive-max M] [--counts-out FILE] [--spp N] ...\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
@@ -307,6 +370,13 @@ static void usage() {
                  "             FILE.f32: K records of 4 float32 (x y z weight); --radiance N: samples per ray (1..4096, default 16) of\n"
                  "             --bounces bounces; --probes-out receives P x 9 float4 SH coefficients, --probe-radiance-out the P x K float4\n"
                  "             running means; single device, not with --rays, no frame options\n"
+                 "  --probe-grid: instead of rendering a frame, shade it from a grid of light probes (srt_shade_probe_grid): probe (0,0,0) at\n"
+                 "             OX,OY,OZ, spacings SX,SY,SZ > 0, NX x NY x NZ probes; the first-hit buffers of the frame are rendered, the probes traced\n"
+                 "             (--probe-directions K: 1..4096 spherical Fibonacci directions; --radiance N: samples per ray, 1..4096, default 16;\n"
+                 "             --bounces, --seed) and --irradiance-out receives W x H float4 (r g b, a = surviving weight), scene rows;\n"
+                 "             --probe-visibility: only probes the surface sees; --probe-normal-weight: favour probes in front of the surface;\n"
+                 "             --probe-albedo: times the albedo guide; --probe-hemisphere: band weights 1, 0.5, 0 (the mean over the hemisphere)\n"
+                 "             instead of the cosine-weighted integral; single device, not with --rays, --probes, --temporal or --devices\n"
                  "  --adaptive ROUNDS: adaptive sampling in place of the uniform frame: an even --spp is the uniform seed, split into two\n"
                  "             independently seeded halves; then ROUNDS (1..64) rounds of srt_variance, srt_sample_budget and srt_render_adaptive\n"
                  "             on both halves, and the mean of the halves goes to --out; the frame's total samples are printed on stderr;\n"
@@ -335,6 +405,8 @@ int main(int argc, char** argv) {
     int radiance = 0;
     bool radiance_given = false;
     std::string probes_in, probes_out, probe_directions, probe_radiance_out;
+    std::string probe_grid_arg, irradiance_out;
+    bool probe_visibility = false, probe_normal_weight = false, probe_albedo = false, probe_hemisphere = false;
     int adaptive = 0, adaptive_max = 0;
     bool adaptive_given = false, adaptive_threshold_given = false, adaptive_max_given = false;
     float adaptive_threshold = 0;
@@ -404,6 +476,12 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--probes-out")) probes_out = need("--probes-out");
         else if (!std::strcmp(argv[i], "--probe-directions")) probe_directions = need("--probe-directions");
         else if (!std::strcmp(argv[i], "--probe-radiance-out")) probe_radiance_out = need("--probe-radiance-out");
+        else if (!std::strcmp(argv[i], "--probe-grid")) probe_grid_arg = need("--probe-grid");
+        else if (!std::strcmp(argv[i], "--irradiance-out")) irradiance_out = need("--irradiance-out");
+        else if (!std::strcmp(argv[i], "--probe-visibility")) probe_visibility = true;
+        else if (!std::strcmp(argv[i], "--probe-normal-weight")) probe_normal_weight = true;
+        else if (!std::strcmp(argv[i], "--probe-albedo")) probe_albedo = true;
+        else if (!std::strcmp(argv[i], "--probe-hemisphere")) probe_hemisphere = true;
         else if (!std::strcmp(argv[i], "--adaptive")) adaptive = std::atoi(need("--adaptive")), adaptive_given = true;
         else if (!std::strcmp(argv[i], "--adaptive-threshold")) adaptive_threshold = std::strtof(need("--adaptive-threshold"), nullptr), adaptive_threshold_given = true;
         else if (!std::strcmp(argv[i], "--adaptive-max")) adaptive_max = std::atoi(need("--adaptive-max")), adaptive_max_given = true;
@@ -469,11 +547,46 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--rays, --rays-out, --rays-normalize and --any-hit go together: --rays IN.f32 --rays-out OUT.bin [--rays-normalize] [--any-hit]\n");
         return 2;
     }
-    if (radiance_given && probes_in.empty() && (rays_in.empty() || rays_any_hit || radiance < 1 || radiance > 4096 || bounces < 0)) {
+    srt_probe_grid probe_grid{};
+    int probe_grid_directions = 0;
+    if (!probe_grid_arg.empty() || !irradiance_out.empty() || probe_visibility || probe_normal_weight || probe_albedo || probe_hemisphere) {
+        if (probe_grid_arg.empty()) {
+            std::fprintf(stderr, "--irradiance-out, --probe-visibility, --probe-normal-weight, --probe-albedo and --probe-hemisphere need --probe-grid\n");
+            return 2;
+        }
+        if (!parse_probe_grid(probe_grid_arg.c_str(), &probe_grid)) {
+            std::fprintf(stderr, "--probe-grid wants OX,OY,OZ,SX,SY,SZ,NX,NY,NZ: a finite origin, finite spacings > 0, integer counts >= 1, at most 2^30 probes\n");
+            return 2;
+        }
+        if (irradiance_out.empty()) {
+            std::fprintf(stderr, "--probe-grid needs --irradiance-out FILE\n");
+            return 2;
+        }
+        if (!rays_in.empty() || !probes_in.empty() || !probes_out.empty() || !probe_radiance_out.empty() || temporal || !devices.empty()) {
+            std::fprintf(stderr, "--probe-grid shades a frame from light probes: single device, not with %s\n",
+                         !rays_in.empty() ? "--rays" : temporal ? "--temporal" : !devices.empty() ? "--devices" : "--probes");
+            return 2;
+        }
+        probe_grid_directions = probe_directions.find_first_not_of("0123456789") == std::string::npos ? std::atoi(probe_directions.c_str()) : 0;
+        if (probe_directions.empty() || probe_grid_directions < 1 || probe_grid_directions > (int)SRT_LIGHT_PROBE_MAX_DIRECTIONS) {
+            std::fprintf(stderr, "--probe-grid needs --probe-directions K with K in 1..4096\n");
+            return 2;
+        }
+        if ((radiance_given && (radiance < 1 || radiance > 4096)) || bounces < 0) {
+            std::fprintf(stderr, "--probe-grid: --radiance N takes 1..4096 samples and --bounces must be >= 0\n");
+            return 2;
+        }
+        if (steps > 1 || aa_given || !gbuffer.empty() || !denoise.empty() || !upsample.empty() || !denoise_variance.empty() || adaptive_given || ao_given ||
+            sun_visibility || !vis_out.empty() || reflection_guides || !reflection_out.empty()) {
+            std::fprintf(stderr, "--probe-grid shades a frame from light probes instead of rendering it: no other frame options\n");
+            return 2;
+        }
+    }
+    if (radiance_given && probes_in.empty() && probe_grid_arg.empty() && (rays_in.empty() || rays_any_hit || radiance < 1 || radiance > 4096 || bounces < 0)) {
         std::fprintf(stderr, "--radiance N (1..4096) needs --rays and --rays-out, a --bounces >= 0, and does not go with --any-hit\n");
         return 2;
     }
-    if (!probes_in.empty() || !probes_out.empty() || !probe_directions.empty() || !probe_radiance_out.empty()) {
+    if (!probes_in.empty() || !probes_out.empty() || (!probe_directions.empty() && probe_grid_arg.empty()) || !probe_radiance_out.empty()) {
         if (probes_in.empty() || probes_out.empty() || probe_directions.empty()) {
             std::fprintf(stderr, "--probes, --probe-directions, --probes-out and --probe-radiance-out go together: --probes IN.f32 --probe-directions K|FILE.f32 "
                                  "--probes-out OUT.bin [--radiance N] [--probe-radiance-out FILE]\n");
@@ -573,6 +686,11 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--move-object: the scene has no object %zu\n", m.index);
             return 2;
         }
+    if (!probe_grid_arg.empty())
+        return shade_probe_grid_file(scene, device, W, H, fov, probe_grid, probe_grid_directions, radiance_given ? radiance : 16, bounces, seed,
+                                     (probe_visibility ? SRT_PROBE_GRID_VISIBILITY : 0u) | (probe_normal_weight ? SRT_PROBE_GRID_NORMAL_WEIGHT : 0u) |
+                                         (probe_albedo ? SRT_PROBE_GRID_ALBEDO : 0u),
+                                     probe_hemisphere, irradiance_out);
     if (!probes_in.empty()) return trace_probe_file(scene, device, probes_in, probe_directions, probes_out, probe_radiance_out, radiance_given ? radiance : 16, bounces, seed);
     if (!rays_in.empty()) return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize, rays_any_hit, radiance_given ? radiance : 0, bounces, seed);
     auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {
