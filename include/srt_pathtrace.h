@@ -1637,6 +1637,120 @@ int srt_get_probe_grid_work(srt_context* ctx, srt_probe_grid_work* out);
  * reference's interface. */
 int srt_selftest_arith(int device, uint32_t seed, uint64_t vectors, uint64_t* mismatches);
 
+/* ---- probe depth moments: a filtered estimate of what a probe sees (ABI 7, backward compatible) ---------------------------------
+ * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of
+ * them runs what it ran before, bit for bit.
+ *
+ * SRT_PROBE_GRID_VISIBILITY answers "does this probe see this point" with one exact any-hit query per corner per pixel per frame:
+ * a hard bit whose cost grows with the scene.  srt_trace_probe_depth instead gives every probe an octahedral map of R x R texels
+ * that holds, per texel direction, the weighted mean and mean square of the distance to the nearest surface over the K shared
+ * directions, once per probe update.  srt_shade_probe_grid_depth (the next block) turns the two moments into a smooth weight.
+ * The probes and directions are the current ones of the light-probe block (srt_write_light_probes, srt_bind_light_probes,
+ * srt_write_light_probe_directions, srt_bind_light_probe_directions): there are no new input calls.
+ *
+ * Rules.  All arithmetic is binary32 without contraction.
+ * 1. Texel directions.  srt_probe_depth_texels gives texel (i, j), 0 <= i, j < R, the index j*R + i.  In double:
+ *    u = (2i + 1) / R - 1, v = (2j + 1) / R - 1, z = 1 - |u| - |v|; if z < 0: (x, y) = ((1 - |v|) * sgn u, (1 - |u|) * sgn v),
+ *    otherwise (x, y) = (u, v), where sgn of a number >= 0 is +1 and -1 otherwise; (x, y, z) is normalised in double, each
+ *    component is rounded once to binary32, and w = 0.  The device reads this table; it does not recompute it.
+ * 2. Distance.  Ray (p, k) has origin position_p and direction d_k, or float3::Normalized(d_k) with SRT_PROBE_DEPTH_NORMALIZE
+ *    (as SRT_RAYS_NORMALIZE).  Let t be what srt_trace_rays writes into SRT_GBUF_NORMAL_DEPTH.w for that ray: the hit distance,
+ *    or +inf on a miss.  r = !(t > 0) ? 0 : (t > max_distance ? max_distance : t).  A probe inside a sphere gets the negative
+ *    distance Sphere::Raytrace reports, so r = 0; a NaN direction misses, so r = max_distance.  DISTANCES[p*K + k] = r.
+ * 3. Accumulation.  For probe p and texel tau with direction e, M1 = M2 = Wt = Ft = +0.0f; then for k = 0 .. K - 1 ascending:
+ *    c = (e.x*d.x + e.y*d.y) + e.z*d.z with d as traced.  If c > 0: w = c, then s times w = w*w, then w = w * d_k.w (the
+ *    direction's weight, unscaled); M1 = M1 + w*r; M2 = M2 + w*(r*r); Wt = Wt + w; and if r >= max_distance, Ft = Ft + w.
+ *    A direction with !(c > 0) contributes nothing.
+ * 4. Texel.  If Wt > 0: MOMENTS[p*R*R + tau] = (M1 / Wt, M2 / Wt, Wt, Ft / Wt).  Otherwise (max_distance,
+ *    max_distance*max_distance, 0, 1).
+ * 5. Determinism.  No atomics reach an output; the order of rule 3 is the only order; repeated calls give the same bits.
+ * 6. Outputs, a bit mask: SRT_PROBE_DEPTH_MOMENTS, P*R*R float4, and SRT_PROBE_DEPTH_DISTANCES, P*K float, optional.  Each is
+ *    the handle's own buffer (allocated on first use, grown when a call needs more) or the caller's: srt_bind_probe_depth_output
+ *    binds a DEVICE buffer, NULL = own, under srt_bind_light_probe_output's rules.  Without DISTANCES nothing of size P*K is
+ *    allocated.  srt_read_probe_depth_output waits, then copies what the last srt_trace_probe_depth wrote of that output, from
+ *    the buffer it wrote; SRT_ERR_STATE when the last trace did not write it.  Asynchrony: as rule 8 of the light-probe block;
+ *    positions, directions and output buffers are those current at enqueue.  The call leaves alone everything
+ *    srt_trace_light_probes leaves alone, and the light-probe outputs and records as well.
+ * 7. Errors, all found before anything is touched, in this order: SRT_ERR_STATE before srt_set_scene; SRT_ERR_INVALID_ARG for
+ *    unknown flags or outputs, outputs == 0, a resolution not in {4, 8, 16}, sharpness > 6, a max_distance that is NaN, infinite
+ *    or <= 0, or a non-zero reserved; SRT_ERR_STATE with no positions or no directions; SRT_ERR_INVALID_ARG for P*K > 2^30 or
+ *    P*R*R > 2^30; SRT_ERR_OOM when a buffer cannot be had.
+ * 8. Work counts.  With SRT_PROBE_DEPTH_COUNT_WORK the launch counts, deterministically: its probes (P), its rays (P*K), the rays
+ *    with r >= max_distance, the wave-level closest-hit invocations and the waves of the launch.  One vector atomic per wave at
+ *    the end; without the flag there are no atomics at all.  srt_get_probe_depth_work waits and copies the record of the last
+ *    srt_trace_probe_depth; SRT_ERR_STATE unless that trace had the flag. */
+#define SRT_PROBE_DEPTH_MOMENTS 1u    /* output: P*R*R float4 */
+#define SRT_PROBE_DEPTH_DISTANCES 2u  /* output: P*K float, optional */
+#define SRT_PROBE_DEPTH_NORMALIZE 1u  /* flags: as SRT_RAYS_NORMALIZE */
+#define SRT_PROBE_DEPTH_COUNT_WORK 2u /* flags: fill srt_probe_depth_work for this call */
+
+typedef struct srt_probe_depth_params { /* 24 bytes */
+    uint32_t resolution;                /* R: 4, 8 or 16 texels per side of a probe's octahedral map */
+    uint32_t sharpness;                 /* s, 0..6: a direction weighs cos^(2^s) */
+    float max_distance;                 /* > 0, finite */
+    uint32_t flags;                     /* SRT_PROBE_DEPTH_NORMALIZE | _COUNT_WORK */
+    uint32_t outputs;                   /* SRT_PROBE_DEPTH_MOMENTS | _DISTANCES, not 0 */
+    uint32_t reserved;                  /* 0 */
+} srt_probe_depth_params;
+
+typedef struct srt_probe_depth_work { /* 48 bytes */
+    uint32_t valid, reserved;         /* 1, 0 */
+    uint64_t probes, rays;            /* P; P*K */
+    uint64_t far_rays;                /* rays with r >= max_distance */
+    uint64_t wave_calls;              /* wave-level closest-hit invocations: P * ceil(K / 64) */
+    uint64_t waves;                   /* waves of the launch */
+} srt_probe_depth_work;
+
+/* resolution 16, sharpness 5, max_distance 10000.0f, flags 0, outputs SRT_PROBE_DEPTH_MOMENTS, reserved 0 (pure host). */
+int srt_probe_depth_params_default(srt_probe_depth_params* out);
+/* Pure host, no device: fills resolution * resolution float4 with rule 1's texel directions.  SRT_ERR_INVALID_ARG for a resolution
+ * not in {4, 8, 16} or a NULL dst. */
+int srt_probe_depth_texels(uint32_t resolution, float* dst);
+int srt_trace_probe_depth(srt_context* ctx, const srt_probe_depth_params* params);
+int srt_bind_probe_depth_output(srt_context* ctx, uint32_t output, void* d_ptr);
+int srt_read_probe_depth_output(srt_context* ctx, uint32_t output, void* dst);
+int srt_get_probe_depth_work(srt_context* ctx, srt_probe_depth_work* out);
+
+/* ---- probe-grid shading with the filtered visibility test (ABI 7, backward compatible) ------------------------------------------
+ * srt_shade_probe_grid_depth is srt_shade_probe_grid rule for rule — the same grid, coefficients, guides, band and band weights,
+ * the same output slot (srt_bind_probe_grid_output, srt_read_probe_grid_output) and the same "last call" record
+ * (srt_get_probe_grid_work serves both calls) — with the probe-grid block's rule 7 replaced by rule 7b below, applied after rule 6.
+ * Accepted flags: SRT_PROBE_GRID_NORMAL_WEIGHT, _ALBEDO and _COUNT_WORK.  SRT_PROBE_GRID_VISIBILITY is SRT_ERR_INVALID_ARG here,
+ * found where an unknown flag is: the exact and the filtered test exclude each other.  srt_shade_probe_grid itself is unchanged.
+ *
+ * The depth maps are P = nx*ny*nz probes of R*R float4 in SRT_PROBE_DEPTH_MOMENTS' layout (probe k's texel tau at k*R*R + tau;
+ * the x and y lanes are read).  srt_write_probe_grid_depth copies them from the host into the handle's own array and waits;
+ * srt_bind_probe_grid_depth binds a DEVICE array, does not copy and does not wait (what srt_bind_probe_depth_output filled can
+ * be bound here); NULL, 0 returns to the own array.  Both want R in {4, 8, 16}, 1 <= probes and probes*R*R <= 2^30, and return
+ * SRT_ERR_INVALID_ARG otherwise, leaving the previous maps.
+ *
+ * 7b. Filtered visibility, for a corner that reached rule 7 (weight > 0 and L > 0), with d and L of rule 5 and the clamped probe
+ *    index k of rule 8:
+ *    Texel lookup.  q = (-d.x, -d.y, -d.z); s = (|q.x| + |q.y|) + |q.z|; u = q.x / s, v = q.y / s.  If q.z < 0:
+ *    u' = (1 - |v|) * sgn u and v' = (1 - |u|) * sgn v, then (u, v) = (u', v'); sgn of a number >= 0 is +1, otherwise -1.
+ *    Per axis, with g standing for u or v: a = ((g*0.5f) + 0.5f) * (float)R; a = !(a > 0) ? 0 : (a > (float)(R-1) ? (float)(R-1) : a);
+ *    the index is (int)a.  tau = j*R + i with i taken from u and j from v.
+ *    Moments.  (m1, m2) = the x and y lanes of depth[k*R*R + tau]: no load can leave the array.
+ *    Weight.  Only if L > m1 + bias: var = |m2 - m1*m1|; var = var > min_variance ? var : min_variance; D = L - m1;
+ *    ch = var / (var + D*D); t = t * ((ch*ch)*ch).
+ *    Skip.  A corner with !(t > 0) is skipped.
+ *    Work counts.  `segments` holds the corners that reach 7b, `open` those that survive it; the three test counters are 0.
+ *    Extra errors, after all of rule 16's: SRT_ERR_STATE for no depth maps, or for a depth probe count other than nx*ny*nz; then
+ *    SRT_ERR_INVALID_ARG for a bias that is NaN, infinite or < 0, a min_variance that is NaN, infinite or <= 0, or a non-zero
+ *    reserved word.
+ *    Pinned domain.  Finite moments are pinned bit for bit.  Other values give some value and no fault. */
+typedef struct srt_probe_grid_depth_params { /* 16 bytes */
+    float bias;                              /* >= 0, finite */
+    float min_variance;                      /* > 0, finite */
+    uint32_t reserved[2];                    /* 0 */
+} srt_probe_grid_depth_params;
+
+/* bias 0.0f, min_variance 1e-4f, reserved 0 (pure host). */
+int srt_probe_grid_depth_params_default(srt_probe_grid_depth_params* out);
+int srt_write_probe_grid_depth(srt_context* ctx, const float* moments, size_t probes, uint32_t resolution);
+int srt_bind_probe_grid_depth(srt_context* ctx, const void* d_ptr, size_t probes, uint32_t resolution);
+int srt_shade_probe_grid_depth(srt_context* ctx, const srt_probe_grid_params* params, const srt_probe_grid_depth_params* depth);
+
 #ifdef __cplusplus
 }
 #endif

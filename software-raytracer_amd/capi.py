@@ -50,6 +50,10 @@ LIGHT_PROBE_COEFFS = 9
 PROBE_GRID_VISIBILITY, PROBE_GRID_NORMAL_WEIGHT, PROBE_GRID_ALBEDO, PROBE_GRID_COUNT_WORK = 1, 2, 4, 8
 PROBE_GRID_BAND_WEIGHT_IRRADIANCE = (3.14159274, 2.09439516, 0.785398185)  # srt_light_probe_irradiance's: the cosine-weighted integral
 PROBE_GRID_BAND_WEIGHT_HEMISPHERE = (1.0, 0.5, 0.0)  # the mean over the hemisphere around the normal
+# probe depth moments (srt_trace_probe_depth): the outputs and flags of srt_probe_depth_params, the accepted resolutions
+PROBE_DEPTH_MOMENTS, PROBE_DEPTH_DISTANCES = 1, 2
+PROBE_DEPTH_NORMALIZE, PROBE_DEPTH_COUNT_WORK = 1, 2
+PROBE_DEPTH_RESOLUTIONS = (4, 8, 16)
 # adaptive sampling (srt_render_adaptive, srt_sample_budget): the flags, the limits of max_samples / max_budget, the last frame
 ADAPTIVE_KEEP_COUNTS, ADAPTIVE_COUNT_WORK = 1, 2
 ADAPTIVE_MAX_SAMPLES = 4096
@@ -110,6 +114,9 @@ EXPORTS = [
     "srt_probe_grid_positions", "srt_probe_grid_params_default", "srt_set_probe_grid", "srt_write_probe_grid_coefficients",
     "srt_bind_probe_grid_coefficients", "srt_shade_probe_grid", "srt_bind_probe_grid_output", "srt_read_probe_grid_output",
     "srt_get_probe_grid_work",
+    "srt_probe_depth_params_default", "srt_probe_depth_texels", "srt_trace_probe_depth", "srt_bind_probe_depth_output",
+    "srt_read_probe_depth_output", "srt_get_probe_depth_work",
+    "srt_probe_grid_depth_params_default", "srt_write_probe_grid_depth", "srt_bind_probe_grid_depth", "srt_shade_probe_grid_depth",
 ]
 
 
@@ -349,6 +356,26 @@ class ProbeGridWork(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+class ProbeDepthParams(C.Structure):
+    """srt_probe_depth_params: the map resolution, the sharpness of the direction weight, the distance clamp, PROBE_DEPTH_* flags and outputs."""
+    _fields_ = [("resolution", C.c_uint32), ("sharpness", C.c_uint32), ("max_distance", C.c_float), ("flags", C.c_uint32),
+                ("outputs", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ProbeDepthWork(C.Structure):
+    """srt_probe_depth_work: what the last counting srt_trace_probe_depth traced."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("rays", C.c_uint64), ("far_rays", C.c_uint64),
+                ("wave_calls", C.c_uint64), ("waves", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class ProbeGridDepthParams(C.Structure):
+    """srt_probe_grid_depth_params: the bias and the variance floor of the filtered visibility test."""
+    _fields_ = [("bias", C.c_float), ("min_variance", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 class UpdateInfo(C.Structure):
     """srt_update_info: what the last successful srt_update_scene did to the mesh image."""
     _fields_ = [("path", C.c_int32), ("reason", C.c_int32), ("levels", C.c_int32), ("triangles", C.c_uint32), ("nodes", C.c_uint32),
@@ -541,6 +568,16 @@ def open_library(path):
     L.srt_bind_probe_grid_output.argtypes = [ctx, C.c_void_p]
     L.srt_read_probe_grid_output.argtypes = [ctx, C.POINTER(C.c_float)]
     L.srt_get_probe_grid_work.argtypes = [ctx, C.POINTER(ProbeGridWork)]
+    L.srt_probe_depth_params_default.argtypes = [C.POINTER(ProbeDepthParams)]
+    L.srt_probe_depth_texels.argtypes = [C.c_uint32, C.POINTER(C.c_float)]
+    L.srt_trace_probe_depth.argtypes = [ctx, C.POINTER(ProbeDepthParams)]
+    L.srt_bind_probe_depth_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_read_probe_depth_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_get_probe_depth_work.argtypes = [ctx, C.POINTER(ProbeDepthWork)]
+    L.srt_probe_grid_depth_params_default.argtypes = [C.POINTER(ProbeGridDepthParams)]
+    L.srt_write_probe_grid_depth.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t, C.c_uint32]
+    L.srt_bind_probe_grid_depth.argtypes = [ctx, C.c_void_p, C.c_size_t, C.c_uint32]
+    L.srt_shade_probe_grid_depth.argtypes = [ctx, C.POINTER(ProbeGridParams), C.POINTER(ProbeGridDepthParams)]
     L.srt_set_sample_counts.argtypes = [ctx, C.c_uint32]
     L.srt_write_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
     L.srt_read_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
@@ -767,6 +804,20 @@ def light_probe_sphere(count, lib=None):
     rc = L.srt_light_probe_sphere(n, out.ctypes.data_as(C.POINTER(C.c_float)))
     if rc:
         raise SrtError(rc, "srt_light_probe_sphere(%d)" % n)
+    return out
+
+
+def probe_depth_texels(resolution, lib=None):
+    """srt_probe_depth_texels: the unit directions of the R x R texels of a probe's octahedral depth map as an (R*R, 4) float32
+    array, texel (i, j) at index j*R + i, w = 0.  Pure host."""
+    L = lib or load_library()
+    r = int(resolution)
+    if r not in PROBE_DEPTH_RESOLUTIONS:
+        raise SrtError(ERR_INVALID_ARG, "srt_probe_depth_texels: want a resolution of 4, 8 or 16, got %d" % r)
+    out = np.empty((r * r, 4), dtype=np.float32)
+    rc = L.srt_probe_depth_texels(r, out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc:
+        raise SrtError(rc, "srt_probe_depth_texels(%d)" % r)
     return out
 
 
@@ -1486,6 +1537,154 @@ class PathTracer:
         w = ProbeGridWork()
         self._ck(self.L.srt_get_probe_grid_work(self._h, C.byref(w)))
         return w.as_dict()
+
+    # ---- probe depth moments and the filtered probe-grid shading -------------------------------
+    def trace_probe_depth(self, positions=None, directions=None, resolution=None, sharpness=None, max_distance=None, normalize=False,
+                          count_work=False, moments=True, distances=False, flags=0, reserved=0):
+        """srt_trace_probe_depth: for each of P probe positions an octahedral map of `resolution` x `resolution` texels (default 16)
+        holding the weighted mean and mean square of the distance to the nearest surface over the K shared directions, each
+        direction weighing cos^(2^sharpness) (default 5) times its quadrature weight, distances clamped to `max_distance` (default
+        10000).  `positions` / `directions`: as trace_light_probes() takes them (they are the same current arrays); None: the
+        current ones.  moments / distances: the outputs (probe_depth_output()); normalize: SRT_PROBE_DEPTH_NORMALIZE; count_work:
+        SRT_PROBE_DEPTH_COUNT_WORK (probe_depth_work() then reads the record).  Asynchronous, like render()."""
+        L = self.L
+        if positions is not None:
+            self._probe_count, self._probe_bound = self._light_probe_input("trace_probe_depth(positions)", positions, L.srt_write_light_probes,
+                                                                           L.srt_bind_light_probes, 1 << 30)
+        if directions is not None:
+            if isinstance(directions, (int, np.integer)):
+                directions = light_probe_sphere(int(directions), lib=L)
+            self._probe_dir_count, self._probe_dir_bound = self._light_probe_input("trace_probe_depth(directions)", directions,
+                                                                                   L.srt_write_light_probe_directions,
+                                                                                   L.srt_bind_light_probe_directions, LIGHT_PROBE_MAX_DIRECTIONS)
+        p = ProbeDepthParams()
+        self._ck(L.srt_probe_depth_params_default(C.byref(p)))
+        if resolution is not None:
+            p.resolution = int(resolution)
+        if sharpness is not None:
+            p.sharpness = int(sharpness)
+        if max_distance is not None:
+            p.max_distance = float(max_distance)
+        p.flags = int(flags) | (PROBE_DEPTH_NORMALIZE if normalize else 0) | (PROBE_DEPTH_COUNT_WORK if count_work else 0)
+        p.outputs = (PROBE_DEPTH_MOMENTS if moments else 0) | (PROBE_DEPTH_DISTANCES if distances else 0)
+        p.reserved = int(reserved)
+        np_, nk = getattr(self, "_probe_count", None), getattr(self, "_probe_dir_count", None)
+        if np_ is not None and nk is not None:
+            bound = self.__dict__.get("_probe_depth_bound", {})
+            for bit, need in ((PROBE_DEPTH_MOMENTS, np_ * int(p.resolution) ** 2 * 4), (PROBE_DEPTH_DISTANCES, np_ * nk)):
+                t = bound.get(bit)
+                if (p.outputs & bit) and t is not None and t.numel() < need:
+                    raise ValueError("trace_probe_depth: the bound tensor holds %d floats, the call writes %d" % (t.numel(), need))
+        self._ck(L.srt_trace_probe_depth(self._h, C.byref(p)))
+        self._probe_depth_traced = (np_, nk, int(p.resolution))
+
+    def bind_probe_depth_output(self, output, tensor):
+        """srt_bind_probe_depth_output: write output "moments" (P*R*R float4: a tensor (M, 4)) or "distances" (P*K float: a tensor
+        (M,)) into a float32 torch tensor on this tracer's device, contiguous, at least that large (checked by trace_probe_depth);
+        None: the handle's own buffer.  The caller keeps the tensor alive until the traces have finished."""
+        bit = {"moments": PROBE_DEPTH_MOMENTS, "distances": PROBE_DEPTH_DISTANCES}.get(output, output)
+        if tensor is not None:
+            import torch
+
+            if not isinstance(tensor, torch.Tensor):
+                raise TypeError("bind_probe_depth_output: expected a torch.Tensor, got %s" % type(tensor).__name__)
+            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
+            if m < 1:
+                raise ValueError("bind_probe_depth_output: shape %s, want at least one element" % (tuple(tensor.shape),))
+            ptr = self._tensor_ptr("bind_probe_depth_output", tensor, np.float32, (m, 4) if bit == PROBE_DEPTH_MOMENTS else (m,))
+        else:
+            ptr = None
+        self._ck(self.L.srt_bind_probe_depth_output(self._h, int(bit), ptr))
+        bound = self.__dict__.setdefault("_probe_depth_bound", {})
+        if tensor is None:
+            bound.pop(bit, None)
+        else:
+            bound[bit] = tensor
+
+    def probe_depth_output(self, output="moments"):
+        """srt_read_probe_depth_output: "moments": (P, R*R, 4) float32 (mean, mean square, weight, share at max_distance);
+        "distances": (P, K) float32 of the last trace_probe_depth().  Waits."""
+        bit = {"moments": PROBE_DEPTH_MOMENTS, "distances": PROBE_DEPTH_DISTANCES}.get(output, output)
+        t = getattr(self, "_probe_depth_traced", None)
+        if t is None or t[0] is None or t[1] is None:
+            raise SrtError(ERR_STATE, "probe_depth_output(): no trace_probe_depth() yet")
+        shape = (t[0], t[2] * t[2], 4) if bit == PROBE_DEPTH_MOMENTS else (t[0], t[1])
+        return self._read_image(self.L.srt_read_probe_depth_output, shape, np.float32, int(bit))
+
+    def probe_depth_work(self):
+        """srt_get_probe_depth_work: the work counts of the last trace_probe_depth(count_work=True) as a dict.  Waits."""
+        w = ProbeDepthWork()
+        self._ck(self.L.srt_get_probe_depth_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def bind_probe_grid_depth(self, moments, resolution=None):
+        """srt_write_probe_grid_depth / srt_bind_probe_grid_depth: the depth maps shade_probe_grid_depth() reads, in
+        probe_depth_output("moments")'s layout.  numpy (P, R*R, 4) or (P*R*R, 4) float32: written; a torch tensor (P*R*R, 4) on
+        this tracer's device: bound, no copy (what bind_probe_depth_output("moments", t) filled); None: back to the own array.
+        `resolution`: R (default: from a three-dimensional array's shape, else 16)."""
+        L = self.L
+        if moments is None:
+            self._ck(L.srt_bind_probe_grid_depth(self._h, None, 0, 0))
+            self._probe_grid_depth_bound = None
+            return
+        a = moments
+        if isinstance(a, np.ndarray) and a.ndim == 3:
+            if resolution is None:
+                resolution = int(round(a.shape[1] ** 0.5))
+            a = a.reshape(-1, 4)
+        r = 16 if resolution is None else int(resolution)
+        kind, arr, n = self._ray_array("bind_probe_grid_depth(moments)", a)
+        if r < 1 or n % (r * r):
+            raise ValueError("bind_probe_grid_depth(moments): %d float4, want %d per probe" % (n, r * r))
+        if kind == "host":
+            self._ck(L.srt_write_probe_grid_depth(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n // (r * r), r))
+            self._probe_grid_depth_bound = None
+        else:
+            self._ck(L.srt_bind_probe_grid_depth(self._h, C.c_void_p(arr.data_ptr()), n // (r * r), r))
+            self._probe_grid_depth_bound = arr  # (a bound tensor stays referenced for as long as it is bound)
+
+    def shade_probe_grid_depth(self, coefficients=None, moments=None, resolution=None, bias=None, min_variance=None, normal_weight=False,
+                               albedo=False, band_weight=None, rows=None, count_work=False, output=None, flags=0, reserved=(0, 0),
+                               depth_reserved=(0, 0)):
+        """srt_shade_probe_grid_depth: shade_probe_grid() with the filtered visibility test in place of the exact one: every corner
+        probe is weighted by Chebyshev's bound on "the probe sees at least as far as this point" from its depth map.  `moments` /
+        `resolution`: as bind_probe_grid_depth() (None: the current maps); `bias` (default 0) and `min_variance` (default 1e-4): the
+        test's parameters; everything else as shade_probe_grid().  probe_grid_output() and probe_grid_work() read the result."""
+        L = self.L
+        if coefficients is not None:
+            a = coefficients
+            if isinstance(a, np.ndarray) and a.ndim == 3:
+                a = a.reshape(-1, 4)
+            kind, arr, n = self._ray_array("shade_probe_grid_depth(coefficients)", a)
+            if n % LIGHT_PROBE_COEFFS:
+                raise ValueError("shade_probe_grid_depth(coefficients): %d float4, want nine per probe" % n)
+            if kind == "host":
+                self._ck(L.srt_write_probe_grid_coefficients(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n // LIGHT_PROBE_COEFFS))
+                self._probe_grid_bound = None
+            else:
+                self._ck(L.srt_bind_probe_grid_coefficients(self._h, C.c_void_p(arr.data_ptr()), n // LIGHT_PROBE_COEFFS))
+                self._probe_grid_bound = arr
+        if moments is not None:
+            self.bind_probe_grid_depth(moments, resolution)
+        if output is not None:
+            self.bind_probe_grid_output(output)
+        p = ProbeGridParams()
+        self._ck(L.srt_probe_grid_params_default(C.byref(p)))
+        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
+        p.flags = (int(flags) | (PROBE_GRID_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_GRID_ALBEDO if albedo else 0) |
+                   (PROBE_GRID_COUNT_WORK if count_work else 0))
+        if band_weight is not None:
+            for b in range(3):
+                p.band_weight[b] = float(band_weight[b])
+        p.reserved[0], p.reserved[1] = int(reserved[0]), int(reserved[1])
+        d = ProbeGridDepthParams()
+        self._ck(L.srt_probe_grid_depth_params_default(C.byref(d)))
+        if bias is not None:
+            d.bias = float(bias)
+        if min_variance is not None:
+            d.min_variance = float(min_variance)
+        d.reserved[0], d.reserved[1] = int(depth_reserved[0]), int(depth_reserved[1])
+        self._ck(L.srt_shade_probe_grid_depth(self._h, C.byref(p), C.byref(d)))
 
     def ray_output(self, name, count=None):
         """srt_read_ray_output: one output of the last trace_rays() as a numpy array: "object" and "occluded" (N,) int32, the

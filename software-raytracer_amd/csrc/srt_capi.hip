@@ -43,6 +43,8 @@
 #include "srt_light_probes_host.h"
 #include "srt_probe_grid.hip.h"
 #include "srt_probe_grid_host.h"
+#include "srt_probe_depth.hip.h"
+#include "srt_probe_depth_host.h"
 #include "srt_adaptive.hip.h"
 #include "srt_adaptive_host.h"
 #include "srt_launch_shape.h"
@@ -416,6 +418,18 @@ struct srt_context {
     DeviceBuffer<float4> d_probe_grid_own;
     srt::OutputSlot probe_grid_out;
     DeviceBuffer<unsigned long long> d_probe_grid_work;
+    // probe depth moments (srt_trace_probe_depth): the three texel tables (uploaded once, on first use); one own output buffer per
+    // SRT_PROBE_DEPTH_* output bit (grown when a call needs more) with its slot (the bound buffer only); what the last trace wrote
+    // and whether it counted (srt_probe_depth_host.h); the record a counting launch adds to (srt::PD_WORK_N words).  The filtered
+    // shading (srt_shade_probe_grid_depth): which moment array is current, and the own one (srt_write_probe_grid_depth).
+    DeviceBuffer<float4> d_probe_depth_texels;
+    bool probe_depth_texels_ready = false;
+    DeviceBuffer<void> d_probe_depth_own[srt::PROBE_DEPTH_SLOTS];
+    srt::OutputSlot probe_depth_out[srt::PROBE_DEPTH_SLOTS];
+    srt::ProbeDepthState probe_depth;
+    DeviceBuffer<unsigned long long> d_probe_depth_work;
+    srt::ProbeGridDepthState probe_grid_depth;
+    DeviceBuffer<float4> d_probe_grid_depth;
     // adaptive sampling (srt_render_adaptive, srt_sample_budget): the per-pixel sample counts and sample budget, W*H uint32 each,
     // own buffer and slot; whether the last adaptive render counted and whether a budget pass has run (srt_adaptive_host.h); the
     // tile ticket of a launch (zeroed on the stream in front of it); the record a counting launch adds to (srt::ADP_WORK_N words);
@@ -2374,6 +2388,185 @@ int srt_get_probe_grid_work(srt_context* ctx, srt_probe_grid_work* out) {
     out->pixels = w[srt::PG_WORK_PIXELS], out->corners = w[srt::PG_WORK_CORNERS], out->segments = w[srt::PG_WORK_SEGMENTS], out->open = w[srt::PG_WORK_OPEN];
     out->wave_trips = w[srt::PG_WORK_TRIPS], out->analytic_tests = w[srt::PG_WORK_ANALYTIC], out->node_visits = w[srt::PG_WORK_NODES];
     out->triangle_tests = w[srt::PG_WORK_TRIANGLES], out->waves = w[srt::PG_WORK_WAVES];
+    return SRT_OK;
+}
+
+// ---- probe depth moments -------------------------------------------------------------------------------------------
+static_assert(SRT_PROBE_DEPTH_MOMENTS == srt::PROBE_DEPTH_OUT_MOMENTS && SRT_PROBE_DEPTH_DISTANCES == srt::PROBE_DEPTH_OUT_DISTANCES &&
+              SRT_PROBE_DEPTH_NORMALIZE == srt::PROBE_DEPTH_FLAG_NORMALIZE && SRT_PROBE_DEPTH_COUNT_WORK == srt::PROBE_DEPTH_FLAG_COUNT_WORK &&
+              sizeof(srt_probe_depth_params) == 24 && sizeof(srt::ProbeDepthCall) == 24 && sizeof(srt_probe_depth_work) == 48 && srt::PD_WORK_N == 5 &&
+              sizeof(srt_probe_grid_depth_params) == 16 && sizeof(srt::ProbeGridDepthCall) == 16,
+              "srt_probe_depth_host.h, srt_probe_depth.hip.h and srt_pathtrace.h disagree");
+
+int srt_probe_depth_params_default(srt_probe_depth_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::ProbeDepthCall c;
+    srt::probe_depth_call_default(c);
+    memcpy(out, &c, sizeof c);
+    return SRT_OK;
+}
+
+int srt_probe_depth_texels(uint32_t resolution, float* dst) {
+    if (!dst || !srt::probe_depth_resolution_ok(resolution)) return SRT_ERR_INVALID_ARG;
+    srt::probe_depth_texels(resolution, dst);
+    return SRT_OK;
+}
+
+// ... in front of the re-allocation of own probe-depth output `i`: earlier traces may still be writing it
+static int probe_depth_output_released(srt_context* ctx, int i) {
+    if (const int rc = finish_stream(ctx)) return rc;
+    srt::probe_depth_output_released(ctx->probe_depth, i, (void*)ctx->d_probe_depth_own[i]);
+    return SRT_OK;
+}
+
+int srt_trace_probe_depth(srt_context* ctx, const srt_probe_depth_params* t) {
+    if (!ctx || !t) return SRT_ERR_INVALID_ARG;
+    srt::ProbeDepthCall call;
+    memcpy(&call, t, sizeof call);
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_depth_check_trace(ctx->probes, ctx->scene_set, call, &why))
+        return fail(ctx, (int)rs, "srt_trace_probe_depth: %s (resolution %u, sharpness %u, max_distance %g, flags 0x%x, outputs 0x%x, reserved %u)", why, t->resolution,
+                    t->sharpness, (double)t->max_distance, t->flags, t->outputs, t->reserved);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t np = ctx->probes.positions.count(), nk = ctx->probes.directions.count();
+    const bool count = (t->flags & SRT_PROBE_DEPTH_COUNT_WORK) != 0;
+    if (!ctx->probe_depth_texels_ready) {  // the three tables, once: no launch has read the buffer yet
+        float table[srt::PROBE_DEPTH_TABLE * 4];
+        for (uint32_t r = 4; r <= 16; r *= 2) srt::probe_depth_texels(r, table + 4 * srt::probe_depth_table_offset(r));
+        SRT_HIP(ctx, ctx->d_probe_depth_texels.ensure(sizeof table));
+        SRT_HIP(ctx, hipMemcpy(ctx->d_probe_depth_texels, table, sizeof table, hipMemcpyHostToDevice));
+        ctx->probe_depth_texels_ready = true;
+    }
+    void* dst[srt::PROBE_DEPTH_SLOTS] = {nullptr, nullptr};
+    for (int i = 0; i < srt::PROBE_DEPTH_SLOTS; ++i)
+        if (t->outputs & (1u << i))
+            SRT_WRITE_TARGET_AFTER(ctx, ctx->probe_depth_out[i], ctx->d_probe_depth_own[i], srt::probe_depth_bytes(i, np, nk, t->resolution), dst[i],
+                                   probe_depth_output_released(ctx, i));
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_probe_depth_work, srt::PD_WORK_N)) return rc;
+    }
+    srt::KernelParams K;
+    const KernelSetup ks = scene_kernel_params(ctx, 0, ctx->height, K);
+    const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::probe_depth_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    const unsigned wgs = srt::probe_depth_grid(np, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
+    srt::ProbeDepthIO io{};
+    io.position = ctx->probes.positions.bound ? (const float4*)ctx->probes.positions.bound : (const float4*)ctx->d_probe_position;
+    io.direction = ctx->probes.directions.bound ? (const float4*)ctx->probes.directions.bound : (const float4*)ctx->d_probe_direction;
+    io.texel = (const float4*)ctx->d_probe_depth_texels + srt::probe_depth_table_offset(t->resolution);
+    io.probes = (uint32_t)np, io.directions = (uint32_t)nk, io.resolution = t->resolution, io.sharpness = t->sharpness;
+    io.max_distance = t->max_distance;
+    io.normalize = (t->flags & SRT_PROBE_DEPTH_NORMALIZE) ? 1u : 0u;
+    io.moments = (float4*)dst[0];
+    io.distances = (float*)dst[1];
+    io.work = count ? (unsigned long long*)ctx->d_probe_depth_work : nullptr;
+    if (const int rc = launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
+    srt::probe_depth_traced(ctx->probe_depth, np, nk, call, dst);
+    return SRT_OK;
+}
+
+int srt_bind_probe_depth_output(srt_context* ctx, uint32_t output, void* d_ptr) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    const int i = srt::probe_depth_slot(output);
+    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_depth_output: output 0x%x is not a single SRT_PROBE_DEPTH_MOMENTS / _DISTANCES bit", output);
+    return ctx->probe_depth_out[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued traces keep the buffer they were given, as srt_bind_ray_output)
+}
+
+int srt_read_probe_depth_output(srt_context* ctx, uint32_t output, void* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    const srt::RaysStatus rs = srt::probe_depth_check_read(ctx->probe_depth, output, &src, &bytes);
+    if (rs == srt::RAYS_INVALID_ARG)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_probe_depth_output: output 0x%x is not a single SRT_PROBE_DEPTH_MOMENTS / _DISTANCES bit", output);
+    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, bytes, "srt_read_probe_depth_output: output 0x%x was not written by the last srt_trace_probe_depth", output);
+}
+
+int srt_get_probe_depth_work(srt_context* ctx, srt_probe_depth_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::probe_depth_check_work(ctx->probe_depth) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_depth_work: the last srt_trace_probe_depth did not ask for SRT_PROBE_DEPTH_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::PD_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_probe_depth_work, w, srt::PD_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0;
+    out->probes = w[srt::PD_WORK_PROBES], out->rays = w[srt::PD_WORK_RAYS], out->far_rays = w[srt::PD_WORK_FAR];
+    out->wave_calls = w[srt::PD_WORK_WAVE_CALLS], out->waves = w[srt::PD_WORK_WAVES];
+    return SRT_OK;
+}
+
+// ---- probe-grid shading with the filtered visibility test ------------------------------------------------------------
+int srt_probe_grid_depth_params_default(srt_probe_grid_depth_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::ProbeGridDepthCall c;
+    srt::probe_grid_depth_call_default(c);
+    memcpy(out, &c, sizeof c);
+    return SRT_OK;
+}
+
+int srt_write_probe_grid_depth(srt_context* ctx, const float* moments, size_t probes, uint32_t resolution) {
+    if (!ctx || !moments) return SRT_ERR_INVALID_ARG;
+    if (srt::probe_grid_depth_check_input(probes, resolution) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_write_probe_grid_depth: %zu probes of resolution %u: want resolution 4, 8 or 16 and 1 <= probes * resolution^2 <= 2^30",
+                    probes, resolution);
+    if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it may be re-allocated below)
+    const size_t bytes = probes * (size_t)resolution * resolution * sizeof(float4);
+    if (ctx->d_probe_grid_depth.bytes() < bytes) {
+        ctx->probe_grid_depth.moments.own_count = 0;  // (a failed allocation leaves no own array)
+        SRT_HIP(ctx, ctx->d_probe_grid_depth.ensure(bytes));
+    }
+    SRT_HIP(ctx, hipMemcpy(ctx->d_probe_grid_depth, moments, bytes, hipMemcpyHostToDevice));
+    srt::probe_grid_depth_written(ctx->probe_grid_depth, probes, resolution);
+    return SRT_OK;
+}
+
+int srt_bind_probe_grid_depth(srt_context* ctx, const void* d_ptr, size_t probes, uint32_t resolution) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    if (srt::probe_grid_depth_bind(ctx->probe_grid_depth, d_ptr, probes, resolution) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_INVALID_ARG,
+                    "srt_bind_probe_grid_depth: want a device array, resolution 4, 8 or 16 and 1 <= probes * resolution^2 <= 2^30, or NULL, 0 (got %zu, %u)", probes,
+                    resolution);
+    return SRT_OK;
+}
+
+int srt_shade_probe_grid_depth(srt_context* ctx, const srt_probe_grid_params* s, const srt_probe_grid_depth_params* d) {
+    if (!ctx || !s || !d) return SRT_ERR_INVALID_ARG;
+    srt::ProbeGridCall call;
+    memcpy(&call, s, sizeof call);
+    srt::ProbeGridDepthCall dcall;
+    memcpy(&dcall, d, sizeof dcall);
+    bool present[srt::PROBE_GRID_GUIDES];
+    for (int i = 0; i < srt::PROBE_GRID_GUIDES; ++i) present[i] = current(ctx->gbuf[i], ctx->d_gbuf_own[i]) != nullptr;
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_grid_depth_check_shade(ctx->probe_grid, ctx->probe_grid_depth, call, dcall, ctx->scene_set, ctx->height, present, &why))
+        return fail(ctx, (int)rs, "srt_shade_probe_grid_depth: %s (rows [%d,%d) of %d, flags 0x%x, band_weight %g %g %g, reserved %u %u; bias %g, min_variance %g, reserved %u %u)",
+                    why, s->row_begin, s->row_end, ctx->height, s->flags, (double)s->band_weight[0], (double)s->band_weight[1], (double)s->band_weight[2], s->reserved[0],
+                    s->reserved[1], (double)d->bias, (double)d->min_variance, d->reserved[0], d->reserved[1]);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const bool count = (s->flags & SRT_PROBE_GRID_COUNT_WORK) != 0;
+    float4* dst = nullptr;
+    SRT_WRITE_TARGET(ctx, ctx->probe_grid_out, ctx->d_probe_grid_own, frame_pixels(ctx) * sizeof(float4), dst);
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_probe_grid_work, srt::PG_WORK_N)) return rc;
+    }
+    srt::KernelParams K;
+    KernelSetup ks = scene_kernel_params(ctx, s->row_begin, s->row_end, K);
+    ks.lds_bytes = 0;  // (the kernel traces nothing: no scene image, and its own LDS is static)
+    const srt::ProbeGrid& g = ctx->probe_grid.grid;
+    srt::ProbeGridDepthIO io{};
+    io.object = (const int32_t*)current(ctx->gbuf[0], ctx->d_gbuf_own[0]);
+    io.normal_depth = (const float4*)current(ctx->gbuf[1], ctx->d_gbuf_own[1]);
+    io.position = (const float4*)current(ctx->gbuf[2], ctx->d_gbuf_own[2]);
+    io.albedo = (s->flags & SRT_PROBE_GRID_ALBEDO) ? (const float4*)current(ctx->gbuf[3], ctx->d_gbuf_own[3]) : nullptr;
+    io.coefficients = ctx->probe_grid.coefficients.bound ? (const float4*)ctx->probe_grid.coefficients.bound : (const float4*)ctx->d_probe_grid_coefficients;
+    io.depth = ctx->probe_grid_depth.moments.bound ? (const float4*)ctx->probe_grid_depth.moments.bound : (const float4*)ctx->d_probe_grid_depth;
+    io.out = dst;
+    for (int a = 0; a < 3; ++a) io.origin[a] = g.origin[a], io.spacing[a] = g.spacing[a], io.counts[a] = g.counts[a], io.band_weight[a] = s->band_weight[a];
+    io.normal_weight = (s->flags & SRT_PROBE_GRID_NORMAL_WEIGHT) ? 1u : 0u;
+    io.resolution = ctx->probe_grid_depth.resolution();
+    io.bias = d->bias, io.min_variance = d->min_variance;
+    io.work = count ? (unsigned long long*)ctx->d_probe_grid_work : nullptr;
+    if (const int rc = launch_tiles(ctx, count ? srt::probe_grid_depth_kernel<true> : srt::probe_grid_depth_kernel<false>, ks, K, io)) return rc;
+    ctx->probe_grid_out.wrote(dst);
+    srt::probe_grid_shaded(ctx->probe_grid, s->flags);
     return SRT_OK;
 }
 

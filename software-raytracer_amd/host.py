@@ -13,6 +13,8 @@ from .capi import (LIGHT_PROBE_COEFFICIENTS, LIGHT_PROBE_COEFFS, LIGHT_PROBE_COU
                    LightProbeParams, LightProbeWork, light_probe_irradiance, light_probe_sphere)  # noqa: F401
 from .capi import (PROBE_GRID_ALBEDO, PROBE_GRID_BAND_WEIGHT_IRRADIANCE, PROBE_GRID_COUNT_WORK, PROBE_GRID_NORMAL_WEIGHT, PROBE_GRID_VISIBILITY,
                    ProbeGrid, ProbeGridParams, ProbeGridWork, probe_grid, probe_grid_positions)  # noqa: F401
+from .capi import (PROBE_DEPTH_COUNT_WORK, PROBE_DEPTH_DISTANCES, PROBE_DEPTH_MOMENTS, PROBE_DEPTH_NORMALIZE, ProbeDepthParams, ProbeDepthWork,
+                   ProbeGridDepthParams, probe_depth_texels)  # noqa: F401
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_PKG, "libsrt_host.so")
@@ -45,6 +47,8 @@ EXPORTS = [
     "srt_host_renderer_trace_light_probes", "srt_host_renderer_read_light_probe_output", "srt_host_renderer_light_probe_work",
     "srt_host_renderer_set_probe_grid", "srt_host_renderer_shade_probe_grid", "srt_host_renderer_read_probe_grid_output",
     "srt_host_renderer_probe_grid_work",
+    "srt_host_renderer_trace_probe_depth", "srt_host_renderer_read_probe_depth_output", "srt_host_renderer_probe_depth_work",
+    "srt_host_renderer_shade_probe_grid_depth",
     "srt_host_renderer_sample_budget", "srt_host_renderer_render_adaptive", "srt_host_renderer_set_sample_counts",
     "srt_host_renderer_read_sample_counts", "srt_host_renderer_adaptive_frame",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
@@ -146,6 +150,11 @@ def load_library():
     L.srt_host_renderer_shade_probe_grid.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(ProbeGridParams)]
     L.srt_host_renderer_read_probe_grid_output.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_probe_grid_work.argtypes = [vp, C.POINTER(ProbeGridWork)]
+    L.srt_host_renderer_trace_probe_depth.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(ProbeDepthParams)]
+    L.srt_host_renderer_read_probe_depth_output.argtypes = [vp, C.c_uint32, C.c_void_p]
+    L.srt_host_renderer_probe_depth_work.argtypes = [vp, C.POINTER(ProbeDepthWork)]
+    L.srt_host_renderer_shade_probe_grid_depth.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_uint32, C.POINTER(ProbeGridParams),
+                                                           C.POINTER(ProbeGridDepthParams)]
     L.srt_host_renderer_sample_budget.argtypes = [vp, C.POINTER(BudgetParams), C.POINTER(C.c_uint64)]
     L.srt_host_renderer_render_adaptive.argtypes = [vp, C.POINTER(AdaptiveParams)]
     L.srt_host_renderer_set_sample_counts.argtypes = [vp, C.c_uint32]
@@ -507,6 +516,65 @@ class Renderer:
         w = ProbeGridWork()
         self._ck(self.L.srt_host_renderer_probe_grid_work(self._h, C.byref(w)))
         return w.as_dict()
+
+    def trace_probe_depth(self, positions, directions, resolution=16, sharpness=5, max_distance=10000.0, normalize=False, count_work=False,
+                          distances=False):
+        """PathTraceRenderer::traceProbeDepth + readProbeDepthOutput: copy P positions and K directions (host arrays (N, 4) float32;
+        directions: an int K for light_probe_sphere(K)), trace srt_trace_probe_depth against the renderer's scene and return the
+        (P, R*R, 4) float32 moments; probe_depth_distances() then returns the (P, K) distances when distances=True.  Waits."""
+        if isinstance(directions, (int, np.integer)):
+            directions = light_probe_sphere(int(directions))
+        o = np.ascontiguousarray(positions, dtype=np.float32)
+        d = np.ascontiguousarray(directions, dtype=np.float32)
+        if o.ndim != 2 or o.shape[1] != 4 or o.shape[0] < 1 or d.ndim != 2 or d.shape[1] != 4 or d.shape[0] < 1:
+            raise ValueError("trace_probe_depth: positions %s and directions %s, want (P, 4) and (K, 4) arrays" % (o.shape, d.shape))
+        p = ProbeDepthParams(int(resolution), int(sharpness), float(max_distance),
+                             (PROBE_DEPTH_NORMALIZE if normalize else 0) | (PROBE_DEPTH_COUNT_WORK if count_work else 0),
+                             PROBE_DEPTH_MOMENTS | (PROBE_DEPTH_DISTANCES if distances else 0), 0)
+        f = C.POINTER(C.c_float)
+        self._ck(self.L.srt_host_renderer_trace_probe_depth(self._h, o.ctypes.data_as(f), o.shape[0], d.ctypes.data_as(f), d.shape[0], C.byref(p)))
+        self._probe_depth_traced = (o.shape[0], d.shape[0], int(resolution))
+        out = np.empty((o.shape[0], int(resolution) ** 2, 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_probe_depth_output(self._h, PROBE_DEPTH_MOMENTS, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def probe_depth_distances(self):
+        """PathTraceRenderer::readProbeDepthOutput(DISTANCES): the (P, K) float32 distances of the last trace_probe_depth(distances=True)."""
+        out = np.empty(self._probe_depth_traced[:2], dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_probe_depth_output(self._h, PROBE_DEPTH_DISTANCES, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def probe_depth_work(self):
+        """PathTraceRenderer::probeDepthWork: the work counts of the last trace_probe_depth(count_work=True) as a dict."""
+        w = ProbeDepthWork()
+        self._ck(self.L.srt_host_renderer_probe_depth_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def shade_probe_grid_depth(self, coefficients=None, moments=None, bias=0.0, min_variance=1e-4, normal_weight=False, albedo=False, band_weight=None,
+                               rows=None, count_work=False):
+        """PathTraceRenderer::shadeProbeGridDepth + readProbeGridOutput: shade_probe_grid() with the filtered visibility test.
+        `moments`: (P, R*R, 4) float32 as trace_probe_depth() returns them (None: the handle's current ones).  Returns the (H, W, 4)
+        float32 result; probe_grid_work() reads the counts.  Waits."""
+        f = C.POINTER(C.c_float)
+        cptr, mptr, n, res = None, None, 0, 0
+        if coefficients is not None:
+            c = np.ascontiguousarray(coefficients, dtype=np.float32).reshape(-1, 4)
+            if c.shape[0] < LIGHT_PROBE_COEFFS or c.shape[0] % LIGHT_PROBE_COEFFS:
+                raise ValueError("shade_probe_grid_depth: %d float4 of coefficients, want nine per probe" % c.shape[0])
+            cptr, n = c.ctypes.data_as(f), c.shape[0] // LIGHT_PROBE_COEFFS
+        if moments is not None:
+            m = np.ascontiguousarray(moments, dtype=np.float32)
+            if m.ndim != 3 or m.shape[2] != 4 or m.shape[0] < 1 or (n and m.shape[0] != n):
+                raise ValueError("shade_probe_grid_depth: moments %s, want (P, R*R, 4)" % (m.shape,))
+            res = int(round(m.shape[1] ** 0.5))
+            mptr, n = m.ctypes.data_as(f), m.shape[0]
+        rb, re = (int(rows[0]), int(rows[1])) if rows is not None else (0, 0)
+        bw = band_weight if band_weight is not None else PROBE_GRID_BAND_WEIGHT_IRRADIANCE
+        p = ProbeGridParams(rb, re, (PROBE_GRID_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_GRID_ALBEDO if albedo else 0) |
+                            (PROBE_GRID_COUNT_WORK if count_work else 0), (C.c_float * 3)(float(bw[0]), float(bw[1]), float(bw[2])), (C.c_uint32 * 2)(0, 0))
+        d = ProbeGridDepthParams(float(bias), float(min_variance), (C.c_uint32 * 2)(0, 0))
+        self._ck(self.L.srt_host_renderer_shade_probe_grid_depth(self._h, cptr, mptr, n, res, C.byref(p), C.byref(d)))
+        return self.probe_grid_output()
 
     def radiance_work(self):
         """PathTraceRenderer::radianceWork: the work counts of the last trace_radiance(count_work=True) as a dict."""

@@ -242,6 +242,18 @@ int srt_host_renderer_shade_probe_grid(srt_host_renderer* h, const float* coeffi
 }
 int srt_host_renderer_read_probe_grid_output(srt_host_renderer* h, float* dst) { SRT_HOST_TRY(h, h->r->readProbeGridOutput(dst)) }
 int srt_host_renderer_probe_grid_work(srt_host_renderer* h, srt_probe_grid_work* out) { SRT_HOST_TRY(h, *out = h->r->probeGridWork()) }
+// probe depth moments against the renderer's scene, and the probe-grid shading that reads them (PathTraceRenderer::traceProbeDepth /
+// shadeProbeGridDepth: coefficients and moments are copied unless NULL; the output and the work record are the probe-grid pass's)
+int srt_host_renderer_trace_probe_depth(srt_host_renderer* h, const float* positions, size_t probes, const float* directions, size_t direction_count,
+                                        const srt_probe_depth_params* p) {
+    SRT_HOST_TRY(h, h->r->traceProbeDepth(positions, probes, directions, direction_count, *p))
+}
+int srt_host_renderer_read_probe_depth_output(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->readProbeDepthOutput(output, dst)) }
+int srt_host_renderer_probe_depth_work(srt_host_renderer* h, srt_probe_depth_work* out) { SRT_HOST_TRY(h, *out = h->r->probeDepthWork()) }
+int srt_host_renderer_shade_probe_grid_depth(srt_host_renderer* h, const float* coefficients, const float* moments, size_t probes, uint32_t resolution,
+                                             const srt_probe_grid_params* p, const srt_probe_grid_depth_params* d) {
+    SRT_HOST_TRY(h, h->r->shadeProbeGridDepth(coefficients, moments, probes, resolution, *p, *d))
+}
 // adaptive sampling on the handle's buffers as they stand (srt_sample_budget + srt_get_budget_total, srt_render_adaptive; a band
 // of [0, 0) means the renderer's own), and the two-half workflow (PathTraceRenderer::renderAdaptiveFrame; counts may be NULL)
 int srt_host_renderer_sample_budget(srt_host_renderer* h, const srt_budget_params* p, uint64_t* total) { SRT_HOST_TRY(h, *total = h->r->sampleBudget(*p)) }

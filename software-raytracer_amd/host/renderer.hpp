@@ -185,6 +185,17 @@ class PathTraceRenderer {
     void shadeProbeGrid(const float* coefficients, size_t probes, const srt_probe_grid_params& params);
     void readProbeGridOutput(float* dst_rgba);
     srt_probe_grid_work probeGridWork();
+    // Probe depth moments (srt_trace_probe_depth) and the filtered probe-grid shading (srt_shade_probe_grid_depth).  traceProbeDepth
+    // copies `probes` positions and `direction_count` directions as traceLightProbes does (they are the same current arrays) and
+    // enqueues the pass; readProbeDepthOutput waits and copies one output of the last trace (SRT_PROBE_DEPTH_MOMENTS: probes * R*R
+    // float4; SRT_PROBE_DEPTH_DISTANCES: probes * directions float); probeDepthWork waits and returns the work counts of a trace
+    // that had SRT_PROBE_DEPTH_COUNT_WORK.  shadeProbeGridDepth is shadeProbeGrid with the filtered test: it also copies `probes`
+    // * resolution^2 float4 moments (NULL: the handle's current ones); readProbeGridOutput and probeGridWork serve both calls.
+    void traceProbeDepth(const float* positions, size_t probes, const float* directions, size_t direction_count, const srt_probe_depth_params& params);
+    void readProbeDepthOutput(uint32_t output, void* dst);
+    srt_probe_depth_work probeDepthWork();
+    void shadeProbeGridDepth(const float* coefficients, const float* moments, size_t probes, uint32_t resolution, const srt_probe_grid_params& params,
+                             const srt_probe_grid_depth_params& depth);
     // Adaptive sampling (srt_sample_budget, srt_render_adaptive), on the handle's buffers as they stand.  sampleBudget turns the
     // variance buffer, the sample counts, the accumulator and the guides into the per-pixel budget and returns its sum (waits).
     // renderAdaptive enqueues the adaptive render with the renderer's scene and camera; a band of [0, 0) means the renderer's

@@ -266,8 +266,18 @@ static bool parse_probe_grid(const char* p, srt_probe_grid* g) {
 // the W x H frame, light probes (srt_trace_light_probes: K spherical Fibonacci directions, samples 1..`samples`, `bounces`, `seed`,
 // id_base 0) at the grid's positions (srt_probe_grid_positions), then srt_shade_probe_grid over the whole frame with `flags` and the
 // default or the hemisphere band weights.  FILE receives W*H float4, scene rows.
+// --probe-depth R: the filtered visibility test instead of none or the exact one: srt_trace_probe_depth at the same positions and
+// directions (resolution R, --probe-depth-sharpness, --probe-depth-max), then srt_shade_probe_grid_depth (--probe-depth-bias);
+// --probe-depth-out receives the probes' R*R float4 moments.
+struct ProbeDepthOptions {
+    int resolution = 0;  // 0: no --probe-depth
+    int sharpness = 5;
+    float max_distance = 10000.0f, bias = 0.0f;
+    std::string out;
+};
+
 static int shade_probe_grid_file(const Scene& scene, int device, int W, int H, int fov, const srt_probe_grid& grid, int directions, int samples, int bounces,
-                                 unsigned seed, uint32_t flags, bool hemisphere, const std::string& out) {
+                                 unsigned seed, uint32_t flags, bool hemisphere, const std::string& out, const ProbeDepthOptions& depth) {
     const size_t np = (size_t)grid.counts[0] * (size_t)grid.counts[1] * (size_t)grid.counts[2];
     std::vector<float> pos(4 * np), dir(4 * (size_t)directions);
     if (srt_probe_grid_positions(&grid, pos.data()) != SRT_OK) {
@@ -292,7 +302,21 @@ static int shade_probe_grid_file(const Scene& scene, int device, int W, int H, i
         sp.row_begin = 0, sp.row_end = H, sp.flags = flags;
         if (hemisphere) sp.band_weight[0] = 1.0f, sp.band_weight[1] = 0.5f, sp.band_weight[2] = 0.0f;
         r.setProbeGrid(grid);
-        r.shadeProbeGrid(coeff.data(), np, sp);
+        if (depth.resolution) {
+            srt_probe_depth_params dp{};
+            srt_probe_depth_params_default(&dp);
+            dp.resolution = (uint32_t)depth.resolution, dp.sharpness = (uint32_t)depth.sharpness, dp.max_distance = depth.max_distance;
+            r.traceProbeDepth(pos.data(), np, dir.data(), (size_t)directions, dp);
+            std::vector<float> moments(np * (size_t)depth.resolution * depth.resolution * 4);
+            r.readProbeDepthOutput(SRT_PROBE_DEPTH_MOMENTS, moments.data());
+            if (!depth.out.empty() && !write_floats(depth.out, moments)) return 1;
+            srt_probe_grid_depth_params gd{};
+            srt_probe_grid_depth_params_default(&gd);
+            gd.bias = depth.bias;
+            r.shadeProbeGridDepth(coeff.data(), moments.data(), np, (uint32_t)depth.resolution, sp, gd);
+        } else {
+            r.shadeProbeGrid(coeff.data(), np, sp);
+        }
         std::vector<float> img((size_t)W * H * 4);
         r.readProbeGridOutput(img.data());
         if (!write_floats(out, img)) return 1;
@@ -320,6 +344,7 @@ static void usage() {
                  "                  [--probe-radiance-out FILE] [--bounces B] [--seed S]\n"
                  "       srt_render --scene FILE --probe-grid OX,OY,OZ,SX,SY,SZ,NX,NY,NZ --probe-directions K [--radiance N] --irradiance-out FILE\n"
                  "                  [--probe-visibility] [--probe-normal-weight] [--probe-albedo] [--probe-hemisphere] [--width W] [--height H] ...\n"
+                 "                  [--probe-depth R [--probe-depth-sharpness S] [--probe-depth-max D] [--probe-depth-bias B] [--probe-depth-out FILE]]\n"
                  "       srt_render --scene FILE --adaptive ROUNDS [--adaptive-threshold T] [--adaptive-max M] [--counts-out FILE] [--spp N] ...\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
@@ -377,6 +402,10 @@ static void usage() {
                  "             --probe-visibility: only probes the surface sees; --probe-normal-weight: favour probes in front of the surface;\n"
                  "             --probe-albedo: times the albedo guide; --probe-hemisphere: band weights 1, 0.5, 0 (the mean over the hemisphere)\n"
                  "             instead of the cosine-weighted integral; single device, not with --rays, --probes, --temporal or --devices\n"
+                 "  --probe-depth R: with --probe-grid, the filtered visibility test (srt_trace_probe_depth + srt_shade_probe_grid_depth): an\n"
+                 "             octahedral depth map of R x R texels (4, 8 or 16) per probe from the same directions; --probe-depth-sharpness S\n"
+                 "             (0..6, default 5); --probe-depth-max D: distance clamp (> 0, default 10000); --probe-depth-bias B (>= 0, default 0);\n"
+                 "             --probe-depth-out receives the probes' R*R float4 moments; not with --probe-visibility\n"
                  "  --adaptive ROUNDS: adaptive sampling in place of the uniform frame: an even --spp is the uniform seed, split into two\n"
                  "             independently seeded halves; then ROUNDS (1..64) rounds of srt_variance, srt_sample_budget and srt_render_adaptive\n"
                  "             on both halves, and the mean of the halves goes to --out; the frame's total samples are printed on stderr;\n"
@@ -407,6 +436,8 @@ int main(int argc, char** argv) {
     std::string probes_in, probes_out, probe_directions, probe_radiance_out;
     std::string probe_grid_arg, irradiance_out;
     bool probe_visibility = false, probe_normal_weight = false, probe_albedo = false, probe_hemisphere = false;
+    ProbeDepthOptions probe_depth;
+    bool probe_depth_given = false, probe_depth_option = false;
     int adaptive = 0, adaptive_max = 0;
     bool adaptive_given = false, adaptive_threshold_given = false, adaptive_max_given = false;
     float adaptive_threshold = 0;
@@ -482,6 +513,11 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--probe-normal-weight")) probe_normal_weight = true;
         else if (!std::strcmp(argv[i], "--probe-albedo")) probe_albedo = true;
         else if (!std::strcmp(argv[i], "--probe-hemisphere")) probe_hemisphere = true;
+        else if (!std::strcmp(argv[i], "--probe-depth")) probe_depth.resolution = std::atoi(need("--probe-depth")), probe_depth_given = true;
+        else if (!std::strcmp(argv[i], "--probe-depth-sharpness")) probe_depth.sharpness = std::atoi(need("--probe-depth-sharpness")), probe_depth_option = true;
+        else if (!std::strcmp(argv[i], "--probe-depth-max")) probe_depth.max_distance = std::strtof(need("--probe-depth-max"), nullptr), probe_depth_option = true;
+        else if (!std::strcmp(argv[i], "--probe-depth-bias")) probe_depth.bias = std::strtof(need("--probe-depth-bias"), nullptr), probe_depth_option = true;
+        else if (!std::strcmp(argv[i], "--probe-depth-out")) probe_depth.out = need("--probe-depth-out"), probe_depth_option = true;
         else if (!std::strcmp(argv[i], "--adaptive")) adaptive = std::atoi(need("--adaptive")), adaptive_given = true;
         else if (!std::strcmp(argv[i], "--adaptive-threshold")) adaptive_threshold = std::strtof(need("--adaptive-threshold"), nullptr), adaptive_threshold_given = true;
         else if (!std::strcmp(argv[i], "--adaptive-max")) adaptive_max = std::atoi(need("--adaptive-max")), adaptive_max_given = true;
@@ -549,6 +585,23 @@ int main(int argc, char** argv) {
     }
     srt_probe_grid probe_grid{};
     int probe_grid_directions = 0;
+    if (probe_depth_given || probe_depth_option) {
+        if (probe_grid_arg.empty() || !probe_depth_given) {
+            std::fprintf(stderr, "--probe-depth R and its options go with --probe-grid: --probe-grid G --probe-depth R [--probe-depth-sharpness S] [--probe-depth-max D] "
+                                 "[--probe-depth-bias B] [--probe-depth-out FILE]\n");
+            return 2;
+        }
+        if (probe_visibility) {
+            std::fprintf(stderr, "--probe-depth and --probe-visibility exclude each other: the filtered or the exact test\n");
+            return 2;
+        }
+        if ((probe_depth.resolution != 4 && probe_depth.resolution != 8 && probe_depth.resolution != 16) || probe_depth.sharpness < 0 || probe_depth.sharpness > 6 ||
+            !(probe_depth.max_distance > 0.0f) || !std::isfinite(probe_depth.max_distance) || !(probe_depth.bias >= 0.0f) || !std::isfinite(probe_depth.bias)) {
+            std::fprintf(stderr, "--probe-depth takes 4, 8 or 16, --probe-depth-sharpness 0..6, --probe-depth-max a finite distance > 0 and --probe-depth-bias a finite "
+                                 "value >= 0\n");
+            return 2;
+        }
+    }
     if (!probe_grid_arg.empty() || !irradiance_out.empty() || probe_visibility || probe_normal_weight || probe_albedo || probe_hemisphere) {
         if (probe_grid_arg.empty()) {
             std::fprintf(stderr, "--irradiance-out, --probe-visibility, --probe-normal-weight, --probe-albedo and --probe-hemisphere need --probe-grid\n");
@@ -690,7 +743,7 @@ int main(int argc, char** argv) {
         return shade_probe_grid_file(scene, device, W, H, fov, probe_grid, probe_grid_directions, radiance_given ? radiance : 16, bounces, seed,
                                      (probe_visibility ? SRT_PROBE_GRID_VISIBILITY : 0u) | (probe_normal_weight ? SRT_PROBE_GRID_NORMAL_WEIGHT : 0u) |
                                          (probe_albedo ? SRT_PROBE_GRID_ALBEDO : 0u),
-                                     probe_hemisphere, irradiance_out);
+                                     probe_hemisphere, irradiance_out, probe_depth);
     if (!probes_in.empty()) return trace_probe_file(scene, device, probes_in, probe_directions, probes_out, probe_radiance_out, radiance_given ? radiance : 16, bounces, seed);
     if (!rays_in.empty()) return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize, rays_any_hit, radiance_given ? radiance : 0, bounces, seed);
     auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {

@@ -1,0 +1,217 @@
+// probe_depth_check.cpp — the host-side rules of the probe depth pass and of the filtered probe-grid shading
+// (software-raytracer_amd/csrc/srt_probe_depth_host.h) as a stand-alone program, built with -fsanitize=address,undefined by
+// tests/test_probe_depth_native.py: the defaults, the texel tables (exactly R*R float4 each, unit, the three laid end to end),
+// which arguments are accepted and in which order the checks come, the sizes of the outputs, what a read returns, the grid
+// sizing, the moment input and the order of the filtered call's checks.  Prints "ok <checks>" or the first failure.
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <limits>
+#include <vector>
+
+#include "srt_probe_depth_host.h"
+
+using namespace srt;
+
+static int checks = 0;
+#define CHECK(cond)                                              \
+    do {                                                         \
+        ++checks;                                                \
+        if (!(cond)) {                                           \
+            printf("FAILED line %d: %s\n", __LINE__, #cond);     \
+            return 1;                                            \
+        }                                                        \
+    } while (0)
+
+int main() {
+    const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
+    static_assert(sizeof(ProbeDepthCall) == 24 && sizeof(ProbeGridDepthCall) == 16, "the structs of the header");
+    const char* why = nullptr;
+    // defaults
+    ProbeDepthCall c;
+    probe_depth_call_default(c);
+    CHECK(c.resolution == 16 && c.sharpness == 5 && c.max_distance == 10000.0f && c.flags == 0 && c.outputs == PROBE_DEPTH_OUT_MOMENTS && c.reserved == 0);
+    ProbeGridDepthCall dc;
+    probe_grid_depth_call_default(dc);
+    CHECK(dc.bias == 0.0f && dc.min_variance == 1e-4f && dc.reserved[0] == 0 && dc.reserved[1] == 0);
+    // texel tables: exactly R*R float4 (the vectors have no slack: ASan sees a write past the end), unit directions, w = 0
+    CHECK(probe_depth_table_offset(4) == 0 && probe_depth_table_offset(8) == 16 && probe_depth_table_offset(16) == 80 && PROBE_DEPTH_TABLE == 336);
+    for (uint32_t R = 4; R <= 16; R *= 2) {
+        CHECK(probe_depth_resolution_ok(R));
+        std::vector<float> t((size_t)R * R * 4);
+        probe_depth_texels(R, t.data());
+        for (size_t k = 0; k < (size_t)R * R; ++k) {
+            const double n = (double)t[4 * k] * t[4 * k] + (double)t[4 * k + 1] * t[4 * k + 1] + (double)t[4 * k + 2] * t[4 * k + 2];
+            CHECK(fabs(n - 1.0) < 1e-6 && t[4 * k + 3] == 0.0f);
+        }
+        // the map's symmetries: texel (i, j) and (R-1-i, j) mirror x; the centre four look up, the corners look down
+        for (uint32_t j = 0; j < R; ++j)
+            for (uint32_t i = 0; i < R; ++i) {
+                const float* a = &t[4 * ((size_t)j * R + i)];
+                const float* b = &t[4 * ((size_t)j * R + (R - 1 - i))];
+                CHECK(a[0] == -b[0] && a[1] == b[1] && a[2] == b[2]);
+            }
+        CHECK(t[4 * ((size_t)(R / 2) * R + R / 2) + 2] > 0.0f && t[2] < 0.0f && t[4 * ((size_t)R * R - 1) + 2] < 0.0f);
+    }
+    const uint32_t bad_r[] = {0, 1, 2, 3, 5, 12, 15, 17, 32, 0xFFFFFFFFu};
+    for (uint32_t r : bad_r) CHECK(!probe_depth_resolution_ok(r));
+    // slots and sizes
+    CHECK(probe_depth_slot(1) == 0 && probe_depth_slot(2) == 1 && probe_depth_slot(0) == -1 && probe_depth_slot(3) == -1 && probe_depth_slot(4) == -1);
+    CHECK(probe_depth_bytes(0, 5, 100, 16) == 5 * 256 * 16 && probe_depth_bytes(1, 5, 100, 16) == 5 * 100 * 4 && probe_depth_bytes(0, 3, 7, 4) == 3 * 16 * 16);
+    CHECK(probe_depth_bytes(0, (size_t)1 << 22, 1, 16) == (size_t)1 << 34);  // (no 32-bit overflow)
+    // the trace's checks, in the header's order
+    LightProbeState in;
+    probe_depth_call_default(c);
+    ProbeDepthCall bad = c;
+    bad.flags = 4;
+    CHECK(probe_depth_check_trace(in, false, bad, &why) == RAYS_STATE && strstr(why, "srt_set_scene"));  // the scene first
+    CHECK(probe_depth_check_trace(in, true, bad, &why) == RAYS_INVALID_ARG && strstr(why, "flags"));     // arguments before inputs
+    bad = c, bad.outputs = 0;
+    CHECK(probe_depth_check_trace(in, true, bad, &why) == RAYS_INVALID_ARG && strstr(why, "outputs"));
+    bad = c, bad.outputs = 4;
+    CHECK(probe_depth_check_trace(in, true, bad, nullptr) == RAYS_INVALID_ARG);
+    bad = c, bad.flags = 4, bad.outputs = 0;
+    CHECK(probe_depth_check_trace(in, true, bad, &why) == RAYS_INVALID_ARG && strstr(why, "flags"));  // flags before outputs
+    for (uint32_t r : bad_r) {
+        bad = c, bad.resolution = r;
+        CHECK(probe_depth_check_trace(in, true, bad, &why) == RAYS_INVALID_ARG && strstr(why, "resolution"));
+    }
+    bad = c, bad.sharpness = 7;
+    CHECK(probe_depth_check_trace(in, true, bad, &why) == RAYS_INVALID_ARG && strstr(why, "sharpness"));
+    const float bad_max[] = {nan, inf, -inf, 0.0f, -0.0f, -1.0f};
+    for (float m : bad_max) {
+        bad = c, bad.max_distance = m;
+        CHECK(probe_depth_check_trace(in, true, bad, &why) == RAYS_INVALID_ARG && strstr(why, "max_distance"));
+    }
+    bad = c, bad.reserved = 1;
+    CHECK(probe_depth_check_trace(in, true, bad, &why) == RAYS_INVALID_ARG && strstr(why, "reserved"));
+    CHECK(probe_depth_check_trace(in, true, c, &why) == RAYS_STATE && strstr(why, "positions"));
+    in.positions.own_count = 5;
+    CHECK(probe_depth_check_trace(in, true, c, &why) == RAYS_STATE && strstr(why, "directions"));
+    in.directions.own_count = 100;
+    for (uint32_t s = 0; s <= 6; ++s) {
+        ProbeDepthCall g = c;
+        g.sharpness = s, g.max_distance = 1e-38f, g.flags = 3, g.outputs = 3, g.resolution = 4u << (s % 3);
+        CHECK(probe_depth_check_trace(in, true, g, &why) == RAYS_OK);
+    }
+    // the sizes: P*K and P*R*R at and past 2^30
+    static const char dummy = 0;
+    CHECK(light_probe_bind(in.positions, &dummy, (size_t)1 << 22, LIGHT_PROBE_MAX_RAYS) == RAYS_OK);
+    in.directions.own_count = 256;
+    CHECK(probe_depth_check_trace(in, true, c, &why) == RAYS_OK);  // exactly 2^30 both ways
+    in.directions.own_count = 257;
+    CHECK(probe_depth_check_trace(in, true, c, &why) == RAYS_INVALID_ARG && strstr(why, "directions exceeds"));
+    in.directions.own_count = 1;
+    CHECK(light_probe_bind(in.positions, &dummy, ((size_t)1 << 22) + 1, LIGHT_PROBE_MAX_RAYS) == RAYS_OK);
+    CHECK(probe_depth_check_trace(in, true, c, &why) == RAYS_INVALID_ARG && strstr(why, "resolution^2"));
+    bad = c, bad.resolution = 8;
+    CHECK(probe_depth_check_trace(in, true, bad, &why) == RAYS_OK);
+    CHECK(light_probe_bind(in.positions, nullptr, 0, LIGHT_PROBE_MAX_RAYS) == RAYS_OK && in.positions.count() == 5);
+    // the record of the last trace, and what a read returns
+    ProbeDepthState s;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    CHECK(probe_depth_check_read(s, 1, &src, &bytes) == RAYS_STATE && probe_depth_check_read(s, 3, &src, &bytes) == RAYS_INVALID_ARG);
+    CHECK(probe_depth_check_work(s) == RAYS_STATE);
+    char own_m = 0, own_d = 0;
+    void* dst[PROBE_DEPTH_SLOTS] = {&own_m, &own_d};
+    ProbeDepthCall t = c;
+    t.outputs = PROBE_DEPTH_OUT_MOMENTS, t.flags = PROBE_DEPTH_FLAG_COUNT_WORK, t.resolution = 8;
+    probe_depth_traced(s, 5, 100, t, dst);
+    CHECK(probe_depth_check_read(s, 1, &src, &bytes) == RAYS_OK && src == &own_m && bytes == 5 * 64 * 16);
+    CHECK(probe_depth_check_read(s, 2, &src, &bytes) == RAYS_STATE);  // not written
+    CHECK(probe_depth_check_work(s) == RAYS_OK);
+    t.outputs = 3, t.flags = 0, t.resolution = 16;
+    probe_depth_traced(s, 7, 65, t, dst);
+    CHECK(probe_depth_check_read(s, 2, &src, &bytes) == RAYS_OK && src == &own_d && bytes == 7 * 65 * 4);
+    CHECK(probe_depth_check_read(s, 1, &src, &bytes) == RAYS_OK && bytes == 7 * 256 * 16);
+    CHECK(probe_depth_check_work(s) == RAYS_STATE);  // that trace did not count
+    probe_depth_output_released(s, 0, &own_d);       // another buffer: nothing goes
+    CHECK(probe_depth_check_read(s, 1, &src, &bytes) == RAYS_OK);
+    probe_depth_output_released(s, 0, &own_m);
+    CHECK(probe_depth_check_read(s, 1, &src, &bytes) == RAYS_STATE && probe_depth_check_read(s, 2, &src, &bytes) == RAYS_OK);
+    // grid sizing: one wave per probe, four per workgroup, never none, never more than resident
+    CHECK(probe_depth_grid(1, 4, 1024) == 1 && probe_depth_grid(4, 4, 1024) == 1 && probe_depth_grid(5, 4, 1024) == 2);
+    CHECK(probe_depth_grid(4096, 4, 1024) == 1024 && probe_depth_grid((size_t)1 << 30, 4, 1024) == 1024 && probe_depth_grid(9, 4, 0) == 1);
+    // the moment input of the filtered call
+    ProbeGridDepthState d;
+    CHECK(d.moments.count() == 0 && d.resolution() == 0);
+    CHECK(probe_grid_depth_check_input(75, 4) == RAYS_OK && probe_grid_depth_check_input((size_t)1 << 22, 16) == RAYS_OK);
+    CHECK(probe_grid_depth_check_input(0, 4) == RAYS_INVALID_ARG && probe_grid_depth_check_input(75, 5) == RAYS_INVALID_ARG);
+    CHECK(probe_grid_depth_check_input(((size_t)1 << 22) + 1, 16) == RAYS_INVALID_ARG && probe_grid_depth_check_input(((size_t)1 << 30) + 1, 4) == RAYS_INVALID_ARG);
+    CHECK(probe_grid_depth_check_input(~(size_t)0, 16) == RAYS_INVALID_ARG);  // (no overflow on the way)
+    probe_grid_depth_written(d, 75, 8);
+    CHECK(d.moments.count() == 75 && d.resolution() == 8);
+    CHECK(probe_grid_depth_bind(d, &dummy, 0, 4) == RAYS_INVALID_ARG && probe_grid_depth_bind(d, nullptr, 3, 4) == RAYS_INVALID_ARG);
+    CHECK(probe_grid_depth_bind(d, &dummy, 10, 7) == RAYS_INVALID_ARG && d.moments.count() == 75 && d.resolution() == 8);  // refused: left as it was
+    CHECK(probe_grid_depth_bind(d, &dummy, 10, 16) == RAYS_OK && d.moments.count() == 10 && d.resolution() == 16);
+    CHECK(probe_grid_depth_bind(d, nullptr, 0, 0) == RAYS_OK && d.moments.count() == 75 && d.resolution() == 8);
+    CHECK(probe_grid_depth_bind(d, &dummy, 10, 16) == RAYS_OK);
+    probe_grid_depth_written(d, 60, 4);  // a write ends the binding
+    CHECK(d.moments.bound == nullptr && d.moments.count() == 60 && d.resolution() == 4);
+    // the filtered call's checks: rule 16 first, VISIBILITY where an unknown flag is, then the maps, then the depth parameters
+    ProbeGridState g;
+    ProbeGridDepthState none;
+    ProbeGridCall pc;
+    probe_grid_call_default(pc);
+    pc.row_begin = 0, pc.row_end = 20;
+    probe_grid_depth_call_default(dc);
+    const bool all[PROBE_GRID_GUIDES] = {true, true, true, true}, no_object[PROBE_GRID_GUIDES] = {false, true, true, true};
+    ProbeGridDepthCall bad_dc = dc;
+    bad_dc.bias = -1.0f;
+    CHECK(probe_grid_depth_check_shade(g, none, pc, bad_dc, false, 20, all, &why) == RAYS_STATE && strstr(why, "srt_set_scene"));
+    ProbeGridCall vis = pc;
+    vis.flags = PROBE_GRID_FLAG_VISIBILITY, vis.row_end = 21;
+    CHECK(probe_grid_depth_check_shade(g, none, vis, dc, true, 20, all, &why) == RAYS_INVALID_ARG && strstr(why, "band"));  // the band before the flags
+    vis.row_end = 20, vis.reserved[0] = 1;
+    CHECK(probe_grid_depth_check_shade(g, none, vis, dc, true, 20, all, &why) == RAYS_INVALID_ARG && strstr(why, "exclude each other"));  // the flags before reserved
+    vis = pc, vis.flags = 16;
+    CHECK(probe_grid_depth_check_shade(g, none, vis, dc, true, 20, all, &why) == RAYS_INVALID_ARG && strstr(why, "unknown flags"));
+    for (uint32_t f = 0; f < 16; ++f) {
+        ProbeGridCall fc = pc;
+        fc.flags = f;
+        const RaysStatus rs = probe_grid_depth_check_shade(g, none, fc, dc, true, 20, all, &why);
+        CHECK((f & 1u) ? rs == RAYS_INVALID_ARG : (rs == RAYS_STATE && strstr(why, "no grid")));
+    }
+    CHECK(probe_grid_depth_check_shade(g, none, pc, bad_dc, true, 20, all, &why) == RAYS_STATE && strstr(why, "no grid"));
+    g.grid_set = true;
+    g.grid.counts[0] = 5, g.grid.counts[1] = 3, g.grid.counts[2] = 5;
+    CHECK(probe_grid_depth_check_shade(g, none, pc, bad_dc, true, 20, all, &why) == RAYS_STATE && strstr(why, "no coefficients"));
+    g.coefficients.own_count = 75;
+    CHECK(probe_grid_depth_check_shade(g, none, pc, bad_dc, true, 20, no_object, &why) == RAYS_STATE && strstr(why, "OBJECT"));
+    g.coefficients.own_count = 74;
+    CHECK(probe_grid_depth_check_shade(g, d, pc, bad_dc, true, 20, all, &why) == RAYS_STATE && strstr(why, "coefficient count"));
+    g.coefficients.own_count = 75;
+    CHECK(probe_grid_depth_check_shade(g, none, pc, bad_dc, true, 20, all, &why) == RAYS_STATE && strstr(why, "no depth maps"));
+    CHECK(probe_grid_depth_check_shade(g, d, pc, bad_dc, true, 20, all, &why) == RAYS_STATE && strstr(why, "depth probe count"));  // 60 maps
+    probe_grid_depth_written(d, 75, 16);
+    CHECK(probe_grid_depth_check_shade(g, d, pc, bad_dc, true, 20, all, &why) == RAYS_INVALID_ARG && strstr(why, "bias"));
+    const float bad_bias[] = {nan, inf, -inf, -1e-30f}, bad_var[] = {nan, inf, -inf, 0.0f, -0.0f, -1.0f};
+    for (float b : bad_bias) {
+        bad_dc = dc, bad_dc.bias = b, bad_dc.min_variance = 0.0f;
+        CHECK(probe_grid_depth_check_shade(g, d, pc, bad_dc, true, 20, all, &why) == RAYS_INVALID_ARG && strstr(why, "bias"));  // the bias before the variance
+    }
+    for (float v : bad_var) {
+        bad_dc = dc, bad_dc.min_variance = v, bad_dc.reserved[1] = 1;
+        CHECK(probe_grid_depth_check_shade(g, d, pc, bad_dc, true, 20, all, &why) == RAYS_INVALID_ARG && strstr(why, "min_variance"));
+    }
+    for (int k = 0; k < 2; ++k) {
+        bad_dc = dc, bad_dc.reserved[k] = 1;
+        CHECK(probe_grid_depth_check_shade(g, d, pc, bad_dc, true, 20, all, &why) == RAYS_INVALID_ARG && strstr(why, "reserved"));
+    }
+    ProbeGridDepthCall ok_dc = dc;
+    ok_dc.bias = -0.0f, ok_dc.min_variance = 1e-45f;
+    CHECK(probe_grid_depth_check_shade(g, d, pc, ok_dc, true, 20, all, &why) == RAYS_OK);
+    ok_dc.bias = 3e38f, ok_dc.min_variance = 3e38f;
+    pc.flags = PROBE_GRID_FLAG_NORMAL_WEIGHT | PROBE_GRID_FLAG_ALBEDO | PROBE_GRID_FLAG_COUNT_WORK;
+    CHECK(probe_grid_depth_check_shade(g, d, pc, ok_dc, true, 20, all, nullptr) == RAYS_OK);
+    // both calls share the "last call" record
+    probe_grid_shaded(g, pc.flags);
+    CHECK(probe_grid_check_work(g) == RAYS_OK);
+    probe_grid_shaded(g, 0);
+    CHECK(probe_grid_check_work(g) == RAYS_STATE);
+    printf("ok %d\n", checks);
+    return 0;
+}
