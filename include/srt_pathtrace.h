@@ -1637,6 +1637,112 @@ int srt_get_probe_grid_work(srt_context* ctx, srt_probe_grid_work* out);
  * reference's interface. */
 int srt_selftest_arith(int device, uint32_t seed, uint64_t vectors, uint64_t* mismatches);
 
+/* ---- probe classification and relocation: states and offsets for a probe grid (ABI 7, backward compatible) ----------------------
+ * These calls were added without changing anything else, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of them
+ * runs what it ran before, bit for bit.  (The rules are numbered S1 .. S9; the blocks that use them follow further down.)
+ *
+ * A grid laid blindly over a scene puts probes inside objects, where they see nothing of use and where the filtered visibility
+ * test cannot tell (a depth map traced from inside a sphere or a box does not give the probe away).  srt_classify_probes finds
+ * those probes, and with SRT_PROBE_CLASSIFY_RELOCATE moves probes that are inside or too near a surface to a free place nearby.
+ * Spheres and axis-aligned boxes have an exact signed distance, so the pass traces no ray.  LIMIT: mesh objects contribute no
+ * distance; a probe inside a mesh is not found, and a scene with a mesh object never gets an IDLE probe.
+ *
+ * Inputs: the grid of srt_set_probe_grid, P = nx*ny*nz probes, probe g at the position of the probe-grid block's rule 4; with
+ * SRT_PROBE_CLASSIFY_RELOCATE the K shared directions of the light-probe block (srt_write_light_probe_directions,
+ * srt_bind_light_probe_directions), of which only xyz is read, each replaced by float3::Normalized(d) with
+ * SRT_PROBE_CLASSIFY_NORMALIZE (as SRT_RAYS_NORMALIZE); and the scene's object list as srt_set_scene / srt_update_scene keep it at
+ * enqueue.  The pass keeps a primitive table of its own, rebuilt from the list at the first srt_classify_probes after the scene
+ * changed (that call then waits for earlier work); srt_set_scene and srt_update_scene do what they did.
+ *
+ * Rules.  All arithmetic is binary32 without contraction.
+ * S1. Scene distance S(x).  S = +inf; then for every sphere and box of the list S = sd < S ? sd : S, so a NaN is ignored and the
+ *    order is irrelevant.  Sphere: e = x - c; D = sqrtf((e.x*e.x + e.y*e.y) + e.z*e.z); sd = D - fabsf(radius).  Box, per axis a:
+ *    q_a = fabsf(x_a - c_a) - h_a; m_a = q_a > 0 ? q_a : 0; then with max(a, b) = a > b ? a : b and min0(a) = a < 0 ? a : 0:
+ *    sd = sqrtf((m.x*m.x + m.y*m.y) + m.z*m.z) + min0(max(max(q.x, q.y), q.z)).  Inert and mesh objects contribute nothing.
+ * S2. Scales.  smin = the smallest spacing component; margin = clearance * smin; reach = sqrtf((sx*sx + sy*sy) + sz*sz);
+ *    dt = max_offset / (float)steps.
+ * S3. Probe at rest.  s0 = S(g).  Without SRT_PROBE_CLASSIFY_RELOCATE: state = s0 < 0 ? BURIED|INSIDE : CLEAR (0), offset 0.
+ *    With it and !(s0 < margin): CLEAR, offset 0.  A CLEAR probe with s0 > 1.0625f * reach additionally gets IDLE, but only when
+ *    the scene has no mesh object: 1.0625f covers the rounding of S and shading rule 5's 1e-5 normal offset, so no first-hit
+ *    point on an analytic surface can lie in one of the probe's eight cells.
+ * S4. Search, with SRT_PROBE_CLASSIFY_RELOCATE and s0 < margin.  For m = 1 .. steps ascending: t = (float)m * dt; for every k the
+ *    offset is o_a = (d_k.a * t) * spacing_a and the candidate x_a = g_a + o_a; a candidate is accepted if S(x) >= margin.  At
+ *    the first m with an accepted candidate the one with the largest S(x) as a binary32 value wins, on equal values the lowest
+ *    k: state = MOVED, plus INSIDE if s0 < 0, offset o.  If no m has one: s0 < 0 ? BURIED|INSIDE : CLEAR, offset 0.
+ * S5. Outputs, a bit mask.  SRT_PROBE_STATE_RECORDS: P float4 (o.x, o.y, o.z, the state's uint32 bits in w).
+ *    SRT_PROBE_STATE_POSITIONS, optional: P float4 (g_a + o_a, w = 0), srt_write_light_probes' layout, so the buffer can be bound
+ *    with srt_bind_light_probes and nothing crosses the bus.  Each is the handle's own buffer (allocated on first use, grown when
+ *    a call needs more) or the caller's: srt_bind_probe_states_output binds a DEVICE buffer, NULL = own, under
+ *    srt_bind_probe_depth_output's rules.  srt_read_probe_states_output waits, then copies what the last srt_classify_probes
+ *    wrote of that output, from the buffer it wrote; SRT_ERR_STATE when the last call did not write it.
+ * S6. Determinism.  No atomics reach an output; repeated calls give the same bits.
+ * S7. Work counts.  With SRT_PROBE_CLASSIFY_COUNT_WORK the launch counts, deterministically: its probes (P), those with INSIDE,
+ *    MOVED, BURIED and IDLE, the candidate positions evaluated (K per step a searching probe ran) and the waves of the launch.
+ *    One vector atomic per wave at the end; without the flag there are no atomics at all.  srt_get_probe_classify_work waits and
+ *    copies the record of the last srt_classify_probes; SRT_ERR_STATE unless that call had the flag.
+ * S8. Parameters.  clearance: finite, 0 < clearance <= 0.5; max_offset: finite, 0 < max_offset <= 0.5, a fraction of the spacing,
+ *    so with directions no longer than 1 a probe never leaves its cell neighbourhood; steps: 1 .. 64.
+ * S9. Errors, all found before anything is touched, in this order: SRT_ERR_STATE before srt_set_scene; SRT_ERR_INVALID_ARG for
+ *    unknown flags or outputs, outputs == 0, a clearance or max_offset outside its range (a NaN included), steps outside 1 .. 64
+ *    or a non-zero reserved; SRT_ERR_STATE with no grid, or (with SRT_PROBE_CLASSIFY_RELOCATE) no directions; SRT_ERR_OOM when
+ *    a buffer cannot be had.  Asynchrony: as rule 8 of the light-probe block. */
+#define SRT_PROBE_STATE_RECORDS 1u      /* output: P float4 (offset, state bits) */
+#define SRT_PROBE_STATE_POSITIONS 2u    /* output: P float4 (position, 0), optional */
+#define SRT_PROBE_CLASSIFY_RELOCATE 1u  /* flags: rule S4 */
+#define SRT_PROBE_CLASSIFY_NORMALIZE 2u /* flags: as SRT_RAYS_NORMALIZE */
+#define SRT_PROBE_CLASSIFY_COUNT_WORK 4u /* flags: fill srt_probe_classify_work for this call */
+#define SRT_PROBE_CLEAR 0u              /* state bits in a record's w lane */
+#define SRT_PROBE_MOVED 1u              /* stands at grid position + offset */
+#define SRT_PROBE_BURIED 2u             /* inside an object and not moved out: shading skips it */
+#define SRT_PROBE_INSIDE 4u             /* the grid position lies inside an object */
+#define SRT_PROBE_IDLE 8u               /* clear, and no analytic surface comes near any of its eight cells */
+
+typedef struct srt_probe_classify_params { /* 24 bytes */
+    float clearance;                       /* margin = clearance * smallest spacing; (0, 0.5] */
+    float max_offset;                      /* longest offset as a fraction of the spacing; (0, 0.5] */
+    uint32_t steps;                        /* 1..64 offset lengths tried, ascending */
+    uint32_t flags;                        /* SRT_PROBE_CLASSIFY_RELOCATE | _NORMALIZE | _COUNT_WORK */
+    uint32_t outputs;                      /* SRT_PROBE_STATE_RECORDS | _POSITIONS, not 0 */
+    uint32_t reserved;                     /* 0 */
+} srt_probe_classify_params;
+
+typedef struct srt_probe_classify_work { /* 64 bytes */
+    uint32_t valid, reserved;            /* 1, 0 */
+    uint64_t probes;                     /* P */
+    uint64_t inside, moved, buried, idle; /* probes whose state has that bit */
+    uint64_t candidates;                 /* candidate positions evaluated: K per step run */
+    uint64_t waves;                      /* waves of the launch */
+} srt_probe_classify_work;
+
+/* clearance 0.2f, max_offset 0.45f, steps 8, flags 0, outputs SRT_PROBE_STATE_RECORDS, reserved 0 (pure host). */
+int srt_probe_classify_params_default(srt_probe_classify_params* out);
+int srt_classify_probes(srt_context* ctx, const srt_probe_classify_params* params);
+int srt_bind_probe_states_output(srt_context* ctx, uint32_t output, void* d_ptr);
+int srt_read_probe_states_output(srt_context* ctx, uint32_t output, void* dst);
+int srt_get_probe_classify_work(srt_context* ctx, srt_probe_classify_work* out);
+
+/* ---- probe-grid shading that obeys the probe states (ABI 7, backward compatible) -------------------------------------------------
+ * srt_shade_probe_grid_states(ctx, params, depth) is srt_shade_probe_grid (depth == NULL) or srt_shade_probe_grid_depth (otherwise)
+ * rule for rule — the same grid, coefficients, depth maps, guides, band and band weights, the same output slot and the same "last
+ * call" record (srt_get_probe_grid_work) — except for two rules:
+ * 3s. After rule 3, rec = states[k] for the clamped probe index k of rule 8 (one 16-byte load).  A corner whose record has
+ *    SRT_PROBE_BURIED is skipped before rule 5 and enters no counter.  IDLE, MOVED and INSIDE are not looked at.
+ * 4s. p_a = (origin_a + (float)(i_a + c_a) * spacing_a) + rec.o_a.  Rules 5, 6, 7b, 8 and 9 use that p.  The trilinear weights
+ *    stay the grid's.  The coefficients and moments are expected to have been traced at the relocated positions.
+ * The states are P = nx*ny*nz float4 in SRT_PROBE_STATE_RECORDS' layout.  srt_write_probe_grid_states copies them from the host
+ * into the handle's own array and waits; srt_bind_probe_grid_states binds a DEVICE array, does not copy and does not wait (what
+ * srt_bind_probe_states_output filled can be bound here); NULL, 0 returns to the own array.  1 <= probes <= 2^30, otherwise
+ * SRT_ERR_INVALID_ARG and the previous states stay.
+ * Flags: SRT_PROBE_GRID_VISIBILITY is SRT_ERR_INVALID_ARG, found where an unknown flag is: the exact test towards relocated
+ * probes needs a tracing kernel and is out of scope.  Without depth the work record's segments and open are 0, as they are for
+ * srt_shade_probe_grid without the query.  Extra errors, after all of the parent call's: SRT_ERR_STATE for no states, or for a
+ * state count other than nx*ny*nz.
+ * Pinned domain.  Finite offsets are pinned bit for bit.  Other values give some value and no fault: indices stay clamped. */
+int srt_write_probe_grid_states(srt_context* ctx, const float* records, size_t probes);
+int srt_bind_probe_grid_states(srt_context* ctx, const void* d_ptr, size_t probes);
+struct srt_probe_grid_depth_params; /* (defined in the filtered-shading block below) */
+int srt_shade_probe_grid_states(srt_context* ctx, const srt_probe_grid_params* params, const struct srt_probe_grid_depth_params* depth);
+
 /* ---- probe depth moments: a filtered estimate of what a probe sees (ABI 7, backward compatible) ---------------------------------
  * These calls were added without changing anything above, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of
  * them runs what it ran before, bit for bit.

@@ -54,6 +54,10 @@ PROBE_GRID_BAND_WEIGHT_HEMISPHERE = (1.0, 0.5, 0.0)  # the mean over the hemisph
 PROBE_DEPTH_MOMENTS, PROBE_DEPTH_DISTANCES = 1, 2
 PROBE_DEPTH_NORMALIZE, PROBE_DEPTH_COUNT_WORK = 1, 2
 PROBE_DEPTH_RESOLUTIONS = (4, 8, 16)
+# probe classification and relocation (srt_classify_probes): the outputs and flags of srt_probe_classify_params, the state bits
+PROBE_STATE_RECORDS, PROBE_STATE_POSITIONS = 1, 2
+PROBE_CLASSIFY_RELOCATE, PROBE_CLASSIFY_NORMALIZE, PROBE_CLASSIFY_COUNT_WORK = 1, 2, 4
+PROBE_CLEAR, PROBE_MOVED, PROBE_BURIED, PROBE_INSIDE, PROBE_IDLE = 0, 1, 2, 4, 8
 # adaptive sampling (srt_render_adaptive, srt_sample_budget): the flags, the limits of max_samples / max_budget, the last frame
 ADAPTIVE_KEEP_COUNTS, ADAPTIVE_COUNT_WORK = 1, 2
 ADAPTIVE_MAX_SAMPLES = 4096
@@ -117,6 +121,8 @@ EXPORTS = [
     "srt_probe_depth_params_default", "srt_probe_depth_texels", "srt_trace_probe_depth", "srt_bind_probe_depth_output",
     "srt_read_probe_depth_output", "srt_get_probe_depth_work",
     "srt_probe_grid_depth_params_default", "srt_write_probe_grid_depth", "srt_bind_probe_grid_depth", "srt_shade_probe_grid_depth",
+    "srt_probe_classify_params_default", "srt_classify_probes", "srt_bind_probe_states_output", "srt_read_probe_states_output",
+    "srt_get_probe_classify_work", "srt_write_probe_grid_states", "srt_bind_probe_grid_states", "srt_shade_probe_grid_states",
 ]
 
 
@@ -376,6 +382,22 @@ class ProbeGridDepthParams(C.Structure):
     _fields_ = [("bias", C.c_float), ("min_variance", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class ProbeClassifyParams(C.Structure):
+    """srt_probe_classify_params: the clearance and the longest offset as fractions of the spacing, the offset steps,
+    PROBE_CLASSIFY_* flags and PROBE_STATE_* outputs."""
+    _fields_ = [("clearance", C.c_float), ("max_offset", C.c_float), ("steps", C.c_uint32), ("flags", C.c_uint32), ("outputs", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class ProbeClassifyWork(C.Structure):
+    """srt_probe_classify_work: what the last counting srt_classify_probes found."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("inside", C.c_uint64), ("moved", C.c_uint64),
+                ("buried", C.c_uint64), ("idle", C.c_uint64), ("candidates", C.c_uint64), ("waves", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class UpdateInfo(C.Structure):
     """srt_update_info: what the last successful srt_update_scene did to the mesh image."""
     _fields_ = [("path", C.c_int32), ("reason", C.c_int32), ("levels", C.c_int32), ("triangles", C.c_uint32), ("nodes", C.c_uint32),
@@ -578,6 +600,14 @@ def open_library(path):
     L.srt_write_probe_grid_depth.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t, C.c_uint32]
     L.srt_bind_probe_grid_depth.argtypes = [ctx, C.c_void_p, C.c_size_t, C.c_uint32]
     L.srt_shade_probe_grid_depth.argtypes = [ctx, C.POINTER(ProbeGridParams), C.POINTER(ProbeGridDepthParams)]
+    L.srt_probe_classify_params_default.argtypes = [C.POINTER(ProbeClassifyParams)]
+    L.srt_classify_probes.argtypes = [ctx, C.POINTER(ProbeClassifyParams)]
+    L.srt_bind_probe_states_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_read_probe_states_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_get_probe_classify_work.argtypes = [ctx, C.POINTER(ProbeClassifyWork)]
+    L.srt_write_probe_grid_states.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t]
+    L.srt_bind_probe_grid_states.argtypes = [ctx, C.c_void_p, C.c_size_t]
+    L.srt_shade_probe_grid_states.argtypes = [ctx, C.POINTER(ProbeGridParams), C.POINTER(ProbeGridDepthParams)]
     L.srt_set_sample_counts.argtypes = [ctx, C.c_uint32]
     L.srt_write_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
     L.srt_read_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
@@ -1685,6 +1715,147 @@ class PathTracer:
             d.min_variance = float(min_variance)
         d.reserved[0], d.reserved[1] = int(depth_reserved[0]), int(depth_reserved[1])
         self._ck(L.srt_shade_probe_grid_depth(self._h, C.byref(p), C.byref(d)))
+
+    # ---- probe classification and relocation, and the probe-grid shading that obeys the records ----
+    def classify_probes(self, directions=None, relocate=False, clearance=None, max_offset=None, steps=None, normalize=False, count_work=False,
+                        records=True, positions=False, flags=0, reserved=0):
+        """srt_classify_probes: the state of every probe of the grid (set_probe_grid() first) from the exact signed distance to the
+        scene's spheres and boxes (meshes contribute nothing): PROBE_INSIDE when the grid position lies inside an object,
+        PROBE_BURIED when it stays there, PROBE_IDLE when no analytic surface comes near its cells.  relocate: probes nearer than
+        `clearance` (default 0.2) times the smallest spacing to a surface are moved along one of the K shared `directions` (as
+        trace_light_probes() takes them; None: the current ones) by at most `max_offset` (default 0.45) of the spacing, tried in
+        `steps` (default 8) lengths: PROBE_MOVED.  records / positions: the outputs (probe_states_output()); count_work:
+        probe_states_work() then reads the record.  Asynchronous, like render()."""
+        L = self.L
+        if directions is not None:
+            if isinstance(directions, (int, np.integer)):
+                directions = light_probe_sphere(int(directions), lib=L)
+            self._probe_dir_count, self._probe_dir_bound = self._light_probe_input("classify_probes(directions)", directions,
+                                                                                   L.srt_write_light_probe_directions,
+                                                                                   L.srt_bind_light_probe_directions, LIGHT_PROBE_MAX_DIRECTIONS)
+        p = ProbeClassifyParams()
+        self._ck(L.srt_probe_classify_params_default(C.byref(p)))
+        if clearance is not None:
+            p.clearance = float(clearance)
+        if max_offset is not None:
+            p.max_offset = float(max_offset)
+        if steps is not None:
+            p.steps = int(steps)
+        p.flags = (int(flags) | (PROBE_CLASSIFY_RELOCATE if relocate else 0) | (PROBE_CLASSIFY_NORMALIZE if normalize else 0) |
+                   (PROBE_CLASSIFY_COUNT_WORK if count_work else 0))
+        p.outputs = (PROBE_STATE_RECORDS if records else 0) | (PROBE_STATE_POSITIONS if positions else 0)
+        p.reserved = int(reserved)
+        n = getattr(self, "_probe_grid_probes", None)
+        if n is not None:
+            for bit, t in self.__dict__.get("_probe_states_bound", {}).items():
+                if (p.outputs & bit) and t.numel() < 4 * n:
+                    raise ValueError("classify_probes: the bound tensor holds %d floats, the call writes %d" % (t.numel(), 4 * n))
+        self._ck(L.srt_classify_probes(self._h, C.byref(p)))
+        self._probe_states_classified = n
+
+    def bind_probe_states_output(self, output, tensor):
+        """srt_bind_probe_states_output: write output "records" or "positions" (P float4 each) into a float32 torch tensor (M, 4),
+        M >= P, on this tracer's device, contiguous (checked by classify_probes); None: the handle's own buffer.  The caller keeps
+        the tensor alive until the calls have finished."""
+        bit = {"records": PROBE_STATE_RECORDS, "positions": PROBE_STATE_POSITIONS}.get(output, output)
+        if tensor is not None:
+            import torch
+
+            if not isinstance(tensor, torch.Tensor):
+                raise TypeError("bind_probe_states_output: expected a torch.Tensor, got %s" % type(tensor).__name__)
+            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
+            if m < 1:
+                raise ValueError("bind_probe_states_output: shape %s, want at least one element" % (tuple(tensor.shape),))
+            ptr = self._tensor_ptr("bind_probe_states_output", tensor, np.float32, (m, 4))
+        else:
+            ptr = None
+        self._ck(self.L.srt_bind_probe_states_output(self._h, int(bit), ptr))
+        bound = self.__dict__.setdefault("_probe_states_bound", {})
+        if tensor is None:
+            bound.pop(bit, None)
+        else:
+            bound[bit] = tensor
+
+    def probe_states_output(self, output="records"):
+        """srt_read_probe_states_output: "records": (P, 4) float32, the offset in xyz and the state's uint32 bits in w
+        (records[:, 3].view(np.uint32)); "positions": (P, 4) float32, the probes where they stand, w = 0.  Waits."""
+        bit = {"records": PROBE_STATE_RECORDS, "positions": PROBE_STATE_POSITIONS}.get(output, output)
+        n = getattr(self, "_probe_states_classified", None)
+        if n is None:
+            raise SrtError(ERR_STATE, "probe_states_output(): no classify_probes() yet")
+        return self._read_image(self.L.srt_read_probe_states_output, (n, 4), np.float32, int(bit))
+
+    def probe_states_work(self):
+        """srt_get_probe_classify_work: the work counts of the last classify_probes(count_work=True) as a dict.  Waits."""
+        w = ProbeClassifyWork()
+        self._ck(self.L.srt_get_probe_classify_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def bind_probe_grid_states(self, records):
+        """srt_write_probe_grid_states / srt_bind_probe_grid_states: the records shade_probe_grid_states() obeys, in
+        probe_states_output("records")'s layout.  numpy (P, 4) float32: written; a torch tensor (P, 4) on this tracer's device: bound,
+        no copy (what bind_probe_states_output("records", t) filled); None: back to the own array."""
+        L = self.L
+        if records is None:
+            self._ck(L.srt_bind_probe_grid_states(self._h, None, 0))
+            self._probe_grid_states_bound = None
+            return
+        kind, arr, n = self._ray_array("bind_probe_grid_states(records)", records)
+        if kind == "host":
+            self._ck(L.srt_write_probe_grid_states(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n))
+            self._probe_grid_states_bound = None
+        else:
+            self._ck(L.srt_bind_probe_grid_states(self._h, C.c_void_p(arr.data_ptr()), n))
+            self._probe_grid_states_bound = arr  # (a bound tensor stays referenced for as long as it is bound)
+
+    def shade_probe_grid_states(self, coefficients=None, states=None, depth=False, moments=None, resolution=None, bias=None, min_variance=None,
+                                normal_weight=False, albedo=False, band_weight=None, rows=None, count_work=False, output=None, flags=0,
+                                reserved=(0, 0), depth_reserved=(0, 0)):
+        """srt_shade_probe_grid_states: shade_probe_grid() (depth=False) or shade_probe_grid_depth() (depth=True, or `moments`
+        given) that obeys the probe records: a PROBE_BURIED probe is skipped, every other probe stands at its grid position plus
+        the record's offset.  `states`: as bind_probe_grid_states() (None: the current records); everything else as the parent
+        calls.  The exact visibility test is not available.  probe_grid_output() and probe_grid_work() read the result."""
+        L = self.L
+        if coefficients is not None:
+            a = coefficients
+            if isinstance(a, np.ndarray) and a.ndim == 3:
+                a = a.reshape(-1, 4)
+            kind, arr, n = self._ray_array("shade_probe_grid_states(coefficients)", a)
+            if n % LIGHT_PROBE_COEFFS:
+                raise ValueError("shade_probe_grid_states(coefficients): %d float4, want nine per probe" % n)
+            if kind == "host":
+                self._ck(L.srt_write_probe_grid_coefficients(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n // LIGHT_PROBE_COEFFS))
+                self._probe_grid_bound = None
+            else:
+                self._ck(L.srt_bind_probe_grid_coefficients(self._h, C.c_void_p(arr.data_ptr()), n // LIGHT_PROBE_COEFFS))
+                self._probe_grid_bound = arr
+        if states is not None:
+            self.bind_probe_grid_states(states)
+        if moments is not None:
+            self.bind_probe_grid_depth(moments, resolution)
+            depth = True
+        if output is not None:
+            self.bind_probe_grid_output(output)
+        p = ProbeGridParams()
+        self._ck(L.srt_probe_grid_params_default(C.byref(p)))
+        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
+        p.flags = (int(flags) | (PROBE_GRID_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_GRID_ALBEDO if albedo else 0) |
+                   (PROBE_GRID_COUNT_WORK if count_work else 0))
+        if band_weight is not None:
+            for b in range(3):
+                p.band_weight[b] = float(band_weight[b])
+        p.reserved[0], p.reserved[1] = int(reserved[0]), int(reserved[1])
+        if not depth:
+            self._ck(L.srt_shade_probe_grid_states(self._h, C.byref(p), None))
+            return
+        d = ProbeGridDepthParams()
+        self._ck(L.srt_probe_grid_depth_params_default(C.byref(d)))
+        if bias is not None:
+            d.bias = float(bias)
+        if min_variance is not None:
+            d.min_variance = float(min_variance)
+        d.reserved[0], d.reserved[1] = int(depth_reserved[0]), int(depth_reserved[1])
+        self._ck(L.srt_shade_probe_grid_states(self._h, C.byref(p), C.byref(d)))
 
     def ray_output(self, name, count=None):
         """srt_read_ray_output: one output of the last trace_rays() as a numpy array: "object" and "occluded" (N,) int32, the

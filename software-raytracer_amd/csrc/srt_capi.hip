@@ -45,6 +45,8 @@
 #include "srt_probe_grid_host.h"
 #include "srt_probe_depth.hip.h"
 #include "srt_probe_depth_host.h"
+#include "srt_probe_states.hip.h"
+#include "srt_probe_states_host.h"
 #include "srt_adaptive.hip.h"
 #include "srt_adaptive_host.h"
 #include "srt_launch_shape.h"
@@ -430,6 +432,20 @@ struct srt_context {
     DeviceBuffer<unsigned long long> d_probe_depth_work;
     srt::ProbeGridDepthState probe_grid_depth;
     DeviceBuffer<float4> d_probe_grid_depth;
+    // probe classification and relocation (srt_classify_probes): the primitive table the kernel reads, built from the object list at
+    // the first classification after the scene changed (scene_changes says when); one own output buffer per SRT_PROBE_STATE_* output
+    // bit with its slot (the bound buffer only); what the last classification wrote, whether it counted and which state array
+    // srt_shade_probe_grid_states reads (srt_probe_states_host.h); the own state array (srt_write_probe_grid_states); the record a
+    // counting launch adds to (srt::PS_WORK_N words).
+    srt::ProbeTable probe_table;
+    DeviceBuffer<float4> d_probe_table;
+    bool probe_table_ready = false;
+    unsigned long long probe_table_scene = 0;
+    DeviceBuffer<void> d_probe_states_own[srt::PROBE_STATE_SLOTS];
+    srt::OutputSlot probe_states_out[srt::PROBE_STATE_SLOTS];
+    srt::ProbeStatesState probe_states;
+    DeviceBuffer<float4> d_probe_grid_states;
+    DeviceBuffer<unsigned long long> d_probe_classify_work;
     // adaptive sampling (srt_render_adaptive, srt_sample_budget): the per-pixel sample counts and sample budget, W*H uint32 each,
     // own buffer and slot; whether the last adaptive render counted and whether a budget pass has run (srt_adaptive_host.h); the
     // tile ticket of a launch (zeroed on the stream in front of it); the record a counting launch adds to (srt::ADP_WORK_N words);
@@ -2565,6 +2581,196 @@ int srt_shade_probe_grid_depth(srt_context* ctx, const srt_probe_grid_params* s,
     io.bias = d->bias, io.min_variance = d->min_variance;
     io.work = count ? (unsigned long long*)ctx->d_probe_grid_work : nullptr;
     if (const int rc = launch_tiles(ctx, count ? srt::probe_grid_depth_kernel<true> : srt::probe_grid_depth_kernel<false>, ks, K, io)) return rc;
+    ctx->probe_grid_out.wrote(dst);
+    srt::probe_grid_shaded(ctx->probe_grid, s->flags);
+    return SRT_OK;
+}
+
+// ---- probe classification and relocation ----------------------------------------------------------------------------
+static_assert(SRT_PROBE_STATE_RECORDS == srt::PROBE_STATE_OUT_RECORDS && SRT_PROBE_STATE_POSITIONS == srt::PROBE_STATE_OUT_POSITIONS &&
+              SRT_PROBE_CLASSIFY_RELOCATE == srt::PROBE_CLASSIFY_FLAG_RELOCATE && SRT_PROBE_CLASSIFY_NORMALIZE == srt::PROBE_CLASSIFY_FLAG_NORMALIZE &&
+              SRT_PROBE_CLASSIFY_COUNT_WORK == srt::PROBE_CLASSIFY_FLAG_COUNT_WORK && SRT_PROBE_MOVED == srt::PROBE_MOVED && SRT_PROBE_BURIED == srt::PROBE_BURIED &&
+              SRT_PROBE_INSIDE == srt::PROBE_INSIDE && SRT_PROBE_IDLE == srt::PROBE_IDLE && (uint32_t)srt::PS_MOVED == srt::PROBE_MOVED &&
+              (uint32_t)srt::PS_BURIED == srt::PROBE_BURIED && (uint32_t)srt::PS_INSIDE == srt::PROBE_INSIDE && (uint32_t)srt::PS_IDLE == srt::PROBE_IDLE &&
+              SRT_OBJ_SPHERE == srt::PROBE_TABLE_OBJ_SPHERE && SRT_OBJ_BOX == srt::PROBE_TABLE_OBJ_BOX && SRT_OBJ_MESH == srt::PROBE_TABLE_OBJ_MESH &&
+              sizeof(srt_probe_classify_params) == 24 && sizeof(srt::ProbeClassifyCall) == 24 && sizeof(srt_probe_classify_work) == 64 && srt::PS_WORK_N == 7,
+              "srt_probe_states_host.h, srt_probe_states.hip.h and srt_pathtrace.h disagree");
+
+int srt_probe_classify_params_default(srt_probe_classify_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::ProbeClassifyCall c;
+    srt::probe_classify_call_default(c);
+    memcpy(out, &c, sizeof c);
+    return SRT_OK;
+}
+
+// ... in front of the re-allocation of own probe-state output `i`: earlier classifications may still be writing it
+static int probe_states_output_released(srt_context* ctx, int i) {
+    if (const int rc = finish_stream(ctx)) return rc;
+    srt::probe_states_output_released(ctx->probe_states, i, (void*)ctx->d_probe_states_own[i]);
+    return SRT_OK;
+}
+
+// The primitive table of the scene as it stands, on the device: rebuilt when the scene has changed since the last build.  Earlier
+// classifications may still read the old one, so the stream is finished first.
+static int probe_table_current(srt_context* ctx) {
+    if (ctx->probe_table_ready && ctx->probe_table_scene == ctx->scene_changes) return SRT_OK;
+    if (const int rc = finish_stream(ctx)) return rc;
+    ctx->probe_table_ready = false;
+    try {
+        srt::probe_table_build(ctx->objects.data(), ctx->objects.size(), ctx->probe_table);
+    } catch (const std::bad_alloc&) {
+        return fail(ctx, SRT_ERR_OOM, "srt_classify_probes: host allocation failed");
+    }
+    const size_t bytes = (ctx->probe_table.vec4() > 0 ? ctx->probe_table.vec4() : 1) * sizeof(float4);
+    SRT_HIP(ctx, ctx->d_probe_table.ensure(bytes));
+    if (ctx->probe_table.vec4() > 0)
+        SRT_HIP(ctx, hipMemcpy(ctx->d_probe_table, ctx->probe_table.rows.data(), ctx->probe_table.vec4() * sizeof(float4), hipMemcpyHostToDevice));
+    ctx->probe_table_ready = true, ctx->probe_table_scene = ctx->scene_changes;
+    return SRT_OK;
+}
+
+int srt_classify_probes(srt_context* ctx, const srt_probe_classify_params* t) {
+    if (!ctx || !t) return SRT_ERR_INVALID_ARG;
+    srt::ProbeClassifyCall call;
+    memcpy(&call, t, sizeof call);
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_classify_check(ctx->probe_grid, ctx->probes.directions.count(), ctx->scene_set, call, &why))
+        return fail(ctx, (int)rs, "srt_classify_probes: %s (clearance %g, max_offset %g, steps %u, flags 0x%x, outputs 0x%x, reserved %u)", why, (double)t->clearance,
+                    (double)t->max_offset, t->steps, t->flags, t->outputs, t->reserved);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const srt::ProbeGrid& g = ctx->probe_grid.grid;
+    const size_t np = srt::probe_grid_probes(g);
+    const bool count = (t->flags & SRT_PROBE_CLASSIFY_COUNT_WORK) != 0, relocate = (t->flags & SRT_PROBE_CLASSIFY_RELOCATE) != 0;
+    if (const int rc = probe_table_current(ctx)) return rc;
+    void* dst[srt::PROBE_STATE_SLOTS] = {nullptr, nullptr};
+    for (int i = 0; i < srt::PROBE_STATE_SLOTS; ++i)
+        if (t->outputs & (1u << i))
+            SRT_WRITE_TARGET_AFTER(ctx, ctx->probe_states_out[i], ctx->d_probe_states_own[i], srt::probe_state_bytes(np), dst[i], probe_states_output_released(ctx, i));
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_probe_classify_work, srt::PS_WORK_N)) return rc;
+    }
+    const srt::ProbeTable& T = ctx->probe_table;
+    const bool in_lds = T.vec4() <= (size_t)srt::PS_TABLE_LDS_VEC4;
+    const size_t lds_bytes = in_lds ? T.vec4() * sizeof(float4) : 0;
+    void (*const kernel)(srt::ProbeClassifyIO) = in_lds ? (count ? srt::probe_classify_kernel<true, true> : srt::probe_classify_kernel<true, false>)
+                                                        : (count ? srt::probe_classify_kernel<false, true> : srt::probe_classify_kernel<false, false>);
+    const unsigned wgs = srt::probe_classify_grid(np, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, lds_bytes));
+    srt::ProbeClassifyIO io{};
+    io.table = (const float4*)ctx->d_probe_table;
+    io.spheres = T.spheres, io.boxes = T.boxes;
+    if (relocate) {
+        io.direction = ctx->probes.directions.bound ? (const float4*)ctx->probes.directions.bound : (const float4*)ctx->d_probe_direction;
+        io.directions = (uint32_t)ctx->probes.directions.count();
+    }
+    io.probes = (uint32_t)np;
+    for (int a = 0; a < 3; ++a) io.origin[a] = g.origin[a], io.spacing[a] = g.spacing[a], io.counts[a] = g.counts[a];
+    io.clearance = t->clearance, io.max_offset = t->max_offset, io.steps = t->steps;
+    io.relocate = relocate ? 1u : 0u, io.normalize = (t->flags & SRT_PROBE_CLASSIFY_NORMALIZE) ? 1u : 0u, io.has_mesh = T.has_mesh ? 1u : 0u;
+    io.records = (float4*)dst[0];
+    io.positions = (float4*)dst[1];
+    io.work = count ? (unsigned long long*)ctx->d_probe_classify_work : nullptr;
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), lds_bytes, ctx->stream, io);
+    SRT_HIP(ctx, hipGetLastError());
+    srt::probe_states_classified(ctx->probe_states, np, call, dst);
+    return SRT_OK;
+}
+
+int srt_bind_probe_states_output(srt_context* ctx, uint32_t output, void* d_ptr) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    const int i = srt::probe_state_slot(output);
+    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_states_output: output 0x%x is not a single SRT_PROBE_STATE_RECORDS / _POSITIONS bit", output);
+    return ctx->probe_states_out[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued calls keep the buffer they were given, as srt_bind_ray_output)
+}
+
+int srt_read_probe_states_output(srt_context* ctx, uint32_t output, void* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    const srt::RaysStatus rs = srt::probe_states_check_read(ctx->probe_states, output, &src, &bytes);
+    if (rs == srt::RAYS_INVALID_ARG)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_probe_states_output: output 0x%x is not a single SRT_PROBE_STATE_RECORDS / _POSITIONS bit", output);
+    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, bytes, "srt_read_probe_states_output: output 0x%x was not written by the last srt_classify_probes", output);
+}
+
+int srt_get_probe_classify_work(srt_context* ctx, srt_probe_classify_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::probe_states_check_work(ctx->probe_states) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_classify_work: the last srt_classify_probes did not ask for SRT_PROBE_CLASSIFY_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::PS_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_probe_classify_work, w, srt::PS_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0;
+    out->probes = w[srt::PS_WORK_PROBES], out->inside = w[srt::PS_WORK_INSIDE], out->moved = w[srt::PS_WORK_MOVED], out->buried = w[srt::PS_WORK_BURIED];
+    out->idle = w[srt::PS_WORK_IDLE], out->candidates = w[srt::PS_WORK_CANDIDATES], out->waves = w[srt::PS_WORK_WAVES];
+    return SRT_OK;
+}
+
+// ---- probe-grid shading that obeys the probe states ---------------------------------------------------------------------
+int srt_write_probe_grid_states(srt_context* ctx, const float* records, size_t probes) {
+    if (!ctx || !records) return SRT_ERR_INVALID_ARG;
+    if (probes < 1 || probes > srt::PROBE_GRID_MAX_PROBES) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_write_probe_grid_states: %zu probes: want 1 .. 2^30", probes);
+    if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it may be re-allocated below)
+    const size_t bytes = probes * sizeof(float4);
+    if (ctx->d_probe_grid_states.bytes() < bytes) {
+        ctx->probe_states.states.own_count = 0;  // (a failed allocation leaves no own array)
+        SRT_HIP(ctx, ctx->d_probe_grid_states.ensure(bytes));
+    }
+    SRT_HIP(ctx, hipMemcpy(ctx->d_probe_grid_states, records, bytes, hipMemcpyHostToDevice));
+    srt::light_probe_written(ctx->probe_states.states, probes);
+    return SRT_OK;
+}
+
+int srt_bind_probe_grid_states(srt_context* ctx, const void* d_ptr, size_t probes) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    if (srt::light_probe_bind(ctx->probe_states.states, d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_grid_states: want a device array and 1 .. 2^30 probes, or NULL, 0 (got %zu)", probes);
+    return SRT_OK;
+}
+
+int srt_shade_probe_grid_states(srt_context* ctx, const srt_probe_grid_params* s, const srt_probe_grid_depth_params* d) {
+    if (!ctx || !s) return SRT_ERR_INVALID_ARG;
+    srt::ProbeGridCall call;
+    memcpy(&call, s, sizeof call);
+    srt::ProbeGridDepthCall dcall{};
+    if (d) memcpy(&dcall, d, sizeof dcall);
+    bool present[srt::PROBE_GRID_GUIDES];
+    for (int i = 0; i < srt::PROBE_GRID_GUIDES; ++i) present[i] = current(ctx->gbuf[i], ctx->d_gbuf_own[i]) != nullptr;
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_grid_states_check_shade(ctx->probe_grid, ctx->probe_grid_depth, ctx->probe_states, call, d ? &dcall : nullptr, ctx->scene_set,
+                                                                      ctx->height, present, &why))
+        return fail(ctx, (int)rs, "srt_shade_probe_grid_states: %s (rows [%d,%d) of %d, flags 0x%x, band_weight %g %g %g, reserved %u %u; depth %s, bias %g, min_variance %g)",
+                    why, s->row_begin, s->row_end, ctx->height, s->flags, (double)s->band_weight[0], (double)s->band_weight[1], (double)s->band_weight[2], s->reserved[0],
+                    s->reserved[1], d ? "given" : "NULL", (double)dcall.bias, (double)dcall.min_variance);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const bool count = (s->flags & SRT_PROBE_GRID_COUNT_WORK) != 0;
+    float4* dst = nullptr;
+    SRT_WRITE_TARGET(ctx, ctx->probe_grid_out, ctx->d_probe_grid_own, frame_pixels(ctx) * sizeof(float4), dst);
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_probe_grid_work, srt::PG_WORK_N)) return rc;
+    }
+    srt::KernelParams K;
+    KernelSetup ks = scene_kernel_params(ctx, s->row_begin, s->row_end, K);
+    ks.lds_bytes = 0;  // (the kernel traces nothing: no scene image, and its own LDS is static)
+    const srt::ProbeGrid& g = ctx->probe_grid.grid;
+    srt::ProbeGridStatesIO io{};
+    io.object = (const int32_t*)current(ctx->gbuf[0], ctx->d_gbuf_own[0]);
+    io.normal_depth = (const float4*)current(ctx->gbuf[1], ctx->d_gbuf_own[1]);
+    io.position = (const float4*)current(ctx->gbuf[2], ctx->d_gbuf_own[2]);
+    io.albedo = (s->flags & SRT_PROBE_GRID_ALBEDO) ? (const float4*)current(ctx->gbuf[3], ctx->d_gbuf_own[3]) : nullptr;
+    io.coefficients = ctx->probe_grid.coefficients.bound ? (const float4*)ctx->probe_grid.coefficients.bound : (const float4*)ctx->d_probe_grid_coefficients;
+    io.states = ctx->probe_states.states.bound ? (const float4*)ctx->probe_states.states.bound : (const float4*)ctx->d_probe_grid_states;
+    io.out = dst;
+    for (int a = 0; a < 3; ++a) io.origin[a] = g.origin[a], io.spacing[a] = g.spacing[a], io.counts[a] = g.counts[a], io.band_weight[a] = s->band_weight[a];
+    io.normal_weight = (s->flags & SRT_PROBE_GRID_NORMAL_WEIGHT) ? 1u : 0u;
+    if (d) {
+        io.depth = ctx->probe_grid_depth.moments.bound ? (const float4*)ctx->probe_grid_depth.moments.bound : (const float4*)ctx->d_probe_grid_depth;
+        io.resolution = ctx->probe_grid_depth.resolution();
+        io.bias = d->bias, io.min_variance = d->min_variance;
+    }
+    io.work = count ? (unsigned long long*)ctx->d_probe_grid_work : nullptr;
+    const auto kernel = d ? (count ? srt::probe_grid_states_kernel<true, true> : srt::probe_grid_states_kernel<true, false>)
+                          : (count ? srt::probe_grid_states_kernel<false, true> : srt::probe_grid_states_kernel<false, false>);
+    if (const int rc = launch_tiles(ctx, kernel, ks, K, io)) return rc;
     ctx->probe_grid_out.wrote(dst);
     srt::probe_grid_shaded(ctx->probe_grid, s->flags);
     return SRT_OK;

@@ -15,6 +15,8 @@ from .capi import (PROBE_GRID_ALBEDO, PROBE_GRID_BAND_WEIGHT_IRRADIANCE, PROBE_G
                    ProbeGrid, ProbeGridParams, ProbeGridWork, probe_grid, probe_grid_positions)  # noqa: F401
 from .capi import (PROBE_DEPTH_COUNT_WORK, PROBE_DEPTH_DISTANCES, PROBE_DEPTH_MOMENTS, PROBE_DEPTH_NORMALIZE, ProbeDepthParams, ProbeDepthWork,
                    ProbeGridDepthParams, probe_depth_texels)  # noqa: F401
+from .capi import (PROBE_CLASSIFY_COUNT_WORK, PROBE_CLASSIFY_NORMALIZE, PROBE_CLASSIFY_RELOCATE, PROBE_STATE_POSITIONS, PROBE_STATE_RECORDS,
+                   ProbeClassifyParams, ProbeClassifyWork)  # noqa: F401
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_PKG, "libsrt_host.so")
@@ -49,6 +51,8 @@ EXPORTS = [
     "srt_host_renderer_probe_grid_work",
     "srt_host_renderer_trace_probe_depth", "srt_host_renderer_read_probe_depth_output", "srt_host_renderer_probe_depth_work",
     "srt_host_renderer_shade_probe_grid_depth",
+    "srt_host_renderer_classify_probes", "srt_host_renderer_read_probe_states_output", "srt_host_renderer_probe_classify_work",
+    "srt_host_renderer_shade_probe_grid_states",
     "srt_host_renderer_sample_budget", "srt_host_renderer_render_adaptive", "srt_host_renderer_set_sample_counts",
     "srt_host_renderer_read_sample_counts", "srt_host_renderer_adaptive_frame",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
@@ -155,6 +159,11 @@ def load_library():
     L.srt_host_renderer_probe_depth_work.argtypes = [vp, C.POINTER(ProbeDepthWork)]
     L.srt_host_renderer_shade_probe_grid_depth.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_uint32, C.POINTER(ProbeGridParams),
                                                            C.POINTER(ProbeGridDepthParams)]
+    L.srt_host_renderer_classify_probes.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(ProbeClassifyParams)]
+    L.srt_host_renderer_read_probe_states_output.argtypes = [vp, C.c_uint32, C.c_void_p]
+    L.srt_host_renderer_probe_classify_work.argtypes = [vp, C.POINTER(ProbeClassifyWork)]
+    L.srt_host_renderer_shade_probe_grid_states.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_uint32,
+                                                            C.POINTER(ProbeGridParams), C.POINTER(ProbeGridDepthParams)]
     L.srt_host_renderer_sample_budget.argtypes = [vp, C.POINTER(BudgetParams), C.POINTER(C.c_uint64)]
     L.srt_host_renderer_render_adaptive.argtypes = [vp, C.POINTER(AdaptiveParams)]
     L.srt_host_renderer_set_sample_counts.argtypes = [vp, C.c_uint32]
@@ -574,6 +583,70 @@ class Renderer:
                             (PROBE_GRID_COUNT_WORK if count_work else 0), (C.c_float * 3)(float(bw[0]), float(bw[1]), float(bw[2])), (C.c_uint32 * 2)(0, 0))
         d = ProbeGridDepthParams(float(bias), float(min_variance), (C.c_uint32 * 2)(0, 0))
         self._ck(self.L.srt_host_renderer_shade_probe_grid_depth(self._h, cptr, mptr, n, res, C.byref(p), C.byref(d)))
+        return self.probe_grid_output()
+
+    def classify_probes(self, probes, directions=None, relocate=False, clearance=0.2, max_offset=0.45, steps=8, normalize=False, count_work=False,
+                        positions=False):
+        """PathTraceRenderer::classifyProbes + readProbeStatesOutput: classify the `probes` = nx*ny*nz probes of the grid of
+        set_probe_grid() against the renderer's scene (directions: a host array (K, 4) float32 or an int K for light_probe_sphere(K);
+        only a relocating call needs them) and return the (P, 4) float32 records, or (records, positions) with positions=True.
+        probe_states_work() reads the counts.  Waits."""
+        f = C.POINTER(C.c_float)
+        dptr, k = None, 0
+        if directions is not None:
+            if isinstance(directions, (int, np.integer)):
+                directions = light_probe_sphere(int(directions))
+            d = np.ascontiguousarray(directions, dtype=np.float32)
+            if d.ndim != 2 or d.shape[1] != 4 or d.shape[0] < 1:
+                raise ValueError("classify_probes: directions %s, want a (K, 4) array" % (d.shape,))
+            dptr, k = d.ctypes.data_as(f), d.shape[0]
+        p = ProbeClassifyParams(float(clearance), float(max_offset), int(steps),
+                                (PROBE_CLASSIFY_RELOCATE if relocate else 0) | (PROBE_CLASSIFY_NORMALIZE if normalize else 0) |
+                                (PROBE_CLASSIFY_COUNT_WORK if count_work else 0), PROBE_STATE_RECORDS | (PROBE_STATE_POSITIONS if positions else 0), 0)
+        self._ck(self.L.srt_host_renderer_classify_probes(self._h, dptr, k, C.byref(p)))
+        rec = np.empty((int(probes), 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_probe_states_output(self._h, PROBE_STATE_RECORDS, rec.ctypes.data_as(C.c_void_p)))
+        if not positions:
+            return rec
+        pos = np.empty((int(probes), 4), dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_probe_states_output(self._h, PROBE_STATE_POSITIONS, pos.ctypes.data_as(C.c_void_p)))
+        return rec, pos
+
+    def probe_states_work(self):
+        """PathTraceRenderer::probeClassifyWork: the work counts of the last classify_probes(count_work=True) as a dict."""
+        w = ProbeClassifyWork()
+        self._ck(self.L.srt_host_renderer_probe_classify_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def shade_probe_grid_states(self, coefficients=None, states=None, moments=None, depth=False, bias=0.0, min_variance=1e-4, normal_weight=False,
+                                albedo=False, band_weight=None, rows=None, count_work=False):
+        """PathTraceRenderer::shadeProbeGridStates + readProbeGridOutput: shade_probe_grid() (depth=False) or shade_probe_grid_depth()
+        (depth=True or `moments` given) that obeys the (P, 4) float32 `states` records (None: the handle's current ones).  Returns
+        the (H, W, 4) float32 result; probe_grid_work() reads the counts.  Waits."""
+        f = C.POINTER(C.c_float)
+        cptr, mptr, sptr, n, res = None, None, None, 0, 0
+        if coefficients is not None:
+            c = np.ascontiguousarray(coefficients, dtype=np.float32).reshape(-1, 4)
+            if c.shape[0] < LIGHT_PROBE_COEFFS or c.shape[0] % LIGHT_PROBE_COEFFS:
+                raise ValueError("shade_probe_grid_states: %d float4 of coefficients, want nine per probe" % c.shape[0])
+            cptr, n = c.ctypes.data_as(f), c.shape[0] // LIGHT_PROBE_COEFFS
+        if moments is not None:
+            m = np.ascontiguousarray(moments, dtype=np.float32)
+            if m.ndim != 3 or m.shape[2] != 4 or m.shape[0] < 1 or (n and m.shape[0] != n):
+                raise ValueError("shade_probe_grid_states: moments %s, want (P, R*R, 4)" % (m.shape,))
+            res = int(round(m.shape[1] ** 0.5))
+            mptr, n, depth = m.ctypes.data_as(f), m.shape[0], True
+        if states is not None:
+            st = np.ascontiguousarray(states, dtype=np.float32)
+            if st.ndim != 2 or st.shape[1] != 4 or st.shape[0] < 1 or (n and st.shape[0] != n):
+                raise ValueError("shade_probe_grid_states: states %s, want (P, 4)" % (st.shape,))
+            sptr, n = st.ctypes.data_as(f), st.shape[0]
+        rb, re = (int(rows[0]), int(rows[1])) if rows is not None else (0, 0)
+        bw = band_weight if band_weight is not None else PROBE_GRID_BAND_WEIGHT_IRRADIANCE
+        p = ProbeGridParams(rb, re, (PROBE_GRID_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_GRID_ALBEDO if albedo else 0) |
+                            (PROBE_GRID_COUNT_WORK if count_work else 0), (C.c_float * 3)(float(bw[0]), float(bw[1]), float(bw[2])), (C.c_uint32 * 2)(0, 0))
+        d = ProbeGridDepthParams(float(bias), float(min_variance), (C.c_uint32 * 2)(0, 0))
+        self._ck(self.L.srt_host_renderer_shade_probe_grid_states(self._h, cptr, mptr, sptr, n, res, C.byref(p), C.byref(d) if depth else None))
         return self.probe_grid_output()
 
     def radiance_work(self):

@@ -254,6 +254,18 @@ int srt_host_renderer_shade_probe_grid_depth(srt_host_renderer* h, const float* 
                                              const srt_probe_grid_params* p, const srt_probe_grid_depth_params* d) {
     SRT_HOST_TRY(h, h->r->shadeProbeGridDepth(coefficients, moments, probes, resolution, *p, *d))
 }
+// probe classification on the renderer's grid and scene, and the probe-grid shading that obeys the records
+// (PathTraceRenderer::classifyProbes / shadeProbeGridStates: directions, coefficients, moments and states are copied unless NULL;
+// depth may be NULL: no filtered test)
+int srt_host_renderer_classify_probes(srt_host_renderer* h, const float* directions, size_t direction_count, const srt_probe_classify_params* p) {
+    SRT_HOST_TRY(h, h->r->classifyProbes(directions, direction_count, *p))
+}
+int srt_host_renderer_read_probe_states_output(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->readProbeStatesOutput(output, dst)) }
+int srt_host_renderer_probe_classify_work(srt_host_renderer* h, srt_probe_classify_work* out) { SRT_HOST_TRY(h, *out = h->r->probeClassifyWork()) }
+int srt_host_renderer_shade_probe_grid_states(srt_host_renderer* h, const float* coefficients, const float* moments, const float* states, size_t probes,
+                                              uint32_t resolution, const srt_probe_grid_params* p, const srt_probe_grid_depth_params* d) {
+    SRT_HOST_TRY(h, h->r->shadeProbeGridStates(coefficients, moments, states, probes, resolution, *p, d))
+}
 // adaptive sampling on the handle's buffers as they stand (srt_sample_budget + srt_get_budget_total, srt_render_adaptive; a band
 // of [0, 0) means the renderer's own), and the two-half workflow (PathTraceRenderer::renderAdaptiveFrame; counts may be NULL)
 int srt_host_renderer_sample_budget(srt_host_renderer* h, const srt_budget_params* p, uint64_t* total) { SRT_HOST_TRY(h, *total = h->r->sampleBudget(*p)) }

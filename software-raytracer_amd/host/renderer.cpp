@@ -373,6 +373,34 @@ void PathTraceRenderer::shadeProbeGridDepth(const float* coefficients, const flo
     check(srt_shade_probe_grid_depth(ctx_, &s, &depth), "srt_shade_probe_grid_depth");
 }
 
+void PathTraceRenderer::classifyProbes(const float* directions, size_t direction_count, const srt_probe_classify_params& params) {
+    if (directions) check(srt_write_light_probe_directions(ctx_, directions, direction_count), "srt_write_light_probe_directions");
+    check(srt_classify_probes(ctx_, &params), "srt_classify_probes");
+}
+
+void PathTraceRenderer::readProbeStatesOutput(uint32_t output, void* dst) {
+    check(srt_read_probe_states_output(ctx_, output, dst), "srt_read_probe_states_output");
+}
+
+srt_probe_classify_work PathTraceRenderer::probeClassifyWork() {
+    srt_probe_classify_work w{};
+    check(srt_get_probe_classify_work(ctx_, &w), "srt_get_probe_classify_work");
+    return w;
+}
+
+void PathTraceRenderer::shadeProbeGridStates(const float* coefficients, const float* moments, const float* states, size_t probes, uint32_t resolution,
+                                             const srt_probe_grid_params& params, const srt_probe_grid_depth_params* depth) {
+    srt_probe_grid_params s = params;
+    if (s.row_begin == 0 && s.row_end == 0) s.row_begin = row_begin_, s.row_end = row_end_;
+    if (coefficients) check(srt_write_probe_grid_coefficients(ctx_, coefficients, probes), "srt_write_probe_grid_coefficients");
+    if (moments) check(srt_write_probe_grid_depth(ctx_, moments, probes, resolution), "srt_write_probe_grid_depth");
+    if (states) check(srt_write_probe_grid_states(ctx_, states, probes), "srt_write_probe_grid_states");
+    FirstHitScope first_hits(*this);  // irradiance AT the first hit
+    RenderGBufferRows(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION | ((s.flags & SRT_PROBE_GRID_ALBEDO) ? SRT_GBUF_ALBEDO : 0u), s.row_begin,
+                      s.row_end);  // (pushes the camera)
+    check(srt_shade_probe_grid_states(ctx_, &s, depth), "srt_shade_probe_grid_states");
+}
+
 uint64_t PathTraceRenderer::sampleBudget(const srt_budget_params& params) {
     check(srt_sample_budget(ctx_, &params), "srt_sample_budget");
     uint64_t total = 0;

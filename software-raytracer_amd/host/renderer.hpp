@@ -196,6 +196,17 @@ class PathTraceRenderer {
     srt_probe_depth_work probeDepthWork();
     void shadeProbeGridDepth(const float* coefficients, const float* moments, size_t probes, uint32_t resolution, const srt_probe_grid_params& params,
                              const srt_probe_grid_depth_params& depth);
+    // Probe classification and relocation (srt_classify_probes) on the grid of setProbeGrid, and the shading that obeys the records
+    // (srt_shade_probe_grid_states).  classifyProbes copies `direction_count` directions (NULL: the handle's current ones; only a
+    // relocating call reads them) and enqueues the pass; readProbeStatesOutput waits and copies one output of the last call
+    // (SRT_PROBE_STATE_RECORDS or SRT_PROBE_STATE_POSITIONS: nx*ny*nz float4); probeClassifyWork waits and returns the counts of a
+    // call that had SRT_PROBE_CLASSIFY_COUNT_WORK.  shadeProbeGridStates is shadeProbeGrid (depth == NULL) or shadeProbeGridDepth
+    // with the records: it also copies `probes` float4 states (NULL: the handle's current ones).
+    void classifyProbes(const float* directions, size_t direction_count, const srt_probe_classify_params& params);
+    void readProbeStatesOutput(uint32_t output, void* dst);
+    srt_probe_classify_work probeClassifyWork();
+    void shadeProbeGridStates(const float* coefficients, const float* moments, const float* states, size_t probes, uint32_t resolution,
+                              const srt_probe_grid_params& params, const srt_probe_grid_depth_params* depth);
     // Adaptive sampling (srt_sample_budget, srt_render_adaptive), on the handle's buffers as they stand.  sampleBudget turns the
     // variance buffer, the sample counts, the accumulator and the guides into the per-pixel budget and returns its sum (waits).
     // renderAdaptive enqueues the adaptive render with the renderer's scene and camera; a band of [0, 0) means the renderer's

@@ -275,9 +275,19 @@ struct ProbeDepthOptions {
     float max_distance = 10000.0f, bias = 0.0f;
     std::string out;
 };
+// --probe-classify: srt_classify_probes on the grid first (--probe-relocate: with relocation along the same directions;
+// --probe-clearance, --probe-max-offset, --probe-steps), the probes and depth maps traced at the positions it gives, and
+// srt_shade_probe_grid_states in place of the shading call; --states-out receives the probes' records (float4 each).
+struct ProbeClassifyOptions {
+    bool on = false, relocate = false;
+    float clearance = 0.2f, max_offset = 0.45f;
+    int steps = 8;
+    std::string out;
+};
 
 static int shade_probe_grid_file(const Scene& scene, int device, int W, int H, int fov, const srt_probe_grid& grid, int directions, int samples, int bounces,
-                                 unsigned seed, uint32_t flags, bool hemisphere, const std::string& out, const ProbeDepthOptions& depth) {
+                                 unsigned seed, uint32_t flags, bool hemisphere, const std::string& out, const ProbeDepthOptions& depth,
+                                 const ProbeClassifyOptions& classify) {
     const size_t np = (size_t)grid.counts[0] * (size_t)grid.counts[1] * (size_t)grid.counts[2];
     std::vector<float> pos(4 * np), dir(4 * (size_t)directions);
     if (srt_probe_grid_positions(&grid, pos.data()) != SRT_OK) {
@@ -294,6 +304,20 @@ static int shade_probe_grid_file(const Scene& scene, int device, int W, int H, i
         srt_light_probe_params lp{};
         srt_light_probe_params_default(&lp);
         lp.sample_count = (uint32_t)samples, lp.max_bounces = bounces, lp.seed = seed;
+        std::vector<float> states;
+        if (classify.on) {  // the states first: the probes are traced where the classification puts them
+            srt_probe_classify_params cp{};
+            srt_probe_classify_params_default(&cp);
+            cp.clearance = classify.clearance, cp.max_offset = classify.max_offset, cp.steps = (uint32_t)classify.steps;
+            cp.flags = classify.relocate ? SRT_PROBE_CLASSIFY_RELOCATE : 0u;
+            cp.outputs = SRT_PROBE_STATE_RECORDS | SRT_PROBE_STATE_POSITIONS;
+            r.setProbeGrid(grid);
+            r.classifyProbes(dir.data(), (size_t)directions, cp);
+            states.resize(4 * np);
+            r.readProbeStatesOutput(SRT_PROBE_STATE_RECORDS, states.data());
+            r.readProbeStatesOutput(SRT_PROBE_STATE_POSITIONS, pos.data());
+            if (!classify.out.empty() && !write_floats(classify.out, states)) return 1;
+        }
         r.traceLightProbes(pos.data(), np, dir.data(), (size_t)directions, lp);
         std::vector<float> coeff(np * 9 * 4);
         r.readLightProbeOutput(SRT_LIGHT_PROBE_COEFFICIENTS, coeff.data());
@@ -313,7 +337,10 @@ static int shade_probe_grid_file(const Scene& scene, int device, int W, int H, i
             srt_probe_grid_depth_params gd{};
             srt_probe_grid_depth_params_default(&gd);
             gd.bias = depth.bias;
-            r.shadeProbeGridDepth(coeff.data(), moments.data(), np, (uint32_t)depth.resolution, sp, gd);
+            if (classify.on) r.shadeProbeGridStates(coeff.data(), moments.data(), states.data(), np, (uint32_t)depth.resolution, sp, &gd);
+            else r.shadeProbeGridDepth(coeff.data(), moments.data(), np, (uint32_t)depth.resolution, sp, gd);
+        } else if (classify.on) {
+            r.shadeProbeGridStates(coeff.data(), nullptr, states.data(), np, 0, sp, nullptr);
         } else {
             r.shadeProbeGrid(coeff.data(), np, sp);
         }
@@ -345,6 +372,7 @@ static void usage() {
                  "       srt_render --scene FILE --probe-grid OX,OY,OZ,SX,SY,SZ,NX,NY,NZ --probe-directions K [--radiance N] --irradiance-out FILE\n"
                  "                  [--probe-visibility] [--probe-normal-weight] [--probe-albedo] [--probe-hemisphere] [--width W] [--height H] ...\n"
                  "                  [--probe-depth R [--probe-depth-sharpness S] [--probe-depth-max D] [--probe-depth-bias B] [--probe-depth-out FILE]]\n"
+                 "                  [--probe-classify [--probe-relocate] [--probe-clearance C] [--probe-max-offset F] [--probe-steps M] [--states-out FILE]]\n"
                  "       srt_render --scene FILE --adaptive ROUNDS [--adaptive-threshold T] [--adaptive-max M] [--counts-out FILE] [--spp N] ...\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
@@ -406,6 +434,11 @@ static void usage() {
                  "             octahedral depth map of R x R texels (4, 8 or 16) per probe from the same directions; --probe-depth-sharpness S\n"
                  "             (0..6, default 5); --probe-depth-max D: distance clamp (> 0, default 10000); --probe-depth-bias B (>= 0, default 0);\n"
                  "             --probe-depth-out receives the probes' R*R float4 moments; not with --probe-visibility\n"
+                 "  --probe-classify: with --probe-grid, srt_classify_probes first: probes inside a sphere or a box are skipped by the shading\n"
+                 "             (srt_shade_probe_grid_states); --probe-relocate: probes inside or nearer than --probe-clearance C (0..0.5 of the\n"
+                 "             spacing, default 0.2) to a surface are moved by at most --probe-max-offset F (0..0.5, default 0.45) in\n"
+                 "             --probe-steps M (1..64, default 8) lengths, and probes and depth maps are traced where they stand;\n"
+                 "             --states-out receives the probes' records (offset, state bits); not with --probe-visibility\n"
                  "  --adaptive ROUNDS: adaptive sampling in place of the uniform frame: an even --spp is the uniform seed, split into two\n"
                  "             independently seeded halves; then ROUNDS (1..64) rounds of srt_variance, srt_sample_budget and srt_render_adaptive\n"
                  "             on both halves, and the mean of the halves goes to --out; the frame's total samples are printed on stderr;\n"
@@ -438,6 +471,8 @@ int main(int argc, char** argv) {
     bool probe_visibility = false, probe_normal_weight = false, probe_albedo = false, probe_hemisphere = false;
     ProbeDepthOptions probe_depth;
     bool probe_depth_given = false, probe_depth_option = false;
+    ProbeClassifyOptions probe_classify;
+    bool probe_classify_option = false;
     int adaptive = 0, adaptive_max = 0;
     bool adaptive_given = false, adaptive_threshold_given = false, adaptive_max_given = false;
     float adaptive_threshold = 0;
@@ -518,6 +553,12 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--probe-depth-max")) probe_depth.max_distance = std::strtof(need("--probe-depth-max"), nullptr), probe_depth_option = true;
         else if (!std::strcmp(argv[i], "--probe-depth-bias")) probe_depth.bias = std::strtof(need("--probe-depth-bias"), nullptr), probe_depth_option = true;
         else if (!std::strcmp(argv[i], "--probe-depth-out")) probe_depth.out = need("--probe-depth-out"), probe_depth_option = true;
+        else if (!std::strcmp(argv[i], "--probe-classify")) probe_classify.on = true;
+        else if (!std::strcmp(argv[i], "--probe-relocate")) probe_classify.relocate = true, probe_classify_option = true;
+        else if (!std::strcmp(argv[i], "--probe-clearance")) probe_classify.clearance = std::strtof(need("--probe-clearance"), nullptr), probe_classify_option = true;
+        else if (!std::strcmp(argv[i], "--probe-max-offset")) probe_classify.max_offset = std::strtof(need("--probe-max-offset"), nullptr), probe_classify_option = true;
+        else if (!std::strcmp(argv[i], "--probe-steps")) probe_classify.steps = std::atoi(need("--probe-steps")), probe_classify_option = true;
+        else if (!std::strcmp(argv[i], "--states-out")) probe_classify.out = need("--states-out"), probe_classify_option = true;
         else if (!std::strcmp(argv[i], "--adaptive")) adaptive = std::atoi(need("--adaptive")), adaptive_given = true;
         else if (!std::strcmp(argv[i], "--adaptive-threshold")) adaptive_threshold = std::strtof(need("--adaptive-threshold"), nullptr), adaptive_threshold_given = true;
         else if (!std::strcmp(argv[i], "--adaptive-max")) adaptive_max = std::atoi(need("--adaptive-max")), adaptive_max_given = true;
@@ -599,6 +640,22 @@ int main(int argc, char** argv) {
             !(probe_depth.max_distance > 0.0f) || !std::isfinite(probe_depth.max_distance) || !(probe_depth.bias >= 0.0f) || !std::isfinite(probe_depth.bias)) {
             std::fprintf(stderr, "--probe-depth takes 4, 8 or 16, --probe-depth-sharpness 0..6, --probe-depth-max a finite distance > 0 and --probe-depth-bias a finite "
                                  "value >= 0\n");
+            return 2;
+        }
+    }
+    if (probe_classify.on || probe_classify_option) {
+        if (probe_grid_arg.empty() || !probe_classify.on) {
+            std::fprintf(stderr, "--probe-classify and its options go with --probe-grid: --probe-grid G --probe-classify [--probe-relocate] [--probe-clearance C] "
+                                 "[--probe-max-offset F] [--probe-steps M] [--states-out FILE]\n");
+            return 2;
+        }
+        if (probe_visibility) {
+            std::fprintf(stderr, "--probe-classify and --probe-visibility exclude each other: the exact test towards relocated probes is not available\n");
+            return 2;
+        }
+        if (!(probe_classify.clearance > 0.0f) || !(probe_classify.clearance <= 0.5f) || !(probe_classify.max_offset > 0.0f) || !(probe_classify.max_offset <= 0.5f) ||
+            probe_classify.steps < 1 || probe_classify.steps > 64) {
+            std::fprintf(stderr, "--probe-classify: --probe-clearance and --probe-max-offset take a value in (0, 0.5], --probe-steps 1..64\n");
             return 2;
         }
     }
@@ -743,7 +800,7 @@ int main(int argc, char** argv) {
         return shade_probe_grid_file(scene, device, W, H, fov, probe_grid, probe_grid_directions, radiance_given ? radiance : 16, bounces, seed,
                                      (probe_visibility ? SRT_PROBE_GRID_VISIBILITY : 0u) | (probe_normal_weight ? SRT_PROBE_GRID_NORMAL_WEIGHT : 0u) |
                                          (probe_albedo ? SRT_PROBE_GRID_ALBEDO : 0u),
-                                     probe_hemisphere, irradiance_out, probe_depth);
+                                     probe_hemisphere, irradiance_out, probe_depth, probe_classify);
     if (!probes_in.empty()) return trace_probe_file(scene, device, probes_in, probe_directions, probes_out, probe_radiance_out, radiance_given ? radiance : 16, bounces, seed);
     if (!rays_in.empty()) return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize, rays_any_hit, radiance_given ? radiance : 0, bounces, seed);
     auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {
