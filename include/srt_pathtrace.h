@@ -1637,6 +1637,135 @@ int srt_get_probe_grid_work(srt_context* ctx, srt_probe_grid_work* out);
  * reference's interface. */
 int srt_selftest_arith(int device, uint32_t seed, uint64_t vectors, uint64_t* mismatches);
 
+/* ---- per-frame probe updates: active-probe lists, listed traces and a hysteresis blend (ABI 7, backward compatible) ---------------
+ * These calls were added without changing anything else, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of them
+ * runs what it ran before, bit for bit.  They keep a classified probe grid alive from frame to frame: srt_list_probes compacts the
+ * probes worth tracing, the two listed traces trace only those, and srt_blend_probes folds a few new samples per frame into a
+ * persistent history (DDGI's exponential blend).  Every buffer stays on the device, and no call waits for a count: the number of
+ * listed probes is read by the kernels from the list's header; the host never learns it.  All arithmetic is binary32 without
+ * contraction.
+ *
+ * The list.  SRT_PROBE_LIST is 4 + P uint32: word 0 the count n, word 1 P, words 2 and 3 zero, words 4 .. 4+n-1 the indices p
+ * with (state & skip_mask) == 0 in ascending order, words 4+n .. 4+P-1 0xFFFFFFFF.  srt_list_probes reads the P records that are
+ * current for srt_shade_probe_grid_states (srt_write_probe_grid_states, srt_bind_probe_grid_states; 1 <= P <= 2^30; with a grid
+ * set, P must be nx*ny*nz) and writes the list into the handle's own buffer or the DEVICE buffer of srt_bind_probe_list_output
+ * (NULL = own), under srt_bind_probe_states_output's rules; srt_read_probe_list_output waits and copies the 4 + P words the last
+ * srt_list_probes wrote, from the buffer it wrote, SRT_ERR_STATE when there has been none.  skip_mask: any subset of
+ * SRT_PROBE_MOVED | _BURIED | _INSIDE | _IDLE; the default is SRT_PROBE_BURIED | SRT_PROBE_IDLE.  The compaction is deterministic:
+ * one workgroup walks the records in chunks with a running base (wave ballots, LDS for the wave counts); no atomic reaches the
+ * output, and repeated calls give the same bits.  With SRT_PROBE_LIST_COUNT_WORK the launch counts its probes (P), the listed
+ * ones (n) and its waves; srt_get_probe_list_work waits and copies that record, SRT_ERR_STATE unless the last call had the flag.
+ * Errors, all found before anything is touched, in this order: SRT_ERR_STATE before srt_set_scene; SRT_ERR_INVALID_ARG for
+ * unknown flags, a skip_mask outside the four bits or a non-zero reserved; SRT_ERR_STATE for no states or a count other than the
+ * grid's; SRT_ERR_OOM when a buffer cannot be had.
+ *
+ * The listed traces.  srt_bind_probe_list(ctx, d_list, capacity) binds a DEVICE buffer in SRT_PROBE_LIST's layout for tracing; it
+ * does not copy and does not wait (what srt_bind_probe_list_output filled can be bound); NULL, 0 unbinds.  srt_write_probe_list
+ * copies `capacity` words from the host into the handle's own array and waits.  capacity = 4 + P', 1 <= P' <= 2^30, otherwise
+ * SRT_ERR_INVALID_ARG.  srt_trace_light_probes_listed and srt_trace_probe_depth_listed take their parents' parameter structs,
+ * output slots, "last trace" records and work records, and make the parents' checks first; then SRT_ERR_STATE for no list or a
+ * capacity other than 4 + P for the current positions' P.
+ * L. Let q run over 0 .. n-1 and p = list[4 + q].  The listed call writes, for each listed p, exactly the bits the unlisted call
+ *    writes there: coefficients [p][0..8], RADIANCE elements p*K + k, moments [p][0..R*R), distances p*K + k; the stream id of ray
+ *    (p, k) stays id_base + p*K + k.  Elements of probes not listed are neither read nor written.  The continuation rule (no
+ *    SRT_LIGHT_PROBE_RESET) holds per slot and is checked on the host as for the parent.  The launch is sized for P (grid, sample
+ *    scratch, partial buffer); the kernel reads n (clamped to P) from the header.  A word list[4 + q] >= P skips that unit, so a
+ *    bad list cannot cause an out-of-range store.  The order of the indices is irrelevant to the bits of a slot.  The indices
+ *    must be DISTINCT (srt_list_probes' are): with an index listed twice two waves would update the same RADIANCE elements of a
+ *    continuing trace, or the same history slot of a listed blend, in no defined order; nothing checks it.  Work counts:
+ *    `probes` counts the listed probes, and the other counters follow.
+ *
+ * The blend.  The histories: coefficients [P][9] float4 (SRT_PROBE_HISTORY_COEFFICIENTS) and, optionally, moments [P][R*R] float4
+ * (SRT_PROBE_HISTORY_MOMENTS), each the handle's own buffer or the DEVICE buffer of srt_bind_probe_history (one bit; NULL = own;
+ * no copy, no wait).  srt_reset_probe_history(ctx, which, probes, resolution) gives the histories of the set `which` their size
+ * (P, and R for the moments: 4, 8 or 16, P*R*R <= 2^30; ignored without the moments) and zero-fills them, enqueued on the stream;
+ * srt_read_probe_history waits and copies one; SRT_ERR_STATE before the first reset.  The new data N are the buffers the last
+ * srt_trace_light_probes[_listed] wrote COEFFICIENTS to and (SRT_PROBE_BLEND_MOMENTS) the last srt_trace_probe_depth[_listed]
+ * wrote MOMENTS to; if that call did not write the output, or wrote it for another P (or R) than the history's, SRT_ERR_STATE.
+ * The history H is updated in place; afterwards it is what srt_bind_probe_grid_coefficients / srt_bind_probe_grid_depth take.
+ * U1. Which probes.  With SRT_PROBE_BLEND_LISTED, p = list[4 + q] for q < n of the list bound for tracing (capacity 4 + P; a word
+ *    >= P is skipped); without it, p = 0 .. P-1.  Every other probe's history keeps its bits.
+ * U2. Restart.  A probe restarts when the bits of H[p][0].w are 0 (the buffer was reset or never filled; a traced probe has the
+ *    sum of 0.282095 * w_k > 0 there), or when SRT_PROBE_BLEND_PREVIOUS_STATES is set and, between the current record (the slot of
+ *    srt_write_probe_grid_states / srt_bind_probe_grid_states) and the previous one (srt_write_probe_previous_states /
+ *    srt_bind_probe_previous_states, the same rules), any offset lane differs bitwise or (state ^ previous) & (BURIED | IDLE) is
+ *    not 0.  A restarting probe gets H = N, bits copied, for the coefficients and (with _MOMENTS) the moments.
+ * U3. Change.  Y(v) = (0.2126f*v.x + 0.7152f*v.y) + 0.0722f*v.z (Rec. 709; no other header of the project fixes luminance
+ *    weights).  yh = Y(H[p][0]), yn = Y(N[p][0]); d = fabsf(yn - yh); m = fabsf(yh) > fabsf(yn) ? fabsf(yh) : fabsf(yn);
+ *    changed = d > change_threshold * m; h = changed ? fast_hysteresis : hysteresis.
+ * U4. Blend.  For every coefficient and lane, H = N + ((H - N) * h).
+ * U5. Moments.  With _MOMENTS the same expression with depth_hysteresis, all four lanes of every texel.
+ * U6. Determinism.  No atomics reach an output; one wave per probe, the decision is wave-uniform.
+ * U7. Work counts.  With SRT_PROBE_BLEND_COUNT_WORK: the probes blended, those that restarted, those that did not restart and
+ *    changed, and the waves of the launch.  One vector atomic per wave at the end; without the flag no atomics at all.
+ *    srt_get_probe_blend_work waits and copies the record; SRT_ERR_STATE unless the last srt_blend_probes had the flag.
+ * U8. Parameters.  hysteresis, fast_hysteresis, depth_hysteresis: each in [0, 1); change_threshold: finite, >= 0.  The defaults
+ *    (0.9, 0.5, 0.9, 0.25) are picks, DDGI's customary values, not measurements.
+ * U9. Errors, all found before anything is touched, in this order: SRT_ERR_STATE before srt_set_scene; SRT_ERR_INVALID_ARG for
+ *    unknown flags, a parameter outside its range (a NaN included) or a non-zero reserved; SRT_ERR_STATE for a history that was
+ *    never reset, new data that are missing or of another size, (with _LISTED) no list or another capacity, (with
+ *    _PREVIOUS_STATES) missing records or another count.  Asynchrony: as rule 8 of the light-probe block. */
+#define SRT_PROBE_LIST_COUNT_WORK 1u           /* srt_probe_list_params.flags: fill srt_probe_list_work for this call */
+#define SRT_PROBE_LIST_HEADER 4u               /* words in front of the indices */
+#define SRT_PROBE_HISTORY_COEFFICIENTS 1u      /* history: [P][9] float4 */
+#define SRT_PROBE_HISTORY_MOMENTS 2u           /* history: [P][R*R] float4 */
+#define SRT_PROBE_BLEND_MOMENTS 1u             /* srt_probe_blend_params.flags: rule U5 */
+#define SRT_PROBE_BLEND_LISTED 2u              /* only the probes of the bound list (rule U1) */
+#define SRT_PROBE_BLEND_PREVIOUS_STATES 4u     /* restart where a record changed (rule U2) */
+#define SRT_PROBE_BLEND_COUNT_WORK 8u          /* fill srt_probe_blend_work for this call */
+
+typedef struct srt_probe_list_params { /* 16 bytes */
+    uint32_t skip_mask;                /* state bits that exclude a probe */
+    uint32_t flags;                    /* SRT_PROBE_LIST_COUNT_WORK */
+    uint32_t reserved[2];              /* 0 */
+} srt_probe_list_params;
+
+typedef struct srt_probe_list_work { /* 32 bytes */
+    uint32_t valid, reserved;        /* 1, 0 */
+    uint64_t probes;                 /* P */
+    uint64_t listed;                 /* n */
+    uint64_t waves;                  /* waves of the launch */
+} srt_probe_list_work;
+
+typedef struct srt_probe_blend_params { /* 24 bytes */
+    float hysteresis;                   /* share of the history kept where the light did not change; [0, 1) */
+    float fast_hysteresis;              /* ... where it did (rule U3); [0, 1) */
+    float depth_hysteresis;             /* ... of the moments; [0, 1) */
+    float change_threshold;             /* relative luminance change of the DC term that counts as a change; >= 0 */
+    uint32_t flags;                     /* SRT_PROBE_BLEND_MOMENTS | _LISTED | _PREVIOUS_STATES | _COUNT_WORK */
+    uint32_t reserved;                  /* 0 */
+} srt_probe_blend_params;
+
+typedef struct srt_probe_blend_work { /* 40 bytes */
+    uint32_t valid, reserved;         /* 1, 0 */
+    uint64_t probes;                  /* probes blended */
+    uint64_t restarted;               /* ... of which restarted (rule U2) */
+    uint64_t changed;                 /* ... of which did not restart and changed (rule U3) */
+    uint64_t waves;                   /* waves of the launch */
+} srt_probe_blend_work;
+
+struct srt_light_probe_params; /* (defined in the light-probe block below) */
+struct srt_probe_depth_params; /* (defined in the probe-depth block below) */
+/* skip_mask SRT_PROBE_BURIED | SRT_PROBE_IDLE, flags 0, reserved 0 (pure host). */
+int srt_probe_list_params_default(srt_probe_list_params* out);
+int srt_list_probes(srt_context* ctx, const srt_probe_list_params* params);
+int srt_bind_probe_list_output(srt_context* ctx, void* d_list);
+int srt_read_probe_list_output(srt_context* ctx, uint32_t* dst);
+int srt_get_probe_list_work(srt_context* ctx, srt_probe_list_work* out);
+int srt_bind_probe_list(srt_context* ctx, const void* d_list, size_t capacity);
+int srt_write_probe_list(srt_context* ctx, const uint32_t* list, size_t capacity);
+int srt_trace_light_probes_listed(srt_context* ctx, const struct srt_light_probe_params* params);
+int srt_trace_probe_depth_listed(srt_context* ctx, const struct srt_probe_depth_params* params);
+/* hysteresis 0.9f, fast_hysteresis 0.5f, depth_hysteresis 0.9f, change_threshold 0.25f, flags 0, reserved 0 (pure host; picks). */
+int srt_probe_blend_params_default(srt_probe_blend_params* out);
+int srt_reset_probe_history(srt_context* ctx, uint32_t which, size_t probes, uint32_t resolution);
+int srt_bind_probe_history(srt_context* ctx, uint32_t which, void* d_ptr);
+int srt_read_probe_history(srt_context* ctx, uint32_t which, float* dst);
+int srt_write_probe_previous_states(srt_context* ctx, const float* records, size_t probes);
+int srt_bind_probe_previous_states(srt_context* ctx, const void* d_ptr, size_t probes);
+int srt_blend_probes(srt_context* ctx, const srt_probe_blend_params* params);
+int srt_get_probe_blend_work(srt_context* ctx, srt_probe_blend_work* out);
+
 /* ---- probe classification and relocation: states and offsets for a probe grid (ABI 7, backward compatible) ----------------------
  * These calls were added without changing anything else, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of them
  * runs what it ran before, bit for bit.  (The rules are numbered S1 .. S9; the blocks that use them follow further down.)

@@ -58,6 +58,11 @@ PROBE_DEPTH_RESOLUTIONS = (4, 8, 16)
 PROBE_STATE_RECORDS, PROBE_STATE_POSITIONS = 1, 2
 PROBE_CLASSIFY_RELOCATE, PROBE_CLASSIFY_NORMALIZE, PROBE_CLASSIFY_COUNT_WORK = 1, 2, 4
 PROBE_CLEAR, PROBE_MOVED, PROBE_BURIED, PROBE_INSIDE, PROBE_IDLE = 0, 1, 2, 4, 8
+# per-frame probe updates (srt_list_probes, the listed traces, srt_blend_probes): the list's flag and header, the histories, the
+# flags of srt_probe_blend_params
+PROBE_LIST_COUNT_WORK, PROBE_LIST_HEADER, PROBE_LIST_NONE = 1, 4, 0xFFFFFFFF
+PROBE_HISTORY_COEFFICIENTS, PROBE_HISTORY_MOMENTS = 1, 2
+PROBE_BLEND_MOMENTS, PROBE_BLEND_LISTED, PROBE_BLEND_PREVIOUS_STATES, PROBE_BLEND_COUNT_WORK = 1, 2, 4, 8
 # adaptive sampling (srt_render_adaptive, srt_sample_budget): the flags, the limits of max_samples / max_budget, the last frame
 ADAPTIVE_KEEP_COUNTS, ADAPTIVE_COUNT_WORK = 1, 2
 ADAPTIVE_MAX_SAMPLES = 4096
@@ -123,6 +128,10 @@ EXPORTS = [
     "srt_probe_grid_depth_params_default", "srt_write_probe_grid_depth", "srt_bind_probe_grid_depth", "srt_shade_probe_grid_depth",
     "srt_probe_classify_params_default", "srt_classify_probes", "srt_bind_probe_states_output", "srt_read_probe_states_output",
     "srt_get_probe_classify_work", "srt_write_probe_grid_states", "srt_bind_probe_grid_states", "srt_shade_probe_grid_states",
+    "srt_probe_list_params_default", "srt_list_probes", "srt_bind_probe_list_output", "srt_read_probe_list_output", "srt_get_probe_list_work",
+    "srt_bind_probe_list", "srt_write_probe_list", "srt_trace_light_probes_listed", "srt_trace_probe_depth_listed",
+    "srt_probe_blend_params_default", "srt_reset_probe_history", "srt_bind_probe_history", "srt_read_probe_history",
+    "srt_write_probe_previous_states", "srt_bind_probe_previous_states", "srt_blend_probes", "srt_get_probe_blend_work",
 ]
 
 
@@ -398,6 +407,34 @@ class ProbeClassifyWork(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+class ProbeListParams(C.Structure):
+    """srt_probe_list_params: the state bits that exclude a probe from the list, PROBE_LIST_COUNT_WORK."""
+    _fields_ = [("skip_mask", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class ProbeListWork(C.Structure):
+    """srt_probe_list_work: what the last counting srt_list_probes found."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("listed", C.c_uint64), ("waves", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class ProbeBlendParams(C.Structure):
+    """srt_probe_blend_params: the three hystereses, the change threshold, PROBE_BLEND_* flags."""
+    _fields_ = [("hysteresis", C.c_float), ("fast_hysteresis", C.c_float), ("depth_hysteresis", C.c_float), ("change_threshold", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ProbeBlendWork(C.Structure):
+    """srt_probe_blend_work: what the last counting srt_blend_probes did."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("restarted", C.c_uint64), ("changed", C.c_uint64),
+                ("waves", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class UpdateInfo(C.Structure):
     """srt_update_info: what the last successful srt_update_scene did to the mesh image."""
     _fields_ = [("path", C.c_int32), ("reason", C.c_int32), ("levels", C.c_int32), ("triangles", C.c_uint32), ("nodes", C.c_uint32),
@@ -608,6 +645,23 @@ def open_library(path):
     L.srt_write_probe_grid_states.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t]
     L.srt_bind_probe_grid_states.argtypes = [ctx, C.c_void_p, C.c_size_t]
     L.srt_shade_probe_grid_states.argtypes = [ctx, C.POINTER(ProbeGridParams), C.POINTER(ProbeGridDepthParams)]
+    L.srt_probe_list_params_default.argtypes = [C.POINTER(ProbeListParams)]
+    L.srt_list_probes.argtypes = [ctx, C.POINTER(ProbeListParams)]
+    L.srt_bind_probe_list_output.argtypes = [ctx, C.c_void_p]
+    L.srt_read_probe_list_output.argtypes = [ctx, C.POINTER(C.c_uint32)]
+    L.srt_get_probe_list_work.argtypes = [ctx, C.POINTER(ProbeListWork)]
+    L.srt_bind_probe_list.argtypes = [ctx, C.c_void_p, C.c_size_t]
+    L.srt_write_probe_list.argtypes = [ctx, C.POINTER(C.c_uint32), C.c_size_t]
+    L.srt_trace_light_probes_listed.argtypes = [ctx, C.POINTER(LightProbeParams)]
+    L.srt_trace_probe_depth_listed.argtypes = [ctx, C.POINTER(ProbeDepthParams)]
+    L.srt_probe_blend_params_default.argtypes = [C.POINTER(ProbeBlendParams)]
+    L.srt_reset_probe_history.argtypes = [ctx, C.c_uint32, C.c_size_t, C.c_uint32]
+    L.srt_bind_probe_history.argtypes = [ctx, C.c_uint32, C.c_void_p]
+    L.srt_read_probe_history.argtypes = [ctx, C.c_uint32, C.POINTER(C.c_float)]
+    L.srt_write_probe_previous_states.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t]
+    L.srt_bind_probe_previous_states.argtypes = [ctx, C.c_void_p, C.c_size_t]
+    L.srt_blend_probes.argtypes = [ctx, C.POINTER(ProbeBlendParams)]
+    L.srt_get_probe_blend_work.argtypes = [ctx, C.POINTER(ProbeBlendWork)]
     L.srt_set_sample_counts.argtypes = [ctx, C.c_uint32]
     L.srt_write_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
     L.srt_read_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
@@ -1422,14 +1476,16 @@ class PathTracer:
         return n, arr  # (a bound tensor stays referenced for as long as it is bound)
 
     def trace_light_probes(self, positions=None, directions=None, samples=None, bounces=None, seed=0, first_sample=1, reset=True, id_base=0,
-                           normalize=False, count_work=False, coefficients=True, radiance=False, flags=0):
+                           normalize=False, count_work=False, coefficients=True, radiance=False, flags=0, listed=False):
         """srt_trace_light_probes: for each of P probe positions, the running mean of `samples` path-traced samples (default 16) of
         `bounces` bounces (default 8) along each of K shared directions, projected onto the nine SH coefficients of bands 0..2.
         `positions`: numpy (P, 4) float32 (written) or a torch tensor on this tracer's device (bound); None: the current ones.
         `directions`: the same, (K, 4) with the quadrature weight in w; an int K: light_probe_sphere(K); None: the current ones.
         Ray (p, k) draws from the stream of pixel id_base + p*K + k.  coefficients / radiance: the outputs (light_probe_coefficients(),
         light_probe_radiance()); reset=False continues the means the RADIANCE buffer holds; normalize: SRT_LIGHT_PROBE_NORMALIZE;
-        count_work: SRT_LIGHT_PROBE_COUNT_WORK (light_probe_work() then reads the record).  Asynchronous, like render()."""
+        count_work: SRT_LIGHT_PROBE_COUNT_WORK (light_probe_work() then reads the record).  listed: srt_trace_light_probes_listed —
+        only the probes of the list bound for tracing (bind_probe_list()); every other probe's outputs keep their bits.
+        Asynchronous, like render()."""
         L = self.L
         if positions is not None:
             self._probe_count, self._probe_bound = self._light_probe_input("trace_light_probes(positions)", positions, L.srt_write_light_probes,
@@ -1457,7 +1513,7 @@ class PathTracer:
                 t = bound.get(bit)
                 if (p.outputs & bit) and t is not None and t.shape[0] < need:
                     raise ValueError("trace_light_probes: the bound tensor holds %d elements, the call writes %d" % (t.shape[0], need))
-        self._ck(L.srt_trace_light_probes(self._h, C.byref(p)))
+        self._ck((L.srt_trace_light_probes_listed if listed else L.srt_trace_light_probes)(self._h, C.byref(p)))
         self._probes_traced = (np_, nk)
 
     def bind_light_probe_output(self, output, tensor):
@@ -1570,13 +1626,14 @@ class PathTracer:
 
     # ---- probe depth moments and the filtered probe-grid shading -------------------------------
     def trace_probe_depth(self, positions=None, directions=None, resolution=None, sharpness=None, max_distance=None, normalize=False,
-                          count_work=False, moments=True, distances=False, flags=0, reserved=0):
+                          count_work=False, moments=True, distances=False, flags=0, reserved=0, listed=False):
         """srt_trace_probe_depth: for each of P probe positions an octahedral map of `resolution` x `resolution` texels (default 16)
         holding the weighted mean and mean square of the distance to the nearest surface over the K shared directions, each
         direction weighing cos^(2^sharpness) (default 5) times its quadrature weight, distances clamped to `max_distance` (default
         10000).  `positions` / `directions`: as trace_light_probes() takes them (they are the same current arrays); None: the
         current ones.  moments / distances: the outputs (probe_depth_output()); normalize: SRT_PROBE_DEPTH_NORMALIZE; count_work:
-        SRT_PROBE_DEPTH_COUNT_WORK (probe_depth_work() then reads the record).  Asynchronous, like render()."""
+        SRT_PROBE_DEPTH_COUNT_WORK (probe_depth_work() then reads the record).  listed: srt_trace_probe_depth_listed — only the probes
+        of the list bound for tracing (bind_probe_list()).  Asynchronous, like render()."""
         L = self.L
         if positions is not None:
             self._probe_count, self._probe_bound = self._light_probe_input("trace_probe_depth(positions)", positions, L.srt_write_light_probes,
@@ -1605,7 +1662,7 @@ class PathTracer:
                 t = bound.get(bit)
                 if (p.outputs & bit) and t is not None and t.numel() < need:
                     raise ValueError("trace_probe_depth: the bound tensor holds %d floats, the call writes %d" % (t.numel(), need))
-        self._ck(L.srt_trace_probe_depth(self._h, C.byref(p)))
+        self._ck((L.srt_trace_probe_depth_listed if listed else L.srt_trace_probe_depth)(self._h, C.byref(p)))
         self._probe_depth_traced = (np_, nk, int(p.resolution))
 
     def bind_probe_depth_output(self, output, tensor):
@@ -1856,6 +1913,170 @@ class PathTracer:
             d.min_variance = float(min_variance)
         d.reserved[0], d.reserved[1] = int(depth_reserved[0]), int(depth_reserved[1])
         self._ck(L.srt_shade_probe_grid_states(self._h, C.byref(p), C.byref(d)))
+
+    # ---- per-frame probe updates: the list of active probes, the histories and the hysteresis blend ----
+    def list_probes(self, skip_mask=None, count_work=False, output=None, flags=0, reserved=(0, 0)):
+        """srt_list_probes: the indices of the probes whose current record (bind_probe_grid_states()) has none of the `skip_mask`
+        bits (default PROBE_BURIED | PROBE_IDLE), ascending, in SRT_PROBE_LIST's layout: 4 + P uint32 (n, P, 0, 0, the n indices,
+        then 0xFFFFFFFF).  output: a torch int32 / uint32 tensor of at least 4 + P words on this tracer's device to write into
+        (bound for later calls too); probe_list_output() reads the list, probe_list_work() the counts.  Asynchronous."""
+        L = self.L
+        if output is not None:
+            self.bind_probe_list_output(output)
+        p = ProbeListParams()
+        self._ck(L.srt_probe_list_params_default(C.byref(p)))
+        if skip_mask is not None:
+            p.skip_mask = int(skip_mask)
+        p.flags = int(flags) | (PROBE_LIST_COUNT_WORK if count_work else 0)
+        p.reserved[0], p.reserved[1] = int(reserved[0]), int(reserved[1])
+        self._ck(L.srt_list_probes(self._h, C.byref(p)))
+
+    def _word_tensor(self, what, tensor):
+        """The device pointer and word count of a contiguous 32-bit integer torch tensor on this tracer's device."""
+        import torch
+
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError("%s: expected a torch.Tensor, got %s" % (what, type(tensor).__name__))
+        if tensor.device.type != "cuda" or tensor.device.index != self.device:
+            raise ValueError("%s: tensor on %s, the tracer renders on cuda:%d" % (what, tensor.device, self.device))
+        if tensor.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+            raise TypeError("%s: dtype %s, want a 32-bit integer type" % (what, tensor.dtype))
+        if tensor.dim() != 1 or not tensor.is_contiguous():
+            raise ValueError("%s: want a contiguous one-dimensional tensor, got shape %s" % (what, tuple(tensor.shape)))
+        return C.c_void_p(tensor.data_ptr()), int(tensor.shape[0])
+
+    def bind_probe_list_output(self, tensor):
+        """srt_bind_probe_list_output: list_probes() writes into a 32-bit integer torch tensor of at least 4 + P words on this
+        tracer's device (the caller sees to the size and keeps it alive); None: the handle's own buffer."""
+        ptr = None if tensor is None else self._word_tensor("bind_probe_list_output", tensor)[0]
+        self._ck(self.L.srt_bind_probe_list_output(self._h, ptr))
+        self._probe_list_out_bound = tensor
+
+    def probe_list_output(self, probes):
+        """srt_read_probe_list_output: the 4 + `probes` uint32 words of the last list_probes().  Waits."""
+        return self._read_image(self.L.srt_read_probe_list_output, (PROBE_LIST_HEADER + int(probes),), np.uint32)
+
+    def probe_list_work(self):
+        """srt_get_probe_list_work: the work counts of the last list_probes(count_work=True) as a dict.  Waits."""
+        w = ProbeListWork()
+        self._ck(self.L.srt_get_probe_list_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def bind_probe_list(self, words):
+        """srt_write_probe_list / srt_bind_probe_list: the list the listed traces and a listed blend read, 4 + P words in
+        SRT_PROBE_LIST's layout.  A numpy array: written; a 32-bit integer torch tensor on this tracer's device: bound, no copy
+        (what bind_probe_list_output(t) filled); None: unbound."""
+        L = self.L
+        if words is None:
+            self._ck(L.srt_bind_probe_list(self._h, None, 0))
+            self._probe_list_bound = None
+            return
+        try:
+            import torch
+        except ImportError:
+            torch = None
+        if torch is not None and isinstance(words, torch.Tensor) and words.device.type == "cuda":
+            ptr, n = self._word_tensor("bind_probe_list", words)
+            self._ck(L.srt_bind_probe_list(self._h, ptr, n))
+            self._probe_list_bound = words  # (a bound tensor stays referenced for as long as it is bound)
+            return
+        a = np.ascontiguousarray(words.numpy() if torch is not None and isinstance(words, torch.Tensor) else words).astype(np.uint32, copy=False).reshape(-1)
+        self._ck(L.srt_write_probe_list(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.shape[0]))
+        self._probe_list_bound = None
+
+    @staticmethod
+    def _history_bits(which):
+        names = {"coefficients": PROBE_HISTORY_COEFFICIENTS, "moments": PROBE_HISTORY_MOMENTS, "both": PROBE_HISTORY_COEFFICIENTS | PROBE_HISTORY_MOMENTS}
+        return int(names.get(which, which))
+
+    def reset_probe_history(self, probes, resolution=0, which=None):
+        """srt_reset_probe_history: give the histories of `which` ("coefficients", "moments", "both"; default: both when a
+        resolution is given) their size — `probes` probes, `resolution` texels a side for the moments — and zero-fill them, so
+        that every probe restarts at the next blend_probes().  Enqueued on the stream."""
+        bits = self._history_bits(which) if which is not None else (PROBE_HISTORY_COEFFICIENTS | (PROBE_HISTORY_MOMENTS if resolution else 0))
+        self._ck(self.L.srt_reset_probe_history(self._h, bits, int(probes), int(resolution)))
+        sizes = self.__dict__.setdefault("_probe_history_sizes", {})
+        for bit in (PROBE_HISTORY_COEFFICIENTS, PROBE_HISTORY_MOMENTS):
+            if bits & bit:
+                sizes[bit] = (int(probes), int(resolution))
+
+    def bind_probe_history(self, which, tensor):
+        """srt_bind_probe_history: keep history "coefficients" (P*9 float4) or "moments" (P*R*R float4) in a float32 torch tensor
+        (M, 4) on this tracer's device, contiguous, at least that large (the caller sees to it and keeps it alive); None: the
+        handle's own buffer.  reset_probe_history() gives it its size."""
+        bit = self._history_bits(which)
+        if tensor is not None:
+            import torch
+
+            if not isinstance(tensor, torch.Tensor):
+                raise TypeError("bind_probe_history: expected a torch.Tensor, got %s" % type(tensor).__name__)
+            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
+            if m < 1:
+                raise ValueError("bind_probe_history: shape %s, want at least one element" % (tuple(tensor.shape),))
+            ptr = self._tensor_ptr("bind_probe_history", tensor, np.float32, (m, 4))
+        else:
+            ptr = None
+        self._ck(self.L.srt_bind_probe_history(self._h, bit, ptr))
+        bound = self.__dict__.setdefault("_probe_history_bound", {})
+        if tensor is None:
+            bound.pop(bit, None)
+        else:
+            bound[bit] = tensor
+
+    def probe_history(self, which="coefficients"):
+        """srt_read_probe_history: "coefficients": (P, 9, 4) float32; "moments": (P, R*R, 4) float32.  Waits."""
+        bit = self._history_bits(which)
+        size = self.__dict__.get("_probe_history_sizes", {}).get(bit)
+        if size is None:
+            raise SrtError(ERR_STATE, "probe_history(): no reset_probe_history() for that history yet")
+        shape = (size[0], LIGHT_PROBE_COEFFS, 4) if bit == PROBE_HISTORY_COEFFICIENTS else (size[0], size[1] * size[1], 4)
+        return self._read_image(self.L.srt_read_probe_history, shape, np.float32, bit)
+
+    def bind_probe_previous_states(self, records):
+        """srt_write_probe_previous_states / srt_bind_probe_previous_states: the records blend_probes(previous_states=True)
+        compares the current ones with; as bind_probe_grid_states() takes them."""
+        L = self.L
+        if records is None:
+            self._ck(L.srt_bind_probe_previous_states(self._h, None, 0))
+            self._probe_previous_bound = None
+            return
+        kind, arr, n = self._ray_array("bind_probe_previous_states(records)", records)
+        if kind == "host":
+            self._ck(L.srt_write_probe_previous_states(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n))
+            self._probe_previous_bound = None
+        else:
+            self._ck(L.srt_bind_probe_previous_states(self._h, C.c_void_p(arr.data_ptr()), n))
+            self._probe_previous_bound = arr
+
+    def blend_probes(self, hysteresis=None, fast_hysteresis=None, depth_hysteresis=None, change_threshold=None, moments=False, listed=False,
+                     previous_states=False, count_work=False, flags=0, reserved=0):
+        """srt_blend_probes: fold what the last trace_light_probes() wrote to COEFFICIENTS (and, moments=True, the last
+        trace_probe_depth() to MOMENTS) into the histories, in place: H = N + (H - N) * h, with h = `hysteresis` (default 0.9), or
+        `fast_hysteresis` (0.5) where the DC luminance changed by more than `change_threshold` (0.25) of the larger value, and
+        `depth_hysteresis` (0.9) for the moments.  A probe whose history is empty restarts (H = N), and with previous_states=True
+        one whose record differs from bind_probe_previous_states()'s in its offset or its BURIED / IDLE bits.  listed: only the
+        probes of bind_probe_list().  probe_history() reads the result; probe_blend_work() the counts.  Asynchronous."""
+        L = self.L
+        p = ProbeBlendParams()
+        self._ck(L.srt_probe_blend_params_default(C.byref(p)))
+        if hysteresis is not None:
+            p.hysteresis = float(hysteresis)
+        if fast_hysteresis is not None:
+            p.fast_hysteresis = float(fast_hysteresis)
+        if depth_hysteresis is not None:
+            p.depth_hysteresis = float(depth_hysteresis)
+        if change_threshold is not None:
+            p.change_threshold = float(change_threshold)
+        p.flags = (int(flags) | (PROBE_BLEND_MOMENTS if moments else 0) | (PROBE_BLEND_LISTED if listed else 0) |
+                   (PROBE_BLEND_PREVIOUS_STATES if previous_states else 0) | (PROBE_BLEND_COUNT_WORK if count_work else 0))
+        p.reserved = int(reserved)
+        self._ck(L.srt_blend_probes(self._h, C.byref(p)))
+
+    def probe_blend_work(self):
+        """srt_get_probe_blend_work: the work counts of the last blend_probes(count_work=True) as a dict.  Waits."""
+        w = ProbeBlendWork()
+        self._ck(self.L.srt_get_probe_blend_work(self._h, C.byref(w)))
+        return w.as_dict()
 
     def ray_output(self, name, count=None):
         """srt_read_ray_output: one output of the last trace_rays() as a numpy array: "object" and "occluded" (N,) int32, the

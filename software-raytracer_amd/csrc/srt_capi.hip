@@ -47,6 +47,8 @@
 #include "srt_probe_depth_host.h"
 #include "srt_probe_states.hip.h"
 #include "srt_probe_states_host.h"
+#include "srt_probe_update.hip.h"
+#include "srt_probe_update_host.h"
 #include "srt_adaptive.hip.h"
 #include "srt_adaptive_host.h"
 #include "srt_launch_shape.h"
@@ -446,6 +448,17 @@ struct srt_context {
     srt::ProbeStatesState probe_states;
     DeviceBuffer<float4> d_probe_grid_states;
     DeviceBuffer<unsigned long long> d_probe_classify_work;
+    // per-frame probe updates (srt_list_probes, the listed traces, srt_blend_probes): the rules' state (srt_probe_update_host.h:
+    // what the last listing wrote, which list is bound for tracing, the previous records, which P and R the histories stand for);
+    // the own list output, the own list input (srt_write_probe_list), the own previous records, the two own histories; the records
+    // the counting launches add to (srt::PL_WORK_N, srt::PB_WORK_N words).
+    srt::ProbeUpdateState probe_update;
+    DeviceBuffer<uint32_t> d_probe_list_out;
+    DeviceBuffer<uint32_t> d_probe_list;
+    DeviceBuffer<float4> d_probe_previous_states;
+    DeviceBuffer<float4> d_probe_history[srt::PROBE_HISTORY_SLOTS];
+    DeviceBuffer<unsigned long long> d_probe_list_work;
+    DeviceBuffer<unsigned long long> d_probe_blend_work;
     // adaptive sampling (srt_render_adaptive, srt_sample_budget): the per-pixel sample counts and sample budget, W*H uint32 each,
     // own buffer and slot; whether the last adaptive render counted and whether a budget pass has run (srt_adaptive_host.h); the
     // tile ticket of a launch (zeroed on the stream in front of it); the record a counting launch adds to (srt::ADP_WORK_N words);
@@ -537,6 +550,11 @@ int read_work(srt_context* ctx, const DeviceBuffer<unsigned long long>& d, unsig
     if (const int rc = finish_stream(ctx)) return rc;
     SRT_HIP(ctx, hipMemcpy(w, d, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return SRT_OK;
+}
+
+// the list the listed traces and a listed blend read: the bound one, else the own one
+const uint32_t* current_probe_list(const srt_context* ctx) {
+    return ctx->probe_update.list.bound ? (const uint32_t*)ctx->probe_update.list.bound : (const uint32_t*)ctx->d_probe_list;
 }
 
 size_t frame_pixels(const srt_context* ctx) { return (size_t)ctx->width * (size_t)ctx->height; }
@@ -1121,6 +1139,11 @@ static int launch_rays(srt_context* ctx, void (*kernel)(srt::KernelParams, IO), 
 #define SRT_KERNEL_LDS_MESH_COUNT(kernel, in_lds, mesh, count)                                                                                  \
     (!(count) ? ((in_lds) ? ((mesh) ? kernel<true, true, false> : kernel<true, false, false>) : ((mesh) ? kernel<false, true, false> : kernel<false, false, false>)) \
               : ((in_lds) ? ((mesh) ? kernel<true, true, true> : kernel<true, false, true>) : ((mesh) ? kernel<false, true, true> : kernel<false, false, true>)))
+// ... the listed instantiations of the two probe tracing kernels
+#define SRT_KERNEL_LDS_MESH_COUNT_LISTED(kernel, in_lds, mesh, count)                                                                                             \
+    (!(count) ? ((in_lds) ? ((mesh) ? kernel<true, true, false, true> : kernel<true, false, false, true>)                                                        \
+                          : ((mesh) ? kernel<false, true, false, true> : kernel<false, false, false, true>))                                                     \
+              : ((in_lds) ? ((mesh) ? kernel<true, true, true, true> : kernel<true, false, true, true>) : ((mesh) ? kernel<false, true, true, true> : kernel<false, false, true, true>)))
 
 // What a block costs, from its counts: the weights are wave instructions per trip of the loop counted (a pool step costs its fixed
 // part plus the uniform-sphere groups, cluster bounds and boxes every step runs through), fitted on measured band times of
@@ -2182,15 +2205,20 @@ static int light_probe_output_released(srt_context* ctx, int i) {
     return SRT_OK;
 }
 
-int srt_trace_light_probes(srt_context* ctx, const srt_light_probe_params* t) {
+// srt_trace_light_probes (listed == false) and srt_trace_light_probes_listed: one body.  The listed call is sized for P as the
+// unlisted one is (the grid, the sample scratch, the partial buffer): the count of the list stays on the device.
+static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t, bool listed, const char* who) {
     if (!ctx || !t) return SRT_ERR_INVALID_ARG;
     const srt::LightProbeCall call{t->first_sample, t->sample_count, t->max_bounces, t->seed, t->id_base, t->flags, t->outputs, t->reserved};
     const char* why = "";
     if (const srt::RaysStatus rs = srt::light_probe_check_trace(ctx->probes, ctx->scene_set, call, current(ctx->probe_out[1], ctx->d_probe_out_own[1]), &why))
-        return fail(ctx, (int)rs, "srt_trace_light_probes: %s (first_sample %u, sample_count %u, max_bounces %d, flags 0x%x, outputs 0x%x, reserved %u)", why,
-                    t->first_sample, t->sample_count, t->max_bounces, t->flags, t->outputs, t->reserved);
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
+        return fail(ctx, (int)rs, "%s: %s (first_sample %u, sample_count %u, max_bounces %d, flags 0x%x, outputs 0x%x, reserved %u)", who, why, t->first_sample,
+                    t->sample_count, t->max_bounces, t->flags, t->outputs, t->reserved);
     const size_t np = ctx->probes.positions.count(), nk = ctx->probes.directions.count();
+    if (listed) {
+        if (const srt::RaysStatus rs = srt::probe_list_check_trace(ctx->probe_update, np, &why)) return fail(ctx, (int)rs, "%s: %s", who, why);
+    }
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t J = srt::light_probe_blocks(nk);
     const bool count = (t->flags & SRT_LIGHT_PROBE_COUNT_WORK) != 0;
     const bool coefficients = (t->outputs & SRT_LIGHT_PROBE_COEFFICIENTS) != 0;
@@ -2209,7 +2237,8 @@ int srt_trace_light_probes(srt_context* ctx, const srt_light_probe_params* t) {
     // (the fields accumulate_sample and the bounce loop read)
     K.first_sample = t->first_sample, K.sample_count = t->sample_count, K.max_bounces = t->max_bounces, K.seed = t->seed;
     if (t->flags & SRT_LIGHT_PROBE_RESET) K.flags |= SRT_RENDER_RESET;
-    const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::light_probe_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    const auto kernel = listed ? SRT_KERNEL_LDS_MESH_COUNT_LISTED(srt::light_probe_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count)
+                               : SRT_KERNEL_LDS_MESH_COUNT(srt::light_probe_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
     // the grid first: the sample scratch is sized by it
     const unsigned wgs = srt::light_probe_grid(np, nk, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
     const size_t scratch = srt::light_probe_scratch_bytes(wgs, srt::OUT_WG_UNITS);
@@ -2231,17 +2260,25 @@ int srt_trace_light_probes(srt_context* ctx, const srt_light_probe_params* t) {
     io.radiance = dst[1];
     io.rows = ctx->d_radiance_rows;
     io.work = count ? (unsigned long long*)ctx->d_probe_work : nullptr;
+    io.list = listed ? current_probe_list(ctx) : nullptr;
     if (const int rc = launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
     if (J > 1 && coefficients) {  // the block sums of every probe, added in ascending block order
         const size_t elems = np * (size_t)srt::LP_COEFFS;
-        hipLaunchKernelGGL(srt::light_probe_sum_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->d_probe_partial,
-                           dst[0], elems, (uint32_t)J);
+        if (listed)
+            hipLaunchKernelGGL(srt::light_probe_sum_listed_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, ctx->stream,
+                               (const float4*)ctx->d_probe_partial, dst[0], io.list, (uint32_t)np, (uint32_t)J);
+        else
+            hipLaunchKernelGGL(srt::light_probe_sum_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->d_probe_partial,
+                               dst[0], elems, (uint32_t)J);
         SRT_HIP(ctx, hipGetLastError());
     }
     void* const wrote[srt::LIGHT_PROBE_SLOTS] = {dst[0], dst[1]};
     srt::light_probe_traced(ctx->probes, np, nk, t->outputs, wrote, t->flags);
     return SRT_OK;
 }
+
+int srt_trace_light_probes(srt_context* ctx, const srt_light_probe_params* t) { return trace_light_probes(ctx, t, false, "srt_trace_light_probes"); }
+int srt_trace_light_probes_listed(srt_context* ctx, const srt_light_probe_params* t) { return trace_light_probes(ctx, t, true, "srt_trace_light_probes_listed"); }
 
 int srt_bind_light_probe_output(srt_context* ctx, uint32_t output, void* d_ptr) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
@@ -2435,16 +2472,20 @@ static int probe_depth_output_released(srt_context* ctx, int i) {
     return SRT_OK;
 }
 
-int srt_trace_probe_depth(srt_context* ctx, const srt_probe_depth_params* t) {
+// srt_trace_probe_depth (listed == false) and srt_trace_probe_depth_listed: one body
+static int trace_probe_depth(srt_context* ctx, const srt_probe_depth_params* t, bool listed, const char* who) {
     if (!ctx || !t) return SRT_ERR_INVALID_ARG;
     srt::ProbeDepthCall call;
     memcpy(&call, t, sizeof call);
     const char* why = "";
     if (const srt::RaysStatus rs = srt::probe_depth_check_trace(ctx->probes, ctx->scene_set, call, &why))
-        return fail(ctx, (int)rs, "srt_trace_probe_depth: %s (resolution %u, sharpness %u, max_distance %g, flags 0x%x, outputs 0x%x, reserved %u)", why, t->resolution,
-                    t->sharpness, (double)t->max_distance, t->flags, t->outputs, t->reserved);
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
+        return fail(ctx, (int)rs, "%s: %s (resolution %u, sharpness %u, max_distance %g, flags 0x%x, outputs 0x%x, reserved %u)", who, why, t->resolution, t->sharpness,
+                    (double)t->max_distance, t->flags, t->outputs, t->reserved);
     const size_t np = ctx->probes.positions.count(), nk = ctx->probes.directions.count();
+    if (listed) {
+        if (const srt::RaysStatus rs = srt::probe_list_check_trace(ctx->probe_update, np, &why)) return fail(ctx, (int)rs, "%s: %s", who, why);
+    }
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
     const bool count = (t->flags & SRT_PROBE_DEPTH_COUNT_WORK) != 0;
     if (!ctx->probe_depth_texels_ready) {  // the three tables, once: no launch has read the buffer yet
         float table[srt::PROBE_DEPTH_TABLE * 4];
@@ -2463,7 +2504,8 @@ int srt_trace_probe_depth(srt_context* ctx, const srt_probe_depth_params* t) {
     }
     srt::KernelParams K;
     const KernelSetup ks = scene_kernel_params(ctx, 0, ctx->height, K);
-    const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::probe_depth_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    const auto kernel = listed ? SRT_KERNEL_LDS_MESH_COUNT_LISTED(srt::probe_depth_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count)
+                               : SRT_KERNEL_LDS_MESH_COUNT(srt::probe_depth_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
     const unsigned wgs = srt::probe_depth_grid(np, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
     srt::ProbeDepthIO io{};
     io.position = ctx->probes.positions.bound ? (const float4*)ctx->probes.positions.bound : (const float4*)ctx->d_probe_position;
@@ -2475,10 +2517,14 @@ int srt_trace_probe_depth(srt_context* ctx, const srt_probe_depth_params* t) {
     io.moments = (float4*)dst[0];
     io.distances = (float*)dst[1];
     io.work = count ? (unsigned long long*)ctx->d_probe_depth_work : nullptr;
+    io.list = listed ? current_probe_list(ctx) : nullptr;
     if (const int rc = launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
     srt::probe_depth_traced(ctx->probe_depth, np, nk, call, dst);
     return SRT_OK;
 }
+
+int srt_trace_probe_depth(srt_context* ctx, const srt_probe_depth_params* t) { return trace_probe_depth(ctx, t, false, "srt_trace_probe_depth"); }
+int srt_trace_probe_depth_listed(srt_context* ctx, const srt_probe_depth_params* t) { return trace_probe_depth(ctx, t, true, "srt_trace_probe_depth_listed"); }
 
 int srt_bind_probe_depth_output(srt_context* ctx, uint32_t output, void* d_ptr) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
@@ -2773,6 +2819,222 @@ int srt_shade_probe_grid_states(srt_context* ctx, const srt_probe_grid_params* s
     if (const int rc = launch_tiles(ctx, kernel, ks, K, io)) return rc;
     ctx->probe_grid_out.wrote(dst);
     srt::probe_grid_shaded(ctx->probe_grid, s->flags);
+    return SRT_OK;
+}
+
+// ---- per-frame probe updates: the list, the histories and the blend (the two listed traces are with their parents) --------
+static_assert(SRT_PROBE_LIST_COUNT_WORK == srt::PROBE_LIST_FLAG_COUNT_WORK && SRT_PROBE_LIST_HEADER == srt::PROBE_LIST_HEADER && srt::PL_HEADER == srt::PROBE_LIST_HEADER &&
+              SRT_PROBE_HISTORY_COEFFICIENTS == srt::PROBE_HISTORY_COEFFICIENTS && SRT_PROBE_HISTORY_MOMENTS == srt::PROBE_HISTORY_MOMENTS &&
+              SRT_PROBE_BLEND_MOMENTS == srt::PROBE_BLEND_FLAG_MOMENTS && SRT_PROBE_BLEND_LISTED == srt::PROBE_BLEND_FLAG_LISTED &&
+              SRT_PROBE_BLEND_PREVIOUS_STATES == srt::PROBE_BLEND_FLAG_PREVIOUS_STATES && SRT_PROBE_BLEND_COUNT_WORK == srt::PROBE_BLEND_FLAG_COUNT_WORK &&
+              sizeof(srt_probe_list_params) == 16 && sizeof(srt::ProbeListCall) == 16 && sizeof(srt_probe_list_work) == 32 && srt::PL_WORK_N == 3 &&
+              sizeof(srt_probe_blend_params) == 24 && sizeof(srt::ProbeBlendCall) == 24 && sizeof(srt_probe_blend_work) == 40 && srt::PB_WORK_N == 4 &&
+              (int)srt::PB_COEFFS == (int)srt::LIGHT_PROBE_COEFFS && (int)srt::LP_COEFFS == (int)srt::PB_COEFFS,
+              "srt_probe_update_host.h, srt_probe_update.hip.h and srt_pathtrace.h disagree");
+
+int srt_probe_list_params_default(srt_probe_list_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::ProbeListCall c;
+    srt::probe_list_call_default(c);
+    memcpy(out, &c, sizeof c);
+    return SRT_OK;
+}
+
+int srt_list_probes(srt_context* ctx, const srt_probe_list_params* t) {
+    if (!ctx || !t) return SRT_ERR_INVALID_ARG;
+    srt::ProbeListCall call;
+    memcpy(&call, t, sizeof call);
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_list_check(ctx->probe_grid, ctx->probe_states, ctx->scene_set, call, &why))
+        return fail(ctx, (int)rs, "srt_list_probes: %s (skip_mask 0x%x, flags 0x%x, reserved %u %u)", why, t->skip_mask, t->flags, t->reserved[0], t->reserved[1]);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t np = ctx->probe_states.states.count();
+    const bool count = (t->flags & SRT_PROBE_LIST_COUNT_WORK) != 0;
+    uint32_t* dst = (uint32_t*)const_cast<void*>(ctx->probe_update.list_out_bound);
+    if (!dst) {
+        if (ctx->d_probe_list_out.bytes() < srt::probe_list_bytes(np)) {  // earlier listings may still be writing it, listed traces reading it
+            if (const int rc = finish_stream(ctx)) return rc;
+            srt::probe_list_output_released(ctx->probe_update, (uint32_t*)ctx->d_probe_list_out);
+            SRT_HIP(ctx, ctx->d_probe_list_out.ensure(srt::probe_list_bytes(np)));
+        }
+        dst = ctx->d_probe_list_out;
+    }
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_probe_list_work, srt::PL_WORK_N)) return rc;
+    }
+    srt::ProbeListIO io{};
+    io.states = ctx->probe_states.states.bound ? (const float4*)ctx->probe_states.states.bound : (const float4*)ctx->d_probe_grid_states;
+    io.list = dst;
+    io.probes = (uint32_t)np, io.skip_mask = t->skip_mask;
+    io.work = count ? (unsigned long long*)ctx->d_probe_list_work : nullptr;
+    hipLaunchKernelGGL(count ? srt::probe_list_kernel<true> : srt::probe_list_kernel<false>, dim3(1), dim3(srt::WG_THREADS), 0, ctx->stream, io);
+    SRT_HIP(ctx, hipGetLastError());
+    srt::probe_list_listed(ctx->probe_update, np, t->flags, dst);
+    return SRT_OK;
+}
+
+int srt_bind_probe_list_output(srt_context* ctx, void* d_list) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    return ctx->probe_update.list_out_bound = d_list, SRT_OK;  // (no synchronisation: enqueued calls keep the buffer they were given, as srt_bind_probe_states_output)
+}
+
+int srt_read_probe_list_output(srt_context* ctx, uint32_t* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    const srt::RaysStatus rs = srt::probe_list_check_read(ctx->probe_update, &src, &bytes);
+    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, bytes, "srt_read_probe_list_output: there has been no srt_list_probes");
+}
+
+int srt_get_probe_list_work(srt_context* ctx, srt_probe_list_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::probe_list_check_work(ctx->probe_update) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_list_work: the last srt_list_probes did not ask for SRT_PROBE_LIST_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::PL_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_probe_list_work, w, srt::PL_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0;
+    out->probes = w[srt::PL_WORK_PROBES], out->listed = w[srt::PL_WORK_LISTED], out->waves = w[srt::PL_WORK_WAVES];
+    return SRT_OK;
+}
+
+int srt_bind_probe_list(srt_context* ctx, const void* d_list, size_t capacity) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    if (srt::probe_list_bind(ctx->probe_update, d_list, capacity) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_list: want a device array and a capacity of 4 + (1 .. 2^30) words, or NULL, 0 (got %zu)", capacity);
+    return SRT_OK;
+}
+
+int srt_write_probe_list(srt_context* ctx, const uint32_t* list, size_t capacity) {
+    if (!ctx || !list) return SRT_ERR_INVALID_ARG;
+    if (!srt::probe_list_capacity_ok(capacity)) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_write_probe_list: %zu words: want 4 + (1 .. 2^30)", capacity);
+    if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it may be re-allocated below)
+    const size_t bytes = capacity * sizeof(uint32_t);
+    if (ctx->d_probe_list.bytes() < bytes) {
+        ctx->probe_update.list.own_count = 0;  // (a failed allocation leaves no own array)
+        SRT_HIP(ctx, ctx->d_probe_list.ensure(bytes));
+    }
+    SRT_HIP(ctx, hipMemcpy(ctx->d_probe_list, list, bytes, hipMemcpyHostToDevice));
+    srt::light_probe_written(ctx->probe_update.list, capacity);
+    return SRT_OK;
+}
+
+int srt_probe_blend_params_default(srt_probe_blend_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::ProbeBlendCall c;
+    srt::probe_blend_call_default(c);
+    memcpy(out, &c, sizeof c);
+    return SRT_OK;
+}
+
+// the history of slot i: the bound buffer, else the own one
+static float4* current_probe_history(const srt_context* ctx, int i) {
+    const void* b = ctx->probe_update.history[i].bound;
+    return b ? (float4*)const_cast<void*>(b) : (float4*)ctx->d_probe_history[i];
+}
+
+int srt_reset_probe_history(srt_context* ctx, uint32_t which, size_t probes, uint32_t resolution) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_history_check_reset(which, probes, resolution, &why))
+        return fail(ctx, (int)rs, "srt_reset_probe_history: %s (which 0x%x, probes %zu, resolution %u)", why, which, probes, resolution);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    for (int i = 0; i < srt::PROBE_HISTORY_SLOTS; ++i) {
+        if (!(which & (1u << i))) continue;
+        const size_t bytes = srt::probe_history_bytes(i, probes, resolution);
+        if (!ctx->probe_update.history[i].bound && ctx->d_probe_history[i].bytes() < bytes) {  // earlier blends and shading calls may still use it
+            if (const int rc = finish_stream(ctx)) return rc;
+            srt::probe_history_lost(ctx->probe_update, i);
+            SRT_HIP(ctx, ctx->d_probe_history[i].ensure(bytes));
+        }
+        SRT_HIP(ctx, hipMemsetAsync(current_probe_history(ctx, i), 0, bytes, ctx->stream));
+        srt::probe_history_was_reset(ctx->probe_update, i, probes, resolution);
+    }
+    return SRT_OK;
+}
+
+int srt_bind_probe_history(srt_context* ctx, uint32_t which, void* d_ptr) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    const int i = srt::probe_history_slot(which);
+    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_history: which 0x%x is not a single SRT_PROBE_HISTORY_COEFFICIENTS / _MOMENTS bit", which);
+    return ctx->probe_update.history[i].bound = d_ptr, SRT_OK;  // (no synchronisation: enqueued calls keep the buffer they were given)
+}
+
+int srt_read_probe_history(srt_context* ctx, uint32_t which, float* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    int i = -1;
+    size_t bytes = 0;
+    const srt::RaysStatus rs = srt::probe_history_check_read(ctx->probe_update, which, &i, &bytes);
+    if (rs == srt::RAYS_INVALID_ARG)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_probe_history: which 0x%x is not a single SRT_PROBE_HISTORY_COEFFICIENTS / _MOMENTS bit", which);
+    const float4* src = rs == srt::RAYS_OK ? current_probe_history(ctx, i) : nullptr;
+    if (src && !ctx->probe_update.history[i].bound && ctx->d_probe_history[i].bytes() < bytes) src = nullptr;  // (unbound after the reset: the own buffer is not that history)
+    return read_slot(ctx, src, dst, bytes, "srt_read_probe_history: history 0x%x has not been reset (srt_reset_probe_history)", which);
+}
+
+int srt_write_probe_previous_states(srt_context* ctx, const float* records, size_t probes) {
+    if (!ctx || !records) return SRT_ERR_INVALID_ARG;
+    return write_light_probe_input(ctx, ctx->probe_update.previous, ctx->d_probe_previous_states, records, probes, srt::PROBE_GRID_MAX_PROBES, "srt_write_probe_previous_states");
+}
+
+int srt_bind_probe_previous_states(srt_context* ctx, const void* d_ptr, size_t probes) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    if (srt::light_probe_bind(ctx->probe_update.previous, d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_previous_states: want a device array and 1 .. 2^30 probes, or NULL, 0 (got %zu)", probes);
+    return SRT_OK;
+}
+
+int srt_blend_probes(srt_context* ctx, const srt_probe_blend_params* t) {
+    if (!ctx || !t) return SRT_ERR_INVALID_ARG;
+    srt::ProbeBlendCall call;
+    memcpy(&call, t, sizeof call);
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_blend_check(ctx->probe_update, ctx->probes, ctx->probe_depth, ctx->probe_states, ctx->scene_set, call, &why))
+        return fail(ctx, (int)rs, "srt_blend_probes: %s (hysteresis %g, fast_hysteresis %g, depth_hysteresis %g, change_threshold %g, flags 0x%x, reserved %u)", why,
+                    (double)t->hysteresis, (double)t->fast_hysteresis, (double)t->depth_hysteresis, (double)t->change_threshold, t->flags, t->reserved);
+    const bool moments = (t->flags & SRT_PROBE_BLEND_MOMENTS) != 0, listed = (t->flags & SRT_PROBE_BLEND_LISTED) != 0;
+    const bool prev = (t->flags & SRT_PROBE_BLEND_PREVIOUS_STATES) != 0, count = (t->flags & SRT_PROBE_BLEND_COUNT_WORK) != 0;
+    const size_t np = ctx->probe_update.history[0].probes;
+    const uint32_t R = moments ? ctx->probe_update.history[1].resolution : 0u;
+    // (a history unbound after its reset may have no own buffer of that size: the one case the rules cannot see)
+    for (int i = 0; i < (moments ? 2 : 1); ++i)
+        if (!ctx->probe_update.history[i].bound && ctx->d_probe_history[i].bytes() < srt::probe_history_bytes(i, np, R))
+            return fail(ctx, SRT_ERR_STATE, "srt_blend_probes: history 0x%x was unbound after its reset (srt_reset_probe_history)", 1u << i);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_probe_blend_work, srt::PB_WORK_N)) return rc;
+    }
+    srt::ProbeBlendIO io{};
+    io.history = current_probe_history(ctx, 0);
+    io.fresh = (const float4*)ctx->probes.last_dst[0];
+    if (moments) io.depth_history = current_probe_history(ctx, 1), io.depth_fresh = (const float4*)ctx->probe_depth.last_dst[0];
+    io.list = listed ? current_probe_list(ctx) : nullptr;
+    if (prev) {
+        io.states = ctx->probe_states.states.bound ? (const float4*)ctx->probe_states.states.bound : (const float4*)ctx->d_probe_grid_states;
+        io.previous = ctx->probe_update.previous.bound ? (const float4*)ctx->probe_update.previous.bound : (const float4*)ctx->d_probe_previous_states;
+    }
+    io.probes = (uint32_t)np, io.texels = R * R;
+    io.hysteresis = t->hysteresis, io.fast_hysteresis = t->fast_hysteresis, io.depth_hysteresis = t->depth_hysteresis, io.change_threshold = t->change_threshold;
+    io.work = count ? (unsigned long long*)ctx->d_probe_blend_work : nullptr;
+    void (*const kernel)(srt::ProbeBlendIO) =
+        listed ? (prev ? (count ? srt::probe_blend_kernel<true, true, true> : srt::probe_blend_kernel<true, true, false>)
+                       : (count ? srt::probe_blend_kernel<true, false, true> : srt::probe_blend_kernel<true, false, false>))
+               : (prev ? (count ? srt::probe_blend_kernel<false, true, true> : srt::probe_blend_kernel<false, true, false>)
+                       : (count ? srt::probe_blend_kernel<false, false, true> : srt::probe_blend_kernel<false, false, false>));
+    const unsigned wgs = srt::probe_blend_grid(np, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, 0));
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), 0, ctx->stream, io);
+    SRT_HIP(ctx, hipGetLastError());
+    srt::probe_blend_blended(ctx->probe_update, t->flags);
+    return SRT_OK;
+}
+
+int srt_get_probe_blend_work(srt_context* ctx, srt_probe_blend_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::probe_blend_check_work(ctx->probe_update) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_blend_work: the last srt_blend_probes did not ask for SRT_PROBE_BLEND_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::PB_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_probe_blend_work, w, srt::PB_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0;
+    out->probes = w[srt::PB_WORK_PROBES], out->restarted = w[srt::PB_WORK_RESTARTED], out->changed = w[srt::PB_WORK_CHANGED], out->waves = w[srt::PB_WORK_WAVES];
     return SRT_OK;
 }
 

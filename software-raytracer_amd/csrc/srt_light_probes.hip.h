@@ -44,6 +44,7 @@ struct LightProbeIO {
     float4* radiance;          // [P*K] the running means (NULL: not requested)
     float4* rows;              // [grid waves][RAD_CHUNK][64] sample colours of the chunk in flight
     unsigned long long* work;  // COUNT: [LP_WORK_N] totals of the launch (zeroed by the host before it)
+    const uint32_t* list;      // LISTED: [4 + P] SRT_PROBE_LIST's layout: n, P, 0, 0, then the probe indices
 };
 // (the sample range, bounces, seed and SRT_LIGHT_PROBE_RESET travel in KernelParams, as radiance_kernel's)
 
@@ -65,7 +66,10 @@ __device__ __forceinline__ float lp_wave_tree(float v) {
 }
 
 // LDS: the path-trace kernel's layout (make_lds with four waves), as radiance_kernel.
-template <bool SCENE_LDS, bool MESH, bool COUNT>
+// LISTED (srt_trace_light_probes_listed): the units are (q, j) for q < n, the count in the list's header, read here: the host never
+// learns it; probe p = list[q], and a word >= P skips the unit.  Everything of probe p is computed and stored as the unlisted
+// launch does it, but a multi-block partial goes to the COMPACT unit q*J + j (light_probe_sum_listed_kernel scatters it).
+template <bool SCENE_LDS, bool MESH, bool COUNT, bool LISTED = false>
 __global__ void __launch_bounds__(WG_THREADS) light_probe_kernel(const KernelParams P, const LightProbeIO io) {
     extern __shared__ float4 lds_scene[];
     if constexpr (SCENE_LDS) {  // staged as pathtrace_kernel stages it: every load issued before the first LDS store
@@ -104,11 +108,26 @@ __global__ void __launch_bounds__(WG_THREADS) light_probe_kernel(const KernelPar
     const int B = P.max_bounces;
     const bool reset = (P.flags & 1u) != 0;
     const uint32_t K = io.directions, J = io.blocks;
-    const uint32_t units = io.probes * J;  // P*K <= 2^30, so P*J <= 2^30
+    uint32_t listed = io.probes;
+    if constexpr (LISTED) {
+        const uint32_t ln = io.list[0];              // (one address for the launch)
+        listed = ln < io.probes ? ln : io.probes;  // (a list holds at most P indices: nothing is read past 4 + P)
+    }
+    const uint32_t units = listed * J;  // P*K <= 2^30, so P*J <= 2^30
     const bool norm = io.normalize != 0u;  // (a kernel argument: wave-uniform)
     // wave-uniform loop: every lane of a wave runs the same trips, so closest_hit sees all 64 lanes in each call
     for (uint32_t u = blockIdx.x * (uint32_t)WAVES + (uint32_t)wave; u < units; u += gridDim.x * (uint32_t)WAVES) {
-        const uint32_t p = u / J, j = u - p * J;
+        uint32_t p = u / J;
+        const uint32_t j = u - p * J;
+        uint32_t slot = u;  // where the projection goes (unlisted, J == 1: u == p)
+        if constexpr (LISTED) {
+            // wave-uniform values, moved to scalar registers: the listed instantiations keep the vector register count, and with it
+            // the occupancy, of the unlisted ones
+            const uint32_t us = (uint32_t)__builtin_amdgcn_readfirstlane((int)u);
+            p = (uint32_t)__builtin_amdgcn_readfirstlane((int)io.list[4u + p]);
+            if (p >= io.probes) continue;  // a bad word skips the unit: no store can go out of range
+            slot = J == 1u ? p : us;
+        }
         const uint32_t k = (j << 6) + (uint32_t)lane;
         const bool active = k < K;
         const uint32_t i = p * K + k;  // the ray's element and stream offset (< 2^30 for an active lane)
@@ -324,7 +343,7 @@ __global__ void __launch_bounds__(WG_THREADS) light_probe_kernel(const KernelPar
             b[6] = 0.315392f * ((3.0f * (z * z)) - 1.0f);
             b[7] = 1.092548f * (x * z);
             b[8] = 0.546274f * ((x * x) - (y * y));
-            float4* const out = dst + (size_t)u * LP_COEFFS;  // (J == 1: u == p)
+            float4* const out = dst + (size_t)slot * LP_COEFFS;
 #pragma unroll
             for (int c = 0; c < LP_COEFFS; ++c) {
                 const float t = w * b[c];

@@ -45,6 +45,7 @@ struct ProbeDepthIO {
     float4* moments;           // [P][R*R] (NULL: not requested)
     float* distances;          // [P][K] (NULL: not requested)
     unsigned long long* work;  // COUNT: [PD_WORK_N] totals of the launch (zeroed by the host before it)
+    const uint32_t* list;      // LISTED: [4 + P] SRT_PROBE_LIST's layout: n, P, 0, 0, then the probe indices
 };
 
 template <bool ON>
@@ -58,9 +59,20 @@ struct PdWork<true> {
 };
 
 // LDS: the path-trace kernel's layout (make_lds with four waves), as rays_kernel.
-template <bool SCENE_LDS, bool MESH, bool COUNT>
+// LISTED (srt_trace_probe_depth_listed): the waves are dealt the q < n of the list, n read from its header here; probe p = list[q],
+// and a word >= P skips the probe.
+template <bool SCENE_LDS, bool MESH, bool COUNT, bool LISTED = false>
 __global__ void __launch_bounds__(WG_THREADS) probe_depth_kernel(const KernelParams P, const ProbeDepthIO io) {
     extern __shared__ float4 lds_scene[];
+    // LISTED: the list's count and the word of this wave's first probe are loaded in front of the scene staging, so that their
+    // latency (the first touch of the list) hides behind it instead of standing in front of the first probe.  (Loading later words one
+    // probe ahead was measured twice and made the call slower, 1.06 - 1.08 of its parent against 1.006 - 1.011: DESIGN.md §4.31.)
+    uint32_t list_count = 0u, first_word = 0u;
+    if constexpr (LISTED) {
+        const uint32_t q0 = blockIdx.x * (uint32_t)(WG_TILES_X * WG_TILES_Y) + (threadIdx.x >> 6);
+        list_count = io.list[0];                             // (one address for the launch)
+        if (q0 < io.probes) first_word = io.list[4u + q0];  // (the list has 4 + P words whatever its count says)
+    }
     if constexpr (SCENE_LDS) {  // staged as pathtrace_kernel stages it: every load issued before the first LDS store
         constexpr int STAGE = 8;
         const int n = P.scene_vec4;
@@ -106,7 +118,14 @@ __global__ void __launch_bounds__(WG_THREADS) probe_depth_kernel(const KernelPar
         ex[q] = e.x, ey[q] = e.y, ez[q] = e.z;
     }
     // wave-uniform loop: every lane of a wave runs the same trips, so closest_hit sees all 64 lanes in each call
-    for (uint32_t p = blockIdx.x * (uint32_t)WAVES + (uint32_t)wave; p < io.probes; p += gridDim.x * (uint32_t)WAVES) {
+    uint32_t units = io.probes;
+    if constexpr (LISTED) units = list_count < io.probes ? list_count : io.probes;  // (a list holds at most P indices: nothing is read past 4 + P)
+    for (uint32_t q = blockIdx.x * (uint32_t)WAVES + (uint32_t)wave; q < units; q += gridDim.x * (uint32_t)WAVES) {
+        uint32_t p = q;
+        if constexpr (LISTED) {
+            p = q == blockIdx.x * (uint32_t)WAVES + (uint32_t)wave ? first_word : io.list[4u + q];  // (one address for the wave)
+            if (p >= io.probes) continue;                                                            // a bad word skips the probe: no store can go out of range
+        }
         const float4 o4 = io.position[p];  // (one address for the wave: a broadcast 16-byte load)
         float M1[PD_TEXELS_PER_LANE], M2[PD_TEXELS_PER_LANE], Wt[PD_TEXELS_PER_LANE], Ft[PD_TEXELS_PER_LANE];
 #pragma unroll

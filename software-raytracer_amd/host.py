@@ -17,6 +17,9 @@ from .capi import (PROBE_DEPTH_COUNT_WORK, PROBE_DEPTH_DISTANCES, PROBE_DEPTH_MO
                    ProbeGridDepthParams, probe_depth_texels)  # noqa: F401
 from .capi import (PROBE_CLASSIFY_COUNT_WORK, PROBE_CLASSIFY_NORMALIZE, PROBE_CLASSIFY_RELOCATE, PROBE_STATE_POSITIONS, PROBE_STATE_RECORDS,
                    ProbeClassifyParams, ProbeClassifyWork)  # noqa: F401
+from .capi import (PROBE_BLEND_COUNT_WORK, PROBE_BLEND_LISTED, PROBE_BLEND_MOMENTS, PROBE_BLEND_PREVIOUS_STATES, PROBE_BURIED, PROBE_HISTORY_COEFFICIENTS,
+                   PROBE_HISTORY_MOMENTS, PROBE_IDLE, PROBE_LIST_COUNT_WORK, PROBE_LIST_HEADER, ProbeBlendParams, ProbeBlendWork, ProbeListParams,
+                   ProbeListWork)  # noqa: F401
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_PKG, "libsrt_host.so")
@@ -53,6 +56,9 @@ EXPORTS = [
     "srt_host_renderer_shade_probe_grid_depth",
     "srt_host_renderer_classify_probes", "srt_host_renderer_read_probe_states_output", "srt_host_renderer_probe_classify_work",
     "srt_host_renderer_shade_probe_grid_states",
+    "srt_host_renderer_list_probes", "srt_host_renderer_read_probe_list_output", "srt_host_renderer_probe_list_work",
+    "srt_host_renderer_trace_light_probes_listed", "srt_host_renderer_trace_probe_depth_listed", "srt_host_renderer_reset_probe_history",
+    "srt_host_renderer_blend_probes", "srt_host_renderer_read_probe_history", "srt_host_renderer_probe_blend_work",
     "srt_host_renderer_sample_budget", "srt_host_renderer_render_adaptive", "srt_host_renderer_set_sample_counts",
     "srt_host_renderer_read_sample_counts", "srt_host_renderer_adaptive_frame",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
@@ -164,6 +170,15 @@ def load_library():
     L.srt_host_renderer_probe_classify_work.argtypes = [vp, C.POINTER(ProbeClassifyWork)]
     L.srt_host_renderer_shade_probe_grid_states.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_uint32,
                                                             C.POINTER(ProbeGridParams), C.POINTER(ProbeGridDepthParams)]
+    L.srt_host_renderer_list_probes.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(ProbeListParams)]
+    L.srt_host_renderer_read_probe_list_output.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.srt_host_renderer_probe_list_work.argtypes = [vp, C.POINTER(ProbeListWork)]
+    L.srt_host_renderer_trace_light_probes_listed.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(LightProbeParams)]
+    L.srt_host_renderer_trace_probe_depth_listed.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(ProbeDepthParams)]
+    L.srt_host_renderer_reset_probe_history.argtypes = [vp, C.c_uint32, C.c_size_t, C.c_uint32]
+    L.srt_host_renderer_blend_probes.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(ProbeBlendParams)]
+    L.srt_host_renderer_read_probe_history.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float)]
+    L.srt_host_renderer_probe_blend_work.argtypes = [vp, C.POINTER(ProbeBlendWork)]
     L.srt_host_renderer_sample_budget.argtypes = [vp, C.POINTER(BudgetParams), C.POINTER(C.c_uint64)]
     L.srt_host_renderer_render_adaptive.argtypes = [vp, C.POINTER(AdaptiveParams)]
     L.srt_host_renderer_set_sample_counts.argtypes = [vp, C.c_uint32]
@@ -648,6 +663,111 @@ class Renderer:
         d = ProbeGridDepthParams(float(bias), float(min_variance), (C.c_uint32 * 2)(0, 0))
         self._ck(self.L.srt_host_renderer_shade_probe_grid_states(self._h, cptr, mptr, sptr, n, res, C.byref(p), C.byref(d) if depth else None))
         return self.probe_grid_output()
+
+    # ---- per-frame probe updates ----
+    def list_probes(self, states=None, probes=None, skip_mask=PROBE_BURIED | PROBE_IDLE, count_work=False):
+        """PathTraceRenderer::listProbes: list the probes whose (P, 4) float32 `states` record (None: the handle's current ones; then
+        `probes` says how many) has none of the `skip_mask` bits, make that list the one the listed traces read, and return its
+        4 + P uint32 words (n, P, 0, 0, the indices ascending, then 0xFFFFFFFF).  probe_list_work() reads the counts.  Waits."""
+        sptr, n = None, int(probes or 0)
+        if states is not None:
+            st = np.ascontiguousarray(states, dtype=np.float32)
+            if st.ndim != 2 or st.shape[1] != 4 or st.shape[0] < 1:
+                raise ValueError("list_probes: states %s, want (P, 4)" % (st.shape,))
+            sptr, n = st.ctypes.data_as(C.POINTER(C.c_float)), st.shape[0]
+        if n < 1:
+            raise ValueError("list_probes: give the states or their count")
+        p = ProbeListParams(int(skip_mask), PROBE_LIST_COUNT_WORK if count_work else 0, (C.c_uint32 * 2)(0, 0))
+        self._ck(self.L.srt_host_renderer_list_probes(self._h, sptr, n, C.byref(p)))
+        out = np.empty(PROBE_LIST_HEADER + n, dtype=np.uint32)
+        self._ck(self.L.srt_host_renderer_read_probe_list_output(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def probe_list_work(self):
+        """PathTraceRenderer::probeListWork: the work counts of the last list_probes(count_work=True) as a dict."""
+        w = ProbeListWork()
+        self._ck(self.L.srt_host_renderer_probe_list_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def _probe_inputs(self, what, positions, directions):
+        f = C.POINTER(C.c_float)
+        optr, np_, dptr, nk = None, 0, None, 0
+        if positions is not None:
+            o = np.ascontiguousarray(positions, dtype=np.float32)
+            if o.ndim != 2 or o.shape[1] != 4 or o.shape[0] < 1:
+                raise ValueError("%s: positions %s, want a (P, 4) array" % (what, o.shape))
+            optr, np_ = o.ctypes.data_as(f), o.shape[0]
+            self._probe_keep_o = o
+        if directions is not None:
+            if isinstance(directions, (int, np.integer)):
+                directions = light_probe_sphere(int(directions))
+            d = np.ascontiguousarray(directions, dtype=np.float32)
+            if d.ndim != 2 or d.shape[1] != 4 or d.shape[0] < 1:
+                raise ValueError("%s: directions %s, want a (K, 4) array" % (what, d.shape))
+            dptr, nk = d.ctypes.data_as(f), d.shape[0]
+            self._probe_keep_d = d
+        return optr, np_, dptr, nk
+
+    def trace_light_probes_listed(self, positions=None, directions=None, samples=16, bounces=8, seed=0, first_sample=1, reset=True, id_base=0,
+                                  normalize=False, count_work=False, radiance=False):
+        """PathTraceRenderer::traceLightProbesListed: trace_light_probes() for the probes of the last list_probes() only (positions
+        / directions None: the handle's current ones).  Enqueues; light_probe_coefficients() etc. read the outputs, in which the
+        slots of the other probes keep what they held."""
+        optr, np_, dptr, nk = self._probe_inputs("trace_light_probes_listed", positions, directions)
+        p = LightProbeParams(int(first_sample), int(samples), int(bounces), int(seed) & 0xFFFFFFFF, int(id_base) & 0xFFFFFFFF,
+                             (LIGHT_PROBE_RESET if reset else 0) | (LIGHT_PROBE_NORMALIZE if normalize else 0) |
+                             (LIGHT_PROBE_COUNT_WORK if count_work else 0), LIGHT_PROBE_COEFFICIENTS | (LIGHT_PROBE_RADIANCE if radiance else 0), 0)
+        self._ck(self.L.srt_host_renderer_trace_light_probes_listed(self._h, optr, np_, dptr, nk, C.byref(p)))
+        t = getattr(self, "_probes_traced", (0, 0))
+        self._probes_traced = (np_ or t[0], nk or t[1])
+
+    def trace_probe_depth_listed(self, positions=None, directions=None, resolution=16, sharpness=5, max_distance=10000.0, normalize=False,
+                                 count_work=False, distances=False):
+        """PathTraceRenderer::traceProbeDepthListed: trace_probe_depth() for the probes of the last list_probes() only.  Enqueues."""
+        optr, np_, dptr, nk = self._probe_inputs("trace_probe_depth_listed", positions, directions)
+        p = ProbeDepthParams(int(resolution), int(sharpness), float(max_distance),
+                             (PROBE_DEPTH_NORMALIZE if normalize else 0) | (PROBE_DEPTH_COUNT_WORK if count_work else 0),
+                             PROBE_DEPTH_MOMENTS | (PROBE_DEPTH_DISTANCES if distances else 0), 0)
+        self._ck(self.L.srt_host_renderer_trace_probe_depth_listed(self._h, optr, np_, dptr, nk, C.byref(p)))
+        t = getattr(self, "_probe_depth_traced", None) or getattr(self, "_probes_traced", (0, 0)) + (0,)
+        self._probe_depth_traced = (np_ or t[0], nk or t[1], int(resolution))
+
+    def reset_probe_history(self, probes, resolution=0):
+        """PathTraceRenderer::resetProbeHistory: size and zero-fill the coefficient history for `probes` probes and, with a
+        `resolution`, the moment history: every probe restarts at the next blend_probes()."""
+        which = PROBE_HISTORY_COEFFICIENTS | (PROBE_HISTORY_MOMENTS if resolution else 0)
+        self._ck(self.L.srt_host_renderer_reset_probe_history(self._h, which, int(probes), int(resolution)))
+        self._probe_history = (int(probes), int(resolution))
+
+    def blend_probes(self, hysteresis=0.9, fast_hysteresis=0.5, depth_hysteresis=0.9, change_threshold=0.25, moments=False, listed=False,
+                     previous_states=None, count_work=False):
+        """PathTraceRenderer::blendProbes: srt_blend_probes on the histories of reset_probe_history() with what the last traces wrote.
+        previous_states: (P, 4) float32 records to compare the current ones with (SRT_PROBE_BLEND_PREVIOUS_STATES); listed: only the
+        probes of the last list_probes().  probe_history() reads the result."""
+        sptr, n = None, 0
+        if previous_states is not None:
+            st = np.ascontiguousarray(previous_states, dtype=np.float32)
+            if st.ndim != 2 or st.shape[1] != 4 or st.shape[0] < 1:
+                raise ValueError("blend_probes: previous_states %s, want (P, 4)" % (st.shape,))
+            sptr, n = st.ctypes.data_as(C.POINTER(C.c_float)), st.shape[0]
+        p = ProbeBlendParams(float(hysteresis), float(fast_hysteresis), float(depth_hysteresis), float(change_threshold),
+                             (PROBE_BLEND_MOMENTS if moments else 0) | (PROBE_BLEND_LISTED if listed else 0) |
+                             (PROBE_BLEND_PREVIOUS_STATES if previous_states is not None else 0) | (PROBE_BLEND_COUNT_WORK if count_work else 0), 0)
+        self._ck(self.L.srt_host_renderer_blend_probes(self._h, sptr, n, C.byref(p)))
+
+    def probe_history(self, which="coefficients"):
+        """PathTraceRenderer::readProbeHistory: "coefficients": (P, 9, 4) float32; "moments": (P, R*R, 4) float32.  Waits."""
+        n, r = self._probe_history
+        bit, shape = (PROBE_HISTORY_COEFFICIENTS, (n, LIGHT_PROBE_COEFFS, 4)) if which == "coefficients" else (PROBE_HISTORY_MOMENTS, (n, r * r, 4))
+        out = np.empty(shape, dtype=np.float32)
+        self._ck(self.L.srt_host_renderer_read_probe_history(self._h, bit, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def probe_blend_work(self):
+        """PathTraceRenderer::probeBlendWork: the work counts of the last blend_probes(count_work=True) as a dict."""
+        w = ProbeBlendWork()
+        self._ck(self.L.srt_host_renderer_probe_blend_work(self._h, C.byref(w)))
+        return w.as_dict()
 
     def radiance_work(self):
         """PathTraceRenderer::radianceWork: the work counts of the last trace_radiance(count_work=True) as a dict."""

@@ -266,6 +266,29 @@ int srt_host_renderer_shade_probe_grid_states(srt_host_renderer* h, const float*
                                               uint32_t resolution, const srt_probe_grid_params* p, const srt_probe_grid_depth_params* d) {
     SRT_HOST_TRY(h, h->r->shadeProbeGridStates(coefficients, moments, states, probes, resolution, *p, d))
 }
+// per-frame probe updates on the renderer's handle (PathTraceRenderer::listProbes ... probeBlendWork: states, positions, directions
+// and previous records are copied unless NULL)
+int srt_host_renderer_list_probes(srt_host_renderer* h, const float* states, size_t probes, const srt_probe_list_params* p) {
+    SRT_HOST_TRY(h, h->r->listProbes(states, probes, *p))
+}
+int srt_host_renderer_read_probe_list_output(srt_host_renderer* h, uint32_t* dst) { SRT_HOST_TRY(h, h->r->readProbeListOutput(dst)) }
+int srt_host_renderer_probe_list_work(srt_host_renderer* h, srt_probe_list_work* out) { SRT_HOST_TRY(h, *out = h->r->probeListWork()) }
+int srt_host_renderer_trace_light_probes_listed(srt_host_renderer* h, const float* positions, size_t probes, const float* directions, size_t direction_count,
+                                                const srt_light_probe_params* p) {
+    SRT_HOST_TRY(h, h->r->traceLightProbesListed(positions, probes, directions, direction_count, *p))
+}
+int srt_host_renderer_trace_probe_depth_listed(srt_host_renderer* h, const float* positions, size_t probes, const float* directions, size_t direction_count,
+                                               const srt_probe_depth_params* p) {
+    SRT_HOST_TRY(h, h->r->traceProbeDepthListed(positions, probes, directions, direction_count, *p))
+}
+int srt_host_renderer_reset_probe_history(srt_host_renderer* h, uint32_t which, size_t probes, uint32_t resolution) {
+    SRT_HOST_TRY(h, h->r->resetProbeHistory(which, probes, resolution))
+}
+int srt_host_renderer_blend_probes(srt_host_renderer* h, const float* previous_states, size_t probes, const srt_probe_blend_params* p) {
+    SRT_HOST_TRY(h, h->r->blendProbes(previous_states, probes, *p))
+}
+int srt_host_renderer_read_probe_history(srt_host_renderer* h, uint32_t which, float* dst) { SRT_HOST_TRY(h, h->r->readProbeHistory(which, dst)) }
+int srt_host_renderer_probe_blend_work(srt_host_renderer* h, srt_probe_blend_work* out) { SRT_HOST_TRY(h, *out = h->r->probeBlendWork()) }
 // adaptive sampling on the handle's buffers as they stand (srt_sample_budget + srt_get_budget_total, srt_render_adaptive; a band
 // of [0, 0) means the renderer's own), and the two-half workflow (PathTraceRenderer::renderAdaptiveFrame; counts may be NULL)
 int srt_host_renderer_sample_budget(srt_host_renderer* h, const srt_budget_params* p, uint64_t* total) { SRT_HOST_TRY(h, *total = h->r->sampleBudget(*p)) }

@@ -401,6 +401,53 @@ void PathTraceRenderer::shadeProbeGridStates(const float* coefficients, const fl
     check(srt_shade_probe_grid_states(ctx_, &s, depth), "srt_shade_probe_grid_states");
 }
 
+void PathTraceRenderer::listProbes(const float* states, size_t probes, const srt_probe_list_params& params) {
+    if (states) check(srt_write_probe_grid_states(ctx_, states, probes), "srt_write_probe_grid_states");
+    check(srt_list_probes(ctx_, &params), "srt_list_probes");
+    probe_list_.resize(SRT_PROBE_LIST_HEADER + probes);
+    check(srt_read_probe_list_output(ctx_, probe_list_.data()), "srt_read_probe_list_output");
+    check(srt_write_probe_list(ctx_, probe_list_.data(), probe_list_.size()), "srt_write_probe_list");
+}
+
+void PathTraceRenderer::readProbeListOutput(uint32_t* dst) { check(srt_read_probe_list_output(ctx_, dst), "srt_read_probe_list_output"); }
+
+srt_probe_list_work PathTraceRenderer::probeListWork() {
+    srt_probe_list_work w{};
+    check(srt_get_probe_list_work(ctx_, &w), "srt_get_probe_list_work");
+    return w;
+}
+
+void PathTraceRenderer::traceLightProbesListed(const float* positions, size_t probes, const float* directions, size_t direction_count,
+                                               const srt_light_probe_params& params) {
+    if (positions) check(srt_write_light_probes(ctx_, positions, probes), "srt_write_light_probes");
+    if (directions) check(srt_write_light_probe_directions(ctx_, directions, direction_count), "srt_write_light_probe_directions");
+    check(srt_trace_light_probes_listed(ctx_, &params), "srt_trace_light_probes_listed");
+}
+
+void PathTraceRenderer::traceProbeDepthListed(const float* positions, size_t probes, const float* directions, size_t direction_count,
+                                              const srt_probe_depth_params& params) {
+    if (positions) check(srt_write_light_probes(ctx_, positions, probes), "srt_write_light_probes");
+    if (directions) check(srt_write_light_probe_directions(ctx_, directions, direction_count), "srt_write_light_probe_directions");
+    check(srt_trace_probe_depth_listed(ctx_, &params), "srt_trace_probe_depth_listed");
+}
+
+void PathTraceRenderer::resetProbeHistory(uint32_t which, size_t probes, uint32_t resolution) {
+    check(srt_reset_probe_history(ctx_, which, probes, resolution), "srt_reset_probe_history");
+}
+
+void PathTraceRenderer::blendProbes(const float* previous_states, size_t probes, const srt_probe_blend_params& params) {
+    if (previous_states) check(srt_write_probe_previous_states(ctx_, previous_states, probes), "srt_write_probe_previous_states");
+    check(srt_blend_probes(ctx_, &params), "srt_blend_probes");
+}
+
+void PathTraceRenderer::readProbeHistory(uint32_t which, float* dst) { check(srt_read_probe_history(ctx_, which, dst), "srt_read_probe_history"); }
+
+srt_probe_blend_work PathTraceRenderer::probeBlendWork() {
+    srt_probe_blend_work w{};
+    check(srt_get_probe_blend_work(ctx_, &w), "srt_get_probe_blend_work");
+    return w;
+}
+
 uint64_t PathTraceRenderer::sampleBudget(const srt_budget_params& params) {
     check(srt_sample_budget(ctx_, &params), "srt_sample_budget");
     uint64_t total = 0;

@@ -207,6 +207,23 @@ class PathTraceRenderer {
     srt_probe_classify_work probeClassifyWork();
     void shadeProbeGridStates(const float* coefficients, const float* moments, const float* states, size_t probes, uint32_t resolution,
                               const srt_probe_grid_params& params, const srt_probe_grid_depth_params* depth);
+    // Per-frame probe updates (srt_list_probes, the listed traces, srt_blend_probes).  listProbes copies `probes` state records (NULL:
+    // the handle's current ones), lists the probes without a params.skip_mask bit, reads the 4 + probes words back and makes them
+    // the list the listed traces read (through the host: waits); readProbeListOutput copies them again; probeListWork returns the
+    // counts of a call that had SRT_PROBE_LIST_COUNT_WORK.  traceLightProbesListed / traceProbeDepthListed are traceLightProbes /
+    // traceProbeDepth for the listed probes only (positions / directions NULL: the handle's current ones); the read and work calls
+    // of the parents serve them.  resetProbeHistory sizes and zero-fills the handle's own histories (SRT_PROBE_HISTORY_* bits);
+    // blendProbes folds the last traces' COEFFICIENTS (and MOMENTS) into them, copying `probes` previous records first unless
+    // NULL; readProbeHistory waits and copies one history; probeBlendWork returns the counts of a counting blend.
+    void listProbes(const float* states, size_t probes, const srt_probe_list_params& params);
+    void readProbeListOutput(uint32_t* dst);
+    srt_probe_list_work probeListWork();
+    void traceLightProbesListed(const float* positions, size_t probes, const float* directions, size_t direction_count, const srt_light_probe_params& params);
+    void traceProbeDepthListed(const float* positions, size_t probes, const float* directions, size_t direction_count, const srt_probe_depth_params& params);
+    void resetProbeHistory(uint32_t which, size_t probes, uint32_t resolution);
+    void blendProbes(const float* previous_states, size_t probes, const srt_probe_blend_params& params);
+    void readProbeHistory(uint32_t which, float* dst);
+    srt_probe_blend_work probeBlendWork();
     // Adaptive sampling (srt_sample_budget, srt_render_adaptive), on the handle's buffers as they stand.  sampleBudget turns the
     // variance buffer, the sample counts, the accumulator and the guides into the per-pixel budget and returns its sum (waits).
     // renderAdaptive enqueues the adaptive render with the renderer's scene and camera; a band of [0, 0) means the renderer's
@@ -336,6 +353,7 @@ class PathTraceRenderer {
     std::vector<std::vector<float>> mesh_vertices_;     // ... and this mesh geometry (UpdateScene takes no other)
     std::vector<std::vector<uint32_t>> mesh_indices_;
     bool SameMeshes(const std::vector<srt_mesh>& meshes) const;
+    std::vector<uint32_t> probe_list_;  // listProbes: the list on its way from the list output to the list for tracing
     bool temporal_reset_ = true;    // the next RenderTemporalFrame drops the history
     uint32_t temporal_frames_ = 0;  // RenderTemporalFrame calls so far (the seed offset)
     bool first_frame_ = true;

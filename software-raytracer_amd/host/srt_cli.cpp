@@ -284,10 +284,27 @@ struct ProbeClassifyOptions {
     int steps = 8;
     std::string out;
 };
+// --move-object IDX:DX,DY,DZ: before every frame but the first, DX, DY, DZ are added to the position of object IDX
+struct ObjectMove {
+    size_t index;
+    float step[3];
+};
 
-static int shade_probe_grid_file(const Scene& scene, int device, int W, int H, int fov, const srt_probe_grid& grid, int directions, int samples, int bounces,
+// --probe-update FRAMES (with --probe-classify): the per-frame route in place of the one trace: the classification once, the list
+// of active probes once (srt_list_probes), then FRAMES times a listed trace of --probe-samples N samples with seed = the frame
+// number (and, with --probe-depth, a listed depth trace) and srt_blend_probes with --probe-hysteresis H for both hystereses; the
+// frame is shaded from the histories.  With --move-object the objects move before every frame but the first: srt_update_scene, the
+// classification and the list again, the traces at the new positions, and the blend with SRT_PROBE_BLEND_PREVIOUS_STATES against the
+// records of the frame before, so that a probe that moved, or went into or came out of an object, restarts.
+struct ProbeUpdateOptions {
+    int frames = 0;  // 0: no --probe-update
+    int samples = 1;
+    float hysteresis = 0.9f;
+};
+
+static int shade_probe_grid_file(Scene& scene, int device, int W, int H, int fov, const srt_probe_grid& grid, int directions, int samples, int bounces,
                                  unsigned seed, uint32_t flags, bool hemisphere, const std::string& out, const ProbeDepthOptions& depth,
-                                 const ProbeClassifyOptions& classify) {
+                                 const ProbeClassifyOptions& classify, const ProbeUpdateOptions& update, const std::vector<ObjectMove>& moves) {
     const size_t np = (size_t)grid.counts[0] * (size_t)grid.counts[1] * (size_t)grid.counts[2];
     std::vector<float> pos(4 * np), dir(4 * (size_t)directions);
     if (srt_probe_grid_positions(&grid, pos.data()) != SRT_OK) {
@@ -305,34 +322,82 @@ static int shade_probe_grid_file(const Scene& scene, int device, int W, int H, i
         srt_light_probe_params_default(&lp);
         lp.sample_count = (uint32_t)samples, lp.max_bounces = bounces, lp.seed = seed;
         std::vector<float> states;
-        if (classify.on) {  // the states first: the probes are traced where the classification puts them
-            srt_probe_classify_params cp{};
-            srt_probe_classify_params_default(&cp);
-            cp.clearance = classify.clearance, cp.max_offset = classify.max_offset, cp.steps = (uint32_t)classify.steps;
-            cp.flags = classify.relocate ? SRT_PROBE_CLASSIFY_RELOCATE : 0u;
-            cp.outputs = SRT_PROBE_STATE_RECORDS | SRT_PROBE_STATE_POSITIONS;
-            r.setProbeGrid(grid);
+        srt_probe_classify_params cp{};
+        srt_probe_classify_params_default(&cp);
+        cp.clearance = classify.clearance, cp.max_offset = classify.max_offset, cp.steps = (uint32_t)classify.steps;
+        cp.flags = classify.relocate ? SRT_PROBE_CLASSIFY_RELOCATE : 0u;
+        cp.outputs = SRT_PROBE_STATE_RECORDS | SRT_PROBE_STATE_POSITIONS;
+        auto classify_now = [&]() {  // the records, and the positions the probes are traced at
             r.classifyProbes(dir.data(), (size_t)directions, cp);
             states.resize(4 * np);
             r.readProbeStatesOutput(SRT_PROBE_STATE_RECORDS, states.data());
             r.readProbeStatesOutput(SRT_PROBE_STATE_POSITIONS, pos.data());
-            if (!classify.out.empty() && !write_floats(classify.out, states)) return 1;
+        };
+        if (classify.on) {  // the states first: the probes are traced where the classification puts them
+            r.setProbeGrid(grid);
+            classify_now();
+            if (!classify.out.empty() && !moves.size() && !write_floats(classify.out, states)) return 1;
         }
-        r.traceLightProbes(pos.data(), np, dir.data(), (size_t)directions, lp);
-        std::vector<float> coeff(np * 9 * 4);
-        r.readLightProbeOutput(SRT_LIGHT_PROBE_COEFFICIENTS, coeff.data());
+        std::vector<float> coeff(np * 9 * 4), moments;
+        srt_probe_depth_params dp{};
+        srt_probe_depth_params_default(&dp);
+        if (depth.resolution) {
+            dp.resolution = (uint32_t)depth.resolution, dp.sharpness = (uint32_t)depth.sharpness, dp.max_distance = depth.max_distance;
+            moments.resize(np * (size_t)depth.resolution * depth.resolution * 4);
+        }
+        if (update.frames) {  // (classify.on: main() has seen to it)
+            srt_probe_list_params ls{};
+            srt_probe_list_params_default(&ls);
+            r.listProbes(states.data(), np, ls);
+            r.resetProbeHistory(SRT_PROBE_HISTORY_COEFFICIENTS | (depth.resolution ? SRT_PROBE_HISTORY_MOMENTS : 0u), np, (uint32_t)depth.resolution);
+            srt_probe_blend_params bp{};
+            srt_probe_blend_params_default(&bp);
+            bp.hysteresis = bp.depth_hysteresis = update.hysteresis;
+            if (bp.fast_hysteresis > update.hysteresis) bp.fast_hysteresis = update.hysteresis;
+            bp.flags = SRT_PROBE_BLEND_LISTED | (depth.resolution ? SRT_PROBE_BLEND_MOMENTS : 0u);
+            lp.sample_count = (uint32_t)update.samples;
+            std::vector<float> previous;
+            for (int f = 1; f <= update.frames; ++f) {
+                const bool moved = f > 1 && !moves.empty();
+                if (moved) {  // the objects move; the classification and the list follow, the records of the frame before are kept
+                    for (const auto& m : moves) {
+                        float* p = scene.Objects()[m.index].position;
+                        for (int a = 0; a < 3; ++a) p[a] = p[a] + m.step[a];
+                    }
+                    r.UpdateScene(scene);
+                    previous = states;
+                    classify_now();
+                    r.listProbes(states.data(), np, ls);
+                }
+                lp.seed = (uint32_t)f;
+                r.traceLightProbesListed(f == 1 || moved ? pos.data() : nullptr, np, f == 1 ? dir.data() : nullptr, (size_t)directions, lp);
+                if (depth.resolution) r.traceProbeDepthListed(nullptr, np, nullptr, (size_t)directions, dp);
+                srt_probe_blend_params b = bp;
+                if (moved) b.flags |= SRT_PROBE_BLEND_PREVIOUS_STATES | SRT_PROBE_BLEND_COUNT_WORK;
+                r.blendProbes(moved ? previous.data() : nullptr, np, b);
+                if (moved) {
+                    const srt_probe_blend_work w = r.probeBlendWork();
+                    std::fprintf(stderr, "probe update frame %d: %llu probes blended, %llu restarted, %llu changed\n", f, (unsigned long long)w.probes,
+                                 (unsigned long long)w.restarted, (unsigned long long)w.changed);
+                }
+            }
+            if (!classify.out.empty() && moves.size() && !write_floats(classify.out, states)) return 1;  // (the records of the last frame)
+            r.readProbeHistory(SRT_PROBE_HISTORY_COEFFICIENTS, coeff.data());
+            if (depth.resolution) r.readProbeHistory(SRT_PROBE_HISTORY_MOMENTS, moments.data());
+        } else {
+            r.traceLightProbes(pos.data(), np, dir.data(), (size_t)directions, lp);
+            r.readLightProbeOutput(SRT_LIGHT_PROBE_COEFFICIENTS, coeff.data());
+        }
         srt_probe_grid_params sp{};
         srt_probe_grid_params_default(&sp);
         sp.row_begin = 0, sp.row_end = H, sp.flags = flags;
         if (hemisphere) sp.band_weight[0] = 1.0f, sp.band_weight[1] = 0.5f, sp.band_weight[2] = 0.0f;
         r.setProbeGrid(grid);
         if (depth.resolution) {
-            srt_probe_depth_params dp{};
-            srt_probe_depth_params_default(&dp);
-            dp.resolution = (uint32_t)depth.resolution, dp.sharpness = (uint32_t)depth.sharpness, dp.max_distance = depth.max_distance;
-            r.traceProbeDepth(pos.data(), np, dir.data(), (size_t)directions, dp);
-            std::vector<float> moments(np * (size_t)depth.resolution * depth.resolution * 4);
-            r.readProbeDepthOutput(SRT_PROBE_DEPTH_MOMENTS, moments.data());
+            if (!update.frames) {
+                r.traceProbeDepth(pos.data(), np, dir.data(), (size_t)directions, dp);
+                r.readProbeDepthOutput(SRT_PROBE_DEPTH_MOMENTS, moments.data());
+            }
             if (!depth.out.empty() && !write_floats(depth.out, moments)) return 1;
             srt_probe_grid_depth_params gd{};
             srt_probe_grid_depth_params_default(&gd);
@@ -373,6 +438,7 @@ static void usage() {
                  "                  [--probe-visibility] [--probe-normal-weight] [--probe-albedo] [--probe-hemisphere] [--width W] [--height H] ...\n"
                  "                  [--probe-depth R [--probe-depth-sharpness S] [--probe-depth-max D] [--probe-depth-bias B] [--probe-depth-out FILE]]\n"
                  "                  [--probe-classify [--probe-relocate] [--probe-clearance C] [--probe-max-offset F] [--probe-steps M] [--states-out FILE]]\n"
+                 "                  [--probe-update FRAMES [--probe-hysteresis H] [--probe-samples N]]\n"
                  "       srt_render --scene FILE --adaptive ROUNDS [--adaptive-threshold T] [--adaptive-max M] [--counts-out FILE] [--spp N] ...\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
@@ -439,6 +505,12 @@ static void usage() {
                  "             spacing, default 0.2) to a surface are moved by at most --probe-max-offset F (0..0.5, default 0.45) in\n"
                  "             --probe-steps M (1..64, default 8) lengths, and probes and depth maps are traced where they stand;\n"
                  "             --states-out receives the probes' records (offset, state bits); not with --probe-visibility\n"
+                 "  --probe-update FRAMES: with --probe-classify, the per-frame route: the active probes are listed once (srt_list_probes), then\n"
+                 "             FRAMES (1..4096) times a listed trace of --probe-samples N (1..4096, default 1) samples with seed = the frame number\n"
+                 "             is blended into a history (srt_blend_probes, --probe-hysteresis H in [0, 1), default 0.9), and the frame is shaded\n"
+                 "             from the history; with --probe-depth the depth maps are traced listed and blended too; with --move-object the\n"
+                 "             objects move before every frame but the first, the grid is classified and listed again, and probes whose record\n"
+                 "             changed restart (SRT_PROBE_BLEND_PREVIOUS_STATES)\n"
                  "  --adaptive ROUNDS: adaptive sampling in place of the uniform frame: an even --spp is the uniform seed, split into two\n"
                  "             independently seeded halves; then ROUNDS (1..64) rounds of srt_variance, srt_sample_budget and srt_render_adaptive\n"
                  "             on both halves, and the mean of the halves goes to --out; the frame's total samples are printed on stderr;\n"
@@ -473,6 +545,8 @@ int main(int argc, char** argv) {
     bool probe_depth_given = false, probe_depth_option = false;
     ProbeClassifyOptions probe_classify;
     bool probe_classify_option = false;
+    ProbeUpdateOptions probe_update;
+    bool probe_update_given = false, probe_update_option = false;
     int adaptive = 0, adaptive_max = 0;
     bool adaptive_given = false, adaptive_threshold_given = false, adaptive_max_given = false;
     float adaptive_threshold = 0;
@@ -489,10 +563,6 @@ int main(int argc, char** argv) {
     bool mirror_history = false, mirror_radius_given = false;
     float mirror_radius = 2.0f;
     float move[3] = {0, 0, 0}, turn_deg = 0;
-    struct ObjectMove {
-        size_t index;
-        float step[3];
-    };
     std::vector<ObjectMove> object_moves;
     int W = 1280, H = 720, spp = 32, bounces = 2, fov = 55, device = 0;  // Raytracer.cpp:26-27,31-32
     unsigned seed = 0;
@@ -559,6 +629,9 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--probe-max-offset")) probe_classify.max_offset = std::strtof(need("--probe-max-offset"), nullptr), probe_classify_option = true;
         else if (!std::strcmp(argv[i], "--probe-steps")) probe_classify.steps = std::atoi(need("--probe-steps")), probe_classify_option = true;
         else if (!std::strcmp(argv[i], "--states-out")) probe_classify.out = need("--states-out"), probe_classify_option = true;
+        else if (!std::strcmp(argv[i], "--probe-update")) probe_update.frames = std::atoi(need("--probe-update")), probe_update_given = true;
+        else if (!std::strcmp(argv[i], "--probe-hysteresis")) probe_update.hysteresis = std::strtof(need("--probe-hysteresis"), nullptr), probe_update_option = true;
+        else if (!std::strcmp(argv[i], "--probe-samples")) probe_update.samples = std::atoi(need("--probe-samples")), probe_update_option = true;
         else if (!std::strcmp(argv[i], "--adaptive")) adaptive = std::atoi(need("--adaptive")), adaptive_given = true;
         else if (!std::strcmp(argv[i], "--adaptive-threshold")) adaptive_threshold = std::strtof(need("--adaptive-threshold"), nullptr), adaptive_threshold_given = true;
         else if (!std::strcmp(argv[i], "--adaptive-max")) adaptive_max = std::atoi(need("--adaptive-max")), adaptive_max_given = true;
@@ -608,8 +681,8 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
-    if (!object_moves.empty() && !temporal) {
-        std::fprintf(stderr, "--move-object needs --temporal\n");
+    if (!object_moves.empty() && !temporal && !probe_update_given) {
+        std::fprintf(stderr, "--move-object needs --temporal or --probe-update\n");
         return 2;
     }
     if (refit && object_moves.empty()) {
@@ -656,6 +729,17 @@ int main(int argc, char** argv) {
         if (!(probe_classify.clearance > 0.0f) || !(probe_classify.clearance <= 0.5f) || !(probe_classify.max_offset > 0.0f) || !(probe_classify.max_offset <= 0.5f) ||
             probe_classify.steps < 1 || probe_classify.steps > 64) {
             std::fprintf(stderr, "--probe-classify: --probe-clearance and --probe-max-offset take a value in (0, 0.5], --probe-steps 1..64\n");
+            return 2;
+        }
+    }
+    if (probe_update_given || probe_update_option) {
+        if (!probe_update_given || !probe_classify.on || probe_grid_arg.empty()) {
+            std::fprintf(stderr, "--probe-update and its options go with --probe-grid G --probe-classify: --probe-update FRAMES [--probe-hysteresis H] [--probe-samples N]\n");
+            return 2;
+        }
+        if (probe_update.frames < 1 || probe_update.frames > 4096 || probe_update.samples < 1 || probe_update.samples > 4096 || !(probe_update.hysteresis >= 0.0f) ||
+            !(probe_update.hysteresis < 1.0f)) {
+            std::fprintf(stderr, "--probe-update takes 1..4096 frames, --probe-samples 1..4096, --probe-hysteresis a value in [0, 1)\n");
             return 2;
         }
     }
@@ -800,7 +884,7 @@ int main(int argc, char** argv) {
         return shade_probe_grid_file(scene, device, W, H, fov, probe_grid, probe_grid_directions, radiance_given ? radiance : 16, bounces, seed,
                                      (probe_visibility ? SRT_PROBE_GRID_VISIBILITY : 0u) | (probe_normal_weight ? SRT_PROBE_GRID_NORMAL_WEIGHT : 0u) |
                                          (probe_albedo ? SRT_PROBE_GRID_ALBEDO : 0u),
-                                     probe_hemisphere, irradiance_out, probe_depth, probe_classify);
+                                     probe_hemisphere, irradiance_out, probe_depth, probe_classify, probe_update, object_moves);
     if (!probes_in.empty()) return trace_probe_file(scene, device, probes_in, probe_directions, probes_out, probe_radiance_out, radiance_given ? radiance : 16, bounces, seed);
     if (!rays_in.empty()) return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize, rays_any_hit, radiance_given ? radiance : 0, bounces, seed);
     auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {
