@@ -531,6 +531,29 @@ int ray_output_released(srt_context* ctx, int i) {
     return SRT_OK;
 }
 
+// ... of own output `i` of a light-probe, probe-depth or probe-state call: `rule` is the state's *_output_released
+template <class S>
+int probe_output_released(srt_context* ctx, void (*rule)(S&, int, const void*), S& state, int i, const void* own) {
+    if (const int rc = finish_stream(ctx)) return rc;
+    rule(state, i, own);
+    return SRT_OK;
+}
+
+// Every srt_write_* of a probe input, its range checked by the caller: `count` elements of `elem_bytes` into the own array, which
+// becomes the current one (a state that keeps more than the count does so after this returns SRT_OK)
+template <class T>
+int write_probe_input(srt_context* ctx, srt::LightProbeInput& in, DeviceBuffer<T>& own, const void* src, size_t count, size_t elem_bytes) {
+    if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it may be re-allocated below)
+    const size_t bytes = count * elem_bytes;
+    if (own.bytes() < bytes) {
+        in.own_count = 0;  // (a failed allocation leaves no own array)
+        SRT_HIP(ctx, own.ensure(bytes));
+    }
+    SRT_HIP(ctx, hipMemcpy(own, src, bytes, hipMemcpyHostToDevice));
+    srt::light_probe_written(in, count);
+    return SRT_OK;
+}
+
 // The tail of every srt_read_*: `src` is what the output's read rule gave (NULL: refused with `why`, which may print `output`).
 int read_slot(srt_context* ctx, const void* src, void* dst, size_t bytes, const char* why, uint32_t output = 0) {
     if (!src) return fail(ctx, SRT_ERR_STATE, why, output);
@@ -552,10 +575,14 @@ int read_work(srt_context* ctx, const DeviceBuffer<unsigned long long>& d, unsig
     return SRT_OK;
 }
 
-// the list the listed traces and a listed blend read: the bound one, else the own one
-const uint32_t* current_probe_list(const srt_context* ctx) {
-    return ctx->probe_update.list.bound ? (const uint32_t*)ctx->probe_update.list.bound : (const uint32_t*)ctx->d_probe_list;
+// the array a call reads an input from: the caller's bound one, else the handle's own
+template <class T>
+const T* current(const srt::LightProbeInput& in, const DeviceBuffer<T>& own) {
+    return in.bound ? (const T*)in.bound : (const T*)own;
 }
+
+// the list the listed traces and a listed blend read
+const uint32_t* current_probe_list(const srt_context* ctx) { return current(ctx->probe_update.list, ctx->d_probe_list); }
 
 size_t frame_pixels(const srt_context* ctx) { return (size_t)ctx->width * (size_t)ctx->height; }
 
@@ -2148,19 +2175,11 @@ static_assert(SRT_LIGHT_PROBE_RESET == srt::LIGHT_PROBE_FLAG_RESET && SRT_LIGHT_
               srt::LP_WORK_N == 6,
               "srt_light_probes_host.h, srt_light_probes.hip.h and srt_pathtrace.h disagree");
 
-// srt_write_light_probes / srt_write_light_probe_directions: `count` float4 into the own array, which becomes the current one
+// srt_write_light_probes / srt_write_light_probe_directions / srt_write_probe_previous_states: 1 .. limit float4
 static int write_light_probe_input(srt_context* ctx, srt::LightProbeInput& in, DeviceBuffer<float4>& own, const float* src, size_t count, size_t limit,
                                    const char* who) {
     if (count < 1 || count > limit) return fail(ctx, SRT_ERR_INVALID_ARG, "%s: %zu elements: want 1 .. %zu", who, count, limit);
-    if (const int rc = finish_stream(ctx)) return rc;  // (traces in flight read the own array; it may be re-allocated below)
-    const size_t bytes = count * sizeof(float4);
-    if (own.bytes() < bytes) {
-        in.own_count = 0;  // (a failed allocation leaves no own array)
-        SRT_HIP(ctx, own.ensure(bytes));
-    }
-    SRT_HIP(ctx, hipMemcpy(own, src, bytes, hipMemcpyHostToDevice));
-    srt::light_probe_written(in, count);
-    return SRT_OK;
+    return write_probe_input(ctx, in, own, src, count, sizeof(float4));
 }
 
 int srt_write_light_probes(srt_context* ctx, const float* positions, size_t count) {
@@ -2198,13 +2217,6 @@ int srt_light_probe_params_default(srt_light_probe_params* out) {
     return SRT_OK;
 }
 
-// ... in front of the re-allocation of own light-probe output `i`: earlier traces may still be writing it
-static int light_probe_output_released(srt_context* ctx, int i) {
-    if (const int rc = finish_stream(ctx)) return rc;
-    srt::light_probe_output_released(ctx->probes, i, (void*)ctx->d_probe_out_own[i]);
-    return SRT_OK;
-}
-
 // srt_trace_light_probes (listed == false) and srt_trace_light_probes_listed: one body.  The listed call is sized for P as the
 // unlisted one is (the grid, the sample scratch, the partial buffer): the count of the list stays on the device.
 static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t, bool listed, const char* who) {
@@ -2226,7 +2238,7 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
     for (int i = 0; i < srt::LIGHT_PROBE_SLOTS; ++i)
         if (t->outputs & (1u << i))
             SRT_WRITE_TARGET_AFTER(ctx, ctx->probe_out[i], ctx->d_probe_out_own[i], srt::light_probe_elems(i, np, nk) * sizeof(float4), dst[i],
-                                   light_probe_output_released(ctx, i));
+                                   probe_output_released(ctx, srt::light_probe_output_released, ctx->probes, i, ctx->d_probe_out_own[i]));
     const size_t partial = coefficients ? srt::light_probe_partial_bytes(np, nk) : 0;
     if (ctx->d_probe_partial.bytes() < partial) {
         if (const int rc = finish_stream(ctx)) return rc;
@@ -2250,8 +2262,8 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
         if (const int rc = zero_work(ctx, ctx->d_probe_work, srt::LP_WORK_N)) return rc;
     }
     srt::LightProbeIO io{};
-    io.position = ctx->probes.positions.bound ? (const float4*)ctx->probes.positions.bound : (const float4*)ctx->d_probe_position;
-    io.direction = ctx->probes.directions.bound ? (const float4*)ctx->probes.directions.bound : (const float4*)ctx->d_probe_direction;
+    io.position = current(ctx->probes.positions, ctx->d_probe_position);
+    io.direction = current(ctx->probes.directions, ctx->d_probe_direction);
     io.probes = (uint32_t)np, io.directions = (uint32_t)nk, io.blocks = (uint32_t)J;
     io.normalize = (t->flags & SRT_LIGHT_PROBE_NORMALIZE) ? 1u : 0u;
     io.id_base = t->id_base;
@@ -2365,15 +2377,7 @@ int srt_write_probe_grid_coefficients(srt_context* ctx, const float* coefficient
     if (!ctx || !coefficients) return SRT_ERR_INVALID_ARG;
     if (probes < 1 || probes > srt::PROBE_GRID_MAX_PROBES)
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_write_probe_grid_coefficients: %zu probes: want 1 .. 2^30", probes);
-    if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it may be re-allocated below)
-    const size_t bytes = probes * (size_t)srt::PG_COEFFS * sizeof(float4);
-    if (ctx->d_probe_grid_coefficients.bytes() < bytes) {
-        ctx->probe_grid.coefficients.own_count = 0;  // (a failed allocation leaves no own array)
-        SRT_HIP(ctx, ctx->d_probe_grid_coefficients.ensure(bytes));
-    }
-    SRT_HIP(ctx, hipMemcpy(ctx->d_probe_grid_coefficients, coefficients, bytes, hipMemcpyHostToDevice));
-    srt::light_probe_written(ctx->probe_grid.coefficients, probes);
-    return SRT_OK;
+    return write_probe_input(ctx, ctx->probe_grid.coefficients, ctx->d_probe_grid_coefficients, coefficients, probes, srt::PG_COEFFS * sizeof(float4));
 }
 
 int srt_bind_probe_grid_coefficients(srt_context* ctx, const void* d_ptr, size_t probes) {
@@ -2383,16 +2387,28 @@ int srt_bind_probe_grid_coefficients(srt_context* ctx, const void* d_ptr, size_t
     return SRT_OK;
 }
 
-int srt_shade_probe_grid(srt_context* ctx, const srt_probe_grid_params* s) {
-    if (!ctx || !s) return SRT_ERR_INVALID_ARG;
+// srt_shade_probe_grid, srt_shade_probe_grid_depth (`d` given) and srt_shade_probe_grid_states (`d` given or NULL): one body.  The
+// entry points have checked ctx, s and, where the call requires it, d.
+enum ProbeGridShading { PG_SHADE_QUERY, PG_SHADE_DEPTH, PG_SHADE_STATES };
+static int shade_probe_grid(srt_context* ctx, const char* who, const srt_probe_grid_params* s, const srt_probe_grid_depth_params* d, ProbeGridShading which) {
     srt::ProbeGridCall call;
     memcpy(&call, s, sizeof call);
+    srt::ProbeGridDepthCall dcall{};
+    if (d) memcpy(&dcall, d, sizeof dcall);
     bool present[srt::PROBE_GRID_GUIDES];
     for (int i = 0; i < srt::PROBE_GRID_GUIDES; ++i) present[i] = current(ctx->gbuf[i], ctx->d_gbuf_own[i]) != nullptr;
     const char* why = "";
-    if (const srt::RaysStatus rs = srt::probe_grid_check_shade(ctx->probe_grid, call, ctx->scene_set, ctx->height, present, &why))
-        return fail(ctx, (int)rs, "srt_shade_probe_grid: %s (rows [%d,%d) of %d, flags 0x%x, band_weight %g %g %g, reserved %u %u)", why, s->row_begin, s->row_end,
-                    ctx->height, s->flags, (double)s->band_weight[0], (double)s->band_weight[1], (double)s->band_weight[2], s->reserved[0], s->reserved[1]);
+    const srt::RaysStatus rs =
+        which == PG_SHADE_QUERY   ? srt::probe_grid_check_shade(ctx->probe_grid, call, ctx->scene_set, ctx->height, present, &why)
+        : which == PG_SHADE_DEPTH ? srt::probe_grid_depth_check_shade(ctx->probe_grid, ctx->probe_grid_depth, call, dcall, ctx->scene_set, ctx->height, present, &why)
+                                  : srt::probe_grid_states_check_shade(ctx->probe_grid, ctx->probe_grid_depth, ctx->probe_states, call, d ? &dcall : nullptr,
+                                                                       ctx->scene_set, ctx->height, present, &why);
+    if (rs) {
+        char depth[96] = "";
+        if (d) snprintf(depth, sizeof depth, "; bias %g, min_variance %g, reserved %u %u", (double)d->bias, (double)d->min_variance, d->reserved[0], d->reserved[1]);
+        return fail(ctx, (int)rs, "%s: %s (rows [%d,%d) of %d, flags 0x%x, band_weight %g %g %g, reserved %u %u%s)", who, why, s->row_begin, s->row_end, ctx->height,
+                    s->flags, (double)s->band_weight[0], (double)s->band_weight[1], (double)s->band_weight[2], s->reserved[0], s->reserved[1], depth);
+    }
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const bool count = (s->flags & SRT_PROBE_GRID_COUNT_WORK) != 0;
     float4* dst = nullptr;
@@ -2401,23 +2417,43 @@ int srt_shade_probe_grid(srt_context* ctx, const srt_probe_grid_params* s) {
         if (const int rc = zero_work(ctx, ctx->d_probe_grid_work, srt::PG_WORK_N)) return rc;
     }
     srt::KernelParams K;
-    const KernelSetup ks = scene_kernel_params(ctx, s->row_begin, s->row_end, K);
+    KernelSetup ks = scene_kernel_params(ctx, s->row_begin, s->row_end, K);
+    void (*kernel)(srt::KernelParams, srt::ProbeGridIO);
+    if (which == PG_SHADE_QUERY) {
+        kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::probe_grid_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    } else {
+        ks.lds_bytes = 0;  // (the kernel traces nothing: no scene image, and its own LDS is static)
+        kernel = which == PG_SHADE_DEPTH ? (count ? srt::probe_grid_depth_kernel<true> : srt::probe_grid_depth_kernel<false>)
+                 : d                     ? (count ? srt::probe_grid_states_kernel<true, true> : srt::probe_grid_states_kernel<true, false>)
+                                         : (count ? srt::probe_grid_states_kernel<false, true> : srt::probe_grid_states_kernel<false, false>);
+    }
     const srt::ProbeGrid& g = ctx->probe_grid.grid;
     srt::ProbeGridIO io{};
     io.object = (const int32_t*)current(ctx->gbuf[0], ctx->d_gbuf_own[0]);
     io.normal_depth = (const float4*)current(ctx->gbuf[1], ctx->d_gbuf_own[1]);
     io.position = (const float4*)current(ctx->gbuf[2], ctx->d_gbuf_own[2]);
     io.albedo = (s->flags & SRT_PROBE_GRID_ALBEDO) ? (const float4*)current(ctx->gbuf[3], ctx->d_gbuf_own[3]) : nullptr;
-    io.coefficients = ctx->probe_grid.coefficients.bound ? (const float4*)ctx->probe_grid.coefficients.bound : (const float4*)ctx->d_probe_grid_coefficients;
+    io.coefficients = current(ctx->probe_grid.coefficients, ctx->d_probe_grid_coefficients);
     io.out = dst;
     for (int a = 0; a < 3; ++a) io.origin[a] = g.origin[a], io.spacing[a] = g.spacing[a], io.counts[a] = g.counts[a], io.band_weight[a] = s->band_weight[a];
-    io.visibility = (s->flags & SRT_PROBE_GRID_VISIBILITY) ? 1u : 0u;
+    io.visibility = (s->flags & SRT_PROBE_GRID_VISIBILITY) ? 1u : 0u;  // (the rules of the other two calls refuse the flag)
     io.normal_weight = (s->flags & SRT_PROBE_GRID_NORMAL_WEIGHT) ? 1u : 0u;
     io.work = count ? (unsigned long long*)ctx->d_probe_grid_work : nullptr;
-    if (const int rc = launch_tiles(ctx, SRT_KERNEL_LDS_MESH_COUNT(srt::probe_grid_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count), ks, K, io)) return rc;
+    if (which == PG_SHADE_STATES) io.states = current(ctx->probe_states.states, ctx->d_probe_grid_states);
+    if (d) {
+        io.depth = current(ctx->probe_grid_depth.moments, ctx->d_probe_grid_depth);
+        io.resolution = ctx->probe_grid_depth.resolution();
+        io.bias = d->bias, io.min_variance = d->min_variance;
+    }
+    if (const int rc = launch_tiles(ctx, kernel, ks, K, io)) return rc;
     ctx->probe_grid_out.wrote(dst);
     srt::probe_grid_shaded(ctx->probe_grid, s->flags);
     return SRT_OK;
+}
+
+int srt_shade_probe_grid(srt_context* ctx, const srt_probe_grid_params* s) {
+    if (!ctx || !s) return SRT_ERR_INVALID_ARG;
+    return shade_probe_grid(ctx, "srt_shade_probe_grid", s, nullptr, PG_SHADE_QUERY);
 }
 
 int srt_bind_probe_grid_output(srt_context* ctx, void* d_float4) {
@@ -2465,13 +2501,6 @@ int srt_probe_depth_texels(uint32_t resolution, float* dst) {
     return SRT_OK;
 }
 
-// ... in front of the re-allocation of own probe-depth output `i`: earlier traces may still be writing it
-static int probe_depth_output_released(srt_context* ctx, int i) {
-    if (const int rc = finish_stream(ctx)) return rc;
-    srt::probe_depth_output_released(ctx->probe_depth, i, (void*)ctx->d_probe_depth_own[i]);
-    return SRT_OK;
-}
-
 // srt_trace_probe_depth (listed == false) and srt_trace_probe_depth_listed: one body
 static int trace_probe_depth(srt_context* ctx, const srt_probe_depth_params* t, bool listed, const char* who) {
     if (!ctx || !t) return SRT_ERR_INVALID_ARG;
@@ -2498,7 +2527,7 @@ static int trace_probe_depth(srt_context* ctx, const srt_probe_depth_params* t, 
     for (int i = 0; i < srt::PROBE_DEPTH_SLOTS; ++i)
         if (t->outputs & (1u << i))
             SRT_WRITE_TARGET_AFTER(ctx, ctx->probe_depth_out[i], ctx->d_probe_depth_own[i], srt::probe_depth_bytes(i, np, nk, t->resolution), dst[i],
-                                   probe_depth_output_released(ctx, i));
+                                   probe_output_released(ctx, srt::probe_depth_output_released, ctx->probe_depth, i, ctx->d_probe_depth_own[i]));
     if (count) {
         if (const int rc = zero_work(ctx, ctx->d_probe_depth_work, srt::PD_WORK_N)) return rc;
     }
@@ -2508,8 +2537,8 @@ static int trace_probe_depth(srt_context* ctx, const srt_probe_depth_params* t, 
                                : SRT_KERNEL_LDS_MESH_COUNT(srt::probe_depth_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
     const unsigned wgs = srt::probe_depth_grid(np, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
     srt::ProbeDepthIO io{};
-    io.position = ctx->probes.positions.bound ? (const float4*)ctx->probes.positions.bound : (const float4*)ctx->d_probe_position;
-    io.direction = ctx->probes.directions.bound ? (const float4*)ctx->probes.directions.bound : (const float4*)ctx->d_probe_direction;
+    io.position = current(ctx->probes.positions, ctx->d_probe_position);
+    io.direction = current(ctx->probes.directions, ctx->d_probe_direction);
     io.texel = (const float4*)ctx->d_probe_depth_texels + srt::probe_depth_table_offset(t->resolution);
     io.probes = (uint32_t)np, io.directions = (uint32_t)nk, io.resolution = t->resolution, io.sharpness = t->sharpness;
     io.max_distance = t->max_distance;
@@ -2569,14 +2598,9 @@ int srt_write_probe_grid_depth(srt_context* ctx, const float* moments, size_t pr
     if (srt::probe_grid_depth_check_input(probes, resolution) != srt::RAYS_OK)
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_write_probe_grid_depth: %zu probes of resolution %u: want resolution 4, 8 or 16 and 1 <= probes * resolution^2 <= 2^30",
                     probes, resolution);
-    if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it may be re-allocated below)
-    const size_t bytes = probes * (size_t)resolution * resolution * sizeof(float4);
-    if (ctx->d_probe_grid_depth.bytes() < bytes) {
-        ctx->probe_grid_depth.moments.own_count = 0;  // (a failed allocation leaves no own array)
-        SRT_HIP(ctx, ctx->d_probe_grid_depth.ensure(bytes));
-    }
-    SRT_HIP(ctx, hipMemcpy(ctx->d_probe_grid_depth, moments, bytes, hipMemcpyHostToDevice));
-    srt::probe_grid_depth_written(ctx->probe_grid_depth, probes, resolution);
+    if (const int rc = write_probe_input(ctx, ctx->probe_grid_depth.moments, ctx->d_probe_grid_depth, moments, probes, (size_t)resolution * resolution * sizeof(float4)))
+        return rc;
+    srt::probe_grid_depth_written(ctx->probe_grid_depth, probes, resolution);  // (the resolution with the count)
     return SRT_OK;
 }
 
@@ -2591,45 +2615,7 @@ int srt_bind_probe_grid_depth(srt_context* ctx, const void* d_ptr, size_t probes
 
 int srt_shade_probe_grid_depth(srt_context* ctx, const srt_probe_grid_params* s, const srt_probe_grid_depth_params* d) {
     if (!ctx || !s || !d) return SRT_ERR_INVALID_ARG;
-    srt::ProbeGridCall call;
-    memcpy(&call, s, sizeof call);
-    srt::ProbeGridDepthCall dcall;
-    memcpy(&dcall, d, sizeof dcall);
-    bool present[srt::PROBE_GRID_GUIDES];
-    for (int i = 0; i < srt::PROBE_GRID_GUIDES; ++i) present[i] = current(ctx->gbuf[i], ctx->d_gbuf_own[i]) != nullptr;
-    const char* why = "";
-    if (const srt::RaysStatus rs = srt::probe_grid_depth_check_shade(ctx->probe_grid, ctx->probe_grid_depth, call, dcall, ctx->scene_set, ctx->height, present, &why))
-        return fail(ctx, (int)rs, "srt_shade_probe_grid_depth: %s (rows [%d,%d) of %d, flags 0x%x, band_weight %g %g %g, reserved %u %u; bias %g, min_variance %g, reserved %u %u)",
-                    why, s->row_begin, s->row_end, ctx->height, s->flags, (double)s->band_weight[0], (double)s->band_weight[1], (double)s->band_weight[2], s->reserved[0],
-                    s->reserved[1], (double)d->bias, (double)d->min_variance, d->reserved[0], d->reserved[1]);
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    const bool count = (s->flags & SRT_PROBE_GRID_COUNT_WORK) != 0;
-    float4* dst = nullptr;
-    SRT_WRITE_TARGET(ctx, ctx->probe_grid_out, ctx->d_probe_grid_own, frame_pixels(ctx) * sizeof(float4), dst);
-    if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_probe_grid_work, srt::PG_WORK_N)) return rc;
-    }
-    srt::KernelParams K;
-    KernelSetup ks = scene_kernel_params(ctx, s->row_begin, s->row_end, K);
-    ks.lds_bytes = 0;  // (the kernel traces nothing: no scene image, and its own LDS is static)
-    const srt::ProbeGrid& g = ctx->probe_grid.grid;
-    srt::ProbeGridDepthIO io{};
-    io.object = (const int32_t*)current(ctx->gbuf[0], ctx->d_gbuf_own[0]);
-    io.normal_depth = (const float4*)current(ctx->gbuf[1], ctx->d_gbuf_own[1]);
-    io.position = (const float4*)current(ctx->gbuf[2], ctx->d_gbuf_own[2]);
-    io.albedo = (s->flags & SRT_PROBE_GRID_ALBEDO) ? (const float4*)current(ctx->gbuf[3], ctx->d_gbuf_own[3]) : nullptr;
-    io.coefficients = ctx->probe_grid.coefficients.bound ? (const float4*)ctx->probe_grid.coefficients.bound : (const float4*)ctx->d_probe_grid_coefficients;
-    io.depth = ctx->probe_grid_depth.moments.bound ? (const float4*)ctx->probe_grid_depth.moments.bound : (const float4*)ctx->d_probe_grid_depth;
-    io.out = dst;
-    for (int a = 0; a < 3; ++a) io.origin[a] = g.origin[a], io.spacing[a] = g.spacing[a], io.counts[a] = g.counts[a], io.band_weight[a] = s->band_weight[a];
-    io.normal_weight = (s->flags & SRT_PROBE_GRID_NORMAL_WEIGHT) ? 1u : 0u;
-    io.resolution = ctx->probe_grid_depth.resolution();
-    io.bias = d->bias, io.min_variance = d->min_variance;
-    io.work = count ? (unsigned long long*)ctx->d_probe_grid_work : nullptr;
-    if (const int rc = launch_tiles(ctx, count ? srt::probe_grid_depth_kernel<true> : srt::probe_grid_depth_kernel<false>, ks, K, io)) return rc;
-    ctx->probe_grid_out.wrote(dst);
-    srt::probe_grid_shaded(ctx->probe_grid, s->flags);
-    return SRT_OK;
+    return shade_probe_grid(ctx, "srt_shade_probe_grid_depth", s, d, PG_SHADE_DEPTH);
 }
 
 // ---- probe classification and relocation ----------------------------------------------------------------------------
@@ -2647,13 +2633,6 @@ int srt_probe_classify_params_default(srt_probe_classify_params* out) {
     srt::ProbeClassifyCall c;
     srt::probe_classify_call_default(c);
     memcpy(out, &c, sizeof c);
-    return SRT_OK;
-}
-
-// ... in front of the re-allocation of own probe-state output `i`: earlier classifications may still be writing it
-static int probe_states_output_released(srt_context* ctx, int i) {
-    if (const int rc = finish_stream(ctx)) return rc;
-    srt::probe_states_output_released(ctx->probe_states, i, (void*)ctx->d_probe_states_own[i]);
     return SRT_OK;
 }
 
@@ -2692,7 +2671,8 @@ int srt_classify_probes(srt_context* ctx, const srt_probe_classify_params* t) {
     void* dst[srt::PROBE_STATE_SLOTS] = {nullptr, nullptr};
     for (int i = 0; i < srt::PROBE_STATE_SLOTS; ++i)
         if (t->outputs & (1u << i))
-            SRT_WRITE_TARGET_AFTER(ctx, ctx->probe_states_out[i], ctx->d_probe_states_own[i], srt::probe_state_bytes(np), dst[i], probe_states_output_released(ctx, i));
+            SRT_WRITE_TARGET_AFTER(ctx, ctx->probe_states_out[i], ctx->d_probe_states_own[i], srt::probe_state_bytes(np), dst[i],
+                                   probe_output_released(ctx, srt::probe_states_output_released, ctx->probe_states, i, ctx->d_probe_states_own[i]));
     if (count) {
         if (const int rc = zero_work(ctx, ctx->d_probe_classify_work, srt::PS_WORK_N)) return rc;
     }
@@ -2706,7 +2686,7 @@ int srt_classify_probes(srt_context* ctx, const srt_probe_classify_params* t) {
     io.table = (const float4*)ctx->d_probe_table;
     io.spheres = T.spheres, io.boxes = T.boxes;
     if (relocate) {
-        io.direction = ctx->probes.directions.bound ? (const float4*)ctx->probes.directions.bound : (const float4*)ctx->d_probe_direction;
+        io.direction = current(ctx->probes.directions, ctx->d_probe_direction);
         io.directions = (uint32_t)ctx->probes.directions.count();
     }
     io.probes = (uint32_t)np;
@@ -2755,15 +2735,7 @@ int srt_get_probe_classify_work(srt_context* ctx, srt_probe_classify_work* out) 
 int srt_write_probe_grid_states(srt_context* ctx, const float* records, size_t probes) {
     if (!ctx || !records) return SRT_ERR_INVALID_ARG;
     if (probes < 1 || probes > srt::PROBE_GRID_MAX_PROBES) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_write_probe_grid_states: %zu probes: want 1 .. 2^30", probes);
-    if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it may be re-allocated below)
-    const size_t bytes = probes * sizeof(float4);
-    if (ctx->d_probe_grid_states.bytes() < bytes) {
-        ctx->probe_states.states.own_count = 0;  // (a failed allocation leaves no own array)
-        SRT_HIP(ctx, ctx->d_probe_grid_states.ensure(bytes));
-    }
-    SRT_HIP(ctx, hipMemcpy(ctx->d_probe_grid_states, records, bytes, hipMemcpyHostToDevice));
-    srt::light_probe_written(ctx->probe_states.states, probes);
-    return SRT_OK;
+    return write_probe_input(ctx, ctx->probe_states.states, ctx->d_probe_grid_states, records, probes, sizeof(float4));
 }
 
 int srt_bind_probe_grid_states(srt_context* ctx, const void* d_ptr, size_t probes) {
@@ -2775,51 +2747,7 @@ int srt_bind_probe_grid_states(srt_context* ctx, const void* d_ptr, size_t probe
 
 int srt_shade_probe_grid_states(srt_context* ctx, const srt_probe_grid_params* s, const srt_probe_grid_depth_params* d) {
     if (!ctx || !s) return SRT_ERR_INVALID_ARG;
-    srt::ProbeGridCall call;
-    memcpy(&call, s, sizeof call);
-    srt::ProbeGridDepthCall dcall{};
-    if (d) memcpy(&dcall, d, sizeof dcall);
-    bool present[srt::PROBE_GRID_GUIDES];
-    for (int i = 0; i < srt::PROBE_GRID_GUIDES; ++i) present[i] = current(ctx->gbuf[i], ctx->d_gbuf_own[i]) != nullptr;
-    const char* why = "";
-    if (const srt::RaysStatus rs = srt::probe_grid_states_check_shade(ctx->probe_grid, ctx->probe_grid_depth, ctx->probe_states, call, d ? &dcall : nullptr, ctx->scene_set,
-                                                                      ctx->height, present, &why))
-        return fail(ctx, (int)rs, "srt_shade_probe_grid_states: %s (rows [%d,%d) of %d, flags 0x%x, band_weight %g %g %g, reserved %u %u; depth %s, bias %g, min_variance %g)",
-                    why, s->row_begin, s->row_end, ctx->height, s->flags, (double)s->band_weight[0], (double)s->band_weight[1], (double)s->band_weight[2], s->reserved[0],
-                    s->reserved[1], d ? "given" : "NULL", (double)dcall.bias, (double)dcall.min_variance);
-    SRT_HIP(ctx, hipSetDevice(ctx->device));
-    const bool count = (s->flags & SRT_PROBE_GRID_COUNT_WORK) != 0;
-    float4* dst = nullptr;
-    SRT_WRITE_TARGET(ctx, ctx->probe_grid_out, ctx->d_probe_grid_own, frame_pixels(ctx) * sizeof(float4), dst);
-    if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_probe_grid_work, srt::PG_WORK_N)) return rc;
-    }
-    srt::KernelParams K;
-    KernelSetup ks = scene_kernel_params(ctx, s->row_begin, s->row_end, K);
-    ks.lds_bytes = 0;  // (the kernel traces nothing: no scene image, and its own LDS is static)
-    const srt::ProbeGrid& g = ctx->probe_grid.grid;
-    srt::ProbeGridStatesIO io{};
-    io.object = (const int32_t*)current(ctx->gbuf[0], ctx->d_gbuf_own[0]);
-    io.normal_depth = (const float4*)current(ctx->gbuf[1], ctx->d_gbuf_own[1]);
-    io.position = (const float4*)current(ctx->gbuf[2], ctx->d_gbuf_own[2]);
-    io.albedo = (s->flags & SRT_PROBE_GRID_ALBEDO) ? (const float4*)current(ctx->gbuf[3], ctx->d_gbuf_own[3]) : nullptr;
-    io.coefficients = ctx->probe_grid.coefficients.bound ? (const float4*)ctx->probe_grid.coefficients.bound : (const float4*)ctx->d_probe_grid_coefficients;
-    io.states = ctx->probe_states.states.bound ? (const float4*)ctx->probe_states.states.bound : (const float4*)ctx->d_probe_grid_states;
-    io.out = dst;
-    for (int a = 0; a < 3; ++a) io.origin[a] = g.origin[a], io.spacing[a] = g.spacing[a], io.counts[a] = g.counts[a], io.band_weight[a] = s->band_weight[a];
-    io.normal_weight = (s->flags & SRT_PROBE_GRID_NORMAL_WEIGHT) ? 1u : 0u;
-    if (d) {
-        io.depth = ctx->probe_grid_depth.moments.bound ? (const float4*)ctx->probe_grid_depth.moments.bound : (const float4*)ctx->d_probe_grid_depth;
-        io.resolution = ctx->probe_grid_depth.resolution();
-        io.bias = d->bias, io.min_variance = d->min_variance;
-    }
-    io.work = count ? (unsigned long long*)ctx->d_probe_grid_work : nullptr;
-    const auto kernel = d ? (count ? srt::probe_grid_states_kernel<true, true> : srt::probe_grid_states_kernel<true, false>)
-                          : (count ? srt::probe_grid_states_kernel<false, true> : srt::probe_grid_states_kernel<false, false>);
-    if (const int rc = launch_tiles(ctx, kernel, ks, K, io)) return rc;
-    ctx->probe_grid_out.wrote(dst);
-    srt::probe_grid_shaded(ctx->probe_grid, s->flags);
-    return SRT_OK;
+    return shade_probe_grid(ctx, "srt_shade_probe_grid_states", s, d, PG_SHADE_STATES);
 }
 
 // ---- per-frame probe updates: the list, the histories and the blend (the two listed traces are with their parents) --------
@@ -2863,7 +2791,7 @@ int srt_list_probes(srt_context* ctx, const srt_probe_list_params* t) {
         if (const int rc = zero_work(ctx, ctx->d_probe_list_work, srt::PL_WORK_N)) return rc;
     }
     srt::ProbeListIO io{};
-    io.states = ctx->probe_states.states.bound ? (const float4*)ctx->probe_states.states.bound : (const float4*)ctx->d_probe_grid_states;
+    io.states = current(ctx->probe_states.states, ctx->d_probe_grid_states);
     io.list = dst;
     io.probes = (uint32_t)np, io.skip_mask = t->skip_mask;
     io.work = count ? (unsigned long long*)ctx->d_probe_list_work : nullptr;
@@ -2907,15 +2835,7 @@ int srt_bind_probe_list(srt_context* ctx, const void* d_list, size_t capacity) {
 int srt_write_probe_list(srt_context* ctx, const uint32_t* list, size_t capacity) {
     if (!ctx || !list) return SRT_ERR_INVALID_ARG;
     if (!srt::probe_list_capacity_ok(capacity)) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_write_probe_list: %zu words: want 4 + (1 .. 2^30)", capacity);
-    if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it may be re-allocated below)
-    const size_t bytes = capacity * sizeof(uint32_t);
-    if (ctx->d_probe_list.bytes() < bytes) {
-        ctx->probe_update.list.own_count = 0;  // (a failed allocation leaves no own array)
-        SRT_HIP(ctx, ctx->d_probe_list.ensure(bytes));
-    }
-    SRT_HIP(ctx, hipMemcpy(ctx->d_probe_list, list, bytes, hipMemcpyHostToDevice));
-    srt::light_probe_written(ctx->probe_update.list, capacity);
-    return SRT_OK;
+    return write_probe_input(ctx, ctx->probe_update.list, ctx->d_probe_list, list, capacity, sizeof(uint32_t));
 }
 
 int srt_probe_blend_params_default(srt_probe_blend_params* out) {
@@ -3009,8 +2929,8 @@ int srt_blend_probes(srt_context* ctx, const srt_probe_blend_params* t) {
     if (moments) io.depth_history = current_probe_history(ctx, 1), io.depth_fresh = (const float4*)ctx->probe_depth.last_dst[0];
     io.list = listed ? current_probe_list(ctx) : nullptr;
     if (prev) {
-        io.states = ctx->probe_states.states.bound ? (const float4*)ctx->probe_states.states.bound : (const float4*)ctx->d_probe_grid_states;
-        io.previous = ctx->probe_update.previous.bound ? (const float4*)ctx->probe_update.previous.bound : (const float4*)ctx->d_probe_previous_states;
+        io.states = current(ctx->probe_states.states, ctx->d_probe_grid_states);
+        io.previous = current(ctx->probe_update.previous, ctx->d_probe_previous_states);
     }
     io.probes = (uint32_t)np, io.texels = R * R;
     io.hysteresis = t->hysteresis, io.fast_hysteresis = t->fast_hysteresis, io.depth_hysteresis = t->depth_hysteresis, io.change_threshold = t->change_threshold;

@@ -17,11 +17,9 @@
 // order of rule 3 is the only order; no atomics reach an output.  Work counts (COUNT instantiations only): wave-uniform 64-bit
 // sums, ONE vector atomic per wave at the end.
 //
-// probe_grid_depth_kernel.  probe_grid_kernel's corner-packed scheme (srt_probe_grid.hip.h, which stays as it is: this is a
-// sibling that reuses probe_grid_cell) with rule 7b in place of the any-hit query: the corner's probe is weighted by Chebyshev's
-// bound on "the probe sees at least as far as this point", from the two moments of the texel that looks from the probe towards
-// the point — one 16-byte load and a dozen operations per corner, whatever the scene holds.  It traces nothing, so it stages no
-// scene and has one template axis; its LDS is the pixel records and the result slots of its four waves, 16 KiB.
+// probe_grid_depth_kernel.  The corner-packed body of srt_probe_grid.hip.h (probe_grid_shade, described there) with rule 7b
+// (probe_depth_weigh) in place of the any-hit query.  It traces nothing, so it stages no scene and has one template axis; its LDS
+// is the pixel records and the result slots of its four waves, 16 KiB.
 #pragma once
 
 #include "srt_kernel.hip.h"
@@ -194,195 +192,14 @@ __global__ void __launch_bounds__(WG_THREADS) probe_depth_kernel(const KernelPar
     }
 }
 
-struct ProbeGridDepthIO {
-    const int32_t* object;       // SRT_GBUF_OBJECT: -1 = miss
-    const float4* normal_depth;  // SRT_GBUF_NORMAL_DEPTH: xyz = normal
-    const float4* position;      // SRT_GBUF_POSITION: xyz = point
-    const float4* albedo;        // SRT_GBUF_ALBEDO; NULL without SRT_PROBE_GRID_ALBEDO
-    const float4* coefficients;  // [nx * ny * nz][9]
-    const float4* depth;         // [nx * ny * nz][R*R]: SRT_PROBE_DEPTH_MOMENTS' layout
-    float4* out;                 // W * H
-    float origin[3], spacing[3];
-    int32_t counts[3];
-    float band_weight[3];
-    uint32_t normal_weight;      // SRT_PROBE_GRID_NORMAL_WEIGHT
-    uint32_t resolution;         // R: 4, 8 or 16
-    float bias, min_variance;
-    unsigned long long* work;    // COUNT: [PG_WORK_N] totals of the launch (zeroed by the host before it)
-};
-
-// rule 7b's texel lookup on one axis: the texel index of the folded octahedral coordinate g
-__device__ __forceinline__ int probe_depth_texel_axis(float g, float fr, float top) {
-    float a = ((g * 0.5f) + 0.5f) * fr;
-    a = !(a > 0.0f) ? 0.0f : (a > top ? top : a);  // (a NaN gives 0)
-    return (int)a;
-}
-
-// One launch covers scene rows [P.y0, P.y0 + P.rows); buffers are indexed x + y * width with the SCENE row y, as the G-buffer.
-// Of P only width, rows and y0 are read.
+// srt_shade_probe_grid_depth: probe_grid_shade with rule 7b; 16 KiB of static LDS
 template <bool COUNT>
-__global__ void __launch_bounds__(WG_THREADS) probe_grid_depth_kernel(const KernelParams P, const ProbeGridDepthIO io) {
+__global__ void __launch_bounds__(WG_THREADS) probe_grid_depth_kernel(const KernelParams P, const ProbeGridIO io) {
     constexpr int WAVES = WG_TILES_X * WG_TILES_Y;
     __shared__ float pix_records[WAVES][64 * PG_REC];
     __shared__ float4 result_slots[WAVES][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* const pixrec = pix_records[wave];
-    float4* const slots = result_slots[wave];  // [64] the results of a trip
-    unsigned long long trips_done = 0ull, pixels = 0ull, corners = 0ull, open = 0ull;
-    const int W = P.width;
-    const int tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (P.rows + TILE_H - 1) / TILE_H;
-    const int tiles = tiles_x * tiles_y;
-    const bool weigh = io.normal_weight != 0u;  // (a kernel argument: wave-uniform)
-    const int nx = io.counts[0], ny = io.counts[1], nz = io.counts[2];
-    const int cx = lane & 1, cy = (lane >> 1) & 1, cz = (lane >> 2) & 1;  // this lane's corner: c = lane & 7 in every trip
-    const int R = (int)io.resolution;
-    const float fr = (float)R, top = (float)(R - 1);
-    for (int t = (int)blockIdx.x * WAVES + wave; t < tiles; t += (int)gridDim.x * WAVES) {
-        const int tx = t % tiles_x, ty = t / tiles_x;
-        const int px = tx * TILE_W + (lane & 7), py = ty * TILE_H + (lane >> 3);
-        const bool in_range = px < W && py < P.rows;
-        const int x = px, y = P.y0 + py;
-        const size_t pix = (size_t)x + (size_t)y * (size_t)W;  // (used by lanes in range only)
-        int obj = -1;
-        if (in_range) obj = io.object[pix];
-        const bool hit = obj != -1;
-        // a miss pixel loads none of its other guide values
-        float4 nd = make_float4(0.0f, 0.0f, 0.0f, 0.0f), xp = make_float4(0.0f, 0.0f, 0.0f, 0.0f), alb = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (hit) nd = io.normal_depth[pix], xp = io.position[pix];  // 16-byte loads
-        if (hit && io.albedo) alb = io.albedo[pix];
-        const unsigned long long hmask = __builtin_amdgcn_ballot_w64(hit);
-        const int h = __builtin_popcountll(hmask);
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hmask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hmask, 0u));
-        const int trips = (h + 7) >> 3;
-        if (trips > 0) {  // the pixel of rank r leaves what its corners need in record r
-            const float ofs = .00001f;
-            int i0, i1, i2;
-            float f0, f1, f2;
-            probe_grid_cell(xp.x, io.origin[0], io.spacing[0], nx, i0, f0);
-            probe_grid_cell(xp.y, io.origin[1], io.spacing[1], ny, i1, f1);
-            probe_grid_cell(xp.z, io.origin[2], io.spacing[2], nz, i2, f2);
-            __builtin_amdgcn_wave_barrier();
-            if (hit) {
-                float* rec = pixrec + rank * PG_REC;
-                rec[0] = xp.x + nd.x * ofs, rec[1] = xp.y + nd.y * ofs, rec[2] = xp.z + nd.z * ofs;  // :177
-                rec[3] = nd.x, rec[4] = nd.y, rec[5] = nd.z;
-                rec[6] = __int_as_float(i0), rec[7] = __int_as_float(i1), rec[8] = __int_as_float(i2);
-                rec[9] = f0, rec[10] = f1, rec[11] = f2;
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        if constexpr (COUNT) pixels += (unsigned long long)h;
-        float E0 = 0.0f, E1 = 0.0f, E2 = 0.0f, T = 0.0f;
-        for (int trip = 0; trip < trips; ++trip) {
-            const int r = (trip << 3) + (lane >> 3);  // item 64 trip + lane = 8 r + c
-            const bool item = r < h;
-            const float* rec = pixrec + (item ? r : 0) * PG_REC;
-            const V3 o = v3(rec[0], rec[1], rec[2]);
-            const V3 pn = v3(rec[3], rec[4], rec[5]);
-            const int i0 = __float_as_int(rec[6]), i1 = __float_as_int(rec[7]), i2 = __float_as_int(rec[8]);
-            const float f0 = rec[9], f1 = rec[10], f2 = rec[11];
-            // rule 3: the trilinear weight
-            const float w0 = cx ? f0 : (1.0f - f0), w1 = cy ? f1 : (1.0f - f1), w2 = cz ? f2 : (1.0f - f2);
-            float tw = (w0 * w1) * w2;
-            bool live = item && tw > 0.0f;  // (a NaN fails)
-            // rule 4: the probe; rule 5: the segment to it
-            const V3 p = v3(io.origin[0] + (float)(i0 + cx) * io.spacing[0], io.origin[1] + (float)(i1 + cy) * io.spacing[1],
-                            io.origin[2] + (float)(i2 + cz) * io.spacing[2]);
-            const V3 v = v3(p.x - o.x, p.y - o.y, p.z - o.z);
-            const float q = (v.x * v.x + v.y * v.y) + v.z * v.z;
-            const float L = sqrtf(q);
-            live = live && L > 0.0f;
-            const V3 d = v3(v.x / L, v.y / L, v.z / L);
-            if (weigh) {  // rule 6
-                const float hh = (((d.x * pn.x + d.y * pn.y) + d.z * pn.z) + 1.0f) * 0.5f;
-                tw = tw * ((hh * hh) + 0.2f);
-            }
-            // clamped per axis: in [0, n_a - 1] whatever the record holds
-            const int k0 = min(max(i0 + cx, 0), nx - 1), k1 = min(max(i1 + cy, 0), ny - 1), k2 = min(max(i2 + cz, 0), nz - 1);
-            const size_t probe = (size_t)k0 + (size_t)nx * ((size_t)k1 + (size_t)ny * (size_t)k2);
-            bool ok = false;
-            if (live) {  // rule 7b: the texel that looks from the probe towards the point
-                const float qx = -d.x, qy = -d.y, qz = -d.z;
-                const float s = (fabsf(qx) + fabsf(qy)) + fabsf(qz);
-                float u = qx / s, vv = qy / s;
-                if (qz < 0.0f) {
-                    const float u2 = (1.0f - fabsf(vv)) * (u >= 0.0f ? 1.0f : -1.0f), v2 = (1.0f - fabsf(u)) * (vv >= 0.0f ? 1.0f : -1.0f);
-                    u = u2, vv = v2;
-                }
-                const int ti = probe_depth_texel_axis(u, fr, top), tj = probe_depth_texel_axis(vv, fr, top);  // in [0, R - 1]
-                const float4 mo = io.depth[probe * (size_t)(R * R) + (size_t)(tj * R + ti)];  // 16-byte load
-                const float m1 = mo.x, m2 = mo.y;
-                if (L > m1 + io.bias) {
-                    float var = fabsf(m2 - m1 * m1);
-                    var = var > io.min_variance ? var : io.min_variance;
-                    const float dl = L - m1;
-                    const float ch = var / (var + dl * dl);
-                    tw = tw * ((ch * ch) * ch);
-                }
-                ok = tw > 0.0f;
-            }
-            if constexpr (COUNT) {
-                corners += (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(live));
-                open += (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(ok));
-                trips_done += 1ull;
-            }
-            // rule 8: the corner's irradiance at the normal
-            float4 res = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (ok) {
-                const float4* co = io.coefficients + probe * (size_t)PG_COEFFS;
-                const float bx = pn.x, by = pn.y, bz = pn.z;
-                float b[PG_COEFFS];
-                b[0] = 0.282095f;
-                b[1] = 0.488603f * by;
-                b[2] = 0.488603f * bz;
-                b[3] = 0.488603f * bx;
-                b[4] = 1.092548f * (bx * by);
-                b[5] = 1.092548f * (by * bz);
-                b[6] = 0.315392f * ((3.0f * (bz * bz)) - 1.0f);
-                b[7] = 1.092548f * (bx * bz);
-                b[8] = 0.546274f * ((bx * bx) - (by * by));
-                float e0 = 0.0f, e1 = 0.0f, e2 = 0.0f;
-#pragma unroll
-                for (int c = 0; c < PG_COEFFS; ++c) {
-                    const float a = c == 0 ? io.band_weight[0] : c < 4 ? io.band_weight[1] : io.band_weight[2];
-                    const float4 k = co[c];  // 16-byte load
-                    const float t0 = (a * k.x) * b[c], t1 = (a * k.y) * b[c], t2 = (a * k.z) * b[c];
-                    e0 = c == 0 ? t0 : e0 + t0, e1 = c == 0 ? t1 : e1 + t1, e2 = c == 0 ? t2 : e2 + t2;
-                }
-                res = make_float4(tw * e0, tw * e1, tw * e2, tw);
-            }
-            // rule 9: the owner adds its eight corners in ascending c
-            slots[lane] = res;
-            __builtin_amdgcn_wave_barrier();
-            if (hit && (rank >> 3) == trip) {
-                const float4* mine = slots + ((rank & 7) << 3);
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const float4 s = mine[c];
-                    E0 = E0 + s.x, E1 = E1 + s.y, E2 = E2 + s.z, T = T + s.w;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        if (in_range) {
-            float4 o4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (hit && T > 0.0f) {
-                o4 = make_float4(E0 / T, E1 / T, E2 / T, T);
-                if (io.albedo) o4.x = o4.x * alb.x, o4.y = o4.y * alb.y, o4.z = o4.z * alb.z;
-            }
-            io.out[pix] = o4;
-        }
-    }
-    if constexpr (COUNT) {  // the wave's sums: lane k adds counter k — one vector atomic per wave; the three test counters stay 0
-        unsigned long long v = 0ull;
-        v = lane == PG_WORK_PIXELS ? pixels : v;
-        v = lane == PG_WORK_CORNERS ? corners : v;
-        v = lane == PG_WORK_SEGMENTS ? corners : v;
-        v = lane == PG_WORK_OPEN ? open : v;
-        v = lane == PG_WORK_TRIPS ? trips_done : v;
-        v = lane == PG_WORK_WAVES ? 1ull : v;
-        if (lane < PG_WORK_N) atomicAdd(&io.work[lane], v);
-    }
+    const int wave = threadIdx.x >> 6;
+    probe_grid_shade<false, PgTest::MOMENTS, COUNT>(P, io, pix_records[wave], result_slots[wave]);
 }
 
 }  // namespace srt

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The image passes of several BUILDS of the library against each other, in ONE process on one box: what tests/ab_libs.py does
-for srt_render, for srt_denoise, srt_denoise_variance, srt_upsample, srt_temporal_accumulate and srt_antialias.
+for srt_render, for srt_denoise, srt_denoise_variance, srt_upsample, srt_temporal_accumulate, srt_antialias and the three probe-grid
+shading calls (srt_shade_probe_grid, srt_shade_probe_grid_depth, srt_shade_probe_grid_states).
 usage: python tests/ab_passes.py --libs base=path/a.so,new=path/b.so [--part bits,time] [--rounds 15] [--noise base,base2]
 
 bits: at the frame shapes SHAPES (one pixel, a tile seam, partial tiles both ways, a partial third workgroup across, the
@@ -24,7 +25,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 import pass_edge_inputs as pe  # noqa: E402
+from probe_grid_time import bounds_grid  # noqa: E402
 import test_gpu_temporal as tp  # noqa: E402
 
 SHAPES = [(1, 1), (9, 9), (17, 15), (33, 18), (37, 21), (64, 48)]
@@ -102,11 +105,67 @@ def pass_results(srt, L, w, h):
     return out
 
 
+def probe_inputs(probes, spacing, R, seed):
+    """Seeded inputs of the three probe-grid shading calls: coefficients (P, 9, 4), depth moments (P, R*R, 4) whose mean distances
+    lie on both sides of a corner's distance, and records (P, 4) with offsets within 0.45 of the spacing and about 30 % BURIED."""
+    rng = np.random.default_rng(seed)
+    coeff = rng.uniform(-1.0, 2.0, (probes, 9, 4)).astype(np.float32)
+    m1 = rng.uniform(0.1, 1.5, (probes, R * R)) * float(np.linalg.norm(spacing))
+    depth = np.stack([m1, m1 * m1 + rng.uniform(0.0, 0.5, m1.shape), rng.uniform(0.0, 4.0, m1.shape), rng.uniform(0.0, 1.0, m1.shape)], -1).astype(np.float32)
+    rec = np.zeros((probes, 4), np.float32)
+    rec[:, :3] = rng.uniform(-0.45, 0.45, (probes, 3)) * np.asarray(spacing, np.float64)[None, :]
+    rec[:, 3] = np.where(rng.random(probes) < 0.3, 2, 0).astype(np.uint32).view(np.float32)  # SRT_PROBE_BURIED
+    return coeff, depth, rec
+
+
+def probe_grid_results(srt, L, w, h, scene):
+    """[(what, bytes)] of srt_shade_probe_grid, _depth and _states on one tracer of library L: the output and the work record of
+    every flag combination the calls' own tests iterate over, on the guides of pass_results and a seeded 3 x 3 x 3 grid."""
+    import ctypes as C
+
+    _, obj, nd, pos, alb = pe.guides(w, h, pe.shape_seed(w, h))
+    keep = {"object": _cuda(obj), "normal_depth": _cuda(nd), "position": _cuda(pos), "albedo": _cuda(alb)}
+    rng = np.random.default_rng(pe.shape_seed(w, h) + 41)
+    origin = np.array([-0.2, -0.2, 1.5]) + rng.uniform(0.0, 0.1, 3)  # (the points lie in [0, 0.01 w] x [0, 0.01 h] x [2, 5.7]; some are clamped)
+    spacing = np.array([rng.uniform(0.2, 0.4), rng.uniform(0.2, 0.4), rng.uniform(1.5, 2.0)])
+    coeff, depth, rec = probe_inputs(27, spacing, 8, pe.shape_seed(w, h) + 43)
+    out = []
+    pt = srt.PathTracer(w, h, lib=L)
+    pt.set_scene(*scene)
+    _bind_guides(pt, keep)
+    pt.set_probe_grid(origin, spacing, (3, 3, 3))
+
+    def took(what):
+        work = srt.capi.ProbeGridWork()
+        pt._ck(L.srt_get_probe_grid_work(pt._h, C.byref(work)))
+        out.append(("%s at %d x %d: output" % (what, w, h), pt.probe_grid_output().tobytes()))
+        out.append(("%s at %d x %d: work" % (what, w, h), bytes(work)))
+
+    first = True
+    for vis, nw, al in itertools.product((False, True), repeat=3):
+        pt.shade_probe_grid(coefficients=coeff if first else None, visibility=vis, normal_weight=nw, albedo=al, count_work=True)
+        took("srt_shade_probe_grid visibility %d normal_weight %d albedo %d" % (vis, nw, al))
+        first = False
+    for nw, al in itertools.product((False, True), repeat=2):
+        pt.shade_probe_grid_depth(moments=depth, resolution=8, normal_weight=nw, albedo=al, count_work=True)
+        took("srt_shade_probe_grid_depth normal_weight %d albedo %d" % (nw, al))
+        for with_depth in (False, True):
+            pt.shade_probe_grid_states(states=rec, depth=with_depth, normal_weight=nw, albedo=al, count_work=True)
+            took("srt_shade_probe_grid_states depth %d normal_weight %d albedo %d" % (with_depth, nw, al))
+    pt.wait()
+    for k in keep:
+        pt.bind_gbuffer(k, None)
+    pt.close()
+    del keep
+    return out
+
+
 def compare_bits(srt, libs):
     """The number of result buffers that differ from the first library's."""
     differ = compared = 0
+    scene = srt.host.Scene(os.path.join(ROOT, "software-raytracer_amd", "scenes", "Scene1.json")).objects_copy()
     for w, h in SHAPES:
-        results = [pass_results(srt, L, w, h) for _, L in libs]
+        results = [pass_results(srt, L, w, h) + probe_grid_results(srt, L, w, h, scene) for _, L in libs]
         for (name, _), got in zip(libs[1:], results[1:]):
             assert [what for what, _ in got] == [what for what, _ in results[0]]
             for (what, a), (_, b) in zip(results[0], got):
@@ -161,7 +220,20 @@ def time_calls(srt, libs, a):
         ("srt_denoise_variance defaults", lambda pt: pt.denoise_variance(gbuffer=False)),
         ("srt_denoise_variance sigma_luminance 0", lambda pt: pt.denoise_variance(sigma_luminance=0.0, gbuffer=False)),
         ("srt_upsample steps 2", lambda pt: pt.upsample(steps=2, gbuffer=False)),
+        ("srt_shade_probe_grid no flags", lambda pt: pt.shade_probe_grid()),
+        ("srt_shade_probe_grid visibility normal_weight", lambda pt: pt.shade_probe_grid(visibility=True, normal_weight=True)),
+        ("srt_shade_probe_grid_depth normal_weight", lambda pt: pt.shade_probe_grid_depth(normal_weight=True)),
+        ("srt_shade_probe_grid_states depth", lambda pt: pt.shade_probe_grid_states(depth=True)),
+        ("srt_shade_probe_grid_states no depth", lambda pt: pt.shade_probe_grid_states()),
     ]
+    # the probe grid of tools/probe_grid_time.py: spacing 1 over the bounds of the frame's hit points, and seeded inputs
+    torch.cuda.synchronize()
+    grid = bounds_grid(guides["object"].cpu().numpy(), guides["position"].cpu().numpy(), 1.0)
+    coeff, depth, rec = probe_inputs(grid.probes, grid.spacing, 8, 7)
+    for pt in pts:
+        pt.set_probe_grid(grid.origin, grid.spacing, grid.counts)
+        pt.shade_probe_grid_states(coefficients=coeff, states=rec, moments=depth, resolution=8)
+        pt.wait()
     ms = {(c, i): [] for c, _ in calls for i in range(len(libs))}
     for r in range(a.warm + a.rounds):
         for cname, call in calls:

@@ -1,8 +1,9 @@
 """Probe-grid shading that obeys the probe records (srt_shade_probe_grid_states, ABI 7) on the MI355X.  Every comparison is bit for
 bit over all four lanes of every pixel.  All-zero records must reproduce srt_shade_probe_grid and srt_shade_probe_grid_depth as the
 device computes them; random records (offsets within 0.45 of the spacing, about 30 % buried, one pixel with all eight corners
-buried) go against tests/probe_states_reference.py's shade(); records of srt_classify_probes are bound device to device; and the
-three existing shading calls return the bits they returned before."""
+buried) go against tests/probe_states_reference.py's shade(); records of srt_classify_probes are bound device to device; the
+three existing shading calls return the bits they returned before; and all three calls, which share one device body, go against
+their references on tiles whose hit counts lie on both sides of a trip boundary."""
 import ctypes as C
 import itertools
 
@@ -92,6 +93,63 @@ def test_zero_records_reproduce_the_parent_calls(frame1, flags):
     other[:, 3] = np.full(grid.probes, PS.MOVED | PS.INSIDE | PS.IDLE, np.uint32).view(F)
     pt.shade_probe_grid_states(states=other, depth=True, **kwargs(flags))
     assert same(pt.probe_grid_output(), parent)
+
+
+# ---- hit counts on both sides of a trip boundary: all three calls ---------------------------------------------------------------------
+@pytest.mark.parametrize("hits", [(0, 1, 8), (9, 63, 64)])
+def test_tiles_whose_hit_count_crosses_a_trip_boundary(srt, oracle, hits):
+    """24 x 8: three tiles with `hits` hit pixels, scattered over the lanes, so that a tile takes 0, 1, 2 or 8 trips, the last one
+    full, with one item or with seven; the lane that takes item 8 r + c past the last rank reads record 0, and the owner of rank r
+    collects in trip r >> 3.  Synthetic guides with points inside a 3 x 3 x 3 grid around one small sphere (the any-hit query
+    decides something, and the reference takes its bits from srt_trace_occlusion)."""
+    import types
+
+    import torch
+
+    from test_gpu_visibility import one_pixel_scene
+
+    w, h = 24, 8
+    rng = np.random.default_rng(50 + sum(hits))
+    obj = np.full((h, w), -1, np.int32)
+    for tile, n in enumerate(hits):
+        lanes = 1 + rng.choice(63, n, replace=False) if n < 64 else np.arange(64)  # (lane 0 misses: the ranks are not the lanes)
+        obj[lanes >> 3, 8 * tile + (lanes & 7)] = 1
+    hit = obj != -1
+    assert [int(hit[:, 8 * t:8 * t + 8].sum()) for t in range(3)] == list(hits)
+    grid = PG.Grid((-1.0, -1.0, 4.0), (1.0, 1.0, 1.0), (3, 3, 3))
+    pos = np.zeros((h, w, 4), F)
+    pos[..., :3] = rng.uniform(-0.95, 0.95, (h, w, 3)) + np.array([0.0, 0.0, 5.0])
+    pos[..., 3] = 1.0
+    nrm = rng.normal(size=(h, w, 3))
+    nd = np.concatenate([nrm / np.linalg.norm(nrm, axis=2, keepdims=True), np.full((h, w, 1), 3.0)], -1).astype(F)
+    alb = np.concatenate([rng.uniform(0.05, 0.9, (h, w, 3)), np.zeros((h, w, 1))], -1).astype(F)
+    nd[~hit], pos[~hit], alb[~hit] = np.array([0, 0, 0, np.inf], F), 0, 0
+    oarr, n = oracle.make_objects(one_pixel_scene(oracle)[0])  # a sphere of radius 0.3 at (0, 0, 5): the grid's centre
+    pt = srt.PathTracer(w, h)
+    keep = {k: torch.from_numpy(v).to("cuda:%d" % pt.device) for k, v in (("object", obj), ("normal_depth", nd), ("position", pos), ("albedo", alb))}
+    torch.cuda.synchronize()
+    try:
+        pt.set_scene(C.cast(oarr, C.POINTER(srt.Object)), n)
+        for k, t in keep.items():
+            pt.bind_gbuffer(k, t)
+        fr = types.SimpleNamespace(pt=pt, obj=obj, nd=nd, pos=pos, alb=alb)
+        coeff = random_coefficients(grid.probes, 51)
+        depth = synthetic_moments(grid.probes, 4, 52, lo=0.3, hi=1.6)  # (the corner distances here run from 0 to 1.7)
+        rec = random_records(fr, grid, 53)
+        assert (rec[:, 3].view(np.uint32) & PS.BURIED).any()
+        flags = PG.NORMAL_WEIGHT | PG.ALBEDO
+        _, work = check_exact(fr, grid, coeff, flags)
+        assert work["pixels"] == sum(hits) and work["wave_trips"] == sum((n + 7) // 8 for n in hits)
+        _, vwork = check_exact(fr, grid, coeff, flags | PG.VISIBILITY, write=False)
+        assert vwork["segments"] == work["corners"]
+        check_depth(fr, grid, coeff, depth, 4, flags)
+        check(fr, grid, coeff, rec, flags)
+        check(fr, grid, coeff, rec, flags, depth=depth, R=4)
+    finally:
+        pt.wait()
+        for k in keep:
+            pt.bind_gbuffer(k, None)
+        pt.close()
 
 
 # ---- random records against the reference ---------------------------------------------------------------------------------------------
