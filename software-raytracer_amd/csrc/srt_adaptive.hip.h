@@ -7,10 +7,11 @@
 // srt_render(1 .. n_p + e_p) leaves there.  It is radiance_kernel (srt_radiance.hip.h) with three changes:
 //   1. The unit is an 8 x 8 pixel TILE of the band (visibility_kernel's lane <-> pixel mapping: x = lane & 7, y = lane >> 3) whose
 //      camera rays the kernel makes itself (GetRayDirection, as gbuffer_kernel), not a strip of 64 caller rays.
-//   2. The sample range is per LANE: slot l hands out samples [0, e_l) of its pixel, row (sample - chunk start) of the wave's
-//      scratch region, and the wave-uniform chunk loop runs to the tile's largest e in steps of RAD_CHUNK.  The frame of a sample is
-//      the slot's first frame n_l + 1 (word 11 of its record) plus the sample index.  The hand-out, the bounce, the scratch rows,
-//      the release / acquire pairs and the 8-in-flight fold are radiance_kernel's, expression by expression.
+//   2. The sample range is per LANE (PixelSamples below, the sample source the pool of srt_sample_pool.hip.h runs on): slot l
+//      hands out samples [0, e_l) of its pixel, row (sample - chunk start) of the wave's scratch region, and the wave-uniform
+//      chunk loop runs to the tile's largest e in steps of RAD_CHUNK.  The frame of a sample is the slot's first frame n_l + 1
+//      (word 11 of its record) plus the sample index.  The hand-out, the bounce, the scratch rows, the release / acquire pairs
+//      and the 8-in-flight fold are the pool's: the text radiance_kernel runs.
 //   3. Waves take tiles from a GLOBAL TICKET (one relaxed device-scope atomic add by one lane, broadcast with readfirstlane):
 //      budgets are skewed by design, and with static striding most waves would sit idle behind those that drew the noisy tiles.
 //      No data passes between waves through the ticket, so it needs no fence.  A wave takes its next tile only when its pool has
@@ -70,27 +71,34 @@ __device__ __forceinline__ uint32_t effective_budget(uint32_t b, uint32_t n, uin
     return e < room ? e : room;
 }
 
+// the samples of adaptive_kernel (srt_sample_pool.hip.h): [0, lim) of the lane's own slot; the
+// frame of a sample is the slot's first frame (word 11 of its record) plus the sample index
+struct PixelSamples {
+    static constexpr int CLOSEST = ADP_WORK_CLOSEST, WAVE_CALLS = ADP_WORK_WAVE_CALLS;
+    uint32_t lim, first_frame;
+    struct Chunk {  // this slot's part of the chunk: samples [begin, end), none once the slot has run out (else begin == c0)
+        uint32_t begin, end;
+        __device__ __forceinline__ uint32_t first() const { return begin; }
+        __device__ __forceinline__ bool owner() const { return begin < end; }
+        __device__ __forceinline__ uint32_t count() const { return end - begin; }
+    };
+    __device__ __forceinline__ uint32_t last() const { return wave_max_u32(lim); }  // (the tile's largest)
+    __device__ __forceinline__ Chunk chunk(uint32_t c0) const {
+        const uint32_t begin = lim < c0 ? lim : c0;
+        return Chunk{begin, lim - begin < (uint32_t)RAD_CHUNK ? lim : begin + (uint32_t)RAD_CHUNK};
+    }
+    __device__ __forceinline__ uint32_t frame(const float* r, uint32_t sidx) const { return __float_as_uint(r[11]) + sidx; }
+    __device__ __forceinline__ void fold(float4& acc, RGB c, float a, uint32_t s) const {
+        const uint32_t f = first_frame + s;
+        accumulate_frame(acc, c, a, f, f == 1u);
+    }
+};
+
 // LDS: the path-trace kernel's layout (make_lds with four waves), as radiance_kernel.
 template <bool SCENE_LDS, bool MESH, bool COUNT>
 __global__ void __launch_bounds__(WG_THREADS) adaptive_kernel(const KernelParams P, const AdaptiveIO io) {
     extern __shared__ float4 lds_scene[];
-    if constexpr (SCENE_LDS) {  // staged as pathtrace_kernel stages it: every load issued before the first LDS store
-        constexpr int STAGE = 8;
-        const int n = P.scene_vec4;
-        float4 row[STAGE];
-#pragma unroll
-        for (int k = 0; k < STAGE; ++k) {
-            const int i = (int)threadIdx.x + k * WG_THREADS;
-            row[k] = i < n ? P.scene[i] : make_float4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int k = 0; k < STAGE; ++k) {
-            const int i = (int)threadIdx.x + k * WG_THREADS;
-            if (i < n) lds_scene[i] = row[k];
-        }
-        for (int i = (int)threadIdx.x + STAGE * WG_THREADS; i < n; i += WG_THREADS) lds_scene[i] = P.scene[i];
-        __syncthreads();
-    }
+    stage_scene<SCENE_LDS>(P, lds_scene);
     constexpr int WAVES = WG_TILES_X * WG_TILES_Y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const Lds S = make_lds<SCENE_LDS>(P, lds_scene, WAVES, wave);
@@ -98,13 +106,8 @@ __global__ void __launch_bounds__(WG_THREADS) adaptive_kernel(const KernelParams
     Prof prof{};
 #endif
     Tally<false> no_tally;
-    RadWork<COUNT> Wk;
-    auto lanes = [](bool b) { return (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(b)); };
-    auto below = [](unsigned long long m) { return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); };
-    // this wave's region of the scratch: RAD_CHUNK rows of 64 slots
-    float4* const rows = io.rows + ((size_t)blockIdx.x * WAVES + (size_t)wave) * (size_t)(RAD_CHUNK * 64);
-    float* const rec = S.pix;                                      // [64][12]: dir, n0, p0, prim0, the key's seed-and-pixel half, the first frame
-    unsigned* const match = reinterpret_cast<unsigned*>(S.work);  // [64] of (sample << 6 | slot), ~0 = nothing
+    WaveWork<COUNT, ADP_WORK_N> Wk;
+    float4* const rows = wave_sample_rows(io.rows, wave);
     const int B = P.max_bounces;
     const int W = P.width, H = P.height;
     const int tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (P.rows + TILE_H - 1) / TILE_H;
@@ -141,210 +144,35 @@ __global__ void __launch_bounds__(WG_THREADS) adaptive_kernel(const KernelParams
         const bool traced = want && h0.prim >= 0 && B > 0;
         const uint32_t first_frame = n0 + 1u;  // (n0 < ADP_FRAME_LIMIT where want)
         Wk.add(ADP_WORK_WAVE_CALLS, 1ull);
-        Wk.add(ADP_WORK_PIXELS, lanes(want));
+        Wk.add(ADP_WORK_PIXELS, wave_lanes(want));
         if constexpr (COUNT) {
             Wk.add(ADP_WORK_SAMPLES, (unsigned long long)wave_sum_u32(e));
             Wk.add(ADP_WORK_CLOSEST, (unsigned long long)wave_sum_u32(traced ? 0u : e));  // the primary counts once per sample (srt_stats.rays' rule)
         }
         float4 acc = make_float4(0, 0, 0, 0);
         if (want && n0 != 0u) acc = P.accumulator[pix];
-        // ---- pixels whose colour does not depend on the sample: a miss -> env(d) every sample (:143-145); MAXBOUNCES == 0 ->
-        // the first hit's EmissiveColor (:162, 212)
-        if (want && !traced) {
-            RGB c;
-            float ca = 0.0f;  // the colour's alpha (+0 from the emissive colour)
-            if (h0.prim < 0) {
-                c = environment(S, dir0);
-                ca = environment_alpha(dir0);
-            } else {
-                const float4 m1 = S.mat(h0.prim, 1);
-                c = RGB{clamp0(m1.y), clamp0(m1.z), clamp0(m1.w)};
-            }
-            for (uint32_t s = 0; s < e; ++s) accumulate_frame(acc, c, ca, first_frame + s, first_frame + s == 1u);
+        // samples [0, lim) of this slot; the chunk loop runs to the tile's largest
+        const uint32_t lim = traced ? e : 0u;
+        const PixelSamples samples{lim, first_frame};
+        if (want && !traced) {  // the colour does not depend on the sample
+            fold_constant_colour(S, samples, dir0, h0, e, acc);
             store_pixel(P, pix, acc);
             if (!io.keep_counts) io.counts[pix] = n0 + e;
         }
         if (__builtin_amdgcn_ballot_w64(traced) == 0ull) continue;
-
-        // ---- wave-level path pool over (slot, sample): lane l owns slot l
-        if (traced) {
-            float* r = rec + lane * 12;
-            r[0] = dir0.x, r[1] = dir0.y, r[2] = dir0.z;
-            r[3] = h0.n.x, r[4] = h0.n.y, r[5] = h0.n.z;
-            r[6] = h0.p.x, r[7] = h0.p.y, r[8] = h0.p.z;
-            r[9] = __int_as_float(h0.prim);
-            // srt_rng_key's first two rounds depend on seed and pixel only: done here once, the sample's round at the hand-out
-            r[10] = __uint_as_float(srt_mix32(srt_mix32(P.seed ^ 0xA511E9B3U) + pix));
-            r[11] = __uint_as_float(first_frame);
+        if (traced) {  // srt_rng_key's id of a pixel: its index
+            write_first_hit_record(S, lane, dir0, h0, P.seed, pix);
+            S.pix[lane * 12 + 11] = __uint_as_float(first_frame);
         }
         __builtin_amdgcn_wave_barrier();
-        const uint32_t lim = traced ? e : 0u;                 // samples [0, lim) of this slot
-        const uint32_t e_max = wave_max_u32(lim);             // (wave-uniform: the chunk loop's end)
-        // path state of the task this lane is running
-        bool busy = false;
-        uint32_t task = 0;  // sample << 6 | slot
-        RGB L{0, 0, 0}, T{0, 0, 0};
-        V3 sray = v3(0, 0, 1), hn = v3(0, 0, 0), hp = v3(0, 0, 0);
-        int hprim = 0, bounce = 0;
-        float spec = 0.0f;
-        uint32_t rng = 0;
-        int rot = 0;  // wave-uniform rotation of the slot priority
-        for (uint32_t c0 = 0; c0 < e_max; c0 += (uint32_t)RAD_CHUNK) {  // (wave-uniform)
-            // this slot's part of the chunk: samples [begin, end), none once the slot has run out
-            const uint32_t begin = lim < c0 ? lim : c0;
-            const uint32_t end = lim - begin < (uint32_t)RAD_CHUNK ? lim : begin + (uint32_t)RAD_CHUNK;
-            uint32_t own_next = begin;  // samples [begin, own_next) of this slot have been handed out
-            // the fold of the chunk before has read the rows this chunk's paths overwrite
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            while (__builtin_amdgcn_ballot_w64(busy || own_next < end) != 0ull) {
-                // ---- hand out tasks: radiance_kernel's — the slots that have samples left are dealt round-robin to the free
-                // lanes, and a slot hands out as many consecutive samples as it is dealt lanes, up to what it has left.  Two
-                // passes: entries that stayed empty in the first because a slot ran out find another slot in the second.
-                bool fresh = false;
-                for (int pass = 0; pass < 2; ++pass) {
-                    const unsigned long long freem = __builtin_amdgcn_ballot_w64(!busy);
-                    const int avail = own_next < end ? (int)(end - own_next) : 0;
-                    const bool can = avail > 0;
-                    const unsigned long long canm = __builtin_amdgcn_ballot_w64(can);
-                    if (freem == 0ull || canm == 0ull) break;
-                    const int nfree = __builtin_popcountll(freem), ncan = __builtin_popcountll(canm);
-                    rot = (rot + 23) & 63;
-                    const int crank = below(canm) - __builtin_popcountll(canm & ((1ull << rot) - 1ull)) + (lane < rot ? ncan : 0);
-                    const int frank = below(freem);
-                    if (!busy) match[frank] = 0xFFFFFFFFu;
-                    __builtin_amdgcn_wave_barrier();
-                    if (can) {
-                        int given = 0;
-                        for (int j = crank; j < nfree && given < avail; j += ncan) {
-                            match[j] = ((own_next + (uint32_t)given) << 6) | (unsigned)lane;
-                            ++given;
-                        }
-                        own_next += (uint32_t)given;
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    const unsigned m = !busy ? match[frank] : 0xFFFFFFFFu;
-                    if (m != 0xFFFFFFFFu) {  // (the sample is set up below, once for the lanes of both passes)
-                        task = m;
-                        busy = true;
-                        fresh = true;
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                }
-                if (fresh) {  // a lane that has just taken a task: Raytracer.cpp:162-166 for sample sidx of that pixel
-                    const uint32_t sidx = task >> 6;
-                    const float* r = rec + (int)(task & 63u) * 12;
-                    const int prim0 = __float_as_int(r[9]);
-                    rng = srt_mix32(__float_as_uint(r[10]) + (__float_as_uint(r[11]) + sidx));  // = srt_rng_key(seed, pixel, frame), see the record
-                    const uint32_t rr = srt_mix32(rng) >> 17;                                    // draw 0: the specular lottery at the first hit
-                    rng += 0x9E3779B9U;
-                    const float4 m0 = S.mat(prim0, 0), m1 = S.mat(prim0, 1);
-                    spec = (m0.y >= rand_unit(rr)) ? 1.0f : 0.0f;  // :165
-                    L = RGB{m1.y, m1.z, m1.w};                     // :162 (clamped in the image)
-                    T = RGB{m0.z, m0.w, m1.x};                     // :163
-                    sray = v3(r[0], r[1], r[2]);                   // :164
-                    hn = v3(r[3], r[4], r[5]);
-                    hp = v3(r[6], r[7], r[8]);
-                    hprim = prim0;
-                    bounce = 0;
-                }
-                Wk.add(ADP_WORK_CLOSEST, lanes(fresh));  // the sample's primary GetClosestObject call (:142)
-                // ---- one bounce for every busy lane
-                V3 o = v3(0, 0, 0);
-                const float ofs = .00001f;
-                if (busy) {
-                    if (bounce != 0) {  // :169-171
-                        T = RGB{T.r * 0.8f, T.g * 0.8f, T.b * 0.8f};  // (NN)
-                    }
-                    // reflectedRay = sray.Reflect(normal)  (:172, Common.hpp:163-165)
-                    const float k2 = 2 * dot3(sray, hn);
-                    const V3 refl = v3(sray.x - hn.x * k2, sray.y - hn.y * k2, sray.z - hn.z * k2);
-                    // GetRandomNormalOrientedHemisphere (:90-105): exactly three draws, x then y then z
-                    const uint32_t r0 = srt_mix32(rng) >> 17;
-                    const uint32_t r1 = srt_mix32(rng + 0x9E3779B9U) >> 17;
-                    const uint32_t r2 = srt_mix32(rng + 2u * 0x9E3779B9U) >> 17;
-                    rng += 3u * 0x9E3779B9U;
-                    V3 sr = v3((rand_unit(r0) - 0.5f) * 2, (rand_unit(r1) - 0.5f) * 2, (rand_unit(r2) - 0.5f) * 2);
-                    sr = normalized_in_window(sr);  // (inside normalized()'s window by construction: see there)
-                    if (dot3(sr, hn) < 0) sr = v3(sr.x * -1, sr.y * -1, sr.z * -1);
-                    // float3::Lerp(sray, reflectedRay, Smoothness * specularProb)  (:175)
-                    const float tt = S.mat(hprim, 0).x * spec;
-                    const V3 l = v3(sr.x * (1 - tt) + refl.x * tt, sr.y * (1 - tt) + refl.y * tt, sr.z * (1 - tt) + refl.z * tt);
-                    sray = normalized(l);                                            // :176
-                    o = v3(hp.x + hn.x * ofs, hp.y + hn.y * ofs, hp.z + hn.z * ofs);  // :177
-                }
-                // the scan runs in wave-uniform control flow: idle lanes help with other lanes' rays
-                const Hit h = closest_hit<MESH, false, SCENE_LDS>(S, P, o, sray, busy, 1, deferred, no_tally SRT_PROF_ARG);
-                Wk.add(ADP_WORK_WAVE_CALLS, 1ull);
-                Wk.add(ADP_WORK_CLOSEST, lanes(busy));
-                if (busy) {
-                    bool end_path;
-                    uint32_t atag = 0u;  // the sample's alpha: NaN only from the environment (T's alpha is +0)
-                    if (h.prim < 0) {    // :178-181
-                        const RGB env = environment(S, sray);
-                        L = RGB{L.r + env.r * T.r, L.g + env.g * T.g, L.b + env.b * T.b};  // (NN)
-                        atag = alpha_tag(environment_alpha(sray));
-                        end_path = true;
-                    } else {
-                        const float4 m0 = S.mat(h.prim, 0), m1 = S.mat(h.prim, 1), m2 = S.mat(h.prim, 2);
-                        const uint32_t r = srt_mix32(rng) >> 17;  // one lottery per further hit
-                        rng += 0x9E3779B9U;
-                        spec = (m0.y >= rand_unit(r)) ? 1.0f : 0.0f;  // :182
-                        const RGB Em{m1.y, m1.z, m1.w};
-                        L = RGB{L.r + Em.r * T.r, L.g + Em.g * T.g, L.b + Em.b * T.b};  // :183 (NN)
-                        const RGB Bc{m0.z, m0.w, m1.x}, Sc{m2.x, m2.y, m2.z};
-                        const float ns = 1 - spec;  // :184, Color::Lerp with t = 0 or 1 (NN)
-                        const RGB f{Bc.r * ns + Sc.r * spec, Bc.g * ns + Sc.g * spec, Bc.b * ns + Sc.b * spec};
-                        T = RGB{T.r * f.r, T.g * f.g, T.b * f.b};
-                        hn = h.n;
-                        hp = h.p;
-                        hprim = h.prim;
-                        ++bounce;
-                        end_path = bounce >= B;
-                    }
-                    if (end_path) {  // the sample's colour into row (sample - c0), slot, of the wave's region; written exactly once
-                        const uint32_t sidx = task >> 6;  // (in [c0, c0 + RAD_CHUNK): handed out by this chunk)
-                        rows[((sidx - c0) << 6) + (task & 63u)] = make_float4(L.r, L.g, L.b, __uint_as_float(sidx | atag));
-                        busy = false;
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
-            // The wave's own stores, made by whichever lane ran the path, are read back by the slots' owner lanes: the ROWS
-            // kernel's release / acquire pair at workgroup scope (see pathtrace_kernel); no other wave ever touches these rows.
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            if (begin < end) {  // lane l folds rows 0 .. end - c0 - 1 of slot l, in sample order (begin == c0 here)
-                const float4* row = rows + lane;
-                const uint32_t cnt = end - begin;
-                const uint32_t f0 = first_frame + begin;  // the frame of row 0
-                uint32_t s = 0;
-                for (; s + ROWS_IN_FLIGHT <= cnt; s += ROWS_IN_FLIGHT) {
-                    float4 c[ROWS_IN_FLIGHT];
-#pragma unroll
-                    for (int k = 0; k < ROWS_IN_FLIGHT; ++k) c[k] = row[(size_t)(s + k) * 64];
-#pragma unroll
-                    for (int k = 0; k < ROWS_IN_FLIGHT; ++k)
-                        accumulate_frame(acc, RGB{c[k].x, c[k].y, c[k].z}, tag_alpha(__float_as_uint(c[k].w)), f0 + s + k, f0 + s + k == 1u);
-                }
-                for (; s < cnt; ++s) {
-                    const float4 c = row[(size_t)s * 64];
-                    accumulate_frame(acc, RGB{c.x, c.y, c.z}, tag_alpha(__float_as_uint(c.w)), f0 + s, f0 + s == 1u);
-                }
-            }
-        }
+        run_sample_pool<MESH, SCENE_LDS>(S, P, samples, rows, lane, acc, Wk SRT_PROF_ARG);
         if (traced) {
             store_pixel(P, pix, acc);
             if (!io.keep_counts) io.counts[pix] = n0 + e;
         }
         __builtin_amdgcn_wave_barrier();  // (the next tile rewrites the records)
     }
-    if constexpr (COUNT) {  // the wave's sums: lane k adds counter k — one vector atomic per wave
-        unsigned long long v = 0ull;
-#pragma unroll
-        for (int k = 0; k < ADP_WORK_N; ++k) v = lane == k ? Wk.n[k] : v;
-        if (lane < ADP_WORK_N) atomicAdd(&io.work[lane], v);
-    }
+    Wk.flush(io.work, lane);
 }
 
 // ---- srt_sample_budget ------------------------------------------------------------------------------------------------------

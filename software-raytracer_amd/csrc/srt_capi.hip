@@ -2081,7 +2081,7 @@ static_assert(SRT_RADIANCE_RESET == srt::RADIANCE_FLAG_RESET && SRT_RADIANCE_NOR
               SRT_RADIANCE_COUNT_WORK == srt::RADIANCE_FLAG_COUNT_WORK && SRT_RADIANCE_RESET == SRT_RENDER_RESET &&
               sizeof(srt_radiance_params) == 24 && sizeof(srt::RadianceCall) == 24 && sizeof(srt_radiance_work) == 40 &&
               srt::RADIANCE_CHUNK == srt::RAD_CHUNK,
-              "srt_radiance_host.h, srt_radiance.hip.h and srt_pathtrace.h disagree");
+              "srt_radiance_host.h, srt_sample_pool.hip.h and srt_pathtrace.h disagree");
 
 int srt_radiance_params_default(srt_radiance_params* out) {
     if (!out) return SRT_ERR_INVALID_ARG;
@@ -2096,6 +2096,18 @@ int srt_radiance_params_default(srt_radiance_params* out) {
 static int radiance_output_released(srt_context* ctx) {
     if (const int rc = finish_stream(ctx)) return rc;
     srt::radiance_output_released(ctx->radiance, (void*)ctx->d_radiance_own);
+    return SRT_OK;
+}
+
+// The sample scratch of the three sample-pool launches (srt_trace_radiance, srt_trace_light_probes, srt_render_adaptive; one
+// stream runs them all): every wave of a grid of `wgs` workgroups has its own region.  Grown once the stream has finished with
+// the smaller one.
+static int ensure_sample_rows(srt_context* ctx, unsigned wgs) {
+    const size_t scratch = srt::radiance_scratch_bytes(wgs, srt::OUT_WG_UNITS);
+    if (ctx->d_radiance_rows.bytes() < scratch) {
+        if (const int rc = finish_stream(ctx)) return rc;
+        SRT_HIP(ctx, ctx->d_radiance_rows.ensure(scratch));
+    }
     return SRT_OK;
 }
 
@@ -2119,11 +2131,7 @@ int srt_trace_radiance(srt_context* ctx, const srt_radiance_params* t) {
     const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::radiance_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
     // the grid first: the sample scratch is sized by it
     const unsigned wgs = srt::radiance_grid(n, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
-    const size_t scratch = srt::radiance_scratch_bytes(wgs, srt::OUT_WG_UNITS);
-    if (ctx->d_radiance_rows.bytes() < scratch) {
-        if (const int rc = finish_stream(ctx)) return rc;
-        SRT_HIP(ctx, ctx->d_radiance_rows.ensure(scratch));
-    }
+    if (const int rc = ensure_sample_rows(ctx, wgs)) return rc;
     if (count) {
         if (const int rc = zero_work(ctx, ctx->d_radiance_work, srt::RAD_WORK_N)) return rc;
     }
@@ -2253,11 +2261,7 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
                                : SRT_KERNEL_LDS_MESH_COUNT(srt::light_probe_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
     // the grid first: the sample scratch is sized by it
     const unsigned wgs = srt::light_probe_grid(np, nk, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
-    const size_t scratch = srt::light_probe_scratch_bytes(wgs, srt::OUT_WG_UNITS);
-    if (ctx->d_radiance_rows.bytes() < scratch) {
-        if (const int rc = finish_stream(ctx)) return rc;
-        SRT_HIP(ctx, ctx->d_radiance_rows.ensure(scratch));
-    }
+    if (const int rc = ensure_sample_rows(ctx, wgs)) return rc;
     if (count) {
         if (const int rc = zero_work(ctx, ctx->d_probe_work, srt::LP_WORK_N)) return rc;
     }
@@ -3050,11 +3054,7 @@ int srt_render_adaptive(srt_context* ctx, const srt_adaptive_params* a) {
     const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::adaptive_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
     // the grid first: the sample scratch is sized by it
     const unsigned wgs = srt::adaptive_grid(K.width, K.rows, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
-    const size_t scratch = srt::adaptive_scratch_bytes(wgs, srt::OUT_WG_UNITS);
-    if (ctx->d_radiance_rows.bytes() < scratch) {
-        if (const int rc = finish_stream(ctx)) return rc;
-        SRT_HIP(ctx, ctx->d_radiance_rows.ensure(scratch));
-    }
+    if (const int rc = ensure_sample_rows(ctx, wgs)) return rc;
     if (!ctx->d_adaptive_ticket) SRT_HIP(ctx, ctx->d_adaptive_ticket.ensure(sizeof(uint32_t)));
     SRT_HIP(ctx, hipMemsetAsync(ctx->d_adaptive_ticket, 0, sizeof(uint32_t), ctx->stream));
     if (count) {

@@ -9,8 +9,8 @@
 //   1. Lane l forms its ray from position[p] — one broadcast 16-byte load — and direction[64j + l]: there is no P*K ray array.
 //   2. ONE closest_hit for the 64 primaries; then radiance_kernel's steps 1-3 (the sample-independent lanes, the wave-level path
 //      pool over (slot, sample) tasks with the sample rows in the wave's own region of the scratch, the ordered fold), restated
-//      here expression by expression as that file restates pathtrace_kernel (which, like radiance_kernel, stays as it is): the
-//      same bits.
+//      here expression by expression from srt_sample_pool.hip.h, the text radiance_kernel runs (DESIGN.md §4.32 says why this
+//      kernel does not call it): the same bits.
 //   3. Each lane multiplies its mean by the nine terms t_c = w * b_c; lanes past K carry +0.0f.  The wave runs 36 butterfly
 //      reductions (9 coefficients x 4 lanes, six levels each, lane-xor 1, 2, 4, 8, 16, 32): binary32 addition commutes, so lane 0
 //      holds exactly the header's pairwise tree v'[m] = v[2m] + v[2m+1].

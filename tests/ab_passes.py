@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """The image passes of several BUILDS of the library against each other, in ONE process on one box: what tests/ab_libs.py does
 for srt_render, for srt_denoise, srt_denoise_variance, srt_upsample, srt_temporal_accumulate, srt_antialias and the three probe-grid
-shading calls (srt_shade_probe_grid, srt_shade_probe_grid_depth, srt_shade_probe_grid_states).
-usage: python tests/ab_passes.py --libs base=path/a.so,new=path/b.so [--part bits,time] [--rounds 15] [--noise base,base2]
+shading calls (srt_shade_probe_grid, srt_shade_probe_grid_depth, srt_shade_probe_grid_states); and, as parts of their own
+(pool_bits, pool_time), for the four calls that run the sample pool: srt_trace_radiance, srt_trace_light_probes, its listed
+form and srt_render_adaptive.
+usage: python tests/ab_passes.py --libs base=path/a.so,new=path/b.so [--part bits,time,pool_bits,pool_time] [--rounds 15] [--noise base,base2]
 
 bits: at the frame shapes SHAPES (one pixel, a tile seam, partial tiles both ways, a partial third workgroup across, the
 prefilter's apron at all four frame edges and inside), on the guides of tests/pass_edge_inputs.py bound as torch tensors and a
@@ -10,10 +12,14 @@ seeded variance with exact zeros, every library runs the same calls on a tracer 
 buffer and of the framebuffer must be the same in all libraries, NaN payloads included.  A difference names the pass, the
 shape and the parameters, and the exit status is 1.
 time: 1920 x 1080 on Scene1's real guides (as tools/denoise_time.py and tools/variance_time.py set them up), one tracer per
-library on one stream; every call is bracketed by two events, the libraries take turns within a round, and the median per
+library on one stream; every call is bracketed by two events, the libraries take turns within a round (the first turn moves on
+every round), and the median per
 (call, library) is printed with its ratio to the first library.  With --noise a,b (two copies of one build under two file
 names) the noise floor of a call is the relative difference of the medians of a and b, and every other library passes the call
-when its median is at most the slower copy's plus that floor."""
+when its median is at most the slower copy's plus that floor.
+pool_bits: the inputs of tests/test_gpu_sample_pool.py; every output buffer and work record, compared as bits does.
+pool_time: the workloads of tools/radiance_time.py, tools/light_probe_time.py, tools/probe_update_time.py (listed, spacing 0.25 on
+Scene_indirect) and tools/adaptive_time.py (the uniform and the map step) at their defaults, timed and judged as time does."""
 import argparse
 import importlib
 import itertools
@@ -26,6 +32,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import pass_edge_inputs as pe  # noqa: E402
 from probe_grid_time import bounds_grid  # noqa: E402
 import test_gpu_temporal as tp  # noqa: E402
@@ -178,6 +185,37 @@ def compare_bits(srt, libs):
     return differ
 
 
+def timed_rounds(libs, pts, calls, stream, a):
+    """Every call on every library's tracer, the libraries taking turns within a round; the medians, and the verdicts of --noise."""
+    import torch
+
+    ms = {(c, i): [] for c, _ in calls for i in range(len(libs))}
+    for r in range(a.warm + a.rounds):
+        for cname, call in calls:
+            for i in [(r + k) % len(pts) for k in range(len(pts))]:  # (the first turn moves on every round: a library's place in the round shifts its time by up to 1 %)
+                pt = pts[i]
+                b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                b.record(stream)
+                call(pt)
+                e.record(stream)
+                stream.synchronize()
+                if r >= a.warm:
+                    ms[cname, i].append(b.elapsed_time(e))
+    names = [name for name, _ in libs]
+    noise = [names.index(x) for x in a.noise.split(",")] if a.noise else None
+    for cname, _ in calls:
+        med = [statistics.median(ms[cname, i]) for i in range(len(libs))]
+        for i, name in enumerate(names):
+            print("%-40s %-9s median %8.4f ms  min %8.4f  x%.4f vs %s" % (cname, name, med[i], min(ms[cname, i]), med[i] / med[0], names[0]), flush=True)
+        if noise:
+            x, y = med[noise[0]], med[noise[1]]
+            floor, slower = abs(x - y) / min(x, y), max(x, y)
+            for i, name in enumerate(names):
+                if i not in noise:
+                    print("%-40s %-9s x%.4f of the slower copy, noise floor %.4f: %s" %
+                          (cname, name, med[i] / slower, floor, "passes" if med[i] <= slower * (1.0 + floor) else "SLOWER"), flush=True)
+
+
 def time_calls(srt, libs, a):
     import torch
 
@@ -234,36 +272,186 @@ def time_calls(srt, libs, a):
         pt.set_probe_grid(grid.origin, grid.spacing, grid.counts)
         pt.shade_probe_grid_states(coefficients=coeff, states=rec, moments=depth, resolution=8)
         pt.wait()
-    ms = {(c, i): [] for c, _ in calls for i in range(len(libs))}
-    for r in range(a.warm + a.rounds):
-        for cname, call in calls:
-            for i, pt in enumerate(pts):
-                b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                b.record(stream)
-                call(pt)
-                e.record(stream)
-                stream.synchronize()
-                if r >= a.warm:
-                    ms[cname, i].append(b.elapsed_time(e))
-    names = [name for name, _ in libs]
-    noise = [names.index(x) for x in a.noise.split(",")] if a.noise else None
-    for cname, _ in calls:
-        med = [statistics.median(ms[cname, i]) for i in range(len(libs))]
-        for i, name in enumerate(names):
-            print("%-40s %-9s median %8.4f ms  min %8.4f  x%.4f vs %s" % (cname, name, med[i], min(ms[cname, i]), med[i] / med[0], names[0]), flush=True)
-        if noise:
-            x, y = med[noise[0]], med[noise[1]]
-            floor, slower = abs(x - y) / min(x, y), max(x, y)
-            for i, name in enumerate(names):
-                if i not in noise:
-                    print("%-40s %-9s x%.4f of the slower copy, noise floor %.4f: %s" %
-                          (cname, name, med[i] / slower, floor, "passes" if med[i] <= slower * (1.0 + floor) else "SLOWER"), flush=True)
+    timed_rounds(libs, pts, calls, stream, a)
     for pt in pts:
         pt.bind_denoised(None)
         pt.bind_half(None)
         pt.bind_variance(None)
         for k in guides:
             pt.bind_gbuffer(k, None)
+        pt.set_stream(0)
+        pt.close()
+
+
+def pool_results(srt, L):
+    """[(what, bytes)] of the four sample-pool calls on the inputs of tests/test_gpu_sample_pool.py, on tracers of library L."""
+    import ctypes as C
+
+    import srt_oracle_py as oracle
+    import test_gpu_sample_pool as sp
+    from test_gpu_light_probes import PROBES
+    from test_gpu_radiance import camera_rays, moved_camera, srt_camera
+    from test_gpu_visibility import closed_room, scene1
+
+    out = []
+
+    def took(what, **buffers):
+        for name, v in buffers.items():
+            out.append(("%s: %s" % (what, name), repr(sorted(v.items())).encode() if isinstance(v, dict) else np.ascontiguousarray(v).tobytes()))
+
+    def tracer(scene, w, h):
+        oarr, n = oracle.make_objects(scene(oracle)[0])
+        pt = srt.PathTracer(w, h, lib=L)
+        pt.set_scene(C.cast(oarr, C.POINTER(srt.Object)), n)
+        return pt
+
+    ocam = moved_camera(oracle)
+    o, d = camera_rays(oracle, ocam, sp.W, sp.H)
+    pt = tracer(scene1, sp.W, sp.H)
+    for n in sp.SAMPLE_COUNTS:
+        for count in (True, False):
+            pt.trace_radiance(o, d, samples=n, bounces=8, seed=3, count_work=count)
+            took("srt_trace_radiance samples %d count_work %d" % (n, count), radiance=pt.radiance(), **(dict(work=pt.radiance_work()) if count else {}))
+    pt.trace_radiance(o, d, samples=64, bounces=8, seed=3)
+    pt.trace_radiance(samples=65, bounces=8, seed=3, first_sample=65, reset=False)
+    took("srt_trace_radiance 64 + 65 samples", radiance=pt.radiance())
+    for bounces in (1, 8):
+        for rays in (1, 63, 64, 65):
+            pt.trace_radiance(o[:rays], d[:rays], samples=65, bounces=bounces, seed=7, count_work=True)
+            took("srt_trace_radiance Scene1 rays %d bounces %d" % (rays, bounces), radiance=pt.radiance(), work=pt.radiance_work())
+    # light probes, unlisted and listed (probes 2 and 0, and a word out of range between them)
+    P = PROBES.shape[0]
+    for k in (1, 63, 64, 65, 129):
+        dirs = srt.light_probe_sphere(k)
+        for n in (1, 9, 64, 65):
+            kw = dict(samples=n, bounces=8, seed=11, id_base=1000)
+            for listed in (False, True):
+                pt.bind_probe_list(np.array([3, P, 0, 0, 2, P + 4, 0], np.uint32) if listed else None)
+                pt.trace_light_probes(PROBES, dirs, radiance=True, **dict(kw, seed=12))
+                pt.trace_light_probes(radiance=True, count_work=True, listed=listed, **kw)
+                took("srt_trace_light_probes%s K %d samples %d" % ("_listed" if listed else "", k, n), radiance=pt.light_probe_radiance(),
+                     coefficients=pt.light_probe_coefficients(), work=pt.light_probe_work())
+                pt.trace_light_probes(listed=listed, **kw)
+                took("srt_trace_light_probes%s K %d samples %d, coefficients alone" % ("_listed" if listed else "", k, n), coefficients=pt.light_probe_coefficients())
+    pt.wait()
+    pt.bind_probe_list(None)
+    # adaptive: 5 samples everywhere, then the budgets of the seam test on counts of 0 and 5
+    pt.set_camera(srt_camera(srt, ocam))
+    b = sp.pool_map()
+    n0 = np.where((np.arange(sp.W)[None, :] + np.arange(sp.H)[:, None]) % 3 == 0, 5, 0).astype(np.uint32)
+    for count in (True, False):
+        pt.render(spp=5, bounces=8, seed=5)
+        pt.write_sample_counts(n0)
+        pt.write_sample_budget(b)
+        pt.render_adaptive(bounces=8, seed=5, count_work=count)
+        took("srt_render_adaptive count_work %d" % count, accumulator=pt.accumulator(), framebuffer=pt.framebuffer(), counts=pt.sample_counts(),
+             **(dict(work=pt.adaptive_work()) if count else {}))
+    pt.close()
+    # the closed room, and a block of misses between two pooled blocks
+    pt = tracer(closed_room, sp.W, sp.H)
+    o, d = camera_rays(oracle, oracle.default_camera(), sp.W, sp.H)
+    for rays in (1, 63, 64, 65):
+        pt.trace_radiance(o[:rays], d[:rays], samples=65, bounces=8, seed=7, count_work=True)
+        took("srt_trace_radiance closed room rays %d" % rays, radiance=pt.radiance(), work=pt.radiance_work())
+    pt.close()
+    pt = tracer(scene1, 24, 8)
+    sky = oracle.default_camera()
+    sky.position[:], sky.forward[:], sky.up[:] = (0.0, 50.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, -1.0)
+    (o, d), (so, sd) = camera_rays(oracle, ocam, 24, 8), camera_rays(oracle, sky, 24, 8)
+    o[64:128], d[64:128] = so[64:128], sd[64:128]
+    pt.trace_radiance(o, d, samples=9, bounces=8, seed=5, count_work=True)
+    took("srt_trace_radiance 192 rays, the middle block misses", radiance=pt.radiance(), work=pt.radiance_work())
+    pt.close()
+    return out
+
+
+def compare_pool_bits(srt, libs):
+    differ = compared = 0
+    results = [pool_results(srt, L) for _, L in libs]
+    for (name, _), got in zip(libs[1:], results[1:]):
+        assert [what for what, _ in got] == [what for what, _ in results[0]]
+        for (what, x), (_, y) in zip(results[0], got):
+            compared += 1
+            if x != y:
+                differ += 1
+                print("!!! %s: %s DIFFERS from %s" % (what, name, libs[0][0]), flush=True)
+    print("pool_bits: %d buffers and work records compared against %s, %d differ" % (compared, libs[0][0], differ), flush=True)
+    return differ
+
+
+def time_pool_calls(srt, libs, a):
+    """Three tracers per library on one stream: Scene1 at 1920 x 1080 (radiance, adaptive), Scene1 and Scene_indirect at 64 x 64
+    (light probes), Scene_indirect at 1920 x 1080 (the listed trace of a classified grid)."""
+    import torch
+
+    import light_probe_time as LT
+    import rays_time as R
+
+    w, h = 1920, 1080
+    stream = torch.cuda.Stream(device=0)
+    torch.cuda.synchronize()
+    scenes = {k: srt.host.Scene(os.path.join(ROOT, "software-raytracer_amd", "scenes", k + ".json")).objects_copy() for k in ("Scene1", "Scene_indirect")}
+    o, d = R.camera_rays(torch, w, h)
+    pos, dirs = LT.grid(np, 4096), srt.light_probe_sphere(256)
+    torch.cuda.synchronize()
+    keep, pts, grid_words = [], [], None
+    for _, L in libs:
+        def tracer(scene, tw, th):
+            pt = srt.PathTracer(tw, th, lib=L)
+            pt.set_scene(*scenes[scene])
+            pt.set_camera(srt.default_camera())
+            pt.set_stream(stream.cuda_stream)
+            keep.append(pt)
+            return pt
+
+        frame, half = tracer("Scene1", w, h), tracer("Scene1", w, h)
+        frame.bind_rays(o, d)
+        frame.set_sample_counts(0)
+        frame.write_sample_budget(np.full((h, w), 32, np.uint32))
+        # tools/adaptive_time.py's map: 8 samples in each of two halves, the variance between them, the library's default budget
+        half.render(spp=8, bounces=8, seed=0)
+        half.bind_output(None, half.half_ptr())
+        half.render(spp=8, bounces=8, seed=0x9E3779B9)
+        half.bind_output()
+        half.set_sample_counts(8)
+        half.variance(merge=False)
+        half.sample_budget()
+        probes = {k: tracer(k, 64, 64) for k in scenes}
+        for pt in probes.values():
+            pt.trace_light_probes(pos, dirs, samples=16, bounces=8, seed=0)
+        # tools/probe_update_time.py's listed trace: spacing 0.25 over the frame's hit points, a relocating classification
+        room = tracer("Scene_indirect", w, h)
+        room.render_gbuffer(outputs=["object", "normal_depth", "position"])
+        grid = bounds_grid(room.gbuffer("object"), room.gbuffer("position"), 0.25)
+        room.set_probe_grid(grid.origin, grid.spacing, grid.counts)
+        room.classify_probes(directions=dirs, relocate=True, positions=True)
+        rec, gpos = room.probe_states_output("records"), room.probe_states_output("positions")
+        room.bind_probe_grid_states(rec)
+        room.list_probes()
+        words = room.probe_list_output(grid.probes)
+        if grid_words is None:
+            grid_words = words
+            print("listed trace: %d of %d probes" % (int(words[0]), grid.probes), flush=True)
+        assert np.array_equal(words, grid_words)
+        room.trace_light_probes(gpos, dirs, samples=16, bounces=8, seed=1)
+        room.bind_probe_list(words)
+        room.wait()
+        pts.append(dict(frame=frame, half=half, room=room, **probes))
+    calls = [
+        ("srt_trace_radiance Scene1 1080p 32 samples", lambda t: t["frame"].trace_radiance(samples=32, bounces=8, seed=0)),
+        ("srt_trace_light_probes Scene1", lambda t: t["Scene1"].trace_light_probes(samples=16, bounces=8, seed=0)),
+        ("srt_trace_light_probes Scene_indirect", lambda t: t["Scene_indirect"].trace_light_probes(samples=16, bounces=8, seed=0)),
+        ("srt_trace_light_probes radiance Scene1", lambda t: t["Scene1"].trace_light_probes(samples=16, bounces=8, seed=0, radiance=True)),
+        ("srt_trace_light_probes_listed spacing 0.25", lambda t: t["room"].trace_light_probes(samples=16, bounces=8, seed=1, listed=True)),
+        ("srt_render_adaptive uniform 32", lambda t: t["frame"].render_adaptive(bounces=8, seed=0, keep_counts=True)),
+        ("srt_render_adaptive map", lambda t: t["half"].render_adaptive(bounces=8, seed=0, keep_counts=True)),
+    ]
+    timed_rounds(libs, pts, calls, stream, a)
+    for t in pts:
+        t["frame"].wait()
+        t["frame"].bind_rays(None, None)
+        t["room"].bind_probe_list(None)
+    for pt in keep:
         pt.set_stream(0)
         pt.close()
 
@@ -281,9 +469,14 @@ def main():
     for item in a.libs.split(","):
         name, path = item.split("=")
         libs.append((name, srt.capi.open_library(os.path.join(ROOT, path))))
-    differ = compare_bits(srt, libs) if "bits" in a.part.split(",") else 0
-    if "time" in a.part.split(","):
+    parts = a.part.split(",")
+    differ = compare_bits(srt, libs) if "bits" in parts else 0
+    if "pool_bits" in parts:
+        differ += compare_pool_bits(srt, libs)
+    if "time" in parts:
         time_calls(srt, libs, a)
+    if "pool_time" in parts:
+        time_pool_calls(srt, libs, a)
     sys.exit(1 if differ else 0)
 
 
