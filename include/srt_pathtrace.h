@@ -1637,6 +1637,81 @@ int srt_get_probe_grid_work(srt_context* ctx, srt_probe_grid_work* out);
  * reference's interface. */
 int srt_selftest_arith(int device, uint32_t seed, uint64_t vectors, uint64_t* mismatches);
 
+/* ---- probe tail: radiance paths that end in the probe grid (ABI 7, backward compatible) -----------------------------------------
+ * These calls were added without changing anything else, so SRT_ABI_VERSION stays 7.  srt_probe_tail sets a per-context mode, off
+ * by default.  With it on, a path of srt_trace_radiance, srt_trace_light_probes or srt_trace_light_probes_listed that ends BECAUSE
+ * THE BOUNCE LIMIT WAS REACHED ON A SURFACE adds the grid's hemisphere-mean radiance at that surface, times the path's throughput:
+ * one or two bounces and a lookup instead of eight bounces, and no light lost to truncation.  Everything else stays as it is, RNG
+ * streams included.  With the mode off every call launches the kernels it launched before.  srt_render, srt_render_adaptive and
+ * every other pass ignore the mode.
+ *
+ * srt_probe_tail touches no device memory and launches nothing.  SRT_ERR_INVALID_ARG, and the previous setting stands, for: enabled
+ * outside 0..1; unknown flags; a NaN band weight; a bias that is NaN, infinite or < 0; a min_variance that is NaN, infinite or
+ * <= 0; a non-zero reserved word.
+ *
+ * The grid, coefficients, depth maps and states are those of srt_set_probe_grid and the three srt_write_ / srt_bind_probe_grid_*
+ * pairs, CURRENT AT THE ENQUEUE OF THE TRACE: exactly what srt_shade_probe_grid_states would read.  Each affected trace call
+ * checks them after its own errors and before anything is touched, and returns SRT_ERR_STATE when there is no grid or there are
+ * no coefficients; when a count is not nx*ny*nz; when the depth maps are missing under DEPTH or the states under STATES; when the
+ * coefficient array the tail would read overlaps, as a byte range, the buffer the call is about to write (RADIANCE, or the
+ * light-probe COEFFICIENTS output): a feedback loop reads the history or the previous frame's buffer, never the one being written.
+ *
+ * T1. Where.  A sample's path (radiance block rule 2) ends at a primary miss, at a bounce ray that leaves the scene, or at
+ *     bounce >= max_bounces after a surface hit.  Only the third case changes, and only for max_bounces >= 1: with
+ *     max_bounces == 0 the call is unchanged (and checks none of the above).
+ * T2. State after Raytracer.cpp:182-184 for that last hit: L; T, already multiplied by the surface's colour of the lottery; spec,
+ *     the lottery just drawn; x and n, the hit's point and normal; Smoothness of the hit material.  No draw is consumed.
+ * T3. g = 1.0f - (Smoothness * spec): the share of the next bounce's direction that would have been the random one (:175).
+ *     If !(g > 0), nothing is added (work: mirror_ends).
+ * T4. (M, a) is the float4 that srt_shade_probe_grid_states (or _depth, or srt_shade_probe_grid without VISIBILITY, according to
+ *     the flags) writes for a pixel whose guides hold a hit, POSITION x and NORMAL n, without ALBEDO, with the mode's band
+ *     weights, bias and min_variance: probe-grid rules 2 - 6, 7b, 3s / 4s, 8 and 9 in the same operation order; corners are
+ *     summed in ascending c, starting from +0; a skipped corner contributes +0; rule 5's origin is x + n * .00001f.
+ *     If !(a > 0), nothing is added (work: dark).  Then M_l = !(M_l > 0) ? 0 : M_l per lane: SH ringing and NaN stay out.
+ * T5. k_l = (T_l * 0.8f) * g and L_l = L_l + (k_l * M_l) for l = 0, 1, 2: the 0.8 is the dissipation the next bounce would have
+ *     applied (:169-171).  The colour's alpha lane and tag are untouched.
+ * T6. Everything after that is as before: the scratch row, the ordered fold, the running mean of rule 3.
+ * Binary32 without contraction throughout.  With all coefficients zero the outputs are, bit for bit, those of the mode off.
+ * srt_trace_light_probes' RADIANCE still equals srt_trace_radiance on the explicit rays under the same mode, its COEFFICIENTS are
+ * still the fixed-order projection of that RADIANCE, and the listed call still writes at the listed probes what the unlisted one
+ * writes there.  Pinned domain: finite coefficients, moments and offsets, over the pinned domain of the trace call; anything else
+ * gives some value and does not fault (every index is clamped as in the shading pass).
+ *
+ * srt_get_probe_tail_work waits and copies the record of the last affected trace; SRT_ERR_STATE unless that trace ran with the
+ * mode on and COUNT_WORK set (all zeros when max_bounces == 0 kept the mode from applying).  srt_radiance_work and
+ * srt_light_probe_work are filled exactly as before: a lookup traces no ray.  wave_lookups counts the steps of a wave's sample
+ * pool in which at least one of its lanes ended at the bounce limit on a surface (the wave then goes through the lookup's
+ * eight-corner loop once, all its terminal lanes together); it depends on the launch's grid only through which wave runs which
+ * block, so repeated runs on one device give the same number. */
+#define SRT_PROBE_TAIL_NORMAL_WEIGHT 1u  /* probe-grid rule 6 */
+#define SRT_PROBE_TAIL_DEPTH 2u          /* rule 7b, from the maps of srt_write/bind_probe_grid_depth */
+#define SRT_PROBE_TAIL_STATES 4u         /* rules 3s, 4s, from the records of srt_write/bind_probe_grid_states */
+#define SRT_PROBE_TAIL_COUNT_WORK 8u
+
+typedef struct srt_probe_tail_params { /* 32 bytes */
+    int32_t enabled;                   /* 0 or 1 */
+    uint32_t flags;                    /* SRT_PROBE_TAIL_* */
+    float band_weight[3];              /* A for SH bands 0, 1, 2 */
+    float bias, min_variance;          /* rule 7b; as srt_probe_grid_depth_params */
+    uint32_t reserved;                 /* 0 */
+} srt_probe_tail_params;
+
+typedef struct srt_probe_tail_work {   /* 56 bytes */
+    uint32_t valid, reserved;          /* 1, 0 */
+    uint64_t tails;        /* paths that ended at the bounce limit on a surface with g > 0: lookups made */
+    uint64_t corners;      /* corners that reached rule 7 (weight > 0, L > 0, not buried) */
+    uint64_t open;         /* corners that entered the sum (== corners without DEPTH) */
+    uint64_t dark;         /* lookups whose weights summed to 0: nothing added */
+    uint64_t mirror_ends;  /* paths that ended at the limit with !(g > 0): no lookup */
+    uint64_t wave_lookups; /* wave-level passes through the lookup code (see above) */
+} srt_probe_tail_work;
+
+/* enabled 1, flags 0, band_weight (1.0f, 0.5f, 0.0f) — the hemisphere MEAN of probe-grid rule 10, which is what this renderer's
+ * diffuse bounce averages — bias 0, min_variance 1e-4f, reserved 0.  Pure host. */
+int srt_probe_tail_params_default(srt_probe_tail_params* out);
+int srt_probe_tail(srt_context* ctx, const srt_probe_tail_params* params);
+int srt_get_probe_tail_work(srt_context* ctx, srt_probe_tail_work* out);
+
 /* ---- per-frame probe updates: active-probe lists, listed traces and a hysteresis blend (ABI 7, backward compatible) ---------------
  * These calls were added without changing anything else, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of them
  * runs what it ran before, bit for bit.  They keep a classified probe grid alive from frame to frame: srt_list_probes compacts the

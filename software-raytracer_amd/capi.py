@@ -132,6 +132,7 @@ EXPORTS = [
     "srt_bind_probe_list", "srt_write_probe_list", "srt_trace_light_probes_listed", "srt_trace_probe_depth_listed",
     "srt_probe_blend_params_default", "srt_reset_probe_history", "srt_bind_probe_history", "srt_read_probe_history",
     "srt_write_probe_previous_states", "srt_bind_probe_previous_states", "srt_blend_probes", "srt_get_probe_blend_work",
+    "srt_probe_tail_params_default", "srt_probe_tail", "srt_get_probe_tail_work",
 ]
 
 
@@ -298,6 +299,24 @@ class ReflectionWork(C.Structure):
 class MirrorHistoryParams(C.Structure):
     """srt_mirror_history_params: the mode (0 or 1) and the radius of its distance test in pixels; flags and reserved must be 0."""
     _fields_ = [("enabled", C.c_int32), ("radius_pixels", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+PROBE_TAIL_NORMAL_WEIGHT, PROBE_TAIL_DEPTH, PROBE_TAIL_STATES, PROBE_TAIL_COUNT_WORK = 1, 2, 4, 8
+
+
+class ProbeTailParams(C.Structure):
+    """srt_probe_tail_params: the mode (0 or 1), PROBE_TAIL_* flags, the band weights of the lookup and rule 7b's parameters."""
+    _fields_ = [("enabled", C.c_int32), ("flags", C.c_uint32), ("band_weight", C.c_float * 3), ("bias", C.c_float),
+                ("min_variance", C.c_float), ("reserved", C.c_uint32)]
+
+
+class ProbeTailWork(C.Structure):
+    """srt_probe_tail_work: the lookups of the last trace that ran under srt_probe_tail with PROBE_TAIL_COUNT_WORK."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("tails", C.c_uint64), ("corners", C.c_uint64), ("open", C.c_uint64),
+                ("dark", C.c_uint64), ("mirror_ends", C.c_uint64), ("wave_lookups", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class RadianceParams(C.Structure):
@@ -602,6 +621,10 @@ def open_library(path):
     L.srt_get_reflection_work.argtypes = [ctx, C.POINTER(ReflectionWork)]
     L.srt_mirror_history_params_default.argtypes = [C.POINTER(MirrorHistoryParams)]
     L.srt_mirror_history.argtypes = [ctx, C.POINTER(MirrorHistoryParams)]
+    if hasattr(L, "srt_probe_tail"):  # (tests/ab_passes.py opens builds of earlier commits next to this one)
+        L.srt_probe_tail_params_default.argtypes = [C.POINTER(ProbeTailParams)]
+        L.srt_probe_tail.argtypes = [ctx, C.POINTER(ProbeTailParams)]
+        L.srt_get_probe_tail_work.argtypes = [ctx, C.POINTER(ProbeTailWork)]
     L.srt_radiance_params_default.argtypes = [C.POINTER(RadianceParams)]
     L.srt_trace_radiance.argtypes = [ctx, C.POINTER(RadianceParams)]
     L.srt_bind_radiance.argtypes = [ctx, C.c_void_p]
@@ -676,6 +699,8 @@ def open_library(path):
     L.srt_sample_budget.argtypes = [ctx, C.POINTER(BudgetParams)]
     L.srt_get_budget_total.argtypes = [ctx, C.POINTER(C.c_uint64)]
     for name in EXPORTS:
+        if "probe_tail" in name and not hasattr(L, name):
+            continue  # (a build of an earlier commit, opened by tests/ab_passes.py)
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
             fn.restype = C.c_int
@@ -1302,6 +1327,31 @@ class PathTracer:
             p.radius_pixels = float(radius_pixels)
         self._ck(self.L.srt_mirror_history(self._h, C.byref(p)))
         self._mirror_history = bool(on)
+
+    def probe_tail(self, enabled=True, normal_weight=False, depth=False, states=False, band_weight=None, count_work=False, bias=None,
+                   min_variance=None):
+        """srt_probe_tail: with `enabled`, a path of trace_radiance() or of the light-probe traces that ends at the bounce limit on a
+        surface adds the probe grid's hemisphere-mean radiance there (the grid, coefficients, depth maps and states current at the
+        trace).  normal_weight / depth / states switch probe-grid rules 6 / 7b / 3s and 4s on; band_weight, bias and min_variance
+        default to the library's (the hemisphere mean).  Touches no device memory."""
+        p = ProbeTailParams()
+        self._ck(self.L.srt_probe_tail_params_default(C.byref(p)))
+        p.enabled = 1 if enabled else 0
+        p.flags = ((PROBE_TAIL_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_TAIL_DEPTH if depth else 0) | (PROBE_TAIL_STATES if states else 0)
+                   | (PROBE_TAIL_COUNT_WORK if count_work else 0))
+        if band_weight is not None:
+            p.band_weight[:] = [float(v) for v in band_weight]
+        if bias is not None:
+            p.bias = float(bias)
+        if min_variance is not None:
+            p.min_variance = float(min_variance)
+        self._ck(self.L.srt_probe_tail(self._h, C.byref(p)))
+
+    def probe_tail_work(self):
+        """srt_get_probe_tail_work as a dict: the record of the last trace that ran under probe_tail(count_work=True)."""
+        w = ProbeTailWork()
+        self._ck(self.L.srt_get_probe_tail_work(self._h, C.byref(w)))
+        return w.as_dict()
 
     def _render_guides(self, outputs, what, first_hit_only=False):
         """The guides a pass with gbuffer=True renders first: first hits, or the reflection guides while they are in use."""

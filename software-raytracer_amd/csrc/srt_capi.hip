@@ -49,6 +49,8 @@
 #include "srt_probe_states_host.h"
 #include "srt_probe_update.hip.h"
 #include "srt_probe_update_host.h"
+#include "srt_probe_tail.hip.h"
+#include "srt_probe_tail_host.h"
 #include "srt_adaptive.hip.h"
 #include "srt_adaptive_host.h"
 #include "srt_launch_shape.h"
@@ -459,6 +461,10 @@ struct srt_context {
     DeviceBuffer<float4> d_probe_history[srt::PROBE_HISTORY_SLOTS];
     DeviceBuffer<unsigned long long> d_probe_list_work;
     DeviceBuffer<unsigned long long> d_probe_blend_work;
+    // the probe tail (srt_probe_tail): the mode's setting and whether the last affected trace ran under it and counted
+    // (srt_probe_tail_host.h); the record a counting launch adds to (srt::PT_WORK_N words)
+    srt::ProbeTailState probe_tail;
+    DeviceBuffer<unsigned long long> d_probe_tail_work;
     // adaptive sampling (srt_render_adaptive, srt_sample_budget): the per-pixel sample counts and sample budget, W*H uint32 each,
     // own buffer and slot; whether the last adaptive render counted and whether a budget pass has run (srt_adaptive_host.h); the
     // tile ticket of a launch (zeroed on the stream in front of it); the record a counting launch adds to (srt::ADP_WORK_N words);
@@ -1144,6 +1150,14 @@ static long long resident_workgroups(srt_context* ctx, const void* kernel, size_
 template <class IO>
 static int launch_persistent(srt_context* ctx, void (*kernel)(srt::KernelParams, IO), unsigned wgs, const KernelSetup& ks, const srt::KernelParams& K, const IO& io) {
     hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io);
+    SRT_HIP(ctx, hipGetLastError());
+    return SRT_OK;
+}
+// ... of a TAIL instantiation (srt_probe_tail.hip.h): the tail's inputs are a kernel argument of their own
+template <class IO>
+static int launch_persistent_tail(srt_context* ctx, void (*kernel)(srt::KernelParams, IO, srt::ProbeTailIO), unsigned wgs, const KernelSetup& ks,
+                                  const srt::KernelParams& K, const IO& io, const srt::ProbeTailIO& tio) {
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io, tio);
     SRT_HIP(ctx, hipGetLastError());
     return SRT_OK;
 }
@@ -2099,6 +2113,40 @@ static int radiance_output_released(srt_context* ctx) {
     return SRT_OK;
 }
 
+// srt_probe_tail is on and changes this trace: what the mode requires of the grid's inputs, and a coefficient array that is not
+// the buffer the call is about to write, `written` (NULL: an own buffer not allocated yet)
+static int check_probe_tail(srt_context* ctx, const char* who, const void* written, size_t written_bytes) {
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_tail_check_trace(ctx->probe_tail, ctx->probe_grid, ctx->probe_grid_depth, ctx->probe_states,
+                                                                current(ctx->probe_grid.coefficients, ctx->d_probe_grid_coefficients), written, written_bytes, &why))
+        return fail(ctx, (int)rs, "%s: %s", who, why);
+    return SRT_OK;
+}
+
+// the record of an affected trace under the mode with SRT_PROBE_TAIL_COUNT_WORK, zeroed on the stream in front of it
+static int zero_probe_tail_work(srt_context* ctx) {
+    if (!ctx->probe_tail.enabled || !(ctx->probe_tail.call.flags & SRT_PROBE_TAIL_COUNT_WORK)) return SRT_OK;
+    return zero_work(ctx, ctx->d_probe_tail_work, srt::PT_WORK_N);
+}
+
+// the tail's kernel argument: the grid and the arrays current now, as shade_probe_grid takes them
+static srt::ProbeTailIO probe_tail_io(srt_context* ctx) {
+    const srt::ProbeTailCall& c = ctx->probe_tail.call;
+    const srt::ProbeGrid& g = ctx->probe_grid.grid;
+    srt::ProbeTailIO io{};
+    io.coefficients = current(ctx->probe_grid.coefficients, ctx->d_probe_grid_coefficients);
+    if (c.flags & SRT_PROBE_TAIL_DEPTH) {
+        io.depth = current(ctx->probe_grid_depth.moments, ctx->d_probe_grid_depth);
+        io.resolution = ctx->probe_grid_depth.resolution();
+    }
+    if (c.flags & SRT_PROBE_TAIL_STATES) io.states = current(ctx->probe_states.states, ctx->d_probe_grid_states);
+    for (int a = 0; a < 3; ++a) io.origin[a] = g.origin[a], io.spacing[a] = g.spacing[a], io.counts[a] = g.counts[a], io.band_weight[a] = c.band_weight[a];
+    io.flags = c.flags & (SRT_PROBE_TAIL_NORMAL_WEIGHT | SRT_PROBE_TAIL_DEPTH | SRT_PROBE_TAIL_STATES);
+    io.bias = c.bias, io.min_variance = c.min_variance;
+    io.work = (c.flags & SRT_PROBE_TAIL_COUNT_WORK) ? (unsigned long long*)ctx->d_probe_tail_work : nullptr;
+    return io;
+}
+
 // The sample scratch of the three sample-pool launches (srt_trace_radiance, srt_trace_light_probes, srt_render_adaptive; one
 // stream runs them all): every wave of a grid of `wgs` workgroups has its own region.  Grown once the stream has finished with
 // the smaller one.
@@ -2121,6 +2169,10 @@ int srt_trace_radiance(srt_context* ctx, const srt_radiance_params* t) {
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = ctx->rays.count();
     const bool count = (t->flags & SRT_RADIANCE_COUNT_WORK) != 0;
+    const bool tail = srt::probe_tail_applies(ctx->probe_tail, t->max_bounces);
+    if (tail) {  // the output where it stands now (an own buffer that is about to be allocated cannot be the bound coefficient array)
+        if (const int rc = check_probe_tail(ctx, "srt_trace_radiance", current(ctx->radiance_out, ctx->d_radiance_own), n * sizeof(float4))) return rc;
+    }
     float4* dst = nullptr;
     SRT_WRITE_TARGET_AFTER(ctx, ctx->radiance_out, ctx->d_radiance_own, n * sizeof(float4), dst, radiance_output_released(ctx));
     srt::KernelParams K;
@@ -2129,12 +2181,14 @@ int srt_trace_radiance(srt_context* ctx, const srt_radiance_params* t) {
     K.first_sample = t->first_sample, K.sample_count = t->sample_count, K.max_bounces = t->max_bounces, K.seed = t->seed;
     if (t->flags & SRT_RADIANCE_RESET) K.flags |= SRT_RENDER_RESET;
     const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::radiance_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    const auto tail_kernel = SRT_KERNEL_LDS_MESH(srt::radiance_tail_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0);
     // the grid first: the sample scratch is sized by it
-    const unsigned wgs = srt::radiance_grid(n, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
+    const unsigned wgs = srt::radiance_grid(n, srt::OUT_WG_UNITS, resident_workgroups(ctx, tail ? (const void*)tail_kernel : (const void*)kernel, ks.lds_bytes));
     if (const int rc = ensure_sample_rows(ctx, wgs)) return rc;
     if (count) {
         if (const int rc = zero_work(ctx, ctx->d_radiance_work, srt::RAD_WORK_N)) return rc;
     }
+    if (const int rc = zero_probe_tail_work(ctx)) return rc;
     srt::RadianceIO io{};
     io.origin = ctx->rays.bound() ? (const float4*)ctx->rays.bound_origin : (const float4*)ctx->d_ray_origin;
     io.direction = ctx->rays.bound() ? (const float4*)ctx->rays.bound_direction : (const float4*)ctx->d_ray_direction;
@@ -2144,8 +2198,9 @@ int srt_trace_radiance(srt_context* ctx, const srt_radiance_params* t) {
     io.out = dst;
     io.rows = ctx->d_radiance_rows;
     io.work = count ? (unsigned long long*)ctx->d_radiance_work : nullptr;
-    if (const int rc = launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
+    if (const int rc = tail ? launch_persistent_tail(ctx, tail_kernel, wgs, ks, K, io, probe_tail_io(ctx)) : launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
     srt::radiance_traced(ctx->radiance, n, dst, t->flags);
+    srt::probe_tail_traced(ctx->probe_tail);
     return SRT_OK;
 }
 
@@ -2238,6 +2293,13 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
     if (listed) {
         if (const srt::RaysStatus rs = srt::probe_list_check_trace(ctx->probe_update, np, &why)) return fail(ctx, (int)rs, "%s: %s", who, why);
     }
+    const bool tail = srt::probe_tail_applies(ctx->probe_tail, t->max_bounces);
+    if (tail) {  // the outputs this call writes, where they stand now: COEFFICIENTS, and RADIANCE as srt_trace_radiance's
+        for (int i = 0; i < srt::LIGHT_PROBE_SLOTS; ++i)
+            if (t->outputs & (1u << i))
+                if (const int rc = check_probe_tail(ctx, who, current(ctx->probe_out[i], ctx->d_probe_out_own[i]), srt::light_probe_elems(i, np, nk) * sizeof(float4)))
+                    return rc;
+    }
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t J = srt::light_probe_blocks(nk);
     const bool count = (t->flags & SRT_LIGHT_PROBE_COUNT_WORK) != 0;
@@ -2259,12 +2321,19 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
     if (t->flags & SRT_LIGHT_PROBE_RESET) K.flags |= SRT_RENDER_RESET;
     const auto kernel = listed ? SRT_KERNEL_LDS_MESH_COUNT_LISTED(srt::light_probe_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count)
                                : SRT_KERNEL_LDS_MESH_COUNT(srt::light_probe_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
+    const auto tail_kernel = listed ? (in_lds ? (mesh ? srt::light_probe_tail_kernel<true, true, true> : srt::light_probe_tail_kernel<true, false, true>)
+                                              : (mesh ? srt::light_probe_tail_kernel<false, true, true> : srt::light_probe_tail_kernel<false, false, true>))
+                                    : (in_lds ? (mesh ? srt::light_probe_tail_kernel<true, true, false> : srt::light_probe_tail_kernel<true, false, false>)
+                                              : (mesh ? srt::light_probe_tail_kernel<false, true, false> : srt::light_probe_tail_kernel<false, false, false>));
     // the grid first: the sample scratch is sized by it
-    const unsigned wgs = srt::light_probe_grid(np, nk, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
+    const unsigned wgs =
+        srt::light_probe_grid(np, nk, srt::OUT_WG_UNITS, resident_workgroups(ctx, tail ? (const void*)tail_kernel : (const void*)kernel, ks.lds_bytes));
     if (const int rc = ensure_sample_rows(ctx, wgs)) return rc;
     if (count) {
         if (const int rc = zero_work(ctx, ctx->d_probe_work, srt::LP_WORK_N)) return rc;
     }
+    if (const int rc = zero_probe_tail_work(ctx)) return rc;
     srt::LightProbeIO io{};
     io.position = current(ctx->probes.positions, ctx->d_probe_position);
     io.direction = current(ctx->probes.directions, ctx->d_probe_direction);
@@ -2277,7 +2346,7 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
     io.rows = ctx->d_radiance_rows;
     io.work = count ? (unsigned long long*)ctx->d_probe_work : nullptr;
     io.list = listed ? current_probe_list(ctx) : nullptr;
-    if (const int rc = launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
+    if (const int rc = tail ? launch_persistent_tail(ctx, tail_kernel, wgs, ks, K, io, probe_tail_io(ctx)) : launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
     if (J > 1 && coefficients) {  // the block sums of every probe, added in ascending block order
         const size_t elems = np * (size_t)srt::LP_COEFFS;
         if (listed)
@@ -2290,6 +2359,7 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
     }
     void* const wrote[srt::LIGHT_PROBE_SLOTS] = {dst[0], dst[1]};
     srt::light_probe_traced(ctx->probes, np, nk, t->outputs, wrote, t->flags);
+    srt::probe_tail_traced(ctx->probe_tail);
     return SRT_OK;
 }
 
@@ -3243,6 +3313,44 @@ int srt_mirror_history(srt_context* ctx, const srt_mirror_history_params* m) {
                     (double)m->radius_pixels, m->flags, m->reserved);
     // a history of the other mode carries or lacks the tags this one relies on: the next call starts afresh
     if (srt::mirror_history_set(ctx->mirror, call)) ctx->tp_valid = false, ctx->mom_history = false;
+    return SRT_OK;
+}
+
+// ---- probe tail ----------------------------------------------------------------------------------------------------
+static_assert(sizeof(srt_probe_tail_params) == 32 && sizeof(srt::ProbeTailCall) == 32 && sizeof(srt_probe_tail_work) == 56 && srt::PT_WORK_N == 6 &&
+                  SRT_PROBE_TAIL_NORMAL_WEIGHT == srt::PROBE_TAIL_FLAG_NORMAL_WEIGHT && SRT_PROBE_TAIL_DEPTH == srt::PROBE_TAIL_FLAG_DEPTH &&
+                  SRT_PROBE_TAIL_STATES == srt::PROBE_TAIL_FLAG_STATES && SRT_PROBE_TAIL_COUNT_WORK == srt::PROBE_TAIL_FLAG_COUNT_WORK &&
+                  SRT_PROBE_TAIL_NORMAL_WEIGHT == srt::PT_NORMAL_WEIGHT && SRT_PROBE_TAIL_DEPTH == srt::PT_DEPTH && SRT_PROBE_TAIL_STATES == srt::PT_STATES,
+              "srt_probe_tail_host.h, srt_probe_tail.hip.h and srt_pathtrace.h disagree");
+
+int srt_probe_tail_params_default(srt_probe_tail_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    const srt::ProbeTailCall c = srt::probe_tail_defaults();
+    memcpy(out, &c, sizeof c);
+    return SRT_OK;
+}
+
+int srt_probe_tail(srt_context* ctx, const srt_probe_tail_params* t) {
+    if (!ctx || !t) return SRT_ERR_INVALID_ARG;
+    srt::ProbeTailCall call;
+    memcpy(&call, t, sizeof call);
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_tail_check(call, &why))
+        return fail(ctx, (int)rs, "srt_probe_tail: %s (enabled %d, flags 0x%x, band_weight %g %g %g, bias %g, min_variance %g, reserved %u)", why, t->enabled, t->flags,
+                    (double)t->band_weight[0], (double)t->band_weight[1], (double)t->band_weight[2], (double)t->bias, (double)t->min_variance, t->reserved);
+    srt::probe_tail_set(ctx->probe_tail, call);  // (an enqueued launch keeps the setting it was given: a kernel argument)
+    return SRT_OK;
+}
+
+int srt_get_probe_tail_work(srt_context* ctx, srt_probe_tail_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::probe_tail_check_work(ctx->probe_tail) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_tail_work: the last radiance or light-probe trace did not run under srt_probe_tail with SRT_PROBE_TAIL_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::PT_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_probe_tail_work, w, srt::PT_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0;
+    out->tails = w[srt::PT_WORK_TAILS], out->corners = w[srt::PT_WORK_CORNERS], out->open = w[srt::PT_WORK_OPEN], out->dark = w[srt::PT_WORK_DARK];
+    out->mirror_ends = w[srt::PT_WORK_MIRROR_ENDS], out->wave_lookups = w[srt::PT_WORK_WAVE_LOOKUPS];
     return SRT_OK;
 }
 

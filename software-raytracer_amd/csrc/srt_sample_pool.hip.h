@@ -30,6 +30,7 @@
 #pragma once
 
 #include "srt_kernel.hip.h"
+#include "srt_probe_tail.hip.h"
 
 namespace srt {
 
@@ -63,11 +64,13 @@ __device__ __forceinline__ void stage_scene(const KernelParams& P, float4* lds_s
 // (lane k adds counter k).  Without ON there is no atomic.
 template <bool ON, int N>
 struct WaveWork {
+    static constexpr bool TAIL = false;
     __device__ __forceinline__ void add(int, unsigned long long) {}
     __device__ __forceinline__ void flush(unsigned long long*, int) const {}
 };
 template <int N>
 struct WaveWork<true, N> {
+    static constexpr bool TAIL = false;
     unsigned long long n[N] = {};
     __device__ __forceinline__ void add(int i, unsigned long long v) { n[i] += v; }
     __device__ __forceinline__ void flush(unsigned long long* work, int lane) const {
@@ -75,6 +78,18 @@ struct WaveWork<true, N> {
 #pragma unroll
         for (int k = 0; k < N; ++k) v = lane == k ? n[k] : v;
         if (lane < N) atomicAdd(&work[lane], v);
+    }
+};
+// the work counts of a TAIL instantiation (srt_probe_tail.hip.h): run_sample_pool ends a path that reaches the bounce limit on a
+// surface in the probe grid when its Work says TAIL, and finds the tail's kernel argument and sums here.  Both records' sums are
+// always kept (they are scalar) and flushed when the launch has the record.
+template <int N>
+struct TailWaveWork : WaveWork<true, N> {
+    static constexpr bool TAIL = true;
+    ProbeTail tail;
+    __device__ __forceinline__ void flush(unsigned long long* work, int lane) const {
+        if (work) WaveWork<true, N>::flush(work, lane);
+        tail.flush(lane);
     }
 };
 
@@ -293,6 +308,8 @@ __device__ __forceinline__ void pool_fold_rows(const Src& src, const float4* row
 
 // ---- the pool over (slot, sample): lane l owns slot l, whose record the caller has written (and passed a wave barrier since);
 // `rows` is the wave's region of the scratch, `acc` the owner's running mean.  Every lane of the wave calls it.
+// A Work with TAIL (TailWaveWork) ends a path that reaches the bounce limit on a surface in the probe grid (srt_probe_tail.hip.h);
+// the tail travels inside the Work, not as a parameter, so that the other instantiations compile to what they did.
 template <bool MESH, bool SCENE_LDS, class Src, class Work>
 __device__ __forceinline__ void run_sample_pool(const Lds& S, const KernelParams& P, const Src& src, float4* rows, int lane, float4& acc, Work& W SRT_PROF_PARAM) {
     unsigned* const match = reinterpret_cast<unsigned*>(S.work);
@@ -319,7 +336,20 @@ __device__ __forceinline__ void run_sample_pool(const Lds& S, const KernelParams
             const Hit h = closest_hit<MESH, false, SCENE_LDS>(S, P, o, t.sray, busy, 1, deferred, no_tally SRT_PROF_ARG);
             W.add(Src::WAVE_CALLS, 1ull);
             W.add(Src::CLOSEST, wave_lanes(busy));
-            if (busy) {
+            if constexpr (Work::TAIL) {  // rules T1 - T6: the lookup runs in wave-uniform control flow, between the hit and the row
+                uint32_t atag = 0u;
+                const bool ended = busy && pool_hit_update(S, h, B, t, atag);
+                // T1, T2: the limit was reached on a surface; T and spec are that hit's, no draw is consumed
+                const bool term = ended && h.prim >= 0;
+                float g = 0.0f;
+                if (term) g = 1.0f - (S.mat(t.hprim, 0).x * t.spec);  // T3 (:175)
+                RGB add;
+                if (probe_tail_lookup(W.tail, term, t.hp, t.hn, t.T, g, add)) t.L = RGB{t.L.r + add.r, t.L.g + add.g, t.L.b + add.b};  // T5
+                if (ended) {
+                    pool_store_row(rows, c0, atag, t);
+                    busy = false;
+                }
+            } else if (busy) {
                 uint32_t atag = 0u;
                 if (pool_hit_update(S, h, B, t, atag)) {
                     pool_store_row(rows, c0, atag, t);

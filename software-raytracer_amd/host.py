@@ -20,6 +20,7 @@ from .capi import (PROBE_CLASSIFY_COUNT_WORK, PROBE_CLASSIFY_NORMALIZE, PROBE_CL
 from .capi import (PROBE_BLEND_COUNT_WORK, PROBE_BLEND_LISTED, PROBE_BLEND_MOMENTS, PROBE_BLEND_PREVIOUS_STATES, PROBE_BURIED, PROBE_HISTORY_COEFFICIENTS,
                    PROBE_HISTORY_MOMENTS, PROBE_IDLE, PROBE_LIST_COUNT_WORK, PROBE_LIST_HEADER, ProbeBlendParams, ProbeBlendWork, ProbeListParams,
                    ProbeListWork)  # noqa: F401
+from .capi import PROBE_TAIL_COUNT_WORK, PROBE_TAIL_DEPTH, PROBE_TAIL_NORMAL_WEIGHT, PROBE_TAIL_STATES, ProbeTailParams, ProbeTailWork  # noqa: F401
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_PKG, "libsrt_host.so")
@@ -48,6 +49,7 @@ EXPORTS = [
     "srt_host_renderer_render_visibility", "srt_host_renderer_read_visibility", "srt_host_renderer_visibility_work",
     "srt_host_renderer_render_reflection", "srt_host_renderer_read_reflection", "srt_host_renderer_reflection_work",
     "srt_host_renderer_reflection_guides", "srt_host_renderer_mirror_history",
+    "srt_host_renderer_probe_tail", "srt_host_renderer_probe_tail_work",
     "srt_host_renderer_trace_radiance", "srt_host_renderer_read_radiance", "srt_host_renderer_radiance_work",
     "srt_host_renderer_trace_light_probes", "srt_host_renderer_read_light_probe_output", "srt_host_renderer_light_probe_work",
     "srt_host_renderer_set_probe_grid", "srt_host_renderer_shade_probe_grid", "srt_host_renderer_read_probe_grid_output",
@@ -150,6 +152,8 @@ def load_library():
     L.srt_host_renderer_reflection_work.argtypes = [vp, C.POINTER(ReflectionWork)]
     L.srt_host_renderer_reflection_guides.argtypes = [vp, C.c_int, C.c_int]
     L.srt_host_renderer_mirror_history.argtypes = [vp, C.c_int, C.c_float]
+    L.srt_host_renderer_probe_tail.argtypes = [vp, C.POINTER(ProbeTailParams)]
+    L.srt_host_renderer_probe_tail_work.argtypes = [vp, C.POINTER(ProbeTailWork)]
     L.srt_host_renderer_trace_radiance.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.POINTER(RadianceParams)]
     L.srt_host_renderer_read_radiance.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_host_renderer_radiance_work.argtypes = [vp, C.POINTER(RadianceWork)]
@@ -856,6 +860,33 @@ class Renderer:
         the virtual image of what they show (it renders the reflection outputs the mode reads itself).  radius_pixels:
         mirrorRadius (None: as it stands).  Switching drops the history."""
         self._ck(self.L.srt_host_renderer_mirror_history(self._h, 1 if on else 0, -1.0 if radius_pixels is None else float(radius_pixels)))
+
+    def probe_tail(self, enabled=True, normal_weight=False, depth=False, states=False, band_weight=None, count_work=False, bias=None,
+                   min_variance=None):
+        """PathTraceRenderer::probeTail: with `enabled`, trace_radiance() and the light-probe traces end a path that reaches the
+        bounce limit on a surface in the probe grid as it stands at the trace (capi.PathTracer.probe_tail says the rest).
+        band_weight None: the library's default, the hemisphere mean."""
+        p = ProbeTailParams()
+        from . import capi
+
+        if capi.load_library().srt_probe_tail_params_default(C.byref(p)):
+            raise ValueError("srt_probe_tail_params_default")
+        p.enabled = 1 if enabled else 0
+        p.flags = ((PROBE_TAIL_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_TAIL_DEPTH if depth else 0) | (PROBE_TAIL_STATES if states else 0)
+                   | (PROBE_TAIL_COUNT_WORK if count_work else 0))
+        if band_weight is not None:
+            p.band_weight[:] = [float(v) for v in band_weight]
+        if bias is not None:
+            p.bias = float(bias)
+        if min_variance is not None:
+            p.min_variance = float(min_variance)
+        self._ck(self.L.srt_host_renderer_probe_tail(self._h, C.byref(p)))
+
+    def probe_tail_work(self):
+        """PathTraceRenderer::probeTailWork: the lookups of the last trace under probe_tail(count_work=True) as a dict."""
+        w = ProbeTailWork()
+        self._ck(self.L.srt_host_renderer_probe_tail_work(self._h, C.byref(w)))
+        return w.as_dict()
 
     def visibility_work(self):
         """PathTraceRenderer::visibilityWork: the work counts of the last render_visibility(count_work=True) as a dict."""

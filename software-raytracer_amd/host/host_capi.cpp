@@ -326,6 +326,9 @@ int srt_host_renderer_mirror_history(srt_host_renderer* h, int on, float radius_
         h->r->mirrorHistory(on != 0);
     })
 }
+// the probe tail of the radiance and light-probe traces (PathTraceRenderer::probeTail) and its work record
+int srt_host_renderer_probe_tail(srt_host_renderer* h, const srt_probe_tail_params* p) { SRT_HOST_TRY(h, h->r->probeTail(*p)) }
+int srt_host_renderer_probe_tail_work(srt_host_renderer* h, srt_probe_tail_work* out) { SRT_HOST_TRY(h, *out = h->r->probeTailWork()) }
 int srt_host_renderer_read_ray_output(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->readRayOutput(output, dst)) }
 // denoiser over the whole frame with the guides as they stand (srt_denoise / srt_read_denoised)
 int srt_host_renderer_denoise(srt_host_renderer* h, const srt_denoise_params* p) { SRT_HOST_TRY(h, h->r->Denoise(*p)) }

@@ -232,6 +232,20 @@ void PathTraceRenderer::mirrorHistory(bool on) {
     mirror_history_ = on;
 }
 
+void PathTraceRenderer::probeTail(const srt_probe_tail_params& params) { check(srt_probe_tail(ctx_, &params), "srt_probe_tail"); }
+
+void PathTraceRenderer::writeProbeGridInputs(const float* coefficients, const float* moments, const float* states, size_t probes, uint32_t resolution) {
+    if (coefficients) check(srt_write_probe_grid_coefficients(ctx_, coefficients, probes), "srt_write_probe_grid_coefficients");
+    if (moments) check(srt_write_probe_grid_depth(ctx_, moments, probes, resolution), "srt_write_probe_grid_depth");
+    if (states) check(srt_write_probe_grid_states(ctx_, states, probes), "srt_write_probe_grid_states");
+}
+
+srt_probe_tail_work PathTraceRenderer::probeTailWork() {
+    srt_probe_tail_work w{};
+    check(srt_get_probe_tail_work(ctx_, &w), "srt_get_probe_tail_work");
+    return w;
+}
+
 void PathTraceRenderer::FirstHitScope::rebind(PathTraceRenderer& r) noexcept {
     try {
         r.bind_guides(true);

@@ -305,6 +305,14 @@ class PathTraceRenderer {
     void mirrorHistory(bool on);
     bool mirrorHistory() const { return mirror_history_; }
     float mirrorRadius = 2.0f;
+    // Probe tail (srt_probe_tail): with params.enabled the radiance and light-probe traces end a path that reaches the bounce limit
+    // on a surface in the probe grid as it stands at the trace.  probeTailWork waits and returns the counts of
+    // the last such trace that had SRT_PROBE_TAIL_COUNT_WORK.
+    void probeTail(const srt_probe_tail_params& params);
+    // What the tail (and the shading calls) read, without shading: each array that is given is written (coefficients probes x 9
+    // float4, moments probes x resolution^2 float4, states probes float4); the grid is setProbeGrid's.
+    void writeProbeGridInputs(const float* coefficients, const float* moments, const float* states, size_t probes, uint32_t resolution);
+    srt_probe_tail_work probeTailWork();
     // One variance-guided denoised frame (whole frame only): push the camera, render spp / 2 samples with SRT_RENDER_RESET and
     // the frame's seed into the accumulator, spp / 2 with seed ^ 0x9E3779B9 into the handle's half buffer through
     // srt_bind_output (the binding is restored), the four guides, srt_variance with SRT_VARIANCE_MERGE, then

@@ -92,8 +92,15 @@ static int write_reflection(PathTraceRenderer& r, const std::string& prefix, int
 // With --any-hit the rays go through srt_trace_occlusion instead and OUT.bin receives the occluded array (N int32) alone.
 // With --radiance N (radiance_samples > 0) they go through srt_trace_radiance — samples 1..N, `bounces`, `seed`, id_base 0 — and
 // OUT.bin receives the N float4 running means alone.
+// With `tail` (--probe-tail: a grid, P x 9 float4 coefficients and SRT_PROBE_TAIL_* flags) the radiance trace runs under srt_probe_tail.
+struct RayTail {
+    const srt_probe_grid* grid = nullptr;
+    std::vector<float> coefficients;
+    uint32_t flags = 0;
+};
+
 static int trace_ray_file(const Scene& scene, int device, const std::string& in, const std::string& out, bool normalize, bool any_hit,
-                          int radiance_samples, int bounces, unsigned seed) {
+                          int radiance_samples, int bounces, unsigned seed, const RayTail& tail = RayTail()) {
     FILE* f = std::fopen(in.c_str(), "rb");
     if (!f) {
         std::perror(in.c_str());
@@ -121,6 +128,14 @@ static int trace_ray_file(const Scene& scene, int device, const std::string& in,
             srt_radiance_params_default(&rp);
             rp.sample_count = (uint32_t)radiance_samples, rp.max_bounces = bounces, rp.seed = seed;
             if (normalize) rp.flags |= SRT_RADIANCE_NORMALIZE;
+            if (tail.grid) {
+                r.setProbeGrid(*tail.grid);
+                r.writeProbeGridInputs(tail.coefficients.data(), nullptr, nullptr, tail.coefficients.size() / 36, 0);
+                srt_probe_tail_params tp{};
+                srt_probe_tail_params_default(&tp);
+                tp.flags = tail.flags;
+                r.probeTail(tp);
+            }
             r.traceRadiance(o.data(), d.data(), n, rp);
             std::vector<float> rad(4 * n);
             r.readRadiance(rad.data());
@@ -302,9 +317,29 @@ struct ProbeUpdateOptions {
     float hysteresis = 0.9f;
 };
 
+// --probe-tail [--probe-tail-depth] [--probe-tail-states] [--probe-tail-normal-weight]: srt_probe_tail for the traces of a flow.
+// With --rays --radiance N the grid and its coefficients come from --probe-tail-grid G and --probe-tail-coefficients FILE.f32 (P x 9
+// float4: what --probes-out writes for the grid's positions); depth maps and records exist in the --probe-grid flow only.
+// With --probe-grid: --probe-feedback F (1..4096; --probe-tail alone means 2) runs F rounds of (trace the probes at --probe-bounces B
+// bounces, default --bounces, seed = the round, then srt_blend_probes with the library's defaults into the coefficient history);
+// round 1 has no history and runs with the mode off, every later round runs with the tail reading the history (copied through the
+// host into the grid's coefficient array: the trace writes its own output, never the array it reads), with the flow's depth maps
+// (--probe-depth R) under --probe-tail-depth and its records (--probe-classify) under --probe-tail-states.  The frame is shaded
+// from the history.
+struct ProbeTailOptions {
+    bool on = false, depth = false, states = false, normal_weight = false;
+    int feedback = 0;  // 0: no --probe-feedback
+    int bounces = -1;  // < 0: --bounces
+    std::string grid, coefficients;
+    uint32_t flags() const {
+        return (depth ? SRT_PROBE_TAIL_DEPTH : 0u) | (states ? SRT_PROBE_TAIL_STATES : 0u) | (normal_weight ? SRT_PROBE_TAIL_NORMAL_WEIGHT : 0u);
+    }
+};
+
 static int shade_probe_grid_file(Scene& scene, int device, int W, int H, int fov, const srt_probe_grid& grid, int directions, int samples, int bounces,
                                  unsigned seed, uint32_t flags, bool hemisphere, const std::string& out, const ProbeDepthOptions& depth,
-                                 const ProbeClassifyOptions& classify, const ProbeUpdateOptions& update, const std::vector<ObjectMove>& moves) {
+                                 const ProbeClassifyOptions& classify, const ProbeUpdateOptions& update, const std::vector<ObjectMove>& moves,
+                                 const ProbeTailOptions& tail) {
     const size_t np = (size_t)grid.counts[0] * (size_t)grid.counts[1] * (size_t)grid.counts[2];
     std::vector<float> pos(4 * np), dir(4 * (size_t)directions);
     if (srt_probe_grid_positions(&grid, pos.data()) != SRT_OK) {
@@ -339,6 +374,7 @@ static int shade_probe_grid_file(Scene& scene, int device, int W, int H, int fov
             if (!classify.out.empty() && !moves.size() && !write_floats(classify.out, states)) return 1;
         }
         std::vector<float> coeff(np * 9 * 4), moments;
+        bool have_moments = false;  // (the feedback rounds trace the maps up front)
         srt_probe_depth_params dp{};
         srt_probe_depth_params_default(&dp);
         if (depth.resolution) {
@@ -384,6 +420,39 @@ static int shade_probe_grid_file(Scene& scene, int device, int W, int H, int fov
             if (!classify.out.empty() && moves.size() && !write_floats(classify.out, states)) return 1;  // (the records of the last frame)
             r.readProbeHistory(SRT_PROBE_HISTORY_COEFFICIENTS, coeff.data());
             if (depth.resolution) r.readProbeHistory(SRT_PROBE_HISTORY_MOMENTS, moments.data());
+        } else if (tail.feedback) {
+            r.setProbeGrid(grid);
+            if (depth.resolution) {  // the maps the tail reads under --probe-tail-depth, and the shading after the last round
+                r.traceProbeDepth(pos.data(), np, dir.data(), (size_t)directions, dp);
+                r.readProbeDepthOutput(SRT_PROBE_DEPTH_MOMENTS, moments.data());
+                have_moments = true;
+            }
+            r.resetProbeHistory(SRT_PROBE_HISTORY_COEFFICIENTS, np, 0);
+            srt_probe_blend_params bp{};
+            srt_probe_blend_params_default(&bp);
+            srt_probe_tail_params tp{};
+            srt_probe_tail_params_default(&tp);
+            tp.flags = tail.flags() | SRT_PROBE_TAIL_COUNT_WORK;
+            if (tail.bounces >= 0) lp.max_bounces = tail.bounces;
+            for (int f = 1; f <= tail.feedback; ++f) {
+                tp.enabled = f > 1 ? 1 : 0;  // round 1 has no history
+                if (f > 1) {
+                    r.readProbeHistory(SRT_PROBE_HISTORY_COEFFICIENTS, coeff.data());
+                    r.writeProbeGridInputs(coeff.data(), tail.depth ? moments.data() : nullptr, tail.states ? states.data() : nullptr, np, (uint32_t)depth.resolution);
+                }
+                r.probeTail(tp);
+                lp.seed = (uint32_t)f;
+                r.traceLightProbes(pos.data(), np, dir.data(), (size_t)directions, lp);
+                r.blendProbes(nullptr, np, bp);
+                if (f > 1) {
+                    const srt_probe_tail_work w = r.probeTailWork();
+                    std::fprintf(stderr, "probe feedback round %d: %llu lookups, %llu dark, %llu mirror ends\n", f, (unsigned long long)w.tails,
+                                 (unsigned long long)w.dark, (unsigned long long)w.mirror_ends);
+                }
+            }
+            tp.enabled = 0;
+            r.probeTail(tp);
+            r.readProbeHistory(SRT_PROBE_HISTORY_COEFFICIENTS, coeff.data());
         } else {
             r.traceLightProbes(pos.data(), np, dir.data(), (size_t)directions, lp);
             r.readLightProbeOutput(SRT_LIGHT_PROBE_COEFFICIENTS, coeff.data());
@@ -394,7 +463,7 @@ static int shade_probe_grid_file(Scene& scene, int device, int W, int H, int fov
         if (hemisphere) sp.band_weight[0] = 1.0f, sp.band_weight[1] = 0.5f, sp.band_weight[2] = 0.0f;
         r.setProbeGrid(grid);
         if (depth.resolution) {
-            if (!update.frames) {
+            if (!update.frames && !have_moments) {
                 r.traceProbeDepth(pos.data(), np, dir.data(), (size_t)directions, dp);
                 r.readProbeDepthOutput(SRT_PROBE_DEPTH_MOMENTS, moments.data());
             }
@@ -530,7 +599,14 @@ static void usage() {
                  "             or --reflection-out\n"
                  "  --reflection-out PREFIX: also write the reflection guides as PREFIX_object.npy, PREFIX_normal_depth.npy, PREFIX_position.npy,\n"
                  "             PREFIX_albedo.npy (as --gbuffer's) and PREFIX_bounces.npy (int32 HxW: reflections followed); not with --devices\n"
-                 "             or --temporal\n");
+                 "             or --temporal\n"
+                 "  --probe-tail: srt_probe_tail: radiance and light-probe paths that reach the bounce limit on a surface add the probe grid's\n"
+                 "             radiance there.  With --rays --radiance N: the grid is --probe-tail-grid G (as --probe-grid's) and its coefficients\n"
+                 "             --probe-tail-coefficients FILE.f32 (P x 9 float4, what --probes-out writes); --probe-tail-normal-weight: rule 6.\n"
+                 "             With --probe-grid: --probe-feedback F (1..4096; --probe-tail alone: 2) rounds of (trace the probes at\n"
+                 "             --probe-bounces B bounces, default --bounces, with the tail reading the coefficient history, then\n"
+                 "             srt_blend_probes); round 1 runs with the mode off; the frame is shaded from the history;\n"
+                 "             --probe-tail-depth needs --probe-depth R, --probe-tail-states needs --probe-classify; not with --probe-update\n");
 }
 
 int main(int argc, char** argv) {
@@ -546,6 +622,8 @@ int main(int argc, char** argv) {
     ProbeClassifyOptions probe_classify;
     bool probe_classify_option = false;
     ProbeUpdateOptions probe_update;
+    ProbeTailOptions probe_tail;
+    bool probe_feedback_given = false, probe_bounces_given = false;
     bool probe_update_given = false, probe_update_option = false;
     int adaptive = 0, adaptive_max = 0;
     bool adaptive_given = false, adaptive_threshold_given = false, adaptive_max_given = false;
@@ -631,6 +709,14 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--states-out")) probe_classify.out = need("--states-out"), probe_classify_option = true;
         else if (!std::strcmp(argv[i], "--probe-update")) probe_update.frames = std::atoi(need("--probe-update")), probe_update_given = true;
         else if (!std::strcmp(argv[i], "--probe-hysteresis")) probe_update.hysteresis = std::strtof(need("--probe-hysteresis"), nullptr), probe_update_option = true;
+        else if (!std::strcmp(argv[i], "--probe-tail")) probe_tail.on = true;
+        else if (!std::strcmp(argv[i], "--probe-tail-depth")) probe_tail.depth = true;
+        else if (!std::strcmp(argv[i], "--probe-tail-states")) probe_tail.states = true;
+        else if (!std::strcmp(argv[i], "--probe-tail-normal-weight")) probe_tail.normal_weight = true;
+        else if (!std::strcmp(argv[i], "--probe-tail-grid")) probe_tail.grid = need("--probe-tail-grid");
+        else if (!std::strcmp(argv[i], "--probe-tail-coefficients")) probe_tail.coefficients = need("--probe-tail-coefficients");
+        else if (!std::strcmp(argv[i], "--probe-feedback")) probe_tail.feedback = std::atoi(need("--probe-feedback")), probe_feedback_given = true;
+        else if (!std::strcmp(argv[i], "--probe-bounces")) probe_tail.bounces = std::atoi(need("--probe-bounces")), probe_bounces_given = true;
         else if (!std::strcmp(argv[i], "--probe-samples")) probe_update.samples = std::atoi(need("--probe-samples")), probe_update_option = true;
         else if (!std::strcmp(argv[i], "--adaptive")) adaptive = std::atoi(need("--adaptive")), adaptive_given = true;
         else if (!std::strcmp(argv[i], "--adaptive-threshold")) adaptive_threshold = std::strtof(need("--adaptive-threshold"), nullptr), adaptive_threshold_given = true;
@@ -741,6 +827,33 @@ int main(int argc, char** argv) {
             !(probe_update.hysteresis < 1.0f)) {
             std::fprintf(stderr, "--probe-update takes 1..4096 frames, --probe-samples 1..4096, --probe-hysteresis a value in [0, 1)\n");
             return 2;
+        }
+    }
+    srt_probe_grid tail_grid{};
+    if (probe_tail.on || probe_tail.depth || probe_tail.states || probe_tail.normal_weight || probe_feedback_given || probe_bounces_given ||
+        !probe_tail.grid.empty() || !probe_tail.coefficients.empty()) {
+        if (!probe_grid_arg.empty()) {  // the --probe-grid flow: feedback rounds
+            if (!probe_tail.grid.empty() || !probe_tail.coefficients.empty() || probe_update_given) {
+                std::fprintf(stderr, "--probe-tail with --probe-grid reads the flow's own grid and history: no --probe-tail-grid / --probe-tail-coefficients, not with --probe-update\n");
+                return 2;
+            }
+            if (!probe_feedback_given) probe_tail.feedback = 2;
+            if (probe_tail.feedback < 1 || probe_tail.feedback > 4096 || (probe_bounces_given && probe_tail.bounces < 0)) {
+                std::fprintf(stderr, "--probe-feedback takes 1..4096 rounds and --probe-bounces a count >= 0\n");
+                return 2;
+            }
+            if ((probe_tail.depth && !probe_depth_given) || (probe_tail.states && !probe_classify.on)) {
+                std::fprintf(stderr, "--probe-tail-depth needs --probe-depth R and --probe-tail-states needs --probe-classify\n");
+                return 2;
+            }
+            probe_tail.on = true;
+        } else {  // --rays --radiance N
+            if (!probe_tail.on || rays_in.empty() || !radiance_given || probe_tail.depth || probe_tail.states || probe_feedback_given || probe_bounces_given ||
+                probe_tail.grid.empty() || probe_tail.coefficients.empty() || !parse_probe_grid(probe_tail.grid.c_str(), &tail_grid)) {
+                std::fprintf(stderr, "--probe-tail goes with --probe-grid, or with --rays --radiance N --probe-tail-grid G --probe-tail-coefficients FILE.f32 "
+                                     "[--probe-tail-normal-weight] (depth maps, records and --probe-feedback exist in the --probe-grid flow only)\n");
+                return 2;
+            }
         }
     }
     if (!probe_grid_arg.empty() || !irradiance_out.empty() || probe_visibility || probe_normal_weight || probe_albedo || probe_hemisphere) {
@@ -884,9 +997,21 @@ int main(int argc, char** argv) {
         return shade_probe_grid_file(scene, device, W, H, fov, probe_grid, probe_grid_directions, radiance_given ? radiance : 16, bounces, seed,
                                      (probe_visibility ? SRT_PROBE_GRID_VISIBILITY : 0u) | (probe_normal_weight ? SRT_PROBE_GRID_NORMAL_WEIGHT : 0u) |
                                          (probe_albedo ? SRT_PROBE_GRID_ALBEDO : 0u),
-                                     probe_hemisphere, irradiance_out, probe_depth, probe_classify, probe_update, object_moves);
+                                     probe_hemisphere, irradiance_out, probe_depth, probe_classify, probe_update, object_moves, probe_tail);
     if (!probes_in.empty()) return trace_probe_file(scene, device, probes_in, probe_directions, probes_out, probe_radiance_out, radiance_given ? radiance : 16, bounces, seed);
-    if (!rays_in.empty()) return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize, rays_any_hit, radiance_given ? radiance : 0, bounces, seed);
+    if (!rays_in.empty()) {
+        RayTail ray_tail;
+        if (probe_tail.on) {
+            ray_tail.coefficients = read_float4_file(probe_tail.coefficients);
+            const size_t np = (size_t)tail_grid.counts[0] * (size_t)tail_grid.counts[1] * (size_t)tail_grid.counts[2];
+            if (ray_tail.coefficients.size() != np * 36) {
+                std::fprintf(stderr, "--probe-tail-coefficients: want %zu probes x 9 float4 for the grid of --probe-tail-grid\n", np);
+                return 2;
+            }
+            ray_tail.grid = &tail_grid, ray_tail.flags = probe_tail.flags();
+        }
+        return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize, rays_any_hit, radiance_given ? radiance : 0, bounces, seed, ray_tail);
+    }
     auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {
         FILE* f = std::fopen(path.c_str(), "wb");
         if (!f) {
