@@ -1712,6 +1712,39 @@ int srt_probe_tail_params_default(srt_probe_tail_params* out);
 int srt_probe_tail(srt_context* ctx, const srt_probe_tail_params* params);
 int srt_get_probe_tail_work(srt_context* ctx, srt_probe_tail_work* out);
 
+/* ---- adaptive renders that end in the probe grid (ABI 7, backward compatible) ---------------------------------------------------
+ * This call was added without changing anything else, so SRT_ABI_VERSION stays 7.  srt_render_adaptive_tail is srt_render_adaptive
+ * (rules 1 - 10 of its block) with rules T1 - T6 of the probe-tail block applied to every sample's path: a picture — band,
+ * framebuffer, per-pixel counts and budget — whose paths take one or two bounces and a lookup in the probe grid.  It uses the
+ * context's srt_probe_tail setting (flags, band weights, bias, min_variance) and reads the grid, coefficients, depth maps and
+ * states CURRENT AT THE ENQUEUE, as the affected traces do.  The struct and its two flags are srt_render_adaptive's.
+ *
+ * R1. Order of checks.  First srt_render_adaptive's own errors, in its order (rule 9).  Then SRT_ERR_STATE when the context's tail
+ *     setting is off (there has been no accepted srt_probe_tail with enabled = 1, or a later one switched it off).  Then, only for
+ *     max_bounces >= 1, the refusals of an affected trace (probe-tail block: no grid, no coefficients, a count that is not
+ *     nx*ny*nz, DEPTH without maps, STATES without records), where "the buffer about to be written" is BOTH the current
+ *     accumulator and the current framebuffer (srt_bind_output): SRT_ERR_STATE when the coefficient array shares a byte with
+ *     either.  Nothing is touched on any refusal.
+ * R2. max_bounces == 0.  After R1's first two steps the call launches exactly what srt_render_adaptive launches and checks no
+ *     grid input (T1).
+ * R3. Equivalence.  After any sequence of srt_render_adaptive_tail calls that started from n_p = 0, with one seed, one bounce
+ *     count, one tail setting and unchanged grid inputs, pixel p's accumulator element equals element p of srt_trace_radiance's
+ *     output under the same mode on the frame's camera rays — origin the camera position, direction GetRayDirection, ray index
+ *     x + y*W, id_base = 0, first_sample = 1, sample_count = n_p, SRT_RADIANCE_RESET, the same seed and bounces — in all four
+ *     lanes (NaN as NaN); the framebuffer pixel is tone_map of that element at memory row H - 1 - y (adaptive rule 3).  The scene
+ *     in LDS or in memory, with or without meshes.  It does NOT hold from a start of srt_render(1..n) followed by
+ *     srt_set_sample_counts(n): srt_render's paths end without the lookup, so the two calls estimate different quantities and
+ *     their samples do not belong in one mean.  Start a tail frame from srt_set_sample_counts(0).
+ * R4. Zero coefficients.  With all coefficients zero the accumulator, the framebuffer, the counts and srt_adaptive_work are those
+ *     of srt_render_adaptive, bit for bit.
+ * R5. Adaptive rules 4 (untouched pixels), 5 (counts, KEEP_COUNTS), 6 (determinism), 7 and 8 hold unchanged.
+ * R6. Work records.  srt_get_adaptive_work treats this call as an adaptive render, under the same SRT_ADAPTIVE_COUNT_WORK rule.
+ *     srt_get_probe_tail_work treats it as the last affected trace (SRT_PROBE_TAIL_COUNT_WORK of the setting); the record is all
+ *     zeros under R2.  wave_lookups is deterministic here: a tile's pool drains before its wave takes another tile, so the count
+ *     does not depend on which wave drew the tile.
+ * R7. srt_render_adaptive, srt_render and every other pass behave exactly as before and still ignore the mode. */
+int srt_render_adaptive_tail(srt_context* ctx, const srt_adaptive_params* params);
+
 /* ---- per-frame probe updates: active-probe lists, listed traces and a hysteresis blend (ABI 7, backward compatible) ---------------
  * These calls were added without changing anything else, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of them
  * runs what it ran before, bit for bit.  They keep a classified probe grid alive from frame to frame: srt_list_probes compacts the

@@ -133,6 +133,7 @@ EXPORTS = [
     "srt_probe_blend_params_default", "srt_reset_probe_history", "srt_bind_probe_history", "srt_read_probe_history",
     "srt_write_probe_previous_states", "srt_bind_probe_previous_states", "srt_blend_probes", "srt_get_probe_blend_work",
     "srt_probe_tail_params_default", "srt_probe_tail", "srt_get_probe_tail_work",
+    "srt_render_adaptive_tail",
 ]
 
 
@@ -695,11 +696,13 @@ def open_library(path):
     L.srt_adaptive_params_default.argtypes = [C.POINTER(AdaptiveParams)]
     L.srt_render_adaptive.argtypes = [ctx, C.POINTER(AdaptiveParams)]
     L.srt_get_adaptive_work.argtypes = [ctx, C.POINTER(AdaptiveWork)]
+    if hasattr(L, "srt_render_adaptive_tail"):  # (as srt_probe_tail above)
+        L.srt_render_adaptive_tail.argtypes = [ctx, C.POINTER(AdaptiveParams)]
     L.srt_budget_params_default.argtypes = [C.POINTER(BudgetParams)]
     L.srt_sample_budget.argtypes = [ctx, C.POINTER(BudgetParams)]
     L.srt_get_budget_total.argtypes = [ctx, C.POINTER(C.c_uint64)]
     for name in EXPORTS:
-        if "probe_tail" in name and not hasattr(L, name):
+        if ("probe_tail" in name or name == "srt_render_adaptive_tail") and not hasattr(L, name):
             continue  # (a build of an earlier commit, opened by tests/ab_passes.py)
         fn = getattr(L, name)
         if name not in ("srt_last_error", "srt_gather_path"):
@@ -1491,10 +1494,10 @@ class PathTracer:
         self._ck(self.L.srt_get_budget_total(self._h, C.byref(t)))
         return int(t.value)
 
-    def render_adaptive(self, bounces=None, seed=0, max_samples=None, rows=None, keep_counts=False, count_work=False, flags=0, reserved=0):
+    def render_adaptive(self, bounces=None, seed=0, max_samples=None, rows=None, keep_counts=False, count_work=False, flags=0, reserved=0, tail=False):
         """srt_render_adaptive: every pixel of memory rows `rows` (default: the whole frame) takes min(budget, max_samples) more
         samples, continuing its running mean from its count; the counts advance unless keep_counts.  Arguments left at None take
-        srt_adaptive_params_default.  Asynchronous, like render()."""
+        srt_adaptive_params_default.  Asynchronous, like render().  (`tail` is render_adaptive_tail()'s switch.)"""
         p = AdaptiveParams()
         self._ck(self.L.srt_adaptive_params_default(C.byref(p)))
         p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
@@ -1505,7 +1508,13 @@ class PathTracer:
         p.seed = int(seed) & 0xFFFFFFFF
         p.flags = int(flags) | (ADAPTIVE_KEEP_COUNTS if keep_counts else 0) | (ADAPTIVE_COUNT_WORK if count_work else 0)
         p.reserved = int(reserved)
-        self._ck(self.L.srt_render_adaptive(self._h, C.byref(p)))
+        self._ck((self.L.srt_render_adaptive_tail if tail else self.L.srt_render_adaptive)(self._h, C.byref(p)))
+
+    def render_adaptive_tail(self, bounces=None, seed=0, max_samples=None, rows=None, keep_counts=False, count_work=False, flags=0, reserved=0):
+        """srt_render_adaptive_tail: render_adaptive() whose paths end in the probe grid under the probe_tail() setting (which must
+        be on), reading the grid, coefficients, depth maps and states as they stand now.  A tail frame starts from
+        set_sample_counts(0); adaptive_work() and probe_tail_work() report it."""
+        self.render_adaptive(bounces, seed, max_samples, rows, keep_counts, count_work, flags, reserved, tail=True)
 
     def adaptive_work(self):
         """srt_get_adaptive_work: the work counts of the last render_adaptive(count_work=True) as a dict.  Waits."""

@@ -53,6 +53,7 @@
 #include "srt_probe_tail_host.h"
 #include "srt_adaptive.hip.h"
 #include "srt_adaptive_host.h"
+#include "srt_adaptive_tail_host.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -3105,15 +3106,9 @@ int srt_adaptive_params_default(srt_adaptive_params* out) {
     return SRT_OK;
 }
 
-int srt_render_adaptive(srt_context* ctx, const srt_adaptive_params* a) {
-    if (!ctx || !a) return SRT_ERR_INVALID_ARG;
-    const srt::AdaptiveCall call{a->row_begin, a->row_end, a->max_bounces, a->seed, a->max_samples, a->flags, a->reserved};
-    uint32_t* const counts = current(ctx->counts, ctx->d_counts_own);
-    const uint32_t* const budget = current(ctx->budget, ctx->d_budget_own);
-    const char* why = "";
-    if (const srt::RaysStatus rs = srt::adaptive_check(call, ctx->scene_set, ctx->camera.set, ctx->height, counts != nullptr, budget != nullptr, &why))
-        return fail(ctx, (int)rs, "srt_render_adaptive: %s (rows [%d,%d) of %d, max_bounces %d, max_samples %u, flags 0x%x, reserved %u)", why, a->row_begin,
-                    a->row_end, ctx->height, a->max_bounces, a->max_samples, a->flags, a->reserved);
+// The launch of srt_render_adaptive and srt_render_adaptive_tail once the call is accepted: `tail` picks adaptive_tail_kernel
+// and gives it the tail's inputs as they stand now; without it the launch is srt_render_adaptive's.
+static int launch_adaptive(srt_context* ctx, const srt_adaptive_params* a, uint32_t* counts, const uint32_t* budget, bool tail) {
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const bool count = (a->flags & SRT_ADAPTIVE_COUNT_WORK) != 0;
     srt::KernelParams K;
@@ -3122,8 +3117,10 @@ int srt_render_adaptive(srt_context* ctx, const srt_adaptive_params* a) {
     K.max_bounces = a->max_bounces, K.seed = a->seed;
     K.accumulator = ctx->d_acc, K.framebuffer = ctx->d_fb;
     const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::adaptive_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    const auto tail_kernel = SRT_KERNEL_LDS_MESH(srt::adaptive_tail_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0);
     // the grid first: the sample scratch is sized by it
-    const unsigned wgs = srt::adaptive_grid(K.width, K.rows, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
+    const unsigned wgs = srt::adaptive_grid(K.width, K.rows, srt::OUT_WG_UNITS,
+                                            resident_workgroups(ctx, tail ? (const void*)tail_kernel : (const void*)kernel, ks.lds_bytes));
     if (const int rc = ensure_sample_rows(ctx, wgs)) return rc;
     if (!ctx->d_adaptive_ticket) SRT_HIP(ctx, ctx->d_adaptive_ticket.ensure(sizeof(uint32_t)));
     SRT_HIP(ctx, hipMemsetAsync(ctx->d_adaptive_ticket, 0, sizeof(uint32_t), ctx->stream));
@@ -3138,9 +3135,43 @@ int srt_render_adaptive(srt_context* ctx, const srt_adaptive_params* a) {
     io.ticket = ctx->d_adaptive_ticket;
     io.rows = ctx->d_radiance_rows;
     io.work = count ? (unsigned long long*)ctx->d_adaptive_work : nullptr;
-    if (const int rc = launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
+    if (const int rc = tail ? launch_persistent_tail(ctx, tail_kernel, wgs, ks, K, io, probe_tail_io(ctx)) : launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
     if (!io.keep_counts) ctx->counts.wrote(counts);
+    return SRT_OK;
+}
+
+int srt_render_adaptive(srt_context* ctx, const srt_adaptive_params* a) {
+    if (!ctx || !a) return SRT_ERR_INVALID_ARG;
+    const srt::AdaptiveCall call{a->row_begin, a->row_end, a->max_bounces, a->seed, a->max_samples, a->flags, a->reserved};
+    uint32_t* const counts = current(ctx->counts, ctx->d_counts_own);
+    const uint32_t* const budget = current(ctx->budget, ctx->d_budget_own);
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::adaptive_check(call, ctx->scene_set, ctx->camera.set, ctx->height, counts != nullptr, budget != nullptr, &why))
+        return fail(ctx, (int)rs, "srt_render_adaptive: %s (rows [%d,%d) of %d, max_bounces %d, max_samples %u, flags 0x%x, reserved %u)", why, a->row_begin,
+                    a->row_end, ctx->height, a->max_bounces, a->max_samples, a->flags, a->reserved);
+    if (const int rc = launch_adaptive(ctx, a, counts, budget, false)) return rc;
     srt::adaptive_rendered(ctx->adaptive, a->flags);
+    return SRT_OK;
+}
+
+// srt_render_adaptive under srt_probe_tail: rules R1 - R7 of srt_pathtrace.h; the order of the checks, which kernel runs and what
+// the call leaves behind are srt_adaptive_tail_host.h's
+int srt_render_adaptive_tail(srt_context* ctx, const srt_adaptive_params* a) {
+    if (!ctx || !a) return SRT_ERR_INVALID_ARG;
+    const srt::AdaptiveCall call{a->row_begin, a->row_end, a->max_bounces, a->seed, a->max_samples, a->flags, a->reserved};
+    uint32_t* const counts = current(ctx->counts, ctx->d_counts_own);
+    const uint32_t* const budget = current(ctx->budget, ctx->d_budget_own);
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::adaptive_tail_check(call, ctx->scene_set, ctx->camera.set, ctx->height, counts != nullptr, budget != nullptr, ctx->probe_tail,
+                                                            ctx->probe_grid, ctx->probe_grid_depth, ctx->probe_states,
+                                                            current(ctx->probe_grid.coefficients, ctx->d_probe_grid_coefficients),
+                                                            srt::adaptive_tail_targets(ctx->d_acc, ctx->d_fb, ctx->width, ctx->height), &why))
+        return fail(ctx, (int)rs, "srt_render_adaptive_tail: %s (rows [%d,%d) of %d, max_bounces %d, max_samples %u, flags 0x%x, reserved %u)", why, a->row_begin,
+                    a->row_end, ctx->height, a->max_bounces, a->max_samples, a->flags, a->reserved);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    if (const int rc = zero_probe_tail_work(ctx)) return rc;
+    if (const int rc = launch_adaptive(ctx, a, counts, budget, srt::adaptive_tail_launches_tail(ctx->probe_tail, call))) return rc;
+    srt::adaptive_tail_rendered(ctx->adaptive, ctx->probe_tail, a->flags);
     return SRT_OK;
 }
 

@@ -50,6 +50,7 @@ EXPORTS = [
     "srt_host_renderer_render_reflection", "srt_host_renderer_read_reflection", "srt_host_renderer_reflection_work",
     "srt_host_renderer_reflection_guides", "srt_host_renderer_mirror_history",
     "srt_host_renderer_probe_tail", "srt_host_renderer_probe_tail_work",
+    "srt_host_renderer_render_adaptive_tail", "srt_host_renderer_render_probe_tail_frame",
     "srt_host_renderer_trace_radiance", "srt_host_renderer_read_radiance", "srt_host_renderer_radiance_work",
     "srt_host_renderer_trace_light_probes", "srt_host_renderer_read_light_probe_output", "srt_host_renderer_light_probe_work",
     "srt_host_renderer_set_probe_grid", "srt_host_renderer_shade_probe_grid", "srt_host_renderer_read_probe_grid_output",
@@ -185,6 +186,8 @@ def load_library():
     L.srt_host_renderer_probe_blend_work.argtypes = [vp, C.POINTER(ProbeBlendWork)]
     L.srt_host_renderer_sample_budget.argtypes = [vp, C.POINTER(BudgetParams), C.POINTER(C.c_uint64)]
     L.srt_host_renderer_render_adaptive.argtypes = [vp, C.POINTER(AdaptiveParams)]
+    L.srt_host_renderer_render_adaptive_tail.argtypes = [vp, C.POINTER(AdaptiveParams)]
+    L.srt_host_renderer_render_probe_tail_frame.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32]
     L.srt_host_renderer_set_sample_counts.argtypes = [vp, C.c_uint32]
     L.srt_host_renderer_read_sample_counts.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.srt_host_renderer_adaptive_frame.argtypes = [vp, C.c_uint32, C.c_int, C.POINTER(BudgetParams), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
@@ -788,12 +791,21 @@ class Renderer:
         self._ck(self.L.srt_host_renderer_sample_budget(self._h, C.byref(self._budget_params(threshold, floor, max_budget, albedo)), C.byref(t)))
         return int(t.value)
 
-    def render_adaptive(self, bounces=8, seed=0, max_samples=4096, rows=None, keep_counts=False, count_work=False):
+    def render_adaptive(self, bounces=8, seed=0, max_samples=4096, rows=None, keep_counts=False, count_work=False, tail=False):
         """PathTraceRenderer::renderAdaptive: srt_render_adaptive with the renderer's scene and camera (rows=None: its own band)."""
         rb, re = rows if rows is not None else (0, 0)
         p = AdaptiveParams(int(rb), int(re), int(bounces), int(seed) & 0xFFFFFFFF, int(max_samples),
                            (ADAPTIVE_KEEP_COUNTS if keep_counts else 0) | (ADAPTIVE_COUNT_WORK if count_work else 0), 0)
-        self._ck(self.L.srt_host_renderer_render_adaptive(self._h, C.byref(p)))
+        self._ck((self.L.srt_host_renderer_render_adaptive_tail if tail else self.L.srt_host_renderer_render_adaptive)(self._h, C.byref(p)))
+
+    def render_adaptive_tail(self, bounces=8, seed=0, max_samples=4096, rows=None, keep_counts=False, count_work=False):
+        """PathTraceRenderer::renderAdaptiveTail: srt_render_adaptive_tail with the renderer's scene and camera, under probe_tail()."""
+        self.render_adaptive(bounces, seed, max_samples, rows, keep_counts, count_work, tail=True)
+
+    def render_probe_tail_frame(self, spp, bounces=1, seed=0):
+        """PathTraceRenderer::renderProbeTailFrame: one whole frame of `spp` samples per pixel from n = 0 whose paths end in the
+        probe grid under probe_tail(); the frame is left in the accumulator and the framebuffer."""
+        self._ck(self.L.srt_host_renderer_render_probe_tail_frame(self._h, int(spp), int(bounces), int(seed) & 0xFFFFFFFF))
 
     def set_sample_counts(self, value):
         """PathTraceRenderer::setSampleCounts (srt_set_sample_counts)."""

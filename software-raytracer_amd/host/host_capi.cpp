@@ -329,6 +329,11 @@ int srt_host_renderer_mirror_history(srt_host_renderer* h, int on, float radius_
 // the probe tail of the radiance and light-probe traces (PathTraceRenderer::probeTail) and its work record
 int srt_host_renderer_probe_tail(srt_host_renderer* h, const srt_probe_tail_params* p) { SRT_HOST_TRY(h, h->r->probeTail(*p)) }
 int srt_host_renderer_probe_tail_work(srt_host_renderer* h, srt_probe_tail_work* out) { SRT_HOST_TRY(h, *out = h->r->probeTailWork()) }
+// pictures under the probe tail: srt_render_adaptive_tail (a band of [0, 0) means the renderer's own) and one whole frame of it
+int srt_host_renderer_render_adaptive_tail(srt_host_renderer* h, const srt_adaptive_params* p) { SRT_HOST_TRY(h, h->r->renderAdaptiveTail(*p)) }
+int srt_host_renderer_render_probe_tail_frame(srt_host_renderer* h, uint32_t spp, int bounces, uint32_t seed) {
+    SRT_HOST_TRY(h, h->r->renderProbeTailFrame(spp, bounces, seed))
+}
 int srt_host_renderer_read_ray_output(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->readRayOutput(output, dst)) }
 // denoiser over the whole frame with the guides as they stand (srt_denoise / srt_read_denoised)
 int srt_host_renderer_denoise(srt_host_renderer* h, const srt_denoise_params* p) { SRT_HOST_TRY(h, h->r->Denoise(*p)) }

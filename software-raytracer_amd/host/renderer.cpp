@@ -476,6 +476,37 @@ void PathTraceRenderer::renderAdaptive(const srt_adaptive_params& params) {
     check(srt_render_adaptive(ctx_, &a), "srt_render_adaptive");
 }
 
+void PathTraceRenderer::renderAdaptiveTail(const srt_adaptive_params& params) {
+    srt_adaptive_params a = params;
+    if (a.row_begin == 0 && a.row_end == 0) a.row_begin = row_begin_, a.row_end = row_end_;
+    push_camera();
+    check(srt_render_adaptive_tail(ctx_, &a), "srt_render_adaptive_tail");
+}
+
+void PathTraceRenderer::renderProbeTailFrame(uint32_t spp, int bounces, uint32_t seed) {
+    if (spp < 1) throw RendererError(SRT_ERR_INVALID_ARG, "renderProbeTailFrame: spp must be >= 1");
+    if (row_begin_ != 0 || row_end_ != height_)
+        throw RendererError(SRT_ERR_STATE, "renderProbeTailFrame: the renderer has a row band; the frame covers the whole image");
+    setSampleCounts(0);
+    srt_adaptive_params a{};
+    check(srt_adaptive_params_default(&a), "srt_adaptive_params_default");
+    a.row_begin = 0, a.row_end = height_, a.max_bounces = bounces, a.seed = seed;
+    std::vector<uint32_t> budget((size_t)width_ * height_);
+    for (uint32_t done = 0; done < spp;) {  // (the counts carry the frame from chunk to chunk)
+        const uint32_t chunk = spp - done < a.max_samples ? spp - done : a.max_samples;
+        if (done == 0 || chunk != budget[0]) {
+            std::fill(budget.begin(), budget.end(), chunk);
+            check(srt_write_sample_budget(ctx_, budget.data()), "srt_write_sample_budget");
+        }
+        renderAdaptiveTail(a);
+        done += chunk;
+    }
+    // the accumulator holds a tail frame, which no srt_render can continue
+    doSetFrame_ = true;
+    clean_reset_ = true;
+    first_frame_ = false;
+}
+
 void PathTraceRenderer::setSampleCounts(uint32_t value) { check(srt_set_sample_counts(ctx_, value), "srt_set_sample_counts"); }
 
 void PathTraceRenderer::readSampleCounts(uint32_t* dst) { check(srt_read_sample_counts(ctx_, dst), "srt_read_sample_counts"); }

@@ -313,6 +313,14 @@ class PathTraceRenderer {
     // float4, moments probes x resolution^2 float4, states probes float4); the grid is setProbeGrid's.
     void writeProbeGridInputs(const float* coefficients, const float* moments, const float* states, size_t probes, uint32_t resolution);
     srt_probe_tail_work probeTailWork();
+    // Pictures under the probe tail (srt_render_adaptive_tail).  renderAdaptiveTail is renderAdaptive with every
+    // path ended in the probe grid under the probeTail setting (which must be on); a band of [0, 0) means the renderer's own.
+    // renderProbeTailFrame renders one whole frame that way: the sample counts set to 0, a uniform budget of `spp` (handed over in
+    // chunks of at most 4096, the call's cap), renderAdaptiveTail with `bounces` and `seed` per chunk; the frame is left in the
+    // accumulator and the framebuffer (ReadFramebuffer).  Whole frame only.  Later RenderFrame / RenderSamples calls start a
+    // fresh accumulation.
+    void renderAdaptiveTail(const srt_adaptive_params& params);
+    void renderProbeTailFrame(uint32_t spp, int bounces, uint32_t seed);
     // One variance-guided denoised frame (whole frame only): push the camera, render spp / 2 samples with SRT_RENDER_RESET and
     // the frame's seed into the accumulator, spp / 2 with seed ^ 0x9E3779B9 into the handle's half buffer through
     // srt_bind_output (the binding is restored), the four guides, srt_variance with SRT_VARIANCE_MERGE, then

@@ -325,9 +325,13 @@ struct ProbeUpdateOptions {
 // round 1 has no history and runs with the mode off, every later round runs with the tail reading the history (copied through the
 // host into the grid's coefficient array: the trace writes its own output, never the array it reads), with the flow's depth maps
 // (--probe-depth R) under --probe-tail-depth and its records (--probe-classify) under --probe-tail-states.  The frame is shaded
-// from the history.
+// from the history.  --probe-tail-frame also renders the picture: after the rounds, PathTraceRenderer::renderProbeTailFrame(--spp,
+// --bounces, --seed) with the tail reading the history (and the maps and records the two flags ask for), written to --out.
 struct ProbeTailOptions {
     bool on = false, depth = false, states = false, normal_weight = false;
+    bool frame = false;     // --probe-tail-frame
+    int frame_spp = 0;      // --spp
+    std::string frame_out;  // --out
     int feedback = 0;  // 0: no --probe-feedback
     int bounces = -1;  // < 0: --bounces
     std::string grid, coefficients;
@@ -335,6 +339,21 @@ struct ProbeTailOptions {
         return (depth ? SRT_PROBE_TAIL_DEPTH : 0u) | (states ? SRT_PROBE_TAIL_STATES : 0u) | (normal_weight ? SRT_PROBE_TAIL_NORMAL_WEIGHT : 0u);
     }
 };
+
+static int write_ppm_file(const std::vector<uint32_t>& fb, int W, int H, const std::string& path) {
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) {
+        std::perror(path.c_str());
+        return 1;
+    }
+    std::fprintf(f, "P6\n%d %d\n255\n", W, H);
+    for (uint32_t px : fb) {
+        unsigned char rgb[3] = {(unsigned char)(px >> 16), (unsigned char)(px >> 8), (unsigned char)px};
+        std::fwrite(rgb, 1, 3, f);
+    }
+    std::fclose(f);
+    return 0;
+}
 
 static int shade_probe_grid_file(Scene& scene, int device, int W, int H, int fov, const srt_probe_grid& grid, int directions, int samples, int bounces,
                                  unsigned seed, uint32_t flags, bool hemisphere, const std::string& out, const ProbeDepthOptions& depth,
@@ -450,9 +469,21 @@ static int shade_probe_grid_file(Scene& scene, int device, int W, int H, int fov
                                  (unsigned long long)w.dark, (unsigned long long)w.mirror_ends);
                 }
             }
+            r.readProbeHistory(SRT_PROBE_HISTORY_COEFFICIENTS, coeff.data());
+            if (tail.frame) {  // the picture: every path of the frame ends in the history the rounds have left
+                r.writeProbeGridInputs(coeff.data(), tail.depth ? moments.data() : nullptr, tail.states ? states.data() : nullptr, np, (uint32_t)depth.resolution);
+                tp.enabled = 1;
+                r.probeTail(tp);
+                r.renderProbeTailFrame((uint32_t)tail.frame_spp, bounces, seed);
+                std::vector<uint32_t> fb((size_t)W * H);
+                r.ReadFramebuffer(fb.data(), (size_t)W * 4);
+                const srt_probe_tail_work w = r.probeTailWork();
+                std::fprintf(stderr, "probe tail frame: %d samples per pixel at %d bounces, %llu lookups, %llu dark, %llu mirror ends: %s\n", tail.frame_spp, bounces,
+                             (unsigned long long)w.tails, (unsigned long long)w.dark, (unsigned long long)w.mirror_ends, tail.frame_out.c_str());
+                if (write_ppm_file(fb, W, H, tail.frame_out)) return 1;
+            }
             tp.enabled = 0;
             r.probeTail(tp);
-            r.readProbeHistory(SRT_PROBE_HISTORY_COEFFICIENTS, coeff.data());
         } else {
             r.traceLightProbes(pos.data(), np, dir.data(), (size_t)directions, lp);
             r.readLightProbeOutput(SRT_LIGHT_PROBE_COEFFICIENTS, coeff.data());
@@ -508,6 +539,7 @@ static void usage() {
                  "                  [--probe-depth R [--probe-depth-sharpness S] [--probe-depth-max D] [--probe-depth-bias B] [--probe-depth-out FILE]]\n"
                  "                  [--probe-classify [--probe-relocate] [--probe-clearance C] [--probe-max-offset F] [--probe-steps M] [--states-out FILE]]\n"
                  "                  [--probe-update FRAMES [--probe-hysteresis H] [--probe-samples N]]\n"
+                 "                  [--probe-tail [--probe-feedback F] [--probe-bounces B] [--probe-tail-frame [--spp N] [--out frame.ppm]]]\n"
                  "       srt_render --scene FILE --adaptive ROUNDS [--adaptive-threshold T] [--adaptive-max M] [--counts-out FILE] [--spp N] ...\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
@@ -606,7 +638,11 @@ static void usage() {
                  "             With --probe-grid: --probe-feedback F (1..4096; --probe-tail alone: 2) rounds of (trace the probes at\n"
                  "             --probe-bounces B bounces, default --bounces, with the tail reading the coefficient history, then\n"
                  "             srt_blend_probes); round 1 runs with the mode off; the frame is shaded from the history;\n"
-                 "             --probe-tail-depth needs --probe-depth R, --probe-tail-states needs --probe-classify; not with --probe-update\n");
+                 "             --probe-tail-depth needs --probe-depth R, --probe-tail-states needs --probe-classify; not with --probe-update\n"
+                 "  --probe-tail-frame: with --probe-grid ... --probe-tail: after the feedback rounds also render the picture — --spp samples per\n"
+                 "             pixel from n = 0 at --bounces bounces with --seed, every path ended in the history (srt_render_adaptive_tail), with\n"
+                 "             the maps and records of --probe-tail-depth / --probe-tail-states — and write it to --out as a PPM; not with\n"
+                 "             --devices, --temporal, --adaptive or --steps\n");
 }
 
 int main(int argc, char** argv) {
@@ -710,6 +746,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--probe-update")) probe_update.frames = std::atoi(need("--probe-update")), probe_update_given = true;
         else if (!std::strcmp(argv[i], "--probe-hysteresis")) probe_update.hysteresis = std::strtof(need("--probe-hysteresis"), nullptr), probe_update_option = true;
         else if (!std::strcmp(argv[i], "--probe-tail")) probe_tail.on = true;
+        else if (!std::strcmp(argv[i], "--probe-tail-frame")) probe_tail.frame = true;
         else if (!std::strcmp(argv[i], "--probe-tail-depth")) probe_tail.depth = true;
         else if (!std::strcmp(argv[i], "--probe-tail-states")) probe_tail.states = true;
         else if (!std::strcmp(argv[i], "--probe-tail-normal-weight")) probe_tail.normal_weight = true;
@@ -828,6 +865,17 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--probe-update takes 1..4096 frames, --probe-samples 1..4096, --probe-hysteresis a value in [0, 1)\n");
             return 2;
         }
+    }
+    if (probe_tail.frame) {
+        if (!probe_tail.on || probe_grid_arg.empty() || !devices.empty() || temporal || adaptive_given || steps > 1) {
+            std::fprintf(stderr, "--probe-tail-frame goes with --probe-grid ... --probe-tail; not with --devices, --temporal, --adaptive or --steps\n");
+            return 2;
+        }
+        if (spp < 1) {
+            std::fprintf(stderr, "--probe-tail-frame: --spp must be >= 1\n");
+            return 2;
+        }
+        probe_tail.frame_spp = spp, probe_tail.frame_out = out;
     }
     srt_probe_grid tail_grid{};
     if (probe_tail.on || probe_tail.depth || probe_tail.states || probe_tail.normal_weight || probe_feedback_given || probe_bounces_given ||
@@ -1012,20 +1060,7 @@ int main(int argc, char** argv) {
         }
         return trace_ray_file(scene, device, rays_in, rays_out, rays_normalize, rays_any_hit, radiance_given ? radiance : 0, bounces, seed, ray_tail);
     }
-    auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) {
-        FILE* f = std::fopen(path.c_str(), "wb");
-        if (!f) {
-            std::perror(path.c_str());
-            return 1;
-        }
-        std::fprintf(f, "P6\n%d %d\n255\n", W, H);
-        for (uint32_t px : fb) {
-            unsigned char rgb[3] = {(unsigned char)(px >> 16), (unsigned char)(px >> 8), (unsigned char)px};
-            std::fwrite(rgb, 1, 3, f);
-        }
-        std::fclose(f);
-        return 0;
-    };
+    auto write_ppm = [&](const std::vector<uint32_t>& fb, const std::string& path) { return write_ppm_file(fb, W, H, path); };
     if (!devices.empty()) {
         try {
             MultiGpuRenderer m(devices, W, H);

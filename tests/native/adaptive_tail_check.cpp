@@ -1,0 +1,187 @@
+// adaptive_tail_check.cpp — the host-side rules of srt_render_adaptive_tail (software-raytracer_amd/csrc/srt_adaptive_tail_host.h) as
+// a stand-alone program: rule R1's order (srt_render_adaptive's own errors in their order, then the mode, then the grid's inputs,
+// then the two overlap tests), rule R2 (max_bounces == 0 checks no grid input and launches the plain kernel), the byte ranges of
+// the accumulator and the framebuffer with their edges, and what the call leaves in the adaptive and the probe-tail state (R6).
+// Built with -fsanitize=address,undefined and run on the CPU.
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "srt_adaptive_tail_host.h"
+#include "srt_pathtrace.h"
+
+using namespace srt;
+
+static int failures = 0;
+#define CHECK(cond)                                                     \
+    do {                                                                \
+        if (!(cond)) {                                                  \
+            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+            ++failures;                                                 \
+        }                                                               \
+    } while (0)
+
+int main() {
+    // the call takes srt_render_adaptive's struct and flags
+    CHECK(sizeof(srt_adaptive_params) == 28 && sizeof(AdaptiveCall) == 28);
+    CHECK(SRT_ADAPTIVE_KEEP_COUNTS == ADAPTIVE_FLAG_KEEP_COUNTS && SRT_ADAPTIVE_COUNT_WORK == ADAPTIVE_FLAG_COUNT_WORK && ADAPTIVE_FLAG_ALL == 3u);
+
+    constexpr int W = 6, H = 4;
+    constexpr size_t PROBES = 2 * 3 * 2, COEFF_BYTES = PROBES * 9 * 16;
+    // one block: [accumulator | framebuffer | coefficients | spare], so that adjacency is exact
+    alignas(16) static unsigned char mem[W * H * 16 + W * H * 4 + COEFF_BYTES + 256];
+    unsigned char* const acc = mem;
+    unsigned char* const fb = acc + W * H * 16;
+    unsigned char* const coeff = fb + W * H * 4;
+
+    const AdaptiveTailTargets tg = adaptive_tail_targets(acc, fb, W, H);
+    CHECK(tg.accumulator == acc && tg.accumulator_bytes == (size_t)W * H * 16 && tg.framebuffer == fb && tg.framebuffer_bytes == (size_t)W * H * 4);
+    const AdaptiveTailTargets none = adaptive_tail_targets(nullptr, nullptr, 0, -3);
+    CHECK(none.accumulator_bytes == 0 && none.framebuffer_bytes == 0);
+    const AdaptiveTailTargets big = adaptive_tail_targets(acc, fb, 65536, 65536);  // (no 32-bit product)
+    CHECK(big.accumulator_bytes == ((size_t)1 << 36) && big.framebuffer_bytes == ((size_t)1 << 34));
+
+    AdaptiveCall c;
+    adaptive_call_default(c);
+    c.row_begin = 0, c.row_end = H, c.max_bounces = 1;
+
+    ProbeTailState tail;  // off
+    ProbeGridState g;
+    ProbeGridDepthState d;
+    ProbeStatesState st;
+    const char* why = nullptr;
+    auto check = [&](const AdaptiveCall& call, bool scene, bool camera, bool counts, bool budget, const void* co, const AdaptiveTailTargets& t) {
+        return adaptive_tail_check(call, scene, camera, H, counts, budget, tail, g, d, st, co, t, &why);
+    };
+    auto ok_call = [&](const void* co, const AdaptiveTailTargets& t) { return check(c, true, true, true, true, co, t); };
+
+    // R1 step 1: srt_render_adaptive's own errors come first and in its order, whatever the mode and the grid are
+    {
+        AdaptiveCall v = c;
+        v.row_end = H + 1, v.flags = 4u, v.reserved = 1u, v.max_samples = 0u, v.max_bounces = -1;
+        CHECK(check(v, false, false, false, false, coeff, tg) == RAYS_STATE && std::strstr(why, "srt_set_scene"));
+        CHECK(check(v, true, false, false, false, coeff, tg) == RAYS_STATE && std::strstr(why, "srt_set_camera"));
+        CHECK(check(v, true, true, false, false, coeff, tg) == RAYS_INVALID_ARG && std::strstr(why, "row band"));
+        v.row_end = H;
+        CHECK(check(v, true, true, false, false, coeff, tg) == RAYS_INVALID_ARG && std::strstr(why, "flags"));
+        v.flags = 3u;
+        CHECK(check(v, true, true, false, false, coeff, tg) == RAYS_INVALID_ARG && std::strstr(why, "reserved"));
+        v.reserved = 0u;
+        CHECK(check(v, true, true, false, false, coeff, tg) == RAYS_INVALID_ARG && std::strstr(why, "max_samples"));
+        v.max_samples = 4096u;
+        CHECK(check(v, true, true, false, false, coeff, tg) == RAYS_INVALID_ARG && std::strstr(why, "max_bounces"));
+        v.max_bounces = 1;
+        CHECK(check(v, true, true, false, false, coeff, tg) == RAYS_STATE && std::strstr(why, "sample counts"));
+        CHECK(check(v, true, true, true, false, coeff, tg) == RAYS_STATE && std::strstr(why, "sample budget"));
+        // every one of them gives what adaptive_check gives
+        const char* why2 = nullptr;
+        CHECK(check(v, true, true, true, false, coeff, tg) == adaptive_check(v, true, true, H, true, false, &why2) && !std::strcmp(why, why2));
+        // R1 step 2: then the mode
+        CHECK(check(v, true, true, true, true, coeff, tg) == RAYS_STATE && std::strstr(why, "srt_probe_tail is off"));
+    }
+    // ... also at max_bounces == 0, and with a NULL why
+    {
+        AdaptiveCall v = c;
+        v.max_bounces = 0;
+        CHECK(check(v, true, true, true, true, coeff, tg) == RAYS_STATE && std::strstr(why, "srt_probe_tail is off"));
+        CHECK(adaptive_tail_check(v, true, true, H, true, true, tail, g, d, st, coeff, tg, nullptr) == RAYS_STATE);
+        CHECK(!adaptive_tail_launches_tail(tail, v) && !adaptive_tail_launches_tail(tail, c));
+    }
+    // a setting that was switched on and off again is off
+    ProbeTailCall set = probe_tail_defaults();
+    set.flags = PROBE_TAIL_FLAG_DEPTH | PROBE_TAIL_FLAG_STATES;
+    probe_tail_set(tail, set);
+    set.enabled = 0;
+    probe_tail_set(tail, set);
+    CHECK(ok_call(coeff, tg) == RAYS_STATE && std::strstr(why, "srt_probe_tail is off"));
+    set.enabled = 1;
+    probe_tail_set(tail, set);
+
+    // R2: max_bounces == 0 asks for nothing of the grid — not even coefficients that are the accumulator — and launches the plain kernel
+    {
+        AdaptiveCall v = c;
+        v.max_bounces = 0;
+        CHECK(check(v, true, true, true, true, nullptr, tg) == RAYS_OK && check(v, true, true, true, true, acc, tg) == RAYS_OK);
+        CHECK(!adaptive_tail_launches_tail(tail, v) && adaptive_tail_launches_tail(tail, c));
+        v.max_samples = 4097u;  // (its own errors still come first)
+        CHECK(check(v, true, true, true, true, nullptr, tg) == RAYS_INVALID_ARG);
+    }
+
+    // R1 step 3: the grid's inputs in the probe-tail block's order
+    CHECK(ok_call(coeff, tg) == RAYS_STATE && std::strstr(why, "no grid"));
+    g.grid_set = true, g.grid = ProbeGrid{{0, 0, 0}, {1, 1, 1}, {2, 3, 2}};
+    CHECK(ok_call(coeff, tg) == RAYS_STATE && std::strstr(why, "no coefficients"));
+    g.coefficients.bound = coeff, g.coefficients.bound_count = PROBES - 1;
+    CHECK(ok_call(coeff, tg) == RAYS_STATE && std::strstr(why, "coefficient count"));
+    g.coefficients.bound_count = PROBES;
+    CHECK(ok_call(coeff, tg) == RAYS_STATE && std::strstr(why, "no depth maps"));
+    d.moments.bound = coeff, d.moments.bound_count = PROBES + 1, d.bound_resolution = 4;
+    CHECK(ok_call(coeff, tg) == RAYS_STATE && std::strstr(why, "depth probe count"));
+    d.moments.bound_count = PROBES;
+    CHECK(ok_call(coeff, tg) == RAYS_STATE && std::strstr(why, "no states"));
+    st.states.bound = coeff, st.states.bound_count = 1;
+    CHECK(ok_call(coeff, tg) == RAYS_STATE && std::strstr(why, "state count"));
+    // ... and they hide the overlap: the order is inputs first
+    CHECK(ok_call(acc, tg) == RAYS_STATE && std::strstr(why, "state count"));
+    st.states.bound_count = PROBES;
+    CHECK(ok_call(coeff, tg) == RAYS_OK);  // (coeff starts where the framebuffer ends: adjacent ranges share no byte)
+    CHECK(adaptive_tail_check(c, true, true, H, true, true, tail, g, d, st, coeff, tg, nullptr) == RAYS_OK);
+
+    // the two overlap tests: the accumulator first, then the framebuffer
+    CHECK(ok_call(acc, tg) == RAYS_STATE && std::strstr(why, "this call writes") && !std::strstr(why, "framebuffer"));
+    CHECK(ok_call(fb, tg) == RAYS_STATE && std::strstr(why, "framebuffer"));
+    CHECK(ok_call(coeff - 1, tg) == RAYS_STATE && std::strstr(why, "framebuffer"));            // the framebuffer's last byte
+    CHECK(ok_call(fb - 1, tg) == RAYS_STATE && !std::strstr(why, "framebuffer"));              // the accumulator's last byte (and the framebuffer)
+    CHECK(ok_call(acc + 5, tg) == RAYS_STATE);                                                  // any byte, aligned or not
+    {
+        // the coefficient array in front of the accumulator: its last byte is the accumulator's first, then adjacent
+        const AdaptiveTailTargets after = adaptive_tail_targets(coeff + COEFF_BYTES - 1, coeff + COEFF_BYTES + 128, 2, 2);
+        CHECK(ok_call(coeff, after) == RAYS_STATE && !std::strstr(why, "framebuffer"));
+        const AdaptiveTailTargets adjacent = adaptive_tail_targets(coeff + COEFF_BYTES, coeff + COEFF_BYTES + 128, 2, 2);
+        CHECK(ok_call(coeff, adjacent) == RAYS_OK);
+        // only the framebuffer inside the array
+        const AdaptiveTailTargets inside = adaptive_tail_targets(coeff + COEFF_BYTES, coeff + 16, 2, 2);
+        CHECK(ok_call(coeff, inside) == RAYS_STATE && std::strstr(why, "framebuffer"));
+        // buffers that are not there yet share nothing
+        CHECK(ok_call(coeff, adaptive_tail_targets(nullptr, nullptr, W, H)) == RAYS_OK);
+    }
+    // without the flags the maps and records are not asked for
+    {
+        set.flags = 0;
+        probe_tail_set(tail, set);
+        const ProbeGridDepthState d0 = d;
+        const ProbeStatesState st0 = st;
+        d = ProbeGridDepthState{}, st = ProbeStatesState{};
+        CHECK(ok_call(coeff, tg) == RAYS_OK && ok_call(fb, tg) == RAYS_STATE);
+        d = d0, st = st0;
+    }
+
+    // R6: an adaptive render for srt_get_adaptive_work, the last affected trace for srt_get_probe_tail_work
+    {
+        AdaptiveState a;
+        ProbeTailState t;
+        CHECK(adaptive_check_work(a) == RAYS_STATE && probe_tail_check_work(t) == RAYS_STATE);
+        ProbeTailCall v = probe_tail_defaults();
+        v.flags = PROBE_TAIL_FLAG_COUNT_WORK;
+        probe_tail_set(t, v);
+        CHECK(adaptive_tail_rendered(a, t, ADAPTIVE_FLAG_COUNT_WORK) && a.rendered && a.counted && t.traced && t.counted);
+        CHECK(adaptive_check_work(a) == RAYS_OK && probe_tail_check_work(t) == RAYS_OK);
+        // the two records follow their own flags
+        CHECK(adaptive_tail_rendered(a, t, ADAPTIVE_FLAG_KEEP_COUNTS) && adaptive_check_work(a) == RAYS_STATE && probe_tail_check_work(t) == RAYS_OK);
+        v.flags = 0;
+        probe_tail_set(t, v);
+        CHECK(!adaptive_tail_rendered(a, t, ADAPTIVE_FLAG_COUNT_WORK) && adaptive_check_work(a) == RAYS_OK && probe_tail_check_work(t) == RAYS_STATE);
+        CHECK(!a.budgeted);  // (the budget pass's flag is not this call's)
+        // srt_render_adaptive after it leaves the tail's record alone
+        v.flags = PROBE_TAIL_FLAG_COUNT_WORK;
+        probe_tail_set(t, v);
+        CHECK(adaptive_tail_rendered(a, t, 0u));
+        adaptive_rendered(a, ADAPTIVE_FLAG_COUNT_WORK);
+        CHECK(probe_tail_check_work(t) == RAYS_OK && adaptive_check_work(a) == RAYS_OK);
+    }
+
+    if (failures) return 1;
+    std::printf("ok adaptive tail host rules\n");
+    return 0;
+}
