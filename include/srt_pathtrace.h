@@ -1637,6 +1637,89 @@ int srt_get_probe_grid_work(srt_context* ctx, srt_probe_grid_work* out);
  * reference's interface. */
 int srt_selftest_arith(int device, uint32_t seed, uint64_t vectors, uint64_t* mismatches);
 
+/* ---- scrolling probe grids: move a grid and keep its histories (ABI 7, backward compatible) --------------------------------------
+ * These calls were added without changing anything else, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of them
+ * runs what it ran before, bit for bit.  A grid that covers only the surroundings of the viewer has to move with the viewer;
+ * srt_set_probe_grid followed by srt_reset_probe_history throws every blended sample away.  srt_scroll_probes moves the grid's
+ * per-probe arrays by a whole number of cells instead: a probe that stands where the old grid had one keeps that probe's history,
+ * the others start over.  Every buffer stays on the device and no call waits.
+ * SC1. Mapping.  The current grid (srt_set_probe_grid) has nx, ny, nz probes, P = nx*ny*nz, probe (ix, iy, iz) at index
+ *    ix + nx*(iy + ny*iz).  For a destination probe i = (ix, iy, iz) the source is j = i + shift per axis, in 64-bit integer
+ *    arithmetic; shift may be any int32.  Probe i is RETAINED when 0 <= j_a < n_a on all three axes, otherwise EXPOSED.  An axis
+ *    with |shift_a| >= n_a exposes every probe.  (The grid moves by +shift cells: new probe i stands where old probe i + shift
+ *    stood.)
+ * SC2. Histories.  `which` selects the histories of the blend: the [P][9] float4 coefficients (SRT_PROBE_SCROLL_COEFFICIENTS) and
+ *    the [P][R*R] float4 moments (SRT_PROBE_SCROLL_MOMENTS), each in its current buffer: the handle's own unless
+ *    srt_bind_probe_history bound the caller's.  After the call that buffer holds, at a retained i, the bits that were at j before
+ *    the call (a NaN stays that NaN, all four lanes) and at an exposed i all-zero bits; srt_blend_probes' rule U2 then restarts
+ *    exactly the exposed probes and goes on blending the retained ones.  The move is never done in place: the kernel reads the
+ *    current buffer and writes a distinct one, a handle-owned spare of the same size, allocated on first use (SRT_ERR_OOM if it
+ *    cannot be had).  An own history then swaps with the spare; a bound history is copied back from it on the launch stream.  A
+ *    zero shift leaves every history bit alone and launches nothing for the histories.
+ * SC3. States.  With SRT_PROBE_SCROLL_STATES the P records current for srt_shade_probe_grid_states (srt_write_probe_grid_states,
+ *    srt_bind_probe_grid_states) are read; that slot is a const pointer and is never written.  The handle's own previous-records
+ *    array, the one srt_write_probe_previous_states fills, then holds record j at a retained i and zero bits at an exposed i, and
+ *    becomes the current previous-records source with count P, as after that call (a binding of srt_bind_probe_previous_states
+ *    ends).  With shift 0 this is a plain device copy "current -> previous", which a per-frame loop wants anyway.
+ *    srt_read_probe_previous_states waits and copies the records that are the current previous-records source (this array, the
+ *    one srt_write_probe_previous_states filled, or the bound one), 4 floats per probe; SRT_ERR_STATE when there is none.
+ * SC4. Grid.  With SRT_PROBE_SCROLL_SET_GRID the handle's grid keeps spacing and counts and origin_a becomes
+ *    origin_a + ((float)shift_a * spacing_a): binary32, no contraction, the product first.  Without the flag the grid is untouched
+ *    and the caller calls srt_set_probe_grid.  New probe i and old probe j are at BIT-EQUAL positions only when these products and
+ *    sums are exact, for instance with a dyadic origin and spacing; otherwise the two positions differ by rounding, and the history
+ *    is kept all the same.  A caller who scrolls often should compute origins from a fixed base and a cumulative integer shift and
+ *    set them with srt_set_probe_grid, not by repeated _SET_GRID: the roundings of repeated steps add up.  A moved origin that is
+ *    not finite is SRT_ERR_INVALID_ARG (after the check for a grid).
+ * SC5. Stale inputs.  After a call with a non-zero shift, the records that say which buffers the last
+ *    srt_trace_light_probes[_listed] wrote COEFFICIENTS to and the last srt_trace_probe_depth[_listed] wrote MOMENTS to count as
+ *    "did not write" (for srt_blend_probes and for the two srt_read_*_output calls alike): srt_blend_probes answers SRT_ERR_STATE
+ *    until a new trace.  A trace indexed by the old grid must not be blended into the new one.  The list bound for tracing, the
+ *    light-probe positions, the current records and a continuing RADIANCE buffer are the caller's to refresh.  A frame:
+ *    srt_scroll_probes (with _STATES and _SET_GRID) -> srt_classify_probes -> bind its positions and records -> srt_list_probes ->
+ *    the listed traces -> srt_blend_probes with _LISTED | _PREVIOUS_STATES.
+ * SC6. Determinism and work.  One wave per destination probe, the decision is wave-uniform; no atomic reaches an output, and
+ *    repeated calls on the same input give the same bits.  With SRT_PROBE_SCROLL_COUNT_WORK the call records the probes (P), the
+ *    retained, the exposed and the waves of the launch, counted once per call, not once per selected array (a call with the flag
+ *    always launches, with a zero shift too); one vector atomic per wave at the end, without the flag no atomics at all.
+ *    srt_get_probe_scroll_work waits and copies the record; SRT_ERR_STATE unless the last srt_scroll_probes had the flag.
+ * SC7. srt_probe_grid_follow (pure host).  Per axis, in binary32 without contraction: c = origin_a + (((float)(n_a - 1)) * 0.5f)
+ *    * spacing_a, u = (point_a - c) / spacing_a, shift_a = (int32)u truncated towards zero after clamping u to +-1048576; a NaN
+ *    gives 0.  Truncation means the grid moves only once the point is a whole cell off centre.  SRT_ERR_INVALID_ARG for a grid
+ *    srt_set_probe_grid would refuse.
+ * SC8. Errors, all found before anything is touched, in this order: SRT_ERR_STATE before srt_set_scene; SRT_ERR_INVALID_ARG for
+ *    which == 0, unknown bits in which or flags, or a non-zero reserved word; SRT_ERR_STATE for no grid, or for a selected history
+ *    that was never reset or whose size is not the grid's P; with _STATES, SRT_ERR_STATE for no current records or a count other
+ *    than P; SRT_ERR_OOM.  Asynchrony: as for the blend; the call is enqueued on the launch stream and covered by srt_wait /
+ *    srt_poll. */
+#define SRT_PROBE_SCROLL_COEFFICIENTS 1u /* srt_probe_scroll_params.which: = SRT_PROBE_HISTORY_COEFFICIENTS */
+#define SRT_PROBE_SCROLL_MOMENTS 2u      /* = SRT_PROBE_HISTORY_MOMENTS */
+#define SRT_PROBE_SCROLL_STATES 4u       /* current records -> previous records, scrolled (rule SC3) */
+#define SRT_PROBE_SCROLL_COUNT_WORK 1u   /* srt_probe_scroll_params.flags: fill srt_probe_scroll_work for this call */
+#define SRT_PROBE_SCROLL_SET_GRID 2u     /* also move the handle's grid origin (rule SC4) */
+
+typedef struct srt_probe_scroll_params { /* 32 bytes */
+    int32_t shift[3];                    /* cells the grid moves along +x, +y, +z */
+    uint32_t which;                      /* SRT_PROBE_SCROLL_COEFFICIENTS | _MOMENTS | _STATES, not 0 */
+    uint32_t flags;                      /* SRT_PROBE_SCROLL_COUNT_WORK | _SET_GRID */
+    uint32_t reserved[3];                /* 0 */
+} srt_probe_scroll_params;
+
+typedef struct srt_probe_scroll_work { /* 40 bytes */
+    uint32_t valid, reserved;          /* 1, 0 */
+    uint64_t probes;                   /* P */
+    uint64_t retained;                 /* ... of which keep a history (rule SC1) */
+    uint64_t exposed;                  /* ... of which start over */
+    uint64_t waves;                    /* waves of the launch */
+} srt_probe_scroll_work;
+
+/* shift 0, which SRT_PROBE_SCROLL_COEFFICIENTS, flags 0, reserved 0 (pure host). */
+int srt_probe_scroll_params_default(srt_probe_scroll_params* out);
+int srt_scroll_probes(srt_context* ctx, const srt_probe_scroll_params* params);
+int srt_get_probe_scroll_work(srt_context* ctx, srt_probe_scroll_work* out);
+int srt_read_probe_previous_states(srt_context* ctx, float* dst);
+/* pure host: the shift that re-centres `grid` on `point` (rule SC7) */
+int srt_probe_grid_follow(const srt_probe_grid* grid, const float point[3], int32_t shift[3]);
+
 /* ---- probe tail: radiance paths that end in the probe grid (ABI 7, backward compatible) -----------------------------------------
  * These calls were added without changing anything else, so SRT_ABI_VERSION stays 7.  srt_probe_tail sets a per-context mode, off
  * by default.  With it on, a path of srt_trace_radiance, srt_trace_light_probes or srt_trace_light_probes_listed that ends BECAUSE

@@ -63,6 +63,9 @@ PROBE_CLEAR, PROBE_MOVED, PROBE_BURIED, PROBE_INSIDE, PROBE_IDLE = 0, 1, 2, 4, 8
 PROBE_LIST_COUNT_WORK, PROBE_LIST_HEADER, PROBE_LIST_NONE = 1, 4, 0xFFFFFFFF
 PROBE_HISTORY_COEFFICIENTS, PROBE_HISTORY_MOMENTS = 1, 2
 PROBE_BLEND_MOMENTS, PROBE_BLEND_LISTED, PROBE_BLEND_PREVIOUS_STATES, PROBE_BLEND_COUNT_WORK = 1, 2, 4, 8
+# scrolling probe grids (srt_scroll_probes): the arrays of srt_probe_scroll_params.which, its flags
+PROBE_SCROLL_COEFFICIENTS, PROBE_SCROLL_MOMENTS, PROBE_SCROLL_STATES = 1, 2, 4
+PROBE_SCROLL_COUNT_WORK, PROBE_SCROLL_SET_GRID = 1, 2
 # adaptive sampling (srt_render_adaptive, srt_sample_budget): the flags, the limits of max_samples / max_budget, the last frame
 ADAPTIVE_KEEP_COUNTS, ADAPTIVE_COUNT_WORK = 1, 2
 ADAPTIVE_MAX_SAMPLES = 4096
@@ -132,6 +135,8 @@ EXPORTS = [
     "srt_bind_probe_list", "srt_write_probe_list", "srt_trace_light_probes_listed", "srt_trace_probe_depth_listed",
     "srt_probe_blend_params_default", "srt_reset_probe_history", "srt_bind_probe_history", "srt_read_probe_history",
     "srt_write_probe_previous_states", "srt_bind_probe_previous_states", "srt_blend_probes", "srt_get_probe_blend_work",
+    "srt_probe_scroll_params_default", "srt_scroll_probes", "srt_get_probe_scroll_work", "srt_probe_grid_follow",
+    "srt_read_probe_previous_states",
     "srt_probe_tail_params_default", "srt_probe_tail", "srt_get_probe_tail_work",
     "srt_render_adaptive_tail",
 ]
@@ -455,6 +460,20 @@ class ProbeBlendWork(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+class ProbeScrollParams(C.Structure):
+    """srt_probe_scroll_params: the shift in cells, the arrays to move (PROBE_SCROLL_COEFFICIENTS | _MOMENTS | _STATES), the flags."""
+    _fields_ = [("shift", C.c_int32 * 3), ("which", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class ProbeScrollWork(C.Structure):
+    """srt_probe_scroll_work: what the last counting srt_scroll_probes did."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("retained", C.c_uint64), ("exposed", C.c_uint64),
+                ("waves", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class UpdateInfo(C.Structure):
     """srt_update_info: what the last successful srt_update_scene did to the mesh image."""
     _fields_ = [("path", C.c_int32), ("reason", C.c_int32), ("levels", C.c_int32), ("triangles", C.c_uint32), ("nodes", C.c_uint32),
@@ -686,6 +705,11 @@ def open_library(path):
     L.srt_bind_probe_previous_states.argtypes = [ctx, C.c_void_p, C.c_size_t]
     L.srt_blend_probes.argtypes = [ctx, C.POINTER(ProbeBlendParams)]
     L.srt_get_probe_blend_work.argtypes = [ctx, C.POINTER(ProbeBlendWork)]
+    L.srt_probe_scroll_params_default.argtypes = [C.POINTER(ProbeScrollParams)]
+    L.srt_scroll_probes.argtypes = [ctx, C.POINTER(ProbeScrollParams)]
+    L.srt_get_probe_scroll_work.argtypes = [ctx, C.POINTER(ProbeScrollWork)]
+    L.srt_read_probe_previous_states.argtypes = [ctx, C.POINTER(C.c_float)]
+    L.srt_probe_grid_follow.argtypes = [C.POINTER(ProbeGrid), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     L.srt_set_sample_counts.argtypes = [ctx, C.c_uint32]
     L.srt_write_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
     L.srt_read_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
@@ -941,6 +965,19 @@ def probe_grid(origin, spacing, counts):
     for a in range(3):
         g.origin[a], g.spacing[a], g.counts[a] = float(origin[a]), float(spacing[a]), int(counts[a])
     return g
+
+
+def probe_grid_follow(grid, point, lib=None):
+    """srt_probe_grid_follow: the shift (sx, sy, sz), in cells, that re-centres `grid` (a ProbeGrid, or a triple of triples) on
+    `point`: per axis (point - centre) / spacing truncated towards zero.  Pure host."""
+    L = lib or load_library()
+    g = grid if isinstance(grid, ProbeGrid) else probe_grid(*grid)
+    pt = (C.c_float * 3)(*[float(v) for v in point])
+    shift = (C.c_int32 * 3)()
+    rc = L.srt_probe_grid_follow(C.byref(g), pt, shift)
+    if rc != OK:
+        raise SrtError(rc, "srt_probe_grid_follow: not a grid srt_set_probe_grid accepts")
+    return tuple(int(v) for v in shift)
 
 
 def probe_grid_positions(origin, spacing=None, counts=None, lib=None):
@@ -2136,6 +2173,55 @@ class PathTracer:
         w = ProbeBlendWork()
         self._ck(self.L.srt_get_probe_blend_work(self._h, C.byref(w)))
         return w.as_dict()
+
+    @staticmethod
+    def _scroll_bits(which):
+        if isinstance(which, (int, np.integer)):
+            return int(which)
+        names = {"coefficients": PROBE_SCROLL_COEFFICIENTS, "moments": PROBE_SCROLL_MOMENTS, "states": PROBE_SCROLL_STATES,
+                 "both": PROBE_SCROLL_COEFFICIENTS | PROBE_SCROLL_MOMENTS, "all": PROBE_SCROLL_COEFFICIENTS | PROBE_SCROLL_MOMENTS | PROBE_SCROLL_STATES}
+        bits = 0
+        for name in ([which] if isinstance(which, str) else which):
+            bits |= names[name]
+        return bits
+
+    def scroll_probes(self, shift, which="coefficients", set_grid=False, count_work=False, flags=0, reserved=(0, 0, 0)):
+        """srt_scroll_probes: move the grid of set_probe_grid() by `shift` = (sx, sy, sz) cells and keep what stays inside: new probe
+        i takes the history of old probe i + shift, a probe without such a source gets zero bits and restarts at the next
+        blend_probes().  `which`: "coefficients", "moments", "states" (the current records, scrolled, become the previous records
+        of blend_probes(previous_states=True)), "both", "all", a sequence of these, or PROBE_SCROLL_* bits.  set_grid: also move the
+        handle's grid origin by shift * spacing; otherwise call set_probe_grid().  A non-zero shift makes the last traces stale:
+        blend_probes() refuses until trace_light_probes() (and trace_probe_depth()) ran again.  count_work: probe_scroll_work()
+        then reads the record.  Asynchronous."""
+        p = ProbeScrollParams()
+        self._ck(self.L.srt_probe_scroll_params_default(C.byref(p)))
+        for a in range(3):
+            p.shift[a], p.reserved[a] = int(shift[a]), int(reserved[a])
+        p.which = self._scroll_bits(which)
+        p.flags = int(flags) | (PROBE_SCROLL_SET_GRID if set_grid else 0) | (PROBE_SCROLL_COUNT_WORK if count_work else 0)
+        self._ck(self.L.srt_scroll_probes(self._h, C.byref(p)))
+        if p.which & PROBE_SCROLL_STATES:
+            self._probe_previous_bound = None  # (the handle's own previous records are current again)
+
+    def probe_grid_follow(self, grid, point, which="all", count_work=False):
+        """srt_probe_grid_follow, then scroll_probes(shift, which, set_grid=True): re-centre the grid on `point`.  `grid`: the
+        ProbeGrid (or triple of triples) last given to set_probe_grid(), or as moved by earlier calls.  Returns the shift."""
+        shift = probe_grid_follow(grid, point, lib=self.L)
+        self.scroll_probes(shift, which=which, set_grid=True, count_work=count_work)
+        return shift
+
+    def probe_scroll_work(self):
+        """srt_get_probe_scroll_work: the work counts of the last scroll_probes(count_work=True) as a dict.  Waits."""
+        w = ProbeScrollWork()
+        self._ck(self.L.srt_get_probe_scroll_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    get_probe_scroll_work = probe_scroll_work
+
+    def probe_previous_states(self, probes):
+        """srt_read_probe_previous_states: the (probes, 4) float32 records blend_probes(previous_states=True) compares with — what
+        bind_probe_previous_states() or scroll_probes(which="states") left.  Waits."""
+        return self._read_image(self.L.srt_read_probe_previous_states, (int(probes), 4), np.float32)
 
     def ray_output(self, name, count=None):
         """srt_read_ray_output: one output of the last trace_rays() as a numpy array: "object" and "occluded" (N,) int32, the

@@ -49,6 +49,8 @@
 #include "srt_probe_states_host.h"
 #include "srt_probe_update.hip.h"
 #include "srt_probe_update_host.h"
+#include "srt_probe_scroll.hip.h"
+#include "srt_probe_scroll_host.h"
 #include "srt_probe_tail.hip.h"
 #include "srt_probe_tail_host.h"
 #include "srt_adaptive.hip.h"
@@ -151,6 +153,11 @@ class Buffer : NoCopy {
         if (e == hipSuccess) bytes_ = bytes;
         else p_ = nullptr;
         return e;
+    }
+    void swap(Buffer& o) {
+        T* const p = p_;
+        const size_t b = bytes_;
+        p_ = o.p_, bytes_ = o.bytes_, o.p_ = p, o.bytes_ = b;
     }
 
   private:
@@ -462,6 +469,12 @@ struct srt_context {
     DeviceBuffer<float4> d_probe_history[srt::PROBE_HISTORY_SLOTS];
     DeviceBuffer<unsigned long long> d_probe_list_work;
     DeviceBuffer<unsigned long long> d_probe_blend_work;
+    // scrolling (srt_scroll_probes): whether the last call counted (srt_probe_scroll_host.h); one spare per history, the buffer a
+    // scroll writes (an own history swaps with it, a bound one is copied back from it); the record a counting launch adds to
+    // (srt::PSC_WORK_N words).  The scrolled records go to d_probe_previous_states.
+    srt::ProbeScrollState probe_scroll;
+    DeviceBuffer<float4> d_probe_history_spare[srt::PROBE_HISTORY_SLOTS];
+    DeviceBuffer<unsigned long long> d_probe_scroll_work;
     // the probe tail (srt_probe_tail): the mode's setting and whether the last affected trace ran under it and counted
     // (srt_probe_tail_host.h); the record a counting launch adds to (srt::PT_WORK_N words)
     srt::ProbeTailState probe_tail;
@@ -3030,6 +3043,117 @@ int srt_get_probe_blend_work(srt_context* ctx, srt_probe_blend_work* out) {
     if (const int rc = read_work(ctx, ctx->d_probe_blend_work, w, srt::PB_WORK_N)) return rc;
     out->valid = 1, out->reserved = 0;
     out->probes = w[srt::PB_WORK_PROBES], out->restarted = w[srt::PB_WORK_RESTARTED], out->changed = w[srt::PB_WORK_CHANGED], out->waves = w[srt::PB_WORK_WAVES];
+    return SRT_OK;
+}
+
+// ---- scrolling probe grids -------------------------------------------------------------------------------------------
+static_assert(SRT_PROBE_SCROLL_COEFFICIENTS == srt::PROBE_SCROLL_COEFFICIENTS && SRT_PROBE_SCROLL_MOMENTS == srt::PROBE_SCROLL_MOMENTS &&
+              SRT_PROBE_SCROLL_STATES == srt::PROBE_SCROLL_STATES && SRT_PROBE_SCROLL_COEFFICIENTS == SRT_PROBE_HISTORY_COEFFICIENTS &&
+              SRT_PROBE_SCROLL_MOMENTS == SRT_PROBE_HISTORY_MOMENTS && SRT_PROBE_SCROLL_COUNT_WORK == srt::PROBE_SCROLL_FLAG_COUNT_WORK &&
+              SRT_PROBE_SCROLL_SET_GRID == srt::PROBE_SCROLL_FLAG_SET_GRID && sizeof(srt_probe_scroll_params) == 32 && sizeof(srt::ProbeScrollCall) == 32 &&
+              sizeof(srt_probe_scroll_work) == 40 && srt::PSC_WORK_N == 4 && (int)srt::PSC_ARRAYS == (int)srt::PROBE_SCROLL_ARRAYS &&
+              srt::PROBE_SCROLL_ARRAYS == srt::PROBE_HISTORY_SLOTS + 1,
+              "srt_probe_scroll_host.h, srt_probe_scroll.hip.h and srt_pathtrace.h disagree");
+
+int srt_probe_scroll_params_default(srt_probe_scroll_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::ProbeScrollCall c;
+    srt::probe_scroll_call_default(c);
+    memcpy(out, &c, sizeof c);
+    return SRT_OK;
+}
+
+int srt_probe_grid_follow(const srt_probe_grid* grid, const float point[3], int32_t shift[3]) {
+    if (!grid || !point || !shift) return SRT_ERR_INVALID_ARG;
+    const srt::ProbeGrid g = probe_grid_of(grid);
+    if (srt::probe_grid_check(g, nullptr) != srt::RAYS_OK) return SRT_ERR_INVALID_ARG;
+    srt::probe_grid_follow(g, point, shift);
+    return SRT_OK;
+}
+
+int srt_scroll_probes(srt_context* ctx, const srt_probe_scroll_params* t) {
+    if (!ctx || !t) return SRT_ERR_INVALID_ARG;
+    srt::ProbeScrollCall call;
+    memcpy(&call, t, sizeof call);
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_scroll_check(ctx->probe_grid, ctx->probe_update, ctx->probe_states, ctx->scene_set, call, &why))
+        return fail(ctx, (int)rs, "srt_scroll_probes: %s (shift %d %d %d, which 0x%x, flags 0x%x, reserved %u %u %u)", why, t->shift[0], t->shift[1], t->shift[2],
+                    t->which, t->flags, t->reserved[0], t->reserved[1], t->reserved[2]);
+    const srt::ProbeGrid& g = ctx->probe_grid.grid;
+    const size_t np = srt::probe_grid_probes(g);
+    const bool moving = !srt::probe_scroll_shift_is_zero(call.shift);
+    const bool states = (t->which & SRT_PROBE_SCROLL_STATES) != 0, count = (t->flags & SRT_PROBE_SCROLL_COUNT_WORK) != 0;
+    size_t bytes[srt::PROBE_HISTORY_SLOTS] = {0, 0};  // of the histories this call moves (a zero shift moves none)
+    for (int i = 0; i < srt::PROBE_HISTORY_SLOTS; ++i) {
+        if (!moving || !(t->which & (1u << i))) continue;
+        bytes[i] = srt::probe_history_bytes(i, np, ctx->probe_update.history[i].resolution);
+        // (a history unbound after its reset may have no own buffer of that size: the one case the rules cannot see)
+        if (!ctx->probe_update.history[i].bound && ctx->d_probe_history[i].bytes() < bytes[i])
+            return fail(ctx, SRT_ERR_STATE, "srt_scroll_probes: history 0x%x was unbound after its reset (srt_reset_probe_history)", 1u << i);
+    }
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    // every buffer first: a failed allocation leaves the histories, the previous records and the grid as they were
+    for (int i = 0; i < srt::PROBE_HISTORY_SLOTS; ++i)
+        if (ctx->d_probe_history_spare[i].bytes() < bytes[i]) {  // an earlier scroll's copy back may still read it
+            if (const int rc = finish_stream(ctx)) return rc;
+            SRT_HIP(ctx, ctx->d_probe_history_spare[i].ensure(bytes[i]));
+        }
+    if (states && ctx->d_probe_previous_states.bytes() < np * sizeof(float4)) {  // earlier blends may still read it
+        if (const int rc = finish_stream(ctx)) return rc;
+        ctx->probe_update.previous.own_count = 0;  // (a failed allocation leaves no own array)
+        SRT_HIP(ctx, ctx->d_probe_previous_states.ensure(np * sizeof(float4)));
+    }
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_probe_scroll_work, srt::PSC_WORK_N)) return rc;
+    }
+    srt::ProbeScrollIO io{};
+    for (int i = 0; i < srt::PROBE_HISTORY_SLOTS; ++i) {
+        if (bytes[i] == 0) continue;
+        io.src[i] = (const uint4*)current_probe_history(ctx, i), io.dst[i] = (uint4*)(float4*)ctx->d_probe_history_spare[i];
+        io.elems[i] = (uint32_t)(bytes[i] / np / sizeof(float4));
+    }
+    if (states) {
+        io.src[2] = (const uint4*)current(ctx->probe_states.states, ctx->d_probe_grid_states), io.dst[2] = (uint4*)(float4*)ctx->d_probe_previous_states;
+        io.elems[2] = 1u;
+    }
+    io.probes = (uint32_t)np;
+    for (int a = 0; a < 3; ++a) io.counts[a] = g.counts[a], io.shift[a] = t->shift[a];
+    io.work = count ? (unsigned long long*)ctx->d_probe_scroll_work : nullptr;
+    if (io.dst[0] || io.dst[1] || io.dst[2] || count) {
+        void (*const kernel)(srt::ProbeScrollIO) = count ? srt::probe_scroll_kernel<true> : srt::probe_scroll_kernel<false>;
+        const unsigned wgs = srt::probe_scroll_grid(np, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, 0));
+        hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), 0, ctx->stream, io);
+        SRT_HIP(ctx, hipGetLastError());
+    }
+    for (int i = 0; i < srt::PROBE_HISTORY_SLOTS; ++i) {
+        if (bytes[i] == 0) continue;
+        if (ctx->probe_update.history[i].bound)
+            SRT_HIP(ctx, hipMemcpyAsync(current_probe_history(ctx, i), ctx->d_probe_history_spare[i], bytes[i], hipMemcpyDeviceToDevice, ctx->stream));
+        else
+            ctx->d_probe_history[i].swap(ctx->d_probe_history_spare[i]);  // (enqueued launches keep the pointers they were given)
+    }
+    if (states) srt::light_probe_written(ctx->probe_update.previous, np);
+    if (t->flags & SRT_PROBE_SCROLL_SET_GRID) srt::probe_scroll_origin(g, call.shift, ctx->probe_grid.grid.origin);
+    if (moving) srt::probe_scroll_stale(ctx->probes, ctx->probe_depth);
+    srt::probe_scroll_scrolled(ctx->probe_scroll, t->flags);
+    return SRT_OK;
+}
+
+int srt_read_probe_previous_states(srt_context* ctx, float* dst) {
+    if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
+    const size_t np = ctx->probe_update.previous.count();
+    return read_slot(ctx, np ? current(ctx->probe_update.previous, ctx->d_probe_previous_states) : nullptr, dst, np * sizeof(float4),
+                     "srt_read_probe_previous_states: no previous states have been written, bound or scrolled");
+}
+
+int srt_get_probe_scroll_work(srt_context* ctx, srt_probe_scroll_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::probe_scroll_check_work(ctx->probe_scroll) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_scroll_work: the last srt_scroll_probes did not ask for SRT_PROBE_SCROLL_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::PSC_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_probe_scroll_work, w, srt::PSC_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0;
+    out->probes = w[srt::PSC_WORK_PROBES], out->retained = w[srt::PSC_WORK_RETAINED], out->exposed = w[srt::PSC_WORK_EXPOSED], out->waves = w[srt::PSC_WORK_WAVES];
     return SRT_OK;
 }
 

@@ -20,6 +20,7 @@ from .capi import (PROBE_CLASSIFY_COUNT_WORK, PROBE_CLASSIFY_NORMALIZE, PROBE_CL
 from .capi import (PROBE_BLEND_COUNT_WORK, PROBE_BLEND_LISTED, PROBE_BLEND_MOMENTS, PROBE_BLEND_PREVIOUS_STATES, PROBE_BURIED, PROBE_HISTORY_COEFFICIENTS,
                    PROBE_HISTORY_MOMENTS, PROBE_IDLE, PROBE_LIST_COUNT_WORK, PROBE_LIST_HEADER, ProbeBlendParams, ProbeBlendWork, ProbeListParams,
                    ProbeListWork)  # noqa: F401
+from .capi import PROBE_SCROLL_COUNT_WORK, PROBE_SCROLL_SET_GRID, PathTracer as _PathTracer, ProbeScrollWork  # noqa: F401
 from .capi import PROBE_TAIL_COUNT_WORK, PROBE_TAIL_DEPTH, PROBE_TAIL_NORMAL_WEIGHT, PROBE_TAIL_STATES, ProbeTailParams, ProbeTailWork  # noqa: F401
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -62,6 +63,7 @@ EXPORTS = [
     "srt_host_renderer_list_probes", "srt_host_renderer_read_probe_list_output", "srt_host_renderer_probe_list_work",
     "srt_host_renderer_trace_light_probes_listed", "srt_host_renderer_trace_probe_depth_listed", "srt_host_renderer_reset_probe_history",
     "srt_host_renderer_blend_probes", "srt_host_renderer_read_probe_history", "srt_host_renderer_probe_blend_work",
+    "srt_host_renderer_scroll_probes", "srt_host_renderer_follow_probe_grid", "srt_host_renderer_probe_scroll_work",
     "srt_host_renderer_sample_budget", "srt_host_renderer_render_adaptive", "srt_host_renderer_set_sample_counts",
     "srt_host_renderer_read_sample_counts", "srt_host_renderer_adaptive_frame",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
@@ -181,6 +183,9 @@ def load_library():
     L.srt_host_renderer_trace_light_probes_listed.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(LightProbeParams)]
     L.srt_host_renderer_trace_probe_depth_listed.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(ProbeDepthParams)]
     L.srt_host_renderer_reset_probe_history.argtypes = [vp, C.c_uint32, C.c_size_t, C.c_uint32]
+    L.srt_host_renderer_scroll_probes.argtypes = [vp, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32]
+    L.srt_host_renderer_follow_probe_grid.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+    L.srt_host_renderer_probe_scroll_work.argtypes = [vp, C.POINTER(ProbeScrollWork)]
     L.srt_host_renderer_blend_probes.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(ProbeBlendParams)]
     L.srt_host_renderer_read_probe_history.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float)]
     L.srt_host_renderer_probe_blend_work.argtypes = [vp, C.POINTER(ProbeBlendWork)]
@@ -749,10 +754,11 @@ class Renderer:
     def blend_probes(self, hysteresis=0.9, fast_hysteresis=0.5, depth_hysteresis=0.9, change_threshold=0.25, moments=False, listed=False,
                      previous_states=None, count_work=False):
         """PathTraceRenderer::blendProbes: srt_blend_probes on the histories of reset_probe_history() with what the last traces wrote.
-        previous_states: (P, 4) float32 records to compare the current ones with (SRT_PROBE_BLEND_PREVIOUS_STATES); listed: only the
+        previous_states: (P, 4) float32 records to compare the current ones with (SRT_PROBE_BLEND_PREVIOUS_STATES), or True for the
+        previous records the handle already has (what scroll_probes(which="states") or follow_probe_grid() left); listed: only the
         probes of the last list_probes().  probe_history() reads the result."""
         sptr, n = None, 0
-        if previous_states is not None:
+        if previous_states is not None and previous_states is not True:  # (True: the handle's current ones, as scroll_probes("states") left them)
             st = np.ascontiguousarray(previous_states, dtype=np.float32)
             if st.ndim != 2 or st.shape[1] != 4 or st.shape[0] < 1:
                 raise ValueError("blend_probes: previous_states %s, want (P, 4)" % (st.shape,))
@@ -774,6 +780,27 @@ class Renderer:
         """PathTraceRenderer::probeBlendWork: the work counts of the last blend_probes(count_work=True) as a dict."""
         w = ProbeBlendWork()
         self._ck(self.L.srt_host_renderer_probe_blend_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def scroll_probes(self, shift, which="coefficients", set_grid=False, count_work=False):
+        """PathTraceRenderer::scrollProbes: srt_scroll_probes on the renderer's grid — move the arrays of `which` (as
+        PathTracer.scroll_probes takes it) by `shift` = (sx, sy, sz) cells; set_grid: the grid's origin follows."""
+        s3 = (C.c_int32 * 3)(*[int(v) for v in shift])
+        flags = (PROBE_SCROLL_SET_GRID if set_grid else 0) | (PROBE_SCROLL_COUNT_WORK if count_work else 0)
+        self._ck(self.L.srt_host_renderer_scroll_probes(self._h, s3, _PathTracer._scroll_bits(which), flags))
+
+    def follow_probe_grid(self, point):
+        """PathTraceRenderer::followProbeGrid: srt_probe_grid_follow on the renderer's grid, then a scroll of the histories that have
+        been reset and of the records, with the grid's origin following.  Returns the shift (sx, sy, sz)."""
+        pt = (C.c_float * 3)(*[float(v) for v in point])
+        s3 = (C.c_int32 * 3)()
+        self._ck(self.L.srt_host_renderer_follow_probe_grid(self._h, pt, s3))
+        return tuple(int(v) for v in s3)
+
+    def probe_scroll_work(self):
+        """PathTraceRenderer::probeScrollWork: the work counts of the last scroll_probes(count_work=True) as a dict."""
+        w = ProbeScrollWork()
+        self._ck(self.L.srt_host_renderer_probe_scroll_work(self._h, C.byref(w)))
         return w.as_dict()
 
     def radiance_work(self):

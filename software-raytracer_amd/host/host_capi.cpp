@@ -289,6 +289,16 @@ int srt_host_renderer_blend_probes(srt_host_renderer* h, const float* previous_s
 }
 int srt_host_renderer_read_probe_history(srt_host_renderer* h, uint32_t which, float* dst) { SRT_HOST_TRY(h, h->r->readProbeHistory(which, dst)) }
 int srt_host_renderer_probe_blend_work(srt_host_renderer* h, srt_probe_blend_work* out) { SRT_HOST_TRY(h, *out = h->r->probeBlendWork()) }
+// scrolling the renderer's grid (PathTraceRenderer::scrollProbes / followProbeGrid / probeScrollWork)
+int srt_host_renderer_scroll_probes(srt_host_renderer* h, const int32_t* shift, uint32_t which, uint32_t flags) {
+    SRT_HOST_TRY(h, h->r->scrollProbes(shift, which, flags))
+}
+int srt_host_renderer_follow_probe_grid(srt_host_renderer* h, const float* point, int32_t* shift) { SRT_HOST_TRY(h, {
+        const auto s = h->r->followProbeGrid(point);
+        std::memcpy(shift, s.data(), sizeof s);
+    })
+}
+int srt_host_renderer_probe_scroll_work(srt_host_renderer* h, srt_probe_scroll_work* out) { SRT_HOST_TRY(h, *out = h->r->probeScrollWork()) }
 // adaptive sampling on the handle's buffers as they stand (srt_sample_budget + srt_get_budget_total, srt_render_adaptive; a band
 // of [0, 0) means the renderer's own), and the two-half workflow (PathTraceRenderer::renderAdaptiveFrame; counts may be NULL)
 int srt_host_renderer_sample_budget(srt_host_renderer* h, const srt_budget_params* p, uint64_t* total) { SRT_HOST_TRY(h, *total = h->r->sampleBudget(*p)) }

@@ -338,7 +338,10 @@ srt_light_probe_work PathTraceRenderer::lightProbeWork() {
     return w;
 }
 
-void PathTraceRenderer::setProbeGrid(const srt_probe_grid& grid) { check(srt_set_probe_grid(ctx_, &grid), "srt_set_probe_grid"); }
+void PathTraceRenderer::setProbeGrid(const srt_probe_grid& grid) {
+    check(srt_set_probe_grid(ctx_, &grid), "srt_set_probe_grid");
+    probe_grid_ = grid, probe_grid_set_ = true;
+}
 
 void PathTraceRenderer::shadeProbeGrid(const float* coefficients, size_t probes, const srt_probe_grid_params& params) {
     srt_probe_grid_params s = params;
@@ -447,6 +450,7 @@ void PathTraceRenderer::traceProbeDepthListed(const float* positions, size_t pro
 
 void PathTraceRenderer::resetProbeHistory(uint32_t which, size_t probes, uint32_t resolution) {
     check(srt_reset_probe_history(ctx_, which, probes, resolution), "srt_reset_probe_history");
+    probe_history_which_ |= which;
 }
 
 void PathTraceRenderer::blendProbes(const float* previous_states, size_t probes, const srt_probe_blend_params& params) {
@@ -459,6 +463,33 @@ void PathTraceRenderer::readProbeHistory(uint32_t which, float* dst) { check(srt
 srt_probe_blend_work PathTraceRenderer::probeBlendWork() {
     srt_probe_blend_work w{};
     check(srt_get_probe_blend_work(ctx_, &w), "srt_get_probe_blend_work");
+    return w;
+}
+
+void PathTraceRenderer::scrollProbes(const int32_t shift[3], uint32_t which, uint32_t flags) {
+    srt_probe_scroll_params p{};
+    check(srt_probe_scroll_params_default(&p), "srt_probe_scroll_params_default");
+    for (int a = 0; a < 3; ++a) p.shift[a] = shift[a];
+    p.which = which, p.flags = flags;
+    check(srt_scroll_probes(ctx_, &p), "srt_scroll_probes");
+    if ((flags & SRT_PROBE_SCROLL_SET_GRID) && probe_grid_set_)
+        for (int a = 0; a < 3; ++a) {  // rule SC4, as the handle moved its own copy
+            volatile float step = (float)shift[a] * probe_grid_.spacing[a];
+            probe_grid_.origin[a] = probe_grid_.origin[a] + step;
+        }
+}
+
+std::array<int32_t, 3> PathTraceRenderer::followProbeGrid(const float point[3]) {
+    if (!probe_grid_set_) throw RendererError(SRT_ERR_STATE, "followProbeGrid: no grid (setProbeGrid)");
+    std::array<int32_t, 3> shift{};
+    check(srt_probe_grid_follow(&probe_grid_, point, shift.data()), "srt_probe_grid_follow");
+    scrollProbes(shift.data(), probe_history_which_ | SRT_PROBE_SCROLL_STATES, SRT_PROBE_SCROLL_SET_GRID);
+    return shift;
+}
+
+srt_probe_scroll_work PathTraceRenderer::probeScrollWork() {
+    srt_probe_scroll_work w{};
+    check(srt_get_probe_scroll_work(ctx_, &w), "srt_get_probe_scroll_work");
     return w;
 }
 

@@ -3,6 +3,7 @@
 // stands relative to its workers (Raytracer/Raytracer.cpp:329-342, 373-384, 572-595).
 #pragma once
 
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
@@ -224,6 +225,15 @@ class PathTraceRenderer {
     void blendProbes(const float* previous_states, size_t probes, const srt_probe_blend_params& params);
     void readProbeHistory(uint32_t which, float* dst);
     srt_probe_blend_work probeBlendWork();
+    // Scrolling (srt_scroll_probes) of the grid of setProbeGrid.  scrollProbes moves the arrays of `which` (SRT_PROBE_SCROLL_* bits)
+    // by `shift` cells with `flags` (SRT_PROBE_SCROLL_COUNT_WORK | _SET_GRID; with _SET_GRID the renderer's copy of the grid
+    // follows by the header's rule SC4).  followProbeGrid is srt_probe_grid_follow on that grid, then scrollProbes with the two
+    // histories that have been reset, _STATES and _SET_GRID; it returns the shift.  probeScrollWork returns the
+    // counts of a counting scroll.
+    void scrollProbes(const int32_t shift[3], uint32_t which, uint32_t flags);
+    std::array<int32_t, 3> followProbeGrid(const float point[3]);
+    srt_probe_scroll_work probeScrollWork();
+    const srt_probe_grid& probeGrid() const { return probe_grid_; }  // setProbeGrid's, as the scrolls have moved it
     // Adaptive sampling (srt_sample_budget, srt_render_adaptive), on the handle's buffers as they stand.  sampleBudget turns the
     // variance buffer, the sample counts, the accumulator and the guides into the per-pixel budget and returns its sum (waits).
     // renderAdaptive enqueues the adaptive render with the renderer's scene and camera; a band of [0, 0) means the renderer's
@@ -369,6 +379,9 @@ class PathTraceRenderer {
     std::vector<std::vector<float>> mesh_vertices_;     // ... and this mesh geometry (UpdateScene takes no other)
     std::vector<std::vector<uint32_t>> mesh_indices_;
     bool SameMeshes(const std::vector<srt_mesh>& meshes) const;
+    srt_probe_grid probe_grid_{};       // setProbeGrid's, moved by scrollProbes with SRT_PROBE_SCROLL_SET_GRID
+    bool probe_grid_set_ = false;
+    uint32_t probe_history_which_ = 0;  // the histories resetProbeHistory has sized
     std::vector<uint32_t> probe_list_;  // listProbes: the list on its way from the list output to the list for tracing
     bool temporal_reset_ = true;    // the next RenderTemporalFrame drops the history
     uint32_t temporal_frames_ = 0;  // RenderTemporalFrame calls so far (the seed offset)

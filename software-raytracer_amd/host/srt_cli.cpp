@@ -327,6 +327,10 @@ struct ProbeUpdateOptions {
 // (--probe-depth R) under --probe-tail-depth and its records (--probe-classify) under --probe-tail-states.  The frame is shaded
 // from the history.  --probe-tail-frame also renders the picture: after the rounds, PathTraceRenderer::renderProbeTailFrame(--spp,
 // --bounces, --seed) with the tail reading the history (and the maps and records the two flags ask for), written to --out.
+// --probe-scroll SX,SY,SZ [--probe-scroll-after ROUND, default 1]: after the blend of round ROUND the grid moves by SX, SY, SZ cells
+// (PathTraceRenderer::scrollProbes on the coefficient history with SRT_PROBE_SCROLL_SET_GRID | _COUNT_WORK); the positions, and the
+// flow's records and depth maps, are made again for the moved grid, and the rounds go on: the probes that stayed inside keep
+// blending, the others restart.  The frame is shaded on the moved grid.
 struct ProbeTailOptions {
     bool on = false, depth = false, states = false, normal_weight = false;
     bool frame = false;     // --probe-tail-frame
@@ -334,6 +338,9 @@ struct ProbeTailOptions {
     std::string frame_out;  // --out
     int feedback = 0;  // 0: no --probe-feedback
     int bounces = -1;  // < 0: --bounces
+    bool scroll_on = false;  // --probe-scroll
+    int32_t scroll[3] = {0, 0, 0};
+    int scroll_after = 1;    // --probe-scroll-after
     std::string grid, coefficients;
     uint32_t flags() const {
         return (depth ? SRT_PROBE_TAIL_DEPTH : 0u) | (states ? SRT_PROBE_TAIL_STATES : 0u) | (normal_weight ? SRT_PROBE_TAIL_NORMAL_WEIGHT : 0u);
@@ -355,7 +362,7 @@ static int write_ppm_file(const std::vector<uint32_t>& fb, int W, int H, const s
     return 0;
 }
 
-static int shade_probe_grid_file(Scene& scene, int device, int W, int H, int fov, const srt_probe_grid& grid, int directions, int samples, int bounces,
+static int shade_probe_grid_file(Scene& scene, int device, int W, int H, int fov, srt_probe_grid grid, int directions, int samples, int bounces,
                                  unsigned seed, uint32_t flags, bool hemisphere, const std::string& out, const ProbeDepthOptions& depth,
                                  const ProbeClassifyOptions& classify, const ProbeUpdateOptions& update, const std::vector<ObjectMove>& moves,
                                  const ProbeTailOptions& tail) {
@@ -468,6 +475,19 @@ static int shade_probe_grid_file(Scene& scene, int device, int W, int H, int fov
                     std::fprintf(stderr, "probe feedback round %d: %llu lookups, %llu dark, %llu mirror ends\n", f, (unsigned long long)w.tails,
                                  (unsigned long long)w.dark, (unsigned long long)w.mirror_ends);
                 }
+                if (tail.scroll_on && f == tail.scroll_after) {  // the grid moves; what is made per grid is made again
+                    r.scrollProbes(tail.scroll, SRT_PROBE_SCROLL_COEFFICIENTS, SRT_PROBE_SCROLL_SET_GRID | SRT_PROBE_SCROLL_COUNT_WORK);
+                    grid = r.probeGrid();
+                    srt_probe_grid_positions(&grid, pos.data());
+                    if (classify.on) classify_now();
+                    if (depth.resolution) {
+                        r.traceProbeDepth(pos.data(), np, dir.data(), (size_t)directions, dp);
+                        r.readProbeDepthOutput(SRT_PROBE_DEPTH_MOMENTS, moments.data());
+                    }
+                    const srt_probe_scroll_work w = r.probeScrollWork();
+                    std::fprintf(stderr, "probe scroll after round %d by %d,%d,%d: %llu probes, %llu retained, %llu exposed\n", f, tail.scroll[0], tail.scroll[1],
+                                 tail.scroll[2], (unsigned long long)w.probes, (unsigned long long)w.retained, (unsigned long long)w.exposed);
+                }
             }
             r.readProbeHistory(SRT_PROBE_HISTORY_COEFFICIENTS, coeff.data());
             if (tail.frame) {  // the picture: every path of the frame ends in the history the rounds have left
@@ -539,7 +559,7 @@ static void usage() {
                  "                  [--probe-depth R [--probe-depth-sharpness S] [--probe-depth-max D] [--probe-depth-bias B] [--probe-depth-out FILE]]\n"
                  "                  [--probe-classify [--probe-relocate] [--probe-clearance C] [--probe-max-offset F] [--probe-steps M] [--states-out FILE]]\n"
                  "                  [--probe-update FRAMES [--probe-hysteresis H] [--probe-samples N]]\n"
-                 "                  [--probe-tail [--probe-feedback F] [--probe-bounces B] [--probe-tail-frame [--spp N] [--out frame.ppm]]]\n"
+                 "                  [--probe-tail [--probe-feedback F [--probe-scroll SX,SY,SZ [--probe-scroll-after ROUND]]] [--probe-bounces B] [--probe-tail-frame [--spp N] [--out frame.ppm]]]\n"
                  "       srt_render --scene FILE --adaptive ROUNDS [--adaptive-threshold T] [--adaptive-max M] [--counts-out FILE] [--spp N] ...\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
                  "             a device may be listed more than once); bands of equal estimated cost (default; --balance is accepted\n"
@@ -639,6 +659,10 @@ static void usage() {
                  "             --probe-bounces B bounces, default --bounces, with the tail reading the coefficient history, then\n"
                  "             srt_blend_probes); round 1 runs with the mode off; the frame is shaded from the history;\n"
                  "             --probe-tail-depth needs --probe-depth R, --probe-tail-states needs --probe-classify; not with --probe-update\n"
+                 "  --probe-scroll SX,SY,SZ: with --probe-grid ... --probe-feedback F: after the blend of round --probe-scroll-after ROUND (1..F,\n"
+                 "             default 1) the grid moves by SX, SY, SZ whole cells (srt_scroll_probes: the coefficient history of the probes\n"
+                 "             that stay inside the grid is kept, the others restart; the origin follows), and the rounds go on; the frame is\n"
+                 "             shaded on the moved grid\n"
                  "  --probe-tail-frame: with --probe-grid ... --probe-tail: after the feedback rounds also render the picture — --spp samples per\n"
                  "             pixel from n = 0 at --bounces bounces with --seed, every path ended in the history (srt_render_adaptive_tail), with\n"
                  "             the maps and records of --probe-tail-depth / --probe-tail-states — and write it to --out as a PPM; not with\n"
@@ -659,7 +683,7 @@ int main(int argc, char** argv) {
     bool probe_classify_option = false;
     ProbeUpdateOptions probe_update;
     ProbeTailOptions probe_tail;
-    bool probe_feedback_given = false, probe_bounces_given = false;
+    bool probe_feedback_given = false, probe_bounces_given = false, probe_scroll_given = false, probe_scroll_ok = true;
     bool probe_update_given = false, probe_update_option = false;
     int adaptive = 0, adaptive_max = 0;
     bool adaptive_given = false, adaptive_threshold_given = false, adaptive_max_given = false;
@@ -753,6 +777,12 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--probe-tail-grid")) probe_tail.grid = need("--probe-tail-grid");
         else if (!std::strcmp(argv[i], "--probe-tail-coefficients")) probe_tail.coefficients = need("--probe-tail-coefficients");
         else if (!std::strcmp(argv[i], "--probe-feedback")) probe_tail.feedback = std::atoi(need("--probe-feedback")), probe_feedback_given = true;
+        else if (!std::strcmp(argv[i], "--probe-scroll")) {
+            int n = 0;
+            probe_scroll_given = probe_tail.scroll_on = true;
+            const char* v = need("--probe-scroll");
+            probe_scroll_ok = std::sscanf(v, "%d,%d,%d%n", &probe_tail.scroll[0], &probe_tail.scroll[1], &probe_tail.scroll[2], &n) == 3 && v[n] == 0;
+        } else if (!std::strcmp(argv[i], "--probe-scroll-after")) probe_tail.scroll_after = std::atoi(need("--probe-scroll-after")), probe_scroll_given = true;
         else if (!std::strcmp(argv[i], "--probe-bounces")) probe_tail.bounces = std::atoi(need("--probe-bounces")), probe_bounces_given = true;
         else if (!std::strcmp(argv[i], "--probe-samples")) probe_update.samples = std::atoi(need("--probe-samples")), probe_update_option = true;
         else if (!std::strcmp(argv[i], "--adaptive")) adaptive = std::atoi(need("--adaptive")), adaptive_given = true;
@@ -878,6 +908,11 @@ int main(int argc, char** argv) {
         probe_tail.frame_spp = spp, probe_tail.frame_out = out;
     }
     srt_probe_grid tail_grid{};
+    if (probe_scroll_given && (probe_grid_arg.empty() || !probe_feedback_given || !probe_tail.scroll_on || !probe_scroll_ok || probe_tail.scroll_after < 1 ||
+                               probe_tail.scroll_after > probe_tail.feedback)) {
+        std::fprintf(stderr, "--probe-scroll SX,SY,SZ (three integers) goes with --probe-grid ... --probe-feedback F, and --probe-scroll-after takes a round in 1..F\n");
+        return 2;
+    }
     if (probe_tail.on || probe_tail.depth || probe_tail.states || probe_tail.normal_weight || probe_feedback_given || probe_bounces_given ||
         !probe_tail.grid.empty() || !probe_tail.coefficients.empty()) {
         if (!probe_grid_arg.empty()) {  // the --probe-grid flow: feedback rounds
