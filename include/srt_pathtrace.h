@@ -1637,6 +1637,132 @@ int srt_get_probe_grid_work(srt_context* ctx, srt_probe_grid_work* out);
  * reference's interface. */
 int srt_selftest_arith(int device, uint32_t seed, uint64_t vectors, uint64_t* mismatches);
 
+/* ---- probe cascades: shade from nested probe grids, blended at borders (ABI 7, backward compatible) ------------------------------
+ * These calls were added without changing anything else, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of them
+ * runs what it ran before, bit for bit.  A grid that follows the viewer is either fine and small — every point outside it is
+ * clamped to its outer probe layer — or coarse and blurred.  A cascade is up to four grids around the same centre, level 0 the
+ * finest; srt_shade_probe_cascade gives every pixel the irradiance of the finest level that holds its first hit, blended into the
+ * next coarser level across a border band, in one pass on the device.  Each level has coefficients, and optionally depth moments
+ * and state records, of its own; the handle's single grid (srt_set_probe_grid) and its arrays are neither read nor changed by the
+ * shading.  The per-level pipeline (scroll, classify, list, trace, blend) runs through the single-grid calls, one level at a time;
+ * srt_capture_probe_cascade_level then keeps that level's results.  All arithmetic is binary32 without contraction.
+ * C1. Per-level evaluation.  For a level l, (I_l, T_l) is what the single-grid pass gives for the pixel on that level's grid,
+ *    coefficients, moments and records: probe-grid rules 1 - 9, with rule 6 under SRT_PROBE_CASCADE_NORMAL_WEIGHT, rules 3s / 4s
+ *    under _STATES and rule 7b under _DEPTH (with the call's bias and min_variance and the cascade's R); there is no any-hit query
+ *    in this pass (rule 7 never applies).  The eight corners are added ascending (rule 9).  I_l = E / T and T_l = T when T > 0,
+ *    otherwise the level is UNUSABLE.  Albedo is not applied here.
+ * C2. Level weight beta_l(x), x = SRT_GBUF_POSITION.xyz.  Per axis a with n_a >= 2: u = (x_a - origin_a) / spacing_a (rule 2's
+ *    expression before its clamp) and m = (float)(n_a - 1).  If !(u >= 0 && u <= m) on any such axis, beta_l = 0: a NaN or a point
+ *    outside gives 0.  Otherwise e starts at +inf and on the axes x, y, z in order: g = m - u; ea = u < g ? u : g;
+ *    e = ea < e ? ea : e.  beta_l = e >= blend_cells ? 1.0f : e / blend_cells.  Axes with n_a == 1 are ignored (a level of one
+ *    probe has beta = 1 everywhere).  The FIRST LEVEL f is the lowest l with beta_l > 0, or levels - 1 when there is none: the
+ *    coarsest level then serves the point through rule 2's clamp, as the single grid does.  If f == levels - 1 or beta_f >= 1 the
+ *    pixel has ONE evaluation, level f.  Otherwise it has TWO: f with weight beta = beta_f and f + 1 with weight 1.0f - beta;
+ *    level f + 1 is evaluated by C1 whatever its own beta is.  srt_probe_cascade_weights (pure host) is this rule for one point:
+ *    it returns f, the number of evaluations and beta_f (0.0f when no level holds the point); SRT_ERR_INVALID_ARG for a cascade
+ *    srt_set_probe_cascade would refuse.
+ * C3. Combination.  One evaluation: out = (I_f, T_f), or zeros if unusable.  Two, both usable:
+ *    out[l] = (beta * I_f[l]) + ((1.0f - beta) * I_f+1[l]) for l = 0, 1, 2 and a = (beta * T_f) + ((1.0f - beta) * T_f+1).  Two,
+ *    one usable: that level's (I, T) unchanged.  None usable: (0, 0, 0, 0).  With SRT_PROBE_CASCADE_ALBEDO, r, g, b are multiplied
+ *    by SRT_GBUF_ALBEDO.rgb last.  A miss pixel (OBJECT == -1) gets zeros and loads no other guide, as rule 1.  The band is rule
+ *    11's: MEMORY rows in, scene rows written, nothing outside the band.
+ * C4. Safety.  Every coefficient, moment and record index is built from cell indices clamped to [0, n_a - 1] per axis and from
+ *    f, f + 1 <= levels - 1: no load can leave an array whatever the guides hold.  The pinned domain is rule 15's.
+ * C5. Work counts.  With SRT_PROBE_CASCADE_COUNT_WORK the launch counts, deterministically: the hit pixels; the level evaluations
+ *    (1 or 2 per hit pixel); the pixels with 2; per k the hit pixels whose first level is k; the corners live after rules
+ *    3 / 3s / 5; with _DEPTH the corners whose weight stays > 0 after rule 7b (`open`, else 0); the wave-level trips — a wave
+ *    numbers its 8 x 8 tile's evaluations in lane order of the hit pixels, a pixel's level f before its level f + 1, and serves
+ *    eight evaluations (64 corner items) per trip, so a tile with Q evaluations takes ceil(Q / 8) trips; and the waves of the
+ *    launch.  One vector atomic per wave at the end; without the flag there are no atomics at all.  srt_get_probe_cascade_work
+ *    waits and copies the record of the last srt_shade_probe_cascade; SRT_ERR_STATE unless that call had the flag (or when there
+ *    has been none).  The record is the cascade's own: srt_get_probe_grid_work answers what it answered before.
+ * C6. The cascade and its arrays.  srt_set_probe_cascade copies the cascade; it refuses, with SRT_ERR_INVALID_ARG, levels outside
+ *    1 .. 4, a resolution not in {0, 4, 8, 16}, a blend_cells that is NaN, infinite or <= 0, a non-zero reserved word and a level
+ *    grid srt_set_probe_grid would refuse, and then leaves the previous cascade and all its arrays.  A level whose probe count
+ *    nx*ny*nz changed (or that is new, or gone) loses its arrays' "present" marks, own and bound, and a changed resolution takes
+ *    every level's moments; a level whose origin or spacing alone changed keeps them: the scroll case.  Per level and array
+ *    (`which` is exactly one bit): srt_write_probe_cascade_level copies `probes` elements from the host into the handle's own
+ *    array and waits, like srt_write_probe_grid_coefficients; srt_bind_probe_cascade_level binds a DEVICE array, does not copy and
+ *    does not wait; NULL, 0 returns to the own array.  Elements: SRT_PROBE_CASCADE_COEFFICIENTS 9 float4, _MOMENTS R*R float4 of
+ *    the cascade's resolution (SRT_ERR_INVALID_ARG when that is 0), _RECORDS one float4, in the single-grid layouts.  Both:
+ *    SRT_ERR_STATE without a cascade; SRT_ERR_INVALID_ARG for level >= levels, a `which` that is not one bit, probes outside
+ *    1 .. 2^30 or probes*R*R > 2^30.  srt_capture_probe_cascade_level copies, device to device on the launch stream and without
+ *    waiting, what the single-grid calls would read right now — the current probe-grid coefficients, depth moments and state
+ *    records, as selected by which_mask — into the level's OWN arrays, which become current (a binding of that array ends).
+ *    SRT_ERR_STATE without a cascade; SRT_ERR_INVALID_ARG for level >= levels or an empty or unknown mask; SRT_ERR_STATE when there
+ *    is no current grid, when its counts differ from the level's, when a selected source is absent or not of the level's P, or,
+ *    for moments, when the current R differs from the cascade's; the level is then as it was.
+ * C7. The call.  srt_shade_probe_cascade writes the probe-grid output slot (srt_bind_probe_grid_output,
+ *    srt_read_probe_grid_output serve it, as for the depth and states calls).  Asynchronous on the launch stream; cascade, arrays,
+ *    guides and output are those current at enqueue.  It leaves alone everything srt_shade_probe_grid_states leaves alone, and
+ *    the single grid, its bindings and its "last call" record as well.  Errors, all found before anything is touched, in this
+ *    order: SRT_ERR_STATE before srt_set_scene; SRT_ERR_INVALID_ARG for an empty or out-of-range band, unknown flags, a non-zero
+ *    reserved word or a NaN band_weight, and with _DEPTH for a NaN or negative bias or min_variance; SRT_ERR_STATE for no cascade;
+ *    SRT_ERR_STATE for a missing OBJECT, NORMAL_DEPTH or POSITION guide, or ALBEDO with the flag; SRT_ERR_STATE, per level
+ *    ascending, for missing coefficients or a count other than that level's P, with _DEPTH for resolution == 0 or missing or
+ *    mis-sized moments, with _STATES for missing or mis-sized records.
+ * C8. srt_probe_cascade_grids (pure host).  Level l has the given counts and spacing_a = ldexpf(base_spacing_a, l).  Its origin is
+ *    snapped to whole cells of its own spacing, so every later move is a whole-cell srt_scroll_probes shift:
+ *    k = floorf(centre_a / spacing_a), clamped to +-1048576, a NaN gives 0; origin_a = (k - (float)((n_a - 1) / 2)) * spacing_a
+ *    with integer division.  blend_cells = 1.0f, resolution = 0.  SRT_ERR_INVALID_ARG for levels outside 1 .. 4 or a level
+ *    srt_set_probe_grid would refuse; *out is then untouched.
+ * Not here: the cascade in srt_probe_tail / srt_render_adaptive_tail, the exact any-hit test per level, more than two levels per
+ * pixel, a per-level blend_cells. */
+#define SRT_PROBE_CASCADE_MAX_LEVELS 4
+/* srt_probe_cascade_params.flags */
+#define SRT_PROBE_CASCADE_NORMAL_WEIGHT 1u /* probe-grid rule 6, every level */
+#define SRT_PROBE_CASCADE_DEPTH 2u         /* rule 7b from each level's moments */
+#define SRT_PROBE_CASCADE_STATES 4u        /* rules 3s, 4s from each level's records */
+#define SRT_PROBE_CASCADE_ALBEDO 8u        /* rule C3: rgb times SRT_GBUF_ALBEDO.rgb */
+#define SRT_PROBE_CASCADE_COUNT_WORK 16u   /* fill srt_probe_cascade_work for this call */
+/* which (level arrays) */
+#define SRT_PROBE_CASCADE_COEFFICIENTS 1u  /* [P][9] float4 */
+#define SRT_PROBE_CASCADE_MOMENTS 2u       /* [P][R*R] float4 */
+#define SRT_PROBE_CASCADE_RECORDS 4u       /* [P] float4 */
+
+typedef struct srt_probe_cascade {                     /* 160 bytes */
+    uint32_t levels;                                   /* 1 .. 4; level 0 is the finest */
+    uint32_t resolution;                               /* R of every level's moments: 0 (none), 4, 8 or 16 */
+    float blend_cells;                                 /* width of the border band in cells of the level, finite, > 0 */
+    uint32_t reserved;                                 /* 0 */
+    srt_probe_grid grid[SRT_PROBE_CASCADE_MAX_LEVELS]; /* entries >= levels are ignored */
+} srt_probe_cascade;
+
+typedef struct srt_probe_cascade_params { /* 40 bytes */
+    int32_t row_begin;                    /* first memory row (inclusive), as srt_probe_grid_params */
+    int32_t row_end;                      /* one past the last memory row */
+    uint32_t flags;                       /* SRT_PROBE_CASCADE_NORMAL_WEIGHT | _DEPTH | _STATES | _ALBEDO | _COUNT_WORK */
+    float band_weight[3];                 /* A for SH bands 0, 1, 2 (probe-grid rule 10) */
+    float bias, min_variance;             /* rule 7b; read only with SRT_PROBE_CASCADE_DEPTH */
+    uint32_t reserved[2];                 /* 0 */
+} srt_probe_cascade_params;
+
+typedef struct srt_probe_cascade_work {                   /* 112 bytes */
+    uint32_t valid, reserved;                             /* 1, 0 */
+    uint64_t pixels;                                      /* hit pixels of the band */
+    uint64_t evaluations;                                 /* level evaluations: 1 or 2 per hit pixel */
+    uint64_t blended;                                     /* hit pixels with 2 */
+    uint64_t first_level[SRT_PROBE_CASCADE_MAX_LEVELS];   /* hit pixels whose first level is k */
+    uint64_t corners, open;                               /* live corners; with _DEPTH those whose weight stays > 0 */
+    uint64_t wave_trips;                                  /* sum over tiles of ceil(Q / 8) */
+    uint64_t waves;                                       /* waves of the launch */
+    uint64_t spare[2];                                    /* 0 */
+} srt_probe_cascade_work;
+
+/* flags 0, band_weight = (3.14159274f, 2.09439516f, 0.785398185f), bias and min_variance as srt_probe_grid_depth_params_default
+ * (0.0f, 1e-4f), reserved 0; row_begin = row_end = 0: the band is the caller's to fill (pure host). */
+int srt_probe_cascade_params_default(srt_probe_cascade_params* out);
+/* pure host: rule C8 */
+int srt_probe_cascade_grids(const float centre[3], const float base_spacing[3], const int32_t counts[3], uint32_t levels, srt_probe_cascade* out);
+/* pure host: rule C2 for one point */
+int srt_probe_cascade_weights(const srt_probe_cascade* cascade, const float point[3], int32_t* first_level, int32_t* evaluations, float* beta);
+int srt_set_probe_cascade(srt_context* ctx, const srt_probe_cascade* cascade);
+int srt_write_probe_cascade_level(srt_context* ctx, uint32_t level, uint32_t which, const float* src, size_t probes);
+int srt_bind_probe_cascade_level(srt_context* ctx, uint32_t level, uint32_t which, const void* d_ptr, size_t probes);
+int srt_capture_probe_cascade_level(srt_context* ctx, uint32_t level, uint32_t which_mask);
+int srt_shade_probe_cascade(srt_context* ctx, const srt_probe_cascade_params* params);
+int srt_get_probe_cascade_work(srt_context* ctx, srt_probe_cascade_work* out);
+
 /* ---- scrolling probe grids: move a grid and keep its histories (ABI 7, backward compatible) --------------------------------------
  * These calls were added without changing anything else, so SRT_ABI_VERSION stays 7.  A sequence of calls that uses none of them
  * runs what it ran before, bit for bit.  A grid that covers only the surroundings of the viewer has to move with the viewer;

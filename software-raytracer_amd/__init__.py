@@ -68,6 +68,12 @@ from .capi import (  # noqa: F401
     ProbeScrollParams,
     ProbeScrollWork,
     probe_grid_follow,
+    ProbeCascade,
+    ProbeCascadeParams,
+    ProbeCascadeWork,
+    probe_cascade,
+    probe_cascade_grids,
+    probe_cascade_weights,
     ProbeTailParams,
     ProbeTailWork,
     AdaptiveParams,
@@ -85,6 +91,6 @@ from . import host  # noqa: F401
 
 __all__ = [
     "capi", "host", "PathTracer", "SrtError", "Object", "Material", "Camera", "Environment",
-    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "SubsampleParams", "AntialiasParams", "VarianceParams", "DenoiseVarianceParams", "TemporalVarianceParams", "TraceParams", "OcclusionParams", "OcclusionWork", "VisibilityParams", "VisibilityWork", "ReflectionParams", "ReflectionWork", "MirrorHistoryParams", "RadianceParams", "RadianceWork", "LightProbeParams", "LightProbeWork", "light_probe_sphere", "light_probe_irradiance", "ProbeGrid", "ProbeGridParams", "ProbeGridWork", "probe_grid_positions", "ProbeDepthParams", "ProbeDepthWork", "ProbeGridDepthParams", "probe_depth_texels", "ProbeClassifyParams", "ProbeClassifyWork", "ProbeListParams", "ProbeListWork", "ProbeBlendParams", "ProbeBlendWork", "ProbeScrollParams", "ProbeScrollWork", "probe_grid_follow", "ProbeTailParams", "ProbeTailWork", "AdaptiveParams", "AdaptiveWork", "BudgetParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
+    "RenderParams", "GBufferParams", "DenoiseParams", "TemporalParams", "UpsampleParams", "SubsampleParams", "AntialiasParams", "VarianceParams", "DenoiseVarianceParams", "TemporalVarianceParams", "TraceParams", "OcclusionParams", "OcclusionWork", "VisibilityParams", "VisibilityWork", "ReflectionParams", "ReflectionWork", "MirrorHistoryParams", "RadianceParams", "RadianceWork", "LightProbeParams", "LightProbeWork", "light_probe_sphere", "light_probe_irradiance", "ProbeGrid", "ProbeGridParams", "ProbeGridWork", "probe_grid_positions", "ProbeDepthParams", "ProbeDepthWork", "ProbeGridDepthParams", "probe_depth_texels", "ProbeClassifyParams", "ProbeClassifyWork", "ProbeListParams", "ProbeListWork", "ProbeBlendParams", "ProbeBlendWork", "ProbeScrollParams", "ProbeScrollWork", "probe_grid_follow", "ProbeCascade", "ProbeCascadeParams", "ProbeCascadeWork", "probe_cascade", "probe_cascade_grids", "probe_cascade_weights", "ProbeTailParams", "ProbeTailWork", "AdaptiveParams", "AdaptiveWork", "BudgetParams", "Stats", "default_camera", "default_environment", "build_native", "lib_path",
     "load_library",
 ]

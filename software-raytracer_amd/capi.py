@@ -66,6 +66,10 @@ PROBE_BLEND_MOMENTS, PROBE_BLEND_LISTED, PROBE_BLEND_PREVIOUS_STATES, PROBE_BLEN
 # scrolling probe grids (srt_scroll_probes): the arrays of srt_probe_scroll_params.which, its flags
 PROBE_SCROLL_COEFFICIENTS, PROBE_SCROLL_MOMENTS, PROBE_SCROLL_STATES = 1, 2, 4
 PROBE_SCROLL_COUNT_WORK, PROBE_SCROLL_SET_GRID = 1, 2
+# probe cascades (srt_shade_probe_cascade): the most levels, the flags of srt_probe_cascade_params, the arrays of a level
+PROBE_CASCADE_MAX_LEVELS = 4
+PROBE_CASCADE_NORMAL_WEIGHT, PROBE_CASCADE_DEPTH, PROBE_CASCADE_STATES, PROBE_CASCADE_ALBEDO, PROBE_CASCADE_COUNT_WORK = 1, 2, 4, 8, 16
+PROBE_CASCADE_COEFFICIENTS, PROBE_CASCADE_MOMENTS, PROBE_CASCADE_RECORDS = 1, 2, 4
 # adaptive sampling (srt_render_adaptive, srt_sample_budget): the flags, the limits of max_samples / max_budget, the last frame
 ADAPTIVE_KEEP_COUNTS, ADAPTIVE_COUNT_WORK = 1, 2
 ADAPTIVE_MAX_SAMPLES = 4096
@@ -137,6 +141,9 @@ EXPORTS = [
     "srt_write_probe_previous_states", "srt_bind_probe_previous_states", "srt_blend_probes", "srt_get_probe_blend_work",
     "srt_probe_scroll_params_default", "srt_scroll_probes", "srt_get_probe_scroll_work", "srt_probe_grid_follow",
     "srt_read_probe_previous_states",
+    "srt_probe_cascade_params_default", "srt_probe_cascade_grids", "srt_probe_cascade_weights", "srt_set_probe_cascade",
+    "srt_write_probe_cascade_level", "srt_bind_probe_cascade_level", "srt_capture_probe_cascade_level", "srt_shade_probe_cascade",
+    "srt_get_probe_cascade_work",
     "srt_probe_tail_params_default", "srt_probe_tail", "srt_get_probe_tail_work",
     "srt_render_adaptive_tail",
 ]
@@ -474,6 +481,32 @@ class ProbeScrollWork(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+class ProbeCascade(C.Structure):
+    """srt_probe_cascade: the level count (level 0 the finest), the resolution of every level's moments (0: none), the width of the
+    border band in cells, and the levels' grids."""
+    _fields_ = [("levels", C.c_uint32), ("resolution", C.c_uint32), ("blend_cells", C.c_float), ("reserved", C.c_uint32),
+                ("grid", ProbeGrid * PROBE_CASCADE_MAX_LEVELS)]
+
+
+class ProbeCascadeParams(C.Structure):
+    """srt_probe_cascade_params: the band of memory rows, PROBE_CASCADE_* flags, the weights of SH bands 0, 1, 2 and rule 7b's bias
+    and variance floor."""
+    _fields_ = [("row_begin", C.c_int32), ("row_end", C.c_int32), ("flags", C.c_uint32), ("band_weight", C.c_float * 3), ("bias", C.c_float),
+                ("min_variance", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class ProbeCascadeWork(C.Structure):
+    """srt_probe_cascade_work: what the last counting srt_shade_probe_cascade did."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_uint64), ("evaluations", C.c_uint64), ("blended", C.c_uint64),
+                ("first_level", C.c_uint64 * PROBE_CASCADE_MAX_LEVELS), ("corners", C.c_uint64), ("open", C.c_uint64), ("wave_trips", C.c_uint64),
+                ("waves", C.c_uint64), ("spare", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "spare", "first_level")}
+        d["first_level"] = [int(v) for v in self.first_level]
+        return d
+
+
 class UpdateInfo(C.Structure):
     """srt_update_info: what the last successful srt_update_scene did to the mesh image."""
     _fields_ = [("path", C.c_int32), ("reason", C.c_int32), ("levels", C.c_int32), ("triangles", C.c_uint32), ("nodes", C.c_uint32),
@@ -710,6 +743,16 @@ def open_library(path):
     L.srt_get_probe_scroll_work.argtypes = [ctx, C.POINTER(ProbeScrollWork)]
     L.srt_read_probe_previous_states.argtypes = [ctx, C.POINTER(C.c_float)]
     L.srt_probe_grid_follow.argtypes = [C.POINTER(ProbeGrid), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+    L.srt_probe_cascade_params_default.argtypes = [C.POINTER(ProbeCascadeParams)]
+    L.srt_probe_cascade_grids.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(ProbeCascade)]
+    L.srt_probe_cascade_weights.argtypes = [C.POINTER(ProbeCascade), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_float)]
+    L.srt_set_probe_cascade.argtypes = [ctx, C.POINTER(ProbeCascade)]
+    L.srt_write_probe_cascade_level.argtypes = [ctx, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_size_t]
+    L.srt_bind_probe_cascade_level.argtypes = [ctx, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]
+    L.srt_capture_probe_cascade_level.argtypes = [ctx, C.c_uint32, C.c_uint32]
+    L.srt_shade_probe_cascade.argtypes = [ctx, C.POINTER(ProbeCascadeParams)]
+    L.srt_get_probe_cascade_work.argtypes = [ctx, C.POINTER(ProbeCascadeWork)]
     L.srt_set_sample_counts.argtypes = [ctx, C.c_uint32]
     L.srt_write_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
     L.srt_read_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
@@ -978,6 +1021,43 @@ def probe_grid_follow(grid, point, lib=None):
     if rc != OK:
         raise SrtError(rc, "srt_probe_grid_follow: not a grid srt_set_probe_grid accepts")
     return tuple(int(v) for v in shift)
+
+
+def probe_cascade(grids, resolution=0, blend_cells=1.0):
+    """An srt_probe_cascade from 1 .. 4 grids (ProbeGrid, or triples of triples), finest first (a ProbeCascade passes through)."""
+    if isinstance(grids, ProbeCascade):
+        return grids
+    c = ProbeCascade()
+    c.levels, c.resolution, c.blend_cells, c.reserved = len(grids), int(resolution), float(blend_cells), 0
+    for l, g in enumerate(grids[:PROBE_CASCADE_MAX_LEVELS]):
+        g = g if isinstance(g, ProbeGrid) else probe_grid(*g)
+        for a in range(3):
+            c.grid[l].origin[a], c.grid[l].spacing[a], c.grid[l].counts[a] = g.origin[a], g.spacing[a], g.counts[a]
+    return c
+
+
+def probe_cascade_grids(centre, base_spacing, counts, levels, lib=None):
+    """srt_probe_cascade_grids: a ProbeCascade of `levels` grids of `counts` probes around `centre`, level l with spacing
+    base_spacing * 2^l and its origin snapped to whole cells of its own spacing; blend_cells 1, resolution 0.  Pure host."""
+    L = lib or load_library()
+    out = ProbeCascade()
+    rc = L.srt_probe_cascade_grids((C.c_float * 3)(*[float(v) for v in centre]), (C.c_float * 3)(*[float(v) for v in base_spacing]),
+                                   (C.c_int32 * 3)(*[int(v) for v in counts]), int(levels), C.byref(out))
+    if rc != OK:
+        raise SrtError(rc, "srt_probe_cascade_grids: levels outside 1 .. 4, or not grids srt_set_probe_grid accepts")
+    return out
+
+
+def probe_cascade_weights(cascade, point, lib=None):
+    """srt_probe_cascade_weights: (first_level, evaluations, beta) of rule C2 for one point: the finest level that holds it (the
+    coarsest when none does), whether it is blended into the next (2) or not (1), and that level's weight.  Pure host."""
+    L = lib or load_library()
+    c = probe_cascade(cascade)
+    f, k, b = C.c_int32(), C.c_int32(), C.c_float()
+    rc = L.srt_probe_cascade_weights(C.byref(c), (C.c_float * 3)(*[float(v) for v in point]), C.byref(f), C.byref(k), C.byref(b))
+    if rc != OK:
+        raise SrtError(rc, "srt_probe_cascade_weights: not a cascade srt_set_probe_cascade accepts")
+    return int(f.value), int(k.value), np.float32(b.value)
 
 
 def probe_grid_positions(origin, spacing=None, counts=None, lib=None):
@@ -2222,6 +2302,94 @@ class PathTracer:
         """srt_read_probe_previous_states: the (probes, 4) float32 records blend_probes(previous_states=True) compares with — what
         bind_probe_previous_states() or scroll_probes(which="states") left.  Waits."""
         return self._read_image(self.L.srt_read_probe_previous_states, (int(probes), 4), np.float32)
+
+    # ---- probe cascades: nested grids, the finest level that holds a pixel blended into the next at its border ----
+    @staticmethod
+    def _cascade_bits(which):
+        if isinstance(which, (int, np.integer)):
+            return int(which)
+        names = {"coefficients": PROBE_CASCADE_COEFFICIENTS, "moments": PROBE_CASCADE_MOMENTS, "records": PROBE_CASCADE_RECORDS,
+                 "all": PROBE_CASCADE_COEFFICIENTS | PROBE_CASCADE_MOMENTS | PROBE_CASCADE_RECORDS}
+        bits = 0
+        for name in ([which] if isinstance(which, str) else which):
+            bits |= names[name]
+        return bits
+
+    def set_probe_cascade(self, grids, resolution=0, blend_cells=1.0):
+        """srt_set_probe_cascade: the cascade shade_probe_cascade() reads: a ProbeCascade (probe_cascade_grids()), or 1 .. 4 grids,
+        finest first, with the resolution R of every level's moments (0: none) and the band width in cells.  A level whose probe
+        count changed loses its arrays; one that only moved keeps them."""
+        c = probe_cascade(grids, resolution, blend_cells)
+        self._ck(self.L.srt_set_probe_cascade(self._h, C.byref(c)))
+        self._probe_cascade = c
+
+    def write_probe_cascade_level(self, level, which, array):
+        """srt_write_probe_cascade_level: copy a level's "coefficients" (P, 9, 4), "moments" (P, R*R, 4) or "records" (P, 4), numpy
+        float32, into the handle's own array of that level.  Waits."""
+        bit = self._cascade_bits(which)
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        probes = int(a.shape[0]) if a.ndim >= 1 else 0
+        self._ck(self.L.srt_write_probe_cascade_level(self._h, int(level), bit, a.ctypes.data_as(C.POINTER(C.c_float)), probes))
+        self.__dict__.setdefault("_probe_cascade_bound", {}).pop((int(level), bit), None)
+
+    def bind_probe_cascade_level(self, level, which, tensor, probes=None):
+        """srt_bind_probe_cascade_level: read a level's "coefficients", "moments" or "records" from a float32 torch tensor on this
+        tracer's device, contiguous, (P, 9, 4) / (P, R*R, 4) / (P, 4) (or flat with `probes` given); no copy, the caller keeps it
+        alive.  None: back to the own array."""
+        bit = self._cascade_bits(which)
+        bound = self.__dict__.setdefault("_probe_cascade_bound", {})
+        if tensor is None:
+            self._ck(self.L.srt_bind_probe_cascade_level(self._h, int(level), bit, None, 0))
+            bound.pop((int(level), bit), None)
+            return
+        import torch
+
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError("bind_probe_cascade_level: expected a torch.Tensor, got %s" % type(tensor).__name__)
+        n = int(probes) if probes is not None else (int(tensor.shape[0]) if tensor.dim() >= 1 else 0)
+        ptr = self._tensor_ptr("bind_probe_cascade_level", tensor, np.float32, tuple(tensor.shape))
+        self._ck(self.L.srt_bind_probe_cascade_level(self._h, int(level), bit, ptr, n))
+        bound[(int(level), bit)] = tensor
+
+    def capture_probe_cascade_level(self, level, which="all"):
+        """srt_capture_probe_cascade_level: copy, on the device, what the single-grid calls would read now (the current probe-grid
+        coefficients, depth moments, state records, as `which` selects) into the level's own arrays.  Asynchronous."""
+        bits = self._cascade_bits(which)
+        self._ck(self.L.srt_capture_probe_cascade_level(self._h, int(level), bits))
+        bound = self.__dict__.setdefault("_probe_cascade_bound", {})
+        for b in (PROBE_CASCADE_COEFFICIENTS, PROBE_CASCADE_MOMENTS, PROBE_CASCADE_RECORDS):
+            if bits & b:
+                bound.pop((int(level), b), None)
+
+    def shade_probe_cascade(self, depth=False, states=False, normal_weight=False, albedo=False, band_weight=None, bias=None, min_variance=None,
+                            rows=None, count_work=False, output=None, flags=0, reserved=(0, 0)):
+        """srt_shade_probe_cascade: per pixel the irradiance of the finest level of set_probe_cascade() that holds its first hit,
+        blended into the next coarser level across the border band.  depth / states: rule 7b from each level's moments, rules
+        3s / 4s from each level's records; the other arguments as shade_probe_grid_states().  probe_grid_output() reads the result,
+        probe_cascade_work() the counts.  Asynchronous."""
+        L = self.L
+        if output is not None:
+            self.bind_probe_grid_output(output)
+        p = ProbeCascadeParams()
+        self._ck(L.srt_probe_cascade_params_default(C.byref(p)))
+        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
+        p.flags = (int(flags) | (PROBE_CASCADE_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_CASCADE_DEPTH if depth else 0) |
+                   (PROBE_CASCADE_STATES if states else 0) | (PROBE_CASCADE_ALBEDO if albedo else 0) | (PROBE_CASCADE_COUNT_WORK if count_work else 0))
+        if band_weight is not None:
+            for b in range(3):
+                p.band_weight[b] = float(band_weight[b])
+        if bias is not None:
+            p.bias = float(bias)
+        if min_variance is not None:
+            p.min_variance = float(min_variance)
+        p.reserved[0], p.reserved[1] = int(reserved[0]), int(reserved[1])
+        self._ck(L.srt_shade_probe_cascade(self._h, C.byref(p)))
+
+    def probe_cascade_work(self):
+        """srt_get_probe_cascade_work: the work counts of the last shade_probe_cascade(count_work=True) as a dict.  Waits."""
+        w = ProbeCascadeWork()
+        self._ck(self.L.srt_get_probe_cascade_work(self._h, C.byref(w)))
+        return w.as_dict()
 
     def ray_output(self, name, count=None):
         """srt_read_ray_output: one output of the last trace_rays() as a numpy array: "object" and "occluded" (N,) int32, the

@@ -51,6 +51,8 @@
 #include "srt_probe_update_host.h"
 #include "srt_probe_scroll.hip.h"
 #include "srt_probe_scroll_host.h"
+#include "srt_probe_cascade.hip.h"
+#include "srt_probe_cascade_host.h"
 #include "srt_probe_tail.hip.h"
 #include "srt_probe_tail_host.h"
 #include "srt_adaptive.hip.h"
@@ -475,6 +477,12 @@ struct srt_context {
     srt::ProbeScrollState probe_scroll;
     DeviceBuffer<float4> d_probe_history_spare[srt::PROBE_HISTORY_SLOTS];
     DeviceBuffer<unsigned long long> d_probe_scroll_work;
+    // the probe cascade (srt_shade_probe_cascade): the cascade, which array of each level is current and whether the last call
+    // counted (srt_probe_cascade_host.h); the own arrays per level (coefficients, moments, records; they grow on demand); the record
+    // a counting launch adds to (srt::PC_WORK_N words).  The output is the probe-grid slot's.
+    srt::ProbeCascadeState probe_cascade;
+    DeviceBuffer<float4> d_probe_cascade[srt::PROBE_CASCADE_MAX_LEVELS][srt::PROBE_CASCADE_ARRAYS];
+    DeviceBuffer<unsigned long long> d_probe_cascade_work;
     // the probe tail (srt_probe_tail): the mode's setting and whether the last affected trace ran under it and counted
     // (srt_probe_tail_host.h); the record a counting launch adds to (srt::PT_WORK_N words)
     srt::ProbeTailState probe_tail;
@@ -3154,6 +3162,165 @@ int srt_get_probe_scroll_work(srt_context* ctx, srt_probe_scroll_work* out) {
     if (const int rc = read_work(ctx, ctx->d_probe_scroll_work, w, srt::PSC_WORK_N)) return rc;
     out->valid = 1, out->reserved = 0;
     out->probes = w[srt::PSC_WORK_PROBES], out->retained = w[srt::PSC_WORK_RETAINED], out->exposed = w[srt::PSC_WORK_EXPOSED], out->waves = w[srt::PSC_WORK_WAVES];
+    return SRT_OK;
+}
+
+// ---- probe cascade -------------------------------------------------------------------------------------------------
+static_assert(SRT_PROBE_CASCADE_MAX_LEVELS == srt::PROBE_CASCADE_MAX_LEVELS && SRT_PROBE_CASCADE_MAX_LEVELS == srt::PC_LEVELS &&
+              SRT_PROBE_CASCADE_NORMAL_WEIGHT == srt::PROBE_CASCADE_FLAG_NORMAL_WEIGHT && SRT_PROBE_CASCADE_DEPTH == srt::PROBE_CASCADE_FLAG_DEPTH &&
+              SRT_PROBE_CASCADE_STATES == srt::PROBE_CASCADE_FLAG_STATES && SRT_PROBE_CASCADE_ALBEDO == srt::PROBE_CASCADE_FLAG_ALBEDO &&
+              SRT_PROBE_CASCADE_COUNT_WORK == srt::PROBE_CASCADE_FLAG_COUNT_WORK && SRT_PROBE_CASCADE_COEFFICIENTS == srt::PROBE_CASCADE_COEFFICIENTS &&
+              SRT_PROBE_CASCADE_MOMENTS == srt::PROBE_CASCADE_MOMENTS && SRT_PROBE_CASCADE_RECORDS == srt::PROBE_CASCADE_RECORDS &&
+              sizeof(srt_probe_cascade) == 160 && sizeof(srt::ProbeCascade) == 160 && sizeof(srt_probe_cascade_params) == 40 && sizeof(srt::ProbeCascadeCall) == 40 &&
+              sizeof(srt_probe_cascade_work) == 112 && srt::PC_WORK_N == 11 && sizeof(srt::ProbeCascadeLevel) == 64,
+              "srt_probe_cascade_host.h, srt_probe_cascade.hip.h and srt_pathtrace.h disagree");
+
+int srt_probe_cascade_params_default(srt_probe_cascade_params* out) {
+    if (!out) return SRT_ERR_INVALID_ARG;
+    srt::ProbeCascadeCall c;
+    srt::probe_cascade_call_default(c);
+    memcpy(out, &c, sizeof c);
+    return SRT_OK;
+}
+
+int srt_probe_cascade_grids(const float centre[3], const float base_spacing[3], const int32_t counts[3], uint32_t levels, srt_probe_cascade* out) {
+    if (!centre || !base_spacing || !counts || !out) return SRT_ERR_INVALID_ARG;
+    srt::ProbeCascade c;
+    if (srt::probe_cascade_grids(centre, base_spacing, counts, levels, c) != srt::RAYS_OK) return SRT_ERR_INVALID_ARG;
+    memcpy(out, &c, sizeof c);
+    return SRT_OK;
+}
+
+int srt_probe_cascade_weights(const srt_probe_cascade* cascade, const float point[3], int32_t* first_level, int32_t* evaluations, float* beta) {
+    if (!cascade || !point || !first_level || !evaluations || !beta) return SRT_ERR_INVALID_ARG;
+    srt::ProbeCascade c;
+    memcpy(&c, cascade, sizeof c);
+    if (srt::probe_cascade_check(c, nullptr) != srt::RAYS_OK) return SRT_ERR_INVALID_ARG;
+    srt::probe_cascade_weights(c, point, first_level, evaluations, beta);
+    return SRT_OK;
+}
+
+int srt_set_probe_cascade(srt_context* ctx, const srt_probe_cascade* cascade) {
+    if (!ctx || !cascade) return SRT_ERR_INVALID_ARG;
+    srt::ProbeCascade c;
+    memcpy(&c, cascade, sizeof c);
+    const char* why = "";
+    if (srt::probe_cascade_set(ctx->probe_cascade, c, &why) != srt::RAYS_OK)  // (an enqueued launch keeps the cascade it was given: a kernel argument)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_set_probe_cascade: %s (levels %u, resolution %u, blend_cells %g, reserved %u)", why, c.levels, c.resolution,
+                    (double)c.blend_cells, c.reserved);
+    return SRT_OK;
+}
+
+int srt_write_probe_cascade_level(srt_context* ctx, uint32_t level, uint32_t which, const float* src, size_t probes) {
+    if (!ctx || !src) return SRT_ERR_INVALID_ARG;
+    int slot = -1;
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_cascade_check_level_array(ctx->probe_cascade, level, which, probes, &slot, &why))
+        return fail(ctx, (int)rs, "srt_write_probe_cascade_level: %s (level %u, which 0x%x, %zu probes)", why, level, which, probes);
+    return write_probe_input(ctx, ctx->probe_cascade.arrays[level][slot], ctx->d_probe_cascade[level][slot], src, probes,
+                             srt::probe_cascade_probe_bytes(slot, ctx->probe_cascade.cascade.resolution));
+}
+
+int srt_bind_probe_cascade_level(srt_context* ctx, uint32_t level, uint32_t which, const void* d_ptr, size_t probes) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    int slot = -1;
+    const char* why = "";
+    const bool unbind = !d_ptr && probes == 0;
+    if (const srt::RaysStatus rs = srt::probe_cascade_check_level_array(ctx->probe_cascade, level, which, unbind ? 1 : probes, &slot, &why))
+        return fail(ctx, (int)rs, "srt_bind_probe_cascade_level: %s (level %u, which 0x%x, %zu probes)", why, level, which, probes);
+    if (srt::light_probe_bind(ctx->probe_cascade.arrays[level][slot], d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_cascade_level: want a device array and 1 .. 2^30 probes, or NULL, 0 (got %zu)", probes);
+    return SRT_OK;
+}
+
+int srt_capture_probe_cascade_level(srt_context* ctx, uint32_t level, uint32_t which_mask) {
+    if (!ctx) return SRT_ERR_INVALID_ARG;
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_cascade_check_capture(ctx->probe_cascade, level, which_mask, ctx->probe_grid, ctx->probe_grid_depth, ctx->probe_states, &why))
+        return fail(ctx, (int)rs, "srt_capture_probe_cascade_level: %s (level %u, which 0x%x)", why, level, which_mask);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t np = srt::probe_grid_probes(ctx->probe_cascade.cascade.grid[level]);
+    const float4* const src[srt::PROBE_CASCADE_ARRAYS] = {current(ctx->probe_grid.coefficients, ctx->d_probe_grid_coefficients),
+                                                          current(ctx->probe_grid_depth.moments, ctx->d_probe_grid_depth),
+                                                          current(ctx->probe_states.states, ctx->d_probe_grid_states)};
+    for (int i = 0; i < srt::PROBE_CASCADE_ARRAYS; ++i) {
+        if (!(which_mask & (1u << i))) continue;
+        const size_t bytes = np * srt::probe_cascade_probe_bytes(i, ctx->probe_cascade.cascade.resolution);
+        DeviceBuffer<float4>& own = ctx->d_probe_cascade[level][i];
+        srt::LightProbeInput& in = ctx->probe_cascade.arrays[level][i];
+        if (own.bytes() < bytes) {
+            if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it is re-allocated below)
+            in.own_count = 0;                                  // (a failed allocation leaves no own array)
+            SRT_HIP(ctx, own.ensure(bytes));
+        }
+        SRT_HIP(ctx, hipMemcpyAsync(own, src[i], bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        srt::light_probe_written(in, np);  // (a binding of that array ends)
+    }
+    return SRT_OK;
+}
+
+int srt_shade_probe_cascade(srt_context* ctx, const srt_probe_cascade_params* s) {
+    if (!ctx || !s) return SRT_ERR_INVALID_ARG;
+    srt::ProbeCascadeCall call;
+    memcpy(&call, s, sizeof call);
+    bool present[srt::PROBE_GRID_GUIDES];
+    for (int i = 0; i < srt::PROBE_GRID_GUIDES; ++i) present[i] = current(ctx->gbuf[i], ctx->d_gbuf_own[i]) != nullptr;
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::probe_cascade_check_shade(ctx->probe_cascade, call, ctx->scene_set, ctx->height, present, &why))
+        return fail(ctx, (int)rs, "srt_shade_probe_cascade: %s (rows [%d,%d) of %d, flags 0x%x, band_weight %g %g %g, bias %g, min_variance %g, reserved %u %u)", why,
+                    s->row_begin, s->row_end, ctx->height, s->flags, (double)s->band_weight[0], (double)s->band_weight[1], (double)s->band_weight[2], (double)s->bias,
+                    (double)s->min_variance, s->reserved[0], s->reserved[1]);
+    SRT_HIP(ctx, hipSetDevice(ctx->device));
+    const bool count = (s->flags & SRT_PROBE_CASCADE_COUNT_WORK) != 0, depth = (s->flags & SRT_PROBE_CASCADE_DEPTH) != 0,
+               states = (s->flags & SRT_PROBE_CASCADE_STATES) != 0;
+    float4* dst = nullptr;
+    SRT_WRITE_TARGET(ctx, ctx->probe_grid_out, ctx->d_probe_grid_own, frame_pixels(ctx) * sizeof(float4), dst);
+    if (count) {
+        if (const int rc = zero_work(ctx, ctx->d_probe_cascade_work, srt::PC_WORK_N)) return rc;
+    }
+    srt::KernelParams K;
+    KernelSetup ks = scene_kernel_params(ctx, s->row_begin, s->row_end, K);
+    ks.lds_bytes = 0;  // (the kernel traces nothing: no scene image, and its own LDS is static)
+    void (*kernel)(srt::KernelParams, srt::ProbeCascadeIO) =
+        depth ? (states ? (count ? srt::probe_cascade_kernel<true, true, true> : srt::probe_cascade_kernel<true, true, false>)
+                        : (count ? srt::probe_cascade_kernel<true, false, true> : srt::probe_cascade_kernel<true, false, false>))
+              : (states ? (count ? srt::probe_cascade_kernel<false, true, true> : srt::probe_cascade_kernel<false, true, false>)
+                        : (count ? srt::probe_cascade_kernel<false, false, true> : srt::probe_cascade_kernel<false, false, false>));
+    const srt::ProbeCascade& c = ctx->probe_cascade.cascade;
+    srt::ProbeCascadeIO io{};
+    io.object = (const int32_t*)current(ctx->gbuf[0], ctx->d_gbuf_own[0]);
+    io.normal_depth = (const float4*)current(ctx->gbuf[1], ctx->d_gbuf_own[1]);
+    io.position = (const float4*)current(ctx->gbuf[2], ctx->d_gbuf_own[2]);
+    io.albedo = (s->flags & SRT_PROBE_CASCADE_ALBEDO) ? (const float4*)current(ctx->gbuf[3], ctx->d_gbuf_own[3]) : nullptr;
+    io.out = dst;
+    for (uint32_t l = 0; l < c.levels; ++l) {
+        srt::ProbeCascadeLevel& lv = io.level[l];
+        for (int a = 0; a < 3; ++a) lv.origin[a] = c.grid[l].origin[a], lv.spacing[a] = c.grid[l].spacing[a], lv.counts[a] = c.grid[l].counts[a];
+        lv.coefficients = current(ctx->probe_cascade.arrays[l][0], ctx->d_probe_cascade[l][0]);
+        lv.depth = depth ? current(ctx->probe_cascade.arrays[l][1], ctx->d_probe_cascade[l][1]) : nullptr;
+        lv.states = states ? current(ctx->probe_cascade.arrays[l][2], ctx->d_probe_cascade[l][2]) : nullptr;
+    }
+    io.levels = c.levels, io.resolution = c.resolution, io.blend_cells = c.blend_cells;
+    for (int b = 0; b < 3; ++b) io.band_weight[b] = s->band_weight[b];
+    io.normal_weight = (s->flags & SRT_PROBE_CASCADE_NORMAL_WEIGHT) ? 1u : 0u;
+    io.bias = s->bias, io.min_variance = s->min_variance;
+    io.work = count ? (unsigned long long*)ctx->d_probe_cascade_work : nullptr;
+    if (const int rc = launch_tiles(ctx, kernel, ks, K, io)) return rc;
+    ctx->probe_grid_out.wrote(dst);
+    srt::probe_cascade_shaded(ctx->probe_cascade, s->flags);
+    return SRT_OK;
+}
+
+int srt_get_probe_cascade_work(srt_context* ctx, srt_probe_cascade_work* out) {
+    if (!ctx || !out) return SRT_ERR_INVALID_ARG;
+    if (srt::probe_cascade_check_work(ctx->probe_cascade) != srt::RAYS_OK)
+        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_cascade_work: the last srt_shade_probe_cascade did not ask for SRT_PROBE_CASCADE_COUNT_WORK (or there has been none)");
+    unsigned long long w[srt::PC_WORK_N];
+    if (const int rc = read_work(ctx, ctx->d_probe_cascade_work, w, srt::PC_WORK_N)) return rc;
+    out->valid = 1, out->reserved = 0, out->spare[0] = 0, out->spare[1] = 0;
+    out->pixels = w[srt::PC_WORK_PIXELS], out->evaluations = w[srt::PC_WORK_EVALUATIONS], out->blended = w[srt::PC_WORK_BLENDED];
+    for (int k = 0; k < SRT_PROBE_CASCADE_MAX_LEVELS; ++k) out->first_level[k] = w[srt::PC_WORK_FIRST0 + k];
+    out->corners = w[srt::PC_WORK_CORNERS], out->open = w[srt::PC_WORK_OPEN], out->wave_trips = w[srt::PC_WORK_TRIPS], out->waves = w[srt::PC_WORK_WAVES];
     return SRT_OK;
 }
 

@@ -21,6 +21,8 @@ from .capi import (PROBE_BLEND_COUNT_WORK, PROBE_BLEND_LISTED, PROBE_BLEND_MOMEN
                    PROBE_HISTORY_MOMENTS, PROBE_IDLE, PROBE_LIST_COUNT_WORK, PROBE_LIST_HEADER, ProbeBlendParams, ProbeBlendWork, ProbeListParams,
                    ProbeListWork)  # noqa: F401
 from .capi import PROBE_SCROLL_COUNT_WORK, PROBE_SCROLL_SET_GRID, PathTracer as _PathTracer, ProbeScrollWork  # noqa: F401
+from .capi import (PROBE_CASCADE_ALBEDO, PROBE_CASCADE_COUNT_WORK, PROBE_CASCADE_DEPTH, PROBE_CASCADE_NORMAL_WEIGHT, PROBE_CASCADE_STATES, ProbeCascade,  # noqa: F401
+                   ProbeCascadeParams, ProbeCascadeWork, probe_cascade)
 from .capi import PROBE_TAIL_COUNT_WORK, PROBE_TAIL_DEPTH, PROBE_TAIL_NORMAL_WEIGHT, PROBE_TAIL_STATES, ProbeTailParams, ProbeTailWork  # noqa: F401
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -64,6 +66,8 @@ EXPORTS = [
     "srt_host_renderer_trace_light_probes_listed", "srt_host_renderer_trace_probe_depth_listed", "srt_host_renderer_reset_probe_history",
     "srt_host_renderer_blend_probes", "srt_host_renderer_read_probe_history", "srt_host_renderer_probe_blend_work",
     "srt_host_renderer_scroll_probes", "srt_host_renderer_follow_probe_grid", "srt_host_renderer_probe_scroll_work",
+    "srt_host_renderer_set_probe_cascade", "srt_host_renderer_capture_probe_cascade_level", "srt_host_renderer_shade_probe_cascade",
+    "srt_host_renderer_probe_cascade_work",
     "srt_host_renderer_sample_budget", "srt_host_renderer_render_adaptive", "srt_host_renderer_set_sample_counts",
     "srt_host_renderer_read_sample_counts", "srt_host_renderer_adaptive_frame",
     "srt_host_multi_create", "srt_host_multi_destroy", "srt_host_multi_set_scene", "srt_host_multi_configure",
@@ -186,6 +190,10 @@ def load_library():
     L.srt_host_renderer_scroll_probes.argtypes = [vp, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32]
     L.srt_host_renderer_follow_probe_grid.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     L.srt_host_renderer_probe_scroll_work.argtypes = [vp, C.POINTER(ProbeScrollWork)]
+    L.srt_host_renderer_set_probe_cascade.argtypes = [vp, C.POINTER(ProbeCascade)]
+    L.srt_host_renderer_capture_probe_cascade_level.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.srt_host_renderer_shade_probe_cascade.argtypes = [vp, C.POINTER(ProbeCascadeParams)]
+    L.srt_host_renderer_probe_cascade_work.argtypes = [vp, C.POINTER(ProbeCascadeWork)]
     L.srt_host_renderer_blend_probes.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(ProbeBlendParams)]
     L.srt_host_renderer_read_probe_history.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float)]
     L.srt_host_renderer_probe_blend_work.argtypes = [vp, C.POINTER(ProbeBlendWork)]
@@ -801,6 +809,39 @@ class Renderer:
         """PathTraceRenderer::probeScrollWork: the work counts of the last scroll_probes(count_work=True) as a dict."""
         w = ProbeScrollWork()
         self._ck(self.L.srt_host_renderer_probe_scroll_work(self._h, C.byref(w)))
+        return w.as_dict()
+
+    def set_probe_cascade(self, grids, resolution=0, blend_cells=1.0):
+        """PathTraceRenderer::setProbeCascade: srt_set_probe_cascade, as PathTracer.set_probe_cascade takes it."""
+        c = probe_cascade(grids, resolution, blend_cells)
+        self._ck(self.L.srt_host_renderer_set_probe_cascade(self._h, C.byref(c)))
+
+    def capture_probe_cascade_level(self, level, which="all"):
+        """PathTraceRenderer::captureProbeCascadeLevel: copy the current probe-grid coefficients, depth moments and state records,
+        as `which` selects (PathTracer.capture_probe_cascade_level's names), into the cascade's level on the device."""
+        self._ck(self.L.srt_host_renderer_capture_probe_cascade_level(self._h, int(level), _PathTracer._cascade_bits(which)))
+
+    def shade_probe_cascade(self, depth=False, states=False, normal_weight=False, albedo=False, band_weight=None, bias=None, min_variance=None, rows=None,
+                            count_work=False):
+        """PathTraceRenderer::shadeProbeCascade + readProbeGridOutput: render the guides of the band with the current scene and
+        camera, enqueue srt_shade_probe_cascade (capi.PathTracer.shade_probe_cascade's arguments; rows=None: the renderer's own
+        band) and return the (H, W, 4) float32 result."""
+        p = ProbeCascadeParams()  # (srt_probe_cascade_params_default's values)
+        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, 0)
+        p.flags = ((PROBE_CASCADE_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_CASCADE_DEPTH if depth else 0) | (PROBE_CASCADE_STATES if states else 0) |
+                   (PROBE_CASCADE_ALBEDO if albedo else 0) | (PROBE_CASCADE_COUNT_WORK if count_work else 0))
+        bw = band_weight if band_weight is not None else PROBE_GRID_BAND_WEIGHT_IRRADIANCE
+        for b in range(3):
+            p.band_weight[b] = float(bw[b])
+        p.bias = float(bias) if bias is not None else 0.0
+        p.min_variance = float(min_variance) if min_variance is not None else 1e-4
+        self._ck(self.L.srt_host_renderer_shade_probe_cascade(self._h, C.byref(p)))
+        return self.probe_grid_output()
+
+    def probe_cascade_work(self):
+        """PathTraceRenderer::probeCascadeWork: the work counts of the last shade_probe_cascade(count_work=True) as a dict."""
+        w = ProbeCascadeWork()
+        self._ck(self.L.srt_host_renderer_probe_cascade_work(self._h, C.byref(w)))
         return w.as_dict()
 
     def radiance_work(self):

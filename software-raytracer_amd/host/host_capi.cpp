@@ -299,6 +299,14 @@ int srt_host_renderer_follow_probe_grid(srt_host_renderer* h, const float* point
     })
 }
 int srt_host_renderer_probe_scroll_work(srt_host_renderer* h, srt_probe_scroll_work* out) { SRT_HOST_TRY(h, *out = h->r->probeScrollWork()) }
+// probe cascades on the renderer's handle (PathTraceRenderer::setProbeCascade / captureProbeCascadeLevel / shadeProbeCascade /
+// probeCascadeWork: the guides are rendered, a band of [0, 0) means the renderer's own; the output is the probe-grid pass's)
+int srt_host_renderer_set_probe_cascade(srt_host_renderer* h, const srt_probe_cascade* c) { SRT_HOST_TRY(h, h->r->setProbeCascade(*c)) }
+int srt_host_renderer_capture_probe_cascade_level(srt_host_renderer* h, uint32_t level, uint32_t which) {
+    SRT_HOST_TRY(h, h->r->captureProbeCascadeLevel(level, which))
+}
+int srt_host_renderer_shade_probe_cascade(srt_host_renderer* h, const srt_probe_cascade_params* p) { SRT_HOST_TRY(h, h->r->shadeProbeCascade(*p)) }
+int srt_host_renderer_probe_cascade_work(srt_host_renderer* h, srt_probe_cascade_work* out) { SRT_HOST_TRY(h, *out = h->r->probeCascadeWork()) }
 // adaptive sampling on the handle's buffers as they stand (srt_sample_budget + srt_get_budget_total, srt_render_adaptive; a band
 // of [0, 0) means the renderer's own), and the two-half workflow (PathTraceRenderer::renderAdaptiveFrame; counts may be NULL)
 int srt_host_renderer_sample_budget(srt_host_renderer* h, const srt_budget_params* p, uint64_t* total) { SRT_HOST_TRY(h, *total = h->r->sampleBudget(*p)) }

@@ -493,6 +493,27 @@ srt_probe_scroll_work PathTraceRenderer::probeScrollWork() {
     return w;
 }
 
+void PathTraceRenderer::setProbeCascade(const srt_probe_cascade& cascade) { check(srt_set_probe_cascade(ctx_, &cascade), "srt_set_probe_cascade"); }
+
+void PathTraceRenderer::captureProbeCascadeLevel(uint32_t level, uint32_t which) {
+    check(srt_capture_probe_cascade_level(ctx_, level, which), "srt_capture_probe_cascade_level");
+}
+
+void PathTraceRenderer::shadeProbeCascade(const srt_probe_cascade_params& params) {
+    srt_probe_cascade_params s = params;
+    if (s.row_begin == 0 && s.row_end == 0) s.row_begin = row_begin_, s.row_end = row_end_;
+    FirstHitScope first_hits(*this);  // irradiance AT the first hit
+    RenderGBufferRows(SRT_GBUF_OBJECT | SRT_GBUF_NORMAL_DEPTH | SRT_GBUF_POSITION | ((s.flags & SRT_PROBE_CASCADE_ALBEDO) ? SRT_GBUF_ALBEDO : 0u), s.row_begin,
+                      s.row_end);  // (pushes the camera)
+    check(srt_shade_probe_cascade(ctx_, &s), "srt_shade_probe_cascade");
+}
+
+srt_probe_cascade_work PathTraceRenderer::probeCascadeWork() {
+    srt_probe_cascade_work w{};
+    check(srt_get_probe_cascade_work(ctx_, &w), "srt_get_probe_cascade_work");
+    return w;
+}
+
 uint64_t PathTraceRenderer::sampleBudget(const srt_budget_params& params) {
     check(srt_sample_budget(ctx_, &params), "srt_sample_budget");
     uint64_t total = 0;

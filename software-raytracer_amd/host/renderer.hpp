@@ -234,6 +234,17 @@ class PathTraceRenderer {
     std::array<int32_t, 3> followProbeGrid(const float point[3]);
     srt_probe_scroll_work probeScrollWork();
     const srt_probe_grid& probeGrid() const { return probe_grid_; }  // setProbeGrid's, as the scrolls have moved it
+    // Probe cascades (srt_set_probe_cascade, srt_capture_probe_cascade_level, srt_shade_probe_cascade): up to four nested grids,
+    // level 0 the finest.  setProbeCascade sets the cascade.  A level is filled through the single-grid calls above (setProbeGrid
+    // on the level's grid, classifyProbes, the traces, the blend, with their results written or bound as the current probe-grid
+    // coefficients, depth moments and states), then captureProbeCascadeLevel copies what is current, as `which`
+    // (SRT_PROBE_CASCADE_COEFFICIENTS | _MOMENTS | _RECORDS) selects, into the level on the device.  shadeProbeCascade renders the
+    // guides as shadeProbeGrid does and enqueues the pass; a band of [0, 0) means the renderer's own; readProbeGridOutput reads the
+    // result; probeCascadeWork returns the counts of a call that had SRT_PROBE_CASCADE_COUNT_WORK.
+    void setProbeCascade(const srt_probe_cascade& cascade);
+    void captureProbeCascadeLevel(uint32_t level, uint32_t which);
+    void shadeProbeCascade(const srt_probe_cascade_params& params);
+    srt_probe_cascade_work probeCascadeWork();
     // Adaptive sampling (srt_sample_budget, srt_render_adaptive), on the handle's buffers as they stand.  sampleBudget turns the
     // variance buffer, the sample counts, the accumulator and the guides into the per-pixel budget and returns its sum (waits).
     // renderAdaptive enqueues the adaptive render with the renderer's scene and camera; a band of [0, 0) means the renderer's

@@ -541,6 +541,88 @@ static int shade_probe_grid_file(Scene& scene, int device, int W, int H, int fov
     }
 }
 
+// --probe-grid G --probe-directions K --probe-cascade L [--probe-cascade-blend B] --irradiance-out FILE: the frame shaded from L
+// nested grids (srt_shade_probe_cascade).  The levels come from srt_probe_cascade_grids around the camera position, with G's
+// spacing as the finest spacing and G's counts (G's origin is not read); per level the route of --probe-grid runs on the level's
+// grid through the single-grid calls — the classification (--probe-classify), the probes traced at the positions it gives, the
+// depth maps (--probe-depth R) — and PathTraceRenderer::captureProbeCascadeLevel keeps its results; then the cascade shading runs
+// in place of the single-grid call.  FILE receives W*H float4, scene rows.
+static int shade_probe_cascade_file(Scene& scene, int device, int W, int H, int fov, const srt_probe_grid& finest, int levels, float blend, int directions,
+                                    int samples, int bounces, unsigned seed, uint32_t grid_flags, bool hemisphere, const std::string& out,
+                                    const ProbeDepthOptions& depth, const ProbeClassifyOptions& classify) {
+    const size_t np = (size_t)finest.counts[0] * (size_t)finest.counts[1] * (size_t)finest.counts[2];
+    std::vector<float> pos(4 * np), dir(4 * (size_t)directions);
+    srt_light_probe_sphere((size_t)directions, dir.data());
+    try {
+        PathTraceRenderer r(device, W, H);
+        r.FOV = fov;
+        r.MAXBOUNCES = bounces;
+        r.seed = seed;
+        r.SetScene(scene);
+        const float centre[3] = {r.camera.position.x, r.camera.position.y, r.camera.position.z};
+        srt_probe_cascade cascade{};
+        if (srt_probe_cascade_grids(centre, finest.spacing, finest.counts, (uint32_t)levels, &cascade) != SRT_OK) {
+            std::fprintf(stderr, "--probe-cascade: the levels' spacings must stay finite and the probes of a level at most 2^30\n");
+            return 2;
+        }
+        cascade.resolution = (uint32_t)depth.resolution, cascade.blend_cells = blend;
+        r.setProbeCascade(cascade);
+        srt_light_probe_params lp{};
+        srt_light_probe_params_default(&lp);
+        lp.sample_count = (uint32_t)samples, lp.max_bounces = bounces, lp.seed = seed;
+        srt_probe_classify_params cp{};
+        srt_probe_classify_params_default(&cp);
+        cp.clearance = classify.clearance, cp.max_offset = classify.max_offset, cp.steps = (uint32_t)classify.steps;
+        cp.flags = classify.relocate ? SRT_PROBE_CLASSIFY_RELOCATE : 0u;
+        cp.outputs = SRT_PROBE_STATE_RECORDS | SRT_PROBE_STATE_POSITIONS;
+        srt_probe_depth_params dp{};
+        srt_probe_depth_params_default(&dp);
+        if (depth.resolution) dp.resolution = (uint32_t)depth.resolution, dp.sharpness = (uint32_t)depth.sharpness, dp.max_distance = depth.max_distance;
+        std::vector<float> coeff(np * 9 * 4), moments(np * (size_t)depth.resolution * depth.resolution * 4), states(classify.on ? 4 * np : 0);
+        for (int l = 0; l < levels; ++l) {
+            const srt_probe_grid& g = cascade.grid[l];
+            r.setProbeGrid(g);
+            srt_probe_grid_positions(&g, pos.data());
+            if (classify.on) {  // the states first: the probes are traced where the classification puts them
+                r.classifyProbes(dir.data(), (size_t)directions, cp);
+                r.readProbeStatesOutput(SRT_PROBE_STATE_RECORDS, states.data());
+                r.readProbeStatesOutput(SRT_PROBE_STATE_POSITIONS, pos.data());
+            }
+            r.traceLightProbes(pos.data(), np, dir.data(), (size_t)directions, lp);
+            r.readLightProbeOutput(SRT_LIGHT_PROBE_COEFFICIENTS, coeff.data());
+            if (depth.resolution) {
+                r.traceProbeDepth(pos.data(), np, dir.data(), (size_t)directions, dp);
+                r.readProbeDepthOutput(SRT_PROBE_DEPTH_MOMENTS, moments.data());
+            }
+            r.writeProbeGridInputs(coeff.data(), depth.resolution ? moments.data() : nullptr, classify.on ? states.data() : nullptr, np, (uint32_t)depth.resolution);
+            r.captureProbeCascadeLevel((uint32_t)l, SRT_PROBE_CASCADE_COEFFICIENTS | (depth.resolution ? SRT_PROBE_CASCADE_MOMENTS : 0u) |
+                                                        (classify.on ? SRT_PROBE_CASCADE_RECORDS : 0u));
+            std::fprintf(stderr, "probe cascade level %d: origin %g %g %g, spacing %g %g %g\n", l, (double)g.origin[0], (double)g.origin[1], (double)g.origin[2],
+                         (double)g.spacing[0], (double)g.spacing[1], (double)g.spacing[2]);
+        }
+        srt_probe_cascade_params sp{};
+        srt_probe_cascade_params_default(&sp);
+        sp.row_begin = 0, sp.row_end = H;
+        sp.flags = ((grid_flags & SRT_PROBE_GRID_NORMAL_WEIGHT) ? SRT_PROBE_CASCADE_NORMAL_WEIGHT : 0u) | ((grid_flags & SRT_PROBE_GRID_ALBEDO) ? SRT_PROBE_CASCADE_ALBEDO : 0u) |
+                   (depth.resolution ? SRT_PROBE_CASCADE_DEPTH : 0u) | (classify.on ? SRT_PROBE_CASCADE_STATES : 0u) | SRT_PROBE_CASCADE_COUNT_WORK;
+        sp.bias = depth.bias;
+        if (hemisphere) sp.band_weight[0] = 1.0f, sp.band_weight[1] = 0.5f, sp.band_weight[2] = 0.0f;
+        r.shadeProbeCascade(sp);
+        std::vector<float> img((size_t)W * H * 4);
+        r.readProbeGridOutput(img.data());
+        if (!write_floats(out, img)) return 1;
+        const srt_probe_cascade_work w = r.probeCascadeWork();
+        std::fprintf(stderr, "%dx%d: %d levels of %zu probes x %d directions, %d samples each, flags 0x%x%s: %llu hit pixels, %llu blended, first level %llu %llu %llu %llu: %s\n",
+                     W, H, levels, np, directions, samples, sp.flags, hemisphere ? " (hemisphere band weights)" : "", (unsigned long long)w.pixels,
+                     (unsigned long long)w.blended, (unsigned long long)w.first_level[0], (unsigned long long)w.first_level[1], (unsigned long long)w.first_level[2],
+                     (unsigned long long)w.first_level[3], out.c_str());
+        return 0;
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+}
+
 static void usage() {
     std::fprintf(stderr,
                  "usage: srt_render --scene FILE [--width 1280] [--height 720] [--spp 32] [--bounces 2]\n"
@@ -559,6 +641,7 @@ static void usage() {
                  "                  [--probe-depth R [--probe-depth-sharpness S] [--probe-depth-max D] [--probe-depth-bias B] [--probe-depth-out FILE]]\n"
                  "                  [--probe-classify [--probe-relocate] [--probe-clearance C] [--probe-max-offset F] [--probe-steps M] [--states-out FILE]]\n"
                  "                  [--probe-update FRAMES [--probe-hysteresis H] [--probe-samples N]]\n"
+                 "                  [--probe-cascade L [--probe-cascade-blend B]]\n"
                  "                  [--probe-tail [--probe-feedback F [--probe-scroll SX,SY,SZ [--probe-scroll-after ROUND]]] [--probe-bounces B] [--probe-tail-frame [--spp N] [--out frame.ppm]]]\n"
                  "       srt_render --scene FILE --adaptive ROUNDS [--adaptive-threshold T] [--adaptive-max M] [--counts-out FILE] [--spp N] ...\n"
                  "  --devices: one frame over several GPUs of this node in one process (equal row bands, one gather;\n"
@@ -659,6 +742,11 @@ static void usage() {
                  "             --probe-bounces B bounces, default --bounces, with the tail reading the coefficient history, then\n"
                  "             srt_blend_probes); round 1 runs with the mode off; the frame is shaded from the history;\n"
                  "             --probe-tail-depth needs --probe-depth R, --probe-tail-states needs --probe-classify; not with --probe-update\n"
+                 "  --probe-cascade L: with --probe-grid ...: shade from L = 1..4 nested grids around the camera position (srt_shade_probe_cascade):\n"
+                 "             level l has the grid's counts and its spacing times 2^l (srt_probe_cascade_grids; the grid's origin is not read);\n"
+                 "             each level is traced as --probe-grid traces its grid (--probe-depth, --probe-classify apply to every level) and\n"
+                 "             a pixel takes the finest level that holds its first hit, blended into the next across a border band of\n"
+                 "             --probe-cascade-blend B cells (default 1).  Not with --probe-visibility, --probe-update or --probe-tail\n"
                  "  --probe-scroll SX,SY,SZ: with --probe-grid ... --probe-feedback F: after the blend of round --probe-scroll-after ROUND (1..F,\n"
                  "             default 1) the grid moves by SX, SY, SZ whole cells (srt_scroll_probes: the coefficient history of the probes\n"
                  "             that stay inside the grid is kept, the others restart; the origin follows), and the rounds go on; the frame is\n"
@@ -683,6 +771,9 @@ int main(int argc, char** argv) {
     bool probe_classify_option = false;
     ProbeUpdateOptions probe_update;
     ProbeTailOptions probe_tail;
+    int probe_cascade_levels = 0;  // 0: no --probe-cascade
+    float probe_cascade_blend = 1.0f;
+    bool probe_cascade_given = false;
     bool probe_feedback_given = false, probe_bounces_given = false, probe_scroll_given = false, probe_scroll_ok = true;
     bool probe_update_given = false, probe_update_option = false;
     int adaptive = 0, adaptive_max = 0;
@@ -777,6 +868,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--probe-tail-grid")) probe_tail.grid = need("--probe-tail-grid");
         else if (!std::strcmp(argv[i], "--probe-tail-coefficients")) probe_tail.coefficients = need("--probe-tail-coefficients");
         else if (!std::strcmp(argv[i], "--probe-feedback")) probe_tail.feedback = std::atoi(need("--probe-feedback")), probe_feedback_given = true;
+        else if (!std::strcmp(argv[i], "--probe-cascade")) probe_cascade_levels = std::atoi(need("--probe-cascade")), probe_cascade_given = true;
+        else if (!std::strcmp(argv[i], "--probe-cascade-blend")) probe_cascade_blend = std::strtof(need("--probe-cascade-blend"), nullptr), probe_cascade_given = true;
         else if (!std::strcmp(argv[i], "--probe-scroll")) {
             int n = 0;
             probe_scroll_given = probe_tail.scroll_on = true;
@@ -908,6 +1001,13 @@ int main(int argc, char** argv) {
         probe_tail.frame_spp = spp, probe_tail.frame_out = out;
     }
     srt_probe_grid tail_grid{};
+    if (probe_cascade_given && (probe_grid_arg.empty() || probe_cascade_levels < 1 || probe_cascade_levels > SRT_PROBE_CASCADE_MAX_LEVELS ||
+                                !(probe_cascade_blend > 0.0f) || !std::isfinite(probe_cascade_blend) || probe_visibility || probe_update_given || probe_tail.on ||
+                                !object_moves.empty() || !probe_depth.out.empty() || !probe_classify.out.empty())) {
+        std::fprintf(stderr, "--probe-cascade L (1..4) [--probe-cascade-blend B, finite and > 0] goes with --probe-grid, not with --probe-visibility, --probe-update, "
+                             "--probe-tail, --move-object, --probe-depth-out or --states-out\n");
+        return 2;
+    }
     if (probe_scroll_given && (probe_grid_arg.empty() || !probe_feedback_given || !probe_tail.scroll_on || !probe_scroll_ok || probe_tail.scroll_after < 1 ||
                                probe_tail.scroll_after > probe_tail.feedback)) {
         std::fprintf(stderr, "--probe-scroll SX,SY,SZ (three integers) goes with --probe-grid ... --probe-feedback F, and --probe-scroll-after takes a round in 1..F\n");
@@ -1076,6 +1176,11 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--move-object: the scene has no object %zu\n", m.index);
             return 2;
         }
+    if (!probe_grid_arg.empty() && probe_cascade_levels)
+        return shade_probe_cascade_file(scene, device, W, H, fov, probe_grid, probe_cascade_levels, probe_cascade_blend, probe_grid_directions,
+                                        radiance_given ? radiance : 16, bounces, seed,
+                                        (probe_normal_weight ? SRT_PROBE_GRID_NORMAL_WEIGHT : 0u) | (probe_albedo ? SRT_PROBE_GRID_ALBEDO : 0u), probe_hemisphere,
+                                        irradiance_out, probe_depth, probe_classify);
     if (!probe_grid_arg.empty())
         return shade_probe_grid_file(scene, device, W, H, fov, probe_grid, probe_grid_directions, radiance_given ? radiance : 16, bounces, seed,
                                      (probe_visibility ? SRT_PROBE_GRID_VISIBILITY : 0u) | (probe_normal_weight ? SRT_PROBE_GRID_NORMAL_WEIGHT : 0u) |
