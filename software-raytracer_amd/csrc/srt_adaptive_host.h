@@ -36,8 +36,7 @@ struct BudgetCall {
 
 // what the last successful calls left behind
 struct AdaptiveState {
-    bool rendered = false;  // there has been an srt_render_adaptive
-    bool counted = false;   // ... and the last one had SRT_ADAPTIVE_COUNT_WORK
+    CallRecord call;        // the last srt_render_adaptive[_tail]; counted: it had SRT_ADAPTIVE_COUNT_WORK
     bool budgeted = false;  // there has been an srt_sample_budget (srt_get_budget_total)
 };
 
@@ -110,9 +109,7 @@ inline uint32_t budget_value(float g, float l, uint32_t n, const BudgetCall& c) 
     return b < 1u ? 1u : b;
 }
 
-inline void adaptive_rendered(AdaptiveState& s, uint32_t flags) { s.rendered = true, s.counted = (flags & ADAPTIVE_FLAG_COUNT_WORK) != 0; }
-// srt_get_adaptive_work: only the record of a last adaptive render that counted
-inline RaysStatus adaptive_check_work(const AdaptiveState& s) { return s.rendered && s.counted ? RAYS_OK : RAYS_STATE; }
+inline void adaptive_rendered(AdaptiveState& s, uint32_t flags) { s.call.done((flags & ADAPTIVE_FLAG_COUNT_WORK) != 0); }
 inline RaysStatus budget_check_total(const AdaptiveState& s) { return s.budgeted ? RAYS_OK : RAYS_STATE; }
 
 // The grid: persistent workgroups of `waves` waves that draw the band's 8 x 8 tiles from a ticket, at most `resident`.

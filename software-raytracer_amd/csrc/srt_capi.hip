@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <exception>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "srt_kernel.hip.h"
@@ -169,6 +170,11 @@ class Buffer : NoCopy {
 template <class T> using DeviceBuffer = Buffer<T>;
 template <class T> using PinnedBuffer = Buffer<T, true>;
 
+// The work record of a counting launch: N counters the kernel adds to (the pass's *_WORK_N, in its enum's order), never an output
+// buffer.  The count is part of the type, so zero_work and read_work cannot be given another pass's.
+template <int N>
+struct WorkBuffer : DeviceBuffer<unsigned long long> {};
+
 // An event or stream, created into h.
 template <class H, hipError_t (*DESTROY)(H)>
 struct Handle : NoCopy {
@@ -292,7 +298,10 @@ struct srt_context {
 
     // Every output a caller can bind or read back is an own buffer (allocated on first use) and an srt::OutputSlot
     // (srt_outputs_host.h): the caller's bound buffer (srt_bind_*; NULL = own) and the record of what has been written.  DESIGN.md
-    // §4.21 lists them with the rule each srt_read_* applies.
+    // §4.21 lists them with the rule each srt_read_* applies.  The ray and probe passes below keep, in their state, the shared
+    // records of the same header: a CallRecord (has the pass run, did its last call count work), a LastOutputs (which outputs that
+    // call wrote, and where) and InputArrays (which input array is current); a counting launch adds to a WorkBuffer<*_WORK_N>,
+    // zeroed on the stream in front of it and never an output buffer.
 
     // first-hit buffers (srt_render_gbuffer), one per SRT_GBUF_* bit
     DeviceBuffer<void> d_gbuf_own[4];
@@ -377,30 +386,29 @@ struct srt_context {
 
     // ray queries (srt_trace_rays): the handle's own ray arrays (srt_write_rays; they grow on demand) and output buffers, one
     // per output bit (grown when a batch needs more) with its slot (the bound buffer only), and the host-side state
-    // (srt_rays_host.h): which arrays are the current rays and what the last trace wrote
+    // (srt_rays_host.h): which arrays are the current rays (d_ray_origin is the own array of rays.origins) and what the last
+    // trace wrote (rays.last)
     DeviceBuffer<float4> d_ray_origin;
     DeviceBuffer<float4> d_ray_direction;
     DeviceBuffer<void> d_rayout_own[srt::RAYS_SLOTS];
     srt::OutputSlot rayout[srt::RAYS_SLOTS];
     srt::RaysState rays;
-    // any-hit queries (srt_trace_occlusion): whether the last one counted its work, and the record its kernel adds to
-    // (srt::OCC_WORK_N words, zeroed on the stream in front of a counting launch; never an output buffer)
-    srt::OcclusionState occlusion;
-    DeviceBuffer<unsigned long long> d_occlusion_work;
+    // any-hit queries (srt_trace_occlusion): the call record (whether the last one counted its work), and the record its kernel
+    // adds to
+    srt::CallRecord occlusion;
+    WorkBuffer<srt::OCC_WORK_N> d_occlusion_work;
     // per-pixel visibility (srt_render_visibility), one own buffer of W*H floats per SRT_VIS_* bit with its slot (the bound
     // buffer only); what the last call wrote and whether it counted (srt_visibility_host.h); the record a counting launch adds to
-    // (srt::VIS_WORK_N words, zeroed on the stream in front of it; never an output buffer)
     DeviceBuffer<void> d_vis_own[srt::VIS_SLOTS];
     srt::OutputSlot vis[srt::VIS_SLOTS];
     srt::VisibilityState visibility;
-    DeviceBuffer<unsigned long long> d_visibility_work;
-    // reflection guides (srt_render_reflection_gbuffer): one own buffer of W*H elements per SRT_REFL_* bit with its slot, whether
-    // the last call counted (srt_reflection_host.h), and the record a counting launch adds to (srt::REFL_WORK_N words, zeroed on
-    // the stream in front of it; never an output buffer)
+    WorkBuffer<srt::VIS_WORK_N> d_visibility_work;
+    // reflection guides (srt_render_reflection_gbuffer): one own buffer of W*H elements per SRT_REFL_* bit with its slot, the call
+    // record (whether the last call counted), and the record a counting launch adds to
     DeviceBuffer<void> d_refl_own[srt::REFL_SLOTS];
     srt::ReflectionSlots refl;
-    srt::ReflectionState reflection;
-    DeviceBuffer<unsigned long long> d_reflection_work;
+    srt::CallRecord reflection;
+    WorkBuffer<srt::REFL_WORK_N> d_reflection_work;
     // the camera each own reflection slot was last rendered with, as gbuf_own_cam (srt_temporal_accumulate with the mirror history
     // on refuses own reflection outputs of another camera), and the mirror history's setting (srt_mirror_history_host.h)
     srt_camera refl_own_cam[srt::REFL_SLOTS] = {};
@@ -408,49 +416,49 @@ struct srt_context {
     srt::MirrorHistoryState mirror;
     // radiance queries (srt_trace_radiance): the own output buffer of N float4 (grown when a batch needs more) with its slot (the
     // bound buffer only); what the last trace wrote and whether it counted (srt_radiance_host.h); the sample scratch of the
-    // launch's grid (grown when a launch has more workgroups); the record a counting launch adds to (srt::RAD_WORK_N words)
+    // launch's grid (grown when a launch has more workgroups); the record a counting launch adds to
     DeviceBuffer<float4> d_radiance_own;
     srt::OutputSlot radiance_out;
     srt::RadianceState radiance;
     DeviceBuffer<float4> d_radiance_rows;
-    DeviceBuffer<unsigned long long> d_radiance_work;
+    WorkBuffer<srt::RAD_WORK_N> d_radiance_work;
     // light probes (srt_trace_light_probes): the own position and direction arrays (srt_write_light_probes,
     // srt_write_light_probe_directions; they grow on demand); one own output buffer per SRT_LIGHT_PROBE_* output bit (grown when
     // a call needs more) with its slot (the bound buffer only); which arrays are current, what the last trace wrote and whether
     // it counted (srt_light_probes_host.h); the block sums of a projection over more than one block of 64 directions; the record
-    // a counting launch adds to (srt::LP_WORK_N words).  The sample scratch is the radiance pass's, d_radiance_rows.
+    // a counting launch adds to.  The sample scratch is the radiance pass's, d_radiance_rows.
     DeviceBuffer<float4> d_probe_position;
     DeviceBuffer<float4> d_probe_direction;
     DeviceBuffer<float4> d_probe_out_own[srt::LIGHT_PROBE_SLOTS];
     srt::OutputSlot probe_out[srt::LIGHT_PROBE_SLOTS];
     srt::LightProbeState probes;
     DeviceBuffer<float4> d_probe_partial;
-    DeviceBuffer<unsigned long long> d_probe_work;
+    WorkBuffer<srt::LP_WORK_N> d_probe_work;
     // probe-grid shading (srt_shade_probe_grid): the grid, which coefficient array is current and whether the last call counted
     // (srt_probe_grid_host.h); the own coefficient array (srt_write_probe_grid_coefficients; it grows on demand); the own output
-    // buffer of W*H float4 with its slot; the record a counting launch adds to (srt::PG_WORK_N words)
+    // buffer of W*H float4 with its slot; the record a counting launch adds to
     srt::ProbeGridState probe_grid;
     DeviceBuffer<float4> d_probe_grid_coefficients;
     DeviceBuffer<float4> d_probe_grid_own;
     srt::OutputSlot probe_grid_out;
-    DeviceBuffer<unsigned long long> d_probe_grid_work;
+    WorkBuffer<srt::PG_WORK_N> d_probe_grid_work;
     // probe depth moments (srt_trace_probe_depth): the three texel tables (uploaded once, on first use); one own output buffer per
     // SRT_PROBE_DEPTH_* output bit (grown when a call needs more) with its slot (the bound buffer only); what the last trace wrote
-    // and whether it counted (srt_probe_depth_host.h); the record a counting launch adds to (srt::PD_WORK_N words).  The filtered
+    // and whether it counted (srt_probe_depth_host.h); the record a counting launch adds to.  The filtered
     // shading (srt_shade_probe_grid_depth): which moment array is current, and the own one (srt_write_probe_grid_depth).
     DeviceBuffer<float4> d_probe_depth_texels;
     bool probe_depth_texels_ready = false;
     DeviceBuffer<void> d_probe_depth_own[srt::PROBE_DEPTH_SLOTS];
     srt::OutputSlot probe_depth_out[srt::PROBE_DEPTH_SLOTS];
     srt::ProbeDepthState probe_depth;
-    DeviceBuffer<unsigned long long> d_probe_depth_work;
+    WorkBuffer<srt::PD_WORK_N> d_probe_depth_work;
     srt::ProbeGridDepthState probe_grid_depth;
     DeviceBuffer<float4> d_probe_grid_depth;
     // probe classification and relocation (srt_classify_probes): the primitive table the kernel reads, built from the object list at
     // the first classification after the scene changed (scene_changes says when); one own output buffer per SRT_PROBE_STATE_* output
     // bit with its slot (the bound buffer only); what the last classification wrote, whether it counted and which state array
     // srt_shade_probe_grid_states reads (srt_probe_states_host.h); the own state array (srt_write_probe_grid_states); the record a
-    // counting launch adds to (srt::PS_WORK_N words).
+    // counting launch adds to.
     srt::ProbeTable probe_table;
     DeviceBuffer<float4> d_probe_table;
     bool probe_table_ready = false;
@@ -459,37 +467,37 @@ struct srt_context {
     srt::OutputSlot probe_states_out[srt::PROBE_STATE_SLOTS];
     srt::ProbeStatesState probe_states;
     DeviceBuffer<float4> d_probe_grid_states;
-    DeviceBuffer<unsigned long long> d_probe_classify_work;
+    WorkBuffer<srt::PS_WORK_N> d_probe_classify_work;
     // per-frame probe updates (srt_list_probes, the listed traces, srt_blend_probes): the rules' state (srt_probe_update_host.h:
     // what the last listing wrote, which list is bound for tracing, the previous records, which P and R the histories stand for);
     // the own list output, the own list input (srt_write_probe_list), the own previous records, the two own histories; the records
-    // the counting launches add to (srt::PL_WORK_N, srt::PB_WORK_N words).
+    // the counting launches of the listing and of the blend add to.
     srt::ProbeUpdateState probe_update;
     DeviceBuffer<uint32_t> d_probe_list_out;
     DeviceBuffer<uint32_t> d_probe_list;
     DeviceBuffer<float4> d_probe_previous_states;
     DeviceBuffer<float4> d_probe_history[srt::PROBE_HISTORY_SLOTS];
-    DeviceBuffer<unsigned long long> d_probe_list_work;
-    DeviceBuffer<unsigned long long> d_probe_blend_work;
-    // scrolling (srt_scroll_probes): whether the last call counted (srt_probe_scroll_host.h); one spare per history, the buffer a
-    // scroll writes (an own history swaps with it, a bound one is copied back from it); the record a counting launch adds to
-    // (srt::PSC_WORK_N words).  The scrolled records go to d_probe_previous_states.
-    srt::ProbeScrollState probe_scroll;
+    WorkBuffer<srt::PL_WORK_N> d_probe_list_work;
+    WorkBuffer<srt::PB_WORK_N> d_probe_blend_work;
+    // scrolling (srt_scroll_probes): the call record (whether the last call counted); one spare per history, the buffer a
+    // scroll writes (an own history swaps with it, a bound one is copied back from it); the record a counting launch adds to.
+    // The scrolled records go to d_probe_previous_states.
+    srt::CallRecord probe_scroll;
     DeviceBuffer<float4> d_probe_history_spare[srt::PROBE_HISTORY_SLOTS];
-    DeviceBuffer<unsigned long long> d_probe_scroll_work;
+    WorkBuffer<srt::PSC_WORK_N> d_probe_scroll_work;
     // the probe cascade (srt_shade_probe_cascade): the cascade, which array of each level is current and whether the last call
     // counted (srt_probe_cascade_host.h); the own arrays per level (coefficients, moments, records; they grow on demand); the record
-    // a counting launch adds to (srt::PC_WORK_N words).  The output is the probe-grid slot's.
+    // a counting launch adds to.  The output is the probe-grid slot's.
     srt::ProbeCascadeState probe_cascade;
     DeviceBuffer<float4> d_probe_cascade[srt::PROBE_CASCADE_MAX_LEVELS][srt::PROBE_CASCADE_ARRAYS];
-    DeviceBuffer<unsigned long long> d_probe_cascade_work;
+    WorkBuffer<srt::PC_WORK_N> d_probe_cascade_work;
     // the probe tail (srt_probe_tail): the mode's setting and whether the last affected trace ran under it and counted
-    // (srt_probe_tail_host.h); the record a counting launch adds to (srt::PT_WORK_N words)
+    // (srt_probe_tail_host.h); the record a counting launch adds to
     srt::ProbeTailState probe_tail;
-    DeviceBuffer<unsigned long long> d_probe_tail_work;
+    WorkBuffer<srt::PT_WORK_N> d_probe_tail_work;
     // adaptive sampling (srt_render_adaptive, srt_sample_budget): the per-pixel sample counts and sample budget, W*H uint32 each,
     // own buffer and slot; whether the last adaptive render counted and whether a budget pass has run (srt_adaptive_host.h); the
-    // tile ticket of a launch (zeroed on the stream in front of it); the record a counting launch adds to (srt::ADP_WORK_N words);
+    // tile ticket of a launch (zeroed on the stream in front of it); the record a counting launch adds to;
     // the budget pass's total (one word).  The sample scratch is the radiance pass's, d_radiance_rows: one stream runs both.
     DeviceBuffer<uint32_t> d_counts_own;
     srt::OutputSlot counts;
@@ -497,8 +505,8 @@ struct srt_context {
     srt::OutputSlot budget;
     srt::AdaptiveState adaptive;
     DeviceBuffer<uint32_t> d_adaptive_ticket;
-    DeviceBuffer<unsigned long long> d_adaptive_work;
-    DeviceBuffer<unsigned long long> d_budget_total;
+    WorkBuffer<srt::ADP_WORK_N> d_adaptive_work;
+    WorkBuffer<1> d_budget_total;
 
     char error[512] = "";
 };
@@ -551,26 +559,19 @@ T* current(const srt::OutputSlot& s, const DeviceBuffer<T>& own) {
     } while (0)
 #define SRT_WRITE_TARGET(ctx, slot, own, nbytes, dst) SRT_WRITE_TARGET_AFTER(ctx, slot, own, nbytes, dst, SRT_OK)
 
-// ... in front of the re-allocation of own ray output `i` (srt_trace_rays, srt_trace_occlusion): earlier traces may still be
-// writing it, so the stream is finished, and the last trace's copy of the output goes with it
-int ray_output_released(srt_context* ctx, int i) {
+// ... in front of the re-allocation of the own buffer, at `own`, of output `i` of a ray, radiance or probe call: earlier calls
+// may still be writing it, so the stream is finished, and the last call's copy of the output goes with it
+template <int N>
+int output_released(srt_context* ctx, srt::LastOutputs<N>& last, int i, const void* own) {
     if (const int rc = finish_stream(ctx)) return rc;
-    srt::rays_output_released(ctx->rays, i, (void*)ctx->d_rayout_own[i]);
-    return SRT_OK;
-}
-
-// ... of own output `i` of a light-probe, probe-depth or probe-state call: `rule` is the state's *_output_released
-template <class S>
-int probe_output_released(srt_context* ctx, void (*rule)(S&, int, const void*), S& state, int i, const void* own) {
-    if (const int rc = finish_stream(ctx)) return rc;
-    rule(state, i, own);
+    last.released(i, own);
     return SRT_OK;
 }
 
 // Every srt_write_* of a probe input, its range checked by the caller: `count` elements of `elem_bytes` into the own array, which
 // becomes the current one (a state that keeps more than the count does so after this returns SRT_OK)
 template <class T>
-int write_probe_input(srt_context* ctx, srt::LightProbeInput& in, DeviceBuffer<T>& own, const void* src, size_t count, size_t elem_bytes) {
+int write_probe_input(srt_context* ctx, srt::InputArray& in, DeviceBuffer<T>& own, const void* src, size_t count, size_t elem_bytes) {
     if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it may be re-allocated below)
     const size_t bytes = count * elem_bytes;
     if (own.bytes() < bytes) {
@@ -578,7 +579,7 @@ int write_probe_input(srt_context* ctx, srt::LightProbeInput& in, DeviceBuffer<T
         SRT_HIP(ctx, own.ensure(bytes));
     }
     SRT_HIP(ctx, hipMemcpy(own, src, bytes, hipMemcpyHostToDevice));
-    srt::light_probe_written(in, count);
+    srt::input_written(in, count);
     return SRT_OK;
 }
 
@@ -590,22 +591,55 @@ int read_slot(srt_context* ctx, const void* src, void* dst, size_t bytes, const 
     return SRT_OK;
 }
 
-// The work record of a counting launch (srt_trace_occlusion, srt_render_visibility): `words` counters, zeroed on the stream in
-// front of the launch, and read back once the stream has finished.
-int zero_work(srt_context* ctx, DeviceBuffer<unsigned long long>& d, size_t words) {
-    if (!d) SRT_HIP(ctx, d.ensure(words * sizeof(unsigned long long)));
-    SRT_HIP(ctx, hipMemsetAsync(d, 0, words * sizeof(unsigned long long), ctx->stream));
+// srt_bind_*_output of a pass with several outputs: `slot` is the pass's slot of `output`, -1 when it is not a single output bit
+// (refused with `not_a_bit`, which prints `output`).  No synchronisation: enqueued launches keep the buffer they were given.
+int bind_output(srt_context* ctx, srt::OutputSlot* slots, int slot, void* d_ptr, const char* not_a_bit, uint32_t output) {
+    if (slot < 0) return fail(ctx, SRT_ERR_INVALID_ARG, not_a_bit, output);
+    return slots[slot].bind(d_ptr), SRT_OK;
+}
+
+// The matching srt_read_*_output: `bytes` of what the last call wrote as `output`, or `not_written`.
+template <int N>
+int read_output(srt_context* ctx, const srt::LastOutputs<N>& last, uint32_t output, int slot, void* dst, size_t bytes, const char* not_a_bit,
+                const char* not_written) {
+    if (slot < 0) return fail(ctx, SRT_ERR_INVALID_ARG, not_a_bit, output);
+    return read_slot(ctx, last.read(output, slot), dst, bytes, not_written, output);
+}
+
+// The work record of a counting launch: zeroed on the stream in front of the launch, and read back once the stream has finished.
+template <int N>
+int zero_work(srt_context* ctx, WorkBuffer<N>& d) {
+    if (!d) SRT_HIP(ctx, d.ensure(N * sizeof(unsigned long long)));
+    SRT_HIP(ctx, hipMemsetAsync(d, 0, N * sizeof(unsigned long long), ctx->stream));
     return SRT_OK;
 }
-int read_work(srt_context* ctx, const DeviceBuffer<unsigned long long>& d, unsigned long long* w, size_t words) {
+template <int N>
+int read_work(srt_context* ctx, const WorkBuffer<N>& d, unsigned long long* w) {
     if (const int rc = finish_stream(ctx)) return rc;
-    SRT_HIP(ctx, hipMemcpy(w, d, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    SRT_HIP(ctx, hipMemcpy(w, d, N * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
 
+// Every srt_get_*_work whose public struct is {uint32 valid, reserved; uint64 counters[N]} in the order of the pass's *_WORK_*
+// enum (SRT_WORK_LAYOUT in front of each use asserts it): only the record of a last call that counted, else `why`.
+template <class Work, int N>
+int get_work(srt_context* ctx, const srt::CallRecord& call, const WorkBuffer<N>& d, Work* out, const char* why) {
+    static_assert(sizeof(Work) == 8 + 8 * N && sizeof(unsigned long long) == sizeof(uint64_t), "the work struct is not two words and N counters");
+    if (call.work() != srt::RAYS_OK) return fail(ctx, SRT_ERR_STATE, "%s", why);
+    unsigned long long w[N];
+    if (const int rc = read_work(ctx, d, w)) return rc;
+    out->valid = 1, out->reserved = 0;
+    memcpy((char*)out + 8, w, sizeof w);
+    return SRT_OK;
+}
+#define SRT_WORK_LAYOUT(Work, N, first, FIRST, last, LAST)                                                                               \
+    static_assert(sizeof(Work) == 8 + 8 * (N) && offsetof(Work, first) == 8 + 8 * (FIRST) && offsetof(Work, last) == 8 + 8 * (LAST) && \
+                      (LAST) == (N)-1,                                                                                                   \
+                  #Work " does not list the counters of its enum in the enum's order")
+
 // the array a call reads an input from: the caller's bound one, else the handle's own
 template <class T>
-const T* current(const srt::LightProbeInput& in, const DeviceBuffer<T>& own) {
+const T* current(const srt::InputArray& in, const DeviceBuffer<T>& own) {
     return in.bound ? (const T*)in.bound : (const T*)own;
 }
 
@@ -1195,18 +1229,19 @@ static int launch_rays(srt_context* ctx, void (*kernel)(srt::KernelParams, IO), 
     return launch_persistent(ctx, kernel, srt::rays_grid(n, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes)), ks, K, io);
 }
 
-// The instantiation of a persistent kernel for a scene image in LDS or in memory, with or without meshes, and (the counting
-// passes) with or without the work record.
-#define SRT_KERNEL_LDS_MESH(kernel, in_lds, mesh) \
-    ((in_lds) ? ((mesh) ? kernel<true, true> : kernel<true, false>) : ((mesh) ? kernel<false, true> : kernel<false, false>))
-#define SRT_KERNEL_LDS_MESH_COUNT(kernel, in_lds, mesh, count)                                                                                  \
-    (!(count) ? ((in_lds) ? ((mesh) ? kernel<true, true, false> : kernel<true, false, false>) : ((mesh) ? kernel<false, true, false> : kernel<false, false, false>)) \
-              : ((in_lds) ? ((mesh) ? kernel<true, true, true> : kernel<true, false, true>) : ((mesh) ? kernel<false, true, true> : kernel<false, false, true>)))
-// ... the listed instantiations of the two probe tracing kernels
-#define SRT_KERNEL_LDS_MESH_COUNT_LISTED(kernel, in_lds, mesh, count)                                                                                             \
-    (!(count) ? ((in_lds) ? ((mesh) ? kernel<true, true, false, true> : kernel<true, false, false, true>)                                                        \
-                          : ((mesh) ? kernel<false, true, false, true> : kernel<false, false, false, true>))                                                     \
-              : ((in_lds) ? ((mesh) ? kernel<true, true, true, true> : kernel<true, false, true, true>) : ((mesh) ? kernel<false, true, true, true> : kernel<false, false, true, true>)))
+// SRT_KERNEL(kernel, b0, b1, ...): the instantiation kernel<b0, b1, ...> of a kernel template whose parameters are all bools, for
+// run-time values — the scene image in LDS or in memory, with or without meshes, with or without the work record, and so on.
+// Every combination is instantiated.  pick_flags turns one bool after the other into std::true_type / std::false_type.
+template <class F>
+static auto pick_flags(F f) {
+    return f();
+}
+template <class F, class... Bools>
+static auto pick_flags(F f, bool b, Bools... rest) {
+    return b ? pick_flags([f](auto... t) { return f(std::true_type{}, t...); }, rest...)
+             : pick_flags([f](auto... t) { return f(std::false_type{}, t...); }, rest...);
+}
+#define SRT_KERNEL(kernel, ...) pick_flags([](auto... flag) { return &kernel<decltype(flag)::value...>; }, __VA_ARGS__)
 
 // What a block costs, from its counts: the weights are wave instructions per trip of the loop counted (a pool step costs its fixed
 // part plus the uniform-sphere groups, cluster bounds and boxes every step runs through), fitted on measured band times of
@@ -1481,7 +1516,7 @@ static int plan_cost_order(srt_context* ctx, const srt_render_params* p, srt::Ke
     if (dev_switches().host_order && (ctx->estimate_stale || ctx->order_gx != grid.x || ctx->order_gy != grid.y)) {
         const size_t image_bytes = (size_t)(K.scene_vec4 > 0 ? K.scene_vec4 : 1) * sizeof(float4);
         const size_t est_lds = (ctx->pick_in_lds[ks.img] ? image_bytes : 0) + srt::WAVE_SCRATCH_BYTES + srt::MESH_WAVE_BYTES;
-        void (*const estimate)(srt::KernelParams, uint32_t*, int, int) = ctx->pick_in_lds[ks.img] ? srt::block_cost_kernel<true> : srt::block_cost_kernel<false>;
+        void (*const estimate)(srt::KernelParams, uint32_t*, int, int) = SRT_KERNEL(srt::block_cost_kernel, ctx->pick_in_lds[ks.img]);
         hipLaunchKernelGGL(estimate, dim3((unsigned)((nwg + 3) / 4)), dim3(64), est_lds, ctx->stream, K, ctx->d_wg_est, (int)grid.x, (int)nwg);
         hipLaunchKernelGGL(srt::smooth_cost_kernel, dim3((unsigned)((nwg + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_wg_est, ctx->d_wg_est + nwg, (int)nwg, (int)grid.x);
         hipLaunchKernelGGL(srt::order_sort_kernel, dim3(1), dim3(srt::ORDER_SORT_THREADS), 0, ctx->stream, ctx->d_wg_est + nwg, ctx->d_wg_order, (int)nwg);
@@ -1729,7 +1764,7 @@ int srt_pick(srt_context* ctx, int x, int y, int* object_index) {
     // one wave: image (if it fits) + one wave's scratch + one wave's mesh queues
     const size_t image_bytes = (size_t)(K.scene_vec4 > 0 ? K.scene_vec4 : 1) * sizeof(float4);
     const bool in_lds = ctx->pick_in_lds[img];
-    hipLaunchKernelGGL(in_lds ? srt::pick_kernel<true> : srt::pick_kernel<false>, dim3(1), dim3(64),
+    hipLaunchKernelGGL(SRT_KERNEL(srt::pick_kernel, in_lds), dim3(1), dim3(64),
                        (in_lds ? image_bytes : 0) + srt::WAVE_SCRATCH_BYTES + srt::MESH_WAVE_BYTES, ctx->stream, K, x, y, d_out);
     SRT_HIP(ctx, hipGetLastError());
     int idx[4] = {-1, 0, 0, 0};
@@ -1793,14 +1828,12 @@ int srt_render_gbuffer(srt_context* ctx, const srt_gbuffer_params* g) {
     srt::KernelParams K;
     const KernelSetup ks = scene_kernel_params(ctx, g->row_begin, g->row_end, K);
     const srt::GBufferOut out{(int32_t*)dst[0], (float4*)dst[1], (float4*)dst[2], (float4*)dst[3]};
-    return launch_tiles(ctx, SRT_KERNEL_LDS_MESH(srt::gbuffer_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0), ks, K, out);
+    return launch_tiles(ctx, SRT_KERNEL(srt::gbuffer_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0), ks, K, out);
 }
 
 int srt_bind_gbuffer(srt_context* ctx, uint32_t output, void* d_ptr) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    const int i = gbuf_slot(output);
-    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_gbuffer: output 0x%x is not a single SRT_GBUF_* bit", output);
-    return ctx->gbuf[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_output)
+    return bind_output(ctx, ctx->gbuf, gbuf_slot(output), d_ptr, "srt_bind_gbuffer: output 0x%x is not a single SRT_GBUF_* bit", output);
 }
 
 int srt_read_gbuffer(srt_context* ctx, uint32_t output, void* dst) {
@@ -1830,7 +1863,7 @@ int srt_write_rays(srt_context* ctx, const float* origins, const float* directio
     if (const int rc = finish_stream(ctx)) return rc;  // (traces in flight read the own arrays; they may be re-allocated below)
     const size_t bytes = count * sizeof(float4);
     if (ctx->d_ray_origin.bytes() < bytes || ctx->d_ray_direction.bytes() < bytes) {
-        ctx->rays.own_count = 0;  // (a failed allocation leaves no own rays)
+        ctx->rays.origins.own_count = 0;  // (a failed allocation leaves no own rays)
         SRT_HIP(ctx, ctx->d_ray_origin.ensure(bytes));
         SRT_HIP(ctx, ctx->d_ray_direction.ensure(bytes));
     }
@@ -1850,9 +1883,7 @@ int srt_bind_rays(srt_context* ctx, const void* d_origins, const void* d_directi
 
 int srt_bind_ray_output(srt_context* ctx, uint32_t output, void* d_ptr) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    const int i = srt::rays_slot(output);
-    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_ray_output: output 0x%x is not a single SRT_GBUF_* / SRT_RAYS_OCCLUDED bit", output);
-    return ctx->rayout[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued traces keep the buffer they were given, as srt_bind_gbuffer)
+    return bind_output(ctx, ctx->rayout, srt::rays_slot(output), d_ptr, "srt_bind_ray_output: output 0x%x is not a single SRT_GBUF_* / SRT_RAYS_OCCLUDED bit", output);
 }
 
 int srt_trace_rays(srt_context* ctx, const srt_trace_params* t) {
@@ -1865,27 +1896,26 @@ int srt_trace_rays(srt_context* ctx, const srt_trace_params* t) {
     void* dst[srt::RAYS_SLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i < srt::RAYS_SLOTS; ++i)
         if (t->outputs & (1u << i))
-            SRT_WRITE_TARGET_AFTER(ctx, ctx->rayout[i], ctx->d_rayout_own[i], n * srt::rays_elem_bytes(i), dst[i], ray_output_released(ctx, i));
+            SRT_WRITE_TARGET_AFTER(ctx, ctx->rayout[i], ctx->d_rayout_own[i], n * srt::rays_elem_bytes(i), dst[i], output_released(ctx, ctx->rays.last, i, ctx->d_rayout_own[i]));
     srt::KernelParams K;
     const KernelSetup ks = scene_kernel_params(ctx, 0, ctx->height, K);
     srt::RaysIO io{};
-    io.origin = ctx->rays.bound() ? (const float4*)ctx->rays.bound_origin : (const float4*)ctx->d_ray_origin;
+    io.origin = current(ctx->rays.origins, ctx->d_ray_origin);
     io.direction = ctx->rays.bound() ? (const float4*)ctx->rays.bound_direction : (const float4*)ctx->d_ray_direction;
     io.count = (uint32_t)n;
     io.normalize = (t->flags & SRT_RAYS_NORMALIZE) ? 1u : 0u;
     io.object = (int32_t*)dst[0], io.normal_depth = (float4*)dst[1], io.position = (float4*)dst[2], io.albedo = (float4*)dst[3], io.occluded = (int32_t*)dst[4];
-    if (const int rc = launch_rays(ctx, SRT_KERNEL_LDS_MESH(srt::rays_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0), n, ks, K, io)) return rc;
+    if (const int rc = launch_rays(ctx, SRT_KERNEL(srt::rays_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0), n, ks, K, io)) return rc;
     srt::rays_traced(ctx->rays, t->outputs, dst);
     return SRT_OK;
 }
 
 int srt_read_ray_output(srt_context* ctx, uint32_t output, void* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
-    const void* src = nullptr;
-    size_t bytes = 0;
-    const srt::RaysStatus rs = srt::rays_check_read(ctx->rays, output, &src, &bytes);
-    if (rs == srt::RAYS_INVALID_ARG) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_ray_output: output 0x%x is not a single SRT_GBUF_* / SRT_RAYS_OCCLUDED bit", output);
-    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, bytes, "srt_read_ray_output: output 0x%x was not written by the last srt_trace_rays", output);
+    const int i = srt::rays_slot(output);
+    return read_output(ctx, ctx->rays.last, output, i, dst, ctx->rays.last_count * srt::rays_elem_bytes(i),
+                       "srt_read_ray_output: output 0x%x is not a single SRT_GBUF_* / SRT_RAYS_OCCLUDED bit",
+                       "srt_read_ray_output: output 0x%x was not written by the last srt_trace_rays");
 }
 
 // ---- any-hit queries -----------------------------------------------------------------------------------------------
@@ -1910,34 +1940,29 @@ int srt_trace_occlusion(srt_context* ctx, const srt_occlusion_params* t) {
     const int slot = srt::OCCLUSION_SLOT;
     const bool count = (t->flags & SRT_OCCLUSION_COUNT_WORK) != 0;
     void* dst = nullptr;
-    SRT_WRITE_TARGET_AFTER(ctx, ctx->rayout[slot], ctx->d_rayout_own[slot], n * sizeof(int32_t), dst, ray_output_released(ctx, slot));
+    SRT_WRITE_TARGET_AFTER(ctx, ctx->rayout[slot], ctx->d_rayout_own[slot], n * sizeof(int32_t), dst, output_released(ctx, ctx->rays.last, slot, ctx->d_rayout_own[slot]));
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_occlusion_work, srt::OCC_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_occlusion_work)) return rc;
     }
     srt::KernelParams K;
     const KernelSetup ks = scene_kernel_params(ctx, 0, ctx->height, K);
     srt::OcclusionIO io{};
-    io.origin = ctx->rays.bound() ? (const float4*)ctx->rays.bound_origin : (const float4*)ctx->d_ray_origin;
+    io.origin = current(ctx->rays.origins, ctx->d_ray_origin);
     io.direction = ctx->rays.bound() ? (const float4*)ctx->rays.bound_direction : (const float4*)ctx->d_ray_direction;
     io.count = (uint32_t)n;
     io.normalize = (t->flags & SRT_OCCLUSION_NORMALIZE) ? 1u : 0u;
     io.occluded = (int32_t*)dst;
     io.work = count ? (unsigned long long*)ctx->d_occlusion_work : nullptr;
-    if (const int rc = launch_rays(ctx, SRT_KERNEL_LDS_MESH_COUNT(srt::occlusion_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count), n, ks, K, io)) return rc;
+    if (const int rc = launch_rays(ctx, SRT_KERNEL(srt::occlusion_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count), n, ks, K, io)) return rc;
     srt::occlusion_traced(ctx->rays, ctx->occlusion, dst, t->flags);
     return SRT_OK;
 }
 
+SRT_WORK_LAYOUT(srt_occlusion_work, srt::OCC_WORK_N, rays, srt::OCC_WORK_RAYS, triangle_tests, srt::OCC_WORK_TRIANGLES);
 int srt_get_occlusion_work(srt_context* ctx, srt_occlusion_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::occlusion_check_work(ctx->occlusion) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_occlusion_work: the last srt_trace_occlusion did not ask for SRT_OCCLUSION_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::OCC_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_occlusion_work, w, srt::OCC_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->rays = w[srt::OCC_WORK_RAYS], out->occluded = w[srt::OCC_WORK_OCCLUDED];
-    out->analytic_tests = w[srt::OCC_WORK_ANALYTIC], out->node_visits = w[srt::OCC_WORK_NODES], out->triangle_tests = w[srt::OCC_WORK_TRIANGLES];
-    return SRT_OK;
+    return get_work(ctx, ctx->occlusion, ctx->d_occlusion_work, out,
+                    "srt_get_occlusion_work: the last srt_trace_occlusion did not ask for SRT_OCCLUSION_COUNT_WORK (or there has been none)");
 }
 
 // ---- per-pixel visibility ------------------------------------------------------------------------------------------
@@ -1972,7 +1997,7 @@ int srt_render_visibility(srt_context* ctx, const srt_visibility_params* v) {
         if (v->outputs & (1u << i))
             SRT_WRITE_TARGET(ctx, ctx->vis[i], ctx->d_vis_own[i], px * sizeof(float), dst[i]);
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_visibility_work, srt::VIS_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_visibility_work)) return rc;
     }
     srt::KernelParams K;
     const KernelSetup ks = scene_kernel_params(ctx, v->row_begin, v->row_end, K);
@@ -1985,37 +2010,28 @@ int srt_render_visibility(srt_context* ctx, const srt_visibility_params* v) {
     io.n = ao ? v->ao_samples : 1u, io.first_sample = ao ? v->first_sample : 1u, io.seed = ao ? v->seed : 0u;
     io.radius = ao ? v->ao_radius : INFINITY;
     io.work = count ? (unsigned long long*)ctx->d_visibility_work : nullptr;
-    if (const int rc = launch_tiles(ctx, SRT_KERNEL_LDS_MESH_COUNT(srt::visibility_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count), ks, K, io)) return rc;
+    if (const int rc = launch_tiles(ctx, SRT_KERNEL(srt::visibility_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count), ks, K, io)) return rc;
     srt::visibility_rendered(ctx->visibility, v->outputs, dst, v->flags);
     return SRT_OK;
 }
 
 int srt_bind_visibility(srt_context* ctx, uint32_t output, void* d_float) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    const int i = srt::visibility_slot(output);
-    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_visibility: output 0x%x is not a single SRT_VIS_* bit", output);
-    return ctx->vis[i].bind(d_float), SRT_OK;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_gbuffer)
+    return bind_output(ctx, ctx->vis, srt::visibility_slot(output), d_float, "srt_bind_visibility: output 0x%x is not a single SRT_VIS_* bit", output);
 }
 
 int srt_read_visibility(srt_context* ctx, uint32_t output, float* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
-    const void* src = nullptr;
-    const srt::RaysStatus rs = srt::visibility_check_read(ctx->visibility, output, &src);
-    if (rs == srt::RAYS_INVALID_ARG) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_visibility: output 0x%x is not a single SRT_VIS_* bit", output);
-    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, frame_pixels(ctx) * sizeof(float),
-                     "srt_read_visibility: the last srt_render_visibility did not write output 0x%x (or there has been none)", output);
+    return read_output(ctx, ctx->visibility.last, output, srt::visibility_slot(output), dst, frame_pixels(ctx) * sizeof(float),
+                       "srt_read_visibility: output 0x%x is not a single SRT_VIS_* bit",
+                       "srt_read_visibility: the last srt_render_visibility did not write output 0x%x (or there has been none)");
 }
 
+SRT_WORK_LAYOUT(srt_visibility_work, srt::VIS_WORK_N, segments, srt::VIS_WORK_SEGMENTS, triangle_tests, srt::VIS_WORK_TRIANGLES);
 int srt_get_visibility_work(srt_context* ctx, srt_visibility_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::visibility_check_work(ctx->visibility) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_visibility_work: the last srt_render_visibility did not ask for SRT_VIS_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::VIS_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_visibility_work, w, srt::VIS_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->segments = w[srt::VIS_WORK_SEGMENTS], out->open = w[srt::VIS_WORK_OPEN], out->wave_trips = w[srt::VIS_WORK_TRIPS];
-    out->analytic_tests = w[srt::VIS_WORK_ANALYTIC], out->node_visits = w[srt::VIS_WORK_NODES], out->triangle_tests = w[srt::VIS_WORK_TRIANGLES];
-    return SRT_OK;
+    return get_work(ctx, ctx->visibility.call, ctx->d_visibility_work, out,
+                    "srt_get_visibility_work: the last srt_render_visibility did not ask for SRT_VIS_COUNT_WORK (or there has been none)");
 }
 
 // ---- reflection guides ---------------------------------------------------------------------------------------------
@@ -2053,7 +2069,7 @@ int srt_render_reflection_gbuffer(srt_context* ctx, const srt_reflection_params*
     for (int i = 0; i < srt::REFL_SLOTS; ++i)
         if ((r->outputs & (1u << i)) && !ctx->refl.out[i].bound) ctx->refl_own_cam[i] = ctx->camera.cam, ctx->refl_own_cam_set[i] = true;
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_reflection_work, srt::REFL_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_reflection_work)) return rc;
     }
     srt::KernelParams K;
     const KernelSetup ks = scene_kernel_params(ctx, r->row_begin, r->row_end, K);
@@ -2062,16 +2078,14 @@ int srt_render_reflection_gbuffer(srt_context* ctx, const srt_reflection_params*
     io.bounces = (int32_t*)dst[4];
     io.max_bounces = r->max_bounces, io.min_smoothness = r->min_smoothness, io.min_specular = r->min_specular;
     io.work = count ? (unsigned long long*)ctx->d_reflection_work : nullptr;
-    if (const int rc = launch_tiles(ctx, SRT_KERNEL_LDS_MESH_COUNT(srt::reflection_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count), ks, K, io)) return rc;
+    if (const int rc = launch_tiles(ctx, SRT_KERNEL(srt::reflection_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count), ks, K, io)) return rc;
     srt::reflection_rendered(ctx->reflection, ctx->refl, r->outputs, dst, r->flags);
     return SRT_OK;
 }
 
 int srt_bind_reflection(srt_context* ctx, uint32_t output, void* d_ptr) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    const int i = srt::reflection_slot(output);
-    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_reflection: output 0x%x is not a single SRT_REFL_* bit", output);
-    return ctx->refl.out[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued launches keep the buffer they were given, as srt_bind_gbuffer)
+    return bind_output(ctx, ctx->refl.out, srt::reflection_slot(output), d_ptr, "srt_bind_reflection: output 0x%x is not a single SRT_REFL_* bit", output);
 }
 
 int srt_read_reflection(srt_context* ctx, uint32_t output, void* dst) {
@@ -2100,16 +2114,11 @@ int srt_device_reflection(srt_context* ctx, uint32_t output, void** d_ptr) {
     return SRT_OK;
 }
 
+SRT_WORK_LAYOUT(srt_reflection_work, srt::REFL_WORK_N, pixels, srt::REFL_WORK_PIXELS, waves, srt::REFL_WORK_WAVES);
 int srt_get_reflection_work(srt_context* ctx, srt_reflection_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::reflection_check_work(ctx->reflection) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_reflection_work: the last srt_render_reflection_gbuffer did not ask for SRT_REFL_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::REFL_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_reflection_work, w, srt::REFL_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->pixels = w[srt::REFL_WORK_PIXELS], out->reflections = w[srt::REFL_WORK_REFLECTIONS];
-    out->wave_calls = w[srt::REFL_WORK_CALLS], out->waves = w[srt::REFL_WORK_WAVES];
-    return SRT_OK;
+    return get_work(ctx, ctx->reflection, ctx->d_reflection_work, out,
+                    "srt_get_reflection_work: the last srt_render_reflection_gbuffer did not ask for SRT_REFL_COUNT_WORK (or there has been none)");
 }
 
 // ---- radiance queries ----------------------------------------------------------------------------------------------
@@ -2128,13 +2137,6 @@ int srt_radiance_params_default(srt_radiance_params* out) {
     return SRT_OK;
 }
 
-// ... in front of the re-allocation of the own radiance buffer or of the sample scratch: earlier traces may still be using them
-static int radiance_output_released(srt_context* ctx) {
-    if (const int rc = finish_stream(ctx)) return rc;
-    srt::radiance_output_released(ctx->radiance, (void*)ctx->d_radiance_own);
-    return SRT_OK;
-}
-
 // srt_probe_tail is on and changes this trace: what the mode requires of the grid's inputs, and a coefficient array that is not
 // the buffer the call is about to write, `written` (NULL: an own buffer not allocated yet)
 static int check_probe_tail(srt_context* ctx, const char* who, const void* written, size_t written_bytes) {
@@ -2148,7 +2150,7 @@ static int check_probe_tail(srt_context* ctx, const char* who, const void* writt
 // the record of an affected trace under the mode with SRT_PROBE_TAIL_COUNT_WORK, zeroed on the stream in front of it
 static int zero_probe_tail_work(srt_context* ctx) {
     if (!ctx->probe_tail.enabled || !(ctx->probe_tail.call.flags & SRT_PROBE_TAIL_COUNT_WORK)) return SRT_OK;
-    return zero_work(ctx, ctx->d_probe_tail_work, srt::PT_WORK_N);
+    return zero_work(ctx, ctx->d_probe_tail_work);
 }
 
 // the tail's kernel argument: the grid and the arrays current now, as shade_probe_grid takes them
@@ -2196,23 +2198,23 @@ int srt_trace_radiance(srt_context* ctx, const srt_radiance_params* t) {
         if (const int rc = check_probe_tail(ctx, "srt_trace_radiance", current(ctx->radiance_out, ctx->d_radiance_own), n * sizeof(float4))) return rc;
     }
     float4* dst = nullptr;
-    SRT_WRITE_TARGET_AFTER(ctx, ctx->radiance_out, ctx->d_radiance_own, n * sizeof(float4), dst, radiance_output_released(ctx));
+    SRT_WRITE_TARGET_AFTER(ctx, ctx->radiance_out, ctx->d_radiance_own, n * sizeof(float4), dst, output_released(ctx, ctx->radiance.last, 0, ctx->d_radiance_own));
     srt::KernelParams K;
     const KernelSetup ks = scene_kernel_params(ctx, 0, ctx->height, K);
     // (the fields accumulate_sample and the bounce loop read)
     K.first_sample = t->first_sample, K.sample_count = t->sample_count, K.max_bounces = t->max_bounces, K.seed = t->seed;
     if (t->flags & SRT_RADIANCE_RESET) K.flags |= SRT_RENDER_RESET;
-    const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::radiance_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
-    const auto tail_kernel = SRT_KERNEL_LDS_MESH(srt::radiance_tail_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0);
+    const auto kernel = SRT_KERNEL(srt::radiance_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    const auto tail_kernel = SRT_KERNEL(srt::radiance_tail_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0);
     // the grid first: the sample scratch is sized by it
     const unsigned wgs = srt::radiance_grid(n, srt::OUT_WG_UNITS, resident_workgroups(ctx, tail ? (const void*)tail_kernel : (const void*)kernel, ks.lds_bytes));
     if (const int rc = ensure_sample_rows(ctx, wgs)) return rc;
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_radiance_work, srt::RAD_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_radiance_work)) return rc;
     }
     if (const int rc = zero_probe_tail_work(ctx)) return rc;
     srt::RadianceIO io{};
-    io.origin = ctx->rays.bound() ? (const float4*)ctx->rays.bound_origin : (const float4*)ctx->d_ray_origin;
+    io.origin = current(ctx->rays.origins, ctx->d_ray_origin);
     io.direction = ctx->rays.bound() ? (const float4*)ctx->rays.bound_direction : (const float4*)ctx->d_ray_direction;
     io.count = (uint32_t)n;
     io.normalize = (t->flags & SRT_RADIANCE_NORMALIZE) ? 1u : 0u;
@@ -2233,22 +2235,15 @@ int srt_bind_radiance(srt_context* ctx, void* d_float4) {
 
 int srt_read_radiance(srt_context* ctx, float* dst_rgba) {
     if (!ctx || !dst_rgba) return SRT_ERR_INVALID_ARG;
-    const void* src = nullptr;
-    size_t bytes = 0;
-    const srt::RaysStatus rs = srt::radiance_check_read(ctx->radiance, &src, &bytes);
-    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst_rgba, bytes, "srt_read_radiance: there has been no srt_trace_radiance (or its buffer has been re-allocated)");
+    return read_slot(ctx, ctx->radiance.last.read(1u, 0), dst_rgba, ctx->radiance.last_count * sizeof(float4),
+                     "srt_read_radiance: there has been no srt_trace_radiance (or its buffer has been re-allocated)");
 }
 
+SRT_WORK_LAYOUT(srt_radiance_work, srt::RAD_WORK_N, rays, srt::RAD_WORK_RAYS, wave_calls, srt::RAD_WORK_WAVE_CALLS);
 int srt_get_radiance_work(srt_context* ctx, srt_radiance_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::radiance_check_work(ctx->radiance) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_radiance_work: the last srt_trace_radiance did not ask for SRT_RADIANCE_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::RAD_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_radiance_work, w, srt::RAD_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->rays = w[srt::RAD_WORK_RAYS], out->samples = w[srt::RAD_WORK_SAMPLES];
-    out->closest_calls = w[srt::RAD_WORK_CLOSEST], out->wave_calls = w[srt::RAD_WORK_WAVE_CALLS];
-    return SRT_OK;
+    return get_work(ctx, ctx->radiance.call, ctx->d_radiance_work, out,
+                    "srt_get_radiance_work: the last srt_trace_radiance did not ask for SRT_RADIANCE_COUNT_WORK (or there has been none)");
 }
 
 // ---- light probes --------------------------------------------------------------------------------------------------
@@ -2261,7 +2256,7 @@ static_assert(SRT_LIGHT_PROBE_RESET == srt::LIGHT_PROBE_FLAG_RESET && SRT_LIGHT_
               "srt_light_probes_host.h, srt_light_probes.hip.h and srt_pathtrace.h disagree");
 
 // srt_write_light_probes / srt_write_light_probe_directions / srt_write_probe_previous_states: 1 .. limit float4
-static int write_light_probe_input(srt_context* ctx, srt::LightProbeInput& in, DeviceBuffer<float4>& own, const float* src, size_t count, size_t limit,
+static int write_light_probe_input(srt_context* ctx, srt::InputArray& in, DeviceBuffer<float4>& own, const float* src, size_t count, size_t limit,
                                    const char* who) {
     if (count < 1 || count > limit) return fail(ctx, SRT_ERR_INVALID_ARG, "%s: %zu elements: want 1 .. %zu", who, count, limit);
     return write_probe_input(ctx, in, own, src, count, sizeof(float4));
@@ -2275,7 +2270,7 @@ int srt_write_light_probes(srt_context* ctx, const float* positions, size_t coun
 int srt_bind_light_probes(srt_context* ctx, const void* d_positions, size_t count) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
     // (no synchronisation: enqueued traces keep the array they were given, as srt_bind_rays)
-    if (srt::light_probe_bind(ctx->probes.positions, d_positions, count, srt::LIGHT_PROBE_MAX_RAYS) != srt::RAYS_OK)
+    if (srt::input_bind(ctx->probes.positions, d_positions, count, srt::LIGHT_PROBE_MAX_RAYS) != srt::RAYS_OK)
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_light_probes: want a device array and 1 .. 2^30 positions, or NULL, 0 (got %zu)", count);
     return SRT_OK;
 }
@@ -2288,7 +2283,7 @@ int srt_write_light_probe_directions(srt_context* ctx, const float* directions, 
 
 int srt_bind_light_probe_directions(srt_context* ctx, const void* d_directions, size_t count) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    if (srt::light_probe_bind(ctx->probes.directions, d_directions, count, srt::LIGHT_PROBE_MAX_DIRECTIONS) != srt::RAYS_OK)
+    if (srt::input_bind(ctx->probes.directions, d_directions, count, srt::LIGHT_PROBE_MAX_DIRECTIONS) != srt::RAYS_OK)
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_light_probe_directions: want a device array and 1 .. 4096 directions, or NULL, 0 (got %zu)", count);
     return SRT_OK;
 }
@@ -2330,7 +2325,7 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
     for (int i = 0; i < srt::LIGHT_PROBE_SLOTS; ++i)
         if (t->outputs & (1u << i))
             SRT_WRITE_TARGET_AFTER(ctx, ctx->probe_out[i], ctx->d_probe_out_own[i], srt::light_probe_elems(i, np, nk) * sizeof(float4), dst[i],
-                                   probe_output_released(ctx, srt::light_probe_output_released, ctx->probes, i, ctx->d_probe_out_own[i]));
+                                   output_released(ctx, ctx->probes.last, i, ctx->d_probe_out_own[i]));
     const size_t partial = coefficients ? srt::light_probe_partial_bytes(np, nk) : 0;
     if (ctx->d_probe_partial.bytes() < partial) {
         if (const int rc = finish_stream(ctx)) return rc;
@@ -2341,19 +2336,14 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
     // (the fields accumulate_sample and the bounce loop read)
     K.first_sample = t->first_sample, K.sample_count = t->sample_count, K.max_bounces = t->max_bounces, K.seed = t->seed;
     if (t->flags & SRT_LIGHT_PROBE_RESET) K.flags |= SRT_RENDER_RESET;
-    const auto kernel = listed ? SRT_KERNEL_LDS_MESH_COUNT_LISTED(srt::light_probe_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count)
-                               : SRT_KERNEL_LDS_MESH_COUNT(srt::light_probe_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
-    const bool in_lds = ctx->scene_in_lds[ks.img], mesh = K.n_tris > 0;
-    const auto tail_kernel = listed ? (in_lds ? (mesh ? srt::light_probe_tail_kernel<true, true, true> : srt::light_probe_tail_kernel<true, false, true>)
-                                              : (mesh ? srt::light_probe_tail_kernel<false, true, true> : srt::light_probe_tail_kernel<false, false, true>))
-                                    : (in_lds ? (mesh ? srt::light_probe_tail_kernel<true, true, false> : srt::light_probe_tail_kernel<true, false, false>)
-                                              : (mesh ? srt::light_probe_tail_kernel<false, true, false> : srt::light_probe_tail_kernel<false, false, false>));
+    const auto kernel = SRT_KERNEL(srt::light_probe_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count, listed);
+    const auto tail_kernel = SRT_KERNEL(srt::light_probe_tail_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, listed);
     // the grid first: the sample scratch is sized by it
     const unsigned wgs =
         srt::light_probe_grid(np, nk, srt::OUT_WG_UNITS, resident_workgroups(ctx, tail ? (const void*)tail_kernel : (const void*)kernel, ks.lds_bytes));
     if (const int rc = ensure_sample_rows(ctx, wgs)) return rc;
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_probe_work, srt::LP_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_probe_work)) return rc;
     }
     if (const int rc = zero_probe_tail_work(ctx)) return rc;
     srt::LightProbeIO io{};
@@ -2390,31 +2380,23 @@ int srt_trace_light_probes_listed(srt_context* ctx, const srt_light_probe_params
 
 int srt_bind_light_probe_output(srt_context* ctx, uint32_t output, void* d_ptr) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    const int i = srt::light_probe_slot(output);
-    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_light_probe_output: output 0x%x is not a single SRT_LIGHT_PROBE_COEFFICIENTS / _RADIANCE bit", output);
-    return ctx->probe_out[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued traces keep the buffer they were given, as srt_bind_ray_output)
+    return bind_output(ctx, ctx->probe_out, srt::light_probe_slot(output), d_ptr,
+                       "srt_bind_light_probe_output: output 0x%x is not a single SRT_LIGHT_PROBE_COEFFICIENTS / _RADIANCE bit", output);
 }
 
 int srt_read_light_probe_output(srt_context* ctx, uint32_t output, void* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
-    const void* src = nullptr;
-    size_t bytes = 0;
-    const srt::RaysStatus rs = srt::light_probe_check_read(ctx->probes, output, &src, &bytes);
-    if (rs == srt::RAYS_INVALID_ARG)
-        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_light_probe_output: output 0x%x is not a single SRT_LIGHT_PROBE_COEFFICIENTS / _RADIANCE bit", output);
-    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, bytes, "srt_read_light_probe_output: output 0x%x was not written by the last srt_trace_light_probes", output);
+    const int i = srt::light_probe_slot(output);
+    return read_output(ctx, ctx->probes.last, output, i, dst, srt::light_probe_elems(i, ctx->probes.last_probes, ctx->probes.last_directions) * sizeof(float4),
+                       "srt_read_light_probe_output: output 0x%x is not a single SRT_LIGHT_PROBE_COEFFICIENTS / _RADIANCE bit",
+                       "srt_read_light_probe_output: output 0x%x was not written by the last srt_trace_light_probes");
 }
 
+SRT_WORK_LAYOUT(srt_light_probe_work, srt::LP_WORK_N, probes, srt::LP_WORK_PROBES, waves, srt::LP_WORK_WAVES);
 int srt_get_light_probe_work(srt_context* ctx, srt_light_probe_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::light_probe_check_work(ctx->probes) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_light_probe_work: the last srt_trace_light_probes did not ask for SRT_LIGHT_PROBE_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::LP_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_probe_work, w, srt::LP_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->probes = w[srt::LP_WORK_PROBES], out->rays = w[srt::LP_WORK_RAYS], out->samples = w[srt::LP_WORK_SAMPLES];
-    out->closest_calls = w[srt::LP_WORK_CLOSEST], out->wave_calls = w[srt::LP_WORK_WAVE_CALLS], out->waves = w[srt::LP_WORK_WAVES];
-    return SRT_OK;
+    return get_work(ctx, ctx->probes.call, ctx->d_probe_work, out,
+                    "srt_get_light_probe_work: the last srt_trace_light_probes did not ask for SRT_LIGHT_PROBE_COUNT_WORK (or there has been none)");
 }
 
 int srt_light_probe_sphere(size_t count, float* dst) {
@@ -2478,7 +2460,7 @@ int srt_write_probe_grid_coefficients(srt_context* ctx, const float* coefficient
 
 int srt_bind_probe_grid_coefficients(srt_context* ctx, const void* d_ptr, size_t probes) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    if (srt::light_probe_bind(ctx->probe_grid.coefficients, d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
+    if (srt::input_bind(ctx->probe_grid.coefficients, d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_grid_coefficients: want a device array and 1 .. 2^30 probes, or NULL, 0 (got %zu)", probes);
     return SRT_OK;
 }
@@ -2510,18 +2492,16 @@ static int shade_probe_grid(srt_context* ctx, const char* who, const srt_probe_g
     float4* dst = nullptr;
     SRT_WRITE_TARGET(ctx, ctx->probe_grid_out, ctx->d_probe_grid_own, frame_pixels(ctx) * sizeof(float4), dst);
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_probe_grid_work, srt::PG_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_probe_grid_work)) return rc;
     }
     srt::KernelParams K;
     KernelSetup ks = scene_kernel_params(ctx, s->row_begin, s->row_end, K);
     void (*kernel)(srt::KernelParams, srt::ProbeGridIO);
     if (which == PG_SHADE_QUERY) {
-        kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::probe_grid_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+        kernel = SRT_KERNEL(srt::probe_grid_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
     } else {
         ks.lds_bytes = 0;  // (the kernel traces nothing: no scene image, and its own LDS is static)
-        kernel = which == PG_SHADE_DEPTH ? (count ? srt::probe_grid_depth_kernel<true> : srt::probe_grid_depth_kernel<false>)
-                 : d                     ? (count ? srt::probe_grid_states_kernel<true, true> : srt::probe_grid_states_kernel<true, false>)
-                                         : (count ? srt::probe_grid_states_kernel<false, true> : srt::probe_grid_states_kernel<false, false>);
+        kernel = which == PG_SHADE_DEPTH ? SRT_KERNEL(srt::probe_grid_depth_kernel, count) : SRT_KERNEL(srt::probe_grid_states_kernel, d != nullptr, count);
     }
     const srt::ProbeGrid& g = ctx->probe_grid.grid;
     srt::ProbeGridIO io{};
@@ -2563,17 +2543,11 @@ int srt_read_probe_grid_output(srt_context* ctx, float* dst) {
                      "srt_read_probe_grid_output: there has been no srt_shade_probe_grid");
 }
 
+SRT_WORK_LAYOUT(srt_probe_grid_work, srt::PG_WORK_N, pixels, srt::PG_WORK_PIXELS, waves, srt::PG_WORK_WAVES);
 int srt_get_probe_grid_work(srt_context* ctx, srt_probe_grid_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::probe_grid_check_work(ctx->probe_grid) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_grid_work: the last srt_shade_probe_grid did not ask for SRT_PROBE_GRID_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::PG_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_probe_grid_work, w, srt::PG_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->pixels = w[srt::PG_WORK_PIXELS], out->corners = w[srt::PG_WORK_CORNERS], out->segments = w[srt::PG_WORK_SEGMENTS], out->open = w[srt::PG_WORK_OPEN];
-    out->wave_trips = w[srt::PG_WORK_TRIPS], out->analytic_tests = w[srt::PG_WORK_ANALYTIC], out->node_visits = w[srt::PG_WORK_NODES];
-    out->triangle_tests = w[srt::PG_WORK_TRIANGLES], out->waves = w[srt::PG_WORK_WAVES];
-    return SRT_OK;
+    return get_work(ctx, ctx->probe_grid.call, ctx->d_probe_grid_work, out,
+                    "srt_get_probe_grid_work: the last srt_shade_probe_grid did not ask for SRT_PROBE_GRID_COUNT_WORK (or there has been none)");
 }
 
 // ---- probe depth moments -------------------------------------------------------------------------------------------
@@ -2623,14 +2597,13 @@ static int trace_probe_depth(srt_context* ctx, const srt_probe_depth_params* t, 
     for (int i = 0; i < srt::PROBE_DEPTH_SLOTS; ++i)
         if (t->outputs & (1u << i))
             SRT_WRITE_TARGET_AFTER(ctx, ctx->probe_depth_out[i], ctx->d_probe_depth_own[i], srt::probe_depth_bytes(i, np, nk, t->resolution), dst[i],
-                                   probe_output_released(ctx, srt::probe_depth_output_released, ctx->probe_depth, i, ctx->d_probe_depth_own[i]));
+                                   output_released(ctx, ctx->probe_depth.last, i, ctx->d_probe_depth_own[i]));
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_probe_depth_work, srt::PD_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_probe_depth_work)) return rc;
     }
     srt::KernelParams K;
     const KernelSetup ks = scene_kernel_params(ctx, 0, ctx->height, K);
-    const auto kernel = listed ? SRT_KERNEL_LDS_MESH_COUNT_LISTED(srt::probe_depth_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count)
-                               : SRT_KERNEL_LDS_MESH_COUNT(srt::probe_depth_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    const auto kernel = SRT_KERNEL(srt::probe_depth_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count, listed);
     const unsigned wgs = srt::probe_depth_grid(np, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, ks.lds_bytes));
     srt::ProbeDepthIO io{};
     io.position = current(ctx->probes.positions, ctx->d_probe_position);
@@ -2653,31 +2626,24 @@ int srt_trace_probe_depth_listed(srt_context* ctx, const srt_probe_depth_params*
 
 int srt_bind_probe_depth_output(srt_context* ctx, uint32_t output, void* d_ptr) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    const int i = srt::probe_depth_slot(output);
-    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_depth_output: output 0x%x is not a single SRT_PROBE_DEPTH_MOMENTS / _DISTANCES bit", output);
-    return ctx->probe_depth_out[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued traces keep the buffer they were given, as srt_bind_ray_output)
+    return bind_output(ctx, ctx->probe_depth_out, srt::probe_depth_slot(output), d_ptr,
+                       "srt_bind_probe_depth_output: output 0x%x is not a single SRT_PROBE_DEPTH_MOMENTS / _DISTANCES bit", output);
 }
 
 int srt_read_probe_depth_output(srt_context* ctx, uint32_t output, void* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
-    const void* src = nullptr;
-    size_t bytes = 0;
-    const srt::RaysStatus rs = srt::probe_depth_check_read(ctx->probe_depth, output, &src, &bytes);
-    if (rs == srt::RAYS_INVALID_ARG)
-        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_probe_depth_output: output 0x%x is not a single SRT_PROBE_DEPTH_MOMENTS / _DISTANCES bit", output);
-    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, bytes, "srt_read_probe_depth_output: output 0x%x was not written by the last srt_trace_probe_depth", output);
+    const srt::ProbeDepthState& s = ctx->probe_depth;
+    const int i = srt::probe_depth_slot(output);
+    return read_output(ctx, s.last, output, i, dst, srt::probe_depth_bytes(i, s.last_probes, s.last_directions, s.last_resolution),
+                       "srt_read_probe_depth_output: output 0x%x is not a single SRT_PROBE_DEPTH_MOMENTS / _DISTANCES bit",
+                       "srt_read_probe_depth_output: output 0x%x was not written by the last srt_trace_probe_depth");
 }
 
+SRT_WORK_LAYOUT(srt_probe_depth_work, srt::PD_WORK_N, probes, srt::PD_WORK_PROBES, waves, srt::PD_WORK_WAVES);
 int srt_get_probe_depth_work(srt_context* ctx, srt_probe_depth_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::probe_depth_check_work(ctx->probe_depth) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_depth_work: the last srt_trace_probe_depth did not ask for SRT_PROBE_DEPTH_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::PD_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_probe_depth_work, w, srt::PD_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->probes = w[srt::PD_WORK_PROBES], out->rays = w[srt::PD_WORK_RAYS], out->far_rays = w[srt::PD_WORK_FAR];
-    out->wave_calls = w[srt::PD_WORK_WAVE_CALLS], out->waves = w[srt::PD_WORK_WAVES];
-    return SRT_OK;
+    return get_work(ctx, ctx->probe_depth.call, ctx->d_probe_depth_work, out,
+                    "srt_get_probe_depth_work: the last srt_trace_probe_depth did not ask for SRT_PROBE_DEPTH_COUNT_WORK (or there has been none)");
 }
 
 // ---- probe-grid shading with the filtered visibility test ------------------------------------------------------------
@@ -2768,15 +2734,14 @@ int srt_classify_probes(srt_context* ctx, const srt_probe_classify_params* t) {
     for (int i = 0; i < srt::PROBE_STATE_SLOTS; ++i)
         if (t->outputs & (1u << i))
             SRT_WRITE_TARGET_AFTER(ctx, ctx->probe_states_out[i], ctx->d_probe_states_own[i], srt::probe_state_bytes(np), dst[i],
-                                   probe_output_released(ctx, srt::probe_states_output_released, ctx->probe_states, i, ctx->d_probe_states_own[i]));
+                                   output_released(ctx, ctx->probe_states.last, i, ctx->d_probe_states_own[i]));
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_probe_classify_work, srt::PS_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_probe_classify_work)) return rc;
     }
     const srt::ProbeTable& T = ctx->probe_table;
     const bool in_lds = T.vec4() <= (size_t)srt::PS_TABLE_LDS_VEC4;
     const size_t lds_bytes = in_lds ? T.vec4() * sizeof(float4) : 0;
-    void (*const kernel)(srt::ProbeClassifyIO) = in_lds ? (count ? srt::probe_classify_kernel<true, true> : srt::probe_classify_kernel<true, false>)
-                                                        : (count ? srt::probe_classify_kernel<false, true> : srt::probe_classify_kernel<false, false>);
+    void (*const kernel)(srt::ProbeClassifyIO) = SRT_KERNEL(srt::probe_classify_kernel, in_lds, count);
     const unsigned wgs = srt::probe_classify_grid(np, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, lds_bytes));
     srt::ProbeClassifyIO io{};
     io.table = (const float4*)ctx->d_probe_table;
@@ -2800,31 +2765,22 @@ int srt_classify_probes(srt_context* ctx, const srt_probe_classify_params* t) {
 
 int srt_bind_probe_states_output(srt_context* ctx, uint32_t output, void* d_ptr) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    const int i = srt::probe_state_slot(output);
-    if (i < 0) return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_states_output: output 0x%x is not a single SRT_PROBE_STATE_RECORDS / _POSITIONS bit", output);
-    return ctx->probe_states_out[i].bind(d_ptr), SRT_OK;  // (no synchronisation: enqueued calls keep the buffer they were given, as srt_bind_ray_output)
+    return bind_output(ctx, ctx->probe_states_out, srt::probe_state_slot(output), d_ptr,
+                       "srt_bind_probe_states_output: output 0x%x is not a single SRT_PROBE_STATE_RECORDS / _POSITIONS bit", output);
 }
 
 int srt_read_probe_states_output(srt_context* ctx, uint32_t output, void* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
-    const void* src = nullptr;
-    size_t bytes = 0;
-    const srt::RaysStatus rs = srt::probe_states_check_read(ctx->probe_states, output, &src, &bytes);
-    if (rs == srt::RAYS_INVALID_ARG)
-        return fail(ctx, SRT_ERR_INVALID_ARG, "srt_read_probe_states_output: output 0x%x is not a single SRT_PROBE_STATE_RECORDS / _POSITIONS bit", output);
-    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, bytes, "srt_read_probe_states_output: output 0x%x was not written by the last srt_classify_probes", output);
+    return read_output(ctx, ctx->probe_states.last, output, srt::probe_state_slot(output), dst, srt::probe_state_bytes(ctx->probe_states.last_probes),
+                       "srt_read_probe_states_output: output 0x%x is not a single SRT_PROBE_STATE_RECORDS / _POSITIONS bit",
+                       "srt_read_probe_states_output: output 0x%x was not written by the last srt_classify_probes");
 }
 
+SRT_WORK_LAYOUT(srt_probe_classify_work, srt::PS_WORK_N, probes, srt::PS_WORK_PROBES, waves, srt::PS_WORK_WAVES);
 int srt_get_probe_classify_work(srt_context* ctx, srt_probe_classify_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::probe_states_check_work(ctx->probe_states) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_classify_work: the last srt_classify_probes did not ask for SRT_PROBE_CLASSIFY_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::PS_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_probe_classify_work, w, srt::PS_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->probes = w[srt::PS_WORK_PROBES], out->inside = w[srt::PS_WORK_INSIDE], out->moved = w[srt::PS_WORK_MOVED], out->buried = w[srt::PS_WORK_BURIED];
-    out->idle = w[srt::PS_WORK_IDLE], out->candidates = w[srt::PS_WORK_CANDIDATES], out->waves = w[srt::PS_WORK_WAVES];
-    return SRT_OK;
+    return get_work(ctx, ctx->probe_states.call, ctx->d_probe_classify_work, out,
+                    "srt_get_probe_classify_work: the last srt_classify_probes did not ask for SRT_PROBE_CLASSIFY_COUNT_WORK (or there has been none)");
 }
 
 // ---- probe-grid shading that obeys the probe states ---------------------------------------------------------------------
@@ -2836,7 +2792,7 @@ int srt_write_probe_grid_states(srt_context* ctx, const float* records, size_t p
 
 int srt_bind_probe_grid_states(srt_context* ctx, const void* d_ptr, size_t probes) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    if (srt::light_probe_bind(ctx->probe_states.states, d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
+    if (srt::input_bind(ctx->probe_states.states, d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_grid_states: want a device array and 1 .. 2^30 probes, or NULL, 0 (got %zu)", probes);
     return SRT_OK;
 }
@@ -2877,21 +2833,20 @@ int srt_list_probes(srt_context* ctx, const srt_probe_list_params* t) {
     uint32_t* dst = (uint32_t*)const_cast<void*>(ctx->probe_update.list_out_bound);
     if (!dst) {
         if (ctx->d_probe_list_out.bytes() < srt::probe_list_bytes(np)) {  // earlier listings may still be writing it, listed traces reading it
-            if (const int rc = finish_stream(ctx)) return rc;
-            srt::probe_list_output_released(ctx->probe_update, (uint32_t*)ctx->d_probe_list_out);
+            if (const int rc = output_released(ctx, ctx->probe_update.list_last, 0, ctx->d_probe_list_out)) return rc;
             SRT_HIP(ctx, ctx->d_probe_list_out.ensure(srt::probe_list_bytes(np)));
         }
         dst = ctx->d_probe_list_out;
     }
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_probe_list_work, srt::PL_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_probe_list_work)) return rc;
     }
     srt::ProbeListIO io{};
     io.states = current(ctx->probe_states.states, ctx->d_probe_grid_states);
     io.list = dst;
     io.probes = (uint32_t)np, io.skip_mask = t->skip_mask;
     io.work = count ? (unsigned long long*)ctx->d_probe_list_work : nullptr;
-    hipLaunchKernelGGL(count ? srt::probe_list_kernel<true> : srt::probe_list_kernel<false>, dim3(1), dim3(srt::WG_THREADS), 0, ctx->stream, io);
+    hipLaunchKernelGGL(SRT_KERNEL(srt::probe_list_kernel, count), dim3(1), dim3(srt::WG_THREADS), 0, ctx->stream, io);
     SRT_HIP(ctx, hipGetLastError());
     srt::probe_list_listed(ctx->probe_update, np, t->flags, dst);
     return SRT_OK;
@@ -2904,21 +2859,15 @@ int srt_bind_probe_list_output(srt_context* ctx, void* d_list) {
 
 int srt_read_probe_list_output(srt_context* ctx, uint32_t* dst) {
     if (!ctx || !dst) return SRT_ERR_INVALID_ARG;
-    const void* src = nullptr;
-    size_t bytes = 0;
-    const srt::RaysStatus rs = srt::probe_list_check_read(ctx->probe_update, &src, &bytes);
-    return read_slot(ctx, rs == srt::RAYS_OK ? src : nullptr, dst, bytes, "srt_read_probe_list_output: there has been no srt_list_probes");
+    return read_slot(ctx, ctx->probe_update.list_last.read(1u, 0), dst, srt::probe_list_bytes(ctx->probe_update.list_probes),
+                     "srt_read_probe_list_output: there has been no srt_list_probes");
 }
 
+SRT_WORK_LAYOUT(srt_probe_list_work, srt::PL_WORK_N, probes, srt::PL_WORK_PROBES, waves, srt::PL_WORK_WAVES);
 int srt_get_probe_list_work(srt_context* ctx, srt_probe_list_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::probe_list_check_work(ctx->probe_update) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_list_work: the last srt_list_probes did not ask for SRT_PROBE_LIST_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::PL_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_probe_list_work, w, srt::PL_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->probes = w[srt::PL_WORK_PROBES], out->listed = w[srt::PL_WORK_LISTED], out->waves = w[srt::PL_WORK_WAVES];
-    return SRT_OK;
+    return get_work(ctx, ctx->probe_update.list_call, ctx->d_probe_list_work, out,
+                    "srt_get_probe_list_work: the last srt_list_probes did not ask for SRT_PROBE_LIST_COUNT_WORK (or there has been none)");
 }
 
 int srt_bind_probe_list(srt_context* ctx, const void* d_list, size_t capacity) {
@@ -2994,7 +2943,7 @@ int srt_write_probe_previous_states(srt_context* ctx, const float* records, size
 
 int srt_bind_probe_previous_states(srt_context* ctx, const void* d_ptr, size_t probes) {
     if (!ctx) return SRT_ERR_INVALID_ARG;
-    if (srt::light_probe_bind(ctx->probe_update.previous, d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
+    if (srt::input_bind(ctx->probe_update.previous, d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_previous_states: want a device array and 1 .. 2^30 probes, or NULL, 0 (got %zu)", probes);
     return SRT_OK;
 }
@@ -3017,12 +2966,12 @@ int srt_blend_probes(srt_context* ctx, const srt_probe_blend_params* t) {
             return fail(ctx, SRT_ERR_STATE, "srt_blend_probes: history 0x%x was unbound after its reset (srt_reset_probe_history)", 1u << i);
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_probe_blend_work, srt::PB_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_probe_blend_work)) return rc;
     }
     srt::ProbeBlendIO io{};
     io.history = current_probe_history(ctx, 0);
-    io.fresh = (const float4*)ctx->probes.last_dst[0];
-    if (moments) io.depth_history = current_probe_history(ctx, 1), io.depth_fresh = (const float4*)ctx->probe_depth.last_dst[0];
+    io.fresh = (const float4*)ctx->probes.last.dst[0];
+    if (moments) io.depth_history = current_probe_history(ctx, 1), io.depth_fresh = (const float4*)ctx->probe_depth.last.dst[0];
     io.list = listed ? current_probe_list(ctx) : nullptr;
     if (prev) {
         io.states = current(ctx->probe_states.states, ctx->d_probe_grid_states);
@@ -3031,11 +2980,7 @@ int srt_blend_probes(srt_context* ctx, const srt_probe_blend_params* t) {
     io.probes = (uint32_t)np, io.texels = R * R;
     io.hysteresis = t->hysteresis, io.fast_hysteresis = t->fast_hysteresis, io.depth_hysteresis = t->depth_hysteresis, io.change_threshold = t->change_threshold;
     io.work = count ? (unsigned long long*)ctx->d_probe_blend_work : nullptr;
-    void (*const kernel)(srt::ProbeBlendIO) =
-        listed ? (prev ? (count ? srt::probe_blend_kernel<true, true, true> : srt::probe_blend_kernel<true, true, false>)
-                       : (count ? srt::probe_blend_kernel<true, false, true> : srt::probe_blend_kernel<true, false, false>))
-               : (prev ? (count ? srt::probe_blend_kernel<false, true, true> : srt::probe_blend_kernel<false, true, false>)
-                       : (count ? srt::probe_blend_kernel<false, false, true> : srt::probe_blend_kernel<false, false, false>));
+    void (*const kernel)(srt::ProbeBlendIO) = SRT_KERNEL(srt::probe_blend_kernel, listed, prev, count);
     const unsigned wgs = srt::probe_blend_grid(np, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, 0));
     hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), 0, ctx->stream, io);
     SRT_HIP(ctx, hipGetLastError());
@@ -3043,15 +2988,11 @@ int srt_blend_probes(srt_context* ctx, const srt_probe_blend_params* t) {
     return SRT_OK;
 }
 
+SRT_WORK_LAYOUT(srt_probe_blend_work, srt::PB_WORK_N, probes, srt::PB_WORK_PROBES, waves, srt::PB_WORK_WAVES);
 int srt_get_probe_blend_work(srt_context* ctx, srt_probe_blend_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::probe_blend_check_work(ctx->probe_update) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_blend_work: the last srt_blend_probes did not ask for SRT_PROBE_BLEND_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::PB_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_probe_blend_work, w, srt::PB_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->probes = w[srt::PB_WORK_PROBES], out->restarted = w[srt::PB_WORK_RESTARTED], out->changed = w[srt::PB_WORK_CHANGED], out->waves = w[srt::PB_WORK_WAVES];
-    return SRT_OK;
+    return get_work(ctx, ctx->probe_update.blend_call, ctx->d_probe_blend_work, out,
+                    "srt_get_probe_blend_work: the last srt_blend_probes did not ask for SRT_PROBE_BLEND_COUNT_WORK (or there has been none)");
 }
 
 // ---- scrolling probe grids -------------------------------------------------------------------------------------------
@@ -3112,7 +3053,7 @@ int srt_scroll_probes(srt_context* ctx, const srt_probe_scroll_params* t) {
         SRT_HIP(ctx, ctx->d_probe_previous_states.ensure(np * sizeof(float4)));
     }
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_probe_scroll_work, srt::PSC_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_probe_scroll_work)) return rc;
     }
     srt::ProbeScrollIO io{};
     for (int i = 0; i < srt::PROBE_HISTORY_SLOTS; ++i) {
@@ -3128,7 +3069,7 @@ int srt_scroll_probes(srt_context* ctx, const srt_probe_scroll_params* t) {
     for (int a = 0; a < 3; ++a) io.counts[a] = g.counts[a], io.shift[a] = t->shift[a];
     io.work = count ? (unsigned long long*)ctx->d_probe_scroll_work : nullptr;
     if (io.dst[0] || io.dst[1] || io.dst[2] || count) {
-        void (*const kernel)(srt::ProbeScrollIO) = count ? srt::probe_scroll_kernel<true> : srt::probe_scroll_kernel<false>;
+        void (*const kernel)(srt::ProbeScrollIO) = SRT_KERNEL(srt::probe_scroll_kernel, count);
         const unsigned wgs = srt::probe_scroll_grid(np, srt::OUT_WG_UNITS, resident_workgroups(ctx, (const void*)kernel, 0));
         hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), 0, ctx->stream, io);
         SRT_HIP(ctx, hipGetLastError());
@@ -3140,7 +3081,7 @@ int srt_scroll_probes(srt_context* ctx, const srt_probe_scroll_params* t) {
         else
             ctx->d_probe_history[i].swap(ctx->d_probe_history_spare[i]);  // (enqueued launches keep the pointers they were given)
     }
-    if (states) srt::light_probe_written(ctx->probe_update.previous, np);
+    if (states) srt::input_written(ctx->probe_update.previous, np);
     if (t->flags & SRT_PROBE_SCROLL_SET_GRID) srt::probe_scroll_origin(g, call.shift, ctx->probe_grid.grid.origin);
     if (moving) srt::probe_scroll_stale(ctx->probes, ctx->probe_depth);
     srt::probe_scroll_scrolled(ctx->probe_scroll, t->flags);
@@ -3154,15 +3095,11 @@ int srt_read_probe_previous_states(srt_context* ctx, float* dst) {
                      "srt_read_probe_previous_states: no previous states have been written, bound or scrolled");
 }
 
+SRT_WORK_LAYOUT(srt_probe_scroll_work, srt::PSC_WORK_N, probes, srt::PSC_WORK_PROBES, waves, srt::PSC_WORK_WAVES);
 int srt_get_probe_scroll_work(srt_context* ctx, srt_probe_scroll_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::probe_scroll_check_work(ctx->probe_scroll) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_scroll_work: the last srt_scroll_probes did not ask for SRT_PROBE_SCROLL_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::PSC_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_probe_scroll_work, w, srt::PSC_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->probes = w[srt::PSC_WORK_PROBES], out->retained = w[srt::PSC_WORK_RETAINED], out->exposed = w[srt::PSC_WORK_EXPOSED], out->waves = w[srt::PSC_WORK_WAVES];
-    return SRT_OK;
+    return get_work(ctx, ctx->probe_scroll, ctx->d_probe_scroll_work, out,
+                    "srt_get_probe_scroll_work: the last srt_scroll_probes did not ask for SRT_PROBE_SCROLL_COUNT_WORK (or there has been none)");
 }
 
 // ---- probe cascade -------------------------------------------------------------------------------------------------
@@ -3228,7 +3165,7 @@ int srt_bind_probe_cascade_level(srt_context* ctx, uint32_t level, uint32_t whic
     const bool unbind = !d_ptr && probes == 0;
     if (const srt::RaysStatus rs = srt::probe_cascade_check_level_array(ctx->probe_cascade, level, which, unbind ? 1 : probes, &slot, &why))
         return fail(ctx, (int)rs, "srt_bind_probe_cascade_level: %s (level %u, which 0x%x, %zu probes)", why, level, which, probes);
-    if (srt::light_probe_bind(ctx->probe_cascade.arrays[level][slot], d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
+    if (srt::input_bind(ctx->probe_cascade.arrays[level][slot], d_ptr, probes, srt::PROBE_GRID_MAX_PROBES) != srt::RAYS_OK)
         return fail(ctx, SRT_ERR_INVALID_ARG, "srt_bind_probe_cascade_level: want a device array and 1 .. 2^30 probes, or NULL, 0 (got %zu)", probes);
     return SRT_OK;
 }
@@ -3247,14 +3184,14 @@ int srt_capture_probe_cascade_level(srt_context* ctx, uint32_t level, uint32_t w
         if (!(which_mask & (1u << i))) continue;
         const size_t bytes = np * srt::probe_cascade_probe_bytes(i, ctx->probe_cascade.cascade.resolution);
         DeviceBuffer<float4>& own = ctx->d_probe_cascade[level][i];
-        srt::LightProbeInput& in = ctx->probe_cascade.arrays[level][i];
+        srt::InputArray& in = ctx->probe_cascade.arrays[level][i];
         if (own.bytes() < bytes) {
             if (const int rc = finish_stream(ctx)) return rc;  // (launches in flight read the own array; it is re-allocated below)
             in.own_count = 0;                                  // (a failed allocation leaves no own array)
             SRT_HIP(ctx, own.ensure(bytes));
         }
         SRT_HIP(ctx, hipMemcpyAsync(own, src[i], bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        srt::light_probe_written(in, np);  // (a binding of that array ends)
+        srt::input_written(in, np);  // (a binding of that array ends)
     }
     return SRT_OK;
 }
@@ -3276,16 +3213,12 @@ int srt_shade_probe_cascade(srt_context* ctx, const srt_probe_cascade_params* s)
     float4* dst = nullptr;
     SRT_WRITE_TARGET(ctx, ctx->probe_grid_out, ctx->d_probe_grid_own, frame_pixels(ctx) * sizeof(float4), dst);
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_probe_cascade_work, srt::PC_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_probe_cascade_work)) return rc;
     }
     srt::KernelParams K;
     KernelSetup ks = scene_kernel_params(ctx, s->row_begin, s->row_end, K);
     ks.lds_bytes = 0;  // (the kernel traces nothing: no scene image, and its own LDS is static)
-    void (*kernel)(srt::KernelParams, srt::ProbeCascadeIO) =
-        depth ? (states ? (count ? srt::probe_cascade_kernel<true, true, true> : srt::probe_cascade_kernel<true, true, false>)
-                        : (count ? srt::probe_cascade_kernel<true, false, true> : srt::probe_cascade_kernel<true, false, false>))
-              : (states ? (count ? srt::probe_cascade_kernel<false, true, true> : srt::probe_cascade_kernel<false, true, false>)
-                        : (count ? srt::probe_cascade_kernel<false, false, true> : srt::probe_cascade_kernel<false, false, false>));
+    void (*kernel)(srt::KernelParams, srt::ProbeCascadeIO) = SRT_KERNEL(srt::probe_cascade_kernel, depth, states, count);
     const srt::ProbeCascade& c = ctx->probe_cascade.cascade;
     srt::ProbeCascadeIO io{};
     io.object = (const int32_t*)current(ctx->gbuf[0], ctx->d_gbuf_own[0]);
@@ -3313,10 +3246,11 @@ int srt_shade_probe_cascade(srt_context* ctx, const srt_probe_cascade_params* s)
 
 int srt_get_probe_cascade_work(srt_context* ctx, srt_probe_cascade_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::probe_cascade_check_work(ctx->probe_cascade) != srt::RAYS_OK)
+    // (field by field, not get_work: the struct ends in spare[2], which the enum does not have)
+    if (ctx->probe_cascade.call.work() != srt::RAYS_OK)
         return fail(ctx, SRT_ERR_STATE, "srt_get_probe_cascade_work: the last srt_shade_probe_cascade did not ask for SRT_PROBE_CASCADE_COUNT_WORK (or there has been none)");
     unsigned long long w[srt::PC_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_probe_cascade_work, w, srt::PC_WORK_N)) return rc;
+    if (const int rc = read_work(ctx, ctx->d_probe_cascade_work, w)) return rc;
     out->valid = 1, out->reserved = 0, out->spare[0] = 0, out->spare[1] = 0;
     out->pixels = w[srt::PC_WORK_PIXELS], out->evaluations = w[srt::PC_WORK_EVALUATIONS], out->blended = w[srt::PC_WORK_BLENDED];
     for (int k = 0; k < SRT_PROBE_CASCADE_MAX_LEVELS; ++k) out->first_level[k] = w[srt::PC_WORK_FIRST0 + k];
@@ -3407,8 +3341,8 @@ static int launch_adaptive(srt_context* ctx, const srt_adaptive_params* a, uint3
     // (the fields the bounce loop and store_pixel read; the frames are per pixel)
     K.max_bounces = a->max_bounces, K.seed = a->seed;
     K.accumulator = ctx->d_acc, K.framebuffer = ctx->d_fb;
-    const auto kernel = SRT_KERNEL_LDS_MESH_COUNT(srt::adaptive_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
-    const auto tail_kernel = SRT_KERNEL_LDS_MESH(srt::adaptive_tail_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0);
+    const auto kernel = SRT_KERNEL(srt::adaptive_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
+    const auto tail_kernel = SRT_KERNEL(srt::adaptive_tail_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0);
     // the grid first: the sample scratch is sized by it
     const unsigned wgs = srt::adaptive_grid(K.width, K.rows, srt::OUT_WG_UNITS,
                                             resident_workgroups(ctx, tail ? (const void*)tail_kernel : (const void*)kernel, ks.lds_bytes));
@@ -3416,7 +3350,7 @@ static int launch_adaptive(srt_context* ctx, const srt_adaptive_params* a, uint3
     if (!ctx->d_adaptive_ticket) SRT_HIP(ctx, ctx->d_adaptive_ticket.ensure(sizeof(uint32_t)));
     SRT_HIP(ctx, hipMemsetAsync(ctx->d_adaptive_ticket, 0, sizeof(uint32_t), ctx->stream));
     if (count) {
-        if (const int rc = zero_work(ctx, ctx->d_adaptive_work, srt::ADP_WORK_N)) return rc;
+        if (const int rc = zero_work(ctx, ctx->d_adaptive_work)) return rc;
     }
     srt::AdaptiveIO io{};
     io.budget = budget;
@@ -3466,16 +3400,11 @@ int srt_render_adaptive_tail(srt_context* ctx, const srt_adaptive_params* a) {
     return SRT_OK;
 }
 
+SRT_WORK_LAYOUT(srt_adaptive_work, srt::ADP_WORK_N, pixels, srt::ADP_WORK_PIXELS, wave_calls, srt::ADP_WORK_WAVE_CALLS);
 int srt_get_adaptive_work(srt_context* ctx, srt_adaptive_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::adaptive_check_work(ctx->adaptive) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_adaptive_work: the last srt_render_adaptive did not ask for SRT_ADAPTIVE_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::ADP_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_adaptive_work, w, srt::ADP_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->pixels = w[srt::ADP_WORK_PIXELS], out->samples = w[srt::ADP_WORK_SAMPLES];
-    out->closest_calls = w[srt::ADP_WORK_CLOSEST], out->wave_calls = w[srt::ADP_WORK_WAVE_CALLS];
-    return SRT_OK;
+    return get_work(ctx, ctx->adaptive.call, ctx->d_adaptive_work, out,
+                    "srt_get_adaptive_work: the last srt_render_adaptive did not ask for SRT_ADAPTIVE_COUNT_WORK (or there has been none)");
 }
 
 int srt_budget_params_default(srt_budget_params* out) {
@@ -3501,7 +3430,7 @@ int srt_sample_budget(srt_context* ctx, const srt_budget_params* b) {
                     b->max_budget, b->flags);
     srt::BudgetLaunch L{};
     if (const int rc = sample_buffer_target(ctx, ctx->budget, ctx->d_budget_own, L.budget)) return rc;
-    if (const int rc = zero_work(ctx, ctx->d_budget_total, 1)) return rc;
+    if (const int rc = zero_work(ctx, ctx->d_budget_total)) return rc;
     L.variance = var, L.counts = counts, L.acc = ctx->d_acc, L.object = object, L.albedo = demod ? albedo : nullptr;
     L.total = ctx->d_budget_total;
     L.width = ctx->width, L.height = ctx->height;
@@ -3517,7 +3446,7 @@ int srt_get_budget_total(srt_context* ctx, uint64_t* total) {
     if (!ctx || !total) return SRT_ERR_INVALID_ARG;
     if (srt::budget_check_total(ctx->adaptive) != srt::RAYS_OK) return fail(ctx, SRT_ERR_STATE, "srt_get_budget_total: there has been no srt_sample_budget");
     unsigned long long w = 0ull;
-    if (const int rc = read_work(ctx, ctx->d_budget_total, &w, 1)) return rc;
+    if (const int rc = read_work(ctx, ctx->d_budget_total, &w)) return rc;
     *total = w;
     return SRT_OK;
 }
@@ -3664,16 +3593,11 @@ int srt_probe_tail(srt_context* ctx, const srt_probe_tail_params* t) {
     return SRT_OK;
 }
 
+SRT_WORK_LAYOUT(srt_probe_tail_work, srt::PT_WORK_N, tails, srt::PT_WORK_TAILS, wave_lookups, srt::PT_WORK_WAVE_LOOKUPS);
 int srt_get_probe_tail_work(srt_context* ctx, srt_probe_tail_work* out) {
     if (!ctx || !out) return SRT_ERR_INVALID_ARG;
-    if (srt::probe_tail_check_work(ctx->probe_tail) != srt::RAYS_OK)
-        return fail(ctx, SRT_ERR_STATE, "srt_get_probe_tail_work: the last radiance or light-probe trace did not run under srt_probe_tail with SRT_PROBE_TAIL_COUNT_WORK (or there has been none)");
-    unsigned long long w[srt::PT_WORK_N];
-    if (const int rc = read_work(ctx, ctx->d_probe_tail_work, w, srt::PT_WORK_N)) return rc;
-    out->valid = 1, out->reserved = 0;
-    out->tails = w[srt::PT_WORK_TAILS], out->corners = w[srt::PT_WORK_CORNERS], out->open = w[srt::PT_WORK_OPEN], out->dark = w[srt::PT_WORK_DARK];
-    out->mirror_ends = w[srt::PT_WORK_MIRROR_ENDS], out->wave_lookups = w[srt::PT_WORK_WAVE_LOOKUPS];
-    return SRT_OK;
+    return get_work(ctx, ctx->probe_tail.last, ctx->d_probe_tail_work, out,
+                    "srt_get_probe_tail_work: the last radiance or light-probe trace did not run under srt_probe_tail with SRT_PROBE_TAIL_COUNT_WORK (or there has been none)");
 }
 
 // The reflection outputs srt_temporal_accumulate reads with the mirror history on (OBJECT, NORMAL_DEPTH, POSITION, BOUNCES), by
@@ -3849,9 +3773,7 @@ int srt_temporal_accumulate(srt_context* ctx, const srt_temporal_params* t) {
         hipLaunchKernelGGL(kernels[pick], grid, block, 0, ctx->stream, M);
     }
     else if (ctx->mom_on) {
-        void (*const kernel)(srt::TemporalLaunch) =
-            motion ? (ctx->mv_on ? srt::temporal_moments_kernel<true, true> : srt::temporal_moments_kernel<true, false>)
-                   : (ctx->mv_on ? srt::temporal_moments_kernel<false, true> : srt::temporal_moments_kernel<false, false>);
+        void (*const kernel)(srt::TemporalLaunch) = SRT_KERNEL(srt::temporal_moments_kernel, motion, ctx->mv_on);
         hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, T);
     }
     else if (!motion && !ctx->mv_on) hipLaunchKernelGGL(srt::temporal_kernel, grid, block, 0, ctx->stream, T);
@@ -4039,7 +3961,7 @@ int srt_render_subsamples(srt_context* ctx, const srt_subsample_params* g) {
     }
     srt::KernelParams K;
     const KernelSetup ks = scene_kernel_params(ctx, g->row_begin, g->row_end, K);
-    if (const int rc = launch_tiles(ctx, SRT_KERNEL_LDS_MESH(srt::subsample_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0), ks, K, out)) return rc;
+    if (const int rc = launch_tiles(ctx, SRT_KERNEL(srt::subsample_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0), ks, K, out)) return rc;
     ctx->ss.wrote(out.sub, (size_t)g->k);
     return SRT_OK;
 }

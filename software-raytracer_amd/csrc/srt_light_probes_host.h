@@ -1,8 +1,9 @@
 // srt_light_probes_host.h — host-side rules of the light probes (srt_write_light_probes, srt_bind_light_probes, the two
 // direction calls, srt_trace_light_probes, srt_bind_light_probe_output, srt_read_light_probe_output, srt_get_light_probe_work)
-// that need no device: which arrays are the current positions and directions, argument validation in the header's order, the
-// continuation rule (no RESET needs the RADIANCE output and a previous trace of the same P and K into the same buffer), the
-// record of what the last trace wrote and where, whether it counted, and the sizes of the launch: the units, the grid, the
+// that need no device: which arrays are the current positions and directions (srt_outputs_host.h's InputArray), argument
+// validation in the header's order, the continuation rule (no RESET needs the RADIANCE output and a previous trace of the same P
+// and K into the same buffer), the record of what the last trace wrote and where and whether it counted (LastOutputs,
+// CallRecord), and the sizes of the launch: the units, the grid, the
 // partial buffer of a multi-block projection and the sample scratch that goes with the grid.  The two pure-host entries
 // (srt_light_probe_sphere, srt_light_probe_irradiance) are here as well.  Plain C++ without HIP, shared by srt_capi.hip and by
 // tests/native/light_probe_check.cpp, which runs it under the address and undefined-behaviour sanitizers on the CPU.
@@ -36,34 +37,12 @@ inline void light_probe_call_default(LightProbeCall& c) {
 // slot of a single output bit, -1 for anything else
 inline int light_probe_slot(uint32_t output) { return output == LIGHT_PROBE_OUT_COEFFICIENTS ? 0 : output == LIGHT_PROBE_OUT_RADIANCE ? 1 : -1; }
 
-// One input array (the positions, or the directions): the caller's bound array, when there is one, comes first; the handle's
-// own buffer holds own_count elements (0: never written).
-struct LightProbeInput {
-    const void* bound = nullptr;
-    size_t bound_count = 0;
-    size_t own_count = 0;
-    size_t count() const { return bound ? bound_count : own_count; }  // 0: none
-};
-
-// srt_bind_light_probes / srt_bind_light_probe_directions: NULL, 0 returns to the own buffer; otherwise an array and a count in
-// 1 .. limit.  On an error the state is left as it was.
-inline RaysStatus light_probe_bind(LightProbeInput& in, const void* d_ptr, size_t count, size_t limit) {
-    if (!d_ptr && count == 0) return in.bound = nullptr, in.bound_count = 0, RAYS_OK;
-    if (!d_ptr || count < 1 || count > limit) return RAYS_INVALID_ARG;
-    in.bound = d_ptr, in.bound_count = count;
-    return RAYS_OK;
-}
-// srt_write_light_probes / srt_write_light_probe_directions once the copy has succeeded: a binding ends
-inline void light_probe_written(LightProbeInput& in, size_t count) { in.own_count = count, in.bound = nullptr, in.bound_count = 0; }
-
 struct LightProbeState {
-    LightProbeInput positions, directions;
+    InputArray positions, directions;
     // the last successful srt_trace_light_probes
-    bool traced = false;
-    bool counted = false;
+    CallRecord call;  // counted: it had SRT_LIGHT_PROBE_COUNT_WORK
     size_t last_probes = 0, last_directions = 0;
-    uint32_t last_outputs = 0;
-    const void* last_dst[LIGHT_PROBE_SLOTS] = {nullptr, nullptr};
+    LastOutputs<LIGHT_PROBE_SLOTS> last;
 };
 
 // direction blocks of 64 per probe, and the units (probe, block) of a launch
@@ -103,8 +82,7 @@ inline RaysStatus light_probe_check_trace(const LightProbeState& s, bool scene_s
     if (P > LIGHT_PROBE_MAX_RAYS || P * K > LIGHT_PROBE_MAX_RAYS) return *why = "probes x directions exceeds 2^30", RAYS_INVALID_ARG;
     if (!(c.flags & LIGHT_PROBE_FLAG_RESET)) {
         if (!(c.outputs & LIGHT_PROBE_OUT_RADIANCE)) return *why = "continuing the means (no SRT_LIGHT_PROBE_RESET) needs the RADIANCE output", RAYS_STATE;
-        if (!s.traced || !(s.last_outputs & LIGHT_PROBE_OUT_RADIANCE) || !radiance_target || s.last_dst[1] != radiance_target || s.last_probes != P ||
-            s.last_directions != K)
+        if (!radiance_target || s.last.read(LIGHT_PROBE_OUT_RADIANCE, 1) != radiance_target || s.last_probes != P || s.last_directions != K)
             return *why = "continuing the means (no SRT_LIGHT_PROBE_RESET) needs a previous trace of the same probe and direction counts into the current RADIANCE buffer",
                    RAYS_STATE;
     }
@@ -113,30 +91,10 @@ inline RaysStatus light_probe_check_trace(const LightProbeState& s, bool scene_s
 
 // srt_trace_light_probes once the launch is enqueued: dst[slot] is where each requested output went.
 inline void light_probe_traced(LightProbeState& s, size_t probes, size_t directions, uint32_t outputs, void* const dst[LIGHT_PROBE_SLOTS], uint32_t flags) {
-    s.traced = true;
-    s.counted = (flags & LIGHT_PROBE_FLAG_COUNT_WORK) != 0;
+    s.call.done((flags & LIGHT_PROBE_FLAG_COUNT_WORK) != 0);
     s.last_probes = probes, s.last_directions = directions;
-    s.last_outputs = outputs;
-    for (int i = 0; i < LIGHT_PROBE_SLOTS; ++i) s.last_dst[i] = (outputs & (1u << i)) ? dst[i] : nullptr;
+    s.last.wrote(outputs, dst);
 }
-
-// The handle's own buffer of output `slot`, at `own`, is about to be re-allocated: the last trace's copy of that output goes with it.
-inline void light_probe_output_released(LightProbeState& s, int slot, const void* own) {
-    if (own && s.last_dst[slot] == own) s.last_dst[slot] = nullptr, s.last_outputs &= ~(1u << slot);
-}
-
-// srt_read_light_probe_output: the buffer and byte count to copy, or why not.
-inline RaysStatus light_probe_check_read(const LightProbeState& s, uint32_t output, const void** src, size_t* bytes) {
-    const int i = light_probe_slot(output);
-    if (i < 0) return RAYS_INVALID_ARG;
-    if (!s.traced || !(s.last_outputs & output) || !s.last_dst[i]) return RAYS_STATE;
-    *src = s.last_dst[i];
-    *bytes = light_probe_elems(i, s.last_probes, s.last_directions) * (4 * sizeof(float));
-    return RAYS_OK;
-}
-
-// srt_get_light_probe_work: only the record of a last trace that counted
-inline RaysStatus light_probe_check_work(const LightProbeState& s) { return s.traced && s.counted ? RAYS_OK : RAYS_STATE; }
 
 // srt_light_probe_sphere: the spherical Fibonacci set, computed in double and rounded once to binary32.
 inline void light_probe_sphere(size_t count, float* dst) {

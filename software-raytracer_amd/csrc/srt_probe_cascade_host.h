@@ -39,9 +39,8 @@ struct ProbeCascadeCall {
 struct ProbeCascadeState {
     bool set = false;
     ProbeCascade cascade{};
-    LightProbeInput arrays[PROBE_CASCADE_MAX_LEVELS][PROBE_CASCADE_ARRAYS];  // counted in probes
-    bool shaded = false;   // there has been an srt_shade_probe_cascade
-    bool counted = false;  // ... and the last one had SRT_PROBE_CASCADE_COUNT_WORK
+    InputArray arrays[PROBE_CASCADE_MAX_LEVELS][PROBE_CASCADE_ARRAYS];  // counted in probes
+    CallRecord call;  // the last srt_shade_probe_cascade; counted: it had SRT_PROBE_CASCADE_COUNT_WORK
 };
 
 inline void probe_cascade_call_default(ProbeCascadeCall& c) {
@@ -86,7 +85,7 @@ inline RaysStatus probe_cascade_set(ProbeCascadeState& s, const ProbeCascade& c,
         const bool was = s.set && l < s.cascade.levels, is = l < c.levels;
         const bool same = was && is && probe_grid_probes(s.cascade.grid[l]) == probe_grid_probes(c.grid[l]);
         for (int i = 0; i < PROBE_CASCADE_ARRAYS; ++i)
-            if (!same || (i == 1 && s.cascade.resolution != c.resolution)) s.arrays[l][i] = LightProbeInput{};
+            if (!same || (i == 1 && s.cascade.resolution != c.resolution)) s.arrays[l][i] = InputArray{};
     }
     s.cascade = c, s.set = true;
     for (uint32_t l = c.levels; l < PROBE_CASCADE_MAX_LEVELS; ++l) s.cascade.grid[l] = ProbeGrid{};  // (entries >= levels are ignored)
@@ -180,10 +179,7 @@ inline RaysStatus probe_cascade_check_shade(const ProbeCascadeState& s, const Pr
 }
 
 // srt_shade_probe_cascade once the launch is enqueued
-inline void probe_cascade_shaded(ProbeCascadeState& s, uint32_t flags) { s.shaded = true, s.counted = (flags & PROBE_CASCADE_FLAG_COUNT_WORK) != 0; }
-
-// srt_get_probe_cascade_work: only the record of a last call that counted
-inline RaysStatus probe_cascade_check_work(const ProbeCascadeState& s) { return s.shaded && s.counted ? RAYS_OK : RAYS_STATE; }
+inline void probe_cascade_shaded(ProbeCascadeState& s, uint32_t flags) { s.call.done((flags & PROBE_CASCADE_FLAG_COUNT_WORK) != 0); }
 
 // srt_probe_cascade_grids: level l has the given counts and spacing_a = ldexpf(base_spacing_a, l); its origin is snapped to whole
 // cells of its own spacing: k = floorf(centre_a / spacing_a), clamped to +-1048576, a NaN gives 0;

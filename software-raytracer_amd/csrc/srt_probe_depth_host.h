@@ -67,12 +67,10 @@ inline void probe_depth_texels(uint32_t R, float* dst) {
 
 struct ProbeDepthState {
     // the last successful srt_trace_probe_depth
-    bool traced = false;
-    bool counted = false;
+    CallRecord call;  // counted: it had SRT_PROBE_DEPTH_COUNT_WORK
     size_t last_probes = 0, last_directions = 0;
     uint32_t last_resolution = 0;
-    uint32_t last_outputs = 0;
-    const void* last_dst[PROBE_DEPTH_SLOTS] = {nullptr, nullptr};
+    LastOutputs<PROBE_DEPTH_SLOTS> last;
 };
 
 // srt_trace_probe_depth's checks in the header's order (rule 7): the scene, the arguments, the inputs, the sizes; touches nothing.
@@ -96,37 +94,17 @@ inline RaysStatus probe_depth_check_trace(const LightProbeState& in, bool scene_
 
 // srt_trace_probe_depth once the launch is enqueued: dst[slot] is where each requested output went.
 inline void probe_depth_traced(ProbeDepthState& s, size_t probes, size_t directions, const ProbeDepthCall& c, void* const dst[PROBE_DEPTH_SLOTS]) {
-    s.traced = true;
-    s.counted = (c.flags & PROBE_DEPTH_FLAG_COUNT_WORK) != 0;
+    s.call.done((c.flags & PROBE_DEPTH_FLAG_COUNT_WORK) != 0);
     s.last_probes = probes, s.last_directions = directions, s.last_resolution = c.resolution;
-    s.last_outputs = c.outputs;
-    for (int i = 0; i < PROBE_DEPTH_SLOTS; ++i) s.last_dst[i] = (c.outputs & (1u << i)) ? dst[i] : nullptr;
+    s.last.wrote(c.outputs, dst);
 }
-
-// The handle's own buffer of output `slot`, at `own`, is about to be re-allocated: the last trace's copy of that output goes with it.
-inline void probe_depth_output_released(ProbeDepthState& s, int slot, const void* own) {
-    if (own && s.last_dst[slot] == own) s.last_dst[slot] = nullptr, s.last_outputs &= ~(1u << slot);
-}
-
-// srt_read_probe_depth_output: the buffer and byte count to copy, or why not.
-inline RaysStatus probe_depth_check_read(const ProbeDepthState& s, uint32_t output, const void** src, size_t* bytes) {
-    const int i = probe_depth_slot(output);
-    if (i < 0) return RAYS_INVALID_ARG;
-    if (!s.traced || !(s.last_outputs & output) || !s.last_dst[i]) return RAYS_STATE;
-    *src = s.last_dst[i];
-    *bytes = probe_depth_bytes(i, s.last_probes, s.last_directions, s.last_resolution);
-    return RAYS_OK;
-}
-
-// srt_get_probe_depth_work: only the record of a last trace that counted
-inline RaysStatus probe_depth_check_work(const ProbeDepthState& s) { return s.traced && s.counted ? RAYS_OK : RAYS_STATE; }
 
 // The grid: one wave per probe, persistent workgroups of `waves` waves, at most `resident`.
 inline unsigned probe_depth_grid(size_t probes, int waves, long long resident) { return persistent_grid((long long)probes, waves, resident); }
 
 // ---- the moments srt_shade_probe_grid_depth reads: counted in probes, R*R float4 each --------------------------------------------
 struct ProbeGridDepthState {
-    LightProbeInput moments;
+    InputArray moments;
     uint32_t bound_resolution = 0, own_resolution = 0;
     uint32_t resolution() const { return moments.bound ? bound_resolution : own_resolution; }
 };
@@ -146,7 +124,7 @@ inline RaysStatus probe_grid_depth_bind(ProbeGridDepthState& s, const void* d_pt
 }
 // srt_write_probe_grid_depth once the copy has succeeded: a binding ends
 inline void probe_grid_depth_written(ProbeGridDepthState& s, size_t probes, uint32_t resolution) {
-    light_probe_written(s.moments, probes);
+    input_written(s.moments, probes);
     s.own_resolution = resolution, s.bound_resolution = 0;
 }
 

@@ -34,9 +34,8 @@ struct ProbeGridCall {
 struct ProbeGridState {
     bool grid_set = false;
     ProbeGrid grid{};
-    LightProbeInput coefficients;  // counted in probes (nine float4 each)
-    bool shaded = false;           // there has been an srt_shade_probe_grid
-    bool counted = false;          // ... and the last one had SRT_PROBE_GRID_COUNT_WORK
+    InputArray coefficients;  // counted in probes (nine float4 each)
+    CallRecord call;          // the last srt_shade_probe_grid[_depth|_states]; counted: it had SRT_PROBE_GRID_COUNT_WORK
 };
 
 inline void probe_grid_call_default(ProbeGridCall& c) {
@@ -103,9 +102,6 @@ inline RaysStatus probe_grid_check_shade(const ProbeGridState& s, const ProbeGri
 }
 
 // srt_shade_probe_grid once the launch is enqueued
-inline void probe_grid_shaded(ProbeGridState& s, uint32_t flags) { s.shaded = true, s.counted = (flags & PROBE_GRID_FLAG_COUNT_WORK) != 0; }
-
-// srt_get_probe_grid_work: only the record of a last call that counted
-inline RaysStatus probe_grid_check_work(const ProbeGridState& s) { return s.shaded && s.counted ? RAYS_OK : RAYS_STATE; }
+inline void probe_grid_shaded(ProbeGridState& s, uint32_t flags) { s.call.done((flags & PROBE_GRID_FLAG_COUNT_WORK) != 0); }
 
 }  // namespace srt

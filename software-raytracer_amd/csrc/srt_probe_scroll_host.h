@@ -29,11 +29,6 @@ inline void probe_scroll_call_default(ProbeScrollCall& c) {
     c.reserved[0] = c.reserved[1] = c.reserved[2] = 0;
 }
 
-struct ProbeScrollState {
-    bool scrolled = false;  // there has been an srt_scroll_probes
-    bool counted = false;   // ... and the last one had SRT_PROBE_SCROLL_COUNT_WORK
-};
-
 inline bool probe_scroll_shift_is_zero(const int32_t shift[3]) { return shift[0] == 0 && shift[1] == 0 && shift[2] == 0; }
 
 // Rule SC1 on one axis: the source coordinate j = i + shift in 64 bits; true (and *j) when 0 <= j < n.
@@ -128,12 +123,12 @@ inline RaysStatus probe_scroll_check(const ProbeGridState& g, const ProbeUpdateS
 // Rule SC5: a scroll with a non-zero shift is enqueued — what the last light-probe trace wrote as COEFFICIENTS and the last depth
 // trace as MOMENTS is indexed by the old grid, and counts as not written.
 inline void probe_scroll_stale(LightProbeState& lp, ProbeDepthState& pd) {
-    lp.last_dst[0] = nullptr, lp.last_outputs &= ~LIGHT_PROBE_OUT_COEFFICIENTS;
-    pd.last_dst[0] = nullptr, pd.last_outputs &= ~PROBE_DEPTH_OUT_MOMENTS;
+    lp.last.forget(0);  // (light_probe_slot(LIGHT_PROBE_OUT_COEFFICIENTS))
+    pd.last.forget(0);  // (probe_depth_slot(PROBE_DEPTH_OUT_MOMENTS))
 }
 
-inline void probe_scroll_scrolled(ProbeScrollState& s, uint32_t flags) { s.scrolled = true, s.counted = (flags & PROBE_SCROLL_FLAG_COUNT_WORK) != 0; }
-inline RaysStatus probe_scroll_check_work(const ProbeScrollState& s) { return s.scrolled && s.counted ? RAYS_OK : RAYS_STATE; }
+// srt_scroll_probes once the launch is enqueued.  `s`: what srt_get_probe_scroll_work may report.
+inline void probe_scroll_scrolled(CallRecord& s, uint32_t flags) { s.done((flags & PROBE_SCROLL_FLAG_COUNT_WORK) != 0); }
 
 // The scroll's grid: one wave per destination probe, persistent workgroups of `waves` waves, at most `resident`.
 inline unsigned probe_scroll_grid(size_t probes, int waves, long long resident) { return persistent_grid((long long)probes, waves, resident); }

@@ -71,13 +71,11 @@ inline size_t probe_state_bytes(size_t probes) { return probes * (4 * sizeof(flo
 
 struct ProbeStatesState {
     // the last successful srt_classify_probes
-    bool classified = false;
-    bool counted = false;
+    CallRecord call;  // counted: it had SRT_PROBE_CLASSIFY_COUNT_WORK
     size_t last_probes = 0;
-    uint32_t last_outputs = 0;
-    const void* last_dst[PROBE_STATE_SLOTS] = {nullptr, nullptr};
+    LastOutputs<PROBE_STATE_SLOTS> last;
     // the records srt_shade_probe_grid_states reads, counted in probes
-    LightProbeInput states;
+    InputArray states;
 };
 
 // srt_classify_probes' checks in the header's order (rule S9): the scene, the arguments, the inputs; touches nothing.
@@ -100,29 +98,10 @@ inline RaysStatus probe_classify_check(const ProbeGridState& g, size_t direction
 
 // srt_classify_probes once the launch is enqueued: dst[slot] is where each requested output went.
 inline void probe_states_classified(ProbeStatesState& s, size_t probes, const ProbeClassifyCall& c, void* const dst[PROBE_STATE_SLOTS]) {
-    s.classified = true;
-    s.counted = (c.flags & PROBE_CLASSIFY_FLAG_COUNT_WORK) != 0;
-    s.last_probes = probes, s.last_outputs = c.outputs;
-    for (int i = 0; i < PROBE_STATE_SLOTS; ++i) s.last_dst[i] = (c.outputs & (1u << i)) ? dst[i] : nullptr;
+    s.call.done((c.flags & PROBE_CLASSIFY_FLAG_COUNT_WORK) != 0);
+    s.last_probes = probes;
+    s.last.wrote(c.outputs, dst);
 }
-
-// The handle's own buffer of output `slot`, at `own`, is about to be re-allocated: the last call's copy of that output goes with it.
-inline void probe_states_output_released(ProbeStatesState& s, int slot, const void* own) {
-    if (own && s.last_dst[slot] == own) s.last_dst[slot] = nullptr, s.last_outputs &= ~(1u << slot);
-}
-
-// srt_read_probe_states_output: the buffer and byte count to copy, or why not.
-inline RaysStatus probe_states_check_read(const ProbeStatesState& s, uint32_t output, const void** src, size_t* bytes) {
-    const int i = probe_state_slot(output);
-    if (i < 0) return RAYS_INVALID_ARG;
-    if (!s.classified || !(s.last_outputs & output) || !s.last_dst[i]) return RAYS_STATE;
-    *src = s.last_dst[i];
-    *bytes = probe_state_bytes(s.last_probes);
-    return RAYS_OK;
-}
-
-// srt_get_probe_classify_work: only the record of a last call that counted
-inline RaysStatus probe_states_check_work(const ProbeStatesState& s) { return s.classified && s.counted ? RAYS_OK : RAYS_STATE; }
 
 // The grid: one wave per probe, persistent workgroups of `waves` waves, at most `resident`.
 inline unsigned probe_classify_grid(size_t probes, int waves, long long resident) { return persistent_grid((long long)probes, waves, resident); }

@@ -28,8 +28,7 @@ struct ProbeTailCall {
 struct ProbeTailState {
     bool enabled = false;
     ProbeTailCall call{0, 0u, {1.0f, 0.5f, 0.0f}, 0.0f, 1e-4f, 0u};
-    bool traced = false;   // the last srt_trace_radiance / srt_trace_light_probes[_listed] ran with the mode on
-    bool counted = false;  // ... and with SRT_PROBE_TAIL_COUNT_WORK
+    CallRecord last;  // ran: the last affected trace ran with the mode ON; counted: ... and with SRT_PROBE_TAIL_COUNT_WORK
 };
 
 // the defaults of srt_probe_tail_params_default: on, no flags, the hemisphere mean of probe-grid rule 10, rule 7b's defaults
@@ -94,11 +93,8 @@ inline RaysStatus probe_tail_check_trace(const ProbeTailState& s, const ProbeGri
 // an affected trace once its launch is enqueued.  True when the mode is on and counts: the record is this trace's (all zeros when
 // max_bounces == 0 kept the mode from applying: the caller zeroes it).
 inline bool probe_tail_traced(ProbeTailState& s) {
-    s.traced = s.enabled, s.counted = s.enabled && (s.call.flags & PROBE_TAIL_FLAG_COUNT_WORK) != 0;
-    return s.counted;
+    s.last = CallRecord{s.enabled, s.enabled && (s.call.flags & PROBE_TAIL_FLAG_COUNT_WORK) != 0};
+    return s.last.counted;
 }
-
-// srt_get_probe_tail_work: only the record of a last affected trace that ran with the mode on and counted
-inline RaysStatus probe_tail_check_work(const ProbeTailState& s) { return s.traced && s.counted ? RAYS_OK : RAYS_STATE; }
 
 }  // namespace srt

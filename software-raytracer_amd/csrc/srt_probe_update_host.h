@@ -59,19 +59,17 @@ struct ProbeHistory {
 
 struct ProbeUpdateState {
     // the last successful srt_list_probes
-    bool listed = false;
-    bool list_counted = false;
+    CallRecord list_call;  // counted: it had SRT_PROBE_LIST_COUNT_WORK
     size_t list_probes = 0;
-    const void* list_dst = nullptr;
+    LastOutputs<1> list_last;              // (one output: bit 1, slot 0)
     const void* list_out_bound = nullptr;  // srt_bind_probe_list_output; NULL: the handle's own buffer
     // the list the listed traces and a listed blend read, counted in words
-    LightProbeInput list;
+    InputArray list;
     // the records a blend with PREVIOUS_STATES compares the current ones with, counted in probes
-    LightProbeInput previous;
+    InputArray previous;
     ProbeHistory history[PROBE_HISTORY_SLOTS];
     // the last successful srt_blend_probes
-    bool blended = false;
-    bool blend_counted = false;
+    CallRecord blend_call;  // counted: it had SRT_PROBE_BLEND_COUNT_WORK
 };
 
 // srt_list_probes' checks in the header's order: the scene, the arguments, the inputs; touches nothing.
@@ -91,28 +89,15 @@ inline RaysStatus probe_list_check(const ProbeGridState& g, const ProbeStatesSta
 
 // srt_list_probes once the launch is enqueued
 inline void probe_list_listed(ProbeUpdateState& s, size_t probes, uint32_t flags, const void* dst) {
-    s.listed = true, s.list_counted = (flags & PROBE_LIST_FLAG_COUNT_WORK) != 0, s.list_probes = probes, s.list_dst = dst;
+    s.list_call.done((flags & PROBE_LIST_FLAG_COUNT_WORK) != 0), s.list_probes = probes, s.list_last.wrote(1u, &dst);
 }
-// The handle's own list output, at `own`, is about to be re-allocated: the last listing's copy goes with it.
-inline void probe_list_output_released(ProbeUpdateState& s, const void* own) {
-    if (own && s.list_dst == own) s.list_dst = nullptr;
-}
-// srt_read_probe_list_output: the buffer and byte count to copy, or why not.
-inline RaysStatus probe_list_check_read(const ProbeUpdateState& s, const void** src, size_t* bytes) {
-    if (!s.listed || !s.list_dst) return RAYS_STATE;
-    *src = s.list_dst, *bytes = probe_list_bytes(s.list_probes);
-    return RAYS_OK;
-}
-inline RaysStatus probe_list_check_work(const ProbeUpdateState& s) { return s.listed && s.list_counted ? RAYS_OK : RAYS_STATE; }
 
 // srt_write_probe_list, srt_bind_probe_list: is `capacity` words a list?  4 + P, P in 1 .. 2^30.
 inline bool probe_list_capacity_ok(size_t capacity) { return capacity > PROBE_LIST_HEADER && capacity - PROBE_LIST_HEADER <= PROBE_LIST_MAX_PROBES; }
 // srt_bind_probe_list: NULL, 0 unbinds; otherwise a device array and its capacity.  On an error the state is left as it was.
 inline RaysStatus probe_list_bind(ProbeUpdateState& s, const void* d_list, size_t capacity) {
-    if (!d_list && capacity == 0) return s.list.bound = nullptr, s.list.bound_count = 0, RAYS_OK;
-    if (!d_list || !probe_list_capacity_ok(capacity)) return RAYS_INVALID_ARG;
-    s.list.bound = d_list, s.list.bound_count = capacity;
-    return RAYS_OK;
+    if (d_list && !probe_list_capacity_ok(capacity)) return RAYS_INVALID_ARG;
+    return input_bind(s.list, d_list, capacity, PROBE_LIST_HEADER + PROBE_LIST_MAX_PROBES);
 }
 
 // The listed traces, after all of the parent call's checks: a list of 4 + P words for the current positions' P.
@@ -157,14 +142,14 @@ inline RaysStatus probe_blend_check(const ProbeUpdateState& s, const LightProbeS
     const ProbeHistory& hc = s.history[0];
     if (!hc.reset) return *why = "no coefficient history (srt_reset_probe_history)", RAYS_STATE;
     const size_t P = hc.probes;
-    if (!lp.traced || !(lp.last_outputs & LIGHT_PROBE_OUT_COEFFICIENTS) || !lp.last_dst[0])
+    if (!lp.last.read(LIGHT_PROBE_OUT_COEFFICIENTS, 0))
         return *why = "the last srt_trace_light_probes did not write COEFFICIENTS", RAYS_STATE;
     if (lp.last_probes != P) return *why = "the last srt_trace_light_probes wrote COEFFICIENTS for another probe count than the history's", RAYS_STATE;
     if (c.flags & PROBE_BLEND_FLAG_MOMENTS) {
         const ProbeHistory& hm = s.history[1];
         if (!hm.reset) return *why = "no moment history (srt_reset_probe_history)", RAYS_STATE;
         if (hm.probes != P) return *why = "the two histories stand for different probe counts", RAYS_STATE;
-        if (!pd.traced || !(pd.last_outputs & PROBE_DEPTH_OUT_MOMENTS) || !pd.last_dst[0]) return *why = "the last srt_trace_probe_depth did not write MOMENTS", RAYS_STATE;
+        if (!pd.last.read(PROBE_DEPTH_OUT_MOMENTS, 0)) return *why = "the last srt_trace_probe_depth did not write MOMENTS", RAYS_STATE;
         if (pd.last_probes != P || pd.last_resolution != hm.resolution)
             return *why = "the last srt_trace_probe_depth wrote MOMENTS for another probe count or resolution than the history's", RAYS_STATE;
     }
@@ -178,8 +163,7 @@ inline RaysStatus probe_blend_check(const ProbeUpdateState& s, const LightProbeS
     }
     return RAYS_OK;
 }
-inline void probe_blend_blended(ProbeUpdateState& s, uint32_t flags) { s.blended = true, s.blend_counted = (flags & PROBE_BLEND_FLAG_COUNT_WORK) != 0; }
-inline RaysStatus probe_blend_check_work(const ProbeUpdateState& s) { return s.blended && s.blend_counted ? RAYS_OK : RAYS_STATE; }
+inline void probe_blend_blended(ProbeUpdateState& s, uint32_t flags) { s.blend_call.done((flags & PROBE_BLEND_FLAG_COUNT_WORK) != 0); }
 
 // srt_read_probe_history: only a history that has a size
 inline RaysStatus probe_history_check_read(const ProbeUpdateState& s, uint32_t which, int* slot, size_t* bytes) {

@@ -24,10 +24,9 @@ struct RadianceCall {
 
 // what the last successful srt_trace_radiance left behind
 struct RadianceState {
-    bool traced = false;   // there has been an srt_trace_radiance
-    bool counted = false;  // ... and the last one had SRT_RADIANCE_COUNT_WORK
+    CallRecord call;  // counted: it had SRT_RADIANCE_COUNT_WORK
     size_t last_count = 0;
-    const void* last_dst = nullptr;
+    LastOutputs<1> last;  // (one output: bit 1, slot 0)
 };
 
 inline void radiance_call_default(RadianceCall& c) {
@@ -51,27 +50,10 @@ inline RaysStatus radiance_check_trace(const RaysState& s, bool scene_set, const
 
 // srt_trace_radiance once the launch is enqueued: `count` float4 went to `dst`.
 inline void radiance_traced(RadianceState& r, size_t count, const void* dst, uint32_t flags) {
-    r.traced = true;
-    r.counted = (flags & RADIANCE_FLAG_COUNT_WORK) != 0;
+    r.call.done((flags & RADIANCE_FLAG_COUNT_WORK) != 0);
     r.last_count = count;
-    r.last_dst = dst;
+    r.last.wrote(1u, &dst);
 }
-
-// The handle's own radiance buffer, at `own`, is about to be re-allocated for a larger batch: the last trace's result goes with it.
-inline void radiance_output_released(RadianceState& r, const void* own) {
-    if (own && r.last_dst == own) r.last_dst = nullptr;
-}
-
-// srt_read_radiance: the buffer and byte count to copy, or SRT_ERR_STATE.
-inline RaysStatus radiance_check_read(const RadianceState& r, const void** src, size_t* bytes) {
-    if (!r.traced || !r.last_dst || r.last_count == 0) return RAYS_STATE;
-    *src = r.last_dst;
-    *bytes = r.last_count * 4 * sizeof(float);
-    return RAYS_OK;
-}
-
-// srt_get_radiance_work: only the record of a last radiance trace that counted
-inline RaysStatus radiance_check_work(const RadianceState& r) { return r.traced && r.counted ? RAYS_OK : RAYS_STATE; }
 
 // The grid: rays_kernel's — persistent workgroups of `waves` waves over blocks of 64 rays, at most `resident`.
 inline unsigned radiance_grid(size_t count, int waves, long long resident) { return rays_grid(count, waves, resident); }

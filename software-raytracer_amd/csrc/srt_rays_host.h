@@ -1,6 +1,6 @@
 // srt_rays_host.h — host-side rules of the ray queries (srt_write_rays, srt_bind_rays, srt_bind_ray_output, srt_trace_rays,
 // srt_read_ray_output) that need no device: argument validation, which arrays are the current rays, element sizes, and the
-// record of what the last trace wrote.  Plain C++ without HIP, shared by srt_capi.hip and by tests/native/rays_check.cpp,
+// record of what the last trace wrote (srt_outputs_host.h's LastOutputs, with the ray count that sizes a read).  Plain C++ without HIP, shared by srt_capi.hip and by tests/native/rays_check.cpp,
 // which runs it under the address and undefined-behaviour sanitizers on the CPU.
 #pragma once
 
@@ -17,8 +17,6 @@ constexpr uint32_t RAYS_FLAG_NORMALIZE = 1u, RAYS_FLAG_ALL = 1u;
 constexpr int RAYS_SLOTS = 5;
 constexpr size_t RAYS_MAX_COUNT = (size_t)1 << 30;
 
-enum RaysStatus { RAYS_OK = 0, RAYS_INVALID_ARG = 1, RAYS_STATE = 4 };  // the values of SRT_OK / SRT_ERR_INVALID_ARG / SRT_ERR_STATE
-
 // slot of a single output bit, -1 for anything else (no bit, several bits, an unknown bit)
 inline int rays_slot(uint32_t output) {
     switch (output) {
@@ -34,39 +32,30 @@ inline int rays_slot(uint32_t output) {
 inline size_t rays_elem_bytes(int slot) { return slot == 0 || slot == 4 ? sizeof(int32_t) : 4 * sizeof(float); }
 inline bool rays_count_ok(size_t count) { return count >= 1 && count <= RAYS_MAX_COUNT; }
 
-// Which arrays are the current rays.  The handle's own buffers hold own_count rays (0: never written); the caller's bound
-// arrays, when there are any, come first.
+// Which arrays are the current rays.  The handle's own buffers hold origins.own_count rays (0: never written); the caller's
+// bound arrays, when there are any, come first.
 struct RaysState {
-    const void* bound_origin = nullptr;
-    const void* bound_direction = nullptr;
-    size_t bound_count = 0;
-    size_t own_count = 0;
+    InputArray origins;                     // the origins, and the one count of both arrays
+    const void* bound_direction = nullptr;  // the directions bound with origins.bound
     // the last trace: how many rays, which outputs, and the buffer each was written to (srt_read_ray_output reads no other)
     size_t last_count = 0;
-    uint32_t last_outputs = 0;
-    const void* last_dst[RAYS_SLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    LastOutputs<RAYS_SLOTS> last;
 
-    bool bound() const { return bound_origin != nullptr; }
-    size_t count() const { return bound() ? bound_count : own_count; }  // 0: no current rays
+    bool bound() const { return origins.bound != nullptr; }
+    size_t count() const { return origins.count(); }  // 0: no current rays
 };
 
 // srt_bind_rays: NULL, NULL, 0 returns to the own buffers; otherwise both arrays and a count in range.  On an error the state
 // is left as it was.
 inline RaysStatus rays_bind(RaysState& s, const void* d_origins, const void* d_directions, size_t count) {
-    if (!d_origins && !d_directions && count == 0) {
-        s.bound_origin = s.bound_direction = nullptr, s.bound_count = 0;
-        return RAYS_OK;
-    }
-    if (!d_origins || !d_directions || !rays_count_ok(count)) return RAYS_INVALID_ARG;
-    s.bound_origin = d_origins, s.bound_direction = d_directions, s.bound_count = count;
+    if (!d_origins && !d_directions && count == 0) return s.bound_direction = nullptr, input_bind(s.origins, nullptr, 0, RAYS_MAX_COUNT);
+    if (!d_origins || !d_directions || input_bind(s.origins, d_origins, count, RAYS_MAX_COUNT) != RAYS_OK) return RAYS_INVALID_ARG;
+    s.bound_direction = d_directions;
     return RAYS_OK;
 }
 
 // srt_write_rays once the copy has succeeded: the own buffers hold `count` rays and are the current ones.
-inline void rays_written(RaysState& s, size_t count) {
-    s.own_count = count;
-    s.bound_origin = s.bound_direction = nullptr, s.bound_count = 0;
-}
+inline void rays_written(RaysState& s, size_t count) { input_written(s.origins, count), s.bound_direction = nullptr; }
 
 // srt_trace_rays' checks, in the order the header gives them; touches nothing.
 inline RaysStatus rays_check_trace(const RaysState& s, bool scene_set, uint32_t outputs, uint32_t flags, const char** why) {
@@ -81,27 +70,7 @@ inline RaysStatus rays_check_trace(const RaysState& s, bool scene_set, uint32_t 
 }
 
 // srt_trace_rays once the launch is enqueued: dst[slot] is where each requested output goes.
-inline void rays_traced(RaysState& s, uint32_t outputs, void* const dst[RAYS_SLOTS]) {
-    s.last_count = s.count();
-    s.last_outputs = outputs;
-    for (int i = 0; i < RAYS_SLOTS; ++i) s.last_dst[i] = (outputs & (1u << i)) ? dst[i] : nullptr;
-}
-
-// The handle's own buffer of output `slot`, at `own`, is about to be re-allocated for a larger batch: the last trace's copy of that
-// output goes with it.
-inline void rays_output_released(RaysState& s, int slot, const void* own) {
-    if (own && s.last_dst[slot] == own) s.last_dst[slot] = nullptr, s.last_outputs &= ~(1u << slot);
-}
-
-// srt_read_ray_output: the buffer and byte count to copy, or why not.
-inline RaysStatus rays_check_read(const RaysState& s, uint32_t output, const void** src, size_t* bytes) {
-    const int i = rays_slot(output);
-    if (i < 0) return RAYS_INVALID_ARG;
-    if (!(s.last_outputs & output) || !s.last_dst[i] || s.last_count == 0) return RAYS_STATE;
-    *src = s.last_dst[i];
-    *bytes = s.last_count * rays_elem_bytes(i);
-    return RAYS_OK;
-}
+inline void rays_traced(RaysState& s, uint32_t outputs, void* const dst[RAYS_SLOTS]) { s.last_count = s.count(), s.last.wrote(outputs, dst); }
 
 // Persistent workgroups of `waves` waves for `count` rays in blocks of 64: as many as there are blocks for, at most `resident`.
 inline unsigned rays_grid(size_t count, int waves, long long resident) { return persistent_grid((long long)((count + 63) / 64), waves, resident); }

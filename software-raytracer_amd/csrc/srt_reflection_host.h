@@ -24,12 +24,6 @@ struct ReflectionCall {
     uint32_t reserved;
 };
 
-// what the last successful srt_render_reflection_gbuffer left behind
-struct ReflectionState {
-    bool rendered = false;  // there has been an srt_render_reflection_gbuffer
-    bool counted = false;   // ... and the last one had SRT_REFL_COUNT_WORK
-};
-
 // the five outputs: the handle's own buffers are the caller's business (srt_capi.hip); the slots say which buffer is current
 struct ReflectionSlots {
     OutputSlot out[REFL_SLOTS];
@@ -68,10 +62,10 @@ inline RaysStatus reflection_check(const ReflectionCall& r, bool scene_set, bool
     return RAYS_OK;
 }
 
-// srt_render_reflection_gbuffer once the launch is enqueued: it wrote `outputs`, output of slot i to dst[i]
-inline void reflection_rendered(ReflectionState& s, ReflectionSlots& slots, uint32_t outputs, void* const dst[REFL_SLOTS], uint32_t flags) {
-    s.rendered = true;
-    s.counted = (flags & REFL_FLAG_COUNT_WORK) != 0;
+// srt_render_reflection_gbuffer once the launch is enqueued: it wrote `outputs`, output of slot i to dst[i].  `s`: what
+// srt_get_reflection_work may report — only the record of a last call with SRT_REFL_COUNT_WORK.
+inline void reflection_rendered(CallRecord& s, ReflectionSlots& slots, uint32_t outputs, void* const dst[REFL_SLOTS], uint32_t flags) {
+    s.done((flags & REFL_FLAG_COUNT_WORK) != 0);
     for (int i = 0; i < REFL_SLOTS; ++i)
         if (outputs & (1u << i)) slots.out[i].wrote(dst[i]);
 }
@@ -86,8 +80,5 @@ inline RaysStatus reflection_check_read(const ReflectionSlots& slots, uint32_t o
     *src = c;
     return RAYS_OK;
 }
-
-// srt_get_reflection_work: only the record of a last call that counted
-inline RaysStatus reflection_check_work(const ReflectionState& s) { return s.rendered && s.counted ? RAYS_OK : RAYS_STATE; }
 
 }  // namespace srt

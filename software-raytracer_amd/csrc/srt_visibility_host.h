@@ -1,7 +1,7 @@
 // srt_visibility_host.h — host-side rules of the per-pixel visibility pass (srt_render_visibility, srt_bind_visibility,
 // srt_read_visibility, srt_get_visibility_work) that need no device: argument validation in the header's order, the record of
 // which outputs the last call wrote to which buffers (srt_read_visibility reads no other), and when the work record may be
-// read.  Plain C++ without HIP, shared by srt_capi.hip and by tests/native/visibility_check.cpp, which runs it under the
+// read (srt_outputs_host.h's LastOutputs and CallRecord).  Plain C++ without HIP, shared by srt_capi.hip and by tests/native/visibility_check.cpp, which runs it under the
 // address and undefined-behaviour sanitizers on the CPU.
 #pragma once
 
@@ -25,10 +25,8 @@ struct VisibilityCall {
 
 // what the last successful srt_render_visibility left behind
 struct VisibilityState {
-    bool rendered = false;  // there has been an srt_render_visibility
-    bool counted = false;   // ... and the last one had SRT_VIS_COUNT_WORK
-    uint32_t last_outputs = 0;
-    const void* last_dst[VIS_SLOTS] = {nullptr, nullptr};
+    CallRecord call;  // counted: it had SRT_VIS_COUNT_WORK
+    LastOutputs<VIS_SLOTS> last;
 };
 
 // slot of a single output bit, -1 for anything else (no bit, both bits, an unknown bit)
@@ -59,22 +57,8 @@ inline RaysStatus visibility_check(const VisibilityCall& v, bool scene_set, int 
 
 // srt_render_visibility once the launch is enqueued: it wrote `outputs`, output of slot i to dst[i], and nothing else.
 inline void visibility_rendered(VisibilityState& s, uint32_t outputs, void* const dst[VIS_SLOTS], uint32_t flags) {
-    s.rendered = true;
-    s.counted = (flags & VIS_FLAG_COUNT_WORK) != 0;
-    s.last_outputs = outputs;
-    for (int i = 0; i < VIS_SLOTS; ++i) s.last_dst[i] = (outputs & (1u << i)) ? dst[i] : nullptr;
+    s.call.done((flags & VIS_FLAG_COUNT_WORK) != 0);
+    s.last.wrote(outputs, dst);
 }
-
-// srt_read_visibility: the buffer to copy W * H floats from, or why not.
-inline RaysStatus visibility_check_read(const VisibilityState& s, uint32_t output, const void** src) {
-    const int i = visibility_slot(output);
-    if (i < 0) return RAYS_INVALID_ARG;
-    if (!s.rendered || !(s.last_outputs & output) || !s.last_dst[i]) return RAYS_STATE;
-    *src = s.last_dst[i];
-    return RAYS_OK;
-}
-
-// srt_get_visibility_work: only the record of a last call that counted
-inline RaysStatus visibility_check_work(const VisibilityState& s) { return s.rendered && s.counted ? RAYS_OK : RAYS_STATE; }
 
 }  // namespace srt

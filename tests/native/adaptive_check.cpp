@@ -108,13 +108,13 @@ int main() {
 
     // what may report
     AdaptiveState st;
-    CHECK(adaptive_check_work(st) == RAYS_STATE && budget_check_total(st) == RAYS_STATE);
+    CHECK(st.call.work() == RAYS_STATE && budget_check_total(st) == RAYS_STATE);
     adaptive_rendered(st, 0);
-    CHECK(adaptive_check_work(st) == RAYS_STATE);
+    CHECK(st.call.work() == RAYS_STATE);
     adaptive_rendered(st, ADAPTIVE_FLAG_COUNT_WORK | ADAPTIVE_FLAG_KEEP_COUNTS);
-    CHECK(adaptive_check_work(st) == RAYS_OK && budget_check_total(st) == RAYS_STATE);
+    CHECK(st.call.work() == RAYS_OK && budget_check_total(st) == RAYS_STATE);
     adaptive_rendered(st, ADAPTIVE_FLAG_KEEP_COUNTS);
-    CHECK(adaptive_check_work(st) == RAYS_STATE);
+    CHECK(st.call.work() == RAYS_STATE);
     st.budgeted = true;
     CHECK(budget_check_total(st) == RAYS_OK);
 

@@ -161,24 +161,24 @@ int main() {
     {
         AdaptiveState a;
         ProbeTailState t;
-        CHECK(adaptive_check_work(a) == RAYS_STATE && probe_tail_check_work(t) == RAYS_STATE);
+        CHECK(a.call.work() == RAYS_STATE && t.last.work() == RAYS_STATE);
         ProbeTailCall v = probe_tail_defaults();
         v.flags = PROBE_TAIL_FLAG_COUNT_WORK;
         probe_tail_set(t, v);
-        CHECK(adaptive_tail_rendered(a, t, ADAPTIVE_FLAG_COUNT_WORK) && a.rendered && a.counted && t.traced && t.counted);
-        CHECK(adaptive_check_work(a) == RAYS_OK && probe_tail_check_work(t) == RAYS_OK);
+        CHECK(adaptive_tail_rendered(a, t, ADAPTIVE_FLAG_COUNT_WORK) && a.call.ran && a.call.counted && t.last.ran && t.last.counted);
+        CHECK(a.call.work() == RAYS_OK && t.last.work() == RAYS_OK);
         // the two records follow their own flags
-        CHECK(adaptive_tail_rendered(a, t, ADAPTIVE_FLAG_KEEP_COUNTS) && adaptive_check_work(a) == RAYS_STATE && probe_tail_check_work(t) == RAYS_OK);
+        CHECK(adaptive_tail_rendered(a, t, ADAPTIVE_FLAG_KEEP_COUNTS) && a.call.work() == RAYS_STATE && t.last.work() == RAYS_OK);
         v.flags = 0;
         probe_tail_set(t, v);
-        CHECK(!adaptive_tail_rendered(a, t, ADAPTIVE_FLAG_COUNT_WORK) && adaptive_check_work(a) == RAYS_OK && probe_tail_check_work(t) == RAYS_STATE);
+        CHECK(!adaptive_tail_rendered(a, t, ADAPTIVE_FLAG_COUNT_WORK) && a.call.work() == RAYS_OK && t.last.work() == RAYS_STATE);
         CHECK(!a.budgeted);  // (the budget pass's flag is not this call's)
         // srt_render_adaptive after it leaves the tail's record alone
         v.flags = PROBE_TAIL_FLAG_COUNT_WORK;
         probe_tail_set(t, v);
         CHECK(adaptive_tail_rendered(a, t, 0u));
         adaptive_rendered(a, ADAPTIVE_FLAG_COUNT_WORK);
-        CHECK(probe_tail_check_work(t) == RAYS_OK && adaptive_check_work(a) == RAYS_OK);
+        CHECK(t.last.work() == RAYS_OK && a.call.work() == RAYS_OK);
     }
 
     if (failures) return 1;

@@ -24,10 +24,19 @@ static int failures = 0;
         }                                                               \
     } while (0)
 
+// srt_read_light_probe_output's rule as srt_capi.hip composes it: the slot, the shared record's read, the byte count of the last trace
+static RaysStatus read_light_probe_output(const LightProbeState& s, uint32_t output, const void** src, size_t* bytes) {
+    const int i = light_probe_slot(output);
+    if (i < 0) return RAYS_INVALID_ARG;
+    if (!(*src = s.last.read(output, i))) return RAYS_STATE;
+    *bytes = light_probe_elems(i, s.last_probes, s.last_directions) * (4 * sizeof(float));
+    return RAYS_OK;
+}
+
 static bool same(const LightProbeState& a, const LightProbeState& b) {
-    auto in = [](const LightProbeInput& x, const LightProbeInput& y) { return x.bound == y.bound && x.bound_count == y.bound_count && x.own_count == y.own_count; };
-    return in(a.positions, b.positions) && in(a.directions, b.directions) && a.traced == b.traced && a.counted == b.counted && a.last_probes == b.last_probes &&
-           a.last_directions == b.last_directions && a.last_outputs == b.last_outputs && a.last_dst[0] == b.last_dst[0] && a.last_dst[1] == b.last_dst[1];
+    auto in = [](const InputArray& x, const InputArray& y) { return x.bound == y.bound && x.bound_count == y.bound_count && x.own_count == y.own_count; };
+    return in(a.positions, b.positions) && in(a.directions, b.directions) && a.call.ran == b.call.ran && a.call.counted == b.call.counted && a.last_probes == b.last_probes &&
+           a.last_directions == b.last_directions && a.last.outputs == b.last.outputs && a.last.dst[0] == b.last.dst[0] && a.last.dst[1] == b.last.dst[1];
 }
 
 static LightProbeCall call(uint32_t f0, uint32_t n, int32_t bounces, uint32_t flags, uint32_t outputs = LIGHT_PROBE_OUT_COEFFICIENTS, uint32_t reserved = 0) {
@@ -66,29 +75,29 @@ int main() {
     size_t bytes = 0;
     int rad_own = 0, rad_other = 0, coeff_own = 0;
     CHECK(s.positions.count() == 0 && s.directions.count() == 0);
-    CHECK(light_probe_bind(s.directions, a.data(), 0, LIGHT_PROBE_MAX_DIRECTIONS) == RAYS_INVALID_ARG);
-    CHECK(light_probe_bind(s.directions, a.data(), 4097, LIGHT_PROBE_MAX_DIRECTIONS) == RAYS_INVALID_ARG);
-    CHECK(light_probe_bind(s.directions, nullptr, 5, LIGHT_PROBE_MAX_DIRECTIONS) == RAYS_INVALID_ARG && s.directions.count() == 0);
-    CHECK(light_probe_bind(s.directions, a.data(), 4096, LIGHT_PROBE_MAX_DIRECTIONS) == RAYS_OK && s.directions.count() == 4096);
-    CHECK(light_probe_bind(s.directions, nullptr, 0, LIGHT_PROBE_MAX_DIRECTIONS) == RAYS_OK && s.directions.count() == 0);
-    CHECK(light_probe_bind(s.positions, a.data(), ((size_t)1 << 30) + 1, LIGHT_PROBE_MAX_RAYS) == RAYS_INVALID_ARG);
-    CHECK(light_probe_bind(s.positions, a.data(), (size_t)1 << 30, LIGHT_PROBE_MAX_RAYS) == RAYS_OK && s.positions.count() == ((size_t)1 << 30));
-    light_probe_written(s.positions, 3);  // a write ends the binding
+    CHECK(input_bind(s.directions, a.data(), 0, LIGHT_PROBE_MAX_DIRECTIONS) == RAYS_INVALID_ARG);
+    CHECK(input_bind(s.directions, a.data(), 4097, LIGHT_PROBE_MAX_DIRECTIONS) == RAYS_INVALID_ARG);
+    CHECK(input_bind(s.directions, nullptr, 5, LIGHT_PROBE_MAX_DIRECTIONS) == RAYS_INVALID_ARG && s.directions.count() == 0);
+    CHECK(input_bind(s.directions, a.data(), 4096, LIGHT_PROBE_MAX_DIRECTIONS) == RAYS_OK && s.directions.count() == 4096);
+    CHECK(input_bind(s.directions, nullptr, 0, LIGHT_PROBE_MAX_DIRECTIONS) == RAYS_OK && s.directions.count() == 0);
+    CHECK(input_bind(s.positions, a.data(), ((size_t)1 << 30) + 1, LIGHT_PROBE_MAX_RAYS) == RAYS_INVALID_ARG);
+    CHECK(input_bind(s.positions, a.data(), (size_t)1 << 30, LIGHT_PROBE_MAX_RAYS) == RAYS_OK && s.positions.count() == ((size_t)1 << 30));
+    input_written(s.positions, 3);  // a write ends the binding
     CHECK(s.positions.count() == 3 && !s.positions.bound);
-    CHECK(light_probe_bind(s.positions, nullptr, 0, LIGHT_PROBE_MAX_RAYS) == RAYS_OK && s.positions.count() == 3);
+    CHECK(input_bind(s.positions, nullptr, 0, LIGHT_PROBE_MAX_RAYS) == RAYS_OK && s.positions.count() == 3);
     s = LightProbeState();
 
     // the checks: the scene, the arguments, the inputs, the continuation
-    CHECK(light_probe_check_work(s) == RAYS_STATE && light_probe_check_read(s, 1, &src, &bytes) == RAYS_STATE && light_probe_check_read(s, 3, &src, &bytes) == RAYS_INVALID_ARG);
+    CHECK(s.call.work() == RAYS_STATE && read_light_probe_output(s, 1, &src, &bytes) == RAYS_STATE && read_light_probe_output(s, 3, &src, &bytes) == RAYS_INVALID_ARG);
     const LightProbeCall ok = call(1, 16, 8, LIGHT_PROBE_FLAG_RESET);
     CHECK(light_probe_check_trace(s, false, ok, nullptr, &why) == RAYS_STATE && std::strstr(why, "srt_set_scene"));
     CHECK(light_probe_check_trace(s, false, call(0, 0, -1, 8, 0, 1), nullptr, &why) == RAYS_STATE);                                         // the scene comes first
     CHECK(light_probe_check_trace(s, true, call(1, 16, 8, 8), nullptr, &why) == RAYS_INVALID_ARG && std::strstr(why, "flags"));  // the arguments before the inputs
     CHECK(light_probe_check_trace(s, true, ok, nullptr, &why) == RAYS_STATE && std::strstr(why, "positions"));
     CHECK(light_probe_check_trace(s, true, ok, nullptr, nullptr) == RAYS_STATE);  // (a NULL reason is allowed)
-    light_probe_written(s.positions, 3);
+    input_written(s.positions, 3);
     CHECK(light_probe_check_trace(s, true, ok, nullptr, &why) == RAYS_STATE && std::strstr(why, "directions"));
-    light_probe_written(s.directions, 100);
+    input_written(s.directions, 100);
     {
         const LightProbeState before = s;
         for (uint32_t f : {1u, 3u, 5u, 7u}) CHECK(light_probe_check_trace(s, true, call(1, 16, 8, f), nullptr, &why) == RAYS_OK);
@@ -110,15 +119,15 @@ int main() {
     s.directions.own_count = 4097;
     CHECK(light_probe_check_trace(s, true, ok, nullptr, &why) == RAYS_INVALID_ARG && std::strstr(why, "4096"));
     s.directions.own_count = 4096;
-    CHECK(light_probe_bind(s.positions, a.data(), (size_t)1 << 18, LIGHT_PROBE_MAX_RAYS) == RAYS_OK);
+    CHECK(input_bind(s.positions, a.data(), (size_t)1 << 18, LIGHT_PROBE_MAX_RAYS) == RAYS_OK);
     CHECK(light_probe_check_trace(s, true, ok, nullptr, &why) == RAYS_OK);  // 2^18 * 2^12 = 2^30
-    CHECK(light_probe_bind(s.positions, a.data(), ((size_t)1 << 18) + 1, LIGHT_PROBE_MAX_RAYS) == RAYS_OK);
+    CHECK(input_bind(s.positions, a.data(), ((size_t)1 << 18) + 1, LIGHT_PROBE_MAX_RAYS) == RAYS_OK);
     CHECK(light_probe_check_trace(s, true, ok, nullptr, &why) == RAYS_INVALID_ARG && std::strstr(why, "2^30"));
     s.directions.own_count = 1;
-    CHECK(light_probe_bind(s.positions, a.data(), (size_t)1 << 30, LIGHT_PROBE_MAX_RAYS) == RAYS_OK && light_probe_check_trace(s, true, ok, nullptr, &why) == RAYS_OK);
+    CHECK(input_bind(s.positions, a.data(), (size_t)1 << 30, LIGHT_PROBE_MAX_RAYS) == RAYS_OK && light_probe_check_trace(s, true, ok, nullptr, &why) == RAYS_OK);
     s.directions.own_count = 2;
     CHECK(light_probe_check_trace(s, true, ok, nullptr, &why) == RAYS_INVALID_ARG && std::strstr(why, "2^30"));
-    CHECK(light_probe_bind(s.positions, nullptr, 0, LIGHT_PROBE_MAX_RAYS) == RAYS_OK && s.positions.count() == 3);
+    CHECK(input_bind(s.positions, nullptr, 0, LIGHT_PROBE_MAX_RAYS) == RAYS_OK && s.positions.count() == 3);
     s.directions.own_count = 100;
 
     // continuing without RESET: needs the RADIANCE output, and a previous trace of the same P and K into the current buffer
@@ -130,41 +139,41 @@ int main() {
         light_probe_traced(s, 3, 100, LIGHT_PROBE_OUT_COEFFICIENTS, dst, LIGHT_PROBE_FLAG_RESET);
     }
     CHECK(light_probe_check_trace(s, true, cont, &rad_own, &why) == RAYS_STATE);  // the last trace had no RADIANCE output
-    CHECK(light_probe_check_read(s, 1, &src, &bytes) == RAYS_OK && src == &coeff_own && bytes == 3 * 9 * 16);
-    CHECK(light_probe_check_read(s, 2, &src, &bytes) == RAYS_STATE && light_probe_check_work(s) == RAYS_STATE);
+    CHECK(read_light_probe_output(s, 1, &src, &bytes) == RAYS_OK && src == &coeff_own && bytes == 3 * 9 * 16);
+    CHECK(read_light_probe_output(s, 2, &src, &bytes) == RAYS_STATE && s.call.work() == RAYS_STATE);
     {
         void* dst[LIGHT_PROBE_SLOTS] = {&coeff_own, &rad_own};
         light_probe_traced(s, 3, 100, LIGHT_PROBE_OUT_ALL, dst, LIGHT_PROBE_FLAG_RESET | LIGHT_PROBE_FLAG_COUNT_WORK);
     }
-    CHECK(light_probe_check_work(s) == RAYS_OK);
-    CHECK(light_probe_check_read(s, 2, &src, &bytes) == RAYS_OK && src == &rad_own && bytes == 300 * 16);
+    CHECK(s.call.work() == RAYS_OK);
+    CHECK(read_light_probe_output(s, 2, &src, &bytes) == RAYS_OK && src == &rad_own && bytes == 300 * 16);
     CHECK(light_probe_check_trace(s, true, cont, &rad_own, &why) == RAYS_OK && light_probe_check_trace(s, true, cont_only, &rad_own, &why) == RAYS_OK);
     CHECK(light_probe_check_trace(s, true, cont, &rad_other, &why) == RAYS_STATE);  // another buffer is bound now
     CHECK(light_probe_check_trace(s, true, cont, nullptr, &why) == RAYS_STATE);
-    light_probe_written(s.positions, 4);  // P changed
+    input_written(s.positions, 4);  // P changed
     CHECK(light_probe_check_trace(s, true, cont, &rad_own, &why) == RAYS_STATE && light_probe_check_trace(s, true, ok, &rad_own, &why) == RAYS_OK);
-    light_probe_written(s.positions, 3);
-    light_probe_written(s.directions, 99);  // K changed
+    input_written(s.positions, 3);
+    input_written(s.directions, 99);  // K changed
     CHECK(light_probe_check_trace(s, true, cont, &rad_own, &why) == RAYS_STATE);
-    light_probe_written(s.directions, 100);
+    input_written(s.directions, 100);
     CHECK(light_probe_check_trace(s, true, cont, &rad_own, &why) == RAYS_OK);
     // a later write changes the current inputs, not what the last trace wrote
-    light_probe_written(s.positions, 7);
-    CHECK(light_probe_check_read(s, 2, &src, &bytes) == RAYS_OK && bytes == 300 * 16);
-    light_probe_written(s.positions, 3);
+    input_written(s.positions, 7);
+    CHECK(read_light_probe_output(s, 2, &src, &bytes) == RAYS_OK && bytes == 300 * 16);
+    input_written(s.positions, 3);
     // the own buffer is re-allocated: the result goes with it, and so does the continuation
-    light_probe_output_released(s, 1, &rad_other);
-    CHECK(light_probe_check_read(s, 2, &src, &bytes) == RAYS_OK);
-    light_probe_output_released(s, 1, nullptr);
-    CHECK(light_probe_check_read(s, 2, &src, &bytes) == RAYS_OK);
-    light_probe_output_released(s, 1, &rad_own);
-    CHECK(light_probe_check_read(s, 2, &src, &bytes) == RAYS_STATE && light_probe_check_read(s, 1, &src, &bytes) == RAYS_OK);
+    s.last.released(1, &rad_other);
+    CHECK(read_light_probe_output(s, 2, &src, &bytes) == RAYS_OK);
+    s.last.released(1, nullptr);
+    CHECK(read_light_probe_output(s, 2, &src, &bytes) == RAYS_OK);
+    s.last.released(1, &rad_own);
+    CHECK(read_light_probe_output(s, 2, &src, &bytes) == RAYS_STATE && read_light_probe_output(s, 1, &src, &bytes) == RAYS_OK);
     CHECK(light_probe_check_trace(s, true, cont, &rad_own, &why) == RAYS_STATE);
     {
         void* dst[LIGHT_PROBE_SLOTS] = {nullptr, &rad_own};
         light_probe_traced(s, 3, 100, LIGHT_PROBE_OUT_RADIANCE, dst, LIGHT_PROBE_FLAG_RESET);  // a trace without the flag ends the work record
     }
-    CHECK(light_probe_check_work(s) == RAYS_STATE && light_probe_check_read(s, 1, &src, &bytes) == RAYS_STATE);
+    CHECK(s.call.work() == RAYS_STATE && read_light_probe_output(s, 1, &src, &bytes) == RAYS_STATE);
 
     // blocks, units, output sizes, the partial buffer [P][J][9] float4 (none for one block)
     CHECK(light_probe_blocks(1) == 1 && light_probe_blocks(64) == 1 && light_probe_blocks(65) == 2 && light_probe_blocks(100) == 2 && light_probe_blocks(4096) == 64);

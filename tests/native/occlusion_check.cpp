@@ -13,6 +13,8 @@
 
 using namespace srt;
 
+#include "read_ray_output.h"
+
 static int failures = 0;
 #define CHECK(cond)                                                     \
     do {                                                                \
@@ -23,9 +25,9 @@ static int failures = 0;
     } while (0)
 
 static bool same(const RaysState& a, const RaysState& b) {
-    bool eq = a.bound_origin == b.bound_origin && a.bound_direction == b.bound_direction && a.bound_count == b.bound_count && a.own_count == b.own_count &&
-              a.last_count == b.last_count && a.last_outputs == b.last_outputs;
-    for (int i = 0; i < RAYS_SLOTS; ++i) eq = eq && a.last_dst[i] == b.last_dst[i];
+    bool eq = a.origins.bound == b.origins.bound && a.bound_direction == b.bound_direction && a.origins.bound_count == b.origins.bound_count && a.origins.own_count == b.origins.own_count &&
+              a.last_count == b.last_count && a.last.outputs == b.last.outputs;
+    for (int i = 0; i < RAYS_SLOTS; ++i) eq = eq && a.last.dst[i] == b.last.dst[i];
     return eq;
 }
 
@@ -42,9 +44,9 @@ int main() {
     // the checks, in srt_trace_rays' order: the scene, the arguments, the rays
     std::vector<float> a(8), b(8);
     RaysState s;
-    OcclusionState w;
+    CallRecord w;
     const char* why = nullptr;
-    CHECK(occlusion_check_work(w) == RAYS_STATE);  // no trace yet
+    CHECK(w.work() == RAYS_STATE);  // no trace yet
     CHECK(occlusion_check_trace(s, false, 0, 0, &why) == RAYS_STATE && std::strstr(why, "srt_set_scene"));
     CHECK(occlusion_check_trace(s, false, 4, 1, &why) == RAYS_STATE);  // the scene comes first
     CHECK(occlusion_check_trace(s, true, 4, 0, &why) == RAYS_INVALID_ARG && std::strstr(why, "flags"));  // the arguments before the rays
@@ -68,32 +70,32 @@ int main() {
     int dummy[RAYS_SLOTS], own;
     void* dst[RAYS_SLOTS] = {&dummy[0], &dummy[1], &dummy[2], &dummy[3], &dummy[4]};
     rays_traced(s, RAYS_OUT_ALL, dst);
-    for (uint32_t bit = 1; bit <= 16; bit <<= 1) CHECK(rays_check_read(s, bit, &src, &bytes) == RAYS_OK);
+    for (uint32_t bit = 1; bit <= 16; bit <<= 1) CHECK(read_ray_output(s, bit, &src, &bytes) == RAYS_OK);
     occlusion_traced(s, w, &own, 0);
-    CHECK(rays_check_read(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_OK && src == &own && bytes == 3 * sizeof(int32_t));
-    for (uint32_t bit = 1; bit <= 8; bit <<= 1) CHECK(rays_check_read(s, bit, &src, &bytes) == RAYS_STATE);
-    CHECK(s.last_outputs == RAYS_OUT_OCCLUDED && s.last_count == 3);
-    for (int i = 0; i < RAYS_SLOTS; ++i) CHECK(s.last_dst[i] == (i == OCCLUSION_SLOT ? (const void*)&own : nullptr));
-    CHECK(occlusion_check_work(w) == RAYS_STATE);  // traced, but not counted
+    CHECK(read_ray_output(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_OK && src == &own && bytes == 3 * sizeof(int32_t));
+    for (uint32_t bit = 1; bit <= 8; bit <<= 1) CHECK(read_ray_output(s, bit, &src, &bytes) == RAYS_STATE);
+    CHECK(s.last.outputs == RAYS_OUT_OCCLUDED && s.last_count == 3);
+    for (int i = 0; i < RAYS_SLOTS; ++i) CHECK(s.last.dst[i] == (i == OCCLUSION_SLOT ? (const void*)&own : nullptr));
+    CHECK(w.work() == RAYS_STATE);  // traced, but not counted
     // a later bind changes the current rays, not what the last trace wrote; the next occlusion trace takes the new count
     CHECK(rays_bind(s, a.data(), b.data(), 9) == RAYS_OK);
-    CHECK(rays_check_read(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_OK && bytes == 3 * sizeof(int32_t));
+    CHECK(read_ray_output(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_OK && bytes == 3 * sizeof(int32_t));
     occlusion_traced(s, w, &dummy[4], OCCLUSION_FLAG_COUNT_WORK | OCCLUSION_FLAG_NORMALIZE);
-    CHECK(rays_check_read(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_OK && src == &dummy[4] && bytes == 9 * sizeof(int32_t));
-    CHECK(occlusion_check_work(w) == RAYS_OK);
+    CHECK(read_ray_output(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_OK && src == &dummy[4] && bytes == 9 * sizeof(int32_t));
+    CHECK(w.work() == RAYS_OK);
     occlusion_traced(s, w, &dummy[4], OCCLUSION_FLAG_NORMALIZE);  // a trace without the flag ends the record
-    CHECK(occlusion_check_work(w) == RAYS_STATE);
+    CHECK(w.work() == RAYS_STATE);
     occlusion_traced(s, w, &dummy[4], OCCLUSION_FLAG_COUNT_WORK);
-    CHECK(occlusion_check_work(w) == RAYS_OK);
+    CHECK(w.work() == RAYS_OK);
     // srt_trace_rays afterwards: its outputs are readable again; the work record is the last OCCLUSION trace's and stays
     rays_traced(s, RAYS_OUT_OBJECT | RAYS_OUT_ALBEDO, dst);
-    CHECK(rays_check_read(s, 1, &src, &bytes) == RAYS_OK && rays_check_read(s, 8, &src, &bytes) == RAYS_OK && bytes == 9 * 16);
-    CHECK(rays_check_read(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_STATE);
-    CHECK(occlusion_check_work(w) == RAYS_OK);
+    CHECK(read_ray_output(s, 1, &src, &bytes) == RAYS_OK && read_ray_output(s, 8, &src, &bytes) == RAYS_OK && bytes == 9 * 16);
+    CHECK(read_ray_output(s, RAYS_OUT_OCCLUDED, &src, &bytes) == RAYS_STATE);
+    CHECK(w.work() == RAYS_OK);
     // a refused check in between changes neither
     {
         const RaysState before = s;
-        CHECK(occlusion_check_trace(s, true, 4, 0, &why) == RAYS_INVALID_ARG && same(s, before) && occlusion_check_work(w) == RAYS_OK);
+        CHECK(occlusion_check_trace(s, true, 4, 0, &why) == RAYS_INVALID_ARG && same(s, before) && w.work() == RAYS_OK);
     }
 
     if (failures) return 1;

@@ -116,8 +116,8 @@ int main() {
     // marks: written and bound arrays, then a refused cascade leaves everything
     int dev = 0;
     for (int l = 0; l < 3; ++l)
-        for (int i = 0; i < 3; ++i) light_probe_written(s.arrays[l][i], 125);
-    CHECK(light_probe_bind(s.arrays[1][0], &dev, 125, PROBE_GRID_MAX_PROBES) == RAYS_OK);
+        for (int i = 0; i < 3; ++i) input_written(s.arrays[l][i], 125);
+    CHECK(input_bind(s.arrays[1][0], &dev, 125, PROBE_GRID_MAX_PROBES) == RAYS_OK);
     bad = good, bad.blend_cells = nan, bad.levels = 2;
     CHECK(probe_cascade_set(s, bad, &why) == RAYS_INVALID_ARG);
     CHECK(s.cascade.levels == 3 && s.cascade.blend_cells == 1.0f && s.arrays[2][0].count() == 125 && s.arrays[1][0].bound == &dev);
@@ -163,9 +163,9 @@ int main() {
         CHECK(probe_cascade_check_capture(cs, 0, 7, g, d, st, &why) == RAYS_STATE && strstr(why, "counts"));
         g.grid = grid_of(7.0f, 3.0f, 5);  // (another origin and spacing: the counts decide)
         CHECK(probe_cascade_check_capture(cs, 0, 1, g, d, st, &why) == RAYS_STATE && strstr(why, "no current probe-grid coefficients"));
-        light_probe_written(g.coefficients, 124);
+        input_written(g.coefficients, 124);
         CHECK(probe_cascade_check_capture(cs, 0, 1, g, d, st, &why) == RAYS_STATE && strstr(why, "coefficient count"));
-        light_probe_written(g.coefficients, 125);
+        input_written(g.coefficients, 125);
         CHECK(probe_cascade_check_capture(cs, 0, 1, g, d, st, &why) == RAYS_OK);
         CHECK(probe_cascade_check_capture(cs, 0, 3, g, d, st, &why) == RAYS_STATE && strstr(why, "no current probe-grid depth"));
         probe_grid_depth_written(d, 125, 16);
@@ -175,9 +175,9 @@ int main() {
         probe_grid_depth_written(d, 125, 8);
         CHECK(probe_cascade_check_capture(cs, 0, 3, g, d, st, &why) == RAYS_OK);
         CHECK(probe_cascade_check_capture(cs, 2, 7, g, d, st, &why) == RAYS_STATE && strstr(why, "no current probe-grid states"));
-        light_probe_written(st.states, 5);
+        input_written(st.states, 5);
         CHECK(probe_cascade_check_capture(cs, 2, 4, g, d, st, &why) == RAYS_STATE && strstr(why, "state count"));
-        light_probe_written(st.states, 125);
+        input_written(st.states, 125);
         CHECK(probe_cascade_check_capture(cs, 2, 7, g, d, st, &why) == RAYS_OK);
         CHECK(cs.arrays[2][0].count() == 0 && cs.arrays[0][0].count() == 0);  // (a check touches nothing)
     }
@@ -230,33 +230,33 @@ int main() {
         b = k, b.flags = PROBE_CASCADE_FLAG_ALBEDO;
         CHECK(probe_cascade_check_shade(cs, b, true, 20, some, &why) == RAYS_STATE && strstr(why, "ALBEDO"));
         // per level ascending: coefficients, then (with _DEPTH) the resolution and the moments, then (with _STATES) the records
-        light_probe_written(cs.arrays[0][0], 125);
-        light_probe_written(cs.arrays[1][0], 124);
+        input_written(cs.arrays[0][0], 125);
+        input_written(cs.arrays[1][0], 124);
         CHECK(probe_cascade_check_shade(cs, k, true, 20, all, &why) == RAYS_STATE && strstr(why, "coefficient count"));
-        light_probe_written(cs.arrays[1][0], 125);
+        input_written(cs.arrays[1][0], 125);
         CHECK(probe_cascade_check_shade(cs, k, true, 20, all, &why) == RAYS_STATE && strstr(why, "no coefficients"));  // (level 2)
         b = k, b.flags = PROBE_CASCADE_FLAG_DEPTH | PROBE_CASCADE_FLAG_STATES;
         CHECK(probe_cascade_check_shade(cs, b, true, 20, all, &why) == RAYS_STATE && strstr(why, "resolution is 0"));  // (level 0's moments before level 2's coefficients)
-        light_probe_written(cs.arrays[2][0], 125);
+        input_written(cs.arrays[2][0], 125);
         CHECK(probe_cascade_check_shade(cs, k, true, 20, all, &why) == RAYS_OK);
         CHECK(probe_cascade_set(cs, good, &why) == RAYS_OK);  // (R = 8: the coefficients stay)
         CHECK(probe_cascade_check_shade(cs, b, true, 20, all, &why) == RAYS_STATE && strstr(why, "no moments"));
-        light_probe_written(cs.arrays[0][1], 5);
+        input_written(cs.arrays[0][1], 5);
         CHECK(probe_cascade_check_shade(cs, b, true, 20, all, &why) == RAYS_STATE && strstr(why, "moment probe count"));
-        light_probe_written(cs.arrays[0][1], 125);
+        input_written(cs.arrays[0][1], 125);
         CHECK(probe_cascade_check_shade(cs, b, true, 20, all, &why) == RAYS_STATE && strstr(why, "no records"));
-        light_probe_written(cs.arrays[0][2], 126);
+        input_written(cs.arrays[0][2], 126);
         CHECK(probe_cascade_check_shade(cs, b, true, 20, all, &why) == RAYS_STATE && strstr(why, "record count"));
-        light_probe_written(cs.arrays[0][2], 125);
+        input_written(cs.arrays[0][2], 125);
         CHECK(probe_cascade_check_shade(cs, b, true, 20, all, &why) == RAYS_STATE && strstr(why, "no moments"));  // (level 1)
-        for (int l = 1; l < 3; ++l) light_probe_written(cs.arrays[l][1], 125), light_probe_written(cs.arrays[l][2], 125);
+        for (int l = 1; l < 3; ++l) input_written(cs.arrays[l][1], 125), input_written(cs.arrays[l][2], 125);
         CHECK(probe_cascade_check_shade(cs, b, true, 20, all, &why) == RAYS_OK);
         // the work record
-        CHECK(probe_cascade_check_work(cs) == RAYS_STATE);
+        CHECK(cs.call.work() == RAYS_STATE);
         probe_cascade_shaded(cs, 0);
-        CHECK(probe_cascade_check_work(cs) == RAYS_STATE);
+        CHECK(cs.call.work() == RAYS_STATE);
         probe_cascade_shaded(cs, PROBE_CASCADE_FLAG_COUNT_WORK);
-        CHECK(probe_cascade_check_work(cs) == RAYS_OK);
+        CHECK(cs.call.work() == RAYS_OK);
     }
 
     // rule C8: the grids helper

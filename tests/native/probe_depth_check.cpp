@@ -25,6 +25,15 @@ static int checks = 0;
         }                                                        \
     } while (0)
 
+// srt_read_probe_depth_output's rule as srt_capi.hip composes it: the slot, the shared record's read, the byte count of the last trace
+static RaysStatus read_probe_depth_output(const ProbeDepthState& s, uint32_t output, const void** src, size_t* bytes) {
+    const int i = probe_depth_slot(output);
+    if (i < 0) return RAYS_INVALID_ARG;
+    if (!(*src = s.last.read(output, i))) return RAYS_STATE;
+    *bytes = probe_depth_bytes(i, s.last_probes, s.last_directions, s.last_resolution);
+    return RAYS_OK;
+}
+
 int main() {
     const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
     static_assert(sizeof(ProbeDepthCall) == 24 && sizeof(ProbeGridDepthCall) == 16, "the structs of the header");
@@ -98,40 +107,40 @@ int main() {
     }
     // the sizes: P*K and P*R*R at and past 2^30
     static const char dummy = 0;
-    CHECK(light_probe_bind(in.positions, &dummy, (size_t)1 << 22, LIGHT_PROBE_MAX_RAYS) == RAYS_OK);
+    CHECK(input_bind(in.positions, &dummy, (size_t)1 << 22, LIGHT_PROBE_MAX_RAYS) == RAYS_OK);
     in.directions.own_count = 256;
     CHECK(probe_depth_check_trace(in, true, c, &why) == RAYS_OK);  // exactly 2^30 both ways
     in.directions.own_count = 257;
     CHECK(probe_depth_check_trace(in, true, c, &why) == RAYS_INVALID_ARG && strstr(why, "directions exceeds"));
     in.directions.own_count = 1;
-    CHECK(light_probe_bind(in.positions, &dummy, ((size_t)1 << 22) + 1, LIGHT_PROBE_MAX_RAYS) == RAYS_OK);
+    CHECK(input_bind(in.positions, &dummy, ((size_t)1 << 22) + 1, LIGHT_PROBE_MAX_RAYS) == RAYS_OK);
     CHECK(probe_depth_check_trace(in, true, c, &why) == RAYS_INVALID_ARG && strstr(why, "resolution^2"));
     bad = c, bad.resolution = 8;
     CHECK(probe_depth_check_trace(in, true, bad, &why) == RAYS_OK);
-    CHECK(light_probe_bind(in.positions, nullptr, 0, LIGHT_PROBE_MAX_RAYS) == RAYS_OK && in.positions.count() == 5);
+    CHECK(input_bind(in.positions, nullptr, 0, LIGHT_PROBE_MAX_RAYS) == RAYS_OK && in.positions.count() == 5);
     // the record of the last trace, and what a read returns
     ProbeDepthState s;
     const void* src = nullptr;
     size_t bytes = 0;
-    CHECK(probe_depth_check_read(s, 1, &src, &bytes) == RAYS_STATE && probe_depth_check_read(s, 3, &src, &bytes) == RAYS_INVALID_ARG);
-    CHECK(probe_depth_check_work(s) == RAYS_STATE);
+    CHECK(read_probe_depth_output(s, 1, &src, &bytes) == RAYS_STATE && read_probe_depth_output(s, 3, &src, &bytes) == RAYS_INVALID_ARG);
+    CHECK(s.call.work() == RAYS_STATE);
     char own_m = 0, own_d = 0;
     void* dst[PROBE_DEPTH_SLOTS] = {&own_m, &own_d};
     ProbeDepthCall t = c;
     t.outputs = PROBE_DEPTH_OUT_MOMENTS, t.flags = PROBE_DEPTH_FLAG_COUNT_WORK, t.resolution = 8;
     probe_depth_traced(s, 5, 100, t, dst);
-    CHECK(probe_depth_check_read(s, 1, &src, &bytes) == RAYS_OK && src == &own_m && bytes == 5 * 64 * 16);
-    CHECK(probe_depth_check_read(s, 2, &src, &bytes) == RAYS_STATE);  // not written
-    CHECK(probe_depth_check_work(s) == RAYS_OK);
+    CHECK(read_probe_depth_output(s, 1, &src, &bytes) == RAYS_OK && src == &own_m && bytes == 5 * 64 * 16);
+    CHECK(read_probe_depth_output(s, 2, &src, &bytes) == RAYS_STATE);  // not written
+    CHECK(s.call.work() == RAYS_OK);
     t.outputs = 3, t.flags = 0, t.resolution = 16;
     probe_depth_traced(s, 7, 65, t, dst);
-    CHECK(probe_depth_check_read(s, 2, &src, &bytes) == RAYS_OK && src == &own_d && bytes == 7 * 65 * 4);
-    CHECK(probe_depth_check_read(s, 1, &src, &bytes) == RAYS_OK && bytes == 7 * 256 * 16);
-    CHECK(probe_depth_check_work(s) == RAYS_STATE);  // that trace did not count
-    probe_depth_output_released(s, 0, &own_d);       // another buffer: nothing goes
-    CHECK(probe_depth_check_read(s, 1, &src, &bytes) == RAYS_OK);
-    probe_depth_output_released(s, 0, &own_m);
-    CHECK(probe_depth_check_read(s, 1, &src, &bytes) == RAYS_STATE && probe_depth_check_read(s, 2, &src, &bytes) == RAYS_OK);
+    CHECK(read_probe_depth_output(s, 2, &src, &bytes) == RAYS_OK && src == &own_d && bytes == 7 * 65 * 4);
+    CHECK(read_probe_depth_output(s, 1, &src, &bytes) == RAYS_OK && bytes == 7 * 256 * 16);
+    CHECK(s.call.work() == RAYS_STATE);  // that trace did not count
+    s.last.released(0, &own_d);       // another buffer: nothing goes
+    CHECK(read_probe_depth_output(s, 1, &src, &bytes) == RAYS_OK);
+    s.last.released(0, &own_m);
+    CHECK(read_probe_depth_output(s, 1, &src, &bytes) == RAYS_STATE && read_probe_depth_output(s, 2, &src, &bytes) == RAYS_OK);
     // grid sizing: one wave per probe, four per workgroup, never none, never more than resident
     CHECK(probe_depth_grid(1, 4, 1024) == 1 && probe_depth_grid(4, 4, 1024) == 1 && probe_depth_grid(5, 4, 1024) == 2);
     CHECK(probe_depth_grid(4096, 4, 1024) == 1024 && probe_depth_grid((size_t)1 << 30, 4, 1024) == 1024 && probe_depth_grid(9, 4, 0) == 1);
@@ -209,9 +218,9 @@ int main() {
     CHECK(probe_grid_depth_check_shade(g, d, pc, ok_dc, true, 20, all, nullptr) == RAYS_OK);
     // both calls share the "last call" record
     probe_grid_shaded(g, pc.flags);
-    CHECK(probe_grid_check_work(g) == RAYS_OK);
+    CHECK(g.call.work() == RAYS_OK);
     probe_grid_shaded(g, 0);
-    CHECK(probe_grid_check_work(g) == RAYS_STATE);
+    CHECK(g.call.work() == RAYS_STATE);
     printf("ok %d\n", checks);
     return 0;
 }

@@ -114,12 +114,12 @@ int main() {
     CHECK(probe_grid_check_shade(s, c, true, 20, all, &why) == RAYS_STATE && strstr(why, "no grid"));
     s.grid = grid(0, 0, 0, 1, 1, 1, 5, 3, 5), s.grid_set = true;
     CHECK(probe_grid_check_shade(s, c, true, 20, all, &why) == RAYS_STATE && strstr(why, "no coefficients"));
-    light_probe_written(s.coefficients, 74);
+    input_written(s.coefficients, 74);
     CHECK(probe_grid_check_shade(s, c, true, 20, none, &why) == RAYS_STATE && strstr(why, "OBJECT"));  // a guide before the count
     const bool no_position[PROBE_GRID_GUIDES] = {true, true, false, true};
     CHECK(probe_grid_check_shade(s, c, true, 20, no_position, &why) == RAYS_STATE && strstr(why, "POSITION"));
     CHECK(probe_grid_check_shade(s, c, true, 20, three, &why) == RAYS_STATE && strstr(why, "nx * ny * nz"));
-    light_probe_written(s.coefficients, 75);
+    input_written(s.coefficients, 75);
     CHECK(probe_grid_check_shade(s, c, true, 20, three, nullptr) == RAYS_OK);
     c.flags = PROBE_GRID_FLAG_ALBEDO;
     CHECK(probe_grid_check_shade(s, c, true, 20, three, &why) == RAYS_STATE && strstr(why, "ALBEDO"));
@@ -128,18 +128,18 @@ int main() {
     CHECK(probe_grid_check_shade(s, c, true, 20, all, nullptr) == RAYS_OK);
     // a bound array comes first, and NULL, 0 returns to the own one
     int dummy = 0;
-    CHECK(light_probe_bind(s.coefficients, &dummy, 76, PROBE_GRID_MAX_PROBES) == RAYS_OK);
+    CHECK(input_bind(s.coefficients, &dummy, 76, PROBE_GRID_MAX_PROBES) == RAYS_OK);
     CHECK(probe_grid_check_shade(s, c, true, 20, all, &why) == RAYS_STATE && strstr(why, "nx * ny * nz"));
-    CHECK(light_probe_bind(s.coefficients, &dummy, PROBE_GRID_MAX_PROBES + 1, PROBE_GRID_MAX_PROBES) == RAYS_INVALID_ARG && s.coefficients.count() == 76);
-    CHECK(light_probe_bind(s.coefficients, nullptr, 0, PROBE_GRID_MAX_PROBES) == RAYS_OK && s.coefficients.count() == 75);
+    CHECK(input_bind(s.coefficients, &dummy, PROBE_GRID_MAX_PROBES + 1, PROBE_GRID_MAX_PROBES) == RAYS_INVALID_ARG && s.coefficients.count() == 76);
+    CHECK(input_bind(s.coefficients, nullptr, 0, PROBE_GRID_MAX_PROBES) == RAYS_OK && s.coefficients.count() == 75);
     // the work record: only of a last call that counted
-    CHECK(probe_grid_check_work(s) == RAYS_STATE);
+    CHECK(s.call.work() == RAYS_STATE);
     probe_grid_shaded(s, PROBE_GRID_FLAG_VISIBILITY);
-    CHECK(probe_grid_check_work(s) == RAYS_STATE);
+    CHECK(s.call.work() == RAYS_STATE);
     probe_grid_shaded(s, PROBE_GRID_FLAG_COUNT_WORK);
-    CHECK(probe_grid_check_work(s) == RAYS_OK);
+    CHECK(s.call.work() == RAYS_OK);
     probe_grid_shaded(s, 0);
-    CHECK(probe_grid_check_work(s) == RAYS_STATE);
+    CHECK(s.call.work() == RAYS_STATE);
     printf("ok %d\n", checks);
     return 0;
 }

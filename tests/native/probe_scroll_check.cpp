@@ -170,9 +170,9 @@ int main() {
     CHECK(probe_scroll_check(gs, us, st, true, all, &why) == RAYS_STATE && strstr(why, "moment history's probe count"));
     probe_history_was_reset(us, 1, 30, 4);
     CHECK(probe_scroll_check(gs, us, st, true, all, &why) == RAYS_STATE && strstr(why, "no states"));
-    light_probe_written(st.states, 29);
+    input_written(st.states, 29);
     CHECK(probe_scroll_check(gs, us, st, true, all, &why) == RAYS_STATE && strstr(why, "state count"));
-    light_probe_written(st.states, 30);
+    input_written(st.states, 30);
     CHECK(probe_scroll_check(gs, us, st, true, all, &why) == RAYS_OK);
     bad = all, bad.which = PROBE_SCROLL_STATES;  // the records alone need no history
     ProbeUpdateState none;
@@ -186,20 +186,20 @@ int main() {
     LightProbeState lp;
     ProbeDepthState pd;
     int a0 = 0, a1 = 0;
-    lp.traced = true, lp.last_outputs = LIGHT_PROBE_OUT_ALL, lp.last_dst[0] = &a0, lp.last_dst[1] = &a1, lp.last_probes = 30;
-    pd.traced = true, pd.last_outputs = 3, pd.last_dst[0] = &a0, pd.last_dst[1] = &a1;
+    lp.call.ran = true, lp.last.outputs = LIGHT_PROBE_OUT_ALL, lp.last.dst[0] = &a0, lp.last.dst[1] = &a1, lp.last_probes = 30;
+    pd.call.ran = true, pd.last.outputs = 3, pd.last.dst[0] = &a0, pd.last.dst[1] = &a1;
     probe_scroll_stale(lp, pd);
-    CHECK(lp.last_outputs == LIGHT_PROBE_OUT_RADIANCE && lp.last_dst[0] == nullptr && lp.last_dst[1] == &a1);
-    CHECK(pd.last_outputs == 2 && pd.last_dst[0] == nullptr && pd.last_dst[1] == &a1);
+    CHECK(lp.last.outputs == LIGHT_PROBE_OUT_RADIANCE && lp.last.dst[0] == nullptr && lp.last.dst[1] == &a1);
+    CHECK(pd.last.outputs == 2 && pd.last.dst[0] == nullptr && pd.last.dst[1] == &a1);
     ProbeBlendCall bc;
     probe_blend_call_default(bc);
     CHECK(probe_blend_check(us, lp, pd, st, true, bc, &why) == RAYS_STATE && strstr(why, "did not write COEFFICIENTS"));
-    ProbeScrollState ss;
-    CHECK(probe_scroll_check_work(ss) == RAYS_STATE);
+    CallRecord ss;
+    CHECK(ss.work() == RAYS_STATE);
     probe_scroll_scrolled(ss, 0);
-    CHECK(probe_scroll_check_work(ss) == RAYS_STATE);
+    CHECK(ss.work() == RAYS_STATE);
     probe_scroll_scrolled(ss, PROBE_SCROLL_FLAG_COUNT_WORK | PROBE_SCROLL_FLAG_SET_GRID);
-    CHECK(probe_scroll_check_work(ss) == RAYS_OK);
+    CHECK(ss.work() == RAYS_OK);
     CHECK(probe_scroll_grid(1005, 4, 1024) == 252 && probe_scroll_grid(1005, 4, 100) == 100 && probe_scroll_grid(1, 4, 100) == 1);
     printf("ok %lld\n", checks);
     return 0;

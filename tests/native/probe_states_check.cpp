@@ -33,6 +33,15 @@ struct Obj {  // the fields of srt_object the table reads
     float half_size[3];
 };
 
+// srt_read_probe_states_output's rule as srt_capi.hip composes it: the slot, the shared record's read, the byte count of the last call
+static RaysStatus read_probe_states_output(const ProbeStatesState& s, uint32_t output, const void** src, size_t* bytes) {
+    const int i = probe_state_slot(output);
+    if (i < 0) return RAYS_INVALID_ARG;
+    if (!(*src = s.last.read(output, i))) return RAYS_STATE;
+    *bytes = probe_state_bytes(s.last_probes);
+    return RAYS_OK;
+}
+
 int main() {
     const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
     static_assert(sizeof(ProbeClassifyCall) == 24, "the struct of the header");
@@ -95,21 +104,21 @@ int main() {
     ProbeStatesState s;
     const void* src = nullptr;
     size_t bytes = 0;
-    CHECK(probe_states_check_read(s, 1, &src, &bytes) == RAYS_STATE && probe_states_check_read(s, 3, &src, &bytes) == RAYS_INVALID_ARG);
-    CHECK(probe_states_check_work(s) == RAYS_STATE);
+    CHECK(read_probe_states_output(s, 1, &src, &bytes) == RAYS_STATE && read_probe_states_output(s, 3, &src, &bytes) == RAYS_INVALID_ARG);
+    CHECK(s.call.work() == RAYS_STATE);
     char own0[16], own1[16];
     void* dst[PROBE_STATE_SLOTS] = {own0, own1};
     probe_states_classified(s, 24, c, dst);  // RECORDS only, not counting
-    CHECK(probe_states_check_read(s, 1, &src, &bytes) == RAYS_OK && src == own0 && bytes == 24 * 16);
-    CHECK(probe_states_check_read(s, 2, &src, &bytes) == RAYS_STATE && probe_states_check_work(s) == RAYS_STATE);
+    CHECK(read_probe_states_output(s, 1, &src, &bytes) == RAYS_OK && src == own0 && bytes == 24 * 16);
+    CHECK(read_probe_states_output(s, 2, &src, &bytes) == RAYS_STATE && s.call.work() == RAYS_STATE);
     ProbeClassifyCall both = c;
     both.outputs = PROBE_STATE_OUT_ALL, both.flags = PROBE_CLASSIFY_FLAG_COUNT_WORK;
     probe_states_classified(s, 7, both, dst);
-    CHECK(probe_states_check_read(s, 2, &src, &bytes) == RAYS_OK && src == own1 && bytes == 7 * 16 && probe_states_check_work(s) == RAYS_OK);
-    probe_states_output_released(s, 1, own0);  // another buffer: nothing happens
-    CHECK(probe_states_check_read(s, 2, &src, &bytes) == RAYS_OK);
-    probe_states_output_released(s, 1, own1);
-    CHECK(probe_states_check_read(s, 2, &src, &bytes) == RAYS_STATE && probe_states_check_read(s, 1, &src, &bytes) == RAYS_OK);
+    CHECK(read_probe_states_output(s, 2, &src, &bytes) == RAYS_OK && src == own1 && bytes == 7 * 16 && s.call.work() == RAYS_OK);
+    s.last.released(1, own0);  // another buffer: nothing happens
+    CHECK(read_probe_states_output(s, 2, &src, &bytes) == RAYS_OK);
+    s.last.released(1, own1);
+    CHECK(read_probe_states_output(s, 2, &src, &bytes) == RAYS_STATE && read_probe_states_output(s, 1, &src, &bytes) == RAYS_OK);
     CHECK(probe_classify_grid(729, 4, 1000) == 183 && probe_classify_grid(100000, 4, 1024) == 1024 && probe_classify_grid(1, 4, 1024) == 1);
     // the shading call's checks: the parent's first, then the records
     ProbeGridState pg;
@@ -133,7 +142,7 @@ int main() {
     pg.grid.counts[0] = 3, pg.grid.counts[1] = 2, pg.grid.counts[2] = 4;
     for (int a = 0; a < 3; ++a) pg.grid.spacing[a] = 1.0f;
     CHECK(probe_grid_states_check_shade(pg, pd, st, call, nullptr, true, 20, present, &why) == RAYS_STATE && strstr(why, "no coefficients"));
-    light_probe_written(pg.coefficients, 24);
+    input_written(pg.coefficients, 24);
     CHECK(probe_grid_states_check_shade(pg, pd, st, call, nullptr, true, 20, present, &why) == RAYS_STATE && strstr(why, "no states"));
     CHECK(probe_grid_states_check_shade(pg, pd, st, call, &dc, true, 20, present, &why) == RAYS_STATE && strstr(why, "no depth maps"));  // the parent's come first
     probe_grid_depth_written(pd, 24, 8);
@@ -143,13 +152,13 @@ int main() {
     CHECK(probe_grid_states_check_shade(pg, pd, st, call, &dc, true, 20, present, &why) == RAYS_STATE && strstr(why, "no states"));
     // the state input: written, bound, unbound
     char dev[16];
-    CHECK(light_probe_bind(st.states, dev, 23, PROBE_GRID_MAX_PROBES) == RAYS_OK);
+    CHECK(input_bind(st.states, dev, 23, PROBE_GRID_MAX_PROBES) == RAYS_OK);
     CHECK(probe_grid_states_check_shade(pg, pd, st, call, nullptr, true, 20, present, &why) == RAYS_STATE && strstr(why, "state count"));
-    light_probe_written(st.states, 24);  // a write ends the binding
+    input_written(st.states, 24);  // a write ends the binding
     CHECK(st.states.bound == nullptr && probe_grid_states_check_shade(pg, pd, st, call, nullptr, true, 20, present, &why) == RAYS_OK);
     CHECK(probe_grid_states_check_shade(pg, pd, st, call, &dc, true, 20, present, &why) == RAYS_OK);
-    CHECK(light_probe_bind(st.states, nullptr, 5, PROBE_GRID_MAX_PROBES) == RAYS_INVALID_ARG && light_probe_bind(st.states, dev, 0, PROBE_GRID_MAX_PROBES) == RAYS_INVALID_ARG);
-    CHECK(light_probe_bind(st.states, dev, PROBE_GRID_MAX_PROBES + 1, PROBE_GRID_MAX_PROBES) == RAYS_INVALID_ARG && st.states.count() == 24);
+    CHECK(input_bind(st.states, nullptr, 5, PROBE_GRID_MAX_PROBES) == RAYS_INVALID_ARG && input_bind(st.states, dev, 0, PROBE_GRID_MAX_PROBES) == RAYS_INVALID_ARG);
+    CHECK(input_bind(st.states, dev, PROBE_GRID_MAX_PROBES + 1, PROBE_GRID_MAX_PROBES) == RAYS_INVALID_ARG && st.states.count() == 24);
     vis = call, vis.flags = PROBE_GRID_FLAG_ALBEDO;
     CHECK(probe_grid_states_check_shade(pg, pd, st, vis, nullptr, true, 20, present, &why) == RAYS_STATE && strstr(why, "ALBEDO"));
     printf("ok %d\n", checks);

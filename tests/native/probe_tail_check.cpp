@@ -48,7 +48,7 @@ int main() {
     CHECK(def.bias == 0.0f && def.min_variance == 1e-4f && def.reserved == 0);
     CHECK(probe_tail_check(def, &why) == RAYS_OK && probe_tail_check(def, nullptr) == RAYS_OK);
     ProbeTailState s;
-    CHECK(!s.enabled && !s.traced && !s.counted && probe_tail_check_work(s) == RAYS_STATE && !probe_tail_applies(s, 8));
+    CHECK(!s.enabled && !s.last.ran && !s.last.counted && s.last.work() == RAYS_STATE && !probe_tail_applies(s, 8));
 
     // every refusal: each error hides the later ones
     {
@@ -128,15 +128,15 @@ int main() {
         bad.enabled = 0, bad.min_variance = nan;
         CHECK(probe_tail_check(bad, &why) == RAYS_INVALID_ARG && t.enabled && t.call.bias == 0.5f);
         // the work record: only of a trace that ran with the mode on and counted
-        CHECK(probe_tail_check_work(t) == RAYS_STATE);
-        CHECK(probe_tail_traced(t) && probe_tail_check_work(t) == RAYS_OK);
+        CHECK(t.last.work() == RAYS_STATE);
+        CHECK(probe_tail_traced(t) && t.last.work() == RAYS_OK);
         v.flags = PROBE_TAIL_FLAG_DEPTH;
         probe_tail_set(t, v);
-        CHECK(probe_tail_check_work(t) == RAYS_OK);  // (setting the mode is not a trace: the last trace's record stands)
-        CHECK(!probe_tail_traced(t) && probe_tail_check_work(t) == RAYS_STATE);
+        CHECK(t.last.work() == RAYS_OK);  // (setting the mode is not a trace: the last trace's record stands)
+        CHECK(!probe_tail_traced(t) && t.last.work() == RAYS_STATE);
         v.flags = PROBE_TAIL_FLAG_COUNT_WORK, v.enabled = 0;
         probe_tail_set(t, v);
-        CHECK(!t.enabled && !probe_tail_applies(t, 8) && !probe_tail_traced(t) && probe_tail_check_work(t) == RAYS_STATE);
+        CHECK(!t.enabled && !probe_tail_applies(t, 8) && !probe_tail_traced(t) && t.last.work() == RAYS_STATE);
     }
 
     // the overlap predicate

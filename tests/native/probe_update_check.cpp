@@ -24,6 +24,13 @@ static int checks = 0;
         }                                                        \
     } while (0)
 
+// srt_read_probe_list_output's rule as srt_capi.hip composes it: the shared record's read of the one output, the byte count of the last listing
+static RaysStatus read_probe_list_output(const ProbeUpdateState& s, const void** src, size_t* bytes) {
+    if (!(*src = s.list_last.read(1u, 0))) return RAYS_STATE;
+    *bytes = probe_list_bytes(s.list_probes);
+    return RAYS_OK;
+}
+
 int main() {
     const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
     static_assert(sizeof(ProbeListCall) == 16 && sizeof(ProbeBlendCall) == 24, "the structs of the header");
@@ -52,7 +59,7 @@ int main() {
     bad = lc, bad.reserved[1] = 1;
     CHECK(probe_list_check(g, st, true, bad, &why) == RAYS_INVALID_ARG && strstr(why, "reserved"));
     CHECK(probe_list_check(g, st, true, lc, &why) == RAYS_STATE && strstr(why, "no states"));
-    light_probe_written(st.states, 24);
+    input_written(st.states, 24);
     CHECK(probe_list_check(g, st, true, lc, nullptr) == RAYS_OK);  // without a grid any count goes
     g.grid_set = true;
     g.grid.counts[0] = 3, g.grid.counts[1] = 2, g.grid.counts[2] = 5;
@@ -66,16 +73,16 @@ int main() {
     ProbeUpdateState s;
     const void* src = nullptr;
     size_t bytes = 0;
-    CHECK(probe_list_check_read(s, &src, &bytes) == RAYS_STATE && probe_list_check_work(s) == RAYS_STATE);
+    CHECK(read_probe_list_output(s, &src, &bytes) == RAYS_STATE && s.list_call.work() == RAYS_STATE);
     char own[16], other[16];
     probe_list_listed(s, 24, 0, own);
-    CHECK(probe_list_check_read(s, &src, &bytes) == RAYS_OK && src == own && bytes == 28 * 4 && probe_list_check_work(s) == RAYS_STATE);
+    CHECK(read_probe_list_output(s, &src, &bytes) == RAYS_OK && src == own && bytes == 28 * 4 && s.list_call.work() == RAYS_STATE);
     probe_list_listed(s, 7, PROBE_LIST_FLAG_COUNT_WORK, own);
-    CHECK(probe_list_check_read(s, &src, &bytes) == RAYS_OK && bytes == 11 * 4 && probe_list_check_work(s) == RAYS_OK);
-    probe_list_output_released(s, other);  // another buffer: nothing happens
-    CHECK(probe_list_check_read(s, &src, &bytes) == RAYS_OK);
-    probe_list_output_released(s, own);
-    CHECK(probe_list_check_read(s, &src, &bytes) == RAYS_STATE);
+    CHECK(read_probe_list_output(s, &src, &bytes) == RAYS_OK && bytes == 11 * 4 && s.list_call.work() == RAYS_OK);
+    s.list_last.released(0, other);  // another buffer: nothing happens
+    CHECK(read_probe_list_output(s, &src, &bytes) == RAYS_OK);
+    s.list_last.released(0, own);
+    CHECK(read_probe_list_output(s, &src, &bytes) == RAYS_STATE);
     // the list bound for tracing
     CHECK(probe_list_check_trace(s, 24, &why) == RAYS_STATE && strstr(why, "no list"));
     CHECK(probe_list_bind(s, own, 4) == RAYS_INVALID_ARG && probe_list_bind(s, own, 0) == RAYS_INVALID_ARG && probe_list_bind(s, nullptr, 28) == RAYS_INVALID_ARG);
@@ -83,7 +90,7 @@ int main() {
     CHECK(probe_list_capacity_ok(5) && probe_list_capacity_ok(((size_t)1 << 30) + 4) && !probe_list_capacity_ok(4) && !probe_list_capacity_ok(0));
     CHECK(probe_list_bind(s, own, 27) == RAYS_OK && probe_list_check_trace(s, 24, &why) == RAYS_STATE && strstr(why, "capacity"));
     CHECK(probe_list_bind(s, own, 28) == RAYS_OK && probe_list_check_trace(s, 24, nullptr) == RAYS_OK && probe_list_check_trace(s, 23, &why) == RAYS_STATE);
-    light_probe_written(s.list, 28);  // a write ends the binding
+    input_written(s.list, 28);  // a write ends the binding
     CHECK(s.list.bound == nullptr && probe_list_check_trace(s, 24, &why) == RAYS_OK);
     CHECK(probe_list_bind(s, own, 11) == RAYS_OK && probe_list_bind(s, nullptr, 0) == RAYS_OK && s.list.count() == 28);  // unbound: back to the own array
     // the histories
@@ -131,7 +138,7 @@ int main() {
     CHECK(probe_blend_check(s, lp, pd, cur, true, bc, &why) == RAYS_STATE && strstr(why, "another probe count"));
     light_probe_traced(lp, 24, 64, LIGHT_PROBE_OUT_COEFFICIENTS, ldst, 0);
     CHECK(probe_blend_check(s, lp, pd, cur, true, bc, nullptr) == RAYS_OK);
-    light_probe_output_released(lp, 0, co);  // the own output was re-allocated: its data are gone
+    lp.last.released(0, co);  // the own output was re-allocated: its data are gone
     CHECK(probe_blend_check(s, lp, pd, cur, true, bc, &why) == RAYS_STATE);
     light_probe_traced(lp, 24, 64, LIGHT_PROBE_OUT_COEFFICIENTS, ldst, 0);
     // ... the moments
@@ -153,26 +160,26 @@ int main() {
     // ... the list
     b.flags |= PROBE_BLEND_FLAG_LISTED;
     CHECK(probe_blend_check(s, lp, pd, cur, true, b, &why) == RAYS_OK);  // the own list of 28 words
-    light_probe_written(s.list, 27);
+    input_written(s.list, 27);
     CHECK(probe_blend_check(s, lp, pd, cur, true, b, &why) == RAYS_STATE && strstr(why, "capacity"));
-    light_probe_written(s.list, 28);
+    input_written(s.list, 28);
     // ... the records
     b.flags |= PROBE_BLEND_FLAG_PREVIOUS_STATES;
     CHECK(probe_blend_check(s, lp, pd, cur, true, b, &why) == RAYS_STATE && strstr(why, "no states"));
-    light_probe_written(cur.states, 23);
+    input_written(cur.states, 23);
     CHECK(probe_blend_check(s, lp, pd, cur, true, b, &why) == RAYS_STATE && strstr(why, "state count"));
-    light_probe_written(cur.states, 24);
+    input_written(cur.states, 24);
     CHECK(probe_blend_check(s, lp, pd, cur, true, b, &why) == RAYS_STATE && strstr(why, "no previous states"));
-    CHECK(light_probe_bind(s.previous, own, 25, PROBE_GRID_MAX_PROBES) == RAYS_OK);
+    CHECK(input_bind(s.previous, own, 25, PROBE_GRID_MAX_PROBES) == RAYS_OK);
     CHECK(probe_blend_check(s, lp, pd, cur, true, b, &why) == RAYS_STATE && strstr(why, "previous state count"));
-    light_probe_written(s.previous, 24);
+    input_written(s.previous, 24);
     CHECK(probe_blend_check(s, lp, pd, cur, true, b, &why) == RAYS_OK);
     // the work record and a lost history
-    CHECK(probe_blend_check_work(s) == RAYS_STATE);
+    CHECK(s.blend_call.work() == RAYS_STATE);
     probe_blend_blended(s, b.flags);
-    CHECK(probe_blend_check_work(s) == RAYS_STATE);
+    CHECK(s.blend_call.work() == RAYS_STATE);
     probe_blend_blended(s, b.flags | PROBE_BLEND_FLAG_COUNT_WORK);
-    CHECK(probe_blend_check_work(s) == RAYS_OK);
+    CHECK(s.blend_call.work() == RAYS_OK);
     probe_history_lost(s, 0);
     CHECK(probe_history_check_read(s, 1, &slot, &bytes) == RAYS_STATE && probe_blend_check(s, lp, pd, cur, true, bc, &why) == RAYS_STATE);
     CHECK(probe_blend_grid(210, 4, 1024) == 53 && probe_blend_grid(8925, 4, 1024) == 1024 && probe_blend_grid(1, 4, 1024) == 1);

@@ -13,6 +13,8 @@
 
 using namespace srt;
 
+#include "read_ray_output.h"
+
 static int failures = 0;
 #define CHECK(cond)                                                     \
     do {                                                                \
@@ -22,10 +24,17 @@ static int failures = 0;
         }                                                               \
     } while (0)
 
+// srt_read_radiance's rule as srt_capi.hip composes it: the shared record's read of the one output, the byte count of the last trace
+static RaysStatus read_radiance(const RadianceState& r, const void** src, size_t* bytes) {
+    if (!(*src = r.last.read(1u, 0))) return RAYS_STATE;
+    *bytes = r.last_count * 4 * sizeof(float);
+    return RAYS_OK;
+}
+
 static bool same(const RaysState& a, const RaysState& b) {
-    bool eq = a.bound_origin == b.bound_origin && a.bound_direction == b.bound_direction && a.bound_count == b.bound_count && a.own_count == b.own_count &&
-              a.last_count == b.last_count && a.last_outputs == b.last_outputs;
-    for (int i = 0; i < RAYS_SLOTS; ++i) eq = eq && a.last_dst[i] == b.last_dst[i];
+    bool eq = a.origins.bound == b.origins.bound && a.bound_direction == b.bound_direction && a.origins.bound_count == b.origins.bound_count && a.origins.own_count == b.origins.own_count &&
+              a.last_count == b.last_count && a.last.outputs == b.last.outputs;
+    for (int i = 0; i < RAYS_SLOTS; ++i) eq = eq && a.last.dst[i] == b.last.dst[i];
     return eq;
 }
 
@@ -57,7 +66,7 @@ int main() {
     const char* why = nullptr;
     const void* src = nullptr;
     size_t bytes = 0;
-    CHECK(radiance_check_work(r) == RAYS_STATE && radiance_check_read(r, &src, &bytes) == RAYS_STATE);  // no trace yet
+    CHECK(r.call.work() == RAYS_STATE && read_radiance(r, &src, &bytes) == RAYS_STATE);  // no trace yet
     const RadianceCall ok = call(1, 16, 8, RADIANCE_FLAG_RESET);
     CHECK(radiance_check_trace(s, false, ok, &why) == RAYS_STATE && std::strstr(why, "srt_set_scene"));
     CHECK(radiance_check_trace(s, false, call(0, 0, -1, 8), &why) == RAYS_STATE);                                 // the scene comes first
@@ -92,30 +101,30 @@ int main() {
         const RaysState before = s;
         radiance_traced(r, s.count(), &own, RADIANCE_FLAG_RESET);
         CHECK(same(s, before));
-        for (uint32_t bit = 1; bit <= 16; bit <<= 1) CHECK(rays_check_read(s, bit, &src, &bytes) == RAYS_OK);
+        for (uint32_t bit = 1; bit <= 16; bit <<= 1) CHECK(read_ray_output(s, bit, &src, &bytes) == RAYS_OK);
     }
-    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_OK && src == &own && bytes == 3 * 16);
-    CHECK(radiance_check_work(r) == RAYS_STATE);  // traced, but not counted
+    CHECK(read_radiance(r, &src, &bytes) == RAYS_OK && src == &own && bytes == 3 * 16);
+    CHECK(r.call.work() == RAYS_STATE);  // traced, but not counted
     // a later bind changes the current rays, not what the last trace wrote; the next trace takes the new count
     CHECK(rays_bind(s, a.data(), b.data(), 9) == RAYS_OK);
-    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_OK && bytes == 3 * 16);
+    CHECK(read_radiance(r, &src, &bytes) == RAYS_OK && bytes == 3 * 16);
     radiance_traced(r, s.count(), &other, RADIANCE_FLAG_COUNT_WORK | RADIANCE_FLAG_NORMALIZE);
-    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_OK && src == &other && bytes == 9 * 16);
-    CHECK(radiance_check_work(r) == RAYS_OK);
+    CHECK(read_radiance(r, &src, &bytes) == RAYS_OK && src == &other && bytes == 9 * 16);
+    CHECK(r.call.work() == RAYS_OK);
     radiance_traced(r, s.count(), &other, RADIANCE_FLAG_RESET);  // a trace without the flag ends the record
-    CHECK(radiance_check_work(r) == RAYS_STATE);
+    CHECK(r.call.work() == RAYS_STATE);
     radiance_traced(r, s.count(), &own, RADIANCE_FLAG_COUNT_WORK);
-    CHECK(radiance_check_work(r) == RAYS_OK);
+    CHECK(r.call.work() == RAYS_OK);
     // a refused check in between changes neither
-    CHECK(radiance_check_trace(s, true, call(1, 0, 8, 1), &why) == RAYS_INVALID_ARG && radiance_check_work(r) == RAYS_OK &&
-          radiance_check_read(r, &src, &bytes) == RAYS_OK && src == &own);
+    CHECK(radiance_check_trace(s, true, call(1, 0, 8, 1), &why) == RAYS_INVALID_ARG && r.call.work() == RAYS_OK &&
+          read_radiance(r, &src, &bytes) == RAYS_OK && src == &own);
     // the own buffer is re-allocated: the result goes with it; another buffer's release does not matter
-    radiance_output_released(r, &other);
-    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_OK);
-    radiance_output_released(r, nullptr);
-    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_OK);
-    radiance_output_released(r, &own);
-    CHECK(radiance_check_read(r, &src, &bytes) == RAYS_STATE);
+    r.last.released(0, &other);
+    CHECK(read_radiance(r, &src, &bytes) == RAYS_OK);
+    r.last.released(0, nullptr);
+    CHECK(read_radiance(r, &src, &bytes) == RAYS_OK);
+    r.last.released(0, &own);
+    CHECK(read_radiance(r, &src, &bytes) == RAYS_STATE);
 
     // the grid: blocks of 64 rays, four to a workgroup, at most the resident workgroups, never none
     const long long resident = 1024;

@@ -11,6 +11,8 @@
 
 using namespace srt;
 
+#include "read_ray_output.h"
+
 static int failures = 0;
 #define CHECK(cond)                                                     \
     do {                                                                \
@@ -21,9 +23,9 @@ static int failures = 0;
     } while (0)
 
 static bool same(const RaysState& a, const RaysState& b) {
-    bool eq = a.bound_origin == b.bound_origin && a.bound_direction == b.bound_direction && a.bound_count == b.bound_count && a.own_count == b.own_count &&
-              a.last_count == b.last_count && a.last_outputs == b.last_outputs;
-    for (int i = 0; i < RAYS_SLOTS; ++i) eq = eq && a.last_dst[i] == b.last_dst[i];
+    bool eq = a.origins.bound == b.origins.bound && a.bound_direction == b.bound_direction && a.origins.bound_count == b.origins.bound_count && a.origins.own_count == b.origins.own_count &&
+              a.last_count == b.last_count && a.last.outputs == b.last.outputs;
+    for (int i = 0; i < RAYS_SLOTS; ++i) eq = eq && a.last.dst[i] == b.last.dst[i];
     return eq;
 }
 
@@ -85,21 +87,21 @@ int main() {
     // the record of the last trace
     const void* src = nullptr;
     size_t bytes = 0;
-    for (uint32_t bit = 1; bit <= 16; bit <<= 1) CHECK(rays_check_read(s, bit, &src, &bytes) == RAYS_STATE);
-    CHECK(rays_check_read(s, 3, &src, &bytes) == RAYS_INVALID_ARG && rays_check_read(s, 0, &src, &bytes) == RAYS_INVALID_ARG);
+    for (uint32_t bit = 1; bit <= 16; bit <<= 1) CHECK(read_ray_output(s, bit, &src, &bytes) == RAYS_STATE);
+    CHECK(read_ray_output(s, 3, &src, &bytes) == RAYS_INVALID_ARG && read_ray_output(s, 0, &src, &bytes) == RAYS_INVALID_ARG);
     int dummy[RAYS_SLOTS];
     void* dst[RAYS_SLOTS] = {&dummy[0], &dummy[1], &dummy[2], &dummy[3], &dummy[4]};
     rays_traced(s, RAYS_OUT_OBJECT | RAYS_OUT_POSITION | RAYS_OUT_OCCLUDED, dst);
-    CHECK(rays_check_read(s, 1, &src, &bytes) == RAYS_OK && src == dst[0] && bytes == 3 * 4);
-    CHECK(rays_check_read(s, 4, &src, &bytes) == RAYS_OK && src == dst[2] && bytes == 3 * 16);
-    CHECK(rays_check_read(s, 16, &src, &bytes) == RAYS_OK && src == dst[4] && bytes == 3 * 4);
-    CHECK(rays_check_read(s, 2, &src, &bytes) == RAYS_STATE && rays_check_read(s, 8, &src, &bytes) == RAYS_STATE);
+    CHECK(read_ray_output(s, 1, &src, &bytes) == RAYS_OK && src == dst[0] && bytes == 3 * 4);
+    CHECK(read_ray_output(s, 4, &src, &bytes) == RAYS_OK && src == dst[2] && bytes == 3 * 16);
+    CHECK(read_ray_output(s, 16, &src, &bytes) == RAYS_OK && src == dst[4] && bytes == 3 * 4);
+    CHECK(read_ray_output(s, 2, &src, &bytes) == RAYS_STATE && read_ray_output(s, 8, &src, &bytes) == RAYS_STATE);
     // a later bind changes the current rays, not what the last trace wrote
     CHECK(rays_bind(s, a.data(), b.data(), 9) == RAYS_OK);
-    CHECK(rays_check_read(s, 1, &src, &bytes) == RAYS_OK && bytes == 3 * 4);
+    CHECK(read_ray_output(s, 1, &src, &bytes) == RAYS_OK && bytes == 3 * 4);
     rays_traced(s, RAYS_OUT_ALBEDO, dst);
-    CHECK(rays_check_read(s, 8, &src, &bytes) == RAYS_OK && src == dst[3] && bytes == 9 * 16);
-    CHECK(rays_check_read(s, 1, &src, &bytes) == RAYS_STATE);
+    CHECK(read_ray_output(s, 8, &src, &bytes) == RAYS_OK && src == dst[3] && bytes == 9 * 16);
+    CHECK(read_ray_output(s, 1, &src, &bytes) == RAYS_STATE);
 
     // the grid: never more workgroups than blocks of 64 rays need, never more than are resident, never none
     CHECK(rays_grid(1, 4, 1024) == 1 && rays_grid(64, 4, 1024) == 1 && rays_grid(256, 4, 1024) == 1 && rays_grid(257, 4, 1024) == 2);

@@ -147,13 +147,13 @@ int main() {
 
     // slots, binding, the read rule and the record of the last call
     ReflectionSlots slots;
-    ReflectionState s;
+    CallRecord s;
     const void* src = nullptr;
     int own_obj, own_nd, own_pos, own_alb, own_j, mine;
     const void* none[REFL_SLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     for (uint32_t o : {1u, 2u, 4u, 8u, 16u}) CHECK(reflection_check_read(slots, o, none, &src) == RAYS_STATE);  // neither bound nor rendered
     for (uint32_t o : {0u, 3u, 31u, 32u}) CHECK(reflection_check_read(slots, o, none, &src) == RAYS_INVALID_ARG);
-    CHECK(reflection_check_work(s) == RAYS_STATE);  // no call yet
+    CHECK(s.work() == RAYS_STATE);  // no call yet
     // a bound buffer is readable at once (srt_read_gbuffer's rule), the others still are not
     slots.out[3].bind(&mine);
     CHECK(reflection_check_read(slots, REFL_OUT_ALBEDO, none, &src) == RAYS_OK && src == &mine);
@@ -164,7 +164,7 @@ int main() {
         CHECK(slots.out[0].target(0, 100).own && slots.out[0].target(0, 100).grow && !slots.out[3].target(0, 100).own && !slots.out[3].target(0, 100).grow);
         void* dst[REFL_SLOTS] = {&own_obj, nullptr, nullptr, &mine, &own_j};
         reflection_rendered(s, slots, REFL_OUT_OBJECT | REFL_OUT_ALBEDO | REFL_OUT_BOUNCES, dst, 0);
-        CHECK(s.rendered && !s.counted && reflection_check_work(s) == RAYS_STATE);
+        CHECK(s.ran && !s.counted && s.work() == RAYS_STATE);
         CHECK(reflection_check_read(slots, REFL_OUT_OBJECT, own, &src) == RAYS_OK && src == &own_obj);
         CHECK(reflection_check_read(slots, REFL_OUT_BOUNCES, own, &src) == RAYS_OK && src == &own_j);
         CHECK(reflection_check_read(slots, REFL_OUT_ALBEDO, own, &src) == RAYS_OK && src == &mine);
@@ -177,7 +177,7 @@ int main() {
         const void* own[REFL_SLOTS] = {&own_obj, &own_nd, &own_pos, &own_alb, &own_j};
         void* dst[REFL_SLOTS] = {&own_obj, &own_nd, &own_pos, &mine, &own_j};
         reflection_rendered(s, slots, REFL_OUT_ALL, dst, REFL_FLAG_COUNT_WORK);
-        CHECK(s.counted && reflection_check_work(s) == RAYS_OK);
+        CHECK(s.counted && s.work() == RAYS_OK);
         CHECK(reflection_check_read(slots, REFL_OUT_ALBEDO, own, &src) == RAYS_OK && src == &mine);
         slots.out[3].bind(nullptr);
         CHECK(reflection_check_read(slots, REFL_OUT_ALBEDO, own, &src) == RAYS_OK && src == &own_alb);
@@ -185,11 +185,11 @@ int main() {
         // a refused check in between changes nothing
         ReflectionCall v = good;
         v.max_bounces = 65;
-        CHECK(reflection_check(v, true, true, H, &why) == RAYS_INVALID_ARG && s.rendered && s.counted && reflection_check_work(s) == RAYS_OK);
+        CHECK(reflection_check(v, true, true, H, &why) == RAYS_INVALID_ARG && s.ran && s.counted && s.work() == RAYS_OK);
         // a call without the flag ends the record
         void* one[REFL_SLOTS] = {nullptr, nullptr, nullptr, nullptr, &own_j};
         reflection_rendered(s, slots, REFL_OUT_BOUNCES, one, 0);
-        CHECK(s.rendered && !s.counted && reflection_check_work(s) == RAYS_STATE);
+        CHECK(s.ran && !s.counted && s.work() == RAYS_STATE);
         CHECK(slots.out[0].last == &own_obj);  // an output not asked for keeps its record
     }
 

@@ -23,8 +23,15 @@ static int failures = 0;
         }                                                               \
     } while (0)
 
+// srt_read_visibility's rule as srt_capi.hip composes it: the slot, then the shared record's read
+static RaysStatus read_visibility(const VisibilityState& s, uint32_t output, const void** src) {
+    const int i = visibility_slot(output);
+    if (i < 0) return RAYS_INVALID_ARG;
+    return (*src = s.last.read(output, i)) ? RAYS_OK : RAYS_STATE;
+}
+
 static bool same(const VisibilityState& a, const VisibilityState& b) {
-    return a.rendered == b.rendered && a.counted == b.counted && a.last_outputs == b.last_outputs && a.last_dst[0] == b.last_dst[0] && a.last_dst[1] == b.last_dst[1];
+    return a.call.ran == b.call.ran && a.call.counted == b.call.counted && a.last.outputs == b.last.outputs && a.last.dst[0] == b.last.dst[0] && a.last.dst[1] == b.last.dst[1];
 }
 
 int main() {
@@ -129,14 +136,14 @@ int main() {
     VisibilityState s;
     const void* src = nullptr;
     float ao_buf, sun_buf, other;
-    CHECK(visibility_check_read(s, SRT_VIS_AO, &src) == RAYS_STATE && visibility_check_read(s, SRT_VIS_SUN, &src) == RAYS_STATE);
-    CHECK(visibility_check_read(s, 3, &src) == RAYS_INVALID_ARG && visibility_check_read(s, 0, &src) == RAYS_INVALID_ARG);
-    CHECK(visibility_check_work(s) == RAYS_STATE);  // no call yet
+    CHECK(read_visibility(s, SRT_VIS_AO, &src) == RAYS_STATE && read_visibility(s, SRT_VIS_SUN, &src) == RAYS_STATE);
+    CHECK(read_visibility(s, 3, &src) == RAYS_INVALID_ARG && read_visibility(s, 0, &src) == RAYS_INVALID_ARG);
+    CHECK(s.call.work() == RAYS_STATE);  // no call yet
     void* both[VIS_SLOTS] = {&ao_buf, &sun_buf};
     visibility_rendered(s, VIS_OUT_ALL, both, 0);
-    CHECK(visibility_check_read(s, SRT_VIS_AO, &src) == RAYS_OK && src == &ao_buf);
-    CHECK(visibility_check_read(s, SRT_VIS_SUN, &src) == RAYS_OK && src == &sun_buf);
-    CHECK(visibility_check_work(s) == RAYS_STATE);  // rendered, but not counted
+    CHECK(read_visibility(s, SRT_VIS_AO, &src) == RAYS_OK && src == &ao_buf);
+    CHECK(read_visibility(s, SRT_VIS_SUN, &src) == RAYS_OK && src == &sun_buf);
+    CHECK(s.call.work() == RAYS_STATE);  // rendered, but not counted
     // a refused check in between changes nothing
     {
         const VisibilityState before = s;
@@ -147,13 +154,13 @@ int main() {
     // AO alone, to another buffer: SUN is no longer readable, and the slot of an output not asked for is not recorded
     void* moved[VIS_SLOTS] = {&other, &sun_buf};
     visibility_rendered(s, VIS_OUT_AO, moved, VIS_FLAG_COUNT_WORK);
-    CHECK(visibility_check_read(s, SRT_VIS_AO, &src) == RAYS_OK && src == &other);
-    CHECK(visibility_check_read(s, SRT_VIS_SUN, &src) == RAYS_STATE && s.last_dst[1] == nullptr);
-    CHECK(visibility_check_work(s) == RAYS_OK);
+    CHECK(read_visibility(s, SRT_VIS_AO, &src) == RAYS_OK && src == &other);
+    CHECK(read_visibility(s, SRT_VIS_SUN, &src) == RAYS_STATE && s.last.dst[1] == nullptr);
+    CHECK(s.call.work() == RAYS_OK);
     void* sun_only[VIS_SLOTS] = {nullptr, &sun_buf};
     visibility_rendered(s, VIS_OUT_SUN, sun_only, 0);  // a call without the flag ends the record
-    CHECK(visibility_check_read(s, SRT_VIS_SUN, &src) == RAYS_OK && src == &sun_buf && visibility_check_read(s, SRT_VIS_AO, &src) == RAYS_STATE);
-    CHECK(visibility_check_work(s) == RAYS_STATE);
+    CHECK(read_visibility(s, SRT_VIS_SUN, &src) == RAYS_OK && src == &sun_buf && read_visibility(s, SRT_VIS_AO, &src) == RAYS_STATE);
+    CHECK(s.call.work() == RAYS_STATE);
 
     if (failures) return 1;
     std::printf("ok visibility host rules\n");
