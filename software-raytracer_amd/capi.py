@@ -264,18 +264,24 @@ class TraceParams(C.Structure):
     _fields_ = [("outputs", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class WorkRecord(C.Structure):
+    """The base of the records a pass leaves of its last call (srt_*_work, srt_work_counts, srt_update_info)."""
+
+    def as_dict(self):
+        """Every field but `reserved` and `spare` as an int, an array field as a list of ints."""
+        values = ((n, getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "spare"))
+        return {n: [int(x) for x in v] if isinstance(v, C.Array) else int(v) for n, v in values}
+
+
 class OcclusionParams(C.Structure):
     """srt_occlusion_params: OCCLUSION_* flags; reserved must be 0."""
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-class OcclusionWork(C.Structure):
+class OcclusionWork(WorkRecord):
     """srt_occlusion_work: lane-level tests executed by the last counting srt_trace_occlusion for rays of its batch."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("rays", C.c_uint64), ("occluded", C.c_uint64),
                 ("analytic_tests", C.c_uint64), ("node_visits", C.c_uint64), ("triangle_tests", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class VisibilityParams(C.Structure):
@@ -284,13 +290,10 @@ class VisibilityParams(C.Structure):
                 ("ao_samples", C.c_uint32), ("first_sample", C.c_uint32), ("seed", C.c_uint32), ("ao_radius", C.c_float)]
 
 
-class VisibilityWork(C.Structure):
+class VisibilityWork(WorkRecord):
     """srt_visibility_work: what the last counting srt_render_visibility traced."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("segments", C.c_uint64), ("open", C.c_uint64), ("wave_trips", C.c_uint64),
                 ("analytic_tests", C.c_uint64), ("node_visits", C.c_uint64), ("triangle_tests", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class ReflectionParams(C.Structure):
@@ -300,13 +303,10 @@ class ReflectionParams(C.Structure):
                 ("max_bounces", C.c_int32), ("min_smoothness", C.c_float), ("min_specular", C.c_float), ("reserved", C.c_uint32)]
 
 
-class ReflectionWork(C.Structure):
+class ReflectionWork(WorkRecord):
     """srt_reflection_work: what the last counting srt_render_reflection_gbuffer traced."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_uint64), ("reflections", C.c_uint64),
                 ("wave_calls", C.c_uint64), ("waves", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class MirrorHistoryParams(C.Structure):
@@ -323,13 +323,10 @@ class ProbeTailParams(C.Structure):
                 ("min_variance", C.c_float), ("reserved", C.c_uint32)]
 
 
-class ProbeTailWork(C.Structure):
+class ProbeTailWork(WorkRecord):
     """srt_probe_tail_work: the lookups of the last trace that ran under srt_probe_tail with PROBE_TAIL_COUNT_WORK."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("tails", C.c_uint64), ("corners", C.c_uint64), ("open", C.c_uint64),
                 ("dark", C.c_uint64), ("mirror_ends", C.c_uint64), ("wave_lookups", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class RadianceParams(C.Structure):
@@ -338,13 +335,10 @@ class RadianceParams(C.Structure):
                 ("id_base", C.c_uint32), ("flags", C.c_uint32)]
 
 
-class RadianceWork(C.Structure):
+class RadianceWork(WorkRecord):
     """srt_radiance_work: what the last counting srt_trace_radiance traced."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("rays", C.c_uint64), ("samples", C.c_uint64),
                 ("closest_calls", C.c_uint64), ("wave_calls", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class AdaptiveParams(C.Structure):
@@ -353,13 +347,10 @@ class AdaptiveParams(C.Structure):
                 ("max_samples", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-class AdaptiveWork(C.Structure):
+class AdaptiveWork(WorkRecord):
     """srt_adaptive_work: what the last counting srt_render_adaptive traced."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_uint64), ("samples", C.c_uint64),
                 ("closest_calls", C.c_uint64), ("wave_calls", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class BudgetParams(C.Structure):
@@ -373,13 +364,10 @@ class LightProbeParams(C.Structure):
                 ("id_base", C.c_uint32), ("flags", C.c_uint32), ("outputs", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-class LightProbeWork(C.Structure):
+class LightProbeWork(WorkRecord):
     """srt_light_probe_work: what the last counting srt_trace_light_probes traced."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("rays", C.c_uint64), ("samples", C.c_uint64),
                 ("closest_calls", C.c_uint64), ("wave_calls", C.c_uint64), ("waves", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class ProbeGrid(C.Structure):
@@ -393,14 +381,11 @@ class ProbeGridParams(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
-class ProbeGridWork(C.Structure):
+class ProbeGridWork(WorkRecord):
     """srt_probe_grid_work: what the last counting srt_shade_probe_grid did."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_uint64), ("corners", C.c_uint64), ("segments", C.c_uint64),
                 ("open", C.c_uint64), ("wave_trips", C.c_uint64), ("analytic_tests", C.c_uint64), ("node_visits", C.c_uint64),
                 ("triangle_tests", C.c_uint64), ("waves", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class ProbeDepthParams(C.Structure):
@@ -409,13 +394,10 @@ class ProbeDepthParams(C.Structure):
                 ("outputs", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-class ProbeDepthWork(C.Structure):
+class ProbeDepthWork(WorkRecord):
     """srt_probe_depth_work: what the last counting srt_trace_probe_depth traced."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("rays", C.c_uint64), ("far_rays", C.c_uint64),
                 ("wave_calls", C.c_uint64), ("waves", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class ProbeGridDepthParams(C.Structure):
@@ -430,13 +412,10 @@ class ProbeClassifyParams(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
-class ProbeClassifyWork(C.Structure):
+class ProbeClassifyWork(WorkRecord):
     """srt_probe_classify_work: what the last counting srt_classify_probes found."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("inside", C.c_uint64), ("moved", C.c_uint64),
                 ("buried", C.c_uint64), ("idle", C.c_uint64), ("candidates", C.c_uint64), ("waves", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class ProbeListParams(C.Structure):
@@ -444,12 +423,9 @@ class ProbeListParams(C.Structure):
     _fields_ = [("skip_mask", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
-class ProbeListWork(C.Structure):
+class ProbeListWork(WorkRecord):
     """srt_probe_list_work: what the last counting srt_list_probes found."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("listed", C.c_uint64), ("waves", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class ProbeBlendParams(C.Structure):
@@ -458,13 +434,10 @@ class ProbeBlendParams(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-class ProbeBlendWork(C.Structure):
+class ProbeBlendWork(WorkRecord):
     """srt_probe_blend_work: what the last counting srt_blend_probes did."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("restarted", C.c_uint64), ("changed", C.c_uint64),
                 ("waves", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class ProbeScrollParams(C.Structure):
@@ -472,13 +445,10 @@ class ProbeScrollParams(C.Structure):
     _fields_ = [("shift", C.c_int32 * 3), ("which", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
-class ProbeScrollWork(C.Structure):
+class ProbeScrollWork(WorkRecord):
     """srt_probe_scroll_work: what the last counting srt_scroll_probes did."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.c_uint64), ("retained", C.c_uint64), ("exposed", C.c_uint64),
                 ("waves", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class ProbeCascade(C.Structure):
@@ -495,25 +465,17 @@ class ProbeCascadeParams(C.Structure):
                 ("min_variance", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
-class ProbeCascadeWork(C.Structure):
+class ProbeCascadeWork(WorkRecord):
     """srt_probe_cascade_work: what the last counting srt_shade_probe_cascade did."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_uint64), ("evaluations", C.c_uint64), ("blended", C.c_uint64),
                 ("first_level", C.c_uint64 * PROBE_CASCADE_MAX_LEVELS), ("corners", C.c_uint64), ("open", C.c_uint64), ("wave_trips", C.c_uint64),
                 ("waves", C.c_uint64), ("spare", C.c_uint64 * 2)]
 
-    def as_dict(self):
-        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "spare", "first_level")}
-        d["first_level"] = [int(v) for v in self.first_level]
-        return d
 
-
-class UpdateInfo(C.Structure):
+class UpdateInfo(WorkRecord):
     """srt_update_info: what the last successful srt_update_scene did to the mesh image."""
     _fields_ = [("path", C.c_int32), ("reason", C.c_int32), ("levels", C.c_int32), ("triangles", C.c_uint32), ("nodes", C.c_uint32),
                 ("moved_mesh_objects", C.c_uint32)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -521,14 +483,11 @@ class Stats(C.Structure):
                 ("tile_rows", C.c_uint32), ("chunk_samples", C.c_uint32), ("shape_source", C.c_uint32)]
 
 
-class WorkCounts(C.Structure):
+class WorkCounts(WorkRecord):
     """srt_work_counts: what one render's kernels executed (SRT_RENDER_COUNT_WORK)."""
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32)] + [(n, C.c_uint64) for n in (
         "waves", "pool_steps", "closest_hit_calls", "uniform_sphere_tests", "cluster_bound_tests", "cluster_sphere_tests",
         "cluster_items", "box_tests", "bvh_child_tests", "triangle_tests", "bvh_node_rounds", "mesh_phases")]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 def lib_path():
@@ -576,319 +535,317 @@ def load_library():
     return _lib
 
 
+_ctx = C.c_void_p
+# the parameter types of every export, one line each, as include/srt_pathtrace.h declares them (tests/test_capi_exports.py compares)
+_PROTOTYPES = {
+    "srt_abi_version": [],
+    "srt_device_count": [C.POINTER(C.c_int)],
+    "srt_create": [C.c_int, C.c_int, C.c_int, C.POINTER(_ctx)],
+    "srt_destroy": [_ctx],
+    "srt_last_error": [_ctx],
+    "srt_set_scene": [_ctx, C.POINTER(Object), C.c_size_t],
+    "srt_set_meshes": [_ctx, C.POINTER(Mesh), C.c_size_t],
+    "srt_set_environment": [_ctx, C.POINTER(Environment)],
+    "srt_environment_default": [C.POINTER(Environment)],
+    "srt_set_camera": [_ctx, C.POINTER(Camera)],
+    "srt_set_stream": [_ctx, C.c_void_p],
+    "srt_bind_output": [_ctx, C.c_void_p, C.c_void_p],
+    "srt_device_framebuffer": [_ctx, C.POINTER(C.c_void_p)],
+    "srt_device_accumulator": [_ctx, C.POINTER(C.c_void_p)],
+    "srt_render": [_ctx, C.POINTER(RenderParams)],
+    "srt_wait": [_ctx],
+    "srt_poll": [_ctx, C.POINTER(C.c_int)],
+    "srt_get_stats": [_ctx, C.POINTER(Stats)],
+    "srt_get_work_counts": [_ctx, C.POINTER(WorkCounts)],
+    "srt_pick": [_ctx, C.c_int, C.c_int, C.POINTER(C.c_int)],
+    "srt_read_framebuffer": [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_int],
+    "srt_read_framebuffer_async": [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p],
+    "srt_read_accumulator": [_ctx, C.POINTER(C.c_float)],
+    "srt_write_accumulator": [_ctx, C.POINTER(C.c_float)],
+    "srt_gather_band": [_ctx, _ctx, C.c_int, C.c_int],
+    "srt_gather_path": [_ctx],
+    "srt_estimate_row_costs": [_ctx, C.c_int, C.c_uint32, C.POINTER(C.c_float)],
+    "srt_selftest_arith": [C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)],
+    "srt_render_gbuffer": [_ctx, C.POINTER(GBufferParams)],
+    "srt_bind_gbuffer": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_read_gbuffer": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_denoise_params_default": [C.POINTER(DenoiseParams)],
+    "srt_denoise": [_ctx, C.POINTER(DenoiseParams)],
+    "srt_bind_denoised": [_ctx, C.c_void_p],
+    "srt_read_denoised": [_ctx, C.POINTER(C.c_float)],
+    "srt_temporal_params_default": [C.POINTER(TemporalParams)],
+    "srt_temporal_accumulate": [_ctx, C.POINTER(TemporalParams)],
+    "srt_read_history_length": [_ctx, C.POINTER(C.c_float)],
+    "srt_update_scene": [_ctx, C.POINTER(Object), C.c_size_t],
+    "srt_motion_output": [_ctx, C.c_int],
+    "srt_bind_motion": [_ctx, C.c_void_p],
+    "srt_read_motion": [_ctx, C.POINTER(C.c_float)],
+    "srt_upsample_params_default": [C.POINTER(UpsampleParams)],
+    "srt_upsample": [_ctx, C.POINTER(UpsampleParams)],
+    "srt_bind_upsampled": [_ctx, C.c_void_p],
+    "srt_read_upsampled": [_ctx, C.POINTER(C.c_float)],
+    "srt_render_subsamples": [_ctx, C.POINTER(SubsampleParams)],
+    "srt_bind_subsamples": [_ctx, C.c_void_p],
+    "srt_read_subsamples": [_ctx, C.POINTER(C.c_int32)],
+    "srt_antialias_params_default": [C.POINTER(AntialiasParams)],
+    "srt_antialias": [_ctx, C.POINTER(AntialiasParams)],
+    "srt_bind_antialiased": [_ctx, C.c_void_p],
+    "srt_read_antialiased": [_ctx, C.POINTER(C.c_float)],
+    "srt_variance_params_default": [C.POINTER(VarianceParams)],
+    "srt_device_half": [_ctx, C.POINTER(C.c_void_p)],
+    "srt_bind_half": [_ctx, C.c_void_p],
+    "srt_variance": [_ctx, C.POINTER(VarianceParams)],
+    "srt_bind_variance": [_ctx, C.c_void_p],
+    "srt_read_variance": [_ctx, C.POINTER(C.c_float)],
+    "srt_denoise_variance_params_default": [C.POINTER(DenoiseVarianceParams)],
+    "srt_denoise_variance": [_ctx, C.POINTER(DenoiseVarianceParams)],
+    "srt_moments_output": [_ctx, C.c_int, C.c_uint32],
+    "srt_read_moments": [_ctx, C.POINTER(C.c_float)],
+    "srt_temporal_variance_params_default": [C.POINTER(TemporalVarianceParams)],
+    "srt_temporal_variance": [_ctx, C.POINTER(TemporalVarianceParams)],
+    "srt_update_mode": [_ctx, C.c_int],
+    "srt_get_update_info": [_ctx, C.POINTER(UpdateInfo)],
+    "srt_mesh_image_size": [_ctx, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    "srt_read_mesh_image": [_ctx, C.c_void_p, C.c_void_p],
+    "srt_trace_params_default": [C.POINTER(TraceParams)],
+    "srt_write_rays": [_ctx, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t],
+    "srt_bind_rays": [_ctx, C.c_void_p, C.c_void_p, C.c_size_t],
+    "srt_bind_ray_output": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_trace_rays": [_ctx, C.POINTER(TraceParams)],
+    "srt_read_ray_output": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_occlusion_params_default": [C.POINTER(OcclusionParams)],
+    "srt_trace_occlusion": [_ctx, C.POINTER(OcclusionParams)],
+    "srt_get_occlusion_work": [_ctx, C.POINTER(OcclusionWork)],
+    "srt_visibility_params_default": [C.POINTER(VisibilityParams)],
+    "srt_render_visibility": [_ctx, C.POINTER(VisibilityParams)],
+    "srt_bind_visibility": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_read_visibility": [_ctx, C.c_uint32, C.POINTER(C.c_float)],
+    "srt_get_visibility_work": [_ctx, C.POINTER(VisibilityWork)],
+    "srt_reflection_params_default": [C.POINTER(ReflectionParams)],
+    "srt_render_reflection_gbuffer": [_ctx, C.POINTER(ReflectionParams)],
+    "srt_bind_reflection": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_read_reflection": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_device_reflection": [_ctx, C.c_uint32, C.POINTER(C.c_void_p)],
+    "srt_get_reflection_work": [_ctx, C.POINTER(ReflectionWork)],
+    "srt_mirror_history_params_default": [C.POINTER(MirrorHistoryParams)],
+    "srt_mirror_history": [_ctx, C.POINTER(MirrorHistoryParams)],
+    "srt_probe_tail_params_default": [C.POINTER(ProbeTailParams)],
+    "srt_probe_tail": [_ctx, C.POINTER(ProbeTailParams)],
+    "srt_get_probe_tail_work": [_ctx, C.POINTER(ProbeTailWork)],
+    "srt_radiance_params_default": [C.POINTER(RadianceParams)],
+    "srt_trace_radiance": [_ctx, C.POINTER(RadianceParams)],
+    "srt_bind_radiance": [_ctx, C.c_void_p],
+    "srt_read_radiance": [_ctx, C.POINTER(C.c_float)],
+    "srt_get_radiance_work": [_ctx, C.POINTER(RadianceWork)],
+    "srt_write_light_probes": [_ctx, C.POINTER(C.c_float), C.c_size_t],
+    "srt_bind_light_probes": [_ctx, C.c_void_p, C.c_size_t],
+    "srt_write_light_probe_directions": [_ctx, C.POINTER(C.c_float), C.c_size_t],
+    "srt_bind_light_probe_directions": [_ctx, C.c_void_p, C.c_size_t],
+    "srt_light_probe_params_default": [C.POINTER(LightProbeParams)],
+    "srt_trace_light_probes": [_ctx, C.POINTER(LightProbeParams)],
+    "srt_bind_light_probe_output": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_read_light_probe_output": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_get_light_probe_work": [_ctx, C.POINTER(LightProbeWork)],
+    "srt_light_probe_sphere": [C.c_size_t, C.POINTER(C.c_float)],
+    "srt_light_probe_irradiance": [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)],
+    "srt_probe_grid_positions": [C.POINTER(ProbeGrid), C.POINTER(C.c_float)],
+    "srt_probe_grid_params_default": [C.POINTER(ProbeGridParams)],
+    "srt_set_probe_grid": [_ctx, C.POINTER(ProbeGrid)],
+    "srt_write_probe_grid_coefficients": [_ctx, C.POINTER(C.c_float), C.c_size_t],
+    "srt_bind_probe_grid_coefficients": [_ctx, C.c_void_p, C.c_size_t],
+    "srt_shade_probe_grid": [_ctx, C.POINTER(ProbeGridParams)],
+    "srt_bind_probe_grid_output": [_ctx, C.c_void_p],
+    "srt_read_probe_grid_output": [_ctx, C.POINTER(C.c_float)],
+    "srt_get_probe_grid_work": [_ctx, C.POINTER(ProbeGridWork)],
+    "srt_probe_depth_params_default": [C.POINTER(ProbeDepthParams)],
+    "srt_probe_depth_texels": [C.c_uint32, C.POINTER(C.c_float)],
+    "srt_trace_probe_depth": [_ctx, C.POINTER(ProbeDepthParams)],
+    "srt_bind_probe_depth_output": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_read_probe_depth_output": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_get_probe_depth_work": [_ctx, C.POINTER(ProbeDepthWork)],
+    "srt_probe_grid_depth_params_default": [C.POINTER(ProbeGridDepthParams)],
+    "srt_write_probe_grid_depth": [_ctx, C.POINTER(C.c_float), C.c_size_t, C.c_uint32],
+    "srt_bind_probe_grid_depth": [_ctx, C.c_void_p, C.c_size_t, C.c_uint32],
+    "srt_shade_probe_grid_depth": [_ctx, C.POINTER(ProbeGridParams), C.POINTER(ProbeGridDepthParams)],
+    "srt_probe_classify_params_default": [C.POINTER(ProbeClassifyParams)],
+    "srt_classify_probes": [_ctx, C.POINTER(ProbeClassifyParams)],
+    "srt_bind_probe_states_output": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_read_probe_states_output": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_get_probe_classify_work": [_ctx, C.POINTER(ProbeClassifyWork)],
+    "srt_write_probe_grid_states": [_ctx, C.POINTER(C.c_float), C.c_size_t],
+    "srt_bind_probe_grid_states": [_ctx, C.c_void_p, C.c_size_t],
+    "srt_shade_probe_grid_states": [_ctx, C.POINTER(ProbeGridParams), C.POINTER(ProbeGridDepthParams)],
+    "srt_probe_list_params_default": [C.POINTER(ProbeListParams)],
+    "srt_list_probes": [_ctx, C.POINTER(ProbeListParams)],
+    "srt_bind_probe_list_output": [_ctx, C.c_void_p],
+    "srt_read_probe_list_output": [_ctx, C.POINTER(C.c_uint32)],
+    "srt_get_probe_list_work": [_ctx, C.POINTER(ProbeListWork)],
+    "srt_bind_probe_list": [_ctx, C.c_void_p, C.c_size_t],
+    "srt_write_probe_list": [_ctx, C.POINTER(C.c_uint32), C.c_size_t],
+    "srt_trace_light_probes_listed": [_ctx, C.POINTER(LightProbeParams)],
+    "srt_trace_probe_depth_listed": [_ctx, C.POINTER(ProbeDepthParams)],
+    "srt_probe_blend_params_default": [C.POINTER(ProbeBlendParams)],
+    "srt_reset_probe_history": [_ctx, C.c_uint32, C.c_size_t, C.c_uint32],
+    "srt_bind_probe_history": [_ctx, C.c_uint32, C.c_void_p],
+    "srt_read_probe_history": [_ctx, C.c_uint32, C.POINTER(C.c_float)],
+    "srt_write_probe_previous_states": [_ctx, C.POINTER(C.c_float), C.c_size_t],
+    "srt_bind_probe_previous_states": [_ctx, C.c_void_p, C.c_size_t],
+    "srt_blend_probes": [_ctx, C.POINTER(ProbeBlendParams)],
+    "srt_get_probe_blend_work": [_ctx, C.POINTER(ProbeBlendWork)],
+    "srt_probe_scroll_params_default": [C.POINTER(ProbeScrollParams)],
+    "srt_scroll_probes": [_ctx, C.POINTER(ProbeScrollParams)],
+    "srt_get_probe_scroll_work": [_ctx, C.POINTER(ProbeScrollWork)],
+    "srt_read_probe_previous_states": [_ctx, C.POINTER(C.c_float)],
+    "srt_probe_grid_follow": [C.POINTER(ProbeGrid), C.POINTER(C.c_float), C.POINTER(C.c_int32)],
+    "srt_probe_cascade_params_default": [C.POINTER(ProbeCascadeParams)],
+    "srt_probe_cascade_grids": [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(ProbeCascade)],
+    "srt_probe_cascade_weights": [C.POINTER(ProbeCascade), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)],
+    "srt_set_probe_cascade": [_ctx, C.POINTER(ProbeCascade)],
+    "srt_write_probe_cascade_level": [_ctx, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_size_t],
+    "srt_bind_probe_cascade_level": [_ctx, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t],
+    "srt_capture_probe_cascade_level": [_ctx, C.c_uint32, C.c_uint32],
+    "srt_shade_probe_cascade": [_ctx, C.POINTER(ProbeCascadeParams)],
+    "srt_get_probe_cascade_work": [_ctx, C.POINTER(ProbeCascadeWork)],
+    "srt_set_sample_counts": [_ctx, C.c_uint32],
+    "srt_write_sample_counts": [_ctx, C.POINTER(C.c_uint32)],
+    "srt_read_sample_counts": [_ctx, C.POINTER(C.c_uint32)],
+    "srt_bind_sample_counts": [_ctx, C.c_void_p],
+    "srt_write_sample_budget": [_ctx, C.POINTER(C.c_uint32)],
+    "srt_read_sample_budget": [_ctx, C.POINTER(C.c_uint32)],
+    "srt_bind_sample_budget": [_ctx, C.c_void_p],
+    "srt_adaptive_params_default": [C.POINTER(AdaptiveParams)],
+    "srt_render_adaptive": [_ctx, C.POINTER(AdaptiveParams)],
+    "srt_get_adaptive_work": [_ctx, C.POINTER(AdaptiveWork)],
+    "srt_render_adaptive_tail": [_ctx, C.POINTER(AdaptiveParams)],
+    "srt_budget_params_default": [C.POINTER(BudgetParams)],
+    "srt_sample_budget": [_ctx, C.POINTER(BudgetParams)],
+    "srt_get_budget_total": [_ctx, C.POINTER(C.c_uint64)],
+}
+# every export returns an srt_status int but these
+_RESTYPES = {"srt_last_error": C.c_char_p, "srt_gather_path": C.c_char_p}
+# exports a build of an earlier commit may lack (tests/ab_passes.py and tests/ab_libs.py open such builds next to this one)
+_OPTIONAL_EXPORTS = ("srt_probe_tail_params_default", "srt_probe_tail", "srt_get_probe_tail_work", "srt_render_adaptive_tail")
+
+
 def open_library(path):
     """dlopen one build of the C-ABI library and declare its prototypes (load_library() for the product's; development
     tools open several builds side by side for interleaved A/B timing, tests/ab_libs.py)."""
     L = C.CDLL(path)
-    ctx = C.c_void_p
-    L.srt_abi_version.restype = C.c_int
-    L.srt_device_count.argtypes = [C.POINTER(C.c_int)]
-    L.srt_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(ctx)]
-    L.srt_destroy.argtypes = [ctx]
-    L.srt_last_error.argtypes = [ctx]
-    L.srt_last_error.restype = C.c_char_p
-    L.srt_set_scene.argtypes = [ctx, C.POINTER(Object), C.c_size_t]
-    L.srt_set_meshes.argtypes = [ctx, C.POINTER(Mesh), C.c_size_t]
-    L.srt_set_environment.argtypes = [ctx, C.POINTER(Environment)]
-    L.srt_environment_default.argtypes = [C.POINTER(Environment)]
-    L.srt_set_camera.argtypes = [ctx, C.POINTER(Camera)]
-    L.srt_set_stream.argtypes = [ctx, C.c_void_p]
-    L.srt_bind_output.argtypes = [ctx, C.c_void_p, C.c_void_p]
-    L.srt_device_framebuffer.argtypes = [ctx, C.POINTER(C.c_void_p)]
-    L.srt_device_accumulator.argtypes = [ctx, C.POINTER(C.c_void_p)]
-    L.srt_render.argtypes = [ctx, C.POINTER(RenderParams)]
-    L.srt_wait.argtypes = [ctx]
-    L.srt_poll.argtypes = [ctx, C.POINTER(C.c_int)]
-    L.srt_get_stats.argtypes = [ctx, C.POINTER(Stats)]
-    L.srt_get_work_counts.argtypes = [ctx, C.POINTER(WorkCounts)]
-    L.srt_pick.argtypes = [ctx, C.c_int, C.c_int, C.POINTER(C.c_int)]
-    L.srt_read_framebuffer.argtypes = [ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
-    L.srt_read_framebuffer_async.argtypes = [ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
-    L.srt_read_accumulator.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_write_accumulator.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_gather_band.argtypes = [ctx, ctx, C.c_int, C.c_int]
-    L.srt_gather_path.argtypes = [ctx]
-    L.srt_gather_path.restype = C.c_char_p
-    L.srt_estimate_row_costs.argtypes = [ctx, C.c_int, C.c_uint32, C.POINTER(C.c_float)]
-    L.srt_selftest_arith.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
-    L.srt_render_gbuffer.argtypes = [ctx, C.POINTER(GBufferParams)]
-    L.srt_bind_gbuffer.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_read_gbuffer.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_denoise_params_default.argtypes = [C.POINTER(DenoiseParams)]
-    L.srt_denoise.argtypes = [ctx, C.POINTER(DenoiseParams)]
-    L.srt_bind_denoised.argtypes = [ctx, C.c_void_p]
-    L.srt_read_denoised.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_temporal_params_default.argtypes = [C.POINTER(TemporalParams)]
-    L.srt_temporal_accumulate.argtypes = [ctx, C.POINTER(TemporalParams)]
-    L.srt_read_history_length.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_update_scene.argtypes = [ctx, C.POINTER(Object), C.c_size_t]
-    L.srt_motion_output.argtypes = [ctx, C.c_int]
-    L.srt_bind_motion.argtypes = [ctx, C.c_void_p]
-    L.srt_read_motion.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_upsample_params_default.argtypes = [C.POINTER(UpsampleParams)]
-    L.srt_upsample.argtypes = [ctx, C.POINTER(UpsampleParams)]
-    L.srt_bind_upsampled.argtypes = [ctx, C.c_void_p]
-    L.srt_read_upsampled.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_render_subsamples.argtypes = [ctx, C.POINTER(SubsampleParams)]
-    L.srt_bind_subsamples.argtypes = [ctx, C.c_void_p]
-    L.srt_read_subsamples.argtypes = [ctx, C.POINTER(C.c_int32)]
-    L.srt_antialias_params_default.argtypes = [C.POINTER(AntialiasParams)]
-    L.srt_antialias.argtypes = [ctx, C.POINTER(AntialiasParams)]
-    L.srt_bind_antialiased.argtypes = [ctx, C.c_void_p]
-    L.srt_read_antialiased.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_variance_params_default.argtypes = [C.POINTER(VarianceParams)]
-    L.srt_device_half.argtypes = [ctx, C.POINTER(C.c_void_p)]
-    L.srt_bind_half.argtypes = [ctx, C.c_void_p]
-    L.srt_variance.argtypes = [ctx, C.POINTER(VarianceParams)]
-    L.srt_bind_variance.argtypes = [ctx, C.c_void_p]
-    L.srt_read_variance.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_denoise_variance_params_default.argtypes = [C.POINTER(DenoiseVarianceParams)]
-    L.srt_denoise_variance.argtypes = [ctx, C.POINTER(DenoiseVarianceParams)]
-    L.srt_moments_output.argtypes = [ctx, C.c_int, C.c_uint32]
-    L.srt_read_moments.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_temporal_variance_params_default.argtypes = [C.POINTER(TemporalVarianceParams)]
-    L.srt_temporal_variance.argtypes = [ctx, C.POINTER(TemporalVarianceParams)]
-    L.srt_update_mode.argtypes = [ctx, C.c_int]
-    L.srt_get_update_info.argtypes = [ctx, C.POINTER(UpdateInfo)]
-    L.srt_mesh_image_size.argtypes = [ctx, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.srt_read_mesh_image.argtypes = [ctx, C.c_void_p, C.c_void_p]
-    L.srt_trace_params_default.argtypes = [C.POINTER(TraceParams)]
-    L.srt_write_rays.argtypes = [ctx, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]
-    L.srt_bind_rays.argtypes = [ctx, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.srt_bind_ray_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_trace_rays.argtypes = [ctx, C.POINTER(TraceParams)]
-    L.srt_read_ray_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_occlusion_params_default.argtypes = [C.POINTER(OcclusionParams)]
-    L.srt_trace_occlusion.argtypes = [ctx, C.POINTER(OcclusionParams)]
-    L.srt_get_occlusion_work.argtypes = [ctx, C.POINTER(OcclusionWork)]
-    L.srt_visibility_params_default.argtypes = [C.POINTER(VisibilityParams)]
-    L.srt_render_visibility.argtypes = [ctx, C.POINTER(VisibilityParams)]
-    L.srt_bind_visibility.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_read_visibility.argtypes = [ctx, C.c_uint32, C.POINTER(C.c_float)]
-    L.srt_get_visibility_work.argtypes = [ctx, C.POINTER(VisibilityWork)]
-    L.srt_reflection_params_default.argtypes = [C.POINTER(ReflectionParams)]
-    L.srt_render_reflection_gbuffer.argtypes = [ctx, C.POINTER(ReflectionParams)]
-    L.srt_bind_reflection.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_read_reflection.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_device_reflection.argtypes = [ctx, C.c_uint32, C.POINTER(C.c_void_p)]
-    L.srt_get_reflection_work.argtypes = [ctx, C.POINTER(ReflectionWork)]
-    L.srt_mirror_history_params_default.argtypes = [C.POINTER(MirrorHistoryParams)]
-    L.srt_mirror_history.argtypes = [ctx, C.POINTER(MirrorHistoryParams)]
-    if hasattr(L, "srt_probe_tail"):  # (tests/ab_passes.py opens builds of earlier commits next to this one)
-        L.srt_probe_tail_params_default.argtypes = [C.POINTER(ProbeTailParams)]
-        L.srt_probe_tail.argtypes = [ctx, C.POINTER(ProbeTailParams)]
-        L.srt_get_probe_tail_work.argtypes = [ctx, C.POINTER(ProbeTailWork)]
-    L.srt_radiance_params_default.argtypes = [C.POINTER(RadianceParams)]
-    L.srt_trace_radiance.argtypes = [ctx, C.POINTER(RadianceParams)]
-    L.srt_bind_radiance.argtypes = [ctx, C.c_void_p]
-    L.srt_read_radiance.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_get_radiance_work.argtypes = [ctx, C.POINTER(RadianceWork)]
-    L.srt_write_light_probes.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t]
-    L.srt_bind_light_probes.argtypes = [ctx, C.c_void_p, C.c_size_t]
-    L.srt_write_light_probe_directions.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t]
-    L.srt_bind_light_probe_directions.argtypes = [ctx, C.c_void_p, C.c_size_t]
-    L.srt_light_probe_params_default.argtypes = [C.POINTER(LightProbeParams)]
-    L.srt_trace_light_probes.argtypes = [ctx, C.POINTER(LightProbeParams)]
-    L.srt_bind_light_probe_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_read_light_probe_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_get_light_probe_work.argtypes = [ctx, C.POINTER(LightProbeWork)]
-    L.srt_light_probe_sphere.argtypes = [C.c_size_t, C.POINTER(C.c_float)]
-    L.srt_light_probe_irradiance.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.srt_probe_grid_positions.argtypes = [C.POINTER(ProbeGrid), C.POINTER(C.c_float)]
-    L.srt_probe_grid_params_default.argtypes = [C.POINTER(ProbeGridParams)]
-    L.srt_set_probe_grid.argtypes = [ctx, C.POINTER(ProbeGrid)]
-    L.srt_write_probe_grid_coefficients.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t]
-    L.srt_bind_probe_grid_coefficients.argtypes = [ctx, C.c_void_p, C.c_size_t]
-    L.srt_shade_probe_grid.argtypes = [ctx, C.POINTER(ProbeGridParams)]
-    L.srt_bind_probe_grid_output.argtypes = [ctx, C.c_void_p]
-    L.srt_read_probe_grid_output.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_get_probe_grid_work.argtypes = [ctx, C.POINTER(ProbeGridWork)]
-    L.srt_probe_depth_params_default.argtypes = [C.POINTER(ProbeDepthParams)]
-    L.srt_probe_depth_texels.argtypes = [C.c_uint32, C.POINTER(C.c_float)]
-    L.srt_trace_probe_depth.argtypes = [ctx, C.POINTER(ProbeDepthParams)]
-    L.srt_bind_probe_depth_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_read_probe_depth_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_get_probe_depth_work.argtypes = [ctx, C.POINTER(ProbeDepthWork)]
-    L.srt_probe_grid_depth_params_default.argtypes = [C.POINTER(ProbeGridDepthParams)]
-    L.srt_write_probe_grid_depth.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t, C.c_uint32]
-    L.srt_bind_probe_grid_depth.argtypes = [ctx, C.c_void_p, C.c_size_t, C.c_uint32]
-    L.srt_shade_probe_grid_depth.argtypes = [ctx, C.POINTER(ProbeGridParams), C.POINTER(ProbeGridDepthParams)]
-    L.srt_probe_classify_params_default.argtypes = [C.POINTER(ProbeClassifyParams)]
-    L.srt_classify_probes.argtypes = [ctx, C.POINTER(ProbeClassifyParams)]
-    L.srt_bind_probe_states_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_read_probe_states_output.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_get_probe_classify_work.argtypes = [ctx, C.POINTER(ProbeClassifyWork)]
-    L.srt_write_probe_grid_states.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t]
-    L.srt_bind_probe_grid_states.argtypes = [ctx, C.c_void_p, C.c_size_t]
-    L.srt_shade_probe_grid_states.argtypes = [ctx, C.POINTER(ProbeGridParams), C.POINTER(ProbeGridDepthParams)]
-    L.srt_probe_list_params_default.argtypes = [C.POINTER(ProbeListParams)]
-    L.srt_list_probes.argtypes = [ctx, C.POINTER(ProbeListParams)]
-    L.srt_bind_probe_list_output.argtypes = [ctx, C.c_void_p]
-    L.srt_read_probe_list_output.argtypes = [ctx, C.POINTER(C.c_uint32)]
-    L.srt_get_probe_list_work.argtypes = [ctx, C.POINTER(ProbeListWork)]
-    L.srt_bind_probe_list.argtypes = [ctx, C.c_void_p, C.c_size_t]
-    L.srt_write_probe_list.argtypes = [ctx, C.POINTER(C.c_uint32), C.c_size_t]
-    L.srt_trace_light_probes_listed.argtypes = [ctx, C.POINTER(LightProbeParams)]
-    L.srt_trace_probe_depth_listed.argtypes = [ctx, C.POINTER(ProbeDepthParams)]
-    L.srt_probe_blend_params_default.argtypes = [C.POINTER(ProbeBlendParams)]
-    L.srt_reset_probe_history.argtypes = [ctx, C.c_uint32, C.c_size_t, C.c_uint32]
-    L.srt_bind_probe_history.argtypes = [ctx, C.c_uint32, C.c_void_p]
-    L.srt_read_probe_history.argtypes = [ctx, C.c_uint32, C.POINTER(C.c_float)]
-    L.srt_write_probe_previous_states.argtypes = [ctx, C.POINTER(C.c_float), C.c_size_t]
-    L.srt_bind_probe_previous_states.argtypes = [ctx, C.c_void_p, C.c_size_t]
-    L.srt_blend_probes.argtypes = [ctx, C.POINTER(ProbeBlendParams)]
-    L.srt_get_probe_blend_work.argtypes = [ctx, C.POINTER(ProbeBlendWork)]
-    L.srt_probe_scroll_params_default.argtypes = [C.POINTER(ProbeScrollParams)]
-    L.srt_scroll_probes.argtypes = [ctx, C.POINTER(ProbeScrollParams)]
-    L.srt_get_probe_scroll_work.argtypes = [ctx, C.POINTER(ProbeScrollWork)]
-    L.srt_read_probe_previous_states.argtypes = [ctx, C.POINTER(C.c_float)]
-    L.srt_probe_grid_follow.argtypes = [C.POINTER(ProbeGrid), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-    L.srt_probe_cascade_params_default.argtypes = [C.POINTER(ProbeCascadeParams)]
-    L.srt_probe_cascade_grids.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(ProbeCascade)]
-    L.srt_probe_cascade_weights.argtypes = [C.POINTER(ProbeCascade), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                            C.POINTER(C.c_float)]
-    L.srt_set_probe_cascade.argtypes = [ctx, C.POINTER(ProbeCascade)]
-    L.srt_write_probe_cascade_level.argtypes = [ctx, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_size_t]
-    L.srt_bind_probe_cascade_level.argtypes = [ctx, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]
-    L.srt_capture_probe_cascade_level.argtypes = [ctx, C.c_uint32, C.c_uint32]
-    L.srt_shade_probe_cascade.argtypes = [ctx, C.POINTER(ProbeCascadeParams)]
-    L.srt_get_probe_cascade_work.argtypes = [ctx, C.POINTER(ProbeCascadeWork)]
-    L.srt_set_sample_counts.argtypes = [ctx, C.c_uint32]
-    L.srt_write_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
-    L.srt_read_sample_counts.argtypes = [ctx, C.POINTER(C.c_uint32)]
-    L.srt_bind_sample_counts.argtypes = [ctx, C.c_void_p]
-    L.srt_write_sample_budget.argtypes = [ctx, C.POINTER(C.c_uint32)]
-    L.srt_read_sample_budget.argtypes = [ctx, C.POINTER(C.c_uint32)]
-    L.srt_bind_sample_budget.argtypes = [ctx, C.c_void_p]
-    L.srt_adaptive_params_default.argtypes = [C.POINTER(AdaptiveParams)]
-    L.srt_render_adaptive.argtypes = [ctx, C.POINTER(AdaptiveParams)]
-    L.srt_get_adaptive_work.argtypes = [ctx, C.POINTER(AdaptiveWork)]
-    if hasattr(L, "srt_render_adaptive_tail"):  # (as srt_probe_tail above)
-        L.srt_render_adaptive_tail.argtypes = [ctx, C.POINTER(AdaptiveParams)]
-    L.srt_budget_params_default.argtypes = [C.POINTER(BudgetParams)]
-    L.srt_sample_budget.argtypes = [ctx, C.POINTER(BudgetParams)]
-    L.srt_get_budget_total.argtypes = [ctx, C.POINTER(C.c_uint64)]
-    for name in EXPORTS:
-        if ("probe_tail" in name or name == "srt_render_adaptive_tail") and not hasattr(L, name):
-            continue  # (a build of an earlier commit, opened by tests/ab_passes.py)
+    for name, argtypes in _PROTOTYPES.items():
+        if name in _OPTIONAL_EXPORTS and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
-        if name not in ("srt_last_error", "srt_gather_path"):
-            fn.restype = C.c_int
+        fn.argtypes, fn.restype = argtypes, _RESTYPES.get(name, C.c_int)
     return L
+
+
+# the names the calls below accept for the bits of an output, a history or a set of arrays (the image outputs, with their dtypes and
+# channels, are GBUFFERS, REFLECTION, RAY_OUTPUTS and VISIBILITY above)
+LIGHT_PROBE_OUTPUTS = {"coefficients": LIGHT_PROBE_COEFFICIENTS, "radiance": LIGHT_PROBE_RADIANCE}
+PROBE_DEPTH_OUTPUTS = {"moments": PROBE_DEPTH_MOMENTS, "distances": PROBE_DEPTH_DISTANCES}
+PROBE_STATE_OUTPUTS = {"records": PROBE_STATE_RECORDS, "positions": PROBE_STATE_POSITIONS}
+PROBE_HISTORIES = {"coefficients": PROBE_HISTORY_COEFFICIENTS, "moments": PROBE_HISTORY_MOMENTS,
+                   "both": PROBE_HISTORY_COEFFICIENTS | PROBE_HISTORY_MOMENTS}
+PROBE_SCROLL_ARRAYS = {"coefficients": PROBE_SCROLL_COEFFICIENTS, "moments": PROBE_SCROLL_MOMENTS, "states": PROBE_SCROLL_STATES,
+                       "both": PROBE_SCROLL_COEFFICIENTS | PROBE_SCROLL_MOMENTS,
+                       "all": PROBE_SCROLL_COEFFICIENTS | PROBE_SCROLL_MOMENTS | PROBE_SCROLL_STATES}
+PROBE_CASCADE_ARRAYS = {"coefficients": PROBE_CASCADE_COEFFICIENTS, "moments": PROBE_CASCADE_MOMENTS, "records": PROBE_CASCADE_RECORDS,
+                        "all": PROBE_CASCADE_COEFFICIENTS | PROBE_CASCADE_MOMENTS | PROBE_CASCADE_RECORDS}
+
+
+def _spec(table, name, what=None):
+    """The entry of one name in a name table.  An unknown name is a ValueError that lists the table's names when `what` says what
+    the table holds, else the table's own KeyError."""
+    if what is not None and name not in table:
+        raise ValueError("unknown %s %r (one of %s)" % (what, name, ", ".join(table)))
+    return table[name]
+
+
+def _mask(table, names, what=None):
+    """A bit mask from an int (the mask itself), a name of `table` or a sequence of names; unknown names as _spec() refuses them."""
+    if isinstance(names, (int, np.integer)):
+        return int(names)
+    mask = 0
+    for name in ([names] if isinstance(names, str) else names):
+        entry = _spec(table, name, what)
+        mask |= entry[0] if isinstance(entry, tuple) else entry
+    return mask
+
+
+def _bit(table, which):
+    """One selector: a name of `table`, or the bits themselves (anything int() takes)."""
+    return int(table[which] if which in table else which)
 
 
 def gbuffer_outputs(outputs):
     """An SRT_GBUF_* mask from an int or from names of GBUFFERS ("object", "normal_depth", "position", "albedo")."""
-    if isinstance(outputs, str):
-        outputs = [outputs]
-    if isinstance(outputs, (int, np.integer)):
-        return int(outputs)
-    mask = 0
-    for name in outputs:
-        if name not in GBUFFERS:
-            raise ValueError("unknown G-buffer output %r (one of %s)" % (name, ", ".join(GBUFFERS)))
-        mask |= GBUFFERS[name][0]
-    return mask
+    return _mask(GBUFFERS, outputs, "G-buffer output")
 
 
 def reflection_outputs(outputs):
     """An SRT_REFL_* mask from an int or from names of REFLECTION (GBUFFERS' four and "bounces")."""
-    if isinstance(outputs, int):
-        return outputs
-    if isinstance(outputs, str):
-        outputs = [outputs]
-    mask = 0
-    for name in outputs:
-        mask |= _reflection_spec(name)[0]
-    return mask
-
-
-def _reflection_spec(name):
-    if name not in REFLECTION:
-        raise ValueError("unknown reflection output %r (one of %s)" % (name, ", ".join(REFLECTION)))
-    return REFLECTION[name]
-
-
-def _gbuffer_spec(name):
-    if name not in GBUFFERS:
-        raise ValueError("unknown G-buffer output %r (one of %s)" % (name, ", ".join(GBUFFERS)))
-    return GBUFFERS[name]
+    return _mask(REFLECTION, outputs, "reflection output")
 
 
 def ray_outputs(outputs):
     """An output mask of srt_trace_rays from an int or from names of RAY_OUTPUTS ("object", "normal_depth", "position",
     "albedo", "occluded")."""
-    if isinstance(outputs, str):
-        outputs = [outputs]
-    if isinstance(outputs, (int, np.integer)):
-        return int(outputs)
-    mask = 0
-    for name in outputs:
-        mask |= _ray_output_spec(name)[0]
-    return mask
+    return _mask(RAY_OUTPUTS, outputs, "ray output")
 
 
-def _ray_output_spec(name):
-    if name not in RAY_OUTPUTS:
-        raise ValueError("unknown ray output %r (one of %s)" % (name, ", ".join(RAY_OUTPUTS)))
-    return RAY_OUTPUTS[name]
+def _set(p, **fields):
+    """Set the fields of struct `p` that were given (None: the field keeps its value), coerced by the field's ctype: float() for a
+    c_float, int() for the integer types, an array field element by element from a sequence.  Returns p."""
+    ctypes_of = dict(p._fields_)
+    for name, value in fields.items():
+        if value is None:
+            continue
+        t = ctypes_of[name]
+        if issubclass(t, C.Array):
+            coerce = float if t._type_ is C.c_float else int
+            array = getattr(p, name)
+            for i in range(t._length_):
+                array[i] = coerce(value[i])
+        else:
+            setattr(p, name, float(value) if t is C.c_float else int(value))
+    return p
 
 
-def _defaults(struct, symbol, lib=None):
-    """The library's defaults of one parameter struct as a dict (pure host: no GPU needed)."""
+def _default_params(struct, symbol, lib=None):
+    """One parameter struct filled with the library's defaults (pure host: no GPU needed)."""
     p = struct()
     rc = getattr(lib if lib is not None else load_library(), symbol)(C.byref(p))
     if rc:
         raise SrtError(rc, symbol)
-    return {n: getattr(p, n) for n, _ in struct._fields_}
+    return p
 
 
-def trace_defaults(lib=None):
-    """srt_trace_params_default as a dict (pure host: no GPU needed)."""
-    return _defaults(TraceParams, "srt_trace_params_default", lib)
+def _defaults_function(name, struct, symbol):
+    def defaults(lib=None):
+        p = _default_params(struct, symbol, lib)
+        return {n: getattr(p, n) for n, _ in struct._fields_}
+
+    defaults.__name__ = defaults.__qualname__ = name
+    defaults.__doc__ = "%s as a dict (pure host: no GPU needed)." % symbol
+    return defaults
 
 
-def denoise_defaults(lib=None):
-    """srt_denoise_params_default as a dict (pure host: no GPU needed)."""
-    return _defaults(DenoiseParams, "srt_denoise_params_default", lib)
-
-
-def temporal_defaults(lib=None):
-    """srt_temporal_params_default as a dict (pure host: no GPU needed)."""
-    return _defaults(TemporalParams, "srt_temporal_params_default", lib)
-
-
-def upsample_defaults(lib=None):
-    """srt_upsample_params_default as a dict (pure host: no GPU needed)."""
-    return _defaults(UpsampleParams, "srt_upsample_params_default", lib)
-
-
-def antialias_defaults(lib=None):
-    """srt_antialias_params_default as a dict (pure host: no GPU needed)."""
-    return _defaults(AntialiasParams, "srt_antialias_params_default", lib)
-
-
-def variance_defaults(lib=None):
-    """srt_variance_params_default as a dict (pure host: no GPU needed)."""
-    return _defaults(VarianceParams, "srt_variance_params_default", lib)
-
-
-def denoise_variance_defaults(lib=None):
-    """srt_denoise_variance_params_default as a dict (pure host: no GPU needed)."""
-    return _defaults(DenoiseVarianceParams, "srt_denoise_variance_params_default", lib)
-
-
-def temporal_variance_defaults(lib=None):
-    """srt_temporal_variance_params_default as a dict (pure host: no GPU needed)."""
-    return _defaults(TemporalVarianceParams, "srt_temporal_variance_params_default", lib)
-
-
-# DENOISE_DEFAULTS, TEMPORAL_DEFAULTS, ...: the library's defaults, read when first asked for, so that importing this module does
-# not need the built library
-_LAZY_DEFAULTS = {"DENOISE_DEFAULTS": denoise_defaults, "TEMPORAL_DEFAULTS": temporal_defaults, "UPSAMPLE_DEFAULTS": upsample_defaults,
-                  "ANTIALIAS_DEFAULTS": antialias_defaults, "VARIANCE_DEFAULTS": variance_defaults,
-                  "DENOISE_VARIANCE_DEFAULTS": denoise_variance_defaults, "TEMPORAL_VARIANCE_DEFAULTS": temporal_variance_defaults,
-                  "TRACE_DEFAULTS": trace_defaults}
+# trace_defaults(lib=None), denoise_defaults(lib=None), ...: the library's defaults of a parameter struct as a dict; and
+# TRACE_DEFAULTS, DENOISE_DEFAULTS, ...: the same, read when first asked for, so that importing this module does not need the built
+# library (and never kept: `lib` exists so that two builds can be driven side by side)
+_DEFAULTS = (
+    ("trace_defaults", TraceParams, "srt_trace_params_default"),
+    ("denoise_defaults", DenoiseParams, "srt_denoise_params_default"),
+    ("temporal_defaults", TemporalParams, "srt_temporal_params_default"),
+    ("upsample_defaults", UpsampleParams, "srt_upsample_params_default"),
+    ("antialias_defaults", AntialiasParams, "srt_antialias_params_default"),
+    ("variance_defaults", VarianceParams, "srt_variance_params_default"),
+    ("denoise_variance_defaults", DenoiseVarianceParams, "srt_denoise_variance_params_default"),
+    ("temporal_variance_defaults", TemporalVarianceParams, "srt_temporal_variance_params_default"),
+)
+_LAZY_DEFAULTS = {}
+for _name, _struct, _symbol in _DEFAULTS:
+    globals()[_name] = _LAZY_DEFAULTS[_name.upper()] = _defaults_function(_name, _struct, _symbol)
 
 
 def __getattr__(name):
@@ -899,65 +856,52 @@ def __getattr__(name):
 
 def denoise_params(iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None, albedo=True, framebuffer=False, lib=None):
     """A DenoiseParams: the library defaults, with every argument that is not None put in their place."""
-    d = denoise_defaults(lib)
     flags = (DENOISE_ALBEDO if albedo else 0) | (DENOISE_FRAMEBUFFER if framebuffer else 0)
-    return DenoiseParams(int(d["iterations"] if iterations is None else iterations),
-                         float(d["sigma_color"] if sigma_color is None else sigma_color),
-                         float(d["sigma_normal"] if sigma_normal is None else sigma_normal),
-                         float(d["sigma_plane"] if sigma_plane is None else sigma_plane), flags)
+    return _set(_default_params(DenoiseParams, "srt_denoise_params_default", lib), iterations=iterations, sigma_color=sigma_color,
+                sigma_normal=sigma_normal, sigma_plane=sigma_plane, flags=flags)
 
 
 def temporal_params(samples=1, max_samples=None, plane_tolerance=None, normal_threshold=None, reset=False, framebuffer=False,
                     lib=None):
     """A TemporalParams: the library defaults, with every argument that is not None put in their place."""
-    d = temporal_defaults(lib)
     flags = (TEMPORAL_RESET if reset else 0) | (TEMPORAL_FRAMEBUFFER if framebuffer else 0)
-    return TemporalParams(int(samples), float(d["max_samples"] if max_samples is None else max_samples),
-                          float(d["plane_tolerance"] if plane_tolerance is None else plane_tolerance),
-                          float(d["normal_threshold"] if normal_threshold is None else normal_threshold), flags)
+    return _set(_default_params(TemporalParams, "srt_temporal_params_default", lib), samples=int(samples), max_samples=max_samples,
+                plane_tolerance=plane_tolerance, normal_threshold=normal_threshold, flags=flags)
 
 
 def upsample_params(steps=None, stripe_width=None, sigma_normal=None, sigma_plane=None, in_place=False, framebuffer=False, lib=None):
     """An UpsampleParams: the library defaults, with every argument that is not None put in their place."""
-    d = upsample_defaults(lib)
     flags = (UPSAMPLE_IN_PLACE if in_place else 0) | (UPSAMPLE_FRAMEBUFFER if framebuffer else 0)
-    return UpsampleParams(int(d["steps"] if steps is None else steps), int(d["stripe_width"] if stripe_width is None else stripe_width),
-                          float(d["sigma_normal"] if sigma_normal is None else sigma_normal),
-                          float(d["sigma_plane"] if sigma_plane is None else sigma_plane), flags)
+    return _set(_default_params(UpsampleParams, "srt_upsample_params_default", lib), steps=steps, stripe_width=stripe_width,
+                sigma_normal=sigma_normal, sigma_plane=sigma_plane, flags=flags)
 
 
 def antialias_params(k=None, denoised=False, framebuffer=False, lib=None):
     """An AntialiasParams: the library's default k unless one is given, the source and the flag by name."""
-    d = antialias_defaults(lib)
-    return AntialiasParams(int(d["k"] if k is None else k), AA_SOURCE_DENOISED if denoised else AA_SOURCE_ACCUMULATOR,
-                           AA_FRAMEBUFFER if framebuffer else 0)
+    return _set(_default_params(AntialiasParams, "srt_antialias_params_default", lib), k=k,
+                source=AA_SOURCE_DENOISED if denoised else AA_SOURCE_ACCUMULATOR, flags=AA_FRAMEBUFFER if framebuffer else 0)
 
 
 def variance_params(albedo=None, merge=None, lib=None):
     """A VarianceParams: the library's default flags, each overridden by name when given."""
-    flags = variance_defaults(lib)["flags"]
+    p = _default_params(VarianceParams, "srt_variance_params_default", lib)
     for bit, on in ((VARIANCE_ALBEDO, albedo), (VARIANCE_MERGE, merge)):
         if on is not None:
-            flags = (flags | bit) if on else (flags & ~bit)
-    return VarianceParams(flags)
+            p.flags = (p.flags | bit) if on else (p.flags & ~bit)
+    return p
 
 
 def denoise_variance_params(iterations=None, sigma_luminance=None, sigma_normal=None, sigma_plane=None, albedo=True,
                             framebuffer=False, lib=None):
     """A DenoiseVarianceParams: the library's defaults with the given fields replaced and the flags by name."""
-    d = denoise_variance_defaults(lib)
     flags = (DENOISE_ALBEDO if albedo else 0) | (DENOISE_FRAMEBUFFER if framebuffer else 0)
-    return DenoiseVarianceParams(int(d["iterations"] if iterations is None else iterations),
-                                 float(d["sigma_luminance"] if sigma_luminance is None else sigma_luminance),
-                                 float(d["sigma_normal"] if sigma_normal is None else sigma_normal),
-                                 float(d["sigma_plane"] if sigma_plane is None else sigma_plane), flags)
+    return _set(_default_params(DenoiseVarianceParams, "srt_denoise_variance_params_default", lib), iterations=iterations,
+                sigma_luminance=sigma_luminance, sigma_normal=sigma_normal, sigma_plane=sigma_plane, flags=flags)
 
 
 def temporal_variance_params(min_frames=None, radius=None, lib=None):
     """A TemporalVarianceParams: the library's defaults with the given fields replaced."""
-    d = temporal_variance_defaults(lib)
-    return TemporalVarianceParams(float(d["min_frames"] if min_frames is None else min_frames),
-                                  int(d["radius"] if radius is None else radius), int(d["flags"]))
+    return _set(_default_params(TemporalVarianceParams, "srt_temporal_variance_params_default", lib), min_frames=min_frames, radius=radius)
 
 
 def _f3(v):
@@ -1113,10 +1057,65 @@ class PathTracer:
         rc = self.L.srt_create(int(device), self.width, self.height, C.byref(self._h))
         if rc:
             raise SrtError(rc, (self.L.srt_last_error(None) or b"").decode())
+        # What this object remembers of its calls: sizes the readers shape their arrays by, switches that change what a later
+        # call enqueues, and the tensors bound by address, which stay referenced for as long as they are bound.
+        self._ray_count = None  # rays of the current batch (written or bound)
+        self._ray_own_count = None  # rays in the handle's own buffers, current again after bind_rays(None, None)
+        self._ray_bound = None  # (origins, directions) tensors of bind_rays
+        self._ray_out_bound = {}  # output name -> tensor of bind_ray_output
+        self._ray_traced = None  # rays of the last trace_rays / trace_occlusion: ray_output()'s length
+        self._radiance_bound = None  # tensor of bind_radiance
+        self._radiance_traced = None  # rays of the last trace_radiance: radiance()'s length
+        self._reflection_guides = False  # use_reflection_guides(): gbuffer=True renders the reflection guides
+        self._mirror_history = False  # mirror_history(): temporal(gbuffer=True) also renders the reflection outputs it reads
+        self._moments_albedo = False  # moments_output(albedo=True): temporal(gbuffer=True) also renders the ALBEDO guide
+        self._subsample_k = 0  # k of the last render_subsamples / bind_subsamples: subsamples()'s shape
+        self._probe_count = None  # current probe positions (written or bound)
+        self._probe_bound = None  # positions tensor, while bound
+        self._probe_dir_count = None  # current shared directions (written or bound)
+        self._probe_dir_bound = None  # directions tensor, while bound
+        self._probe_out_bound = {}  # LIGHT_PROBE_* bit -> tensor of bind_light_probe_output
+        self._probes_traced = (None, None)  # (probes, directions) of the last trace_light_probes: its readers' shapes
+        self._probe_grid_probes = None  # probes of the grid of set_probe_grid
+        self._probe_grid_bound = None  # coefficients tensor a shade_probe_grid* call bound
+        self._probe_grid_out_bound = None  # tensor of bind_probe_grid_output
+        self._probe_depth_bound = {}  # PROBE_DEPTH_* bit -> tensor of bind_probe_depth_output
+        self._probe_depth_traced = None  # (probes, directions, resolution) of the last trace_probe_depth
+        self._probe_grid_depth_bound = None  # moments tensor of bind_probe_grid_depth
+        self._probe_states_bound = {}  # PROBE_STATE_* bit -> tensor of bind_probe_states_output
+        self._probe_states_classified = None  # probes of the last classify_probes: probe_states_output()'s length
+        self._probe_grid_states_bound = None  # records tensor of bind_probe_grid_states
+        self._probe_list_out_bound = None  # tensor of bind_probe_list_output
+        self._probe_list_bound = None  # tensor of bind_probe_list
+        self._probe_history_sizes = {}  # PROBE_HISTORY_* bit -> (probes, resolution) of reset_probe_history
+        self._probe_history_bound = {}  # PROBE_HISTORY_* bit -> tensor of bind_probe_history
+        self._probe_previous_bound = None  # records tensor of bind_probe_previous_states
+        self._probe_cascade = None  # the ProbeCascade of set_probe_cascade
+        self._probe_cascade_bound = {}  # (level, PROBE_CASCADE_* bit) -> tensor of bind_probe_cascade_level
 
     def _ck(self, rc):
         if rc:
             raise SrtError(rc, (self.L.srt_last_error(self._h) or b"").decode())
+
+    def _default(self, struct, fn):
+        """A parameter struct filled by one srt_*_params_default of this tracer's library."""
+        p = struct()
+        self._ck(fn(C.byref(p)))
+        return p
+
+    def _band(self, rows):
+        """A band of memory rows as (begin, end); None: the whole frame."""
+        return (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
+
+    def _get_record(self, struct, fn):
+        """One srt_get_*: a new `struct` filled by fn(handle, pointer to it)."""
+        record = struct()
+        self._ck(fn(self._h, C.byref(record)))
+        return record
+
+    def _get_work(self, struct, fn):
+        """The record a counting call left, as a dict (WorkRecord.as_dict).  Waits."""
+        return self._get_record(struct, fn).as_dict()
 
     def close(self):
         if self._h:
@@ -1155,9 +1154,7 @@ class PathTracer:
 
     def update_info(self):
         """srt_get_update_info: what the last update_scene() did, as a dict (path 1 rebuilt, 2 refitted, 3 kept; UPDATE_PATHS)."""
-        u = UpdateInfo()
-        self._ck(self.L.srt_get_update_info(self._h, C.byref(u)))
-        return u.as_dict()
+        return self._get_work(UpdateInfo, self.L.srt_get_update_info)
 
     def mesh_image(self):
         """srt_read_mesh_image: the mesh image as the kernels read it: (nodes (N, 5, 4) float32, triangles (T, 3, 4) float32)."""
@@ -1197,7 +1194,7 @@ class PathTracer:
     def render_gbuffer(self, rows=None, outputs=GBUF_ALL, flags=0):
         """srt_render_gbuffer: the first-hit buffers of memory rows `rows` (default: the whole frame).  `outputs`: an SRT_GBUF_*
         mask or names of GBUFFERS.  Asynchronous, like render()."""
-        rb, re = rows if rows is not None else (0, self.height)
+        rb, re = self._band(rows)
         p = GBufferParams(int(rb), int(re), gbuffer_outputs(outputs), int(flags))
         self._ck(self.L.srt_render_gbuffer(self._h, C.byref(p)))
 
@@ -1207,22 +1204,22 @@ class PathTracer:
         self._ck(fn(self._h, *args, out.ctypes.data_as(fn.argtypes[-1])))
         return out
 
-    def _gbuffer_shape(self, name):
-        _, dtype, ch = _gbuffer_spec(name)
-        return dtype, ((self.height, self.width) if ch == 1 else (self.height, self.width, ch))
+    def _image_spec(self, table, name, what):
+        """(bit, dtype, shape) of one per-pixel output of GBUFFERS or REFLECTION."""
+        bit, dtype, ch = _spec(table, name, what)
+        return bit, dtype, ((self.height, self.width) if ch == 1 else (self.height, self.width, ch))
 
     def gbuffer(self, name):
         """srt_read_gbuffer: the whole buffer of one output as a numpy array, rows = scene rows (the orientation of
         accumulator()): "object" (H, W) int32, the others (H, W, 4) float32."""
-        dtype, shape = self._gbuffer_shape(name)
-        return self._read_image(self.L.srt_read_gbuffer, shape, dtype, GBUFFERS[name][0])
+        bit, dtype, shape = self._image_spec(GBUFFERS, name, "G-buffer output")
+        return self._read_image(self.L.srt_read_gbuffer, shape, dtype, bit)
 
     def bind_gbuffer(self, name, tensor):
         """srt_bind_gbuffer: write output `name` into a torch tensor on this tracer's device (None: the handle's own buffer).
         Device, dtype, shape and contiguity are checked here, before any native call; the caller keeps the tensor alive
         until the work that writes it has finished."""
-        bit = _gbuffer_spec(name)[0]
-        dtype, shape = self._gbuffer_shape(name)
+        bit, dtype, shape = self._image_spec(GBUFFERS, name, "G-buffer output")
         ptr = self._tensor_ptr("bind_gbuffer(%r)" % name, tensor, dtype, shape)  # (checked before the library is touched)
         self._ck(self.L.srt_bind_gbuffer(self._h, bit, ptr))
 
@@ -1272,7 +1269,7 @@ class PathTracer:
         caller keeps the arrays alive until the traces that read them have finished."""
         if origins is None and directions is None:
             self._ck(self.L.srt_bind_rays(self._h, None, None, 0))
-            self._ray_count = getattr(self, "_ray_own_count", None)
+            self._ray_count = self._ray_own_count
             self._ray_bound = None
             return
         if isinstance(origins, (int, np.integer)) and isinstance(directions, (int, np.integer)):
@@ -1297,12 +1294,23 @@ class PathTracer:
         self._ray_count = n
         self._ray_bound = keep  # (bound tensors stay referenced for as long as they are bound)
 
+    def _rays_given(self, what, origins, directions):
+        """The `origins` / `directions` of a trace: host arrays are written (write_rays), device tensors bound (bind_rays); both
+        None: the current rays stay."""
+        if (origins is None) != (directions is None):
+            raise ValueError("%s: origins and directions go together" % what)
+        if origins is not None:
+            if self._ray_array("%s(origins)" % what, origins)[0] == "host":
+                self.write_rays(origins, directions)
+            else:
+                self.bind_rays(origins, directions)
+
     def trace_rays(self, outputs=RAYS_ALL, normalize=False, flags=0):
         """srt_trace_rays: the closest hit of every current ray against the current scene.  `outputs`: a mask or names of
         RAY_OUTPUTS; normalize=True normalizes every direction first (SRT_RAYS_NORMALIZE).  Asynchronous, like render()."""
         p = TraceParams(ray_outputs(outputs), int(flags) | (RAYS_NORMALIZE if normalize else 0))
-        n = getattr(self, "_ray_count", None)
-        for name, t in getattr(self, "_ray_out_bound", {}).items():
+        n = self._ray_count
+        for name, t in self._ray_out_bound.items():
             if n is not None and (p.outputs & RAY_OUTPUTS[name][0]) and t.shape[0] < n:
                 raise ValueError("trace_rays: the tensor bound to %r holds %d elements, the batch has %d rays" % (name, t.shape[0], n))
         self._ck(self.L.srt_trace_rays(self._h, C.byref(p)))
@@ -1314,16 +1322,10 @@ class PathTracer:
         write_rays) or torch tensors on this tracer's device (bound with bind_rays, by data_ptr, no copy); both None: the current
         rays.  normalize: SRT_OCCLUSION_NORMALIZE; count_work: SRT_OCCLUSION_COUNT_WORK (occlusion_work() then reads the
         record).  Asynchronous, like render(); ray_output("occluded") reads the result."""
-        if (origins is None) != (directions is None):
-            raise ValueError("trace_occlusion: origins and directions go together")
-        if origins is not None:
-            if self._ray_array("trace_occlusion(origins)", origins)[0] == "host":
-                self.write_rays(origins, directions)
-            else:
-                self.bind_rays(origins, directions)
+        self._rays_given("trace_occlusion", origins, directions)
         p = OcclusionParams(int(flags) | (OCCLUSION_NORMALIZE if normalize else 0) | (OCCLUSION_COUNT_WORK if count_work else 0), 0)
-        n = getattr(self, "_ray_count", None)
-        t = getattr(self, "_ray_out_bound", {}).get("occluded")
+        n = self._ray_count
+        t = self._ray_out_bound.get("occluded")
         if n is not None and t is not None and t.shape[0] < n:
             raise ValueError("trace_occlusion: the tensor bound to 'occluded' holds %d elements, the batch has %d rays" % (t.shape[0], n))
         self._ck(self.L.srt_trace_occlusion(self._h, C.byref(p)))
@@ -1331,9 +1333,7 @@ class PathTracer:
 
     def occlusion_work(self):
         """srt_get_occlusion_work: the work counts of the last trace_occlusion(count_work=True) as a dict.  Waits."""
-        w = OcclusionWork()
-        self._ck(self.L.srt_get_occlusion_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(OcclusionWork, self.L.srt_get_occlusion_work)
 
     # ---- per-pixel visibility ------------------------------------------------------------
     def render_visibility(self, ao_samples=None, radius=None, sun=True, ao=True, first_sample=1, seed=0, rows=None, count_work=False):
@@ -1342,33 +1342,25 @@ class PathTracer:
         pixel, from the OBJECT, NORMAL_DEPTH and POSITION guides as they stand (render_gbuffer() first, or bind them).  `rows`:
         a band of memory rows (default: the whole frame).  count_work: SRT_VIS_COUNT_WORK (visibility_work() then reads the
         record).  Asynchronous, like render(); visibility("ao" | "sun") reads a result."""
-        p = VisibilityParams()
-        self._ck(self.L.srt_visibility_params_default(C.byref(p)))
-        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
-        p.outputs = (VIS_AO if ao else 0) | (VIS_SUN if sun else 0)
-        p.flags = VIS_COUNT_WORK if count_work else 0
-        if ao_samples is not None:
-            p.ao_samples = int(ao_samples)
-        if radius is not None:
-            p.ao_radius = float(radius)
-        p.first_sample, p.seed = int(first_sample), int(seed)
+        p = self._default(VisibilityParams, self.L.srt_visibility_params_default)
+        p.row_begin, p.row_end = self._band(rows)
+        _set(p, outputs=(VIS_AO if ao else 0) | (VIS_SUN if sun else 0), flags=VIS_COUNT_WORK if count_work else 0, ao_samples=ao_samples,
+             ao_radius=radius, first_sample=first_sample, seed=seed)
         self._ck(self.L.srt_render_visibility(self._h, C.byref(p)))
 
     def visibility(self, name):
         """srt_read_visibility: output "ao" or "sun" of the last render_visibility() as an (H, W) float32 array, rows = scene rows."""
-        return self._read_image(self.L.srt_read_visibility, (self.height, self.width), np.float32, VISIBILITY[name])
+        return self._read_image(self.L.srt_read_visibility, (self.height, self.width), np.float32, _spec(VISIBILITY, name))
 
     def bind_visibility(self, name, tensor):
         """srt_bind_visibility: write output "ao" or "sun" into a torch tensor (H, W) float32 on this tracer's device (None: the
         handle's own buffer), checked like bind_gbuffer's."""
         ptr = self._tensor_ptr("bind_visibility(%r)" % name, tensor, np.float32, (self.height, self.width))
-        self._ck(self.L.srt_bind_visibility(self._h, VISIBILITY[name], ptr))
+        self._ck(self.L.srt_bind_visibility(self._h, _spec(VISIBILITY, name), ptr))
 
     def visibility_work(self):
         """srt_get_visibility_work: the work counts of the last render_visibility(count_work=True) as a dict.  Waits."""
-        w = VisibilityWork()
-        self._ck(self.L.srt_get_visibility_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(VisibilityWork, self.L.srt_get_visibility_work)
 
     # ---- radiance queries ----------------------------------------------------------------
     # ---- reflection guides ----------------------------------------------------------------
@@ -1379,49 +1371,34 @@ class PathTracer:
         one, and the number of reflections.  `outputs`: an SRT_REFL_* mask or names of REFLECTION.  Arguments left at None take
         the library's defaults (8 reflections, smoothness and specular amount of at least 1).  count_work: SRT_REFL_COUNT_WORK
         (reflection_work() then reads the record).  Asynchronous, like render_gbuffer()."""
-        p = ReflectionParams()
-        self._ck(self.L.srt_reflection_params_default(C.byref(p)))
-        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
-        p.outputs = reflection_outputs(outputs)
-        p.flags = int(flags) | (REFL_COUNT_WORK if count_work else 0)
-        if max_bounces is not None:
-            p.max_bounces = int(max_bounces)
-        if min_smoothness is not None:
-            p.min_smoothness = float(min_smoothness)
-        if min_specular is not None:
-            p.min_specular = float(min_specular)
-        p.reserved = int(reserved)
+        p = self._default(ReflectionParams, self.L.srt_reflection_params_default)
+        p.row_begin, p.row_end = self._band(rows)
+        _set(p, outputs=reflection_outputs(outputs), flags=int(flags) | (REFL_COUNT_WORK if count_work else 0), max_bounces=max_bounces,
+             min_smoothness=min_smoothness, min_specular=min_specular, reserved=reserved)
         self._ck(self.L.srt_render_reflection_gbuffer(self._h, C.byref(p)))
-
-    def _reflection_shape(self, name):
-        _, dtype, ch = _reflection_spec(name)
-        return dtype, ((self.height, self.width) if ch == 1 else (self.height, self.width, ch))
 
     def read_reflection(self, name):
         """srt_read_reflection: the whole buffer of one output as a numpy array, rows = scene rows: "object" and "bounces"
         (H, W) int32, the others (H, W, 4) float32.  Waits."""
-        dtype, shape = self._reflection_shape(name)
-        return self._read_image(self.L.srt_read_reflection, shape, dtype, REFLECTION[name][0])
+        bit, dtype, shape = self._image_spec(REFLECTION, name, "reflection output")
+        return self._read_image(self.L.srt_read_reflection, shape, dtype, bit)
 
     def bind_reflection(self, name, tensor):
         """srt_bind_reflection: write output `name` into a torch tensor on this tracer's device (None: the handle's own
         buffer), checked like bind_gbuffer's."""
-        bit = _reflection_spec(name)[0]
-        dtype, shape = self._reflection_shape(name)
+        bit, dtype, shape = self._image_spec(REFLECTION, name, "reflection output")
         ptr = self._tensor_ptr("bind_reflection(%r)" % name, tensor, dtype, shape)
         self._ck(self.L.srt_bind_reflection(self._h, bit, ptr))
 
     def reflection_ptr(self, name):
         """srt_device_reflection: the device address of the handle's own buffer of output `name` (allocated on first use)."""
         p = C.c_void_p()
-        self._ck(self.L.srt_device_reflection(self._h, _reflection_spec(name)[0], C.byref(p)))
+        self._ck(self.L.srt_device_reflection(self._h, _spec(REFLECTION, name, "reflection output")[0], C.byref(p)))
         return p.value
 
     def reflection_work(self):
         """srt_get_reflection_work: the work counts of the last render_reflection_gbuffer(count_work=True) as a dict.  Waits."""
-        w = ReflectionWork()
-        self._ck(self.L.srt_get_reflection_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ReflectionWork, self.L.srt_get_reflection_work)
 
     def use_reflection_guides(self, on=True):
         """Steer the guided passes by the reflection guides: with `on` the handle's own four reflection guide buffers are bound
@@ -1440,11 +1417,7 @@ class PathTracer:
         they show, and accepts only history seen through the same mirror near the same terminal point (radius_pixels: the radius
         of that test in pixels; None: the library's default).  While on, temporal(gbuffer=True) renders the first hits AND the
         four reflection outputs the mode reads (object, normal_depth, position, bounces).  Switching drops the history."""
-        p = MirrorHistoryParams()
-        self._ck(self.L.srt_mirror_history_params_default(C.byref(p)))
-        p.enabled = 1 if on else 0
-        if radius_pixels is not None:
-            p.radius_pixels = float(radius_pixels)
+        p = _set(self._default(MirrorHistoryParams, self.L.srt_mirror_history_params_default), enabled=1 if on else 0, radius_pixels=radius_pixels)
         self._ck(self.L.srt_mirror_history(self._h, C.byref(p)))
         self._mirror_history = bool(on)
 
@@ -1454,28 +1427,21 @@ class PathTracer:
         surface adds the probe grid's hemisphere-mean radiance there (the grid, coefficients, depth maps and states current at the
         trace).  normal_weight / depth / states switch probe-grid rules 6 / 7b / 3s and 4s on; band_weight, bias and min_variance
         default to the library's (the hemisphere mean).  Touches no device memory."""
-        p = ProbeTailParams()
-        self._ck(self.L.srt_probe_tail_params_default(C.byref(p)))
-        p.enabled = 1 if enabled else 0
-        p.flags = ((PROBE_TAIL_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_TAIL_DEPTH if depth else 0) | (PROBE_TAIL_STATES if states else 0)
-                   | (PROBE_TAIL_COUNT_WORK if count_work else 0))
+        p = self._default(ProbeTailParams, self.L.srt_probe_tail_params_default)
+        flags = ((PROBE_TAIL_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_TAIL_DEPTH if depth else 0) | (PROBE_TAIL_STATES if states else 0)
+                 | (PROBE_TAIL_COUNT_WORK if count_work else 0))
         if band_weight is not None:
-            p.band_weight[:] = [float(v) for v in band_weight]
-        if bias is not None:
-            p.bias = float(bias)
-        if min_variance is not None:
-            p.min_variance = float(min_variance)
+            p.band_weight[:] = [float(v) for v in band_weight]  # (exactly three: a slice assignment refuses any other length)
+        _set(p, enabled=1 if enabled else 0, flags=flags, bias=bias, min_variance=min_variance)
         self._ck(self.L.srt_probe_tail(self._h, C.byref(p)))
 
     def probe_tail_work(self):
         """srt_get_probe_tail_work as a dict: the record of the last trace that ran under probe_tail(count_work=True)."""
-        w = ProbeTailWork()
-        self._ck(self.L.srt_get_probe_tail_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeTailWork, self.L.srt_get_probe_tail_work)
 
     def _render_guides(self, outputs, what, first_hit_only=False):
         """The guides a pass with gbuffer=True renders first: first hits, or the reflection guides while they are in use."""
-        if not getattr(self, "_reflection_guides", False):
+        if not self._reflection_guides:
             return self.render_gbuffer(outputs=outputs)
         if first_hit_only:
             raise ValueError("%s works on first hits: use_reflection_guides(False) first, or pass guides of your own" % what)
@@ -1489,24 +1455,12 @@ class PathTracer:
         the current rays.  Ray i draws from the stream of pixel id_base + i; reset=False continues the mean the output holds;
         normalize: SRT_RADIANCE_NORMALIZE; count_work: SRT_RADIANCE_COUNT_WORK (radiance_work() then reads the record).
         Asynchronous, like render(); radiance() reads the result."""
-        if (origins is None) != (directions is None):
-            raise ValueError("trace_radiance: origins and directions go together")
-        if origins is not None:
-            if self._ray_array("trace_radiance(origins)", origins)[0] == "host":
-                self.write_rays(origins, directions)
-            else:
-                self.bind_rays(origins, directions)
-        p = RadianceParams()
-        self._ck(self.L.srt_radiance_params_default(C.byref(p)))
-        if samples is not None:
-            p.sample_count = int(samples)
-        if bounces is not None:
-            p.max_bounces = int(bounces)
-        p.first_sample, p.seed, p.id_base = int(first_sample), int(seed) & 0xFFFFFFFF, int(id_base) & 0xFFFFFFFF
-        p.flags = (int(flags) | (RADIANCE_RESET if reset else 0) | (RADIANCE_NORMALIZE if normalize else 0) |
-                   (RADIANCE_COUNT_WORK if count_work else 0))
-        n = getattr(self, "_ray_count", None)
-        t = getattr(self, "_radiance_bound", None)
+        self._rays_given("trace_radiance", origins, directions)
+        p = self._default(RadianceParams, self.L.srt_radiance_params_default)
+        _set(p, sample_count=samples, max_bounces=bounces, first_sample=first_sample, seed=int(seed) & 0xFFFFFFFF, id_base=int(id_base) & 0xFFFFFFFF,
+             flags=int(flags) | (RADIANCE_RESET if reset else 0) | (RADIANCE_NORMALIZE if normalize else 0) | (RADIANCE_COUNT_WORK if count_work else 0))
+        n = self._ray_count
+        t = self._radiance_bound
         if n is not None and t is not None and t.shape[0] < n:
             raise ValueError("trace_radiance: the bound tensor holds %d elements, the batch has %d rays" % (t.shape[0], n))
         self._ck(self.L.srt_trace_radiance(self._h, C.byref(p)))
@@ -1516,33 +1470,20 @@ class PathTracer:
         """srt_bind_radiance: write the radiance into a torch tensor (M, 4) float32 on this tracer's device, contiguous, M at least
         the batch size (checked by trace_radiance); None: the handle's own buffer.  The caller keeps the tensor alive until the
         traces have finished."""
-        if tensor is not None:
-            import torch
-
-            if not isinstance(tensor, torch.Tensor):
-                raise TypeError("bind_radiance: expected a torch.Tensor, got %s" % type(tensor).__name__)
-            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
-            if m < 1:
-                raise ValueError("bind_radiance: shape %s, want at least one element" % (tuple(tensor.shape),))
-            ptr = self._tensor_ptr("bind_radiance", tensor, np.float32, (m, 4))
-        else:
-            ptr = None
-        self._ck(self.L.srt_bind_radiance(self._h, ptr))
+        self._bind_sized("bind_radiance", self.L.srt_bind_radiance, (), tensor, np.float32, (4,))
         self._radiance_bound = tensor
 
     def radiance(self, count=None):
         """srt_read_radiance: the result of the last trace_radiance() as an (N, 4) float32 array.  `count`: N, for rays bound by
         raw pointer on another PathTracer object (default: this one's).  Waits."""
-        n = count if count is not None else getattr(self, "_radiance_traced", None)
+        n = count if count is not None else self._radiance_traced
         if n is None:
             raise SrtError(ERR_STATE, "radiance(): no trace_radiance() yet")
         return self._read_image(self.L.srt_read_radiance, (n, 4), np.float32)
 
     def radiance_work(self):
         """srt_get_radiance_work: the work counts of the last trace_radiance(count_work=True) as a dict.  Waits."""
-        w = RadianceWork()
-        self._ck(self.L.srt_get_radiance_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(RadianceWork, self.L.srt_get_radiance_work)
 
     # ---- adaptive sampling -----------------------------------------------------------------
     def _u32_frame(self, what, arr):
@@ -1591,18 +1532,10 @@ class PathTracer:
         """srt_sample_budget over the whole frame: the variance buffer, the counts, the accumulator and the OBJECT (and ALBEDO)
         guides as they stand -> the budget buffer.  Arguments left at None take srt_budget_params_default.  Asynchronous;
         budget_total() reads the sum, sample_budget_map() the map."""
-        p = BudgetParams()
-        self._ck(self.L.srt_budget_params_default(C.byref(p)))
-        if threshold is not None:
-            p.threshold = float(threshold)
-        if floor is not None:
-            p.floor = float(floor)
-        if max_budget is not None:
-            p.max_budget = int(max_budget)
+        p = _set(self._default(BudgetParams, self.L.srt_budget_params_default), threshold=threshold, floor=floor, max_budget=max_budget)
         if albedo is not None:
             p.flags = (p.flags & ~BUDGET_ALBEDO) | (BUDGET_ALBEDO if albedo else 0)
-        if flags is not None:
-            p.flags = int(flags)
+        _set(p, flags=flags)
         self._ck(self.L.srt_sample_budget(self._h, C.byref(p)))
 
     def budget_total(self):
@@ -1615,16 +1548,10 @@ class PathTracer:
         """srt_render_adaptive: every pixel of memory rows `rows` (default: the whole frame) takes min(budget, max_samples) more
         samples, continuing its running mean from its count; the counts advance unless keep_counts.  Arguments left at None take
         srt_adaptive_params_default.  Asynchronous, like render().  (`tail` is render_adaptive_tail()'s switch.)"""
-        p = AdaptiveParams()
-        self._ck(self.L.srt_adaptive_params_default(C.byref(p)))
-        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
-        if bounces is not None:
-            p.max_bounces = int(bounces)
-        if max_samples is not None:
-            p.max_samples = int(max_samples)
-        p.seed = int(seed) & 0xFFFFFFFF
-        p.flags = int(flags) | (ADAPTIVE_KEEP_COUNTS if keep_counts else 0) | (ADAPTIVE_COUNT_WORK if count_work else 0)
-        p.reserved = int(reserved)
+        p = self._default(AdaptiveParams, self.L.srt_adaptive_params_default)
+        p.row_begin, p.row_end = self._band(rows)
+        _set(p, max_bounces=bounces, max_samples=max_samples, seed=int(seed) & 0xFFFFFFFF, reserved=reserved,
+             flags=int(flags) | (ADAPTIVE_KEEP_COUNTS if keep_counts else 0) | (ADAPTIVE_COUNT_WORK if count_work else 0))
         self._ck((self.L.srt_render_adaptive_tail if tail else self.L.srt_render_adaptive)(self._h, C.byref(p)))
 
     def render_adaptive_tail(self, bounces=None, seed=0, max_samples=None, rows=None, keep_counts=False, count_work=False, flags=0, reserved=0):
@@ -1635,21 +1562,61 @@ class PathTracer:
 
     def adaptive_work(self):
         """srt_get_adaptive_work: the work counts of the last render_adaptive(count_work=True) as a dict.  Waits."""
-        w = AdaptiveWork()
-        self._ck(self.L.srt_get_adaptive_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(AdaptiveWork, self.L.srt_get_adaptive_work)
 
     # ---- light probes ----------------------------------------------------------------------
-    def _light_probe_input(self, what, a, write, bind, limit):
-        """Make `a` the current positions or directions: a host array (N, 4) is written, a device tensor bound."""
+    def _input(self, what, a, write, bind, per_probe=1, want=None, limit=None, extra=()):
+        """Make `a` a current input array of float4: a host array (N, 4) float32 is written (copied) with `write`, a torch tensor
+        (N, 4) on this tracer's device is bound with `bind` by its data_ptr(), no copy, and None unbinds: the handle's own array
+        is current again.  The native call gets N / per_probe as its count (`want` says per_probe in the refusal of an N that
+        is no multiple of it; `limit`: the largest N), then `extra`.  Returns (count, tensor): the caller keeps the tensor
+        referenced for as long as it is bound (None: nothing is bound)."""
+        if a is None:
+            self._ck(bind(self._h, None, 0, *extra))
+            return 0, None
         kind, arr, n = self._ray_array(what, a)
-        if n > limit:
+        if limit is not None and n > limit:
             raise ValueError("%s: %d elements, want 1 .. %d" % (what, n, limit))
+        if per_probe < 1 or n % per_probe:
+            raise ValueError("%s: %d float4, want %s per probe" % (what, n, want))
         if kind == "host":
-            self._ck(write(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n))
-            return n, None
-        self._ck(bind(self._h, C.c_void_p(arr.data_ptr()), n))
-        return n, arr  # (a bound tensor stays referenced for as long as it is bound)
+            self._ck(write(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n // per_probe, *extra))
+            return n // per_probe, None
+        self._ck(bind(self._h, C.c_void_p(arr.data_ptr()), n // per_probe, *extra))
+        return n // per_probe, arr
+
+    def _probe_inputs(self, what, positions, directions):
+        """The `positions` / `directions` of a probe trace: each a host array (written) or a device tensor (bound), `directions`
+        also an int K for light_probe_sphere(K); None: the current ones stay."""
+        L = self.L
+        if positions is not None:
+            self._probe_count, self._probe_bound = self._input("%s(positions)" % what, positions, L.srt_write_light_probes,
+                                                               L.srt_bind_light_probes, limit=1 << 30)
+        if directions is not None:
+            if isinstance(directions, (int, np.integer)):
+                directions = light_probe_sphere(int(directions), lib=L)
+            self._probe_dir_count, self._probe_dir_bound = self._input("%s(directions)" % what, directions, L.srt_write_light_probe_directions,
+                                                                       L.srt_bind_light_probe_directions, limit=LIGHT_PROBE_MAX_DIRECTIONS)
+
+    def _bind_sized(self, what, fn, args, tensor, dtype, row, bound=None, key=None):
+        """Bind an output whose length the traces set: a torch tensor (M,) + `row` of numpy dtype `dtype` on this tracer's device,
+        contiguous, M >= 1 (the trace that writes it checks M against its batch); None: the handle's own buffer.  All checks come
+        first, then fn(handle, *args, pointer), then `bound[key]` keeps the tensor referenced for as long as it is bound."""
+        ptr = None
+        if tensor is not None:
+            import torch
+
+            if not isinstance(tensor, torch.Tensor):
+                raise TypeError("%s: expected a torch.Tensor, got %s" % (what, type(tensor).__name__))
+            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
+            if m < 1:
+                raise ValueError("%s: shape %s, want at least one element" % (what, tuple(tensor.shape)))
+            ptr = self._tensor_ptr(what, tensor, dtype, (m,) + row)
+        self._ck(fn(self._h, *args, ptr))
+        if bound is not None and tensor is None:
+            bound.pop(key, None)
+        elif bound is not None:
+            bound[key] = tensor
 
     def trace_light_probes(self, positions=None, directions=None, samples=None, bounces=None, seed=0, first_sample=1, reset=True, id_base=0,
                            normalize=False, count_work=False, coefficients=True, radiance=False, flags=0, listed=False):
@@ -1663,30 +1630,16 @@ class PathTracer:
         only the probes of the list bound for tracing (bind_probe_list()); every other probe's outputs keep their bits.
         Asynchronous, like render()."""
         L = self.L
-        if positions is not None:
-            self._probe_count, self._probe_bound = self._light_probe_input("trace_light_probes(positions)", positions, L.srt_write_light_probes,
-                                                                           L.srt_bind_light_probes, 1 << 30)
-        if directions is not None:
-            if isinstance(directions, (int, np.integer)):
-                directions = light_probe_sphere(int(directions), lib=L)
-            self._probe_dir_count, self._probe_dir_bound = self._light_probe_input("trace_light_probes(directions)", directions,
-                                                                                   L.srt_write_light_probe_directions,
-                                                                                   L.srt_bind_light_probe_directions, LIGHT_PROBE_MAX_DIRECTIONS)
-        p = LightProbeParams()
-        self._ck(L.srt_light_probe_params_default(C.byref(p)))
-        if samples is not None:
-            p.sample_count = int(samples)
-        if bounces is not None:
-            p.max_bounces = int(bounces)
-        p.first_sample, p.seed, p.id_base = int(first_sample), int(seed) & 0xFFFFFFFF, int(id_base) & 0xFFFFFFFF
-        p.flags = (int(flags) | (LIGHT_PROBE_RESET if reset else 0) | (LIGHT_PROBE_NORMALIZE if normalize else 0) |
-                   (LIGHT_PROBE_COUNT_WORK if count_work else 0))
-        p.outputs = (LIGHT_PROBE_COEFFICIENTS if coefficients else 0) | (LIGHT_PROBE_RADIANCE if radiance else 0)
-        np_, nk = getattr(self, "_probe_count", None), getattr(self, "_probe_dir_count", None)
+        self._probe_inputs("trace_light_probes", positions, directions)
+        p = self._default(LightProbeParams, L.srt_light_probe_params_default)
+        _set(p, sample_count=samples, max_bounces=bounces, first_sample=first_sample, seed=int(seed) & 0xFFFFFFFF, id_base=int(id_base) & 0xFFFFFFFF,
+             flags=int(flags) | (LIGHT_PROBE_RESET if reset else 0) | (LIGHT_PROBE_NORMALIZE if normalize else 0) |
+             (LIGHT_PROBE_COUNT_WORK if count_work else 0),
+             outputs=(LIGHT_PROBE_COEFFICIENTS if coefficients else 0) | (LIGHT_PROBE_RADIANCE if radiance else 0))
+        np_, nk = self._probe_count, self._probe_dir_count
         if np_ is not None and nk is not None:
-            bound = self.__dict__.get("_probe_out_bound", {})
             for bit, need in ((LIGHT_PROBE_COEFFICIENTS, np_ * LIGHT_PROBE_COEFFS), (LIGHT_PROBE_RADIANCE, np_ * nk)):
-                t = bound.get(bit)
+                t = self._probe_out_bound.get(bit)
                 if (p.outputs & bit) and t is not None and t.shape[0] < need:
                     raise ValueError("trace_light_probes: the bound tensor holds %d elements, the call writes %d" % (t.shape[0], need))
         self._ck((L.srt_trace_light_probes_listed if listed else L.srt_trace_light_probes)(self._h, C.byref(p)))
@@ -1696,29 +1649,12 @@ class PathTracer:
         """srt_bind_light_probe_output: write output "coefficients" (P*9 float4) or "radiance" (P*K float4) into a torch tensor (M, 4)
         float32 on this tracer's device, contiguous, M at least that many (checked by trace_light_probes); None: the handle's own
         buffer.  The caller keeps the tensor alive until the traces have finished."""
-        bit = {"coefficients": LIGHT_PROBE_COEFFICIENTS, "radiance": LIGHT_PROBE_RADIANCE}.get(output, output)
-        if tensor is not None:
-            import torch
-
-            if not isinstance(tensor, torch.Tensor):
-                raise TypeError("bind_light_probe_output: expected a torch.Tensor, got %s" % type(tensor).__name__)
-            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
-            if m < 1:
-                raise ValueError("bind_light_probe_output: shape %s, want at least one element" % (tuple(tensor.shape),))
-            ptr = self._tensor_ptr("bind_light_probe_output", tensor, np.float32, (m, 4))
-        else:
-            ptr = None
-        self._ck(self.L.srt_bind_light_probe_output(self._h, int(bit), ptr))
-        bound = self.__dict__.setdefault("_probe_out_bound", {})
-        if tensor is None:
-            bound.pop(bit, None)
-        else:
-            bound[bit] = tensor
+        bit = _bit(LIGHT_PROBE_OUTPUTS, output)
+        self._bind_sized("bind_light_probe_output", self.L.srt_bind_light_probe_output, (bit,), tensor, np.float32, (4,), self._probe_out_bound, bit)
 
     def _light_probe_counts(self, what, probes, directions):
-        t = getattr(self, "_probes_traced", None) or (None, None)
-        p = probes if probes is not None else t[0]
-        k = directions if directions is not None else t[1]
+        p = probes if probes is not None else self._probes_traced[0]
+        k = directions if directions is not None else self._probes_traced[1]
         if p is None or k is None:
             raise SrtError(ERR_STATE, "%s: no trace_light_probes() yet" % what)
         return int(p), int(k)
@@ -1736,9 +1672,7 @@ class PathTracer:
 
     def light_probe_work(self):
         """srt_get_light_probe_work: the work counts of the last trace_light_probes(count_work=True) as a dict.  Waits."""
-        w = LightProbeWork()
-        self._ck(self.L.srt_get_light_probe_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(LightProbeWork, self.L.srt_get_light_probe_work)
 
     # ---- probe-grid shading -----------------------------------------------------------------
     def set_probe_grid(self, origin, spacing=None, counts=None):
@@ -1757,32 +1691,35 @@ class PathTracer:
         of SH bands 0, 1, 2 (default PROBE_GRID_BAND_WEIGHT_IRRADIANCE).  `output`: a torch tensor (H, W, 4) float32 to write
         (bind_probe_grid_output).  count_work: SRT_PROBE_GRID_COUNT_WORK (probe_grid_work() then reads the record).  Asynchronous,
         like render(); probe_grid_output() reads the result."""
-        L = self.L
-        if coefficients is not None:
-            a = coefficients
-            if isinstance(a, np.ndarray) and a.ndim == 3:
-                a = a.reshape(-1, 4)
-            kind, arr, n = self._ray_array("shade_probe_grid(coefficients)", a)
-            if n % LIGHT_PROBE_COEFFS:
-                raise ValueError("shade_probe_grid(coefficients): %d float4, want nine per probe" % n)
-            if kind == "host":
-                self._ck(L.srt_write_probe_grid_coefficients(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n // LIGHT_PROBE_COEFFS))
-                self._probe_grid_bound = None
-            else:
-                self._ck(L.srt_bind_probe_grid_coefficients(self._h, C.c_void_p(arr.data_ptr()), n // LIGHT_PROBE_COEFFS))
-                self._probe_grid_bound = arr  # (a bound tensor stays referenced for as long as it is bound)
+        self._probe_grid_coefficients("shade_probe_grid(coefficients)", coefficients)
         if output is not None:
             self.bind_probe_grid_output(output)
-        p = ProbeGridParams()
-        self._ck(L.srt_probe_grid_params_default(C.byref(p)))
-        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
-        p.flags = (int(flags) | (PROBE_GRID_VISIBILITY if visibility else 0) | (PROBE_GRID_NORMAL_WEIGHT if normal_weight else 0) |
-                   (PROBE_GRID_ALBEDO if albedo else 0) | (PROBE_GRID_COUNT_WORK if count_work else 0))
-        if band_weight is not None:
-            for b in range(3):
-                p.band_weight[b] = float(band_weight[b])
-        p.reserved[0], p.reserved[1] = int(reserved[0]), int(reserved[1])
-        self._ck(L.srt_shade_probe_grid(self._h, C.byref(p)))
+        p = self._probe_grid_params(rows, int(flags) | (PROBE_GRID_VISIBILITY if visibility else 0), normal_weight, albedo, count_work, band_weight,
+                                    reserved)
+        self._ck(self.L.srt_shade_probe_grid(self._h, C.byref(p)))
+
+    def _probe_grid_coefficients(self, what, coefficients):
+        """The `coefficients` of a shade_probe_grid* call: numpy (P, 9, 4) or (P*9, 4) is written, a device tensor (P*9, 4) bound
+        (_input); None: the current ones stay."""
+        if coefficients is None:
+            return
+        if isinstance(coefficients, np.ndarray) and coefficients.ndim == 3:
+            coefficients = coefficients.reshape(-1, 4)
+        _, self._probe_grid_bound = self._input(what, coefficients, self.L.srt_write_probe_grid_coefficients,
+                                                self.L.srt_bind_probe_grid_coefficients, LIGHT_PROBE_COEFFS, "nine")
+
+    def _probe_grid_params(self, rows, flags, normal_weight, albedo, count_work, band_weight, reserved):
+        """The srt_probe_grid_params of a shade_probe_grid* call: the library's defaults, the band, `flags` and the three switches,
+        and band_weight when given."""
+        p = self._default(ProbeGridParams, self.L.srt_probe_grid_params_default)
+        p.row_begin, p.row_end = self._band(rows)
+        flags |= (PROBE_GRID_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_GRID_ALBEDO if albedo else 0) | (PROBE_GRID_COUNT_WORK if count_work else 0)
+        return _set(p, flags=flags, band_weight=band_weight, reserved=reserved)
+
+    def _probe_grid_depth_params(self, bias, min_variance, reserved):
+        """The srt_probe_grid_depth_params of the filtered visibility test: the library's defaults with what was given."""
+        return _set(self._default(ProbeGridDepthParams, self.L.srt_probe_grid_depth_params_default), bias=bias, min_variance=min_variance,
+                    reserved=reserved)
 
     def bind_probe_grid_output(self, tensor):
         """srt_bind_probe_grid_output: write the result into a torch tensor on this tracer's device, (H, W, 4) float32 and contiguous
@@ -1796,9 +1733,7 @@ class PathTracer:
 
     def probe_grid_work(self):
         """srt_get_probe_grid_work: the work counts of the last shade_probe_grid(count_work=True) as a dict.  Waits."""
-        w = ProbeGridWork()
-        self._ck(self.L.srt_get_probe_grid_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeGridWork, self.L.srt_get_probe_grid_work)
 
     # ---- probe depth moments and the filtered probe-grid shading -------------------------------
     def trace_probe_depth(self, positions=None, directions=None, resolution=None, sharpness=None, max_distance=None, normalize=False,
@@ -1811,31 +1746,15 @@ class PathTracer:
         SRT_PROBE_DEPTH_COUNT_WORK (probe_depth_work() then reads the record).  listed: srt_trace_probe_depth_listed — only the probes
         of the list bound for tracing (bind_probe_list()).  Asynchronous, like render()."""
         L = self.L
-        if positions is not None:
-            self._probe_count, self._probe_bound = self._light_probe_input("trace_probe_depth(positions)", positions, L.srt_write_light_probes,
-                                                                           L.srt_bind_light_probes, 1 << 30)
-        if directions is not None:
-            if isinstance(directions, (int, np.integer)):
-                directions = light_probe_sphere(int(directions), lib=L)
-            self._probe_dir_count, self._probe_dir_bound = self._light_probe_input("trace_probe_depth(directions)", directions,
-                                                                                   L.srt_write_light_probe_directions,
-                                                                                   L.srt_bind_light_probe_directions, LIGHT_PROBE_MAX_DIRECTIONS)
-        p = ProbeDepthParams()
-        self._ck(L.srt_probe_depth_params_default(C.byref(p)))
-        if resolution is not None:
-            p.resolution = int(resolution)
-        if sharpness is not None:
-            p.sharpness = int(sharpness)
-        if max_distance is not None:
-            p.max_distance = float(max_distance)
-        p.flags = int(flags) | (PROBE_DEPTH_NORMALIZE if normalize else 0) | (PROBE_DEPTH_COUNT_WORK if count_work else 0)
-        p.outputs = (PROBE_DEPTH_MOMENTS if moments else 0) | (PROBE_DEPTH_DISTANCES if distances else 0)
-        p.reserved = int(reserved)
-        np_, nk = getattr(self, "_probe_count", None), getattr(self, "_probe_dir_count", None)
+        self._probe_inputs("trace_probe_depth", positions, directions)
+        p = self._default(ProbeDepthParams, L.srt_probe_depth_params_default)
+        _set(p, resolution=resolution, sharpness=sharpness, max_distance=max_distance, reserved=reserved,
+             flags=int(flags) | (PROBE_DEPTH_NORMALIZE if normalize else 0) | (PROBE_DEPTH_COUNT_WORK if count_work else 0),
+             outputs=(PROBE_DEPTH_MOMENTS if moments else 0) | (PROBE_DEPTH_DISTANCES if distances else 0))
+        np_, nk = self._probe_count, self._probe_dir_count
         if np_ is not None and nk is not None:
-            bound = self.__dict__.get("_probe_depth_bound", {})
             for bit, need in ((PROBE_DEPTH_MOMENTS, np_ * int(p.resolution) ** 2 * 4), (PROBE_DEPTH_DISTANCES, np_ * nk)):
-                t = bound.get(bit)
+                t = self._probe_depth_bound.get(bit)
                 if (p.outputs & bit) and t is not None and t.numel() < need:
                     raise ValueError("trace_probe_depth: the bound tensor holds %d floats, the call writes %d" % (t.numel(), need))
         self._ck((L.srt_trace_probe_depth_listed if listed else L.srt_trace_probe_depth)(self._h, C.byref(p)))
@@ -1845,66 +1764,37 @@ class PathTracer:
         """srt_bind_probe_depth_output: write output "moments" (P*R*R float4: a tensor (M, 4)) or "distances" (P*K float: a tensor
         (M,)) into a float32 torch tensor on this tracer's device, contiguous, at least that large (checked by trace_probe_depth);
         None: the handle's own buffer.  The caller keeps the tensor alive until the traces have finished."""
-        bit = {"moments": PROBE_DEPTH_MOMENTS, "distances": PROBE_DEPTH_DISTANCES}.get(output, output)
-        if tensor is not None:
-            import torch
-
-            if not isinstance(tensor, torch.Tensor):
-                raise TypeError("bind_probe_depth_output: expected a torch.Tensor, got %s" % type(tensor).__name__)
-            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
-            if m < 1:
-                raise ValueError("bind_probe_depth_output: shape %s, want at least one element" % (tuple(tensor.shape),))
-            ptr = self._tensor_ptr("bind_probe_depth_output", tensor, np.float32, (m, 4) if bit == PROBE_DEPTH_MOMENTS else (m,))
-        else:
-            ptr = None
-        self._ck(self.L.srt_bind_probe_depth_output(self._h, int(bit), ptr))
-        bound = self.__dict__.setdefault("_probe_depth_bound", {})
-        if tensor is None:
-            bound.pop(bit, None)
-        else:
-            bound[bit] = tensor
+        bit = _bit(PROBE_DEPTH_OUTPUTS, output)
+        self._bind_sized("bind_probe_depth_output", self.L.srt_bind_probe_depth_output, (bit,), tensor, np.float32,
+                         (4,) if bit == PROBE_DEPTH_MOMENTS else (), self._probe_depth_bound, bit)
 
     def probe_depth_output(self, output="moments"):
         """srt_read_probe_depth_output: "moments": (P, R*R, 4) float32 (mean, mean square, weight, share at max_distance);
         "distances": (P, K) float32 of the last trace_probe_depth().  Waits."""
-        bit = {"moments": PROBE_DEPTH_MOMENTS, "distances": PROBE_DEPTH_DISTANCES}.get(output, output)
-        t = getattr(self, "_probe_depth_traced", None)
+        bit = _bit(PROBE_DEPTH_OUTPUTS, output)
+        t = self._probe_depth_traced
         if t is None or t[0] is None or t[1] is None:
             raise SrtError(ERR_STATE, "probe_depth_output(): no trace_probe_depth() yet")
         shape = (t[0], t[2] * t[2], 4) if bit == PROBE_DEPTH_MOMENTS else (t[0], t[1])
-        return self._read_image(self.L.srt_read_probe_depth_output, shape, np.float32, int(bit))
+        return self._read_image(self.L.srt_read_probe_depth_output, shape, np.float32, bit)
 
     def probe_depth_work(self):
         """srt_get_probe_depth_work: the work counts of the last trace_probe_depth(count_work=True) as a dict.  Waits."""
-        w = ProbeDepthWork()
-        self._ck(self.L.srt_get_probe_depth_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeDepthWork, self.L.srt_get_probe_depth_work)
 
     def bind_probe_grid_depth(self, moments, resolution=None):
         """srt_write_probe_grid_depth / srt_bind_probe_grid_depth: the depth maps shade_probe_grid_depth() reads, in
         probe_depth_output("moments")'s layout.  numpy (P, R*R, 4) or (P*R*R, 4) float32: written; a torch tensor (P*R*R, 4) on
         this tracer's device: bound, no copy (what bind_probe_depth_output("moments", t) filled); None: back to the own array.
         `resolution`: R (default: from a three-dimensional array's shape, else 16)."""
-        L = self.L
-        if moments is None:
-            self._ck(L.srt_bind_probe_grid_depth(self._h, None, 0, 0))
-            self._probe_grid_depth_bound = None
-            return
         a = moments
         if isinstance(a, np.ndarray) and a.ndim == 3:
             if resolution is None:
                 resolution = int(round(a.shape[1] ** 0.5))
             a = a.reshape(-1, 4)
-        r = 16 if resolution is None else int(resolution)
-        kind, arr, n = self._ray_array("bind_probe_grid_depth(moments)", a)
-        if r < 1 or n % (r * r):
-            raise ValueError("bind_probe_grid_depth(moments): %d float4, want %d per probe" % (n, r * r))
-        if kind == "host":
-            self._ck(L.srt_write_probe_grid_depth(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n // (r * r), r))
-            self._probe_grid_depth_bound = None
-        else:
-            self._ck(L.srt_bind_probe_grid_depth(self._h, C.c_void_p(arr.data_ptr()), n // (r * r), r))
-            self._probe_grid_depth_bound = arr  # (a bound tensor stays referenced for as long as it is bound)
+        r = 0 if a is None else 16 if resolution is None else int(resolution)
+        _, self._probe_grid_depth_bound = self._input("bind_probe_grid_depth(moments)", a, self.L.srt_write_probe_grid_depth,
+                                                      self.L.srt_bind_probe_grid_depth, r * r if r > 0 else 0, "%d" % (r * r), extra=(r,))
 
     def shade_probe_grid_depth(self, coefficients=None, moments=None, resolution=None, bias=None, min_variance=None, normal_weight=False,
                                albedo=False, band_weight=None, rows=None, count_work=False, output=None, flags=0, reserved=(0, 0),
@@ -1913,41 +1803,14 @@ class PathTracer:
         probe is weighted by Chebyshev's bound on "the probe sees at least as far as this point" from its depth map.  `moments` /
         `resolution`: as bind_probe_grid_depth() (None: the current maps); `bias` (default 0) and `min_variance` (default 1e-4): the
         test's parameters; everything else as shade_probe_grid().  probe_grid_output() and probe_grid_work() read the result."""
-        L = self.L
-        if coefficients is not None:
-            a = coefficients
-            if isinstance(a, np.ndarray) and a.ndim == 3:
-                a = a.reshape(-1, 4)
-            kind, arr, n = self._ray_array("shade_probe_grid_depth(coefficients)", a)
-            if n % LIGHT_PROBE_COEFFS:
-                raise ValueError("shade_probe_grid_depth(coefficients): %d float4, want nine per probe" % n)
-            if kind == "host":
-                self._ck(L.srt_write_probe_grid_coefficients(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n // LIGHT_PROBE_COEFFS))
-                self._probe_grid_bound = None
-            else:
-                self._ck(L.srt_bind_probe_grid_coefficients(self._h, C.c_void_p(arr.data_ptr()), n // LIGHT_PROBE_COEFFS))
-                self._probe_grid_bound = arr
+        self._probe_grid_coefficients("shade_probe_grid_depth(coefficients)", coefficients)
         if moments is not None:
             self.bind_probe_grid_depth(moments, resolution)
         if output is not None:
             self.bind_probe_grid_output(output)
-        p = ProbeGridParams()
-        self._ck(L.srt_probe_grid_params_default(C.byref(p)))
-        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
-        p.flags = (int(flags) | (PROBE_GRID_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_GRID_ALBEDO if albedo else 0) |
-                   (PROBE_GRID_COUNT_WORK if count_work else 0))
-        if band_weight is not None:
-            for b in range(3):
-                p.band_weight[b] = float(band_weight[b])
-        p.reserved[0], p.reserved[1] = int(reserved[0]), int(reserved[1])
-        d = ProbeGridDepthParams()
-        self._ck(L.srt_probe_grid_depth_params_default(C.byref(d)))
-        if bias is not None:
-            d.bias = float(bias)
-        if min_variance is not None:
-            d.min_variance = float(min_variance)
-        d.reserved[0], d.reserved[1] = int(depth_reserved[0]), int(depth_reserved[1])
-        self._ck(L.srt_shade_probe_grid_depth(self._h, C.byref(p), C.byref(d)))
+        p = self._probe_grid_params(rows, int(flags), normal_weight, albedo, count_work, band_weight, reserved)
+        d = self._probe_grid_depth_params(bias, min_variance, depth_reserved)
+        self._ck(self.L.srt_shade_probe_grid_depth(self._h, C.byref(p), C.byref(d)))
 
     # ---- probe classification and relocation, and the probe-grid shading that obeys the records ----
     def classify_probes(self, directions=None, relocate=False, clearance=None, max_offset=None, steps=None, normalize=False, count_work=False,
@@ -1960,27 +1823,15 @@ class PathTracer:
         `steps` (default 8) lengths: PROBE_MOVED.  records / positions: the outputs (probe_states_output()); count_work:
         probe_states_work() then reads the record.  Asynchronous, like render()."""
         L = self.L
-        if directions is not None:
-            if isinstance(directions, (int, np.integer)):
-                directions = light_probe_sphere(int(directions), lib=L)
-            self._probe_dir_count, self._probe_dir_bound = self._light_probe_input("classify_probes(directions)", directions,
-                                                                                   L.srt_write_light_probe_directions,
-                                                                                   L.srt_bind_light_probe_directions, LIGHT_PROBE_MAX_DIRECTIONS)
-        p = ProbeClassifyParams()
-        self._ck(L.srt_probe_classify_params_default(C.byref(p)))
-        if clearance is not None:
-            p.clearance = float(clearance)
-        if max_offset is not None:
-            p.max_offset = float(max_offset)
-        if steps is not None:
-            p.steps = int(steps)
-        p.flags = (int(flags) | (PROBE_CLASSIFY_RELOCATE if relocate else 0) | (PROBE_CLASSIFY_NORMALIZE if normalize else 0) |
-                   (PROBE_CLASSIFY_COUNT_WORK if count_work else 0))
-        p.outputs = (PROBE_STATE_RECORDS if records else 0) | (PROBE_STATE_POSITIONS if positions else 0)
-        p.reserved = int(reserved)
-        n = getattr(self, "_probe_grid_probes", None)
+        self._probe_inputs("classify_probes", None, directions)
+        p = self._default(ProbeClassifyParams, L.srt_probe_classify_params_default)
+        _set(p, clearance=clearance, max_offset=max_offset, steps=steps, reserved=reserved,
+             flags=int(flags) | (PROBE_CLASSIFY_RELOCATE if relocate else 0) | (PROBE_CLASSIFY_NORMALIZE if normalize else 0) |
+             (PROBE_CLASSIFY_COUNT_WORK if count_work else 0),
+             outputs=(PROBE_STATE_RECORDS if records else 0) | (PROBE_STATE_POSITIONS if positions else 0))
+        n = self._probe_grid_probes
         if n is not None:
-            for bit, t in self.__dict__.get("_probe_states_bound", {}).items():
+            for bit, t in self._probe_states_bound.items():
                 if (p.outputs & bit) and t.numel() < 4 * n:
                     raise ValueError("classify_probes: the bound tensor holds %d floats, the call writes %d" % (t.numel(), 4 * n))
         self._ck(L.srt_classify_probes(self._h, C.byref(p)))
@@ -1990,56 +1841,28 @@ class PathTracer:
         """srt_bind_probe_states_output: write output "records" or "positions" (P float4 each) into a float32 torch tensor (M, 4),
         M >= P, on this tracer's device, contiguous (checked by classify_probes); None: the handle's own buffer.  The caller keeps
         the tensor alive until the calls have finished."""
-        bit = {"records": PROBE_STATE_RECORDS, "positions": PROBE_STATE_POSITIONS}.get(output, output)
-        if tensor is not None:
-            import torch
-
-            if not isinstance(tensor, torch.Tensor):
-                raise TypeError("bind_probe_states_output: expected a torch.Tensor, got %s" % type(tensor).__name__)
-            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
-            if m < 1:
-                raise ValueError("bind_probe_states_output: shape %s, want at least one element" % (tuple(tensor.shape),))
-            ptr = self._tensor_ptr("bind_probe_states_output", tensor, np.float32, (m, 4))
-        else:
-            ptr = None
-        self._ck(self.L.srt_bind_probe_states_output(self._h, int(bit), ptr))
-        bound = self.__dict__.setdefault("_probe_states_bound", {})
-        if tensor is None:
-            bound.pop(bit, None)
-        else:
-            bound[bit] = tensor
+        bit = _bit(PROBE_STATE_OUTPUTS, output)
+        self._bind_sized("bind_probe_states_output", self.L.srt_bind_probe_states_output, (bit,), tensor, np.float32, (4,), self._probe_states_bound, bit)
 
     def probe_states_output(self, output="records"):
         """srt_read_probe_states_output: "records": (P, 4) float32, the offset in xyz and the state's uint32 bits in w
         (records[:, 3].view(np.uint32)); "positions": (P, 4) float32, the probes where they stand, w = 0.  Waits."""
-        bit = {"records": PROBE_STATE_RECORDS, "positions": PROBE_STATE_POSITIONS}.get(output, output)
-        n = getattr(self, "_probe_states_classified", None)
+        bit = _bit(PROBE_STATE_OUTPUTS, output)
+        n = self._probe_states_classified
         if n is None:
             raise SrtError(ERR_STATE, "probe_states_output(): no classify_probes() yet")
-        return self._read_image(self.L.srt_read_probe_states_output, (n, 4), np.float32, int(bit))
+        return self._read_image(self.L.srt_read_probe_states_output, (n, 4), np.float32, bit)
 
     def probe_states_work(self):
         """srt_get_probe_classify_work: the work counts of the last classify_probes(count_work=True) as a dict.  Waits."""
-        w = ProbeClassifyWork()
-        self._ck(self.L.srt_get_probe_classify_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeClassifyWork, self.L.srt_get_probe_classify_work)
 
     def bind_probe_grid_states(self, records):
         """srt_write_probe_grid_states / srt_bind_probe_grid_states: the records shade_probe_grid_states() obeys, in
         probe_states_output("records")'s layout.  numpy (P, 4) float32: written; a torch tensor (P, 4) on this tracer's device: bound,
         no copy (what bind_probe_states_output("records", t) filled); None: back to the own array."""
-        L = self.L
-        if records is None:
-            self._ck(L.srt_bind_probe_grid_states(self._h, None, 0))
-            self._probe_grid_states_bound = None
-            return
-        kind, arr, n = self._ray_array("bind_probe_grid_states(records)", records)
-        if kind == "host":
-            self._ck(L.srt_write_probe_grid_states(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n))
-            self._probe_grid_states_bound = None
-        else:
-            self._ck(L.srt_bind_probe_grid_states(self._h, C.c_void_p(arr.data_ptr()), n))
-            self._probe_grid_states_bound = arr  # (a bound tensor stays referenced for as long as it is bound)
+        _, self._probe_grid_states_bound = self._input("bind_probe_grid_states(records)", records, self.L.srt_write_probe_grid_states,
+                                                       self.L.srt_bind_probe_grid_states)
 
     def shade_probe_grid_states(self, coefficients=None, states=None, depth=False, moments=None, resolution=None, bias=None, min_variance=None,
                                 normal_weight=False, albedo=False, band_weight=None, rows=None, count_work=False, output=None, flags=0,
@@ -2048,20 +1871,7 @@ class PathTracer:
         given) that obeys the probe records: a PROBE_BURIED probe is skipped, every other probe stands at its grid position plus
         the record's offset.  `states`: as bind_probe_grid_states() (None: the current records); everything else as the parent
         calls.  The exact visibility test is not available.  probe_grid_output() and probe_grid_work() read the result."""
-        L = self.L
-        if coefficients is not None:
-            a = coefficients
-            if isinstance(a, np.ndarray) and a.ndim == 3:
-                a = a.reshape(-1, 4)
-            kind, arr, n = self._ray_array("shade_probe_grid_states(coefficients)", a)
-            if n % LIGHT_PROBE_COEFFS:
-                raise ValueError("shade_probe_grid_states(coefficients): %d float4, want nine per probe" % n)
-            if kind == "host":
-                self._ck(L.srt_write_probe_grid_coefficients(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n // LIGHT_PROBE_COEFFS))
-                self._probe_grid_bound = None
-            else:
-                self._ck(L.srt_bind_probe_grid_coefficients(self._h, C.c_void_p(arr.data_ptr()), n // LIGHT_PROBE_COEFFS))
-                self._probe_grid_bound = arr
+        self._probe_grid_coefficients("shade_probe_grid_states(coefficients)", coefficients)
         if states is not None:
             self.bind_probe_grid_states(states)
         if moments is not None:
@@ -2069,26 +1879,9 @@ class PathTracer:
             depth = True
         if output is not None:
             self.bind_probe_grid_output(output)
-        p = ProbeGridParams()
-        self._ck(L.srt_probe_grid_params_default(C.byref(p)))
-        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
-        p.flags = (int(flags) | (PROBE_GRID_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_GRID_ALBEDO if albedo else 0) |
-                   (PROBE_GRID_COUNT_WORK if count_work else 0))
-        if band_weight is not None:
-            for b in range(3):
-                p.band_weight[b] = float(band_weight[b])
-        p.reserved[0], p.reserved[1] = int(reserved[0]), int(reserved[1])
-        if not depth:
-            self._ck(L.srt_shade_probe_grid_states(self._h, C.byref(p), None))
-            return
-        d = ProbeGridDepthParams()
-        self._ck(L.srt_probe_grid_depth_params_default(C.byref(d)))
-        if bias is not None:
-            d.bias = float(bias)
-        if min_variance is not None:
-            d.min_variance = float(min_variance)
-        d.reserved[0], d.reserved[1] = int(depth_reserved[0]), int(depth_reserved[1])
-        self._ck(L.srt_shade_probe_grid_states(self._h, C.byref(p), C.byref(d)))
+        p = self._probe_grid_params(rows, int(flags), normal_weight, albedo, count_work, band_weight, reserved)
+        d = C.byref(self._probe_grid_depth_params(bias, min_variance, depth_reserved)) if depth else None
+        self._ck(self.L.srt_shade_probe_grid_states(self._h, C.byref(p), d))
 
     # ---- per-frame probe updates: the list of active probes, the histories and the hysteresis blend ----
     def list_probes(self, skip_mask=None, count_work=False, output=None, flags=0, reserved=(0, 0)):
@@ -2096,16 +1889,11 @@ class PathTracer:
         bits (default PROBE_BURIED | PROBE_IDLE), ascending, in SRT_PROBE_LIST's layout: 4 + P uint32 (n, P, 0, 0, the n indices,
         then 0xFFFFFFFF).  output: a torch int32 / uint32 tensor of at least 4 + P words on this tracer's device to write into
         (bound for later calls too); probe_list_output() reads the list, probe_list_work() the counts.  Asynchronous."""
-        L = self.L
         if output is not None:
             self.bind_probe_list_output(output)
-        p = ProbeListParams()
-        self._ck(L.srt_probe_list_params_default(C.byref(p)))
-        if skip_mask is not None:
-            p.skip_mask = int(skip_mask)
-        p.flags = int(flags) | (PROBE_LIST_COUNT_WORK if count_work else 0)
-        p.reserved[0], p.reserved[1] = int(reserved[0]), int(reserved[1])
-        self._ck(L.srt_list_probes(self._h, C.byref(p)))
+        p = _set(self._default(ProbeListParams, self.L.srt_probe_list_params_default), skip_mask=skip_mask,
+                 flags=int(flags) | (PROBE_LIST_COUNT_WORK if count_work else 0), reserved=reserved)
+        self._ck(self.L.srt_list_probes(self._h, C.byref(p)))
 
     def _word_tensor(self, what, tensor):
         """The device pointer and word count of a contiguous 32-bit integer torch tensor on this tracer's device."""
@@ -2134,9 +1922,7 @@ class PathTracer:
 
     def probe_list_work(self):
         """srt_get_probe_list_work: the work counts of the last list_probes(count_work=True) as a dict.  Waits."""
-        w = ProbeListWork()
-        self._ck(self.L.srt_get_probe_list_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeListWork, self.L.srt_get_probe_list_work)
 
     def bind_probe_list(self, words):
         """srt_write_probe_list / srt_bind_probe_list: the list the listed traces and a listed blend read, 4 + P words in
@@ -2160,49 +1946,27 @@ class PathTracer:
         self._ck(L.srt_write_probe_list(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.shape[0]))
         self._probe_list_bound = None
 
-    @staticmethod
-    def _history_bits(which):
-        names = {"coefficients": PROBE_HISTORY_COEFFICIENTS, "moments": PROBE_HISTORY_MOMENTS, "both": PROBE_HISTORY_COEFFICIENTS | PROBE_HISTORY_MOMENTS}
-        return int(names.get(which, which))
-
     def reset_probe_history(self, probes, resolution=0, which=None):
         """srt_reset_probe_history: give the histories of `which` ("coefficients", "moments", "both"; default: both when a
         resolution is given) their size — `probes` probes, `resolution` texels a side for the moments — and zero-fill them, so
         that every probe restarts at the next blend_probes().  Enqueued on the stream."""
-        bits = self._history_bits(which) if which is not None else (PROBE_HISTORY_COEFFICIENTS | (PROBE_HISTORY_MOMENTS if resolution else 0))
+        bits = _bit(PROBE_HISTORIES, which) if which is not None else (PROBE_HISTORY_COEFFICIENTS | (PROBE_HISTORY_MOMENTS if resolution else 0))
         self._ck(self.L.srt_reset_probe_history(self._h, bits, int(probes), int(resolution)))
-        sizes = self.__dict__.setdefault("_probe_history_sizes", {})
         for bit in (PROBE_HISTORY_COEFFICIENTS, PROBE_HISTORY_MOMENTS):
             if bits & bit:
-                sizes[bit] = (int(probes), int(resolution))
+                self._probe_history_sizes[bit] = (int(probes), int(resolution))
 
     def bind_probe_history(self, which, tensor):
         """srt_bind_probe_history: keep history "coefficients" (P*9 float4) or "moments" (P*R*R float4) in a float32 torch tensor
         (M, 4) on this tracer's device, contiguous, at least that large (the caller sees to it and keeps it alive); None: the
         handle's own buffer.  reset_probe_history() gives it its size."""
-        bit = self._history_bits(which)
-        if tensor is not None:
-            import torch
-
-            if not isinstance(tensor, torch.Tensor):
-                raise TypeError("bind_probe_history: expected a torch.Tensor, got %s" % type(tensor).__name__)
-            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
-            if m < 1:
-                raise ValueError("bind_probe_history: shape %s, want at least one element" % (tuple(tensor.shape),))
-            ptr = self._tensor_ptr("bind_probe_history", tensor, np.float32, (m, 4))
-        else:
-            ptr = None
-        self._ck(self.L.srt_bind_probe_history(self._h, bit, ptr))
-        bound = self.__dict__.setdefault("_probe_history_bound", {})
-        if tensor is None:
-            bound.pop(bit, None)
-        else:
-            bound[bit] = tensor
+        bit = _bit(PROBE_HISTORIES, which)
+        self._bind_sized("bind_probe_history", self.L.srt_bind_probe_history, (bit,), tensor, np.float32, (4,), self._probe_history_bound, bit)
 
     def probe_history(self, which="coefficients"):
         """srt_read_probe_history: "coefficients": (P, 9, 4) float32; "moments": (P, R*R, 4) float32.  Waits."""
-        bit = self._history_bits(which)
-        size = self.__dict__.get("_probe_history_sizes", {}).get(bit)
+        bit = _bit(PROBE_HISTORIES, which)
+        size = self._probe_history_sizes.get(bit)
         if size is None:
             raise SrtError(ERR_STATE, "probe_history(): no reset_probe_history() for that history yet")
         shape = (size[0], LIGHT_PROBE_COEFFS, 4) if bit == PROBE_HISTORY_COEFFICIENTS else (size[0], size[1] * size[1], 4)
@@ -2211,18 +1975,8 @@ class PathTracer:
     def bind_probe_previous_states(self, records):
         """srt_write_probe_previous_states / srt_bind_probe_previous_states: the records blend_probes(previous_states=True)
         compares the current ones with; as bind_probe_grid_states() takes them."""
-        L = self.L
-        if records is None:
-            self._ck(L.srt_bind_probe_previous_states(self._h, None, 0))
-            self._probe_previous_bound = None
-            return
-        kind, arr, n = self._ray_array("bind_probe_previous_states(records)", records)
-        if kind == "host":
-            self._ck(L.srt_write_probe_previous_states(self._h, arr.ctypes.data_as(C.POINTER(C.c_float)), n))
-            self._probe_previous_bound = None
-        else:
-            self._ck(L.srt_bind_probe_previous_states(self._h, C.c_void_p(arr.data_ptr()), n))
-            self._probe_previous_bound = arr
+        _, self._probe_previous_bound = self._input("bind_probe_previous_states(records)", records, self.L.srt_write_probe_previous_states,
+                                                    self.L.srt_bind_probe_previous_states)
 
     def blend_probes(self, hysteresis=None, fast_hysteresis=None, depth_hysteresis=None, change_threshold=None, moments=False, listed=False,
                      previous_states=False, count_work=False, flags=0, reserved=0):
@@ -2232,38 +1986,15 @@ class PathTracer:
         `depth_hysteresis` (0.9) for the moments.  A probe whose history is empty restarts (H = N), and with previous_states=True
         one whose record differs from bind_probe_previous_states()'s in its offset or its BURIED / IDLE bits.  listed: only the
         probes of bind_probe_list().  probe_history() reads the result; probe_blend_work() the counts.  Asynchronous."""
-        L = self.L
-        p = ProbeBlendParams()
-        self._ck(L.srt_probe_blend_params_default(C.byref(p)))
-        if hysteresis is not None:
-            p.hysteresis = float(hysteresis)
-        if fast_hysteresis is not None:
-            p.fast_hysteresis = float(fast_hysteresis)
-        if depth_hysteresis is not None:
-            p.depth_hysteresis = float(depth_hysteresis)
-        if change_threshold is not None:
-            p.change_threshold = float(change_threshold)
-        p.flags = (int(flags) | (PROBE_BLEND_MOMENTS if moments else 0) | (PROBE_BLEND_LISTED if listed else 0) |
-                   (PROBE_BLEND_PREVIOUS_STATES if previous_states else 0) | (PROBE_BLEND_COUNT_WORK if count_work else 0))
-        p.reserved = int(reserved)
-        self._ck(L.srt_blend_probes(self._h, C.byref(p)))
+        p = self._default(ProbeBlendParams, self.L.srt_probe_blend_params_default)
+        _set(p, hysteresis=hysteresis, fast_hysteresis=fast_hysteresis, depth_hysteresis=depth_hysteresis, change_threshold=change_threshold,
+             reserved=reserved, flags=int(flags) | (PROBE_BLEND_MOMENTS if moments else 0) | (PROBE_BLEND_LISTED if listed else 0) |
+             (PROBE_BLEND_PREVIOUS_STATES if previous_states else 0) | (PROBE_BLEND_COUNT_WORK if count_work else 0))
+        self._ck(self.L.srt_blend_probes(self._h, C.byref(p)))
 
     def probe_blend_work(self):
         """srt_get_probe_blend_work: the work counts of the last blend_probes(count_work=True) as a dict.  Waits."""
-        w = ProbeBlendWork()
-        self._ck(self.L.srt_get_probe_blend_work(self._h, C.byref(w)))
-        return w.as_dict()
-
-    @staticmethod
-    def _scroll_bits(which):
-        if isinstance(which, (int, np.integer)):
-            return int(which)
-        names = {"coefficients": PROBE_SCROLL_COEFFICIENTS, "moments": PROBE_SCROLL_MOMENTS, "states": PROBE_SCROLL_STATES,
-                 "both": PROBE_SCROLL_COEFFICIENTS | PROBE_SCROLL_MOMENTS, "all": PROBE_SCROLL_COEFFICIENTS | PROBE_SCROLL_MOMENTS | PROBE_SCROLL_STATES}
-        bits = 0
-        for name in ([which] if isinstance(which, str) else which):
-            bits |= names[name]
-        return bits
+        return self._get_work(ProbeBlendWork, self.L.srt_get_probe_blend_work)
 
     def scroll_probes(self, shift, which="coefficients", set_grid=False, count_work=False, flags=0, reserved=(0, 0, 0)):
         """srt_scroll_probes: move the grid of set_probe_grid() by `shift` = (sx, sy, sz) cells and keep what stays inside: new probe
@@ -2273,12 +2004,9 @@ class PathTracer:
         handle's grid origin by shift * spacing; otherwise call set_probe_grid().  A non-zero shift makes the last traces stale:
         blend_probes() refuses until trace_light_probes() (and trace_probe_depth()) ran again.  count_work: probe_scroll_work()
         then reads the record.  Asynchronous."""
-        p = ProbeScrollParams()
-        self._ck(self.L.srt_probe_scroll_params_default(C.byref(p)))
-        for a in range(3):
-            p.shift[a], p.reserved[a] = int(shift[a]), int(reserved[a])
-        p.which = self._scroll_bits(which)
-        p.flags = int(flags) | (PROBE_SCROLL_SET_GRID if set_grid else 0) | (PROBE_SCROLL_COUNT_WORK if count_work else 0)
+        p = self._default(ProbeScrollParams, self.L.srt_probe_scroll_params_default)
+        _set(p, shift=shift, reserved=reserved, which=_mask(PROBE_SCROLL_ARRAYS, which),
+             flags=int(flags) | (PROBE_SCROLL_SET_GRID if set_grid else 0) | (PROBE_SCROLL_COUNT_WORK if count_work else 0))
         self._ck(self.L.srt_scroll_probes(self._h, C.byref(p)))
         if p.which & PROBE_SCROLL_STATES:
             self._probe_previous_bound = None  # (the handle's own previous records are current again)
@@ -2292,9 +2020,7 @@ class PathTracer:
 
     def probe_scroll_work(self):
         """srt_get_probe_scroll_work: the work counts of the last scroll_probes(count_work=True) as a dict.  Waits."""
-        w = ProbeScrollWork()
-        self._ck(self.L.srt_get_probe_scroll_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeScrollWork, self.L.srt_get_probe_scroll_work)
 
     get_probe_scroll_work = probe_scroll_work
 
@@ -2304,17 +2030,6 @@ class PathTracer:
         return self._read_image(self.L.srt_read_probe_previous_states, (int(probes), 4), np.float32)
 
     # ---- probe cascades: nested grids, the finest level that holds a pixel blended into the next at its border ----
-    @staticmethod
-    def _cascade_bits(which):
-        if isinstance(which, (int, np.integer)):
-            return int(which)
-        names = {"coefficients": PROBE_CASCADE_COEFFICIENTS, "moments": PROBE_CASCADE_MOMENTS, "records": PROBE_CASCADE_RECORDS,
-                 "all": PROBE_CASCADE_COEFFICIENTS | PROBE_CASCADE_MOMENTS | PROBE_CASCADE_RECORDS}
-        bits = 0
-        for name in ([which] if isinstance(which, str) else which):
-            bits |= names[name]
-        return bits
-
     def set_probe_cascade(self, grids, resolution=0, blend_cells=1.0):
         """srt_set_probe_cascade: the cascade shade_probe_cascade() reads: a ProbeCascade (probe_cascade_grids()), or 1 .. 4 grids,
         finest first, with the resolution R of every level's moments (0: none) and the band width in cells.  A level whose probe
@@ -2326,40 +2041,35 @@ class PathTracer:
     def write_probe_cascade_level(self, level, which, array):
         """srt_write_probe_cascade_level: copy a level's "coefficients" (P, 9, 4), "moments" (P, R*R, 4) or "records" (P, 4), numpy
         float32, into the handle's own array of that level.  Waits."""
-        bit = self._cascade_bits(which)
+        bit = _mask(PROBE_CASCADE_ARRAYS, which)
         a = np.ascontiguousarray(array, dtype=np.float32)
         probes = int(a.shape[0]) if a.ndim >= 1 else 0
         self._ck(self.L.srt_write_probe_cascade_level(self._h, int(level), bit, a.ctypes.data_as(C.POINTER(C.c_float)), probes))
-        self.__dict__.setdefault("_probe_cascade_bound", {}).pop((int(level), bit), None)
+        self._probe_cascade_bound.pop((int(level), bit), None)
 
     def bind_probe_cascade_level(self, level, which, tensor, probes=None):
         """srt_bind_probe_cascade_level: read a level's "coefficients", "moments" or "records" from a float32 torch tensor on this
         tracer's device, contiguous, (P, 9, 4) / (P, R*R, 4) / (P, 4) (or flat with `probes` given); no copy, the caller keeps it
         alive.  None: back to the own array."""
-        bit = self._cascade_bits(which)
-        bound = self.__dict__.setdefault("_probe_cascade_bound", {})
+        bit = _mask(PROBE_CASCADE_ARRAYS, which)
         if tensor is None:
             self._ck(self.L.srt_bind_probe_cascade_level(self._h, int(level), bit, None, 0))
-            bound.pop((int(level), bit), None)
+            self._probe_cascade_bound.pop((int(level), bit), None)
             return
-        import torch
-
-        if not isinstance(tensor, torch.Tensor):
-            raise TypeError("bind_probe_cascade_level: expected a torch.Tensor, got %s" % type(tensor).__name__)
+        # (the tensor's own shape is the wanted one: any shape goes, with `probes` or its first dimension as the count)
+        ptr = self._tensor_ptr("bind_probe_cascade_level", tensor, np.float32, getattr(tensor, "shape", ()))
         n = int(probes) if probes is not None else (int(tensor.shape[0]) if tensor.dim() >= 1 else 0)
-        ptr = self._tensor_ptr("bind_probe_cascade_level", tensor, np.float32, tuple(tensor.shape))
         self._ck(self.L.srt_bind_probe_cascade_level(self._h, int(level), bit, ptr, n))
-        bound[(int(level), bit)] = tensor
+        self._probe_cascade_bound[(int(level), bit)] = tensor
 
     def capture_probe_cascade_level(self, level, which="all"):
         """srt_capture_probe_cascade_level: copy, on the device, what the single-grid calls would read now (the current probe-grid
         coefficients, depth moments, state records, as `which` selects) into the level's own arrays.  Asynchronous."""
-        bits = self._cascade_bits(which)
+        bits = _mask(PROBE_CASCADE_ARRAYS, which)
         self._ck(self.L.srt_capture_probe_cascade_level(self._h, int(level), bits))
-        bound = self.__dict__.setdefault("_probe_cascade_bound", {})
         for b in (PROBE_CASCADE_COEFFICIENTS, PROBE_CASCADE_MOMENTS, PROBE_CASCADE_RECORDS):
             if bits & b:
-                bound.pop((int(level), b), None)
+                self._probe_cascade_bound.pop((int(level), b), None)
 
     def shade_probe_cascade(self, depth=False, states=False, normal_weight=False, albedo=False, band_weight=None, bias=None, min_variance=None,
                             rows=None, count_work=False, output=None, flags=0, reserved=(0, 0)):
@@ -2367,35 +2077,24 @@ class PathTracer:
         blended into the next coarser level across the border band.  depth / states: rule 7b from each level's moments, rules
         3s / 4s from each level's records; the other arguments as shade_probe_grid_states().  probe_grid_output() reads the result,
         probe_cascade_work() the counts.  Asynchronous."""
-        L = self.L
         if output is not None:
             self.bind_probe_grid_output(output)
-        p = ProbeCascadeParams()
-        self._ck(L.srt_probe_cascade_params_default(C.byref(p)))
-        p.row_begin, p.row_end = (int(rows[0]), int(rows[1])) if rows is not None else (0, self.height)
-        p.flags = (int(flags) | (PROBE_CASCADE_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_CASCADE_DEPTH if depth else 0) |
-                   (PROBE_CASCADE_STATES if states else 0) | (PROBE_CASCADE_ALBEDO if albedo else 0) | (PROBE_CASCADE_COUNT_WORK if count_work else 0))
-        if band_weight is not None:
-            for b in range(3):
-                p.band_weight[b] = float(band_weight[b])
-        if bias is not None:
-            p.bias = float(bias)
-        if min_variance is not None:
-            p.min_variance = float(min_variance)
-        p.reserved[0], p.reserved[1] = int(reserved[0]), int(reserved[1])
-        self._ck(L.srt_shade_probe_cascade(self._h, C.byref(p)))
+        p = self._default(ProbeCascadeParams, self.L.srt_probe_cascade_params_default)
+        p.row_begin, p.row_end = self._band(rows)
+        flags = (int(flags) | (PROBE_CASCADE_NORMAL_WEIGHT if normal_weight else 0) | (PROBE_CASCADE_DEPTH if depth else 0) |
+                 (PROBE_CASCADE_STATES if states else 0) | (PROBE_CASCADE_ALBEDO if albedo else 0) | (PROBE_CASCADE_COUNT_WORK if count_work else 0))
+        _set(p, flags=flags, band_weight=band_weight, bias=bias, min_variance=min_variance, reserved=reserved)
+        self._ck(self.L.srt_shade_probe_cascade(self._h, C.byref(p)))
 
     def probe_cascade_work(self):
         """srt_get_probe_cascade_work: the work counts of the last shade_probe_cascade(count_work=True) as a dict.  Waits."""
-        w = ProbeCascadeWork()
-        self._ck(self.L.srt_get_probe_cascade_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeCascadeWork, self.L.srt_get_probe_cascade_work)
 
     def ray_output(self, name, count=None):
         """srt_read_ray_output: one output of the last trace_rays() as a numpy array: "object" and "occluded" (N,) int32, the
         others (N, 4) float32.  `count`: N, for rays bound by raw pointer on another PathTracer object (default: this one's)."""
-        bit, dtype, ch = _ray_output_spec(name)
-        n = count if count is not None else getattr(self, "_ray_traced", None)
+        bit, dtype, ch = _spec(RAY_OUTPUTS, name, "ray output")
+        n = count if count is not None else self._ray_traced
         if n is None:
             raise SrtError(ERR_STATE, "ray_output(%r): no trace_rays() yet" % name)
         return self._read_image(self.L.srt_read_ray_output, (n,) if ch == 1 else (n, ch), dtype, bit)
@@ -2404,25 +2103,9 @@ class PathTracer:
         """srt_bind_ray_output: write output `name` into a torch tensor on this tracer's device (None: the handle's own buffer):
         (M,) int32 for "object" / "occluded", (M, 4) float32 for the others, contiguous, M at least the batch size (checked by
         trace_rays).  Checked here, before any native call; the caller keeps the tensor alive until the traces have finished."""
-        bit, dtype, ch = _ray_output_spec(name)
-        if tensor is not None:
-            import torch
-
-            if not isinstance(tensor, torch.Tensor):
-                raise TypeError("bind_ray_output(%r): expected a torch.Tensor, got %s" % (name, type(tensor).__name__))
-            m = int(tensor.shape[0]) if tensor.dim() >= 1 else 0
-            if m < 1:
-                raise ValueError("bind_ray_output(%r): shape %s, want at least one element" % (name, tuple(tensor.shape)))
-            shape = (m,) if ch == 1 else (m, ch)
-            ptr = self._tensor_ptr("bind_ray_output(%r)" % name, tensor, dtype, shape)
-        else:
-            ptr = None
-        self._ck(self.L.srt_bind_ray_output(self._h, bit, ptr))
-        bound = self.__dict__.setdefault("_ray_out_bound", {})
-        if tensor is None:
-            bound.pop(name, None)
-        else:
-            bound[name] = tensor
+        bit, dtype, ch = _spec(RAY_OUTPUTS, name, "ray output")
+        self._bind_sized("bind_ray_output(%r)" % name, self.L.srt_bind_ray_output, (bit,), tensor, dtype, () if ch == 1 else (ch,),
+                         self._ray_out_bound, name)
 
     def _tensor_ptr(self, what, tensor, dtype, shape):
         """The device pointer of a tensor an output is bound to: on this tracer's device, of numpy dtype `dtype` (int32 or
@@ -2476,8 +2159,8 @@ class PathTracer:
         are.  Asynchronous.  The next render() must reset."""
         p = temporal_params(samples, max_samples, plane_tolerance, normal_threshold, reset, framebuffer, lib=self.L)
         if gbuffer:
-            self._render_guides(TEMPORAL_GUIDES | (GBUF_ALBEDO if getattr(self, "_moments_albedo", False) else 0), "temporal", True)
-            if getattr(self, "_mirror_history", False):
+            self._render_guides(TEMPORAL_GUIDES | (GBUF_ALBEDO if self._moments_albedo else 0), "temporal", True)
+            if self._mirror_history:
                 self.render_reflection_gbuffer(outputs=MIRROR_HISTORY_GUIDES)
         self._ck(self.L.srt_temporal_accumulate(self._h, C.byref(p)))
 
@@ -2522,7 +2205,7 @@ class PathTracer:
     def render_subsamples(self, k=None, rows=None, flags=0):
         """srt_render_subsamples: the hit object of the k x k sub-pixel rays of every pixel of memory rows `rows` (default: the
         whole frame); k None takes ANTIALIAS_DEFAULTS.  Asynchronous, like render_gbuffer()."""
-        rb, re = rows if rows is not None else (0, self.height)
+        rb, re = self._band(rows)
         p = SubsampleParams(int(rb), int(re), int(antialias_defaults(self.L)["k"] if k is None else k), int(flags))
         self._ck(self.L.srt_render_subsamples(self._h, C.byref(p)))
         self._subsample_k = p.k
@@ -2530,7 +2213,7 @@ class PathTracer:
     def subsamples(self, k=None):
         """srt_read_subsamples: (k*k, H, W) int32, rows = scene rows; k is that of the last render_subsamples of this tracer
         unless given (a buffer filled by other means)."""
-        k = int(getattr(self, "_subsample_k", 0) if k is None else k)
+        k = int(self._subsample_k if k is None else k)
         return self._read_image(self.L.srt_read_subsamples, (max(k, 1) ** 2, self.height, self.width), np.int32)
 
     def bind_subsamples(self, tensor, k=None):
@@ -2650,9 +2333,7 @@ class PathTracer:
 
     def work_counts(self):
         """srt_get_work_counts: the loop counts of the last render (it must have had count_work=True)."""
-        w = WorkCounts()
-        self._ck(self.L.srt_get_work_counts(self._h, C.byref(w)))
-        return w
+        return self._get_record(WorkCounts, self.L.srt_get_work_counts)
 
     # ---- buffers ---------------------------------------------------------------------
     def framebuffer(self, rows=None):
@@ -2664,7 +2345,7 @@ class PathTracer:
     def read_framebuffer_async(self, dst_ptr, rows=None, copy_stream=0):
         """srt_read_framebuffer_async: memory rows `rows` into host memory at dst_ptr (pinned, tightly packed), enqueued on
         hipStream_t `copy_stream` (0: the launch stream) behind the renders enqueued so far; returns at once."""
-        rb, re = rows if rows is not None else (0, self.height)
+        rb, re = self._band(rows)
         self._ck(self.L.srt_read_framebuffer_async(self._h, C.c_void_p(dst_ptr), self.width * 4, rb, re, C.c_void_p(copy_stream or 0)))
 
     def accumulator(self):

@@ -20,7 +20,7 @@ from .capi import (PROBE_CLASSIFY_COUNT_WORK, PROBE_CLASSIFY_NORMALIZE, PROBE_CL
 from .capi import (PROBE_BLEND_COUNT_WORK, PROBE_BLEND_LISTED, PROBE_BLEND_MOMENTS, PROBE_BLEND_PREVIOUS_STATES, PROBE_BURIED, PROBE_HISTORY_COEFFICIENTS,
                    PROBE_HISTORY_MOMENTS, PROBE_IDLE, PROBE_LIST_COUNT_WORK, PROBE_LIST_HEADER, ProbeBlendParams, ProbeBlendWork, ProbeListParams,
                    ProbeListWork)  # noqa: F401
-from .capi import PROBE_SCROLL_COUNT_WORK, PROBE_SCROLL_SET_GRID, PathTracer as _PathTracer, ProbeScrollWork  # noqa: F401
+from .capi import PROBE_CASCADE_ARRAYS, PROBE_SCROLL_ARRAYS, PROBE_SCROLL_COUNT_WORK, PROBE_SCROLL_SET_GRID, ProbeScrollWork, WorkRecord, _mask  # noqa: F401
 from .capi import (PROBE_CASCADE_ALBEDO, PROBE_CASCADE_COUNT_WORK, PROBE_CASCADE_DEPTH, PROBE_CASCADE_NORMAL_WEIGHT, PROBE_CASCADE_STATES, ProbeCascade,  # noqa: F401
                    ProbeCascadeParams, ProbeCascadeWork, probe_cascade)
 from .capi import PROBE_TAIL_COUNT_WORK, PROBE_TAIL_DEPTH, PROBE_TAIL_NORMAL_WEIGHT, PROBE_TAIL_STATES, ProbeTailParams, ProbeTailWork  # noqa: F401
@@ -356,6 +356,27 @@ class Renderer:
         if rc != 0:
             raise RuntimeError("host renderer error %d: %s" % (rc, self.L.srt_host_last_error().decode()))
 
+    def _get_work(self, struct, fn):
+        """The record a counting call left (a capi.WorkRecord), as a dict."""
+        record = struct()
+        self._ck(fn(self._h, C.byref(record)))
+        return record.as_dict()
+
+    def _read(self, fn, shape, dtype, *args):
+        """One srt_host_renderer_read_*: a new array of `shape` filled by fn(handle, *args, pointer to the array's data)."""
+        out = np.empty(shape, dtype=dtype)
+        self._ck(fn(self._h, *args, out.ctypes.data_as(fn.argtypes[-1])))
+        return out
+
+    @staticmethod
+    def _ray_pair(what, origins, directions):
+        """The origins and directions of a ray batch as two contiguous (N, 4) float32 arrays of one N >= 1."""
+        o = np.ascontiguousarray(origins, dtype=np.float32)
+        d = np.ascontiguousarray(directions, dtype=np.float32)
+        if o.ndim != 2 or o.shape[1] != 4 or o.shape != d.shape or o.shape[0] < 1:
+            raise ValueError("%s: origins %s and directions %s, want two (N, 4) arrays" % (what, o.shape, d.shape))
+        return o, d
+
     def close(self):
         if self._h:
             self.L.srt_host_renderer_destroy(self._h)
@@ -431,18 +452,13 @@ class Renderer:
     def gbuffer(self, name):
         """PathTraceRenderer::ReadGBuffer: one output, scene rows, as capi.PathTracer.gbuffer returns it."""
         bit, dtype, ch = GBUFFERS[name]
-        out = np.empty((self.height, self.width) if ch == 1 else (self.height, self.width, ch), dtype=dtype)
-        self._ck(self.L.srt_host_renderer_read_gbuffer(self._h, bit, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._read(self.L.srt_host_renderer_read_gbuffer, (self.height, self.width) if ch == 1 else (self.height, self.width, ch), dtype, bit)
 
     def trace_rays(self, origins, directions, outputs=RAYS_ALL, normalize=False):
         """PathTraceRenderer::traceRays: copy N rays from host arrays (N, 4) float32 — origin (x, y, z, ignored), direction
         (x, y, z, t_max) — and enqueue their closest-hit query against the renderer's scene (outputs: a mask or names of
         capi.RAY_OUTPUTS; normalize: SRT_RAYS_NORMALIZE)."""
-        o = np.ascontiguousarray(origins, dtype=np.float32)
-        d = np.ascontiguousarray(directions, dtype=np.float32)
-        if o.ndim != 2 or o.shape[1] != 4 or o.shape != d.shape or o.shape[0] < 1:
-            raise ValueError("trace_rays: origins %s and directions %s, want two (N, 4) arrays" % (o.shape, d.shape))
+        o, d = self._ray_pair("trace_rays", origins, directions)
         f = C.POINTER(C.c_float)
         self._ck(self.L.srt_host_renderer_trace_rays(self._h, o.ctypes.data_as(f), d.ctypes.data_as(f), o.shape[0], ray_outputs(outputs),
                                                      RAYS_NORMALIZE if normalize else 0))
@@ -451,10 +467,7 @@ class Renderer:
     def trace_occlusion(self, origins, directions, normalize=False, count_work=False):
         """PathTraceRenderer::traceOcclusion: copy N rays from host arrays (N, 4) float32 and enqueue their any-hit query (is
         there a valid hit with distance < t_max, the directions' w?); ray_output("occluded") reads the result."""
-        o = np.ascontiguousarray(origins, dtype=np.float32)
-        d = np.ascontiguousarray(directions, dtype=np.float32)
-        if o.ndim != 2 or o.shape[1] != 4 or o.shape != d.shape or o.shape[0] < 1:
-            raise ValueError("trace_occlusion: origins %s and directions %s, want two (N, 4) arrays" % (o.shape, d.shape))
+        o, d = self._ray_pair("trace_occlusion", origins, directions)
         f = C.POINTER(C.c_float)
         self._ck(self.L.srt_host_renderer_trace_occlusion(self._h, o.ctypes.data_as(f), d.ctypes.data_as(f), o.shape[0],
                                                           (OCCLUSION_NORMALIZE if normalize else 0) | (OCCLUSION_COUNT_WORK if count_work else 0)))
@@ -462,9 +475,7 @@ class Renderer:
 
     def occlusion_work(self):
         """PathTraceRenderer::occlusionWork: the work counts of the last trace_occlusion(count_work=True) as a dict."""
-        w = OcclusionWork()
-        self._ck(self.L.srt_host_renderer_occlusion_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(OcclusionWork, self.L.srt_host_renderer_occlusion_work)
 
     def trace_radiance(self, origins, directions, samples=16, bounces=8, seed=0, first_sample=1, reset=True, id_base=0, normalize=False,
                        count_work=False):
@@ -472,17 +483,12 @@ class Renderer:
         samples of `bounces` bounces along each against the renderer's scene (srt_trace_radiance: ray i draws from the stream of
         pixel id_base + i, samples first_sample .. first_sample + samples - 1; reset=False continues the running mean the handle's
         buffer holds) and return the (N, 4) float32 running means.  Waits."""
-        o = np.ascontiguousarray(origins, dtype=np.float32)
-        d = np.ascontiguousarray(directions, dtype=np.float32)
-        if o.ndim != 2 or o.shape[1] != 4 or o.shape != d.shape or o.shape[0] < 1:
-            raise ValueError("trace_radiance: origins %s and directions %s, want two (N, 4) arrays" % (o.shape, d.shape))
+        o, d = self._ray_pair("trace_radiance", origins, directions)
         p = RadianceParams(int(first_sample), int(samples), int(bounces), int(seed) & 0xFFFFFFFF, int(id_base) & 0xFFFFFFFF,
                            (RADIANCE_RESET if reset else 0) | (RADIANCE_NORMALIZE if normalize else 0) | (RADIANCE_COUNT_WORK if count_work else 0))
         f = C.POINTER(C.c_float)
         self._ck(self.L.srt_host_renderer_trace_radiance(self._h, o.ctypes.data_as(f), d.ctypes.data_as(f), o.shape[0], C.byref(p)))
-        out = np.empty((o.shape[0], 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_radiance(self._h, out.ctypes.data_as(f)))
-        return out
+        return self._read(self.L.srt_host_renderer_read_radiance, (o.shape[0], 4), np.float32)
 
     def trace_light_probes(self, positions, directions, samples=16, bounces=8, seed=0, first_sample=1, reset=True, id_base=0, normalize=False,
                            count_work=False, radiance=False):
@@ -502,27 +508,19 @@ class Renderer:
         f = C.POINTER(C.c_float)
         self._ck(self.L.srt_host_renderer_trace_light_probes(self._h, o.ctypes.data_as(f), o.shape[0], d.ctypes.data_as(f), d.shape[0], C.byref(p)))
         self._probes_traced = (o.shape[0], d.shape[0])
-        out = np.empty((o.shape[0], LIGHT_PROBE_COEFFS, 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_light_probe_output(self._h, LIGHT_PROBE_COEFFICIENTS, out.ctypes.data_as(f)))
-        return out
+        return self._read(self.L.srt_host_renderer_read_light_probe_output, (o.shape[0], LIGHT_PROBE_COEFFS, 4), np.float32, LIGHT_PROBE_COEFFICIENTS)
 
     def light_probe_coefficients(self):
         """PathTraceRenderer::readLightProbeOutput(COEFFICIENTS): the (P, 9, 4) float32 coefficients of the last trace_light_probes()."""
-        out = np.empty((self._probes_traced[0], LIGHT_PROBE_COEFFS, 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_light_probe_output(self._h, LIGHT_PROBE_COEFFICIENTS, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_light_probe_output, (self._probes_traced[0], LIGHT_PROBE_COEFFS, 4), np.float32, LIGHT_PROBE_COEFFICIENTS)
 
     def light_probe_radiance(self):
         """PathTraceRenderer::readLightProbeOutput(RADIANCE): the (P, K, 4) float32 means of the last trace_light_probes(radiance=True)."""
-        out = np.empty(self._probes_traced + (4,), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_light_probe_output(self._h, LIGHT_PROBE_RADIANCE, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_light_probe_output, self._probes_traced + (4,), np.float32, LIGHT_PROBE_RADIANCE)
 
     def light_probe_work(self):
         """PathTraceRenderer::lightProbeWork: the work counts of the last trace_light_probes(count_work=True) as a dict."""
-        w = LightProbeWork()
-        self._ck(self.L.srt_host_renderer_light_probe_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(LightProbeWork, self.L.srt_host_renderer_light_probe_work)
 
     def set_probe_grid(self, origin, spacing=None, counts=None):
         """PathTraceRenderer::setProbeGrid: the grid shade_probe_grid() interpolates on (a capi.ProbeGrid, or three triples)."""
@@ -551,15 +549,11 @@ class Renderer:
 
     def probe_grid_output(self):
         """PathTraceRenderer::readProbeGridOutput: the (H, W, 4) float32 result of the last shade_probe_grid(), rows = scene rows."""
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_probe_grid_output(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_probe_grid_output, (self.height, self.width, 4), np.float32)
 
     def probe_grid_work(self):
         """PathTraceRenderer::probeGridWork: the work counts of the last shade_probe_grid(count_work=True) as a dict."""
-        w = ProbeGridWork()
-        self._ck(self.L.srt_host_renderer_probe_grid_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeGridWork, self.L.srt_host_renderer_probe_grid_work)
 
     def trace_probe_depth(self, positions, directions, resolution=16, sharpness=5, max_distance=10000.0, normalize=False, count_work=False,
                           distances=False):
@@ -578,21 +572,15 @@ class Renderer:
         f = C.POINTER(C.c_float)
         self._ck(self.L.srt_host_renderer_trace_probe_depth(self._h, o.ctypes.data_as(f), o.shape[0], d.ctypes.data_as(f), d.shape[0], C.byref(p)))
         self._probe_depth_traced = (o.shape[0], d.shape[0], int(resolution))
-        out = np.empty((o.shape[0], int(resolution) ** 2, 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_probe_depth_output(self._h, PROBE_DEPTH_MOMENTS, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._read(self.L.srt_host_renderer_read_probe_depth_output, (o.shape[0], int(resolution) ** 2, 4), np.float32, PROBE_DEPTH_MOMENTS)
 
     def probe_depth_distances(self):
         """PathTraceRenderer::readProbeDepthOutput(DISTANCES): the (P, K) float32 distances of the last trace_probe_depth(distances=True)."""
-        out = np.empty(self._probe_depth_traced[:2], dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_probe_depth_output(self._h, PROBE_DEPTH_DISTANCES, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._read(self.L.srt_host_renderer_read_probe_depth_output, self._probe_depth_traced[:2], np.float32, PROBE_DEPTH_DISTANCES)
 
     def probe_depth_work(self):
         """PathTraceRenderer::probeDepthWork: the work counts of the last trace_probe_depth(count_work=True) as a dict."""
-        w = ProbeDepthWork()
-        self._ck(self.L.srt_host_renderer_probe_depth_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeDepthWork, self.L.srt_host_renderer_probe_depth_work)
 
     def shade_probe_grid_depth(self, coefficients=None, moments=None, bias=0.0, min_variance=1e-4, normal_weight=False, albedo=False, band_weight=None,
                                rows=None, count_work=False):
@@ -639,19 +627,14 @@ class Renderer:
                                 (PROBE_CLASSIFY_RELOCATE if relocate else 0) | (PROBE_CLASSIFY_NORMALIZE if normalize else 0) |
                                 (PROBE_CLASSIFY_COUNT_WORK if count_work else 0), PROBE_STATE_RECORDS | (PROBE_STATE_POSITIONS if positions else 0), 0)
         self._ck(self.L.srt_host_renderer_classify_probes(self._h, dptr, k, C.byref(p)))
-        rec = np.empty((int(probes), 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_probe_states_output(self._h, PROBE_STATE_RECORDS, rec.ctypes.data_as(C.c_void_p)))
+        rec = self._read(self.L.srt_host_renderer_read_probe_states_output, (int(probes), 4), np.float32, PROBE_STATE_RECORDS)
         if not positions:
             return rec
-        pos = np.empty((int(probes), 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_probe_states_output(self._h, PROBE_STATE_POSITIONS, pos.ctypes.data_as(C.c_void_p)))
-        return rec, pos
+        return rec, self._read(self.L.srt_host_renderer_read_probe_states_output, (int(probes), 4), np.float32, PROBE_STATE_POSITIONS)
 
     def probe_states_work(self):
         """PathTraceRenderer::probeClassifyWork: the work counts of the last classify_probes(count_work=True) as a dict."""
-        w = ProbeClassifyWork()
-        self._ck(self.L.srt_host_renderer_probe_classify_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeClassifyWork, self.L.srt_host_renderer_probe_classify_work)
 
     def shade_probe_grid_states(self, coefficients=None, states=None, moments=None, depth=False, bias=0.0, min_variance=1e-4, normal_weight=False,
                                 albedo=False, band_weight=None, rows=None, count_work=False):
@@ -699,15 +682,11 @@ class Renderer:
             raise ValueError("list_probes: give the states or their count")
         p = ProbeListParams(int(skip_mask), PROBE_LIST_COUNT_WORK if count_work else 0, (C.c_uint32 * 2)(0, 0))
         self._ck(self.L.srt_host_renderer_list_probes(self._h, sptr, n, C.byref(p)))
-        out = np.empty(PROBE_LIST_HEADER + n, dtype=np.uint32)
-        self._ck(self.L.srt_host_renderer_read_probe_list_output(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_probe_list_output, PROBE_LIST_HEADER + n, np.uint32)
 
     def probe_list_work(self):
         """PathTraceRenderer::probeListWork: the work counts of the last list_probes(count_work=True) as a dict."""
-        w = ProbeListWork()
-        self._ck(self.L.srt_host_renderer_probe_list_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeListWork, self.L.srt_host_renderer_probe_list_work)
 
     def _probe_inputs(self, what, positions, directions):
         f = C.POINTER(C.c_float)
@@ -780,22 +759,18 @@ class Renderer:
         """PathTraceRenderer::readProbeHistory: "coefficients": (P, 9, 4) float32; "moments": (P, R*R, 4) float32.  Waits."""
         n, r = self._probe_history
         bit, shape = (PROBE_HISTORY_COEFFICIENTS, (n, LIGHT_PROBE_COEFFS, 4)) if which == "coefficients" else (PROBE_HISTORY_MOMENTS, (n, r * r, 4))
-        out = np.empty(shape, dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_probe_history(self._h, bit, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_probe_history, shape, np.float32, bit)
 
     def probe_blend_work(self):
         """PathTraceRenderer::probeBlendWork: the work counts of the last blend_probes(count_work=True) as a dict."""
-        w = ProbeBlendWork()
-        self._ck(self.L.srt_host_renderer_probe_blend_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeBlendWork, self.L.srt_host_renderer_probe_blend_work)
 
     def scroll_probes(self, shift, which="coefficients", set_grid=False, count_work=False):
         """PathTraceRenderer::scrollProbes: srt_scroll_probes on the renderer's grid — move the arrays of `which` (as
         PathTracer.scroll_probes takes it) by `shift` = (sx, sy, sz) cells; set_grid: the grid's origin follows."""
         s3 = (C.c_int32 * 3)(*[int(v) for v in shift])
         flags = (PROBE_SCROLL_SET_GRID if set_grid else 0) | (PROBE_SCROLL_COUNT_WORK if count_work else 0)
-        self._ck(self.L.srt_host_renderer_scroll_probes(self._h, s3, _PathTracer._scroll_bits(which), flags))
+        self._ck(self.L.srt_host_renderer_scroll_probes(self._h, s3, _mask(PROBE_SCROLL_ARRAYS, which), flags))
 
     def follow_probe_grid(self, point):
         """PathTraceRenderer::followProbeGrid: srt_probe_grid_follow on the renderer's grid, then a scroll of the histories that have
@@ -807,9 +782,7 @@ class Renderer:
 
     def probe_scroll_work(self):
         """PathTraceRenderer::probeScrollWork: the work counts of the last scroll_probes(count_work=True) as a dict."""
-        w = ProbeScrollWork()
-        self._ck(self.L.srt_host_renderer_probe_scroll_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeScrollWork, self.L.srt_host_renderer_probe_scroll_work)
 
     def set_probe_cascade(self, grids, resolution=0, blend_cells=1.0):
         """PathTraceRenderer::setProbeCascade: srt_set_probe_cascade, as PathTracer.set_probe_cascade takes it."""
@@ -819,7 +792,7 @@ class Renderer:
     def capture_probe_cascade_level(self, level, which="all"):
         """PathTraceRenderer::captureProbeCascadeLevel: copy the current probe-grid coefficients, depth moments and state records,
         as `which` selects (PathTracer.capture_probe_cascade_level's names), into the cascade's level on the device."""
-        self._ck(self.L.srt_host_renderer_capture_probe_cascade_level(self._h, int(level), _PathTracer._cascade_bits(which)))
+        self._ck(self.L.srt_host_renderer_capture_probe_cascade_level(self._h, int(level), _mask(PROBE_CASCADE_ARRAYS, which)))
 
     def shade_probe_cascade(self, depth=False, states=False, normal_weight=False, albedo=False, band_weight=None, bias=None, min_variance=None, rows=None,
                             count_work=False):
@@ -840,15 +813,11 @@ class Renderer:
 
     def probe_cascade_work(self):
         """PathTraceRenderer::probeCascadeWork: the work counts of the last shade_probe_cascade(count_work=True) as a dict."""
-        w = ProbeCascadeWork()
-        self._ck(self.L.srt_host_renderer_probe_cascade_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeCascadeWork, self.L.srt_host_renderer_probe_cascade_work)
 
     def radiance_work(self):
         """PathTraceRenderer::radianceWork: the work counts of the last trace_radiance(count_work=True) as a dict."""
-        w = RadianceWork()
-        self._ck(self.L.srt_host_renderer_radiance_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(RadianceWork, self.L.srt_host_renderer_radiance_work)
 
     def _budget_params(self, threshold, floor, max_budget, albedo):
         return BudgetParams(float(threshold), float(floor), int(max_budget), BUDGET_ALBEDO if albedo else 0)
@@ -881,9 +850,7 @@ class Renderer:
 
     def sample_counts(self):
         """PathTraceRenderer::readSampleCounts: (H, W) uint32, scene rows.  Waits."""
-        out = np.empty((self.height, self.width), dtype=np.uint32)
-        self._ck(self.L.srt_host_renderer_read_sample_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_sample_counts, (self.height, self.width), np.uint32)
 
     def render_adaptive_frame(self, spp, rounds=1, threshold=0.05, floor=0.01, max_budget=64, albedo=True, max_samples=None):
         """PathTraceRenderer::renderAdaptiveFrame: the two-half adaptive workflow; returns (total samples, (H, W) uint32 samples per
@@ -904,9 +871,7 @@ class Renderer:
 
     def visibility(self, name):
         """PathTraceRenderer::readVisibility: output "ao" or "sun" of the last render_visibility() as an (H, W) float32 array."""
-        out = np.empty((self.height, self.width), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_visibility(self._h, VISIBILITY[name], out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_visibility, (self.height, self.width), np.float32, VISIBILITY[name])
 
     def render_reflection_gbuffer(self, rows=None, outputs=REFL_ALL, max_bounces=8, min_smoothness=1.0, min_specular=1.0, count_work=False):
         """PathTraceRenderer::renderReflectionGBuffer: push the camera and enqueue srt_render_reflection_gbuffer
@@ -919,15 +884,11 @@ class Renderer:
     def read_reflection(self, name):
         """PathTraceRenderer::readReflection: one output as a numpy array, "object" and "bounces" (H, W) int32, the others (H, W, 4) float32."""
         bit, dtype, ch = REFLECTION[name]
-        out = np.empty((self.height, self.width) if ch == 1 else (self.height, self.width, ch), dtype=dtype)
-        self._ck(self.L.srt_host_renderer_read_reflection(self._h, bit, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._read(self.L.srt_host_renderer_read_reflection, (self.height, self.width) if ch == 1 else (self.height, self.width, ch), dtype, bit)
 
     def reflection_work(self):
         """PathTraceRenderer::reflectionWork: the work counts of the last render_reflection_gbuffer(count_work=True) as a dict."""
-        w = ReflectionWork()
-        self._ck(self.L.srt_host_renderer_reflection_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ReflectionWork, self.L.srt_host_renderer_reflection_work)
 
     def reflection_guides(self, on=True, bounces=None):
         """PathTraceRenderer::reflectionGuides: with `on`, render_gbuffer() and every pass that takes its guides from it (denoise,
@@ -964,15 +925,11 @@ class Renderer:
 
     def probe_tail_work(self):
         """PathTraceRenderer::probeTailWork: the lookups of the last trace under probe_tail(count_work=True) as a dict."""
-        w = ProbeTailWork()
-        self._ck(self.L.srt_host_renderer_probe_tail_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(ProbeTailWork, self.L.srt_host_renderer_probe_tail_work)
 
     def visibility_work(self):
         """PathTraceRenderer::visibilityWork: the work counts of the last render_visibility(count_work=True) as a dict."""
-        w = VisibilityWork()
-        self._ck(self.L.srt_host_renderer_visibility_work(self._h, C.byref(w)))
-        return w.as_dict()
+        return self._get_work(VisibilityWork, self.L.srt_host_renderer_visibility_work)
 
     def ray_output(self, name):
         """PathTraceRenderer::readRayOutput: one output of the last trace_rays(), as capi.PathTracer.ray_output returns it."""
@@ -982,9 +939,7 @@ class Renderer:
         n = getattr(self, "_ray_traced", None)
         if n is None:
             raise RuntimeError("ray_output(%r): no trace_rays() yet" % name)
-        out = np.empty((n,) if ch == 1 else (n, ch), dtype=dtype)
-        self._ck(self.L.srt_host_renderer_read_ray_output(self._h, bit, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._read(self.L.srt_host_renderer_read_ray_output, (n,) if ch == 1 else (n, ch), dtype, bit)
 
     def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None, albedo=True, framebuffer=False,
                 gbuffer=True):
@@ -996,9 +951,7 @@ class Renderer:
 
     def denoised(self):
         """PathTraceRenderer::ReadDenoised: (H, W, 4) float32, scene rows, as capi.PathTracer.denoised returns it."""
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_denoised(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_denoised, (self.height, self.width, 4), np.float32)
 
     def temporal(self, samples=1, max_samples=None, plane_tolerance=None, normal_threshold=None, reset=False, framebuffer=False,
                  gbuffer=True):
@@ -1010,9 +963,7 @@ class Renderer:
 
     def history_length(self):
         """PathTraceRenderer::ReadHistoryLength: (H, W) float32, scene rows."""
-        out = np.empty((self.height, self.width), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_history_length(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_history_length, (self.height, self.width), np.float32)
 
     def render_temporal_frame(self, spp=1, denoise=False):
         """PathTraceRenderer::RenderTemporalFrame: render, guides, reprojection (and the denoiser) into the framebuffer."""
@@ -1030,9 +981,7 @@ class Renderer:
 
     def motion(self):
         """PathTraceRenderer::ReadMotion: (H, W, 4) float32 (u - x, v - y, Wsum, 0), scene rows."""
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_motion(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_motion, (self.height, self.width, 4), np.float32)
 
     def upsample(self, steps=None, stripe_width=None, sigma_normal=None, sigma_plane=None, in_place=False, framebuffer=False,
                  gbuffer=True):
@@ -1044,9 +993,7 @@ class Renderer:
 
     def upsampled(self):
         """PathTraceRenderer::ReadUpsampled: (H, W, 4) float32, scene rows, as capi.PathTracer.upsampled returns it."""
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_upsampled(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_upsampled, (self.height, self.width, 4), np.float32)
 
     def guided_upsample(self, on=True):
         """PathTraceRenderer::guidedUpsample: render_frame() follows every frame of blocks with the guides and the upsampler
@@ -1060,9 +1007,7 @@ class Renderer:
 
     def update_info(self):
         """PathTraceRenderer::UpdateInfo: what the last update_scene() did to the mesh BVH, as capi.UpdateInfo's dict."""
-        u = UpdateInfo()
-        self._ck(self.L.srt_host_renderer_update_info(self._h, C.byref(u)))
-        return u.as_dict()
+        return self._get_work(UpdateInfo, self.L.srt_host_renderer_update_info)
 
     def antialias(self, k=None, denoised=False, framebuffer=False):
         """PathTraceRenderer::Antialias: the OBJECT guide and the k x k sub-samples when they are stale, then srt_antialias
@@ -1072,9 +1017,7 @@ class Renderer:
 
     def antialiased(self):
         """PathTraceRenderer::ReadAntialiased: (H, W, 4) float32, scene rows, as capi.PathTracer.antialiased returns it."""
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_antialiased(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_antialiased, (self.height, self.width, 4), np.float32)
 
     def set_antialias(self, k):
         """PathTraceRenderer::antialias: render_frame() and render_temporal_frame() end in the resolve with this k (0: off)."""
@@ -1087,9 +1030,7 @@ class Renderer:
 
     def variance_map(self):
         """PathTraceRenderer::ReadVariance: (H, W) float32, scene rows, as capi.PathTracer.variance_map returns it."""
-        out = np.empty((self.height, self.width), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_variance(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_variance, (self.height, self.width), np.float32)
 
     def temporal_variance(self, on=True):
         """PathTraceRenderer::temporalVariance: render_temporal_frame() also keeps the luminance moments of the history and,
@@ -1098,9 +1039,7 @@ class Renderer:
 
     def moments(self):
         """PathTraceRenderer::ReadMoments: (H, W, 4) float32 (M1, M2, Lm, 0), scene rows, as capi.PathTracer.moments returns it."""
-        out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._ck(self.L.srt_host_renderer_read_moments(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self.L.srt_host_renderer_read_moments, (self.height, self.width, 4), np.float32)
 
     def stats(self):
         s = Stats()

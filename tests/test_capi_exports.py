@@ -23,6 +23,49 @@ def test_header_symbols_exported(srt):
     assert L.srt_abi_version() == srt.capi.ABI_VERSION
 
 
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "float": C.c_float}
+_DECLARATION = re.compile(r"^[ \t]*(const\s+char\s*\*|int)\s*(srt_[a-z_]+)\s*\(([^()]*)\)\s*;", re.M)
+_PARAMETER = re.compile(r"^(?:const\s+)?(?:struct\s+)?(\w+)\s*(\*{0,2})\s*\w*\s*(\[\d+\])?$")
+
+
+def _prototypes(header):
+    """Every function declaration of the header as (return type text, name, [parameter texts])."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(header).read(), flags=re.S)
+    out = []
+    for ret, name, params in _DECLARATION.findall(text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out.append((" ".join(ret.split()), name, [] if params == ["void"] else params))
+    return out
+
+
+def _ctype_of(capi, parameter):
+    """The ctypes type a header parameter maps to; anything the mapping does not name is an error, not a guess."""
+    m = _PARAMETER.match(parameter)
+    assert m, parameter
+    base, stars, array = m.group(1), len(m.group(2)), m.group(3)
+    if base in ("srt_context", "void"):
+        assert stars in (1, 2) and not array, parameter
+        return C.c_void_p if stars == 1 else C.POINTER(C.c_void_p)
+    if base in _SCALARS:
+        assert stars + (1 if array else 0) <= 1, parameter
+        return C.POINTER(_SCALARS[base]) if stars or array else _SCALARS[base]
+    assert base.startswith("srt_") and stars == 1 and not array, parameter
+    structs = {n.lower(): v for n, v in vars(capi).items() if isinstance(v, type) and issubclass(v, C.Structure)}
+    return C.POINTER(structs[base[len("srt_"):].replace("_", "")])
+
+
+def test_prototypes_match_header(srt):
+    """argtypes and restype of every function load_library() declares are what include/srt_pathtrace.h declares, under one
+    strict mapping and with no exemptions."""
+    declared = _prototypes(os.path.join(ROOT, "include", "srt_pathtrace.h"))
+    assert len(declared) == 182 and sorted(n for _, n, _ in declared) == sorted(srt.capi.EXPORTS)
+    L = srt.load_library()
+    for ret, name, params in declared:
+        fn = getattr(L, name)
+        assert list(fn.argtypes or []) == [_ctype_of(srt.capi, p) for p in params], (name, fn.argtypes, params)
+        assert fn.restype is {"int": C.c_int, "const char*": C.c_char_p}[ret.replace(" *", "*")], (name, fn.restype, ret)
+
+
 def test_struct_layouts_match_header(srt):
     # sizes the header implies (all 4-byte fields, no padding)
     assert C.sizeof(srt.Material) == 44 and C.sizeof(srt.Object) == 80
