@@ -1060,6 +1060,7 @@ int srt_get_visibility_work(srt_context* ctx, srt_visibility_work* out);
 #define SRT_RADIANCE_RESET 1u      /* sample first_sample overwrites the output element; without it the running mean continues */
 #define SRT_RADIANCE_NORMALIZE 2u  /* as SRT_RAYS_NORMALIZE */
 #define SRT_RADIANCE_COUNT_WORK 4u /* fill srt_radiance_work for this call */
+#define SRT_RADIANCE_SUN_SAMPLING 0x10u /* 16: sun sampling at diffuse bounces, rules S1 - S9 at the end of this file (8 is unassigned and refused) */
 
 typedef struct srt_radiance_params { /* 24 bytes */
     uint32_t first_sample;           /* f0 >= 1 */
@@ -1441,6 +1442,7 @@ int srt_write_accumulator(srt_context* ctx, const float* src_rgba);
 #define SRT_LIGHT_PROBE_RESET 1u      /* sample first_sample overwrites the means; without it they continue from the RADIANCE buffer */
 #define SRT_LIGHT_PROBE_NORMALIZE 2u  /* as SRT_RADIANCE_NORMALIZE */
 #define SRT_LIGHT_PROBE_COUNT_WORK 4u /* fill srt_light_probe_work for this call */
+#define SRT_LIGHT_PROBE_SUN_SAMPLING 0x10u /* 16: srt_trace_light_probes and srt_trace_light_probes_listed, rules S1 - S9 (8 is refused) */
 #define SRT_LIGHT_PROBE_COEFFICIENTS 1u /* output: P*9 float4 */
 #define SRT_LIGHT_PROBE_RADIANCE 2u     /* output: P*K float4 */
 #define SRT_LIGHT_PROBE_MAX_DIRECTIONS 4096u
@@ -2302,6 +2304,53 @@ int srt_probe_grid_depth_params_default(srt_probe_grid_depth_params* out);
 int srt_write_probe_grid_depth(srt_context* ctx, const float* moments, size_t probes, uint32_t resolution);
 int srt_bind_probe_grid_depth(srt_context* ctx, const void* d_ptr, size_t probes, uint32_t resolution);
 int srt_shade_probe_grid_depth(srt_context* ctx, const srt_probe_grid_params* params, const srt_probe_grid_depth_params* depth);
+
+/* ---- sun sampling at diffuse bounces (ABI 7, backward compatible) ---------------------------------------------------------------
+ * One flag bit, value 16, on two existing parameter structs: SRT_RADIANCE_SUN_SAMPLING (srt_trace_radiance) and
+ * SRT_LIGHT_PROBE_SUN_SAMPLING (srt_trace_light_probes, srt_trace_light_probes_listed), defined next to the flags they join
+ * (written 0x10u: the decimal constants of the two passes as they shipped are a closed set that their ABI tests keep pinned).  No entry point, no exported symbol; without
+ * the flag every call launches the kernel it launched before.  Every path otherwise finds the sun by accident: GetEnvironmentColor
+ * adds SunColor where dot(d, -SunDirection) > 0.99, and a diffuse bounce draws its direction blindly.  With the flag every diffuse
+ * vertex sends one shadow segment to a point of that cap, and its own bounce sees the environment without the sun: next-event
+ * estimation for the sun, converging to what the calls converge to without the flag.
+ *
+ * Binary32 without contraction throughout.  G = 0x9E3779B9; c is the float 0x3F7D70A4, GetEnvironmentColor's threshold as a float
+ * compare; k = 1.0f - c; W0 = (float)(3.14159265358979323846 / 6.0 * (double)k).
+ *
+ * S1. Where the flag applies.  The path of radiance rule 2 is unchanged: the main stream's draws and their order, every bounce
+ *     direction, every GetClosestObject call, the alpha lane, the fold.  Only the colour L changes.  With max_bounces == 0, or at a
+ *     primary miss, nothing changes.
+ * S2. Which vertex is diffuse.  A vertex is diffuse when tt = Smoothness * specularProb (Raytracer.cpp:175) == 0.0f.  Every other
+ *     vertex is treated as without the flag, the sun inside its environment term.
+ * S3. The sun stream of the vertex of loop iteration b.  With i, i+1, i+2 the indices of that iteration's three hemisphere draws
+ *     in the stream of key = srt_rng_key(seed, id, f):  ks = srt_mix32((key + (i + 3) * G) ^ 0x53554E21u); the sun's draws are
+ *     srt_rng_draw(ks, j).  The main stream is not advanced.
+ * S4. Sampling the cap.  For J = 0 .. 7: a = (rand_unit(draw 2J) - 0.5f) * 2, b = (rand_unit(draw 2J + 1) - 0.5f) * 2,
+ *     q = a*a + b*b (rand_unit(r) = (float)r / 32767.0f); take the first J with q <= 1, and a = b = q = 0 if there is none
+ *     (probability 0.215^8).  Then z = 1 - q*k, h = sqrtf(k * (1 + z)), w' = (t1*(a*h) + t2*(b*h)) + s*z per component, in that
+ *     order, w = float3::Normalized(w'): Lambert's equal-area map of the disc onto the cap, without trigonometry.
+ * S5. The frame, made on the host once per enqueue from the environment captured there: s = sun_direction * -1,
+ *     e = |s.x| < 0.5f ? (1,0,0) : (0,1,0), t1 = Normalized(cross(e, s)), t2 = cross(s, t1), the cross products written out
+ *     component by component.  The flag is refused with SRT_ERR_STATE, after the call's own argument errors and before anything is
+ *     touched, when a component of s is not finite or (s.x*s.x + s.y*s.y) + s.z*s.z lies outside [0.9999, 1.0001], and when the
+ *     context's probe-tail mode is on (the combination is not built).
+ * S6. The segment.  At a diffuse vertex with point p, normal n and the throughput T its bounce's result meets (after this
+ *     iteration's x 0.8): sd = (w.x*s.x + w.y*s.y) + w.z*s.z, cn = (w.x*n.x + w.y*n.y) + w.z*n.z.  If sd >= c && cn > 0 the segment
+ *     (p + n * .00001f, w, t_max = +inf) is traced by srt_trace_occlusion's predicate; if it is open, m = max(|w.x|, |w.y|, |w.z|),
+ *     weight = W0 / ((m*m)*m) (one IEEE division) and L_l = L_l + ((Sun_l * weight) * T_l) for l = 0, 1, 2, Sun the clamped sun
+ *     colour.  The add comes BEFORE the add of the same iteration's bounce result.  (The blind bounce is a normalised point of
+ *     the cube [-1, 1]^3 folded into the normal's hemisphere — GetRandomDirection's rejection test never rejects — with density
+ *     1 / (12 m^3) per steradian, not 1 / (2 pi): the cap of solid angle 2 pi k is met with probability (pi k / 6) / m^3.)
+ * S7. The blind bounce of a diffuse vertex.  When its ray leaves the scene it adds E0(ray) * T, E0 being GetEnvironmentColor with
+ *     SunColor = (0, 0, 0): its last line adds + 0.0f.  The alpha tag is as before.
+ * S8. Invariants.  With SunColor = (0, 0, 0) the outputs are bit for bit those without the flag.  In a scene without a diffuse
+ *     vertex (SpecularAmount >= 1 and Smoothness > 0 everywhere) the outputs and the work record are those without the flag.
+ *     Radiance rules 3 - 6 hold under the flag (mean, camera-ray equivalence with the flag on both sides, splitting, continuation);
+ *     srt_trace_light_probes' RADIANCE equals srt_trace_radiance on the explicit rays under the flag, its COEFFICIENTS are the
+ *     fixed-order projection of that RADIANCE, and the listed call writes at the listed probes what the unlisted call writes.
+ * S9. Work.  Under the flag wave_calls of srt_radiance_work (and of srt_light_probe_work) additionally counts one for every
+ *     wave-level any-hit invocation; closest_calls is unchanged.  The number of sun segments is not reported.
+ * srt_render, srt_render_adaptive[_tail] and the probe tail do not take the flag. */
 
 #ifdef __cplusplus
 }

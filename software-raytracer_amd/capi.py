@@ -40,9 +40,11 @@ REFLECTION = dict(GBUFFERS, bounces=(REFL_BOUNCES, np.int32, 1))
 MIRROR_HISTORY_GUIDES = REFL_OBJECT | REFL_NORMAL_DEPTH | REFL_POSITION | REFL_BOUNCES
 # radiance queries (srt_trace_radiance): the flags of srt_radiance_params and the sample limit
 RADIANCE_RESET, RADIANCE_NORMALIZE, RADIANCE_COUNT_WORK = 1, 2, 4
+RADIANCE_SUN_SAMPLING = 16  # SRT_RADIANCE_SUN_SAMPLING: sun sampling at diffuse bounces (rules S1 - S9); 8 is unassigned
 RADIANCE_MAX_SAMPLES = 4096
 # light probes (srt_trace_light_probes): the flags and outputs of srt_light_probe_params, the direction limit, float4 per probe
 LIGHT_PROBE_RESET, LIGHT_PROBE_NORMALIZE, LIGHT_PROBE_COUNT_WORK = 1, 2, 4
+LIGHT_PROBE_SUN_SAMPLING = 16  # SRT_LIGHT_PROBE_SUN_SAMPLING: the listed call takes it too
 LIGHT_PROBE_COEFFICIENTS, LIGHT_PROBE_RADIANCE = 1, 2
 LIGHT_PROBE_MAX_DIRECTIONS = 4096
 LIGHT_PROBE_COEFFS = 9
@@ -1448,17 +1450,20 @@ class PathTracer:
         self.render_reflection_gbuffer(outputs=outputs)
 
     def trace_radiance(self, origins=None, directions=None, samples=None, bounces=None, seed=0, first_sample=1, reset=True, id_base=0,
-                       normalize=False, count_work=False, flags=0):
+                       normalize=False, count_work=False, flags=0, sun_sampling=False):
         """srt_trace_radiance: the running mean of `samples` path-traced samples (default 16) of `bounces` bounces (default 8) along
         every ray: what render() leaves in the accumulator for a pixel, for rays of the caller's.  `origins` / `directions`: numpy
         arrays (N, 4) float32 (written with write_rays) or torch tensors on this tracer's device (bound with bind_rays); both None:
         the current rays.  Ray i draws from the stream of pixel id_base + i; reset=False continues the mean the output holds;
         normalize: SRT_RADIANCE_NORMALIZE; count_work: SRT_RADIANCE_COUNT_WORK (radiance_work() then reads the record).
-        Asynchronous, like render(); radiance() reads the result."""
+        sun_sampling: SRT_RADIANCE_SUN_SAMPLING — one shadow segment towards the sun at every diffuse bounce, the sun taken out of
+        that bounce (rules S1 - S9): the same mean with far less noise in sunlit scenes; refused (SRT_ERR_STATE) while probe_tail is on
+        or when the environment's sun_direction is not a unit vector.  Asynchronous, like render(); radiance() reads the result."""
         self._rays_given("trace_radiance", origins, directions)
         p = self._default(RadianceParams, self.L.srt_radiance_params_default)
         _set(p, sample_count=samples, max_bounces=bounces, first_sample=first_sample, seed=int(seed) & 0xFFFFFFFF, id_base=int(id_base) & 0xFFFFFFFF,
-             flags=int(flags) | (RADIANCE_RESET if reset else 0) | (RADIANCE_NORMALIZE if normalize else 0) | (RADIANCE_COUNT_WORK if count_work else 0))
+             flags=int(flags) | (RADIANCE_RESET if reset else 0) | (RADIANCE_NORMALIZE if normalize else 0) | (RADIANCE_COUNT_WORK if count_work else 0) |
+             (RADIANCE_SUN_SAMPLING if sun_sampling else 0))
         n = self._ray_count
         t = self._radiance_bound
         if n is not None and t is not None and t.shape[0] < n:
@@ -1619,7 +1624,7 @@ class PathTracer:
             bound[key] = tensor
 
     def trace_light_probes(self, positions=None, directions=None, samples=None, bounces=None, seed=0, first_sample=1, reset=True, id_base=0,
-                           normalize=False, count_work=False, coefficients=True, radiance=False, flags=0, listed=False):
+                           normalize=False, count_work=False, coefficients=True, radiance=False, flags=0, listed=False, sun_sampling=False):
         """srt_trace_light_probes: for each of P probe positions, the running mean of `samples` path-traced samples (default 16) of
         `bounces` bounces (default 8) along each of K shared directions, projected onto the nine SH coefficients of bands 0..2.
         `positions`: numpy (P, 4) float32 (written) or a torch tensor on this tracer's device (bound); None: the current ones.
@@ -1628,13 +1633,14 @@ class PathTracer:
         light_probe_radiance()); reset=False continues the means the RADIANCE buffer holds; normalize: SRT_LIGHT_PROBE_NORMALIZE;
         count_work: SRT_LIGHT_PROBE_COUNT_WORK (light_probe_work() then reads the record).  listed: srt_trace_light_probes_listed —
         only the probes of the list bound for tracing (bind_probe_list()); every other probe's outputs keep their bits.
+        sun_sampling: SRT_LIGHT_PROBE_SUN_SAMPLING, as trace_radiance's (the listed call takes it too).
         Asynchronous, like render()."""
         L = self.L
         self._probe_inputs("trace_light_probes", positions, directions)
         p = self._default(LightProbeParams, L.srt_light_probe_params_default)
         _set(p, sample_count=samples, max_bounces=bounces, first_sample=first_sample, seed=int(seed) & 0xFFFFFFFF, id_base=int(id_base) & 0xFFFFFFFF,
              flags=int(flags) | (LIGHT_PROBE_RESET if reset else 0) | (LIGHT_PROBE_NORMALIZE if normalize else 0) |
-             (LIGHT_PROBE_COUNT_WORK if count_work else 0),
+             (LIGHT_PROBE_COUNT_WORK if count_work else 0) | (LIGHT_PROBE_SUN_SAMPLING if sun_sampling else 0),
              outputs=(LIGHT_PROBE_COEFFICIENTS if coefficients else 0) | (LIGHT_PROBE_RADIANCE if radiance else 0))
         np_, nk = self._probe_count, self._probe_dir_count
         if np_ is not None and nk is not None:

@@ -56,6 +56,8 @@
 #include "srt_probe_cascade_host.h"
 #include "srt_probe_tail.hip.h"
 #include "srt_probe_tail_host.h"
+#include "srt_sun_sampling.hip.h"
+#include "srt_sun_sampling_host.h"
 #include "srt_adaptive.hip.h"
 #include "srt_adaptive_host.h"
 #include "srt_adaptive_tail_host.h"
@@ -1217,6 +1219,14 @@ static int launch_persistent_tail(srt_context* ctx, void (*kernel)(srt::KernelPa
     SRT_HIP(ctx, hipGetLastError());
     return SRT_OK;
 }
+// ... of a SUN instantiation (srt_sun_sampling.hip.h): the frame is a kernel argument of its own
+template <class IO>
+static int launch_persistent_sun(srt_context* ctx, void (*kernel)(srt::KernelParams, IO, srt::SunIO), unsigned wgs, const KernelSetup& ks,
+                                 const srt::KernelParams& K, const IO& io, const srt::SunIO& sio) {
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io, sio);
+    SRT_HIP(ctx, hipGetLastError());
+    return SRT_OK;
+}
 // ... over the tiles of K's band
 template <class IO>
 static int launch_tiles(srt_context* ctx, void (*kernel)(srt::KernelParams, IO), const KernelSetup& ks, const srt::KernelParams& K, const IO& io) {
@@ -2171,6 +2181,29 @@ static srt::ProbeTailIO probe_tail_io(srt_context* ctx) {
     return io;
 }
 
+// ---- sun sampling (rules S1 - S9; srt_sun_sampling_host.h) -----------------------------------------------------------
+static_assert(SRT_RADIANCE_SUN_SAMPLING == srt::SUN_SAMPLING_FLAG && SRT_LIGHT_PROBE_SUN_SAMPLING == srt::SUN_SAMPLING_FLAG &&
+                  !(srt::RADIANCE_FLAG_ALL & srt::SUN_SAMPLING_FLAG) && !(srt::LIGHT_PROBE_FLAG_ALL & srt::SUN_SAMPLING_FLAG) &&
+                  sizeof(srt::SunFrame) == sizeof(srt::SunIO) && sizeof(srt::SunIO) == 36,
+              "srt_sun_sampling_host.h, srt_sun_sampling.hip.h and srt_pathtrace.h disagree");
+
+// the flag's refusals (S5), after the call's own errors and before anything is touched
+static int check_sun_sampling(srt_context* ctx, const char* who) {
+    const char* why = "";
+    if (const srt::RaysStatus rs = srt::sun_sampling_check(ctx->env.sun_direction, ctx->probe_tail.enabled, &why))
+        return fail(ctx, (int)rs, "%s: %s (sun_direction %g %g %g)", who, why, ctx->env.sun_direction[0], ctx->env.sun_direction[1], ctx->env.sun_direction[2]);
+    return SRT_OK;
+}
+
+// the frame of the environment as it stands at the enqueue: a kernel argument, so an enqueued launch keeps it
+static srt::SunIO sun_io(srt_context* ctx) {
+    srt::SunFrame f;
+    srt::sun_frame(ctx->env.sun_direction, f);
+    srt::SunIO io;
+    for (int a = 0; a < 3; ++a) io.s[a] = f.s[a], io.t1[a] = f.t1[a], io.t2[a] = f.t2[a];
+    return io;
+}
+
 // The sample scratch of the three sample-pool launches (srt_trace_radiance, srt_trace_light_probes, srt_render_adaptive; one
 // stream runs them all): every wave of a grid of `wgs` workgroups has its own region.  Grown once the stream has finished with
 // the smaller one.
@@ -2187,9 +2220,13 @@ int srt_trace_radiance(srt_context* ctx, const srt_radiance_params* t) {
     if (!ctx || !t) return SRT_ERR_INVALID_ARG;
     const srt::RadianceCall call{t->first_sample, t->sample_count, t->max_bounces, t->seed, t->id_base, t->flags};
     const char* why = "";
-    if (const srt::RaysStatus rs = srt::radiance_check_trace(ctx->rays, ctx->scene_set, call, &why))
+    if (const srt::RaysStatus rs = srt::sun_radiance_check_trace(ctx->rays, ctx->scene_set, call, &why))
         return fail(ctx, (int)rs, "srt_trace_radiance: %s (first_sample %u, sample_count %u, max_bounces %d, flags 0x%x)", why, t->first_sample,
                     t->sample_count, t->max_bounces, t->flags);
+    if (srt::sun_sampling_asked(t->flags)) {
+        if (const int rc = check_sun_sampling(ctx, "srt_trace_radiance")) return rc;
+    }
+    const bool sun = srt::sun_sampling_applies(t->flags, t->max_bounces);
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = ctx->rays.count();
     const bool count = (t->flags & SRT_RADIANCE_COUNT_WORK) != 0;
@@ -2206,8 +2243,10 @@ int srt_trace_radiance(srt_context* ctx, const srt_radiance_params* t) {
     if (t->flags & SRT_RADIANCE_RESET) K.flags |= SRT_RENDER_RESET;
     const auto kernel = SRT_KERNEL(srt::radiance_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
     const auto tail_kernel = SRT_KERNEL(srt::radiance_tail_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0);
+    const auto sun_kernel = SRT_KERNEL(srt::radiance_sun_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0);
     // the grid first: the sample scratch is sized by it
-    const unsigned wgs = srt::radiance_grid(n, srt::OUT_WG_UNITS, resident_workgroups(ctx, tail ? (const void*)tail_kernel : (const void*)kernel, ks.lds_bytes));
+    const unsigned wgs = srt::radiance_grid(
+        n, srt::OUT_WG_UNITS, resident_workgroups(ctx, sun ? (const void*)sun_kernel : tail ? (const void*)tail_kernel : (const void*)kernel, ks.lds_bytes));
     if (const int rc = ensure_sample_rows(ctx, wgs)) return rc;
     if (count) {
         if (const int rc = zero_work(ctx, ctx->d_radiance_work)) return rc;
@@ -2222,7 +2261,10 @@ int srt_trace_radiance(srt_context* ctx, const srt_radiance_params* t) {
     io.out = dst;
     io.rows = ctx->d_radiance_rows;
     io.work = count ? (unsigned long long*)ctx->d_radiance_work : nullptr;
-    if (const int rc = tail ? launch_persistent_tail(ctx, tail_kernel, wgs, ks, K, io, probe_tail_io(ctx)) : launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
+    if (const int rc = sun    ? launch_persistent_sun(ctx, sun_kernel, wgs, ks, K, io, sun_io(ctx))
+                       : tail ? launch_persistent_tail(ctx, tail_kernel, wgs, ks, K, io, probe_tail_io(ctx))
+                              : launch_persistent(ctx, kernel, wgs, ks, K, io))
+        return rc;
     srt::radiance_traced(ctx->radiance, n, dst, t->flags);
     srt::probe_tail_traced(ctx->probe_tail);
     return SRT_OK;
@@ -2303,13 +2345,17 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
     if (!ctx || !t) return SRT_ERR_INVALID_ARG;
     const srt::LightProbeCall call{t->first_sample, t->sample_count, t->max_bounces, t->seed, t->id_base, t->flags, t->outputs, t->reserved};
     const char* why = "";
-    if (const srt::RaysStatus rs = srt::light_probe_check_trace(ctx->probes, ctx->scene_set, call, current(ctx->probe_out[1], ctx->d_probe_out_own[1]), &why))
+    if (const srt::RaysStatus rs = srt::sun_light_probe_check_trace(ctx->probes, ctx->scene_set, call, current(ctx->probe_out[1], ctx->d_probe_out_own[1]), &why))
         return fail(ctx, (int)rs, "%s: %s (first_sample %u, sample_count %u, max_bounces %d, flags 0x%x, outputs 0x%x, reserved %u)", who, why, t->first_sample,
                     t->sample_count, t->max_bounces, t->flags, t->outputs, t->reserved);
     const size_t np = ctx->probes.positions.count(), nk = ctx->probes.directions.count();
     if (listed) {
         if (const srt::RaysStatus rs = srt::probe_list_check_trace(ctx->probe_update, np, &why)) return fail(ctx, (int)rs, "%s: %s", who, why);
     }
+    if (srt::sun_sampling_asked(t->flags)) {
+        if (const int rc = check_sun_sampling(ctx, who)) return rc;
+    }
+    const bool sun = srt::sun_sampling_applies(t->flags, t->max_bounces);
     const bool tail = srt::probe_tail_applies(ctx->probe_tail, t->max_bounces);
     if (tail) {  // the outputs this call writes, where they stand now: COEFFICIENTS, and RADIANCE as srt_trace_radiance's
         for (int i = 0; i < srt::LIGHT_PROBE_SLOTS; ++i)
@@ -2338,9 +2384,10 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
     if (t->flags & SRT_LIGHT_PROBE_RESET) K.flags |= SRT_RENDER_RESET;
     const auto kernel = SRT_KERNEL(srt::light_probe_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count, listed);
     const auto tail_kernel = SRT_KERNEL(srt::light_probe_tail_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, listed);
+    const auto sun_kernel = SRT_KERNEL(srt::light_probe_sun_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, listed);
     // the grid first: the sample scratch is sized by it
-    const unsigned wgs =
-        srt::light_probe_grid(np, nk, srt::OUT_WG_UNITS, resident_workgroups(ctx, tail ? (const void*)tail_kernel : (const void*)kernel, ks.lds_bytes));
+    const unsigned wgs = srt::light_probe_grid(
+        np, nk, srt::OUT_WG_UNITS, resident_workgroups(ctx, sun ? (const void*)sun_kernel : tail ? (const void*)tail_kernel : (const void*)kernel, ks.lds_bytes));
     if (const int rc = ensure_sample_rows(ctx, wgs)) return rc;
     if (count) {
         if (const int rc = zero_work(ctx, ctx->d_probe_work)) return rc;
@@ -2358,7 +2405,10 @@ static int trace_light_probes(srt_context* ctx, const srt_light_probe_params* t,
     io.rows = ctx->d_radiance_rows;
     io.work = count ? (unsigned long long*)ctx->d_probe_work : nullptr;
     io.list = listed ? current_probe_list(ctx) : nullptr;
-    if (const int rc = tail ? launch_persistent_tail(ctx, tail_kernel, wgs, ks, K, io, probe_tail_io(ctx)) : launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
+    if (const int rc = sun    ? launch_persistent_sun(ctx, sun_kernel, wgs, ks, K, io, sun_io(ctx))
+                       : tail ? launch_persistent_tail(ctx, tail_kernel, wgs, ks, K, io, probe_tail_io(ctx))
+                              : launch_persistent(ctx, kernel, wgs, ks, K, io))
+        return rc;
     if (J > 1 && coefficients) {  // the block sums of every probe, added in ascending block order
         const size_t elems = np * (size_t)srt::LP_COEFFS;
         if (listed)

@@ -1196,7 +1196,10 @@ __device__ __forceinline__ RGB color_lerp(RGB a, RGB b, float t) {
 
 // GetEnvironmentColor (Raytracer.cpp:77-89).  The four colours arrive clamped (Color's constructor, Common.hpp:253-262) in
 // the image's constants block, next to srt_powf's table: LDS reads, no kernel-argument registers, no constant-memory trips.
-__device__ __forceinline__ RGB environment(const Lds& S, V3 d) {
+// E0 (sun sampling's rule S7, srt_sun_sampling.hip.h): for a lane with `no_sun` SunColor counts as (0, 0, 0) — the last line adds
+// +0.0f.  Without E0 the flag is not read: the function every other caller has.
+template <bool E0 = false>
+__device__ __forceinline__ RGB environment(const Lds& S, V3 d, [[maybe_unused]] bool no_sun = false) {
     const float4 e0 = S.c[CONST_ENV_ROW], e1 = S.c[CONST_ENV_ROW + 1], e2 = S.c[CONST_ENV_ROW + 2], e3 = S.c[CONST_ENV_ROW + 3];
     RGB Sky{e0.x, e0.y, e0.z};
     RGB Horizon{e1.x, e1.y, e1.z};
@@ -1206,6 +1209,7 @@ __device__ __forceinline__ RGB environment(const Lds& S, V3 d) {
     // :79 compares the float with the DOUBLE literal 0.99, which lies between the floats 0x3F7D70A3 (0.98999995) and 0x3F7D70A4
     // (0.99000001): (double)sd > 0.99 exactly when sd >= 0x3F7D70A4 (a NaN fails both) — one float compare, no conversion
     bool sunny = sd >= __uint_as_float(0x3F7D70A4u);
+    if constexpr (E0) sunny = sunny && !no_sun;
     RGB Sun{sunny ? e0.w : 0.0f, sunny ? e1.w : 0.0f, sunny ? e2.w : 0.0f};
     // one srt_powf call site for both branches (:81 powf(upd, 0.1f) / :87 powf(|upd|, .05f)):
     // the arguments are selected per lane, so up- and down-going lanes do not serialize.

@@ -61,6 +61,10 @@ struct LpWork<true> {
 struct LpTailWork : LpWork<true> {
     ProbeTail tail;
 };
+// ... of a SUN instantiation (srt_sun_sampling.hip.h): the sums are always kept and flushed when the launch has the record
+struct LpSunWork : LpWork<true> {
+    const SunIO* sun = nullptr;
+};
 
 // one butterfly of six levels: afterwards every lane holds the sum; lane 0's association is the header's pairwise tree
 __device__ __forceinline__ float lp_wave_tree(float v) {
@@ -73,12 +77,14 @@ __device__ __forceinline__ float lp_wave_tree(float v) {
 // LISTED (srt_trace_light_probes_listed): the units are (q, j) for q < n, the count in the list's header, read here: the host never
 // learns it; probe p = list[q], and a word >= P skips the unit.  Everything of probe p is computed and stored as the unlisted
 // launch does it, but a multi-block partial goes to the COMPACT unit q*J + j (light_probe_sum_listed_kernel scatters it).
-// The kernel's text is srt_light_probes_body.inc, included by the two kernels that run it, as radiance_kernel's (see there); TAIL
-// (srt_probe_tail.hip.h) runs the lookup run_sample_pool calls at this text's own path end.
+// The kernel's text is srt_light_probes_body.inc, included by the three kernels that run it, as radiance_kernel's (see there); TAIL
+// (srt_probe_tail.hip.h) runs the lookup run_sample_pool calls at this text's own path end, SUN (srt_sun_sampling.hip.h) the sun
+// sample run_sample_pool makes between the bounce and its closest_hit.
 template <bool SCENE_LDS, bool MESH, bool COUNT, bool LISTED = false>
 __global__ void __launch_bounds__(WG_THREADS) light_probe_kernel(const KernelParams P, const LightProbeIO io) {
-    constexpr bool TAIL = false;
+    constexpr bool TAIL = false, SUN = false;
     [[maybe_unused]] constexpr const ProbeTailIO* tio = nullptr;
+    [[maybe_unused]] constexpr const SunIO* sio = nullptr;
 #include "srt_light_probes_body.inc"
 }
 
@@ -86,8 +92,19 @@ __global__ void __launch_bounds__(WG_THREADS) light_probe_kernel(const KernelPar
 // has the record
 template <bool SCENE_LDS, bool MESH, bool LISTED>
 __global__ void __launch_bounds__(WG_THREADS) light_probe_tail_kernel(const KernelParams P, const LightProbeIO io, const ProbeTailIO tail_io) {
-    constexpr bool TAIL = true, COUNT = true;
+    constexpr bool TAIL = true, SUN = false, COUNT = true;
     const ProbeTailIO* const tio = &tail_io;
+    [[maybe_unused]] constexpr const SunIO* sio = nullptr;
+#include "srt_light_probes_body.inc"
+}
+
+// srt_trace_light_probes[_listed] with SRT_LIGHT_PROBE_SUN_SAMPLING (srt_sun_sampling.hip.h): the frame is a kernel argument of its
+// own; the work sums are always kept and flushed when the launch has the record
+template <bool SCENE_LDS, bool MESH, bool LISTED>
+__global__ void __launch_bounds__(WG_THREADS) light_probe_sun_kernel(const KernelParams P, const LightProbeIO io, const SunIO sun_io) {
+    constexpr bool TAIL = false, SUN = true, COUNT = true;
+    [[maybe_unused]] constexpr const ProbeTailIO* tio = nullptr;
+    const SunIO* const sio = &sun_io;
 #include "srt_light_probes_body.inc"
 }
 

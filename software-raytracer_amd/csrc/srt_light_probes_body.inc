@@ -1,5 +1,6 @@
-    // srt_light_probes_body.inc — the text of light_probe_kernel and light_probe_tail_kernel (srt_light_probes.hip.h includes it
-    // into both).  Reads the kernel's P and io, its template parameters, and TAIL, COUNT and tio as the including function has them.
+    // srt_light_probes_body.inc — the text of light_probe_kernel, light_probe_tail_kernel and light_probe_sun_kernel
+    // (srt_light_probes.hip.h includes it into all three).  Reads the kernel's P and io, its template parameters, and TAIL, SUN, COUNT,
+    // tio and sio as the including function has them.
     extern __shared__ float4 lds_scene[];
     if constexpr (SCENE_LDS) {  // staged as pathtrace_kernel stages it: every load issued before the first LDS store
         constexpr int STAGE = 8;
@@ -25,8 +26,12 @@
     Prof prof{};
 #endif
     Tally<false> no_tally;
-    std::conditional_t<TAIL, LpTailWork, LpWork<COUNT>> W;
+    // (named through a template parameter: the type is dependent in every including kernel, so the branches of the modes a kernel
+    // does not have are discarded without being checked against its Work)
+    using WorkOfMode = std::conditional_t<SUN, LpSunWork, std::conditional_t<TAIL, LpTailWork, LpWork<COUNT>>>;
+    std::conditional_t<SCENE_LDS, WorkOfMode, WorkOfMode> W;
     if constexpr (TAIL) W.tail.io = tio;
+    if constexpr (SUN) W.sun = sio;
     W.add(LP_WORK_WAVES, 1ull);
     auto lanes = [](bool b) { return (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(b)); };
     auto below = [](unsigned long long m) { return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); };
@@ -193,6 +198,11 @@
                         sray = normalized(l);                                            // :176
                         o = v3(hp.x + hn.x * ofs, hp.y + hn.y * ofs, hp.z + hn.z * ofs);  // :177
                     }
+                    [[maybe_unused]] bool diffuse = false;  // SUN: this lane's bounce was blind (rule S2); kept across closest_hit for S7
+                    if constexpr (SUN) {  // rules S3 - S6 in wave-uniform control flow, before the bounce's own result is added
+                        diffuse = busy && (S.mat(hprim, 0).x * spec) == 0.0f;  // tt of :175, as computed above
+                        W.add(LP_WORK_WAVE_CALLS, sun_sample<MESH, SCENE_LDS>(S, P, *W.sun, diffuse, rng, o, hn, T, L));
+                    }
                     // the scan runs in wave-uniform control flow: idle lanes help with other lanes' rays
                     const Hit h = closest_hit<MESH, false, SCENE_LDS>(S, P, o, sray, busy, 1, deferred, no_tally SRT_PROF_ARG);
                     W.add(LP_WORK_WAVE_CALLS, 1ull);
@@ -203,7 +213,7 @@
                         bool end_path;
                         uint32_t atag = 0u;  // the sample's alpha: NaN only from the environment (T's alpha is +0)
                         if (h.prim < 0) {    // :178-181
-                            const RGB e = environment(S, sray);
+                            const RGB e = environment<SUN>(S, sray, diffuse);  // (S7: without the sun after a blind bounce)
                             L = RGB{L.r + e.r * T.r, L.g + e.g * T.g, L.b + e.b * T.b};  // (NN)
                             atag = alpha_tag(environment_alpha(sray));
                             end_path = true;
@@ -310,6 +320,13 @@
             if (lane < LP_WORK_N) atomicAdd(&io.work[lane], v);
         }
         W.tail.flush(lane);
+    } else if constexpr (SUN) {  // the sums are always kept; flushed when the launch has the record
+        if (io.work) {
+            unsigned long long v = 0ull;
+#pragma unroll
+            for (int q = 0; q < LP_WORK_N; ++q) v = lane == q ? W.n[q] : v;
+            if (lane < LP_WORK_N) atomicAdd(&io.work[lane], v);
+        }
     } else if constexpr (COUNT) {  // the wave's sums: lane k adds counter k — one vector atomic per wave
         unsigned long long v = 0ull;
 #pragma unroll

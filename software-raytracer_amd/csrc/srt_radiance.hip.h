@@ -49,8 +49,9 @@ struct RadianceIO {
 // COUNT and tio of the function it stands in.
 template <bool SCENE_LDS, bool MESH, bool COUNT>
 __global__ void __launch_bounds__(WG_THREADS) radiance_kernel(const KernelParams P, const RadianceIO io) {
-    constexpr bool TAIL = false;
+    constexpr bool TAIL = false, SUN = false;
     [[maybe_unused]] constexpr const ProbeTailIO* tio = nullptr;
+    [[maybe_unused]] constexpr const SunIO* sio = nullptr;
 #include "srt_radiance_body.inc"
 }
 
@@ -58,8 +59,19 @@ __global__ void __launch_bounds__(WG_THREADS) radiance_kernel(const KernelParams
 // and flushed when the launch has the record
 template <bool SCENE_LDS, bool MESH>
 __global__ void __launch_bounds__(WG_THREADS) radiance_tail_kernel(const KernelParams P, const RadianceIO io, const ProbeTailIO tail_io) {
-    constexpr bool TAIL = true, COUNT = true;
+    constexpr bool TAIL = true, SUN = false, COUNT = true;
     const ProbeTailIO* const tio = &tail_io;
+    [[maybe_unused]] constexpr const SunIO* sio = nullptr;
+#include "srt_radiance_body.inc"
+}
+
+// srt_trace_radiance with SRT_RADIANCE_SUN_SAMPLING (srt_sun_sampling.hip.h): the frame is a kernel argument of its own; the work
+// sums are always kept and flushed when the launch has the record
+template <bool SCENE_LDS, bool MESH>
+__global__ void __launch_bounds__(WG_THREADS) radiance_sun_kernel(const KernelParams P, const RadianceIO io, const SunIO sun_io) {
+    constexpr bool TAIL = false, SUN = true, COUNT = true;
+    [[maybe_unused]] constexpr const ProbeTailIO* tio = nullptr;
+    const SunIO* const sio = &sun_io;
 #include "srt_radiance_body.inc"
 }
 

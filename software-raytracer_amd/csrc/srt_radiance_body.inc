@@ -1,5 +1,6 @@
-    // srt_radiance_body.inc — the text of radiance_kernel and radiance_tail_kernel (srt_radiance.hip.h includes it into both and
-    // says why).  Reads the kernel's P and io, its template parameters, and TAIL, COUNT and tio as the including function has them.
+    // srt_radiance_body.inc — the text of radiance_kernel, radiance_tail_kernel and radiance_sun_kernel (srt_radiance.hip.h includes
+    // it into all three and says why).  Reads the kernel's P and io, its template parameters, and TAIL, SUN, COUNT, tio and sio as the
+    // including function has them.
     extern __shared__ float4 lds_scene[];
     stage_scene<SCENE_LDS>(P, lds_scene);
     constexpr int WAVES = WG_TILES_X * WG_TILES_Y;
@@ -9,8 +10,12 @@
     Prof prof{};
 #endif
     Tally<false> no_tally;
-    std::conditional_t<TAIL, TailWaveWork<RAD_WORK_N>, WaveWork<COUNT, RAD_WORK_N>> W;
+    // (named through a template parameter: the type is dependent in every including kernel, so the branches of the modes a kernel
+    // does not have are discarded without being checked against its Work)
+    using WorkOfMode = std::conditional_t<SUN, SunWaveWork<RAD_WORK_N>, std::conditional_t<TAIL, TailWaveWork<RAD_WORK_N>, WaveWork<COUNT, RAD_WORK_N>>>;
+    std::conditional_t<SCENE_LDS, WorkOfMode, WorkOfMode> W;
     if constexpr (TAIL) W.tail.io = tio;
+    if constexpr (SUN) W.sun = sio;
     float4* const rows = wave_sample_rows(io.rows, wave);
     const uint32_t n = P.sample_count;
     const int B = P.max_bounces;

@@ -31,6 +31,7 @@
 
 #include "srt_kernel.hip.h"
 #include "srt_probe_tail.hip.h"
+#include "srt_sun_sampling.hip.h"
 
 namespace srt {
 
@@ -64,13 +65,13 @@ __device__ __forceinline__ void stage_scene(const KernelParams& P, float4* lds_s
 // (lane k adds counter k).  Without ON there is no atomic.
 template <bool ON, int N>
 struct WaveWork {
-    static constexpr bool TAIL = false;
+    static constexpr bool TAIL = false, SUN = false;
     __device__ __forceinline__ void add(int, unsigned long long) {}
     __device__ __forceinline__ void flush(unsigned long long*, int) const {}
 };
 template <int N>
 struct WaveWork<true, N> {
-    static constexpr bool TAIL = false;
+    static constexpr bool TAIL = false, SUN = false;
     unsigned long long n[N] = {};
     __device__ __forceinline__ void add(int i, unsigned long long v) { n[i] += v; }
     __device__ __forceinline__ void flush(unsigned long long* work, int lane) const {
@@ -90,6 +91,17 @@ struct TailWaveWork : WaveWork<true, N> {
     __device__ __forceinline__ void flush(unsigned long long* work, int lane) const {
         if (work) WaveWork<true, N>::flush(work, lane);
         tail.flush(lane);
+    }
+};
+
+// the work counts of a SUN instantiation (srt_sun_sampling.hip.h): run_sample_pool samples the sun at every diffuse vertex when its
+// Work says SUN, and finds the frame here.  The sums are always kept and flushed when the launch has the record.
+template <int N>
+struct SunWaveWork : WaveWork<true, N> {
+    static constexpr bool SUN = true;
+    const SunIO* sun = nullptr;
+    __device__ __forceinline__ void flush(unsigned long long* work, int lane) const {
+        if (work) WaveWork<true, N>::flush(work, lane);
     }
 };
 
@@ -254,11 +266,13 @@ __device__ __forceinline__ V3 pool_bounce(const Lds& S, bool busy, PoolLane& t) 
 }
 
 // ---- what the bounce's ray met (Raytracer.cpp:178-184), for a busy lane.  True when the path has ended; `atag` is then the
-// sample's alpha: NaN only from the environment (T's alpha is +0)
-__device__ __forceinline__ bool pool_hit_update(const Lds& S, const Hit& h, int B, PoolLane& t, uint32_t& atag) {
+// sample's alpha: NaN only from the environment (T's alpha is +0).  E0: a lane with `no_sun` — its bounce was blind and the sun has
+// been sampled for it (rule S7) — meets the environment without the sun.
+template <bool E0 = false>
+__device__ __forceinline__ bool pool_hit_update(const Lds& S, const Hit& h, int B, PoolLane& t, uint32_t& atag, [[maybe_unused]] bool no_sun = false) {
     bool end_path;
     if (h.prim < 0) {  // :178-181
-        const RGB e = environment(S, t.sray);
+        const RGB e = environment<E0>(S, t.sray, no_sun);
         t.L = RGB{t.L.r + e.r * t.T.r, t.L.g + e.g * t.T.g, t.L.b + e.b * t.T.b};  // (NN)
         atag = alpha_tag(environment_alpha(t.sray));
         end_path = true;
@@ -310,6 +324,7 @@ __device__ __forceinline__ void pool_fold_rows(const Src& src, const float4* row
 // `rows` is the wave's region of the scratch, `acc` the owner's running mean.  Every lane of the wave calls it.
 // A Work with TAIL (TailWaveWork) ends a path that reaches the bounce limit on a surface in the probe grid (srt_probe_tail.hip.h);
 // the tail travels inside the Work, not as a parameter, so that the other instantiations compile to what they did.
+// A Work with SUN (SunWaveWork) samples the sun at every diffuse vertex (srt_sun_sampling.hip.h), by the same scheme.
 template <bool MESH, bool SCENE_LDS, class Src, class Work>
 __device__ __forceinline__ void run_sample_pool(const Lds& S, const KernelParams& P, const Src& src, float4* rows, int lane, float4& acc, Work& W SRT_PROF_PARAM) {
     unsigned* const match = reinterpret_cast<unsigned*>(S.work);
@@ -332,6 +347,11 @@ __device__ __forceinline__ void run_sample_pool(const Lds& S, const KernelParams
             if (fresh) pool_start_sample(S, src, t);
             W.add(Src::CLOSEST, wave_lanes(fresh));  // the sample's primary GetClosestObject call (:142)
             const V3 o = pool_bounce(S, busy, t);
+            [[maybe_unused]] bool diffuse = false;  // SUN: this lane's bounce was blind (rule S2); kept across closest_hit for S7
+            if constexpr (Work::SUN) {  // rules S3 - S6 in wave-uniform control flow, before the bounce's own result is added
+                diffuse = busy && (S.mat(t.hprim, 0).x * t.spec) == 0.0f;  // tt of :175, as pool_bounce computed it
+                W.add(Src::WAVE_CALLS, sun_sample<MESH, SCENE_LDS>(S, P, *W.sun, diffuse, t.rng, o, t.hn, t.T, t.L));
+            }
             // the scan runs in wave-uniform control flow: idle lanes help with other lanes' rays
             const Hit h = closest_hit<MESH, false, SCENE_LDS>(S, P, o, t.sray, busy, 1, deferred, no_tally SRT_PROF_ARG);
             W.add(Src::WAVE_CALLS, 1ull);
@@ -351,7 +371,7 @@ __device__ __forceinline__ void run_sample_pool(const Lds& S, const KernelParams
                 }
             } else if (busy) {
                 uint32_t atag = 0u;
-                if (pool_hit_update(S, h, B, t, atag)) {
+                if (pool_hit_update<Work::SUN>(S, h, B, t, atag, diffuse)) {
                     pool_store_row(rows, c0, atag, t);
                     busy = false;
                 }

@@ -162,7 +162,10 @@ class PathTraceRenderer {
     // Radiance queries (srt_write_rays + srt_trace_radiance): the running mean of params.sample_count path-traced samples along
     // each of `count` caller-supplied rays — what Render leaves in the accumulator for a pixel, without a camera.  Asynchronous
     // once the rays are copied; readRadiance waits and copies the `count` float4 of the last traceRadiance; radianceWork waits and
-    // returns the work counts of a trace that had SRT_RADIANCE_COUNT_WORK.
+    // returns the work counts of a trace that had SRT_RADIANCE_COUNT_WORK.  params.flags | SRT_RADIANCE_SUN_SAMPLING (and
+    // SRT_LIGHT_PROBE_SUN_SAMPLING for traceLightProbes / traceLightProbesListed below): one shadow segment towards the sun at every
+    // diffuse bounce, the sun taken out of that bounce (rules S1 - S9 of srt_pathtrace.h) — the same mean, far less noise in
+    // sunlit scenes; throws (SRT_ERR_STATE) while the probe tail is on or when sun_direction is not a unit vector.
     void traceRadiance(const float* origins, const float* directions, size_t count, const srt_radiance_params& params);
     void readRadiance(float* dst_rgba);
     srt_radiance_work radianceWork();
