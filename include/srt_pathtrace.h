@@ -1168,6 +1168,7 @@ int srt_get_radiance_work(srt_context* ctx, srt_radiance_work* out);
  * A and B are seeded differently throughout. */
 #define SRT_ADAPTIVE_KEEP_COUNTS 1u /* do not write the counts back */
 #define SRT_ADAPTIVE_COUNT_WORK 2u  /* fill srt_adaptive_work for this call */
+#define SRT_ADAPTIVE_SUN_SAMPLING 0x10u /* 16: sun sampling at diffuse bounces, rules AS1 - AS8 at the end of this file (4 and 8 are unassigned and refused) */
 #define SRT_BUDGET_ALBEDO 1u        /* the luminance of the demodulated colour: must agree with the variance buffer */
 
 typedef struct srt_adaptive_params { /* 28 bytes */
@@ -2350,7 +2351,52 @@ int srt_shade_probe_grid_depth(srt_context* ctx, const srt_probe_grid_params* pa
  *     fixed-order projection of that RADIANCE, and the listed call writes at the listed probes what the unlisted call writes.
  * S9. Work.  Under the flag wave_calls of srt_radiance_work (and of srt_light_probe_work) additionally counts one for every
  *     wave-level any-hit invocation; closest_calls is unchanged.  The number of sun segments is not reported.
- * srt_render, srt_render_adaptive[_tail] and the probe tail do not take the flag. */
+ * srt_render does not take the flag, and srt_trace_radiance and the light-probe traces refuse it under the probe-tail mode;
+ * srt_render_adaptive and srt_render_adaptive_tail take it as SRT_ADAPTIVE_SUN_SAMPLING, the latter together with the probe tail:
+ * the next block. */
+
+/* ---- sun sampling in adaptive renders (ABI 7, backward compatible) ---------------------------------------------------------------
+ * One flag bit, value 16, on srt_adaptive_params.flags: SRT_ADAPTIVE_SUN_SAMPLING, defined next to the two adaptive flags (written
+ * 0x10u for the reason given above), accepted by srt_render_adaptive and srt_render_adaptive_tail.  No entry point, no exported
+ * symbol, no struct, so SRT_ABI_VERSION stays 7; without the flag both calls launch the kernel they launched before.  Bits 4 and
+ * 8 stay unassigned and refused with SRT_ERR_INVALID_ARG.  It is sun sampling (rules S1 - S9 above) for pictures: per-pixel counts,
+ * budgets, a framebuffer — and, in srt_render_adaptive_tail, the one-bounce frame that ends in the probe grid.
+ *
+ * AS1. srt_render_adaptive with the flag.  Adaptive rules 1 - 10 hold unchanged.  Every sample's path follows S1 - S9 with id = the
+ *      pixel index x + y*W and f = the sample's frame.  Only the colour changes: the draws, the directions, the GetClosestObject
+ *      calls and the fold are untouched.  The call ignores the context's probe-tail mode, as before: the tail-mode refusal of S5
+ *      does not apply to it.
+ * AS2. Equivalence.  After the call, pixel p's accumulator element equals element p of srt_trace_radiance with
+ *      SRT_RADIANCE_SUN_SAMPLING on the frame's camera rays — ray index x + y*W, id_base 0, the same seed and bounces,
+ *      first_sample = n_p + 1, sample_count = e_p — continuing from the element the pixel held by radiance's continuation rule, or
+ *      with SRT_RADIANCE_RESET when n_p = 0; in all four lanes, NaN as NaN.  The framebuffer pixel is its tone map at the memory
+ *      row of adaptive rule 3.
+ * AS3. Mixing is allowed.  Samples with the flag and samples without it estimate the same quantity and may share one mean: a pixel
+ *      that took frames 1..n without the flag (srt_render or srt_render_adaptive) and n+1..n+e with it holds the running mean in
+ *      frame order, each frame computed under its own call's flag.  (R3 forbids such mixing for the tail: a path that ends in the
+ *      probe grid estimates a different quantity from one that does not.  The sun flag only changes how the same quantity is
+ *      estimated.)
+ * AS4. srt_render_adaptive_tail with the flag: the combination, built for pictures only.  R1 - R7 hold.  Every sample's path
+ *      follows S1 - S4 and S6 - S9, and T1 - T6.  A vertex from which a bounce is taken gets its sun segment, as without the tail.
+ *      The vertex at which the path reaches the bounce limit takes no bounce, so it gets no segment; it gets the lookup of T1 - T6,
+ *      unchanged.  The bounce that led to that vertex — like every bounce — met the environment under its own vertex's no_sun
+ *      (S7) had it left the scene.  The expectation is that of the same call without the flag.  srt_trace_radiance and the
+ *      light-probe traces keep refusing the flag under the mode, so R3's equivalence has no radiance counterpart under AS4.
+ * AS5. Order of checks.  srt_render_adaptive: first the call's own errors in their order (rule 9), evaluated with the bit masked
+ *      off; then S5's direction test: SRT_ERR_STATE when a component of s is not finite or its squared length lies outside
+ *      [0.9999, 1.0001].  srt_render_adaptive_tail: all of R1 first, the direction test last.  The direction test runs whenever the
+ *      bit is set, also with max_bounces == 0, as in srt_trace_radiance.  Nothing is touched on a refusal.
+ * AS6. max_bounces == 0.  An accepted call launches exactly what it launches without the flag: srt_render_adaptive's kernel, also
+ *      for the tail call (R2).
+ * AS7. Invariants.  With SunColor = (0, 0, 0) the accumulator, the framebuffer and the counts are bit for bit those without the
+ *      flag.  In a scene without a diffuse vertex those buffers and srt_adaptive_work are those without the flag.  Adaptive rules
+ *      4 - 8 hold under the flag (untouched pixels, counts and KEEP_COUNTS, determinism, the rest).  R4 holds with the flag on both
+ *      sides: zero coefficients give srt_render_adaptive's buffers.
+ * AS8. Work.  Under the flag srt_adaptive_work.wave_calls additionally counts one for every wave-level any-hit invocation;
+ *      pixels, samples and closest_calls are unchanged.  The count is deterministic: a tile's pool drains before its wave draws
+ *      the next ticket.  srt_probe_tail_work is unchanged by the flag.
+ * Not built: the flag in srt_render, the combination in srt_trace_radiance and the light-probe traces, a sun segment at the path's
+ * last vertex, emissive objects, glossy vertices. */
 
 #ifdef __cplusplus
 }

@@ -74,6 +74,7 @@ PROBE_CASCADE_NORMAL_WEIGHT, PROBE_CASCADE_DEPTH, PROBE_CASCADE_STATES, PROBE_CA
 PROBE_CASCADE_COEFFICIENTS, PROBE_CASCADE_MOMENTS, PROBE_CASCADE_RECORDS = 1, 2, 4
 # adaptive sampling (srt_render_adaptive, srt_sample_budget): the flags, the limits of max_samples / max_budget, the last frame
 ADAPTIVE_KEEP_COUNTS, ADAPTIVE_COUNT_WORK = 1, 2
+ADAPTIVE_SUN_SAMPLING = 16  # SRT_ADAPTIVE_SUN_SAMPLING: sun sampling in render_adaptive[_tail] (rules AS1 - AS8); 4 and 8 are unassigned
 ADAPTIVE_MAX_SAMPLES = 4096
 ADAPTIVE_FRAME_LIMIT = 2147483646
 BUDGET_ALBEDO = 1
@@ -1549,21 +1550,27 @@ class PathTracer:
         self._ck(self.L.srt_get_budget_total(self._h, C.byref(t)))
         return int(t.value)
 
-    def render_adaptive(self, bounces=None, seed=0, max_samples=None, rows=None, keep_counts=False, count_work=False, flags=0, reserved=0, tail=False):
+    def render_adaptive(self, bounces=None, seed=0, max_samples=None, rows=None, keep_counts=False, count_work=False, flags=0, reserved=0, tail=False,
+                        sun_sampling=False):
         """srt_render_adaptive: every pixel of memory rows `rows` (default: the whole frame) takes min(budget, max_samples) more
         samples, continuing its running mean from its count; the counts advance unless keep_counts.  Arguments left at None take
-        srt_adaptive_params_default.  Asynchronous, like render().  (`tail` is render_adaptive_tail()'s switch.)"""
+        srt_adaptive_params_default.  Asynchronous, like render().  (`tail` is render_adaptive_tail()'s switch.)
+        sun_sampling: SRT_ADAPTIVE_SUN_SAMPLING — trace_radiance's sun sampling for every sample of the call (rules AS1 - AS8);
+        samples with and without it may share a pixel's mean."""
         p = self._default(AdaptiveParams, self.L.srt_adaptive_params_default)
         p.row_begin, p.row_end = self._band(rows)
         _set(p, max_bounces=bounces, max_samples=max_samples, seed=int(seed) & 0xFFFFFFFF, reserved=reserved,
-             flags=int(flags) | (ADAPTIVE_KEEP_COUNTS if keep_counts else 0) | (ADAPTIVE_COUNT_WORK if count_work else 0))
+             flags=int(flags) | (ADAPTIVE_KEEP_COUNTS if keep_counts else 0) | (ADAPTIVE_COUNT_WORK if count_work else 0) |
+             (ADAPTIVE_SUN_SAMPLING if sun_sampling else 0))
         self._ck((self.L.srt_render_adaptive_tail if tail else self.L.srt_render_adaptive)(self._h, C.byref(p)))
 
-    def render_adaptive_tail(self, bounces=None, seed=0, max_samples=None, rows=None, keep_counts=False, count_work=False, flags=0, reserved=0):
+    def render_adaptive_tail(self, bounces=None, seed=0, max_samples=None, rows=None, keep_counts=False, count_work=False, flags=0, reserved=0,
+                             sun_sampling=False):
         """srt_render_adaptive_tail: render_adaptive() whose paths end in the probe grid under the probe_tail() setting (which must
         be on), reading the grid, coefficients, depth maps and states as they stand now.  A tail frame starts from
-        set_sample_counts(0); adaptive_work() and probe_tail_work() report it."""
-        self.render_adaptive(bounces, seed, max_samples, rows, keep_counts, count_work, flags, reserved, tail=True)
+        set_sample_counts(0); adaptive_work() and probe_tail_work() report it.  sun_sampling: every vertex a bounce is taken
+        from gets its sun segment, the vertex at the bounce limit its lookup (rule AS4)."""
+        self.render_adaptive(bounces, seed, max_samples, rows, keep_counts, count_work, flags, reserved, tail=True, sun_sampling=sun_sampling)
 
     def adaptive_work(self):
         """srt_get_adaptive_work: the work counts of the last render_adaptive(count_work=True) as a dict.  Waits."""

@@ -95,13 +95,15 @@ struct PixelSamples {
 };
 
 // LDS: the path-trace kernel's layout (make_lds with four waves), as radiance_kernel.
-// The kernel's text is srt_adaptive_body.inc, included by the two kernels that run it, as srt_radiance.hip.h does and for its reason:
-// the tail's inputs are a kernel argument of their own, given only to the TAIL kernel, and adaptive_kernel keeps the instructions
-// it had.  The text reads P, io and the names TAIL, COUNT and tio of the function it stands in.
+// The kernel's text is srt_adaptive_body.inc, included by the four kernels that run it, as srt_radiance.hip.h does and for its reason:
+// the tail's inputs and the sun's frame are kernel arguments of their own, given only to the kernels that use them, and
+// adaptive_kernel keeps the instructions it had.  The text reads P, io and the names TAIL, SUN, COUNT, tio
+// and sio of the function it stands in.
 template <bool SCENE_LDS, bool MESH, bool COUNT>
 __global__ void __launch_bounds__(WG_THREADS) adaptive_kernel(const KernelParams P, const AdaptiveIO io) {
-    constexpr bool TAIL = false;
+    constexpr bool TAIL = false, SUN = false;
     [[maybe_unused]] constexpr const ProbeTailIO* tio = nullptr;
+    [[maybe_unused]] constexpr const SunIO* sio = nullptr;
 #include "srt_adaptive_body.inc"
 }
 
@@ -110,8 +112,30 @@ __global__ void __launch_bounds__(WG_THREADS) adaptive_kernel(const KernelParams
 // A tile's pool drains before the wave draws its next ticket, so the lookups a wave makes depend only on the tile.
 template <bool SCENE_LDS, bool MESH>
 __global__ void __launch_bounds__(WG_THREADS) adaptive_tail_kernel(const KernelParams P, const AdaptiveIO io, const ProbeTailIO tail_io) {
-    constexpr bool TAIL = true, COUNT = true;
+    constexpr bool TAIL = true, SUN = false, COUNT = true;
     const ProbeTailIO* const tio = &tail_io;
+    [[maybe_unused]] constexpr const SunIO* sio = nullptr;
+#include "srt_adaptive_body.inc"
+}
+
+// srt_render_adaptive with SRT_ADAPTIVE_SUN_SAMPLING (srt_sun_sampling.hip.h, rules AS1 - AS3): the frame is a kernel argument of
+// its own; the work sums are always kept and flushed when the launch has the record.  The segment's any_hit runs between two
+// closest_hit calls on S.res and S.meshq; the first-hit records in S.pix, word 11 (the slot's first frame) among them, are not its.
+template <bool SCENE_LDS, bool MESH>
+__global__ void __launch_bounds__(WG_THREADS) adaptive_sun_kernel(const KernelParams P, const AdaptiveIO io, const SunIO sun_io) {
+    constexpr bool TAIL = false, SUN = true, COUNT = true;
+    [[maybe_unused]] constexpr const ProbeTailIO* tio = nullptr;
+    const SunIO* const sio = &sun_io;
+#include "srt_adaptive_body.inc"
+}
+
+// srt_render_adaptive_tail with the flag (rule AS4): every vertex a bounce is taken from gets its segment, the vertex at the
+// bounce limit gets the lookup, and the hit that ends the path is read under the bounce's no_sun
+template <bool SCENE_LDS, bool MESH>
+__global__ void __launch_bounds__(WG_THREADS) adaptive_tail_sun_kernel(const KernelParams P, const AdaptiveIO io, const ProbeTailIO tail_io, const SunIO sun_io) {
+    constexpr bool TAIL = true, SUN = true, COUNT = true;
+    const ProbeTailIO* const tio = &tail_io;
+    const SunIO* const sio = &sun_io;
 #include "srt_adaptive_body.inc"
 }
 

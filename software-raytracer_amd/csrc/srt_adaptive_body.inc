@@ -1,5 +1,6 @@
-    // srt_adaptive_body.inc — the text of adaptive_kernel and adaptive_tail_kernel (srt_adaptive.hip.h includes it into both and
-    // says why).  Reads the kernel's P and io, its template parameters, and TAIL, COUNT and tio as the including function has them.
+    // srt_adaptive_body.inc — the text of adaptive_kernel, adaptive_tail_kernel, adaptive_sun_kernel and adaptive_tail_sun_kernel
+    // (srt_adaptive.hip.h includes it into all four and says why).  Reads the kernel's P and io, its template parameters, and TAIL,
+    // SUN, COUNT, tio and sio as the including function has them.
     extern __shared__ float4 lds_scene[];
     stage_scene<SCENE_LDS>(P, lds_scene);
     constexpr int WAVES = WG_TILES_X * WG_TILES_Y;
@@ -9,8 +10,13 @@
     Prof prof{};
 #endif
     Tally<false> no_tally;
-    std::conditional_t<TAIL, TailWaveWork<ADP_WORK_N>, WaveWork<COUNT, ADP_WORK_N>> Wk;
+    // (named through a template parameter: the type is dependent in every including kernel, so the branches of the modes a kernel
+    // does not have are discarded without being checked against its Work)
+    using WorkOfMode = std::conditional_t<SUN, std::conditional_t<TAIL, TailSunWaveWork<ADP_WORK_N>, SunWaveWork<ADP_WORK_N>>,
+                                          std::conditional_t<TAIL, TailWaveWork<ADP_WORK_N>, WaveWork<COUNT, ADP_WORK_N>>>;
+    std::conditional_t<SCENE_LDS, WorkOfMode, WorkOfMode> Wk;
     if constexpr (TAIL) Wk.tail.io = tio;
+    if constexpr (SUN) Wk.sun = sio;
     float4* const rows = wave_sample_rows(io.rows, wave);
     const int B = P.max_bounces;
     const int W = P.width, H = P.height;

@@ -61,6 +61,7 @@
 #include "srt_adaptive.hip.h"
 #include "srt_adaptive_host.h"
 #include "srt_adaptive_tail_host.h"
+#include "srt_adaptive_sun_host.h"
 #include "srt_launch_shape.h"
 #include "srt_scene_image.h"
 #include "srt_mesh_bvh.h"
@@ -1224,6 +1225,14 @@ template <class IO>
 static int launch_persistent_sun(srt_context* ctx, void (*kernel)(srt::KernelParams, IO, srt::SunIO), unsigned wgs, const KernelSetup& ks,
                                  const srt::KernelParams& K, const IO& io, const srt::SunIO& sio) {
     hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io, sio);
+    SRT_HIP(ctx, hipGetLastError());
+    return SRT_OK;
+}
+// ... of an instantiation with both (srt_render_adaptive_tail with SRT_ADAPTIVE_SUN_SAMPLING): two arguments of their own
+template <class IO>
+static int launch_persistent_tail_sun(srt_context* ctx, void (*kernel)(srt::KernelParams, IO, srt::ProbeTailIO, srt::SunIO), unsigned wgs, const KernelSetup& ks,
+                                      const srt::KernelParams& K, const IO& io, const srt::ProbeTailIO& tio, const srt::SunIO& sio) {
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(srt::WG_THREADS), ks.lds_bytes, ctx->stream, K, io, tio, sio);
     SRT_HIP(ctx, hipGetLastError());
     return SRT_OK;
 }
@@ -3310,6 +3319,7 @@ int srt_get_probe_cascade_work(srt_context* ctx, srt_probe_cascade_work* out) {
 
 // ---- adaptive sampling ---------------------------------------------------------------------------------------------
 static_assert(SRT_ADAPTIVE_KEEP_COUNTS == srt::ADAPTIVE_FLAG_KEEP_COUNTS && SRT_ADAPTIVE_COUNT_WORK == srt::ADAPTIVE_FLAG_COUNT_WORK &&
+              SRT_ADAPTIVE_SUN_SAMPLING == srt::ADAPTIVE_FLAG_SUN_SAMPLING && !(srt::ADAPTIVE_FLAG_ALL & srt::ADAPTIVE_FLAG_SUN_SAMPLING) &&
               SRT_BUDGET_ALBEDO == srt::BUDGET_FLAG_ALBEDO && sizeof(srt_adaptive_params) == 28 && sizeof(srt::AdaptiveCall) == 28 &&
               sizeof(srt_budget_params) == 16 && sizeof(srt::BudgetCall) == 16 && sizeof(srt_adaptive_work) == 40 &&
               srt::ADP_FRAME_LIMIT == srt::ADAPTIVE_FRAME_LIMIT && (int)srt::ADP_WORK_N == (int)srt::RAD_WORK_N,
@@ -3381,9 +3391,10 @@ int srt_adaptive_params_default(srt_adaptive_params* out) {
     return SRT_OK;
 }
 
-// The launch of srt_render_adaptive and srt_render_adaptive_tail once the call is accepted: `tail` picks adaptive_tail_kernel
-// and gives it the tail's inputs as they stand now; without it the launch is srt_render_adaptive's.
-static int launch_adaptive(srt_context* ctx, const srt_adaptive_params* a, uint32_t* counts, const uint32_t* budget, bool tail) {
+// The launch of srt_render_adaptive and srt_render_adaptive_tail once the call is accepted: `choice` (srt_adaptive_sun_host.h)
+// picks one of the four adaptive kernels; a TAIL kernel gets the tail's inputs as they stand now, a SUN kernel the frame of the
+// environment as it stands now.  ADAPTIVE_KERNEL_PLAIN is srt_render_adaptive's launch without the flag.
+static int launch_adaptive(srt_context* ctx, const srt_adaptive_params* a, uint32_t* counts, const uint32_t* budget, srt::AdaptiveKernelChoice choice) {
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     const bool count = (a->flags & SRT_ADAPTIVE_COUNT_WORK) != 0;
     srt::KernelParams K;
@@ -3393,9 +3404,14 @@ static int launch_adaptive(srt_context* ctx, const srt_adaptive_params* a, uint3
     K.accumulator = ctx->d_acc, K.framebuffer = ctx->d_fb;
     const auto kernel = SRT_KERNEL(srt::adaptive_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0, count);
     const auto tail_kernel = SRT_KERNEL(srt::adaptive_tail_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0);
-    // the grid first: the sample scratch is sized by it
-    const unsigned wgs = srt::adaptive_grid(K.width, K.rows, srt::OUT_WG_UNITS,
-                                            resident_workgroups(ctx, tail ? (const void*)tail_kernel : (const void*)kernel, ks.lds_bytes));
+    const auto sun_kernel = SRT_KERNEL(srt::adaptive_sun_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0);
+    const auto tail_sun_kernel = SRT_KERNEL(srt::adaptive_tail_sun_kernel, ctx->scene_in_lds[ks.img], K.n_tris > 0);
+    // the grid first, by the kernel that runs: the sample scratch is sized by it
+    const void* const runs = choice == srt::ADAPTIVE_KERNEL_TAIL_SUN ? (const void*)tail_sun_kernel
+                             : choice == srt::ADAPTIVE_KERNEL_SUN    ? (const void*)sun_kernel
+                             : choice == srt::ADAPTIVE_KERNEL_TAIL   ? (const void*)tail_kernel
+                                                                     : (const void*)kernel;
+    const unsigned wgs = srt::adaptive_grid(K.width, K.rows, srt::OUT_WG_UNITS, resident_workgroups(ctx, runs, ks.lds_bytes));
     if (const int rc = ensure_sample_rows(ctx, wgs)) return rc;
     if (!ctx->d_adaptive_ticket) SRT_HIP(ctx, ctx->d_adaptive_ticket.ensure(sizeof(uint32_t)));
     SRT_HIP(ctx, hipMemsetAsync(ctx->d_adaptive_ticket, 0, sizeof(uint32_t), ctx->stream));
@@ -3410,7 +3426,11 @@ static int launch_adaptive(srt_context* ctx, const srt_adaptive_params* a, uint3
     io.ticket = ctx->d_adaptive_ticket;
     io.rows = ctx->d_radiance_rows;
     io.work = count ? (unsigned long long*)ctx->d_adaptive_work : nullptr;
-    if (const int rc = tail ? launch_persistent_tail(ctx, tail_kernel, wgs, ks, K, io, probe_tail_io(ctx)) : launch_persistent(ctx, kernel, wgs, ks, K, io)) return rc;
+    if (const int rc = choice == srt::ADAPTIVE_KERNEL_TAIL_SUN ? launch_persistent_tail_sun(ctx, tail_sun_kernel, wgs, ks, K, io, probe_tail_io(ctx), sun_io(ctx))
+                       : choice == srt::ADAPTIVE_KERNEL_SUN    ? launch_persistent_sun(ctx, sun_kernel, wgs, ks, K, io, sun_io(ctx))
+                       : choice == srt::ADAPTIVE_KERNEL_TAIL   ? launch_persistent_tail(ctx, tail_kernel, wgs, ks, K, io, probe_tail_io(ctx))
+                                                               : launch_persistent(ctx, kernel, wgs, ks, K, io))
+        return rc;
     if (!io.keep_counts) ctx->counts.wrote(counts);
     return SRT_OK;
 }
@@ -3421,10 +3441,12 @@ int srt_render_adaptive(srt_context* ctx, const srt_adaptive_params* a) {
     uint32_t* const counts = current(ctx->counts, ctx->d_counts_own);
     const uint32_t* const budget = current(ctx->budget, ctx->d_budget_own);
     const char* why = "";
-    if (const srt::RaysStatus rs = srt::adaptive_check(call, ctx->scene_set, ctx->camera.set, ctx->height, counts != nullptr, budget != nullptr, &why))
+    // (AS5: the own errors with the bit taken out, then the sun's direction)
+    if (const srt::RaysStatus rs = srt::sun_adaptive_check(call, ctx->scene_set, ctx->camera.set, ctx->height, counts != nullptr, budget != nullptr,
+                                                           ctx->env.sun_direction, &why))
         return fail(ctx, (int)rs, "srt_render_adaptive: %s (rows [%d,%d) of %d, max_bounces %d, max_samples %u, flags 0x%x, reserved %u)", why, a->row_begin,
                     a->row_end, ctx->height, a->max_bounces, a->max_samples, a->flags, a->reserved);
-    if (const int rc = launch_adaptive(ctx, a, counts, budget, false)) return rc;
+    if (const int rc = launch_adaptive(ctx, a, counts, budget, srt::adaptive_kernel_choice(false, ctx->probe_tail, call))) return rc;
     srt::adaptive_rendered(ctx->adaptive, a->flags);
     return SRT_OK;
 }
@@ -3437,15 +3459,16 @@ int srt_render_adaptive_tail(srt_context* ctx, const srt_adaptive_params* a) {
     uint32_t* const counts = current(ctx->counts, ctx->d_counts_own);
     const uint32_t* const budget = current(ctx->budget, ctx->d_budget_own);
     const char* why = "";
-    if (const srt::RaysStatus rs = srt::adaptive_tail_check(call, ctx->scene_set, ctx->camera.set, ctx->height, counts != nullptr, budget != nullptr, ctx->probe_tail,
-                                                            ctx->probe_grid, ctx->probe_grid_depth, ctx->probe_states,
-                                                            current(ctx->probe_grid.coefficients, ctx->d_probe_grid_coefficients),
-                                                            srt::adaptive_tail_targets(ctx->d_acc, ctx->d_fb, ctx->width, ctx->height), &why))
+    // (AS5: all of R1 with the bit taken out, then the sun's direction)
+    if (const srt::RaysStatus rs = srt::sun_adaptive_tail_check(call, ctx->scene_set, ctx->camera.set, ctx->height, counts != nullptr, budget != nullptr, ctx->probe_tail,
+                                                                ctx->probe_grid, ctx->probe_grid_depth, ctx->probe_states,
+                                                                current(ctx->probe_grid.coefficients, ctx->d_probe_grid_coefficients),
+                                                                srt::adaptive_tail_targets(ctx->d_acc, ctx->d_fb, ctx->width, ctx->height), ctx->env.sun_direction, &why))
         return fail(ctx, (int)rs, "srt_render_adaptive_tail: %s (rows [%d,%d) of %d, max_bounces %d, max_samples %u, flags 0x%x, reserved %u)", why, a->row_begin,
                     a->row_end, ctx->height, a->max_bounces, a->max_samples, a->flags, a->reserved);
     SRT_HIP(ctx, hipSetDevice(ctx->device));
     if (const int rc = zero_probe_tail_work(ctx)) return rc;
-    if (const int rc = launch_adaptive(ctx, a, counts, budget, srt::adaptive_tail_launches_tail(ctx->probe_tail, call))) return rc;
+    if (const int rc = launch_adaptive(ctx, a, counts, budget, srt::adaptive_kernel_choice(true, ctx->probe_tail, call))) return rc;
     srt::adaptive_tail_rendered(ctx->adaptive, ctx->probe_tail, a->flags);
     return SRT_OK;
 }

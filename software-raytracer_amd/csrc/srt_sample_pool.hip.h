@@ -105,6 +105,14 @@ struct SunWaveWork : WaveWork<true, N> {
     }
 };
 
+// the work counts of an instantiation with both (srt_render_adaptive_tail with SRT_ADAPTIVE_SUN_SAMPLING, rule AS4): the tail's
+// kernel argument and sums, and the frame
+template <int N>
+struct TailSunWaveWork : TailWaveWork<N> {
+    static constexpr bool SUN = true;
+    const SunIO* sun = nullptr;
+};
+
 // the number of lanes for which b holds / of set bits of m below this lane
 __device__ __forceinline__ unsigned long long wave_lanes(bool b) { return (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(b)); }
 __device__ __forceinline__ int lanes_below(unsigned long long m) {
@@ -325,6 +333,8 @@ __device__ __forceinline__ void pool_fold_rows(const Src& src, const float4* row
 // A Work with TAIL (TailWaveWork) ends a path that reaches the bounce limit on a surface in the probe grid (srt_probe_tail.hip.h);
 // the tail travels inside the Work, not as a parameter, so that the other instantiations compile to what they did.
 // A Work with SUN (SunWaveWork) samples the sun at every diffuse vertex (srt_sun_sampling.hip.h), by the same scheme.
+// A Work with both (TailSunWaveWork) does both: the segment stands before the bounce's closest_hit and the lookup behind it, so the
+// two never share a moment — any_hit's words in S.res and S.meshq are dead again when the lookup, which uses no LDS, runs.
 template <bool MESH, bool SCENE_LDS, class Src, class Work>
 __device__ __forceinline__ void run_sample_pool(const Lds& S, const KernelParams& P, const Src& src, float4* rows, int lane, float4& acc, Work& W SRT_PROF_PARAM) {
     unsigned* const match = reinterpret_cast<unsigned*>(S.work);
@@ -358,7 +368,7 @@ __device__ __forceinline__ void run_sample_pool(const Lds& S, const KernelParams
             W.add(Src::CLOSEST, wave_lanes(busy));
             if constexpr (Work::TAIL) {  // rules T1 - T6: the lookup runs in wave-uniform control flow, between the hit and the row
                 uint32_t atag = 0u;
-                const bool ended = busy && pool_hit_update(S, h, B, t, atag);
+                const bool ended = busy && pool_hit_update<Work::SUN>(S, h, B, t, atag, diffuse);  // (AS4: the hit the limit is reached at, too)
                 // T1, T2: the limit was reached on a surface; T and spec are that hit's, no draw is consumed
                 const bool term = ended && h.prim >= 0;
                 float g = 0.0f;

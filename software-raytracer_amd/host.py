@@ -7,6 +7,7 @@ import subprocess
 
 import numpy as np
 
+from .capi import ADAPTIVE_SUN_SAMPLING, LIGHT_PROBE_SUN_SAMPLING, RADIANCE_SUN_SAMPLING  # noqa: F401
 from .capi import (REFL_ALL, REFL_COUNT_WORK, REFLECTION, ReflectionParams, ReflectionWork, reflection_outputs, ADAPTIVE_COUNT_WORK, ADAPTIVE_KEEP_COUNTS, BUDGET_ALBEDO, AdaptiveParams, BudgetParams, RADIANCE_COUNT_WORK, RADIANCE_NORMALIZE, RADIANCE_RESET, RadianceParams, RadianceWork, VIS_AO, VIS_COUNT_WORK, VIS_SUN, VISIBILITY, VisibilityParams, VisibilityWork, OCCLUSION_COUNT_WORK, OCCLUSION_NORMALIZE, OcclusionWork, RAY_OUTPUTS, RAYS_ALL, RAYS_NORMALIZE, ray_outputs, DENOISE_FRAMEBUFFER, DENOISE_GUIDES, GBUF_ALBEDO, GBUFFERS, TEMPORAL_GUIDES, UPSAMPLE_GUIDES, AntialiasParams, UpdateInfo, DenoiseParams, Mesh, Object, Stats,
                    TemporalParams, UpsampleParams, antialias_params, denoise_params, gbuffer_outputs, temporal_params, upsample_params)
 from .capi import (LIGHT_PROBE_COEFFICIENTS, LIGHT_PROBE_COEFFS, LIGHT_PROBE_COUNT_WORK, LIGHT_PROBE_NORMALIZE, LIGHT_PROBE_RADIANCE, LIGHT_PROBE_RESET,
@@ -53,7 +54,7 @@ EXPORTS = [
     "srt_host_renderer_render_reflection", "srt_host_renderer_read_reflection", "srt_host_renderer_reflection_work",
     "srt_host_renderer_reflection_guides", "srt_host_renderer_mirror_history",
     "srt_host_renderer_probe_tail", "srt_host_renderer_probe_tail_work",
-    "srt_host_renderer_render_adaptive_tail", "srt_host_renderer_render_probe_tail_frame",
+    "srt_host_renderer_render_adaptive_tail", "srt_host_renderer_render_probe_tail_frame", "srt_host_renderer_sun_sampling",
     "srt_host_renderer_trace_radiance", "srt_host_renderer_read_radiance", "srt_host_renderer_radiance_work",
     "srt_host_renderer_trace_light_probes", "srt_host_renderer_read_light_probe_output", "srt_host_renderer_light_probe_work",
     "srt_host_renderer_set_probe_grid", "srt_host_renderer_shade_probe_grid", "srt_host_renderer_read_probe_grid_output",
@@ -201,6 +202,7 @@ def load_library():
     L.srt_host_renderer_render_adaptive.argtypes = [vp, C.POINTER(AdaptiveParams)]
     L.srt_host_renderer_render_adaptive_tail.argtypes = [vp, C.POINTER(AdaptiveParams)]
     L.srt_host_renderer_render_probe_tail_frame.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32]
+    L.srt_host_renderer_sun_sampling.argtypes = [vp, C.c_int]
     L.srt_host_renderer_set_sample_counts.argtypes = [vp, C.c_uint32]
     L.srt_host_renderer_read_sample_counts.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.srt_host_renderer_adaptive_frame.argtypes = [vp, C.c_uint32, C.c_int, C.POINTER(BudgetParams), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
@@ -478,24 +480,26 @@ class Renderer:
         return self._get_work(OcclusionWork, self.L.srt_host_renderer_occlusion_work)
 
     def trace_radiance(self, origins, directions, samples=16, bounces=8, seed=0, first_sample=1, reset=True, id_base=0, normalize=False,
-                       count_work=False):
+                       count_work=False, sun_sampling=False):
         """PathTraceRenderer::traceRadiance + readRadiance: copy N rays from host arrays (N, 4) float32, trace `samples` path-traced
         samples of `bounces` bounces along each against the renderer's scene (srt_trace_radiance: ray i draws from the stream of
         pixel id_base + i, samples first_sample .. first_sample + samples - 1; reset=False continues the running mean the handle's
-        buffer holds) and return the (N, 4) float32 running means.  Waits."""
+        buffer holds) and return the (N, 4) float32 running means.  sun_sampling: SRT_RADIANCE_SUN_SAMPLING.  Waits."""
         o, d = self._ray_pair("trace_radiance", origins, directions)
         p = RadianceParams(int(first_sample), int(samples), int(bounces), int(seed) & 0xFFFFFFFF, int(id_base) & 0xFFFFFFFF,
-                           (RADIANCE_RESET if reset else 0) | (RADIANCE_NORMALIZE if normalize else 0) | (RADIANCE_COUNT_WORK if count_work else 0))
+                           (RADIANCE_RESET if reset else 0) | (RADIANCE_NORMALIZE if normalize else 0) | (RADIANCE_COUNT_WORK if count_work else 0) |
+                           (RADIANCE_SUN_SAMPLING if sun_sampling else 0))
         f = C.POINTER(C.c_float)
         self._ck(self.L.srt_host_renderer_trace_radiance(self._h, o.ctypes.data_as(f), d.ctypes.data_as(f), o.shape[0], C.byref(p)))
         return self._read(self.L.srt_host_renderer_read_radiance, (o.shape[0], 4), np.float32)
 
     def trace_light_probes(self, positions, directions, samples=16, bounces=8, seed=0, first_sample=1, reset=True, id_base=0, normalize=False,
-                           count_work=False, radiance=False):
+                           count_work=False, radiance=False, sun_sampling=False):
         """PathTraceRenderer::traceLightProbes + readLightProbeOutput: copy P positions and K directions (host arrays (N, 4) float32;
         directions: an int K for light_probe_sphere(K)), trace srt_trace_light_probes against the renderer's scene and return the
         (P, 9, 4) float32 SH coefficients; light_probe_radiance() then returns the (P, K, 4) running means when radiance=True.
-        reset=False continues the means of the handle's RADIANCE buffer (needs radiance=True).  Waits."""
+        reset=False continues the means of the handle's RADIANCE buffer (needs radiance=True).  sun_sampling:
+        SRT_LIGHT_PROBE_SUN_SAMPLING.  Waits."""
         if isinstance(directions, (int, np.integer)):
             directions = light_probe_sphere(int(directions))
         o = np.ascontiguousarray(positions, dtype=np.float32)
@@ -504,7 +508,8 @@ class Renderer:
             raise ValueError("trace_light_probes: positions %s and directions %s, want (P, 4) and (K, 4) arrays" % (o.shape, d.shape))
         p = LightProbeParams(int(first_sample), int(samples), int(bounces), int(seed) & 0xFFFFFFFF, int(id_base) & 0xFFFFFFFF,
                              (LIGHT_PROBE_RESET if reset else 0) | (LIGHT_PROBE_NORMALIZE if normalize else 0) |
-                             (LIGHT_PROBE_COUNT_WORK if count_work else 0), LIGHT_PROBE_COEFFICIENTS | (LIGHT_PROBE_RADIANCE if radiance else 0), 0)
+                             (LIGHT_PROBE_COUNT_WORK if count_work else 0) | (LIGHT_PROBE_SUN_SAMPLING if sun_sampling else 0),
+                             LIGHT_PROBE_COEFFICIENTS | (LIGHT_PROBE_RADIANCE if radiance else 0), 0)
         f = C.POINTER(C.c_float)
         self._ck(self.L.srt_host_renderer_trace_light_probes(self._h, o.ctypes.data_as(f), o.shape[0], d.ctypes.data_as(f), d.shape[0], C.byref(p)))
         self._probes_traced = (o.shape[0], d.shape[0])
@@ -828,21 +833,44 @@ class Renderer:
         self._ck(self.L.srt_host_renderer_sample_budget(self._h, C.byref(self._budget_params(threshold, floor, max_budget, albedo)), C.byref(t)))
         return int(t.value)
 
-    def render_adaptive(self, bounces=8, seed=0, max_samples=4096, rows=None, keep_counts=False, count_work=False, tail=False):
-        """PathTraceRenderer::renderAdaptive: srt_render_adaptive with the renderer's scene and camera (rows=None: its own band)."""
+    def render_adaptive(self, bounces=8, seed=0, max_samples=4096, rows=None, keep_counts=False, count_work=False, tail=False, sun_sampling=False):
+        """PathTraceRenderer::renderAdaptive: srt_render_adaptive with the renderer's scene and camera (rows=None: its own band).
+        sun_sampling: SRT_ADAPTIVE_SUN_SAMPLING in the struct's flags (the call passes the caller's flags through; the renderer's
+        sun_sampling() setting is not read here)."""
         rb, re = rows if rows is not None else (0, 0)
         p = AdaptiveParams(int(rb), int(re), int(bounces), int(seed) & 0xFFFFFFFF, int(max_samples),
-                           (ADAPTIVE_KEEP_COUNTS if keep_counts else 0) | (ADAPTIVE_COUNT_WORK if count_work else 0), 0)
+                           (ADAPTIVE_KEEP_COUNTS if keep_counts else 0) | (ADAPTIVE_COUNT_WORK if count_work else 0) |
+                           (ADAPTIVE_SUN_SAMPLING if sun_sampling else 0), 0)
         self._ck((self.L.srt_host_renderer_render_adaptive_tail if tail else self.L.srt_host_renderer_render_adaptive)(self._h, C.byref(p)))
 
-    def render_adaptive_tail(self, bounces=8, seed=0, max_samples=4096, rows=None, keep_counts=False, count_work=False):
+    def render_adaptive_tail(self, bounces=8, seed=0, max_samples=4096, rows=None, keep_counts=False, count_work=False, sun_sampling=False):
         """PathTraceRenderer::renderAdaptiveTail: srt_render_adaptive_tail with the renderer's scene and camera, under probe_tail()."""
-        self.render_adaptive(bounces, seed, max_samples, rows, keep_counts, count_work, tail=True)
+        self.render_adaptive(bounces, seed, max_samples, rows, keep_counts, count_work, tail=True, sun_sampling=sun_sampling)
 
-    def render_probe_tail_frame(self, spp, bounces=1, seed=0):
+    def sun_sampling(self, on=True):
+        """PathTraceRenderer::sunSampling: with `on`, every adaptive render that render_adaptive_frame() and
+        render_probe_tail_frame() issue carries SRT_ADAPTIVE_SUN_SAMPLING.  Off by default; no other call reads it."""
+        self._ck(self.L.srt_host_renderer_sun_sampling(self._h, 1 if on else 0))
+        self._sun_sampling = bool(on)
+
+    def _frame_sun_sampling(self, sun_sampling, frame):
+        """Run frame() with the renderer's sun_sampling() setting on if `sun_sampling`, and as it stands otherwise; the setting is
+        what it was afterwards."""
+        was = getattr(self, "_sun_sampling", False)
+        if not sun_sampling or was:
+            return frame()
+        self.sun_sampling(True)
+        try:
+            return frame()
+        finally:
+            self.sun_sampling(False)
+
+    def render_probe_tail_frame(self, spp, bounces=1, seed=0, sun_sampling=False):
         """PathTraceRenderer::renderProbeTailFrame: one whole frame of `spp` samples per pixel from n = 0 whose paths end in the
-        probe grid under probe_tail(); the frame is left in the accumulator and the framebuffer."""
-        self._ck(self.L.srt_host_renderer_render_probe_tail_frame(self._h, int(spp), int(bounces), int(seed) & 0xFFFFFFFF))
+        probe grid under probe_tail(); the frame is left in the accumulator and the framebuffer.  sun_sampling=True: with the
+        sun_sampling() setting on for this frame (False: as the setting stands)."""
+        self._frame_sun_sampling(sun_sampling, lambda: self._ck(
+            self.L.srt_host_renderer_render_probe_tail_frame(self._h, int(spp), int(bounces), int(seed) & 0xFFFFFFFF)))
 
     def set_sample_counts(self, value):
         """PathTraceRenderer::setSampleCounts (srt_set_sample_counts)."""
@@ -852,13 +880,15 @@ class Renderer:
         """PathTraceRenderer::readSampleCounts: (H, W) uint32, scene rows.  Waits."""
         return self._read(self.L.srt_host_renderer_read_sample_counts, (self.height, self.width), np.uint32)
 
-    def render_adaptive_frame(self, spp, rounds=1, threshold=0.05, floor=0.01, max_budget=64, albedo=True, max_samples=None):
+    def render_adaptive_frame(self, spp, rounds=1, threshold=0.05, floor=0.01, max_budget=64, albedo=True, max_samples=None, sun_sampling=False):
         """PathTraceRenderer::renderAdaptiveFrame: the two-half adaptive workflow; returns (total samples, (H, W) uint32 samples per
-        pixel, both halves).  The accumulator then holds the mean of the halves.  Waits."""
+        pixel, both halves).  The accumulator then holds the mean of the halves.  sun_sampling=True: with the sun_sampling()
+        setting on for this frame — the adaptive renders of every round carry the flag (False: as the setting stands).  Waits."""
         t = C.c_uint64(0)
         n = np.empty((self.height, self.width), dtype=np.uint32)
-        self._ck(self.L.srt_host_renderer_adaptive_frame(self._h, int(spp), int(rounds), C.byref(self._budget_params(threshold, floor, max_budget, albedo)),
-                                                         int(max_budget if max_samples is None else max_samples), n.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(t)))
+        self._frame_sun_sampling(sun_sampling, lambda: self._ck(self.L.srt_host_renderer_adaptive_frame(
+            self._h, int(spp), int(rounds), C.byref(self._budget_params(threshold, floor, max_budget, albedo)),
+            int(max_budget if max_samples is None else max_samples), n.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(t))))
         return int(t.value), n
 
     def render_visibility(self, ao_samples=16, radius=float("inf"), sun=True, ao=True, first_sample=1, seed=0, rows=None, count_work=False):

@@ -352,6 +352,8 @@ int srt_host_renderer_render_adaptive_tail(srt_host_renderer* h, const srt_adapt
 int srt_host_renderer_render_probe_tail_frame(srt_host_renderer* h, uint32_t spp, int bounces, uint32_t seed) {
     SRT_HOST_TRY(h, h->r->renderProbeTailFrame(spp, bounces, seed))
 }
+// sun sampling in renderAdaptiveFrame and renderProbeTailFrame (PathTraceRenderer::sunSampling)
+int srt_host_renderer_sun_sampling(srt_host_renderer* h, int on) { SRT_HOST_TRY(h, h->r->sunSampling(on != 0)) }
 int srt_host_renderer_read_ray_output(srt_host_renderer* h, uint32_t output, void* dst) { SRT_HOST_TRY(h, h->r->readRayOutput(output, dst)) }
 // denoiser over the whole frame with the guides as they stand (srt_denoise / srt_read_denoised)
 int srt_host_renderer_denoise(srt_host_renderer* h, const srt_denoise_params* p) { SRT_HOST_TRY(h, h->r->Denoise(*p)) }

@@ -543,6 +543,7 @@ void PathTraceRenderer::renderProbeTailFrame(uint32_t spp, int bounces, uint32_t
     srt_adaptive_params a{};
     check(srt_adaptive_params_default(&a), "srt_adaptive_params_default");
     a.row_begin = 0, a.row_end = height_, a.max_bounces = bounces, a.seed = seed;
+    if (sun_sampling_) a.flags |= SRT_ADAPTIVE_SUN_SAMPLING;
     std::vector<uint32_t> budget((size_t)width_ * height_);
     for (uint32_t done = 0; done < spp;) {  // (the counts carry the frame from chunk to chunk)
         const uint32_t chunk = spp - done < a.max_samples ? spp - done : a.max_samples;
@@ -599,13 +600,14 @@ uint64_t PathTraceRenderer::renderAdaptiveFrame(uint32_t spp, int rounds, const 
     srt_adaptive_params a{};
     check(srt_adaptive_params_default(&a), "srt_adaptive_params_default");
     a.row_begin = 0, a.row_end = height_, a.max_bounces = p.max_bounces, a.max_samples = max_samples;
+    const uint32_t sun = sun_sampling_ ? SRT_ADAPTIVE_SUN_SAMPLING : 0u;  // (mixing with the uniform halves is rule AS3)
     for (int k = 0; k < rounds; ++k) {
         check(srt_variance(ctx_, &v), "srt_variance");
         (void)sampleBudget(budget);
-        a.seed = seed, a.flags = SRT_ADAPTIVE_KEEP_COUNTS;
+        a.seed = seed, a.flags = SRT_ADAPTIVE_KEEP_COUNTS | sun;
         check(srt_render_adaptive(ctx_, &a), "srt_render_adaptive");  // half A: the counts stay for half B
         check(srt_bind_output(ctx_, fb, half), "srt_bind_output");
-        a.seed = seed_b, a.flags = 0;
+        a.seed = seed_b, a.flags = sun;
         rc = srt_render_adaptive(ctx_, &a);
         check(srt_bind_output(ctx_, fb, acc), "srt_bind_output");
         check(rc, "srt_render_adaptive");

@@ -345,6 +345,13 @@ class PathTraceRenderer {
     // fresh accumulation.
     void renderAdaptiveTail(const srt_adaptive_params& params);
     void renderProbeTailFrame(uint32_t spp, int bounces, uint32_t seed);
+    // Sun sampling in pictures (SRT_ADAPTIVE_SUN_SAMPLING).  Off by default.  The setting is read only by
+    // renderAdaptiveFrame and renderProbeTailFrame, which build their parameter structs themselves: with it on, every
+    // srt_render_adaptive / srt_render_adaptive_tail they issue — both halves, every round, every chunk — carries the flag
+    // (renderAdaptiveFrame's two uniform srt_render halves cannot take it).  renderAdaptive and renderAdaptiveTail pass the
+    // caller's flags through as they are.
+    void sunSampling(bool on) { sun_sampling_ = on; }
+    bool sunSampling() const { return sun_sampling_; }
     // One variance-guided denoised frame (whole frame only): push the camera, render spp / 2 samples with SRT_RENDER_RESET and
     // the frame's seed into the accumulator, spp / 2 with seed ^ 0x9E3779B9 into the handle's half buffer through
     // srt_bind_output (the binding is restored), the four guides, srt_variance with SRT_VARIANCE_MERGE, then
@@ -368,6 +375,7 @@ class PathTraceRenderer {
     srt_camera current_camera() const;
     bool reflection_guides_ = false;
     bool mirror_history_ = false;
+    bool sun_sampling_ = false;
     void bind_guides(bool reflection);  // the four G-buffer slots: the own reflection guide buffers, or NULL
     // first hits for the lifetime of the object, whatever reflectionGuides says
     struct FirstHitScope {
