@@ -1164,6 +1164,9 @@ static KernelSetup fill_kernel_params(srt_context* ctx, const srt_render_params*
     K.off_bounds = SL.off_bounds;
     K.off_box = SL.off_box;
     K.off_mat = SL.off_mat;
+    K.off_bounds2 = SL.off_bounds2;
+    for (int i = 0; i < 3; ++i) K.bound_G[i] = SL.G[i];
+    K.bound_cmaxp = SL.cmaxp, K.bound_Rgmax2 = SL.Rgmax2, K.bound_aG = SL.aG;
     K.scene_vec4 = SL.total_vec4;
     K.scene = ctx->d_scene[img];
     K.bvh_nodes = ctx->d_bvh_nodes;

@@ -79,6 +79,9 @@ struct KernelParams {
     int32_t nu4, nc, K, nsT, nb;
     int32_t nu;  // uniform spheres that are not padding
     int32_t off_bounds, off_box, off_mat;
+    int32_t off_bounds2;  // the cluster bounds about bound_G, behind the materials (closest_hit)
+    // closest_hit's cluster bound test (srt_scene_image.h): the scene's reference point, max |C'|_2, 2 * max Rg', 8.2e-6 * |G|_1
+    float bound_G[3], bound_cmaxp, bound_Rgmax2, bound_aG;
     int32_t scene_vec4;  // number of float4 in the scene image
     const float4* scene;
     // EXTENSION: triangle meshes (srt_mesh_bvh.h); n_tris == 0 -> none
@@ -164,7 +167,10 @@ __device__ __forceinline__ TilePixel tile_pixel() {
 }
 // per-wave LDS scratch behind the scene image: work list of (ray lane, cluster) items + one
 // 64-bit result slot per lane (balanced phase 2 of closest_hit)
-constexpr int WORK_MAX = 512;
+// (480 items, 512 until the scene image got a second row per cluster for closest_hit's bound test: the 64 bytes per wave pay for the
+// sixteen rows of a Scene1-sized image, whose workgroups hold as much LDS as before — srt_launch_shape.h: rows_six_waves.  A step
+// of Scene1 has 79 items on average; a step with more than WORK_MAX takes the per-lane loop, same bits.)
+constexpr int WORK_MAX = 480;
 // ring entries per slot when all 64 pixels of the tile are traced (a power of two).  Round 3: 2 (4 before).  The analytic kernel
 // runs FIVE waves per SIMD (96 VGPRs) and the mesh kernel FOUR (128): that many workgroups' LDS fit into a CU's 160 KiB only
 // with the shorter ring.  With unchanged occupancy the shorter ring costs 3..7 % (a slot whose sample runs long can have only one
@@ -346,14 +352,15 @@ constexpr int CONST_ROWS = 46, CONST_ENV_ROW = 32, CONST_COEF_ROW = 36;  // srt_
 struct Lds {
     const float4* c;  // the image's constants block: srt_powf's table (32 rows), the environment (4 rows)
     const float4* v;  // the primitives behind it (all offsets below count from here)
-    int nu4, nu, nc, K, nsT, nb, off_bounds, off_box, off_mat;
+    int nu4, nu, nc, K, nsT, nb, off_bounds, off_box, off_mat, off_bounds2;
     unsigned long long* res;  // this wave's 64 result slots
     unsigned short* work;     // this wave's work list
     float* pix;               // this wave's 64 pixel records (12 floats each)
     float4* ring;             // this wave's sample-colour ring
     unsigned* meshq;          // mesh kernel only: [MESH_Q] node LIFO from the bottom, leaf queue from the top
     __device__ __forceinline__ float4 sphere(int p) const { return v[p]; }
-    __device__ __forceinline__ float4 bound(int k) const { return v[off_bounds + k]; }
+    __device__ __forceinline__ float4 bound(int k) const { return v[off_bounds + k]; }    // (Cx, Cy, Cz, Rg): srt_occlusion.hip.h
+    __device__ __forceinline__ float4 bound2(int k) const { return v[off_bounds2 + k]; }  // (C'x, C'y, C'z, K) about P.bound_G: closest_hit
     __device__ __forceinline__ float4 box_c(int j) const { return v[off_box + 2 * j]; }
     __device__ __forceinline__ float4 box_h(int j) const { return v[off_box + 2 * j + 1]; }
     // (the compiler makes one v_mad_u64_u32 of `base + 48 * p`; spelled with 24-bit multiplies it was 0..1 % slower: profiles/r04/ab_notes.txt)
@@ -589,7 +596,21 @@ __device__ __forceinline__ Hit closest_hit(const Lds& S, const KernelParams& P, 
         const float dd = __builtin_fmaf(d.z, d.z, __builtin_fmaf(d.y, d.y, d.x * d.x));
         const bool unit = fabsf(dd - 1.0f) <= 1e-6f;  // false for NaN
         if (__builtin_amdgcn_ballot_w64(active && !unit) == 0ull) {
-            const float o1 = (fabsf(o.x) + fabsf(o.y)) + fabsf(o.z);
+            // The bound test about the foot point of the ray's line, relative to the scene's reference point G (srt_scene_image.h has
+            // the form and the proof that it is conservative): what depends on the ray alone — the foot point w, |w|^2 and the slack —
+            // is computed here once, and a bound costs two dot products with the row (C', K), one FMA and the compare: 8 instructions
+            // where the test about the origin (L = C - o, LL, s, Rinf, Rinf^2, 4e-6 LL) took 14.  Same bits; the slack is a little looser
+            // (Scene1 +0.12 % items per call, Scene3 +0.42 %).  Config 2: SQ_INSTS_VALU -5.4 % (73 instructions a step); interleaved A/B
+            // (profiles/bound_form/ab_notes.txt): config 2 1.822 -> 1.772 ms (-2.7 %), Scene3 -3.4 %, Scene1_reflection -3.2 %, config 3's
+            // floor / middle bands -3.0 / -2.9 %, one-sample launches -2.7 %, Scene_indirect -2.3 %, config 4 +0.2 .. +0.8 % (floor 0.6 %).
+            const float ox = o.x - P.bound_G[0], oy = o.y - P.bound_G[1], oz = o.z - P.bound_G[2];
+            const float od = __builtin_fmaf(oz, d.z, __builtin_fmaf(oy, d.y, ox * d.x));
+            const float wx = __builtin_fmaf(-od, d.x, ox), wy = __builtin_fmaf(-od, d.y, oy), wz = __builtin_fmaf(-od, d.z, oz);
+            const float w2x = 2.0f * wx, w2y = 2.0f * wy, w2z = 2.0f * wz;
+            const float WW = __builtin_fmaf(wz, wz, __builtin_fmaf(wy, wy, wx * wx));
+            const float p1 = (fabsf(ox) + fabsf(oy)) + fabsf(oz);
+            const float Mb = __builtin_fmaf(2.1f, p1, P.bound_cmaxp), ab = __builtin_fmaf(8.2e-6f, p1, P.bound_aG);
+            const float Tb = __builtin_fmaf(ab, P.bound_Rgmax2 + ab, (1e-5f * Mb) * Mb) - WW;
             unsigned mlo = 0u, mhi = 0u;  // this lane's clusters: bit k of (mhi : mlo) = the ray may touch cluster k
             // (Tried in round 4 and dropped: ONE bound around all clustered spheres first — the same test, the same proof — so that a wave
             // none of whose rays passes it skips the nc cluster bounds: Scene3 -1.1 %, config 3's middle band -1.4 %, but Scene1 +1.9 %,
@@ -601,14 +622,11 @@ __device__ __forceinline__ Hit closest_hit(const Lds& S, const KernelParams& P, 
             // with more than 32 clusters take a second loop).  Round 4; same bits; interleaved A/B (profiles/r04/ab_notes.txt): config 2
             // 2.165 -> 2.085 ms, config 3's middle band -2.7 %, one-sample launches -2.3 %, Scene3 -1.8 %, config 4 -1.6 %, the others -0.5 %.
             auto passes = [&](int k) {
-                const float4 b = S.bound(k);
-                float Lx = b.x - o.x, Ly = b.y - o.y, Lz = b.z - o.z;
-                float LL = __builtin_fmaf(Lz, Lz, __builtin_fmaf(Ly, Ly, Lx * Lx));
-                float sd = __builtin_fmaf(Lz, d.z, __builtin_fmaf(Ly, d.y, Lx * d.x));
-                float Rinf = __builtin_fmaf(8e-6f, o1, b.w);
-                float lhs = __builtin_fmaf(-sd, sd, LL);
-                float rhs = __builtin_fmaf(4e-6f, LL, Rinf * Rinf);
-                return lhs <= rhs ? 1u : 0u;
+                const float4 b = S.bound2(k);
+                const float g = __builtin_fmaf(-b.z, w2z, __builtin_fmaf(-b.y, w2y, __builtin_fmaf(-b.x, w2x, b.w)));
+                const float e = __builtin_fmaf(b.z, d.z, __builtin_fmaf(b.y, d.y, b.x * d.x));
+                const float lhs = __builtin_fmaf(-e, e, g);
+                return lhs > Tb ? 0u : 1u;  // (a NaN or inf - inf anywhere passes the cluster)
             };
             {
                 const int n_lo = S.nc < 32 ? S.nc : 32;
@@ -1316,7 +1334,7 @@ __device__ __forceinline__ Lds make_lds(const KernelParams& P, float4* lds, int 
         image = lds;
     else
         image = P.scene;
-    return Lds{image, image + CONST_ROWS, P.nu4, P.nu, P.nc, P.K, P.nsT, P.nb, P.off_bounds, P.off_box, P.off_mat,
+    return Lds{image, image + CONST_ROWS, P.nu4, P.nu, P.nc, P.K, P.nsT, P.nb, P.off_bounds, P.off_box, P.off_mat, P.off_bounds2,
                reinterpret_cast<unsigned long long*>(scratch), reinterpret_cast<unsigned short*>(scratch + 64 * 8),
                reinterpret_cast<float*>(scratch + 64 * 8 + WORK_MAX * 2),
                reinterpret_cast<float4*>(scratch + 64 * 8 + WORK_MAX * 2 + 64 * 12 * 4),

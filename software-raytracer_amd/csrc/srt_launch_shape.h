@@ -272,10 +272,10 @@ inline unsigned long long rows_bytes(const LaunchShape& s, uint32_t sample_count
 // `lds_bytes` is what the launch asks for per workgroup.  The hardware hands LDS out in granules: gfx950 divides its 160 KiB into
 // 128 allocation units of 320 dwords = 1280 bytes (LLVM's AMDGPU target: getLdsDwGranularity is 320 for the 160 KiB parts, as it
 // is 128 dwords = 512 bytes for the 64 KiB of gfx90a: always 1 / 128 of the CU's LDS), so a workgroup occupies its request rounded up to
-// 1280 and six fit up to 21 granules = 26 880 bytes each (an image of 8448 bytes; Scene1's 5.2 KB image: 19 granules).  The
+// 1280 and six fit up to 21 granules = 26 880 bytes each (an image of 8704 bytes; Scene1's 5.5 KB image: 19 granules).  The
 // answer at that edge does not hinge on the granule: 26 880 bytes rounded up to 512 are 27 136, and six of those fit as well.
 // The 160 KiB are a constant, not a device query: the same request takes the same kernel on every machine (as ROWS_MAX_BYTES).
-constexpr size_t SHAPE_ROWS_WG_SCRATCH_BYTES = 18432;
+constexpr size_t SHAPE_ROWS_WG_SCRATCH_BYTES = 18176;
 constexpr size_t LDS_BYTES_PER_CU = 160 * 1024, LDS_GRANULE_BYTES = 1280;
 inline bool rows_six_waves(size_t lds_bytes) {
     if (lds_bytes > LDS_BYTES_PER_CU) return false;  // (nothing below can wrap)

@@ -25,6 +25,9 @@
 //                              (smoothness, specular_amount, base.r, base.g)
 //                              (base.b, emissive.r, emissive.g, emissive.b)
 //                              (specular.r, specular.g, specular.b, bits(list index))
+//   [off_bounds2, +nc)       the cluster bounds once more, in the form closest_hit's bound test reads: (C'x,C'y,C'z,K) about
+//                            the scene's reference point G (SceneLayout::G), K = |C'|^2 - Rg'^2 (proof below).  Behind the
+//                            materials, so that every older offset stays where it was.
 //
 // The list index restores the reference's tie rule (strict '<' in list order keeps the
 // lower index, Raytracer.cpp:132) after the spheres have been permuted.
@@ -42,11 +45,42 @@
 // |e|^2 = |L|^2 + (3+eta) s^2 >= |L|^2 >= D^2, so the same bound holds.  Hence a sphere can be
 // a candidate only if  D <= r + rho,  rho = 4e-6*(|o|+|c|+|L|) + 1e-5*r   (2x margin).
 // For a cluster with centre C and R_geo >= |c_j - C| + r_j for all members:
-//   D_C <= D_j + |c_j - C| <= R_geo*(1+1e-5) + 8e-6*(|o|_1 + cmax),   cmax = max |c_j|.
-// The kernel evaluates  lhs = fma(-s,s,LL)  (LL = |C-o|^2, s = (C-o).d, FMA chains) whose error
-// against D_C^2 is below 1.6e-6*LL, and passes the cluster iff
-//   lhs <= (Rg + 8e-6*|o|_1)^2 + 4e-6*LL,   Rg = R_geo*(1+1e-5) + 8e-6*cmax  rounded UP.
-// So "cluster fails" implies no member can be a candidate: culling never changes the result.
+//   D_C <= D_j + |c_j - C| <= R_geo*(1+1e-5) + 8e-6*(|o|_1 + cmax),   cmax = max |c_j|_1.                                  (*)
+// So a cluster whose centre is farther from the ray's line than Rg + 8e-6*|o|_1, Rg >= R_geo*(1+1e-5) + 8e-6*cmax, has no
+// candidate among its members.  srt_occlusion.hip.h tests that with the rows (Cx,Cy,Cz,Rg) at off_bounds:
+//   lhs = fma(-s,s,LL) <= (Rg + 8e-6*|o|_1)^2 + 4e-6*LL    (LL = |C-o|^2, s = (C-o).d, FMA chains; error against D_C^2 < 1.6e-6*LL).
+//
+// closest_hit tests the same thing about the FOOT POINT of the ray's line, in 8 instructions per cluster, with the rows at
+// off_bounds2.  Host: one point G per scene (the middle of the cluster centres' box, binary32).  Per cluster C' = float(C - G),
+// and R_geo is taken about the point G + C' itself (in double, plus 2^-52*(|G|_1 + |C'|_1) for that sum's own rounding), so the
+// rounding of the centre needs no accounting.  Rg' = (R_geo*(1+1e-5) + 8e-6*cmax)*(1+1e-6), K = |C'|^2 - Rg'^2 in double, rounded
+// once.  Scene-wide, rounded up: cmaxp = max|C'|_2, Rgmax2 = 2*max Rg', aG = 8.2e-6*|G|_1.
+// Kernel, once per ray (eps = 2^-24, every line one FMA chain):
+//   o' = o - G;  t = o'.d;  w = fma(-t, d, o');  w2 = 2w;  WW = w.w;  p1 = |o'|_1;  M = fma(2.1, p1, cmaxp);
+//   a = fma(8.2e-6, p1, aG);  T = fma(a, Rgmax2 + a, (1e-5*M)*M) - WW
+// per cluster:
+//   g = K - C'.w2;  e = C'.d;  lhs = fma(-e, e, g);  culled iff lhs > T     (a NaN anywhere: not culled)
+// Why "culled" implies (*)'s premise fails, i.e. D_C > Rg + 8e-6*|o|_1.  Write |d|^2 = 1 + dl, |dl| <= 1e-6 (checked by the
+// kernel), L = C - o, s = L.d, and take the line through o~ = G + o' (o' as rounded): it is the ray's line moved by at most
+// eps*|o'|_2.  The point p = o' - t*d lies EXACTLY on that line whatever t's rounding (t = o'.d + tau, |tau| <= 3.01*eps*|o'|),
+// and w = p + eta with |eta| <= eps*|p|, |p| <= 1.00001*|o'|.  In exact arithmetic
+//   Q := |C'-p|^2 - (C'.d)^2 = |L|^2 - s^2 + 2*s*tau + (o'.d)^2*dl + 2*(o'.d)*tau*(1+dl) + tau^2*(1+dl)
+// and |L|^2 - s^2 = D~^2 + s^2*(1 - 1/|d|^2) with D~ the distance of G + C' from the moved line, so with
+// M' = |C'|_2 + 2.1*|o'|_2 (>= |L|, >= 2.1*|o'|):   D~^2 >= Q - (4.3*eps + 0.23e-6 + 1.01e-6)*M'^2.
+// The kernel compares lhs and T, i.e. K - 2C'.p - (C'.d)^2 + |p|^2 = Q - Rg'^2 against the slack, up to these roundings:
+//   chain g (3 roundings at magnitude <= |K| + 2|C'||w|), K's own, and w for p:  eps*(4.01*(|C'|^2 + Rg'^2) + 8.03*|C'||o'|)
+//   chain e and its square: 6.1*eps*|C'|^2;    the last FMA: 1.01*eps*(2.01*|C'|^2 + 2.01*|C'||o'| + Rg'^2)
+//   WW against |p|^2 and T's subtraction: 6.11*eps*|o'|^2
+// together below 12.2*eps*M'^2 + 5.02*eps*Rg'^2.  All of it against M'^2: (16.5*eps + 1.24e-6) = 2.23e-6, and the test allows
+// 1e-5*M^2 with M >= M'*(1 - 4*eps) (|o'|_1 >= |o'|_2, cmaxp >= |C'|_2): more than four times as much.  The Rg'^2 share and the
+// roundings of a*(Rgmax2 + a) (three, relative) are covered by Rg'^2 >= Rg^2*(1 + 2e-6) and by a >= 1.017 times what is needed:
+//   a >= 8e-6*|o|_1 + eps*|o'|_2   because |o|_1 <= |o'|_1*(1+eps) + |G|_1 and 0.2e-6*p1 pays for the moved line,
+//   a*(Rgmax2 + a) >= 2*a*Rg' + a^2, so the right-hand side is at least (Rg + a)^2 + the M^2 term.
+// Hence culled => D~ > Rg + a => D_C > Rg + 8e-6*|o|_1 => by (*) no member is a candidate.  Translating by G keeps the slack from
+// growing with the scene's distance from the world origin: it grows with the ray's distance from the cluster field only.
+// Overflow: where M*M overflows T is NaN or +inf and nothing is culled; WW alone can overflow (|w| > 1.8e19 with |o'| < 2.8e21),
+// T is then -inf and everything finite is culled — rightly: p is then farther than 1.8e19 from G along a direction at most
+// 1.3e-6*|o'| off the foot point, and every centre lies within 1e15 of it (finite_sphere).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -80,6 +114,9 @@ struct SceneLayout {
     int nb = 0;       // boxes
     int nm = 0;       // mesh objects (EXTENSION): primitive ids nsT + nb + m, geometry lives in the BVH
     int off_bounds = 0, off_box = 0, off_mat = 0;
+    int off_bounds2 = 0;  // the bounds about G, behind the materials (closest_hit's bound test)
+    // closest_hit's bound test (proof above): the reference point, and max |C'|_2, 2 * max Rg', 8.2e-6 * |G|_1, each rounded up
+    float G[3] = {0, 0, 0}, cmaxp = 0, Rgmax2 = 0, aG = 0;
     int total_vec4 = 0;
     int n_spheres = 0;  // real spheres (for statistics)
     // every box centre and half size is a number of magnitude below SRT_BOX_NO_NAN_BOUND (the kernel's NaN-free slab test relies on
@@ -223,7 +260,8 @@ inline SceneLayout build_scene_image(const srt_object* objects, size_t count, bo
     L.off_bounds = L.nsT;
     L.off_box = L.off_bounds + L.nc;
     L.off_mat = L.off_box + 2 * L.nb;
-    L.total_vec4 = SRT_CONST_ROWS + L.off_mat + 3 * (L.nsT + L.nb + L.nm);
+    L.off_bounds2 = L.off_mat + 3 * (L.nsT + L.nb + L.nm);
+    L.total_vec4 = SRT_CONST_ROWS + L.off_bounds2 + L.nc;
 
     std::vector<float4> full((size_t)L.total_vec4, make_float4(0, 0, 0, 0));
     memcpy(full.data(), srt_pow_table_host, 32 * sizeof(float4));  // 64 doubles = 32 rows; the environment rows are patched by the caller
@@ -251,6 +289,7 @@ inline SceneLayout build_scene_image(const srt_object* objects, size_t count, bo
         put_material(p, i);
     };
     for (size_t k = 0; k < uni.size(); ++k) put_sphere((int)k, uni[k]);
+    std::vector<double> centres((size_t)L.nc * 3), cmaxs((size_t)L.nc);  // what the walk below found, for the bounds about G
     for (int c = 0; c < L.nc; ++c) {
         const size_t b = (size_t)c * L.K, e = std::min(small.size(), b + L.K);
         double C[3] = {0, 0, 0};
@@ -296,6 +335,45 @@ inline SceneLayout build_scene_image(const srt_object* objects, size_t count, bo
         float Rgf = (float)Rg;
         if ((double)Rgf < Rg) Rgf = nextafterf(Rgf, INFINITY);
         img[L.off_bounds + c] = make_float4(Cf[0], Cf[1], Cf[2], Rgf);
+        for (int a = 0; a < 3; ++a) centres[(size_t)c * 3 + a] = C[a];
+        cmaxs[(size_t)c] = cmax;
+    }
+    if (L.nc > 0) {  // the bounds about G (proof at the top)
+        auto up = [](double v) {  // binary32, rounded up
+            float f = (float)v;
+            return (double)f < v ? nextafterf(f, INFINITY) : f;
+        };
+        double G1 = 0;
+        for (int a = 0; a < 3; ++a) {
+            double lo = 1e300, hi = -1e300;
+            for (int c = 0; c < L.nc; ++c) lo = std::min(lo, centres[(size_t)c * 3 + a]), hi = std::max(hi, centres[(size_t)c * 3 + a]);
+            L.G[a] = (float)(0.5 * (lo + hi));
+            G1 += fabs((double)L.G[a]);
+        }
+        double cmaxp = 0, Rgmax = 0;
+        for (int c = 0; c < L.nc; ++c) {
+            const size_t b = (size_t)c * L.K, e = std::min(small.size(), b + L.K);
+            float Cp[3];
+            double P[3], CC = 0, C1 = 0;
+            for (int a = 0; a < 3; ++a) {
+                Cp[a] = (float)(centres[(size_t)c * 3 + a] - (double)L.G[a]);
+                P[a] = (double)L.G[a] + (double)Cp[a];
+                CC += (double)Cp[a] * (double)Cp[a];
+                C1 += fabs((double)Cp[a]);
+            }
+            double Rgeo = 0;
+            for (size_t k = b; k < e; ++k) {
+                const srt_object& o = objects[small[k]];
+                const double dx = (double)o.position[0] - P[0], dy = (double)o.position[1] - P[1], dz = (double)o.position[2] - P[2];
+                Rgeo = std::max(Rgeo, sqrt(dx * dx + dy * dy + dz * dz) + fabs((double)o.radius));
+            }
+            Rgeo += 0x1p-52 * (G1 + C1);
+            const double Rg = ((Rgeo * (1.0 + 1e-5) + 8e-6 * cmaxs[(size_t)c] + 1e-30) * (1.0 + 1e-6));
+            img[L.off_bounds2 + c] = make_float4(Cp[0], Cp[1], Cp[2], (float)(CC - Rg * Rg));
+            cmaxp = std::max(cmaxp, sqrt(CC));
+            Rgmax = std::max(Rgmax, Rg);
+        }
+        L.cmaxp = up(cmaxp * (1.0 + 1e-12)), L.Rgmax2 = up(2.0 * Rgmax), L.aG = up(8.2e-6 * G1);
     }
     for (size_t j = 0; j < boxes.size(); ++j) {
         const srt_object& o = objects[boxes[j]];
